@@ -26,6 +26,11 @@ stream inside the timed region; `roofline.step_frac` is SURVEY 8d's formula over
 by several per cent with where a batch lands in physical memory: the median is the figure of record).  `cpu_baseline` is
 the oracle (a C restatement of the reference's awk/fgrep semantics) timed on this box's host cores on a bounded
 sample of the same VCFs -- a reported baseline, not the target.
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step if `--dump-outputs DIR` is given
+(dump_outputs) and prints the line.  Everything else -- the counter guards and oracle checks after the timed region, the
+bandwidth probe, the re-created allocations, the CPU and shell baselines, the side workloads (shuffled, allele-extended, per
+contig) and the detail file -- runs only with `--full`.
 """
 import argparse
 import json
@@ -81,9 +86,16 @@ def main():
                     help="re-create the timed batch this many times after the timed region and report k_classify's time for each "
                          "(roofline.alloc_spread: the kernel moves by several per cent with where a batch lands in memory); N=1, config 2; 0 disables")
     ap.add_argument("--detail", default=os.environ.get("QM_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json")),
-                    help="where the full record goes (every side measurement with its notes, nested); the ONE line on stdout is the flat summary of it")
+                    help="where the full record goes (every side measurement with its notes, nested; written by --full runs only); the ONE line on stdout is the flat summary of it")
     ap.add_argument("--check-vcfs", type=int, default=2, help="VCFs of this rank's batch checked against the oracle after the timed region (N > 1 and configs 3 / 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every check and side measurement after the timed region (the options above) and write the detail file; "
+                         "without it a run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB; dump_outputs)")
     args = ap.parse_args()
+    if not args.full and args.detail != ap.get_default("detail"):
+        print("bench.py: --detail %s is not written without --full" % args.detail, file=sys.stderr)
     P = dict(PRESETS[args.config])
     custom = False
     for k in ("vcfs", "records", "genome", "truth"):
@@ -212,26 +224,30 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # ---- correctness guards on the timed data (cheap, outside the timed region) ----
-    scal = batch.scalars()
-    roc = batch.roc()
-    assert int(scal[:, 6].sum()) == n_vcf * P["records"]
-    assert np.array_equal(roc[:, 0, 20].astype(np.int64), scal[:, 1]) and np.array_equal(roc[:, 1, 20].astype(np.int64), scal[:, 2])
-    local_sum = np.zeros((batch.n_truth, 3, args.bins), np.int64)
-    for w, t_ in enumerate(tids):
-        local_sum[t_] = roc[(w - g0) % len(tids)::len(tids)].sum(axis=0).astype(np.int64)
-    got = glob.cpu().numpy()
-    if world == 1:
-        assert np.array_equal(got, local_sum), "per-truth counters != sum of the per-VCF ROC rows"
-    else:
-        ref = torch.from_numpy(local_sum).to(dev)
-        dist.all_reduce(ref, op=dist.ReduceOp.SUM)
-        if not np.array_equal(got, ref.cpu().numpy()):
-            raise AssertionError("all-reduced counters != sum over ranks of the per-VCF ROC rows: rank %d got %d, local %d, summed %d"
-                                 % (rank, int(got.sum()), int(local_sum.sum()), int(ref.sum().item())))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, glob.cpu().numpy(), args.dump_outputs)
+
+    # ---- correctness guards on the timed data (cheap, outside the timed region; --full) ----
     checked = 0
-    if (world > 1 or args.config != 2) and args.check_vcfs > 0:
-        checked = oracle_check(batch, P, tseeds, g0, alleles, args.bins, min(args.check_vcfs, n_vcf), roc, scal)
+    if args.full:
+        scal = batch.scalars()
+        roc = batch.roc()
+        assert int(scal[:, 6].sum()) == n_vcf * P["records"]
+        assert np.array_equal(roc[:, 0, 20].astype(np.int64), scal[:, 1]) and np.array_equal(roc[:, 1, 20].astype(np.int64), scal[:, 2])
+        local_sum = np.zeros((batch.n_truth, 3, args.bins), np.int64)
+        for w, t_ in enumerate(tids):
+            local_sum[t_] = roc[(w - g0) % len(tids)::len(tids)].sum(axis=0).astype(np.int64)
+        got = glob.cpu().numpy()
+        if world == 1:
+            assert np.array_equal(got, local_sum), "per-truth counters != sum of the per-VCF ROC rows"
+        else:
+            ref = torch.from_numpy(local_sum).to(dev)
+            dist.all_reduce(ref, op=dist.ReduceOp.SUM)
+            if not np.array_equal(got, ref.cpu().numpy()):
+                raise AssertionError("all-reduced counters != sum over ranks of the per-VCF ROC rows: rank %d got %d, local %d, summed %d"
+                                     % (rank, int(got.sum()), int(local_sum.sum()), int(ref.sum().item())))
+        if (world > 1 or args.config != 2) and args.check_vcfs > 0:
+            checked = oracle_check(batch, P, tseeds, g0, alleles, args.bins, min(args.check_vcfs, n_vcf), roc, scal)
 
     total_records = float(n_vcf) * P["records"] * world
     value = total_records * args.steps / dt
@@ -305,7 +321,7 @@ def main():
         "device_bytes": batch.device_bytes,
     }
 
-    if rank == 0:
+    if args.full and rank == 0:
         # the second denominator SURVEY 8d asks for: what this very GPU streams, measured with the library's own
         # 16-byte-per-lane kernels after the timed region (read only / copy = read + written / write only)
         try:
@@ -314,7 +330,7 @@ def main():
                                    frac_of_measured_read=achieved / bw["read_GBps"] if bw["read_GBps"] > 0 else None)
         except Exception as e:   # never fatal
             out["roofline"]["measured_error"] = str(e)[:120]
-    side = rank == 0 and world == 1
+    side = args.full and rank == 0 and world == 1
     if side and args.config == 2 and not custom and not args.shuffled and args.alloc_reps > 0:
         # The same workload in fresh allocations, outside the timed region: within one allocation the step is steady to a per
         # cent, from one allocation to the next it moves by several (profiles/r03_alloc_pmc.log: the same requests, 5-9 % more
@@ -366,7 +382,8 @@ def main():
     if side and args.config == 2 and not custom and not args.shuffled and args.multicontig_vcfs > 0:
         out["multicontig_variant"] = multicontig_variant(eng, tids[0], P, args.bins, min(args.multicontig_vcfs, n_vcf), tseeds[0], roc, scal)
     if rank == 0:
-        write_detail(out, args.detail)
+        if args.full:
+            write_detail(out, args.detail)
         sys.stdout.flush()
         os.dup2(fd_out, 1)
         print(json.dumps(compact_line(out)), flush=True)
@@ -398,6 +415,58 @@ def write_detail(out, path):
         os.replace(path + ".tmp", path)
     except OSError as e:   # a read-only tree: the line on stdout is what counts
         print("bench.py: detail file not written: %s" % e, file=sys.stderr)
+
+
+DUMP_LIMIT = 64 << 20   # bytes of .npy data one --dump-outputs may write
+
+
+def _exact_float(a):
+    """an integer array as float32 when every value fits its 24-bit mantissa, else float64 (exact up to 2^53)"""
+    import numpy as np
+    a = np.asarray(a)
+    big = int(np.abs(a.astype(np.float64)).max()) if a.size else 0
+    assert big < 2 ** 53, "output value %d is not exact in float64" % big
+    return a.astype(np.float32 if big < 2 ** 24 else np.float64)
+
+
+def dump_outputs(batch, glob, path, seed=0):
+    """What a caller of the timed path receives after the last step, as <path>/<name>.npy (at most DUMP_LIMIT bytes in all):
+      roc [rows][3][n_bins], scalars [rows][QM_N_SCALARS]  the per-VCF ROC counters and scalars of this rank's batch (every VCF,
+                                                          or a fixed sample of them beyond 3/8 of the limit); roc_vcfs = rows
+      global_counts [n_truth][3][n_bins]                  the per-truth-set sums (all-reduced when N > 1)
+      cls, idx [k][m]                                     class bits and index lists (TP indices first, FP indices last, -1
+                                                          between) of k VCFs (record_vcfs) at m record slots (record_slots:
+                                                          every slot, or a fixed sample when a VCF is larger than the rest allows)
+    Integers are written as float32 where that is exact, else float64.  The samples come from a fixed seed: two runs with the
+    same arguments write the same entries."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    nv, n = batch.n_vcf, int(batch.n_records[0])      # (the bench's batches: every VCF has the same number of records)
+    scal = batch.scalars()
+    roc, sc = _exact_float(batch.roc()), _exact_float(scal)
+    row_bytes = roc[0].nbytes + sc[0].nbytes
+    rows = np.arange(nv) if nv * row_bytes <= DUMP_LIMIT * 3 // 8 else \
+        np.sort(rng.choice(nv, max(1, DUMP_LIMIT * 3 // 8 // row_bytes), replace=False))
+    k = min(4, nv)
+    vcfs = np.sort(rng.choice(nv, k, replace=False))
+    item = 4 if n < 2 ** 24 else 8                    # record indices are exact in float32 below 2^24
+    m = min(n, DUMP_LIMIT // 2 // (2 * k * item))
+    slots = np.arange(n) if m == n else np.sort(rng.choice(n, m, replace=False))
+    cls = np.zeros((k, m), np.int64)
+    idx = np.zeros((k, m), np.int64)
+    for i, v in enumerate(vcfs):
+        cls[i] = batch.cls(int(v))[slots]
+        lists = batch.idx(int(v)).astype(np.int64)
+        tp, fp = int(scal[v, 1]), int(scal[v, 2])
+        lists[tp:n - fp] = -1                         # the slots between the two lists hold nothing defined
+        idx[i] = lists[slots]
+    out = {"roc": roc[rows], "scalars": sc[rows], "roc_vcfs": _exact_float(rows), "global_counts": _exact_float(glob),
+           "cls": _exact_float(cls), "idx": _exact_float(idx), "record_vcfs": _exact_float(vcfs), "record_slots": _exact_float(slots)}
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, "the outputs take %d bytes" % total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def compact_line(out):

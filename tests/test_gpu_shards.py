@@ -182,7 +182,7 @@ def test_workflows_on_two_ranks_of_this_gpu_write_what_one_gpu_writes(tmp_path, 
 
 
 def test_bench_line_contract_on_a_small_batch(qmlib, tmp_path):
-    """`python bench.py` as the driver runs it (N = 1), on a reduced batch: ONE JSON line of at most 2 000 characters (what the driver's
+    """`python bench.py --full` (N = 1), on a reduced batch: ONE JSON line of at most 2 000 characters (what the driver's
     record keeps) with the contract's keys and every figure of record as a FLAT scalar of `roofline` / `cpu_baseline` (the driver's
     parser drops nested objects: VERDICT round 5) -- the whole step over the timed batch and its re-creations, the first-seen rates of
     the shuffled shapes, the allele-extended and per-contig-sorted side workloads, the oracle on one and on all cores, the reference's
@@ -194,7 +194,7 @@ def test_bench_line_contract_on_a_small_batch(qmlib, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, QM_BENCH_SHELL_JOBS="4")
     detail = tmp_path / "detail.json"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--vcfs", "40", "--steps", "3", "--warmup", "1", "--cpu-sample", "3000000",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--vcfs", "40", "--steps", "3", "--warmup", "1", "--cpu-sample", "3000000",
                         "--shell-sample", "1", "--shuffled-vcfs", "40", "--shuffled3-vcfs", "2", "--alleles-vcfs", "40", "--shuffled-alleles-vcfs", "40",
                         "--shuffled4-vcfs", "6", "--multicontig-vcfs", "40", "--alloc-reps", "2", "--detail", str(detail)], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -236,6 +236,50 @@ def test_bench_line_contract_on_a_small_batch(qmlib, tmp_path):
     assert D["alleles_variant"]["equals_oracle_on_vcf0"] is True
     mc = D["multicontig_variant"]
     assert mc["equals_sorted_variant"] is True and mc["contigs"] == 24
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_same_outputs_twice(engine, oracle, tmp_path):
+    """`python bench.py` without --full: the contract's keys, no side measurement and no detail file; --dump-outputs writes the
+    last step's outputs, identical from one run to the next, and they agree with the oracle on the VCFs they sample."""
+    import json
+    import subprocess
+    import sys
+    from oracle.synth import synth_truth_keys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--vcfs", "12", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(d), "--detail", str(tmp_path / "detail.json")], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+        assert abs(line["value"] - 12e6 / (line["ms_per_step"] * 1e-3)) < 1e-4 * line["value"]
+        assert "cpu_baseline" not in line and "measured_read_GBps" not in line["roofline"] and not (tmp_path / "detail.json").exists()
+        assert "is not written without --full" in p.stderr
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in ("roc", "scalars", "roc_vcfs", "global_counts", "cls", "idx", "record_vcfs", "record_slots"))
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    a = dumps[0]
+    assert a["roc"].shape == (12, 3, 256) and a["cls"].shape == (4, 1_000_000) and a["global_counts"].astype(np.int64).sum() == a["roc"].astype(np.int64).sum()
+    # the VCFs of bench.py's default batch (configs[2]: VCF v has seed 3000 + v), generated again on the device
+    tid = engine.truth_synth(5_000_000, 100_000, 3)
+    b = engine.batch([1_000_000] * 12, [tid] * 12)
+    b.synth(5_000_000, 100_000, 3, 3000)
+    truth = synth_truth_keys(5_000_000, 100_000, 3)
+    for i, v in enumerate(a["record_vcfs"].astype(int)):
+        cls, roc, sc = oracle.classify_columns(*b.columns(v), *truth, n_bins=256)
+        assert np.array_equal(a["cls"][i], cls) and np.array_equal(a["roc"][v], roc)
+        idx = a["idx"][i].astype(np.int64)
+        assert np.array_equal(idx[:sc["tp_lines"]], np.nonzero(cls == 3)[0]) and np.array_equal(idx[len(cls) - sc["fp_lines"]:], np.nonzero(cls == 1)[0])
+        assert (idx[sc["tp_lines"]:len(cls) - sc["fp_lines"]] == -1).all()
+    b.close()
+    engine.truth_release(tid)
 
 
 def test_the_two_bucket_joins_agree_behind_one_scatter(qmlib):

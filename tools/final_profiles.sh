@@ -4,6 +4,7 @@
 TAG=${1:-r06f}; PART=${2:-1}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $ROOT; mkdir -p gpurun_out
+OUT=$ROOT/$_      # the directory the line above made: where this script's outputs go
 export TMPDIR=/tmp
 R=${TAG%%f*}
 if [ "$PART" = "1" ]; then
@@ -33,7 +34,8 @@ python3 tools/shuffled_ext.py 256 > gpurun_out/${TAG}_shuffled_ext.log 2>&1
 python3 tools/shuffled_ext.py 64 2000000 10000000 200000 >> gpurun_out/${TAG}_shuffled_ext.log 2>&1
 python3 tools/e2e_files_bench.py 16 > gpurun_out/${TAG}_e2e.log 2>&1
 bash tools/pmc_compact.sh $TAG > gpurun_out/${TAG}_pmc_compact.log 2>&1
-python3 bench.py --detail gpurun_out/${TAG}_bench_detail.json > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-python3 bench.py --config 3 --detail gpurun_out/${TAG}_bench_config3_detail.json > gpurun_out/${TAG}_bench_config3.json 2> gpurun_out/${TAG}_bench_config3.err
-python3 bench.py --config 4 --detail gpurun_out/${TAG}_bench_config4_detail.json > gpurun_out/${TAG}_bench_config4.json 2> gpurun_out/${TAG}_bench_config4.err
+# --full: the records hold every check and side measurement (baselines, bandwidth probe, re-created allocations, side workloads)
+python3 bench.py --full --detail $OUT/${TAG}_bench_detail.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full --config 3 --detail $OUT/${TAG}_bench_config3_detail.json > $OUT/${TAG}_bench_config3.json 2> $OUT/${TAG}_bench_config3.err
+python3 bench.py --full --config 4 --detail $OUT/${TAG}_bench_config4_detail.json > $OUT/${TAG}_bench_config4.json 2> $OUT/${TAG}_bench_config4.err
 cat gpurun_out/${TAG}_bench.json gpurun_out/${TAG}_bench_config3.json gpurun_out/${TAG}_bench_config4.json

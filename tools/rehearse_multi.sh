@@ -5,10 +5,10 @@
 export QM_BENCH_SAME_DEVICE=1 QM_BENCH_BACKEND=gloo
 for spec in "2 60" "3 12" "4 30"; do
   set -- $spec
-  python3 bench.py --gpus 2 --config $1 --vcfs $2 --steps 3 --warmup 1 2>/dev/null | tail -1
+  python3 bench.py --full --gpus 2 --config $1 --vcfs $2 --steps 3 --warmup 1 2>/dev/null | tail -1
 done
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
-  bench.py --gpus 2 --config 2 --vcfs 60 --steps 3 --warmup 1 2>/dev/null | tail -1
+  bench.py --full --gpus 2 --config 2 --vcfs 60 --steps 3 --warmup 1 2>/dev/null | tail -1
 # and the collective over RCCL itself at the only world size one card allows (QM_BENCH_FORCE_PG=1: process group "nccl" on the
 # device, the all-reduce of the engine's buffer inside every step)
 unset QM_BENCH_SAME_DEVICE QM_BENCH_BACKEND
