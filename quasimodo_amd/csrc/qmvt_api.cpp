@@ -367,6 +367,9 @@ static void build_layout(const int64_t* n_records, const int32_t* truth_ids, int
   L.n_pad = off + K1_TILE;  // the last tile's vector loads may run past its VCF
 }
 
+// the paths of a VCF found out of order (route())
+enum class Path : uint8_t { Radix, OneLevel, TwoLevel, Partitions, Wide };
+
 struct qm_batch {
   qm_ctx* ctx = nullptr;
   int n_vcf = 0, n_bins = 256;
@@ -396,8 +399,6 @@ struct qm_batch {
   HashRow* bk_rows = nullptr;       // one descriptor per (segment, bucket)
   int64_t cap_bk_rowdesc = 0;
   int64_t cap_bk_ent = 0, cap_bk_cursor = 0, cap_bk_tiles = 0;
-  bool bk_tiles_valid = false;      // d_bk_tile_seg holds the tile map of last_segs
-  bool bk_fake_valid = false;       // d_bk_vcfs holds the row descriptors of last_segs
   // rows (ROC, scalars, flags) of the VCFs a bucket chunk redoes, before they are copied under the original VCFs
   uint64_t* bk_roc = nullptr;
   int64_t* bk_rscal = nullptr;
@@ -411,21 +412,24 @@ struct qm_batch {
   SortSeg* d_vsegs = nullptr;
   int32_t* d_vparts = nullptr;          // partitions in use per VCF
   int64_t cap_vparts = 0;
-  std::vector<int> last2_seg_vcf;       // VCF of every level-2 segment of that chunk
-  std::vector<int> last2_vs;            // the chunk these tables were built for, and its counts: a batch run again with the same
-  std::vector<uint32_t> last2_cnt;      // VCFs out of order keeps them on the device (as last_segs does on the one-level path)
-  int last2_nseg = 0;
-  bool last2_halves = false;          // a VCF of the chunk has more than 2^24 records (BucketScatterParams.l1_half)
   uint32_t* p_half = nullptr;
   int64_t cap_p_half = 0;
-  int64_t last2_nbt = 0, last2_nkt = 0;
   int64_t cap_p_segs = 0, cap_p_tiles = 0, cap_p_cnt = 0, cap_p_off = 0, cap_p_cursor = 0, cap_p_flags = 0, cap_p_ent = 0, cap_vsegs = 0;
   // throw-away outputs of the rescan after a sort (kept: an allocation per finish costs more than the rescan)
   uint64_t* rs_roc = nullptr;
   int64_t* rs_scal = nullptr;
   uint32_t* rs_flags = nullptr;
-  // the segment tables of the last chunk, as uploaded: a batch that is run again with the same VCFs unsorted skips the upload
-  std::vector<SortSeg> last_segs;
+  // Which chunk's tables the shared arrays hold (d_segs, d_tile_seg, d_bk_tile_seg, d_ktile_*, d_bk_vcfs, d_vsegs, d_vparts, p_*): the
+  // path that built them, its VCFs, what else they follow from (their position bits; the two levels' counts) and what the path needs
+  // to launch over them again.  A path that finds its own chunk here uploads nothing (empty vcfs: nothing known).
+  struct Tables {
+    Path path = Path::Radix;
+    std::vector<int> vcfs;
+    std::vector<uint32_t> key;
+    int nseg = 0;
+    int64_t nbt = 0, nkt = 0;        // scatter tiles, K1 tiles
+    std::vector<int> seg_vcf;        // the VCF of every segment
+  } tables;
   uint64_t *roc = nullptr, *global_acc = nullptr;
   int64_t* scalars = nullptr;
   VcfDesc* d_vcfs = nullptr;
@@ -441,7 +445,7 @@ struct qm_batch {
   SortSeg* d_segs = nullptr;
   int32_t *d_tile_seg = nullptr, *d_ktile_seg = nullptr, *d_ktile_local = nullptr;
   int64_t cap_sort_n = 0, cap_sort_hist = 0;
-  int cap_segs = 0, cap_stiles = 0, cap_ktiles = 0;
+  int64_t cap_segs = 0, cap_stiles = 0, cap_ktiles = 0;
   // The run is pipelined over a few ranges of VCFs: k_compact of range i (issue-bound, writes) runs on the context's
   // second stream beside k_classify of range i + 1 (latency-bound, reads).
   static constexpr int MAX_CHUNKS = 8;
@@ -453,9 +457,9 @@ struct qm_batch {
   // while the run's compaction and row sums are still going, and starts right behind them
   hipEvent_t ev_flags = nullptr;
   bool flags_recorded = false;
-  // bucket chunks whose flags (overflow, bad position, highest bucket) nobody has looked at yet: their last kernels were queued
+  // one-level chunks whose flags (overflow, bad position, highest bucket) nobody has looked at yet: their last kernels were queued
   // without a round trip through the host (k_sort_copy_rows looks at the chunk's "bad" word itself); qm_batch_finish settles them
-  // behind its last wait and sends a chunk that did not fit through the radix sort then
+  // behind its last wait (settle_pending) and redoes a chunk that did not fit then
   struct Pending { std::vector<int> vs; int off; int nbk_launch; bool tight, direct; };
   std::vector<Pending> pend;
   int pend_segs = 0;   // mirror words handed out to the chunks of this finish
@@ -482,12 +486,6 @@ struct qm_batch {
   // What a finish found stays known while the columns stay the same (only qm_batch_upload* / qm_batch_synth write them): a VCF found out
   // of order is not streamed by the optimistic pass again, and qm_batch_finish queues its bucket path behind the run without first
   // waiting for the flags (a host round trip of ~ 0.15 ms per step).  QM_MEMO=0: off.
-  std::vector<int> lastx_vs;          // bucketx_chunk: the chunk whose tables are on the device (a batch run again)
-  std::vector<uint32_t> lastx_por;
-  bool lastx_wide = false;            // ... with the wide buckets of 2^17 positions (bucketw_takes)
-  std::vector<int> lastx_seg_vcf;     // VCF of every segment
-  int lastx_nseg = 0;
-  int64_t lastx_nbt = 0, lastx_nkt = 0;
   std::vector<uint8_t> known;         // per VCF: 1 = out of order, as the last finish found it
   std::vector<uint32_t> known_posor;  // its position bits (vcf_posor of that finish)
   // The position bits a VCF is remembered with come from what the optimistic pass SAW before it left (the first 256 records of a
@@ -911,12 +909,122 @@ extern "C" int qm_batch_timings(qm_batch* b, float* ms4) {
   return QM_OK;
 }
 
-// ---- sort path: unsorted VCFs are redone in chunks; every step of a chunk is one launch ----
+// ---- VCFs found out of order: redone in chunks of <= 2^28 records, every step of a chunk one launch ----
 constexpr int64_t SORT_CHUNK_RECORDS = 1ll << 28;
 static int64_t sort_chunk_records() {   // QM_SORT_CHUNK_RECORDS (tests, tools/gpu_fuzz.py): small chunks, several of them per finish
   if (const char* e = getenv("QM_SORT_CHUNK_RECORDS")) { const long long v = atoll(e); if (v > 0) return std::min<int64_t>(v, SORT_CHUNK_RECORDS); }
   return SORT_CHUNK_RECORDS;
 }
+
+// --- which path a VCF takes.  Plain values in, no batch: the routing compiles on its own.
+constexpr int N_PATHS = 5;
+constexpr int PX_MAX_PARTS = 4;              // partitions of 2^27 keys a VCF of the partitions path may span
+constexpr int PW_SHIFT = DJ_BIG_SHIFT + 8;   // 29: a partition of wide buckets
+// The knobs of the routing, read from the environment ONCE per qm_batch_finish: route() runs once per VCF, and ten getenv calls per
+// VCF were 22 us of a first-seen step's host time (256 VCFs) -- between the flags' arrival and the first launch, with the device waiting.
+struct PathEnv {
+  int forced = -1;                       // QM_UNSORTED_PATH (tests, fuzz): a Path every unsorted VCF it holds takes first, or -1
+  bool join_hash = false;                // QM_JOIN=hash: the hashed bucket join; the paths that have only k_join_lean are off
+  bool speculate = true;                 // QM_SPECULATE=0: every one-level chunk is looked at before its results are handed over
+  int64_t bucket_min = HB_MIN_RECORDS;   // QM_BUCKET_MIN: tests and tools/gpu_fuzz.py send their small VCFs through the buckets too
+};
+// partitions of 2^pshift keys a VCF's position bits reach into (key = pos << 4 | nibble)
+static int parts_of(uint32_t posor, int pshift = P2_SHIFT) { return (int)((((uint64_t)posor << 4) | 15u) >> pshift) + 1; }
+// the one-level path's bucket shift: the top eight key bits in use are the bucket number
+static int onelevel_shift(uint32_t posor) {
+  const uint32_t kor = (posor << 4) | 15u;
+  int msb = 31;
+  while (msb > 0 && !((kor >> msb) & 1u)) --msb;
+  return std::max(4, msb - 7);
+}
+// Capacity: what a path's tables and entries can hold at all.  One level: 256 buckets x 8 sub-regions x 1 024 entries at five eighths
+// full, 21 index bits.  Two levels: 26 index bits (runs of 2^24).  Partitions: <= 4 of 2^27 keys, 21 (allele-extended: the second
+// stream's entries) or 26 index bits.  Wide: <= 2 partitions of 2^29 keys.  The bucket joins of the last three are k_join_lean's.
+static bool onelevel_holds(int64_t n, const PathEnv& env) {
+  return n >= env.bucket_min && n <= (int64_t)HB_BUCKETS * HB_MAX_RECORDS * 5 / 8 && n <= ((int64_t)1 << HB_INDEX_BITS);
+}
+static bool wide_fits(bool ext, int64_t n, uint32_t posor, const PathEnv& env) {
+  return !ext && !env.join_hash && n <= ((int64_t)1 << 26) && parts_of(posor, PW_SHIFT) <= 2;
+}
+static bool path_holds(Path p, bool ext, int64_t n, uint32_t posor, const PathEnv& env) {
+  switch (p) {
+    case Path::Radix: return true;
+    case Path::OneLevel: return onelevel_holds(n, env);
+    case Path::TwoLevel: return !ext && !env.join_hash && n > 0 && n <= ((int64_t)P2_MAX_HALVES << P2_INDEX_BITS);
+    case Path::Partitions:
+      return !env.join_hash && n >= HB_MIN_RECORDS && n <= ((int64_t)1 << (ext ? HB_INDEX_BITS : 26)) && parts_of(posor) <= PX_MAX_PARTS;
+    case Path::Wide: return wide_fits(ext, n, posor, env) && n >= env.bucket_min;
+  }
+  return false;
+}
+// The path of one unsorted VCF of n records whose position bits are posor, against a truth set of truth_n keys.  The first row of
+// DESIGN.md §4.4's table that takes it.
+static Path route(bool ext, int64_t n, uint32_t posor, int64_t truth_n, const PathEnv& env) {
+  if (env.forced >= 0 && path_holds((Path)env.forced, ext, n, posor, env)) return (Path)env.forced;
+  const int parts = parts_of(posor);
+  const int64_t kor = ((int64_t)posor << 4) | 15;
+  // More records than the narrow buckets of its reference hold (8 192 per 2^15 positions, the sub-regions 13/16 full on average: 0.2
+  // records per position) overflow the partitions and the two levels alike: such a VCF goes to the radix sort alone instead of taking
+  // its chunk with it.  (The position bits are an upper bound of up to twice the highest position: this errs towards the buckets.)
+  const bool dense = !ext && n > ((kor >> DJ_MAX_SHIFT) + 1) * (HB_MAX_RECORDS * 13 / 16);
+  // row "allele-extended batches; default-mode VCFs on 8.4-16.8 M positions": partitions.  Default mode: a reference of 8.4 ... 16.8 M
+  // positions is ONE pair of partitions = one pass of the 512-digit scatter and the bit-map join, where the one-level path would need
+  // the hashed join and larger VCFs two levels (eight partitions per pass lost to the two levels by 2.6x: the pieces a tile leaves per
+  // bucket fall below an L2 line, profiles/r06_pmc_scatter2048_not_kept.json).  Allele-extended: whatever the one-level path does not
+  // take on a single partition.
+  if (!dense && path_holds(Path::Partitions, ext, n, posor, env) && (ext ? parts > 1 || !onelevel_holds(n, env) : parts == 2)) return Path::Partitions;
+  // row "default mode, 16.8-67 M positions": wide buckets, one pass of the 512-digit scatter over the columns where the two levels move
+  // every record twice.  Not fuller than eight sub-regions of 4 096 take; a bucket stages 4 096 truth keys (three quarters of that on
+  // average: the rest is room for an uneven truth set).
+  if (wide_fits(ext, n, posor, env) && n >= HB_MIN_RECORDS && parts >= 3) {
+    const int64_t buckets = (kor >> DJ_BIG_SHIFT) + 1;
+    if (n <= buckets * (4 * HB_MAX_RECORDS * 13 / 16) && truth_n <= buckets * (4 * DJ_TRUTH_MAX * 3 / 4)) {
+      // above the one-level path's 1.31 M records (50 Mb, 1.6e8 records per step: 2 M-record VCFs 4.3e10 /s against the two levels'
+      // 2.8e10, 5 M 6.7e10 against 3.6e10)
+      if (!onelevel_holds(n, env)) return Path::Wide;
+      // below it, the one-level path's hashed join (7.5e10 /s where it fits, the wide buckets 3.9e10) -- unless the truth set is
+      // too dense for the 1 024 truth keys it stages per bucket of 2^18+ positions (the chunk would overflow: radix sort, 1.3-1.7e10 /s;
+      // wide buckets 2.7-3.4e10)
+      if (truth_n > ((kor >> onelevel_shift(posor)) + 1) * (HB_TRUTH_SLOTS / 2 * 5 / 8)) return Path::Wide;
+    }
+  }
+  // rows "16 384 ... 1.31 M records" (k_join_lean) and "wider references" (k_classify_hash): one level, a VCF's 256 workgroups
+  // and rows whatever it holds (smaller VCFs are sorted in no time)
+  if (path_holds(Path::OneLevel, ext, n, posor, env)) return Path::OneLevel;
+  // row "1.31 M ... 67 M records on references beyond that": two levels
+  if (!dense && n >= HB_MIN_RECORDS && path_holds(Path::TwoLevel, ext, n, posor, env)) return Path::TwoLevel;
+  // last row: the radix sort
+  return Path::Radix;
+}
+
+// What a path does with a chunk: how many VCFs it takes (rows of 1.5 KB and >= 1 MB of bucket regions per VCF; wide buckets 2 x 67 MB),
+// whether a VCF weighs its records once per pass over its columns (partitions: a PAIR of them per pass), how often a chunk and the
+// VCFs of it that fitted run before what is left without a result goes to the next path.
+struct PathInfo { int max_vcfs; bool per_pass; int runs; Path next; };
+static const PathInfo PATHS[N_PATHS] = {
+    /* Radix      */ {INT32_MAX, false, 1, Path::Radix},
+    /* OneLevel   */ {4096, false, INT32_MAX, Path::Radix},
+    /* TwoLevel   */ {4096, false, 3, Path::Radix},   // (a partition too dense names one VCF at a time)
+    /* Partitions */ {4096 / PX_MAX_PARTS, true, 2, Path::Radix},
+    /* Wide       */ {64, false, 2, Path::TwoLevel},
+};
+
+static thread_local PathEnv g_penv;
+static int read_path_env() {
+  PathEnv e;
+  if (const char* v = getenv("QM_UNSORTED_PATH")) {
+    static const char* const names[N_PATHS] = {"radix", nullptr, "two_level", "partitions", "wide"};
+    for (int p = 0; p < N_PATHS; ++p) if (names[p] && strcmp(v, names[p]) == 0) e.forced = p;
+    if (e.forced < 0 && *v) return fail(QM_E_INVAL, "QM_UNSORTED_PATH=%s: radix, two_level, partitions or wide", v);
+  }
+  if (const char* v = getenv("QM_JOIN")) e.join_hash = strcmp(v, "hash") == 0;
+  if (const char* v = getenv("QM_SPECULATE")) e.speculate = atoi(v) != 0;
+  if (const char* v = getenv("QM_BUCKET_MIN")) e.bucket_min = atoll(v);
+  g_penv = e;
+  return QM_OK;
+}
+
+// --- the device arrays of a chunk
 
 // (Growing an array frees the old one.  A speculative bucket chunk returns with its last kernels still queued -- they read d_segs,
 // the cursors' "bad" word, the rows -- and the NEXT chunk of the same finish may grow exactly those: the device is drained first,
@@ -936,47 +1044,11 @@ static int regrow(T** p, int64_t* cap, int64_t need, int64_t* bytes) {
   return QM_OK;
 }
 
-// Which unsorted VCFs go through the bucket path (k_bucket_scatter + k_classify_hash): default-mode batches; large enough to be
-// worth 256 workgroups and 256 histogram rows (smaller ones are sorted in no time); small enough for 256 buckets x 8 sub-regions
-// x 1 024 entries at five eighths full and for the 21 index bits of an entry.  QM_SORT_PATH=radix keeps everything on the sort,
-// QM_BUCKET_MIN moves the lower limit.
-// The knobs that say which path an unsorted VCF takes, read from the environment ONCE per qm_batch_finish (redo_unsorted): the
-// predicates below run once per VCF, and ten getenv calls per VCF were 22 us of a first-seen step's host time (256 VCFs) -- between
-// the flags' arrival and the first launch of the bucket path, with the device waiting.
-struct PathEnv {
-  bool radix_only = false;     // QM_SORT_PATH=radix
-  int bucket_ext = -1;         // QM_BUCKET_EXT (-1: unset)
-  int bucket2 = -1;            // QM_BUCKET2
-  int bucketx = -1;            // QM_BUCKETX
-  int64_t bucket_min = HB_MIN_RECORDS;   // QM_BUCKET_MIN: tests and tools/gpu_fuzz.py send their small VCFs through the buckets too
-};
-static thread_local PathEnv g_penv;
-static void refresh_path_env() {
-  PathEnv e;
-  if (const char* v = getenv("QM_SORT_PATH")) e.radix_only = strcmp(v, "radix") == 0;
-  if (const char* v = getenv("QM_BUCKET_EXT")) e.bucket_ext = atoi(v);
-  if (const char* v = getenv("QM_BUCKET2")) e.bucket2 = atoi(v);
-  if (const char* v = getenv("QM_BUCKETX")) e.bucketx = atoi(v);
-  if (const char* v = getenv("QM_BUCKET_MIN")) e.bucket_min = atoll(v);
-  g_penv = e;
-}
-static bool bucket_path_takes(const qm_batch* b, int64_t n) {
-  if (b->ext && g_penv.bucket_ext == 0) return false;   // allele-extended batches on the radix sort only
-  if (g_penv.radix_only) return false;
-  return n >= g_penv.bucket_min && n <= (int64_t)HB_BUCKETS * HB_MAX_RECORDS * 5 / 8 && n <= ((int64_t)1 << HB_INDEX_BITS);
-}
-
-static bool join_hash_forced() {
-  static const bool on = getenv("QM_JOIN") && strcmp(getenv("QM_JOIN"), "hash") == 0;
-  return on;
-}
-
-// the scratch batch of a chunk of unsorted VCFs: their sorted copies on the radix path, the rows (ROC, scalars, flags) of every
-// path; rebuilt only when the chunk's shape changes
-static int ensure_sub(qm_batch* b, const std::vector<int>& vs, std::vector<int32_t>& tids) {
+// the scratch batch of a radix chunk: the sorted copies of its VCFs and their rows; rebuilt only when the chunk's shape changes
+static int ensure_sub(qm_batch* b, const std::vector<int>& vs) {
   const int nseg = (int)vs.size();
   std::vector<int64_t> sig((size_t)nseg);
-  tids.assign((size_t)nseg, 0);
+  std::vector<int32_t> tids((size_t)nseg);
   for (int i = 0; i < nseg; ++i) { sig[(size_t)i] = b->L.vcfs[(size_t)vs[(size_t)i]].n; tids[(size_t)i] = b->L.vcfs[(size_t)vs[(size_t)i]].truth; }
   if (!b->sub || b->sub_sig != sig) {
     if (b->sub) { b->dev_bytes -= b->sub->dev_bytes; batch_free(b->sub); b->sub = nullptr; }
@@ -986,10 +1058,8 @@ static int ensure_sub(qm_batch* b, const std::vector<int>& vs, std::vector<int32
     b->dev_bytes += b->sub->dev_bytes;
     b->sub_sig = sig;
     b->sub_tids = tids;
-    b->bk_fake_valid = false;
   } else if (b->sub_tids != tids) {
     b->sub_tids = tids;
-    b->bk_fake_valid = false;   // the row descriptors name the truth sets
     for (int i = 0; i < nseg; ++i) b->sub->L.vcfs[(size_t)i].truth = tids[(size_t)i];
     for (SpanDesc& sd : b->sub->L.spans) sd.truth = b->sub->L.vcfs[(size_t)sd.vcf].truth;
     int rc = upload_layout(b->sub);
@@ -998,13 +1068,127 @@ static int ensure_sub(qm_batch* b, const std::vector<int>& vs, std::vector<int32
   return QM_OK;
 }
 
-// the rows of a bucket chunk's VCFs (k_finalize over the buckets' rows writes them; k_sort_copy_rows takes them home): small
-// arrays of their own, so that a bucket chunk needs no scratch batch with room for sorted copies
-static int ensure_bucket_rows(qm_batch* b, int nv) {
-  int rc = regrow(&b->bk_roc, &b->cap_bk_roc, (int64_t)nv * 3 * b->n_bins, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_rscal, &b->cap_bk_rscal, (int64_t)nv * 8, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_vflags, &b->cap_bk_vflags, (int64_t)nv, &b->dev_bytes);
+// the segment table and k_tile_counts' map (every path): d_segs, d_ktile_seg, d_ktile_local
+static int ensure_seg_arrays(qm_batch* b, int64_t nseg, int64_t nkt) {
+  int rc = regrow(&b->d_segs, &b->cap_segs, nseg, &b->dev_bytes);
+  int64_t cap = b->cap_ktiles;
+  if (rc == QM_OK) rc = regrow(&b->d_ktile_seg, &cap, nkt, &b->dev_bytes);
+  cap = b->cap_ktiles;
+  if (rc == QM_OK) rc = regrow(&b->d_ktile_local, &cap, nkt, &b->dev_bytes);
+  if (rc == QM_OK) b->cap_ktiles = std::max(b->cap_ktiles, nkt);
   return rc;
+}
+
+// behind a bucket chunk's cursors ([nseg][256][8], then one flag word per segment): 32 + 16 * 65 phase clocks of a profiling build, the
+// scatter's per-segment histograms, seg_maxd, the chunk's "bad" word -- all of it cleared in front of the scatter
+static int64_t cursor_words(int64_t nseg) { return nseg * HB_BUCKETS * HB_SUBS + nseg + 32 + 16 * 65 + nseg * (SEG_HIST_WORDS + 1) + 1; }
+struct CursorRegion { uint32_t *seg_hist, *seg_maxd, *chunk_bad; uint32_t words; };
+static CursorRegion cursor_region(const qm_batch* b, int nseg) {
+  CursorRegion C;
+  C.seg_hist = b->bk_cursor + (size_t)nseg * HB_BUCKETS * HB_SUBS + (size_t)nseg + 32 + 16 * 65;
+  C.seg_maxd = C.seg_hist + (size_t)nseg * SEG_HIST_WORDS;
+  C.chunk_bad = C.seg_maxd + nseg;
+  C.words = (uint32_t)cursor_words(nseg);
+  return C;
+}
+
+// The arrays every bucket path fills for nseg segments: bucket regions (xs: the second entry stream's too), cursors, row descriptors,
+// the rows, the scatter's tile map, the row descriptors of k_finalize, and the rows (ROC, scalars, flags) of the VCFs before
+// k_sort_copy_rows takes them home -- small arrays of their own, so that a bucket chunk needs no scratch batch
+static int ensure_bucket_arrays(qm_batch* b, int64_t nseg, int64_t bk_ents, int64_t nbt, bool xs) {
+  const int64_t rows = nseg * HB_BUCKETS, orows = nseg * (xs ? 2 * HB_BUCKETS : HB_BUCKETS);
+  int64_t c1 = b->cap_bk_rows * SPAN_HIST_WORDS, c2 = b->cap_bk_rows * 8;   // (cap_bk_rows counts rows for both arrays)
+  int rc = regrow(&b->bk_hist, &c1, orows * SPAN_HIST_WORDS, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_scal, &c2, orows * 8, &b->dev_bytes);
+  if (rc == QM_OK) b->cap_bk_rows = std::max(b->cap_bk_rows, orows);
+  if (rc == QM_OK && xs) rc = regrow(&b->bk_xent, &b->cap_bk_xent, 2 * bk_ents, &b->dev_bytes);
+  if (rc == QM_OK && xs) rc = regrow(&b->bk_xcursor, &b->cap_bk_xcursor, rows * HB_SUBS, &b->dev_bytes);
+  if (rc == QM_OK && xs) rc = regrow(&b->bk_xrows, &b->cap_bk_xrows, rows, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->d_bk_vcfs, &b->cap_bk_vcfs, nseg, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_ent, &b->cap_bk_ent, bk_ents, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_rows, &b->cap_bk_rowdesc, rows, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_cursor, &b->cap_bk_cursor, cursor_words(nseg), &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->d_bk_tile_seg, &b->cap_bk_tiles, nbt, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_roc, &b->cap_bk_roc, nseg * 3 * b->n_bins, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_rscal, &b->cap_bk_rscal, nseg * 8, &b->dev_bytes);
+  if (rc == QM_OK) rc = regrow(&b->bk_vflags, &b->cap_bk_vflags, nseg, &b->dev_bytes);
+  return rc;
+}
+
+// --- the tables of a chunk on the device.  d_segs, the tile maps, d_bk_vcfs, d_vsegs, d_vparts and the two levels' p_* hold ONE chunk's
+// tables at a time: b->tables says which path built them for which VCFs, and what else they follow from.  A path rebuilds them when
+// its chunk's record differs -- a batch run again with the same VCFs out of order uploads nothing.
+static bool owns(const qm_batch* b, Path path, const std::vector<int>& vs, const std::vector<uint32_t>& key) {
+  return b->tables.path == path && b->tables.vcfs == vs && b->tables.key == key;
+}
+static std::vector<uint32_t> posor_of(const std::vector<int>& vs, const std::vector<uint32_t>& posor) {
+  std::vector<uint32_t> k(vs.size());
+  for (size_t i = 0; i < vs.size(); ++i) k[i] = posor[(size_t)vs[i]];
+  return k;
+}
+// k_tile_counts' map: the VCF (index into vs) and the tile inside it of every K1 tile of the chunk
+static void ktile_maps(const qm_batch* b, const std::vector<int>& vs, std::vector<int32_t>& seg, std::vector<int32_t>& local) {
+  for (size_t i = 0; i < vs.size(); ++i)
+    for (int t = 0; t < b->L.vcfs[(size_t)vs[i]].ntiles; ++t) { seg.push_back((int32_t)i); local.push_back(t); }
+}
+// the rows of a segment's buckets as the "spans" of a VCF, for k_finalize
+static VcfDesc bucket_vcf(int64_t n, int32_t truth, int32_t span0, int32_t nspans) {
+  VcfDesc f = VcfDesc();
+  f.off = 0; f.n = n; f.truth = truth; f.tile0 = 0; f.ntiles = 0; f.span0 = span0; f.nspans = nspans; f.pad = 0;
+  return f;
+}
+
+// One segment per VCF (the radix sort, the one-level buckets): where its records are, its sort tiles, its digit histograms, its buckets
+struct VcfSegs {
+  std::vector<SortSeg> segs;
+  int64_t koff = 0, hoff = 0, bk_ents = 0, nst = 0, nkt = 0, nbt = 0;
+};
+static int vcf_segs(const qm_batch* b, const std::vector<int>& vs, const std::vector<uint32_t>& posor, VcfSegs* T) {
+  T->segs.resize(vs.size());
+  int64_t dst_off = 0;
+  for (size_t i = 0; i < vs.size(); ++i) {
+    const VcfDesc& d = b->L.vcfs[(size_t)vs[i]];
+    SortSeg& g = T->segs[i];
+    g.src_off = d.off; g.dst_off = dst_off; g.koff = T->koff; g.hoff = T->hoff; g.n = d.n;   // dst_off: as build_layout lays the scratch batch out
+    dst_off += (d.n + VCF_ALIGN - 1) / VCF_ALIGN * VCF_ALIGN;
+    g.tile0 = (int32_t)T->nst; g.ntiles = (int32_t)((d.n + SORT_TILE - 1) / SORT_TILE);
+    g.main_vcf = vs[i]; g.sub_vcf = (int32_t)i; g.main_tile0 = d.tile0;
+    g.pad = onelevel_shift(posor[(size_t)vs[i]]);
+    // buckets above the VCF's highest position are empty by construction: <= 256
+    g.nbk = std::min((int)(((posor[(size_t)vs[i]] << 4) | 15u) >> g.pad) + 1, (int)HB_BUCKETS); g.key_base = 0u;
+    // room per sub-region: between 128 and 256 buckets are in use, a sub-region takes every eighth tile; half as much again on top
+    int64_t want = d.n / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;
+    while (cap2 < want && cap2 < HB_SUB_MAX) cap2 *= 2;
+    g.bk_cap = (int32_t)cap2; g.bk_off = T->bk_ents; g.bk_tile0 = (int32_t)T->nbt;
+    T->bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
+    T->nbt += (d.n + BK_TILE - 1) / BK_TILE;
+    T->nst += g.ntiles;
+    T->nkt += d.ntiles;
+    T->koff += (d.n + 63) / 64 * 64;
+    T->hoff += (int64_t)g.ntiles * 256;
+  }
+  if (T->nst > INT32_MAX || T->nkt > INT32_MAX || T->nbt > INT32_MAX) return fail(QM_E_LIMIT, "sort chunk: too many tiles");
+  return QM_OK;
+}
+
+// --- what the bucket paths share
+
+// The launch parameters of every bucket path, for the segment table in d_segs: cursors, entries, rows.  What differs is set by the
+// path itself: l1_ent / l1_half (two levels), pairs (partitions), seg_maxd (one level), H.zero.
+static void bucket_params(qm_batch* b, int nseg, bool xs, uint32_t* seg_hist, BucketScatterParams* S, HashParams* H) {
+  S->segs = b->d_segs; S->tile_seg = b->d_bk_tile_seg; S->pos = b->pos; S->ref = b->ref; S->alt = b->alt; S->qual = b->qual; S->flags = b->flags;
+  S->cursor = b->bk_cursor; S->ent = b->bk_ent; S->mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); S->mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp);
+  S->n_seg = nseg; S->n_bins = b->n_bins; S->tile_base = 0;
+  S->xent = xs ? b->bk_xent : nullptr; S->xcursor = xs ? b->bk_xcursor : nullptr; S->ext = xs ? 1 : 0;
+  S->seg_hist = seg_hist;   // k_join_lean follows: the scatter counts every record by bin
+  S->l1_ent = nullptr; S->l1_half = nullptr; S->pairs = 0; S->seg_maxd = nullptr;
+  H->segs = b->d_segs; H->rows = b->bk_rows; H->rows_out = b->bk_rows; H->ent = b->bk_ent; H->cursor = b->bk_cursor; H->truths = b->ctx->d_truths; H->vcfs = b->d_vcfs;
+  H->mask_tp = b->mask_tp; H->row_hist = b->bk_hist; H->row_scal = b->bk_scal; H->n_seg = nseg; H->n_bins = b->n_bins; H->seg_base = 0;
+  H->xrows = xs ? b->bk_xrows : nullptr; H->xent = xs ? b->bk_xent : nullptr; H->xcursor = xs ? b->bk_xcursor : nullptr;
+  H->out_stride = xs ? 2 * HB_BUCKETS : HB_BUCKETS; H->ext = xs ? 1 : 0;
+  H->scatter_hist = seg_hist ? 1 : 0;
+  H->seg_maxd = nullptr;
+  H->zero = nullptr; H->n_zero = 0u;
 }
 static FinalizeParams bucket_rows_finalize(qm_batch* b, const uint32_t* all_hist) {
   FinalizeParams F = finalize_params(b, nullptr);   // the rows join the per-truth sums only once no bucket is known to have overflowed
@@ -1015,315 +1199,82 @@ static FinalizeParams bucket_rows_finalize(qm_batch* b, const uint32_t* all_hist
   return F;
 }
 
-// posor[v]: OR of the positions the optimistic pass saw in VCF v (which position bits are in use)
-static thread_local double g_ftrace[4];   // QM_FINISH_TRACE: host clock inside the latest sort_chunk (entered, tables ready, scatter queued)
-static double ftrace_now() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; }
-static int sort_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, uint64_t* global, const std::vector<uint32_t>& posor, bool buckets, bool may_speculate);
-// A one-level bucket chunk one of whose VCFs did not fit: `bad` (the VCFs with the flag) through the radix sort, `good` (the others)
-// through the buckets once more, looked at before they are handed over.  (Through round 5 the whole chunk took the radix sort: one
-// VCF with a crowd of records on a few positions sent up to 4 096 others onto the path that is four times slower.)
-static int redo_overflowed(qm_batch* b, const std::vector<int>& bad, const std::vector<int>& good, hipStream_t st, uint64_t* global, const std::vector<uint32_t>& posor) {
-  int rc = QM_OK;
-  if (!good.empty()) rc = sort_chunk(b, good, st, global, posor, true, false);
-  if (rc == QM_OK && !bad.empty()) {
-    b->path_stats[QM_PATH_RADIX_AFTER_OVERFLOW] += (int64_t)bad.size();
-    rc = sort_chunk(b, bad, st, global, posor, false, false);
-    b->path_stats[QM_PATH_RADIX] -= (int64_t)bad.size();
+// The verdict on a bucket chunk whose rows' flags are on the host: per segment its flag word and (maxd, or null) the highest bucket its
+// records reached, against the nbk launched.  A bad position fails the finish; *named gets the VCFs with an overflowing bucket (a VCF's
+// segments lie one behind the other) -- nothing of such a chunk may be handed over.
+static int bucket_verdict(qm_batch* b, const uint32_t* fl, const uint32_t* maxd, uint32_t nbk, const std::vector<int>& seg_vcf, std::vector<int>* named) {
+  named->clear();
+  for (size_t i = 0; i < seg_vcf.size(); ++i) {
+    const int v = seg_vcf[i];
+    if (fl[i] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", v);
+    // (maxd above nbk: a remembered bound that no longer holds -- cannot happen while the columns stay the same)
+    const bool over = (fl[i] & SPANF_OVERFLOW) || (maxd && maxd[i] > nbk);
+    if (over && (named->empty() || named->back() != v)) named->push_back(v);
   }
-  return rc;
+  if (!named->empty()) b->path_stats[QM_PATH_OVERFLOW_CHUNKS] += 1;
+  return QM_OK;
 }
 
-// may_speculate = false: the chunk's flags are looked at before its results are handed over (the re-run of the VCFs that fitted, above)
-static int sort_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, uint64_t* global, const std::vector<uint32_t>& posor, bool buckets, bool may_speculate = true) {
+// A bucket chunk's results home: its rows under the original VCFs and into the per-truth sums (k_sort_copy_rows; nparts: segments per
+// VCF to add up, or null), the tile counts from its masks.  segs: one per VCF.  gate (a speculative chunk): the chunk's "bad" word --
+// k_sort_copy_rows leaves everything alone if it says the chunk overflowed; such a chunk is counted when it is settled (stat < 0).
+static int hand_over(qm_batch* b, const SortSeg* segs, int nv, const int32_t* nparts, int64_t nkt, const uint32_t* gate, int stat, hipStream_t st) {
+  launch_sort_copy_rows(segs, nv, b->bk_roc, b->bk_rscal, b->roc, b->scalars, b->n_bins, st, b->last_global, b->d_vcfs, nparts, gate);
+  launch_tile_counts(segs, b->d_ktile_seg, b->d_ktile_local, (int)nkt, b->mask_pass, b->mask_tp, b->tile_tp, b->tile_fp, st);
+  HIPCHK(hipGetLastError());
+  if (stat >= 0) b->path_stats[stat] += nv;
+  return QM_OK;   // no wait: the rescan that follows is on the same stream and ends with one
+}
+
+static thread_local double g_ftrace[4];   // QM_FINISH_TRACE: host clock inside the latest chunk (entered, tables ready, scatter queued)
+static double ftrace_now() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; }
+
+// --- the radix sort: stable LSD passes by position over the digits in use, k_classify<PACKED> on the sorted copies, results home.
+// stat: the counter its VCFs go to (QM_PATH_RADIX, or QM_PATH_RADIX_AFTER_OVERFLOW behind a bucket path).
+static int radix_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, const std::vector<uint32_t>& posor, int stat) {
   g_ftrace[0] = ftrace_now();
   const int nseg = (int)vs.size();
-  std::vector<int32_t> tids((size_t)nseg);
-  for (int i = 0; i < nseg; ++i) tids[(size_t)i] = b->L.vcfs[(size_t)vs[(size_t)i]].truth;
-  if (!buckets) {   // the scratch batch of the sorted copies: only the radix sort needs it (a bucket chunk that overflows makes it below)
-    int rc = ensure_sub(b, vs, tids);
-    if (rc != QM_OK) return rc;
-  }
-  // --- segment table and tile maps
-  std::vector<SortSeg> segs((size_t)nseg);
-  std::vector<int> nbk_used((size_t)nseg, HB_BUCKETS);
-  int64_t koff = 0, hoff = 0, bk_ents = 0, nst64 = 0, nkt64 = 0, nbt64 = 0, dst_off = 0;
-  for (int i = 0; i < nseg; ++i) {
-    const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
-    SortSeg& g = segs[(size_t)i];
-    g.src_off = d.off; g.dst_off = dst_off; g.koff = koff; g.hoff = hoff; g.n = d.n;   // dst_off: as build_layout lays the scratch batch out
-    dst_off += (d.n + VCF_ALIGN - 1) / VCF_ALIGN * VCF_ALIGN;
-    g.tile0 = (int32_t)nst64; g.ntiles = (int32_t)((d.n + SORT_TILE - 1) / SORT_TILE);
-    g.main_vcf = vs[(size_t)i]; g.sub_vcf = i; g.main_tile0 = d.tile0;
-    {   // bucket path: the shift that makes the top eight key bits in use the bucket number (key = pos << 4 | nibble)
-      const uint32_t kor = (posor[(size_t)vs[(size_t)i]] << 4) | 15u;
-      int msb = 31;
-      while (msb > 0 && !((kor >> msb) & 1u)) --msb;
-      g.pad = std::max(4, msb - 7);
-      nbk_used[(size_t)i] = (int)(kor >> g.pad) + 1;   // buckets above the VCF's highest position are empty by construction: <= 256
-      g.nbk = std::min(nbk_used[(size_t)i], (int)HB_BUCKETS); g.key_base = 0u;
-      // room per sub-region: between 128 and 256 buckets are in use, a sub-region takes every eighth tile; half as much again on top
-      int64_t want = d.n / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;
-      while (cap2 < want && cap2 < HB_SUB_MAX) cap2 *= 2;
-      g.bk_cap = (int32_t)cap2;
-      g.bk_off = bk_ents;
-      g.bk_tile0 = (int32_t)nbt64;
-      bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
-      nbt64 += (d.n + BK_TILE - 1) / BK_TILE;
-    }
-    nst64 += g.ntiles;
-    nkt64 += d.ntiles;
-    koff += (d.n + 63) / 64 * 64;
-    hoff += (int64_t)g.ntiles * 256;
-  }
-  if (nst64 > INT32_MAX || nkt64 > INT32_MAX || nbt64 > INT32_MAX) return fail(QM_E_LIMIT, "sort chunk: too many tiles");
-  const int nst = (int)nst64, nkt = (int)nkt64, nbt = (int)nbt64;
-  // the tile maps (which segment a tile belongs to) follow from the segment table and are only spelled out when it changed:
-  // a batch that is run again and again with the same VCFs out of order keeps them on the device
-  std::vector<int32_t> tile_seg, ktile_seg, ktile_local, bk_tile_seg;
-  auto build_tile_maps = [&]() {
-    tile_seg.reserve((size_t)nst); ktile_seg.reserve((size_t)nkt); ktile_local.reserve((size_t)nkt); bk_tile_seg.reserve((size_t)nbt);
-    for (int i = 0; i < nseg; ++i) {
-      const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
-      for (int t = 0; t < segs[(size_t)i].ntiles; ++t) tile_seg.push_back(i);
-      for (int t = 0; t < d.ntiles; ++t) { ktile_seg.push_back(i); ktile_local.push_back(t); }
-      for (int64_t t = 0; t < (d.n + BK_TILE - 1) / BK_TILE; ++t) bk_tile_seg.push_back(i);
-    }
-  };
-  int rc = QM_OK;
-  int64_t cap;
-  if (rc == QM_OK) { cap = b->cap_segs; rc = regrow(&b->d_segs, &cap, (int64_t)nseg, &b->dev_bytes); b->cap_segs = (int)cap; }
-  if (rc == QM_OK) { cap = b->cap_stiles; rc = regrow(&b->d_tile_seg, &cap, (int64_t)nst, &b->dev_bytes); b->cap_stiles = (int)cap; }
-  if (rc == QM_OK) {
-    cap = b->cap_ktiles; rc = regrow(&b->d_ktile_seg, &cap, (int64_t)nkt, &b->dev_bytes);
-    if (rc == QM_OK) { cap = b->cap_ktiles; rc = regrow(&b->d_ktile_local, &cap, (int64_t)nkt, &b->dev_bytes); }
-    if (rc == QM_OK) b->cap_ktiles = std::max(b->cap_ktiles, nkt);
-  }
+  int rc = ensure_sub(b, vs);
+  VcfSegs T;
+  if (rc == QM_OK) rc = vcf_segs(b, vs, posor, &T);
+  if (rc == QM_OK) rc = ensure_seg_arrays(b, nseg, T.nkt);
+  if (rc == QM_OK) rc = regrow(&b->d_tile_seg, &b->cap_stiles, T.nst, &b->dev_bytes);
   if (rc == QM_OK && !b->sorbits) rc = dalloc(&b->sorbits, 1);
-  // The bucket path (k_classify_hash): ONE scatter pass, no sort.  For batches of the default mode whose VCFs are small enough
-  // for 256 buckets of at most HB_MAX_RECORDS records; QM_SORT_PATH=radix keeps everything on the radix sort.
-  bool try_buckets = buckets;   // the caller chose the chunk's VCFs by size (bucket_path_takes)
-  int lb_all = 0, nbk_all = 1;
-  for (int i = 0; i < nseg; ++i) { lb_all = std::max(lb_all, (int)segs[(size_t)i].pad); nbk_all = std::max(nbk_all, std::min(nbk_used[(size_t)i], (int)HB_BUCKETS)); }
-  const bool direct = lb_all <= DJ_MAX_SHIFT && !join_hash_forced();
-  // allele-extended batches: two entry streams and two joins per bucket (k_join_lean for the single-base records, k_join_ext
-  // for the others), both of which need the bucket's key range to fit the bit maps; wider key ranges take the radix sort
-  const bool xstream = b->ext;
-  if (xstream && !direct) try_buckets = false;
-  const int out_stride = xstream ? 2 * HB_BUCKETS : HB_BUCKETS;
-  if (xstream) nbk_all = HB_BUCKETS;   // every row of a segment is written (the rows of the second stream follow at a fixed distance)
-  if (rc == QM_OK && !try_buckets && buckets) rc = ensure_sub(b, vs, tids);
-  if (rc == QM_OK && try_buckets) {
-    const int64_t rows = (int64_t)nseg * HB_BUCKETS;   // cap_bk_rows counts rows for both arrays
-    const int64_t orows = (int64_t)nseg * out_stride;
-    int64_t c1 = b->cap_bk_rows * SPAN_HIST_WORDS, c2 = b->cap_bk_rows * 8;
-    rc = regrow(&b->bk_hist, &c1, orows * SPAN_HIST_WORDS, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_scal, &c2, orows * 8, &b->dev_bytes);
-    if (rc == QM_OK) b->cap_bk_rows = std::max(b->cap_bk_rows, orows);
-    if (rc == QM_OK && xstream) {
-      rc = regrow(&b->bk_xent, &b->cap_bk_xent, 2 * bk_ents, &b->dev_bytes);
-      if (rc == QM_OK) rc = regrow(&b->bk_xcursor, &b->cap_bk_xcursor, rows * HB_SUBS, &b->dev_bytes);
-      if (rc == QM_OK) rc = regrow(&b->bk_xrows, &b->cap_bk_xrows, rows, &b->dev_bytes);
-    }
-    if (rc == QM_OK) rc = regrow(&b->d_bk_vcfs, &b->cap_bk_vcfs, (int64_t)nseg, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_ent, &b->cap_bk_ent, bk_ents, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_rows, &b->cap_bk_rowdesc, rows, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_cursor, &b->cap_bk_cursor, rows * HB_SUBS + nseg + 32 + 16 * 65 + (int64_t)nseg * (SEG_HIST_WORDS + 1) + 1, &b->dev_bytes);   // + 32 + 16 * 65: phase clocks of a profiling build; + 1: the chunk's "bad" word
-    if (rc == QM_OK) rc = ensure_bucket_rows(b, nseg);
-    if (rc == QM_OK && (int64_t)nbt > b->cap_bk_tiles) {
-      b->bk_tiles_valid = false;
-      rc = regrow(&b->d_bk_tile_seg, &b->cap_bk_tiles, (int64_t)nbt, &b->dev_bytes);
-    }
-  }
   if (rc != QM_OK) return rc;
-  b->last2_vs.clear(); b->lastx_vs.clear();   // (the two-level path and the partitions path keep their tables in the same arrays)
-  const bool same_tables = b->last_segs.size() == segs.size() && memcmp(b->last_segs.data(), segs.data(), sizeof(SortSeg) * segs.size()) == 0;
-  if (!same_tables || (try_buckets && !b->bk_tiles_valid)) {
-    build_tile_maps();
-    if (!same_tables) {
-      HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(b->d_tile_seg, tile_seg.data(), 4 * tile_seg.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-      b->bk_tiles_valid = false;
-      b->bk_fake_valid = false;
-    }
-    if (try_buckets && !b->bk_tiles_valid) HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // the host vectors die with this call
-    b->last_segs = segs;
-    b->bk_tiles_valid = try_buckets;
+  const int nst = (int)T.nst, nkt = (int)T.nkt;
+  const std::vector<uint32_t> key = posor_of(vs, posor);
+  if (!owns(b, Path::Radix, vs, key)) {
+    b->tables = qm_batch::Tables();
+    std::vector<int32_t> tile_seg, ktile_seg, ktile_local;
+    for (int i = 0; i < nseg; ++i) tile_seg.insert(tile_seg.end(), (size_t)T.segs[(size_t)i].ntiles, (int32_t)i);
+    ktile_maps(b, vs, ktile_seg, ktile_local);
+    HIPCHK(hipMemcpyAsync(b->d_segs, T.segs.data(), sizeof(SortSeg) * T.segs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_tile_seg, tile_seg.data(), 4 * tile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // the host vectors die with this block
+    b->tables = qm_batch::Tables{Path::Radix, vs, key, nseg, T.nbt, T.nkt, vs};
   }
-  SortCols src = {b->pos, b->ref, b->alt, b->qual, b->flags};
-  if (try_buckets) {
-    // --- bucket path: ONE scatter on each VCF's top eight key bits into fixed-size bucket regions, then the hash-join per bucket
-    if (!b->bk_fake_valid) {   // the buckets of a VCF as the "spans" of a VCF, for k_finalize
-      std::vector<VcfDesc> fake((size_t)nseg);
-      for (int i = 0; i < nseg; ++i) {
-        VcfDesc& f = fake[(size_t)i];
-        f = VcfDesc();
-        f.off = 0; f.n = segs[(size_t)i].n; f.truth = tids[(size_t)i]; f.tile0 = 0; f.ntiles = 0; f.span0 = i * out_stride;
-        f.nspans = xstream ? out_stride : std::min(nbk_used[(size_t)i], (int)HB_BUCKETS); f.pad = 0;
-      }
-      HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-      b->bk_fake_valid = true;
-    }
-    const size_t nhist0 = (size_t)nseg * HB_BUCKETS * HB_SUBS + (size_t)nseg + 32 + 16 * 65;   // the scatter's per-segment histograms lie behind the cursors, flags and phase clocks
-  const size_t ncur = (nhist0 + (size_t)nseg * (SEG_HIST_WORDS + 1) + 1) * 4;   // (+ 1: seg_maxd behind the histograms; + 1: the chunk's "bad" word behind them)
-    BucketScatterParams S;
-    S.segs = b->d_segs; S.tile_seg = b->d_bk_tile_seg; S.pos = b->pos; S.ref = b->ref; S.alt = b->alt; S.qual = b->qual; S.flags = b->flags;
-    S.cursor = b->bk_cursor; S.ent = b->bk_ent; S.mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); S.mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp);
-    S.n_seg = nseg; S.n_bins = b->n_bins; S.tile_base = 0; S.l1_ent = nullptr;
-    S.xent = xstream ? b->bk_xent : nullptr; S.xcursor = xstream ? b->bk_xcursor : nullptr; S.ext = xstream ? 1 : 0; S.pairs = 0;
-    uint32_t* const seg_hist = direct ? b->bk_cursor + nhist0 : nullptr;   // k_join_lean follows: the scatter counts every record by bin
-    S.seg_hist = seg_hist; S.l1_half = nullptr;
-    uint32_t* const seg_maxd = b->bk_cursor + nhist0 + (size_t)nseg * SEG_HIST_WORDS;
-    uint32_t* const chunk_bad = seg_maxd + nseg;
-    S.seg_maxd = seg_maxd;
-    if (xstream) HIPCHK(hipMemsetAsync(b->bk_xcursor, 0, (size_t)nseg * HB_BUCKETS * HB_SUBS * 4, st));
-    HashParams H;
-    H.segs = b->d_segs; H.rows = b->bk_rows; H.rows_out = b->bk_rows; H.ent = b->bk_ent; H.cursor = b->bk_cursor; H.truths = b->ctx->d_truths; H.vcfs = b->d_vcfs;
-    H.mask_tp = b->mask_tp; H.row_hist = b->bk_hist; H.row_scal = b->bk_scal; H.n_seg = nseg; H.n_bins = b->n_bins; H.seg_base = 0;
-    H.xrows = xstream ? b->bk_xrows : nullptr; H.xent = b->bk_xent; H.xcursor = b->bk_xcursor; H.out_stride = out_stride; H.ext = xstream ? 1 : 0;
-    H.scatter_hist = seg_hist ? 1 : 0;
-    H.seg_maxd = nullptr;   // (set below once the launch shape is known)
-    H.zero = b->bk_cursor; H.n_zero = (uint32_t)(ncur / 4);   // the scatter's cursors, flags, counts: cleared by the kernel that writes the rows
-    g_ftrace[1] = ftrace_now();
-    launch_bucket_rows(H, nseg, st);
-    H.zero = nullptr; H.n_zero = 0u;
-    // The scatter streams (memory-bound, its SIMDs half idle), the join issues instructions (and hardly waits for memory): in a
-    // few segment ranges, the join of one range on the second stream beside the scatter of the next, they fill each other's gaps.
-    // k_classify_hash issues instructions where the scatter waits for memory: a few segment ranges, the join of one on the second
-    // stream beside the scatter of the next, fill each other's gaps (- 7 %).  The bit-map join (then k_join_direct) was bound by the latency of a
-    // workgroup's serial steps and wants every LDS slot of the chip: beside a scatter it only loses (3.06 ms in one piece
-    // against 3.11 - 3.22 in 2 - 8 ranges, same box)
-    int nbk_launch = nbk_all;
-    int parts = nseg >= 8 && b->ev_sync[0] && !direct ? 4 : 1;
-    if (!b->ev_sync[0]) parts = 1;
-    const bool tight_nbk = direct && parts == 1;
-    if (tight_nbk) H.seg_maxd = seg_maxd;
-    hipStream_t aux = parts > 1 ? b->ctx->aux : st;
-    int i0 = 0;
-    for (int p = 0; p < parts; ++p) {
-      // ranges of about equal record counts
-      int i1 = p + 1 == parts ? nseg : i0;
-      if (p + 1 < parts) {
-        const int64_t want = (int64_t)nbt * (p + 1) / parts;
-        while (i1 < nseg && segs[(size_t)i1].bk_tile0 < want) ++i1;
-        i1 = std::max(i1, i0);
-      }
-      if (i1 > i0) {
-        const int t0 = segs[(size_t)i0].bk_tile0, t1 = i1 < nseg ? segs[(size_t)i1].bk_tile0 : nbt;
-        S.tile_base = t0;
-        launch_bucket_scatter(S, t1 - t0, st);
-        g_ftrace[2] = ftrace_now();
-        if (parts > 1) {
-          HIPCHK(hipEventRecord(b->ev_sync[p], st));
-          HIPCHK(hipStreamWaitEvent(aux, b->ev_sync[p], 0));
-        }
-        H.seg_base = i0;
-        // The buckets above a VCF's highest position hold nothing, and a workgroup that finds its bucket empty has still held a
-        // slot of its CU for a memory round trip: 40 % of the grid on a 5 Mb genome, whose position BITS (all the optimistic pass
-        // hands over) bound the buckets in use only by 256 -- 0.09 of the step's 2.65 ms (same box).  The scatter notes the
-        // highest bucket it filled per segment (seg_maxd): the join's workgroups above it leave at once and k_finalize sums no
-        // row of theirs -- no round trip through the host.
-        if (tight_nbk) {   // a batch that ran before remembers the highest bucket of every VCF: nothing is launched above
-          bool have = memo_on() && !b->known_nbk.empty();
-          uint32_t m = 0;
-          if (have) for (int i = 0; i < nseg && have; ++i) { const uint32_t k = b->known_nbk[(size_t)vs[(size_t)i]]; have = k != 0u; m = std::max(m, k); }
-          if (have && !xstream) nbk_launch = (int)std::min<uint32_t>(std::max(m, 1u), (uint32_t)nbk_all);   // (two streams: every bucket is launched, the rows of the second follow at a fixed distance)
-        }
-        // the join: one bit per key of the bucket in LDS where a bucket's key range allows it (k_join_lean: two bits per position), the hashed
-        // tables of k_classify_hash otherwise (QM_JOIN=hash: always)
-        if (direct) launch_join_lean(H, i1 - i0, lb_all, nbk_launch, aux);
-        else launch_classify_hash(H, i1 - i0, aux);
-        if (xstream) launch_join_ext(H, i1 - i0, nbk_all, aux);
-      }
-      i0 = i1;
-    }
-    if (parts > 1) {
-      HIPCHK(hipEventRecord(b->ev_sync[qm_batch::MAX_CHUNKS + 1], aux));
-      HIPCHK(hipStreamWaitEvent(st, b->ev_sync[qm_batch::MAX_CHUNKS + 1], 0));
-    }
-    const bool mirrors = b->d_summary != nullptr && nseg <= b->n_vcf;   // (one segment per VCF on this path)
-    // No round trip through the host between the rows' k_finalize and the kernels that hand the chunk's results over: they are queued
-    // at once, k_sort_copy_rows looks at the chunk's "bad" word on the device, and qm_batch_finish reads the mirrors behind its last
-    // wait (settle_pending) -- 15-25 us per chunk of 2.5 ms.  Every chunk of a finish has mirror words of its own (b->pend_segs).
-    const bool speculate = may_speculate && mirrors && b->pend_segs + nseg <= b->n_vcf && !(getenv("QM_SPECULATE") && atoi(getenv("QM_SPECULATE")) == 0);
-    const int moff = speculate ? b->pend_segs : 0;
-    {
-      FinalizeParams F = bucket_rows_finalize(b, seg_hist);
-      if (tight_nbk) F.row_cap = seg_maxd;   // (the rows above were not written by this run)
-      if (mirrors) { F.host_flags = b->d_summary + 16 + 2 * b->n_vcf + moff; F.host_aux = b->d_summary + 16 + 3 * b->n_vcf + moff; }   // (a place of their own: the run's flags may still be unread)
-      if (speculate) { F.chunk_bad = chunk_bad; F.row_cap_limit = (uint32_t)nbk_launch; }
-      launch_finalize(F, nseg, st);
-    }
-    if (speculate) {
-      launch_sort_copy_rows(b->d_segs, nseg, b->bk_roc, b->bk_rscal, b->roc, b->scalars, b->n_bins, st, global, b->d_vcfs, nullptr, chunk_bad);
-      launch_tile_counts(b->d_segs, b->d_ktile_seg, b->d_ktile_local, nkt, b->mask_pass, b->mask_tp, b->tile_tp, b->tile_fp, st);
-      HIPCHK(hipGetLastError());
-      b->path_stats[QM_PATH_BUCKET_CHUNKS] += 1;
-      b->pend.push_back(qm_batch::Pending{vs, moff, nbk_launch, tight_nbk, direct});
-      b->pend_segs += nseg;
-      return QM_OK;
-    }
-    HIPCHK(hipGetLastError());
-    std::vector<uint32_t> hfl((size_t)nseg), hmd((size_t)nseg, 0u);
-    if (!mirrors) {
-      HIPCHK(hipMemcpyAsync(hfl.data(), b->bk_vflags, 4 * hfl.size(), hipMemcpyDeviceToHost, st));
-      if (tight_nbk) HIPCHK(hipMemcpyAsync(hmd.data(), seg_maxd, 4 * hmd.size(), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));   // also makes the host tables above safe to free
-    if (mirrors) {   // k_finalize's host-mapped mirrors: the flags and (row_cap) the highest buckets, no copy
-      memcpy(hfl.data(), b->h_summary + 16 + 2 * b->n_vcf, 4 * hfl.size());
-      if (tight_nbk) memcpy(hmd.data(), b->h_summary + 16 + 3 * b->n_vcf, 4 * hmd.size());
-    }
-    if (tight_nbk) {
-      for (int i = 0; i < nseg; ++i) if (hmd[(size_t)i] > (uint32_t)nbk_launch) hfl[(size_t)i] |= SPANF_OVERFLOW;   // (a remembered bound that no longer holds: cannot happen while the columns stay the same)
-      if (memo_on()) {
-        if (b->known_nbk.empty()) b->known_nbk.assign((size_t)b->n_vcf, 0u);
-        for (int i = 0; i < nseg; ++i) b->known_nbk[(size_t)vs[(size_t)i]] = std::max(hmd[(size_t)i], 1u);
-      }
-    }
-    bool overflow = false;
-    for (int i = 0; i < nseg; ++i) {
-      if (hfl[(size_t)i] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", vs[(size_t)i]);
-      overflow = overflow || (hfl[(size_t)i] & SPANF_OVERFLOW);
-    }
-    b->path_stats[QM_PATH_BUCKET_CHUNKS] += 1;
-    if (!overflow) {
-      b->path_stats[direct ? QM_PATH_DIRECT : QM_PATH_HASHED] += nseg;
-      launch_sort_copy_rows(b->d_segs, nseg, b->bk_roc, b->bk_rscal, b->roc, b->scalars, b->n_bins, st, global, b->d_vcfs);
-      launch_tile_counts(b->d_segs, b->d_ktile_seg, b->d_ktile_local, nkt, b->mask_pass, b->mask_tp, b->tile_tp, b->tile_fp, st);
-      HIPCHK(hipGetLastError());
-      return QM_OK;   // no wait: the rescan that follows is on the same stream and ends with one
-    }
-    // a bucket did not fit its tables (dense positions, a dense truth set): the radix sort redoes THAT VCF from the columns; the
-    // VCFs of the chunk that fitted take the buckets again, among themselves (nothing of a chunk with a flag is handed over)
-    b->path_stats[QM_PATH_OVERFLOW_CHUNKS] += 1;
-    std::vector<int> bad, good;
-    for (int i = 0; i < nseg; ++i) ((hfl[(size_t)i] & SPANF_OVERFLOW) ? bad : good).push_back(vs[(size_t)i]);
-    return redo_overflowed(b, bad, good, st, global, posor);
-  } else {
-    b->path_stats[QM_PATH_RADIX] += nseg;
-  }
+  b->path_stats[stat] += nseg;
   b->path_stats[QM_PATH_RADIX_CHUNKS] += 1;
   qm_batch* s = b->sub;
   // --- 1. + 2. stable LSD radix sort by position (key bits 4..31), only the digits in use.  The first pass packs the
   //        records to (key, info, original index) on the fly; the last pass drops keys and infos straight into the
   //        scratch batch.  (Its ping-pong arrays exist only once a chunk has come this way.)
+  int64_t cap;
   for (int i = 0; i < 2 && rc == QM_OK; ++i) {
-    cap = b->cap_sort_n; rc = regrow(&b->sk[i], &cap, koff, &b->dev_bytes);
-    if (rc == QM_OK) { cap = b->cap_sort_n; rc = regrow(&b->sv[i], &cap, koff, &b->dev_bytes); }
-    if (rc == QM_OK) { cap = b->cap_sort_n; rc = regrow(&b->si[i], &cap, koff, &b->dev_bytes); }
+    cap = b->cap_sort_n; rc = regrow(&b->sk[i], &cap, T.koff, &b->dev_bytes);
+    if (rc == QM_OK) { cap = b->cap_sort_n; rc = regrow(&b->sv[i], &cap, T.koff, &b->dev_bytes); }
+    if (rc == QM_OK) { cap = b->cap_sort_n; rc = regrow(&b->si[i], &cap, T.koff, &b->dev_bytes); }
   }
-  if (rc == QM_OK) b->cap_sort_n = std::max(b->cap_sort_n, koff);
-  if (rc == QM_OK) rc = regrow(&b->shist, &b->cap_sort_hist, hoff, &b->dev_bytes);
+  if (rc == QM_OK) b->cap_sort_n = std::max(b->cap_sort_n, T.koff);
+  if (rc == QM_OK) rc = regrow(&b->shist, &b->cap_sort_hist, T.hoff, &b->dev_bytes);
   if (rc != QM_OK) return rc;
   HIPCHK(hipMemsetAsync(b->sorbits, 0, 4, st));
   launch_sort_first_hist(b->d_segs, b->d_tile_seg, nst, b->pos, b->shist, b->sorbits, st);
   uint32_t orbits = 0;
   HIPCHK(hipMemcpyAsync(&orbits, b->sorbits, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));   // also makes the host tables above safe to free
+  HIPCHK(hipStreamSynchronize(st));
   if (memo_on()) {   // every position bit in use in this chunk: corrects an under-estimate the VCFs were (or will be) remembered with
     if (b->posor_seen.empty()) b->posor_seen.assign((size_t)b->n_vcf, 0u);
     for (int v : vs) {
@@ -1334,6 +1285,7 @@ static int sort_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, u
   int npass = 1;
   while (4 + 8 * npass < 32 && (orbits >> (4 + 8 * npass)) != 0) ++npass;
   int cur = 0;
+  const SortCols src = {b->pos, b->ref, b->alt, b->qual, b->flags};
   {
     const bool last = npass == 1;
     launch_sort_first_scatter(b->d_segs, b->d_tile_seg, nseg, nst, src, b->n_bins, b->ext ? 1 : 0, b->shist, last ? s->pkey : b->sk[0],
@@ -1349,7 +1301,7 @@ static int sort_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, u
   if (b->ext) launch_sort_gather_alleles(b->d_segs, b->d_tile_seg, nst, perm, b->ref, b->alt, s->ref, s->alt, st);
   // --- 3. the normal path on the sorted copies (their ROC rows go into the caller's per-truth sums)
   launch_classify(classify_params(s), (int)s->L.spans.size(), st);
-  launch_finalize(finalize_params(s, global), nseg, st);
+  launch_finalize(finalize_params(s, b->last_global), nseg, st);
   // --- 4. results back under the original VCFs: ROC + scalar rows, class bits in input order
   launch_sort_copy_rows(b->d_segs, nseg, s->roc, s->scalars, b->roc, b->scalars, b->n_bins, st);
   launch_sort_scatter_tp(b->d_segs, b->d_tile_seg, nst, s->mask_tp, perm, b->mask_tp, st);
@@ -1369,28 +1321,170 @@ static int sort_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, u
   return QM_OK;
 }
 
-// ---- two-level bucket path (qmvt_dev.h): VCFs too large for 256 buckets of 8 192 records ----
-static bool bucket2_takes(const qm_batch* b, int64_t n) {
-  if (b->ext) return false;
-  if (g_penv.radix_only) return false;
-  if (g_penv.bucket2 == 0) return false;
-  if (join_hash_forced()) return false;
-  if (n > (int64_t)P2_MAX_HALVES << P2_INDEX_BITS) return false;   // (VCFs above 2^24 records: in runs of 2^24, level-1 segments of their own)
-  if (g_penv.bucket2 == 2) return n > 0;   // tests and tools/gpu_fuzz.py: every unsorted VCF takes the two levels
-  return !bucket_path_takes(b, n) && n >= HB_MIN_RECORDS;
+// --- one level: ONE scatter of each VCF's records on its top eight key bits into fixed-size bucket regions, the join per bucket.
+// *named: the VCFs whose buckets overflowed (nothing of the chunk was handed over); empty when the chunk is done -- or queued
+// (may_speculate: its results are handed over without a look at its flags, settle_pending looks at them behind the finish's last wait).
+static int onelevel_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, const std::vector<uint32_t>& posor, bool may_speculate,
+                          std::vector<int>* named) {
+  named->clear();
+  g_ftrace[0] = ftrace_now();
+  const int nseg = (int)vs.size();
+  VcfSegs T;
+  int rc = vcf_segs(b, vs, posor, &T);
+  if (rc != QM_OK) return rc;
+  const std::vector<SortSeg>& segs = T.segs;
+  int lb_all = 0, nbk_all = 1;
+  for (const SortSeg& g : segs) { lb_all = std::max(lb_all, (int)g.pad); nbk_all = std::max(nbk_all, (int)g.nbk); }
+  // the join: one bit per key of the bucket in LDS where a bucket's key range allows it (k_join_lean: two bits per position), the hashed
+  // tables of k_classify_hash otherwise (QM_JOIN=hash: always)
+  const bool direct = lb_all <= DJ_MAX_SHIFT && !g_penv.join_hash;
+  // allele-extended batches: two entry streams and two joins per bucket (k_join_lean for the single-base records, k_join_ext for the
+  // others), both of which need the bucket's key range to fit the bit maps; wider key ranges take the radix sort
+  const bool xs = b->ext;
+  if (xs && !direct) return radix_chunk(b, vs, st, posor, QM_PATH_RADIX);
+  const int out_stride = xs ? 2 * HB_BUCKETS : HB_BUCKETS;
+  if (xs) nbk_all = HB_BUCKETS;   // every row of a segment is written (the rows of the second stream follow at a fixed distance)
+  const int nbt = (int)T.nbt, nkt = (int)T.nkt;
+  rc = ensure_seg_arrays(b, nseg, nkt);
+  if (rc == QM_OK) rc = ensure_bucket_arrays(b, nseg, T.bk_ents, nbt, xs);
+  if (rc != QM_OK) return rc;
+  const std::vector<uint32_t> key = posor_of(vs, posor);
+  if (!owns(b, Path::OneLevel, vs, key)) {
+    b->tables = qm_batch::Tables();
+    std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local;
+    std::vector<VcfDesc> fake((size_t)nseg);
+    for (int i = 0; i < nseg; ++i) {
+      const SortSeg& g = segs[(size_t)i];
+      bk_tile_seg.insert(bk_tile_seg.end(), (size_t)((g.n + BK_TILE - 1) / BK_TILE), (int32_t)i);
+      fake[(size_t)i] = bucket_vcf(g.n, b->L.vcfs[(size_t)vs[(size_t)i]].truth, i * out_stride, xs ? out_stride : g.nbk);
+    }
+    ktile_maps(b, vs, ktile_seg, ktile_local);
+    HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // the host vectors die with this block
+    b->tables = qm_batch::Tables{Path::OneLevel, vs, key, nseg, T.nbt, T.nkt, vs};
+  }
+  const CursorRegion C = cursor_region(b, nseg);
+  BucketScatterParams S;
+  HashParams H;
+  bucket_params(b, nseg, xs, direct ? C.seg_hist : nullptr, &S, &H);
+  S.seg_maxd = C.seg_maxd;
+  if (xs) HIPCHK(hipMemsetAsync(b->bk_xcursor, 0, (size_t)nseg * HB_BUCKETS * HB_SUBS * 4, st));
+  H.zero = b->bk_cursor; H.n_zero = C.words;   // the scatter's cursors, flags, counts: cleared by the kernel that writes the rows
+  g_ftrace[1] = ftrace_now();
+  launch_bucket_rows(H, nseg, st);
+  H.zero = nullptr; H.n_zero = 0u;
+  // k_classify_hash issues instructions where the scatter waits for memory: a few segment ranges, the join of one on the second
+  // stream beside the scatter of the next, fill each other's gaps (- 7 %).  The bit-map join was bound by the latency of a
+  // workgroup's serial steps and wants every LDS slot of the chip: beside a scatter it only loses (3.06 ms in one piece
+  // against 3.11 - 3.22 in 2 - 8 ranges, same box)
+  int nbk_launch = nbk_all;
+  const int parts = nseg >= 8 && b->ev_sync[0] && !direct ? 4 : 1;
+  // The buckets above a VCF's highest position hold nothing, and a workgroup that finds its bucket empty has still held a slot of its
+  // CU for a memory round trip: 40 % of the grid on a 5 Mb genome, whose position BITS (all the optimistic pass hands over) bound the
+  // buckets in use only by 256 -- 0.09 of the step's 2.65 ms (same box).  The scatter notes the highest bucket it filled per segment
+  // (seg_maxd): the join's workgroups above it leave at once and k_finalize sums no row of theirs -- no round trip through the host.
+  const bool tight_nbk = direct && parts == 1;
+  if (tight_nbk) H.seg_maxd = C.seg_maxd;
+  hipStream_t aux = parts > 1 ? b->ctx->aux : st;
+  int i0 = 0;
+  for (int p = 0; p < parts; ++p) {
+    // ranges of about equal record counts
+    int i1 = p + 1 == parts ? nseg : i0;
+    if (p + 1 < parts) {
+      const int64_t want = (int64_t)nbt * (p + 1) / parts;
+      while (i1 < nseg && segs[(size_t)i1].bk_tile0 < want) ++i1;
+      i1 = std::max(i1, i0);
+    }
+    if (i1 > i0) {
+      const int t0 = segs[(size_t)i0].bk_tile0, t1 = i1 < nseg ? segs[(size_t)i1].bk_tile0 : nbt;
+      S.tile_base = t0;
+      launch_bucket_scatter(S, t1 - t0, st);
+      g_ftrace[2] = ftrace_now();
+      if (parts > 1) {
+        HIPCHK(hipEventRecord(b->ev_sync[p], st));
+        HIPCHK(hipStreamWaitEvent(aux, b->ev_sync[p], 0));
+      }
+      H.seg_base = i0;
+      if (tight_nbk) {   // a batch that ran before remembers the highest bucket of every VCF: nothing is launched above
+        bool have = memo_on() && !b->known_nbk.empty();
+        uint32_t m = 0;
+        if (have) for (int i = 0; i < nseg && have; ++i) { const uint32_t k = b->known_nbk[(size_t)vs[(size_t)i]]; have = k != 0u; m = std::max(m, k); }
+        if (have && !xs) nbk_launch = (int)std::min<uint32_t>(std::max(m, 1u), (uint32_t)nbk_all);   // (two streams: every bucket is launched, the rows of the second follow at a fixed distance)
+      }
+      if (direct) launch_join_lean(H, i1 - i0, lb_all, nbk_launch, aux);
+      else launch_classify_hash(H, i1 - i0, aux);
+      if (xs) launch_join_ext(H, i1 - i0, nbk_all, aux);
+    }
+    i0 = i1;
+  }
+  if (parts > 1) {
+    HIPCHK(hipEventRecord(b->ev_sync[qm_batch::MAX_CHUNKS + 1], aux));
+    HIPCHK(hipStreamWaitEvent(st, b->ev_sync[qm_batch::MAX_CHUNKS + 1], 0));
+  }
+  const bool mirrors = b->d_summary != nullptr && nseg <= b->n_vcf;   // (one segment per VCF on this path)
+  // No round trip through the host between the rows' k_finalize and the kernels that hand the chunk's results over: they are queued
+  // at once, k_sort_copy_rows looks at the chunk's "bad" word on the device, and qm_batch_finish reads the mirrors behind its last
+  // wait (settle_pending) -- 15-25 us per chunk of 2.5 ms.  Every chunk of a finish has mirror words of its own (b->pend_segs).
+  const bool speculate = may_speculate && mirrors && b->pend_segs + nseg <= b->n_vcf && g_penv.speculate;
+  const int moff = speculate ? b->pend_segs : 0;
+  {
+    FinalizeParams F = bucket_rows_finalize(b, S.seg_hist);
+    if (tight_nbk) F.row_cap = C.seg_maxd;   // (the rows above were not written by this run)
+    if (mirrors) { F.host_flags = b->d_summary + 16 + 2 * b->n_vcf + moff; F.host_aux = b->d_summary + 16 + 3 * b->n_vcf + moff; }   // (a place of their own: the run's flags may still be unread)
+    if (speculate) { F.chunk_bad = C.chunk_bad; F.row_cap_limit = (uint32_t)nbk_launch; }
+    launch_finalize(F, nseg, st);
+  }
+  b->path_stats[QM_PATH_BUCKET_CHUNKS] += 1;
+  if (speculate) {
+    rc = hand_over(b, b->d_segs, nseg, nullptr, nkt, C.chunk_bad, -1, st);
+    if (rc != QM_OK) return rc;
+    b->pend.push_back(qm_batch::Pending{vs, moff, nbk_launch, tight_nbk, direct});
+    b->pend_segs += nseg;
+    return QM_OK;
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> hfl((size_t)nseg), hmd((size_t)nseg, 0u);
+  if (!mirrors) {
+    HIPCHK(hipMemcpyAsync(hfl.data(), b->bk_vflags, 4 * hfl.size(), hipMemcpyDeviceToHost, st));
+    if (tight_nbk) HIPCHK(hipMemcpyAsync(hmd.data(), C.seg_maxd, 4 * hmd.size(), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (mirrors) {   // k_finalize's host-mapped mirrors: the flags and (row_cap) the highest buckets, no copy
+    memcpy(hfl.data(), b->h_summary + 16 + 2 * b->n_vcf, 4 * hfl.size());
+    if (tight_nbk) memcpy(hmd.data(), b->h_summary + 16 + 3 * b->n_vcf, 4 * hmd.size());
+  }
+  if (tight_nbk && memo_on()) {
+    if (b->known_nbk.empty()) b->known_nbk.assign((size_t)b->n_vcf, 0u);
+    for (int i = 0; i < nseg; ++i) b->known_nbk[(size_t)vs[(size_t)i]] = std::max(hmd[(size_t)i], 1u);
+  }
+  rc = bucket_verdict(b, hfl.data(), tight_nbk ? hmd.data() : nullptr, (uint32_t)nbk_launch, vs, named);
+  if (rc != QM_OK || !named->empty()) return rc;
+  return hand_over(b, b->d_segs, nseg, nullptr, nkt, nullptr, direct ? QM_PATH_DIRECT : QM_PATH_HASHED, st);
 }
 
-// *taken = false: the chunk is not for this path after all (a partition too dense for its buckets, a bucket overflowed): the
-// caller sends it through the radix sort; nothing the path wrote is kept in that case (the sort rewrites masks, counts and rows)
-// bad (when the chunk is not taken): the VCF with a partition too dense for its buckets, or the VCFs whose buckets overflowed
-static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, uint64_t* global, bool* taken, std::vector<int>* bad = nullptr) {
-  if (bad) bad->clear();
-  *taken = false;
+// The flags of a bucket chunk with one segment per (VCF, partition), copied back; the verdict; the hand-over of a chunk that fitted
+static int look_and_hand_over(qm_batch* b, int nv, int stat, hipStream_t st, std::vector<int>* named) {
+  HIPCHK(hipGetLastError());
+  const int nseg = b->tables.nseg;
+  std::vector<uint32_t> hfl((size_t)nseg);
+  HIPCHK(hipMemcpyAsync(hfl.data(), b->bk_vflags, 4 * hfl.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int rc = bucket_verdict(b, hfl.data(), nullptr, 0u, b->tables.seg_vcf, named);
+  if (rc != QM_OK || !named->empty()) return rc;
+  return hand_over(b, b->d_vsegs, nv, b->d_vparts, b->tables.nkt, nullptr, stat, st);
+}
+
+// --- two levels (qmvt_dev.h): VCFs too large for 256 buckets of 8 192 records.  k_part_hist + k_part_scatter deal the records to
+// partitions of 2^27 keys in exactly sized regions; every (VCF, partition in use) is then a segment of the one-level scatter, read from
+// those entries.  *named: a VCF with a partition too dense for its buckets (named before anything is scattered), or the VCFs whose
+// buckets overflowed.
+static int two_level_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, std::vector<int>* named) {
+  named->clear();
   const int nv = (int)vs.size();
-  std::vector<int32_t> tids((size_t)nv);
-  for (int i = 0; i < nv; ++i) tids[(size_t)i] = b->L.vcfs[(size_t)vs[(size_t)i]].truth;
-  int rc = ensure_bucket_rows(b, nv);
-  if (rc != QM_OK) return rc;
   // --- level 1: descriptors, tile map, counting pass.  A level-1 entry has 24 index bits: a VCF above 2^24 records is dealt out in
   //     HALVES -- runs of 2^24 records, each a level-1 segment of its own (own counts, own regions, indices relative to its first
   //     record) -- whose regions lie one behind the other inside every partition of the VCF, so that a partition still is ONE run of
@@ -1400,7 +1494,7 @@ static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st
   std::vector<int> half_vcf, vcf_half0((size_t)nv + 1, 0);   // VCF (index into vs) of every half; first half of every VCF
   std::vector<int32_t> ptile;
   int64_t ent_total = 0, nt1 = 0;
-  const bool build1 = b->last2_vs != vs;   // the level-1 tables depend on the chunk's VCFs only
+  const bool same_vs = b->tables.path == Path::TwoLevel && b->tables.vcfs == vs;   // the level-1 tables depend on the chunk's VCFs only
   bool any_halves = false;
   for (int i = 0; i < nv; ++i) {
     const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
@@ -1411,7 +1505,7 @@ static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st
       PartSeg g;
       g.src_off = d.off + (int64_t)h * HALF; g.n = std::min<int64_t>(HALF, d.n - (int64_t)h * HALF); g.ent_off = ent_total; g.tile0 = (int32_t)nt1; g.main_vcf = vs[(size_t)i];
       const int64_t t = (g.n + BK_TILE - 1) / BK_TILE;
-      if (build1) ptile.insert(ptile.end(), (size_t)t, (int32_t)ps.size());
+      if (!same_vs) ptile.insert(ptile.end(), (size_t)t, (int32_t)ps.size());
       nt1 += t;
       ps.push_back(g);
       half_vcf.push_back(i);
@@ -1422,7 +1516,7 @@ static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st
   const int nh_all = (int)ps.size();
   if (nt1 > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
   constexpr int NC = P2_PARTS * P2_SUBS;
-  if (rc == QM_OK) rc = regrow(&b->p_segs, &b->cap_p_segs, (int64_t)nh_all, &b->dev_bytes);
+  int rc = regrow(&b->p_segs, &b->cap_p_segs, (int64_t)nh_all, &b->dev_bytes);
   if (rc == QM_OK) rc = regrow(&b->p_tile_seg, &b->cap_p_tiles, nt1, &b->dev_bytes);
   if (rc == QM_OK) rc = regrow(&b->p_cnt, &b->cap_p_cnt, (int64_t)nh_all * NC, &b->dev_bytes);
   if (rc == QM_OK) rc = regrow(&b->p_off, &b->cap_p_off, (int64_t)nh_all * (NC + 1), &b->dev_bytes);
@@ -1430,9 +1524,7 @@ static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st
   if (rc == QM_OK) rc = regrow(&b->p_flags, &b->cap_p_flags, (int64_t)nh_all, &b->dev_bytes);
   if (rc == QM_OK) rc = regrow(&b->p_ent, &b->cap_p_ent, ent_total + 64, &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool same_vs = b->last2_vs == vs;
   if (!same_vs) {
-    b->last2_cnt.clear();
     HIPCHK(hipMemcpyAsync(b->p_segs, ps.data(), sizeof(PartSeg) * ps.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->p_tile_seg, ptile.data(), 4 * ptile.size(), hipMemcpyHostToDevice, st));
   }
@@ -1452,156 +1544,101 @@ static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st
     if (pfl[(size_t)hh] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", vs[(size_t)half_vcf[(size_t)hh]]);
   // --- exact regions; one level-2 segment per (VCF, partition in use).  The same VCFs with the same counts as last time (a batch
   //     run again): every table below is still on the device
-  const bool same_cnt = same_vs && b->last2_cnt == cnt && !b->last2_cnt.empty();
-  if (!same_cnt) {
-  std::vector<uint32_t> off((size_t)nh_all * (NC + 1));
-  std::vector<uint32_t> half_off;   // [segment][4]: where the entries of the VCF's 2nd, 3rd, 4th half begin inside the segment's run
-  std::vector<SortSeg> segs;
-  std::vector<VcfDesc> fake;
-  std::vector<SortSeg> vsegs((size_t)nv);
-  std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local, vparts((size_t)nv);
-  int64_t bk_ents = 0, nbt = 0, nkt = 0;
-  b->last2_vs.clear();
-  for (int i = 0; i < nv; ++i) {
-    const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
-    uint32_t run = 0;
-    const int seg0 = (int)segs.size();
-    const int h0 = vcf_half0[(size_t)i], h1 = vcf_half0[(size_t)i + 1];
-    for (int p = 0; p < P2_PARTS; ++p) {
-      run = (run + 1u) & ~1u;
-      const uint32_t start = run;
-      uint32_t hb[4] = {0u, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-      for (int hh = h0; hh < h1; ++hh) {   // the halves' regions of the partition one behind the other
-        hb[hh - h0] = run - start;
-        for (int k = 0; k < P2_SUBS; ++k) { off[(size_t)hh * (NC + 1) + (size_t)p * P2_SUBS + k] = run; run += cnt[(size_t)hh * NC + (size_t)p * P2_SUBS + k]; }
+  if (!(same_vs && b->tables.key == cnt)) {
+    b->tables = qm_batch::Tables();
+    std::vector<uint32_t> off((size_t)nh_all * (NC + 1));
+    std::vector<uint32_t> half_off;   // [segment][4]: where the entries of the VCF's 2nd, 3rd, 4th half begin inside the segment's run
+    std::vector<SortSeg> segs;
+    std::vector<VcfDesc> fake;
+    std::vector<SortSeg> vsegs((size_t)nv);
+    std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local, vparts((size_t)nv);
+    std::vector<int> seg_vcf;
+    int64_t bk_ents = 0, nbt = 0;
+    for (int i = 0; i < nv; ++i) {
+      const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
+      uint32_t run = 0;
+      const int seg0 = (int)segs.size();
+      const int h0 = vcf_half0[(size_t)i], h1 = vcf_half0[(size_t)i + 1];
+      for (int p = 0; p < P2_PARTS; ++p) {
+        run = (run + 1u) & ~1u;
+        const uint32_t start = run;
+        uint32_t hb[4] = {0u, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+        for (int hh = h0; hh < h1; ++hh) {   // the halves' regions of the partition one behind the other
+          hb[hh - h0] = run - start;
+          for (int k = 0; k < P2_SUBS; ++k) { off[(size_t)hh * (NC + 1) + (size_t)p * P2_SUBS + k] = run; run += cnt[(size_t)hh * NC + (size_t)p * P2_SUBS + k]; }
+        }
+        const int64_t np = (int64_t)run - start;
+        if (np == 0) continue;
+        half_off.insert(half_off.end(), hb, hb + 4);
+        // all 256 buckets of a partition are in use: more than 6 656 records per bucket on average will not fit 8 x 1 024
+        if (np > (int64_t)HB_BUCKETS * HB_MAX_RECORDS * 13 / 16) { named->push_back(vs[(size_t)i]); return QM_OK; }
+        SortSeg g;
+        memset(&g, 0, sizeof g);
+        g.src_off = d.off; g.koff = ps[(size_t)h0].ent_off + start; g.n = np;   // (the halves of a VCF share its level-1 region)
+        g.main_vcf = vs[(size_t)i]; g.sub_vcf = i; g.main_tile0 = d.tile0;
+        g.pad = DJ_MAX_SHIFT; g.nbk = HB_BUCKETS; g.key_base = (uint32_t)p << P2_SHIFT;
+        int64_t want = np / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;
+        while (cap2 < want && cap2 < HB_SUB_MAX) cap2 *= 2;
+        g.bk_cap = (int32_t)cap2; g.bk_off = bk_ents; g.bk_tile0 = (int32_t)nbt;
+        bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
+        const int64_t t = (np + BK_TILE - 1) / BK_TILE;
+        bk_tile_seg.insert(bk_tile_seg.end(), (size_t)t, (int32_t)segs.size());
+        nbt += t;
+        // the buckets of a PARTITION as the "spans" of a VCF for k_finalize: one workgroup per partition (one per VCF summed
+        // 1 536 rows by itself); k_sort_copy_rows adds a VCF's partitions up when the rows go home
+        fake.push_back(bucket_vcf(np, d.truth, (int32_t)segs.size() * HB_BUCKETS, HB_BUCKETS));
+        segs.push_back(g);
+        seg_vcf.push_back(vs[(size_t)i]);
       }
-      const int64_t np = (int64_t)run - start;
-      if (np == 0) continue;
-      half_off.insert(half_off.end(), hb, hb + 4);
-      if (np > (int64_t)HB_BUCKETS * HB_MAX_RECORDS * 13 / 16) { if (bad) bad->push_back(vs[(size_t)i]); return QM_OK; }   // all 256 buckets of a partition are in use: more than 6 656 records per bucket on average will not fit 8 x 1 024 (not for this path: *taken stays false)
-      SortSeg g;
-      memset(&g, 0, sizeof g);
-      g.src_off = d.off; g.koff = ps[(size_t)h0].ent_off + start; g.n = np;   // (the halves of a VCF share its level-1 region)
-      g.main_vcf = vs[(size_t)i]; g.sub_vcf = i; g.main_tile0 = d.tile0;
-      g.pad = DJ_MAX_SHIFT; g.nbk = HB_BUCKETS; g.key_base = (uint32_t)p << P2_SHIFT;
-      int64_t want = np / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;
-      while (cap2 < want && cap2 < HB_SUB_MAX) cap2 *= 2;
-      g.bk_cap = (int32_t)cap2; g.bk_off = bk_ents; g.bk_tile0 = (int32_t)nbt;
-      bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
-      const int64_t t = (np + BK_TILE - 1) / BK_TILE;
-      bk_tile_seg.insert(bk_tile_seg.end(), (size_t)t, (int32_t)segs.size());
-      nbt += t;
-      // the buckets of a PARTITION as the "spans" of a VCF for k_finalize: one workgroup per partition (one per VCF summed
-      // 1 536 rows by itself); k_sort_copy_rows adds a VCF's partitions up when the rows go home
-      VcfDesc f = VcfDesc();
-      f.off = 0; f.n = np; f.truth = tids[(size_t)i]; f.tile0 = 0; f.ntiles = 0; f.span0 = (int32_t)segs.size() * HB_BUCKETS; f.nspans = HB_BUCKETS; f.pad = 0;
-      fake.push_back(f);
-      segs.push_back(g);
+      for (int hh = h0; hh < h1; ++hh) off[(size_t)hh * (NC + 1) + NC] = run;
+      SortSeg& vg = vsegs[(size_t)i];
+      memset(&vg, 0, sizeof vg);
+      vg.src_off = d.off; vg.n = d.n; vg.main_vcf = vs[(size_t)i]; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
+      vparts[(size_t)i] = (int32_t)segs.size() - seg0;
     }
-    for (int hh = h0; hh < h1; ++hh) off[(size_t)hh * (NC + 1) + NC] = run;
-    SortSeg& vg = vsegs[(size_t)i];
-    memset(&vg, 0, sizeof vg);
-    vg.src_off = d.off; vg.n = d.n; vg.main_vcf = vs[(size_t)i]; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
-    vparts[(size_t)i] = (int32_t)segs.size() - seg0;
-    const size_t k0 = ktile_seg.size();
-    ktile_seg.insert(ktile_seg.end(), (size_t)d.ntiles, (int32_t)i);
-    ktile_local.resize(k0 + (size_t)d.ntiles);
-    for (int t = 0; t < d.ntiles; ++t) ktile_local[k0 + (size_t)t] = t;
-    nkt += d.ntiles;
-  }
-  const int nseg = (int)segs.size();
-  if (nbt > INT32_MAX || nkt > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
-  // --- the arrays of the one-level path, sized for the level-2 segments (its cached tables are gone after this)
-  b->last_segs.clear(); b->bk_tiles_valid = false; b->bk_fake_valid = false; b->lastx_vs.clear();
-  int64_t cap;
-  if (rc == QM_OK) { cap = b->cap_segs; rc = regrow(&b->d_segs, &cap, (int64_t)nseg, &b->dev_bytes); b->cap_segs = (int)cap; }
-  if (rc == QM_OK) rc = regrow(&b->d_vsegs, &b->cap_vsegs, (int64_t)nv, &b->dev_bytes);
-  if (rc == QM_OK) {
-    cap = b->cap_ktiles; rc = regrow(&b->d_ktile_seg, &cap, nkt, &b->dev_bytes);
-    if (rc == QM_OK) { cap = b->cap_ktiles; rc = regrow(&b->d_ktile_local, &cap, nkt, &b->dev_bytes); }
-    if (rc == QM_OK) b->cap_ktiles = std::max(b->cap_ktiles, (int)nkt);
-  }
-  {
-    const int64_t rows = (int64_t)nseg * HB_BUCKETS;
-    int64_t c1 = b->cap_bk_rows * SPAN_HIST_WORDS, c2 = b->cap_bk_rows * 8;
-    if (rc == QM_OK) rc = regrow(&b->bk_hist, &c1, rows * SPAN_HIST_WORDS, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_scal, &c2, rows * 8, &b->dev_bytes);
-    if (rc == QM_OK) b->cap_bk_rows = std::max(b->cap_bk_rows, rows);
-    if (rc == QM_OK) rc = regrow(&b->d_bk_vcfs, &b->cap_bk_vcfs, (int64_t)nseg, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_ent, &b->cap_bk_ent, bk_ents, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_rows, &b->cap_bk_rowdesc, rows, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_cursor, &b->cap_bk_cursor, rows * HB_SUBS + nseg + 32 + 16 * 65 + (int64_t)nseg * (SEG_HIST_WORDS + 1), &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->d_bk_tile_seg, &b->cap_bk_tiles, nbt, &b->dev_bytes);
+    ktile_maps(b, vs, ktile_seg, ktile_local);
+    const int nseg = (int)segs.size();
+    const int64_t nkt = (int64_t)ktile_seg.size();
+    if (nbt > INT32_MAX || nkt > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
+    rc = ensure_seg_arrays(b, nseg, nkt);
+    if (rc == QM_OK) rc = regrow(&b->d_vsegs, &b->cap_vsegs, (int64_t)nv, &b->dev_bytes);
     if (rc == QM_OK) rc = regrow(&b->d_vparts, &b->cap_vparts, (int64_t)nv, &b->dev_bytes);
     if (rc == QM_OK) rc = regrow(&b->p_half, &b->cap_p_half, (int64_t)nseg * 4, &b->dev_bytes);
-    if (rc == QM_OK) rc = ensure_bucket_rows(b, nseg);
+    if (rc == QM_OK) rc = ensure_bucket_arrays(b, nseg, bk_ents, nbt, false);
+    if (rc != QM_OK) return rc;
+    HIPCHK(hipMemcpyAsync(b->p_half, half_off.data(), 4 * half_off.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->p_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_vsegs, vsegs.data(), sizeof(SortSeg) * vsegs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_vparts, vparts.data(), 4 * vparts.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // the host tables die with this block
+    b->tables = qm_batch::Tables{Path::TwoLevel, vs, cnt, nseg, nbt, nkt, seg_vcf};
   }
-  if (rc != QM_OK) return rc;
-  b->last2_halves = any_halves;
-  HIPCHK(hipMemcpyAsync(b->p_half, half_off.data(), 4 * half_off.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->p_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_vsegs, vsegs.data(), sizeof(SortSeg) * vsegs.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_vparts, vparts.data(), 4 * vparts.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));   // the host tables die with this block
-  b->last2_vs = vs; b->last2_cnt = cnt; b->last2_nseg = nseg; b->last2_nbt = nbt; b->last2_nkt = nkt;
-  b->last2_seg_vcf.resize(segs.size());
-  for (size_t i = 0; i < segs.size(); ++i) b->last2_seg_vcf[i] = segs[i].main_vcf;
-  }   // !same_cnt
-  const int nseg = b->last2_nseg;
-  const int64_t nbt = b->last2_nbt, nkt = b->last2_nkt;
-  const size_t nhist0 = (size_t)nseg * HB_BUCKETS * HB_SUBS + (size_t)nseg + 32 + 16 * 65;   // the scatter's per-segment histograms lie behind the cursors, flags and phase clocks
-  const size_t ncur = (nhist0 + (size_t)nseg * (SEG_HIST_WORDS + 1)) * 4;   // (+ 1: seg_maxd behind the histograms)
-  HIPCHK(hipMemsetAsync(b->bk_cursor, 0, ncur, st));
+  const int nseg = b->tables.nseg;
+  const CursorRegion C = cursor_region(b, nseg);
+  HIPCHK(hipMemsetAsync(b->bk_cursor, 0, (size_t)C.words * 4, st));
   // --- level 1 scatter, then the one-level path over the partitions: rows, scatter from the level-1 entries, join, rows summed per VCF
   launch_part_scatter(PP, (int)nt1, st);
   BucketScatterParams S;
-  S.segs = b->d_segs; S.tile_seg = b->d_bk_tile_seg; S.pos = b->pos; S.ref = b->ref; S.alt = b->alt; S.qual = b->qual; S.flags = b->flags;
-  S.cursor = b->bk_cursor; S.ent = b->bk_ent; S.mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); S.mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp);
-  S.n_seg = nseg; S.n_bins = b->n_bins; S.tile_base = 0; S.l1_ent = b->p_ent; S.xent = nullptr; S.xcursor = nullptr; S.ext = 0; S.pairs = 0;
-  uint32_t* const seg_hist = b->bk_cursor + nhist0;
-  // (no look at the highest bucket here: every partition but a VCF's last fills its 256 buckets, and the look costs the scatter more than
-  // the few empty workgroups cost the join -- 2.81 against 2.71 ms per 16 x 10 M records)
-  uint32_t* const seg_maxd = nullptr;   // (the look at the highest filled bucket was measured on this path and lost: 2.08 against 2.02 ms per 64 x 2 M)
-  S.seg_hist = seg_hist; S.seg_maxd = seg_maxd; S.l1_half = b->last2_halves ? b->p_half : nullptr;
   HashParams H;
-  H.segs = b->d_segs; H.rows = b->bk_rows; H.rows_out = b->bk_rows; H.ent = b->bk_ent; H.cursor = b->bk_cursor; H.truths = b->ctx->d_truths; H.vcfs = b->d_vcfs;
-  H.mask_tp = b->mask_tp; H.row_hist = b->bk_hist; H.row_scal = b->bk_scal; H.n_seg = nseg; H.n_bins = b->n_bins; H.seg_base = 0;
-  H.xrows = nullptr; H.xent = nullptr; H.xcursor = nullptr; H.out_stride = HB_BUCKETS; H.ext = 0; H.scatter_hist = seg_hist ? 1 : 0; H.seg_maxd = seg_maxd;
+  bucket_params(b, nseg, false, C.seg_hist, &S, &H);
+  S.l1_ent = b->p_ent; S.l1_half = any_halves ? b->p_half : nullptr;
+  // (no look at the highest filled bucket, seg_maxd: every partition but a VCF's last fills its 256 buckets, and the look costs the
+  // scatter more than the few empty workgroups cost the join -- 2.81 against 2.71 ms per 16 x 10 M records)
   launch_bucket_rows(H, nseg, st);
-  launch_bucket_scatter(S, (int)nbt, st);
+  launch_bucket_scatter(S, (int)b->tables.nbt, st);
   launch_join_lean(H, nseg, DJ_MAX_SHIFT, HB_BUCKETS, st);
-  {
-    FinalizeParams F = bucket_rows_finalize(b, seg_hist);
-    F.row_cap = seg_maxd;
-    launch_finalize(F, nseg, st);
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<uint32_t> hfl((size_t)nseg);
-  HIPCHK(hipMemcpyAsync(hfl.data(), b->bk_vflags, 4 * hfl.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  launch_finalize(bucket_rows_finalize(b, C.seg_hist), nseg, st);
   b->path_stats[QM_PATH_BUCKET_CHUNKS] += 1;
-  bool overflow = false;
-  for (int i = 0; i < nseg; ++i)
-    if (hfl[(size_t)i] & SPANF_OVERFLOW) {   // a bucket did not fit: nothing of the chunk is handed over
-      overflow = true;
-      if (bad && (size_t)i < b->last2_seg_vcf.size() && (bad->empty() || bad->back() != b->last2_seg_vcf[(size_t)i])) bad->push_back(b->last2_seg_vcf[(size_t)i]);
-    }
-  if (overflow) { b->path_stats[QM_PATH_OVERFLOW_CHUNKS] += 1; b->last2_vs.clear(); return QM_OK; }
-  launch_sort_copy_rows(b->d_vsegs, nv, b->bk_roc, b->bk_rscal, b->roc, b->scalars, b->n_bins, st, global, b->d_vcfs, b->d_vparts);
-  launch_tile_counts(b->d_vsegs, b->d_ktile_seg, b->d_ktile_local, (int)nkt, b->mask_pass, b->mask_tp, b->tile_tp, b->tile_fp, st);
-  HIPCHK(hipGetLastError());
-  b->path_stats[QM_PATH_DIRECT2] += nv;
-  *taken = true;
-  return QM_OK;
+  return look_and_hand_over(b, nv, QM_PATH_DIRECT2, st, named);
 }
 
-// ---- VCFs too large or too wide for 256 buckets (allele-extended ones; default-mode ones on references of 8.4 ... 16.8 M positions):
-//      partitions of the key space, read from the columns ----
+// --- partitions of the key space, read from the columns: VCFs too large or too wide for 256 buckets (allele-extended ones;
+// default-mode ones on references of 8.4 ... 16.8 M positions), and (wide) the wide buckets.
 // The one-level path needs <= 8 192 records and <= 2^19 keys per bucket: configs[4]'s VCFs (2 M records on a 10 Mb genome) have
 // neither.  The two-level path's first scatter packs level-1 entries that have no room for allele codes, so for these batches
 // every PARTITION of 2^27 keys (256 buckets of 2^19) is a segment of the one-level scatter that reads ALL of its VCF's columns
@@ -1609,333 +1646,196 @@ static int bucket2_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st
 // instantiation of the scatter: the first one's tiles fill both), so a 10 Mb genome costs ONE read of the columns, four partitions
 // two; nothing else is new -- bucket rows, the two joins, the rows per segment and their sum per VCF are the one-level and
 // two-level paths'.
-constexpr int PX_MAX_PARTS = 4;
-static int ext_parts_of(uint32_t posor, int pshift = P2_SHIFT) { return (int)((((uint64_t)posor << 4) | 15u) >> pshift) + 1; }
-// WIDE buckets (round 6): 2^17 positions and up to 32 768 records per bucket, 256 of them per partition of 2^29 keys.  A shuffled
+// WIDE buckets: 2^17 positions and up to 32 768 records per bucket, 256 of them per partition of 2^29 keys.  A shuffled
 // default-mode VCF of 1.3 ... 67 M records on a reference of up to 67 M positions -- configs[3]'s 10 M records on 50 Mb -- is then
 // TWO partitions = ONE pass of the 512-digit scatter over its columns (pieces of 64 bytes and more: whole sectors) and
 // k_join_lean<.., BIG> per bucket, where the two-level path moves every record twice.
-constexpr int PW_SHIFT = DJ_BIG_SHIFT + 8;   // 29
-static bool join_hash_forced();
-static bool bucketw_takes(const qm_batch* b, int v, int64_t n, uint32_t posor) {
-  if (b->ext || g_penv.radix_only || join_hash_forced() || g_penv.bucketx == 0) return false;
-  if (n > ((int64_t)1 << 26) || ext_parts_of(posor, PW_SHIFT) > 2) return false;    // (26 index bits of an entry; wider references: two levels)
-  if (g_penv.bucketx == 3) return n >= g_penv.bucket_min;                          // 3: every default-mode unsorted VCF that fits (tests, fuzz)
-  if (n < HB_MIN_RECORDS || ext_parts_of(posor) < 3) return false;                 // narrower references have cheaper paths
-  const int64_t kor = ((int64_t)posor << 4) | 15;
-  const int64_t buckets = (kor >> DJ_BIG_SHIFT) + 1;
-  const int64_t truth = b->ctx->truths[(size_t)b->L.vcfs[(size_t)v].truth].n;
-  // not fuller than eight sub-regions of 4 096 take; a bucket stages 4 096 truth keys (three quarters of that on average: the rest
-  // is room for an uneven truth set)
-  if (n > buckets * (4 * HB_MAX_RECORDS * 13 / 16) || truth > buckets * (4 * DJ_TRUTH_MAX * 3 / 4)) return false;
-  if (!bucket_path_takes(b, n)) return true;   // (above the one-level path's 1.31 M records.  Measured on 50 Mb, 1.6e8 records per step: 2 M-record VCFs 4.3e10 /s against the two levels' 2.8e10, 5 M 6.7e10 against 3.6e10)
-  // Up to 1.31 M records the one-level path takes a VCF of such a reference with the hashed join (7.5e10 /s where it fits, the
-  // wide buckets 3.9e10: their workgroups have a fixed cost and few records each) -- but a one-level bucket is 2^18+ positions
-  // here and the hashed join stages 1 024 truth keys: a denser truth set flags the chunk and the radix sort redoes it
-  // (1.3-1.7e10 /s; wide buckets: 2.7-3.4e10).
-  int msb = 31;
-  while (msb > 0 && !((kor >> msb) & 1)) --msb;
-  const int64_t one_level_buckets = (kor >> std::max(4, msb - 7)) + 1;
-  return truth > one_level_buckets * (HB_TRUTH_SLOTS / 2 * 5 / 8);
-}
-static bool bucketx_takes(const qm_batch* b, int64_t n, uint32_t posor) {
-  if (b->ext && g_penv.bucket_ext == 0) return false;
-  if (g_penv.radix_only) return false;
-  if (join_hash_forced()) return false;
-  if (n < HB_MIN_RECORDS || n > ((int64_t)1 << (b->ext ? HB_INDEX_BITS : 26))) return false;   // (the second stream's entries hold 21 index bits, the first stream's 26)
-  const int parts = ext_parts_of(posor);
-  if (parts > PX_MAX_PARTS) return false;
-  if (g_penv.bucketx == 0) return false;
-  if (g_penv.bucketx == 2) return true;   // 2: every unsorted VCF that fits (tests, fuzz)
-  if (b->ext) return parts > 1 || !bucket_path_takes(b, n);
-  // default mode: a reference of 8.4 ... 16.8 M positions is ONE pair of partitions = one pass of the 512-digit scatter and the
-  // bit-map join, where the one-level path would need the hashed join (bucket key ranges of 2^20) and larger VCFs two levels
-  // (more partitions per pass were tried in round 6 -- eight, a 2 048-digit scatter -- and lost to the two levels by 2.6x: the
-  // pieces a tile leaves per bucket fall below an L2 line and are evicted half written, profiles/r06_pmc_scatter2048_not_kept.json)
-  return parts == 2;
-}
-
-// bad (when the chunk is not taken): the VCFs whose buckets overflowed -- the others would have fitted among themselves
-static int bucketx_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, uint64_t* global, const std::vector<uint32_t>& posor, bool* taken, bool wide = false,
-                         std::vector<int>* bad = nullptr) {
-  *taken = false;
-  if (bad) bad->clear();
+// *named: the VCFs whose buckets overflowed.
+static int partitions_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, const std::vector<uint32_t>& posor, bool wide,
+                            std::vector<int>* named) {
+  named->clear();
   const int nv = (int)vs.size();
+  const Path path = wide ? Path::Wide : Path::Partitions;
   const int pshift = wide ? PW_SHIFT : P2_SHIFT, bshift = wide ? DJ_BIG_SHIFT : DJ_MAX_SHIFT;
   const int64_t sub_max = wide ? 4 * HB_SUB_MAX : HB_SUB_MAX;
-  std::vector<uint32_t> por((size_t)nv);
-  for (int i = 0; i < nv; ++i) por[(size_t)i] = posor[(size_t)vs[(size_t)i]];
-  const bool same = !b->lastx_vs.empty() && b->lastx_vs == vs && b->lastx_por == por && b->lastx_wide == wide;   // the tables of this chunk are still on the device
-  int nseg = b->lastx_nseg;
-  int64_t nbt = b->lastx_nbt, nkt = b->lastx_nkt;
   const bool xs = b->ext;                                  // two entry streams (allele-extended batches)
   const int out_stride = xs ? 2 * HB_BUCKETS : HB_BUCKETS;
   constexpr int G = 2;                                     // partitions per pass over the columns
-  if (!same) {
-  nbt = 0; nkt = 0;
-  std::vector<SortSeg> segs, vsegs((size_t)nv);
-  std::vector<VcfDesc> fake;
-  std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local, vparts((size_t)nv);
-  int64_t bk_ents = 0;
-  for (int i = 0; i < nv; ++i) {
-    const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
-    const uint32_t kor = (posor[(size_t)vs[(size_t)i]] << 4) | 15u;
-    const int parts = ext_parts_of(posor[(size_t)vs[(size_t)i]], pshift);
-    const int seg0 = (int)segs.size();
-    for (int p = 0; p < parts; ++p) {
-      SortSeg g;
-      memset(&g, 0, sizeof g);
-      g.src_off = d.off; g.n = d.n; g.main_vcf = vs[(size_t)i]; g.sub_vcf = i; g.main_tile0 = d.tile0;
-      g.pad = bshift; g.key_base = (uint32_t)p << pshift;
-      // two neighbouring partitions share ONE pass over the columns: the tiles belong to the first of the pair, whose digits (512
-      // of them) reach into the second's cursors, regions and rows (same capacity, laid out one behind the other)
-      const int gfirst = p / G * G, gsize = std::min(G, parts - gfirst);
-      const bool lead = p == gfirst && gsize > 1, follow = p != gfirst;
-      const bool pair_last = gfirst + gsize == parts;
-      g.part = (pair_last ? 2 : 1) | (lead ? 4 | (gsize << 4) : 0);
-      g.nbk = p + 1 == parts ? std::min<int>(HB_BUCKETS, (int)((kor - g.key_base) >> bshift) + 1) : HB_BUCKETS;
-      int64_t want = d.n / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;   // (how the records spread over the partitions is not known: room as for all of them)
-      while (cap2 < want && cap2 < sub_max) cap2 *= 2;
-      g.bk_cap = (int32_t)cap2; g.bk_off = bk_ents; g.bk_tile0 = (int32_t)nbt;
-      bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
-      const int64_t t = follow ? 0 : (d.n + BK_TILE - 1) / BK_TILE;   // (the second of a pair has no tiles of its own)
-      bk_tile_seg.insert(bk_tile_seg.end(), (size_t)t, (int32_t)segs.size());
-      nbt += t;
-      VcfDesc f = VcfDesc();   // the two streams' rows of a partition as the "spans" of a VCF for k_finalize
-      f.off = 0; f.n = d.n; f.truth = d.truth; f.tile0 = 0; f.ntiles = 0; f.span0 = (int32_t)segs.size() * out_stride; f.nspans = out_stride; f.pad = 0;
-      fake.push_back(f);
-      segs.push_back(g);
+  const std::vector<uint32_t> key = posor_of(vs, posor);
+  if (!owns(b, path, vs, key)) {
+    b->tables = qm_batch::Tables();
+    int64_t nbt = 0;
+    std::vector<SortSeg> segs, vsegs((size_t)nv);
+    std::vector<VcfDesc> fake;
+    std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local, vparts((size_t)nv);
+    std::vector<int> seg_vcf;
+    int64_t bk_ents = 0;
+    for (int i = 0; i < nv; ++i) {
+      const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
+      const uint32_t kor = (key[(size_t)i] << 4) | 15u;
+      const int parts = parts_of(key[(size_t)i], pshift);
+      const int seg0 = (int)segs.size();
+      for (int p = 0; p < parts; ++p) {
+        SortSeg g;
+        memset(&g, 0, sizeof g);
+        g.src_off = d.off; g.n = d.n; g.main_vcf = vs[(size_t)i]; g.sub_vcf = i; g.main_tile0 = d.tile0;
+        g.pad = bshift; g.key_base = (uint32_t)p << pshift;
+        // two neighbouring partitions share ONE pass over the columns: the tiles belong to the first of the pair, whose digits (512
+        // of them) reach into the second's cursors, regions and rows (same capacity, laid out one behind the other)
+        const int gfirst = p / G * G, gsize = std::min(G, parts - gfirst);
+        const bool lead = p == gfirst && gsize > 1, follow = p != gfirst;
+        const bool pair_last = gfirst + gsize == parts;
+        g.part = (pair_last ? 2 : 1) | (lead ? 4 | (gsize << 4) : 0);
+        g.nbk = p + 1 == parts ? std::min<int>(HB_BUCKETS, (int)((kor - g.key_base) >> bshift) + 1) : HB_BUCKETS;
+        int64_t want = d.n / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;   // (how the records spread over the partitions is not known: room as for all of them)
+        while (cap2 < want && cap2 < sub_max) cap2 *= 2;
+        g.bk_cap = (int32_t)cap2; g.bk_off = bk_ents; g.bk_tile0 = (int32_t)nbt;
+        bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
+        const int64_t t = follow ? 0 : (d.n + BK_TILE - 1) / BK_TILE;   // (the second of a pair has no tiles of its own)
+        bk_tile_seg.insert(bk_tile_seg.end(), (size_t)t, (int32_t)segs.size());
+        nbt += t;
+        fake.push_back(bucket_vcf(d.n, d.truth, (int32_t)segs.size() * out_stride, out_stride));   // the two streams' rows of a partition
+        segs.push_back(g);
+        seg_vcf.push_back(vs[(size_t)i]);
+      }
+      SortSeg& vg = vsegs[(size_t)i];
+      memset(&vg, 0, sizeof vg);
+      vg.src_off = d.off; vg.n = d.n; vg.main_vcf = vs[(size_t)i]; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
+      vparts[(size_t)i] = parts;
     }
-    SortSeg& vg = vsegs[(size_t)i];
-    memset(&vg, 0, sizeof vg);
-    vg.src_off = d.off; vg.n = d.n; vg.main_vcf = vs[(size_t)i]; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
-    vparts[(size_t)i] = parts;
-    const size_t k0 = ktile_seg.size();
-    ktile_seg.insert(ktile_seg.end(), (size_t)d.ntiles, (int32_t)i);
-    ktile_local.resize(k0 + (size_t)d.ntiles);
-    for (int t = 0; t < d.ntiles; ++t) ktile_local[k0 + (size_t)t] = t;
-    nkt += d.ntiles;
-  }
-  nseg = (int)segs.size();
-  if (nbt > INT32_MAX || nkt > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
-  // the arrays of the one-level path, sized for these segments (its cached tables, and the two-level path's, are gone after this)
-  b->last_segs.clear(); b->bk_tiles_valid = false; b->bk_fake_valid = false; b->last2_vs.clear(); b->lastx_vs.clear();
-  int rc = QM_OK;
-  int64_t cap;
-  { cap = b->cap_segs; rc = regrow(&b->d_segs, &cap, (int64_t)nseg, &b->dev_bytes); b->cap_segs = (int)cap; }
-  if (rc == QM_OK) rc = regrow(&b->d_vsegs, &b->cap_vsegs, (int64_t)nv, &b->dev_bytes);
-  if (rc == QM_OK) {
-    cap = b->cap_ktiles; rc = regrow(&b->d_ktile_seg, &cap, nkt, &b->dev_bytes);
-    if (rc == QM_OK) { cap = b->cap_ktiles; rc = regrow(&b->d_ktile_local, &cap, nkt, &b->dev_bytes); }
-    if (rc == QM_OK) b->cap_ktiles = std::max(b->cap_ktiles, (int)nkt);
-  }
-  {
-    const int64_t rows = (int64_t)nseg * HB_BUCKETS, orows = (int64_t)nseg * out_stride;
-    int64_t c1 = b->cap_bk_rows * SPAN_HIST_WORDS, c2 = b->cap_bk_rows * 8;
-    if (rc == QM_OK) rc = regrow(&b->bk_hist, &c1, orows * SPAN_HIST_WORDS, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_scal, &c2, orows * 8, &b->dev_bytes);
-    if (rc == QM_OK) b->cap_bk_rows = std::max(b->cap_bk_rows, orows);
-    if (rc == QM_OK && xs) rc = regrow(&b->bk_xent, &b->cap_bk_xent, 2 * bk_ents, &b->dev_bytes);
-    if (rc == QM_OK && xs) rc = regrow(&b->bk_xcursor, &b->cap_bk_xcursor, rows * HB_SUBS, &b->dev_bytes);
-    if (rc == QM_OK && xs) rc = regrow(&b->bk_xrows, &b->cap_bk_xrows, rows, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->d_bk_vcfs, &b->cap_bk_vcfs, (int64_t)nseg, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_ent, &b->cap_bk_ent, bk_ents, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_rows, &b->cap_bk_rowdesc, rows, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->bk_cursor, &b->cap_bk_cursor, rows * HB_SUBS + nseg + 32 + 16 * 65 + (int64_t)nseg * (SEG_HIST_WORDS + 1), &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->d_bk_tile_seg, &b->cap_bk_tiles, nbt, &b->dev_bytes);
+    ktile_maps(b, vs, ktile_seg, ktile_local);
+    const int nseg = (int)segs.size();
+    const int64_t nkt = (int64_t)ktile_seg.size();
+    if (nbt > INT32_MAX || nkt > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
+    int rc = ensure_seg_arrays(b, nseg, nkt);
+    if (rc == QM_OK) rc = regrow(&b->d_vsegs, &b->cap_vsegs, (int64_t)nv, &b->dev_bytes);
     if (rc == QM_OK) rc = regrow(&b->d_vparts, &b->cap_vparts, (int64_t)nv, &b->dev_bytes);
-    if (rc == QM_OK) rc = ensure_bucket_rows(b, nseg);
+    if (rc == QM_OK) rc = ensure_bucket_arrays(b, nseg, bk_ents, nbt, xs);
+    if (rc != QM_OK) return rc;
+    HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_vsegs, vsegs.data(), sizeof(SortSeg) * vsegs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_vparts, vparts.data(), 4 * vparts.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // the host tables die with this block
+    b->tables = qm_batch::Tables{path, vs, key, nseg, nbt, nkt, seg_vcf};
   }
-  if (rc != QM_OK) return rc;
-  HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_vsegs, vsegs.data(), sizeof(SortSeg) * vsegs.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_vparts, vparts.data(), 4 * vparts.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));   // the host tables die with this block
-  b->lastx_vs = vs; b->lastx_por = por; b->lastx_wide = wide; b->lastx_nseg = nseg; b->lastx_nbt = nbt; b->lastx_nkt = nkt;
-  b->lastx_seg_vcf.resize((size_t)nseg);
-  for (int i = 0; i < nseg; ++i) b->lastx_seg_vcf[(size_t)i] = segs[(size_t)i].main_vcf;
-  }   // !same
-  const size_t nhist0 = (size_t)nseg * HB_BUCKETS * HB_SUBS + (size_t)nseg + 32 + 16 * 65;   // the scatter's per-segment histograms lie behind the cursors, flags and phase clocks
-  const size_t ncur = (nhist0 + (size_t)nseg * (SEG_HIST_WORDS + 1)) * 4;   // (+ 1: seg_maxd behind the histograms)
+  const int nseg = b->tables.nseg;
+  const CursorRegion C = cursor_region(b, nseg);
   if (xs) HIPCHK(hipMemsetAsync(b->bk_xcursor, 0, (size_t)nseg * HB_BUCKETS * HB_SUBS * 4, st));
   BucketScatterParams S;
-  S.segs = b->d_segs; S.tile_seg = b->d_bk_tile_seg; S.pos = b->pos; S.ref = b->ref; S.alt = b->alt; S.qual = b->qual; S.flags = b->flags;
-  S.cursor = b->bk_cursor; S.ent = b->bk_ent; S.mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); S.mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp);
-  S.n_seg = nseg; S.n_bins = b->n_bins; S.tile_base = 0; S.l1_ent = nullptr; S.xent = xs ? b->bk_xent : nullptr; S.xcursor = xs ? b->bk_xcursor : nullptr; S.ext = xs ? 1 : 0;
-  S.pairs = 1;   // (tiles of single partitions run through the 512-digit instantiation as well)
-  uint32_t* const seg_hist = b->bk_cursor + nhist0;
-  uint32_t* const seg_maxd = nullptr;   // (the look at the highest filled bucket was measured on this path and lost: 2.08 against 2.02 ms per 64 x 2 M)
-  S.seg_hist = seg_hist; S.seg_maxd = seg_maxd; S.l1_half = nullptr;
   HashParams H;
-  H.segs = b->d_segs; H.rows = b->bk_rows; H.rows_out = b->bk_rows; H.ent = b->bk_ent; H.cursor = b->bk_cursor; H.truths = b->ctx->d_truths; H.vcfs = b->d_vcfs;
-  H.mask_tp = b->mask_tp; H.row_hist = b->bk_hist; H.row_scal = b->bk_scal; H.n_seg = nseg; H.n_bins = b->n_bins; H.seg_base = 0;
-  H.xrows = xs ? b->bk_xrows : nullptr; H.xent = b->bk_xent; H.xcursor = b->bk_xcursor; H.out_stride = out_stride; H.ext = xs ? 1 : 0; H.scatter_hist = seg_hist ? 1 : 0; H.seg_maxd = seg_maxd;
-  H.zero = b->bk_cursor; H.n_zero = (uint32_t)(ncur / 4);   // the scatter's cursors, flags and counts: cleared by the kernel that writes the rows (one dispatch instead of a memset's two)
+  bucket_params(b, nseg, xs, C.seg_hist, &S, &H);
+  S.pairs = 1;   // (tiles of single partitions run through the 512-digit instantiation as well)
+  // (no look at the highest filled bucket, seg_maxd: measured on this path and lost, 2.08 against 2.02 ms per 64 x 2 M)
+  H.zero = b->bk_cursor; H.n_zero = C.words;   // the scatter's cursors, flags and counts: cleared by the kernel that writes the rows (one dispatch instead of a memset's two)
   launch_bucket_rows(H, nseg, st);
   H.zero = nullptr; H.n_zero = 0u;
-  launch_bucket_scatter(S, (int)nbt, st);
+  launch_bucket_scatter(S, (int)b->tables.nbt, st);
   if (wide) launch_join_big(H, nseg, HB_BUCKETS, st);
   else launch_join_lean(H, nseg, DJ_MAX_SHIFT, HB_BUCKETS, st);
   if (xs) launch_join_ext(H, nseg, HB_BUCKETS, st);
-  {
-    FinalizeParams F = bucket_rows_finalize(b, seg_hist);
-    F.row_cap = seg_maxd;
-    launch_finalize(F, nseg, st);
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<uint32_t> hfl((size_t)nseg);
-  HIPCHK(hipMemcpyAsync(hfl.data(), b->bk_vflags, 4 * hfl.size(), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  launch_finalize(bucket_rows_finalize(b, C.seg_hist), nseg, st);
   b->path_stats[QM_PATH_BUCKET_CHUNKS] += 1;
-  bool overflow = false;
-  for (int i = 0; i < nseg; ++i) {
-    if (hfl[(size_t)i] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", b->lastx_seg_vcf[(size_t)i]);
-    if (hfl[(size_t)i] & SPANF_OVERFLOW) {   // a bucket did not fit: nothing of the chunk is handed over
-      overflow = true;
-      if (bad && (bad->empty() || bad->back() != b->lastx_seg_vcf[(size_t)i])) bad->push_back(b->lastx_seg_vcf[(size_t)i]);   // (a VCF's segments lie one behind the other)
+  return look_and_hand_over(b, nv, QM_PATH_PARTITIONS, st, named);
+}
+
+// --- one chunk on its path, and what an overflow leaves.  A run that overflows hands nothing over: the VCFs it names are held back
+// and the others run again among themselves, up to PATHS[path].runs runs; every VCF then still without a result goes to the next path
+// (the radix sort counts it as QM_PATH_RADIX_AFTER_OVERFLOW).  named: VCFs a run of this chunk has named already (settle_pending:
+// the speculative run of a one-level chunk).
+static int run_chunk_with_fallback(qm_batch* b, Path path, const std::vector<int>& chunk, hipStream_t st, const std::vector<uint32_t>& posor,
+                                   std::vector<int> named = {}) {
+  if (path == Path::Radix) return radix_chunk(b, chunk, st, posor, QM_PATH_RADIX);
+  auto without = [](const std::vector<int>& a, const std::vector<int>& drop) {
+    std::vector<int> r;
+    for (int v : a) if (std::find(drop.begin(), drop.end(), v) == drop.end()) r.push_back(v);
+    return r;
+  };
+  std::vector<int> vs = without(chunk, named);   // the VCFs of the next run
+  bool done = false;
+  for (int k = named.empty() ? 0 : 1; k < PATHS[(int)path].runs && !vs.empty(); ++k) {
+    std::vector<int> more;
+    int rc = QM_OK;
+    switch (path) {
+      case Path::OneLevel: rc = onelevel_chunk(b, vs, st, posor, k == 0, &more); break;
+      case Path::TwoLevel: rc = two_level_chunk(b, vs, st, &more); break;
+      default: rc = partitions_chunk(b, vs, st, posor, path == Path::Wide, &more); break;
     }
+    if (rc != QM_OK) return rc;
+    if (more.empty()) { done = true; break; }
+    if (more.size() >= vs.size()) break;
+    named.insert(named.end(), more.begin(), more.end());
+    vs = without(vs, more);
   }
-  if (overflow) { b->path_stats[QM_PATH_OVERFLOW_CHUNKS] += 1; b->lastx_vs.clear(); return QM_OK; }
-  launch_sort_copy_rows(b->d_vsegs, nv, b->bk_roc, b->bk_rscal, b->roc, b->scalars, b->n_bins, st, global, b->d_vcfs, b->d_vparts);
-  launch_tile_counts(b->d_vsegs, b->d_ktile_seg, b->d_ktile_local, (int)nkt, b->mask_pass, b->mask_tp, b->tile_tp, b->tile_fp, st);
-  HIPCHK(hipGetLastError());
-  b->path_stats[QM_PATH_PARTITIONS] += nv;
-  *taken = true;
-  return QM_OK;
+  const std::vector<int>& left = done ? named : chunk;
+  if (left.empty()) return QM_OK;
+  const Path next = PATHS[(int)path].next;
+  if (next == Path::Radix) return radix_chunk(b, left, st, posor, QM_PATH_RADIX_AFTER_OVERFLOW);
+  return run_chunk_with_fallback(b, next, left, st, posor);
 }
 
 // re-derive tile offsets + compaction for every VCF (cheap: masks only)
 static int rescan_and_compact(qm_batch* b, hipStream_t st);
 
-// The VCFs found out of order, redone: by size on the two-level bucket path (kind 2), the bucket path (1) or the radix sort (0),
-// in chunks of <= 2^28 records.  posor[v]: the position bits the optimistic pass saw in VCF v.
+// The VCFs found out of order, redone: each on the path route() gives it, in chunks of that path.  posor[v]: the position bits the
+// optimistic pass saw in VCF v.
 static int redo_unsorted(qm_batch* b, const std::vector<int>& todo, const std::vector<uint32_t>& posor, hipStream_t st) {
-  // the VCFs the bucket path takes (by size: a VCF costs it 256 workgroups and 256 rows whatever it holds, and its
-  // buckets hold 8 192 records at most) in chunks of their own, the others on the radix sort
-  // kind 3: allele-extended VCFs in partitions read from the columns (bucketx_chunk)
-  refresh_path_env();
-  std::vector<int> part[5];   // 4: partitions of WIDE buckets (bucketw_takes)
+  std::vector<int> by_path[N_PATHS];
   for (int v : todo) {
-    const int64_t n = b->L.vcfs[(size_t)v].n;
-    const bool force2 = g_penv.bucket2 == 2 && bucket2_takes(b, n);
-    const bool wide = bucketw_takes(b, v, n, posor[(size_t)v]);
-    // A default-mode VCF with more records than the narrow buckets of its reference hold (8 192 per 2^15 positions, the
-    // sub-regions 13/16 full on average: 0.2 records per position) overflows the partitions and the two levels alike, and a
-    // chunk falls back as a whole: such a VCF goes to the radix sort alone instead of taking its neighbours with it.  (The
-    // position bits are an upper bound of up to twice the highest position: this errs towards trying the buckets.)
-    const int64_t narrow_buckets = ((((int64_t)posor[(size_t)v] << 4) | 15) >> DJ_MAX_SHIFT) + 1;
-    const bool dense = !b->ext && g_penv.bucketx != 2 && g_penv.bucket2 != 2 && n > narrow_buckets * (HB_MAX_RECORDS * 13 / 16);
-    part[wide && g_penv.bucketx == 3 ? 4 : !dense && bucketx_takes(b, n, posor[(size_t)v]) ? 3 : force2 ? 2 : wide ? 4 : bucket_path_takes(b, n) ? 1
-         : !dense && bucket2_takes(b, n) ? 2 : 0].push_back(v);
+    const VcfDesc& d = b->L.vcfs[(size_t)v];
+    by_path[(int)route(b->ext, d.n, posor[(size_t)v], b->ctx->truths[(size_t)d.truth].n, g_penv)].push_back(v);
   }
-  const int64_t chunk_records = sort_chunk_records();
-  // the two levels for a chunk; the VCFs of it that do not fit (a partition too dense, a bucket that overflowed) go through the
-  // radix sort, the others through the two levels again among themselves
-  auto two_levels_or_sort = [&](const std::vector<int>& chunk) -> int {
-    std::vector<int> pending = chunk, bad;   // pending: the VCFs without a result so far
-    for (int round = 0; round < 3; ++round) {   // (a partition too dense names one VCF at a time: three tries, then everything left is sorted)
-      std::vector<int> good, named;
-      for (int v : pending) if (std::find(bad.begin(), bad.end(), v) == bad.end()) good.push_back(v);
-      if (good.empty()) break;
-      bool taken = false;
-      const int rc = bucket2_chunk(b, good, st, b->last_global, &taken, &named);
-      if (rc != QM_OK) return rc;
-      if (taken) { pending = bad; break; }
-      if (named.empty() || named.size() >= good.size()) break;
-      bad.insert(bad.end(), named.begin(), named.end());
-    }
-    if (pending.empty()) return QM_OK;
-    b->path_stats[QM_PATH_RADIX_AFTER_OVERFLOW] += (int64_t)pending.size();
-    const int rc = sort_chunk(b, pending, st, b->last_global, posor, false);
-    b->path_stats[QM_PATH_RADIX] -= (int64_t)pending.size();
-    return rc;
-  };
-  for (int kind = 4; kind >= 0; --kind) {
+  const int64_t budget = sort_chunk_records();
+  for (int p = N_PATHS - 1; p >= 0; --p) {   // (the wide buckets first, the radix sort last)
+    const PathInfo& P = PATHS[p];
     std::vector<int> chunk;
     int64_t chunk_n = 0;
-    for (size_t i = 0; i <= part[kind].size(); ++i) {
-      // (kind 3: every PAIR of partitions reads its whole VCF)
-      const int64_t wgt = i < part[kind].size() ? b->L.vcfs[(size_t)part[kind][i]].n * (kind == 3 ? (ext_parts_of(posor[(size_t)part[kind][i]]) + 1) / 2 : 1) : 0;
-      const bool flush = i == part[kind].size() || (!chunk.empty() && chunk_n + wgt > chunk_records) ||
-                         (kind >= 1 && chunk.size() >= (size_t)(kind == 3 ? 4096 / PX_MAX_PARTS : kind == 4 ? 64 : 4096));   // (kind 4: 2 x 67 MB of bucket regions per VCF)   // 256 rows of 1.5 KB and >= 1 MB of bucket regions per VCF: bounded per chunk
-      if (flush && !chunk.empty()) {
-        int rc = QM_OK;
-        bool taken = false;
-        if (kind == 4 || kind == 3) {
-          // a chunk one of whose VCFs overflowed is not handed over: the VCFs that fitted take the same buckets again, among
-          // themselves; the others go on to the next path (wide buckets: two levels, then the radix sort)
-          std::vector<int> bad, rest = chunk;
-          rc = bucketx_chunk(b, chunk, st, b->last_global, posor, &taken, kind == 4, &bad);
-          if (rc == QM_OK && !taken && !bad.empty() && bad.size() < chunk.size()) {
-            std::vector<int> good;
-            for (int v : chunk) if (std::find(bad.begin(), bad.end(), v) == bad.end()) good.push_back(v);
-            bool taken_good = false;
-            rc = bucketx_chunk(b, good, st, b->last_global, posor, &taken_good, kind == 4);
-            if (taken_good) rest = bad;
-          }
-          if (rc == QM_OK && !taken) {
-            if (kind == 4) rc = two_levels_or_sort(rest);
-            else { b->path_stats[QM_PATH_RADIX_AFTER_OVERFLOW] += (int64_t)rest.size(); rc = sort_chunk(b, rest, st, b->last_global, posor, false); b->path_stats[QM_PATH_RADIX] -= (int64_t)rest.size(); }
-          }
-        } else if (kind == 2) {
-          rc = two_levels_or_sort(chunk);
-        } else {
-          rc = sort_chunk(b, chunk, st, b->last_global, posor, kind == 1);
-        }
+    for (size_t i = 0; i <= by_path[p].size(); ++i) {
+      const bool end = i == by_path[p].size();
+      const int v = end ? -1 : by_path[p][i];
+      const int64_t w = end ? 0 : b->L.vcfs[(size_t)v].n * (P.per_pass ? (parts_of(posor[(size_t)v]) + 1) / 2 : 1);
+      if (!chunk.empty() && (end || chunk_n + w > budget || (int)chunk.size() >= P.max_vcfs)) {
+        const int rc = run_chunk_with_fallback(b, (Path)p, chunk, st, posor);
         if (rc != QM_OK) return rc;
         chunk.clear();
         chunk_n = 0;
       }
-      if (i < part[kind].size()) { chunk.push_back(part[kind][i]); chunk_n += wgt; }
+      if (!end) { chunk.push_back(v); chunk_n += w; }
     }
   }
   return QM_OK;
 }
 
-// The bucket chunks queued without a look at their flags (sort_chunk: speculate), behind the wait that ended the step: the mirrors
-// of their rows' k_finalize say whether a chunk fitted.  One that did not was left alone by k_sort_copy_rows (nothing of it joined
-// the per-truth sums) and goes through the radix sort now, followed by another rescan.
+// The one-level chunks queued without a look at their flags (onelevel_chunk: speculate), behind the wait that ended the step: the
+// mirrors of their rows' k_finalize say whether a chunk fitted.  One that did not was left alone by k_sort_copy_rows (nothing of it
+// joined the per-truth sums) and takes run_chunk_with_fallback now, followed by another rescan.
 static int settle_pending(qm_batch* b, const std::vector<uint32_t>& posor, hipStream_t st) {
   std::vector<qm_batch::Pending> pend;
   pend.swap(b->pend);
   b->pend_segs = 0;
-  // every chunk's mirror words first: a re-run below writes its own over them
-  std::vector<std::vector<uint32_t>> flags(pend.size());
+  // every chunk's verdict first: a re-run below writes its own mirror words over theirs
+  std::vector<std::vector<int>> named(pend.size());
   for (size_t k = 0; k < pend.size(); ++k) {
     const qm_batch::Pending& p = pend[k];
-    const int nseg = (int)p.vs.size();
-    flags[k].resize((size_t)nseg);
-    for (int i = 0; i < nseg; ++i) {
-      uint32_t fl = b->h_summary[16 + 2 * (size_t)b->n_vcf + (size_t)p.off + (size_t)i];
-      if (p.tight) {
-        const uint32_t md = b->h_summary[16 + 3 * (size_t)b->n_vcf + (size_t)p.off + (size_t)i];
-        if (md > (uint32_t)p.nbk_launch) fl |= SPANF_OVERFLOW;   // (a remembered bound that no longer holds: cannot happen while the columns stay the same)
-        else if (memo_on()) {
-          if (b->known_nbk.empty()) b->known_nbk.assign((size_t)b->n_vcf, 0u);
-          b->known_nbk[(size_t)p.vs[(size_t)i]] = std::max(md, 1u);
-        }
-      }
-      if (fl & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", p.vs[(size_t)i]);
-      flags[k][(size_t)i] = fl;
+    const uint32_t* fl = b->h_summary + 16 + 2 * (size_t)b->n_vcf + (size_t)p.off;
+    const uint32_t* md = b->h_summary + 16 + 3 * (size_t)b->n_vcf + (size_t)p.off;
+    if (p.tight && memo_on()) {
+      if (b->known_nbk.empty()) b->known_nbk.assign((size_t)b->n_vcf, 0u);
+      for (size_t i = 0; i < p.vs.size(); ++i) if (md[i] <= (uint32_t)p.nbk_launch) b->known_nbk[(size_t)p.vs[i]] = std::max(md[i], 1u);
     }
+    const int rc = bucket_verdict(b, fl, p.tight ? md : nullptr, (uint32_t)p.nbk_launch, p.vs, &named[k]);
+    if (rc != QM_OK) return rc;
   }
   bool again = false;
   for (size_t k = 0; k < pend.size(); ++k) {
     const qm_batch::Pending& p = pend[k];
-    const int nseg = (int)p.vs.size();
-    std::vector<int> bad, good;
-    for (int i = 0; i < nseg; ++i) ((flags[k][(size_t)i] & SPANF_OVERFLOW) ? bad : good).push_back(p.vs[(size_t)i]);
-    if (bad.empty()) { b->path_stats[p.direct ? QM_PATH_DIRECT : QM_PATH_HASHED] += nseg; continue; }
-    // a bucket of a VCF did not fit its tables (dense positions, a dense truth set): nothing of the chunk was handed over
-    // (k_sort_copy_rows saw its "bad" word).  The radix sort redoes that VCF from the columns, the others take the buckets again.
+    if (named[k].empty()) { b->path_stats[p.direct ? QM_PATH_DIRECT : QM_PATH_HASHED] += (int64_t)p.vs.size(); continue; }
     if (p.tight && !b->known_nbk.empty()) for (int v : p.vs) b->known_nbk[(size_t)v] = 0u;
     // (what the radix sort learns about its chunk's positions corrects the estimate such a VCF is remembered with: posor_seen)
-    b->path_stats[QM_PATH_OVERFLOW_CHUNKS] += 1;
-    const int rc = redo_overflowed(b, bad, good, st, b->last_global, posor);
+    const int rc = run_chunk_with_fallback(b, Path::OneLevel, p.vs, st, posor, named[k]);
     if (rc != QM_OK) return rc;
     again = true;
   }
@@ -1948,6 +1848,7 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
   HIPCHK(hipSetDevice(c->dev));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   if (b->finished) { HIPCHK(hipStreamSynchronize(st)); return QM_OK; }
+  if (read_path_env() != QM_OK) { (void)hipStreamSynchronize(st); return QM_E_INVAL; }
   for (auto& x : b->path_stats) x = 0;
   b->pend.clear(); b->pend_segs = 0;
   // QM_FINISH_TRACE=1: the host's clock at the stations of this call, in us since it was entered (stderr)

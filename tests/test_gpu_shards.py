@@ -284,8 +284,8 @@ def test_plain_bench_run_times_the_steps_and_dumps_the_same_outputs_twice(engine
 
 def test_the_two_bucket_joins_agree_behind_one_scatter(qmlib):
     """k_join_lean (default) and the hashed join (QM_JOIN=hash) behind the same scatter, on the same 24 shuffled VCFs of configs[2]'s
-    shape: one digest over ROC rows, scalars, an index list and a VCF's class bits.  (The choice is read once per process, so every
-    variant is a process of its own; with and without the batch's memory.)  Round 3's third join, one bit per key, left the library in
+    shape: one digest over ROC rows, scalars, an index list and a VCF's class bits.  (Every variant is a
+    process of its own; with and without the batch's memory.)  Round 3's third join, one bit per key, left the library in
     round 6 (tools/probe/k_join_direct.hip.txt)."""
     import re
     import subprocess

@@ -5,15 +5,14 @@ mkdir -p gpurun_out
 OUT=gpurun_out/fuzz_campaign.log; : > $OUT
 run() { echo "== $*" >> $OUT; env "$@" python3 tools/gpu_fuzz.py $N $SEED 2>&1 | tail -1 >> $OUT; }
 SEED=101 run QM_X=0
-SEED=102 run QM_BUCKET2=2
+SEED=102 run QM_UNSORTED_PATH=two_level
 SEED=103 run QM_JOIN=hash
-SEED=104 run QM_SORT_PATH=radix
-SEED=105 run QM_BUCKET_EXT=0
+SEED=104 run QM_UNSORTED_PATH=radix
 SEED=106 run QM_MEMO=0
 SEED=108 run QM_PIPE_CHUNKS=3
-SEED=109 run QM_BUCKETX=2
-SEED=110 run QM_BUCKETX=3
-SEED=112 run QM_BUCKET2=2 QM_MEMO=0
+SEED=109 run QM_UNSORTED_PATH=partitions
+SEED=110 run QM_UNSORTED_PATH=wide
+SEED=112 run QM_UNSORTED_PATH=two_level QM_MEMO=0
 # finish without its round trips (flags event, queued chunk tails) against the old waits; several chunks per finish
 SEED=117 run QM_SPECULATE=0
 SEED=118 run QM_FLAGS_WAIT=stream

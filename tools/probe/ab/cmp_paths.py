@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The same shuffled batch through the default routing and through QM_BUCKETX=3 / 0, against the sorted run and the oracle.
+"""The same shuffled batch through the default routing and through QM_UNSORTED_PATH=wide / two_level, against the sorted run and the oracle.
 usage: python3 tools/probe/ab/cmp_paths.py n_vcf records genome truth"""
 import os
 import sys
@@ -17,11 +17,11 @@ eng = q.Engine(0)
 tid = eng.truth_synth(L, T, 4)
 tk = synth_truth_keys(L, T, 4)
 res = {}
-for name, shuffled, env in (("sorted", False, None), ("default", True, None), ("X3", True, "3"), ("X0", True, "0")):
+for name, shuffled, env in (("sorted", False, None), ("default", True, None), ("wide", True, "wide"), ("two_level", True, "two_level")):
     if env is None:
-        os.environ.pop("QM_BUCKETX", None)
+        os.environ.pop("QM_UNSORTED_PATH", None)
     else:
-        os.environ["QM_BUCKETX"] = env
+        os.environ["QM_UNSORTED_PATH"] = env
     b = eng.batch([N] * nv, [tid] * nv)
     b.synth(L, T, 4, 4000, shuffled=shuffled)
     b.run(); b.finish()
@@ -36,7 +36,7 @@ for name, shuffled, env in (("sorted", False, None), ("default", True, None), ("
         print("oracle vs shuffled default: cls", np.array_equal(cls, res[name][2][nv - 1]), "roc", np.array_equal(oroc, res[name][0][nv - 1]),
               "scal", [int(x) for x in res[name][1][nv - 1]] == [sc[k] for k in ("n_pass", "tp_lines", "fp_lines", "TP_R", "FP_R")])
         ocls = cls
-    if name in ("X3", "X0"):
+    if name in ("wide", "two_level"):
         print("oracle vs shuffled", name, ": cls", np.array_equal(ocls, res[name][2][nv - 1]))
     b.close()
     print(name, {k: v for k, v in res[name][3].items() if v})
