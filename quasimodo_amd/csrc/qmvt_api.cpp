@@ -70,7 +70,7 @@ struct Truth {
 struct qm_ctx {
   int dev = 0;
   hipStream_t stream = nullptr;
-  hipStream_t aux = nullptr;     // compaction of one span range runs here, beside the classification of the next
+  hipStream_t aux = nullptr;     // the run's row sums beside its compaction; the hashed join of a bucket chunk beside its scatter
   std::vector<Truth> truths;
   TruthDev* d_truths = nullptr;  // device copy of the descriptors
   int d_truths_cap = 0;
@@ -446,12 +446,11 @@ struct qm_batch {
   int32_t *d_tile_seg = nullptr, *d_ktile_seg = nullptr, *d_ktile_local = nullptr;
   int64_t cap_sort_n = 0, cap_sort_hist = 0;
   int64_t cap_segs = 0, cap_stiles = 0, cap_ktiles = 0;
-  // The run is pipelined over a few ranges of VCFs: k_compact of range i (issue-bound, writes) runs on the context's
-  // second stream beside k_classify of range i + 1 (latency-bound, reads).
-  static constexpr int MAX_CHUNKS = 8;
-  struct Chunk { int v0, v1, s0, s1; };
-  std::vector<Chunk> chunks;
-  hipEvent_t ev_sync[MAX_CHUNKS + 2] = {};   // ordering between the two streams (no timing)
+  // Ordering between the context's two streams (no timing).  The run: [0] behind the flags' k_finalize, [1] behind the rows'.
+  // The hashed join of a one-level chunk (onelevel_chunk): [p] behind the scatter of range p, ev_join behind the last join.
+  static constexpr int JOIN_PARTS = 4;
+  hipEvent_t ev_sync[JOIN_PARTS] = {};
+  hipEvent_t ev_join = nullptr;
   // behind the k_finalize part of the run that writes the per-VCF flags (and their host-mapped mirrors): qm_batch_finish waits for
   // THIS, not for the whole stream -- what it then queues (the bucket path of the VCFs found out of order) is built and launched
   // while the run's compaction and row sums are still going, and starts right behind them
@@ -466,9 +465,8 @@ struct qm_batch {
   // timing
   bool timing = false;
   static constexpr int EV_RING = 32;   // per-kernel events of the latest runs
-  static constexpr int EV_PER_RUN = 2 + 5 * MAX_CHUNKS;   // [0] start [1] end, then per chunk: classify start / end, finalize end (main stream); compact start / end (second stream)
+  static constexpr int EV_PER_RUN = 2 + 5;   // [0] start [1] end, classify start / end, finalize end, compact start / end
   hipEvent_t ev[EV_RING][EV_PER_RUN] = {};
-  int ev_chunks[EV_RING] = {};
   int64_t n_timed = 0;
   bool ran = false, finished = false;
   bool ext = false;   // allele-extended: any valid allele code takes part (build-defined widening, config 5)
@@ -505,10 +503,6 @@ static bool memo_on() {   // read at every run / finish: bench.py times a batch 
   const char* e = getenv("QM_MEMO");
   return !e || atoi(e) != 0;
 }
-static bool flags_event_on() {   // QM_FLAGS_WAIT=stream: qm_batch_finish waits for the whole stream before it looks at the flags (rounds 1-4)
-  const char* e = getenv("QM_FLAGS_WAIT");
-  return !(e && strcmp(e, "stream") == 0);
-}
 static void forget_known(qm_batch* b, int v) {   // v < 0: every VCF
   if (!b->posor_seen.empty()) { if (v < 0) std::fill(b->posor_seen.begin(), b->posor_seen.end(), 0u); else b->posor_seen[(size_t)v] = 0u; }
   if (!b->known_nbk.empty()) { if (v < 0) std::fill(b->known_nbk.begin(), b->known_nbk.end(), 0u); else b->known_nbk[(size_t)v] = 0u; }
@@ -529,6 +523,7 @@ static void batch_free(qm_batch* b) {
   if (b->h_summary) (void)hipHostFree(b->h_summary);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
+  if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   if (b->ev_flags) (void)hipEventDestroy(b->ev_flags);
   delete b;
 }
@@ -572,30 +567,12 @@ static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int
   A_(b->d_vcfs, (size_t)n_vcf) A_(b->d_spans, b->cap_spans) A_(b->d_tile_vcf, b->cap_tiles) A_(b->cls_scratch, (size_t)L.max_n)
 #undef A_
   if (rc == QM_OK) rc = upload_layout(b);
-  if (rc == QM_OK) {
-    // ranges of whole VCFs with about equal numbers of spans; small batches stay in one piece
-    int want = 1;   // measured on MI355X: more than one range is SLOWER (the two kernels slow each other down by more than the overlap gains; profiles/README.md)
-    int min_spans = 4096;   // a range should fill the chip (5 120 waves) a few times over
-    if (const char* e = getenv("QM_PIPE_CHUNKS")) { want = atoi(e); min_spans = 1; }   // (tests, tools/gpu_fuzz.py: the ranges asked for, however small the batch)
-    want = std::max(1, std::min(want, (int)qm_batch::MAX_CHUNKS));
-    const int ns = (int)L.spans.size();
-    if (ns < min_spans * want) want = std::max(1, ns / min_spans);
-    int v = 0;
-    for (int k = 0; k < want && v < n_vcf; ++k) {
-      qm_batch::Chunk ck;
-      ck.v0 = v; ck.s0 = L.vcfs[(size_t)v].span0;
-      const int target = (int)((int64_t)ns * (k + 1) / want);
-      while (v < n_vcf && (k == want - 1 || L.vcfs[(size_t)v].span0 + L.vcfs[(size_t)v].nspans <= target || v == ck.v0)) ++v;
-      ck.v1 = v; ck.s1 = v < n_vcf ? L.vcfs[(size_t)v].span0 : ns;
-      b->chunks.push_back(ck);
-    }
-    if (b->chunks.empty()) b->chunks.push_back(qm_batch::Chunk{0, n_vcf, 0, ns});
-    b->chunks.back().v1 = n_vcf; b->chunks.back().s1 = ns;
-    for (auto& e : b->ev_sync) {
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { rc = fail(QM_E_HIP, "hipEventCreate failed"); break; }
-    }
-    if (rc == QM_OK && hipEventCreateWithFlags(&b->ev_flags, hipEventDisableTiming) != hipSuccess) rc = fail(QM_E_HIP, "hipEventCreate failed");
-  }
+  auto create_event = [&](hipEvent_t& e) {
+    if (rc == QM_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = fail(QM_E_HIP, "hipEventCreate failed");
+  };
+  for (auto& e : b->ev_sync) create_event(e);
+  create_event(b->ev_join);
+  create_event(b->ev_flags);
   if (rc == QM_OK && !packed) {
     // padding lanes are masked in the kernels, but keep the columns defined.  On the context's
     // stream (hipMemset on the null stream would not be ordered before work on a non-blocking stream).
@@ -797,13 +774,8 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
       return fail(QM_E_STATE, "qm_batch_run: truth set %d was released after the batch was created", tg.first);
   const size_t gbytes = (size_t)b->n_truth * 3 * (size_t)b->n_bins * 8;   // as allocated at batch creation
   hipEvent_t* ev = b->ev[b->n_timed % qm_batch::EV_RING];
-  const int nch = (int)b->chunks.size();
   const bool T = b->timing;
-  if (T) { HIPCHK(hipEventRecord(ev[0], st)); b->ev_chunks[b->n_timed % qm_batch::EV_RING] = nch; }
-  // main stream: classify and finalize of every range, in order; second stream: the compaction of a range as soon as its
-  // tile offsets exist.  The second stream starts behind everything queued on the main one so far (an earlier run's
-  // compaction reads the masks this run rewrites) and the main stream ends behind the last compaction.
-  hipStream_t aux = nch > 1 ? c->aux : st;
+  if (T) HIPCHK(hipEventRecord(ev[0], st));
   // VCFs an earlier finish found out of order, columns unchanged since: their spans return at once (qm_batch: known)
   const bool use_known = memo_on() && b->n_known > 0;
   if (use_known && (b->known_dirty || !b->d_known)) {
@@ -813,70 +785,44 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   }
   b->run_used_known = use_known;
   b->flags_recorded = false;
-  if (nch > 1) {
-    HIPCHK(hipEventRecord(b->ev_sync[qm_batch::MAX_CHUNKS], st));
-    HIPCHK(hipStreamWaitEvent(aux, b->ev_sync[qm_batch::MAX_CHUNKS], 0));
-  }
-  // every VCF known to be out of order: the optimistic pass, its k_finalize and its compaction would find and write what the
-  // earlier run left (flags, position bits, rows nobody reads) -- only the per-truth sums are cleared
-  const bool all_known = use_known && b->n_known == b->n_vcf;
-  for (int k = 0; k < nch; ++k) {
-    const qm_batch::Chunk& ck = b->chunks[(size_t)k];
-    hipEvent_t* e5 = ev + 2 + 5 * k;
-    if (all_known) {
-      if (k == 0) HIPCHK(hipMemsetAsync(g, 0, gbytes, st));
-      if (T) for (int q = 0; q < 5; ++q) HIPCHK(hipEventRecord(e5[q], st));
-      continue;
-    }
+  const int ns = (int)b->L.spans.size();
+  if (use_known && b->n_known == b->n_vcf) {
+    // every VCF known to be out of order: the optimistic pass, its k_finalize and its compaction would find and write what the
+    // earlier run left (flags, position bits, rows nobody reads) -- only the per-truth sums are cleared
+    HIPCHK(hipMemsetAsync(g, 0, gbytes, st));
+    if (T) for (int q = 2; q < 7; ++q) HIPCHK(hipEventRecord(ev[q], st));
+  } else {
     ClassifyParams P = classify_params(b);
-    P.span_base = ck.s0;
-    if (k == 0) {   // k_finalize, behind this launch, adds to the per-truth sums: the first wave of the launch clears them
-      if (ck.s1 > ck.s0) { P.zero_acc = g; P.zero_words = (int32_t)(gbytes / 8); }
-      else HIPCHK(hipMemsetAsync(g, 0, gbytes, st));   // a batch of empty VCFs launches nothing
-    }
+    // k_finalize, behind this launch, adds to the per-truth sums: the first wave of the launch clears them
+    if (ns > 0) { P.zero_acc = g; P.zero_words = (int32_t)(gbytes / 8); }
+    else HIPCHK(hipMemsetAsync(g, 0, gbytes, st));   // a batch of empty VCFs launches nothing
     if (use_known) P.known = b->d_known;
-    if (T) HIPCHK(hipEventRecord(e5[0], st));
-    launch_classify(P, ck.s1 - ck.s0, st);
-    if (T) HIPCHK(hipEventRecord(e5[1], st));
+    if (T) HIPCHK(hipEventRecord(ev[2], st));
+    launch_classify(P, ns, st);
+    if (T) HIPCHK(hipEventRecord(ev[3], st));
     FinalizeParams F = finalize_params(b, g);
-    F.vcf_base = ck.v0;
     // (no summary word: with the mirrors, qm_batch_finish looks through the VCFs' flag words itself -- and every workgroup of a
     // batch of shuffled VCFs storing to that ONE word of host memory made this kernel 50 us instead of 15: same-address stores
     // to system memory queue up.)
     if (b->d_summary) { F.host_flags = b->d_summary + 16; F.host_aux = b->d_summary + 16 + b->n_vcf; }
     if (use_known) F.known = b->d_known;
     F.lazy_unsorted = 1;
-    // In one piece (the default), the compaction waits only for what it needs of k_finalize -- per-VCF flags and tile offsets --
-    // and the rows (ROC, scalars, per-truth sums: 96 MB of span histograms to sum) go to the second stream beside it.
-    const bool split = nch == 1 && b->ev_sync[0] != nullptr;
-    // (host order: what the compaction -- and a first-seen step's look at the flags -- waits for is queued first, the rows' part
-    // behind it; it starts beside the compaction either way)
-    if (split) F.parts = 1;
-    launch_finalize(F, ck.v1 - ck.v0, st);
-    if (k == nch - 1 && b->ev_flags && flags_event_on()) { HIPCHK(hipEventRecord(b->ev_flags, st)); b->flags_recorded = true; }   // every VCF's flags are written
-    if (split) HIPCHK(hipEventRecord(b->ev_sync[0], st));
-    if (T) HIPCHK(hipEventRecord(e5[2], st));
-    CompactParams K = compact_params(b);
-    K.span_base = ck.s0;
-    if (nch > 1) {
-      HIPCHK(hipEventRecord(b->ev_sync[k], st));
-      HIPCHK(hipStreamWaitEvent(aux, b->ev_sync[k], 0));
-    }
-    if (T) HIPCHK(hipEventRecord(e5[3], aux));
-    launch_compact(K, ck.s1 - ck.s0, aux);
-    if (split) {
-      HIPCHK(hipStreamWaitEvent(c->aux, b->ev_sync[0], 0));
-      F.parts = 2;
-      launch_finalize(F, ck.v1 - ck.v0, c->aux);
-      HIPCHK(hipEventRecord(b->ev_sync[1], c->aux));
-    }
-    if (T) HIPCHK(hipEventRecord(e5[4], aux));
-  }
-  if (all_known) {
-  } else if (nch > 1) {
-    HIPCHK(hipEventRecord(b->ev_sync[qm_batch::MAX_CHUNKS + 1], aux));
-    HIPCHK(hipStreamWaitEvent(st, b->ev_sync[qm_batch::MAX_CHUNKS + 1], 0));
-  } else if (b->ev_sync[0] != nullptr) {
+    // The compaction waits only for what it needs of k_finalize -- per-VCF flags and tile offsets -- and the rows (ROC, scalars,
+    // per-truth sums: 96 MB of span histograms to sum) go to the second stream beside it.  (Host order: what the compaction --
+    // and a first-seen step's look at the flags -- waits for is queued first, the rows' part behind it; it starts beside the
+    // compaction either way.)
+    F.parts = 1;
+    launch_finalize(F, b->n_vcf, st);
+    HIPCHK(hipEventRecord(b->ev_flags, st));   // every VCF's flags are written
+    b->flags_recorded = true;
+    HIPCHK(hipEventRecord(b->ev_sync[0], st));
+    if (T) { HIPCHK(hipEventRecord(ev[4], st)); HIPCHK(hipEventRecord(ev[5], st)); }
+    launch_compact(compact_params(b), ns, st);
+    HIPCHK(hipStreamWaitEvent(c->aux, b->ev_sync[0], 0));
+    F.parts = 2;
+    launch_finalize(F, b->n_vcf, c->aux);
+    HIPCHK(hipEventRecord(b->ev_sync[1], c->aux));
+    if (T) HIPCHK(hipEventRecord(ev[6], st));
     HIPCHK(hipStreamWaitEvent(st, b->ev_sync[1], 0));   // the rows of k_finalize
   }
   if (T) { HIPCHK(hipEventRecord(ev[1], st)); b->n_timed++; }
@@ -897,12 +843,9 @@ extern "C" int qm_batch_timings(qm_batch* b, float* ms4) {
     hipEvent_t* ev = b->ev[slot];
     HIPCHK(hipEventSynchronize(ev[1]));
     float t;
-    for (int k = 0; k < b->ev_chunks[slot]; ++k) {   // kernel times add up over the ranges; compaction overlaps the next range's classification
-      hipEvent_t* e5 = ev + 2 + 5 * k;
-      HIPCHK(hipEventElapsedTime(&t, e5[0], e5[1])); acc[0] += t;
-      HIPCHK(hipEventElapsedTime(&t, e5[1], e5[2])); acc[1] += t;
-      HIPCHK(hipEventElapsedTime(&t, e5[3], e5[4])); acc[2] += t;
-    }
+    HIPCHK(hipEventElapsedTime(&t, ev[2], ev[3])); acc[0] += t;   // classify
+    HIPCHK(hipEventElapsedTime(&t, ev[3], ev[4])); acc[1] += t;   // finalize (the flags' part)
+    HIPCHK(hipEventElapsedTime(&t, ev[5], ev[6])); acc[2] += t;   // compact
     HIPCHK(hipEventElapsedTime(&t, ev[0], ev[1])); acc[3] += t;
   }
   for (int k = 0; k < 4; ++k) ms4[k] = (float)(acc[k] / n);
@@ -1382,7 +1325,7 @@ static int onelevel_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t s
   // workgroup's serial steps and wants every LDS slot of the chip: beside a scatter it only loses (3.06 ms in one piece
   // against 3.11 - 3.22 in 2 - 8 ranges, same box)
   int nbk_launch = nbk_all;
-  const int parts = nseg >= 8 && b->ev_sync[0] && !direct ? 4 : 1;
+  const int parts = nseg >= 8 && !direct ? qm_batch::JOIN_PARTS : 1;
   // The buckets above a VCF's highest position hold nothing, and a workgroup that finds its bucket empty has still held a slot of its
   // CU for a memory round trip: 40 % of the grid on a 5 Mb genome, whose position BITS (all the optimistic pass hands over) bound the
   // buckets in use only by 256 -- 0.09 of the step's 2.65 ms (same box).  The scatter notes the highest bucket it filled per segment
@@ -1422,8 +1365,8 @@ static int onelevel_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t s
     i0 = i1;
   }
   if (parts > 1) {
-    HIPCHK(hipEventRecord(b->ev_sync[qm_batch::MAX_CHUNKS + 1], aux));
-    HIPCHK(hipStreamWaitEvent(st, b->ev_sync[qm_batch::MAX_CHUNKS + 1], 0));
+    HIPCHK(hipEventRecord(b->ev_join, aux));
+    HIPCHK(hipStreamWaitEvent(st, b->ev_join, 0));
   }
   const bool mirrors = b->d_summary != nullptr && nseg <= b->n_vcf;   // (one segment per VCF on this path)
   // No round trip through the host between the rows' k_finalize and the kernels that hand the chunk's results over: they are queued
@@ -1871,11 +1814,11 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
   // goes onto the stream behind the bucket path without a round trip through the host in between
   const bool nothing_ran = b->run_used_known && b->n_known == b->n_vcf && b->h_summary != nullptr;
   // the flags (and their mirrors) are complete behind the k_finalize part that writes them: the wait is for that kernel, while the
-  // run's compaction and row sums go on -- the bucket path of what is found out of order is built and queued beside them
-  // (QM_FLAGS_WAIT=stream: wait for everything, as rounds 1-4 did)
+  // run's compaction and row sums go on -- the bucket path of what is found out of order is built and queued beside them.
+  // Without the mirrors the flags are copied back: the wait is for the whole stream.
   bool idle = nothing_ran;   // has the stream been waited for?
   if (!nothing_ran) {
-    if (b->flags_recorded && b->h_summary && flags_event_on()) HIPCHK(hipEventSynchronize(b->ev_flags));
+    if (b->flags_recorded && b->h_summary) HIPCHK(hipEventSynchronize(b->ev_flags));
     else { HIPCHK(hipStreamSynchronize(st)); idle = true; }
   }
   if (ftrace) ft[1] = now_us();
@@ -2013,7 +1956,7 @@ extern "C" int qm_batch_get_global(qm_batch* b, uint64_t* out) {
   HIPCHK(hipMemcpy(out, b->last_global, (size_t)b->n_truth * 3 * (size_t)b->n_bins * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
-// dst[i] += src[i] for device arrays (qm_extract_files_ex adds the per-truth sums of its groups into the caller's buffer)
+// dst[i] += src[i] for device arrays (qm_extract_files_ex adds the per-truth sums of its batch into the caller's buffer)
 int qm_device_add_u64(qm_ctx* c, uint64_t* dst, const uint64_t* src, int64_t n) {
   if (!c || !dst || !src || n < 0) return fail(QM_E_INVAL, "qm_device_add_u64: bad arguments");
   HIPCHK(hipSetDevice(c->dev));

@@ -108,7 +108,7 @@ struct ClassifyParams {
   uint32_t* span_scal;  // [n_spans][8]
   int32_t n_bins;
   int32_t ext;     // allele-extended batch: k_classify<false, true> against the truth sets' extended tables
-  int32_t span_base;   // first span of this launch (the batch is run in a few span ranges so that compaction overlaps classification)
+  int32_t span_base;   // first span of this launch (the host runs the batch in one piece: 0)
   uint64_t* zero_acc;  // or null: the per-truth sums k_finalize adds to, cleared by the first wave of this launch (saves a memset node per run)
   int32_t zero_words;
   const uint8_t* known;   // or null: known[v] != 0 = an earlier run of this batch found VCF v out of order and its columns have not changed since:

@@ -114,7 +114,7 @@ struct PinnedArena {
 // One arena per context (= per device): calls on different contexts -- a thread and a context per GPU, examples/qm_multi.c --
 // tokenise, upload and write side by side; two calls on ONE context take turns.  The table itself is never destroyed: at
 // process exit the HIP runtime may be gone before static destructors run; qm_destroy releases a context's arena.
-struct CtxArena { PinnedArena arena[2]; std::mutex mu; };
+struct CtxArena { PinnedArena arena; std::mutex mu; };
 std::map<qm_ctx*, CtxArena*>& g_arenas = *new std::map<qm_ctx*, CtxArena*>();
 std::mutex* g_arenas_mu = new std::mutex();
 CtxArena* arena_of(qm_ctx* ctx) {
@@ -163,7 +163,7 @@ void qm_pipeline_ctx_destroyed(qm_ctx* ctx) {
     auto it = g_arenas.find(ctx);
     if (it != g_arenas.end()) { a = it->second; g_arenas.erase(it); }
   }
-  if (a) { { std::lock_guard<std::mutex> g(a->mu); a->arena[0].release(); a->arena[1].release(); } delete a; }
+  if (a) { { std::lock_guard<std::mutex> g(a->mu); a->arena.release(); } delete a; }
 }
 
 extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
@@ -185,8 +185,7 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
   }
   const bool ext = (mode & QM_BATCH_ALLELES) != 0;
   // map + count, truth sets (beside the former), batch layout, tokenise + host path (+ uploads beside it), engine, masks back,
-  // write, release -- summed over the groups of the pipeline below (stages of different groups overlap, so the sum of the
-  // phases exceeds the wall time of the call)
+  // write, release (the truth sets overlap the first phases, so the sum of the phases exceeds the wall time of the call)
   double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, phc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::mutex ph_mu;
   const bool trace = getenv("QM_FILES_TRACE") != nullptr;
@@ -202,53 +201,19 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
   qm_dict* dict = ext ? qm_dict_create() : nullptr;
   std::vector<TruthState> T;
 
-  // ---- groups: the VCFs CAN go through a two-stage pipeline, group after group -- while group g is on the engine and its
-  //      files are being written (a thread of its own, fanning out over the host threads), group g + 1 is mapped, tokenised
-  //      and uploaded.  Measured (round 3, 16 VCFs of 10^6 lines, profiles/r03_e2e_groups.log): 83 ms in one group, 86 / 108 /
-  //      142 ms in 2 / 4 / 6 -- every stage parallelises over FILES (one thread counts a file, one thread writes an output
-  //      file), so a stage takes as long as its slowest file however few files it holds, and smaller groups only idle
-  //      threads.  The default is therefore ONE group (QM_FILES_GROUPS / QM_FILES_GROUP_MB for experiments); what would make
-  //      groups pay is parallelism INSIDE a file in the count and in the writers.
-  struct Group {
-    std::vector<int> jobs;             // indices into `jobs`, ascending
-    qm_batch* batch = nullptr;
-    std::vector<int64_t> nrec;
-    std::vector<int32_t> tids;
-    hipStream_t copy_stream = nullptr;
-    std::vector<int64_t> scal;
-    std::vector<uint64_t> roc;
-    int rc = QM_OK;
-    std::string err;
-  };
-  std::vector<Group> G;
-  {
-    int64_t total = 0;
-    std::vector<int64_t> sz((size_t)n_jobs, 0);
-    for (int j = 0; j < n_jobs; ++j) { struct stat st; if (stat(jobs[j].vcf_path, &st) == 0) sz[(size_t)j] = (int64_t)st.st_size; total += sz[(size_t)j]; }
-    int want = 1;
-    if (const char* e = getenv("QM_FILES_GROUPS")) want = std::max(1, atoi(e));
-    want = std::min(want, n_jobs);
-    G.resize((size_t)want);
-    int64_t acc = 0;
-    int g = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-      while (g + 1 < want && acc >= total * (g + 1) / want && !G[(size_t)g].jobs.empty()) ++g;
-      G[(size_t)g].jobs.push_back(j);
-      acc += sz[(size_t)j];
-    }
-    while (!G.empty() && G.back().jobs.empty()) G.pop_back();
-  }
-  // The context is not made for two threads: with more than one group (QM_FILES_GROUPS / QM_FILES_GROUP_MB; experimental, the
-  // default is one) stage one of group g + 1 runs beside stage two of group g, so whatever touches the context's streams and
-  // truth tables -- batch creation there, run / finish / row read-back here -- takes turns.  (The uploads of the tokenizer
-  // threads write their own batch through a stream of its own.)
-  std::mutex engine_mu;
+  // ---- the VCFs go through as ONE batch: stage one (map, count, tokenise, upload) of every VCF, then stage two (engine,
+  //      masks, files).  A pipeline of groups -- stage two of group g on a thread of its own beside stage one of group g + 1 --
+  //      was slower: 83 ms in one group, 86 / 108 / 142 ms in 2 / 4 / 6 (round 3, 16 VCFs of 10^6 lines; LABNOTES.md): every
+  //      stage parallelises over files, so smaller groups only idle threads.
+  qm_batch* batch = nullptr;        // the VCFs with a truth set, in job order
+  std::vector<int64_t> nrec;
+  std::vector<int32_t> tids;
+  hipStream_t copy_stream = nullptr;
   std::thread truth_thread;   // ends with the patterns of the truth files
-  std::thread stage2;         // engine + masks + files of the group before the one being tokenised
   auto cleanup = [&]() {
-    if (stage2.joinable()) stage2.join();
     if (truth_thread.joinable()) truth_thread.join();
-    for (auto& g : G) { if (g.batch) { qm_batch_destroy(g.batch); g.batch = nullptr; } if (g.copy_stream) { (void)hipStreamDestroy(g.copy_stream); g.copy_stream = nullptr; } }
+    if (batch) { qm_batch_destroy(batch); batch = nullptr; }
+    if (copy_stream) { (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
     for (auto& t : T) { if (t.pats) qm_patterns_destroy(t.pats); if (t.tid >= 0) (void)qm_truth_release(ctx, t.tid); }
     if (dict) qm_dict_destroy(dict);
   };
@@ -321,14 +286,12 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
   auto wait_patterns = [&]() { std::unique_lock<std::mutex> g(pats_mu); pats_cv.wait(g, [&] { return pats_ready; }); };
 
   CtxArena* const ca = arena_of(ctx);
-  std::unique_lock<std::mutex> arena_lock(ca->mu);   // one call at a time per context uses its page-locked arenas
+  std::unique_lock<std::mutex> arena_lock(ca->mu);   // one call at a time per context uses its page-locked arena
 
-  // ---- stage 1 of a group: map + count, batch layout, tokenise + host path + uploads ----
-  auto stage_one = [&](Group& gr, int gi) -> int {
-    const int ng = (int)gr.jobs.size();
+  // ---- stage 1: map + count, batch layout, tokenise + host path + uploads ----
+  auto stage_one = [&]() -> int {
     double t0 = now(), c0 = trace ? cpu_now() : 0.0;
-    parallel_for(ng, nthr, [&](int k) {
-      const int j = gr.jobs[(size_t)k];
+    parallel_for(n_jobs, nthr, [&](int j) {
       JobState& s = J[(size_t)j];
       s.vcf.open_file(jobs[j].vcf_path);
       if (!s.vcf.ok) { s.rc = QM_E_IO; return; }
@@ -338,35 +301,33 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
     });
     add_ph(0, now() - t0, trace ? cpu_now() - c0 : 0.0);
     { std::unique_lock<std::mutex> g(pats_mu); pats_cv.wait(g, [&] { return keys_ready; }); }   // the thread itself ends with the patterns
-    for (int j : gr.jobs)
+    for (int j = 0; j < n_jobs; ++j)
       if (J[(size_t)j].rc != QM_OK) return fail(QM_E_IO, std::string("cannot read ") + jobs[j].vcf_path);
     if (truth_rc != QM_OK) return fail(truth_rc, truth_msg);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
-    for (int j : gr.jobs)
-      if (!jobs[j].pure) { J[(size_t)j].batch_v = (int)gr.nrec.size(); gr.nrec.push_back(J[(size_t)j].n_data); gr.tids.push_back(T[(size_t)J[(size_t)j].truth].tid); }
-    if (!gr.nrec.empty()) {
-      std::lock_guard<std::mutex> eg(engine_mu);
-      const int rc = qm_batch_create_ext(ctx, (int)gr.nrec.size(), gr.nrec.data(), gr.tids.data(), n_bins, mode, &gr.batch);
+    for (int j = 0; j < n_jobs; ++j)
+      if (!jobs[j].pure) { J[(size_t)j].batch_v = (int)nrec.size(); nrec.push_back(J[(size_t)j].n_data); tids.push_back(T[(size_t)J[(size_t)j].truth].tid); }
+    if (!nrec.empty()) {
+      const int rc = qm_batch_create_ext(ctx, (int)nrec.size(), nrec.data(), tids.data(), n_bins, mode, &batch);
       if (rc != QM_OK) return rc;
     }
     size_t need = 0;
-    std::vector<size_t> aoff((size_t)ng);
-    for (int k = 0; k < ng; ++k) {
-      aoff[(size_t)k] = need;
-      const size_t cap = (size_t)J[(size_t)gr.jobs[(size_t)k]].n_lines + 1;
+    std::vector<size_t> aoff((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+      aoff[(size_t)j] = need;
+      const size_t cap = (size_t)J[(size_t)j].n_lines + 1;
       need += ((cap * 17 + 255) & ~(size_t)255) + ((((cap + 63) / 64) * 16 + 255) & ~(size_t)255);
     }
-    uint8_t* arena = ca->arena[gi & 1].get(need);   // two arenas take turns: group g - 2 has been written by now
+    uint8_t* arena = ca->arena.get(need);
     if (!arena) return fail(QM_E_NOMEM, "qm_extract_files: no memory for the column buffers");
-    if (hipStreamCreateWithFlags(&gr.copy_stream, hipStreamNonBlocking) != hipSuccess) return fail(QM_E_HIP, "hipStreamCreate failed");
+    if (hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess) return fail(QM_E_HIP, "hipStreamCreate failed");
     add_ph(2, now() - t0, trace ? cpu_now() - c0 : 0.0);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
-    const int per_file_threads = std::max(1, nthr / std::max(1, std::min(ng, nthr)));
-    parallel_for(ng, nthr, [&](int k) {
-      const int j = gr.jobs[(size_t)k];
+    const int per_file_threads = std::max(1, nthr / std::max(1, std::min(n_jobs, nthr)));
+    parallel_for(n_jobs, nthr, [&](int j) {
       JobState& s = J[(size_t)j];
       const size_t cap = (size_t)s.n_lines + 1;
-      uint8_t* a = arena + aoff[(size_t)k];
+      uint8_t* a = arena + aoff[(size_t)j];
       s.pos = (int32_t*)a; s.ref = s.pos + cap; s.alt = s.ref + cap; s.qual = (float*)(s.alt + cap); s.flags = (uint8_t*)(s.qual + cap);
       s.kept = (uint64_t*)(a + ((cap * 17 + 255) & ~(size_t)255)); s.tp = s.kept + (cap + 63) / 64;
       s.line_off.resize(cap + 1);
@@ -388,7 +349,7 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
         if (s.rc != QM_OK) s.err = "the host path (fgrep -w on the text) failed";
       }
       if (s.rc == QM_OK && !(strict && s.info.n_refused)) {
-        s.rc = qm_batch_upload_async(gr.batch, s.batch_v, s.pos, s.ref, s.alt, s.qual, s.flags, gr.copy_stream);
+        s.rc = qm_batch_upload_async(batch, s.batch_v, s.pos, s.ref, s.alt, s.qual, s.flags, copy_stream);
         if (s.rc != QM_OK) s.err = qm_last_error(ctx);   // this thread's message: the caller's thread would not see it
       }
     });
@@ -399,8 +360,7 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
       if (t.rc != QM_OK) rc = fail(t.rc, "cannot take the patterns of truth file " + t.path);
       else if (strict && t.info[3] > 0) rc = fail(QM_E_NONCANON, t.path + ": " + std::to_string(t.info[3]) + " truth rows hold NUL or non-ASCII bytes");
     }
-    for (int k = 0; k < ng && rc == QM_OK; ++k) {
-      const int j = gr.jobs[(size_t)k];
+    for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
       const JobState& s = J[(size_t)j];
       if (s.rc != QM_OK) rc = fail(s.rc, std::string("tokenising / uploading failed for ") + jobs[j].vcf_path + (s.err.empty() ? "" : ": " + s.err));
       else if (strict && s.info.n_refused)
@@ -408,52 +368,50 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
                                      ": a kept line holds NUL or non-ASCII bytes -- the reference's answer for it depends on the locale "
                                      "Python exports to grep; set QM_LENIENT=1 to classify it by its columns");
     }
-    if (hipStreamSynchronize(gr.copy_stream) != hipSuccess && rc == QM_OK) rc = fail(QM_E_HIP, "upload failed");
+    if (hipStreamSynchronize(copy_stream) != hipSuccess && rc == QM_OK) rc = fail(QM_E_HIP, "upload failed");
     add_ph(3, now() - t0, trace ? cpu_now() - c0 : 0.0);
     return rc;
   };
 
-  // ---- stage 2 of a group (a thread of its own): the engine, the class masks back, the three files of every VCF, the rows ----
-  auto stage_two = [&](Group& gr) {
+  // ---- stage 2: the engine, the class masks back, the three files of every VCF, the rows ----
+  auto stage_two = [&](std::string& err) -> int {
     int rc = QM_OK;
     double t0 = now(), c0 = trace ? cpu_now() : 0.0;
-    if (gr.batch) {
-      std::lock_guard<std::mutex> eg(engine_mu);
-      rc = qm_batch_run(gr.batch, nullptr, nullptr);
-      if (rc == QM_OK) rc = qm_batch_finish(gr.batch, nullptr);
-      gr.scal.resize(gr.nrec.size() * QM_N_SCALARS);
-      gr.roc.resize(gr.nrec.size() * 3 * (size_t)n_bins);
-      if (rc == QM_OK) rc = qm_batch_get_scalars(gr.batch, gr.scal.data());
-      if (rc == QM_OK) rc = qm_batch_get_roc(gr.batch, gr.roc.data());
+    std::vector<int64_t> scal(nrec.size() * QM_N_SCALARS);
+    std::vector<uint64_t> roc(nrec.size() * 3 * (size_t)n_bins);
+    if (batch) {
+      rc = qm_batch_run(batch, nullptr, nullptr);
+      if (rc == QM_OK) rc = qm_batch_finish(batch, nullptr);
+      if (rc == QM_OK) rc = qm_batch_get_scalars(batch, scal.data());
+      if (rc == QM_OK) rc = qm_batch_get_roc(batch, roc.data());
       if (rc == QM_OK && global_dev) {
         // the per-truth-set sums as the engine left them in HBM, row by row ADDED into the caller's layout: what a multi-GPU
         // caller all-reduces (device to device: the counters never visit the host)
         void* src = nullptr;
-        rc = qm_batch_global_device(gr.batch, &src);
+        rc = qm_batch_global_device(batch, &src);
         const size_t roww = 3 * (size_t)n_bins;
         for (size_t k = 0; k < T.size() && rc == QM_OK; ++k) {
           if (slot_of_truth[k] < 0 || T[k].tid < 0) continue;
           rc = qm_device_add_u64(ctx, (uint64_t*)global_dev + (size_t)slot_of_truth[k] * roww, (const uint64_t*)src + (size_t)T[k].tid * roww, (int64_t)roww);
         }
       }
-      if (rc != QM_OK) gr.err = qm_last_error(ctx);
+      if (rc != QM_OK) err = qm_last_error(ctx);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
-    for (size_t k = 0; k < gr.jobs.size() && rc == QM_OK; ++k) {
-      const int j = gr.jobs[k];
+    for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
       JobState& s = J[(size_t)j];
       if (jobs[j].pure) continue;
-      rc = qm_batch_get_masks(gr.batch, s.batch_v, s.kept, s.tp);
-      if (rc != QM_OK) gr.err = qm_last_error(ctx);
+      rc = qm_batch_get_masks(batch, s.batch_v, s.kept, s.tp);
+      if (rc != QM_OK) err = qm_last_error(ctx);
     }
     add_ph(5, now() - t0, trace ? cpu_now() - c0 : 0.0);
-    if (gr.copy_stream) { (void)hipStreamDestroy(gr.copy_stream); gr.copy_stream = nullptr; }
-    if (rc != QM_OK) { gr.rc = rc; return; }
+    if (copy_stream) { (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
+    if (rc != QM_OK) return rc;
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
     struct WTask { int j, select; const char* path; bool pure; };
     std::vector<WTask> W;
-    for (int j : gr.jobs) {
+    for (int j = 0; j < n_jobs; ++j) {
       if (jobs[j].pure) { W.push_back({j, 0, jobs[j].filtered_out, true}); W.push_back({j, 0, jobs[j].fp_out, true}); }   // cp filtered fp (:33-36)
       else { W.push_back({j, 0, jobs[j].filtered_out, false}); W.push_back({j, 1, jobs[j].tp_out, false}); W.push_back({j, 2, jobs[j].fp_out, false}); }
     }
@@ -466,10 +424,10 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
                                            w.pure ? nullptr : s.kept, w.pure ? nullptr : s.tp, s.flags, w.select);
     });
     for (size_t k = 0; k < W.size(); ++k)
-      if (wrc[k] != QM_OK) { gr.rc = wrc[k]; gr.err = std::string("cannot write ") + W[k].path; return; }
+      if (wrc[k] != QM_OK) { err = std::string("cannot write ") + W[k].path; return wrc[k]; }
     add_ph(6, now() - t0, trace ? cpu_now() - c0 : 0.0);
     // per-VCF rows
-    for (int j : gr.jobs) {
+    for (int j = 0; j < n_jobs; ++j) {
       const JobState& s = J[(size_t)j];
       int64_t hk = 0, hk_tp = 0;
       for (int64_t i = 0; i < s.info.n_lines; ++i) { hk += s.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT || s.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT_TP; hk_tp += s.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT_TP; }
@@ -482,7 +440,7 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
           for (int64_t r = 0; r < s.n_data; ++r) np += s.flags[r] & QM_F_PASS;
           o.scalars[QM_S_NPASS] = np; o.scalars[QM_S_FP_LINES] = np; o.scalars[QM_S_SORTED] = 1; o.scalars[QM_S_NREC] = s.n_data;
         } else {
-          memcpy(o.scalars, &gr.scal[(size_t)s.batch_v * QM_N_SCALARS], sizeof o.scalars);
+          memcpy(o.scalars, &scal[(size_t)s.batch_v * QM_N_SCALARS], sizeof o.scalars);
           // R keys a line by the TEXT of POS / REF / ALT; for lines without a comparable key the device counted distinct
           // (carried pos, ref, alt) instead: swap those for the text keys (qm_vcf_hostpath)
           o.scalars[QM_S_FP_R] += s.ex[4] - s.ex[2];
@@ -493,29 +451,23 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
       if (roc_out) {
         uint64_t* dst = roc_out + (size_t)j * 3 * (size_t)n_bins;
         if (jobs[j].pure) memset(dst, 0, sizeof(uint64_t) * 3 * (size_t)n_bins);
-        else memcpy(dst, &gr.roc[(size_t)s.batch_v * 3 * (size_t)n_bins], sizeof(uint64_t) * 3 * (size_t)n_bins);
+        else memcpy(dst, &roc[(size_t)s.batch_v * 3 * (size_t)n_bins], sizeof(uint64_t) * 3 * (size_t)n_bins);
       }
     }
-    // the group is done: its batch, its mappings and its line tables go while the next group is at work
+    // done: the batch, the mappings and the line tables go
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
-    if (gr.batch) { qm_batch_destroy(gr.batch); gr.batch = nullptr; }
+    if (batch) { qm_batch_destroy(batch); batch = nullptr; }
     const double t1 = now();
-    parallel_for((int)gr.jobs.size(), nthr, [&](int k) { JobState tmp = std::move(J[(size_t)gr.jobs[(size_t)k]]); (void)tmp; });   // unmap / free in parallel
+    parallel_for(n_jobs, nthr, [&](int j) { JobState tmp = std::move(J[(size_t)j]); (void)tmp; });   // unmap / free in parallel
     if (getenv("QM_FILES_TRACE")) fprintf(stderr, "release: batch destroy %.2f ms, unmap + free %.2f ms\n", (t1 - t0) * 1e3, (now() - t1) * 1e3);
     add_ph(7, now() - t0, trace ? cpu_now() - c0 : 0.0);
+    return QM_OK;
   };
 
-  int rc = QM_OK;
   std::string msg;
-  for (size_t g = 0; g < G.size() && rc == QM_OK; ++g) {
-    rc = stage_one(G[g], (int)g);
-    if (rc != QM_OK) msg = qm_last_error(ctx);
-    if (stage2.joinable()) stage2.join();          // group g - 1 is written (and its arena free for group g + 1)
-    if (g > 0 && rc == QM_OK && G[g - 1].rc != QM_OK) { rc = G[g - 1].rc; msg = G[g - 1].err; }
-    if (rc == QM_OK) stage2 = std::thread(stage_two, std::ref(G[g]));
-  }
-  if (stage2.joinable()) stage2.join();
-  if (rc == QM_OK) for (auto& g : G) if (g.rc != QM_OK) { rc = g.rc; msg = g.err; break; }
+  int rc = stage_one();
+  if (rc != QM_OK) msg = qm_last_error(ctx);
+  else rc = stage_two(msg);
   cleanup();
   if (rc != QM_OK) return fail(rc, msg);
   if (phase_seconds) memcpy(phase_seconds, ph, sizeof ph);

@@ -254,11 +254,12 @@ def test_every_knob_the_sources_read_is_named_in_integration_md():
         read |= set(re.findall(r'environ[^\n"]*"(QM_[A-Z0-9_]+)"', open(f).read()))
     missing = sorted(k for k in read if k not in named and not k.startswith("QM_BENCH_"))
     assert not missing, "not named in INTEGRATION.md: %s" % ", ".join(missing)
-    # round 6 cut the library's knobs to those a user or a test needs: the count is part of the contract (<= 20)
+    # round 6 cut the library's knobs to those a user or a test needs, and the execution modes measured slower than the
+    # default went later: the count is part of the contract (<= 20), so a removed knob cannot come back unnoticed
     lib = set()
     for f in glob.glob(os.path.join(root, "quasimodo_amd", "csrc", "*.[ch]*")):
         lib |= set(re.findall(r'getenv\("(QM_[A-Z0-9_]+)"\)', open(f, errors="replace").read()))
-    assert len(lib) <= 20, sorted(lib)
+    assert len(lib) <= 11, sorted(lib)
     # ... and the shipped kernels compile ONE way: no ablation / profiling conditionals, only #ifndef defaults of tuning constants
     ksrc = open(os.path.join(root, "quasimodo_amd", "csrc", "qmvt_kernels.hip")).read()
     conds = re.findall(r"^#\s*(?:if|ifdef|elif)\b.*$", ksrc, flags=re.M)

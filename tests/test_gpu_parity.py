@@ -58,13 +58,11 @@ def test_ragged_sorted_batch(engine, oracle, seed):
         assert np.array_equal(glob[tids[w]], want)
 
 
-@pytest.mark.parametrize("chunks", [2, 4, 8])
-def test_pipelined_ranges_give_the_same_answers(engine, oracle, monkeypatch, chunks):
-    """qm_batch_run works through the batch in a few ranges of VCFs, the compaction of one range on a second stream
-    beside the classification of the next.  Forced here on a small ragged batch (the default only splits batches
-    that fill the chip several times over), sorted and unsorted VCFs mixed, run twice back to back."""
-    monkeypatch.setenv("QM_PIPE_CHUNKS", str(chunks))      # (a test knob: the ranges asked for, however small the batch)
-    rng = np.random.default_rng(500 + chunks)
+def test_ragged_batch_run_twice_with_timing_gives_the_same_answers(engine, oracle):
+    """qm_batch_run queues the compaction on the main stream and the rows' k_finalize on the context's second stream.  A small
+    ragged batch (empty and one-record VCFs, sizes either side of the bucket path's 16 384), sorted and unsorted VCFs mixed,
+    run twice back to back with timing on, agrees with the oracle."""
+    rng = np.random.default_rng(502)
     L = 90000
     truth = random_truth(rng, 3000, L)
     tid = engine.truth_load(*truth)
@@ -1221,14 +1219,15 @@ def test_positions_above_what_the_optimistic_pass_saw(engine, oracle):
     b.close()
 
 
-@pytest.mark.parametrize("knobs", [{}, {"QM_SPECULATE": "0"}, {"QM_FLAGS_WAIT": "stream"}, {"QM_NO_MIRRORS": "1"}],
-                         ids=["queued", "looked-at", "round-4-waits", "no-host-mapped-mirrors"])
+@pytest.mark.parametrize("knobs", [{}, {"QM_SPECULATE": "0"}, {"QM_NO_MIRRORS": "1"}],
+                         ids=["queued", "looked-at", "no-host-mapped-mirrors"])
 def test_several_bucket_chunks_in_one_finish_one_of_which_does_not_fit(engine, oracle, monkeypatch, knobs):
     """qm_batch_finish queues the last kernels of a bucket chunk without looking at the chunk's flags first (a round trip through
     the host per chunk) and settles all chunks behind its last wait: a chunk whose buckets did not fit must not have added its
     rows to the per-truth sums, goes through the radix sort then, and the compaction runs again.  Five unsorted VCFs in five
     chunks (QM_SORT_CHUNK_RECORDS), the third of them 60 000 records on 16 positions; twice, the second time with the batch's
-    memory of the first; the knobs switch the round trips of round 4 back on, one by one."""
+    memory of the first; the knobs switch the round trips of round 4 back on: the look at a chunk's flags before its last
+    kernels, and (without the mirrors) the wait for the whole stream before the flags are read."""
     from conftest import random_columns, random_truth
     from quasimodo_amd.engine import SCALAR_NAMES
     for k, v in knobs.items():
