@@ -380,6 +380,9 @@ struct qm_batch {
   int32_t *pos = nullptr, *ref = nullptr, *alt = nullptr;
   float* qual = nullptr;
   uint8_t* flags = nullptr;
+  // batches without QM_BATCH_ALLELES: allele_byte(ref, alt) per record (qmvt_dev.h), what the kernels read instead of the two
+  // codes; every writer of ref / alt keeps it up to date
+  uint8_t* anib = nullptr;
   // outputs / workspace
   uint64_t *mask_pass = nullptr, *mask_tp = nullptr;
   int32_t* idx = nullptr;
@@ -515,7 +518,7 @@ static void batch_free(qm_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->ctx->dev);
   if (b->sub) { batch_free(b->sub); b->sub = nullptr; }
-  void* ptrs[] = {b->pkey, b->pinf, b->pos, b->ref, b->alt, b->qual, b->flags, b->mask_pass, b->mask_tp, b->idx, b->tile_tp, b->tile_fp,
+  void* ptrs[] = {b->pkey, b->pinf, b->pos, b->ref, b->alt, b->qual, b->flags, b->anib, b->mask_pass, b->mask_tp, b->idx, b->tile_tp, b->tile_fp,
                   b->tile_tp_off, b->tile_fp_off, b->vcf_tot, b->span_hist, b->span_scal, b->vcf_flags, b->vcf_posor, b->bk_hist, b->bk_scal, b->d_bk_vcfs, b->bk_ent, b->bk_cursor, b->d_bk_tile_seg, b->bk_rows, b->bk_xent, b->bk_xcursor, b->bk_xrows, b->bk_roc, b->bk_rscal, b->bk_vflags, b->p_segs, b->p_tile_seg, b->p_cnt, b->p_off, b->p_half, b->p_cursor, b->p_flags, b->p_ent, b->d_vsegs, b->d_vparts, b->rs_roc, b->rs_scal, b->rs_flags, b->roc, b->global_acc,
                   b->scalars, b->d_vcfs, b->d_spans, b->d_tile_vcf, b->cls_scratch, b->sk[0], b->sk[1], b->sv[0],
                   b->sv[1], b->si[0], b->si[1], b->shist, b->sorbits, b->d_segs, b->d_tile_seg, b->d_ktile_seg, b->d_ktile_local, b->d_known};
@@ -537,7 +540,7 @@ static int upload_layout(qm_batch* b) {
 }
 
 static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int32_t* truth_ids, int n_bins, qm_batch** out,
-                       bool packed = false, bool packed_alleles = false) {
+                       bool packed = false, bool packed_alleles = false, bool alleles = false) {
   qm_batch* b = new qm_batch();
   b->ctx = c;
   b->n_vcf = n_vcf;
@@ -559,7 +562,10 @@ static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int
     A_(b->pkey, np) A_(b->pinf, np)
     if (packed_alleles) { A_(b->ref, np) A_(b->alt, np) }   // sorted copies of the allele codes
   }
-  else { A_(b->pos, np) A_(b->ref, np) A_(b->alt, np) A_(b->qual, np) A_(b->flags, np) }
+  else {
+    A_(b->pos, np) A_(b->ref, np) A_(b->alt, np) A_(b->qual, np) A_(b->flags, np)
+    if (!alleles) A_(b->anib, np)
+  }
   A_(b->mask_pass, np / 64 + 64) A_(b->mask_tp, np / 64 + 64) A_(b->idx, np)
   A_(b->tile_tp, b->cap_tiles) A_(b->tile_fp, b->cap_tiles) A_(b->tile_tp_off, b->cap_tiles + SPAN_TILES) A_(b->tile_fp_off, b->cap_tiles + SPAN_TILES) A_(b->vcf_tot, (size_t)n_vcf * 2)
   A_(b->span_hist, b->cap_spans * SPAN_HIST_WORDS) A_(b->span_scal, b->cap_spans * 8) A_(b->vcf_flags, (size_t)n_vcf) A_(b->vcf_posor, (size_t)n_vcf)
@@ -581,6 +587,7 @@ static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int
     if (e == hipSuccess) e = hipMemsetAsync(b->ref, 0, np * 4, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(b->alt, 0, np * 4, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(b->qual, 0, np * 4, c->stream);
+    if (e == hipSuccess && b->anib) e = hipMemsetAsync(b->anib, 0, np, c->stream);   // = allele_byte(0, 0)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = fail(QM_E_HIP, "hipMemset: %s", hipGetErrorString(e));
   }
@@ -614,7 +621,7 @@ extern "C" int qm_batch_create_ext(qm_ctx* c, int n_vcf, const int64_t* n_record
       return fail(QM_E_INVAL, "qm_batch_create: VCF %d names truth set %d (have %zu)", v, truth_id_per_vcf[v], c->truths.size());
   }
   HIPCHK(hipSetDevice(c->dev));
-  int rc = batch_alloc(c, n_vcf, n_records, truth_id_per_vcf, n_bins, out);
+  int rc = batch_alloc(c, n_vcf, n_records, truth_id_per_vcf, n_bins, out, false, false, (mode & QM_BATCH_ALLELES) != 0);
   if (rc == QM_OK) (*out)->ext = (mode & QM_BATCH_ALLELES) != 0;
   return rc;
 }
@@ -640,6 +647,11 @@ extern "C" int qm_batch_upload(qm_batch* b, int v, const int32_t* pos, const int
   HIPCHK(hipMemcpy(b->alt + d.off, alt, n * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(b->qual + d.off, qual, n * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(b->flags + d.off, flags, n, hipMemcpyHostToDevice));
+  if (b->anib) {   // the allele bytes from the codes just copied, complete when this returns (as the copies are)
+    launch_allele_byte(b->ref + d.off, b->alt + d.off, b->anib + d.off, d.n, b->ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->ctx->stream));
+  }
   b->ran = b->finished = false;
   forget_known(b, v);
   return QM_OK;
@@ -661,6 +673,10 @@ extern "C" int qm_batch_upload_async(qm_batch* b, int v, const int32_t* pos, con
   HIPCHK(hipMemcpyAsync(b->alt + d.off, alt, n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(b->qual + d.off, qual, n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(b->flags + d.off, flags, n, hipMemcpyHostToDevice, st));
+  if (b->anib) {   // the allele bytes, queued behind the copies on the same stream
+    launch_allele_byte(b->ref + d.off, b->alt + d.off, b->anib + d.off, d.n, st);
+    HIPCHK(hipGetLastError());
+  }
   b->ran = b->finished = false;
   forget_known(b, v);
   return QM_OK;
@@ -680,7 +696,7 @@ extern "C" int qm_batch_synth(qm_batch* b, const qm_synth_cfg* cfg) {
     return fail(QM_E_INVAL, "qm_batch_synth: need truth_n | genome_len < 2^28");
   HIPCHK(hipSetDevice(b->ctx->dev));
   SynthParams S;
-  S.vcfs = b->d_vcfs; S.pos = b->pos; S.ref = b->ref; S.alt = b->alt; S.qual = b->qual; S.flags = b->flags;
+  S.vcfs = b->d_vcfs; S.pos = b->pos; S.ref = b->ref; S.alt = b->alt; S.qual = b->qual; S.flags = b->flags; S.anib = b->anib;
   S.genome_len = cfg->genome_len; S.truth_n = cfg->truth_n; S.truth_seed = cfg->truth_seed; S.seed = cfg->seed;
   S.per_vcf_truth = 0;
   if (cfg->truth_seed == QM_SYNTH_TRUTH_PER_VCF) {
@@ -721,7 +737,7 @@ extern "C" int qm_batch_synth(qm_batch* b, const qm_synth_cfg* cfg) {
 
 static ClassifyParams classify_params(qm_batch* b) {
   ClassifyParams P;
-  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.qual = b->qual; P.flags = b->flags;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.qual = b->qual; P.flags = b->flags; P.anib = b->anib;
   P.pkey = b->pkey; P.pinf = b->pinf;
   P.spans = b->d_spans; P.vcfs = b->d_vcfs; P.truths = b->ctx->d_truths;
   P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp; P.tile_tp = b->tile_tp; P.tile_fp = b->tile_fp;
@@ -1119,7 +1135,7 @@ static int vcf_segs(const qm_batch* b, const std::vector<int>& vs, const std::ve
 // The launch parameters of every bucket path, for the segment table in d_segs: cursors, entries, rows.  What differs is set by the
 // path itself: l1_ent / l1_half (two levels), pairs (partitions), seg_maxd (one level), H.zero.
 static void bucket_params(qm_batch* b, int nseg, bool xs, uint32_t* seg_hist, BucketScatterParams* S, HashParams* H) {
-  S->segs = b->d_segs; S->tile_seg = b->d_bk_tile_seg; S->pos = b->pos; S->ref = b->ref; S->alt = b->alt; S->qual = b->qual; S->flags = b->flags;
+  S->segs = b->d_segs; S->tile_seg = b->d_bk_tile_seg; S->pos = b->pos; S->ref = b->ref; S->alt = b->alt; S->qual = b->qual; S->flags = b->flags; S->anib = b->anib;
   S->cursor = b->bk_cursor; S->ent = b->bk_ent; S->mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); S->mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp);
   S->n_seg = nseg; S->n_bins = b->n_bins; S->tile_base = 0;
   S->xent = xs ? b->bk_xent : nullptr; S->xcursor = xs ? b->bk_xcursor : nullptr; S->ext = xs ? 1 : 0;
@@ -1228,7 +1244,7 @@ static int radix_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, 
   int npass = 1;
   while (4 + 8 * npass < 32 && (orbits >> (4 + 8 * npass)) != 0) ++npass;
   int cur = 0;
-  const SortCols src = {b->pos, b->ref, b->alt, b->qual, b->flags};
+  const SortCols src = {b->pos, b->ref, b->alt, b->qual, b->flags, b->anib};
   {
     const bool last = npass == 1;
     launch_sort_first_scatter(b->d_segs, b->d_tile_seg, nseg, nst, src, b->n_bins, b->ext ? 1 : 0, b->shist, last ? s->pkey : b->sk[0],
@@ -1475,7 +1491,7 @@ static int two_level_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t 
   HIPCHK(hipMemsetAsync(b->p_cursor, 0, (size_t)nh_all * NC * 4, st));
   HIPCHK(hipMemsetAsync(b->p_flags, 0, (size_t)nh_all * 4, st));
   PartParams PP;
-  PP.segs = b->p_segs; PP.tile_seg = b->p_tile_seg; PP.pos = b->pos; PP.ref = b->ref; PP.alt = b->alt; PP.qual = b->qual; PP.flags = b->flags;
+  PP.segs = b->p_segs; PP.tile_seg = b->p_tile_seg; PP.pos = b->pos; PP.ref = b->ref; PP.alt = b->alt; PP.qual = b->qual; PP.flags = b->flags; PP.anib = b->anib;
   PP.cnt = b->p_cnt; PP.off = b->p_off; PP.cursor = b->p_cursor; PP.segflags = b->p_flags; PP.ent = b->p_ent;
   PP.mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); PP.mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp); PP.n_seg = nh_all; PP.n_bins = b->n_bins;
   launch_part_hist(PP, (int)nt1, st);

@@ -52,6 +52,13 @@ __host__ __device__ inline uint32_t allele_nib(int32_t r, int32_t a) {
   const uint32_t ur = (uint32_t)r, ua = (uint32_t)a;
   return ((ur << 2) ^ ua ^ ((ur ^ ua) >> 4)) & 15u;
 }
+// The derived allele byte of a batch without QM_BATCH_ALLELES (qm_batch.anib): ref << 2 | alt when both codes are
+// single bases -- judged on the whole int32 codes --, 0x10 otherwise.  The kernels that read the single-base columns read this
+// byte instead of the two int32 codes; every writer of ref / alt keeps it equal to allele_byte(ref, alt).
+constexpr uint32_t ANIB_NONE = 0x10u;
+__host__ __device__ inline uint8_t allele_byte(int32_t r, int32_t a) {
+  return (uint32_t)(r | a) < 4u ? (uint8_t)(((uint32_t)r << 2) | (uint32_t)a) : (uint8_t)ANIB_NONE;
+}
 
 struct TruthDev {
   const uint32_t* keys;  // sorted distinct pos<<4 | ref<<2 | alt
@@ -95,6 +102,7 @@ struct ClassifyParams {
   const int32_t* alt;
   const float* qual;
   const uint8_t* flags;
+  const uint8_t* anib;    // batches without QM_BATCH_ALLELES: allele_byte(ref, alt), read instead of ref / alt
   const uint32_t* pkey;   // packed input (radix-sort path): key / info pairs instead of the five columns
   const uint32_t* pinf;
   const SpanDesc* spans;
@@ -234,6 +242,7 @@ struct PartParams {
   const int32_t* alt;
   const float* qual;
   const uint8_t* flags;
+  const uint8_t* anib;        // read instead of ref / alt (the two-level path takes no allele-extended batch)
   uint32_t* cnt;              // [n_seg][P2_PARTS * P2_SUBS] records per (partition, sub-region): the counting pass
   const uint32_t* off;        // [n_seg][P2_PARTS * P2_SUBS + 1] where each sub-region starts (entries from ent_off): the host's prefix sums
   uint32_t* cursor;           // [n_seg][P2_PARTS * P2_SUBS] entries written so far; zeroed before the launch
@@ -255,6 +264,7 @@ struct BucketScatterParams {
   const int32_t* alt;
   const float* qual;
   const uint8_t* flags;
+  const uint8_t* anib;        // !ext: read instead of ref / alt
   uint32_t* cursor;           // [n_seg][256][8] entries written so far, then [n_seg] flag words (SPANF_*); zeroed before the launch
   uint64_t* ent;
   uint32_t* mask_pass;        // main batch, as 32-bit words: the kept mask is written here, the TP mask cleared
@@ -335,7 +345,7 @@ struct HashParams {
   uint32_t* zero = nullptr;   // k_bucket_rows only, or null: n_zero words it clears on the way (the cursors, flags and counts of the scatter behind it:
   uint32_t n_zero = 0;        // one dispatch instead of a memset's two in front of every chunk)
 };
-struct SortCols { const int32_t* pos; const int32_t* ref; const int32_t* alt; const float* qual; const uint8_t* flags; };
+struct SortCols { const int32_t* pos; const int32_t* ref; const int32_t* alt; const float* qual; const uint8_t* flags; const uint8_t* anib; };   // anib: !ext
 
 struct SynthParams {
   const VcfDesc* vcfs;
@@ -344,6 +354,7 @@ struct SynthParams {
   int32_t* alt;
   float* qual;
   uint8_t* flags;
+  uint8_t* anib;           // or null (allele-extended batches)
   int64_t genome_len;
   int64_t truth_n;
   uint64_t truth_seed;
@@ -432,6 +443,7 @@ void launch_finalize(const FinalizeParams& P, int n_vcf, hipStream_t st);
 void launch_compact(const CompactParams& P, int n_spans, hipStream_t st);
 void launch_masks_to_cls(const uint64_t* mp, const uint64_t* mt, int64_t off, int64_t n, uint8_t* cls, hipStream_t st);
 void launch_synth(const SynthParams& S, int n_vcf, int64_t max_n, hipStream_t st);
+void launch_allele_byte(const int32_t* ref, const int32_t* alt, uint8_t* anib, int64_t n, hipStream_t st);   // records 0 .. n - 1
 void launch_classify_hash(const HashParams& P, int nseg, hipStream_t st);   // segments P.seg_base .. + nseg
 void launch_bucket_rows(const HashParams& P, int nseg, hipStream_t st);
 void launch_join_ext(const HashParams& P, int nseg, int nbk, hipStream_t st);     // the second stream of an allele-extended batch

@@ -108,25 +108,25 @@ constexpr uint32_t I_KEPT = 1u << 16;    // live and PASS: the line is in <x>.fi
 constexpr uint32_t I_IDDOT4 = 1u << 20;  // copy of I_IDDOT
 constexpr uint32_t I_TPLINE = 1u << 24;  // flags bit3: the host found the line selected by fgrep (a TP line whatever its key says)
 
-// key and info of one record from its columns (qmvt_dev.h: the radix-sort path uses the same)
-// EXT (allele-extended batches, include/qmvt.h "allele codes"): any valid allele code is live; the
-// key's nibble is ref << 2 | alt for single bases and a hash of the two codes otherwise, so key
-// equality is necessary and (key, ref, alt) equality is the match.
-template <bool EXT = false>
-__device__ __forceinline__ void pack_record(int p, int r, int a, float q, uint32_t fl, int nb, uint32_t& key, uint32_t& inf) {
+// key and info of one record from its columns (qmvt_dev.h: the radix-sort path uses the same), given whether its alleles
+// take part and the key's nibble: pack_record reads them off the allele byte (qmvt_dev.h allele_byte), pack_record_ext off
+// the two codes (allele-extended batches, include/qmvt.h "allele codes": any valid allele code is live; the key's nibble is
+// ref << 2 | alt for single bases and a hash of the two codes otherwise, so key equality is necessary and (key, ref, alt)
+// equality is the match).
+__device__ __forceinline__ void pack_record_nib(int p, bool alive, uint32_t nib, float q, uint32_t fl, int nb, uint32_t& key, uint32_t& inf) {
   const bool okpos = (uint32_t)p < (uint32_t)QM_POS_LIMIT_DEV;
-  bool live;
-  uint32_t nib;
-  if (EXT) {
-    live = okpos && allele_valid(r) && allele_valid(a);
-    nib = allele_nib(r, a);
-  } else {
-    live = okpos & ((uint32_t)(r | a) < 4u);
-    nib = ((uint32_t)r << 2) | (uint32_t)a;
-  }
+  const bool live = okpos && alive;
   key = ((uint32_t)p << 4) | (live ? nib : 0u);
   inf = (live ? (uint32_t)(qual_bin(q, nb) + 1) : 0u) | ((fl & 7u) << 9) | (live ? I_LIVE : 0u) | (okpos ? 0u : I_BADPOS) |
         ((live && (fl & QMF_PASS)) ? I_KEPT : 0u) | ((fl & QMF_IDDOT) ? I_IDDOT4 : 0u) | ((live && (fl & QMF_TPLINE)) ? I_TPLINE : 0u);
+}
+// d: the allele byte in bits 0..7 (what lies above them is ignored, as with fl)
+__device__ __forceinline__ void pack_record(int p, uint32_t d, float q, uint32_t fl, int nb, uint32_t& key, uint32_t& inf) {
+  d &= 0xffu;
+  pack_record_nib(p, d < 16u, d, q, fl, nb, key, inf);
+}
+__device__ __forceinline__ void pack_record_ext(int p, int r, int a, float q, uint32_t fl, int nb, uint32_t& key, uint32_t& inf) {
+  pack_record_nib(p, allele_valid(r) && allele_valid(a), allele_nib(r, a), q, fl, nb, key, inf);
 }
 
 // The flag byte's part of the info word: PASS / IDDOT / NOKEY to bits 9..11, PASS, IDDOT and TPLINE again to the nibble
@@ -135,15 +135,13 @@ __host__ __device__ inline uint32_t flag_info(uint32_t f) {
   return ((f & 7u) << 9) | I_LIVE | ((f & QMF_PASS) ? I_KEPT : 0u) | ((f & QMF_IDDOT) ? I_IDDOT4 : 0u) | ((f & QMF_TPLINE) ? I_TPLINE : 0u);
 }
 
-// The same key and info as pack_record<false> for a record that is in range (out-of-range positions are collected by
-// the caller in one OR over the round), written for the VALU-bound main loop: 15 vector instructions and one LDS
-// read per record.  bin + 1 = min(floor(max(q, -1)), n_bins - 1) + 1 (NaN -> 0); flut = the flag_info table in LDS.
-__device__ __forceinline__ void pack_record_fast(int p, int r, int a, float q, uint32_t f4x4 /* flag byte index * 4 */, float nbm1f,
+// The same key and info as pack_record for a record that is in range (out-of-range positions are collected by the caller
+// in one OR over the round), written for the VALU-bound main loop: one LDS read per record.  d = the allele byte (0..255);
+// bin + 1 = min(floor(max(q, -1)), n_bins - 1) + 1 (NaN -> 0); flut = the flag_info table in LDS.
+__device__ __forceinline__ void pack_record_fast(int p, uint32_t d, float q, uint32_t f4x4 /* flag byte index * 4 */, float nbm1f,
                                                  const uint32_t* flut, uint32_t& key, uint32_t& inf) {
-  const uint32_t t = (uint32_t)r | (uint32_t)a;
-  const bool live = (((uint32_t)p >> 26) | t) < 4u;          // 0 <= p < 2^28 and both alleles single bases
-  const uint32_t nib = ((uint32_t)r << 2) | (uint32_t)a;
-  key = ((uint32_t)p << 4) | (live ? nib : 0u);
+  const bool live = ((uint32_t)p | (d << 24)) < (uint32_t)QM_POS_LIMIT_DEV;   // 0 <= p < 2^28 and a single-base pair (d < 16)
+  key = ((uint32_t)p << 4) | (live ? d : 0u);
   const float c = fminf(fmaxf(q, -1.0f), nbm1f);            // NaN -> -1
   const uint32_t b1 = (uint32_t)((int)floorf(c) + 1);
   const uint32_t g = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(flut) + f4x4);
@@ -151,7 +149,7 @@ __device__ __forceinline__ void pack_record_fast(int p, int r, int a, float q, u
 }
 
 // The allele-extended counterpart (any valid allele code takes part, include/qmvt.h): the same key and info as
-// pack_record<true> for a record whose position is in range.  A code is valid iff it is < 4 or in [2^27, 2^31): by its number
+// pack_record_ext for a record whose position is in range.  A code is valid iff it is < 4 or in [2^27, 2^31): by its number
 // of leading zeros -- 30 and more, or 1..4 -- which one shift of a constant turns into a bit (c | 1 has c's count for c >= 2 and
 // stands for 0 and 1 alike); the nibble is allele_nib's branch-free fold.
 __device__ __forceinline__ void pack_record_fast_ext(int p, int r, int a, float q, uint32_t f4x4, float nbm1f, const uint32_t* flut,
@@ -168,18 +166,19 @@ __device__ __forceinline__ void pack_record_fast_ext(int p, int r, int a, float 
   inf = live ? (b1 | g) : 0u;
 }
 
-struct Cols {  // bases of one VCF: the five columns, or the packed pair
+struct Cols {  // bases of one VCF: the five columns (the allele byte instead of ref / alt unless EXT), or the packed pair
   const int32_t* pos;
   const int32_t* ref;
   const int32_t* alt;
   const float* qual;
   const uint8_t* flags;
+  const uint8_t* anib;
   const uint32_t* pkey;
   const uint32_t* pinf;
 };
 
 template <bool PACKED> struct Raw4;   // one round's loads, still in flight
-template <> struct Raw4<false> { int4 p, r, a; float4 q; uint32_t f; };
+template <> struct Raw4<false> { int4 p, r, a; float4 q; uint32_t f, d; };   // r / a: EXT only; d (four allele bytes): !EXT only
 template <> struct Raw4<true> { uint4 k, i; int4 r, a; };   // r / a: allele-extended batches only
 
 template <bool EXT>
@@ -188,13 +187,18 @@ __device__ __forceinline__ void load_raw(const Cols& C, int idx, Raw4<false>& R)
   // outputs in L2 (same-box A/B: +3.5 % on this kernel, k_finalize 10 % faster)
   typedef int v4i __attribute__((ext_vector_type(4)));
   typedef float v4f __attribute__((ext_vector_type(4)));
+  // (!EXT: the allele byte instead of the two int32 codes, 10 bytes per record instead of 17)
   const v4i vp = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(C.pos + idx));
-  const v4i vr = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(C.ref + idx));
-  const v4i va = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(C.alt + idx));
+  if (EXT) {
+    const v4i vr = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(C.ref + idx));
+    const v4i va = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(C.alt + idx));
+    R.r = make_int4(vr.x, vr.y, vr.z, vr.w);
+    R.a = make_int4(va.x, va.y, va.z, va.w);
+  } else {
+    R.d = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(C.anib + idx));
+  }
   const v4f vq = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(C.qual + idx));
   R.p = make_int4(vp.x, vp.y, vp.z, vp.w);
-  R.r = make_int4(vr.x, vr.y, vr.z, vr.w);
-  R.a = make_int4(va.x, va.y, va.z, va.w);
   R.q = make_float4(vq.x, vq.y, vq.z, vq.w);
   R.f = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(C.flags + idx));
 }
@@ -219,34 +223,21 @@ struct In4 {   // the lane's 4 records of the round, packed
 
 template <bool EXT>
 __device__ __forceinline__ void unpack_raw(const Raw4<false>& R, int nb, In4& X, const uint32_t* flut) {
-  X.posor = 0u;
+  const float nbm1f = (float)(nb - 1);
   if (!EXT) {
-    const float nbm1f = (float)(nb - 1);
-    pack_record_fast(R.p.x, R.r.x, R.a.x, R.q.x, (R.f << 2) & 0x3cu, nbm1f, flut, X.key[0], X.inf[0]);
-    pack_record_fast(R.p.y, R.r.y, R.a.y, R.q.y, (R.f >> 6) & 0x3cu, nbm1f, flut, X.key[1], X.inf[1]);
-    pack_record_fast(R.p.z, R.r.z, R.a.z, R.q.z, (R.f >> 14) & 0x3cu, nbm1f, flut, X.key[2], X.inf[2]);
-    pack_record_fast(R.p.w, R.r.w, R.a.w, R.q.w, (R.f >> 22) & 0x3cu, nbm1f, flut, X.key[3], X.inf[3]);
-    X.posor = (uint32_t)R.p.x | (uint32_t)R.p.y | (uint32_t)R.p.z | (uint32_t)R.p.w;
-    return;
-  }
-  if (EXT) {
-    const float nbm1f = (float)(nb - 1);
+    pack_record_fast(R.p.x, R.d & 0xffu, R.q.x, (R.f << 2) & 0x3cu, nbm1f, flut, X.key[0], X.inf[0]);
+    pack_record_fast(R.p.y, (R.d >> 8) & 0xffu, R.q.y, (R.f >> 6) & 0x3cu, nbm1f, flut, X.key[1], X.inf[1]);
+    pack_record_fast(R.p.z, (R.d >> 16) & 0xffu, R.q.z, (R.f >> 14) & 0x3cu, nbm1f, flut, X.key[2], X.inf[2]);
+    pack_record_fast(R.p.w, R.d >> 24, R.q.w, (R.f >> 22) & 0x3cu, nbm1f, flut, X.key[3], X.inf[3]);
+  } else {
     pack_record_fast_ext(R.p.x, R.r.x, R.a.x, R.q.x, (R.f << 2) & 0x3cu, nbm1f, flut, X.key[0], X.inf[0]);
     pack_record_fast_ext(R.p.y, R.r.y, R.a.y, R.q.y, (R.f >> 6) & 0x3cu, nbm1f, flut, X.key[1], X.inf[1]);
     pack_record_fast_ext(R.p.z, R.r.z, R.a.z, R.q.z, (R.f >> 14) & 0x3cu, nbm1f, flut, X.key[2], X.inf[2]);
     pack_record_fast_ext(R.p.w, R.r.w, R.a.w, R.q.w, (R.f >> 22) & 0x3cu, nbm1f, flut, X.key[3], X.inf[3]);
-    X.posor = (uint32_t)R.p.x | (uint32_t)R.p.y | (uint32_t)R.p.z | (uint32_t)R.p.w;   // anything at or above bit 28: out of range (SPANF_BADPOS)
-  } else
-  {
-  pack_record<EXT>(R.p.x, R.r.x, R.a.x, R.q.x, R.f, nb, X.key[0], X.inf[0]);
-  pack_record<EXT>(R.p.y, R.r.y, R.a.y, R.q.y, R.f >> 8, nb, X.key[1], X.inf[1]);
-  pack_record<EXT>(R.p.z, R.r.z, R.a.z, R.q.z, R.f >> 16, nb, X.key[2], X.inf[2]);
-  pack_record<EXT>(R.p.w, R.r.w, R.a.w, R.q.w, R.f >> 24, nb, X.key[3], X.inf[3]);
-  }
-  if (EXT) {
     X.r[0] = R.r.x; X.r[1] = R.r.y; X.r[2] = R.r.z; X.r[3] = R.r.w;
     X.a[0] = R.a.x; X.a[1] = R.a.y; X.a[2] = R.a.z; X.a[3] = R.a.w;
   }
+  X.posor = (uint32_t)R.p.x | (uint32_t)R.p.y | (uint32_t)R.p.z | (uint32_t)R.p.w;   // anything at or above bit 28: out of range (SPANF_BADPOS)
 }
 template <bool EXT>
 __device__ __forceinline__ void unpack_raw(const Raw4<true>& R, int, In4& X, const uint32_t*) {
@@ -280,7 +271,8 @@ template <bool PACKED> __device__ __forceinline__ int rec_pos(const Cols& C, int
 template <bool PACKED, bool EXT = false>
 __device__ __forceinline__ void rec_packed(const Cols& C, int i, int nb, uint32_t& key, uint32_t& inf) {
   if (PACKED) { key = C.pkey[i]; inf = C.pinf[i]; return; }
-  pack_record<EXT>(C.pos[i], C.ref[i], C.alt[i], C.qual[i], C.flags[i], nb, key, inf);
+  if (EXT) pack_record_ext(C.pos[i], C.ref[i], C.alt[i], C.qual[i], C.flags[i], nb, key, inf);
+  else pack_record(C.pos[i], C.anib[i], C.qual[i], C.flags[i], nb, key, inf);
 }
 
 typedef const __attribute__((address_space(1))) uint32_t* gu32p;
@@ -679,6 +671,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EXT ? K1_WAV
   const TruthG tr = truth_global<EXT>(P.truths[sp.truth]);
   Cols C;
   C.pos = P.pos + sp.voff; C.ref = P.ref + sp.voff; C.alt = P.alt + sp.voff; C.qual = P.qual + sp.voff; C.flags = P.flags + sp.voff;
+  C.anib = P.anib + sp.voff;
   C.pkey = P.pkey + sp.voff; C.pinf = P.pinf + sp.voff;
   uint32_t* const mpass32 = reinterpret_cast<uint32_t*>(P.mask_pass + (sp.voff >> 6));
   uint32_t* const mtp32 = reinterpret_cast<uint32_t*>(P.mask_tp + (sp.voff >> 6));
@@ -1439,6 +1432,23 @@ __global__ void k_synth(SynthParams S) {
   synth_record(S.genome_len, vd.n, S.truth_n, tseed, seed, src, &p, &r, &a, &q, &f, S.indel_pct);
   const int64_t g = vd.off + i;
   S.pos[g] = p; S.ref[g] = r; S.alt[g] = a; S.qual[g] = q; S.flags[g] = f;
+  if (S.anib) S.anib[g] = allele_byte(r, a);
+}
+
+// The allele bytes of n records from their two codes (qm_batch_upload / _async of a batch without QM_BATCH_ALLELES, behind the
+// copies of one VCF): 8 bytes read and 1 written per record, four records per thread.  ref / alt / anib start a VCF (16-byte
+// aligned); nothing past record n is written.
+__global__ __launch_bounds__(256) void k_allele_byte(const int32_t* ref, const int32_t* alt, uint8_t* anib, int64_t n) {
+  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  if (i4 + 4 <= n) {
+    const int4 r = *reinterpret_cast<const int4*>(ref + i4);
+    const int4 a = *reinterpret_cast<const int4*>(alt + i4);
+    *reinterpret_cast<uint32_t*>(anib + i4) = (uint32_t)allele_byte(r.x, a.x) | ((uint32_t)allele_byte(r.y, a.y) << 8) |
+                                              ((uint32_t)allele_byte(r.z, a.z) << 16) | ((uint32_t)allele_byte(r.w, a.w) << 24);
+  } else {
+    for (int64_t i = i4; i < n; ++i) anib[i] = allele_byte(ref[i], alt[i]);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1614,21 +1624,22 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const SortSeg* segs, const
       if (i4 < sg.n) {   // whole 16-byte pieces: the columns are padded past every VCF
         const int64_t g = sg.src_off + i4;
         const v4i p = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(src.pos + g));
-        const v4i r = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(src.ref + g));
-        const v4i a = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(src.alt + g));
         const v4f q = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src.qual + g));
         const uint32_t f = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src.flags + g));
         uint32_t kx[4], ix[4];
         if (ext) {
-          pack_record<true>(p.x, r.x, a.x, q.x, f, n_bins, kx[0], ix[0]);
-          pack_record<true>(p.y, r.y, a.y, q.y, f >> 8, n_bins, kx[1], ix[1]);
-          pack_record<true>(p.z, r.z, a.z, q.z, f >> 16, n_bins, kx[2], ix[2]);
-          pack_record<true>(p.w, r.w, a.w, q.w, f >> 24, n_bins, kx[3], ix[3]);
-        } else {
-          pack_record<false>(p.x, r.x, a.x, q.x, f, n_bins, kx[0], ix[0]);
-          pack_record<false>(p.y, r.y, a.y, q.y, f >> 8, n_bins, kx[1], ix[1]);
-          pack_record<false>(p.z, r.z, a.z, q.z, f >> 16, n_bins, kx[2], ix[2]);
-          pack_record<false>(p.w, r.w, a.w, q.w, f >> 24, n_bins, kx[3], ix[3]);
+          const v4i r = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(src.ref + g));
+          const v4i a = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(src.alt + g));
+          pack_record_ext(p.x, r.x, a.x, q.x, f, n_bins, kx[0], ix[0]);
+          pack_record_ext(p.y, r.y, a.y, q.y, f >> 8, n_bins, kx[1], ix[1]);
+          pack_record_ext(p.z, r.z, a.z, q.z, f >> 16, n_bins, kx[2], ix[2]);
+          pack_record_ext(p.w, r.w, a.w, q.w, f >> 24, n_bins, kx[3], ix[3]);
+        } else {   // the allele byte instead of the two codes
+          const uint32_t d = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src.anib + g));
+          pack_record(p.x, d, q.x, f, n_bins, kx[0], ix[0]);
+          pack_record(p.y, d >> 8, q.y, f >> 8, n_bins, kx[1], ix[1]);
+          pack_record(p.z, d >> 16, q.z, f >> 16, n_bins, kx[2], ix[2]);
+          pack_record(p.w, d >> 24, q.w, f >> 24, n_bins, kx[3], ix[3]);
         }
         k4.x = kx[0]; k4.y = kx[1]; k4.z = kx[2]; k4.w = kx[3];
         f4.x = ix[0]; f4.y = ix[1]; f4.z = ix[2]; f4.w = ix[3];
@@ -1806,9 +1817,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(EXT ? 5 : B
   uint32_t segfl = 0;
   typedef int v4i __attribute__((ext_vector_type(4)));
   typedef float v4f __attribute__((ext_vector_type(4)));
-  v4i p[PER / 4], r[PER / 4], a[PER / 4];
+  v4i p[PER / 4], r[PER / 4], a[PER / 4];   // r / a: EXT only
   v4f q[PER / 4];
-  uint32_t f[PER / 4];
+  uint32_t f[PER / 4], d[PER / 4];           // d: four allele bytes, !EXT only
   typedef unsigned v4u __attribute__((ext_vector_type(4)));
   if (L2) {
     // level-1 entries -> bucket entries: four per thread and group, two 16-byte loads (the partition's region starts on a
@@ -1852,8 +1863,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(EXT ? 5 : B
     if (i4 < sg.n) {
       const int64_t g = sg.src_off + i4;
       p[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.pos + g));
-      r[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.ref + g));
-      a[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.alt + g));
+      if (EXT) {
+        r[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.ref + g));
+        a[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.alt + g));
+      } else {
+        d[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(P.anib + g));
+      }
       q[j] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(P.qual + g));
       f[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(P.flags + g));
     }
@@ -1873,7 +1888,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(EXT ? 5 : B
         uint32_t key, inf;
         const uint32_t f4x4 = ((f[j] >> (8 * u)) & 15u) << 2;
         if (EXT) pack_record_fast_ext(p[j][u], r[j][u], a[j][u], q[j][u], f4x4, nbm1f, s_flut, key, inf);
-        else pack_record_fast(p[j][u], r[j][u], a[j][u], q[j][u], f4x4, nbm1f, s_flut, key, inf);
+        else pack_record_fast(p[j][u], (d[j] >> (8 * u)) & 0xffu, q[j][u], f4x4, nbm1f, s_flut, key, inf);
         segfl |= ((uint32_t)p[j][u] >> 28) ? SPANF_BADPOS : 0u;
         if (inf & I_LIVE) {
           kept |= ((inf >> 16) & 1u) << u;
@@ -2102,9 +2117,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BK_WAVES_PE
   uint32_t dr[PER];   // partition << 16 | rank inside the tile's partition; 0xffffffff: position out of range (the VCF is refused)
   typedef int v4i __attribute__((ext_vector_type(4)));
   typedef float v4f __attribute__((ext_vector_type(4)));
-  v4i p[PER / 4], r[PER / 4], a[PER / 4];
+  v4i p[PER / 4];
   v4f q[PER / 4];
-  uint32_t f[PER / 4];
+  uint32_t f[PER / 4], d[PER / 4];   // d: four allele bytes
 #pragma unroll
   for (int j = 0; j < PER / 4; ++j) {
     const int64_t i4 = tbase + (int64_t)j * 2048 + tid * 4;
@@ -2112,8 +2127,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BK_WAVES_PE
     if (i4 < sg.n) {
       const int64_t g = sg.src_off + i4;
       p[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.pos + g));
-      r[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.ref + g));
-      a[j] = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.alt + g));
+      d[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(P.anib + g));
       q[j] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(P.qual + g));
       f[j] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(P.flags + g));
     }
@@ -2129,7 +2143,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BK_WAVES_PE
       ent[k] = 0ull;
       if (i4 + u < sg.n) {
         uint32_t key, inf;
-        pack_record_fast(p[j][u], r[j][u], a[j][u], q[j][u], ((f[j] >> (8 * u)) & 15u) << 2, nbm1f, s_flut, key, inf);
+        pack_record_fast(p[j][u], (d[j] >> (8 * u)) & 0xffu, q[j][u], ((f[j] >> (8 * u)) & 15u) << 2, nbm1f, s_flut, key, inf);
         if (!((uint32_t)p[j][u] >> 28)) {   // (the counting pass has flagged the VCF otherwise)
           const bool live = (inf & I_LIVE) != 0u;
           kept |= ((inf >> 16) & 1u) << u;
@@ -3446,6 +3460,9 @@ void launch_masks_to_cls(const uint64_t* mp, const uint64_t* mt, int64_t off, in
 void launch_synth(const SynthParams& S, int n_vcf, int64_t max_n, hipStream_t st) {
   if (n_vcf > 0 && max_n > 0)
     hipLaunchKernelGGL(k_synth, dim3((unsigned)((max_n + 255) / 256), (unsigned)n_vcf), dim3(256), 0, st, S);
+}
+void launch_allele_byte(const int32_t* ref, const int32_t* alt, uint8_t* anib, int64_t n, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(k_allele_byte, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, st, ref, alt, anib, n);
 }
 // first pass of the batch's sort, in two steps because the host needs the OR of the keys in between
 void launch_sort_first_hist(const SortSeg* segs, const int32_t* tile_seg, int ntiles, const int32_t* pos_col, uint32_t* hist, uint32_t* orbits,
