@@ -83,6 +83,16 @@ extern "C" {
 #define QM_MAX_BINS 256
 #define QM_POS_LIMIT (1 << 28)
 
+/* mutation-context spectra (qm_batch_motifs): per VCF [3][QM_MOTIF_COLS] uint64, rows kept / TP / FP (kept = TP + FP).
+ * Columns 0..95: the 96 SomaticSignatures motifs "<ref><alt> <l>.<r>" in lexicographic order (REF folded to C / T, the
+ * context reverse-complemented with it): 16 k + 4 base(l) + base(r), k = index of REF ALT in CA CG CT TA TC TG, A=0 C=1 G=2 T=3.
+ * QM_MOTIF_OTHER: kept SNVs outside the 96 (QM_F_NOKEY, a flank outside the genome or not ACGTacgt, REF == ALT).
+ * QM_MOTIF_REF_MISMATCH: of those in 0..95, the ones whose genome base differs from the VCF's REF (a diagnostic on top). */
+#define QM_N_MOTIFS 96
+#define QM_MOTIF_OTHER 96
+#define QM_MOTIF_REF_MISMATCH 97
+#define QM_MOTIF_COLS 98
+
 /* per-VCF scalar slots (int64 each) */
 enum {
   QM_S_NPASS = 0,    /* kept lines = R `calleridentify` (caller_performance_compare.R:82) */
@@ -129,6 +139,15 @@ int qm_truth_count(qm_ctx* ctx);
 /* Frees a truth set's device memory.  Its id may be handed out again by a later load; a batch created
  * against the released set refuses to run (QM_E_STATE). */
 int qm_truth_release(qm_ctx* ctx, int truth_id);
+
+/* ---- genomes ----------------------------------------------------------------
+ * Replaces the BSgenome-style reference lookup of rule mutationcontext (rules/mutationcontext.smk,
+ * scripts/mutation_context_profile.R: the mix's Merlin / AD169 FASTA read for SomaticSignatures' mutationContext): one
+ * contig's raw bytes (no header, no newlines; POS p is seq[p-1]; ACGTacgt are bases, any other byte is "no base"), packed
+ * on the host, kept in HBM.  len > QM_POS_LIMIT: QM_E_RANGE.  Ids follow the rules of truth sets: a released id may be
+ * handed out again by a later load, and a qm_batch_motifs that names a released id returns QM_E_STATE. */
+int qm_genome_load(qm_ctx* ctx, const uint8_t* seq, int64_t len, int* genome_id);
+int qm_genome_release(qm_ctx* ctx, int genome_id);
 
 /* ---- one-shot, host buffers -------------------------------------------------
  * What n_vcf invocations of the reference script compute (A2 flags in, A4/A5
@@ -220,6 +239,14 @@ int qm_batch_get_scalars(qm_batch* b, int64_t* out /*[n_vcf][QM_N_SCALARS]*/);
 int qm_batch_get_global(qm_batch* b, uint64_t* out /*[qm_batch_n_truth(b)][3][n_bins]*/);
 int qm_batch_get_columns(qm_batch* b, int vcf, int32_t* pos, int32_t* ref, int32_t* alt, float* qual,
                          uint8_t* flags);
+/* The 96-motif spectra of the kept, TP and FP SNVs of every VCF (rule mutationcontext: mutationContext(unify = TRUE,
+ * check = FALSE) + motifMatrix over the filtered / tp / fp VCFs, scripts/mutation_context_profile.R), read from the finished
+ * batch's columns and class masks in input order.  genome_id_per_vcf: host array [n_vcf], -1 = no genome (the VCF's rows are
+ * zero).  Counted: kept records whose REF and ALT are single bases.  Asynchronous on `stream` (NULL = the context's own);
+ * QM_E_STATE unless the latest qm_batch_run was finished.  The output is allocated on the first call. */
+int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, void* stream);
+/* Waits for the latest qm_batch_motifs, then copies [n_vcf][3][QM_MOTIF_COLS] uint64; QM_E_STATE if the batch ran since. */
+int qm_batch_get_motifs(qm_batch* b, uint64_t* out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -423,6 +450,14 @@ int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bin
 int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                         qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                         void* global_dev);
+/* qm_extract_files_ex plus rule mutationcontext over its outputs (rules/mutationcontext.smk): genome_id[j] (a
+ * qm_genome_load id, -1 = none) and motifs[j][3][QM_MOTIF_COLS] (qm_batch_motifs' rows; zero for jobs without a genome).
+ * Mixed-sample jobs: the motif pass runs behind the classification.  Pure-strain jobs that name a genome join the batch
+ * against an empty truth set: kept = the filter's verdict, TP = none, FP = kept (extract_TP_FP_SNPs.py:33-36); their files,
+ * stats and ROC rows are those of qm_extract_files_ex. */
+int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                            qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                            void* global_dev, const int32_t* genome_id, uint64_t* motifs);
 
 /* `bgzip -c` (the *.vcf.gz outputs the same rules declare, rules/vis_eval_vcf.smk:29,36 ...): BGZF = gzip members of at
  * most 64 KiB with a 'BC' extra field + the EOF member; zcat and tabix / htslib read it.  level -1 = zlib's default (6,

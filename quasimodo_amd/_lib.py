@@ -14,6 +14,10 @@ ERRORS = {-1: "QM_E_INVAL", -2: "QM_E_NODEVICE", -3: "QM_E_HIP", -4: "QM_E_NOMEM
 QM_E_UNSORTED = -10
 QM_BATCH_ALLELES = 1
 QM_ABI_VERSION = 6
+QM_N_MOTIFS = 96
+QM_MOTIF_OTHER = 96
+QM_MOTIF_REF_MISMATCH = 97
+QM_MOTIF_COLS = 98
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -28,6 +32,7 @@ EXPORTS = (
     "qm_bw_probe", "qm_bgzf_write", "qm_bgzf_write_tbi", "qm_extract_files", "qm_extract_files_ex", "qm_batch_global_device", "qm_batch_path_stats", "qm_path_stats_total", "qm_batch_upload_async", "qm_batch_get_masks", "qm_patterns_create", "qm_patterns_destroy", "qm_patterns_info", "qm_vcf_hostpath",
     "qm_mummer2vcf", "qm_free",
     "qm_comm_create", "qm_comm_make_id", "qm_comm_create_rank", "qm_allreduce_counters", "qm_comm_collectives", "qm_comm_destroy",
+    "qm_genome_load", "qm_genome_release", "qm_batch_motifs", "qm_batch_get_motifs", "qm_extract_files_motifs",
 )
 
 
@@ -68,7 +73,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -223,6 +228,12 @@ def lib():
     L.qm_vcf_hostpath.argtypes = [vp, C.c_char_p, C.c_size_t, i64, vp, vp, vp, vp, vp, vp, vp]
     L.qm_vcf_write.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, i64, vp, vp, vp, i32]
     L.qm_vcf_split_write.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, i32, i32, C.POINTER(C.c_int64)]
+    L.qm_genome_load.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
+    L.qm_genome_release.argtypes = [vp, i32]
+    L.qm_batch_motifs.argtypes = [vp, vp, vp]
+    L.qm_batch_get_motifs.argtypes = [vp, vp]
+    L.qm_extract_files_motifs.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                          vp, vp]
     _lib = L
     return L
 

@@ -22,6 +22,7 @@
 
 #include "../../include/qmvt.h"
 #include "qmvt_dev.h"
+#include "qmvt_motif.h"
 
 using namespace qm;
 
@@ -67,6 +68,14 @@ struct Truth {
   uint32_t gen = 0;
 };
 
+// a genome of qm_genome_load: the 4-bit packed sequence k_motif gathers its 3-base windows from.  Slots follow
+// the rules of truth sets: stable ids, a released slot is reused by a later load.
+struct Genome {
+  uint32_t* d_words = nullptr;
+  int64_t len = 0;
+  bool released = false;
+};
+
 struct qm_ctx {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -75,6 +84,7 @@ struct qm_ctx {
   TruthDev* d_truths = nullptr;  // device copy of the descriptors
   int d_truths_cap = 0;
   int64_t path_total[QM_N_PATH_STATS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // qm_path_stats_total: every finish of every batch of this context
+  std::vector<Genome> genomes;
 };
 
 template <typename T>
@@ -135,6 +145,7 @@ extern "C" void qm_destroy(qm_ctx* c) {
     (void)hipFree(t.d_xkeys); (void)hipFree(t.d_xref); (void)hipFree(t.d_xalt); (void)hipFree(t.d_xtidx);
   }
   (void)hipFree(c->d_truths);
+  for (auto& g : c->genomes) (void)hipFree(g.d_words);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->aux) (void)hipStreamDestroy(c->aux);
   delete c;
@@ -261,6 +272,49 @@ extern "C" int qm_truth_release(qm_ctx* c, int truth_id) {
   c->truths[(size_t)truth_id].released = true;
   c->truths[(size_t)truth_id].gen = g;
   return upload_truth_table(c);
+}
+
+// ---------------------------------------------------------------------------
+// genomes
+// ---------------------------------------------------------------------------
+extern "C" int qm_genome_load(qm_ctx* c, const uint8_t* seq, int64_t len, int* genome_id) {
+  if (!c || !seq || !genome_id || len < 1) return fail(QM_E_INVAL, "qm_genome_load: bad arguments");
+  if (len > (int64_t)QM_POS_LIMIT) return fail(QM_E_RANGE, "qm_genome_load: %lld bases, more than 2^28", (long long)len);
+  HIPCHK(hipSetDevice(c->dev));
+  uint8_t code[256];
+  memset(code, (int)GENOME_NOBASE, sizeof code);
+  code['A'] = code['a'] = 0; code['C'] = code['c'] = 1; code['G'] = code['g'] = 2; code['T'] = code['t'] = 3;
+  const size_t nw = (size_t)(len / 8 + 2);
+  std::vector<uint32_t> w(nw, 0xffffffffu);   // no base past the end
+  for (int64_t i = 0; i < len; i += 8) {
+    uint32_t x = 0xffffffffu;
+    for (int64_t k = 0; k < 8 && i + k < len; ++k) x = (x & ~(15u << (4 * k))) | ((uint32_t)code[seq[i + k]] << (4 * k));
+    w[(size_t)(i / 8)] = x;
+  }
+  Genome g;
+  g.len = len;
+  DALLOC(g.d_words, nw);
+  hipError_t e = hipMemcpy(g.d_words, w.data(), nw * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(g.d_words); return fail(QM_E_HIP, "qm_genome_load: hipMemcpy: %s", hipGetErrorString(e)); }
+  int slot = -1;
+  for (size_t i = 0; i < c->genomes.size(); ++i) if (c->genomes[i].released) { slot = (int)i; break; }
+  if (slot >= 0) c->genomes[(size_t)slot] = g;
+  else { c->genomes.push_back(g); slot = (int)c->genomes.size() - 1; }
+  *genome_id = slot;
+  return QM_OK;
+}
+
+extern "C" int qm_genome_release(qm_ctx* c, int genome_id) {
+  if (!c || genome_id < 0 || genome_id >= (int)c->genomes.size() || c->genomes[(size_t)genome_id].released)
+    return fail(QM_E_INVAL, "qm_genome_release: no live genome %d", genome_id);
+  HIPCHK(hipSetDevice(c->dev));
+  HIPCHK(hipDeviceSynchronize());   // a motif pass may still read it on a stream of the caller's
+  Genome& g = c->genomes[(size_t)genome_id];
+  (void)hipFree(g.d_words);
+  g.d_words = nullptr;
+  g.len = 0;
+  g.released = true;
+  return QM_OK;
 }
 
 extern "C" int qm_truth_load(qm_ctx* c, const int32_t* pos, const int32_t* ref, const int32_t* alt, int64_t n, int* truth_id) {
@@ -500,6 +554,13 @@ struct qm_batch {
   bool known_dirty = false;           // the device copy is stale
   uint8_t* d_known = nullptr;
   bool run_used_known = false;        // the run in flight was launched with d_known
+  // qm_batch_motifs (lazy: a batch that never asks allocates nothing): the [n_vcf][3][QM_MOTIF_COLS] counts, the per-VCF genome
+  // descriptors (page-locked: copied on the call's stream; ev_motif says when the copy and the pass are done)
+  uint64_t* d_motifs = nullptr;
+  GenomeRef* d_mgen = nullptr;
+  GenomeRef* h_mgen = nullptr;
+  hipEvent_t ev_motif = nullptr;
+  bool motifs_valid = false;          // qm_batch_motifs was called behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -524,6 +585,9 @@ static void batch_free(qm_batch* b) {
                   b->sv[1], b->si[0], b->si[1], b->shist, b->sorbits, b->d_segs, b->d_tile_seg, b->d_ktile_seg, b->d_ktile_local, b->d_known};
   for (void* p : ptrs) (void)hipFree(p);
   if (b->h_summary) (void)hipHostFree(b->h_summary);
+  (void)hipFree(b->d_motifs); (void)hipFree(b->d_mgen);
+  if (b->h_mgen) (void)hipHostFree(b->h_mgen);
+  if (b->ev_motif) (void)hipEventDestroy(b->ev_motif);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -845,6 +909,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   HIPCHK(hipGetLastError());
   b->ran = true;
   b->finished = false;
+  b->motifs_valid = false;
   b->last_global = g;
   return QM_OK;
 }
@@ -1970,6 +2035,54 @@ extern "C" int qm_batch_get_global(qm_batch* b, uint64_t* out) {
   NEED_FINISHED(b, "qm_batch_get_global");
   HIPCHK(hipSetDevice(b->ctx->dev));
   HIPCHK(hipMemcpy(out, b->last_global, (size_t)b->n_truth * 3 * (size_t)b->n_bins * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+// the mutation-context spectra of the finished batch
+extern "C" int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, void* stream) {
+  NEED_FINISHED(b, "qm_batch_motifs");
+  if (!genome_id_per_vcf) return fail(QM_E_INVAL, "qm_batch_motifs: NULL genome ids");
+  qm_ctx* c = b->ctx;
+  for (int v = 0; v < b->n_vcf; ++v) {
+    const int gid = genome_id_per_vcf[v];
+    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_motifs: VCF %d names genome %d (have %zu)", v, gid, c->genomes.size());
+    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_motifs: VCF %d names released genome %d", v, gid);
+  }
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const size_t nv = (size_t)b->n_vcf;
+  if (!b->d_motifs) {
+    DALLOC(b->d_motifs, nv * MOTIF_ROW_WORDS);
+    DALLOC(b->d_mgen, nv);
+    HIPCHK(hipHostMalloc((void**)&b->h_mgen, nv * sizeof(GenomeRef), hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&b->ev_motif, hipEventDisableTiming));
+    b->dev_bytes += (int64_t)(nv * (MOTIF_ROW_WORDS * 8 + sizeof(GenomeRef)));
+  } else {
+    HIPCHK(hipEventSynchronize(b->ev_motif));   // the previous call's copy has read the page-locked descriptors
+  }
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = genome_id_per_vcf[v];
+    b->h_mgen[v] = gid < 0 ? GenomeRef{nullptr, 0} : GenomeRef{c->genomes[(size_t)gid].d_words, c->genomes[(size_t)gid].len};
+  }
+  HIPCHK(hipMemcpyAsync(b->d_mgen, b->h_mgen, nv * sizeof(GenomeRef), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(b->d_motifs, 0, nv * MOTIF_ROW_WORDS * 8, st));
+  MotifParams P;
+  P.spans = b->d_spans; P.genomes = b->d_mgen;
+  P.pos = b->pos; P.anib = b->anib; P.ref = b->ref; P.alt = b->alt; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  P.out = b->d_motifs;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_motif(P, b->ext, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(b->ev_motif, st));
+  b->motifs_valid = true;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_motifs(qm_batch* b, uint64_t* out) {
+  if (!b || !out) return fail(QM_E_INVAL, "qm_batch_get_motifs: bad arguments");
+  if (!b->motifs_valid) return fail(QM_E_STATE, "qm_batch_get_motifs: no qm_batch_motifs behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_motif));
+  HIPCHK(hipMemcpy(out, b->d_motifs, (size_t)b->n_vcf * MOTIF_ROW_WORDS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 // dst[i] += src[i] for device arrays (qm_extract_files_ex adds the per-truth sums of its batch into the caller's buffer)

@@ -171,9 +171,28 @@ extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs
   return qm_extract_files_ex(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, nullptr, 0, nullptr);
 }
 
+static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
+                         uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
+                         const int32_t* genome_id, uint64_t* motifs_out);
+
 extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                    qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
                                    int n_slots, void* global_dev) {
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr);
+}
+
+// rule mutationcontext behind the worker: the motif pass runs on the batch the classification leaves in HBM
+extern "C" int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                       qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                       int n_slots, void* global_dev, const int32_t* genome_id, uint64_t* motifs_out) {
+  if (n_jobs > 0 && (!genome_id || !motifs_out)) return fail(QM_E_INVAL, "qm_extract_files_motifs: NULL genome ids or output");
+  if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out);
+}
+
+static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
+                         uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
+                         const int32_t* genome_id, uint64_t* motifs_out) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
     return fail(QM_E_INVAL, "qm_extract_files: bad arguments");
   if (global_dev && (n_slots < 1 || (n_jobs && !truth_slot))) return fail(QM_E_INVAL, "qm_extract_files_ex: global_dev needs truth_slot and n_slots >= 1");
@@ -200,6 +219,11 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
   }
   qm_dict* dict = ext ? qm_dict_create() : nullptr;
   std::vector<TruthState> T;
+  // which jobs the batch holds: every mixed-sample job, and the pure-strain jobs that name a genome (against an empty truth set,
+  // for their motif rows only: their files, stats and ROC rows are made as for any pure-strain job)
+  auto has_genome = [&](int j) { return genome_id && genome_id[j] >= 0; };
+  auto in_batch = [&](int j) { return !jobs[j].pure || has_genome(j); };
+  int empty_tid = -1;
 
   // ---- the VCFs go through as ONE batch: stage one (map, count, tokenise, upload) of every VCF, then stage two (engine,
   //      masks, files).  A pipeline of groups -- stage two of group g on a thread of its own beside stage one of group g + 1 --
@@ -214,6 +238,7 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
     if (truth_thread.joinable()) truth_thread.join();
     if (batch) { qm_batch_destroy(batch); batch = nullptr; }
     if (copy_stream) { (void)hipStreamDestroy(copy_stream); copy_stream = nullptr; }
+    if (empty_tid >= 0) { (void)qm_truth_release(ctx, empty_tid); empty_tid = -1; }
     for (auto& t : T) { if (t.pats) qm_patterns_destroy(t.pats); if (t.tid >= 0) (void)qm_truth_release(ctx, t.tid); }
     if (dict) qm_dict_destroy(dict);
   };
@@ -306,7 +331,15 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
     if (truth_rc != QM_OK) return fail(truth_rc, truth_msg);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
     for (int j = 0; j < n_jobs; ++j)
-      if (!jobs[j].pure) { J[(size_t)j].batch_v = (int)nrec.size(); nrec.push_back(J[(size_t)j].n_data); tids.push_back(T[(size_t)J[(size_t)j].truth].tid); }
+      if (jobs[j].pure && has_genome(j) && empty_tid < 0) {
+        const int rc = qm_truth_load(ctx, nullptr, nullptr, nullptr, 0, &empty_tid);
+        if (rc != QM_OK) return rc;
+      }
+    for (int j = 0; j < n_jobs; ++j)
+      if (in_batch(j)) {
+        J[(size_t)j].batch_v = (int)nrec.size(); nrec.push_back(J[(size_t)j].n_data);
+        tids.push_back(jobs[j].pure ? empty_tid : T[(size_t)J[(size_t)j].truth].tid);
+      }
     if (!nrec.empty()) {
       const int rc = qm_batch_create_ext(ctx, (int)nrec.size(), nrec.data(), tids.data(), n_bins, mode, &batch);
       if (rc != QM_OK) return rc;
@@ -340,7 +373,13 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
         if (s.rc == QM_OK) s.rc = QM_E_INVAL;
         return;
       }
-      if (jobs[j].pure) return;
+      if (jobs[j].pure) {
+        if (has_genome(j) && !(strict && s.info.n_refused)) {
+          s.rc = qm_batch_upload_async(batch, s.batch_v, s.pos, s.ref, s.alt, s.qual, s.flags, copy_stream);
+          if (s.rc != QM_OK) s.err = qm_last_error(ctx);
+        }
+        return;
+      }
       wait_patterns();
       const TruthState& t = T[(size_t)s.truth];
       if (t.rc != QM_OK) { s.rc = t.rc; return; }
@@ -393,6 +432,20 @@ extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* j
         for (size_t k = 0; k < T.size() && rc == QM_OK; ++k) {
           if (slot_of_truth[k] < 0 || T[k].tid < 0) continue;
           rc = qm_device_add_u64(ctx, (uint64_t*)global_dev + (size_t)slot_of_truth[k] * roww, (const uint64_t*)src + (size_t)T[k].tid * roww, (int64_t)roww);
+        }
+      }
+      if (rc == QM_OK && motifs_out) {   // the motif pass behind the classification, on the columns and masks still in HBM
+        std::vector<int32_t> gid(nrec.size(), -1);
+        bool any = false;
+        for (int j = 0; j < n_jobs; ++j)
+          if (in_batch(j) && has_genome(j)) { gid[(size_t)J[(size_t)j].batch_v] = genome_id[j]; any = true; }
+        if (any) {
+          std::vector<uint64_t> mo(nrec.size() * 3 * QM_MOTIF_COLS);
+          rc = qm_batch_motifs(batch, gid.data(), nullptr);
+          if (rc == QM_OK) rc = qm_batch_get_motifs(batch, mo.data());
+          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
+            if (in_batch(j) && has_genome(j))
+              memcpy(motifs_out + (size_t)j * 3 * QM_MOTIF_COLS, &mo[(size_t)J[(size_t)j].batch_v * 3 * QM_MOTIF_COLS], sizeof(uint64_t) * 3 * QM_MOTIF_COLS);
         }
       }
       if (rc != QM_OK) err = qm_last_error(ctx);

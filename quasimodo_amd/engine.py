@@ -77,6 +77,17 @@ class Engine:
     def n_truth(self):
         return self._L.qm_truth_count(self._h)
 
+    # -- genomes (mutation-context spectra) ---------------------
+    def genome_load(self, seq):
+        """one contig's raw bytes (motifs.read_fasta) into HBM; returns its id"""
+        seq = bytes(seq)
+        gid = C.c_int(-1)
+        check(self._L.qm_genome_load(self._h, seq, len(seq), C.byref(gid)), self._h)
+        return gid.value
+
+    def genome_release(self, gid):
+        check(self._L.qm_genome_release(self._h, int(gid)), self._h)
+
     # -- one-shot ---------------------------------------------------------------
     def classify_batch(self, columns, truth_ids, n_bins=256, alleles=False):
         """columns: list of (pos, ref, alt, qual, flags) per VCF.  Returns (per-VCF result dicts,
@@ -139,11 +150,13 @@ class Engine:
         check(self._L.qm_bench_synth(self._h, C.byref(cfg), int(n_vcf), int(records), int(n_bins), int(steps), C.byref(r)), self._h)
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
-    def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None):
+    def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
         this call's VCFs land in rows truth_slots[j] of the caller's [n_slots][3][n_bins] uint64 device buffer (cleared first).
+        genomes: per-job genome ids (genome_load) or None / -1; when any job has one, qm_extract_files_motifs runs and every row
+        gains `motifs` ([3][QM_MOTIF_COLS] uint64: kept, TP, FP).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         import os
         n = len(file_jobs)
@@ -156,14 +169,25 @@ class Engine:
         roc = np.zeros((max(n, 1), 3, n_bins), np.uint64)
         ph = (C.c_double * 8)()
         slots = None if truth_slots is None else _c(list(truth_slots) + [0] * (1 if n == 0 else 0), np.int32)
-        check(self._L.qm_extract_files_ex(self._h, n, arr, int(n_bins), _lib.QM_BATCH_ALLELES if alleles else 0, int(bool(strict)), st, _p(roc), ph,
-                                          _p(slots), int(n_slots), C.c_void_p(global_dev) if global_dev else None), self._h)
+        gids = None if genomes is None else [-1 if g is None else int(g) for g in genomes]
+        motifs = None
+        if gids is not None and len(gids) != n:
+            raise ValueError("genomes: %d entries for %d jobs" % (len(gids), n))
+        args = (self._h, n, arr, int(n_bins), _lib.QM_BATCH_ALLELES if alleles else 0, int(bool(strict)), st, _p(roc), ph,
+                _p(slots), int(n_slots), C.c_void_p(global_dev) if global_dev else None)
+        if gids is not None and any(g >= 0 for g in gids):
+            motifs = np.zeros((n, 3, _lib.QM_MOTIF_COLS), np.uint64)
+            check(self._L.qm_extract_files_motifs(*args, _p(_c(gids, np.int32)), _p(motifs)), self._h)
+        else:
+            check(self._L.qm_extract_files_ex(*args), self._h)
         rows = []
         for k in range(n):
             r = dict(zip(SCALAR_NAMES, list(st[k].scalars)))
             r.update(n_lines=st[k].n_lines, n_refused=st[k].n_refused, genomediff=st[k].genomediff,
                      header_kept=(st[k].header_kept, st[k].header_kept_tp), host_decided=st[k].host_decided, r_hostile=st[k].r_hostile,
                      roc=roc[k].copy())
+            if motifs is not None:
+                r["motifs"] = motifs[k].copy()
             rows.append(r)
         phases = dict(zip(("map_count", "truth_beside", "batch_layout", "tokenise_upload", "engine", "masks_back", "write", "release"), list(ph)))
         return rows, phases
@@ -293,6 +317,19 @@ class Batch:
         qual, flags = np.zeros(n, np.float32), np.zeros(n, np.uint8)
         self._ck(self._L.qm_batch_get_columns(self._h, int(v), _p(pos), _p(ref), _p(alt), _p(qual), _p(flags)))
         return pos, ref, alt, qual, flags
+
+    def motifs(self, genome_ids, stream=None):
+        """qm_batch_motifs: enqueue the mutation-context pass of the finished batch (genome_ids: one genome id or -1 per VCF)"""
+        g = _c(genome_ids, np.int32)
+        if g.shape[0] != self.n_vcf:
+            raise ValueError("genome_ids: %d entries for %d VCFs" % (g.shape[0], self.n_vcf))
+        self._ck(self._L.qm_batch_motifs(self._h, _p(g), C.c_void_p(stream) if stream else None))
+
+    def motif_counts(self):
+        """qm_batch_get_motifs: [n_vcf][3][QM_MOTIF_COLS] uint64 (rows kept, TP, FP; columns motifs.MOTIFS, outside, REF mismatch)"""
+        out = np.zeros((self.n_vcf, 3, _lib.QM_MOTIF_COLS), np.uint64)
+        self._ck(self._L.qm_batch_get_motifs(self._h, _p(out)))
+        return out
 
     def path_stats(self):
         """qm_batch_path_stats: where the VCFs the last finish found out of order went"""

@@ -39,6 +39,7 @@ class Job:
     tp_out: str = ""
     fp_out: str = ""
     stats: dict = field(default_factory=dict)
+    genome: str = None        # FASTA of the sample's genome: the mutation-context spectra come back in stats["motifs"]
 
 
 def _paths(job):
@@ -73,16 +74,25 @@ def _alleles_default():
     return os.environ.get("QM_ALLELES", "0") not in ("", "0")
 
 
-def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None):
+def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
+                 genomes=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
     alleles=True (or QM_ALLELES=1): the allele-extended mode -- every record whose REF and ALT are
     [ACGT]+ takes part, not only single bases (a build-defined widening of the reference's filter,
     include/qmvt.h; hcmv mode only).
-    truth_slots / n_slots / global_dev: this call is one rank's share of a multi-GPU run (Engine.extract_files)."""
+    truth_slots / n_slots / global_dev: this call is one rank's share of a multi-GPU run (Engine.extract_files).
+    genomes: per job a FASTA path (one sequence) or None (default: Job.genome): the jobs that have one get
+    stats["motifs"], their [3][98] mutation-context rows (kept, TP, FP; quasimodo_amd.motifs).  Every distinct FASTA is
+    loaded once and released before this returns."""
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
+    if genomes is not None:
+        if len(genomes) != len(jobs):
+            raise ValueError("genomes: %d entries for %d jobs" % (len(genomes), len(jobs)))
+        for j, g in zip(jobs, genomes):
+            j.genome = g
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -98,7 +108,9 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if not all(pure) else None
+        need = not all(pure) or any(j.genome for j in jobs)
+        engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
+    loaded = {}
     try:
         for job, p in zip(jobs, pure):
             os.makedirs(os.path.dirname(job.fp_out) or ".", exist_ok=True)
@@ -112,12 +124,22 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             rows = _pure_only(fj, strict)
         else:
             before = engine.path_stats_total()
+            gids = None
+            if any(j.genome for j in jobs):
+                from .motifs import read_fasta
+                for j in jobs:
+                    if j.genome and j.genome not in loaded:
+                        loaded[j.genome] = engine.genome_load(read_fasta(j.genome))
+                gids = [loaded[j.genome] if j.genome else -1 for j in jobs]
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev)
+                                                global_dev=global_dev, genomes=gids)
             extract_many.last_phases = phases
             # where the VCFs found out of order went (bucket paths / radix sort: a silent fall onto the slow path shows here)
             extract_many.last_paths = {k: v - before[k] for k, v in engine.path_stats_total().items()}
     finally:
+        if engine is not None:
+            for gid in loaded.values():
+                engine.genome_release(gid)
         if own and engine is not None:
             engine.close()
     for job, p, r in zip(jobs, pure, rows):

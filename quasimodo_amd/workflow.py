@@ -153,13 +153,15 @@ def hcmv_rank_post(engine, jobs, indices, args):
 
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
-                         _same_device=False):
+                         _same_device=False, mutation_context=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
     gpus > 1: one process per GPU (quasimodo_amd.multigpu); the VCFs are dealt by SAMPLE (longest first), so the four
     compared callers of a sample meet on one rank and the FP overlap needs no exchange; every rank writes its own files,
-    the confusion counters go through the one all-reduce, the rows come to this process for the three tables."""
+    the confusion counters go through the one all-reduce, the rows come to this process for the three tables.
+    mutation_context: {"TM": FASTA, "TA": FASTA} (rules/mutationcontext.smk): the motif pass runs behind the classification and
+    final_tables/{mix}.{caller}.mutationcontext.tsv is written for every caller and every mix that has samples."""
     callers = list(callers or SNPCALLERS)
     data_dir = ensure_bundle(data_dir)
     results = os.path.join(outpath.rstrip("/"), "results")
@@ -176,9 +178,19 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             if not os.path.exists(src):
                 raise WorkflowError("missing input %s" % src)
             plan.append((s, c, src))
+    mixes = sorted({s[:2] for s in samples}, reverse=True)              # TM, TA
+    if mutation_context is not None:
+        for mix in mixes:
+            fa = mutation_context.get(mix)
+            if not fa or not os.path.isfile(fa):
+                raise WorkflowError("mutation context: no genome FASTA for %s (%s)" % (mix, fa))
     if dryrun:
         for s, c, src in plan:
             print("extractTP\t%s\t%s" % (c, src))
+        if mutation_context is not None:
+            for mix in mixes:
+                for c in callers:
+                    print("mutationcontext\t%s\t%s" % (mix, c))
         return None
     os.makedirs(os.path.join(snp_dir, "nucmer"), exist_ok=True)
     for mix in ("TM", "TA"):                                           # cp_genome_diff
@@ -191,7 +203,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         os.makedirs(os.path.join(d, "fp"), exist_ok=True)
         dst = os.path.join(d, os.path.basename(src))
         shutil.copyfile(src, dst)
-        jobs.append(Job(dst, os.path.join(snp_dir, "nucmer", "%s.maskrepeat.variants.vcf" % s[:2]), "hcmv", d, c))
+        jobs.append(Job(dst, os.path.join(snp_dir, "nucmer", "%s.maskrepeat.variants.vcf" % s[:2]), "hcmv", d, c,
+                        genome=mutation_context.get(s[:2]) if mutation_context is not None and not s.endswith("-1-0") else None))
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -216,6 +229,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         _flag_truth_rows(jobs)
         write_caller_performance(os.path.join(tables, "caller_performance.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
         _write_snp_rocs(meta, jobs, snp_dir)
+        if mutation_context is not None:
+            _write_mutation_context(meta, jobs, tables, callers, mixes)
         if mixed and len(cmp_callers) >= 2:
             reg = {}
             for e in res["extras"]:
@@ -236,6 +251,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         write_caller_performance(os.path.join(results, "final_tables", "caller_performance.tsv"),
                                  [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
         _write_snp_rocs(meta, jobs, snp_dir)
+        if mutation_context is not None:
+            _write_mutation_context(meta, jobs, os.path.join(results, "final_tables"), callers, mixes)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
         if mixed and len(cmp_callers) >= 2:                              # compareFP (counts only)
             files = {s: {c: j.fp_out for (c, ss), j in zip(meta, jobs) if ss == s and c in cmp_callers} for s in mixed}
@@ -248,6 +265,16 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
 
 
 run_hcmv_variantcall.last_result = None
+
+
+def _write_mutation_context(meta, jobs, tables, callers, mixes):
+    """rule mutationcontext's numbers (scripts/mutation_context_profile.R without the plot): one table per mix and caller"""
+    from .motifs import study_columns, write_mutation_context
+    for mix in mixes:
+        for c in callers:
+            rows = {s: j.stats["motifs"] for (cc, s), j in zip(meta, jobs) if cc == c and s[:2] == mix and not s.endswith("-1-0")}
+            if rows:
+                write_mutation_context(os.path.join(tables, "%s.%s.mutationcontext.tsv" % (mix, c)), study_columns(rows))
 
 
 def _write_snp_rocs(meta, jobs, snp_dir):

@@ -56,6 +56,8 @@ def _write_json(path, command, jobs, workflow_fn):
     for j in jobs or []:
         st = j.stats or {}
         row = {k: int(st[k]) for k in ("n_records", "n_pass", "tp_lines", "fp_lines", "TP_R", "FP_R", "genomediff", "truth_unique", "sorted") if k in st}
+        if st.get("motifs") is not None:   # (--mutation-context) kept SNVs outside the 96 motifs, and REF mismatches
+            row.update(motif_other=int(st["motifs"][0][96]), motif_ref_mismatch=int(st["motifs"][0][97]))
         rows.append(dict(vcf=j.vcf_file, filtered=j.filtered_out, tp=j.tp_out, fp=j.fp_out, pure_strain=bool(st.get("pure_strain")), **row))
     with open(os.path.join(cd, path), "w") as fh:
         json.dump({"command": command, "rows": rows, "unsorted_paths": paths,
@@ -74,7 +76,12 @@ def _fail(e):
 @click.option("-e", "--evaluation", required=True, type=click.Choice(["all", "variantcall", "assembly"]), help="The evaluation to run.")
 @click.option("-s", "--slow", is_flag=True, default=False, show_default=True, help="Run the evaluation based on reads (not supported by this build).")
 @click.option("--data", type=click.Path(), default=None, help="Unpacked bundle directory (default: <repo>/data/snp).")
-def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None):
+@click.option("--mutation-context", "mutation_context", is_flag=True, default=False,
+              help="Also write final_tables/{mix}.{caller}.mutationcontext.tsv (96-motif spectra of kept, TP and FP SNVs).")
+@click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
+@click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
+def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
+         mutation_context=False, merlin_ref=None, ad169_ref=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -82,16 +89,21 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
         click.echo("assembly evaluation is outside the accelerated path; not supported", err=True)
         sys.exit(2)
     from quasimodo_amd import workflow
+    cfg_file = os.path.join(wd, "config", "config.yaml")
+    cfg = workflow.load_yaml(cfg_file) if os.path.exists(cfg_file) else {}
     if outpath:
         out = os.path.join(cd, outpath)
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
-        cfg_file = os.path.join(wd, "config", "config.yaml")
-        cfg = workflow.load_yaml(cfg_file) if os.path.exists(cfg_file) else {}
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
+    genomes = None
+    if mutation_context:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+        pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
+        genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
         # data/snp is unpacked from data/snp.tar.gz when it is not there yet (rules/load_config.smk:28-31)
         workflow.run_hcmv_variantcall.last_result = None
-        jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None)
+        jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None,
+                                             mutation_context=genomes)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
