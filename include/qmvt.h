@@ -247,6 +247,31 @@ int qm_batch_get_columns(qm_batch* b, int vcf, int32_t* pos, int32_t* ref, int32
 int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, void* stream);
 /* Waits for the latest qm_batch_motifs, then copies [n_vcf][3][QM_MOTIF_COLS] uint64; QM_E_STATE if the batch ran since. */
 int qm_batch_get_motifs(qm_batch* b, uint64_t* out);
+/* ---- the truth-side view ------------------------------------------------------------------------------
+ * The sets behind scripts/caller_performance_compare.R:110-119,510-549 (`Genome` against the callers' distinct single-base
+ * keys) seen from the truth set: which truth keys a VCF's kept records hit, which records carry a key of the truth set, and,
+ * for groups of VCFs of one truth set, how many truth keys lie in every region of their Venn diagram.
+ * qm_batch_truth_hits: one pass over the finished batch's columns in input order (sorted and unsorted VCFs alike), asynchronous
+ * on `stream` (NULL = the context's own).  QM_E_STATE unless the latest qm_batch_run was finished, when a truth set of the batch
+ * was released, and for an allele-extended batch (single-base batches only).  The outputs are allocated on the first call. */
+#define QM_TRUTH_GROUP_MAX 5
+#define QM_TRUTH_REGIONS 32
+int qm_batch_truth_hits(qm_batch* b, void* stream);
+/* The hit bitmap of one VCF: n_words = (T' + 31) / 32 words (T' = QM_S_TRUTH of the VCF), bit k & 31 of word k / 32 set iff some
+ * record of the VCF is kept, has a comparable key (no QM_F_NOKEY) and that key is entry k of the truth set's sorted distinct keys
+ * pos << 4 | ref << 2 | alt.  The ID column plays no part: the popcount is the device's QM_S_TP_R.  Bits at and beyond T' are 0.
+ * Waits for the latest qm_batch_truth_hits; QM_E_STATE if the batch ran since (or none was made), QM_E_INVAL for another n_words. */
+int qm_batch_get_truth_hits(qm_batch* b, int vcf, uint32_t* bits, int64_t n_words);
+/* The record mask of one VCF, laid out like qm_batch_get_masks' ((n + 63) / 64 words): the bit is set iff the record is kept, has
+ * a comparable key and the key is in the truth set.  kept & ~mask: the records whose distinct keys QM_S_FP_R counts. */
+int qm_batch_get_intruth_mask(qm_batch* b, int vcf, uint64_t* mask);
+/* Group g holds the VCFs vcf_ids[group_offsets[g] .. group_offsets[g + 1]): 1 to QM_TRUTH_GROUP_MAX distinct VCFs of this batch
+ * that share one truth set (anything else: QM_E_INVAL).  regions[g][m] = the truth keys whose membership mask over the group's
+ * VCFs is m (bit i = member i hit it): slot 0 = keys no member hit, slots at and above 1 << n are 0, the slots sum to T'.
+ * union_bits (may be NULL): per group, one behind the other, the (T' + 31) / 32 words of the OR of its members' bitmaps.
+ * Blocking.  QM_E_STATE without a qm_batch_truth_hits behind the latest run. */
+int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids,
+                           uint64_t* regions /*[n_groups][QM_TRUTH_REGIONS]*/, uint32_t* union_bits);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -458,6 +483,30 @@ int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_
 int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                             void* global_dev, const int32_t* genome_id, uint64_t* motifs);
+
+/* qm_extract_files_ex plus the truth-side view over its batch (single-base mode only: QM_E_STATE otherwise).
+ * fn_out[j] (or NULL): a missed-variant list for job j -- the header ('#') lines of its truth file, then, in file order, every
+ * data row whose key the reference would have put into `Genome` (make_snp_vector, scripts/caller_performance_compare.R:29-55:
+ * single-base REF and ALT; custom mode: custom_snp_benchmark.R:23-27) and that is not among the VCF's kept single-base keys; a
+ * key on several rows is written on each.  Pure-strain jobs write none (the reference never reads their truth).
+ * group[j]: -1 or a group id < n_groups; a group holds 1 to QM_TRUTH_GROUP_MAX mixed-sample jobs of one truth file, its members
+ * in job order (anything else: QM_E_INVAL).  regions[g][m]: qm_batch_truth_regions' slots.  fp_regions[g][m] (may be NULL):
+ * qm_fp_overlap's slots over the members' kept keys that are NOT in the truth set (the regions without the `Genome` bit).
+ * missed_out[g] (array or entries may be NULL): the list of the rows no member hit.
+ * R compares keys as text.  A VCF that asks for a list or sits in a group and holds a kept line without a comparable key
+ * (QM_F_NOKEY) is refused with QM_E_NONCANON and a message that names the line: its text key has no place in the bitmaps. */
+typedef struct qm_truthside_args {
+  const char* const* fn_out;      /* [n_jobs] */
+  const int32_t* group;           /* [n_jobs] */
+  int32_t n_groups;
+  int32_t reserved;
+  uint64_t* regions;              /* [n_groups][QM_TRUTH_REGIONS] */
+  int64_t* fp_regions;            /* [n_groups][QM_TRUTH_REGIONS] or NULL */
+  const char* const* missed_out;  /* [n_groups] or NULL */
+} qm_truthside_args;
+int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                               qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                               void* global_dev, const qm_truthside_args* ts);
 
 /* `bgzip -c` (the *.vcf.gz outputs the same rules declare, rules/vis_eval_vcf.smk:29,36 ...): BGZF = gzip members of at
  * most 64 KiB with a 'BC' extra field + the EOF member; zcat and tabix / htslib read it.  level -1 = zlib's default (6,

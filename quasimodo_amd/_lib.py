@@ -18,6 +18,8 @@ QM_N_MOTIFS = 96
 QM_MOTIF_OTHER = 96
 QM_MOTIF_REF_MISMATCH = 97
 QM_MOTIF_COLS = 98
+QM_TRUTH_GROUP_MAX = 5
+QM_TRUTH_REGIONS = 32
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -33,6 +35,7 @@ EXPORTS = (
     "qm_mummer2vcf", "qm_free",
     "qm_comm_create", "qm_comm_make_id", "qm_comm_create_rank", "qm_allreduce_counters", "qm_comm_collectives", "qm_comm_destroy",
     "qm_genome_load", "qm_genome_release", "qm_batch_motifs", "qm_batch_get_motifs", "qm_extract_files_motifs",
+    "qm_batch_truth_hits", "qm_batch_get_truth_hits", "qm_batch_get_intruth_mask", "qm_batch_truth_regions", "qm_extract_files_truthside",
 )
 
 
@@ -51,6 +54,12 @@ class QmvtError(RuntimeError):
 class SynthCfg(C.Structure):
     _fields_ = [("genome_len", C.c_int64), ("seed", C.c_uint64), ("truth_seed", C.c_uint64), ("truth_n", C.c_int64),
                 ("shuffled", C.c_int32), ("indel_pct", C.c_int32)]
+
+
+class TruthSideArgs(C.Structure):
+    """include/qmvt.h qm_truthside_args"""
+    _fields_ = [("fn_out", C.POINTER(C.c_char_p)), ("group", C.c_void_p), ("n_groups", C.c_int32), ("reserved", C.c_int32),
+                ("regions", C.c_void_p), ("fp_regions", C.c_void_p), ("missed_out", C.POINTER(C.c_char_p))]
 
 
 class FileJob(C.Structure):
@@ -73,7 +82,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -234,6 +243,12 @@ def lib():
     L.qm_batch_get_motifs.argtypes = [vp, vp]
     L.qm_extract_files_motifs.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                           vp, vp]
+    L.qm_batch_truth_hits.argtypes = [vp, vp]
+    L.qm_batch_get_truth_hits.argtypes = [vp, i32, vp, i64]
+    L.qm_batch_get_intruth_mask.argtypes = [vp, i32, vp]
+    L.qm_batch_truth_regions.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.qm_extract_files_truthside.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                             C.POINTER(TruthSideArgs)]
     _lib = L
     return L
 

@@ -23,6 +23,7 @@
 #include "../../include/qmvt.h"
 #include "qmvt_dev.h"
 #include "qmvt_motif.h"
+#include "qmvt_truthside.h"
 
 using namespace qm;
 
@@ -561,6 +562,15 @@ struct qm_batch {
   GenomeRef* h_mgen = nullptr;
   hipEvent_t ev_motif = nullptr;
   bool motifs_valid = false;          // qm_batch_motifs was called behind the latest run
+  // qm_batch_truth_hits (lazy): the per-VCF hit bitmaps one behind the other (h_hit_off[v] = first word of VCF v,
+  // h_hit_off[n_vcf] = all), the record mask (the size of mask_pass), the lookup counter; ev_truth says when the pass is done
+  uint32_t* d_hits = nullptr;
+  uint64_t* d_intruth = nullptr;
+  int64_t* d_hit_off = nullptr;
+  std::vector<int64_t> h_hit_off, h_hit_tn;   // h_hit_tn[v]: T' of VCF v's truth set when the bitmaps were sized
+  bool hit_off_uploaded = false, intruth_cleared = false, hits_enqueued = false;
+  hipEvent_t ev_truth = nullptr;
+  bool hits_valid = false;            // qm_batch_truth_hits was called behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -588,6 +598,8 @@ static void batch_free(qm_batch* b) {
   (void)hipFree(b->d_motifs); (void)hipFree(b->d_mgen);
   if (b->h_mgen) (void)hipHostFree(b->h_mgen);
   if (b->ev_motif) (void)hipEventDestroy(b->ev_motif);
+  (void)hipFree(b->d_hits); (void)hipFree(b->d_intruth); (void)hipFree(b->d_hit_off);
+  if (b->ev_truth) (void)hipEventDestroy(b->ev_truth);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -910,6 +922,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->ran = true;
   b->finished = false;
   b->motifs_valid = false;
+  b->hits_valid = false;
   b->last_global = g;
   return QM_OK;
 }
@@ -2083,6 +2096,149 @@ extern "C" int qm_batch_get_motifs(qm_batch* b, uint64_t* out) {
   HIPCHK(hipSetDevice(b->ctx->dev));
   HIPCHK(hipEventSynchronize(b->ev_motif));
   HIPCHK(hipMemcpy(out, b->d_motifs, (size_t)b->n_vcf * MOTIF_ROW_WORDS * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+// the truth-side view of the finished batch
+extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
+  NEED_FINISHED(b, "qm_batch_truth_hits");
+  qm_ctx* c = b->ctx;
+  if (b->ext) return fail(QM_E_STATE, "qm_batch_truth_hits: allele-extended batches have no truth-side bitmaps (single-base batches only)");
+  for (const auto& tg : b->truth_gens)
+    if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
+      return fail(QM_E_STATE, "qm_batch_truth_hits: truth set %d was released after the batch was created", tg.first);
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const size_t nv = (size_t)b->n_vcf;
+  const size_t mask_words = (size_t)b->L.n_pad / 64 + 64;   // as mask_pass
+  // first use: every buffer guarded on its own (a call that failed half way leaks nothing when it is repeated); the sizes follow
+  // from the truth sets' T', which cannot change while the generations above hold
+  if (b->h_hit_tn.empty()) {
+    b->h_hit_off.assign(nv + 1, 0);
+    b->h_hit_tn.assign(nv, 0);
+    for (size_t v = 0; v < nv; ++v) {
+      b->h_hit_tn[v] = c->truths[(size_t)b->L.vcfs[v].truth].n;
+      b->h_hit_off[v + 1] = b->h_hit_off[v] + (b->h_hit_tn[v] + 31) / 32;
+    }
+  }
+  const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
+  if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
+  else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
+  if (!b->d_hit_off) {
+    DALLOC(b->d_hit_off, nv + 1);
+    b->dev_bytes += (int64_t)((nv + 1) * 8);
+    b->hit_off_uploaded = false;
+  }
+  if (!b->hit_off_uploaded) {
+    HIPCHK(hipMemcpy(b->d_hit_off, b->h_hit_off.data(), (nv + 1) * 8, hipMemcpyHostToDevice));
+    b->hit_off_uploaded = true;
+  }
+  if (!b->d_intruth) {
+    DALLOC(b->d_intruth, mask_words);
+    b->dev_bytes += (int64_t)(mask_words * 8);
+    b->intruth_cleared = false;
+  }
+  if (!b->intruth_cleared) {
+    HIPCHK(hipMemsetAsync(b->d_intruth, 0, mask_words * 8, st));   // the bytes between the VCFs are never written again
+    b->intruth_cleared = true;
+  }
+  if (!b->d_hits) {
+    DALLOC(b->d_hits, hw);
+    b->dev_bytes += (int64_t)(hw * 4);
+  }
+  HIPCHK(hipMemsetAsync(b->d_hits, 0, hw * 4, st));
+  TruthHitsParams P;
+  P.spans = b->d_spans; P.truths = c->d_truths; P.hit_off = b->d_hit_off;
+  P.pos = b->pos; P.anib = b->anib; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  P.hits = b->d_hits; P.mask_intruth = reinterpret_cast<uint8_t*>(b->d_intruth);
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_truth_hits(P, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(b->ev_truth, st));
+  b->hits_enqueued = true;
+  b->hits_valid = true;
+  return QM_OK;
+}
+#define NEED_HITS(b, name) \
+  if (!(b)) return fail(QM_E_INVAL, name ": NULL batch"); \
+  if (!(b)->hits_valid) return fail(QM_E_STATE, name ": no qm_batch_truth_hits behind the latest run")
+extern "C" int qm_batch_get_truth_hits(qm_batch* b, int v, uint32_t* bits, int64_t n_words) {
+  NEED_HITS(b, "qm_batch_get_truth_hits");
+  if (v < 0 || v >= b->n_vcf || (!bits && n_words)) return fail(QM_E_INVAL, "qm_batch_get_truth_hits: bad arguments");
+  const int64_t have = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
+  if (n_words != have) return fail(QM_E_INVAL, "qm_batch_get_truth_hits: VCF %d has %lld words, not %lld", v, (long long)have, (long long)n_words);
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_truth));
+  if (have) HIPCHK(hipMemcpy(bits, b->d_hits + b->h_hit_off[(size_t)v], (size_t)have * 4, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_intruth_mask(qm_batch* b, int v, uint64_t* mask) {
+  NEED_HITS(b, "qm_batch_get_intruth_mask");
+  if (v < 0 || v >= b->n_vcf || !mask) return fail(QM_E_INVAL, "qm_batch_get_intruth_mask: bad arguments");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_truth));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  const size_t nw = (size_t)((d.n + 63) / 64);
+  if (nw) {
+    HIPCHK(hipMemcpy(mask, b->d_intruth + (d.off >> 6), nw * 8, hipMemcpyDeviceToHost));
+    if (d.n & 63) mask[nw - 1] &= (1ull << (d.n & 63)) - 1ull;
+  }
+  return QM_OK;
+}
+extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, uint64_t* regions,
+                                      uint32_t* union_bits) {
+  NEED_HITS(b, "qm_batch_truth_regions");
+  if (n_groups < 0 || (n_groups && (!group_offsets || !vcf_ids || !regions))) return fail(QM_E_INVAL, "qm_batch_truth_regions: bad arguments");
+  if (n_groups == 0) return QM_OK;
+  std::vector<TruthGroup> G((size_t)n_groups);
+  std::vector<int64_t> uoff((size_t)n_groups + 1, 0);
+  int64_t max_words = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    const int32_t o0 = group_offsets[g], o1 = group_offsets[g + 1];
+    if (o0 < 0 || o1 - o0 < 1 || o1 - o0 > TS_MAX_GROUP)
+      return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d has %d VCFs (1 to %d)", g, o1 - o0, TS_MAX_GROUP);
+    TruthGroup& t = G[(size_t)g];
+    memset(&t, 0, sizeof t);
+    t.n = o1 - o0;
+    int truth = -1;
+    for (int i = 0; i < t.n; ++i) {
+      const int v = vcf_ids[o0 + i];
+      if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d names VCF %d (the batch has %d)", g, v, b->n_vcf);
+      for (int k = 0; k < i; ++k)
+        if (vcf_ids[o0 + k] == v) return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d names VCF %d twice", g, v);
+      const int tv = b->L.vcfs[(size_t)v].truth;
+      if (i == 0) truth = tv;
+      else if (tv != truth) return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d mixes truth sets %d and %d", g, truth, tv);
+      t.bits[i] = b->d_hits + b->h_hit_off[(size_t)v];
+      t.words = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
+    }
+    t.tn = b->h_hit_tn[(size_t)vcf_ids[o0]];   // T' as it was when the bitmaps were sized (qm_batch_truth_hits checked the generations)
+    uoff[(size_t)g + 1] = uoff[(size_t)g] + t.words;
+    max_words = std::max(max_words, t.words);
+  }
+  qm_ctx* c = b->ctx;
+  HIPCHK(hipSetDevice(c->dev));
+  HIPCHK(hipEventSynchronize(b->ev_truth));
+  TruthGroup* d_groups = nullptr;
+  unsigned long long* d_reg = nullptr;
+  uint32_t* d_uni = nullptr;
+  int rc = dalloc(&d_groups, (size_t)n_groups);
+  if (rc == QM_OK) rc = dalloc(&d_reg, (size_t)n_groups * TS_REGIONS);
+  if (rc == QM_OK && union_bits) rc = dalloc(&d_uni, (size_t)uoff[(size_t)n_groups]);
+  hipError_t e = hipSuccess;
+  if (rc == QM_OK) {
+    if (d_uni) for (int g = 0; g < n_groups; ++g) G[(size_t)g].uni = d_uni + uoff[(size_t)g];
+    e = hipMemcpyAsync(d_groups, G.data(), sizeof(TruthGroup) * (size_t)n_groups, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_reg, 0, (size_t)n_groups * TS_REGIONS * 8, c->stream);
+    if (e == hipSuccess) { launch_truth_regions(d_groups, n_groups, max_words, d_reg, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(regions, d_reg, (size_t)n_groups * TS_REGIONS * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && d_uni && uoff[(size_t)n_groups])
+      e = hipMemcpyAsync(union_bits, d_uni, (size_t)uoff[(size_t)n_groups] * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (G stays alive until here)
+  }
+  (void)hipFree(d_groups); (void)hipFree(d_reg); (void)hipFree(d_uni);
+  if (rc != QM_OK) return rc;
+  if (e != hipSuccess) return fail(QM_E_HIP, "qm_batch_truth_regions: %s", hipGetErrorString(e));
   return QM_OK;
 }
 // dst[i] += src[i] for device arrays (qm_extract_files_ex adds the per-truth sums of its batch into the caller's buffer)

@@ -17,6 +17,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -149,9 +150,72 @@ struct TruthState {
   int64_t info[4] = {0, 0, 0, 0}, counts[5] = {0, 0, 0, 0, 0};
   int tid = -1;
   int rc = QM_OK;
+  std::vector<uint32_t> keys;   // (truth-side calls) the sorted distinct single-base keys, as the device holds them
 };
 
 int fail(int code, const std::string& msg) { qm_set_error(msg.c_str()); return code; }
+
+// ---- missed-variant lists ----
+bool ts_canon_pos(const uint8_t* s, size_t n, uint32_t* out) {   // "0" or [1-9][0-9]*, value < 2^28: qmvt_host.cpp's rule
+  if (n == 0 || n > 9 || (n > 1 && s[0] == '0')) return false;
+  uint32_t v = 0;
+  for (size_t i = 0; i < n; ++i) { if (s[i] < '0' || s[i] > '9') return false; v = v * 10 + (uint32_t)(s[i] - '0'); }
+  if (v >= (uint32_t)QM_POS_LIMIT) return false;
+  *out = v;
+  return true;
+}
+int ts_base(const uint8_t* s, size_t n) {
+  if (n != 1) return -1;
+  switch (s[0]) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; }
+}
+int write_all_atomic(const char* path, const std::string& data) {
+  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
+  FILE* fh = fopen(tmp.c_str(), "wb");
+  if (!fh) return QM_E_IO;
+  const bool ok = data.empty() || fwrite(data.data(), 1, data.size(), fh) == data.size();
+  if (fclose(fh) != 0 || !ok || rename(tmp.c_str(), path) != 0) { (void)unlink(tmp.c_str()); return QM_E_IO; }
+  return QM_OK;
+}
+// The truth file's '#' lines, then, in file order, every data row whose key the reference puts into `Genome` (mode 0: single-base
+// REF and ALT, caller_performance_compare.R:29-55; mode 1: neither SUB column '.', custom_snp_benchmark.R:23-27) and whose bit
+// in `bits` (over the truth set's sorted distinct keys) is clear.  A row whose key the device cannot hold (POS spelled
+// non-canonically, a longer allele in mode 1) could only be matched by a kept line without a comparable key; the caller refuses
+// VCFs that have such lines, so the row is a missed one.
+int write_fn_file(const char* path, const TruthState& t, const uint32_t* bits) {
+  std::string head, rows;
+  const uint8_t* text = t.file.p;
+  const size_t len = t.file.n;
+  size_t off = 0;
+  while (off < len) {
+    const uint8_t* s = text + off;
+    const uint8_t* e = (const uint8_t*)memchr(s, '\n', len - off);
+    const size_t n = e ? (size_t)(e - s) : len - off;
+    off += n + 1;
+    if (n && s[0] == '#') { head.append((const char*)s, n); head.push_back('\n'); continue; }
+    const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+    const uint8_t* q = s;
+    while (nf < 6) {
+      const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(s + n - q));
+      f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(s + n - q); ++nf;
+      if (!tb) break;
+      q = tb + 1;
+    }
+    const int ix = t.mode == 0 ? 1 : 0, iy = t.mode == 0 ? 3 : 1, iz = t.mode == 0 ? 4 : 2;
+    if (nf <= iz) continue;
+    const int y = ts_base(f[iy], fl[iy]), z = ts_base(f[iz], fl[iz]);
+    const bool in_genome = t.mode == 0 ? (y >= 0 && z >= 0) : (n > 0 && !(fl[iy] == 1 && f[iy][0] == '.') && !(fl[iz] == 1 && f[iz][0] == '.'));
+    if (!in_genome) continue;
+    bool hit = false;
+    uint32_t p = 0;
+    if (y >= 0 && z >= 0 && ts_canon_pos(f[ix], fl[ix], &p)) {
+      const uint32_t key = (p << 4) | ((uint32_t)y << 2) | (uint32_t)z;
+      const auto it = std::lower_bound(t.keys.begin(), t.keys.end(), key);
+      if (it != t.keys.end() && *it == key && bits) { const size_t k = (size_t)(it - t.keys.begin()); hit = (bits[k >> 5] >> (k & 31)) & 1u; }
+    }
+    if (!hit) { rows.append((const char*)s, n); rows.push_back('\n'); }
+  }
+  return write_all_atomic(path, head + rows);
+}
 
 }  // namespace
 
@@ -173,12 +237,12 @@ extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out);
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts);
 
 extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                    qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
                                    int n_slots, void* global_dev) {
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr);
 }
 
 // rule mutationcontext behind the worker: the motif pass runs on the batch the classification leaves in HBM
@@ -187,12 +251,34 @@ extern "C" int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_jo
                                        int n_slots, void* global_dev, const int32_t* genome_id, uint64_t* motifs_out) {
   if (n_jobs > 0 && (!genome_id || !motifs_out)) return fail(QM_E_INVAL, "qm_extract_files_motifs: NULL genome ids or output");
   if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr);
+}
+
+// the truth-side view behind the worker: missed-variant lists and the caller Venn regions of groups of jobs
+extern "C" int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                          qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                          int n_slots, void* global_dev, const qm_truthside_args* ts) {
+  if (!ts || ts->n_groups < 0 || (n_jobs > 0 && (!ts->fn_out || !ts->group)) || (ts->n_groups > 0 && !ts->regions))
+    return fail(QM_E_INVAL, "qm_extract_files_truthside: NULL arguments");
+  if (mode & QM_BATCH_ALLELES) return fail(QM_E_STATE, "qm_extract_files_truthside: allele-extended batches have no truth-side view (single-base batches only)");
+  for (int g = 0; g < ts->n_groups; ++g) {
+    int members = 0;
+    for (int j = 0; j < n_jobs; ++j) members += ts->group[j] == g;
+    if (members < 1 || members > QM_TRUTH_GROUP_MAX)
+      return fail(QM_E_INVAL, "qm_extract_files_truthside: group " + std::to_string(g) + " has " + std::to_string(members) + " jobs (1 to 5)");
+  }
+  for (int j = 0; j < n_jobs; ++j) {
+    if (ts->group[j] < -1 || ts->group[j] >= ts->n_groups) return fail(QM_E_INVAL, "qm_extract_files_truthside: job " + std::to_string(j) + " names group " + std::to_string(ts->group[j]));
+    if (jobs[j].pure && ts->group[j] >= 0) return fail(QM_E_INVAL, "qm_extract_files_truthside: pure-strain job " + std::to_string(j) + " cannot be in a group (its truth is never read)");
+  }
+  memset(ts->regions, 0, sizeof(uint64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
+  if (ts->fp_regions) memset(ts->fp_regions, 0, sizeof(int64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, ts);
 }
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out) {
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
     return fail(QM_E_INVAL, "qm_extract_files: bad arguments");
   if (global_dev && (n_slots < 1 || (n_jobs && !truth_slot))) return fail(QM_E_INVAL, "qm_extract_files_ex: global_dev needs truth_slot and n_slots >= 1");
@@ -302,6 +388,12 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (k < 0) { truth_rc = (int)k; truth_msg = "qm_truth_scan failed for " + t.path; break; }
       const int rc = qm_truth_load(ctx, tp.data(), tr.data(), ta.data(), k, &t.tid);
       if (rc != QM_OK) { truth_rc = rc; truth_msg = qm_last_error(ctx); break; }
+      if (ts) {
+        for (int64_t i = 0; i < k; ++i)
+          if ((uint32_t)(tr[(size_t)i] | ta[(size_t)i]) < 4u) t.keys.push_back(((uint32_t)tp[(size_t)i] << 4) | ((uint32_t)tr[(size_t)i] << 2) | (uint32_t)ta[(size_t)i]);
+        std::sort(t.keys.begin(), t.keys.end());
+        t.keys.erase(std::unique(t.keys.begin(), t.keys.end()), t.keys.end());
+      }
     }
     add_ph(1, now() - tt0, trace ? cpu_now() - tc0 : 0.0);
     { std::lock_guard<std::mutex> g(pats_mu); keys_ready = true; }
@@ -448,6 +540,90 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
               memcpy(motifs_out + (size_t)j * 3 * QM_MOTIF_COLS, &mo[(size_t)J[(size_t)j].batch_v * 3 * QM_MOTIF_COLS], sizeof(uint64_t) * 3 * QM_MOTIF_COLS);
         }
       }
+      std::vector<std::vector<uint32_t>> hitbits, unibits;
+      std::vector<std::vector<int>> members;
+      if (rc == QM_OK && ts) {   // the truth-side pass behind the classification, on the columns and masks still in HBM
+        // R keys a kept line by its TEXT; a kept line without a comparable key has none the bitmaps could hold: refuse it by name
+        for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
+          const JobState& s = J[(size_t)j];
+          if (jobs[j].pure || (!ts->fn_out[j] && ts->group[j] < 0) || s.info.n_nokey_kept == 0) continue;
+          int64_t line = 0, rec = 0;
+          for (int64_t i = 0; i < s.info.n_lines && !line; ++i) {
+            const uint8_t k = s.line_kind[(size_t)i];
+            if (k == QM_LINE_HEADER || k == QM_LINE_HEADER_KEPT || k == QM_LINE_HEADER_KEPT_TP || k == QM_LINE_HEADER_REFUSED) continue;
+            if ((s.flags[rec] & QM_F_PASS) && (s.flags[rec] & QM_F_NOKEY)) line = i + 1;
+            ++rec;
+          }
+          err = std::string(jobs[j].vcf_path) + " line " + std::to_string(line) + ": a kept line has no comparable key (POS is not a canonical decimal) -- "
+                "the truth-side view compares keys, not text, and does not take this VCF";
+          rc = QM_E_NONCANON;
+        }
+        if (rc == QM_OK) { rc = qm_batch_truth_hits(batch, nullptr); if (rc != QM_OK) err = qm_last_error(ctx); }
+        hitbits.resize((size_t)n_jobs);
+        for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
+          if (jobs[j].pure || !ts->fn_out[j]) continue;
+          const TruthState& t = T[(size_t)J[(size_t)j].truth];
+          hitbits[(size_t)j].assign((t.keys.size() + 31) / 32, 0u);
+          rc = qm_batch_get_truth_hits(batch, J[(size_t)j].batch_v, hitbits[(size_t)j].data(), (int64_t)hitbits[(size_t)j].size());
+          if (rc != QM_OK) err = qm_last_error(ctx);
+        }
+        if (rc == QM_OK && ts->n_groups > 0) {
+          members.resize((size_t)ts->n_groups);
+          for (int j = 0; j < n_jobs; ++j) if (ts->group[j] >= 0) members[(size_t)ts->group[j]].push_back(j);
+          std::vector<int32_t> goff(1, 0), gids;
+          size_t uw = 0;
+          for (const auto& m : members) {
+            for (int j : m) gids.push_back(J[(size_t)j].batch_v);
+            goff.push_back((int32_t)gids.size());
+            uw += (T[(size_t)J[(size_t)m[0]].truth].keys.size() + 31) / 32;
+          }
+          std::vector<uint32_t> uni(uw + 1, 0u);
+          rc = qm_batch_truth_regions(batch, ts->n_groups, goff.data(), gids.data(), ts->regions, uni.data());
+          if (rc != QM_OK) err = qm_last_error(ctx);
+          unibits.resize((size_t)ts->n_groups);
+          size_t o = 0;
+          for (size_t g = 0; g < members.size() && rc == QM_OK; ++g) {
+            const size_t nw = (T[(size_t)J[(size_t)members[g][0]].truth].keys.size() + 31) / 32;
+            unibits[g].assign(uni.begin() + (long)o, uni.begin() + (long)(o + nw));
+            o += nw;
+          }
+          // the callers' side of the Venn: the keys of the kept records outside the in-truth record mask, through qm_fp_overlap
+          for (size_t g = 0; g < members.size() && rc == QM_OK && ts->fp_regions; ++g) {
+            std::vector<int64_t> so(1, 0);
+            std::vector<int32_t> kp, kr, ka;
+            for (int j : members[g]) {
+              const JobState& s = J[(size_t)j];
+              std::vector<uint64_t> kept((size_t)(s.n_data + 63) / 64 + 1), tpm(kept.size()), in(kept.size());
+              rc = qm_batch_get_masks(batch, s.batch_v, kept.data(), tpm.data());
+              if (rc == QM_OK) rc = qm_batch_get_intruth_mask(batch, s.batch_v, in.data());
+              if (rc != QM_OK) { err = qm_last_error(ctx); break; }
+              for (int64_t r = 0; r < s.n_data; ++r)
+                if (((kept[(size_t)r >> 6] & ~in[(size_t)r >> 6]) >> (r & 63)) & 1ull) { kp.push_back(s.pos[r]); kr.push_back(s.ref[r]); ka.push_back(s.alt[r]); }
+              so.push_back((int64_t)kp.size());
+            }
+            if (rc != QM_OK) break;
+            int64_t reg[QM_TRUTH_REGIONS] = {0};
+            int32_t dummy = 0;
+            rc = qm_fp_overlap(ctx, (int)members[g].size(), so.data(), kp.empty() ? &dummy : kp.data(), kr.empty() ? &dummy : kr.data(),
+                               ka.empty() ? &dummy : ka.data(), reg);
+            if (rc != QM_OK) { err = qm_last_error(ctx); break; }
+            memcpy(ts->fp_regions + g * QM_TRUTH_REGIONS, reg, sizeof reg);
+          }
+        }
+        // the lists: one per job that asked, one per group that asked (missed by every member)
+        if (rc == QM_OK) {
+          struct FTask { const char* path; const TruthState* t; const uint32_t* bits; };
+          std::vector<FTask> F;
+          for (int j = 0; j < n_jobs; ++j)
+            if (!jobs[j].pure && ts->fn_out[j]) F.push_back({ts->fn_out[j], &T[(size_t)J[(size_t)j].truth], hitbits[(size_t)j].data()});
+          for (size_t g = 0; g < members.size(); ++g)
+            if (ts->missed_out && ts->missed_out[g]) F.push_back({ts->missed_out[g], &T[(size_t)J[(size_t)members[g][0]].truth], unibits[g].data()});
+          std::vector<int> frc(F.size(), QM_OK);
+          parallel_for((int)F.size(), nthr, [&](int k) { frc[(size_t)k] = write_fn_file(F[(size_t)k].path, *F[(size_t)k].t, F[(size_t)k].bits); });
+          for (size_t k = 0; k < F.size() && rc == QM_OK; ++k)
+            if (frc[k] != QM_OK) { rc = frc[k]; err = std::string("cannot write ") + F[k].path; }
+        }
+      } else
       if (rc != QM_OK) err = qm_last_error(ctx);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

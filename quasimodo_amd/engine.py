@@ -150,13 +150,17 @@ class Engine:
         check(self._L.qm_bench_synth(self._h, C.byref(cfg), int(n_vcf), int(records), int(n_bins), int(steps), C.byref(r)), self._h)
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
-    def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None):
+    def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
+                      truthside=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
         this call's VCFs land in rows truth_slots[j] of the caller's [n_slots][3][n_bins] uint64 device buffer (cleared first).
         genomes: per-job genome ids (genome_load) or None / -1; when any job has one, qm_extract_files_motifs runs and every row
         gains `motifs` ([3][QM_MOTIF_COLS] uint64: kept, TP, FP).
+        truthside: {"fn": [path or None per job], "group": [group id or -1 per job], "missed": [path or None per group]} --
+        qm_extract_files_truthside: the missed-variant lists are written, the rows of grouped jobs gain
+        `truth_regions` and `fp_regions` (int64 [32] each, the same for every member; members in job order).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         import os
         n = len(file_jobs)
@@ -175,7 +179,23 @@ class Engine:
             raise ValueError("genomes: %d entries for %d jobs" % (len(gids), n))
         args = (self._h, n, arr, int(n_bins), _lib.QM_BATCH_ALLELES if alleles else 0, int(bool(strict)), st, _p(roc), ph,
                 _p(slots), int(n_slots), C.c_void_p(global_dev) if global_dev else None)
-        if gids is not None and any(g >= 0 for g in gids):
+        regs = None
+        if truthside is not None:
+            if gids is not None and any(g >= 0 for g in gids):
+                raise ValueError("truthside and genomes in one call are not supported")
+            enc = lambda x: None if x is None else os.fsencode(x)
+            grp = _c([-1 if g is None else int(g) for g in truthside["group"]] or [-1], np.int32)
+            ng = len(truthside.get("missed") or []) or (int(grp.max()) + 1 if n else 0)
+            if len(truthside["fn"]) != n or (n and grp.shape[0] != n):
+                raise ValueError("truthside: %d fn / %d group entries for %d jobs" % (len(truthside["fn"]), grp.shape[0], n))
+            fn_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in truthside["fn"]])
+            missed = list(truthside.get("missed") or [None] * ng)
+            ms_arr = (C.c_char_p * max(ng, 1))(*[enc(x) for x in missed])
+            regs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.uint64)
+            fregs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.int64)
+            ta = _lib.TruthSideArgs(fn_arr, _p(grp), ng, 0, _p(regs), _p(fregs), ms_arr)
+            check(self._L.qm_extract_files_truthside(*args, C.byref(ta)), self._h)
+        elif gids is not None and any(g >= 0 for g in gids):
             motifs = np.zeros((n, 3, _lib.QM_MOTIF_COLS), np.uint64)
             check(self._L.qm_extract_files_motifs(*args, _p(_c(gids, np.int32)), _p(motifs)), self._h)
         else:
@@ -188,6 +208,9 @@ class Engine:
                      roc=roc[k].copy())
             if motifs is not None:
                 r["motifs"] = motifs[k].copy()
+            if regs is not None and grp[k] >= 0:
+                r["truth_regions"] = regs[grp[k]].astype(np.int64)
+                r["fp_regions"] = fregs[grp[k]].copy()
             rows.append(r)
         phases = dict(zip(("map_count", "truth_beside", "batch_layout", "tokenise_upload", "engine", "masks_back", "write", "release"), list(ph)))
         return rows, phases
@@ -330,6 +353,55 @@ class Batch:
         out = np.zeros((self.n_vcf, 3, _lib.QM_MOTIF_COLS), np.uint64)
         self._ck(self._L.qm_batch_get_motifs(self._h, _p(out)))
         return out
+
+    # -- the truth-side view -------------------------------------
+    def truth_hits(self, stream=None):
+        """qm_batch_truth_hits: enqueue the truth-side pass of the finished batch (hit bitmaps + the in-truth record mask)"""
+        self._ck(self._L.qm_batch_truth_hits(self._h, C.c_void_p(stream) if stream else None))
+
+    def truth_hit_bits(self, v):
+        """qm_batch_get_truth_hits: bool[T'] -- entry k: some kept record of VCF v carries key k of the truth set's sorted
+        distinct keys (pos << 4 | ref << 2 | alt); its sum is the device's QM_S_TP_R"""
+        t = self.engine.truth_size(int(self.truth_ids[int(v)]))
+        w = np.zeros((t + 31) // 32, np.uint32)
+        self._ck(self._L.qm_batch_get_truth_hits(self._h, int(v), _p(w), int(w.shape[0])))
+        bits = np.unpackbits(w.view(np.uint8), bitorder="little").astype(bool)
+        if bits[t:].any():
+            raise RuntimeError("qm_batch_get_truth_hits: bits set beyond T' = %d" % t)
+        return bits[:t]
+
+    def intruth_mask(self, v):
+        """qm_batch_get_intruth_mask: bool[n] -- record r of VCF v is kept, has a comparable key, and the key is in the truth set"""
+        n = int(self.n_records[int(v)])
+        w = np.zeros((n + 63) // 64, np.uint64)
+        self._ck(self._L.qm_batch_get_intruth_mask(self._h, int(v), _p(w) if n else _p(np.zeros(1, np.uint64))))
+        return np.unpackbits(w.view(np.uint8), bitorder="little").astype(bool)[:n]
+
+    def truth_regions(self, groups, union=False):
+        """qm_batch_truth_regions.  groups: lists of 1..5 VCF ids that share a truth set.  Returns int64 [n_groups][32]:
+        [g][m] = truth keys whose membership mask over group g is m (bit i = groups[g][i] hit it; slot 0 = missed by all).
+        union=True: also a list of bool[T'] per group, the keys some member hit."""
+        groups = [[int(v) for v in g] for g in groups]
+        offs = np.zeros(len(groups) + 1, np.int32)
+        offs[1:] = np.cumsum([len(g) for g in groups])
+        ids = _c([v for g in groups for v in g] or [0], np.int32)
+        reg = np.zeros((max(len(groups), 1), _lib.QM_TRUTH_REGIONS), np.uint64)
+        ts, uni = [], None
+        if union:
+            for g in groups:   # (a group the library will refuse gets no room: it fails before it writes)
+                ok = g and all(0 <= v < self.n_vcf for v in g)
+                ts.append(self.engine.truth_size(int(self.truth_ids[g[0]])) if ok else 0)
+            uni = np.zeros(max(sum((t + 31) // 32 for t in ts), 1), np.uint32)
+        self._ck(self._L.qm_batch_truth_regions(self._h, len(groups), _p(offs), _p(ids), _p(reg), _p(uni) if union else None))
+        reg = reg[:len(groups)].astype(np.int64)
+        if not union:
+            return reg
+        out, o = [], 0
+        for t in ts:
+            nw = (t + 31) // 32
+            out.append(np.unpackbits(uni[o:o + nw].view(np.uint8), bitorder="little").astype(bool)[:t])
+            o += nw
+        return reg, out
 
     def path_stats(self):
         """qm_batch_path_stats: where the VCFs the last finish found out of order went"""

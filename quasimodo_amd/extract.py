@@ -40,6 +40,10 @@ class Job:
     fp_out: str = ""
     stats: dict = field(default_factory=dict)
     genome: str = None        # FASTA of the sample's genome: the mutation-context spectra come back in stats["motifs"]
+    # the truth-side view; mixed samples only
+    fn_out: str = None        # where the missed-variant list goes (extract_many(fn=True) derives it)
+    group: str = None         # label of the job's group (1 to 5 jobs of one truth file): stats gain truth_regions / fp_regions
+    missed_out: str = None    # where the group's missed-by-all list goes (any member may carry it)
 
 
 def _paths(job):
@@ -56,6 +60,12 @@ def _paths(job):
         job.tp_out = os.path.join(job.outdir, "tp", job.caller + ".tp.vcf")
     else:
         raise ValueError("data must be 'hcmv' or 'custom', got %r" % job.mode)
+
+
+def fn_path(job):
+    """the missed-variant list beside fp/ and tp/: fn/<x>.fn.vcf"""
+    d, base = os.path.split(job.fp_out)
+    return os.path.join(os.path.dirname(d), "fn", base[:-len(".fp.vcf")] + ".fn.vcf")
 
 
 def _strict_default():
@@ -75,7 +85,7 @@ def _alleles_default():
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None):
+                 genomes=None, fn=False, groups=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -85,7 +95,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     truth_slots / n_slots / global_dev: this call is one rank's share of a multi-GPU run (Engine.extract_files).
     genomes: per job a FASTA path (one sequence) or None (default: Job.genome): the jobs that have one get
     stats["motifs"], their [3][98] mutation-context rows (kept, TP, FP; quasimodo_amd.motifs).  Every distinct FASTA is
-    loaded once and released before this returns."""
+    loaded once and released before this returns.
+    fn=True: every mixed-sample job also gets fn/<x>.fn.vcf (Job.fn_out), the rows of its truth file no kept record carries.
+    groups: lists of job indices (1 to 5 mixed-sample jobs of one truth file each; default: the jobs' Job.group labels): the
+    members' stats gain truth_regions / fp_regions (quasimodo_amd.truthside.venn_counts), members in job order.  Over several
+    GPUs a group must sit on one rank (WorkflowError otherwise)."""
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
     if genomes is not None:
@@ -93,11 +107,30 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             raise ValueError("genomes: %d entries for %d jobs" % (len(genomes), len(jobs)))
         for j, g in zip(jobs, genomes):
             j.genome = g
+    if groups is not None:
+        from .truthside import MAX_GROUP
+        for k, g in enumerate(groups):
+            if not 1 <= len(g) <= MAX_GROUP:
+                raise ValueError("a truth-side group holds 1 to %d jobs, not %d" % (MAX_GROUP, len(g)))
+            for i in g:
+                if jobs[i].group is not None and jobs[i].group != "g%d" % k:
+                    raise ValueError("job %d sits in two groups" % i)
+                jobs[i].group = "g%d" % k
+    for j in jobs:
+        if fn and j.fn_out is None and not is_pure_strain(j.vcf_file):
+            _paths(j)
+            j.fn_out = fn_path(j)
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
         from .multigpu import extract_many_sharded
-        return extract_many_sharded(jobs, int(gpus), n_bins=n_bins, alleles=alleles, strict=strict)[0]
+        plan = None
+        if any(j.group is not None for j in jobs):   # the members of a truth-side group go to one rank
+            by = {}
+            for i, j in enumerate(jobs):
+                by.setdefault(("g", j.group) if j.group is not None else ("j", i), []).append(i)
+            plan = list(by.values())
+        return extract_many_sharded(jobs, int(gpus), n_bins=n_bins, alleles=alleles, strict=strict, groups=plan)[0]
     if alleles and any(j.mode != "hcmv" for j in jobs):
         raise ValueError("the allele-extended mode needs VCF truth sets (hcmv mode)")
     own = engine is None
@@ -111,6 +144,24 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         need = not all(pure) or any(j.genome for j in jobs)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
+    ts = None
+    if any((j.fn_out or j.group is not None) and not p for j, p in zip(jobs, pure)):
+        from .truthside import MAX_GROUP
+        labels = []
+        for j, p in zip(jobs, pure):
+            if j.group is not None and p:
+                raise ValueError("%s: a pure-strain sample cannot be in a truth-side group (its truth is never read)" % j.vcf_file)
+            if j.group is not None and j.group not in labels:
+                labels.append(j.group)
+        for lab in labels:
+            k = sum(j.group == lab for j in jobs)
+            if k > MAX_GROUP:
+                raise ValueError("truth-side group %r holds %d jobs (1 to %d)" % (lab, k, MAX_GROUP))
+        missed = [next((j.missed_out for j in jobs if j.group == lab and j.missed_out), None) for lab in labels]
+        ts = {"fn": [None if p else j.fn_out for j, p in zip(jobs, pure)],
+              "group": [-1 if j.group is None else labels.index(j.group) for j in jobs], "missed": missed}
+        for path in [x for x in ts["fn"] + missed if x]:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     try:
         for job, p in zip(jobs, pure):
             os.makedirs(os.path.dirname(job.fp_out) or ".", exist_ok=True)
@@ -132,7 +183,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                         loaded[j.genome] = engine.genome_load(read_fasta(j.genome))
                 gids = [loaded[j.genome] if j.genome else -1 for j in jobs]
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids)
+                                                global_dev=global_dev, genomes=gids, truthside=ts)
             extract_many.last_phases = phases
             # where the VCFs found out of order went (bucket paths / radix sort: a silent fall onto the slow path shows here)
             extract_many.last_paths = {k: v - before[k] for k, v in engine.path_stats_total().items()}

@@ -118,6 +118,12 @@ def run_rank(jobs, rank, world, backend="nccl", body=None, n_bins=256, alleles=N
     body = _resolve(body)
     shards = plan_shards(jobs, world, groups)
     mine = shards[rank]
+    where = {}
+    for r, sh in enumerate(shards):   # a truth-side group is joined on one GPU: its members must have been dealt to one rank
+        for i in sh:
+            if jobs[i].group is not None and where.setdefault(jobs[i].group, r) != r:
+                from .workflow import WorkflowError
+                raise WorkflowError("truth-side group %r: its VCFs are not all on one rank (deal the VCFs by group)" % jobs[i].group)
     device = 0 if same_device else rank
     keys, slot = truth_layout(jobs)
     opts = dict(n_bins=n_bins, alleles=alleles, strict=strict, slots=[slot[i] for i in mine], n_slots=len(keys), backend=backend,
@@ -208,7 +214,8 @@ def extract_many_sharded(jobs, gpus, backend="nccl", body=None, n_bins=256, alle
         _paths(j)
     timeout = DEFAULT_TIMEOUT if timeout is None else timeout
     with tempfile.TemporaryDirectory(prefix="qmvt_mgpu_") as tmp:
-        spec = {"jobs": [dict(vcf_file=j.vcf_file, snp_file=j.snp_file, mode=j.mode, outdir=j.outdir, caller=j.caller, genome=j.genome)
+        spec = {"jobs": [dict(vcf_file=j.vcf_file, snp_file=j.snp_file, mode=j.mode, outdir=j.outdir, caller=j.caller, genome=j.genome,
+                              fn_out=j.fn_out, group=j.group, missed_out=j.missed_out)
                          for j in jobs],
                 "world": gpus, "backend": backend, "body": body, "n_bins": n_bins, "alleles": alleles, "strict": strict,
                 "same_device": same_device, "result": os.path.join(tmp, "result.pkl"), "groups": groups, "post": post,

@@ -153,7 +153,7 @@ def hcmv_rank_post(engine, jobs, indices, args):
 
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
-                         _same_device=False, mutation_context=None):
+                         _same_device=False, mutation_context=None, truth_side=False):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -161,7 +161,10 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     compared callers of a sample meet on one rank and the FP overlap needs no exchange; every rank writes its own files,
     the confusion counters go through the one all-reduce, the rows come to this process for the three tables.
     mutation_context: {"TM": FASTA, "TA": FASTA} (rules/mutationcontext.smk): the motif pass runs behind the classification and
-    final_tables/{mix}.{caller}.mutationcontext.tsv is written for every caller and every mix that has samples."""
+    final_tables/{mix}.{caller}.mutationcontext.tsv is written for every caller and every mix that has samples.
+    truth_side: the truth set's side of the join: callers/{caller}/fn/{sample}.{ref}.{caller}.fn.vcf for every
+    mixed sample, nucmer/{sample}.missed_by_all.vcf over the Venn callers (rules/vis_eval_vcf.smk:2, those of the run) and
+    final_tables/caller_snp_venn.tsv."""
     callers = list(callers or SNPCALLERS)
     data_dir = ensure_bundle(data_dir)
     results = os.path.join(outpath.rstrip("/"), "results")
@@ -191,6 +194,17 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             for mix in mixes:
                 for c in callers:
                     print("mutationcontext\t%s\t%s" % (mix, c))
+        if truth_side:
+            from .truthside import venn_callers
+            for s, c, src in plan:
+                if not s.endswith(("-1-0", "-0-1")):
+                    print("truthside_fn\t%s\t%s" % (c, s))
+            vc = venn_callers(callers)
+            for s in samples:
+                if vc and not s.endswith(("-1-0", "-0-1")):
+                    print("missed_by_all\t%s\t%s" % (s, ",".join(vc)))
+            if vc:
+                print("caller_snp_venn\t%s" % ",".join(vc))
         return None
     os.makedirs(os.path.join(snp_dir, "nucmer"), exist_ok=True)
     for mix in ("TM", "TA"):                                           # cp_genome_diff
@@ -215,6 +229,17 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             if os.path.exists(t):
                 split_variants(t, os.path.join(snp_dir, "nucmer", "%s.maskrepeat.%s.vcf" % (mix, kind)), kind, bgz=True, tbi="if-sorted")
     mixed = [s for s in samples if not s.endswith(("-1-0", "-0-1"))]
+    if truth_side:
+        from .extract import _paths, fn_path
+        from .truthside import venn_callers
+        vc = venn_callers(callers)
+        for (c, s), j in zip(meta, jobs):
+            if s in mixed:
+                _paths(j)
+                j.fn_out = fn_path(j)
+                if c in vc:
+                    j.group = s
+                    j.missed_out = os.path.join(snp_dir, "nucmer", "%s.missed_by_all.vcf" % s)
     cmp_callers = [c for c in FP_COMPARED if c in callers]
     tables = os.path.join(results, "final_tables")
     if gpus is not None and (int(gpus) > 1 or _body):
@@ -231,6 +256,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         _write_snp_rocs(meta, jobs, snp_dir)
         if mutation_context is not None:
             _write_mutation_context(meta, jobs, tables, callers, mixes)
+        if truth_side:
+            _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
         if mixed and len(cmp_callers) >= 2:
             reg = {}
             for e in res["extras"]:
@@ -253,6 +280,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         _write_snp_rocs(meta, jobs, snp_dir)
         if mutation_context is not None:
             _write_mutation_context(meta, jobs, os.path.join(results, "final_tables"), callers, mixes)
+        if truth_side:
+            _write_caller_snp_venn(meta, jobs, os.path.join(results, "final_tables"), callers, mixed)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
         if mixed and len(cmp_callers) >= 2:                              # compareFP (counts only)
             files = {s: {c: j.fp_out for (c, ss), j in zip(meta, jobs) if ss == s and c in cmp_callers} for s in mixed}
@@ -265,6 +294,25 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
 
 
 run_hcmv_variantcall.last_result = None
+
+
+def _write_caller_snp_venn(meta, jobs, tables, callers, mixed):
+    """final_tables/caller_snp_venn.tsv (the numbers behind final_figures/caller_snp_venndiagram.pdf): per mixed sample the
+    regions of Genome + the Venn callers, from the rows of the sample's group (members in job order, put into the Venn callers' order)"""
+    from .truthside import reorder_regions, venn_callers, write_caller_snp_venn
+    vc = venn_callers(callers)
+    if not vc or not mixed:
+        return
+    per = {}
+    for s in mixed:
+        mem = [(c, j) for (c, ss), j in zip(meta, jobs) if ss == s and c in vc]
+        have = [c for c, _ in mem]
+        st = mem[0][1].stats
+        if len(mem) != len(vc) or "truth_regions" not in st:
+            raise WorkflowError("sample %s: no truth-side regions came back for its Venn callers" % s)
+        n = len(vc)
+        per[s] = (reorder_regions(st["truth_regions"][:1 << n], have, vc), reorder_regions(st["fp_regions"][:1 << n], have, vc))
+    write_caller_snp_venn(os.path.join(tables, "caller_snp_venn.tsv"), per, vc)
 
 
 def _write_mutation_context(meta, jobs, tables, callers, mixes):
@@ -325,9 +373,13 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
         adict.close()
 
 
-def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False):
+def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
+                truth_side=False):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
-    gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table."""
+    gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
+    truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
+    final_tables/caller_snp_venn.tsv is written, more are told so and get their FN files only."""
+    from .truthside import MAX_GROUP
     results = os.path.join(outpath.rstrip("/"), "results")
     call_dir = os.path.join(results, "snp", "callers")
     labels = list(labels) if labels else [os.path.splitext(os.path.basename(v))[0] for v in vcfs]
@@ -336,16 +388,32 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     if dryrun:
         for lab, v in zip(labels, vcfs):
             print("extract_TP\t%s\t%s" % (lab, v))
+        if truth_side:
+            for lab in labels:
+                print("truthside_fn\t%s" % lab)
+            if len(labels) <= MAX_GROUP:
+                print("caller_snp_venn\t%s" % ",".join(labels))
         return None
     if not os.path.exists(snps_file) or os.path.getsize(snps_file) == 0:
         raise WorkflowError("No difference between two genomes!")       # custom_snp_benchmark.R:19-21
     os.makedirs(os.path.join(call_dir, "fp"), exist_ok=True)
     jobs = [Job(v, snps_file, "custom", call_dir, lab) for lab, v in zip(labels, vcfs)]
+    grouped = truth_side and len(labels) <= MAX_GROUP and not any(is_pure_strain(v) for v in vcfs)
+    if truth_side:
+        from .extract import _paths, fn_path
+        if not grouped:
+            print("truth side: %d labels (or pure-strain names): the Venn regions are skipped, FN files are still written" % len(labels))
+        for j in jobs:
+            _paths(j)
+            if not is_pure_strain(j.vcf_file):
+                j.fn_out = fn_path(j)
+                j.group = "vareval" if grouped else None
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
         from .multigpu import extract_many_sharded
-        jobs, res = extract_many_sharded(jobs, int(gpus), backend=_backend, body=_body, same_device=_same_device)
+        jobs, res = extract_many_sharded(jobs, int(gpus), backend=_backend, body=_body, same_device=_same_device,
+                                         groups=[list(range(len(jobs)))] if grouped else None)
         run_vareval.last_result = res
     else:
         extract_many(jobs, engine=engine)
@@ -353,6 +421,12 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     _flag_truth_rows(jobs)
     write_snpcall_benchmark(os.path.join(results, "final_tables", "snpcall_benchmark.txt"),
                             [(lab, j.stats) for lab, j in zip(labels, jobs)])
+    if grouped:
+        from .truthside import write_caller_snp_venn
+        n = len(labels)
+        st = jobs[0].stats
+        write_caller_snp_venn(os.path.join(results, "final_tables", "caller_snp_venn.tsv"),
+                              {"custom": (list(st["truth_regions"][:1 << n]), list(st["fp_regions"][:1 << n]))}, labels)
     return jobs
 
 

@@ -78,10 +78,12 @@ def _fail(e):
 @click.option("--data", type=click.Path(), default=None, help="Unpacked bundle directory (default: <repo>/data/snp).")
 @click.option("--mutation-context", "mutation_context", is_flag=True, default=False,
               help="Also write final_tables/{mix}.{caller}.mutationcontext.tsv (96-motif spectra of kept, TP and FP SNVs).")
+@click.option("--truth-side", "truth_side", is_flag=True, default=False,
+              help="Also write the missed-variant lists (callers/*/fn/*.fn.vcf, nucmer/*.missed_by_all.vcf) and final_tables/caller_snp_venn.tsv.")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
-         mutation_context=False, merlin_ref=None, ad169_ref=None):
+         mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -103,7 +105,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
         # data/snp is unpacked from data/snp.tar.gz when it is not there yet (rules/load_config.smk:28-31)
         workflow.run_hcmv_variantcall.last_result = None
         jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None,
-                                             mutation_context=genomes)
+                                             mutation_context=genomes, truth_side=truth_side)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -122,8 +124,10 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="show-snps -CTHIlr table of the two references; default <outpath>/results/snp/nucmer/<g1>_<g2>.maskrepeat.snps")
 @click.option("--config", type=click.Path(exists=True), default=None,
               help="YAML with vcfs / refs / outpath / labels for what the command line leaves out (default: config/customize_data.yaml).")
+@click.option("--truth-side", "truth_side", is_flag=True, default=False,
+              help="Also write callers/fn/{label}.fn.vcf and, for up to 5 labels, final_tables/caller_snp_venn.tsv.")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
-            config=None, json_out=None):
+            config=None, json_out=None, truth_side=False):
     from quasimodo_amd import workflow
     try:
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
@@ -140,7 +144,8 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
         else:
             snps = os.path.join(cd, snps)
         workflow.run_vareval.last_result = None
-        jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None)
+        jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None,
+                                    truth_side=truth_side)
         if json_out and not dryrun:
             _write_json(json_out, "vareval", jobs, workflow.run_vareval)
     except Exception as e:
