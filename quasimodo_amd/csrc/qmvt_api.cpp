@@ -103,6 +103,36 @@ static int dalloc(T** p, size_t count) {
     if (rc_ != QM_OK) return rc_;    \
   } while (0)
 
+// A device array a batch owns: the pointer and how many elements it holds, freed with its owner.  It reads as a T* wherever launch
+// parameters are filled in.  grow() is the only place an array is allocated, freed or counted (*bytes: qm_batch::dev_bytes).
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  int64_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void)hipFree(p); }
+  operator T*() const { return p; }
+  // At least `need` elements (a first use allocates whatever it asks for); the contents do not survive growing.
+  // (Growing an array frees the old one.  A speculative bucket chunk returns with its last kernels still queued -- they read d_segs,
+  // the cursors' "bad" word, the rows -- and the NEXT chunk of the same finish may grow exactly those: the device is drained first,
+  // explicitly.  hipFree would do so implicitly; the code must not depend on that.  ADVICE round 5.)
+  int grow(int64_t need, int64_t* bytes) {
+    if (p && need <= cap) return QM_OK;
+    if (p) (void)hipDeviceSynchronize();
+    (void)hipFree(p);
+    p = nullptr;
+    *bytes -= cap * (int64_t)sizeof(T);
+    cap = 0;
+    const int rc = dalloc(&p, (size_t)need);
+    if (rc != QM_OK) return rc;
+    *bytes += need * (int64_t)sizeof(T);
+    cap = need;
+    return QM_OK;
+  }
+};
+
 extern "C" int qm_abi_version(void) { return QM_ABI_VERSION; }
 #ifndef QM_KERNELS_ID
 #define QM_KERNELS_ID "unknown"
@@ -429,54 +459,46 @@ struct qm_batch {
   qm_ctx* ctx = nullptr;
   int n_vcf = 0, n_bins = 256;
   Layout L;
-  size_t cap_spans = 0, cap_tiles = 0;
+  // Every device array is a DevBuf: it is counted in dev_bytes where it grows and freed with the batch.
   // columns (or, for the radix-sort scratch batch, the packed key / info pairs)
-  uint32_t *pkey = nullptr, *pinf = nullptr;
-  int32_t *pos = nullptr, *ref = nullptr, *alt = nullptr;
-  float* qual = nullptr;
-  uint8_t* flags = nullptr;
+  DevBuf<uint32_t> pkey, pinf;
+  DevBuf<int32_t> pos, ref, alt;
+  DevBuf<float> qual;
+  DevBuf<uint8_t> flags;
   // batches without QM_BATCH_ALLELES: allele_byte(ref, alt) per record (qmvt_dev.h), what the kernels read instead of the two
   // codes; every writer of ref / alt keeps it up to date
-  uint8_t* anib = nullptr;
+  DevBuf<uint8_t> anib;
   // outputs / workspace
-  uint64_t *mask_pass = nullptr, *mask_tp = nullptr;
-  int32_t* idx = nullptr;
-  uint32_t *tile_tp = nullptr, *tile_fp = nullptr, *tile_tp_off = nullptr, *tile_fp_off = nullptr, *vcf_tot = nullptr;
-  uint32_t *span_hist = nullptr, *span_scal = nullptr, *vcf_flags = nullptr, *vcf_posor = nullptr;
+  DevBuf<uint64_t> mask_pass, mask_tp;
+  DevBuf<int32_t> idx;
+  DevBuf<uint32_t> tile_tp, tile_fp, tile_tp_off, tile_fp_off, vcf_tot;
+  DevBuf<uint32_t> span_hist, span_scal, vcf_flags, vcf_posor;
   // bucket path of the unsorted VCFs: one "span" row per (segment, bucket), fake VCF descriptors for k_finalize
-  uint32_t *bk_hist = nullptr, *bk_scal = nullptr;
-  VcfDesc* d_bk_vcfs = nullptr;
-  int64_t cap_bk_rows = 0, cap_bk_vcfs = 0;
-  uint64_t* bk_xent = nullptr;      // allele-extended batches: the second stream's regions (16-byte entries), its cursors and row descriptors
-  uint32_t* bk_xcursor = nullptr;
-  HashRowX* bk_xrows = nullptr;
-  int64_t cap_bk_xent = 0, cap_bk_xcursor = 0, cap_bk_xrows = 0;
-  uint64_t* bk_ent = nullptr;       // the bucket regions: [segment][256][8][SortSeg.bk_cap] packed records
-  uint32_t* bk_cursor = nullptr;    // [segment][256][8] fill counts, then one flag word per segment
-  int32_t* d_bk_tile_seg = nullptr;
-  HashRow* bk_rows = nullptr;       // one descriptor per (segment, bucket)
-  int64_t cap_bk_rowdesc = 0;
-  int64_t cap_bk_ent = 0, cap_bk_cursor = 0, cap_bk_tiles = 0;
+  DevBuf<uint32_t> bk_hist, bk_scal;
+  DevBuf<VcfDesc> d_bk_vcfs;
+  DevBuf<uint64_t> bk_xent;         // allele-extended batches: the second stream's regions (16-byte entries), its cursors and row descriptors
+  DevBuf<uint32_t> bk_xcursor;
+  DevBuf<HashRowX> bk_xrows;
+  DevBuf<uint64_t> bk_ent;          // the bucket regions: [segment][256][8][SortSeg.bk_cap] packed records
+  DevBuf<uint32_t> bk_cursor;       // [segment][256][8] fill counts, then one flag word per segment
+  DevBuf<int32_t> d_bk_tile_seg;
+  DevBuf<HashRow> bk_rows;          // one descriptor per (segment, bucket)
   // rows (ROC, scalars, flags) of the VCFs a bucket chunk redoes, before they are copied under the original VCFs
-  uint64_t* bk_roc = nullptr;
-  int64_t* bk_rscal = nullptr;
-  uint32_t* bk_vflags = nullptr;
-  int64_t cap_bk_roc = 0, cap_bk_rscal = 0, cap_bk_vflags = 0;
+  DevBuf<uint64_t> bk_roc;
+  DevBuf<int64_t> bk_rscal;
+  DevBuf<uint32_t> bk_vflags;
   // two-level bucket path (large VCFs): level-1 descriptors, counts, offsets, cursors, entries; VCF-level segment table
-  PartSeg* p_segs = nullptr;
-  int32_t* p_tile_seg = nullptr;
-  uint32_t *p_cnt = nullptr, *p_off = nullptr, *p_cursor = nullptr, *p_flags = nullptr;
-  uint64_t* p_ent = nullptr;
-  SortSeg* d_vsegs = nullptr;
-  int32_t* d_vparts = nullptr;          // partitions in use per VCF
-  int64_t cap_vparts = 0;
-  uint32_t* p_half = nullptr;
-  int64_t cap_p_half = 0;
-  int64_t cap_p_segs = 0, cap_p_tiles = 0, cap_p_cnt = 0, cap_p_off = 0, cap_p_cursor = 0, cap_p_flags = 0, cap_p_ent = 0, cap_vsegs = 0;
+  DevBuf<PartSeg> p_segs;
+  DevBuf<int32_t> p_tile_seg;
+  DevBuf<uint32_t> p_cnt, p_off, p_cursor, p_flags;
+  DevBuf<uint64_t> p_ent;
+  DevBuf<SortSeg> d_vsegs;
+  DevBuf<int32_t> d_vparts;         // partitions in use per VCF
+  DevBuf<uint32_t> p_half;
   // throw-away outputs of the rescan after a sort (kept: an allocation per finish costs more than the rescan)
-  uint64_t* rs_roc = nullptr;
-  int64_t* rs_scal = nullptr;
-  uint32_t* rs_flags = nullptr;
+  DevBuf<uint64_t> rs_roc;
+  DevBuf<int64_t> rs_scal;
+  DevBuf<uint32_t> rs_flags;
   // Which chunk's tables the shared arrays hold (d_segs, d_tile_seg, d_bk_tile_seg, d_ktile_*, d_bk_vcfs, d_vsegs, d_vparts, p_*): the
   // path that built them, its VCFs, what else they follow from (their position bits; the two levels' counts) and what the path needs
   // to launch over them again.  A path that finds its own chunk here uploads nothing (empty vcfs: nothing known).
@@ -488,22 +510,20 @@ struct qm_batch {
     int64_t nbt = 0, nkt = 0;        // scatter tiles, K1 tiles
     std::vector<int> seg_vcf;        // the VCF of every segment
   } tables;
-  uint64_t *roc = nullptr, *global_acc = nullptr;
-  int64_t* scalars = nullptr;
-  VcfDesc* d_vcfs = nullptr;
-  SpanDesc* d_spans = nullptr;
-  int32_t* d_tile_vcf = nullptr;
-  uint8_t* cls_scratch = nullptr;  // max_n bytes
-  int64_t dev_bytes = 0;
+  DevBuf<uint64_t> roc, global_acc;
+  DevBuf<int64_t> scalars;
+  DevBuf<VcfDesc> d_vcfs;
+  DevBuf<SpanDesc> d_spans;
+  DevBuf<int32_t> d_tile_vcf;
+  DevBuf<uint8_t> cls_scratch;     // max_n bytes
+  int64_t dev_bytes = 0;           // written by DevBuf::grow, and where the scratch batch comes and goes (ensure_sub)
   // sort path scratch (lazy): one chunk of unsorted VCFs at a time
   qm_batch* sub = nullptr;               // sorted copies of the chunk's VCFs
   std::vector<int64_t> sub_sig;          // record counts the scratch batch was built for
   std::vector<int32_t> sub_tids;         // truth ids its layout was uploaded with
-  uint32_t *sk[2] = {nullptr, nullptr}, *sv[2] = {nullptr, nullptr}, *si[2] = {nullptr, nullptr}, *shist = nullptr, *sorbits = nullptr;
-  SortSeg* d_segs = nullptr;
-  int32_t *d_tile_seg = nullptr, *d_ktile_seg = nullptr, *d_ktile_local = nullptr;
-  int64_t cap_sort_n = 0, cap_sort_hist = 0;
-  int64_t cap_segs = 0, cap_stiles = 0, cap_ktiles = 0;
+  DevBuf<uint32_t> sk[2], sv[2], si[2], shist, sorbits;
+  DevBuf<SortSeg> d_segs;
+  DevBuf<int32_t> d_tile_seg, d_ktile_seg, d_ktile_local;
   // Ordering between the context's two streams (no timing).  The run: [0] behind the flags' k_finalize, [1] behind the rows'.
   // The hashed join of a one-level chunk (onelevel_chunk): [p] behind the scatter of range p, ev_join behind the last join.
   static constexpr int JOIN_PARTS = 4;
@@ -553,20 +573,20 @@ struct qm_batch {
   std::vector<uint32_t> known_nbk;    // 1 + the highest bucket its records reached on the one-level bucket path (0: not known)
   int n_known = 0;
   bool known_dirty = false;           // the device copy is stale
-  uint8_t* d_known = nullptr;
+  DevBuf<uint8_t> d_known;
   bool run_used_known = false;        // the run in flight was launched with d_known
   // qm_batch_motifs (lazy: a batch that never asks allocates nothing): the [n_vcf][3][QM_MOTIF_COLS] counts, the per-VCF genome
   // descriptors (page-locked: copied on the call's stream; ev_motif says when the copy and the pass are done)
-  uint64_t* d_motifs = nullptr;
-  GenomeRef* d_mgen = nullptr;
+  DevBuf<uint64_t> d_motifs;
+  DevBuf<GenomeRef> d_mgen;
   GenomeRef* h_mgen = nullptr;
   hipEvent_t ev_motif = nullptr;
   bool motifs_valid = false;          // qm_batch_motifs was called behind the latest run
   // qm_batch_truth_hits (lazy): the per-VCF hit bitmaps one behind the other (h_hit_off[v] = first word of VCF v,
   // h_hit_off[n_vcf] = all), the record mask (the size of mask_pass), the lookup counter; ev_truth says when the pass is done
-  uint32_t* d_hits = nullptr;
-  uint64_t* d_intruth = nullptr;
-  int64_t* d_hit_off = nullptr;
+  DevBuf<uint32_t> d_hits;
+  DevBuf<uint64_t> d_intruth;
+  DevBuf<int64_t> d_hit_off;
   std::vector<int64_t> h_hit_off, h_hit_tn;   // h_hit_tn[v]: T' of VCF v's truth set when the bitmaps were sized
   bool hit_off_uploaded = false, intruth_cleared = false, hits_enqueued = false;
   hipEvent_t ev_truth = nullptr;
@@ -589,22 +609,15 @@ static void batch_free(qm_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->ctx->dev);
   if (b->sub) { batch_free(b->sub); b->sub = nullptr; }
-  void* ptrs[] = {b->pkey, b->pinf, b->pos, b->ref, b->alt, b->qual, b->flags, b->anib, b->mask_pass, b->mask_tp, b->idx, b->tile_tp, b->tile_fp,
-                  b->tile_tp_off, b->tile_fp_off, b->vcf_tot, b->span_hist, b->span_scal, b->vcf_flags, b->vcf_posor, b->bk_hist, b->bk_scal, b->d_bk_vcfs, b->bk_ent, b->bk_cursor, b->d_bk_tile_seg, b->bk_rows, b->bk_xent, b->bk_xcursor, b->bk_xrows, b->bk_roc, b->bk_rscal, b->bk_vflags, b->p_segs, b->p_tile_seg, b->p_cnt, b->p_off, b->p_half, b->p_cursor, b->p_flags, b->p_ent, b->d_vsegs, b->d_vparts, b->rs_roc, b->rs_scal, b->rs_flags, b->roc, b->global_acc,
-                  b->scalars, b->d_vcfs, b->d_spans, b->d_tile_vcf, b->cls_scratch, b->sk[0], b->sk[1], b->sv[0],
-                  b->sv[1], b->si[0], b->si[1], b->shist, b->sorbits, b->d_segs, b->d_tile_seg, b->d_ktile_seg, b->d_ktile_local, b->d_known};
-  for (void* p : ptrs) (void)hipFree(p);
   if (b->h_summary) (void)hipHostFree(b->h_summary);
-  (void)hipFree(b->d_motifs); (void)hipFree(b->d_mgen);
   if (b->h_mgen) (void)hipHostFree(b->h_mgen);
   if (b->ev_motif) (void)hipEventDestroy(b->ev_motif);
-  (void)hipFree(b->d_hits); (void)hipFree(b->d_intruth); (void)hipFree(b->d_hit_off);
   if (b->ev_truth) (void)hipEventDestroy(b->ev_truth);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
   if (b->ev_flags) (void)hipEventDestroy(b->ev_flags);
-  delete b;
+  delete b;   // the device arrays go with it
 }
 
 static int upload_layout(qm_batch* b) {
@@ -623,8 +636,7 @@ static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int
   b->n_bins = n_bins;
   build_layout(n_records, truth_ids, n_vcf, b->L);
   const Layout& L = b->L;
-  b->cap_spans = L.spans.size();
-  b->cap_tiles = L.tile_vcf.size();
+  const size_t nspans = L.spans.size(), ntiles = L.tile_vcf.size();
   const size_t np = (size_t)L.n_pad;
   const size_t nt = std::max<size_t>(1, (size_t)c->truths.size());
   b->n_truth = (int)nt;
@@ -633,21 +645,19 @@ static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int
     if (std::find(b->truth_gens.begin(), b->truth_gens.end(), tg) == b->truth_gens.end()) b->truth_gens.push_back(tg);
   }
   int rc = QM_OK;
-#define A_(p, n) if (rc == QM_OK) { rc = dalloc(&(p), (n)); if (rc == QM_OK) b->dev_bytes += (int64_t)((n) * sizeof(*(p))); }
+  auto A = [&](auto& buf, size_t n) { if (rc == QM_OK) rc = buf.grow((int64_t)n, &b->dev_bytes); };
   if (packed) {
-    A_(b->pkey, np) A_(b->pinf, np)
-    if (packed_alleles) { A_(b->ref, np) A_(b->alt, np) }   // sorted copies of the allele codes
+    A(b->pkey, np); A(b->pinf, np);
+    if (packed_alleles) { A(b->ref, np); A(b->alt, np); }   // sorted copies of the allele codes
+  } else {
+    A(b->pos, np); A(b->ref, np); A(b->alt, np); A(b->qual, np); A(b->flags, np);
+    if (!alleles) A(b->anib, np);
   }
-  else {
-    A_(b->pos, np) A_(b->ref, np) A_(b->alt, np) A_(b->qual, np) A_(b->flags, np)
-    if (!alleles) A_(b->anib, np)
-  }
-  A_(b->mask_pass, np / 64 + 64) A_(b->mask_tp, np / 64 + 64) A_(b->idx, np)
-  A_(b->tile_tp, b->cap_tiles) A_(b->tile_fp, b->cap_tiles) A_(b->tile_tp_off, b->cap_tiles + SPAN_TILES) A_(b->tile_fp_off, b->cap_tiles + SPAN_TILES) A_(b->vcf_tot, (size_t)n_vcf * 2)
-  A_(b->span_hist, b->cap_spans * SPAN_HIST_WORDS) A_(b->span_scal, b->cap_spans * 8) A_(b->vcf_flags, (size_t)n_vcf) A_(b->vcf_posor, (size_t)n_vcf)
-  A_(b->roc, (size_t)n_vcf * 3 * (size_t)n_bins) A_(b->global_acc, nt * 3 * (size_t)n_bins) A_(b->scalars, (size_t)n_vcf * 8)
-  A_(b->d_vcfs, (size_t)n_vcf) A_(b->d_spans, b->cap_spans) A_(b->d_tile_vcf, b->cap_tiles) A_(b->cls_scratch, (size_t)L.max_n)
-#undef A_
+  A(b->mask_pass, np / 64 + 64); A(b->mask_tp, np / 64 + 64); A(b->idx, np);
+  A(b->tile_tp, ntiles); A(b->tile_fp, ntiles); A(b->tile_tp_off, ntiles + SPAN_TILES); A(b->tile_fp_off, ntiles + SPAN_TILES); A(b->vcf_tot, (size_t)n_vcf * 2);
+  A(b->span_hist, nspans * SPAN_HIST_WORDS); A(b->span_scal, nspans * 8); A(b->vcf_flags, (size_t)n_vcf); A(b->vcf_posor, (size_t)n_vcf);
+  A(b->roc, (size_t)n_vcf * 3 * (size_t)n_bins); A(b->global_acc, nt * 3 * (size_t)n_bins); A(b->scalars, (size_t)n_vcf * 8);
+  A(b->d_vcfs, (size_t)n_vcf); A(b->d_spans, nspans); A(b->d_tile_vcf, ntiles); A(b->cls_scratch, (size_t)L.max_n);
   if (rc == QM_OK) rc = upload_layout(b);
   auto create_event = [&](hipEvent_t& e) {
     if (rc == QM_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = fail(QM_E_HIP, "hipEventCreate failed");
@@ -871,7 +881,8 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   // VCFs an earlier finish found out of order, columns unchanged since: their spans return at once (qm_batch: known)
   const bool use_known = memo_on() && b->n_known > 0;
   if (use_known && (b->known_dirty || !b->d_known)) {
-    if (!b->d_known) { DALLOC(b->d_known, (size_t)b->n_vcf); b->dev_bytes += b->n_vcf; }
+    const int rc = b->d_known.grow(b->n_vcf, &b->dev_bytes);
+    if (rc != QM_OK) return rc;
     HIPCHK(hipMemcpy(b->d_known, b->known.data(), (size_t)b->n_vcf, hipMemcpyHostToDevice));
     b->known_dirty = false;
   }
@@ -1063,24 +1074,6 @@ static int read_path_env() {
 
 // --- the device arrays of a chunk
 
-// (Growing an array frees the old one.  A speculative bucket chunk returns with its last kernels still queued -- they read d_segs,
-// the cursors' "bad" word, the rows -- and the NEXT chunk of the same finish may grow exactly those: the device is drained first,
-// explicitly.  hipFree would do so implicitly; the code must not depend on that.  ADVICE round 5.)
-template <typename T>
-static int regrow(T** p, int64_t* cap, int64_t need, int64_t* bytes) {
-  if (need <= *cap) return QM_OK;
-  if (*p) (void)hipDeviceSynchronize();
-  (void)hipFree(*p);
-  *p = nullptr;
-  *bytes -= *cap * (int64_t)sizeof(T);
-  *cap = 0;
-  int rc = dalloc(p, (size_t)need);
-  if (rc != QM_OK) return rc;
-  *bytes += need * (int64_t)sizeof(T);
-  *cap = need;
-  return QM_OK;
-}
-
 // the scratch batch of a radix chunk: the sorted copies of its VCFs and their rows; rebuilt only when the chunk's shape changes
 static int ensure_sub(qm_batch* b, const std::vector<int>& vs) {
   const int nseg = (int)vs.size();
@@ -1105,17 +1098,6 @@ static int ensure_sub(qm_batch* b, const std::vector<int>& vs) {
   return QM_OK;
 }
 
-// the segment table and k_tile_counts' map (every path): d_segs, d_ktile_seg, d_ktile_local
-static int ensure_seg_arrays(qm_batch* b, int64_t nseg, int64_t nkt) {
-  int rc = regrow(&b->d_segs, &b->cap_segs, nseg, &b->dev_bytes);
-  int64_t cap = b->cap_ktiles;
-  if (rc == QM_OK) rc = regrow(&b->d_ktile_seg, &cap, nkt, &b->dev_bytes);
-  cap = b->cap_ktiles;
-  if (rc == QM_OK) rc = regrow(&b->d_ktile_local, &cap, nkt, &b->dev_bytes);
-  if (rc == QM_OK) b->cap_ktiles = std::max(b->cap_ktiles, nkt);
-  return rc;
-}
-
 // behind a bucket chunk's cursors ([nseg][256][8], then one flag word per segment): 32 + 16 * 65 phase clocks of a profiling build, the
 // scatter's per-segment histograms, seg_maxd, the chunk's "bad" word -- all of it cleared in front of the scatter
 static int64_t cursor_words(int64_t nseg) { return nseg * HB_BUCKETS * HB_SUBS + nseg + 32 + 16 * 65 + nseg * (SEG_HIST_WORDS + 1) + 1; }
@@ -1134,21 +1116,20 @@ static CursorRegion cursor_region(const qm_batch* b, int nseg) {
 // k_sort_copy_rows takes them home -- small arrays of their own, so that a bucket chunk needs no scratch batch
 static int ensure_bucket_arrays(qm_batch* b, int64_t nseg, int64_t bk_ents, int64_t nbt, bool xs) {
   const int64_t rows = nseg * HB_BUCKETS, orows = nseg * (xs ? 2 * HB_BUCKETS : HB_BUCKETS);
-  int64_t c1 = b->cap_bk_rows * SPAN_HIST_WORDS, c2 = b->cap_bk_rows * 8;   // (cap_bk_rows counts rows for both arrays)
-  int rc = regrow(&b->bk_hist, &c1, orows * SPAN_HIST_WORDS, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_scal, &c2, orows * 8, &b->dev_bytes);
-  if (rc == QM_OK) b->cap_bk_rows = std::max(b->cap_bk_rows, orows);
-  if (rc == QM_OK && xs) rc = regrow(&b->bk_xent, &b->cap_bk_xent, 2 * bk_ents, &b->dev_bytes);
-  if (rc == QM_OK && xs) rc = regrow(&b->bk_xcursor, &b->cap_bk_xcursor, rows * HB_SUBS, &b->dev_bytes);
-  if (rc == QM_OK && xs) rc = regrow(&b->bk_xrows, &b->cap_bk_xrows, rows, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->d_bk_vcfs, &b->cap_bk_vcfs, nseg, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_ent, &b->cap_bk_ent, bk_ents, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_rows, &b->cap_bk_rowdesc, rows, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_cursor, &b->cap_bk_cursor, cursor_words(nseg), &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->d_bk_tile_seg, &b->cap_bk_tiles, nbt, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_roc, &b->cap_bk_roc, nseg * 3 * b->n_bins, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_rscal, &b->cap_bk_rscal, nseg * 8, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->bk_vflags, &b->cap_bk_vflags, nseg, &b->dev_bytes);
+  int64_t* by = &b->dev_bytes;
+  int rc = b->bk_hist.grow(orows * SPAN_HIST_WORDS, by);
+  if (rc == QM_OK) rc = b->bk_scal.grow(orows * 8, by);
+  if (rc == QM_OK && xs) rc = b->bk_xent.grow(2 * bk_ents, by);
+  if (rc == QM_OK && xs) rc = b->bk_xcursor.grow(rows * HB_SUBS, by);
+  if (rc == QM_OK && xs) rc = b->bk_xrows.grow(rows, by);
+  if (rc == QM_OK) rc = b->d_bk_vcfs.grow(nseg, by);
+  if (rc == QM_OK) rc = b->bk_ent.grow(bk_ents, by);
+  if (rc == QM_OK) rc = b->bk_rows.grow(rows, by);
+  if (rc == QM_OK) rc = b->bk_cursor.grow(cursor_words(nseg), by);
+  if (rc == QM_OK) rc = b->d_bk_tile_seg.grow(nbt, by);
+  if (rc == QM_OK) rc = b->bk_roc.grow(nseg * 3 * b->n_bins, by);
+  if (rc == QM_OK) rc = b->bk_rscal.grow(nseg * 8, by);
+  if (rc == QM_OK) rc = b->bk_vflags.grow(nseg, by);
   return rc;
 }
 
@@ -1163,29 +1144,66 @@ static std::vector<uint32_t> posor_of(const std::vector<int>& vs, const std::vec
   for (size_t i = 0; i < vs.size(); ++i) k[i] = posor[(size_t)vs[i]];
   return k;
 }
-// k_tile_counts' map: the VCF (index into vs) and the tile inside it of every K1 tile of the chunk
-static void ktile_maps(const qm_batch* b, const std::vector<int>& vs, std::vector<int32_t>& seg, std::vector<int32_t>& local) {
-  for (size_t i = 0; i < vs.size(); ++i)
-    for (int t = 0; t < b->L.vcfs[(size_t)vs[i]].ntiles; ++t) { seg.push_back((int32_t)i); local.push_back(t); }
+
+// One chunk's tables on the host, built by its path segment by segment (add_bucket_seg, add_vcf_row, ktile_maps) and put on the device
+// in one go (upload_tables).
+struct ChunkTables {
+  bool maps = true;                              // false: the tables are on the device already, only the geometry is wanted -- no per-tile entries
+  std::vector<SortSeg> segs, vsegs;              // the segments; where a VCF has several, one row per VCF for the hand-over
+  std::vector<int32_t> vparts;                   // segments per VCF (beside vsegs)
+  std::vector<VcfDesc> fake;                     // the rows of a segment's buckets as the "spans" of a VCF, for k_finalize
+  std::vector<int32_t> tile_seg, bk_tile_seg;    // the segment of every sort tile (radix) / scatter tile (buckets)
+  std::vector<int32_t> ktile_seg, ktile_local;   // k_tile_counts' map: the VCF (index into the chunk) and the tile inside it of every K1 tile
+  std::vector<int> seg_vcf;                      // the VCF of every segment
+  int64_t bk_ents = 0, nbt = 0, nst = 0, nkt = 0, koff = 0, hoff = 0;   // bucket entries, scatter / sort / K1 tiles, keys, histogram words so far
+};
+// Entries per sub-region of a segment of n records: between 128 and 256 buckets are in use, a sub-region takes every eighth tile; half
+// as much again on top, a power of two up to sub_max
+static int64_t sub_cap(int64_t n, int64_t sub_max) {
+  const int64_t want = n / (128 * HB_SUBS) * 3 / 2 + 16;
+  int64_t cap = 16;
+  while (cap < want && cap < sub_max) cap *= 2;
+  return cap;
 }
-// the rows of a segment's buckets as the "spans" of a VCF, for k_finalize
-static VcfDesc bucket_vcf(int64_t n, int32_t truth, int32_t span0, int32_t nspans) {
+// One more segment of the bucket scatter.  g: who it is (records, VCF, shift, buckets, key range); tiles: the scatter tiles it owns.
+// Its regions, its place in the tile map, its `rows` bucket rows as the "spans" of a VCF of `truth` for k_finalize (the rows of a
+// segment lie 256 apart; xs, two entry streams: 512).
+static void add_bucket_seg(ChunkTables* T, SortSeg g, int64_t tiles, int64_t sub_max, int32_t truth, bool xs, int rows) {
+  const int32_t i = (int32_t)T->segs.size();
+  g.bk_cap = (int32_t)sub_cap(g.n, sub_max); g.bk_off = T->bk_ents; g.bk_tile0 = (int32_t)T->nbt;
+  T->bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * g.bk_cap;
+  T->nbt += tiles;
+  if (T->maps) T->bk_tile_seg.insert(T->bk_tile_seg.end(), (size_t)tiles, i);
   VcfDesc f = VcfDesc();
-  f.off = 0; f.n = n; f.truth = truth; f.tile0 = 0; f.ntiles = 0; f.span0 = span0; f.nspans = nspans; f.pad = 0;
-  return f;
+  f.off = 0; f.n = g.n; f.truth = truth; f.tile0 = 0; f.ntiles = 0; f.span0 = i * (xs ? 2 * HB_BUCKETS : HB_BUCKETS); f.nspans = rows; f.pad = 0;
+  T->fake.push_back(f);
+  T->seg_vcf.push_back(g.main_vcf);
+  T->segs.push_back(g);
+}
+// the row of VCF v (descriptor d) whose segments begin at seg0 and end here: what hand_over adds up per VCF
+static void add_vcf_row(ChunkTables* T, const VcfDesc& d, int v, int seg0) {
+  SortSeg vg;
+  memset(&vg, 0, sizeof vg);
+  vg.src_off = d.off; vg.n = d.n; vg.main_vcf = v; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
+  T->vsegs.push_back(vg);
+  T->vparts.push_back((int32_t)T->segs.size() - seg0);
+}
+static void ktile_maps(const qm_batch* b, const std::vector<int>& vs, ChunkTables* T) {
+  for (size_t i = 0; i < vs.size(); ++i) {
+    const int nt = b->L.vcfs[(size_t)vs[i]].ntiles;
+    T->nkt += nt;
+    if (T->maps) for (int t = 0; t < nt; ++t) { T->ktile_seg.push_back((int32_t)i); T->ktile_local.push_back(t); }
+  }
 }
 
 // One segment per VCF (the radix sort, the one-level buckets): where its records are, its sort tiles, its digit histograms, its buckets
-struct VcfSegs {
-  std::vector<SortSeg> segs;
-  int64_t koff = 0, hoff = 0, bk_ents = 0, nst = 0, nkt = 0, nbt = 0;
-};
-static int vcf_segs(const qm_batch* b, const std::vector<int>& vs, const std::vector<uint32_t>& posor, VcfSegs* T) {
-  T->segs.resize(vs.size());
+static void vcf_segs(const qm_batch* b, const std::vector<int>& vs, const std::vector<uint32_t>& posor, ChunkTables* T) {
+  const bool xs = b->ext;
   int64_t dst_off = 0;
   for (size_t i = 0; i < vs.size(); ++i) {
     const VcfDesc& d = b->L.vcfs[(size_t)vs[i]];
-    SortSeg& g = T->segs[i];
+    SortSeg g;
+    memset(&g, 0, sizeof g);
     g.src_off = d.off; g.dst_off = dst_off; g.koff = T->koff; g.hoff = T->hoff; g.n = d.n;   // dst_off: as build_layout lays the scratch batch out
     dst_off += (d.n + VCF_ALIGN - 1) / VCF_ALIGN * VCF_ALIGN;
     g.tile0 = (int32_t)T->nst; g.ntiles = (int32_t)((d.n + SORT_TILE - 1) / SORT_TILE);
@@ -1193,18 +1211,45 @@ static int vcf_segs(const qm_batch* b, const std::vector<int>& vs, const std::ve
     g.pad = onelevel_shift(posor[(size_t)vs[i]]);
     // buckets above the VCF's highest position are empty by construction: <= 256
     g.nbk = std::min((int)(((posor[(size_t)vs[i]] << 4) | 15u) >> g.pad) + 1, (int)HB_BUCKETS); g.key_base = 0u;
-    // room per sub-region: between 128 and 256 buckets are in use, a sub-region takes every eighth tile; half as much again on top
-    int64_t want = d.n / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;
-    while (cap2 < want && cap2 < HB_SUB_MAX) cap2 *= 2;
-    g.bk_cap = (int32_t)cap2; g.bk_off = T->bk_ents; g.bk_tile0 = (int32_t)T->nbt;
-    T->bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
-    T->nbt += (d.n + BK_TILE - 1) / BK_TILE;
+    if (T->maps) T->tile_seg.insert(T->tile_seg.end(), (size_t)g.ntiles, (int32_t)i);
     T->nst += g.ntiles;
-    T->nkt += d.ntiles;
     T->koff += (d.n + 63) / 64 * 64;
     T->hoff += (int64_t)g.ntiles * 256;
+    add_bucket_seg(T, g, (d.n + BK_TILE - 1) / BK_TILE, HB_SUB_MAX, d.truth, xs, xs ? 2 * HB_BUCKETS : g.nbk);
   }
-  if (T->nst > INT32_MAX || T->nkt > INT32_MAX || T->nbt > INT32_MAX) return fail(QM_E_LIMIT, "sort chunk: too many tiles");
+  ktile_maps(b, vs, T);
+}
+
+// A chunk's tables onto the device: the arrays grown to hold them (bucket paths: the chunk's regions, cursors and rows with them), the
+// copies, one wait -- the host tables may go when this returns -- and the record of what the shared arrays hold now.  key: what the
+// tables follow from besides the chunk's VCFs.
+static int upload_tables(qm_batch* b, Path path, const std::vector<int>& vs, const std::vector<uint32_t>& key, const ChunkTables& T, hipStream_t st) {
+  b->tables = qm_batch::Tables();
+  const bool radix = path == Path::Radix;
+  if (T.nst > INT32_MAX || T.nkt > INT32_MAX || T.nbt > INT32_MAX)
+    return fail(QM_E_LIMIT, "%s: too many tiles", path == Path::Radix || path == Path::OneLevel ? "sort chunk" : "bucket path");
+  const int64_t nseg = (int64_t)T.segs.size(), nv = (int64_t)T.vsegs.size();
+  int64_t* by = &b->dev_bytes;
+  int rc = b->d_segs.grow(nseg, by);
+  if (rc == QM_OK) rc = b->d_ktile_seg.grow(T.nkt, by);
+  if (rc == QM_OK) rc = b->d_ktile_local.grow(T.nkt, by);
+  if (rc == QM_OK && radix) rc = b->d_tile_seg.grow(T.nst, by);
+  if (rc == QM_OK && nv) rc = b->d_vsegs.grow(nv, by);
+  if (rc == QM_OK && nv) rc = b->d_vparts.grow(nv, by);
+  if (rc == QM_OK && !radix) rc = ensure_bucket_arrays(b, nseg, T.bk_ents, T.nbt, b->ext);
+  if (rc != QM_OK) return rc;
+  auto put = [st](void* dst, const auto& v) {
+    return v.empty() ? hipSuccess : hipMemcpyAsync(dst, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice, st);
+  };
+  HIPCHK(put(b->d_segs, T.segs));
+  HIPCHK(put(b->d_vsegs, T.vsegs));
+  HIPCHK(radix ? put(b->d_tile_seg, T.tile_seg) : put(b->d_bk_tile_seg, T.bk_tile_seg));
+  HIPCHK(put(b->d_ktile_seg, T.ktile_seg));
+  HIPCHK(put(b->d_ktile_local, T.ktile_local));
+  if (!radix) HIPCHK(put(b->d_bk_vcfs, T.fake));
+  HIPCHK(put(b->d_vparts, T.vparts));
+  HIPCHK(hipStreamSynchronize(st));
+  b->tables = qm_batch::Tables{path, vs, key, (int)nseg, T.nbt, T.nkt, T.seg_vcf};
   return QM_OK;
 }
 
@@ -1214,14 +1259,14 @@ static int vcf_segs(const qm_batch* b, const std::vector<int>& vs, const std::ve
 // path itself: l1_ent / l1_half (two levels), pairs (partitions), seg_maxd (one level), H.zero.
 static void bucket_params(qm_batch* b, int nseg, bool xs, uint32_t* seg_hist, BucketScatterParams* S, HashParams* H) {
   S->segs = b->d_segs; S->tile_seg = b->d_bk_tile_seg; S->pos = b->pos; S->ref = b->ref; S->alt = b->alt; S->qual = b->qual; S->flags = b->flags; S->anib = b->anib;
-  S->cursor = b->bk_cursor; S->ent = b->bk_ent; S->mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); S->mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp);
+  S->cursor = b->bk_cursor; S->ent = b->bk_ent; S->mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass.p); S->mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp.p);
   S->n_seg = nseg; S->n_bins = b->n_bins; S->tile_base = 0;
-  S->xent = xs ? b->bk_xent : nullptr; S->xcursor = xs ? b->bk_xcursor : nullptr; S->ext = xs ? 1 : 0;
+  S->xent = xs ? b->bk_xent.p : nullptr; S->xcursor = xs ? b->bk_xcursor.p : nullptr; S->ext = xs ? 1 : 0;
   S->seg_hist = seg_hist;   // k_join_lean follows: the scatter counts every record by bin
   S->l1_ent = nullptr; S->l1_half = nullptr; S->pairs = 0; S->seg_maxd = nullptr;
   H->segs = b->d_segs; H->rows = b->bk_rows; H->rows_out = b->bk_rows; H->ent = b->bk_ent; H->cursor = b->bk_cursor; H->truths = b->ctx->d_truths; H->vcfs = b->d_vcfs;
   H->mask_tp = b->mask_tp; H->row_hist = b->bk_hist; H->row_scal = b->bk_scal; H->n_seg = nseg; H->n_bins = b->n_bins; H->seg_base = 0;
-  H->xrows = xs ? b->bk_xrows : nullptr; H->xent = xs ? b->bk_xent : nullptr; H->xcursor = xs ? b->bk_xcursor : nullptr;
+  H->xrows = xs ? b->bk_xrows.p : nullptr; H->xent = xs ? b->bk_xent.p : nullptr; H->xcursor = xs ? b->bk_xcursor.p : nullptr;
   H->out_stride = xs ? 2 * HB_BUCKETS : HB_BUCKETS; H->ext = xs ? 1 : 0;
   H->scatter_hist = seg_hist ? 1 : 0;
   H->seg_maxd = nullptr;
@@ -1236,6 +1281,14 @@ static FinalizeParams bucket_rows_finalize(qm_batch* b, const uint32_t* all_hist
   return F;
 }
 
+// what the flag word of VCF v says went wrong with it: a position out of range, the de-duplication limit; QM_OK for neither
+static int flag_failure(uint32_t fl, int v) {
+  if (fl & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", v);
+  if (fl & SPANF_RUNLIMIT)
+    return fail(QM_E_LIMIT, "VCF %d repeats one position more than %d times between equal alleles (allele-extended de-duplication limit)", v, 1 << 14);
+  return QM_OK;
+}
+
 // The verdict on a bucket chunk whose rows' flags are on the host: per segment its flag word and (maxd, or null) the highest bucket its
 // records reached, against the nbk launched.  A bad position fails the finish; *named gets the VCFs with an overflowing bucket (a VCF's
 // segments lie one behind the other) -- nothing of such a chunk may be handed over.
@@ -1243,7 +1296,8 @@ static int bucket_verdict(qm_batch* b, const uint32_t* fl, const uint32_t* maxd,
   named->clear();
   for (size_t i = 0; i < seg_vcf.size(); ++i) {
     const int v = seg_vcf[i];
-    if (fl[i] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", v);
+    const int rc = flag_failure(fl[i] & SPANF_BADPOS, v);
+    if (rc != QM_OK) return rc;
     // (maxd above nbk: a remembered bound that no longer holds -- cannot happen while the columns stay the same)
     const bool over = (fl[i] & SPANF_OVERFLOW) || (maxd && maxd[i] > nbk);
     if (over && (named->empty() || named->back() != v)) named->push_back(v);
@@ -1263,8 +1317,9 @@ static int hand_over(qm_batch* b, const SortSeg* segs, int nv, const int32_t* np
   return QM_OK;   // no wait: the rescan that follows is on the same stream and ends with one
 }
 
-static thread_local double g_ftrace[4];   // QM_FINISH_TRACE: host clock inside the latest chunk (entered, tables ready, scatter queued)
+// QM_FINISH_TRACE: the host's clock (us), and its readings inside the latest chunk (entered, tables ready, scatter queued)
 static double ftrace_now() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; }
+static thread_local double g_ftrace[4];
 
 // --- the radix sort: stable LSD passes by position over the digits in use, k_classify<PACKED> on the sorted copies, results home.
 // stat: the counter its VCFs go to (QM_PATH_RADIX, or QM_PATH_RADIX_AFTER_OVERFLOW behind a bucket path).
@@ -1272,40 +1327,27 @@ static int radix_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, 
   g_ftrace[0] = ftrace_now();
   const int nseg = (int)vs.size();
   int rc = ensure_sub(b, vs);
-  VcfSegs T;
-  if (rc == QM_OK) rc = vcf_segs(b, vs, posor, &T);
-  if (rc == QM_OK) rc = ensure_seg_arrays(b, nseg, T.nkt);
-  if (rc == QM_OK) rc = regrow(&b->d_tile_seg, &b->cap_stiles, T.nst, &b->dev_bytes);
-  if (rc == QM_OK && !b->sorbits) rc = dalloc(&b->sorbits, 1);
+  if (rc != QM_OK) return rc;
+  const std::vector<uint32_t> key = posor_of(vs, posor);
+  ChunkTables T;
+  T.maps = !owns(b, Path::Radix, vs, key);
+  vcf_segs(b, vs, posor, &T);
+  if (T.maps) rc = upload_tables(b, Path::Radix, vs, key, T, st);
   if (rc != QM_OK) return rc;
   const int nst = (int)T.nst, nkt = (int)T.nkt;
-  const std::vector<uint32_t> key = posor_of(vs, posor);
-  if (!owns(b, Path::Radix, vs, key)) {
-    b->tables = qm_batch::Tables();
-    std::vector<int32_t> tile_seg, ktile_seg, ktile_local;
-    for (int i = 0; i < nseg; ++i) tile_seg.insert(tile_seg.end(), (size_t)T.segs[(size_t)i].ntiles, (int32_t)i);
-    ktile_maps(b, vs, ktile_seg, ktile_local);
-    HIPCHK(hipMemcpyAsync(b->d_segs, T.segs.data(), sizeof(SortSeg) * T.segs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_tile_seg, tile_seg.data(), 4 * tile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // the host vectors die with this block
-    b->tables = qm_batch::Tables{Path::Radix, vs, key, nseg, T.nbt, T.nkt, vs};
-  }
   b->path_stats[stat] += nseg;
   b->path_stats[QM_PATH_RADIX_CHUNKS] += 1;
   qm_batch* s = b->sub;
   // --- 1. + 2. stable LSD radix sort by position (key bits 4..31), only the digits in use.  The first pass packs the
   //        records to (key, info, original index) on the fly; the last pass drops keys and infos straight into the
   //        scratch batch.  (Its ping-pong arrays exist only once a chunk has come this way.)
-  int64_t cap;
   for (int i = 0; i < 2 && rc == QM_OK; ++i) {
-    cap = b->cap_sort_n; rc = regrow(&b->sk[i], &cap, T.koff, &b->dev_bytes);
-    if (rc == QM_OK) { cap = b->cap_sort_n; rc = regrow(&b->sv[i], &cap, T.koff, &b->dev_bytes); }
-    if (rc == QM_OK) { cap = b->cap_sort_n; rc = regrow(&b->si[i], &cap, T.koff, &b->dev_bytes); }
+    rc = b->sk[i].grow(T.koff, &b->dev_bytes);
+    if (rc == QM_OK) rc = b->sv[i].grow(T.koff, &b->dev_bytes);
+    if (rc == QM_OK) rc = b->si[i].grow(T.koff, &b->dev_bytes);
   }
-  if (rc == QM_OK) b->cap_sort_n = std::max(b->cap_sort_n, T.koff);
-  if (rc == QM_OK) rc = regrow(&b->shist, &b->cap_sort_hist, T.hoff, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->shist.grow(T.hoff, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->sorbits.grow(1, &b->dev_bytes);
   if (rc != QM_OK) return rc;
   HIPCHK(hipMemsetAsync(b->sorbits, 0, 4, st));
   launch_sort_first_hist(b->d_segs, b->d_tile_seg, nst, b->pos, b->shist, b->sorbits, st);
@@ -1350,10 +1392,8 @@ static int radix_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, 
   for (int i = 0; i < nseg; ++i) {
     if (sfl[(size_t)i] & SPANF_UNSORTED) return fail(QM_E_HIP, "internal: VCF %d still unsorted after the radix sort", vs[(size_t)i]);
     // the optimistic pass stops streaming at the first out-of-order tile: a bad position behind it shows up only here
-    if (sfl[(size_t)i] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", vs[(size_t)i]);
-    if (sfl[(size_t)i] & SPANF_RUNLIMIT)
-      return fail(QM_E_LIMIT, "VCF %d repeats one position more than %d times between equal alleles (allele-extended de-duplication limit)",
-                  vs[(size_t)i], 1 << 14);
+    rc = flag_failure(sfl[(size_t)i], vs[(size_t)i]);
+    if (rc != QM_OK) return rc;
   }
   return QM_OK;
 }
@@ -1366,9 +1406,10 @@ static int onelevel_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t s
   named->clear();
   g_ftrace[0] = ftrace_now();
   const int nseg = (int)vs.size();
-  VcfSegs T;
-  int rc = vcf_segs(b, vs, posor, &T);
-  if (rc != QM_OK) return rc;
+  const std::vector<uint32_t> key = posor_of(vs, posor);
+  ChunkTables T;
+  T.maps = !owns(b, Path::OneLevel, vs, key);
+  vcf_segs(b, vs, posor, &T);
   const std::vector<SortSeg>& segs = T.segs;
   int lb_all = 0, nbk_all = 1;
   for (const SortSeg& g : segs) { lb_all = std::max(lb_all, (int)g.pad); nbk_all = std::max(nbk_all, (int)g.nbk); }
@@ -1379,31 +1420,10 @@ static int onelevel_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t s
   // others), both of which need the bucket's key range to fit the bit maps; wider key ranges take the radix sort
   const bool xs = b->ext;
   if (xs && !direct) return radix_chunk(b, vs, st, posor, QM_PATH_RADIX);
-  const int out_stride = xs ? 2 * HB_BUCKETS : HB_BUCKETS;
   if (xs) nbk_all = HB_BUCKETS;   // every row of a segment is written (the rows of the second stream follow at a fixed distance)
-  const int nbt = (int)T.nbt, nkt = (int)T.nkt;
-  rc = ensure_seg_arrays(b, nseg, nkt);
-  if (rc == QM_OK) rc = ensure_bucket_arrays(b, nseg, T.bk_ents, nbt, xs);
+  int rc = T.maps ? upload_tables(b, Path::OneLevel, vs, key, T, st) : QM_OK;
   if (rc != QM_OK) return rc;
-  const std::vector<uint32_t> key = posor_of(vs, posor);
-  if (!owns(b, Path::OneLevel, vs, key)) {
-    b->tables = qm_batch::Tables();
-    std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local;
-    std::vector<VcfDesc> fake((size_t)nseg);
-    for (int i = 0; i < nseg; ++i) {
-      const SortSeg& g = segs[(size_t)i];
-      bk_tile_seg.insert(bk_tile_seg.end(), (size_t)((g.n + BK_TILE - 1) / BK_TILE), (int32_t)i);
-      fake[(size_t)i] = bucket_vcf(g.n, b->L.vcfs[(size_t)vs[(size_t)i]].truth, i * out_stride, xs ? out_stride : g.nbk);
-    }
-    ktile_maps(b, vs, ktile_seg, ktile_local);
-    HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // the host vectors die with this block
-    b->tables = qm_batch::Tables{Path::OneLevel, vs, key, nseg, T.nbt, T.nkt, vs};
-  }
+  const int nbt = (int)T.nbt, nkt = (int)T.nkt;
   const CursorRegion C = cursor_region(b, nseg);
   BucketScatterParams S;
   HashParams H;
@@ -1553,13 +1573,14 @@ static int two_level_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t 
   const int nh_all = (int)ps.size();
   if (nt1 > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
   constexpr int NC = P2_PARTS * P2_SUBS;
-  int rc = regrow(&b->p_segs, &b->cap_p_segs, (int64_t)nh_all, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->p_tile_seg, &b->cap_p_tiles, nt1, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->p_cnt, &b->cap_p_cnt, (int64_t)nh_all * NC, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->p_off, &b->cap_p_off, (int64_t)nh_all * (NC + 1), &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->p_cursor, &b->cap_p_cursor, (int64_t)nh_all * NC, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->p_flags, &b->cap_p_flags, (int64_t)nh_all, &b->dev_bytes);
-  if (rc == QM_OK) rc = regrow(&b->p_ent, &b->cap_p_ent, ent_total + 64, &b->dev_bytes);
+  int64_t* by = &b->dev_bytes;
+  int rc = b->p_segs.grow((int64_t)nh_all, by);
+  if (rc == QM_OK) rc = b->p_tile_seg.grow(nt1, by);
+  if (rc == QM_OK) rc = b->p_cnt.grow((int64_t)nh_all * NC, by);
+  if (rc == QM_OK) rc = b->p_off.grow((int64_t)nh_all * (NC + 1), by);
+  if (rc == QM_OK) rc = b->p_cursor.grow((int64_t)nh_all * NC, by);
+  if (rc == QM_OK) rc = b->p_flags.grow((int64_t)nh_all, by);
+  if (rc == QM_OK) rc = b->p_ent.grow(ent_total + 64, by);
   if (rc != QM_OK) return rc;
   if (!same_vs) {
     HIPCHK(hipMemcpyAsync(b->p_segs, ps.data(), sizeof(PartSeg) * ps.size(), hipMemcpyHostToDevice, st));
@@ -1571,30 +1592,27 @@ static int two_level_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t 
   PartParams PP;
   PP.segs = b->p_segs; PP.tile_seg = b->p_tile_seg; PP.pos = b->pos; PP.ref = b->ref; PP.alt = b->alt; PP.qual = b->qual; PP.flags = b->flags; PP.anib = b->anib;
   PP.cnt = b->p_cnt; PP.off = b->p_off; PP.cursor = b->p_cursor; PP.segflags = b->p_flags; PP.ent = b->p_ent;
-  PP.mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass); PP.mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp); PP.n_seg = nh_all; PP.n_bins = b->n_bins;
+  PP.mask_pass = reinterpret_cast<uint32_t*>(b->mask_pass.p); PP.mask_tp = reinterpret_cast<uint32_t*>(b->mask_tp.p); PP.n_seg = nh_all; PP.n_bins = b->n_bins;
   launch_part_hist(PP, (int)nt1, st);
   std::vector<uint32_t> cnt((size_t)nh_all * NC), pfl((size_t)nh_all);
   HIPCHK(hipMemcpyAsync(cnt.data(), b->p_cnt, 4 * cnt.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(pfl.data(), b->p_flags, 4 * pfl.size(), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));   // (also: the host tables above may go)
-  for (int hh = 0; hh < nh_all; ++hh)
-    if (pfl[(size_t)hh] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", vs[(size_t)half_vcf[(size_t)hh]]);
+  for (int hh = 0; hh < nh_all; ++hh) {
+    rc = flag_failure(pfl[(size_t)hh] & SPANF_BADPOS, vs[(size_t)half_vcf[(size_t)hh]]);
+    if (rc != QM_OK) return rc;
+  }
   // --- exact regions; one level-2 segment per (VCF, partition in use).  The same VCFs with the same counts as last time (a batch
   //     run again): every table below is still on the device
   if (!(same_vs && b->tables.key == cnt)) {
     b->tables = qm_batch::Tables();
     std::vector<uint32_t> off((size_t)nh_all * (NC + 1));
     std::vector<uint32_t> half_off;   // [segment][4]: where the entries of the VCF's 2nd, 3rd, 4th half begin inside the segment's run
-    std::vector<SortSeg> segs;
-    std::vector<VcfDesc> fake;
-    std::vector<SortSeg> vsegs((size_t)nv);
-    std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local, vparts((size_t)nv);
-    std::vector<int> seg_vcf;
-    int64_t bk_ents = 0, nbt = 0;
+    ChunkTables T;
     for (int i = 0; i < nv; ++i) {
       const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
       uint32_t run = 0;
-      const int seg0 = (int)segs.size();
+      const int seg0 = (int)T.segs.size();
       const int h0 = vcf_half0[(size_t)i], h1 = vcf_half0[(size_t)i + 1];
       for (int p = 0; p < P2_PARTS; ++p) {
         run = (run + 1u) & ~1u;
@@ -1614,46 +1632,20 @@ static int two_level_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t 
         g.src_off = d.off; g.koff = ps[(size_t)h0].ent_off + start; g.n = np;   // (the halves of a VCF share its level-1 region)
         g.main_vcf = vs[(size_t)i]; g.sub_vcf = i; g.main_tile0 = d.tile0;
         g.pad = DJ_MAX_SHIFT; g.nbk = HB_BUCKETS; g.key_base = (uint32_t)p << P2_SHIFT;
-        int64_t want = np / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;
-        while (cap2 < want && cap2 < HB_SUB_MAX) cap2 *= 2;
-        g.bk_cap = (int32_t)cap2; g.bk_off = bk_ents; g.bk_tile0 = (int32_t)nbt;
-        bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
-        const int64_t t = (np + BK_TILE - 1) / BK_TILE;
-        bk_tile_seg.insert(bk_tile_seg.end(), (size_t)t, (int32_t)segs.size());
-        nbt += t;
         // the buckets of a PARTITION as the "spans" of a VCF for k_finalize: one workgroup per partition (one per VCF summed
         // 1 536 rows by itself); k_sort_copy_rows adds a VCF's partitions up when the rows go home
-        fake.push_back(bucket_vcf(np, d.truth, (int32_t)segs.size() * HB_BUCKETS, HB_BUCKETS));
-        segs.push_back(g);
-        seg_vcf.push_back(vs[(size_t)i]);
+        add_bucket_seg(&T, g, (np + BK_TILE - 1) / BK_TILE, HB_SUB_MAX, d.truth, false, HB_BUCKETS);
       }
       for (int hh = h0; hh < h1; ++hh) off[(size_t)hh * (NC + 1) + NC] = run;
-      SortSeg& vg = vsegs[(size_t)i];
-      memset(&vg, 0, sizeof vg);
-      vg.src_off = d.off; vg.n = d.n; vg.main_vcf = vs[(size_t)i]; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
-      vparts[(size_t)i] = (int32_t)segs.size() - seg0;
+      add_vcf_row(&T, d, vs[(size_t)i], seg0);
     }
-    ktile_maps(b, vs, ktile_seg, ktile_local);
-    const int nseg = (int)segs.size();
-    const int64_t nkt = (int64_t)ktile_seg.size();
-    if (nbt > INT32_MAX || nkt > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
-    rc = ensure_seg_arrays(b, nseg, nkt);
-    if (rc == QM_OK) rc = regrow(&b->d_vsegs, &b->cap_vsegs, (int64_t)nv, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->d_vparts, &b->cap_vparts, (int64_t)nv, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->p_half, &b->cap_p_half, (int64_t)nseg * 4, &b->dev_bytes);
-    if (rc == QM_OK) rc = ensure_bucket_arrays(b, nseg, bk_ents, nbt, false);
+    ktile_maps(b, vs, &T);
+    rc = b->p_half.grow((int64_t)T.segs.size() * 4, by);
     if (rc != QM_OK) return rc;
     HIPCHK(hipMemcpyAsync(b->p_half, half_off.data(), 4 * half_off.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->p_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_vsegs, vsegs.data(), sizeof(SortSeg) * vsegs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_vparts, vparts.data(), 4 * vparts.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // the host tables die with this block
-    b->tables = qm_batch::Tables{Path::TwoLevel, vs, cnt, nseg, nbt, nkt, seg_vcf};
+    rc = upload_tables(b, Path::TwoLevel, vs, cnt, T, st);   // (its wait: the two tables above may go as well)
+    if (rc != QM_OK) return rc;
   }
   const int nseg = b->tables.nseg;
   const CursorRegion C = cursor_region(b, nseg);
@@ -1663,7 +1655,7 @@ static int two_level_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t 
   BucketScatterParams S;
   HashParams H;
   bucket_params(b, nseg, false, C.seg_hist, &S, &H);
-  S.l1_ent = b->p_ent; S.l1_half = any_halves ? b->p_half : nullptr;
+  S.l1_ent = b->p_ent; S.l1_half = any_halves ? b->p_half.p : nullptr;
   // (no look at the highest filled bucket, seg_maxd: every partition but a VCF's last fills its 256 buckets, and the look costs the
   // scatter more than the few empty workgroups cost the join -- 2.81 against 2.71 ms per 16 x 10 M records)
   launch_bucket_rows(H, nseg, st);
@@ -1696,22 +1688,15 @@ static int partitions_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t
   const int pshift = wide ? PW_SHIFT : P2_SHIFT, bshift = wide ? DJ_BIG_SHIFT : DJ_MAX_SHIFT;
   const int64_t sub_max = wide ? 4 * HB_SUB_MAX : HB_SUB_MAX;
   const bool xs = b->ext;                                  // two entry streams (allele-extended batches)
-  const int out_stride = xs ? 2 * HB_BUCKETS : HB_BUCKETS;
   constexpr int G = 2;                                     // partitions per pass over the columns
   const std::vector<uint32_t> key = posor_of(vs, posor);
   if (!owns(b, path, vs, key)) {
-    b->tables = qm_batch::Tables();
-    int64_t nbt = 0;
-    std::vector<SortSeg> segs, vsegs((size_t)nv);
-    std::vector<VcfDesc> fake;
-    std::vector<int32_t> bk_tile_seg, ktile_seg, ktile_local, vparts((size_t)nv);
-    std::vector<int> seg_vcf;
-    int64_t bk_ents = 0;
+    ChunkTables T;
     for (int i = 0; i < nv; ++i) {
       const VcfDesc& d = b->L.vcfs[(size_t)vs[(size_t)i]];
       const uint32_t kor = (key[(size_t)i] << 4) | 15u;
       const int parts = parts_of(key[(size_t)i], pshift);
-      const int seg0 = (int)segs.size();
+      const int seg0 = (int)T.segs.size();
       for (int p = 0; p < parts; ++p) {
         SortSeg g;
         memset(&g, 0, sizeof g);
@@ -1724,40 +1709,15 @@ static int partitions_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t
         const bool pair_last = gfirst + gsize == parts;
         g.part = (pair_last ? 2 : 1) | (lead ? 4 | (gsize << 4) : 0);
         g.nbk = p + 1 == parts ? std::min<int>(HB_BUCKETS, (int)((kor - g.key_base) >> bshift) + 1) : HB_BUCKETS;
-        int64_t want = d.n / (128 * HB_SUBS) * 3 / 2 + 16, cap2 = 16;   // (how the records spread over the partitions is not known: room as for all of them)
-        while (cap2 < want && cap2 < sub_max) cap2 *= 2;
-        g.bk_cap = (int32_t)cap2; g.bk_off = bk_ents; g.bk_tile0 = (int32_t)nbt;
-        bk_ents += (int64_t)HB_BUCKETS * HB_SUBS * cap2;
-        const int64_t t = follow ? 0 : (d.n + BK_TILE - 1) / BK_TILE;   // (the second of a pair has no tiles of its own)
-        bk_tile_seg.insert(bk_tile_seg.end(), (size_t)t, (int32_t)segs.size());
-        nbt += t;
-        fake.push_back(bucket_vcf(d.n, d.truth, (int32_t)segs.size() * out_stride, out_stride));   // the two streams' rows of a partition
-        segs.push_back(g);
-        seg_vcf.push_back(vs[(size_t)i]);
+        // (how the records spread over the partitions is not known: room as for all of them; the second of a pair has no tiles of
+        // its own; the two streams' rows of a partition)
+        add_bucket_seg(&T, g, follow ? 0 : (d.n + BK_TILE - 1) / BK_TILE, sub_max, d.truth, xs, xs ? 2 * HB_BUCKETS : HB_BUCKETS);
       }
-      SortSeg& vg = vsegs[(size_t)i];
-      memset(&vg, 0, sizeof vg);
-      vg.src_off = d.off; vg.n = d.n; vg.main_vcf = vs[(size_t)i]; vg.sub_vcf = seg0; vg.main_tile0 = d.tile0;
-      vparts[(size_t)i] = parts;
+      add_vcf_row(&T, d, vs[(size_t)i], seg0);
     }
-    ktile_maps(b, vs, ktile_seg, ktile_local);
-    const int nseg = (int)segs.size();
-    const int64_t nkt = (int64_t)ktile_seg.size();
-    if (nbt > INT32_MAX || nkt > INT32_MAX) return fail(QM_E_LIMIT, "bucket path: too many tiles");
-    int rc = ensure_seg_arrays(b, nseg, nkt);
-    if (rc == QM_OK) rc = regrow(&b->d_vsegs, &b->cap_vsegs, (int64_t)nv, &b->dev_bytes);
-    if (rc == QM_OK) rc = regrow(&b->d_vparts, &b->cap_vparts, (int64_t)nv, &b->dev_bytes);
-    if (rc == QM_OK) rc = ensure_bucket_arrays(b, nseg, bk_ents, nbt, xs);
+    ktile_maps(b, vs, &T);
+    const int rc = upload_tables(b, path, vs, key, T, st);
     if (rc != QM_OK) return rc;
-    HIPCHK(hipMemcpyAsync(b->d_segs, segs.data(), sizeof(SortSeg) * segs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_vsegs, vsegs.data(), sizeof(SortSeg) * vsegs.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_bk_tile_seg, bk_tile_seg.data(), 4 * bk_tile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_seg, ktile_seg.data(), 4 * ktile_seg.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_ktile_local, ktile_local.data(), 4 * ktile_local.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_bk_vcfs, fake.data(), sizeof(VcfDesc) * fake.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(b->d_vparts, vparts.data(), 4 * vparts.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // the host tables die with this block
-    b->tables = qm_batch::Tables{path, vs, key, nseg, nbt, nkt, seg_vcf};
   }
   const int nseg = b->tables.nseg;
   const CursorRegion C = cursor_region(b, nseg);
@@ -1891,8 +1851,15 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
   // QM_FINISH_TRACE=1: the host's clock at the stations of this call, in us since it was entered (stderr)
   static const bool ftrace = getenv("QM_FINISH_TRACE") != nullptr;
   double ft[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto now_us = []() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; };
-  if (ftrace) ft[0] = now_us();
+  if (ftrace) ft[0] = ftrace_now();
+  // an error exit: nothing of this run is left in flight behind it, no chunk waits to be settled; what the batch remembers goes where
+  // the error may have come from what it remembered (forget: all of it)
+  auto abandon = [&](int rc, bool forget) {
+    (void)hipStreamSynchronize(st);
+    b->pend.clear(); b->pend_segs = 0;
+    if (forget) forget_known(b, -1);
+    return rc;
+  };
   std::vector<uint32_t> posor((size_t)b->n_vcf, 0u);
   bool redone = false;
   if (b->run_used_known) {
@@ -1901,7 +1868,7 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
     for (int v = 0; v < b->n_vcf; ++v) if (b->known[(size_t)v]) { kn.push_back(v); posor[(size_t)v] = b->known_posor[(size_t)v]; }
     b->path_stats[QM_PATH_UNSORTED] += (int64_t)kn.size();
     const int rc = redo_unsorted(b, kn, posor, st);
-    if (rc != QM_OK) { (void)hipStreamSynchronize(st); b->pend.clear(); b->pend_segs = 0; forget_known(b, -1); return rc; }
+    if (rc != QM_OK) return abandon(rc, true);
     redone = !kn.empty();
   }
   // every VCF known to be out of order: the run launched no optimistic pass, nothing can have raised a flag, and the rescan below
@@ -1915,19 +1882,14 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
     if (b->flags_recorded && b->h_summary) HIPCHK(hipEventSynchronize(b->ev_flags));
     else { HIPCHK(hipStreamSynchronize(st)); idle = true; }
   }
-  if (ftrace) ft[1] = now_us();
+  if (ftrace) ft[1] = ftrace_now();
   std::vector<int> todo;
   if (!nothing_ran) {
     std::vector<uint32_t> fl((size_t)b->n_vcf);
     if (b->h_summary) memcpy(fl.data(), b->h_summary + 16, 4 * fl.size());   // k_finalize's host-mapped mirror: complete behind the wait above
     else HIPCHK(hipMemcpy(fl.data(), b->vcf_flags, 4 * fl.size(), hipMemcpyDeviceToHost));
     for (int v = 0; v < b->n_vcf; ++v) {
-      if (fl[(size_t)v] & (SPANF_BADPOS | SPANF_RUNLIMIT)) {
-        (void)hipStreamSynchronize(st);   // nothing of this run is left in flight behind the error
-        b->pend.clear(); b->pend_segs = 0;
-        if (fl[(size_t)v] & SPANF_BADPOS) return fail(QM_E_RANGE, "VCF %d holds a position outside [0, 2^28)", v);
-        return fail(QM_E_LIMIT, "VCF %d repeats one position more than %d times between equal alleles (allele-extended de-duplication limit)", v, 1 << 14);
-      }
+      if (fl[(size_t)v] & (SPANF_BADPOS | SPANF_RUNLIMIT)) return abandon(flag_failure(fl[(size_t)v], v), false);
       if ((fl[(size_t)v] & SPANF_UNSORTED) && !(b->run_used_known && b->known[(size_t)v])) todo.push_back(v);
     }
     if (!todo.empty()) {
@@ -1936,17 +1898,17 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
       else HIPCHK(hipMemcpy(po.data(), b->vcf_posor, 4 * po.size(), hipMemcpyDeviceToHost));
       for (int v : todo) posor[(size_t)v] = po[(size_t)v];
       b->path_stats[QM_PATH_UNSORTED] += (int64_t)todo.size();
-      if (ftrace) ft[2] = now_us();
+      if (ftrace) ft[2] = ftrace_now();
       const int rc = redo_unsorted(b, todo, posor, st);
-      if (rc != QM_OK) { (void)hipStreamSynchronize(st); b->pend.clear(); b->pend_segs = 0; return rc; }
-      if (ftrace) ft[3] = now_us();
+      if (rc != QM_OK) return abandon(rc, false);
+      if (ftrace) ft[3] = ftrace_now();
       redone = true;
     }
   }
   if (redone) {
     int rc = rescan_and_compact(b, st);
     if (rc == QM_OK && !b->pend.empty()) rc = settle_pending(b, posor, st);
-    if (rc != QM_OK) { (void)hipStreamSynchronize(st); b->pend.clear(); b->pend_segs = 0; if (memo_on()) forget_known(b, -1); return rc; }
+    if (rc != QM_OK) return abandon(rc, memo_on());
   } else if (nothing_ran || !idle) {
     HIPCHK(hipStreamSynchronize(st));
   }
@@ -1960,7 +1922,7 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
   for (int k = 0; k < QM_N_PATH_STATS; ++k) c->path_total[k] += b->path_stats[k];
   b->finished = true;
   if (ftrace) {
-    ft[4] = now_us();
+    ft[4] = ftrace_now();
     fprintf(stderr, "finish trace: flags waited for %.1f us, read %.1f, bucket path queued %.1f, everything done %.1f (the latest chunk: entered %.1f, tables %.1f, scatter queued %.1f)\n", ft[1] - ft[0],
             ft[2] ? ft[2] - ft[0] : 0.0, ft[3] ? ft[3] - ft[0] : 0.0, ft[4] - ft[0], g_ftrace[0] - ft[0], g_ftrace[1] - ft[0], g_ftrace[2] - ft[0]);
   }
@@ -1970,12 +1932,10 @@ extern "C" int qm_batch_finish(qm_batch* b, void* stream) {
 // k_finalize recomputes the offsets of every tile; to keep ROC rows and per-truth
 // sums untouched it runs on a throw-away output set.
 static int rescan_and_compact(qm_batch* b, hipStream_t st) {
-  if (!b->rs_roc) {
-    DALLOC(b->rs_roc, (size_t)b->n_vcf * 3 * (size_t)b->n_bins);
-    DALLOC(b->rs_scal, (size_t)b->n_vcf * 8);
-    DALLOC(b->rs_flags, (size_t)b->n_vcf);
-    b->dev_bytes += (int64_t)b->n_vcf * (3 * b->n_bins * 8 + 64 + 4);
-  }
+  int rc = b->rs_roc.grow((int64_t)b->n_vcf * 3 * b->n_bins, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->rs_scal.grow((int64_t)b->n_vcf * 8, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->rs_flags.grow(b->n_vcf, &b->dev_bytes);
+  if (rc != QM_OK) return rc;
   FinalizeParams F = finalize_params(b, nullptr);
   F.roc = b->rs_roc; F.scalars = b->rs_scal; F.vcf_flags = b->rs_flags; F.vcf_posor = nullptr;
   F.parts = 1;   // the tile offsets only: the rows it would sum are thrown away (611 span rows per 10 M-record VCF: 0.3 ms for sixteen of them)
@@ -2063,15 +2023,13 @@ extern "C" int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, vo
   HIPCHK(hipSetDevice(c->dev));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   const size_t nv = (size_t)b->n_vcf;
-  if (!b->d_motifs) {
-    DALLOC(b->d_motifs, nv * MOTIF_ROW_WORDS);
-    DALLOC(b->d_mgen, nv);
-    HIPCHK(hipHostMalloc((void**)&b->h_mgen, nv * sizeof(GenomeRef), hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&b->ev_motif, hipEventDisableTiming));
-    b->dev_bytes += (int64_t)(nv * (MOTIF_ROW_WORDS * 8 + sizeof(GenomeRef)));
-  } else {
-    HIPCHK(hipEventSynchronize(b->ev_motif));   // the previous call's copy has read the page-locked descriptors
-  }
+  // first use: every piece on its own, so that a call that failed half way is completed by the next
+  int rc = b->d_motifs.grow((int64_t)(nv * MOTIF_ROW_WORDS), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->d_mgen.grow((int64_t)nv, &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  if (!b->h_mgen) HIPCHK(hipHostMalloc((void**)&b->h_mgen, nv * sizeof(GenomeRef), hipHostMallocDefault));
+  if (!b->ev_motif) HIPCHK(hipEventCreateWithFlags(&b->ev_motif, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(b->ev_motif));   // the previous call's copy has read the page-locked descriptors
   for (size_t v = 0; v < nv; ++v) {
     const int gid = genome_id_per_vcf[v];
     b->h_mgen[v] = gid < 0 ? GenomeRef{nullptr, 0} : GenomeRef{c->genomes[(size_t)gid].d_words, c->genomes[(size_t)gid].len};
@@ -2123,34 +2081,24 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
   if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
   else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
-  if (!b->d_hit_off) {
-    DALLOC(b->d_hit_off, nv + 1);
-    b->dev_bytes += (int64_t)((nv + 1) * 8);
-    b->hit_off_uploaded = false;
-  }
+  int rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->d_intruth.grow((int64_t)mask_words, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->d_hits.grow((int64_t)hw, &b->dev_bytes);
+  if (rc != QM_OK) return rc;
   if (!b->hit_off_uploaded) {
     HIPCHK(hipMemcpy(b->d_hit_off, b->h_hit_off.data(), (nv + 1) * 8, hipMemcpyHostToDevice));
     b->hit_off_uploaded = true;
   }
-  if (!b->d_intruth) {
-    DALLOC(b->d_intruth, mask_words);
-    b->dev_bytes += (int64_t)(mask_words * 8);
-    b->intruth_cleared = false;
-  }
   if (!b->intruth_cleared) {
     HIPCHK(hipMemsetAsync(b->d_intruth, 0, mask_words * 8, st));   // the bytes between the VCFs are never written again
     b->intruth_cleared = true;
-  }
-  if (!b->d_hits) {
-    DALLOC(b->d_hits, hw);
-    b->dev_bytes += (int64_t)(hw * 4);
   }
   HIPCHK(hipMemsetAsync(b->d_hits, 0, hw * 4, st));
   TruthHitsParams P;
   P.spans = b->d_spans; P.truths = c->d_truths; P.hit_off = b->d_hit_off;
   P.pos = b->pos; P.anib = b->anib; P.flags = b->flags;
   P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
-  P.hits = b->d_hits; P.mask_intruth = reinterpret_cast<uint8_t*>(b->d_intruth);
+  P.hits = b->d_hits; P.mask_intruth = reinterpret_cast<uint8_t*>(b->d_intruth.p);
   P.n_spans = (int32_t)b->L.spans.size();
   launch_truth_hits(P, st);
   HIPCHK(hipGetLastError());
