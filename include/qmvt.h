@@ -93,6 +93,14 @@ extern "C" {
 #define QM_MOTIF_REF_MISMATCH 97
 #define QM_MOTIF_COLS 98
 
+/* allele-frequency profiles (qm_batch_af_profile): per VCF and class (0 = TP, 1 = FP) a grid
+ * [n_af_bins][n_pos_bins] and QM_AFP_EXTRA further counts; every counted record is in exactly one of the three. */
+#define QM_AFP_NO_AF 0    /* the record's allele frequency is NaN (INFO carries none the rule's pattern takes) */
+#define QM_AFP_OUTSIDE 1  /* af < 0, af > 1, pos < 1 or (pos - 1) / window >= n_pos_bins */
+#define QM_AFP_N_GRID 2   /* counted in the grid: the grid's total */
+#define QM_AFP_EXTRA 3
+#define QM_AFP_MAX_CELLS 8192 /* n_af_bins * n_pos_bins at most */
+
 /* per-VCF scalar slots (int64 each) */
 enum {
   QM_S_NPASS = 0,    /* kept lines = R `calleridentify` (caller_performance_compare.R:82) */
@@ -247,6 +255,26 @@ int qm_batch_get_columns(qm_batch* b, int vcf, int32_t* pos, int32_t* ref, int32
 int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, void* stream);
 /* Waits for the latest qm_batch_motifs, then copies [n_vcf][3][QM_MOTIF_COLS] uint64; QM_E_STATE if the batch ran since. */
 int qm_batch_get_motifs(qm_batch* b, uint64_t* out);
+/* ---- allele-frequency profiles --------------------------------------------------------------------------
+ * The numbers behind `{mix}.{caller}.snp.profile.pdf` of rule mutationcontext (scripts/mutation_context_profile.R:19-46,
+ * filterVCF + varPlot: genome position against allele frequency of every TP and FP SNV).
+ * qm_batch_upload_af: the allele frequencies of one VCF (qm_vcf_scan_af's column; NaN = none), [n_records of vcf] floats, into
+ * an optional device column that is allocated on the first call; blocking.  The VCF is then marked as having frequencies;
+ * qm_batch_upload, qm_batch_upload_async and qm_batch_synth of the VCF clear the mark (upload the frequencies after the
+ * columns).  A batch that never calls it allocates nothing.
+ * qm_batch_af_profile: one streaming pass over the finished batch in input order, asynchronous on `stream` (NULL = the
+ * context's own).  Counted: the records qm_batch_motifs counts (kept, single-base REF and ALT), class 0 = TP, 1 = FP.  A counted
+ * record goes to QM_AFP_NO_AF (af is NaN), else to QM_AFP_OUTSIDE (af < 0, af > 1, pos < 1, (pos - 1) / window >= n_pos_bins),
+ * else to QM_AFP_N_GRID and cell [min(n_af_bins - 1, (int)(af * (float)n_af_bins))][(pos - 1) / window] of the grid.  VCFs
+ * without the mark keep zero rows.  1 <= window < 2^28, 1 <= n_af_bins, 1 <= n_pos_bins, n_af_bins * n_pos_bins <=
+ * QM_AFP_MAX_CELLS: QM_E_INVAL otherwise.  QM_E_STATE unless the latest qm_batch_run was finished.  May be repeated with
+ * other bin counts.
+ * qm_batch_get_af_profile: waits for the latest qm_batch_af_profile, then copies its counts (`extra` may be NULL);
+ * QM_E_STATE if the batch ran since or no profile was made. */
+int qm_batch_upload_af(qm_batch* b, int vcf, const float* af);
+int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bins, int32_t n_af_bins, void* stream);
+int qm_batch_get_af_profile(qm_batch* b, uint64_t* grid /*[n_vcf][2][n_af_bins][n_pos_bins]*/,
+                            uint64_t* extra /*[n_vcf][2][QM_AFP_EXTRA]*/);
 /* ---- the truth-side view ------------------------------------------------------------------------------
  * The sets behind scripts/caller_performance_compare.R:110-119,510-549 (`Genome` against the callers' distinct single-base
  * keys) seen from the truth set: which truth keys a VCF's kept records hit, which records carry a key of the truth set, and,
@@ -399,6 +427,19 @@ int qm_vcf_scan_ext(const uint8_t* text, size_t len, int64_t cap_lines, int64_t*
 int64_t qm_truth_scan_ext(const uint8_t* text, size_t len, int mode, int64_t cap, int32_t* pos, int32_t* ref,
                           int32_t* alt, int64_t* out_counts /*[5]*/, qm_dict* dict);
 
+/* The allele frequency of every data line as rule mutationcontext reads it (scripts/mutation_context_profile.R:26:
+ * `as.numeric(gsub(".*AF=([01]\\.[0-9]+);.*$", "\\1", INFO, perl=T))`), from a text that qm_vcf_scan / qm_vcf_scan_ext has
+ * scanned: one float per data line (kinds QM_LINE_DATA, QM_LINE_DATA_HOST, QM_LINE_REFUSED), in record order.  INFO is the
+ * 8th tab-separated field (up to the next tab or the line's end; a '\r' in front of the newline belongs to it).  The value
+ * comes from the LAST place in the field where `AF=` is followed by 0 or 1, '.', one or more digits and ';' (the pattern's
+ * leading `.*` is greedy: `MAF=0.2;` counts, `AF=0.5` at the field's end without ';' does not); its text is converted as a
+ * correctly rounded double and then rounded to float.  No such place, or fewer than 8 fields: quiet NaN.  (R hands an INFO
+ * field without a match to as.numeric whole, so a field that is itself a number becomes a frequency there; here it is NaN:
+ * DESIGN.md 4.9.)  info[0] = data lines with a value, info[1] = data lines with fewer than 8 fields.  The inputs are not
+ * modified. */
+int qm_vcf_scan_af(const uint8_t* text, size_t len, int64_t n_lines, const int64_t* line_off,
+                   const uint8_t* line_kind, float* af /*[n_data]*/, int64_t* info /*[2]*/);
+
 /* ---- host path for what the columns cannot describe -----------
  * qm_patterns is the pattern list the reference feeds to `fgrep -wf` (extract_TP_FP_SNPs.py:47-53, :92-98), kept as
  * TEXT: one pattern X \t . \t Y \t Z per truth row that satisfies the awk program, '#' rows included.  mode as
@@ -507,6 +548,25 @@ typedef struct qm_truthside_args {
 int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                                void* global_dev, const qm_truthside_args* ts);
+
+/* qm_extract_files_motifs plus the allele-frequency profile: both halves of rule mutationcontext in one call.
+ * genome_id / motifs may be NULL (no spectra).  Jobs with want[j] != 0 have their INFO column scanned (qm_vcf_scan_af) and
+ * uploaded beside the other columns; the profile pass runs behind the classification (and behind the motif pass).  Wanted
+ * pure-strain jobs join the batch against an empty truth set, as those that name a genome do: everything kept is FP.
+ * grid / extra: qm_batch_af_profile's rows per job (zero for jobs that are not wanted).  points_out[j] (array or entries may be
+ * NULL): the data frame R plots, "Position\tFrequency\ttype\n", then every counted record, the FP ones first, then the TP
+ * ones, each in file order (rbind(fp_snp, tp_snp)): the line's POS text, the text the pattern captured or NA, FP / TP.
+ * Atomic (temp file + rename).  The VCF outputs, stats and roc are those of qm_extract_files_ex. */
+typedef struct qm_profile_args {
+  const uint8_t* want;            /* [n_jobs] 0/1 */
+  int32_t window, n_pos_bins, n_af_bins, reserved;
+  uint64_t* grid;                 /* [n_jobs][2][n_af_bins][n_pos_bins] */
+  uint64_t* extra;                /* [n_jobs][2][QM_AFP_EXTRA] */
+  const char* const* points_out;  /* [n_jobs] or entries NULL */
+} qm_profile_args;
+int qm_extract_files_profile(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                             void* global_dev, const int32_t* genome_id, uint64_t* motifs, const qm_profile_args* profile);
 
 /* `bgzip -c` (the *.vcf.gz outputs the same rules declare, rules/vis_eval_vcf.smk:29,36 ...): BGZF = gzip members of at
  * most 64 KiB with a 'BC' extra field + the EOF member; zcat and tabix / htslib read it.  level -1 = zlib's default (6,

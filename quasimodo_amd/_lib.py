@@ -20,6 +20,11 @@ QM_MOTIF_REF_MISMATCH = 97
 QM_MOTIF_COLS = 98
 QM_TRUTH_GROUP_MAX = 5
 QM_TRUTH_REGIONS = 32
+QM_AFP_NO_AF = 0
+QM_AFP_OUTSIDE = 1
+QM_AFP_N_GRID = 2
+QM_AFP_EXTRA = 3
+QM_AFP_MAX_CELLS = 8192
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -36,6 +41,7 @@ EXPORTS = (
     "qm_comm_create", "qm_comm_make_id", "qm_comm_create_rank", "qm_allreduce_counters", "qm_comm_collectives", "qm_comm_destroy",
     "qm_genome_load", "qm_genome_release", "qm_batch_motifs", "qm_batch_get_motifs", "qm_extract_files_motifs",
     "qm_batch_truth_hits", "qm_batch_get_truth_hits", "qm_batch_get_intruth_mask", "qm_batch_truth_regions", "qm_extract_files_truthside",
+    "qm_vcf_scan_af", "qm_batch_upload_af", "qm_batch_af_profile", "qm_batch_get_af_profile", "qm_extract_files_profile",
 )
 
 
@@ -62,6 +68,12 @@ class TruthSideArgs(C.Structure):
                 ("regions", C.c_void_p), ("fp_regions", C.c_void_p), ("missed_out", C.POINTER(C.c_char_p))]
 
 
+class ProfileArgs(C.Structure):
+    """include/qmvt.h qm_profile_args"""
+    _fields_ = [("want", C.c_void_p), ("window", C.c_int32), ("n_pos_bins", C.c_int32), ("n_af_bins", C.c_int32), ("reserved", C.c_int32),
+                ("grid", C.c_void_p), ("extra", C.c_void_p), ("points_out", C.POINTER(C.c_char_p))]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -82,7 +94,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -249,6 +261,12 @@ def lib():
     L.qm_batch_truth_regions.argtypes = [vp, i32, vp, vp, vp, vp]
     L.qm_extract_files_truthside.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                              C.POINTER(TruthSideArgs)]
+    L.qm_vcf_scan_af.argtypes = [C.c_char_p, C.c_size_t, i64, vp, vp, vp, vp]
+    L.qm_batch_upload_af.argtypes = [vp, i32, vp]
+    L.qm_batch_af_profile.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.qm_batch_get_af_profile.argtypes = [vp, vp, vp]
+    L.qm_extract_files_profile.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                           vp, vp, C.POINTER(ProfileArgs)]
     _lib = L
     return L
 

@@ -23,6 +23,7 @@
 #include "../../include/qmvt.h"
 #include "qmvt_dev.h"
 #include "qmvt_motif.h"
+#include "qmvt_afprofile.h"
 #include "qmvt_truthside.h"
 
 using namespace qm;
@@ -582,6 +583,17 @@ struct qm_batch {
   GenomeRef* h_mgen = nullptr;
   hipEvent_t ev_motif = nullptr;
   bool motifs_valid = false;          // qm_batch_motifs was called behind the latest run
+  // qm_batch_upload_af / qm_batch_af_profile (lazy, DESIGN.md 4.9: a batch that never uploads frequencies allocates nothing): the
+  // af column laid out like pos, the per-VCF "has af" marks (host: set by qm_batch_upload_af, cleared by every writer of the
+  // VCF's columns; device: the copy the latest pass read), the [n_vcf][2][n_af][n_pos] grids and [n_vcf][2][QM_AFP_EXTRA] extras
+  DevBuf<float> d_af;
+  std::vector<uint8_t> h_afmark;      // [n_vcf], sized with the batch: threads that upload different VCFs touch different bytes
+  std::mutex af_mu;                   // the first qm_batch_upload_af allocates the column
+  DevBuf<uint8_t> d_afmark;
+  DevBuf<uint64_t> d_afgrid, d_afextra;
+  hipEvent_t ev_afp = nullptr;
+  int32_t afp_cells = 0;              // n_af * n_pos of the latest qm_batch_af_profile
+  bool afp_valid = false;             // qm_batch_af_profile was called behind the latest run
   // qm_batch_truth_hits (lazy): the per-VCF hit bitmaps one behind the other (h_hit_off[v] = first word of VCF v,
   // h_hit_off[n_vcf] = all), the record mask (the size of mask_pass), the lookup counter; ev_truth says when the pass is done
   DevBuf<uint32_t> d_hits;
@@ -613,6 +625,7 @@ static void batch_free(qm_batch* b) {
   if (b->h_mgen) (void)hipHostFree(b->h_mgen);
   if (b->ev_motif) (void)hipEventDestroy(b->ev_motif);
   if (b->ev_truth) (void)hipEventDestroy(b->ev_truth);
+  if (b->ev_afp) (void)hipEventDestroy(b->ev_afp);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -634,6 +647,7 @@ static int batch_alloc(qm_ctx* c, int n_vcf, const int64_t* n_records, const int
   b->ctx = c;
   b->n_vcf = n_vcf;
   b->n_bins = n_bins;
+  b->h_afmark.assign((size_t)n_vcf, (uint8_t)0);
   build_layout(n_records, truth_ids, n_vcf, b->L);
   const Layout& L = b->L;
   const size_t nspans = L.spans.size(), ntiles = L.tile_vcf.size();
@@ -739,6 +753,7 @@ extern "C" int qm_batch_upload(qm_batch* b, int v, const int32_t* pos, const int
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
   }
   b->ran = b->finished = false;
+  b->h_afmark[(size_t)v] = 0;   // the frequencies belonged to the records just replaced
   forget_known(b, v);
   return QM_OK;
 }
@@ -764,6 +779,7 @@ extern "C" int qm_batch_upload_async(qm_batch* b, int v, const int32_t* pos, con
     HIPCHK(hipGetLastError());
   }
   b->ran = b->finished = false;
+  b->h_afmark[(size_t)v] = 0;   // the frequencies belonged to the records just replaced
   forget_known(b, v);
   return QM_OK;
 }
@@ -817,6 +833,7 @@ extern "C" int qm_batch_synth(qm_batch* b, const qm_synth_cfg* cfg) {
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(b->ctx->stream));
   b->ran = b->finished = false;
+  std::fill(b->h_afmark.begin(), b->h_afmark.end(), (uint8_t)0);
   forget_known(b, -1);
   return QM_OK;
 }
@@ -933,6 +950,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->ran = true;
   b->finished = false;
   b->motifs_valid = false;
+  b->afp_valid = false;
   b->hits_valid = false;
   b->last_global = g;
   return QM_OK;
@@ -2054,6 +2072,70 @@ extern "C" int qm_batch_get_motifs(qm_batch* b, uint64_t* out) {
   HIPCHK(hipSetDevice(b->ctx->dev));
   HIPCHK(hipEventSynchronize(b->ev_motif));
   HIPCHK(hipMemcpy(out, b->d_motifs, (size_t)b->n_vcf * MOTIF_ROW_WORDS * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+// the allele-frequency profiles of the finished batch
+extern "C" int qm_batch_upload_af(qm_batch* b, int v, const float* af) {
+  if (!b || v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_upload_af: bad arguments");
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  if (d.n > 0 && !af) return fail(QM_E_INVAL, "qm_batch_upload_af: NULL column");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  {
+    std::lock_guard<std::mutex> g(b->af_mu);
+    if (!b->d_af) {   // first use: the column, defined everywhere (lanes past a VCF's last record are loaded and masked)
+      const int rc = b->d_af.grow(b->L.n_pad, &b->dev_bytes);
+      if (rc != QM_OK) return rc;
+      HIPCHK(hipMemsetAsync(b->d_af, 0, (size_t)b->L.n_pad * sizeof(float), b->ctx->stream));   // (on the context's stream, as at create)
+      HIPCHK(hipStreamSynchronize(b->ctx->stream));
+    }
+  }
+  if (d.n > 0) HIPCHK(hipMemcpy(b->d_af + d.off, af, (size_t)d.n * sizeof(float), hipMemcpyHostToDevice));
+  b->h_afmark[(size_t)v] = 1;
+  return QM_OK;
+}
+extern "C" int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bins, int32_t n_af_bins, void* stream) {
+  NEED_FINISHED(b, "qm_batch_af_profile");
+  if (window < 1 || window >= QM_POS_LIMIT || n_pos_bins < 1 || n_af_bins < 1 || (int64_t)n_pos_bins * n_af_bins > QM_AFP_MAX_CELLS)
+    return fail(QM_E_INVAL, "qm_batch_af_profile: window %d, %d x %d bins (1 <= window < 2^28, at most %d cells)", window, n_af_bins, n_pos_bins, QM_AFP_MAX_CELLS);
+  qm_ctx* c = b->ctx;
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const size_t nv = (size_t)b->n_vcf, cells = (size_t)n_pos_bins * (size_t)n_af_bins;
+  if (!b->ev_afp) HIPCHK(hipEventCreateWithFlags(&b->ev_afp, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(b->ev_afp));   // the previous pass has read the marks and left the outputs
+  int rc = b->d_afgrid.grow((int64_t)(nv * 2 * cells), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->d_afextra.grow((int64_t)(nv * 2 * AFP_EXTRA), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->d_afmark.grow((int64_t)nv, &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  bool any = false;
+  for (size_t v = 0; v < nv; ++v) any = any || b->h_afmark[v];
+  HIPCHK(hipMemcpy(b->d_afmark, b->h_afmark.data(), nv, hipMemcpyHostToDevice));   // blocking: the marks may change behind the call
+  HIPCHK(hipMemsetAsync(b->d_afgrid, 0, nv * 2 * cells * 8, st));
+  HIPCHK(hipMemsetAsync(b->d_afextra, 0, nv * 2 * AFP_EXTRA * 8, st));
+  if (any) {   // (no mark anywhere: there may be no column at all, and every row is zero)
+    AfProfileParams P;
+    P.spans = b->d_spans; P.has_af = b->d_afmark;
+    P.pos = b->pos; P.af = b->d_af; P.anib = b->anib; P.ref = b->ref; P.alt = b->alt;
+    P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+    P.grid = b->d_afgrid; P.extra = b->d_afextra;
+    P.n_spans = (int32_t)b->L.spans.size();
+    P.window = window; P.n_pos = n_pos_bins; P.n_af = n_af_bins;
+    P.div = afp_div((uint32_t)window);
+    launch_af_profile(P, b->ext, st);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(b->ev_afp, st));
+  b->afp_cells = (int32_t)cells;
+  b->afp_valid = true;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_af_profile(qm_batch* b, uint64_t* grid, uint64_t* extra) {
+  if (!b || !grid) return fail(QM_E_INVAL, "qm_batch_get_af_profile: bad arguments");
+  if (!b->afp_valid) return fail(QM_E_STATE, "qm_batch_get_af_profile: no qm_batch_af_profile behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_afp));
+  HIPCHK(hipMemcpy(grid, b->d_afgrid, (size_t)b->n_vcf * 2 * (size_t)b->afp_cells * 8, hipMemcpyDeviceToHost));
+  if (extra) HIPCHK(hipMemcpy(extra, b->d_afextra, (size_t)b->n_vcf * 2 * AFP_EXTRA * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 // the truth-side view of the finished batch

@@ -11,11 +11,13 @@
 #include <array>
 #include <atomic>
 #include <cerrno>
+#include <charconv>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <set>
@@ -1624,4 +1626,72 @@ extern "C" int qm_mummer2vcf(const uint8_t* table, size_t table_len, const uint8
   *out = buf; *out_len = o.size();
   return QM_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The allele frequency of a data line as rule mutationcontext reads it (scripts/mutation_context_profile.R:26):
+// gsub(".*AF=([01]\\.[0-9]+);.*$", "\\1", INFO, perl = T), then as.numeric.  A scanner of its own: the tokeniser above stops
+// at QUAL and stays as it is.
+// ---------------------------------------------------------------------------
+// The INFO field of the line [s, e) (no newline): false when the line has fewer than 8 tab-separated fields.
+static bool af_info_field(const uint8_t* s, const uint8_t* e, const uint8_t** fb, const uint8_t** fe) {
+  for (int k = 0; k < 7; ++k) {
+    const uint8_t* t = (const uint8_t*)memchr(s, '\t', (size_t)(e - s));
+    if (!t) return false;
+    s = t + 1;
+  }
+  const uint8_t* t = (const uint8_t*)memchr(s, '\t', (size_t)(e - s));
+  *fb = s;
+  *fe = t ? t : e;
+  return true;
+}
+// What the pattern captures in the field [fb, fe): the leading `.*` is greedy, so the LAST place where "AF=" is followed by
+// [01], '.', one or more digits and ';'.  ([0-9]+ takes every digit there is: a run that does not end at ';' cannot match shorter.)
+static bool af_capture(const uint8_t* fb, const uint8_t* fe, const uint8_t** cb, const uint8_t** ce) {
+  for (ptrdiff_t o = (fe - fb) - 7; o >= 0; --o) {   // the shortest match, "AF=0.0;", is 7 bytes
+    const uint8_t* p = fb + o;
+    if (p[0] != 'A' || p[1] != 'F' || p[2] != '=' || (p[3] != '0' && p[3] != '1') || p[4] != '.') continue;
+    const uint8_t* q = p + 5;
+    while (q < fe && *q >= '0' && *q <= '9') ++q;
+    if (q == p + 5 || q == fe || *q != ';') continue;
+    *cb = p + 3;
+    *ce = q;
+    return true;
+  }
+  return false;
+}
+// internal (qmvt_pipeline.cpp: the points file carries the captured text): 1 = captured, 0 = no match, -1 = fewer than 8 fields
+int qm_host_af_text(const uint8_t* line, size_t n, const uint8_t** cb, const uint8_t** ce) {
+  const uint8_t *fb, *fe;
+  if (!af_info_field(line, line + n, &fb, &fe)) return -1;
+  return af_capture(fb, fe, cb, ce) ? 1 : 0;
+}
+
+extern "C" int qm_vcf_scan_af(const uint8_t* text, size_t len, int64_t n_lines, const int64_t* line_off, const uint8_t* line_kind,
+                              float* af, int64_t* info) {
+  if (n_lines < 0 || (n_lines && (!line_off || !line_kind)) || (!text && len)) return QM_E_INVAL;
+  int64_t rec = 0, n_val = 0, n_short = 0;
+  for (int64_t i = 0; i < n_lines; ++i) {
+    const uint8_t k = line_kind[i];
+    if (!(k == QM_LINE_DATA || k == QM_LINE_DATA_HOST || k == QM_LINE_REFUSED)) continue;   // the kinds that own a record
+    if (!af) return QM_E_INVAL;
+    size_t b = (size_t)line_off[i], e = (size_t)line_off[i + 1];
+    if (e > len) e = len;
+    if (b > e) return QM_E_INVAL;
+    if (e > b && text[e - 1] == '\n') --e;
+    float v = std::numeric_limits<float>::quiet_NaN();
+    const uint8_t *cb, *ce;
+    const int got = qm_host_af_text(text + b, e - b, &cb, &ce);
+    if (got < 0) ++n_short;
+    if (got > 0) {
+      double d = 0.0;   // [01].[0-9]+ : always in range; correctly rounded, whatever the locale
+      (void)std::from_chars((const char*)cb, (const char*)ce, d, std::chars_format::fixed);
+      v = (float)d;
+      ++n_val;
+    }
+    af[rec++] = v;
+  }
+  if (info) { info[0] = n_val; info[1] = n_short; }
+  return QM_OK;
+}
+
 extern "C" void qm_free(void* p) { free(p); }

@@ -39,6 +39,7 @@ int qm_host_scan_threads(const uint8_t* text, size_t len, int64_t cap_lines, int
 int qm_host_write_masks(const char* path, const uint8_t* text, size_t len, int64_t n_lines, const int64_t* line_off,
                         const uint8_t* line_kind, const uint64_t* kept, const uint64_t* tp, const uint8_t* flags, int select);
 int qm_host_threads(void);
+int qm_host_af_text(const uint8_t* line, size_t n, const uint8_t** cb, const uint8_t** ce);   // what the rule's AF pattern captures in a data line
 void qm_set_error(const char* msg);   // qmvt_api.cpp: what qm_last_error returns
 int qm_device_add_u64(qm_ctx* ctx, uint64_t* dst, const uint64_t* src, int64_t n);   // qmvt_api.cpp: dst[i] += src[i] on the device, blocking
 int qm_device_zero(qm_ctx* ctx, void* dst, size_t bytes);                              // qmvt_api.cpp: on the context's device, blocking
@@ -136,6 +137,7 @@ struct JobState {
   uint64_t *kept = nullptr, *tp = nullptr;   // class masks, (n_data + 63) / 64 words each
   qm_vcf_cols info{};
   int64_t ex[5] = {0, 0, 0, 0, 0};
+  std::vector<float> af;   // (profiled jobs) qm_vcf_scan_af's column
   int truth = -1;      // index into the call's distinct truth files
   int batch_v = -1;    // VCF index inside the engine batch (mixed samples only)
   int rc = QM_OK;
@@ -217,6 +219,37 @@ int write_fn_file(const char* path, const TruthState& t, const uint32_t* bits) {
   return write_all_atomic(path, head + rows);
 }
 
+// `Position Frequency type` of every counted record (kept by the class mask, single-base REF and ALT) of one profiled job: the
+// FP records, then the TP records, each in file order -- rbind(fp_snp, tp_snp) of varPlot (scripts/mutation_context_profile.R:
+// 29-40).  Position is the line's POS text, Frequency the text the rule's pattern captured or NA.
+int write_points_file(const char* path, const JobState& s) {
+  std::string out[2];   // [FP, TP]
+  const uint8_t* text = s.vcf.p;
+  const size_t len = s.vcf.n;
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    const uint8_t k = s.line_kind[(size_t)i];
+    if (!(k == QM_LINE_DATA || k == QM_LINE_DATA_HOST || k == QM_LINE_REFUSED)) continue;
+    const int64_t r = rec++;
+    if (!((s.kept[r >> 6] >> (r & 63)) & 1ull) || (uint32_t)(s.ref[r] | s.alt[r]) >= 4u) continue;
+    const int tp = (int)((s.tp[r >> 6] >> (r & 63)) & 1ull);
+    size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], len);
+    if (e > b && text[e - 1] == '\n') --e;
+    const uint8_t* t1 = (const uint8_t*)memchr(text + b, '\t', e - b);
+    if (!t1) continue;   // (a kept line has its five columns)
+    const uint8_t* p0 = t1 + 1;
+    const uint8_t* t2 = (const uint8_t*)memchr(p0, '\t', (size_t)(text + e - p0));
+    std::string& o = out[tp];
+    o.append((const char*)p0, (size_t)((t2 ? t2 : text + e) - p0));
+    o.push_back('\t');
+    const uint8_t *cb, *ce;
+    if (qm_host_af_text(text + b, e - b, &cb, &ce) > 0) o.append((const char*)cb, (size_t)(ce - cb));
+    else o.append("NA");
+    o.append(tp ? "\tTP\n" : "\tFP\n");
+  }
+  return write_all_atomic(path, "Position\tFrequency\ttype\n" + out[0] + out[1]);
+}
+
 }  // namespace
 
 // called by qm_destroy: the page-locked buffers of a context go with it
@@ -237,12 +270,12 @@ extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts);
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa);
 
 extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                    qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
                                    int n_slots, void* global_dev) {
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr);
 }
 
 // rule mutationcontext behind the worker: the motif pass runs on the batch the classification leaves in HBM
@@ -251,7 +284,27 @@ extern "C" int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_jo
                                        int n_slots, void* global_dev, const int32_t* genome_id, uint64_t* motifs_out) {
   if (n_jobs > 0 && (!genome_id || !motifs_out)) return fail(QM_E_INVAL, "qm_extract_files_motifs: NULL genome ids or output");
   if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, nullptr);
+}
+
+// both halves of rule mutationcontext behind the worker: the spectra (optional) and the allele-frequency profile
+extern "C" int qm_extract_files_profile(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                        qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                        int n_slots, void* global_dev, const int32_t* genome_id, uint64_t* motifs_out,
+                                        const qm_profile_args* profile) {
+  if (!profile || (n_jobs > 0 && (!profile->want || !profile->grid || !profile->extra))) return fail(QM_E_INVAL, "qm_extract_files_profile: NULL arguments");
+  if ((genome_id == nullptr) != (motifs_out == nullptr)) return fail(QM_E_INVAL, "qm_extract_files_profile: genome ids and the motif output come together");
+  if (profile->window < 1 || profile->window >= QM_POS_LIMIT || profile->n_pos_bins < 1 || profile->n_af_bins < 1 ||
+      (int64_t)profile->n_pos_bins * profile->n_af_bins > QM_AFP_MAX_CELLS)
+    return fail(QM_E_INVAL, "qm_extract_files_profile: window " + std::to_string(profile->window) + ", " + std::to_string(profile->n_af_bins) + " x " +
+                                std::to_string(profile->n_pos_bins) + " bins (1 <= window < 2^28, at most " + std::to_string(QM_AFP_MAX_CELLS) + " cells)");
+  const size_t cells = (size_t)profile->n_pos_bins * (size_t)profile->n_af_bins;
+  if (n_jobs > 0) {
+    memset(profile->grid, 0, sizeof(uint64_t) * 2 * cells * (size_t)n_jobs);
+    memset(profile->extra, 0, sizeof(uint64_t) * 2 * QM_AFP_EXTRA * (size_t)n_jobs);
+  }
+  if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, profile);
 }
 
 // the truth-side view behind the worker: missed-variant lists and the caller Venn regions of groups of jobs
@@ -273,12 +326,12 @@ extern "C" int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file
   }
   memset(ts->regions, 0, sizeof(uint64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
   if (ts->fp_regions) memset(ts->fp_regions, 0, sizeof(int64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, ts);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, ts, nullptr);
 }
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts) {
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
     return fail(QM_E_INVAL, "qm_extract_files: bad arguments");
   if (global_dev && (n_slots < 1 || (n_jobs && !truth_slot))) return fail(QM_E_INVAL, "qm_extract_files_ex: global_dev needs truth_slot and n_slots >= 1");
@@ -305,10 +358,11 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
   }
   qm_dict* dict = ext ? qm_dict_create() : nullptr;
   std::vector<TruthState> T;
-  // which jobs the batch holds: every mixed-sample job, and the pure-strain jobs that name a genome (against an empty truth set,
-  // for their motif rows only: their files, stats and ROC rows are made as for any pure-strain job)
+  // which jobs the batch holds: every mixed-sample job, and the pure-strain jobs that name a genome or want a profile (against an
+  // empty truth set, for their motif / profile rows only: their files, stats and ROC rows are made as for any pure-strain job)
   auto has_genome = [&](int j) { return genome_id && genome_id[j] >= 0; };
-  auto in_batch = [&](int j) { return !jobs[j].pure || has_genome(j); };
+  auto wants_profile = [&](int j) { return pa && pa->want[j] != 0; };
+  auto in_batch = [&](int j) { return !jobs[j].pure || has_genome(j) || wants_profile(j); };
   int empty_tid = -1;
 
   // ---- the VCFs go through as ONE batch: stage one (map, count, tokenise, upload) of every VCF, then stage two (engine,
@@ -423,7 +477,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
     if (truth_rc != QM_OK) return fail(truth_rc, truth_msg);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
     for (int j = 0; j < n_jobs; ++j)
-      if (jobs[j].pure && has_genome(j) && empty_tid < 0) {
+      if (jobs[j].pure && in_batch(j) && empty_tid < 0) {
         const int rc = qm_truth_load(ctx, nullptr, nullptr, nullptr, 0, &empty_tid);
         if (rc != QM_OK) return rc;
       }
@@ -465,10 +519,23 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
         if (s.rc == QM_OK) s.rc = QM_E_INVAL;
         return;
       }
+      if (wants_profile(j)) {   // the INFO column, by a scanner of its own
+        int64_t ai[2];
+        s.af.resize((size_t)s.n_data + 1);
+        s.rc = qm_vcf_scan_af(s.vcf.p, s.vcf.n, s.info.n_lines, s.line_off.data(), s.line_kind.data(), s.af.data(), ai);
+        if (s.rc != QM_OK) { s.err = "scanning the INFO column failed"; return; }
+      }
+      // the frequencies follow the columns (whose upload clears the VCF's mark); a blocking copy of this VCF's floats
+      auto upload_af = [&]() {
+        if (s.rc != QM_OK || !wants_profile(j)) return;
+        s.rc = qm_batch_upload_af(batch, s.batch_v, s.af.data());
+        if (s.rc != QM_OK) s.err = qm_last_error(ctx);
+      };
       if (jobs[j].pure) {
-        if (has_genome(j) && !(strict && s.info.n_refused)) {
+        if (in_batch(j) && !(strict && s.info.n_refused)) {
           s.rc = qm_batch_upload_async(batch, s.batch_v, s.pos, s.ref, s.alt, s.qual, s.flags, copy_stream);
           if (s.rc != QM_OK) s.err = qm_last_error(ctx);
+          upload_af();
         }
         return;
       }
@@ -482,6 +549,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (s.rc == QM_OK && !(strict && s.info.n_refused)) {
         s.rc = qm_batch_upload_async(batch, s.batch_v, s.pos, s.ref, s.alt, s.qual, s.flags, copy_stream);
         if (s.rc != QM_OK) s.err = qm_last_error(ctx);   // this thread's message: the caller's thread would not see it
+        upload_af();
       }
     });
     int rc = QM_OK;
@@ -538,6 +606,21 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
           for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
             if (in_batch(j) && has_genome(j))
               memcpy(motifs_out + (size_t)j * 3 * QM_MOTIF_COLS, &mo[(size_t)J[(size_t)j].batch_v * 3 * QM_MOTIF_COLS], sizeof(uint64_t) * 3 * QM_MOTIF_COLS);
+        }
+      }
+      if (rc == QM_OK && pa) {   // the profile pass behind the motif pass, on the same columns and masks
+        bool any = false;
+        for (int j = 0; j < n_jobs; ++j) any = any || wants_profile(j);
+        if (any) {
+          const size_t cells = (size_t)pa->n_pos_bins * (size_t)pa->n_af_bins;
+          std::vector<uint64_t> gr(nrec.size() * 2 * cells), exx(nrec.size() * 2 * QM_AFP_EXTRA);
+          rc = qm_batch_af_profile(batch, pa->window, pa->n_pos_bins, pa->n_af_bins, nullptr);
+          if (rc == QM_OK) rc = qm_batch_get_af_profile(batch, gr.data(), exx.data());
+          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
+            if (wants_profile(j)) {
+              memcpy(pa->grid + (size_t)j * 2 * cells, &gr[(size_t)J[(size_t)j].batch_v * 2 * cells], sizeof(uint64_t) * 2 * cells);
+              memcpy(pa->extra + (size_t)j * 2 * QM_AFP_EXTRA, &exx[(size_t)J[(size_t)j].batch_v * 2 * QM_AFP_EXTRA], sizeof(uint64_t) * 2 * QM_AFP_EXTRA);
+            }
         }
       }
       std::vector<std::vector<uint32_t>> hitbits, unibits;
@@ -630,7 +713,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
     for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
       JobState& s = J[(size_t)j];
-      if (jobs[j].pure) continue;
+      if (jobs[j].pure && !(wants_profile(j) && pa->points_out && pa->points_out[j])) continue;   // (a pure-strain job's masks: for its points file only)
       rc = qm_batch_get_masks(batch, s.batch_v, s.kept, s.tp);
       if (rc != QM_OK) err = qm_last_error(ctx);
     }
@@ -643,6 +726,14 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
     for (int j = 0; j < n_jobs; ++j) {
       if (jobs[j].pure) { W.push_back({j, 0, jobs[j].filtered_out, true}); W.push_back({j, 0, jobs[j].fp_out, true}); }   // cp filtered fp (:33-36)
       else { W.push_back({j, 0, jobs[j].filtered_out, false}); W.push_back({j, 1, jobs[j].tp_out, false}); W.push_back({j, 2, jobs[j].fp_out, false}); }
+    }
+    if (pa && pa->points_out) {   // the data frames R plots
+      std::vector<int> pj;
+      for (int j = 0; j < n_jobs; ++j) if (wants_profile(j) && pa->points_out[j]) pj.push_back(j);
+      std::vector<int> prc(pj.size(), QM_OK);
+      parallel_for((int)pj.size(), nthr, [&](int k) { prc[(size_t)k] = write_points_file(pa->points_out[pj[(size_t)k]], J[(size_t)pj[(size_t)k]]); });
+      for (size_t k = 0; k < pj.size(); ++k)
+        if (prc[k] != QM_OK) { err = std::string("cannot write ") + pa->points_out[pj[k]]; return prc[k]; }
     }
     std::vector<int> wrc(W.size(), QM_OK);
     parallel_for((int)W.size(), nthr, [&](int k) {

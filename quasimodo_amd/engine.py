@@ -151,7 +151,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None):
+                      truthside=None, profile=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -161,8 +161,13 @@ class Engine:
         truthside: {"fn": [path or None per job], "group": [group id or -1 per job], "missed": [path or None per group]} --
         qm_extract_files_truthside: the missed-variant lists are written, the rows of grouped jobs gain
         `truth_regions` and `fp_regions` (int64 [32] each, the same for every member; members in job order).
+        profile: {"want": [0/1 per job], "window": 1024, "n_pos_bins": 256, "n_af_bins": 20, "points": [path or None per job]} --
+        qm_extract_files_profile (combines with genomes, not with truthside): wanted rows gain `af_grid`
+        ([2][n_af_bins][n_pos_bins] uint64: TP, FP) and `af_extra` ([2][QM_AFP_EXTRA]); the points files are written.
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         import os
+        if profile is not None and truthside is not None:
+            raise ValueError("truthside and profile in one call are not supported")
         n = len(file_jobs)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
@@ -180,7 +185,24 @@ class Engine:
         args = (self._h, n, arr, int(n_bins), _lib.QM_BATCH_ALLELES if alleles else 0, int(bool(strict)), st, _p(roc), ph,
                 _p(slots), int(n_slots), C.c_void_p(global_dev) if global_dev else None)
         regs = None
-        if truthside is not None:
+        afg = None
+        if profile is not None:
+            want = _c([int(bool(w)) for w in profile["want"]] or [0], np.uint8)
+            pts = list(profile.get("points") or [None] * n)
+            if (n and want.shape[0] != n) or len(pts) != n:
+                raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(profile["want"]), len(pts), n))
+            nA, nP = int(profile.get("n_af_bins", 20)), int(profile.get("n_pos_bins", 256))
+            if nA < 1 or nP < 1 or nA * nP > _lib.QM_AFP_MAX_CELLS:
+                raise ValueError("profile: %d x %d bins (at most %d cells)" % (nA, nP, _lib.QM_AFP_MAX_CELLS))
+            afg = np.zeros((max(n, 1), 2, nA, nP), np.uint64)
+            afx = np.zeros((max(n, 1), 2, _lib.QM_AFP_EXTRA), np.uint64)
+            pt_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in pts])
+            pa = _lib.ProfileArgs(_p(want), int(profile.get("window", 1024)), nP, nA, 0, _p(afg), _p(afx), pt_arr)
+            with_g = gids is not None and any(g >= 0 for g in gids)
+            if with_g:
+                motifs = np.zeros((max(n, 1), 3, _lib.QM_MOTIF_COLS), np.uint64)
+            check(self._L.qm_extract_files_profile(*args, _p(_c(gids, np.int32)) if with_g else None, _p(motifs) if with_g else None, C.byref(pa)), self._h)
+        elif truthside is not None:
             if gids is not None and any(g >= 0 for g in gids):
                 raise ValueError("truthside and genomes in one call are not supported")
             enc = lambda x: None if x is None else os.fsencode(x)
@@ -208,6 +230,9 @@ class Engine:
                      roc=roc[k].copy())
             if motifs is not None:
                 r["motifs"] = motifs[k].copy()
+            if afg is not None and want[k]:
+                r["af_grid"] = afg[k].copy()
+                r["af_extra"] = afx[k].copy()
             if regs is not None and grp[k] >= 0:
                 r["truth_regions"] = regs[grp[k]].astype(np.int64)
                 r["fp_regions"] = fregs[grp[k]].copy()
@@ -353,6 +378,28 @@ class Batch:
         out = np.zeros((self.n_vcf, 3, _lib.QM_MOTIF_COLS), np.uint64)
         self._ck(self._L.qm_batch_get_motifs(self._h, _p(out)))
         return out
+
+    # -- allele-frequency profiles --------------------------------
+    def upload_af(self, v, af):
+        """qm_batch_upload_af: the allele frequencies of VCF v (float32 [n_records[v]], NaN = none), after its columns"""
+        a = _c(af, np.float32)
+        if a.shape[0] != int(self.n_records[v]):
+            raise ValueError("column length != n_records[%d]" % v)
+        self._ck(self._L.qm_batch_upload_af(self._h, int(v), _p(a) if a.shape[0] else _p(np.zeros(1, np.float32))))
+
+    def af_profile(self, window=1024, n_pos_bins=256, n_af_bins=20, stream=None):
+        """qm_batch_af_profile: enqueue the AF x position pass of the finished batch"""
+        self._ck(self._L.qm_batch_af_profile(self._h, int(window), int(n_pos_bins), int(n_af_bins), C.c_void_p(stream) if stream else None))
+        self._af_shape = (int(n_af_bins), int(n_pos_bins))
+
+    def af_profile_counts(self):
+        """qm_batch_get_af_profile: (grid [n_vcf][2][n_af_bins][n_pos_bins], extra [n_vcf][2][QM_AFP_EXTRA]) uint64; class 0 = TP,
+        1 = FP; extra columns QM_AFP_NO_AF, QM_AFP_OUTSIDE, QM_AFP_N_GRID"""
+        nA, nP = getattr(self, "_af_shape", (1, 1))
+        grid = np.zeros((self.n_vcf, 2, nA, nP), np.uint64)
+        extra = np.zeros((self.n_vcf, 2, _lib.QM_AFP_EXTRA), np.uint64)
+        self._ck(self._L.qm_batch_get_af_profile(self._h, _p(grid), _p(extra)))
+        return grid, extra
 
     # -- the truth-side view (DESIGN.md 4.8) -------------------------------------
     def truth_hits(self, stream=None):

@@ -44,6 +44,9 @@ class Job:
     fn_out: str = None        # where the missed-variant list goes (extract_many(fn=True) derives it)
     group: str = None         # label of the job's group (1 to 5 jobs of one truth file): stats gain truth_regions / fp_regions
     missed_out: str = None    # where the group's missed-by-all list goes (any member may carry it)
+    # the allele-frequency profile
+    profile: tuple = None     # (window, n_pos_bins, n_af_bins): stats gain af_grid / af_extra (the same for every profiled job of a call)
+    points_out: str = None    # where the job's Position / Frequency / type table goes
 
 
 def _paths(job):
@@ -85,7 +88,7 @@ def _alleles_default():
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None, fn=False, groups=None):
+                 genomes=None, fn=False, groups=None, profile=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -99,7 +102,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     fn=True: every mixed-sample job also gets fn/<x>.fn.vcf (Job.fn_out), the rows of its truth file no kept record carries.
     groups: lists of job indices (1 to 5 mixed-sample jobs of one truth file each; default: the jobs' Job.group labels): the
     members' stats gain truth_regions / fp_regions (quasimodo_amd.truthside.venn_counts), members in job order.  Over several
-    GPUs a group must sit on one rank (WorkflowError otherwise)."""
+    GPUs a group must sit on one rank (WorkflowError otherwise).
+    profile: {"want": [0/1 per job], "window": 1024, "n_pos_bins": 256, "n_af_bins": 20, "points": [path or None per job]}
+    (default: the jobs' Job.profile / Job.points_out): the wanted jobs get stats["af_grid"] ([2][n_af_bins][n_pos_bins]: TP, FP
+    SNVs by allele frequency and position) and stats["af_extra"] ([2][3]: no AF, outside, in the grid; quasimodo_amd.afprofile),
+    and their points files are written.  Combines with genomes; not with fn / groups (ValueError)."""
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
     if genomes is not None:
@@ -107,6 +114,19 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             raise ValueError("genomes: %d entries for %d jobs" % (len(genomes), len(jobs)))
         for j, g in zip(jobs, genomes):
             j.genome = g
+    if profile is not None:
+        want = list(profile["want"])
+        pts = list(profile.get("points") or [None] * len(jobs))
+        if len(want) != len(jobs) or len(pts) != len(jobs):
+            raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(want), len(pts), len(jobs)))
+        par = (int(profile.get("window", 1024)), int(profile.get("n_pos_bins", 256)), int(profile.get("n_af_bins", 20)))
+        for j, w, pt in zip(jobs, want, pts):
+            j.profile = par if w else None
+            j.points_out = pt if w else None
+    if any(j.profile for j in jobs) and (fn or groups is not None or any(j.fn_out or j.group is not None for j in jobs)):
+        raise ValueError("the truth-side view (fn / groups) and profile in one call are not supported")
+    if len({j.profile for j in jobs if j.profile}) > 1:
+        raise ValueError("profile: the profiled jobs of one call share one window and one pair of bin counts")
     if groups is not None:
         from .truthside import MAX_GROUP
         for k, g in enumerate(groups):
@@ -141,7 +161,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        need = not all(pure) or any(j.genome for j in jobs)
+        need = not all(pure) or any(j.genome or j.profile for j in jobs)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     ts = None
@@ -182,8 +202,15 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                     if j.genome and j.genome not in loaded:
                         loaded[j.genome] = engine.genome_load(read_fasta(j.genome))
                 gids = [loaded[j.genome] if j.genome else -1 for j in jobs]
+            prof = None
+            if any(j.profile for j in jobs):
+                par = next(j.profile for j in jobs if j.profile)
+                prof = {"want": [1 if j.profile else 0 for j in jobs], "window": par[0], "n_pos_bins": par[1], "n_af_bins": par[2],
+                        "points": [j.points_out if j.profile else None for j in jobs]}
+                for path in [x for x in prof["points"] if x]:
+                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof)
             extract_many.last_phases = phases
             # where the VCFs found out of order went (bucket paths / radix sort: a silent fall onto the slow path shows here)
             extract_many.last_paths = {k: v - before[k] for k, v in engine.path_stats_total().items()}

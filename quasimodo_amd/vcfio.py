@@ -56,6 +56,16 @@ class ScannedVcf:
             raise QmvtError(rc, "qm_vcf_hostpath failed")
         return dict(decided=int(out[0]), selected=int(out[1]), device_nokey_keys=int(out[2]), tp_r=int(out[3]), fp_r=int(out[4]))
 
+    def scan_af(self):
+        """qm_vcf_scan_af: the allele frequency of every record as rule mutationcontext reads INFO: float32
+        [n_records] (NaN = none), and (records with a value, records with fewer than 8 fields)"""
+        af = np.zeros(max(self.n_records, 1), np.float32)
+        info = np.zeros(2, np.int64)
+        rc = _lib.lib().qm_vcf_scan_af(self.text, len(self.text), self.n_lines, _p(self.line_off), _p(self.line_kind), _p(af), _p(info))
+        if rc < 0:
+            raise QmvtError(rc, "qm_vcf_scan_af failed")
+        return af[:self.n_records], (int(info[0]), int(info[1]))
+
     @property
     def header_kept(self):
         """'#' lines that pass the A2 filter: (all, those fgrep selects)"""

@@ -153,7 +153,7 @@ def hcmv_rank_post(engine, jobs, indices, args):
 
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
-                         _same_device=False, mutation_context=None, truth_side=False):
+                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -164,8 +164,22 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     final_tables/{mix}.{caller}.mutationcontext.tsv is written for every caller and every mix that has samples.
     truth_side: the truth set's side of the join: callers/{caller}/fn/{sample}.{ref}.{caller}.fn.vcf for every
     mixed sample, nucmer/{sample}.missed_by_all.vcf over the Venn callers (rules/vis_eval_vcf.smk:2, those of the run) and
-    final_tables/caller_snp_venn.tsv."""
+    final_tables/caller_snp_venn.tsv.
+    snp_profile: True or {"window", "n_pos_bins", "n_af_bins"} (the rule's first output): the profile pass runs
+    behind the classification; final_tables/{mix}.{caller}.snp.profile.tsv and ...snp.profile.afsweep.tsv are written for every
+    caller and mix (`-1-0` left out, `-0-1` as FP only) and callers/{caller}/profile/{sample}.{ref}.{caller}.points.tsv for
+    every profiled sample.  Combines with mutation_context, not with truth_side."""
     callers = list(callers or SNPCALLERS)
+    prof = None
+    if snp_profile:
+        from .afprofile import DEFAULTS
+        if truth_side:
+            raise WorkflowError("--snp-profile and --truth-side cannot be combined: the truth-side view runs in a call of its own.")
+        opts = dict(DEFAULTS)
+        opts.update({k: int(v) for k, v in (snp_profile.items() if isinstance(snp_profile, dict) else ()) if v is not None})
+        prof = (opts["window"], opts["n_pos_bins"], opts["n_af_bins"])
+        if not (1 <= prof[0] < (1 << 28) and prof[1] >= 1 and prof[2] >= 1 and prof[1] * prof[2] <= 8192):
+            raise WorkflowError("snp profile: window %d, %d x %d bins (1 <= window < 2^28, at most 8192 cells)" % (prof[0], prof[2], prof[1]))
     data_dir = ensure_bundle(data_dir)
     results = os.path.join(outpath.rstrip("/"), "results")
     snp_dir = os.path.join(results, "snp")
@@ -194,6 +208,10 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             for mix in mixes:
                 for c in callers:
                     print("mutationcontext\t%s\t%s" % (mix, c))
+        if prof is not None:
+            for mix in mixes:
+                for c in callers:
+                    print("snp_profile\t%s\t%s" % (mix, c))
         if truth_side:
             from .truthside import venn_callers
             for s, c, src in plan:
@@ -219,6 +237,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         shutil.copyfile(src, dst)
         jobs.append(Job(dst, os.path.join(snp_dir, "nucmer", "%s.maskrepeat.variants.vcf" % s[:2]), "hcmv", d, c,
                         genome=mutation_context.get(s[:2]) if mutation_context is not None and not s.endswith("-1-0") else None))
+        if prof is not None and not s.endswith("-1-0"):
+            jobs[-1].profile = prof
+            jobs[-1].points_out = os.path.join(d, "profile", os.path.basename(src)[:-4] + ".points.tsv")
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -256,6 +277,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         _write_snp_rocs(meta, jobs, snp_dir)
         if mutation_context is not None:
             _write_mutation_context(meta, jobs, tables, callers, mixes)
+        if prof is not None:
+            _write_snp_profile(meta, jobs, tables, callers, mixes, prof[0])
         if truth_side:
             _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
         if mixed and len(cmp_callers) >= 2:
@@ -280,6 +303,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         _write_snp_rocs(meta, jobs, snp_dir)
         if mutation_context is not None:
             _write_mutation_context(meta, jobs, os.path.join(results, "final_tables"), callers, mixes)
+        if prof is not None:
+            _write_snp_profile(meta, jobs, os.path.join(results, "final_tables"), callers, mixes, prof[0])
         if truth_side:
             _write_caller_snp_venn(meta, jobs, os.path.join(results, "final_tables"), callers, mixed)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
@@ -323,6 +348,18 @@ def _write_mutation_context(meta, jobs, tables, callers, mixes):
             rows = {s: j.stats["motifs"] for (cc, s), j in zip(meta, jobs) if cc == c and s[:2] == mix and not s.endswith("-1-0")}
             if rows:
                 write_mutation_context(os.path.join(tables, "%s.%s.mutationcontext.tsv" % (mix, c)), study_columns(rows))
+
+
+def _write_snp_profile(meta, jobs, tables, callers, mixes, window):
+    """the numbers behind {mix}.{caller}.snp.profile.pdf (varPlot of scripts/mutation_context_profile.R): two tables per mix and caller"""
+    from .afprofile import sample_rows, write_af_sweep, write_profile_grid
+    for mix in mixes:
+        for c in callers:
+            st = {s: j.stats for (cc, s), j in zip(meta, jobs) if cc == c and s[:2] == mix and not s.endswith("-1-0")}
+            if st:
+                rows = sample_rows(st)
+                write_profile_grid(os.path.join(tables, "%s.%s.snp.profile.tsv" % (mix, c)), rows, window=window)
+                write_af_sweep(os.path.join(tables, "%s.%s.snp.profile.afsweep.tsv" % (mix, c)), rows)
 
 
 def _write_snp_rocs(meta, jobs, snp_dir):

@@ -80,10 +80,17 @@ def _fail(e):
               help="Also write final_tables/{mix}.{caller}.mutationcontext.tsv (96-motif spectra of kept, TP and FP SNVs).")
 @click.option("--truth-side", "truth_side", is_flag=True, default=False,
               help="Also write the missed-variant lists (callers/*/fn/*.fn.vcf, nucmer/*.missed_by_all.vcf) and final_tables/caller_snp_venn.tsv.")
+@click.option("--snp-profile", "snp_profile", is_flag=True, default=False,
+              help="Also write final_tables/{mix}.{caller}.snp.profile.tsv and ...afsweep.tsv (TP / FP SNVs by allele frequency and position) "
+                   "and callers/*/profile/*.points.tsv.  Not together with --truth-side.")
+@click.option("--profile-window", type=int, default=1024, show_default=True, help="--snp-profile: positions per position bin.")
+@click.option("--profile-pos-bins", type=int, default=256, show_default=True, help="--snp-profile: position bins.")
+@click.option("--profile-af-bins", type=int, default=20, show_default=True, help="--snp-profile: allele-frequency bins (times position bins: at most 8192).")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
-         mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False):
+         mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
+         profile_pos_bins=256, profile_af_bins=20):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -105,7 +112,9 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
         # data/snp is unpacked from data/snp.tar.gz when it is not there yet (rules/load_config.smk:28-31)
         workflow.run_hcmv_variantcall.last_result = None
         jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None,
-                                             mutation_context=genomes, truth_side=truth_side)
+                                             mutation_context=genomes, truth_side=truth_side,
+                                             snp_profile=dict(window=profile_window, n_pos_bins=profile_pos_bins, n_af_bins=profile_af_bins)
+                                             if snp_profile else None)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
