@@ -275,6 +275,40 @@ int qm_batch_upload_af(qm_batch* b, int vcf, const float* af);
 int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bins, int32_t n_af_bins, void* stream);
 int qm_batch_get_af_profile(qm_batch* b, uint64_t* grid /*[n_vcf][2][n_af_bins][n_pos_bins]*/,
                             uint64_t* extra /*[n_vcf][2][QM_AFP_EXTRA]*/);
+/* ---- counts per genome region: BED strata ---------------------------------------------------------------
+ * A strata set is 1 .. QM_STRATA_MAX strata; stratum s is the union of the BED intervals start[offsets[s] .. offsets[s + 1]) /
+ * end[...] (0-based, half-open: the interval holds the 1-based POS values p with start < p <= end; intervals may overlap or
+ * touch, strata may overlap each other).  There is no contig column: only POS decides membership, as everywhere in the engine.
+ * qm_strata_load flattens the set into sorted breakpoints b[0] = INT32_MIN < b[1] < ... < b[m - 1] with masks M[i] (bit s =
+ * stratum s) valid on [b[i], b[i + 1]), the last segment running to INT32_MAX, equal neighbours merged:
+ * mask(p) = M[upper_bound(b, p) - 1] for every int32 p.  QM_E_INVAL: n_strata outside 1 .. QM_STRATA_MAX, start < 0,
+ * end <= start (end > 2^31 - 1 cannot be said in int32: the text readers refuse it); QM_E_LIMIT: m > QM_STRATA_MAX_SEGMENTS.
+ * Ids are stable; a released slot is reused by a later load; a released id is QM_E_INVAL everywhere.
+ * qm_strata_info: info[0] = n_strata, info[1] = m.  qm_strata_segments: the flattened table, m entries each.
+ * qm_batch_strata: asynchronous on `stream` (NULL = the context's own); `what` = QM_STRATA_RECORDS, QM_STRATA_TRUTH or both.
+ *   Records: one streaming pass over the finished batch in input order.  Counted: every record with its kept bit (the
+ *   population of QM_S_NPASS, indels of an allele-extended batch included); TP by the TP mask.  rec[v][S + 2][3] = kept, TP and
+ *   FP lines; rows 0 .. S - 1 the strata, row S `outside` (mask 0), row S + 1 `nokey`: a counted record with QM_F_NOKEY goes
+ *   there only (its pos is not consulted), every other one to each stratum of mask(pos), or to `outside`.
+ *   Truth: tru[v][S + 1][2], rows the strata then `outside`; column 0 = the distinct keys of v's truth set in the row, by the
+ *   key's position; column 1 = those with their bit in v's hit bitmap (FN = column 0 - column 1).  Needs a
+ *   qm_batch_truth_hits behind the latest run (so: single-base batches only), QM_E_STATE otherwise.
+ *   QM_E_STATE unless the latest qm_batch_run was finished.  The outputs are allocated on the first call; may be repeated with
+ *   another strata set.
+ * qm_batch_get_strata: waits for the latest qm_batch_strata, then copies (either pointer may be NULL); QM_E_STATE if the batch
+ * ran since or the half that is asked for was not made. */
+#define QM_STRATA_MAX 32
+#define QM_STRATA_LDS_SEGMENTS 4096      /* tables up to here are looked up in LDS, larger ones in global memory */
+#define QM_STRATA_MAX_SEGMENTS (1 << 22)
+#define QM_STRATA_RECORDS 1u
+#define QM_STRATA_TRUTH 2u
+int qm_strata_load(qm_ctx* ctx, int n_strata, const int64_t* offsets /*[n_strata+1]*/, const int32_t* start, const int32_t* end,
+                   int* strata_id);
+int qm_strata_info(qm_ctx* ctx, int strata_id, int64_t* info /*[2]: n_strata, n_segments*/);
+int qm_strata_segments(qm_ctx* ctx, int strata_id, int32_t* breakpoints, uint32_t* masks);
+int qm_strata_release(qm_ctx* ctx, int strata_id);
+int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* stream);
+int qm_batch_get_strata(qm_batch* b, uint64_t* rec /*[n_vcf][S+2][3] or NULL*/, uint64_t* tru /*[n_vcf][S+1][2] or NULL*/);
 /* ---- the truth-side view ------------------------------------------------------------------------------
  * The sets behind scripts/caller_performance_compare.R:110-119,510-549 (`Genome` against the callers' distinct single-base
  * keys) seen from the truth set: which truth keys a VCF's kept records hit, which records carry a key of the truth set, and,
@@ -567,6 +601,22 @@ typedef struct qm_profile_args {
 int qm_extract_files_profile(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                              qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                              void* global_dev, const int32_t* genome_id, uint64_t* motifs, const qm_profile_args* profile);
+
+/* qm_extract_files_ex plus the counts per stratum over its batch.  Jobs with want[j] != 0 get their rows:
+ * rec[j][S + 2][3] and tru[j][S + 1][2] of qm_batch_get_strata, S the size of strata set `strata_id`; the others get zero rows.
+ * Single-base mode: truth hits and both halves run behind the batch's finish; QM_BATCH_ALLELES: the record side only (tru stays
+ * zero).  Wanted pure-strain jobs join the batch against an empty truth set, as in qm_extract_files_motifs: everything kept is
+ * FP, their tru rows are zero.  The VCF outputs, stats and roc are those of qm_extract_files_ex. */
+typedef struct qm_strata_args {
+  int32_t strata_id;
+  int32_t reserved;
+  const uint8_t* want;            /* [n_jobs] 0/1 */
+  uint64_t* rec;                  /* [n_jobs][S + 2][3] */
+  uint64_t* tru;                  /* [n_jobs][S + 1][2] */
+} qm_strata_args;
+int qm_extract_files_strata(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                            qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                            void* global_dev, const qm_strata_args* strata);
 
 /* `bgzip -c` (the *.vcf.gz outputs the same rules declare, rules/vis_eval_vcf.smk:29,36 ...): BGZF = gzip members of at
  * most 64 KiB with a 'BC' extra field + the EOF member; zcat and tabix / htslib read it.  level -1 = zlib's default (6,

@@ -25,6 +25,11 @@ QM_AFP_OUTSIDE = 1
 QM_AFP_N_GRID = 2
 QM_AFP_EXTRA = 3
 QM_AFP_MAX_CELLS = 8192
+QM_STRATA_MAX = 32
+QM_STRATA_LDS_SEGMENTS = 4096
+QM_STRATA_MAX_SEGMENTS = 1 << 22
+QM_STRATA_RECORDS = 1
+QM_STRATA_TRUTH = 2
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -42,6 +47,8 @@ EXPORTS = (
     "qm_genome_load", "qm_genome_release", "qm_batch_motifs", "qm_batch_get_motifs", "qm_extract_files_motifs",
     "qm_batch_truth_hits", "qm_batch_get_truth_hits", "qm_batch_get_intruth_mask", "qm_batch_truth_regions", "qm_extract_files_truthside",
     "qm_vcf_scan_af", "qm_batch_upload_af", "qm_batch_af_profile", "qm_batch_get_af_profile", "qm_extract_files_profile",
+    "qm_strata_load", "qm_strata_info", "qm_strata_segments", "qm_strata_release", "qm_batch_strata", "qm_batch_get_strata",
+    "qm_extract_files_strata",
 )
 
 
@@ -74,6 +81,11 @@ class ProfileArgs(C.Structure):
                 ("grid", C.c_void_p), ("extra", C.c_void_p), ("points_out", C.POINTER(C.c_char_p))]
 
 
+class StrataArgs(C.Structure):
+    """include/qmvt.h qm_strata_args"""
+    _fields_ = [("strata_id", C.c_int32), ("reserved", C.c_int32), ("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p)]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -94,7 +106,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -267,6 +279,14 @@ def lib():
     L.qm_batch_get_af_profile.argtypes = [vp, vp, vp]
     L.qm_extract_files_profile.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                            vp, vp, C.POINTER(ProfileArgs)]
+    L.qm_strata_load.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32)]
+    L.qm_strata_info.argtypes = [vp, i32, vp]
+    L.qm_strata_segments.argtypes = [vp, i32, vp, vp]
+    L.qm_strata_release.argtypes = [vp, i32]
+    L.qm_batch_strata.argtypes = [vp, i32, C.c_uint, vp]
+    L.qm_batch_get_strata.argtypes = [vp, vp, vp]
+    L.qm_extract_files_strata.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                          C.POINTER(StrataArgs)]
     _lib = L
     return L
 

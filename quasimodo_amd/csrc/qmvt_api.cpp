@@ -25,6 +25,7 @@
 #include "qmvt_motif.h"
 #include "qmvt_afprofile.h"
 #include "qmvt_truthside.h"
+#include "qmvt_strata.h"
 
 using namespace qm;
 
@@ -78,6 +79,18 @@ struct Genome {
   bool released = false;
 };
 
+// a strata set of qm_strata_load: the flattened segment table on both sides, and, for tables too large for LDS,
+// the coarse index over the int32 positions.  Slots follow the rules of genomes.
+struct Strata {
+  std::vector<int32_t> bp;
+  std::vector<uint32_t> masks;
+  int32_t* d_bp = nullptr;
+  uint32_t* d_masks = nullptr;
+  int32_t* d_cidx = nullptr;
+  int32_t shift = 0, n_strata = 0;
+  bool released = false;
+};
+
 struct qm_ctx {
   int dev = 0;
   hipStream_t stream = nullptr;
@@ -87,6 +100,7 @@ struct qm_ctx {
   int d_truths_cap = 0;
   int64_t path_total[QM_N_PATH_STATS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // qm_path_stats_total: every finish of every batch of this context
   std::vector<Genome> genomes;
+  std::vector<Strata> strata;
 };
 
 template <typename T>
@@ -178,6 +192,7 @@ extern "C" void qm_destroy(qm_ctx* c) {
   }
   (void)hipFree(c->d_truths);
   for (auto& g : c->genomes) (void)hipFree(g.d_words);
+  for (auto& t : c->strata) { (void)hipFree(t.d_bp); (void)hipFree(t.d_masks); (void)hipFree(t.d_cidx); }
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->aux) (void)hipStreamDestroy(c->aux);
   delete c;
@@ -346,6 +361,125 @@ extern "C" int qm_genome_release(qm_ctx* c, int genome_id) {
   g.d_words = nullptr;
   g.len = 0;
   g.released = true;
+  return QM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// strata sets
+// ---------------------------------------------------------------------------
+extern "C" int qm_strata_load(qm_ctx* c, int n_strata, const int64_t* offsets, const int32_t* start, const int32_t* end, int* strata_id) {
+  if (!c || !offsets || !strata_id) return fail(QM_E_INVAL, "qm_strata_load: bad arguments");
+  if (n_strata < 1 || n_strata > QM_STRATA_MAX) return fail(QM_E_INVAL, "qm_strata_load: %d strata (1 to %d)", n_strata, QM_STRATA_MAX);
+  if (offsets[0] != 0) return fail(QM_E_INVAL, "qm_strata_load: offsets[0] must be 0");
+  for (int s = 0; s < n_strata; ++s)
+    if (offsets[s + 1] < offsets[s]) return fail(QM_E_INVAL, "qm_strata_load: offsets step backwards at stratum %d", s);
+  if (offsets[n_strata] > 0 && (!start || !end)) return fail(QM_E_INVAL, "qm_strata_load: NULL intervals");
+  // per stratum: the union of its intervals as closed 1-based runs [start + 1, end]; every run toggles its bit at its first
+  // position and behind its last (a run that ends at INT32_MAX is never closed)
+  std::vector<std::pair<int64_t, uint32_t>> tog;
+  std::vector<std::pair<int32_t, int32_t>> iv;
+  for (int s = 0; s < n_strata; ++s) {
+    iv.clear();
+    for (int64_t i = offsets[s]; i < offsets[s + 1]; ++i) {
+      if (start[i] < 0 || end[i] <= start[i])
+        return fail(QM_E_INVAL, "qm_strata_load: stratum %d, interval %lld: (%d, %d) (need 0 <= start < end)", s, (long long)(i - offsets[s]), start[i], end[i]);
+      iv.emplace_back(start[i], end[i]);
+    }
+    std::sort(iv.begin(), iv.end());
+    for (size_t i = 0; i < iv.size();) {
+      const int32_t a = iv[i].first;
+      int32_t e = iv[i].second;
+      size_t k = i + 1;
+      while (k < iv.size() && iv[k].first <= e) { e = std::max(e, iv[k].second); ++k; }   // overlapping or touching
+      tog.emplace_back((int64_t)a + 1, 1u << s);
+      tog.emplace_back((int64_t)e + 1, 1u << s);
+      i = k;
+    }
+  }
+  std::sort(tog.begin(), tog.end());
+  Strata t;
+  t.n_strata = n_strata;
+  t.bp.push_back(INT32_MIN);
+  t.masks.push_back(0u);
+  uint32_t cur = 0u;
+  for (size_t i = 0; i < tog.size();) {
+    const int64_t p = tog[i].first;
+    for (; i < tog.size() && tog[i].first == p; ++i) cur ^= tog[i].second;
+    if (p > (int64_t)INT32_MAX) break;
+    if (cur == t.masks.back()) continue;
+    if ((int64_t)t.bp.size() >= (int64_t)QM_STRATA_MAX_SEGMENTS)
+      return fail(QM_E_LIMIT, "qm_strata_load: more than %d segments", QM_STRATA_MAX_SEGMENTS);
+    t.bp.push_back((int32_t)p);
+    t.masks.push_back(cur);
+  }
+  const size_t m = t.bp.size();
+  HIPCHK(hipSetDevice(c->dev));
+  std::vector<int32_t> cidx;
+  if (m > (size_t)QM_STRATA_LDS_SEGMENTS) {
+    // cells of 1 << shift positions from INT32_MIN: about 16 per segment (the positions of a genome fill 1/16 of int32), 2^16 .. 2^22
+    int lg = 0;
+    while (((size_t)1 << lg) < m) ++lg;
+    lg = std::min(22, std::max(16, lg + 4));
+    t.shift = 32 - lg;
+    const int64_t ncell = (int64_t)1 << lg;
+    cidx.resize((size_t)ncell + 1);
+    size_t i = 0;
+    for (int64_t cell = 0; cell < ncell; ++cell) {
+      const int64_t first = (int64_t)INT32_MIN + (cell << t.shift);
+      while (i + 1 < m && (int64_t)t.bp[i + 1] <= first) ++i;
+      cidx[(size_t)cell] = (int32_t)i;
+    }
+    cidx[(size_t)ncell] = (int32_t)(m - 1);
+  }
+  int rc = dalloc(&t.d_bp, m);
+  if (rc == QM_OK) rc = dalloc(&t.d_masks, m);
+  if (rc == QM_OK && !cidx.empty()) rc = dalloc(&t.d_cidx, cidx.size());
+  hipError_t e = hipSuccess;
+  if (rc == QM_OK) {
+    e = hipMemcpy(t.d_bp, t.bp.data(), m * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t.d_masks, t.masks.data(), m * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !cidx.empty()) e = hipMemcpy(t.d_cidx, cidx.data(), cidx.size() * 4, hipMemcpyHostToDevice);
+  }
+  if (rc != QM_OK || e != hipSuccess) {
+    (void)hipFree(t.d_bp); (void)hipFree(t.d_masks); (void)hipFree(t.d_cidx);
+    return rc != QM_OK ? rc : fail(QM_E_HIP, "qm_strata_load: hipMemcpy: %s", hipGetErrorString(e));
+  }
+  int slot = -1;
+  for (size_t i = 0; i < c->strata.size(); ++i) if (c->strata[i].released) { slot = (int)i; break; }
+  if (slot >= 0) c->strata[(size_t)slot] = std::move(t);
+  else { c->strata.push_back(std::move(t)); slot = (int)c->strata.size() - 1; }
+  *strata_id = slot;
+  return QM_OK;
+}
+
+static const Strata* strata_live(qm_ctx* c, int id) {
+  return (c && id >= 0 && id < (int)c->strata.size() && !c->strata[(size_t)id].released) ? &c->strata[(size_t)id] : nullptr;
+}
+
+extern "C" int qm_strata_info(qm_ctx* c, int strata_id, int64_t* info) {
+  const Strata* t = strata_live(c, strata_id);
+  if (!t || !info) return fail(QM_E_INVAL, "qm_strata_info: no live strata set %d", strata_id);
+  info[0] = t->n_strata;
+  info[1] = (int64_t)t->bp.size();
+  return QM_OK;
+}
+
+extern "C" int qm_strata_segments(qm_ctx* c, int strata_id, int32_t* breakpoints, uint32_t* masks) {
+  const Strata* t = strata_live(c, strata_id);
+  if (!t || !breakpoints || !masks) return fail(QM_E_INVAL, "qm_strata_segments: no live strata set %d", strata_id);
+  memcpy(breakpoints, t->bp.data(), t->bp.size() * 4);
+  memcpy(masks, t->masks.data(), t->masks.size() * 4);
+  return QM_OK;
+}
+
+extern "C" int qm_strata_release(qm_ctx* c, int strata_id) {
+  if (!strata_live(c, strata_id)) return fail(QM_E_INVAL, "qm_strata_release: no live strata set %d", strata_id);
+  HIPCHK(hipSetDevice(c->dev));
+  HIPCHK(hipDeviceSynchronize());   // a pass may still read it on a stream of the caller's
+  Strata& t = c->strata[(size_t)strata_id];
+  (void)hipFree(t.d_bp); (void)hipFree(t.d_masks); (void)hipFree(t.d_cidx);
+  t = Strata();
+  t.released = true;
   return QM_OK;
 }
 
@@ -603,6 +737,14 @@ struct qm_batch {
   bool hit_off_uploaded = false, intruth_cleared = false, hits_enqueued = false;
   hipEvent_t ev_truth = nullptr;
   bool hits_valid = false;            // qm_batch_truth_hits was called behind the latest run
+  // qm_batch_strata (lazy): [n_vcf][S + 2][2] kept / TP lines, [n_vcf][S + 1][2] truth keys / hit ones, the bit
+  // planes of every distinct truth set one behind the other, the per-VCF rows of k_strata_truth; ev_strata says when the pass is done
+  DevBuf<uint64_t> d_srec, d_stru;
+  DevBuf<uint32_t> d_splanes;
+  DevBuf<StrataTruthRow> d_srows;
+  hipEvent_t ev_strata = nullptr;
+  int32_t strata_S = 0;               // strata of the latest qm_batch_strata
+  unsigned strata_made = 0;           // QM_STRATA_* halves the latest qm_batch_strata made behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -626,6 +768,7 @@ static void batch_free(qm_batch* b) {
   if (b->ev_motif) (void)hipEventDestroy(b->ev_motif);
   if (b->ev_truth) (void)hipEventDestroy(b->ev_truth);
   if (b->ev_afp) (void)hipEventDestroy(b->ev_afp);
+  if (b->ev_strata) (void)hipEventDestroy(b->ev_strata);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -952,6 +1095,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->motifs_valid = false;
   b->afp_valid = false;
   b->hits_valid = false;
+  b->strata_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -2136,6 +2280,105 @@ extern "C" int qm_batch_get_af_profile(qm_batch* b, uint64_t* grid, uint64_t* ex
   HIPCHK(hipEventSynchronize(b->ev_afp));
   HIPCHK(hipMemcpy(grid, b->d_afgrid, (size_t)b->n_vcf * 2 * (size_t)b->afp_cells * 8, hipMemcpyDeviceToHost));
   if (extra) HIPCHK(hipMemcpy(extra, b->d_afextra, (size_t)b->n_vcf * 2 * AFP_EXTRA * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+// the counts per stratum of the finished batch
+extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_strata");
+  qm_ctx* c = b->ctx;
+  const Strata* t = strata_live(c, strata_id);
+  if (!t) return fail(QM_E_INVAL, "qm_batch_strata: no live strata set %d", strata_id);
+  if (!what || (what & ~(QM_STRATA_RECORDS | QM_STRATA_TRUTH))) return fail(QM_E_INVAL, "qm_batch_strata: what = %u", what);
+  if (what & QM_STRATA_TRUTH) {
+    if (b->ext) return fail(QM_E_STATE, "qm_batch_strata: allele-extended batches have no truth-side bitmaps (QM_STRATA_RECORDS only)");
+    if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_strata: QM_STRATA_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    for (const auto& tg : b->truth_gens)
+      if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
+        return fail(QM_E_STATE, "qm_batch_strata: truth set %d was released after the batch was created", tg.first);
+  }
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const size_t nv = (size_t)b->n_vcf;
+  const int S = t->n_strata;
+  if (!b->ev_strata) HIPCHK(hipEventCreateWithFlags(&b->ev_strata, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(b->ev_strata));   // the previous pass has read its rows and left the outputs
+  b->strata_made = 0;
+  StrataTable tab;
+  tab.bp = t->d_bp; tab.masks = t->d_masks; tab.cidx = t->d_cidx;
+  tab.m = (int32_t)t->bp.size(); tab.shift = t->shift; tab.n_strata = S; tab.pad = 0;
+  if (what & QM_STRATA_RECORDS) {
+    const size_t words = nv * (size_t)(S + 2) * 2;
+    const int rc = b->d_srec.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
+    if (rc != QM_OK) return rc;
+    HIPCHK(hipMemsetAsync(b->d_srec, 0, words * 8, st));
+    StrataRecParams P;
+    P.spans = b->d_spans; P.pos = b->pos; P.flags = b->flags;
+    P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+    P.out = b->d_srec; P.tab = tab;
+    P.n_spans = (int32_t)b->L.spans.size();
+    launch_strata_records(P, st);
+    HIPCHK(hipGetLastError());
+  }
+  if (what & QM_STRATA_TRUTH) {
+    // the planes of every distinct truth set of the batch, one behind the other (T' as the hit bitmaps were sized)
+    std::vector<int64_t> plane_off(c->truths.size(), -1);
+    int64_t total = 0, max_words = 0;
+    for (size_t v = 0; v < nv; ++v) {
+      const size_t tid = (size_t)b->L.vcfs[v].truth;
+      if (plane_off[tid] >= 0) continue;
+      const int64_t w = (b->h_hit_tn[v] + 31) / 32;
+      plane_off[tid] = total;
+      total += (int64_t)(S + 1) * w;
+      max_words = std::max(max_words, w);
+    }
+    const size_t words = nv * (size_t)(S + 1) * 2;
+    int rc = b->d_splanes.grow(std::max<int64_t>(total, 1), &b->dev_bytes);
+    if (rc == QM_OK) rc = b->d_srows.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+    if (rc == QM_OK) rc = b->d_stru.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
+    if (rc != QM_OK) return rc;
+    std::vector<StrataTruthRow> rows(nv);
+    std::vector<uint8_t> done(c->truths.size(), 0);
+    HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+    for (size_t v = 0; v < nv; ++v) {
+      const size_t tid = (size_t)b->L.vcfs[v].truth;
+      const int64_t tn = b->h_hit_tn[v];
+      rows[v].planes = b->d_splanes + plane_off[tid];
+      rows[v].hits = b->d_hits + b->h_hit_off[v];
+      rows[v].words = (tn + 31) / 32;
+      if (!done[tid]) {
+        done[tid] = 1;
+        launch_strata_planes(tab, c->truths[tid].d_keys, tn, b->d_splanes + plane_off[tid], st);
+      }
+    }
+    HIPCHK(hipGetLastError());
+    if (nv) HIPCHK(hipMemcpy(b->d_srows, rows.data(), nv * sizeof(StrataTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
+    HIPCHK(hipMemsetAsync(b->d_stru, 0, words * 8, st));
+    launch_strata_truth(b->d_srows, (int)nv, max_words, S, reinterpret_cast<unsigned long long*>(b->d_stru.p), st);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipEventRecord(b->ev_strata, st));
+  b->strata_S = S;
+  b->strata_made = what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_strata(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_strata: NULL batch");
+  if (!b->strata_made) return fail(QM_E_STATE, "qm_batch_get_strata: no qm_batch_strata behind the latest run");
+  if ((rec && !(b->strata_made & QM_STRATA_RECORDS)) || (tru && !(b->strata_made & QM_STRATA_TRUTH)))
+    return fail(QM_E_STATE, "qm_batch_get_strata: the latest qm_batch_strata did not make the %s side", rec && !(b->strata_made & QM_STRATA_RECORDS) ? "record" : "truth");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_strata));
+  const size_t nv = (size_t)b->n_vcf, S = (size_t)b->strata_S;
+  if (rec && nv) {
+    std::vector<uint64_t> kt(nv * (S + 2) * 2);
+    HIPCHK(hipMemcpy(kt.data(), b->d_srec, kt.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nv * (S + 2); ++i) {   // FP lines = kept - TP
+      rec[3 * i] = kt[2 * i];
+      rec[3 * i + 1] = kt[2 * i + 1];
+      rec[3 * i + 2] = kt[2 * i] - kt[2 * i + 1];
+    }
+  }
+  if (tru && nv) HIPCHK(hipMemcpy(tru, b->d_stru, nv * (S + 1) * 2 * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 // the truth-side view of the finished batch

@@ -88,6 +88,35 @@ class Engine:
     def genome_release(self, gid):
         check(self._L.qm_genome_release(self._h, int(gid)), self._h)
 
+    # -- strata sets (counts per genome region) -------------------
+    def strata_load(self, strata):
+        """strata: list of (name, starts, ends) BED intervals (quasimodo_amd.strata); returns the set's id"""
+        from .strata import check as check_strata
+        st = check_strata(strata)
+        offs = np.zeros(len(st) + 1, np.int64)
+        offs[1:] = np.cumsum([s.shape[0] for _, s, _ in st])
+        start = _c(np.concatenate([s for _, s, _ in st] + [np.zeros(1, np.int64)]), np.int32)   # (never an empty buffer)
+        end = _c(np.concatenate([e for _, _, e in st] + [np.zeros(1, np.int64)]), np.int32)
+        sid = C.c_int(-1)
+        check(self._L.qm_strata_load(self._h, len(st), _p(offs), _p(start), _p(end), C.byref(sid)), self._h)
+        return sid.value
+
+    def strata_info(self, sid):
+        """(strata, segments of the flattened table)"""
+        info = np.zeros(2, np.int64)
+        check(self._L.qm_strata_info(self._h, int(sid), _p(info)), self._h)
+        return int(info[0]), int(info[1])
+
+    def strata_segments(self, sid):
+        """the flattened table as the library built it: (breakpoints int32 [m], masks uint32 [m]); strata.flatten restates it"""
+        m = self.strata_info(sid)[1]
+        b, k = np.zeros(m, np.int32), np.zeros(m, np.uint32)
+        check(self._L.qm_strata_segments(self._h, int(sid), _p(b), _p(k)), self._h)
+        return b, k
+
+    def strata_release(self, sid):
+        check(self._L.qm_strata_release(self._h, int(sid)), self._h)
+
     # -- one-shot ---------------------------------------------------------------
     def classify_batch(self, columns, truth_ids, n_bins=256, alleles=False):
         """columns: list of (pos, ref, alt, qual, flags) per VCF.  Returns (per-VCF result dicts,
@@ -151,7 +180,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None):
+                      truthside=None, profile=None, strata=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -164,10 +193,15 @@ class Engine:
         profile: {"want": [0/1 per job], "window": 1024, "n_pos_bins": 256, "n_af_bins": 20, "points": [path or None per job]} --
         qm_extract_files_profile (combines with genomes, not with truthside): wanted rows gain `af_grid`
         ([2][n_af_bins][n_pos_bins] uint64: TP, FP) and `af_extra` ([2][QM_AFP_EXTRA]); the points files are written.
+        strata: {"id": strata_load id, "want": [0/1 per job]} -- qm_extract_files_strata (combines with none of the
+        above): wanted rows gain `strata_rec` ([S + 2][3] uint64: kept, TP, FP lines per stratum, outside, nokey) and `strata_tru`
+        ([S + 1][2]: truth keys, hit ones; None in the allele-extended mode).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         import os
         if profile is not None and truthside is not None:
             raise ValueError("truthside and profile in one call are not supported")
+        if strata is not None and (profile is not None or truthside is not None or (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
+            raise ValueError("strata does not combine with genomes, truthside or profile in one call")
         n = len(file_jobs)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
@@ -186,7 +220,17 @@ class Engine:
                 _p(slots), int(n_slots), C.c_void_p(global_dev) if global_dev else None)
         regs = None
         afg = None
-        if profile is not None:
+        srec = None
+        if strata is not None:
+            swant = _c([int(bool(w)) for w in strata["want"]] or [0], np.uint8)
+            if n and swant.shape[0] != n:
+                raise ValueError("strata: %d want entries for %d jobs" % (len(strata["want"]), n))
+            S = self.strata_info(strata["id"])[0]
+            srec = np.zeros((max(n, 1), S + 2, 3), np.uint64)
+            stru = np.zeros((max(n, 1), S + 1, 2), np.uint64)
+            sa = _lib.StrataArgs(int(strata["id"]), 0, _p(swant), _p(srec), _p(stru))
+            check(self._L.qm_extract_files_strata(*args, C.byref(sa)), self._h)
+        elif profile is not None:
             want = _c([int(bool(w)) for w in profile["want"]] or [0], np.uint8)
             pts = list(profile.get("points") or [None] * n)
             if (n and want.shape[0] != n) or len(pts) != n:
@@ -233,6 +277,9 @@ class Engine:
             if afg is not None and want[k]:
                 r["af_grid"] = afg[k].copy()
                 r["af_extra"] = afx[k].copy()
+            if srec is not None and swant[k]:
+                r["strata_rec"] = srec[k].copy()
+                r["strata_tru"] = None if alleles else stru[k].copy()
             if regs is not None and grp[k] >= 0:
                 r["truth_regions"] = regs[grp[k]].astype(np.int64)
                 r["fp_regions"] = fregs[grp[k]].copy()
@@ -400,6 +447,22 @@ class Batch:
         extra = np.zeros((self.n_vcf, 2, _lib.QM_AFP_EXTRA), np.uint64)
         self._ck(self._L.qm_batch_get_af_profile(self._h, _p(grid), _p(extra)))
         return grid, extra
+
+    # -- counts per genome region ---------------------------------
+    def strata(self, strata_id, truth=False, stream=None):
+        """qm_batch_strata: enqueue the record side of the finished batch; truth=True: the truth side too (needs truth_hits)"""
+        what = _lib.QM_STRATA_RECORDS | (_lib.QM_STRATA_TRUTH if truth else 0)
+        self._ck(self._L.qm_batch_strata(self._h, int(strata_id), what, C.c_void_p(stream) if stream else None))
+        self._strata = (self.engine.strata_info(strata_id)[0], bool(truth))
+
+    def strata_counts(self):
+        """qm_batch_get_strata: (rec [n_vcf][S + 2][3] uint64 -- kept, TP, FP lines; rows the strata, outside, nokey --,
+        tru [n_vcf][S + 1][2] -- truth keys, hit ones; rows the strata, outside -- or None when the truth side was not made)"""
+        S, truth = getattr(self, "_strata", (1, False))
+        rec = np.zeros((self.n_vcf, S + 2, 3), np.uint64)
+        tru = np.zeros((self.n_vcf, S + 1, 2), np.uint64) if truth else None
+        self._ck(self._L.qm_batch_get_strata(self._h, _p(rec), _p(tru)))
+        return rec, tru
 
     # -- the truth-side view (DESIGN.md 4.8) -------------------------------------
     def truth_hits(self, stream=None):

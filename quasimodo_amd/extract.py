@@ -47,6 +47,8 @@ class Job:
     # the allele-frequency profile
     profile: tuple = None     # (window, n_pos_bins, n_af_bins): stats gain af_grid / af_extra (the same for every profiled job of a call)
     points_out: str = None    # where the job's Position / Frequency / type table goes
+    # counts per genome region
+    strata: tuple = None      # ((name, starts, ends), ...): stats gain strata_rec / strata_tru (the same set for every such job of a call)
 
 
 def _paths(job):
@@ -88,7 +90,7 @@ def _alleles_default():
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None, fn=False, groups=None, profile=None):
+                 genomes=None, fn=False, groups=None, profile=None, strata=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -106,7 +108,22 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     profile: {"want": [0/1 per job], "window": 1024, "n_pos_bins": 256, "n_af_bins": 20, "points": [path or None per job]}
     (default: the jobs' Job.profile / Job.points_out): the wanted jobs get stats["af_grid"] ([2][n_af_bins][n_pos_bins]: TP, FP
     SNVs by allele frequency and position) and stats["af_extra"] ([2][3]: no AF, outside, in the grid; quasimodo_amd.afprofile),
-    and their points files are written.  Combines with genomes; not with fn / groups (ValueError)."""
+    and their points files are written.  Combines with genomes; not with fn / groups (ValueError).
+    strata: a list of (name, starts, ends) BED strata (quasimodo_amd.strata; default: the jobs' Job.strata): every job gets
+    stats["strata_rec"] ([S + 2][3]: kept, TP, FP lines per stratum, then outside, nokey) and stats["strata_tru"] ([S + 1][2]:
+    truth keys and hit ones per stratum, then outside; None in the allele-extended mode; zero for pure-strain samples).  Combines
+    with none of genomes, fn, groups, profile (ValueError)."""
+    if strata is not None:
+        from .strata import freeze
+        frozen = freeze(strata)
+        for j in jobs:
+            j.strata = frozen
+    if any(j.strata for j in jobs):
+        if genomes is not None or fn or groups is not None or profile is not None or any(
+                j.genome or j.fn_out or j.group is not None or j.profile for j in jobs):
+            raise ValueError("strata does not combine with genomes, fn, groups or profile in one call")
+        if len({j.strata for j in jobs if j.strata}) > 1:
+            raise ValueError("strata: the stratified jobs of one call share one strata set")
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
     if genomes is not None:
@@ -161,9 +178,10 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        need = not all(pure) or any(j.genome or j.profile for j in jobs)
+        need = not all(pure) or any(j.genome or j.profile or j.strata for j in jobs)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
+    sid = None
     ts = None
     if any((j.fn_out or j.group is not None) and not p for j, p in zip(jobs, pure)):
         from .truthside import MAX_GROUP
@@ -209,8 +227,12 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                         "points": [j.points_out if j.profile else None for j in jobs]}
                 for path in [x for x in prof["points"] if x]:
                     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            strat = None
+            if any(j.strata for j in jobs):
+                sid = engine.strata_load(next(j.strata for j in jobs if j.strata))
+                strat = {"id": sid, "want": [1 if j.strata else 0 for j in jobs]}
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat)
             extract_many.last_phases = phases
             # where the VCFs found out of order went (bucket paths / radix sort: a silent fall onto the slow path shows here)
             extract_many.last_paths = {k: v - before[k] for k, v in engine.path_stats_total().items()}
@@ -218,6 +240,8 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         if engine is not None:
             for gid in loaded.values():
                 engine.genome_release(gid)
+            if sid is not None:
+                engine.strata_release(sid)
         if own and engine is not None:
             engine.close()
     for job, p, r in zip(jobs, pure, rows):

@@ -153,7 +153,7 @@ def hcmv_rank_post(engine, jobs, indices, args):
 
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
-                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None):
+                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -168,8 +168,19 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     snp_profile: True or {"window", "n_pos_bins", "n_af_bins"} (the rule's first output): the profile pass runs
     behind the classification; final_tables/{mix}.{caller}.snp.profile.tsv and ...snp.profile.afsweep.tsv are written for every
     caller and mix (`-1-0` left out, `-0-1` as FP only) and callers/{caller}/profile/{sample}.{ref}.{caller}.points.tsv for
-    every profiled sample.  Combines with mutation_context, not with truth_side."""
+    every profiled sample.  Combines with mutation_context, not with truth_side.
+    strata: a list of (name, starts, ends) BED strata (quasimodo_amd.strata): the counts per stratum are taken
+    behind the classification and final_tables/caller_performance_strata.tsv is written (per caller x sample one row per
+    stratum, then outside, then nokey).  Combines with none of the three above."""
     callers = list(callers or SNPCALLERS)
+    if strata is not None:
+        from .strata import freeze
+        if mutation_context is not None or truth_side or snp_profile:
+            raise WorkflowError("--strata cannot be combined with --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
+        try:
+            strata = freeze(strata)
+        except ValueError as e:
+            raise WorkflowError("strata: %s" % e) from None
     prof = None
     if snp_profile:
         from .afprofile import DEFAULTS
@@ -212,6 +223,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             for mix in mixes:
                 for c in callers:
                     print("snp_profile\t%s\t%s" % (mix, c))
+        if strata is not None:
+            print("caller_performance_strata\t%s" % ",".join(s[0] for s in strata))
         if truth_side:
             from .truthside import venn_callers
             for s, c, src in plan:
@@ -240,6 +253,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if prof is not None and not s.endswith("-1-0"):
             jobs[-1].profile = prof
             jobs[-1].points_out = os.path.join(d, "profile", os.path.basename(src)[:-4] + ".points.tsv")
+        jobs[-1].strata = strata
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -279,6 +293,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_mutation_context(meta, jobs, tables, callers, mixes)
         if prof is not None:
             _write_snp_profile(meta, jobs, tables, callers, mixes, prof[0])
+        if strata is not None:
+            _write_strata(meta, jobs, tables, strata)
         if truth_side:
             _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
         if mixed and len(cmp_callers) >= 2:
@@ -305,6 +321,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_mutation_context(meta, jobs, os.path.join(results, "final_tables"), callers, mixes)
         if prof is not None:
             _write_snp_profile(meta, jobs, os.path.join(results, "final_tables"), callers, mixes, prof[0])
+        if strata is not None:
+            _write_strata(meta, jobs, os.path.join(results, "final_tables"), strata)
         if truth_side:
             _write_caller_snp_venn(meta, jobs, os.path.join(results, "final_tables"), callers, mixed)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
@@ -338,6 +356,29 @@ def _write_caller_snp_venn(meta, jobs, tables, callers, mixed):
         n = len(vc)
         per[s] = (reorder_regions(st["truth_regions"][:1 << n], have, vc), reorder_regions(st["fp_regions"][:1 << n], have, vc))
     write_caller_snp_venn(os.path.join(tables, "caller_snp_venn.tsv"), per, vc)
+
+
+def _strata_genomediff(jobs, strata):
+    """stats["strata_genomediff"] of every mixed-sample job: its truth file's rows per stratum as R counts them (one read per file)"""
+    from .strata import truth_rows
+    seen = {}
+    for j in jobs:
+        if not j.stats.get("pure_strain"):
+            key = (j.snp_file, j.mode)
+            if key not in seen:
+                seen[key] = truth_rows(j.snp_file, j.mode, strata)
+            j.stats["strata_genomediff"] = seen[key]
+
+
+def _write_strata(meta, jobs, tables, strata):
+    """final_tables/caller_performance_strata.tsv: the rows of caller_performance.tsv per stratum"""
+    from .strata import write_performance_strata
+    names = [s[0] for s in strata]
+    for (c, s), j in zip(meta, jobs):
+        if "strata_rec" not in j.stats:
+            raise WorkflowError("%s / %s: no counts per stratum came back" % (c, s))
+    _strata_genomediff(jobs, strata)
+    write_performance_strata(os.path.join(tables, "caller_performance_strata.tsv"), [(c, s, names, j.stats) for (c, s), j in zip(meta, jobs)])
 
 
 def _write_mutation_context(meta, jobs, tables, callers, mixes):
@@ -411,12 +452,22 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
 
 
 def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
-                truth_side=False):
+                truth_side=False, strata=None):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
-    final_tables/caller_snp_venn.tsv is written, more are told so and get their FN files only."""
+    final_tables/caller_snp_venn.tsv is written, more are told so and get their FN files only.
+    strata: a list of (name, starts, ends) BED strata: final_tables/snpcall_benchmark_strata.txt is written; not
+    together with truth_side."""
     from .truthside import MAX_GROUP
+    if strata is not None:
+        from .strata import freeze
+        if truth_side:
+            raise WorkflowError("--strata cannot be combined with --truth-side: it runs in a call of its own.")
+        try:
+            strata = freeze(strata)
+        except ValueError as e:
+            raise WorkflowError("strata: %s" % e) from None
     results = os.path.join(outpath.rstrip("/"), "results")
     call_dir = os.path.join(results, "snp", "callers")
     labels = list(labels) if labels else [os.path.splitext(os.path.basename(v))[0] for v in vcfs]
@@ -434,7 +485,7 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     if not os.path.exists(snps_file) or os.path.getsize(snps_file) == 0:
         raise WorkflowError("No difference between two genomes!")       # custom_snp_benchmark.R:19-21
     os.makedirs(os.path.join(call_dir, "fp"), exist_ok=True)
-    jobs = [Job(v, snps_file, "custom", call_dir, lab) for lab, v in zip(labels, vcfs)]
+    jobs = [Job(v, snps_file, "custom", call_dir, lab, strata=strata) for lab, v in zip(labels, vcfs)]
     grouped = truth_side and len(labels) <= MAX_GROUP and not any(is_pure_strain(v) for v in vcfs)
     if truth_side:
         from .extract import _paths, fn_path
@@ -458,6 +509,11 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     _flag_truth_rows(jobs)
     write_snpcall_benchmark(os.path.join(results, "final_tables", "snpcall_benchmark.txt"),
                             [(lab, j.stats) for lab, j in zip(labels, jobs)])
+    if strata is not None:
+        from .strata import write_performance_strata
+        _strata_genomediff(jobs, strata)
+        write_performance_strata(os.path.join(results, "final_tables", "snpcall_benchmark_strata.txt"),
+                                 [(lab, None, [s[0] for s in strata], j.stats) for lab, j in zip(labels, jobs)], custom=True)
     if grouped:
         from .truthside import write_caller_snp_venn
         n = len(labels)

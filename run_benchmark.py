@@ -71,6 +71,18 @@ def _fail(e):
     raise RuntimeError(e)
 
 
+def _read_strata(files, by_name):
+    """--strata / --strata-by-name -> a list of (name, starts, ends), or None when neither is given"""
+    if not files and not by_name:
+        return None
+    if files and by_name:
+        raise ValueError("--strata and --strata-by-name cannot be combined")
+    from quasimodo_amd.strata import read_bed, read_bed_by_name
+    if by_name:
+        return read_bed_by_name(os.path.join(cd, by_name))
+    return [read_bed(os.path.join(cd, f)) for f in files]
+
+
 @cli.command(help="Benchmarking for HCMV dataset")
 @common_options
 @click.option("-e", "--evaluation", required=True, type=click.Choice(["all", "variantcall", "assembly"]), help="The evaluation to run.")
@@ -86,11 +98,16 @@ def _fail(e):
 @click.option("--profile-window", type=int, default=1024, show_default=True, help="--snp-profile: positions per position bin.")
 @click.option("--profile-pos-bins", type=int, default=256, show_default=True, help="--snp-profile: position bins.")
 @click.option("--profile-af-bins", type=int, default=20, show_default=True, help="--snp-profile: allele-frequency bins (times position bins: at most 8192).")
+@click.option("--strata", "strata", type=click.Path(), multiple=True,
+              help="BED file (repeatable, one stratum per file, named by its stem): also write final_tables/caller_performance_strata.tsv "
+                   "(TP, FP and FN counts per region; the chrom column is ignored).")
+@click.option("--strata-by-name", "strata_by_name", type=click.Path(), default=None,
+              help="One BED file, one stratum per distinct value of column 4: the same table.")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
          mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
-         profile_pos_bins=256, profile_af_bins=20):
+         profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -110,11 +127,12 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
         # data/snp is unpacked from data/snp.tar.gz when it is not there yet (rules/load_config.smk:28-31)
+        strata_set = _read_strata(strata, strata_by_name)
         workflow.run_hcmv_variantcall.last_result = None
         jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None,
                                              mutation_context=genomes, truth_side=truth_side,
                                              snp_profile=dict(window=profile_window, n_pos_bins=profile_pos_bins, n_af_bins=profile_af_bins)
-                                             if snp_profile else None)
+                                             if snp_profile else None, strata=strata_set)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -135,8 +153,13 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="YAML with vcfs / refs / outpath / labels for what the command line leaves out (default: config/customize_data.yaml).")
 @click.option("--truth-side", "truth_side", is_flag=True, default=False,
               help="Also write callers/fn/{label}.fn.vcf and, for up to 5 labels, final_tables/caller_snp_venn.tsv.")
+@click.option("--strata", "strata", type=click.Path(), multiple=True,
+              help="BED file (repeatable, one stratum per file, named by its stem): also write final_tables/snpcall_benchmark_strata.txt "
+                   "(TP, FP and FN counts per region; the chrom column is ignored).")
+@click.option("--strata-by-name", "strata_by_name", type=click.Path(), default=None,
+              help="One BED file, one stratum per distinct value of column 4: the same table.")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
-            config=None, json_out=None, truth_side=False):
+            config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None):
     from quasimodo_amd import workflow
     try:
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
@@ -154,7 +177,7 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
             snps = os.path.join(cd, snps)
         workflow.run_vareval.last_result = None
         jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None,
-                                    truth_side=truth_side)
+                                    truth_side=truth_side, strata=_read_strata(strata, strata_by_name))
         if json_out and not dryrun:
             _write_json(json_out, "vareval", jobs, workflow.run_vareval)
     except Exception as e:
