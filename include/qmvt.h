@@ -309,6 +309,38 @@ int qm_strata_segments(qm_ctx* ctx, int strata_id, int32_t* breakpoints, uint32_
 int qm_strata_release(qm_ctx* ctx, int strata_id);
 int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* stream);
 int qm_batch_get_strata(qm_batch* b, uint64_t* rec /*[n_vcf][S+2][3] or NULL*/, uint64_t* tru /*[n_vcf][S+1][2] or NULL*/);
+/* ---- paired block-bootstrap replicates over genome windows ---------------------------------------------
+ * Windows: a position p >= 1 with (p - 1) / window < n_win lies in window (p - 1) / window; every other position is `outside`.
+ * Counts: cnt[v][n_win + 2][4], rows the windows, then `outside`, then `nokey`; column 0 = kept lines (every record with its
+ * kept bit, the population of QM_S_NPASS; a counted record with QM_F_NOKEY goes to `nokey` only, its pos is not consulted),
+ * column 1 = TP lines (those with the TP bit), column 2 = the distinct keys of v's truth set by the key's position (`nokey`: 0),
+ * column 3 = those with their bit in v's hit bitmap.  The definitions of qm_batch_strata: a one-stratum set covering
+ * 1 .. 2^31 - 1 gives the same sums.
+ * Draws: replicate b draws n_win window indices, j = 0 .. n_win - 1, all arithmetic mod 2^64:
+ *   x = seed + 0x9E3779B97F4A7C15 * (b * n_win + j + 1)
+ *   z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ *   idx(b, j) = ((z >> 32) * n_win) >> 32
+ * mult[b][w] = #{j : idx(b, j) = w}.  The draws depend on (seed, b, n_win) only: every VCF, batch, rank and device sees the same.
+ * Replicates: rep[v][b][c] = sum_w mult[b][w] * cnt[v][w][c] + cnt[v][n_win][c] + cnt[v][n_win + 1][c] (`outside` and `nokey`
+ * are not resampled).
+ * qm_batch_boot: the kernels are enqueued on `stream` (NULL = the context's own) and not waited for; with QM_BOOT_TRUTH the
+ *   call itself blocks for one small host-to-device copy (the per-VCF key and bitmap pointers, 24 bytes per VCF), as
+ *   qm_batch_strata does for its rows, and it waits for the previous qm_batch_boot of the batch before it reuses the outputs.
+ *   `what` = QM_BOOT_RECORDS, QM_BOOT_TRUTH or both; the
+ *   columns of a side that was not asked for are zero.  QM_E_INVAL: window < 1, n_win outside 1 .. QM_BOOT_MAX_WINDOWS, n_rep
+ *   outside 0 .. QM_BOOT_MAX_REP (0: counts only), `what` without a side.  QM_E_STATE unless the latest qm_batch_run was
+ *   finished; QM_BOOT_TRUTH needs a qm_batch_truth_hits behind that run (so: single-base batches only), QM_E_STATE otherwise.
+ *   The outputs are allocated on the first call; may be repeated with other parameters.
+ * qm_batch_get_boot: waits for the latest qm_batch_boot, then copies (either pointer may be NULL); QM_E_STATE if the batch ran
+ *   since or none was made.
+ * qm_boot_draws: host only, the same hash: mult[n_rep][n_win]. */
+#define QM_BOOT_MAX_WINDOWS 4096
+#define QM_BOOT_MAX_REP 16384
+#define QM_BOOT_RECORDS 1u
+#define QM_BOOT_TRUTH 2u
+int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t n_rep, uint64_t seed, unsigned what, void* stream);
+int qm_batch_get_boot(qm_batch* b, uint64_t* cnt /*[n_vcf][n_win+2][4] or NULL*/, uint64_t* rep /*[n_vcf][n_rep][4] or NULL*/);
+int qm_boot_draws(uint64_t seed, int32_t n_win, int32_t n_rep, uint16_t* mult /*[n_rep][n_win]*/);
 /* ---- the truth-side view ------------------------------------------------------------------------------
  * The sets behind scripts/caller_performance_compare.R:110-119,510-549 (`Genome` against the callers' distinct single-base
  * keys) seen from the truth set: which truth keys a VCF's kept records hit, which records carry a key of the truth set, and,
@@ -617,6 +649,23 @@ typedef struct qm_strata_args {
 int qm_extract_files_strata(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                             void* global_dev, const qm_strata_args* strata);
+
+/* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
+ * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and
+ * both sides run behind the batch's finish; QM_BATCH_ALLELES: the record side only (columns 2 and 3 stay zero).  Wanted
+ * pure-strain jobs join the batch against an empty truth set, as in qm_extract_files_strata.  The VCF outputs, stats and roc
+ * are those of qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_boot_args {
+  int32_t window, n_win, n_rep;
+  int32_t reserved;
+  uint64_t seed;
+  const uint8_t* want;            /* [n_jobs] 0/1 */
+  uint64_t* cnt;                  /* [n_jobs][n_win + 2][4] */
+  uint64_t* rep;                  /* [n_jobs][n_rep][4] (may be NULL when n_rep = 0) */
+} qm_boot_args;
+int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                          qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                          void* global_dev, const qm_boot_args* boot);
 
 /* `bgzip -c` (the *.vcf.gz outputs the same rules declare, rules/vis_eval_vcf.smk:29,36 ...): BGZF = gzip members of at
  * most 64 KiB with a 'BC' extra field + the EOF member; zcat and tabix / htslib read it.  level -1 = zlib's default (6,

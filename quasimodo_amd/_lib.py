@@ -30,6 +30,10 @@ QM_STRATA_LDS_SEGMENTS = 4096
 QM_STRATA_MAX_SEGMENTS = 1 << 22
 QM_STRATA_RECORDS = 1
 QM_STRATA_TRUTH = 2
+QM_BOOT_MAX_WINDOWS = 4096
+QM_BOOT_MAX_REP = 16384
+QM_BOOT_RECORDS = 1
+QM_BOOT_TRUTH = 2
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -49,6 +53,7 @@ EXPORTS = (
     "qm_vcf_scan_af", "qm_batch_upload_af", "qm_batch_af_profile", "qm_batch_get_af_profile", "qm_extract_files_profile",
     "qm_strata_load", "qm_strata_info", "qm_strata_segments", "qm_strata_release", "qm_batch_strata", "qm_batch_get_strata",
     "qm_extract_files_strata",
+    "qm_batch_boot", "qm_batch_get_boot", "qm_boot_draws", "qm_extract_files_boot",
 )
 
 
@@ -86,6 +91,12 @@ class StrataArgs(C.Structure):
     _fields_ = [("strata_id", C.c_int32), ("reserved", C.c_int32), ("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p)]
 
 
+class BootArgs(C.Structure):
+    """include/qmvt.h qm_boot_args"""
+    _fields_ = [("window", C.c_int32), ("n_win", C.c_int32), ("n_rep", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64),
+                ("want", C.c_void_p), ("cnt", C.c_void_p), ("rep", C.c_void_p)]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -106,7 +117,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -287,6 +298,11 @@ def lib():
     L.qm_batch_get_strata.argtypes = [vp, vp, vp]
     L.qm_extract_files_strata.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                           C.POINTER(StrataArgs)]
+    L.qm_batch_boot.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint, vp]
+    L.qm_batch_get_boot.argtypes = [vp, vp, vp]
+    L.qm_boot_draws.argtypes = [C.c_uint64, C.c_int32, C.c_int32, vp]
+    L.qm_extract_files_boot.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                        C.POINTER(BootArgs)]
     _lib = L
     return L
 

@@ -26,6 +26,7 @@
 #include "qmvt_afprofile.h"
 #include "qmvt_truthside.h"
 #include "qmvt_strata.h"
+#include "qmvt_boot.h"
 
 using namespace qm;
 
@@ -745,6 +746,13 @@ struct qm_batch {
   hipEvent_t ev_strata = nullptr;
   int32_t strata_S = 0;               // strata of the latest qm_batch_strata
   unsigned strata_made = 0;           // QM_STRATA_* halves the latest qm_batch_strata made behind the latest run
+  // qm_batch_boot (lazy): [n_vcf][n_win + 2][4] counts, [n_vcf][n_rep][4] replicates, the per-VCF rows of
+  // k_boot_truth; ev_boot says when the pass is done
+  DevBuf<uint64_t> d_bcnt, d_brep;
+  DevBuf<BootTruthRow> d_brows;
+  hipEvent_t ev_boot = nullptr;
+  int32_t boot_nwin = 0, boot_nrep = 0;   // of the latest qm_batch_boot
+  unsigned boot_made = 0;             // QM_BOOT_* sides the latest qm_batch_boot made behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -769,6 +777,7 @@ static void batch_free(qm_batch* b) {
   if (b->ev_truth) (void)hipEventDestroy(b->ev_truth);
   if (b->ev_afp) (void)hipEventDestroy(b->ev_afp);
   if (b->ev_strata) (void)hipEventDestroy(b->ev_strata);
+  if (b->ev_boot) (void)hipEventDestroy(b->ev_boot);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -1096,6 +1105,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->afp_valid = false;
   b->hits_valid = false;
   b->strata_made = 0;
+  b->boot_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -2379,6 +2389,81 @@ extern "C" int qm_batch_get_strata(qm_batch* b, uint64_t* rec, uint64_t* tru) {
     }
   }
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->d_stru, nv * (S + 1) * 2 * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+// paired block-bootstrap replicates of the finished batch's counts
+extern "C" int qm_boot_draws(uint64_t seed, int32_t n_win, int32_t n_rep, uint16_t* mult) {
+  if (n_win < 1 || n_win > QM_BOOT_MAX_WINDOWS || n_rep < 0 || n_rep > QM_BOOT_MAX_REP || (n_rep > 0 && !mult))
+    return fail(QM_E_INVAL, "qm_boot_draws: n_win = %d (1 to %d), n_rep = %d (0 to %d)", n_win, QM_BOOT_MAX_WINDOWS, n_rep, QM_BOOT_MAX_REP);
+  if (n_rep) memset(mult, 0, sizeof(uint16_t) * (size_t)n_rep * (size_t)n_win);
+  for (int32_t r = 0; r < n_rep; ++r)
+    for (int32_t j = 0; j < n_win; ++j) ++mult[(size_t)r * (size_t)n_win + boot_draw(seed, (uint32_t)r, (uint32_t)j, (uint32_t)n_win)];
+  return QM_OK;
+}
+extern "C" int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t n_rep, uint64_t seed, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_boot");
+  qm_ctx* c = b->ctx;
+  if (window < 1) return fail(QM_E_INVAL, "qm_batch_boot: window = %d (at least 1)", window);
+  if (n_win < 1 || n_win > QM_BOOT_MAX_WINDOWS) return fail(QM_E_INVAL, "qm_batch_boot: n_win = %d (1 to %d)", n_win, QM_BOOT_MAX_WINDOWS);
+  if (n_rep < 0 || n_rep > QM_BOOT_MAX_REP) return fail(QM_E_INVAL, "qm_batch_boot: n_rep = %d (0 to %d)", n_rep, QM_BOOT_MAX_REP);
+  if (!what || (what & ~(QM_BOOT_RECORDS | QM_BOOT_TRUTH))) return fail(QM_E_INVAL, "qm_batch_boot: what = %u", what);
+  if (what & QM_BOOT_TRUTH) {
+    if (b->ext) return fail(QM_E_STATE, "qm_batch_boot: allele-extended batches have no truth-side bitmaps (QM_BOOT_RECORDS only)");
+    if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_boot: QM_BOOT_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    for (const auto& tg : b->truth_gens)
+      if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
+        return fail(QM_E_STATE, "qm_batch_boot: truth set %d was released after the batch was created", tg.first);
+  }
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const size_t nv = (size_t)b->n_vcf;
+  if (!b->ev_boot) HIPCHK(hipEventCreateWithFlags(&b->ev_boot, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(b->ev_boot));   // the previous pass has read its rows and left the outputs
+  b->boot_made = 0;
+  const size_t cw = nv * (size_t)(n_win + 2) * BOOT_COLS, rw = nv * (size_t)n_rep * BOOT_COLS;
+  int rc = b->d_bcnt.grow((int64_t)std::max<size_t>(cw, 1), &b->dev_bytes);
+  if (rc == QM_OK && n_rep) rc = b->d_brep.grow((int64_t)std::max<size_t>(rw, 1), &b->dev_bytes);
+  if (rc == QM_OK && (what & QM_BOOT_TRUTH)) rc = b->d_brows.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  HIPCHK(hipMemsetAsync(b->d_bcnt, 0, cw * 8, st));
+  if (what & QM_BOOT_RECORDS) {
+    BootRecParams P;
+    P.spans = b->d_spans; P.pos = b->pos; P.flags = b->flags;
+    P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+    P.cnt = b->d_bcnt;
+    P.n_spans = (int32_t)b->L.spans.size();
+    P.window = window; P.n_win = n_win; P.div = boot_div(window);
+    launch_boot_records(P, st);
+    HIPCHK(hipGetLastError());
+  }
+  if ((what & QM_BOOT_TRUTH) && nv) {
+    std::vector<BootTruthRow> rows(nv);
+    for (size_t v = 0; v < nv; ++v) {
+      rows[v].keys = c->truths[(size_t)b->L.vcfs[v].truth].d_keys;
+      rows[v].hits = b->d_hits + b->h_hit_off[v];
+      rows[v].n = b->h_hit_tn[v];   // T' as the hit bitmaps were sized
+    }
+    HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(hipMemcpy(b->d_brows, rows.data(), nv * sizeof(BootTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
+    launch_boot_truth(b->d_brows, (int)nv, window, n_win, b->d_bcnt, st);
+    HIPCHK(hipGetLastError());
+  }
+  launch_boot_resample(b->d_bcnt, (int)nv, n_win, n_rep, seed, b->d_brep, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(b->ev_boot, st));
+  b->boot_nwin = n_win;
+  b->boot_nrep = n_rep;
+  b->boot_made = what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_boot(qm_batch* b, uint64_t* cnt, uint64_t* rep) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_boot: NULL batch");
+  if (!b->boot_made) return fail(QM_E_STATE, "qm_batch_get_boot: no qm_batch_boot behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_boot));
+  const size_t nv = (size_t)b->n_vcf;
+  if (cnt && nv) HIPCHK(hipMemcpy(cnt, b->d_bcnt, nv * (size_t)(b->boot_nwin + 2) * BOOT_COLS * 8, hipMemcpyDeviceToHost));
+  if (rep && nv && b->boot_nrep) HIPCHK(hipMemcpy(rep, b->d_brep, nv * (size_t)b->boot_nrep * BOOT_COLS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 // the truth-side view of the finished batch

@@ -270,12 +270,12 @@ extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa);
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba);
 
 extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                    qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
                                    int n_slots, void* global_dev) {
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // rule mutationcontext behind the worker: the motif pass runs on the batch the classification leaves in HBM
@@ -284,7 +284,7 @@ extern "C" int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_jo
                                        int n_slots, void* global_dev, const int32_t* genome_id, uint64_t* motifs_out) {
   if (n_jobs > 0 && (!genome_id || !motifs_out)) return fail(QM_E_INVAL, "qm_extract_files_motifs: NULL genome ids or output");
   if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, nullptr, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, nullptr, nullptr, nullptr);
 }
 
 // both halves of rule mutationcontext behind the worker: the spectra (optional) and the allele-frequency profile
@@ -304,7 +304,7 @@ extern "C" int qm_extract_files_profile(qm_ctx* ctx, int n_jobs, const qm_file_j
     memset(profile->extra, 0, sizeof(uint64_t) * 2 * QM_AFP_EXTRA * (size_t)n_jobs);
   }
   if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, profile, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, profile, nullptr, nullptr);
 }
 
 // the truth-side view behind the worker: missed-variant lists and the caller Venn regions of groups of jobs
@@ -326,7 +326,7 @@ extern "C" int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file
   }
   memset(ts->regions, 0, sizeof(uint64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
   if (ts->fp_regions) memset(ts->fp_regions, 0, sizeof(int64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, ts, nullptr, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, ts, nullptr, nullptr, nullptr);
 }
 
 // the counts per stratum behind the worker
@@ -341,12 +341,27 @@ extern "C" int qm_extract_files_strata(qm_ctx* ctx, int n_jobs, const qm_file_jo
     memset(strata->rec, 0, sizeof(uint64_t) * 3 * (size_t)(info[0] + 2) * (size_t)n_jobs);
     memset(strata->tru, 0, sizeof(uint64_t) * 2 * (size_t)(info[0] + 1) * (size_t)n_jobs);
   }
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, strata);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, strata, nullptr);
+}
+
+// the bootstrap pass behind the worker
+extern "C" int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                     qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                     int n_slots, void* global_dev, const qm_boot_args* boot) {
+  if (!boot || (n_jobs > 0 && (!boot->want || !boot->cnt || (boot->n_rep > 0 && !boot->rep)))) return fail(QM_E_INVAL, "qm_extract_files_boot: NULL arguments");
+  if (boot->window < 1 || boot->n_win < 1 || boot->n_win > QM_BOOT_MAX_WINDOWS || boot->n_rep < 0 || boot->n_rep > QM_BOOT_MAX_REP)
+    return fail(QM_E_INVAL, "qm_extract_files_boot: window = " + std::to_string(boot->window) + " (at least 1), n_win = " + std::to_string(boot->n_win) +
+                                " (1 to " + std::to_string(QM_BOOT_MAX_WINDOWS) + "), n_rep = " + std::to_string(boot->n_rep) + " (0 to " + std::to_string(QM_BOOT_MAX_REP) + ")");
+  if (n_jobs > 0) {
+    memset(boot->cnt, 0, sizeof(uint64_t) * 4 * (size_t)(boot->n_win + 2) * (size_t)n_jobs);
+    if (boot->n_rep) memset(boot->rep, 0, sizeof(uint64_t) * 4 * (size_t)boot->n_rep * (size_t)n_jobs);
+  }
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, boot);
 }
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa) {
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
     return fail(QM_E_INVAL, "qm_extract_files: bad arguments");
   if (global_dev && (n_slots < 1 || (n_jobs && !truth_slot))) return fail(QM_E_INVAL, "qm_extract_files_ex: global_dev needs truth_slot and n_slots >= 1");
@@ -378,7 +393,8 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
   auto has_genome = [&](int j) { return genome_id && genome_id[j] >= 0; };
   auto wants_profile = [&](int j) { return pa && pa->want[j] != 0; };
   auto wants_strata = [&](int j) { return sa && sa->want[j] != 0; };
-  auto in_batch = [&](int j) { return !jobs[j].pure || has_genome(j) || wants_profile(j) || wants_strata(j); };
+  auto wants_boot = [&](int j) { return ba && ba->want[j] != 0; };
+  auto in_batch = [&](int j) { return !jobs[j].pure || has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j); };
   int empty_tid = -1;
 
   // ---- the VCFs go through as ONE batch: stage one (map, count, tokenise, upload) of every VCF, then stage two (engine,
@@ -654,6 +670,23 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
             if (wants_strata(j)) {
               memcpy(sa->rec + (size_t)j * rw, &rec[(size_t)J[(size_t)j].batch_v * rw], sizeof(uint64_t) * rw);
               if (!ext) memcpy(sa->tru + (size_t)j * tw, &tru[(size_t)J[(size_t)j].batch_v * tw], sizeof(uint64_t) * tw);
+            }
+        }
+        if (rc != QM_OK) err = qm_last_error(ctx);
+      }
+      if (rc == QM_OK && ba) {   // the bootstrap pass behind the classification, on the columns, masks and truth keys still in HBM
+        bool any = false;
+        for (int j = 0; j < n_jobs; ++j) any = any || wants_boot(j);
+        if (any) {
+          const size_t cw = 4 * (size_t)(ba->n_win + 2), rw = 4 * (size_t)ba->n_rep;
+          std::vector<uint64_t> cnt(nrec.size() * cw), rep(nrec.size() * rw);
+          if (!ext) rc = qm_batch_truth_hits(batch, nullptr);
+          if (rc == QM_OK) rc = qm_batch_boot(batch, ba->window, ba->n_win, ba->n_rep, ba->seed, ext ? QM_BOOT_RECORDS : (QM_BOOT_RECORDS | QM_BOOT_TRUTH), nullptr);
+          if (rc == QM_OK) rc = qm_batch_get_boot(batch, cnt.data(), rw ? rep.data() : nullptr);
+          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
+            if (wants_boot(j)) {
+              memcpy(ba->cnt + (size_t)j * cw, &cnt[(size_t)J[(size_t)j].batch_v * cw], sizeof(uint64_t) * cw);
+              if (rw) memcpy(ba->rep + (size_t)j * rw, &rep[(size_t)J[(size_t)j].batch_v * rw], sizeof(uint64_t) * rw);
             }
         }
         if (rc != QM_OK) err = qm_last_error(ctx);

@@ -180,7 +180,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None):
+                      truthside=None, profile=None, strata=None, boot=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -196,12 +196,18 @@ class Engine:
         strata: {"id": strata_load id, "want": [0/1 per job]} -- qm_extract_files_strata (combines with none of the
         above): wanted rows gain `strata_rec` ([S + 2][3] uint64: kept, TP, FP lines per stratum, outside, nokey) and `strata_tru`
         ([S + 1][2]: truth keys, hit ones; None in the allele-extended mode).
+        boot: {"want": [0/1 per job], "window": 1024, "n_win": 256, "n_rep": 1000, "seed": 0} -- qm_extract_files_boot (DESIGN.md
+        4.11; combines with none of the above): wanted rows gain `boot_cnt` ([n_win + 2][4] uint64: kept lines, TP lines, truth
+        keys, hit keys per window, then outside, nokey) and `boot_rep` ([n_rep][4], the bootstrap replicates of the four sums).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         import os
         if profile is not None and truthside is not None:
             raise ValueError("truthside and profile in one call are not supported")
         if strata is not None and (profile is not None or truthside is not None or (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
             raise ValueError("strata does not combine with genomes, truthside or profile in one call")
+        if boot is not None and (strata is not None or profile is not None or truthside is not None or
+                                 (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
+            raise ValueError("boot does not combine with genomes, truthside, profile or strata in one call")
         n = len(file_jobs)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
@@ -221,7 +227,19 @@ class Engine:
         regs = None
         afg = None
         srec = None
-        if strata is not None:
+        bcnt = None
+        if boot is not None:
+            bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
+            if n and bwant.shape[0] != n:
+                raise ValueError("boot: %d want entries for %d jobs" % (len(boot["want"]), n))
+            bw, bn, br = int(boot.get("window", 1024)), int(boot.get("n_win", 256)), int(boot.get("n_rep", 1000))
+            if bw < 1 or not 1 <= bn <= _lib.QM_BOOT_MAX_WINDOWS or not 0 <= br <= _lib.QM_BOOT_MAX_REP:
+                raise ValueError("boot: window %d, n_win %d (1 to %d), n_rep %d (0 to %d)" % (bw, bn, _lib.QM_BOOT_MAX_WINDOWS, br, _lib.QM_BOOT_MAX_REP))
+            bcnt = np.zeros((max(n, 1), bn + 2, 4), np.uint64)
+            brep = np.zeros((max(n, 1), max(br, 1), 4), np.uint64)
+            ba = _lib.BootArgs(bw, bn, br, 0, int(boot.get("seed", 0)) & ((1 << 64) - 1), _p(bwant), _p(bcnt), _p(brep))
+            check(self._L.qm_extract_files_boot(*args, C.byref(ba)), self._h)
+        elif strata is not None:
             swant = _c([int(bool(w)) for w in strata["want"]] or [0], np.uint8)
             if n and swant.shape[0] != n:
                 raise ValueError("strata: %d want entries for %d jobs" % (len(strata["want"]), n))
@@ -280,6 +298,9 @@ class Engine:
             if srec is not None and swant[k]:
                 r["strata_rec"] = srec[k].copy()
                 r["strata_tru"] = None if alleles else stru[k].copy()
+            if bcnt is not None and bwant[k]:
+                r["boot_cnt"] = bcnt[k].copy()
+                r["boot_rep"] = brep[k, :br].copy()
             if regs is not None and grp[k] >= 0:
                 r["truth_regions"] = regs[grp[k]].astype(np.int64)
                 r["fp_regions"] = fregs[grp[k]].copy()
@@ -331,6 +352,7 @@ class Batch:
         check(self._L.qm_batch_create_ext(engine._h, self.n_vcf, _p(self.n_records), _p(self.truth_ids), self.n_bins,
                                           _lib.QM_BATCH_ALLELES if alleles else 0, C.byref(h)), engine._h)
         self._h = h
+        self._boot = None   # (n_win, n_rep) of the latest boot() that the library accepted
         engine._batches.add(self)
 
     def close(self):
@@ -463,6 +485,26 @@ class Batch:
         tru = np.zeros((self.n_vcf, S + 1, 2), np.uint64) if truth else None
         self._ck(self._L.qm_batch_get_strata(self._h, _p(rec), _p(tru)))
         return rec, tru
+
+    # -- paired block-bootstrap replicates ------------------------
+    def boot(self, window=1024, n_win=256, n_rep=1000, seed=0, truth=False, stream=None):
+        """qm_batch_boot: enqueue the window counts of the finished batch's record side and n_rep replicates of their sums;
+        truth=True: the truth side too (needs truth_hits)"""
+        what = _lib.QM_BOOT_RECORDS | (_lib.QM_BOOT_TRUTH if truth else 0)
+        self._ck(self._L.qm_batch_boot(self._h, int(window), int(n_win), int(n_rep), int(seed) & ((1 << 64) - 1), what,
+                                       C.c_void_p(stream) if stream else None))
+        self._boot = (int(n_win), int(n_rep))   # (a refused call leaves the library's latest pass, and this, as they were)
+
+    def boot_counts(self):
+        """qm_batch_get_boot: (cnt [n_vcf][n_win + 2][4] uint64 -- kept lines, TP lines, truth keys, hit keys; rows the windows,
+        outside, nokey --, rep [n_vcf][n_rep][4]: the replicates of the four sums)"""
+        if self._boot is None:   # the host arrays are sized by the pass this wrapper enqueued: none, so nothing to copy into
+            raise QmvtError(-6, "boot_counts: no Batch.boot on this batch")
+        n_win, n_rep = self._boot
+        cnt = np.zeros((self.n_vcf, n_win + 2, 4), np.uint64)
+        rep = np.zeros((self.n_vcf, n_rep, 4), np.uint64)
+        self._ck(self._L.qm_batch_get_boot(self._h, _p(cnt), _p(rep) if n_rep and self.n_vcf else None))
+        return cnt, rep
 
     # -- the truth-side view (DESIGN.md 4.8) -------------------------------------
     def truth_hits(self, stream=None):

@@ -49,6 +49,8 @@ class Job:
     points_out: str = None    # where the job's Position / Frequency / type table goes
     # counts per genome region
     strata: tuple = None      # ((name, starts, ends), ...): stats gain strata_rec / strata_tru (the same set for every such job of a call)
+    # paired block-bootstrap replicates
+    boot: tuple = None        # (window, n_win, n_rep, seed): stats gain boot_cnt / boot_rep (the same for every such job of a call)
 
 
 def _paths(job):
@@ -90,7 +92,7 @@ def _alleles_default():
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None, fn=False, groups=None, profile=None, strata=None):
+                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -112,7 +114,23 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     strata: a list of (name, starts, ends) BED strata (quasimodo_amd.strata; default: the jobs' Job.strata): every job gets
     stats["strata_rec"] ([S + 2][3]: kept, TP, FP lines per stratum, then outside, nokey) and stats["strata_tru"] ([S + 1][2]:
     truth keys and hit ones per stratum, then outside; None in the allele-extended mode; zero for pure-strain samples).  Combines
-    with none of genomes, fn, groups, profile (ValueError)."""
+    with none of genomes, fn, groups, profile (ValueError).
+    boot: {"window": 1024, "n_win": 256, "n_rep": 1000, "seed": 0} (quasimodo_amd.bootstrap; default: the jobs' Job.boot): every
+    job gets stats["boot_cnt"] ([n_win + 2][4]: kept lines, TP lines, truth keys, hit keys per window, then outside, nokey),
+    stats["boot_rep"] ([n_rep][4]: the bootstrap replicates of the four sums, the same draws for every job, call, rank and
+    device), stats["boot_params"] and stats["boot_truth"] (False in the allele-extended mode: columns 2 and 3 are zero).
+    Combines with none of genomes, fn, groups, profile, strata (ValueError)."""
+    if boot is not None:
+        from .bootstrap import DEFAULTS
+        par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
+        for j in jobs:
+            j.boot = par
+    if any(j.boot for j in jobs):
+        if genomes is not None or fn or groups is not None or profile is not None or strata is not None or any(
+                j.genome or j.fn_out or j.group is not None or j.profile or j.strata for j in jobs):
+            raise ValueError("boot does not combine with genomes, fn, groups, profile or strata in one call")
+        if len({j.boot for j in jobs if j.boot}) > 1:
+            raise ValueError("boot: the resampled jobs of one call share one window, window count, replicate count and seed")
     if strata is not None:
         from .strata import freeze
         frozen = freeze(strata)
@@ -178,7 +196,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        need = not all(pure) or any(j.genome or j.profile or j.strata for j in jobs)
+        need = not all(pure) or any(j.genome or j.profile or j.strata or j.boot for j in jobs)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
@@ -231,8 +249,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if any(j.strata for j in jobs):
                 sid = engine.strata_load(next(j.strata for j in jobs if j.strata))
                 strat = {"id": sid, "want": [1 if j.strata else 0 for j in jobs]}
+            bt = None
+            if any(j.boot for j in jobs):
+                par = next(j.boot for j in jobs if j.boot)
+                bt = {"want": [1 if j.boot else 0 for j in jobs], "window": par[0], "n_win": par[1], "n_rep": par[2], "seed": par[3]}
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt)
+            if bt is not None:
+                for r in rows:
+                    if "boot_cnt" in r:
+                        r["boot_params"] = {k: bt[k] for k in ("window", "n_win", "n_rep", "seed")}
+                        r["boot_truth"] = not alleles
             extract_many.last_phases = phases
             # where the VCFs found out of order went (bucket paths / radix sort: a silent fall onto the slow path shows here)
             extract_many.last_paths = {k: v - before[k] for k, v in engine.path_stats_total().items()}

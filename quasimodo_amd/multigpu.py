@@ -82,7 +82,7 @@ def default_body(jobs, indices, device, opts):
     dev = torch.device("cuda", device)
     counters = torch.zeros((n_slots, 3, n_bins), dtype=torch.int64, device=dev) if on_gpu else None
     extra = None
-    need_engine = bool(jobs) and (not all(is_pure_strain(j.vcf_file) for j in jobs) or opts.get("post") or any(j.genome or j.profile or j.strata for j in jobs))
+    need_engine = bool(jobs) and (not all(is_pure_strain(j.vcf_file) for j in jobs) or opts.get("post") or any(j.genome or j.profile or j.strata or j.boot for j in jobs))
     eng = Engine(device) if need_engine else None
     try:
         if jobs:
@@ -215,7 +215,7 @@ def extract_many_sharded(jobs, gpus, backend="nccl", body=None, n_bins=256, alle
     timeout = DEFAULT_TIMEOUT if timeout is None else timeout
     with tempfile.TemporaryDirectory(prefix="qmvt_mgpu_") as tmp:
         spec = {"jobs": [dict(vcf_file=j.vcf_file, snp_file=j.snp_file, mode=j.mode, outdir=j.outdir, caller=j.caller, genome=j.genome,
-                              fn_out=j.fn_out, group=j.group, missed_out=j.missed_out, profile=j.profile, points_out=j.points_out, strata=j.strata)
+                              fn_out=j.fn_out, group=j.group, missed_out=j.missed_out, profile=j.profile, points_out=j.points_out, strata=j.strata, boot=j.boot)
                          for j in jobs],
                 "world": gpus, "backend": backend, "body": body, "n_bins": n_bins, "alleles": alleles, "strict": strict,
                 "same_device": same_device, "result": os.path.join(tmp, "result.pkl"), "groups": groups, "post": post,

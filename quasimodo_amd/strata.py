@@ -119,18 +119,11 @@ def row_names(strata):
     return [str(s[0]) for s in strata] + [OUTSIDE, NOKEY]
 
 
-def truth_rows(path, mode, strata):
-    """int64 [S + 1]: the rows of a truth file that R counts as `genomediff`, per stratum and then `outside`, by the row's POS.
-    hcmv: rows whose REF and ALT are each one of A, C, G, T (caller_performance_compare.R:29-55); custom: rows of the show-snps
-    table with neither allele '.' (custom_snp_benchmark.R:23-27).  R counts ROWS, as text: a key on two rows counts twice, and
-    a row the device can hold no key for (`N`, a lower-case base, a POS that is no canonical decimal below 2^28) counts too.
-    Those are the rows by which this differs from the distinct keys of the bitmaps (strata_tru column 0); none of them can be
-    hit, so they are missed variants.  A POS that is no plain decimal number of at most 2^31 - 1 lies in no stratum: `outside`."""
-    table = flatten(strata)
-    S = len(strata)
-    out = np.zeros(S + 1, np.int64)
+def truth_row_positions(path, mode):
+    """(POS of every row of a truth file that R counts as `genomediff` and whose POS is a plain decimal number of at most
+    2^31 - 1, how many counted rows have no such POS).  What truth_rows and bootstrap.truth_row_windows place."""
     ix, iy, iz = (1, 3, 4) if mode == "hcmv" else (0, 1, 2)
-    pos = []
+    pos, unplaced = [], 0
     with open(path, "rb") as fh:
         for ln in fh.read().split(b"\n"):
             if not ln or ln[:1] == b"#":
@@ -146,7 +139,22 @@ def truth_rows(path, mode, strata):
             if p.isdigit() and len(p) <= 10 and int(p) <= INT32_MAX:
                 pos.append(int(p))
             else:
-                out[S] += 1
+                unplaced += 1
+    return pos, unplaced
+
+
+def truth_rows(path, mode, strata):
+    """int64 [S + 1]: the rows of a truth file that R counts as `genomediff`, per stratum and then `outside`, by the row's POS.
+    hcmv: rows whose REF and ALT are each one of A, C, G, T (caller_performance_compare.R:29-55); custom: rows of the show-snps
+    table with neither allele '.' (custom_snp_benchmark.R:23-27).  R counts ROWS, as text: a key on two rows counts twice, and
+    a row the device can hold no key for (`N`, a lower-case base, a POS that is no canonical decimal below 2^28) counts too.
+    Those are the rows by which this differs from the distinct keys of the bitmaps (strata_tru column 0); none of them can be
+    hit, so they are missed variants.  A POS that is no plain decimal number of at most 2^31 - 1 lies in no stratum: `outside`."""
+    table = flatten(strata)
+    S = len(strata)
+    out = np.zeros(S + 1, np.int64)
+    pos, unplaced = truth_row_positions(path, mode)
+    out[S] += unplaced
     m = mask_of(table, np.array(pos, np.int32))
     for s in range(S):
         out[s] += int((((m >> np.uint32(s)) & 1) != 0).sum())

@@ -153,7 +153,7 @@ def hcmv_rank_post(engine, jobs, indices, args):
 
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
-                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None):
+                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -171,8 +171,15 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     every profiled sample.  Combines with mutation_context, not with truth_side.
     strata: a list of (name, starts, ends) BED strata (quasimodo_amd.strata): the counts per stratum are taken
     behind the classification and final_tables/caller_performance_strata.tsv is written (per caller x sample one row per
-    stratum, then outside, then nokey).  Combines with none of the three above."""
+    stratum, then outside, then nokey).  Combines with none of the three above.
+    bootstrap: a replicate count or {"n_rep", "window", "n_win", "seed"} (quasimodo_amd.bootstrap): the window
+    counts and the replicates are taken behind the classification; final_tables/caller_performance_ci.tsv (percentile
+    intervals of Precision, Recall and F1 per caller x sample) and caller_performance_ci_pairs.tsv (the F1 difference of every
+    pair of callers on a mixed sample, over the shared draws) are written.  n_win is raised to cover the truth files' largest
+    POS.  Combines with none of the four above."""
     callers = list(callers or SNPCALLERS)
+    if bootstrap is not None and (strata is not None or mutation_context is not None or truth_side or snp_profile):
+        raise WorkflowError("--bootstrap cannot be combined with --strata, --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
     if strata is not None:
         from .strata import freeze
         if mutation_context is not None or truth_side or snp_profile:
@@ -225,6 +232,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                     print("snp_profile\t%s\t%s" % (mix, c))
         if strata is not None:
             print("caller_performance_strata\t%s" % ",".join(s[0] for s in strata))
+        if bootstrap is not None:
+            print("caller_performance_ci\t%d" % _boot_params(bootstrap, [])[2])
         if truth_side:
             from .truthside import venn_callers
             for s, c, src in plan:
@@ -242,6 +251,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         src = os.path.join(data_dir, "nucmer", "%s.maskrepeat.variants.vcf" % mix)
         if os.path.exists(src):
             shutil.copyfile(src, os.path.join(snp_dir, "nucmer", os.path.basename(src)))
+    boot = None
+    if bootstrap is not None:
+        boot = _boot_params(bootstrap, [(t, "hcmv") for t in sorted(glob.glob(os.path.join(snp_dir, "nucmer", "T?.maskrepeat.variants.vcf")))])
     jobs, meta = [], []
     for s, c, src in plan:                                              # cp_vcf
         d = os.path.join(call_dir, c)
@@ -254,6 +266,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             jobs[-1].profile = prof
             jobs[-1].points_out = os.path.join(d, "profile", os.path.basename(src)[:-4] + ".points.tsv")
         jobs[-1].strata = strata
+        jobs[-1].boot = boot
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -295,6 +308,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_snp_profile(meta, jobs, tables, callers, mixes, prof[0])
         if strata is not None:
             _write_strata(meta, jobs, tables, strata)
+        if boot is not None:
+            _write_bootstrap(meta, jobs, tables)
         if truth_side:
             _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
         if mixed and len(cmp_callers) >= 2:
@@ -323,6 +338,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_snp_profile(meta, jobs, os.path.join(results, "final_tables"), callers, mixes, prof[0])
         if strata is not None:
             _write_strata(meta, jobs, os.path.join(results, "final_tables"), strata)
+        if boot is not None:
+            _write_bootstrap(meta, jobs, os.path.join(results, "final_tables"))
         if truth_side:
             _write_caller_snp_venn(meta, jobs, os.path.join(results, "final_tables"), callers, mixed)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
@@ -379,6 +396,49 @@ def _write_strata(meta, jobs, tables, strata):
             raise WorkflowError("%s / %s: no counts per stratum came back" % (c, s))
     _strata_genomediff(jobs, strata)
     write_performance_strata(os.path.join(tables, "caller_performance_strata.tsv"), [(c, s, names, j.stats) for (c, s), j in zip(meta, jobs)])
+
+
+def _boot_params(bootstrap, truth_files):
+    """(window, n_win, n_rep, seed) of a run: the defaults, what `bootstrap` (a replicate count or a dict) says, and n_win raised
+    to cover the largest POS of truth_files [(path, mode)]; ValueError when that takes more than 4096 windows"""
+    from .bootstrap import DEFAULTS, MAX_REP, truth_max_pos, windows_for
+    opts = dict(DEFAULTS)
+    if isinstance(bootstrap, dict):
+        opts.update({k: int(v) for k, v in bootstrap.items() if v is not None})
+    else:
+        opts["n_rep"] = int(bootstrap)
+    if opts["window"] < 1 or opts["window"] > (1 << 31) - 1:
+        raise ValueError("bootstrap: window %d (1 to 2^31 - 1)" % opts["window"])
+    if not 1 <= opts["n_rep"] <= MAX_REP:
+        raise ValueError("bootstrap: %d replicates (1 to %d)" % (opts["n_rep"], MAX_REP))
+    top = max([truth_max_pos(p, m) for p, m in truth_files] or [0])
+    return (opts["window"], windows_for(top, opts["window"], opts["n_win"]), opts["n_rep"], opts["seed"])
+
+
+def _boot_extra(jobs):
+    """stats["boot_extra"] of every mixed-sample job: its truth file's rows per window as R counts them minus the device's
+    distinct keys there (one read per file)"""
+    from .bootstrap import TRUTH_KEYS, truth_row_windows
+    seen = {}
+    for j in jobs:
+        if not j.stats.get("pure_strain") and j.stats.get("boot_truth", True):
+            prm = j.stats["boot_params"]
+            key = (j.snp_file, j.mode)
+            if key not in seen:
+                seen[key] = truth_row_windows(j.snp_file, j.mode, prm["window"], prm["n_win"])
+            j.stats["boot_extra"] = seen[key] - j.stats["boot_cnt"][:prm["n_win"] + 1, TRUTH_KEYS].astype("int64")
+
+
+def _write_bootstrap(meta, jobs, tables):
+    """final_tables/caller_performance_ci.tsv and caller_performance_ci_pairs.tsv"""
+    from .bootstrap import write_performance_ci, write_performance_ci_pairs
+    for (c, s), j in zip(meta, jobs):
+        if "boot_cnt" not in j.stats:
+            raise WorkflowError("%s / %s: no bootstrap counts came back" % (c, s))
+    _boot_extra(jobs)
+    rows = [(c, s, j.stats) for (c, s), j in zip(meta, jobs)]
+    write_performance_ci(os.path.join(tables, "caller_performance_ci.tsv"), rows)
+    write_performance_ci_pairs(os.path.join(tables, "caller_performance_ci_pairs.tsv"), rows)
 
 
 def _write_mutation_context(meta, jobs, tables, callers, mixes):
@@ -452,14 +512,18 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
 
 
 def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
-                truth_side=False, strata=None):
+                truth_side=False, strata=None, bootstrap=None):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
     final_tables/caller_snp_venn.tsv is written, more are told so and get their FN files only.
     strata: a list of (name, starts, ends) BED strata: final_tables/snpcall_benchmark_strata.txt is written; not
-    together with truth_side."""
+    together with truth_side.
+    bootstrap: a replicate count or {"n_rep", "window", "n_win", "seed"}: final_tables/snpcall_benchmark_ci.txt
+    is written; not together with truth_side or strata."""
     from .truthside import MAX_GROUP
+    if bootstrap is not None and (truth_side or strata is not None):
+        raise WorkflowError("--bootstrap cannot be combined with --truth-side or --strata: it runs in a call of its own.")
     if strata is not None:
         from .strata import freeze
         if truth_side:
@@ -485,7 +549,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     if not os.path.exists(snps_file) or os.path.getsize(snps_file) == 0:
         raise WorkflowError("No difference between two genomes!")       # custom_snp_benchmark.R:19-21
     os.makedirs(os.path.join(call_dir, "fp"), exist_ok=True)
-    jobs = [Job(v, snps_file, "custom", call_dir, lab, strata=strata) for lab, v in zip(labels, vcfs)]
+    boot = _boot_params(bootstrap, [(snps_file, "custom")]) if bootstrap is not None else None
+    jobs = [Job(v, snps_file, "custom", call_dir, lab, strata=strata, boot=boot) for lab, v in zip(labels, vcfs)]
     grouped = truth_side and len(labels) <= MAX_GROUP and not any(is_pure_strain(v) for v in vcfs)
     if truth_side:
         from .extract import _paths, fn_path
@@ -514,6 +579,10 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
         _strata_genomediff(jobs, strata)
         write_performance_strata(os.path.join(results, "final_tables", "snpcall_benchmark_strata.txt"),
                                  [(lab, None, [s[0] for s in strata], j.stats) for lab, j in zip(labels, jobs)], custom=True)
+    if boot is not None:
+        from .bootstrap import write_performance_ci
+        _boot_extra(jobs)
+        write_performance_ci(os.path.join(results, "final_tables", "snpcall_benchmark_ci.txt"), [(lab, None, j.stats) for lab, j in zip(labels, jobs)], custom=True)
     if grouped:
         from .truthside import write_caller_snp_venn
         n = len(labels)

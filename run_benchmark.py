@@ -83,6 +83,11 @@ def _read_strata(files, by_name):
     return [read_bed(os.path.join(cd, f)) for f in files]
 
 
+def _bootstrap_opts(n_rep, window, seed):
+    """--bootstrap / --bootstrap-window / --bootstrap-seed -> what the workflows take, or None without --bootstrap"""
+    return None if n_rep is None else {"n_rep": n_rep, "window": window, "seed": seed}
+
+
 @cli.command(help="Benchmarking for HCMV dataset")
 @common_options
 @click.option("-e", "--evaluation", required=True, type=click.Choice(["all", "variantcall", "assembly"]), help="The evaluation to run.")
@@ -103,11 +108,16 @@ def _read_strata(files, by_name):
                    "(TP, FP and FN counts per region; the chrom column is ignored).")
 @click.option("--strata-by-name", "strata_by_name", type=click.Path(), default=None,
               help="One BED file, one stratum per distinct value of column 4: the same table.")
+@click.option("--bootstrap", "bootstrap", type=int, default=None,
+              help="Replicates of the paired block bootstrap over genome windows: also write final_tables/caller_performance_ci.tsv and caller_performance_ci_pairs.tsv "
+                   "(percentile intervals of precision, recall and F1; the same draws for every VCF).")
+@click.option("--bootstrap-window", "bootstrap_window", type=int, default=1024, show_default=True, help="--bootstrap: positions per window.")
+@click.option("--bootstrap-seed", "bootstrap_seed", type=int, default=0, show_default=True, help="--bootstrap: seed of the draws.")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
          mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
-         profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None):
+         profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -132,7 +142,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
         jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None,
                                              mutation_context=genomes, truth_side=truth_side,
                                              snp_profile=dict(window=profile_window, n_pos_bins=profile_pos_bins, n_af_bins=profile_af_bins)
-                                             if snp_profile else None, strata=strata_set)
+                                             if snp_profile else None, strata=strata_set,
+                                             bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed))
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -158,8 +169,13 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                    "(TP, FP and FN counts per region; the chrom column is ignored).")
 @click.option("--strata-by-name", "strata_by_name", type=click.Path(), default=None,
               help="One BED file, one stratum per distinct value of column 4: the same table.")
+@click.option("--bootstrap", "bootstrap", type=int, default=None,
+              help="Replicates of the paired block bootstrap over genome windows: also write final_tables/snpcall_benchmark_ci.txt "
+                   "(percentile intervals of precision, recall and F1; the same draws for every VCF).")
+@click.option("--bootstrap-window", "bootstrap_window", type=int, default=1024, show_default=True, help="--bootstrap: positions per window.")
+@click.option("--bootstrap-seed", "bootstrap_seed", type=int, default=0, show_default=True, help="--bootstrap: seed of the draws.")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
-            config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None):
+            config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0):
     from quasimodo_amd import workflow
     try:
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
@@ -177,7 +193,8 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
             snps = os.path.join(cd, snps)
         workflow.run_vareval.last_result = None
         jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None,
-                                    truth_side=truth_side, strata=_read_strata(strata, strata_by_name))
+                                    truth_side=truth_side, strata=_read_strata(strata, strata_by_name),
+                                    bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed))
         if json_out and not dryrun:
             _write_json(json_out, "vareval", jobs, workflow.run_vareval)
     except Exception as e:
