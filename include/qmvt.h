@@ -366,6 +366,37 @@ int qm_batch_get_intruth_mask(qm_batch* b, int vcf, uint64_t* mask);
  * Blocking.  QM_E_STATE without a qm_batch_truth_hits behind the latest run. */
 int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids,
                            uint64_t* regions /*[n_groups][QM_TRUTH_REGIONS]*/, uint32_t* union_bits);
+/* ---- k-of-n caller consensus --------------------------------------------------------------------------
+ * For groups of 1 to QM_VOTE_GROUP_MAX VCFs of one truth set (members in the order given; a VCF sits in at most one group, VCFs
+ * outside every group take no part): how many members call every key.  Member i calls key K = pos << 4 | ref << 2 | alt iff one
+ * of its records is kept, has a comparable key (no QM_F_NOKEY) and carries K; the ID column plays no part and a key on several
+ * lines of one member counts once.  mask(K): bit i set iff member i calls K; votes(K) = its popcount.
+ *   tp_votes[g][c], c = 0 .. n: truth keys with exactly c votes (c = 0: missed by all); the row sums to T'.
+ *   fp_votes[g][c], c = 1 .. n: distinct keys outside the truth set with exactly c votes; slot 0 is 0.
+ *   private_tp[g][i], private_fp[g][i]: the keys with votes = 1 that member i calls.
+ *   Slots at and above n + 1 (vote tables) and n (private tables) are 0.
+ *   nokey[g]: kept QM_F_NOKEY records of the group's members; they are skipped.
+ * qm_batch_votes: asynchronous on `stream` (NULL = the context's own) but for small blocking copies of its tables; it waits for
+ *   the previous qm_batch_votes of the batch before it reuses the outputs, which are allocated on the first call.  QM_E_STATE
+ *   unless the latest qm_batch_run was finished and a qm_batch_truth_hits lies behind it (so: single-base batches only).
+ *   QM_E_INVAL: a group of 0 or more than QM_VOTE_GROUP_MAX members, a VCF in two groups (or twice in one), members of
+ *   different truth sets, a VCF id out of range.  May be repeated with other groups.
+ * qm_batch_get_votes: waits for the latest qm_batch_votes, then copies (any pointer may be NULL); QM_E_STATE if the batch ran
+ *   since or none was made.
+ * qm_batch_get_vote_keys: the ascending distinct keys of group `group` outside the truth set and their masks; *n_out = how
+ *   many (keys = masks = NULL: the count alone).  QM_E_INVAL if `capacity` is smaller. */
+#define QM_VOTE_GROUP_MAX 32
+#define QM_VOTE_SLOTS 33
+int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, void* stream);
+int qm_batch_get_votes(qm_batch* b, uint64_t* tp_votes /*[n_groups][QM_VOTE_SLOTS]*/, uint64_t* fp_votes /*[n_groups][QM_VOTE_SLOTS]*/,
+                       uint64_t* private_tp /*[n_groups][QM_VOTE_GROUP_MAX]*/, uint64_t* private_fp /*[n_groups][QM_VOTE_GROUP_MAX]*/,
+                       int64_t* nokey /*[n_groups]*/);
+int qm_batch_get_vote_keys(qm_batch* b, int group, uint32_t* keys, uint32_t* masks, int64_t capacity, int64_t* n_out);
+/* groups of the latest qm_batch_votes (what sizes qm_batch_get_votes' arrays), or QM_E_STATE as qm_batch_get_votes */
+int qm_batch_vote_groups(qm_batch* b);
+/* with qm_batch_set_timing on: milliseconds of the latest qm_batch_votes between HIP events on its stream -- [0] k_vote_truth,
+ * [1] k_vote_keys + k_vote_segs, [2] the four radix passes, [3] k_vote_heads + k_vote_scan + k_vote_runs.  Waits for the pass. */
+int qm_batch_vote_timings(qm_batch* b, float* ms4);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -614,6 +645,31 @@ typedef struct qm_truthside_args {
 int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                                void* global_dev, const qm_truthside_args* ts);
+
+/* qm_extract_files_ex plus the k-of-n consensus over its batch (single-base mode only: QM_E_STATE otherwise).
+ * group[j]: -1 or a group id < n_groups; a group holds 1 to QM_VOTE_GROUP_MAX mixed-sample jobs of one truth file, its members in
+ * job order (anything else: QM_E_INVAL).  Behind the batch's finish the call runs qm_batch_truth_hits and qm_batch_votes; the four
+ * tables are qm_batch_get_votes' rows.  consensus_k[g] (array may be NULL; 0 = no file; above the group's size: QM_E_INVAL) with
+ * consensus_out[g]: the group's consensus VCF at that level -- the '#' lines of the first member's filtered file, then one line
+ * per key that at least k members call, in ascending key order (pos << 4 | ref << 2 | alt; keys inside and outside the truth set
+ * interleaved): the first kept line carrying the key in the lowest-numbered member that calls it, byte for byte.  Atomic (temp
+ * file + rename).  A group member that holds a kept line without a comparable key (QM_F_NOKEY) is refused with QM_E_NONCANON and
+ * a message that names the file and the line, as qm_extract_files_truthside does.  The VCF outputs, stats and roc are those of
+ * qm_extract_files_ex. */
+typedef struct qm_votes_args {
+  const int32_t* group;             /* [n_jobs] */
+  int32_t n_groups;
+  int32_t reserved;
+  uint64_t* tp_votes;               /* [n_groups][QM_VOTE_SLOTS] */
+  uint64_t* fp_votes;               /* [n_groups][QM_VOTE_SLOTS] */
+  uint64_t* private_tp;             /* [n_groups][QM_VOTE_GROUP_MAX] */
+  uint64_t* private_fp;             /* [n_groups][QM_VOTE_GROUP_MAX] */
+  const int32_t* consensus_k;       /* [n_groups] or NULL */
+  const char* const* consensus_out; /* [n_groups] or NULL */
+} qm_votes_args;
+int qm_extract_files_votes(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                           qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                           void* global_dev, const qm_votes_args* votes);
 
 /* qm_extract_files_motifs plus the allele-frequency profile: both halves of rule mutationcontext in one call.
  * genome_id / motifs may be NULL (no spectra).  Jobs with want[j] != 0 have their INFO column scanned (qm_vcf_scan_af) and

@@ -34,6 +34,8 @@ QM_BOOT_MAX_WINDOWS = 4096
 QM_BOOT_MAX_REP = 16384
 QM_BOOT_RECORDS = 1
 QM_BOOT_TRUTH = 2
+QM_VOTE_GROUP_MAX = 32
+QM_VOTE_SLOTS = 33
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -54,6 +56,7 @@ EXPORTS = (
     "qm_strata_load", "qm_strata_info", "qm_strata_segments", "qm_strata_release", "qm_batch_strata", "qm_batch_get_strata",
     "qm_extract_files_strata",
     "qm_batch_boot", "qm_batch_get_boot", "qm_boot_draws", "qm_extract_files_boot",
+    "qm_batch_votes", "qm_batch_get_votes", "qm_batch_get_vote_keys", "qm_batch_vote_groups", "qm_batch_vote_timings", "qm_extract_files_votes",
 )
 
 
@@ -97,6 +100,12 @@ class BootArgs(C.Structure):
                 ("want", C.c_void_p), ("cnt", C.c_void_p), ("rep", C.c_void_p)]
 
 
+class VotesArgs(C.Structure):
+    """include/qmvt.h qm_votes_args"""
+    _fields_ = [("group", C.c_void_p), ("n_groups", C.c_int32), ("reserved", C.c_int32), ("tp_votes", C.c_void_p), ("fp_votes", C.c_void_p),
+                ("private_tp", C.c_void_p), ("private_fp", C.c_void_p), ("consensus_k", C.c_void_p), ("consensus_out", C.POINTER(C.c_char_p))]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -117,7 +126,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -303,6 +312,13 @@ def lib():
     L.qm_boot_draws.argtypes = [C.c_uint64, C.c_int32, C.c_int32, vp]
     L.qm_extract_files_boot.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                         C.POINTER(BootArgs)]
+    L.qm_batch_votes.argtypes = [vp, i32, vp, vp, vp]
+    L.qm_batch_get_votes.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.qm_batch_get_vote_keys.argtypes = [vp, i32, vp, vp, i64, C.POINTER(i64)]
+    L.qm_batch_vote_groups.argtypes = [vp]
+    L.qm_batch_vote_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_extract_files_votes.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                         C.POINTER(VotesArgs)]
     _lib = L
     return L
 

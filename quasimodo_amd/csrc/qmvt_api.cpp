@@ -26,6 +26,7 @@
 #include "qmvt_afprofile.h"
 #include "qmvt_truthside.h"
 #include "qmvt_strata.h"
+#include "qmvt_votes.h"
 #include "qmvt_boot.h"
 
 using namespace qm;
@@ -753,6 +754,20 @@ struct qm_batch {
   hipEvent_t ev_boot = nullptr;
   int32_t boot_nwin = 0, boot_nrep = 0;   // of the latest qm_batch_boot
   unsigned boot_made = 0;             // QM_BOOT_* sides the latest qm_batch_boot made behind the latest run
+  // qm_batch_votes (lazy): the (key, member) pair buffers of the radix sort (the second pair holds the distinct keys
+  // and their masks afterwards), its histograms and tables, the per-group descriptors, cursors, counts and the five output
+  // tables one behind the other; ev_votes says when the pass is done
+  DevBuf<uint32_t> vt_k[2], vt_v[2], vt_hist, vt_thd, vt_cursor;   // vt_cursor: [n_groups] pairs written, then [n_groups] distinct keys
+  DevBuf<SortSeg> vt_segs;
+  DevBuf<int32_t> vt_tile_seg, vt_slot;
+  DevBuf<VoteGroup> vt_groups;
+  DevBuf<uint64_t> vt_out;
+  std::vector<int64_t> vt_koff;       // first pair of every group of the latest qm_batch_votes
+  hipEvent_t ev_votes = nullptr;
+  hipEvent_t ev_vt[5] = {};           // qm_batch_set_timing: around k_vote_truth, k_vote_keys + k_vote_segs, the sort, the run kernels
+  bool vt_timed = false;              // the latest qm_batch_votes recorded them
+  int32_t votes_groups = 0;
+  bool votes_valid = false;           // qm_batch_votes was called behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -778,6 +793,8 @@ static void batch_free(qm_batch* b) {
   if (b->ev_afp) (void)hipEventDestroy(b->ev_afp);
   if (b->ev_strata) (void)hipEventDestroy(b->ev_strata);
   if (b->ev_boot) (void)hipEventDestroy(b->ev_boot);
+  if (b->ev_votes) (void)hipEventDestroy(b->ev_votes);
+  for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -1106,6 +1123,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->hits_valid = false;
   b->strata_made = 0;
   b->boot_made = 0;
+  b->votes_valid = false;
   b->last_global = g;
   return QM_OK;
 }
@@ -2597,6 +2615,185 @@ extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* 
   (void)hipFree(d_groups); (void)hipFree(d_reg); (void)hipFree(d_uni);
   if (rc != QM_OK) return rc;
   if (e != hipSuccess) return fail(QM_E_HIP, "qm_batch_truth_regions: %s", hipGetErrorString(e));
+  return QM_OK;
+}
+// k-of-n consensus over groups of the finished batch's VCFs
+extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, void* stream) {
+  NEED_FINISHED(b, "qm_batch_votes");
+  qm_ctx* c = b->ctx;
+  if (b->ext) return fail(QM_E_STATE, "qm_batch_votes: allele-extended batches have no truth-side bitmaps (single-base batches only)");
+  if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_votes: needs a qm_batch_truth_hits behind the latest run");
+  for (const auto& tg : b->truth_gens)
+    if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
+      return fail(QM_E_STATE, "qm_batch_votes: truth set %d was released after the batch was created", tg.first);
+  if (n_groups < 0 || (n_groups && (!group_offsets || !vcf_ids))) return fail(QM_E_INVAL, "qm_batch_votes: bad arguments");
+  if (n_groups >= (1 << 23)) return fail(QM_E_LIMIT, "qm_batch_votes: %d groups", n_groups);
+  const size_t nv = (size_t)b->n_vcf, ng = (size_t)n_groups;
+  std::vector<int32_t> slot(std::max<size_t>(nv, 1), -1);
+  std::vector<VoteGroup> G(std::max<size_t>(ng, 1));
+  int64_t max_words = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    const int32_t o0 = group_offsets[g], o1 = group_offsets[g + 1];
+    if (o0 < 0 || o1 - o0 < 1 || o1 - o0 > VT_MAX_GROUP)
+      return fail(QM_E_INVAL, "qm_batch_votes: group %d has %d VCFs (1 to %d)", g, o1 - o0, VT_MAX_GROUP);
+    VoteGroup& t = G[(size_t)g];
+    memset(&t, 0, sizeof t);
+    t.n = o1 - o0;
+    int truth = -1;
+    for (int i = 0; i < t.n; ++i) {
+      const int v = vcf_ids[o0 + i];
+      if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_votes: group %d names VCF %d (the batch has %d)", g, v, b->n_vcf);
+      if (slot[(size_t)v] >= 0) return fail(QM_E_INVAL, "qm_batch_votes: VCF %d sits in groups %d and %d (at most one)", v, slot[(size_t)v] >> 8, g);
+      const int tv = b->L.vcfs[(size_t)v].truth;
+      if (i == 0) truth = tv;
+      else if (tv != truth) return fail(QM_E_INVAL, "qm_batch_votes: group %d mixes truth sets %d and %d", g, truth, tv);
+      slot[(size_t)v] = (int32_t)(((uint32_t)g << 8) | (uint32_t)i);
+      t.bits[i] = b->d_hits + b->h_hit_off[(size_t)v];
+      t.words = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
+    }
+    t.tn = b->h_hit_tn[(size_t)vcf_ids[o0]];   // T' as it was when the bitmaps were sized
+    max_words = std::max(max_words, t.words);
+  }
+  HIPCHK(hipSetDevice(c->dev));
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (!b->ev_votes) HIPCHK(hipEventCreateWithFlags(&b->ev_votes, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(b->ev_votes));   // the previous pass has read its tables and left the outputs
+  // a group's segment of the pair buffers holds its members' kept lines: the finished n_pass scalars bound the pairs from above
+  std::vector<int64_t> sc(std::max<size_t>(nv, 1) * QM_N_SCALARS, 0);
+  if (nv) HIPCHK(hipMemcpy(sc.data(), b->scalars, nv * QM_N_SCALARS * 8, hipMemcpyDeviceToHost));
+  std::vector<SortSeg> segs(std::max<size_t>(ng, 1));
+  std::vector<int32_t> tile_seg;
+  int64_t koff = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    SortSeg& s = segs[(size_t)g];
+    memset(&s, 0, sizeof s);
+    for (int32_t o = group_offsets[g]; o < group_offsets[g + 1]; ++o) s.n += std::max<int64_t>(sc[(size_t)vcf_ids[o] * QM_N_SCALARS + QM_S_NPASS], 0);
+    s.koff = koff;
+    s.tile0 = (int32_t)tile_seg.size();
+    s.hoff = (int64_t)s.tile0 * 256;
+    s.ntiles = (int32_t)((s.n + SORT_TILE - 1) / SORT_TILE);
+    koff += (s.n + 63) & ~(int64_t)63;
+    if (koff > 0x7fff0000ll) return fail(QM_E_LIMIT, "qm_batch_votes: the groups' members hold more than 2^31 kept lines");
+    tile_seg.insert(tile_seg.end(), (size_t)s.ntiles, (int32_t)g);
+  }
+  const int64_t nst = (int64_t)tile_seg.size();
+  const size_t out_words = ng * (2 * VT_SLOTS + 2 * VT_MAX_GROUP + 1);
+  int rc = QM_OK;
+  for (int i = 0; i < 2 && rc == QM_OK; ++i) {   // the sort kernels read whole 16-byte pieces
+    rc = b->vt_k[i].grow(koff + 64, &b->dev_bytes);
+    if (rc == QM_OK) rc = b->vt_v[i].grow(koff + 64, &b->dev_bytes);
+  }
+  if (rc == QM_OK) rc = b->vt_hist.grow(std::max<int64_t>(nst * 256, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_thd.grow(std::max<int64_t>(nst * VT_RUN_PER_SORT, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_cursor.grow((int64_t)std::max<size_t>(2 * ng, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_segs.grow((int64_t)std::max<size_t>(ng, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_tile_seg.grow(std::max<int64_t>(nst, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_slot.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_groups.grow((int64_t)std::max<size_t>(ng, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->vt_out.grow((int64_t)std::max<size_t>(out_words, 1), &b->dev_bytes);
+  // (growing keeps what fits: a call refused up to here leaves the previous pass and its outputs as they were, unless an
+  //  array had to be replaced and then could not be)
+  if (rc != QM_OK) { b->votes_valid = false; return rc; }
+  b->votes_valid = false;   // from here on the outputs are rewritten
+  b->vt_koff.assign(ng + 1, 0);
+  for (size_t g = 0; g < ng; ++g) b->vt_koff[g] = segs[g].koff;
+  b->vt_koff[ng] = koff;
+  b->votes_groups = n_groups;
+  if (n_groups == 0) {
+    HIPCHK(hipEventRecord(b->ev_votes, st));
+    b->votes_valid = true;
+    return QM_OK;
+  }
+  // blocking copies: the tables die here
+  HIPCHK(hipMemcpy(b->vt_segs, segs.data(), ng * sizeof(SortSeg), hipMemcpyHostToDevice));
+  if (nst) HIPCHK(hipMemcpy(b->vt_tile_seg, tile_seg.data(), (size_t)nst * 4, hipMemcpyHostToDevice));
+  if (nv) HIPCHK(hipMemcpy(b->vt_slot, slot.data(), nv * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(b->vt_groups, G.data(), ng * sizeof(VoteGroup), hipMemcpyHostToDevice));
+  HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps and the record mask, on whatever stream they were made
+  HIPCHK(hipMemsetAsync(b->vt_out, 0, out_words * 8, st));
+  HIPCHK(hipMemsetAsync(b->vt_cursor, 0, 2 * ng * 4, st));
+  VoteOut O;
+  O.tp = reinterpret_cast<unsigned long long*>(b->vt_out.p);
+  O.fp = O.tp + ng * VT_SLOTS;
+  O.ptp = O.fp + ng * VT_SLOTS;
+  O.pfp = O.ptp + ng * VT_MAX_GROUP;
+  O.nokey = O.pfp + ng * VT_MAX_GROUP;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_vt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->vt_timed = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_vt[0], st));
+  launch_vote_truth(b->vt_groups, n_groups, max_words, O, st);
+  if (T) HIPCHK(hipEventRecord(b->ev_vt[1], st));
+  VoteKeysParams P;
+  P.spans = b->d_spans; P.vcf_slot = b->vt_slot; P.segs = b->vt_segs;
+  P.pos = b->pos; P.anib = b->anib; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_intruth = b->d_intruth;
+  P.cursor = b->vt_cursor; P.keys = b->vt_k[0]; P.vals = b->vt_v[0]; P.nokey = O.nokey;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_vote_keys(P, st);
+  launch_vote_segs(b->vt_segs, b->vt_cursor, n_groups, st);
+  if (T) HIPCHK(hipEventRecord(b->ev_vt[2], st));
+  int cur = 0;
+  for (int shift = 0; shift < 32; shift += 8) {
+    launch_sort_pass(b->vt_segs, b->vt_tile_seg, n_groups, (int)nst, b->vt_k[cur], nullptr, b->vt_v[cur], shift, b->vt_hist, b->vt_k[cur ^ 1], nullptr,
+                     b->vt_v[cur ^ 1], 0, st);
+    cur ^= 1;
+  }
+  if (T) HIPCHK(hipEventRecord(b->ev_vt[3], st));
+  // (four passes: the sorted pairs are back in the first pair of buffers, the second takes the distinct keys and masks)
+  launch_vote_runs(b->vt_segs, b->vt_tile_seg, n_groups, (int)nst, b->vt_k[0], b->vt_v[0], b->vt_thd, b->vt_k[1], b->vt_v[1], b->vt_cursor + ng, O, st);
+  if (T) { HIPCHK(hipEventRecord(b->ev_vt[4], st)); b->vt_timed = true; }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(b->ev_votes, st));
+  b->votes_valid = true;
+  return QM_OK;
+}
+extern "C" int qm_batch_vote_timings(qm_batch* b, float* ms4) {
+  if (!b || !ms4) return fail(QM_E_INVAL, "qm_batch_vote_timings: NULL");
+  if (!b->votes_valid || !b->vt_timed) return fail(QM_E_STATE, "qm_batch_vote_timings: timing is off or no qm_batch_votes behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_vt[4]));
+  for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(ms4 + i, b->ev_vt[i], b->ev_vt[i + 1]));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_votes(qm_batch* b, uint64_t* tp_votes, uint64_t* fp_votes, uint64_t* private_tp, uint64_t* private_fp, int64_t* nokey) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_votes: NULL batch");
+  if (!b->votes_valid) return fail(QM_E_STATE, "qm_batch_get_votes: no qm_batch_votes behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_votes));
+  const size_t ng = (size_t)b->votes_groups;
+  if (!ng) return QM_OK;
+  const uint64_t* o = b->vt_out;
+  if (tp_votes) HIPCHK(hipMemcpy(tp_votes, o, ng * VT_SLOTS * 8, hipMemcpyDeviceToHost));
+  o += ng * VT_SLOTS;
+  if (fp_votes) HIPCHK(hipMemcpy(fp_votes, o, ng * VT_SLOTS * 8, hipMemcpyDeviceToHost));
+  o += ng * VT_SLOTS;
+  if (private_tp) HIPCHK(hipMemcpy(private_tp, o, ng * VT_MAX_GROUP * 8, hipMemcpyDeviceToHost));
+  o += ng * VT_MAX_GROUP;
+  if (private_fp) HIPCHK(hipMemcpy(private_fp, o, ng * VT_MAX_GROUP * 8, hipMemcpyDeviceToHost));
+  o += ng * VT_MAX_GROUP;
+  if (nokey) HIPCHK(hipMemcpy(nokey, o, ng * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_vote_groups(qm_batch* b) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_vote_groups: NULL batch");
+  if (!b->votes_valid) return fail(QM_E_STATE, "qm_batch_vote_groups: no qm_batch_votes behind the latest run");
+  return b->votes_groups;
+}
+extern "C" int qm_batch_get_vote_keys(qm_batch* b, int group, uint32_t* keys, uint32_t* masks, int64_t capacity, int64_t* n_out) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_vote_keys: NULL batch");
+  if (!b->votes_valid) return fail(QM_E_STATE, "qm_batch_get_vote_keys: no qm_batch_votes behind the latest run");
+  if (group < 0 || group >= b->votes_groups || capacity < 0) return fail(QM_E_INVAL, "qm_batch_get_vote_keys: group %d (the pass had %d)", group, b->votes_groups);
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_votes));
+  uint32_t n = 0;
+  HIPCHK(hipMemcpy(&n, b->vt_cursor + (size_t)b->votes_groups + (size_t)group, 4, hipMemcpyDeviceToHost));
+  if (n_out) *n_out = (int64_t)n;
+  if (!keys && !masks) return QM_OK;   // (the count alone)
+  if ((int64_t)n > capacity) return fail(QM_E_INVAL, "qm_batch_get_vote_keys: group %d has %u distinct keys, capacity %lld", group, n, (long long)capacity);
+  const int64_t off = b->vt_koff[(size_t)group];
+  if (n && keys) HIPCHK(hipMemcpy(keys, b->vt_k[1] + off, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (n && masks) HIPCHK(hipMemcpy(masks, b->vt_v[1] + off, (size_t)n * 4, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 // dst[i] += src[i] for device arrays (qm_extract_files_ex adds the per-truth sums of its batch into the caller's buffer)

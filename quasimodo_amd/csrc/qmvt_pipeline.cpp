@@ -28,6 +28,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/qmvt.h"
@@ -263,6 +264,101 @@ void qm_pipeline_ctx_destroyed(qm_ctx* ctx) {
   if (a) { { std::lock_guard<std::mutex> g(a->mu); a->arena.release(); } delete a; }
 }
 
+// ---- k-of-n consensus over groups of jobs ----
+// The vote pass of the finished batch, the tables of every group, and for the groups that name a level k their consensus VCF: the
+// '#' lines of the first member as its filtered file holds them, then one line per key with votes >= k in ascending key order --
+// the votes from the device (hit bitmaps for the truth keys, the distinct keys and masks for the others), the line from the host:
+// the first kept line carrying the key in the lowest-numbered member that calls it, byte for byte.  Atomic.
+static int votes_pass(qm_ctx* ctx, qm_batch* batch, int n_jobs, const qm_file_job* jobs, const std::vector<JobState>& J, const std::vector<TruthState>& T,
+                      const qm_votes_args* va, std::string& err) {
+  auto is_header = [](uint8_t k) { return k == QM_LINE_HEADER || k == QM_LINE_HEADER_KEPT || k == QM_LINE_HEADER_KEPT_TP || k == QM_LINE_HEADER_REFUSED; };
+  // a kept line without a comparable key has a text key the bitmaps cannot hold: refuse the member by name (as DESIGN.md 4.8 does)
+  for (int j = 0; j < n_jobs; ++j) {
+    const JobState& s = J[(size_t)j];
+    if (va->group[j] < 0 || s.info.n_nokey_kept == 0) continue;
+    int64_t line = 0, rec = 0;
+    for (int64_t i = 0; i < s.info.n_lines && !line; ++i) {
+      if (is_header(s.line_kind[(size_t)i])) continue;
+      if ((s.flags[rec] & QM_F_PASS) && (s.flags[rec] & QM_F_NOKEY)) line = i + 1;
+      ++rec;
+    }
+    err = std::string(jobs[j].vcf_path) + " line " + std::to_string(line) + ": a kept line has no comparable key (POS is not a canonical decimal) -- "
+          "the vote pass compares keys, not text, and does not take this VCF";
+    return QM_E_NONCANON;
+  }
+  const int ng = va->n_groups;
+  std::vector<std::vector<int>> members((size_t)ng);
+  for (int j = 0; j < n_jobs; ++j) if (va->group[j] >= 0) members[(size_t)va->group[j]].push_back(j);
+  std::vector<int32_t> goff(1, 0), gids;
+  for (const auto& m : members) {
+    for (int j : m) gids.push_back(J[(size_t)j].batch_v);
+    goff.push_back((int32_t)gids.size());
+  }
+  int rc = qm_batch_truth_hits(batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_votes(batch, ng, goff.data(), gids.data(), nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_votes(batch, va->tp_votes, va->fp_votes, va->private_tp, va->private_fp, nullptr);
+  if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
+  for (int g = 0; g < ng; ++g) {
+    const int k = va->consensus_k ? va->consensus_k[g] : 0;
+    if (k <= 0) continue;
+    const std::vector<int>& m = members[(size_t)g];
+    const TruthState& t = T[(size_t)J[(size_t)m[0]].truth];
+    // votes: the truth keys from the members' hit bitmaps, the others from the pass's distinct keys and masks
+    std::vector<uint32_t> want;
+    {
+      const size_t nw = (t.keys.size() + 31) / 32;
+      std::vector<uint8_t> cnt(t.keys.size(), 0);
+      std::vector<uint32_t> bits(nw + 1, 0u);
+      for (int j : m) {
+        rc = qm_batch_get_truth_hits(batch, J[(size_t)j].batch_v, bits.data(), (int64_t)nw);
+        if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
+        for (size_t i = 0; i < t.keys.size(); ++i) cnt[i] += (uint8_t)((bits[i >> 5] >> (i & 31)) & 1u);
+      }
+      for (size_t i = 0; i < t.keys.size(); ++i) if ((int)cnt[i] >= k) want.push_back(t.keys[i]);
+      int64_t nu = 0;
+      rc = qm_batch_get_vote_keys(batch, g, nullptr, nullptr, 0, &nu);
+      std::vector<uint32_t> uk((size_t)nu + 1), um((size_t)nu + 1);
+      if (rc == QM_OK) rc = qm_batch_get_vote_keys(batch, g, uk.data(), um.data(), nu, &nu);
+      if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
+      for (int64_t i = 0; i < nu; ++i) if (__builtin_popcount(um[(size_t)i]) >= k) want.push_back(uk[(size_t)i]);
+      std::sort(want.begin(), want.end());
+    }
+    // lines: the first kept line of every key in the lowest-numbered member that carries it
+    std::unordered_map<uint32_t, std::pair<int, int64_t>> first;   // key -> (member, line)
+    for (size_t mi = 0; mi < m.size(); ++mi) {
+      const JobState& s = J[(size_t)m[mi]];
+      std::vector<uint64_t> kept((size_t)(s.n_data + 63) / 64 + 1), tpm(kept.size());
+      rc = qm_batch_get_masks(batch, s.batch_v, kept.data(), tpm.data());
+      if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
+      int64_t rec = 0;
+      for (int64_t i = 0; i < s.info.n_lines; ++i) {
+        if (is_header(s.line_kind[(size_t)i])) continue;
+        const int64_t r = rec++;
+        if (!((kept[(size_t)r >> 6] >> (r & 63)) & 1ull) || (s.flags[r] & QM_F_NOKEY) || (uint32_t)(s.ref[r] | s.alt[r]) >= 4u) continue;
+        first.emplace(((uint32_t)s.pos[r] << 4) | ((uint32_t)s.ref[r] << 2) | (uint32_t)s.alt[r], std::make_pair((int)mi, i));
+      }
+    }
+    std::string out;
+    auto put = [&](const JobState& s, int64_t i) {
+      const int64_t a = s.line_off[(size_t)i], b = (i + 1 < s.info.n_lines) ? s.line_off[(size_t)i + 1] : (int64_t)s.vcf.n;
+      out.append((const char*)s.vcf.p + a, (size_t)(b - a));
+      if (out.empty() || out.back() != '\n') out.push_back('\n');
+    };
+    const JobState& s0 = J[(size_t)m[0]];
+    for (int64_t i = 0; i < s0.info.n_lines; ++i) if (is_header(s0.line_kind[(size_t)i])) put(s0, i);
+    for (int64_t i = 0; i < s0.info.n_lines; ++i)   // '#' lines the filter keeps stand among the kept lines of the filtered file once more
+      if (s0.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT || s0.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT_TP) put(s0, i);
+    for (uint32_t key : want) {
+      const auto it = first.find(key);
+      if (it == first.end()) { err = std::string(va->consensus_out[g]) + ": key " + std::to_string(key) + " has votes and no kept line"; return QM_E_STATE; }
+      put(J[(size_t)m[(size_t)it->second.first]], it->second.second);
+    }
+    rc = write_all_atomic(va->consensus_out[g], out);
+    if (rc != QM_OK) { err = std::string("cannot write ") + va->consensus_out[g]; return rc; }
+  }
+  return QM_OK;
+}
+
 extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                 qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds) {
   return qm_extract_files_ex(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, nullptr, 0, nullptr);
@@ -270,7 +366,8 @@ extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba);
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba,
+                         const qm_votes_args* va = nullptr);
 
 extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                    qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
@@ -359,9 +456,40 @@ extern "C" int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job*
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, boot);
 }
 
+// k-of-n caller consensus behind the worker: vote tables of groups of jobs, and a group's consensus VCF
+extern "C" int qm_extract_files_votes(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                      qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                      int n_slots, void* global_dev, const qm_votes_args* votes) {
+  const qm_votes_args* va = votes;
+  if (!va || va->n_groups < 0 || (n_jobs > 0 && !va->group) || (va->n_groups > 0 && (!va->tp_votes || !va->fp_votes || !va->private_tp || !va->private_fp)))
+    return fail(QM_E_INVAL, "qm_extract_files_votes: NULL arguments");
+  if (mode & QM_BATCH_ALLELES) return fail(QM_E_STATE, "qm_extract_files_votes: allele-extended batches have no vote pass (single-base batches only)");
+  for (int j = 0; j < n_jobs; ++j) {
+    if (va->group[j] < -1 || va->group[j] >= va->n_groups) return fail(QM_E_INVAL, "qm_extract_files_votes: job " + std::to_string(j) + " names group " + std::to_string(va->group[j]));
+    if (jobs[j].pure && va->group[j] >= 0) return fail(QM_E_INVAL, "qm_extract_files_votes: pure-strain job " + std::to_string(j) + " cannot be in a group (its truth is never read)");
+  }
+  for (int g = 0; g < va->n_groups; ++g) {
+    int members = 0;
+    for (int j = 0; j < n_jobs; ++j) members += va->group[j] == g;
+    if (members < 1 || members > QM_VOTE_GROUP_MAX)
+      return fail(QM_E_INVAL, "qm_extract_files_votes: group " + std::to_string(g) + " has " + std::to_string(members) + " jobs (1 to " + std::to_string(QM_VOTE_GROUP_MAX) + ")");
+    const int k = va->consensus_k ? va->consensus_k[g] : 0;
+    if (k < 0 || k > members) return fail(QM_E_INVAL, "qm_extract_files_votes: group " + std::to_string(g) + ": consensus level " + std::to_string(k) + " with " + std::to_string(members) + " members");
+    if (k > 0 && (!va->consensus_out || !va->consensus_out[g])) return fail(QM_E_INVAL, "qm_extract_files_votes: group " + std::to_string(g) + " names a consensus level and no file");
+  }
+  if (va->n_groups > 0) {
+    memset(va->tp_votes, 0, sizeof(uint64_t) * QM_VOTE_SLOTS * (size_t)va->n_groups);
+    memset(va->fp_votes, 0, sizeof(uint64_t) * QM_VOTE_SLOTS * (size_t)va->n_groups);
+    memset(va->private_tp, 0, sizeof(uint64_t) * QM_VOTE_GROUP_MAX * (size_t)va->n_groups);
+    memset(va->private_fp, 0, sizeof(uint64_t) * QM_VOTE_GROUP_MAX * (size_t)va->n_groups);
+  }
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, va);
+}
+
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba) {
+                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba,
+                         const qm_votes_args* va) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
     return fail(QM_E_INVAL, "qm_extract_files: bad arguments");
   if (global_dev && (n_slots < 1 || (n_jobs && !truth_slot))) return fail(QM_E_INVAL, "qm_extract_files_ex: global_dev needs truth_slot and n_slots >= 1");
@@ -474,7 +602,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (k < 0) { truth_rc = (int)k; truth_msg = "qm_truth_scan failed for " + t.path; break; }
       const int rc = qm_truth_load(ctx, tp.data(), tr.data(), ta.data(), k, &t.tid);
       if (rc != QM_OK) { truth_rc = rc; truth_msg = qm_last_error(ctx); break; }
-      if (ts) {
+      if (ts || va) {
         for (int64_t i = 0; i < k; ++i)
           if ((uint32_t)(tr[(size_t)i] | ta[(size_t)i]) < 4u) t.keys.push_back(((uint32_t)tp[(size_t)i] << 4) | ((uint32_t)tr[(size_t)i] << 2) | (uint32_t)ta[(size_t)i]);
         std::sort(t.keys.begin(), t.keys.end());
@@ -776,6 +904,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
         }
       } else
       if (rc != QM_OK) err = qm_last_error(ctx);
+      if (rc == QM_OK && va && va->n_groups > 0) rc = votes_pass(ctx, batch, n_jobs, jobs, J, T, va, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;

@@ -180,7 +180,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None, boot=None):
+                      truthside=None, profile=None, strata=None, boot=None, votes=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -199,8 +199,15 @@ class Engine:
         boot: {"want": [0/1 per job], "window": 1024, "n_win": 256, "n_rep": 1000, "seed": 0} -- qm_extract_files_boot (DESIGN.md
         4.11; combines with none of the above): wanted rows gain `boot_cnt` ([n_win + 2][4] uint64: kept lines, TP lines, truth
         keys, hit keys per window, then outside, nokey) and `boot_rep` ([n_rep][4], the bootstrap replicates of the four sums).
+        votes: {"group": [group id or -1 per job], "k": [consensus level or 0 per group], "out": [path or None per group]} --
+        qm_extract_files_votes (combines with none of the above): the rows of grouped jobs gain `tp_votes`,
+        `fp_votes` ([33] uint64), `private_tp`, `private_fp` ([32]; the same for every member, members in job order) and
+        `vote_member` (the job's index in its group); the consensus VCFs of the groups with a level are written.
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         import os
+        if votes is not None and (boot is not None or strata is not None or profile is not None or truthside is not None or
+                                  (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
+            raise ValueError("votes does not combine with genomes, truthside, profile, strata or boot in one call")
         if profile is not None and truthside is not None:
             raise ValueError("truthside and profile in one call are not supported")
         if strata is not None and (profile is not None or truthside is not None or (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
@@ -228,7 +235,21 @@ class Engine:
         afg = None
         srec = None
         bcnt = None
-        if boot is not None:
+        vtab = None
+        if votes is not None:
+            vgrp = _c([-1 if g is None else int(g) for g in votes["group"]] or [-1], np.int32)
+            if n and vgrp.shape[0] != n:
+                raise ValueError("votes: %d group entries for %d jobs" % (vgrp.shape[0], n))
+            vng = (int(vgrp.max()) + 1) if n else 0
+            vk = _c(list(votes.get("k") or [0] * vng) or [0], np.int32)
+            vout = list(votes.get("out") or [None] * vng)
+            if vng and (vk.shape[0] != vng or len(vout) != vng):
+                raise ValueError("votes: %d levels / %d files for %d groups" % (vk.shape[0], len(vout), vng))
+            vtab = [np.zeros((max(vng, 1), w), np.uint64) for w in (_lib.QM_VOTE_SLOTS, _lib.QM_VOTE_SLOTS, _lib.QM_VOTE_GROUP_MAX, _lib.QM_VOTE_GROUP_MAX)]
+            out_arr = (C.c_char_p * max(vng, 1))(*[None if x is None else os.fsencode(x) for x in vout])
+            va = _lib.VotesArgs(_p(vgrp), vng, 0, _p(vtab[0]), _p(vtab[1]), _p(vtab[2]), _p(vtab[3]), _p(vk), out_arr)
+            check(self._L.qm_extract_files_votes(*args, C.byref(va)), self._h)
+        elif boot is not None:
             bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
             if n and bwant.shape[0] != n:
                 raise ValueError("boot: %d want entries for %d jobs" % (len(boot["want"]), n))
@@ -301,6 +322,10 @@ class Engine:
             if bcnt is not None and bwant[k]:
                 r["boot_cnt"] = bcnt[k].copy()
                 r["boot_rep"] = brep[k, :br].copy()
+            if vtab is not None and vgrp[k] >= 0:
+                g = int(vgrp[k])
+                r.update(tp_votes=vtab[0][g].copy(), fp_votes=vtab[1][g].copy(), private_tp=vtab[2][g].copy(), private_fp=vtab[3][g].copy(),
+                         vote_member=int((vgrp[:k] == g).sum()))
             if regs is not None and grp[k] >= 0:
                 r["truth_regions"] = regs[grp[k]].astype(np.int64)
                 r["fp_regions"] = fregs[grp[k]].copy()
@@ -554,6 +579,44 @@ class Batch:
             out.append(np.unpackbits(uni[o:o + nw].view(np.uint8), bitorder="little").astype(bool)[:t])
             o += nw
         return reg, out
+
+    # -- k-of-n caller consensus ----------------------------------
+    def votes(self, groups, stream=None):
+        """qm_batch_votes: enqueue the vote pass of the finished batch (needs truth_hits).  groups: lists of 1..32 VCF ids that
+        share a truth set, a VCF in at most one of them."""
+        groups = [[int(v) for v in g] for g in groups]
+        offs = np.zeros(len(groups) + 1, np.int32)
+        offs[1:] = np.cumsum([len(g) for g in groups])
+        ids = _c([v for g in groups for v in g] or [0], np.int32)
+        self._ck(self._L.qm_batch_votes(self._h, len(groups), _p(offs), _p(ids), C.c_void_p(stream) if stream else None))
+
+    def vote_counts(self):
+        """qm_batch_get_votes: dict of tp_votes, fp_votes [n_groups][33], private_tp, private_fp [n_groups][32] (uint64) and
+        nokey [n_groups] (int64).  [g][c] = keys of group g that exactly c members call (tp: truth keys, c = 0 missed by all;
+        fp: distinct keys outside the truth set); private_*[g][i] = keys only member i calls."""
+        ng = self._ck(self._L.qm_batch_vote_groups(self._h))   # the library's count: the arrays fit whoever enqueued the pass
+        m = max(ng, 1)
+        out = {"tp_votes": np.zeros((m, _lib.QM_VOTE_SLOTS), np.uint64), "fp_votes": np.zeros((m, _lib.QM_VOTE_SLOTS), np.uint64),
+               "private_tp": np.zeros((m, _lib.QM_VOTE_GROUP_MAX), np.uint64), "private_fp": np.zeros((m, _lib.QM_VOTE_GROUP_MAX), np.uint64),
+               "nokey": np.zeros(m, np.int64)}
+        self._ck(self._L.qm_batch_get_votes(self._h, _p(out["tp_votes"]), _p(out["fp_votes"]), _p(out["private_tp"]), _p(out["private_fp"]),
+                                            _p(out["nokey"])))
+        return {k: v[:ng] for k, v in out.items()}
+
+    def vote_timings(self):
+        """qm_batch_vote_timings (set_timing on): milliseconds of the latest votes() between HIP events, stage by stage"""
+        ms = (C.c_float * 4)()
+        self._ck(self._L.qm_batch_vote_timings(self._h, ms))
+        return {"vote_truth_ms": ms[0], "vote_keys_ms": ms[1], "sort_ms": ms[2], "vote_runs_ms": ms[3]}
+
+    def vote_keys(self, g):
+        """qm_batch_get_vote_keys: (ukeys, umasks) uint32 -- the ascending distinct keys pos << 4 | ref << 2 | alt of group g
+        outside the truth set, and per key the mask of the members that call it (bit i = member i)"""
+        n = C.c_int64(0)
+        self._ck(self._L.qm_batch_get_vote_keys(self._h, int(g), None, None, 0, C.byref(n)))
+        keys, masks = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        self._ck(self._L.qm_batch_get_vote_keys(self._h, int(g), _p(keys), _p(masks), int(keys.shape[0]), C.byref(n)))
+        return keys[:n.value], masks[:n.value]
 
     def path_stats(self):
         """qm_batch_path_stats: where the VCFs the last finish found out of order went"""

@@ -51,6 +51,10 @@ class Job:
     strata: tuple = None      # ((name, starts, ends), ...): stats gain strata_rec / strata_tru (the same set for every such job of a call)
     # paired block-bootstrap replicates
     boot: tuple = None        # (window, n_win, n_rep, seed): stats gain boot_cnt / boot_rep (the same for every such job of a call)
+    # k-of-n caller consensus; mixed samples only
+    vote_group: str = None    # label of the job's vote group (1 to 32 jobs of one truth file): stats gain tp_votes / fp_votes / private_*
+    consensus_k: int = 0      # the group's consensus level (any member may carry it, with consensus_out); 0 = no file
+    consensus_out: str = None
 
 
 def _paths(job):
@@ -92,7 +96,7 @@ def _alleles_default():
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None):
+                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -119,7 +123,35 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     job gets stats["boot_cnt"] ([n_win + 2][4]: kept lines, TP lines, truth keys, hit keys per window, then outside, nokey),
     stats["boot_rep"] ([n_rep][4]: the bootstrap replicates of the four sums, the same draws for every job, call, rank and
     device), stats["boot_params"] and stats["boot_truth"] (False in the allele-extended mode: columns 2 and 3 are zero).
-    Combines with none of genomes, fn, groups, profile, strata (ValueError)."""
+    Combines with none of genomes, fn, groups, profile, strata (ValueError).
+    votes: True or {"k": [level or 0 per group], "out": [path or None per group]} (quasimodo_amd.consensus; default: the jobs'
+    Job.vote_group / consensus_k / consensus_out): `groups` then names the VOTE groups (1 to 32 mixed-sample jobs of one truth
+    file each, a job in at most one): the members' stats gain tp_votes / fp_votes ([33]), private_tp / private_fp ([32]),
+    vote_member (the job's index in its group) and vote_callers (the members' Job.caller, in member order = job order), and the
+    groups with a level get their consensus VCF.  Over several GPUs a group must sit on one rank (WorkflowError otherwise).
+    Combines with none of genomes, fn, profile, strata, boot (ValueError)."""
+    if votes:
+        from .consensus import MAX_GROUP as VMAX
+        if groups is None:
+            raise ValueError("votes: groups (lists of job indices) are needed")
+        opt = votes if isinstance(votes, dict) else {}
+        ks, outs = list(opt.get("k") or [0] * len(groups)), list(opt.get("out") or [None] * len(groups))
+        if len(ks) != len(groups) or len(outs) != len(groups):
+            raise ValueError("votes: %d levels / %d files for %d groups" % (len(ks), len(outs), len(groups)))
+        for k, g in enumerate(groups):
+            if not 1 <= len(g) <= VMAX:
+                raise ValueError("a vote group holds 1 to %d jobs, not %d" % (VMAX, len(g)))
+            if not 0 <= int(ks[k]) <= len(g):
+                raise ValueError("vote group %d: consensus level %d with %d members" % (k, int(ks[k]), len(g)))
+            for i in g:
+                if jobs[i].vote_group is not None and jobs[i].vote_group != "v%d" % k:
+                    raise ValueError("job %d sits in two vote groups" % i)
+                jobs[i].vote_group, jobs[i].consensus_k, jobs[i].consensus_out = "v%d" % k, int(ks[k]), outs[k]
+        groups = None
+    if any(j.vote_group is not None for j in jobs):
+        if genomes is not None or fn or groups is not None or profile is not None or strata is not None or boot is not None or any(
+                j.genome or j.fn_out or j.group is not None or j.profile or j.strata or j.boot for j in jobs):
+            raise ValueError("votes does not combine with genomes, fn, truth-side groups, profile, strata or boot in one call")
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -180,10 +212,10 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
         from .multigpu import extract_many_sharded
         plan = None
-        if any(j.group is not None for j in jobs):   # the members of a truth-side group go to one rank
+        if any(j.group is not None or j.vote_group is not None for j in jobs):   # the members of a group go to one rank
             by = {}
             for i, j in enumerate(jobs):
-                by.setdefault(("g", j.group) if j.group is not None else ("j", i), []).append(i)
+                by.setdefault(("g", j.group) if j.group is not None else ("v", j.vote_group) if j.vote_group is not None else ("j", i), []).append(i)
             plan = list(by.values())
         return extract_many_sharded(jobs, int(gpus), n_bins=n_bins, alleles=alleles, strict=strict, groups=plan)[0]
     if alleles and any(j.mode != "hcmv" for j in jobs):
@@ -196,7 +228,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        need = not all(pure) or any(j.genome or j.profile or j.strata or j.boot for j in jobs)
+        need = not all(pure) or any(j.genome or j.profile or j.strata or j.boot for j in jobs)   # (a vote group holds no pure-strain sample)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
@@ -218,6 +250,28 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
               "group": [-1 if j.group is None else labels.index(j.group) for j in jobs], "missed": missed}
         for path in [x for x in ts["fn"] + missed if x]:
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    vt = None
+    vlabels = []
+    if any(j.vote_group is not None for j in jobs):
+        from .consensus import MAX_GROUP as VMAX
+        for j, p in zip(jobs, pure):
+            if j.vote_group is not None and p:
+                raise ValueError("%s: a pure-strain sample cannot be in a vote group (its truth is never read)" % j.vcf_file)
+            if j.vote_group is not None and j.vote_group not in vlabels:
+                vlabels.append(j.vote_group)
+        vt = {"group": [-1 if j.vote_group is None else vlabels.index(j.vote_group) for j in jobs], "k": [], "out": []}
+        for lab in vlabels:
+            mem = [j for j in jobs if j.vote_group == lab]
+            if len(mem) > VMAX:
+                raise ValueError("vote group %r holds %d jobs (1 to %d)" % (lab, len(mem), VMAX))
+            k = next((j.consensus_k for j in mem if j.consensus_k), 0)
+            out = next((j.consensus_out for j in mem if j.consensus_out), None)
+            if k > len(mem):
+                raise ValueError("vote group %r: consensus level %d with %d members" % (lab, k, len(mem)))
+            vt["k"].append(k if out else 0)
+            vt["out"].append(out if k else None)
+            if k and out:
+                os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
     try:
         for job, p in zip(jobs, pure):
             os.makedirs(os.path.dirname(job.fp_out) or ".", exist_ok=True)
@@ -254,7 +308,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                 par = next(j.boot for j in jobs if j.boot)
                 bt = {"want": [1 if j.boot else 0 for j in jobs], "window": par[0], "n_win": par[1], "n_rep": par[2], "seed": par[3]}
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt)
+            if vt is not None:
+                for r, j in zip(rows, jobs):
+                    if j.vote_group is not None:
+                        r["vote_callers"] = [m.caller for m in jobs if m.vote_group == j.vote_group]
             if bt is not None:
                 for r in rows:
                     if "boot_cnt" in r:

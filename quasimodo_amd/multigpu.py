@@ -124,6 +124,10 @@ def run_rank(jobs, rank, world, backend="nccl", body=None, n_bins=256, alleles=N
             if jobs[i].group is not None and where.setdefault(jobs[i].group, r) != r:
                 from .workflow import WorkflowError
                 raise WorkflowError("truth-side group %r: its VCFs are not all on one rank (deal the VCFs by group)" % jobs[i].group)
+            vg = getattr(jobs[i], "vote_group", None)
+            if vg is not None and where.setdefault(("votes", vg), r) != r:
+                from .workflow import WorkflowError
+                raise WorkflowError("vote group %r: its VCFs are not all on one rank (deal the VCFs by group)" % vg)
     device = 0 if same_device else rank
     keys, slot = truth_layout(jobs)
     opts = dict(n_bins=n_bins, alleles=alleles, strict=strict, slots=[slot[i] for i in mine], n_slots=len(keys), backend=backend,
@@ -215,7 +219,8 @@ def extract_many_sharded(jobs, gpus, backend="nccl", body=None, n_bins=256, alle
     timeout = DEFAULT_TIMEOUT if timeout is None else timeout
     with tempfile.TemporaryDirectory(prefix="qmvt_mgpu_") as tmp:
         spec = {"jobs": [dict(vcf_file=j.vcf_file, snp_file=j.snp_file, mode=j.mode, outdir=j.outdir, caller=j.caller, genome=j.genome,
-                              fn_out=j.fn_out, group=j.group, missed_out=j.missed_out, profile=j.profile, points_out=j.points_out, strata=j.strata, boot=j.boot)
+                              fn_out=j.fn_out, group=j.group, missed_out=j.missed_out, profile=j.profile, points_out=j.points_out, strata=j.strata, boot=j.boot,
+                              vote_group=j.vote_group, consensus_k=j.consensus_k, consensus_out=j.consensus_out)
                          for j in jobs],
                 "world": gpus, "backend": backend, "body": body, "n_bins": n_bins, "alleles": alleles, "strict": strict,
                 "same_device": same_device, "result": os.path.join(tmp, "result.pkl"), "groups": groups, "post": post,

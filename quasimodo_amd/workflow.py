@@ -153,7 +153,8 @@ def hcmv_rank_post(engine, jobs, indices, args):
 
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
-                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None):
+                         _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
+                         votes=False, consensus_vcf=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -176,8 +177,18 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     counts and the replicates are taken behind the classification; final_tables/caller_performance_ci.tsv (percentile
     intervals of Precision, Recall and F1 per caller x sample) and caller_performance_ci_pairs.tsv (the F1 difference of every
     pair of callers on a mixed sample, over the shared draws) are written.  n_win is raised to cover the truth files' largest
-    POS.  Combines with none of the four above."""
+    POS.  Combines with none of the four above.
+    votes: k-of-n caller consensus (quasimodo_amd.consensus): all callers of the run form one vote group per mixed
+    sample; final_tables/caller_consensus.tsv (TP, FP, FN, Precision, Recall, F1 of "at least k of n callers") and
+    caller_private.tsv (what each caller alone calls) are written.  consensus_vcf=K (implies votes) also writes
+    snp/consensus/{sample}.{ref}.k{K}.vcf; K above the sample's caller count is a WorkflowError that names the sample.  Combines
+    with none of the five above."""
     callers = list(callers or SNPCALLERS)
+    votes = bool(votes) or consensus_vcf is not None
+    if votes and (bootstrap is not None or strata is not None or mutation_context is not None or truth_side or snp_profile):
+        raise WorkflowError("--votes cannot be combined with --bootstrap, --strata, --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
+    if consensus_vcf is not None and int(consensus_vcf) < 1:
+        raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if bootstrap is not None and (strata is not None or mutation_context is not None or truth_side or snp_profile):
         raise WorkflowError("--bootstrap cannot be combined with --strata, --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
     if strata is not None:
@@ -234,6 +245,13 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("caller_performance_strata\t%s" % ",".join(s[0] for s in strata))
         if bootstrap is not None:
             print("caller_performance_ci\t%d" % _boot_params(bootstrap, [])[2])
+        if votes:
+            _vote_plan(plan, consensus_vcf)
+            print("caller_consensus\t%s" % ",".join(callers))
+            if consensus_vcf is not None:
+                for s in samples:
+                    if not s.endswith(("-1-0", "-0-1")):
+                        print("consensus_vcf\t%s\t%d" % (s, int(consensus_vcf)))
         if truth_side:
             from .truthside import venn_callers
             for s, c, src in plan:
@@ -288,6 +306,14 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 if c in vc:
                     j.group = s
                     j.missed_out = os.path.join(snp_dir, "nucmer", "%s.missed_by_all.vcf" % s)
+    if votes:
+        _vote_plan(plan, consensus_vcf)
+        for (c, s), j in zip(meta, jobs):
+            if s in mixed:
+                j.vote_group = s
+                if consensus_vcf is not None:
+                    j.consensus_k = int(consensus_vcf)
+                    j.consensus_out = os.path.join(snp_dir, "consensus", "%s.%s.k%d.vcf" % (s, SAMPLE_REF[s], int(consensus_vcf)))
     cmp_callers = [c for c in FP_COMPARED if c in callers]
     tables = os.path.join(results, "final_tables")
     if gpus is not None and (int(gpus) > 1 or _body):
@@ -312,6 +338,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_bootstrap(meta, jobs, tables)
         if truth_side:
             _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
+        if votes:
+            _write_votes(meta, jobs, tables, mixed)
         if mixed and len(cmp_callers) >= 2:
             reg = {}
             for e in res["extras"]:
@@ -342,6 +370,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_bootstrap(meta, jobs, os.path.join(results, "final_tables"))
         if truth_side:
             _write_caller_snp_venn(meta, jobs, os.path.join(results, "final_tables"), callers, mixed)
+        if votes:
+            _write_votes(meta, jobs, os.path.join(results, "final_tables"), mixed)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
         if mixed and len(cmp_callers) >= 2:                              # compareFP (counts only)
             files = {s: {c: j.fp_out for (c, ss), j in zip(meta, jobs) if ss == s and c in cmp_callers} for s in mixed}
@@ -354,6 +384,38 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
 
 
 run_hcmv_variantcall.last_result = None
+
+
+def _vote_plan(plan, consensus_vcf):
+    """the callers of every mixed sample of the run: 1 to 32, and not fewer than the consensus level"""
+    from .consensus import MAX_GROUP
+    per = {}
+    for s, c, _ in plan:
+        if not s.endswith(("-1-0", "-0-1")):
+            per.setdefault(s, []).append(c)
+    for s in sorted(per):
+        if len(per[s]) > MAX_GROUP:
+            raise WorkflowError("sample %s: %d callers, a vote group holds at most %d" % (s, len(per[s]), MAX_GROUP))
+        if consensus_vcf is not None and int(consensus_vcf) > len(per[s]):
+            raise WorkflowError("sample %s: --consensus-vcf %d, but the sample has %d callers" % (s, int(consensus_vcf), len(per[s])))
+    return per
+
+
+def _write_votes(meta, jobs, tables, mixed):
+    """final_tables/caller_consensus.tsv and caller_private.tsv from the rows of every mixed sample's vote group"""
+    from .consensus import write_caller_consensus, write_caller_private
+    cons, priv = {}, {}
+    for s in mixed:
+        mem = [(c, j) for (c, ss), j in zip(meta, jobs) if ss == s]
+        st = mem[0][1].stats
+        if "tp_votes" not in st or len(st.get("vote_callers") or []) != len(mem):
+            raise WorkflowError("sample %s: no vote counts came back for its callers" % s)
+        n = len(mem)
+        cons[s] = (n, [int(x) for x in st["tp_votes"]], [int(x) for x in st["fp_votes"]])
+        priv[s] = (list(st["vote_callers"]), [int(x) for x in st["private_tp"]], [int(x) for x in st["private_fp"]])
+    if cons:
+        write_caller_consensus(os.path.join(tables, "caller_consensus.tsv"), cons)
+        write_caller_private(os.path.join(tables, "caller_private.tsv"), priv)
 
 
 def _write_caller_snp_venn(meta, jobs, tables, callers, mixed):
@@ -512,7 +574,7 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
 
 
 def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
-                truth_side=False, strata=None, bootstrap=None):
+                truth_side=False, strata=None, bootstrap=None, votes=False, consensus_vcf=None):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
@@ -520,8 +582,17 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     strata: a list of (name, starts, ends) BED strata: final_tables/snpcall_benchmark_strata.txt is written; not
     together with truth_side.
     bootstrap: a replicate count or {"n_rep", "window", "n_win", "seed"}: final_tables/snpcall_benchmark_ci.txt
-    is written; not together with truth_side or strata."""
+    is written; not together with truth_side or strata.
+    votes: the labels form one vote group: final_tables/caller_consensus.tsv and caller_private.tsv (sample
+    "custom"); more than 32 labels (or pure-strain names) are told so and get no table.  consensus_vcf=K (implies votes) also writes
+    snp/consensus/custom.k{K}.vcf; K above the label count is a WorkflowError.  Not together with the three above."""
     from .truthside import MAX_GROUP
+    from .consensus import MAX_GROUP as VOTE_MAX
+    votes = bool(votes) or consensus_vcf is not None
+    if votes and (bootstrap is not None or truth_side or strata is not None):
+        raise WorkflowError("--votes cannot be combined with --bootstrap, --truth-side or --strata: it runs in a call of its own.")
+    if consensus_vcf is not None and int(consensus_vcf) < 1:
+        raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if bootstrap is not None and (truth_side or strata is not None):
         raise WorkflowError("--bootstrap cannot be combined with --truth-side or --strata: it runs in a call of its own.")
     if strata is not None:
@@ -537,9 +608,18 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     labels = list(labels) if labels else [os.path.splitext(os.path.basename(v))[0] for v in vcfs]
     if len(labels) != len(vcfs):
         raise WorkflowError("labels and vcfs differ in length")
+    voted = votes and len(labels) <= VOTE_MAX and not any(is_pure_strain(v) for v in vcfs)
+    if votes and not voted:
+        print("votes: %d labels (or pure-strain names): a vote group holds 1 to %d mixed samples, no table is written" % (len(labels), VOTE_MAX))
+    if voted and consensus_vcf is not None and int(consensus_vcf) > len(labels):
+        raise WorkflowError("sample custom: --consensus-vcf %d, but there are %d labels" % (int(consensus_vcf), len(labels)))
     if dryrun:
         for lab, v in zip(labels, vcfs):
             print("extract_TP\t%s\t%s" % (lab, v))
+        if voted:
+            print("caller_consensus\t%s" % ",".join(labels))
+            if consensus_vcf is not None:
+                print("consensus_vcf\tcustom\t%d" % int(consensus_vcf))
         if truth_side:
             for lab in labels:
                 print("truthside_fn\t%s" % lab)
@@ -561,12 +641,18 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
             if not is_pure_strain(j.vcf_file):
                 j.fn_out = fn_path(j)
                 j.group = "vareval" if grouped else None
+    if voted:
+        for j in jobs:
+            j.vote_group = "custom"
+            if consensus_vcf is not None:
+                j.consensus_k = int(consensus_vcf)
+                j.consensus_out = os.path.join(results, "snp", "consensus", "custom.k%d.vcf" % int(consensus_vcf))
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
         from .multigpu import extract_many_sharded
         jobs, res = extract_many_sharded(jobs, int(gpus), backend=_backend, body=_body, same_device=_same_device,
-                                         groups=[list(range(len(jobs)))] if grouped else None)
+                                         groups=[list(range(len(jobs)))] if grouped or voted else None)
         run_vareval.last_result = res
     else:
         extract_many(jobs, engine=engine)
@@ -583,6 +669,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
         from .bootstrap import write_performance_ci
         _boot_extra(jobs)
         write_performance_ci(os.path.join(results, "final_tables", "snpcall_benchmark_ci.txt"), [(lab, None, j.stats) for lab, j in zip(labels, jobs)], custom=True)
+    if voted:
+        _write_votes([(lab, "custom") for lab in labels], jobs, os.path.join(results, "final_tables"), ["custom"])
     if grouped:
         from .truthside import write_caller_snp_venn
         n = len(labels)
