@@ -2143,6 +2143,48 @@ static int rescan_and_compact(qm_batch* b, hipStream_t st) {
 #define NEED_FINISHED(b, name) \
   if (!(b) || !(b)->finished) return fail(QM_E_STATE, name ": call qm_batch_run + qm_batch_finish first")
 
+// ---- what the passes over a finished batch share ----
+// The truth sets of the batch are the ones it was created with: asked by every pass that reads their keys or the hit bitmaps.
+static int truths_live(const qm_batch* b, const char* who) {
+  const qm_ctx* c = b->ctx;
+  for (const auto& tg : b->truth_gens)
+    if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
+      return fail(QM_E_STATE, "%s: truth set %d was released after the batch was created", who, tg.first);
+  return QM_OK;
+}
+// How a pass opens (PassStream of DESIGN.md 4.13): the context's device, the caller's stream or the context's, and the pass's event -- created at first use,
+// waited for on the host afterwards (the previous call of the pass has read its tables and left its outputs).
+static int pass_stream(qm_batch* b, void* stream, hipEvent_t* ev, hipStream_t* st) {
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  *st = stream ? (hipStream_t)stream : b->ctx->stream;
+  if (!*ev) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(*ev));
+  return QM_OK;
+}
+// One group of a pass over the hit bitmaps (G: TruthGroup, VoteGroup): VCFs vcf_ids[group_offsets[g] .. group_offsets[g + 1]), 1 to
+// `max` of them, all of one truth set.  Fills t's bitmaps, words, T' and n; per_member(i, v) is the caller's own check of member i.
+template <typename G, typename F>
+static int walk_hit_group(const qm_batch* b, const char* who, int g, const int32_t* group_offsets, const int32_t* vcf_ids, int max, G& t, F&& per_member) {
+  const int32_t o0 = group_offsets[g], o1 = group_offsets[g + 1];
+  if (o0 < 0 || o1 - o0 < 1 || o1 - o0 > max) return fail(QM_E_INVAL, "%s: group %d has %d VCFs (1 to %d)", who, g, o1 - o0, max);
+  memset(&t, 0, sizeof t);
+  t.n = o1 - o0;
+  int truth = -1;
+  for (int i = 0; i < t.n; ++i) {
+    const int v = vcf_ids[o0 + i];
+    if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "%s: group %d names VCF %d (the batch has %d)", who, g, v, b->n_vcf);
+    const int rc = per_member(i, v);
+    if (rc != QM_OK) return rc;
+    const int tv = b->L.vcfs[(size_t)v].truth;
+    if (i == 0) truth = tv;
+    else if (tv != truth) return fail(QM_E_INVAL, "%s: group %d mixes truth sets %d and %d", who, g, truth, tv);
+    t.bits[i] = b->d_hits + b->h_hit_off[(size_t)v];
+    t.words = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
+  }
+  t.tn = b->h_hit_tn[(size_t)vcf_ids[o0]];   // T' as it was when the bitmaps were sized (qm_batch_truth_hits checked the generations)
+  return QM_OK;
+}
+
 extern "C" int qm_batch_get_cls(qm_batch* b, int v, uint8_t* out) {
   NEED_FINISHED(b, "qm_batch_get_cls");
   if (v < 0 || v >= b->n_vcf || !out) return fail(QM_E_INVAL, "qm_batch_get_cls: bad arguments");
@@ -2210,16 +2252,15 @@ extern "C" int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, vo
     if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_motifs: VCF %d names genome %d (have %zu)", v, gid, c->genomes.size());
     if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_motifs: VCF %d names released genome %d", v, gid);
   }
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st;   // (the previous call's copy has read the page-locked descriptors)
+  int rc = pass_stream(b, stream, &b->ev_motif, &st);
+  if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf;
   // first use: every piece on its own, so that a call that failed half way is completed by the next
-  int rc = b->d_motifs.grow((int64_t)(nv * MOTIF_ROW_WORDS), &b->dev_bytes);
+  rc = b->d_motifs.grow((int64_t)(nv * MOTIF_ROW_WORDS), &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_mgen.grow((int64_t)nv, &b->dev_bytes);
   if (rc != QM_OK) return rc;
   if (!b->h_mgen) HIPCHK(hipHostMalloc((void**)&b->h_mgen, nv * sizeof(GenomeRef), hipHostMallocDefault));
-  if (!b->ev_motif) HIPCHK(hipEventCreateWithFlags(&b->ev_motif, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(b->ev_motif));   // the previous call's copy has read the page-locked descriptors
   for (size_t v = 0; v < nv; ++v) {
     const int gid = genome_id_per_vcf[v];
     b->h_mgen[v] = gid < 0 ? GenomeRef{nullptr, 0} : GenomeRef{c->genomes[(size_t)gid].d_words, c->genomes[(size_t)gid].len};
@@ -2269,13 +2310,11 @@ extern "C" int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bi
   NEED_FINISHED(b, "qm_batch_af_profile");
   if (window < 1 || window >= QM_POS_LIMIT || n_pos_bins < 1 || n_af_bins < 1 || (int64_t)n_pos_bins * n_af_bins > QM_AFP_MAX_CELLS)
     return fail(QM_E_INVAL, "qm_batch_af_profile: window %d, %d x %d bins (1 <= window < 2^28, at most %d cells)", window, n_af_bins, n_pos_bins, QM_AFP_MAX_CELLS);
-  qm_ctx* c = b->ctx;
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st;   // (the previous pass has read the marks and left the outputs)
+  int rc = pass_stream(b, stream, &b->ev_afp, &st);
+  if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf, cells = (size_t)n_pos_bins * (size_t)n_af_bins;
-  if (!b->ev_afp) HIPCHK(hipEventCreateWithFlags(&b->ev_afp, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(b->ev_afp));   // the previous pass has read the marks and left the outputs
-  int rc = b->d_afgrid.grow((int64_t)(nv * 2 * cells), &b->dev_bytes);
+  rc = b->d_afgrid.grow((int64_t)(nv * 2 * cells), &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_afextra.grow((int64_t)(nv * 2 * AFP_EXTRA), &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_afmark.grow((int64_t)nv, &b->dev_bytes);
   if (rc != QM_OK) return rc;
@@ -2320,16 +2359,14 @@ extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* 
   if (what & QM_STRATA_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_strata: allele-extended batches have no truth-side bitmaps (QM_STRATA_RECORDS only)");
     if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_strata: QM_STRATA_TRUTH needs a qm_batch_truth_hits behind the latest run");
-    for (const auto& tg : b->truth_gens)
-      if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
-        return fail(QM_E_STATE, "qm_batch_strata: truth set %d was released after the batch was created", tg.first);
+    const int rc = truths_live(b, "qm_batch_strata");
+    if (rc != QM_OK) return rc;
   }
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st;
+  const int rc0 = pass_stream(b, stream, &b->ev_strata, &st);
+  if (rc0 != QM_OK) return rc0;
   const size_t nv = (size_t)b->n_vcf;
   const int S = t->n_strata;
-  if (!b->ev_strata) HIPCHK(hipEventCreateWithFlags(&b->ev_strata, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(b->ev_strata));   // the previous pass has read its rows and left the outputs
   b->strata_made = 0;
   StrataTable tab;
   tab.bp = t->d_bp; tab.masks = t->d_masks; tab.cidx = t->d_cidx;
@@ -2428,18 +2465,16 @@ extern "C" int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t
   if (what & QM_BOOT_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_boot: allele-extended batches have no truth-side bitmaps (QM_BOOT_RECORDS only)");
     if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_boot: QM_BOOT_TRUTH needs a qm_batch_truth_hits behind the latest run");
-    for (const auto& tg : b->truth_gens)
-      if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
-        return fail(QM_E_STATE, "qm_batch_boot: truth set %d was released after the batch was created", tg.first);
+    const int rc = truths_live(b, "qm_batch_boot");
+    if (rc != QM_OK) return rc;
   }
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t st;
+  int rc = pass_stream(b, stream, &b->ev_boot, &st);
+  if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf;
-  if (!b->ev_boot) HIPCHK(hipEventCreateWithFlags(&b->ev_boot, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(b->ev_boot));   // the previous pass has read its rows and left the outputs
   b->boot_made = 0;
   const size_t cw = nv * (size_t)(n_win + 2) * BOOT_COLS, rw = nv * (size_t)n_rep * BOOT_COLS;
-  int rc = b->d_bcnt.grow((int64_t)std::max<size_t>(cw, 1), &b->dev_bytes);
+  rc = b->d_bcnt.grow((int64_t)std::max<size_t>(cw, 1), &b->dev_bytes);
   if (rc == QM_OK && n_rep) rc = b->d_brep.grow((int64_t)std::max<size_t>(rw, 1), &b->dev_bytes);
   if (rc == QM_OK && (what & QM_BOOT_TRUTH)) rc = b->d_brows.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
@@ -2489,9 +2524,8 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   NEED_FINISHED(b, "qm_batch_truth_hits");
   qm_ctx* c = b->ctx;
   if (b->ext) return fail(QM_E_STATE, "qm_batch_truth_hits: allele-extended batches have no truth-side bitmaps (single-base batches only)");
-  for (const auto& tg : b->truth_gens)
-    if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
-      return fail(QM_E_STATE, "qm_batch_truth_hits: truth set %d was released after the batch was created", tg.first);
+  int rc = truths_live(b, "qm_batch_truth_hits");
+  if (rc != QM_OK) return rc;
   HIPCHK(hipSetDevice(c->dev));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   const size_t nv = (size_t)b->n_vcf;
@@ -2509,7 +2543,8 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
   if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
   else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
-  int rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
+  // (the one pass that does not open with pass_stream: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
+  rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_intruth.grow((int64_t)mask_words, &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_hits.grow((int64_t)hw, &b->dev_bytes);
   if (rc != QM_OK) return rc;
@@ -2570,25 +2605,12 @@ extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* 
   std::vector<int64_t> uoff((size_t)n_groups + 1, 0);
   int64_t max_words = 0;
   for (int g = 0; g < n_groups; ++g) {
-    const int32_t o0 = group_offsets[g], o1 = group_offsets[g + 1];
-    if (o0 < 0 || o1 - o0 < 1 || o1 - o0 > TS_MAX_GROUP)
-      return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d has %d VCFs (1 to %d)", g, o1 - o0, TS_MAX_GROUP);
     TruthGroup& t = G[(size_t)g];
-    memset(&t, 0, sizeof t);
-    t.n = o1 - o0;
-    int truth = -1;
-    for (int i = 0; i < t.n; ++i) {
-      const int v = vcf_ids[o0 + i];
-      if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d names VCF %d (the batch has %d)", g, v, b->n_vcf);
-      for (int k = 0; k < i; ++k)
-        if (vcf_ids[o0 + k] == v) return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d names VCF %d twice", g, v);
-      const int tv = b->L.vcfs[(size_t)v].truth;
-      if (i == 0) truth = tv;
-      else if (tv != truth) return fail(QM_E_INVAL, "qm_batch_truth_regions: group %d mixes truth sets %d and %d", g, truth, tv);
-      t.bits[i] = b->d_hits + b->h_hit_off[(size_t)v];
-      t.words = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
-    }
-    t.tn = b->h_hit_tn[(size_t)vcf_ids[o0]];   // T' as it was when the bitmaps were sized (qm_batch_truth_hits checked the generations)
+    const int32_t* ids = vcf_ids + group_offsets[g];
+    const int rc = walk_hit_group(b, "qm_batch_truth_regions", g, group_offsets, vcf_ids, TS_MAX_GROUP, t, [&](int i, int v) {
+      return std::find(ids, ids + i, v) == ids + i ? QM_OK : fail(QM_E_INVAL, "qm_batch_truth_regions: group %d names VCF %d twice", g, v);
+    });
+    if (rc != QM_OK) return rc;
     uoff[(size_t)g + 1] = uoff[(size_t)g] + t.words;
     max_words = std::max(max_words, t.words);
   }
@@ -2620,12 +2642,10 @@ extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* 
 // k-of-n consensus over groups of the finished batch's VCFs
 extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, void* stream) {
   NEED_FINISHED(b, "qm_batch_votes");
-  qm_ctx* c = b->ctx;
   if (b->ext) return fail(QM_E_STATE, "qm_batch_votes: allele-extended batches have no truth-side bitmaps (single-base batches only)");
   if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_votes: needs a qm_batch_truth_hits behind the latest run");
-  for (const auto& tg : b->truth_gens)
-    if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
-      return fail(QM_E_STATE, "qm_batch_votes: truth set %d was released after the batch was created", tg.first);
+  int rc = truths_live(b, "qm_batch_votes");
+  if (rc != QM_OK) return rc;
   if (n_groups < 0 || (n_groups && (!group_offsets || !vcf_ids))) return fail(QM_E_INVAL, "qm_batch_votes: bad arguments");
   if (n_groups >= (1 << 23)) return fail(QM_E_LIMIT, "qm_batch_votes: %d groups", n_groups);
   const size_t nv = (size_t)b->n_vcf, ng = (size_t)n_groups;
@@ -2633,31 +2653,18 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   std::vector<VoteGroup> G(std::max<size_t>(ng, 1));
   int64_t max_words = 0;
   for (int g = 0; g < n_groups; ++g) {
-    const int32_t o0 = group_offsets[g], o1 = group_offsets[g + 1];
-    if (o0 < 0 || o1 - o0 < 1 || o1 - o0 > VT_MAX_GROUP)
-      return fail(QM_E_INVAL, "qm_batch_votes: group %d has %d VCFs (1 to %d)", g, o1 - o0, VT_MAX_GROUP);
     VoteGroup& t = G[(size_t)g];
-    memset(&t, 0, sizeof t);
-    t.n = o1 - o0;
-    int truth = -1;
-    for (int i = 0; i < t.n; ++i) {
-      const int v = vcf_ids[o0 + i];
-      if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_votes: group %d names VCF %d (the batch has %d)", g, v, b->n_vcf);
+    rc = walk_hit_group(b, "qm_batch_votes", g, group_offsets, vcf_ids, VT_MAX_GROUP, t, [&](int i, int v) {
       if (slot[(size_t)v] >= 0) return fail(QM_E_INVAL, "qm_batch_votes: VCF %d sits in groups %d and %d (at most one)", v, slot[(size_t)v] >> 8, g);
-      const int tv = b->L.vcfs[(size_t)v].truth;
-      if (i == 0) truth = tv;
-      else if (tv != truth) return fail(QM_E_INVAL, "qm_batch_votes: group %d mixes truth sets %d and %d", g, truth, tv);
       slot[(size_t)v] = (int32_t)(((uint32_t)g << 8) | (uint32_t)i);
-      t.bits[i] = b->d_hits + b->h_hit_off[(size_t)v];
-      t.words = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
-    }
-    t.tn = b->h_hit_tn[(size_t)vcf_ids[o0]];   // T' as it was when the bitmaps were sized
+      return (int)QM_OK;
+    });
+    if (rc != QM_OK) return rc;
     max_words = std::max(max_words, t.words);
   }
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  if (!b->ev_votes) HIPCHK(hipEventCreateWithFlags(&b->ev_votes, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(b->ev_votes));   // the previous pass has read its tables and left the outputs
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_votes, &st);
+  if (rc != QM_OK) return rc;
   // a group's segment of the pair buffers holds its members' kept lines: the finished n_pass scalars bound the pairs from above
   std::vector<int64_t> sc(std::max<size_t>(nv, 1) * QM_N_SCALARS, 0);
   if (nv) HIPCHK(hipMemcpy(sc.data(), b->scalars, nv * QM_N_SCALARS * 8, hipMemcpyDeviceToHost));
@@ -2678,7 +2685,6 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   }
   const int64_t nst = (int64_t)tile_seg.size();
   const size_t out_words = ng * (2 * VT_SLOTS + 2 * VT_MAX_GROUP + 1);
-  int rc = QM_OK;
   for (int i = 0; i < 2 && rc == QM_OK; ++i) {   // the sort kernels read whole 16-byte pieces
     rc = b->vt_k[i].grow(koff + 64, &b->dev_bytes);
     if (rc == QM_OK) rc = b->vt_v[i].grow(koff + 64, &b->dev_bytes);

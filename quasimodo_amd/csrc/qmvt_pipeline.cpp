@@ -264,100 +264,278 @@ void qm_pipeline_ctx_destroyed(qm_ctx* ctx) {
   if (a) { { std::lock_guard<std::mutex> g(a->mu); a->arena.release(); } delete a; }
 }
 
-// ---- k-of-n consensus over groups of jobs (DESIGN.md 4.12) ----
-// The vote pass of the finished batch, the tables of every group, and for the groups that name a level k their consensus VCF: the
-// '#' lines of the first member as its filtered file holds them, then one line per key with votes >= k in ascending key order --
-// the votes from the device (hit bitmaps for the truth keys, the distinct keys and masks for the others), the line from the host:
-// the first kept line carrying the key in the lowest-numbered member that calls it, byte for byte.  Atomic.
-static int votes_pass(qm_ctx* ctx, qm_batch* batch, int n_jobs, const qm_file_job* jobs, const std::vector<JobState>& J, const std::vector<TruthState>& T,
-                      const qm_votes_args* va, std::string& err) {
-  auto is_header = [](uint8_t k) { return k == QM_LINE_HEADER || k == QM_LINE_HEADER_KEPT || k == QM_LINE_HEADER_KEPT_TP || k == QM_LINE_HEADER_REFUSED; };
-  // a kept line without a comparable key has a text key the bitmaps cannot hold: refuse the member by name (as DESIGN.md 4.8 does)
-  for (int j = 0; j < n_jobs; ++j) {
-    const JobState& s = J[(size_t)j];
-    if (va->group[j] < 0 || s.info.n_nokey_kept == 0) continue;
-    int64_t line = 0, rec = 0;
-    for (int64_t i = 0; i < s.info.n_lines && !line; ++i) {
-      if (is_header(s.line_kind[(size_t)i])) continue;
-      if ((s.flags[rec] & QM_F_PASS) && (s.flags[rec] & QM_F_NOKEY)) line = i + 1;
-      ++rec;
-    }
-    err = std::string(jobs[j].vcf_path) + " line " + std::to_string(line) + ": a kept line has no comparable key (POS is not a canonical decimal) -- "
-          "the vote pass compares keys, not text, and does not take this VCF";
-    return QM_E_NONCANON;
+namespace {
+
+// ---- the passes over the finished batch of one call (how a pass is wired) ----
+// What a call was asked for beyond the three files: every qm_extract_files_* wrapper fills the fields of its pass.
+struct Passes {
+  const int32_t* genome_id = nullptr;   // the motif pass: a genome id or -1 per job, with motifs_out
+  uint64_t* motifs_out = nullptr;
+  const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
+  const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr;
+  bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
+  bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
+  bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
+  bool wants_boot(int j) const { return ba && ba->want[j] != 0; }
+  // the passes a pure-strain job joins the batch for (against an empty truth set, for its rows of the pass only: its files,
+  // stats and ROC rows are made as for any pure-strain job); every mixed-sample job is in the batch anyway
+  bool any_batch_only(int j) const { return has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j); }
+};
+
+// what a pass sees of the call: the finished batch and the jobs behind its VCFs
+struct PassCtx {
+  qm_ctx* ctx; qm_batch* batch; int n_jobs; const qm_file_job* jobs;
+  const std::vector<JobState>& J; const std::vector<TruthState>& T;
+  size_t nv;   // VCFs in the batch
+  bool ext; int nthr;
+  // the one rule for errors: a pass that fails sets err
+  int lib(int rc, std::string& err) const { if (rc != QM_OK) err = qm_last_error(ctx); return rc; }
+  template <typename W> bool any(W want) const { for (int j = 0; j < n_jobs; ++j) if (want(j)) return true; return false; }
+  // the batch's row of every wanted job (src, one row of w words per VCF of the batch) into the job's row of the caller's array
+  template <typename W> void scatter_rows(uint64_t* dst, const std::vector<uint64_t>& src, size_t w, W want) const {
+    for (int j = 0; j < n_jobs && w; ++j)
+      if (want(j)) memcpy(dst + (size_t)j * w, &src[(size_t)J[(size_t)j].batch_v * w], sizeof(uint64_t) * w);
   }
-  const int ng = va->n_groups;
-  std::vector<std::vector<int>> members((size_t)ng);
-  for (int j = 0; j < n_jobs; ++j) if (va->group[j] >= 0) members[(size_t)va->group[j]].push_back(j);
-  std::vector<int32_t> goff(1, 0), gids;
-  for (const auto& m : members) {
-    for (int j : m) gids.push_back(J[(size_t)j].batch_v);
-    goff.push_back((int32_t)gids.size());
+  const TruthState& truth_of(int j) const { return T[(size_t)J[(size_t)j].truth]; }
+};
+
+bool is_header(uint8_t k) { return k == QM_LINE_HEADER || k == QM_LINE_HEADER_KEPT || k == QM_LINE_HEADER_KEPT_TP || k == QM_LINE_HEADER_REFUSED; }
+
+// the first kept line (1-based) without a comparable key, 0 when there is none
+int64_t first_nokey_kept_line(const JobState& s) {
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    if ((s.flags[rec] & QM_F_PASS) && (s.flags[rec] & QM_F_NOKEY)) return i + 1;
+    ++rec;
   }
-  int rc = qm_batch_truth_hits(batch, nullptr);
-  if (rc == QM_OK) rc = qm_batch_votes(batch, ng, goff.data(), gids.data(), nullptr);
-  if (rc == QM_OK) rc = qm_batch_get_votes(batch, va->tp_votes, va->fp_votes, va->private_tp, va->private_fp, nullptr);
-  if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
-  for (int g = 0; g < ng; ++g) {
-    const int k = va->consensus_k ? va->consensus_k[g] : 0;
-    if (k <= 0) continue;
-    const std::vector<int>& m = members[(size_t)g];
-    const TruthState& t = T[(size_t)J[(size_t)m[0]].truth];
-    // votes: the truth keys from the members' hit bitmaps, the others from the pass's distinct keys and masks
-    std::vector<uint32_t> want;
-    {
-      const size_t nw = (t.keys.size() + 31) / 32;
-      std::vector<uint8_t> cnt(t.keys.size(), 0);
-      std::vector<uint32_t> bits(nw + 1, 0u);
-      for (int j : m) {
-        rc = qm_batch_get_truth_hits(batch, J[(size_t)j].batch_v, bits.data(), (int64_t)nw);
-        if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
-        for (size_t i = 0; i < t.keys.size(); ++i) cnt[i] += (uint8_t)((bits[i >> 5] >> (i & 31)) & 1u);
-      }
-      for (size_t i = 0; i < t.keys.size(); ++i) if ((int)cnt[i] >= k) want.push_back(t.keys[i]);
-      int64_t nu = 0;
-      rc = qm_batch_get_vote_keys(batch, g, nullptr, nullptr, 0, &nu);
-      std::vector<uint32_t> uk((size_t)nu + 1), um((size_t)nu + 1);
-      if (rc == QM_OK) rc = qm_batch_get_vote_keys(batch, g, uk.data(), um.data(), nu, &nu);
-      if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
-      for (int64_t i = 0; i < nu; ++i) if (__builtin_popcount(um[(size_t)i]) >= k) want.push_back(uk[(size_t)i]);
-      std::sort(want.begin(), want.end());
-    }
-    // lines: the first kept line of every key in the lowest-numbered member that carries it
-    std::unordered_map<uint32_t, std::pair<int, int64_t>> first;   // key -> (member, line)
-    for (size_t mi = 0; mi < m.size(); ++mi) {
-      const JobState& s = J[(size_t)m[mi]];
-      std::vector<uint64_t> kept((size_t)(s.n_data + 63) / 64 + 1), tpm(kept.size());
-      rc = qm_batch_get_masks(batch, s.batch_v, kept.data(), tpm.data());
-      if (rc != QM_OK) { err = qm_last_error(ctx); return rc; }
-      int64_t rec = 0;
-      for (int64_t i = 0; i < s.info.n_lines; ++i) {
-        if (is_header(s.line_kind[(size_t)i])) continue;
-        const int64_t r = rec++;
-        if (!((kept[(size_t)r >> 6] >> (r & 63)) & 1ull) || (s.flags[r] & QM_F_NOKEY) || (uint32_t)(s.ref[r] | s.alt[r]) >= 4u) continue;
-        first.emplace(((uint32_t)s.pos[r] << 4) | ((uint32_t)s.ref[r] << 2) | (uint32_t)s.alt[r], std::make_pair((int)mi, i));
-      }
-    }
-    std::string out;
-    auto put = [&](const JobState& s, int64_t i) {
-      const int64_t a = s.line_off[(size_t)i], b = (i + 1 < s.info.n_lines) ? s.line_off[(size_t)i + 1] : (int64_t)s.vcf.n;
-      out.append((const char*)s.vcf.p + a, (size_t)(b - a));
-      if (out.empty() || out.back() != '\n') out.push_back('\n');
-    };
-    const JobState& s0 = J[(size_t)m[0]];
-    for (int64_t i = 0; i < s0.info.n_lines; ++i) if (is_header(s0.line_kind[(size_t)i])) put(s0, i);
-    for (int64_t i = 0; i < s0.info.n_lines; ++i)   // '#' lines the filter keeps stand among the kept lines of the filtered file once more
-      if (s0.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT || s0.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT_TP) put(s0, i);
-    for (uint32_t key : want) {
-      const auto it = first.find(key);
-      if (it == first.end()) { err = std::string(va->consensus_out[g]) + ": key " + std::to_string(key) + " has votes and no kept line"; return QM_E_STATE; }
-      put(J[(size_t)m[(size_t)it->second.first]], it->second.second);
-    }
-    rc = write_all_atomic(va->consensus_out[g], out);
-    if (rc != QM_OK) { err = std::string("cannot write ") + va->consensus_out[g]; return rc; }
+  return 0;
+}
+// R keys a kept line by its TEXT; a kept line without a comparable key has none the hit bitmaps could hold: the passes that read
+// them refuse the VCF by name (`pass`: "the vote pass", "the truth-side view")
+int refuse_nokey(const char* vcf_path, const JobState& s, const char* pass, std::string& err) {
+  err = std::string(vcf_path) + " line " + std::to_string(first_nokey_kept_line(s)) + ": a kept line has no comparable key (POS is not a canonical decimal) -- " +
+        pass + " compares keys, not text, and does not take this VCF";
+  return QM_E_NONCANON;
+}
+
+// the jobs of every group, and the same as the offsets and batch VCF ids qm_batch_truth_regions / qm_batch_votes take
+struct GroupTables { std::vector<std::vector<int>> members; std::vector<int32_t> goff, gids; };
+GroupTables group_tables(const PassCtx& c, const int32_t* group, int n_groups) {
+  GroupTables g;
+  g.members.resize((size_t)n_groups);
+  for (int j = 0; j < c.n_jobs; ++j) if (group[j] >= 0) g.members[(size_t)group[j]].push_back(j);
+  g.goff.push_back(0);
+  for (const auto& m : g.members) {
+    for (int j : m) g.gids.push_back(c.J[(size_t)j].batch_v);
+    g.goff.push_back((int32_t)g.gids.size());
   }
+  return g;
+}
+
+// the mutation-context spectra, on the columns and masks still in HBM
+int motifs_pass(const PassCtx& c, const Passes& P, std::string& err) {
+  auto want = [&](int j) { return P.has_genome(j); };
+  if (!P.motifs_out || !c.any(want)) return QM_OK;
+  std::vector<int32_t> gid(c.nv, -1);
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) gid[(size_t)c.J[(size_t)j].batch_v] = P.genome_id[j];
+  std::vector<uint64_t> mo(c.nv * 3 * QM_MOTIF_COLS);
+  int rc = qm_batch_motifs(c.batch, gid.data(), nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_motifs(c.batch, mo.data());
+  if (rc == QM_OK) c.scatter_rows(P.motifs_out, mo, 3 * QM_MOTIF_COLS, want);
+  return c.lib(rc, err);
+}
+
+// the allele-frequency profile, behind the motif pass on the same columns and masks
+int profile_pass(const PassCtx& c, const qm_profile_args* pa, std::string& err) {
+  auto want = [&](int j) { return pa->want[j] != 0; };
+  if (!pa || !c.any(want)) return QM_OK;
+  const size_t cells = (size_t)pa->n_pos_bins * (size_t)pa->n_af_bins;
+  std::vector<uint64_t> gr(c.nv * 2 * cells), ex(c.nv * 2 * QM_AFP_EXTRA);
+  int rc = qm_batch_af_profile(c.batch, pa->window, pa->n_pos_bins, pa->n_af_bins, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_af_profile(c.batch, gr.data(), ex.data());
+  if (rc == QM_OK) { c.scatter_rows(pa->grid, gr, 2 * cells, want); c.scatter_rows(pa->extra, ex, 2 * QM_AFP_EXTRA, want); }
+  return c.lib(rc, err);
+}
+
+// the counts per stratum, on the columns, masks and truth keys still in HBM
+int strata_pass(const PassCtx& c, const qm_strata_args* sa, std::string& err) {
+  auto want = [&](int j) { return sa->want[j] != 0; };
+  if (!sa || !c.any(want)) return QM_OK;
+  int64_t si[2] = {0, 0};
+  int rc = qm_strata_info(c.ctx, sa->strata_id, si);
+  const size_t rw = 3 * (size_t)(si[0] + 2), tw = 2 * (size_t)(si[0] + 1);
+  std::vector<uint64_t> rec(c.nv * rw), tru(c.nv * tw);
+  if (rc == QM_OK && !c.ext) rc = qm_batch_truth_hits(c.batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_strata(c.batch, sa->strata_id, c.ext ? QM_STRATA_RECORDS : (QM_STRATA_RECORDS | QM_STRATA_TRUTH), nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_strata(c.batch, rec.data(), c.ext ? nullptr : tru.data());
+  if (rc == QM_OK) { c.scatter_rows(sa->rec, rec, rw, want); if (!c.ext) c.scatter_rows(sa->tru, tru, tw, want); }
+  return c.lib(rc, err);
+}
+
+// the bootstrap replicates, on the columns, masks and truth keys still in HBM
+int boot_pass(const PassCtx& c, const qm_boot_args* ba, std::string& err) {
+  auto want = [&](int j) { return ba->want[j] != 0; };
+  if (!ba || !c.any(want)) return QM_OK;
+  const size_t cw = 4 * (size_t)(ba->n_win + 2), rw = 4 * (size_t)ba->n_rep;
+  std::vector<uint64_t> cnt(c.nv * cw), rep(c.nv * rw);
+  int rc = c.ext ? QM_OK : qm_batch_truth_hits(c.batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_boot(c.batch, ba->window, ba->n_win, ba->n_rep, ba->seed, c.ext ? QM_BOOT_RECORDS : (QM_BOOT_RECORDS | QM_BOOT_TRUTH), nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_boot(c.batch, cnt.data(), rw ? rep.data() : nullptr);
+  if (rc == QM_OK) { c.scatter_rows(ba->cnt, cnt, cw, want); c.scatter_rows(ba->rep, rep, rw, want); }
+  return c.lib(rc, err);
+}
+
+// the callers' side of one group's Venn: the keys of the members' kept records outside the in-truth record mask, through qm_fp_overlap
+int fp_regions_of(const PassCtx& c, const std::vector<int>& members, int64_t* out, std::string& err) {
+  std::vector<int64_t> so(1, 0);
+  std::vector<int32_t> kp, kr, ka;
+  for (int j : members) {
+    const JobState& s = c.J[(size_t)j];
+    std::vector<uint64_t> kept((size_t)(s.n_data + 63) / 64 + 1), tpm(kept.size()), in(kept.size());
+    int rc = qm_batch_get_masks(c.batch, s.batch_v, kept.data(), tpm.data());
+    if (rc == QM_OK) rc = qm_batch_get_intruth_mask(c.batch, s.batch_v, in.data());
+    if (rc != QM_OK) return c.lib(rc, err);
+    for (int64_t r = 0; r < s.n_data; ++r)
+      if (((kept[(size_t)r >> 6] & ~in[(size_t)r >> 6]) >> (r & 63)) & 1ull) { kp.push_back(s.pos[r]); kr.push_back(s.ref[r]); ka.push_back(s.alt[r]); }
+    so.push_back((int64_t)kp.size());
+  }
+  int64_t reg[QM_TRUTH_REGIONS] = {0};
+  int32_t dummy = 0;
+  const int rc = qm_fp_overlap(c.ctx, (int)members.size(), so.data(), kp.empty() ? &dummy : kp.data(), kr.empty() ? &dummy : kr.data(),
+                               ka.empty() ? &dummy : ka.data(), reg);
+  if (rc == QM_OK) memcpy(out, reg, sizeof reg);
+  return c.lib(rc, err);
+}
+
+// the truth-side view: the missed-variant lists of the jobs, the Venn regions and missed-by-all lists of the groups
+int truthside_pass(const PassCtx& c, const qm_truthside_args* ts, std::string& err) {
+  if (!ts) return QM_OK;
+  auto listed = [&](int j) { return !c.jobs[j].pure && ts->fn_out[j]; };
+  for (int j = 0; j < c.n_jobs; ++j)
+    if (!c.jobs[j].pure && (ts->fn_out[j] || ts->group[j] >= 0) && c.J[(size_t)j].info.n_nokey_kept)
+      return refuse_nokey(c.jobs[j].vcf_path, c.J[(size_t)j], "the truth-side view", err);
+  int rc = qm_batch_truth_hits(c.batch, nullptr);
+  std::vector<std::vector<uint32_t>> hitbits((size_t)c.n_jobs), unibits((size_t)ts->n_groups);
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    if (!listed(j)) continue;
+    hitbits[(size_t)j].assign((c.truth_of(j).keys.size() + 31) / 32, 0u);
+    rc = qm_batch_get_truth_hits(c.batch, c.J[(size_t)j].batch_v, hitbits[(size_t)j].data(), (int64_t)hitbits[(size_t)j].size());
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  const GroupTables G = group_tables(c, ts->group, ts->n_groups);
+  if (ts->n_groups > 0) {
+    auto words_of = [&](size_t g) { return (c.truth_of(G.members[g][0]).keys.size() + 31) / 32; };
+    size_t uw = 0;
+    for (size_t g = 0; g < G.members.size(); ++g) uw += words_of(g);
+    std::vector<uint32_t> uni(uw + 1, 0u);
+    rc = qm_batch_truth_regions(c.batch, ts->n_groups, G.goff.data(), G.gids.data(), ts->regions, uni.data());
+    if (rc != QM_OK) return c.lib(rc, err);
+    size_t o = 0;
+    for (size_t g = 0; g < G.members.size(); ++g) {
+      unibits[g].assign(uni.begin() + (long)o, uni.begin() + (long)(o + words_of(g)));
+      o += words_of(g);
+    }
+    for (size_t g = 0; g < G.members.size() && ts->fp_regions; ++g) {
+      rc = fp_regions_of(c, G.members[g], ts->fp_regions + g * QM_TRUTH_REGIONS, err);
+      if (rc != QM_OK) return rc;
+    }
+  }
+  // the lists: one per job that asked, one per group that asked (missed by every member)
+  struct FTask { const char* path; const TruthState* t; const uint32_t* bits; };
+  std::vector<FTask> F;
+  for (int j = 0; j < c.n_jobs; ++j)
+    if (listed(j)) F.push_back({ts->fn_out[j], &c.truth_of(j), hitbits[(size_t)j].data()});
+  for (size_t g = 0; g < G.members.size(); ++g)
+    if (ts->missed_out && ts->missed_out[g]) F.push_back({ts->missed_out[g], &c.truth_of(G.members[g][0]), unibits[g].data()});
+  std::vector<int> frc(F.size(), QM_OK);
+  parallel_for((int)F.size(), c.nthr, [&](int k) { frc[(size_t)k] = write_fn_file(F[(size_t)k].path, *F[(size_t)k].t, F[(size_t)k].bits); });
+  for (size_t k = 0; k < F.size(); ++k)
+    if (frc[k] != QM_OK) { err = std::string("cannot write ") + F[k].path; return frc[k]; }
   return QM_OK;
 }
+
+// ---- k-of-n consensus over groups of jobs (DESIGN.md 4.12) ----
+// The consensus VCF of one group at level k: the '#' lines of the first member as its filtered file holds them, then one line per
+// key with votes >= k in ascending key order -- the votes from the device (hit bitmaps for the truth keys, the distinct keys and
+// masks for the others), the line from the host: the first kept line carrying the key in the lowest-numbered member that calls
+// it, byte for byte.  Atomic.
+int write_consensus(const PassCtx& c, int g, const std::vector<int>& m, int k, const char* path, std::string& err) {
+  const TruthState& t = c.truth_of(m[0]);
+  int rc = QM_OK;
+  // votes: the truth keys from the members' hit bitmaps, the others from the pass's distinct keys and masks
+  std::vector<uint32_t> want;
+  {
+    const size_t nw = (t.keys.size() + 31) / 32;
+    std::vector<uint8_t> cnt(t.keys.size(), 0);
+    std::vector<uint32_t> bits(nw + 1, 0u);
+    for (int j : m) {
+      rc = qm_batch_get_truth_hits(c.batch, c.J[(size_t)j].batch_v, bits.data(), (int64_t)nw);
+      if (rc != QM_OK) return c.lib(rc, err);
+      for (size_t i = 0; i < t.keys.size(); ++i) cnt[i] += (uint8_t)((bits[i >> 5] >> (i & 31)) & 1u);
+    }
+    for (size_t i = 0; i < t.keys.size(); ++i) if ((int)cnt[i] >= k) want.push_back(t.keys[i]);
+    int64_t nu = 0;
+    rc = qm_batch_get_vote_keys(c.batch, g, nullptr, nullptr, 0, &nu);
+    std::vector<uint32_t> uk((size_t)nu + 1), um((size_t)nu + 1);
+    if (rc == QM_OK) rc = qm_batch_get_vote_keys(c.batch, g, uk.data(), um.data(), nu, &nu);
+    if (rc != QM_OK) return c.lib(rc, err);
+    for (int64_t i = 0; i < nu; ++i) if (__builtin_popcount(um[(size_t)i]) >= k) want.push_back(uk[(size_t)i]);
+    std::sort(want.begin(), want.end());
+  }
+  // lines: the first kept line of every key in the lowest-numbered member that carries it
+  std::unordered_map<uint32_t, std::pair<int, int64_t>> first;   // key -> (member, line)
+  for (size_t mi = 0; mi < m.size(); ++mi) {
+    const JobState& s = c.J[(size_t)m[mi]];
+    std::vector<uint64_t> kept((size_t)(s.n_data + 63) / 64 + 1), tpm(kept.size());
+    rc = qm_batch_get_masks(c.batch, s.batch_v, kept.data(), tpm.data());
+    if (rc != QM_OK) return c.lib(rc, err);
+    int64_t rec = 0;
+    for (int64_t i = 0; i < s.info.n_lines; ++i) {
+      if (is_header(s.line_kind[(size_t)i])) continue;
+      const int64_t r = rec++;
+      if (!((kept[(size_t)r >> 6] >> (r & 63)) & 1ull) || (s.flags[r] & QM_F_NOKEY) || (uint32_t)(s.ref[r] | s.alt[r]) >= 4u) continue;
+      first.emplace(((uint32_t)s.pos[r] << 4) | ((uint32_t)s.ref[r] << 2) | (uint32_t)s.alt[r], std::make_pair((int)mi, i));
+    }
+  }
+  std::string out;
+  auto put = [&](const JobState& s, int64_t i) {
+    const int64_t a = s.line_off[(size_t)i], b = (i + 1 < s.info.n_lines) ? s.line_off[(size_t)i + 1] : (int64_t)s.vcf.n;
+    out.append((const char*)s.vcf.p + a, (size_t)(b - a));
+    if (out.empty() || out.back() != '\n') out.push_back('\n');
+  };
+  const JobState& s0 = c.J[(size_t)m[0]];
+  for (int64_t i = 0; i < s0.info.n_lines; ++i) if (is_header(s0.line_kind[(size_t)i])) put(s0, i);
+  for (int64_t i = 0; i < s0.info.n_lines; ++i)   // '#' lines the filter keeps stand among the kept lines of the filtered file once more
+    if (s0.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT || s0.line_kind[(size_t)i] == QM_LINE_HEADER_KEPT_TP) put(s0, i);
+  for (uint32_t key : want) {
+    const auto it = first.find(key);
+    if (it == first.end()) { err = std::string(path) + ": key " + std::to_string(key) + " has votes and no kept line"; return QM_E_STATE; }
+    put(c.J[(size_t)m[(size_t)it->second.first]], it->second.second);
+  }
+  rc = write_all_atomic(path, out);
+  if (rc != QM_OK) err = std::string("cannot write ") + path;
+  return rc;
+}
+
+// the vote tables of every group, and the consensus VCF of the groups that name a level
+int votes_pass(const PassCtx& c, const qm_votes_args* va, std::string& err) {
+  if (!va || va->n_groups <= 0) return QM_OK;
+  for (int j = 0; j < c.n_jobs; ++j)
+    if (va->group[j] >= 0 && c.J[(size_t)j].info.n_nokey_kept) return refuse_nokey(c.jobs[j].vcf_path, c.J[(size_t)j], "the vote pass", err);
+  const GroupTables G = group_tables(c, va->group, va->n_groups);
+  int rc = qm_batch_truth_hits(c.batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_votes(c.batch, va->n_groups, G.goff.data(), G.gids.data(), nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_votes(c.batch, va->tp_votes, va->fp_votes, va->private_tp, va->private_fp, nullptr);
+  if (rc != QM_OK) return c.lib(rc, err);
+  for (int g = 0; g < va->n_groups && rc == QM_OK; ++g) {
+    const int k = va->consensus_k ? va->consensus_k[g] : 0;
+    if (k > 0) rc = write_consensus(c, g, G.members[(size_t)g], k, va->consensus_out[g], err);
+  }
+  return rc;
+}
+
+}  // namespace
 
 extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                 qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds) {
@@ -365,14 +543,13 @@ extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs
 }
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
-                         uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba,
-                         const qm_votes_args* va = nullptr);
+                         uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev, const Passes& P);
 
+// The entry points of the passes: validate, zero the outputs, fill the pass's fields of Passes, call.
 extern "C" int qm_extract_files_ex(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                    qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
                                    int n_slots, void* global_dev) {
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, Passes());
 }
 
 // rule mutationcontext behind the worker: the motif pass runs on the batch the classification leaves in HBM
@@ -381,7 +558,8 @@ extern "C" int qm_extract_files_motifs(qm_ctx* ctx, int n_jobs, const qm_file_jo
                                        int n_slots, void* global_dev, const int32_t* genome_id, uint64_t* motifs_out) {
   if (n_jobs > 0 && (!genome_id || !motifs_out)) return fail(QM_E_INVAL, "qm_extract_files_motifs: NULL genome ids or output");
   if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, nullptr, nullptr, nullptr);
+  Passes P; P.genome_id = genome_id; P.motifs_out = motifs_out;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
 // both halves of rule mutationcontext behind the worker: the spectra (optional) and the allele-frequency profile
@@ -401,7 +579,22 @@ extern "C" int qm_extract_files_profile(qm_ctx* ctx, int n_jobs, const qm_file_j
     memset(profile->extra, 0, sizeof(uint64_t) * 2 * QM_AFP_EXTRA * (size_t)n_jobs);
   }
   if (motifs_out) memset(motifs_out, 0, sizeof(uint64_t) * 3 * QM_MOTIF_COLS * (size_t)n_jobs);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, genome_id, motifs_out, nullptr, profile, nullptr, nullptr);
+  Passes P; P.genome_id = genome_id; P.motifs_out = motifs_out; P.pa = profile;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// the two group passes: every job names no group or one of the call's, none of them pure-strain, 1 to max_members jobs per group
+static int check_groups(const std::string& who, int n_jobs, const qm_file_job* jobs, const int32_t* group, int n_groups, int max_members) {
+  for (int j = 0; j < n_jobs; ++j) {
+    if (group[j] < -1 || group[j] >= n_groups) return fail(QM_E_INVAL, who + ": job " + std::to_string(j) + " names group " + std::to_string(group[j]));
+    if (jobs[j].pure && group[j] >= 0) return fail(QM_E_INVAL, who + ": pure-strain job " + std::to_string(j) + " cannot be in a group (its truth is never read)");
+  }
+  for (int g = 0; g < n_groups; ++g) {
+    const int members = (int)std::count(group, group + n_jobs, g);
+    if (members < 1 || members > max_members)
+      return fail(QM_E_INVAL, who + ": group " + std::to_string(g) + " has " + std::to_string(members) + " jobs (1 to " + std::to_string(max_members) + ")");
+  }
+  return QM_OK;
 }
 
 // the truth-side view behind the worker: missed-variant lists and the caller Venn regions of groups of jobs
@@ -411,19 +604,12 @@ extern "C" int qm_extract_files_truthside(qm_ctx* ctx, int n_jobs, const qm_file
   if (!ts || ts->n_groups < 0 || (n_jobs > 0 && (!ts->fn_out || !ts->group)) || (ts->n_groups > 0 && !ts->regions))
     return fail(QM_E_INVAL, "qm_extract_files_truthside: NULL arguments");
   if (mode & QM_BATCH_ALLELES) return fail(QM_E_STATE, "qm_extract_files_truthside: allele-extended batches have no truth-side view (single-base batches only)");
-  for (int g = 0; g < ts->n_groups; ++g) {
-    int members = 0;
-    for (int j = 0; j < n_jobs; ++j) members += ts->group[j] == g;
-    if (members < 1 || members > QM_TRUTH_GROUP_MAX)
-      return fail(QM_E_INVAL, "qm_extract_files_truthside: group " + std::to_string(g) + " has " + std::to_string(members) + " jobs (1 to 5)");
-  }
-  for (int j = 0; j < n_jobs; ++j) {
-    if (ts->group[j] < -1 || ts->group[j] >= ts->n_groups) return fail(QM_E_INVAL, "qm_extract_files_truthside: job " + std::to_string(j) + " names group " + std::to_string(ts->group[j]));
-    if (jobs[j].pure && ts->group[j] >= 0) return fail(QM_E_INVAL, "qm_extract_files_truthside: pure-strain job " + std::to_string(j) + " cannot be in a group (its truth is never read)");
-  }
+  const int rc = check_groups("qm_extract_files_truthside", n_jobs, jobs, ts->group, ts->n_groups, QM_TRUTH_GROUP_MAX);
+  if (rc != QM_OK) return rc;
   memset(ts->regions, 0, sizeof(uint64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
   if (ts->fp_regions) memset(ts->fp_regions, 0, sizeof(int64_t) * QM_TRUTH_REGIONS * (size_t)ts->n_groups);
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, ts, nullptr, nullptr, nullptr);
+  Passes P; P.ts = ts;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
 // the counts per stratum behind the worker
@@ -438,7 +624,8 @@ extern "C" int qm_extract_files_strata(qm_ctx* ctx, int n_jobs, const qm_file_jo
     memset(strata->rec, 0, sizeof(uint64_t) * 3 * (size_t)(info[0] + 2) * (size_t)n_jobs);
     memset(strata->tru, 0, sizeof(uint64_t) * 2 * (size_t)(info[0] + 1) * (size_t)n_jobs);
   }
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, strata, nullptr);
+  Passes P; P.sa = strata;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
 // the bootstrap pass behind the worker
@@ -453,7 +640,8 @@ extern "C" int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job*
     memset(boot->cnt, 0, sizeof(uint64_t) * 4 * (size_t)(boot->n_win + 2) * (size_t)n_jobs);
     if (boot->n_rep) memset(boot->rep, 0, sizeof(uint64_t) * 4 * (size_t)boot->n_rep * (size_t)n_jobs);
   }
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, boot);
+  Passes P; P.ba = boot;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
 // k-of-n caller consensus behind the worker: vote tables of groups of jobs, and a group's consensus VCF
@@ -464,15 +652,10 @@ extern "C" int qm_extract_files_votes(qm_ctx* ctx, int n_jobs, const qm_file_job
   if (!va || va->n_groups < 0 || (n_jobs > 0 && !va->group) || (va->n_groups > 0 && (!va->tp_votes || !va->fp_votes || !va->private_tp || !va->private_fp)))
     return fail(QM_E_INVAL, "qm_extract_files_votes: NULL arguments");
   if (mode & QM_BATCH_ALLELES) return fail(QM_E_STATE, "qm_extract_files_votes: allele-extended batches have no vote pass (single-base batches only)");
-  for (int j = 0; j < n_jobs; ++j) {
-    if (va->group[j] < -1 || va->group[j] >= va->n_groups) return fail(QM_E_INVAL, "qm_extract_files_votes: job " + std::to_string(j) + " names group " + std::to_string(va->group[j]));
-    if (jobs[j].pure && va->group[j] >= 0) return fail(QM_E_INVAL, "qm_extract_files_votes: pure-strain job " + std::to_string(j) + " cannot be in a group (its truth is never read)");
-  }
+  const int rc = check_groups("qm_extract_files_votes", n_jobs, jobs, va->group, va->n_groups, QM_VOTE_GROUP_MAX);
+  if (rc != QM_OK) return rc;
   for (int g = 0; g < va->n_groups; ++g) {
-    int members = 0;
-    for (int j = 0; j < n_jobs; ++j) members += va->group[j] == g;
-    if (members < 1 || members > QM_VOTE_GROUP_MAX)
-      return fail(QM_E_INVAL, "qm_extract_files_votes: group " + std::to_string(g) + " has " + std::to_string(members) + " jobs (1 to " + std::to_string(QM_VOTE_GROUP_MAX) + ")");
+    const int members = (int)std::count(va->group, va->group + n_jobs, g);
     const int k = va->consensus_k ? va->consensus_k[g] : 0;
     if (k < 0 || k > members) return fail(QM_E_INVAL, "qm_extract_files_votes: group " + std::to_string(g) + ": consensus level " + std::to_string(k) + " with " + std::to_string(members) + " members");
     if (k > 0 && (!va->consensus_out || !va->consensus_out[g])) return fail(QM_E_INVAL, "qm_extract_files_votes: group " + std::to_string(g) + " names a consensus level and no file");
@@ -483,13 +666,12 @@ extern "C" int qm_extract_files_votes(qm_ctx* ctx, int n_jobs, const qm_file_job
     memset(va->private_tp, 0, sizeof(uint64_t) * QM_VOTE_GROUP_MAX * (size_t)va->n_groups);
     memset(va->private_fp, 0, sizeof(uint64_t) * QM_VOTE_GROUP_MAX * (size_t)va->n_groups);
   }
-  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, va);
+  Passes P; P.va = va;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
-                         uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev,
-                         const int32_t* genome_id, uint64_t* motifs_out, const qm_truthside_args* ts, const qm_profile_args* pa, const qm_strata_args* sa, const qm_boot_args* ba,
-                         const qm_votes_args* va) {
+                         uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev, const Passes& P) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
     return fail(QM_E_INVAL, "qm_extract_files: bad arguments");
   if (global_dev && (n_slots < 1 || (n_jobs && !truth_slot))) return fail(QM_E_INVAL, "qm_extract_files_ex: global_dev needs truth_slot and n_slots >= 1");
@@ -516,13 +698,6 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
   }
   qm_dict* dict = ext ? qm_dict_create() : nullptr;
   std::vector<TruthState> T;
-  // which jobs the batch holds: every mixed-sample job, and the pure-strain jobs that name a genome or want a profile (against an
-  // empty truth set, for their motif / profile rows only: their files, stats and ROC rows are made as for any pure-strain job)
-  auto has_genome = [&](int j) { return genome_id && genome_id[j] >= 0; };
-  auto wants_profile = [&](int j) { return pa && pa->want[j] != 0; };
-  auto wants_strata = [&](int j) { return sa && sa->want[j] != 0; };
-  auto wants_boot = [&](int j) { return ba && ba->want[j] != 0; };
-  auto in_batch = [&](int j) { return !jobs[j].pure || has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j); };
   int empty_tid = -1;
 
   // ---- the VCFs go through as ONE batch: stage one (map, count, tokenise, upload) of every VCF, then stage two (engine,
@@ -602,7 +777,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (k < 0) { truth_rc = (int)k; truth_msg = "qm_truth_scan failed for " + t.path; break; }
       const int rc = qm_truth_load(ctx, tp.data(), tr.data(), ta.data(), k, &t.tid);
       if (rc != QM_OK) { truth_rc = rc; truth_msg = qm_last_error(ctx); break; }
-      if (ts || va) {
+      if (P.ts || P.va) {
         for (int64_t i = 0; i < k; ++i)
           if ((uint32_t)(tr[(size_t)i] | ta[(size_t)i]) < 4u) t.keys.push_back(((uint32_t)tp[(size_t)i] << 4) | ((uint32_t)tr[(size_t)i] << 2) | (uint32_t)ta[(size_t)i]);
         std::sort(t.keys.begin(), t.keys.end());
@@ -636,16 +811,16 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (J[(size_t)j].rc != QM_OK) return fail(QM_E_IO, std::string("cannot read ") + jobs[j].vcf_path);
     if (truth_rc != QM_OK) return fail(truth_rc, truth_msg);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
-    for (int j = 0; j < n_jobs; ++j)
-      if (jobs[j].pure && in_batch(j) && empty_tid < 0) {
+    // the batch holds every mixed-sample job, and the pure-strain jobs a pass wants (against an empty truth set)
+    for (int j = 0; j < n_jobs; ++j) {
+      if (jobs[j].pure && !P.any_batch_only(j)) continue;
+      if (jobs[j].pure && empty_tid < 0) {
         const int rc = qm_truth_load(ctx, nullptr, nullptr, nullptr, 0, &empty_tid);
         if (rc != QM_OK) return rc;
       }
-    for (int j = 0; j < n_jobs; ++j)
-      if (in_batch(j)) {
-        J[(size_t)j].batch_v = (int)nrec.size(); nrec.push_back(J[(size_t)j].n_data);
-        tids.push_back(jobs[j].pure ? empty_tid : T[(size_t)J[(size_t)j].truth].tid);
-      }
+      J[(size_t)j].batch_v = (int)nrec.size(); nrec.push_back(J[(size_t)j].n_data);
+      tids.push_back(jobs[j].pure ? empty_tid : T[(size_t)J[(size_t)j].truth].tid);
+    }
     if (!nrec.empty()) {
       const int rc = qm_batch_create_ext(ctx, (int)nrec.size(), nrec.data(), tids.data(), n_bins, mode, &batch);
       if (rc != QM_OK) return rc;
@@ -679,7 +854,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
         if (s.rc == QM_OK) s.rc = QM_E_INVAL;
         return;
       }
-      if (wants_profile(j)) {   // the INFO column, by a scanner of its own
+      if (P.wants_profile(j)) {   // the INFO column, by a scanner of its own
         int64_t ai[2];
         s.af.resize((size_t)s.n_data + 1);
         s.rc = qm_vcf_scan_af(s.vcf.p, s.vcf.n, s.info.n_lines, s.line_off.data(), s.line_kind.data(), s.af.data(), ai);
@@ -687,12 +862,12 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       }
       // the frequencies follow the columns (whose upload clears the VCF's mark); a blocking copy of this VCF's floats
       auto upload_af = [&]() {
-        if (s.rc != QM_OK || !wants_profile(j)) return;
+        if (s.rc != QM_OK || !P.wants_profile(j)) return;
         s.rc = qm_batch_upload_af(batch, s.batch_v, s.af.data());
         if (s.rc != QM_OK) s.err = qm_last_error(ctx);
       };
       if (jobs[j].pure) {
-        if (in_batch(j) && !(strict && s.info.n_refused)) {
+        if (s.batch_v >= 0 && !(strict && s.info.n_refused)) {
           s.rc = qm_batch_upload_async(batch, s.batch_v, s.pos, s.ref, s.alt, s.qual, s.flags, copy_stream);
           if (s.rc != QM_OK) s.err = qm_last_error(ctx);
           upload_af();
@@ -754,163 +929,21 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
           rc = qm_device_add_u64(ctx, (uint64_t*)global_dev + (size_t)slot_of_truth[k] * roww, (const uint64_t*)src + (size_t)T[k].tid * roww, (int64_t)roww);
         }
       }
-      if (rc == QM_OK && motifs_out) {   // the motif pass behind the classification, on the columns and masks still in HBM
-        std::vector<int32_t> gid(nrec.size(), -1);
-        bool any = false;
-        for (int j = 0; j < n_jobs; ++j)
-          if (in_batch(j) && has_genome(j)) { gid[(size_t)J[(size_t)j].batch_v] = genome_id[j]; any = true; }
-        if (any) {
-          std::vector<uint64_t> mo(nrec.size() * 3 * QM_MOTIF_COLS);
-          rc = qm_batch_motifs(batch, gid.data(), nullptr);
-          if (rc == QM_OK) rc = qm_batch_get_motifs(batch, mo.data());
-          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
-            if (in_batch(j) && has_genome(j))
-              memcpy(motifs_out + (size_t)j * 3 * QM_MOTIF_COLS, &mo[(size_t)J[(size_t)j].batch_v * 3 * QM_MOTIF_COLS], sizeof(uint64_t) * 3 * QM_MOTIF_COLS);
-        }
-      }
-      if (rc == QM_OK && pa) {   // the profile pass behind the motif pass, on the same columns and masks
-        bool any = false;
-        for (int j = 0; j < n_jobs; ++j) any = any || wants_profile(j);
-        if (any) {
-          const size_t cells = (size_t)pa->n_pos_bins * (size_t)pa->n_af_bins;
-          std::vector<uint64_t> gr(nrec.size() * 2 * cells), exx(nrec.size() * 2 * QM_AFP_EXTRA);
-          rc = qm_batch_af_profile(batch, pa->window, pa->n_pos_bins, pa->n_af_bins, nullptr);
-          if (rc == QM_OK) rc = qm_batch_get_af_profile(batch, gr.data(), exx.data());
-          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
-            if (wants_profile(j)) {
-              memcpy(pa->grid + (size_t)j * 2 * cells, &gr[(size_t)J[(size_t)j].batch_v * 2 * cells], sizeof(uint64_t) * 2 * cells);
-              memcpy(pa->extra + (size_t)j * 2 * QM_AFP_EXTRA, &exx[(size_t)J[(size_t)j].batch_v * 2 * QM_AFP_EXTRA], sizeof(uint64_t) * 2 * QM_AFP_EXTRA);
-            }
-        }
-      }
-      if (rc == QM_OK && sa) {   // the counts per stratum behind the classification, on the columns, masks and truth keys still in HBM
-        bool any = false;
-        for (int j = 0; j < n_jobs; ++j) any = any || wants_strata(j);
-        int64_t si[2] = {0, 0};
-        if (any) rc = qm_strata_info(ctx, sa->strata_id, si);
-        if (any && rc == QM_OK) {
-          const size_t rw = 3 * (size_t)(si[0] + 2), tw = 2 * (size_t)(si[0] + 1);
-          std::vector<uint64_t> rec(nrec.size() * rw), tru(nrec.size() * tw);
-          if (!ext) rc = qm_batch_truth_hits(batch, nullptr);
-          if (rc == QM_OK) rc = qm_batch_strata(batch, sa->strata_id, ext ? QM_STRATA_RECORDS : (QM_STRATA_RECORDS | QM_STRATA_TRUTH), nullptr);
-          if (rc == QM_OK) rc = qm_batch_get_strata(batch, rec.data(), ext ? nullptr : tru.data());
-          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
-            if (wants_strata(j)) {
-              memcpy(sa->rec + (size_t)j * rw, &rec[(size_t)J[(size_t)j].batch_v * rw], sizeof(uint64_t) * rw);
-              if (!ext) memcpy(sa->tru + (size_t)j * tw, &tru[(size_t)J[(size_t)j].batch_v * tw], sizeof(uint64_t) * tw);
-            }
-        }
-        if (rc != QM_OK) err = qm_last_error(ctx);
-      }
-      if (rc == QM_OK && ba) {   // the bootstrap pass behind the classification, on the columns, masks and truth keys still in HBM
-        bool any = false;
-        for (int j = 0; j < n_jobs; ++j) any = any || wants_boot(j);
-        if (any) {
-          const size_t cw = 4 * (size_t)(ba->n_win + 2), rw = 4 * (size_t)ba->n_rep;
-          std::vector<uint64_t> cnt(nrec.size() * cw), rep(nrec.size() * rw);
-          if (!ext) rc = qm_batch_truth_hits(batch, nullptr);
-          if (rc == QM_OK) rc = qm_batch_boot(batch, ba->window, ba->n_win, ba->n_rep, ba->seed, ext ? QM_BOOT_RECORDS : (QM_BOOT_RECORDS | QM_BOOT_TRUTH), nullptr);
-          if (rc == QM_OK) rc = qm_batch_get_boot(batch, cnt.data(), rw ? rep.data() : nullptr);
-          for (int j = 0; j < n_jobs && rc == QM_OK; ++j)
-            if (wants_boot(j)) {
-              memcpy(ba->cnt + (size_t)j * cw, &cnt[(size_t)J[(size_t)j].batch_v * cw], sizeof(uint64_t) * cw);
-              if (rw) memcpy(ba->rep + (size_t)j * rw, &rep[(size_t)J[(size_t)j].batch_v * rw], sizeof(uint64_t) * rw);
-            }
-        }
-        if (rc != QM_OK) err = qm_last_error(ctx);
-      }
-      std::vector<std::vector<uint32_t>> hitbits, unibits;
-      std::vector<std::vector<int>> members;
-      if (rc == QM_OK && ts) {   // the truth-side pass behind the classification, on the columns and masks still in HBM
-        // R keys a kept line by its TEXT; a kept line without a comparable key has none the bitmaps could hold: refuse it by name
-        for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
-          const JobState& s = J[(size_t)j];
-          if (jobs[j].pure || (!ts->fn_out[j] && ts->group[j] < 0) || s.info.n_nokey_kept == 0) continue;
-          int64_t line = 0, rec = 0;
-          for (int64_t i = 0; i < s.info.n_lines && !line; ++i) {
-            const uint8_t k = s.line_kind[(size_t)i];
-            if (k == QM_LINE_HEADER || k == QM_LINE_HEADER_KEPT || k == QM_LINE_HEADER_KEPT_TP || k == QM_LINE_HEADER_REFUSED) continue;
-            if ((s.flags[rec] & QM_F_PASS) && (s.flags[rec] & QM_F_NOKEY)) line = i + 1;
-            ++rec;
-          }
-          err = std::string(jobs[j].vcf_path) + " line " + std::to_string(line) + ": a kept line has no comparable key (POS is not a canonical decimal) -- "
-                "the truth-side view compares keys, not text, and does not take this VCF";
-          rc = QM_E_NONCANON;
-        }
-        if (rc == QM_OK) { rc = qm_batch_truth_hits(batch, nullptr); if (rc != QM_OK) err = qm_last_error(ctx); }
-        hitbits.resize((size_t)n_jobs);
-        for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
-          if (jobs[j].pure || !ts->fn_out[j]) continue;
-          const TruthState& t = T[(size_t)J[(size_t)j].truth];
-          hitbits[(size_t)j].assign((t.keys.size() + 31) / 32, 0u);
-          rc = qm_batch_get_truth_hits(batch, J[(size_t)j].batch_v, hitbits[(size_t)j].data(), (int64_t)hitbits[(size_t)j].size());
-          if (rc != QM_OK) err = qm_last_error(ctx);
-        }
-        if (rc == QM_OK && ts->n_groups > 0) {
-          members.resize((size_t)ts->n_groups);
-          for (int j = 0; j < n_jobs; ++j) if (ts->group[j] >= 0) members[(size_t)ts->group[j]].push_back(j);
-          std::vector<int32_t> goff(1, 0), gids;
-          size_t uw = 0;
-          for (const auto& m : members) {
-            for (int j : m) gids.push_back(J[(size_t)j].batch_v);
-            goff.push_back((int32_t)gids.size());
-            uw += (T[(size_t)J[(size_t)m[0]].truth].keys.size() + 31) / 32;
-          }
-          std::vector<uint32_t> uni(uw + 1, 0u);
-          rc = qm_batch_truth_regions(batch, ts->n_groups, goff.data(), gids.data(), ts->regions, uni.data());
-          if (rc != QM_OK) err = qm_last_error(ctx);
-          unibits.resize((size_t)ts->n_groups);
-          size_t o = 0;
-          for (size_t g = 0; g < members.size() && rc == QM_OK; ++g) {
-            const size_t nw = (T[(size_t)J[(size_t)members[g][0]].truth].keys.size() + 31) / 32;
-            unibits[g].assign(uni.begin() + (long)o, uni.begin() + (long)(o + nw));
-            o += nw;
-          }
-          // the callers' side of the Venn: the keys of the kept records outside the in-truth record mask, through qm_fp_overlap
-          for (size_t g = 0; g < members.size() && rc == QM_OK && ts->fp_regions; ++g) {
-            std::vector<int64_t> so(1, 0);
-            std::vector<int32_t> kp, kr, ka;
-            for (int j : members[g]) {
-              const JobState& s = J[(size_t)j];
-              std::vector<uint64_t> kept((size_t)(s.n_data + 63) / 64 + 1), tpm(kept.size()), in(kept.size());
-              rc = qm_batch_get_masks(batch, s.batch_v, kept.data(), tpm.data());
-              if (rc == QM_OK) rc = qm_batch_get_intruth_mask(batch, s.batch_v, in.data());
-              if (rc != QM_OK) { err = qm_last_error(ctx); break; }
-              for (int64_t r = 0; r < s.n_data; ++r)
-                if (((kept[(size_t)r >> 6] & ~in[(size_t)r >> 6]) >> (r & 63)) & 1ull) { kp.push_back(s.pos[r]); kr.push_back(s.ref[r]); ka.push_back(s.alt[r]); }
-              so.push_back((int64_t)kp.size());
-            }
-            if (rc != QM_OK) break;
-            int64_t reg[QM_TRUTH_REGIONS] = {0};
-            int32_t dummy = 0;
-            rc = qm_fp_overlap(ctx, (int)members[g].size(), so.data(), kp.empty() ? &dummy : kp.data(), kr.empty() ? &dummy : kr.data(),
-                               ka.empty() ? &dummy : ka.data(), reg);
-            if (rc != QM_OK) { err = qm_last_error(ctx); break; }
-            memcpy(ts->fp_regions + g * QM_TRUTH_REGIONS, reg, sizeof reg);
-          }
-        }
-        // the lists: one per job that asked, one per group that asked (missed by every member)
-        if (rc == QM_OK) {
-          struct FTask { const char* path; const TruthState* t; const uint32_t* bits; };
-          std::vector<FTask> F;
-          for (int j = 0; j < n_jobs; ++j)
-            if (!jobs[j].pure && ts->fn_out[j]) F.push_back({ts->fn_out[j], &T[(size_t)J[(size_t)j].truth], hitbits[(size_t)j].data()});
-          for (size_t g = 0; g < members.size(); ++g)
-            if (ts->missed_out && ts->missed_out[g]) F.push_back({ts->missed_out[g], &T[(size_t)J[(size_t)members[g][0]].truth], unibits[g].data()});
-          std::vector<int> frc(F.size(), QM_OK);
-          parallel_for((int)F.size(), nthr, [&](int k) { frc[(size_t)k] = write_fn_file(F[(size_t)k].path, *F[(size_t)k].t, F[(size_t)k].bits); });
-          for (size_t k = 0; k < F.size() && rc == QM_OK; ++k)
-            if (frc[k] != QM_OK) { rc = frc[k]; err = std::string("cannot write ") + F[k].path; }
-        }
-      } else
       if (rc != QM_OK) err = qm_last_error(ctx);
-      if (rc == QM_OK && va && va->n_groups > 0) rc = votes_pass(ctx, batch, n_jobs, jobs, J, T, va, err);
+      // the passes, on the columns, masks and truth keys the classification leaves in HBM; the one that fails sets err
+      const PassCtx pc{ctx, batch, n_jobs, jobs, J, T, nrec.size(), ext, nthr};
+      if (rc == QM_OK) rc = motifs_pass(pc, P, err);
+      if (rc == QM_OK) rc = profile_pass(pc, P.pa, err);
+      if (rc == QM_OK) rc = strata_pass(pc, P.sa, err);
+      if (rc == QM_OK) rc = boot_pass(pc, P.ba, err);
+      if (rc == QM_OK) rc = truthside_pass(pc, P.ts, err);
+      if (rc == QM_OK) rc = votes_pass(pc, P.va, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;
     for (int j = 0; j < n_jobs && rc == QM_OK; ++j) {
       JobState& s = J[(size_t)j];
-      if (jobs[j].pure && !(wants_profile(j) && pa->points_out && pa->points_out[j])) continue;   // (a pure-strain job's masks: for its points file only)
+      if (jobs[j].pure && !(P.wants_profile(j) && P.pa->points_out && P.pa->points_out[j])) continue;   // (a pure-strain job's masks: for its points file only)
       rc = qm_batch_get_masks(batch, s.batch_v, s.kept, s.tp);
       if (rc != QM_OK) err = qm_last_error(ctx);
     }
@@ -924,9 +957,10 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (jobs[j].pure) { W.push_back({j, 0, jobs[j].filtered_out, true}); W.push_back({j, 0, jobs[j].fp_out, true}); }   // cp filtered fp (:33-36)
       else { W.push_back({j, 0, jobs[j].filtered_out, false}); W.push_back({j, 1, jobs[j].tp_out, false}); W.push_back({j, 2, jobs[j].fp_out, false}); }
     }
-    if (pa && pa->points_out) {   // the data frames R plots
+    if (P.pa && P.pa->points_out) {   // the data frames R plots
+      const qm_profile_args* pa = P.pa;
       std::vector<int> pj;
-      for (int j = 0; j < n_jobs; ++j) if (wants_profile(j) && pa->points_out[j]) pj.push_back(j);
+      for (int j = 0; j < n_jobs; ++j) if (P.wants_profile(j) && pa->points_out[j]) pj.push_back(j);
       std::vector<int> prc(pj.size(), QM_OK);
       parallel_for((int)pj.size(), nthr, [&](int k) { prc[(size_t)k] = write_points_file(pa->points_out[pj[(size_t)k]], J[(size_t)pj[(size_t)k]]); });
       for (size_t k = 0; k < pj.size(); ++k)

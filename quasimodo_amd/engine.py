@@ -1,5 +1,6 @@
 """Engine / Batch: thin object layer over the C ABI (include/qmvt.h)."""
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -191,31 +192,29 @@ class Engine:
         qm_extract_files_truthside: the missed-variant lists are written, the rows of grouped jobs gain
         `truth_regions` and `fp_regions` (int64 [32] each, the same for every member; members in job order).
         profile: {"want": [0/1 per job], "window": 1024, "n_pos_bins": 256, "n_af_bins": 20, "points": [path or None per job]} --
-        qm_extract_files_profile (combines with genomes, not with truthside): wanted rows gain `af_grid`
-        ([2][n_af_bins][n_pos_bins] uint64: TP, FP) and `af_extra` ([2][QM_AFP_EXTRA]); the points files are written.
-        strata: {"id": strata_load id, "want": [0/1 per job]} -- qm_extract_files_strata (combines with none of the
-        above): wanted rows gain `strata_rec` ([S + 2][3] uint64: kept, TP, FP lines per stratum, outside, nokey) and `strata_tru`
-        ([S + 1][2]: truth keys, hit ones; None in the allele-extended mode).
+        qm_extract_files_profile: wanted rows gain `af_grid` ([2][n_af_bins][n_pos_bins] uint64: TP, FP) and
+        `af_extra` ([2][QM_AFP_EXTRA]); the points files are written.
+        strata: {"id": strata_load id, "want": [0/1 per job]} -- qm_extract_files_strata: wanted rows gain
+        `strata_rec` ([S + 2][3] uint64: kept, TP, FP lines per stratum, outside, nokey) and `strata_tru` ([S + 1][2]: truth keys,
+        hit ones; None in the allele-extended mode).
         boot: {"want": [0/1 per job], "window": 1024, "n_win": 256, "n_rep": 1000, "seed": 0} -- qm_extract_files_boot (DESIGN.md
-        4.11; combines with none of the above): wanted rows gain `boot_cnt` ([n_win + 2][4] uint64: kept lines, TP lines, truth
-        keys, hit keys per window, then outside, nokey) and `boot_rep` ([n_rep][4], the bootstrap replicates of the four sums).
+        4.11): wanted rows gain `boot_cnt` ([n_win + 2][4] uint64: kept lines, TP lines, truth keys, hit keys per window, then
+        outside, nokey) and `boot_rep` ([n_rep][4], the bootstrap replicates of the four sums).
         votes: {"group": [group id or -1 per job], "k": [consensus level or 0 per group], "out": [path or None per group]} --
-        qm_extract_files_votes (combines with none of the above): the rows of grouped jobs gain `tp_votes`,
-        `fp_votes` ([33] uint64), `private_tp`, `private_fp` ([32]; the same for every member, members in job order) and
-        `vote_member` (the job's index in its group); the consensus VCFs of the groups with a level are written.
+        qm_extract_files_votes: the rows of grouped jobs gain `tp_votes`, `fp_votes` ([33] uint64), `private_tp`,
+        `private_fp` ([32]; the same for every member, members in job order) and `vote_member` (the job's index in its group);
+        the consensus VCFs of the groups with a level are written.
+        Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        import os
-        if votes is not None and (boot is not None or strata is not None or profile is not None or truthside is not None or
-                                  (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
-            raise ValueError("votes does not combine with genomes, truthside, profile, strata or boot in one call")
-        if profile is not None and truthside is not None:
-            raise ValueError("truthside and profile in one call are not supported")
-        if strata is not None and (profile is not None or truthside is not None or (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
-            raise ValueError("strata does not combine with genomes, truthside or profile in one call")
-        if boot is not None and (strata is not None or profile is not None or truthside is not None or
-                                 (genomes is not None and any(g is not None and int(g) >= 0 for g in genomes))):
-            raise ValueError("boot does not combine with genomes, truthside, profile or strata in one call")
+        from .passes import check_shared_call
         n = len(file_jobs)
+        gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
+        if gids is not None and gids.shape[0] != n:
+            raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
+        if gids is not None and not (gids >= 0).any():
+            gids = None
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes}
+        check_shared_call({name for name, spec in specs.items() if spec is not None})
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -225,113 +224,106 @@ class Engine:
         roc = np.zeros((max(n, 1), 3, n_bins), np.uint64)
         ph = (C.c_double * 8)()
         slots = None if truth_slots is None else _c(list(truth_slots) + [0] * (1 if n == 0 else 0), np.int32)
-        gids = None if genomes is None else [-1 if g is None else int(g) for g in genomes]
-        motifs = None
-        if gids is not None and len(gids) != n:
-            raise ValueError("genomes: %d entries for %d jobs" % (len(gids), n))
         args = (self._h, n, arr, int(n_bins), _lib.QM_BATCH_ALLELES if alleles else 0, int(bool(strict)), st, _p(roc), ph,
                 _p(slots), int(n_slots), C.c_void_p(global_dev) if global_dev else None)
-        regs = None
-        afg = None
-        srec = None
-        bcnt = None
-        vtab = None
-        if votes is not None:
-            vgrp = _c([-1 if g is None else int(g) for g in votes["group"]] or [-1], np.int32)
-            if n and vgrp.shape[0] != n:
-                raise ValueError("votes: %d group entries for %d jobs" % (vgrp.shape[0], n))
-            vng = (int(vgrp.max()) + 1) if n else 0
-            vk = _c(list(votes.get("k") or [0] * vng) or [0], np.int32)
-            vout = list(votes.get("out") or [None] * vng)
-            if vng and (vk.shape[0] != vng or len(vout) != vng):
-                raise ValueError("votes: %d levels / %d files for %d groups" % (vk.shape[0], len(vout), vng))
-            vtab = [np.zeros((max(vng, 1), w), np.uint64) for w in (_lib.QM_VOTE_SLOTS, _lib.QM_VOTE_SLOTS, _lib.QM_VOTE_GROUP_MAX, _lib.QM_VOTE_GROUP_MAX)]
-            out_arr = (C.c_char_p * max(vng, 1))(*[None if x is None else os.fsencode(x) for x in vout])
-            va = _lib.VotesArgs(_p(vgrp), vng, 0, _p(vtab[0]), _p(vtab[1]), _p(vtab[2]), _p(vtab[3]), _p(vk), out_arr)
-            check(self._L.qm_extract_files_votes(*args, C.byref(va)), self._h)
-        elif boot is not None:
-            bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
-            if n and bwant.shape[0] != n:
-                raise ValueError("boot: %d want entries for %d jobs" % (len(boot["want"]), n))
-            bw, bn, br = int(boot.get("window", 1024)), int(boot.get("n_win", 256)), int(boot.get("n_rep", 1000))
-            if bw < 1 or not 1 <= bn <= _lib.QM_BOOT_MAX_WINDOWS or not 0 <= br <= _lib.QM_BOOT_MAX_REP:
-                raise ValueError("boot: window %d, n_win %d (1 to %d), n_rep %d (0 to %d)" % (bw, bn, _lib.QM_BOOT_MAX_WINDOWS, br, _lib.QM_BOOT_MAX_REP))
-            bcnt = np.zeros((max(n, 1), bn + 2, 4), np.uint64)
-            brep = np.zeros((max(n, 1), max(br, 1), 4), np.uint64)
-            ba = _lib.BootArgs(bw, bn, br, 0, int(boot.get("seed", 0)) & ((1 << 64) - 1), _p(bwant), _p(bcnt), _p(brep))
-            check(self._L.qm_extract_files_boot(*args, C.byref(ba)), self._h)
-        elif strata is not None:
-            swant = _c([int(bool(w)) for w in strata["want"]] or [0], np.uint8)
-            if n and swant.shape[0] != n:
-                raise ValueError("strata: %d want entries for %d jobs" % (len(strata["want"]), n))
-            S = self.strata_info(strata["id"])[0]
-            srec = np.zeros((max(n, 1), S + 2, 3), np.uint64)
-            stru = np.zeros((max(n, 1), S + 1, 2), np.uint64)
-            sa = _lib.StrataArgs(int(strata["id"]), 0, _p(swant), _p(srec), _p(stru))
-            check(self._L.qm_extract_files_strata(*args, C.byref(sa)), self._h)
-        elif profile is not None:
-            want = _c([int(bool(w)) for w in profile["want"]] or [0], np.uint8)
-            pts = list(profile.get("points") or [None] * n)
-            if (n and want.shape[0] != n) or len(pts) != n:
-                raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(profile["want"]), len(pts), n))
-            nA, nP = int(profile.get("n_af_bins", 20)), int(profile.get("n_pos_bins", 256))
-            if nA < 1 or nP < 1 or nA * nP > _lib.QM_AFP_MAX_CELLS:
-                raise ValueError("profile: %d x %d bins (at most %d cells)" % (nA, nP, _lib.QM_AFP_MAX_CELLS))
-            afg = np.zeros((max(n, 1), 2, nA, nP), np.uint64)
-            afx = np.zeros((max(n, 1), 2, _lib.QM_AFP_EXTRA), np.uint64)
-            pt_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in pts])
-            pa = _lib.ProfileArgs(_p(want), int(profile.get("window", 1024)), nP, nA, 0, _p(afg), _p(afx), pt_arr)
-            with_g = gids is not None and any(g >= 0 for g in gids)
-            if with_g:
-                motifs = np.zeros((max(n, 1), 3, _lib.QM_MOTIF_COLS), np.uint64)
-            check(self._L.qm_extract_files_profile(*args, _p(_c(gids, np.int32)) if with_g else None, _p(motifs) if with_g else None, C.byref(pa)), self._h)
-        elif truthside is not None:
-            if gids is not None and any(g >= 0 for g in gids):
-                raise ValueError("truthside and genomes in one call are not supported")
-            enc = lambda x: None if x is None else os.fsencode(x)
-            grp = _c([-1 if g is None else int(g) for g in truthside["group"]] or [-1], np.int32)
-            ng = len(truthside.get("missed") or []) or (int(grp.max()) + 1 if n else 0)
-            if len(truthside["fn"]) != n or (n and grp.shape[0] != n):
-                raise ValueError("truthside: %d fn / %d group entries for %d jobs" % (len(truthside["fn"]), grp.shape[0], n))
-            fn_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in truthside["fn"]])
-            missed = list(truthside.get("missed") or [None] * ng)
-            ms_arr = (C.c_char_p * max(ng, 1))(*[enc(x) for x in missed])
-            regs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.uint64)
-            fregs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.int64)
-            ta = _lib.TruthSideArgs(fn_arr, _p(grp), ng, 0, _p(regs), _p(fregs), ms_arr)
-            check(self._L.qm_extract_files_truthside(*args, C.byref(ta)), self._h)
-        elif gids is not None and any(g >= 0 for g in gids):
-            motifs = np.zeros((n, 3, _lib.QM_MOTIF_COLS), np.uint64)
-            check(self._L.qm_extract_files_motifs(*args, _p(_c(gids, np.int32)), _p(motifs)), self._h)
-        else:
-            check(self._L.qm_extract_files_ex(*args), self._h)
+        # the call's pass (check_shared_call left one; motifs may come with profile, whose entry point takes both)
+        entry, extra, unpack = self._L.qm_extract_files_ex, (), lambda k: {}
+        for name, spec in specs.items():
+            if spec is not None and not (name == "motifs" and profile is not None):
+                entry, extra, unpack = getattr(self, "_files_" + name)(n, spec, gids=gids, alleles=alleles)
+        check(entry(*args, *extra), self._h)
         rows = []
         for k in range(n):
             r = dict(zip(SCALAR_NAMES, list(st[k].scalars)))
             r.update(n_lines=st[k].n_lines, n_refused=st[k].n_refused, genomediff=st[k].genomediff,
                      header_kept=(st[k].header_kept, st[k].header_kept_tp), host_decided=st[k].host_decided, r_hostile=st[k].r_hostile,
                      roc=roc[k].copy())
-            if motifs is not None:
-                r["motifs"] = motifs[k].copy()
-            if afg is not None and want[k]:
-                r["af_grid"] = afg[k].copy()
-                r["af_extra"] = afx[k].copy()
-            if srec is not None and swant[k]:
-                r["strata_rec"] = srec[k].copy()
-                r["strata_tru"] = None if alleles else stru[k].copy()
-            if bcnt is not None and bwant[k]:
-                r["boot_cnt"] = bcnt[k].copy()
-                r["boot_rep"] = brep[k, :br].copy()
-            if vtab is not None and vgrp[k] >= 0:
-                g = int(vgrp[k])
-                r.update(tp_votes=vtab[0][g].copy(), fp_votes=vtab[1][g].copy(), private_tp=vtab[2][g].copy(), private_fp=vtab[3][g].copy(),
-                         vote_member=int((vgrp[:k] == g).sum()))
-            if regs is not None and grp[k] >= 0:
-                r["truth_regions"] = regs[grp[k]].astype(np.int64)
-                r["fp_regions"] = fregs[grp[k]].copy()
+            r.update(unpack(k))
             rows.append(r)
         phases = dict(zip(("map_count", "truth_beside", "batch_layout", "tokenise_upload", "engine", "masks_back", "write", "release"), list(ph)))
         return rows, phases
+
+    # -- the passes of extract_files: (entry point, its arguments behind the common ones, row k -> what the job's row gains) --
+    def _files_motifs(self, n, spec, gids=None, **kw):   # (spec: the genome ids themselves)
+        motifs = np.zeros((max(n, 1), 3, _lib.QM_MOTIF_COLS), np.uint64)
+        return self._L.qm_extract_files_motifs, (_p(gids), _p(motifs)), lambda k: {"motifs": motifs[k].copy()}
+
+    def _files_profile(self, n, profile, gids=None, **kw):
+        want = _c([int(bool(w)) for w in profile["want"]] or [0], np.uint8)
+        pts = list(profile.get("points") or [None] * n)
+        if (n and want.shape[0] != n) or len(pts) != n:
+            raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(profile["want"]), len(pts), n))
+        nA, nP = int(profile.get("n_af_bins", 20)), int(profile.get("n_pos_bins", 256))
+        if nA < 1 or nP < 1 or nA * nP > _lib.QM_AFP_MAX_CELLS:
+            raise ValueError("profile: %d x %d bins (at most %d cells)" % (nA, nP, _lib.QM_AFP_MAX_CELLS))
+        afg = np.zeros((max(n, 1), 2, nA, nP), np.uint64)
+        afx = np.zeros((max(n, 1), 2, _lib.QM_AFP_EXTRA), np.uint64)
+        pt_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in pts])
+        pa = _lib.ProfileArgs(_p(want), int(profile.get("window", 1024)), nP, nA, 0, _p(afg), _p(afx), pt_arr)
+        motifs = None if gids is None else np.zeros((max(n, 1), 3, _lib.QM_MOTIF_COLS), np.uint64)
+
+        def unpack(k):
+            r = {} if motifs is None else {"motifs": motifs[k].copy()}
+            return dict(r, af_grid=afg[k].copy(), af_extra=afx[k].copy()) if want[k] else r
+        return self._L.qm_extract_files_profile, (_p(gids), _p(motifs), C.byref(pa)), unpack
+
+    def _files_truthside(self, n, truthside, **kw):
+        enc = lambda x: None if x is None else os.fsencode(x)
+        grp = _c([-1 if g is None else int(g) for g in truthside["group"]] or [-1], np.int32)
+        ng = len(truthside.get("missed") or []) or (int(grp.max()) + 1 if n else 0)
+        if len(truthside["fn"]) != n or (n and grp.shape[0] != n):
+            raise ValueError("truthside: %d fn / %d group entries for %d jobs" % (len(truthside["fn"]), grp.shape[0], n))
+        fn_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in truthside["fn"]])
+        ms_arr = (C.c_char_p * max(ng, 1))(*[enc(x) for x in truthside.get("missed") or [None] * ng])
+        regs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.uint64)
+        fregs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.int64)
+        ta = _lib.TruthSideArgs(fn_arr, _p(grp), ng, 0, _p(regs), _p(fregs), ms_arr)
+        unpack = lambda k: {"truth_regions": regs[grp[k]].astype(np.int64), "fp_regions": fregs[grp[k]].copy()} if grp[k] >= 0 else {}
+        return self._L.qm_extract_files_truthside, (C.byref(ta),), unpack
+
+    def _files_strata(self, n, strata, alleles=False, **kw):
+        swant = _c([int(bool(w)) for w in strata["want"]] or [0], np.uint8)
+        if n and swant.shape[0] != n:
+            raise ValueError("strata: %d want entries for %d jobs" % (len(strata["want"]), n))
+        S = self.strata_info(strata["id"])[0]
+        srec = np.zeros((max(n, 1), S + 2, 3), np.uint64)
+        stru = np.zeros((max(n, 1), S + 1, 2), np.uint64)
+        sa = _lib.StrataArgs(int(strata["id"]), 0, _p(swant), _p(srec), _p(stru))
+        unpack = lambda k: {"strata_rec": srec[k].copy(), "strata_tru": None if alleles else stru[k].copy()} if swant[k] else {}
+        return self._L.qm_extract_files_strata, (C.byref(sa),), unpack
+
+    def _files_boot(self, n, boot, **kw):
+        bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
+        if n and bwant.shape[0] != n:
+            raise ValueError("boot: %d want entries for %d jobs" % (len(boot["want"]), n))
+        bw, bn, br = int(boot.get("window", 1024)), int(boot.get("n_win", 256)), int(boot.get("n_rep", 1000))
+        if bw < 1 or not 1 <= bn <= _lib.QM_BOOT_MAX_WINDOWS or not 0 <= br <= _lib.QM_BOOT_MAX_REP:
+            raise ValueError("boot: window %d, n_win %d (1 to %d), n_rep %d (0 to %d)" % (bw, bn, _lib.QM_BOOT_MAX_WINDOWS, br, _lib.QM_BOOT_MAX_REP))
+        bcnt = np.zeros((max(n, 1), bn + 2, 4), np.uint64)
+        brep = np.zeros((max(n, 1), max(br, 1), 4), np.uint64)
+        ba = _lib.BootArgs(bw, bn, br, 0, int(boot.get("seed", 0)) & ((1 << 64) - 1), _p(bwant), _p(bcnt), _p(brep))
+        unpack = lambda k: {"boot_cnt": bcnt[k].copy(), "boot_rep": brep[k, :br].copy()} if bwant[k] else {}
+        return self._L.qm_extract_files_boot, (C.byref(ba),), unpack
+
+    def _files_votes(self, n, votes, **kw):
+        vgrp = _c([-1 if g is None else int(g) for g in votes["group"]] or [-1], np.int32)
+        if n and vgrp.shape[0] != n:
+            raise ValueError("votes: %d group entries for %d jobs" % (vgrp.shape[0], n))
+        vng = (int(vgrp.max()) + 1) if n else 0
+        vk = _c(list(votes.get("k") or [0] * vng) or [0], np.int32)
+        vout = list(votes.get("out") or [None] * vng)
+        if vng and (vk.shape[0] != vng or len(vout) != vng):
+            raise ValueError("votes: %d levels / %d files for %d groups" % (vk.shape[0], len(vout), vng))
+        vtab = [np.zeros((max(vng, 1), w), np.uint64) for w in (_lib.QM_VOTE_SLOTS, _lib.QM_VOTE_SLOTS, _lib.QM_VOTE_GROUP_MAX, _lib.QM_VOTE_GROUP_MAX)]
+        out_arr = (C.c_char_p * max(vng, 1))(*[None if x is None else os.fsencode(x) for x in vout])
+        va = _lib.VotesArgs(_p(vgrp), vng, 0, _p(vtab[0]), _p(vtab[1]), _p(vtab[2]), _p(vtab[3]), _p(vk), out_arr)
+        va.keep = vk   # (the levels are read during the call; the other arrays live in unpack)
+
+        def unpack(k):
+            g = int(vgrp[k])
+            return {} if g < 0 else dict(zip(("tp_votes", "fp_votes", "private_tp", "private_fp"), (t[g].copy() for t in vtab)),
+                                         vote_member=int((vgrp[:k] == g).sum()))
+        return self._L.qm_extract_files_votes, (C.byref(va),), unpack
 
     def path_stats_total(self):
         """qm_path_stats_total: where the VCFs found out of order went, summed over every batch this context has finished

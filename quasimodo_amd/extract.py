@@ -19,6 +19,7 @@ import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
+from .passes import PASSES, check_shared_call, requested_by
 from .vcfio import scan_vcf
 
 
@@ -95,6 +96,34 @@ def _alleles_default():
     return os.environ.get("QM_ALLELES", "0") not in ("", "0")
 
 
+def _label_groups(jobs, groups, field, prefix, max_members, what, two):
+    """extract_many's `groups` (lists of job indices) as labels in Job.<field>"""
+    for k, g in enumerate(groups):
+        if not 1 <= len(g) <= max_members:
+            raise ValueError("a %s group holds 1 to %d jobs, not %d" % (what, max_members, len(g)))
+        for i in g:
+            if getattr(jobs[i], field) not in (None, "%s%d" % (prefix, k)):
+                raise ValueError("job %d sits in two %sgroups" % (i, two))
+            setattr(jobs[i], field, "%s%d" % (prefix, k))
+
+
+def _group_indices(jobs, pure, field, max_members, what):
+    """The labels in Job.<field>, in job order, and per job the index of its label or -1: what the engine takes.  A group holds 1 to
+    max_members mixed-sample jobs."""
+    labels = []
+    for j, p in zip(jobs, pure):
+        lab = getattr(j, field)
+        if lab is not None and p:
+            raise ValueError("%s: a pure-strain sample cannot be in a %s group (its truth is never read)" % (j.vcf_file, what))
+        if lab is not None and lab not in labels:
+            labels.append(lab)
+    for lab in labels:
+        k = sum(getattr(j, field) == lab for j in jobs)
+        if k > max_members:
+            raise ValueError("%s group %r holds %d jobs (1 to %d)" % (what, lab, k, max_members))
+    return labels, [-1 if getattr(j, field) is None else labels.index(getattr(j, field)) for j in jobs]
+
+
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
@@ -114,68 +143,50 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     profile: {"want": [0/1 per job], "window": 1024, "n_pos_bins": 256, "n_af_bins": 20, "points": [path or None per job]}
     (default: the jobs' Job.profile / Job.points_out): the wanted jobs get stats["af_grid"] ([2][n_af_bins][n_pos_bins]: TP, FP
     SNVs by allele frequency and position) and stats["af_extra"] ([2][3]: no AF, outside, in the grid; quasimodo_amd.afprofile),
-    and their points files are written.  Combines with genomes; not with fn / groups (ValueError).
+    and their points files are written.
     strata: a list of (name, starts, ends) BED strata (quasimodo_amd.strata; default: the jobs' Job.strata): every job gets
     stats["strata_rec"] ([S + 2][3]: kept, TP, FP lines per stratum, then outside, nokey) and stats["strata_tru"] ([S + 1][2]:
-    truth keys and hit ones per stratum, then outside; None in the allele-extended mode; zero for pure-strain samples).  Combines
-    with none of genomes, fn, groups, profile (ValueError).
+    truth keys and hit ones per stratum, then outside; None in the allele-extended mode; zero for pure-strain samples).
     boot: {"window": 1024, "n_win": 256, "n_rep": 1000, "seed": 0} (quasimodo_amd.bootstrap; default: the jobs' Job.boot): every
     job gets stats["boot_cnt"] ([n_win + 2][4]: kept lines, TP lines, truth keys, hit keys per window, then outside, nokey),
     stats["boot_rep"] ([n_rep][4]: the bootstrap replicates of the four sums, the same draws for every job, call, rank and
     device), stats["boot_params"] and stats["boot_truth"] (False in the allele-extended mode: columns 2 and 3 are zero).
-    Combines with none of genomes, fn, groups, profile, strata (ValueError).
     votes: True or {"k": [level or 0 per group], "out": [path or None per group]} (quasimodo_amd.consensus; default: the jobs'
     Job.vote_group / consensus_k / consensus_out): `groups` then names the VOTE groups (1 to 32 mixed-sample jobs of one truth
     file each, a job in at most one): the members' stats gain tp_votes / fp_votes ([33]), private_tp / private_fp ([32]),
     vote_member (the job's index in its group) and vote_callers (the members' Job.caller, in member order = job order), and the
     groups with a level get their consensus VCF.  Over several GPUs a group must sit on one rank (WorkflowError otherwise).
-    Combines with none of genomes, fn, profile, strata, boot (ValueError)."""
+    Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
+    from .consensus import MAX_GROUP as VMAX
+    from .truthside import MAX_GROUP
+    given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
+             "strata": strata is not None, "boot": boot is not None, "votes": bool(votes)}
+    # the keywords onto the jobs ...
     if votes:
-        from .consensus import MAX_GROUP as VMAX
         if groups is None:
             raise ValueError("votes: groups (lists of job indices) are needed")
         opt = votes if isinstance(votes, dict) else {}
         ks, outs = list(opt.get("k") or [0] * len(groups)), list(opt.get("out") or [None] * len(groups))
         if len(ks) != len(groups) or len(outs) != len(groups):
             raise ValueError("votes: %d levels / %d files for %d groups" % (len(ks), len(outs), len(groups)))
+        _label_groups(jobs, groups, "vote_group", "v", VMAX, "vote", "vote ")
         for k, g in enumerate(groups):
-            if not 1 <= len(g) <= VMAX:
-                raise ValueError("a vote group holds 1 to %d jobs, not %d" % (VMAX, len(g)))
             if not 0 <= int(ks[k]) <= len(g):
                 raise ValueError("vote group %d: consensus level %d with %d members" % (k, int(ks[k]), len(g)))
             for i in g:
-                if jobs[i].vote_group is not None and jobs[i].vote_group != "v%d" % k:
-                    raise ValueError("job %d sits in two vote groups" % i)
-                jobs[i].vote_group, jobs[i].consensus_k, jobs[i].consensus_out = "v%d" % k, int(ks[k]), outs[k]
-        groups = None
-    if any(j.vote_group is not None for j in jobs):
-        if genomes is not None or fn or groups is not None or profile is not None or strata is not None or boot is not None or any(
-                j.genome or j.fn_out or j.group is not None or j.profile or j.strata or j.boot for j in jobs):
-            raise ValueError("votes does not combine with genomes, fn, truth-side groups, profile, strata or boot in one call")
+                jobs[i].consensus_k, jobs[i].consensus_out = int(ks[k]), outs[k]
+    elif groups is not None:
+        _label_groups(jobs, groups, "group", "g", MAX_GROUP, "truth-side", "")
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
         for j in jobs:
             j.boot = par
-    if any(j.boot for j in jobs):
-        if genomes is not None or fn or groups is not None or profile is not None or strata is not None or any(
-                j.genome or j.fn_out or j.group is not None or j.profile or j.strata for j in jobs):
-            raise ValueError("boot does not combine with genomes, fn, groups, profile or strata in one call")
-        if len({j.boot for j in jobs if j.boot}) > 1:
-            raise ValueError("boot: the resampled jobs of one call share one window, window count, replicate count and seed")
     if strata is not None:
         from .strata import freeze
         frozen = freeze(strata)
         for j in jobs:
             j.strata = frozen
-    if any(j.strata for j in jobs):
-        if genomes is not None or fn or groups is not None or profile is not None or any(
-                j.genome or j.fn_out or j.group is not None or j.profile for j in jobs):
-            raise ValueError("strata does not combine with genomes, fn, groups or profile in one call")
-        if len({j.strata for j in jobs if j.strata}) > 1:
-            raise ValueError("strata: the stratified jobs of one call share one strata set")
-    strict = _strict_default() if strict is None else strict
-    alleles = _alleles_default() if alleles is None else bool(alleles)
     if genomes is not None:
         if len(genomes) != len(jobs):
             raise ValueError("genomes: %d entries for %d jobs" % (len(genomes), len(jobs)))
@@ -190,23 +201,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         for j, w, pt in zip(jobs, want, pts):
             j.profile = par if w else None
             j.points_out = pt if w else None
-    if any(j.profile for j in jobs) and (fn or groups is not None or any(j.fn_out or j.group is not None for j in jobs)):
-        raise ValueError("the truth-side view (fn / groups) and profile in one call are not supported")
-    if len({j.profile for j in jobs if j.profile}) > 1:
-        raise ValueError("profile: the profiled jobs of one call share one window and one pair of bin counts")
-    if groups is not None:
-        from .truthside import MAX_GROUP
-        for k, g in enumerate(groups):
-            if not 1 <= len(g) <= MAX_GROUP:
-                raise ValueError("a truth-side group holds 1 to %d jobs, not %d" % (MAX_GROUP, len(g)))
-            for i in g:
-                if jobs[i].group is not None and jobs[i].group != "g%d" % k:
-                    raise ValueError("job %d sits in two groups" % i)
-                jobs[i].group = "g%d" % k
     for j in jobs:
         if fn and j.fn_out is None and not is_pure_strain(j.vcf_file):
             _paths(j)
             j.fn_out = fn_path(j)
+    # ... which may share the call, and agree on the parameters of a pass
+    check_shared_call({name for name, g in given.items() if g} | requested_by(jobs))
+    for p in PASSES:
+        if p.agree and len({getattr(j, p.name) for j in jobs if getattr(j, p.name)}) > 1:
+            raise ValueError(p.agree)
+    strict = _strict_default() if strict is None else strict
+    alleles = _alleles_default() if alleles is None else bool(alleles)
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -232,38 +237,18 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = None
+    ts = vt = None
     if any((j.fn_out or j.group is not None) and not p for j, p in zip(jobs, pure)):
-        from .truthside import MAX_GROUP
-        labels = []
-        for j, p in zip(jobs, pure):
-            if j.group is not None and p:
-                raise ValueError("%s: a pure-strain sample cannot be in a truth-side group (its truth is never read)" % j.vcf_file)
-            if j.group is not None and j.group not in labels:
-                labels.append(j.group)
-        for lab in labels:
-            k = sum(j.group == lab for j in jobs)
-            if k > MAX_GROUP:
-                raise ValueError("truth-side group %r holds %d jobs (1 to %d)" % (lab, k, MAX_GROUP))
+        labels, index = _group_indices(jobs, pure, "group", MAX_GROUP, "truth-side")
         missed = [next((j.missed_out for j in jobs if j.group == lab and j.missed_out), None) for lab in labels]
-        ts = {"fn": [None if p else j.fn_out for j, p in zip(jobs, pure)],
-              "group": [-1 if j.group is None else labels.index(j.group) for j in jobs], "missed": missed}
+        ts = {"fn": [None if p else j.fn_out for j, p in zip(jobs, pure)], "group": index, "missed": missed}
         for path in [x for x in ts["fn"] + missed if x]:
             os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    vt = None
-    vlabels = []
     if any(j.vote_group is not None for j in jobs):
-        from .consensus import MAX_GROUP as VMAX
-        for j, p in zip(jobs, pure):
-            if j.vote_group is not None and p:
-                raise ValueError("%s: a pure-strain sample cannot be in a vote group (its truth is never read)" % j.vcf_file)
-            if j.vote_group is not None and j.vote_group not in vlabels:
-                vlabels.append(j.vote_group)
-        vt = {"group": [-1 if j.vote_group is None else vlabels.index(j.vote_group) for j in jobs], "k": [], "out": []}
-        for lab in vlabels:
+        labels, index = _group_indices(jobs, pure, "vote_group", VMAX, "vote")
+        vt = {"group": index, "k": [], "out": []}
+        for lab in labels:
             mem = [j for j in jobs if j.vote_group == lab]
-            if len(mem) > VMAX:
-                raise ValueError("vote group %r holds %d jobs (1 to %d)" % (lab, len(mem), VMAX))
             k = next((j.consensus_k for j in mem if j.consensus_k), 0)
             out = next((j.consensus_out for j in mem if j.consensus_out), None)
             if k > len(mem):
@@ -292,21 +277,20 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                     if j.genome and j.genome not in loaded:
                         loaded[j.genome] = engine.genome_load(read_fasta(j.genome))
                 gids = [loaded[j.genome] if j.genome else -1 for j in jobs]
-            prof = None
-            if any(j.profile for j in jobs):
-                par = next(j.profile for j in jobs if j.profile)
-                prof = {"want": [1 if j.profile else 0 for j in jobs], "window": par[0], "n_pos_bins": par[1], "n_af_bins": par[2],
-                        "points": [j.points_out if j.profile else None for j in jobs]}
+            # the passes with parameters: the tuple the jobs agreed on, and who wants the pass
+            par = {f: next((getattr(j, f) for j in jobs if getattr(j, f)), None) for f in ("profile", "strata", "boot")}
+            want = lambda f: [1 if getattr(j, f) else 0 for j in jobs]
+            prof = strat = bt = None
+            if par["profile"]:
+                prof = dict(zip(("window", "n_pos_bins", "n_af_bins"), par["profile"]), want=want("profile"),
+                            points=[j.points_out if j.profile else None for j in jobs])
                 for path in [x for x in prof["points"] if x]:
                     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            strat = None
-            if any(j.strata for j in jobs):
-                sid = engine.strata_load(next(j.strata for j in jobs if j.strata))
-                strat = {"id": sid, "want": [1 if j.strata else 0 for j in jobs]}
-            bt = None
-            if any(j.boot for j in jobs):
-                par = next(j.boot for j in jobs if j.boot)
-                bt = {"want": [1 if j.boot else 0 for j in jobs], "window": par[0], "n_win": par[1], "n_rep": par[2], "seed": par[3]}
+            if par["strata"]:
+                sid = engine.strata_load(par["strata"])
+                strat = {"id": sid, "want": want("strata")}
+            if par["boot"]:
+                bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
                                                 global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt)
             if vt is not None:

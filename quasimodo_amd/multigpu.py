@@ -15,6 +15,7 @@ The parent never touches a GPU: it writes the job list to a spec file, starts on
 (`python -m quasimodo_amd.multigpu <spec>`, quasimodo_amd.launch.spawn_ranks; children rendezvous on 127.0.0.1) and, when
 all of them have left with status 0, puts the ranks' rows together.
 """
+import dataclasses
 import datetime
 import importlib
 import os
@@ -121,13 +122,11 @@ def run_rank(jobs, rank, world, backend="nccl", body=None, n_bins=256, alleles=N
     where = {}
     for r, sh in enumerate(shards):   # a truth-side group is joined on one GPU: its members must have been dealt to one rank
         for i in sh:
-            if jobs[i].group is not None and where.setdefault(jobs[i].group, r) != r:
-                from .workflow import WorkflowError
-                raise WorkflowError("truth-side group %r: its VCFs are not all on one rank (deal the VCFs by group)" % jobs[i].group)
-            vg = getattr(jobs[i], "vote_group", None)
-            if vg is not None and where.setdefault(("votes", vg), r) != r:
-                from .workflow import WorkflowError
-                raise WorkflowError("vote group %r: its VCFs are not all on one rank (deal the VCFs by group)" % vg)
+            for field, what in (("group", "truth-side"), ("vote_group", "vote")):
+                lab = getattr(jobs[i], field, None)
+                if lab is not None and where.setdefault((field, lab), r) != r:
+                    from .workflow import WorkflowError
+                    raise WorkflowError("%s group %r: its VCFs are not all on one rank (deal the VCFs by group)" % (what, lab))
     device = 0 if same_device else rank
     keys, slot = truth_layout(jobs)
     opts = dict(n_bins=n_bins, alleles=alleles, strict=strict, slots=[slot[i] for i in mine], n_slots=len(keys), backend=backend,
@@ -218,10 +217,7 @@ def extract_many_sharded(jobs, gpus, backend="nccl", body=None, n_bins=256, alle
         _paths(j)
     timeout = DEFAULT_TIMEOUT if timeout is None else timeout
     with tempfile.TemporaryDirectory(prefix="qmvt_mgpu_") as tmp:
-        spec = {"jobs": [dict(vcf_file=j.vcf_file, snp_file=j.snp_file, mode=j.mode, outdir=j.outdir, caller=j.caller, genome=j.genome,
-                              fn_out=j.fn_out, group=j.group, missed_out=j.missed_out, profile=j.profile, points_out=j.points_out, strata=j.strata, boot=j.boot,
-                              vote_group=j.vote_group, consensus_k=j.consensus_k, consensus_out=j.consensus_out)
-                         for j in jobs],
+        spec = {"jobs": [dataclasses.replace(j, stats={}) for j in jobs],   # every field a worker's Job needs, whatever passes ask
                 "world": gpus, "backend": backend, "body": body, "n_bins": n_bins, "alleles": alleles, "strict": strict,
                 "same_device": same_device, "result": os.path.join(tmp, "result.pkl"), "groups": groups, "post": post,
                 "post_args": post_args, "timeout": timeout}
@@ -252,9 +248,9 @@ def _main(argv):
         spec = pickle.load(fh)
     import torch
     import torch.distributed as dist
-    from .extract import Job, _paths
+    from .extract import _paths
     world, backend = spec["world"], spec["backend"]
-    jobs = [Job(**d) for d in spec["jobs"]]
+    jobs = spec["jobs"]
     for j in jobs:
         _paths(j)
     tmo = datetime.timedelta(seconds=max(60.0, float(spec.get("timeout") or DEFAULT_TIMEOUT)))

@@ -1,0 +1,45 @@
+"""The opt-in passes over a finished batch: one description per pass, and the one rule for which of them
+may share a call -- motifs with profile; every other pass runs in a call of its own."""
+from collections import namedtuple
+
+# name: the pass, and Engine.extract_files' keyword but for motifs (`genomes`); fields: the Job fields that ask for it;
+# keywords: extract_many's; flag: the CLI's, for messages; agree: what to say when the jobs of a call name different parameter
+# tuples in Job.<name> (None: the pass has none); shares: the passes it may share a call with
+Pass = namedtuple("Pass", "name fields keywords flag agree shares")
+PASSES = (
+    Pass("motifs", ("genome",), ("genomes",), "--mutation-context", None, ("profile",)),
+    Pass("truthside", ("fn_out", "group"), ("fn", "groups"), "--truth-side", None, ()),
+    Pass("profile", ("profile",), ("profile",), "--snp-profile",
+         "profile: the profiled jobs of one call share one window and one pair of bin counts", ("motifs",)),
+    Pass("strata", ("strata",), ("strata",), "--strata", "strata: the stratified jobs of one call share one strata set", ()),
+    Pass("boot", ("boot",), ("boot",), "--bootstrap",
+         "boot: the resampled jobs of one call share one window, window count, replicate count and seed", ()),
+    Pass("votes", ("vote_group",), ("votes",), "--votes", None, ()),
+)
+
+
+class SharedCallError(ValueError):
+    """two passes that do not share a call; .flags: their CLI names"""
+
+    def __init__(self, a, b):
+        said = lambda p: p.name if p.keywords == (p.name,) else "%s (%s)" % (p.name, " / ".join(p.keywords))
+        ValueError.__init__(self, "%s does not combine with %s in one call: it runs in a call of its own" % (said(a), said(b)))
+        self.flags = (a.flag, b.flag)
+
+    def for_cli(self):
+        return "%s cannot be combined with %s: it runs in a call of its own." % self.flags
+
+
+def check_shared_call(requested):
+    """requested: names of the passes one call is asked for.  Raises SharedCallError for the first pair that may not share it
+    (the later pass of PASSES named first)."""
+    want = [p for p in PASSES if p.name in requested]
+    for i, a in enumerate(want):
+        for b in want[:i]:
+            if b.name not in a.shares:
+                raise SharedCallError(a, b)
+
+
+def requested_by(jobs):
+    """the passes the fields of these Jobs ask for"""
+    return {p.name for p in PASSES if any(getattr(j, f) not in (None, "") for j in jobs for f in p.fields)}

@@ -152,6 +152,15 @@ def hcmv_rank_post(engine, jobs, indices, args):
     return {"overlap": out}
 
 
+def _shared_call(**asked):
+    """the passes the flags ask for may share the run's one call (passes.check_shared_call), said with the CLI's names"""
+    from .passes import SharedCallError, check_shared_call
+    try:
+        check_shared_call({name for name, on in asked.items() if on})
+    except SharedCallError as e:
+        raise WorkflowError(e.for_cli()) from None
+
+
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
                          votes=False, consensus_vcf=None):
@@ -169,32 +178,27 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     snp_profile: True or {"window", "n_pos_bins", "n_af_bins"} (the rule's first output): the profile pass runs
     behind the classification; final_tables/{mix}.{caller}.snp.profile.tsv and ...snp.profile.afsweep.tsv are written for every
     caller and mix (`-1-0` left out, `-0-1` as FP only) and callers/{caller}/profile/{sample}.{ref}.{caller}.points.tsv for
-    every profiled sample.  Combines with mutation_context, not with truth_side.
+    every profiled sample.
     strata: a list of (name, starts, ends) BED strata (quasimodo_amd.strata): the counts per stratum are taken
     behind the classification and final_tables/caller_performance_strata.tsv is written (per caller x sample one row per
-    stratum, then outside, then nokey).  Combines with none of the three above.
+    stratum, then outside, then nokey).
     bootstrap: a replicate count or {"n_rep", "window", "n_win", "seed"} (quasimodo_amd.bootstrap): the window
     counts and the replicates are taken behind the classification; final_tables/caller_performance_ci.tsv (percentile
     intervals of Precision, Recall and F1 per caller x sample) and caller_performance_ci_pairs.tsv (the F1 difference of every
-    pair of callers on a mixed sample, over the shared draws) are written.  n_win is raised to cover the truth files' largest
-    POS.  Combines with none of the four above.
+    pair of callers on a mixed sample, over the shared draws) are written.  n_win is raised to cover the truth files' largest POS.
     votes: k-of-n caller consensus (quasimodo_amd.consensus): all callers of the run form one vote group per mixed
     sample; final_tables/caller_consensus.tsv (TP, FP, FN, Precision, Recall, F1 of "at least k of n callers") and
     caller_private.tsv (what each caller alone calls) are written.  consensus_vcf=K (implies votes) also writes
-    snp/consensus/{sample}.{ref}.k{K}.vcf; K above the sample's caller count is a WorkflowError that names the sample.  Combines
-    with none of the five above."""
+    snp/consensus/{sample}.{ref}.k{K}.vcf; K above the sample's caller count is a WorkflowError that names the sample.
+    Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
-    if votes and (bootstrap is not None or strata is not None or mutation_context is not None or truth_side or snp_profile):
-        raise WorkflowError("--votes cannot be combined with --bootstrap, --strata, --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
+    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
+                 truthside=truth_side, profile=snp_profile)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
-    if bootstrap is not None and (strata is not None or mutation_context is not None or truth_side or snp_profile):
-        raise WorkflowError("--bootstrap cannot be combined with --strata, --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
     if strata is not None:
         from .strata import freeze
-        if mutation_context is not None or truth_side or snp_profile:
-            raise WorkflowError("--strata cannot be combined with --mutation-context, --truth-side or --snp-profile: it runs in a call of its own.")
         try:
             strata = freeze(strata)
         except ValueError as e:
@@ -202,8 +206,6 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     prof = None
     if snp_profile:
         from .afprofile import DEFAULTS
-        if truth_side:
-            raise WorkflowError("--snp-profile and --truth-side cannot be combined: the truth-side view runs in a call of its own.")
         opts = dict(DEFAULTS)
         opts.update({k: int(v) for k, v in (snp_profile.items() if isinstance(snp_profile, dict) else ()) if v is not None})
         prof = (opts["window"], opts["n_pos_bins"], opts["n_af_bins"])
@@ -316,14 +318,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                     j.consensus_out = os.path.join(snp_dir, "consensus", "%s.%s.k%d.vcf" % (s, SAMPLE_REF[s], int(consensus_vcf)))
     cmp_callers = [c for c in FP_COMPARED if c in callers]
     tables = os.path.join(results, "final_tables")
-    if gpus is not None and (int(gpus) > 1 or _body):
-        if engine is not None:
-            raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
-        from .multigpu import extract_many_sharded
-        groups = [[i for i, (c, s) in enumerate(meta) if s == smp] for smp in samples]
-        jobs, res = extract_many_sharded(jobs, int(gpus), backend=_backend, body=_body, same_device=_same_device, groups=groups,
-                                         post="quasimodo_amd.workflow:hcmv_rank_post",
-                                         post_args=dict(meta=meta, cmp_callers=cmp_callers, snp_dir=snp_dir))
+
+    def write_tables(jobs):   # the tables of the rows and of every pass of the run: the same on one GPU and on several
         os.makedirs(tables, exist_ok=True)
         _flag_truth_rows(jobs)
         write_caller_performance(os.path.join(tables, "caller_performance.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
@@ -340,6 +336,15 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
         if votes:
             _write_votes(meta, jobs, tables, mixed)
+    if gpus is not None and (int(gpus) > 1 or _body):
+        if engine is not None:
+            raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
+        from .multigpu import extract_many_sharded
+        groups = [[i for i, (c, s) in enumerate(meta) if s == smp] for smp in samples]
+        jobs, res = extract_many_sharded(jobs, int(gpus), backend=_backend, body=_body, same_device=_same_device, groups=groups,
+                                         post="quasimodo_amd.workflow:hcmv_rank_post",
+                                         post_args=dict(meta=meta, cmp_callers=cmp_callers, snp_dir=snp_dir))
+        write_tables(jobs)
         if mixed and len(cmp_callers) >= 2:
             reg = {}
             for e in res["extras"]:
@@ -355,28 +360,12 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         engine = Engine(int(os.environ.get("QM_DEVICE", "0")))
     try:
         extract_many(jobs, engine=engine)                                # extractTP, one batch
-        os.makedirs(os.path.join(results, "final_tables"), exist_ok=True)
-        _flag_truth_rows(jobs)
-        write_caller_performance(os.path.join(results, "final_tables", "caller_performance.tsv"),
-                                 [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
-        _write_snp_rocs(meta, jobs, snp_dir)
-        if mutation_context is not None:
-            _write_mutation_context(meta, jobs, os.path.join(results, "final_tables"), callers, mixes)
-        if prof is not None:
-            _write_snp_profile(meta, jobs, os.path.join(results, "final_tables"), callers, mixes, prof[0])
-        if strata is not None:
-            _write_strata(meta, jobs, os.path.join(results, "final_tables"), strata)
-        if boot is not None:
-            _write_bootstrap(meta, jobs, os.path.join(results, "final_tables"))
-        if truth_side:
-            _write_caller_snp_venn(meta, jobs, os.path.join(results, "final_tables"), callers, mixed)
-        if votes:
-            _write_votes(meta, jobs, os.path.join(results, "final_tables"), mixed)
+        write_tables(jobs)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
         if mixed and len(cmp_callers) >= 2:                              # compareFP (counts only)
             files = {s: {c: j.fp_out for (c, ss), j in zip(meta, jobs) if ss == s and c in cmp_callers} for s in mixed}
             reg = fp_overlap_tables(engine, files, cmp_callers)
-            write_fp_overlap(os.path.join(results, "final_tables", "snpcaller_fp_snp_compare.txt"), reg, cmp_callers)
+            write_fp_overlap(os.path.join(tables, "snpcaller_fp_snp_compare.txt"), reg, cmp_callers)
     finally:
         if own:
             engine.close()
@@ -579,26 +568,21 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
     final_tables/caller_snp_venn.tsv is written, more are told so and get their FN files only.
-    strata: a list of (name, starts, ends) BED strata: final_tables/snpcall_benchmark_strata.txt is written; not
-    together with truth_side.
+    strata: a list of (name, starts, ends) BED strata: final_tables/snpcall_benchmark_strata.txt is written.
     bootstrap: a replicate count or {"n_rep", "window", "n_win", "seed"}: final_tables/snpcall_benchmark_ci.txt
-    is written; not together with truth_side or strata.
+    is written.
     votes: the labels form one vote group: final_tables/caller_consensus.tsv and caller_private.tsv (sample
     "custom"); more than 32 labels (or pure-strain names) are told so and get no table.  consensus_vcf=K (implies votes) also writes
-    snp/consensus/custom.k{K}.vcf; K above the label count is a WorkflowError.  Not together with the three above."""
+    snp/consensus/custom.k{K}.vcf; K above the label count is a WorkflowError.
+    Each of the four runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
     from .truthside import MAX_GROUP
     from .consensus import MAX_GROUP as VOTE_MAX
     votes = bool(votes) or consensus_vcf is not None
-    if votes and (bootstrap is not None or truth_side or strata is not None):
-        raise WorkflowError("--votes cannot be combined with --bootstrap, --truth-side or --strata: it runs in a call of its own.")
+    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
-    if bootstrap is not None and (truth_side or strata is not None):
-        raise WorkflowError("--bootstrap cannot be combined with --truth-side or --strata: it runs in a call of its own.")
     if strata is not None:
         from .strata import freeze
-        if truth_side:
-            raise WorkflowError("--strata cannot be combined with --truth-side: it runs in a call of its own.")
         try:
             strata = freeze(strata)
         except ValueError as e:

@@ -397,6 +397,37 @@ def test_extract_many_profile_matches_the_written_files(engine, tmp_path):
     assert not [f for f in os.listdir(str(tmp_path / "points")) if ".tmp." in f]
 
 
+def test_extract_many_genomes_and_profile_in_one_call_match_a_call_each(engine, tmp_path):
+    """The one pair of passes that shares a call (qm_extract_files_profile takes the genome ids too): the spectra, the profiles and
+    the three VCFs of every job are those of a call with genomes= alone and of a call with profile= alone."""
+    from quasimodo_amd.extract import extract_many
+    from test_gpu_motifs import random_genome
+    genome = random_genome(np.random.default_rng(9606), 240_000, lower=0.1, nfrac=0.002)
+    fa = tmp_path / "g.fa"
+    fa.write_bytes(b">seeded test genome\n" + b"\n".join(genome[i:i + 70] for i in range(0, len(genome), 70)) + b"\n")
+    runs = {}
+    for name in ("both", "genomes", "profile"):
+        jobs = _golden_jobs(str(tmp_path / name))
+        want = [0 if os.path.basename(j.vcf_file).split(".")[0].endswith("-1-0") else 1 for j in jobs]
+        kw = {} if name == "profile" else {"genomes": [str(fa)] * len(jobs)}
+        if name != "genomes":
+            kw["profile"] = dict(PAR, want=want)
+        runs[name] = extract_many(jobs, engine=engine, **kw)
+    seen_motifs = seen_grid = False
+    for b, g, p in zip(runs["both"], runs["genomes"], runs["profile"]):
+        np.testing.assert_array_equal(b.stats["motifs"], g.stats["motifs"], err_msg=b.vcf_file)
+        seen_motifs = seen_motifs or bool(b.stats["motifs"].any())
+        assert ("af_grid" in b.stats) == ("af_grid" in p.stats) and "af_grid" not in g.stats and "motifs" not in p.stats
+        if "af_grid" in p.stats:
+            np.testing.assert_array_equal(b.stats["af_grid"], p.stats["af_grid"], err_msg=b.vcf_file)
+            np.testing.assert_array_equal(b.stats["af_extra"], p.stats["af_extra"], err_msg=b.vcf_file)
+            seen_grid = seen_grid or bool(b.stats["af_grid"].any())
+        for other in (g, p):
+            for x, y in ((b.filtered_out, other.filtered_out), (b.fp_out, other.fp_out)) + (((b.tp_out, other.tp_out),) if b.tp_out else ()):
+                assert open(x, "rb").read() == open(y, "rb").read(), (x, y)
+    assert seen_motifs and seen_grid
+
+
 def _tree(root):
     out = {}
     for d, _, fs in os.walk(root):
