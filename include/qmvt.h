@@ -397,6 +397,47 @@ int qm_batch_vote_groups(qm_batch* b);
 /* with qm_batch_set_timing on: milliseconds of the latest qm_batch_votes between HIP events on its stream -- [0] k_vote_truth,
  * [1] k_vote_keys + k_vote_segs, [2] the four radix passes, [3] k_vote_heads + k_vote_scan + k_vote_runs.  Waits for the pass. */
 int qm_batch_vote_timings(qm_batch* b, float* ms4);
+/* ---- near-miss classes: why a line is FP and a truth key FN --------------------------------------------
+ * One parameter, `radius`, 0 .. QM_NM_MAX_RADIUS.  A record has a comparable key iff it has neither QM_F_NOKEY nor alleles that
+ * are not single bases (key = pos << 4 | ref << 2 | alt), and a usable position iff it has no QM_F_NOKEY.
+ * Record side: every FP line of a VCF (kept, no TP line; QM_S_FP_LINES of them) gets the first class that applies --
+ *   QM_NM_R_IDCOL    comparable key, and the key is in the truth set: FP by its text alone (the ID column is not `.`)
+ *   QM_NM_R_ALLELE   comparable key; the truth set has a key with the same pos and ref base and another alt
+ *   QM_NM_R_REFBASE  comparable key; the truth set has keys at the same pos, none with this ref base
+ *   QM_NM_R_NEAR     comparable key, no truth key at pos, a truth key with 1 <= |dpos| <= radius
+ *   QM_NM_R_ISOLATED comparable key, none of the above
+ *   QM_NM_R_NOKEY    no comparable key (pos is not consulted)
+ * Truth side: every distinct truth key whose bit in the VCF's hit bitmap is clear gets the first class that applies (records
+ * with QM_F_NOKEY are ignored) --
+ *   QM_NM_T_FILTERED some record that is not kept carries exactly this comparable key
+ *   QM_NM_T_ALLELE   some record, kept or not, with a comparable key has the same pos and ref base and another alt
+ *   QM_NM_T_POSITION some record with a usable position sits at the same pos (another ref base, or alleles that are not single bases)
+ *   QM_NM_T_NEAR     some record with a usable position has 1 <= |dpos| <= radius
+ *   QM_NM_T_UNCALLED none of the above
+ * A hit key, and a record that is no FP line, has QM_NM_NONE.
+ * qm_batch_nearmiss: asynchronous on `stream` (NULL = the context's own); it waits for the previous qm_batch_nearmiss of the
+ *   batch before it reuses the outputs, which are allocated on the first call.  QM_E_INVAL for a radius outside
+ *   0 .. QM_NM_MAX_RADIUS; QM_E_STATE unless the latest qm_batch_run was finished and a qm_batch_truth_hits lies behind it
+ *   (so: single-base batches only).  May be repeated with another radius.
+ * qm_batch_get_nearmiss: waits for the pass, then copies the counts (either pointer may be NULL); rec[v] sums to QM_S_FP_LINES
+ *   of VCF v, tru[v] to T' minus the popcount of its hit bitmap.  QM_E_STATE if the batch ran since or no pass was made, as
+ *   for the two getters below.
+ * qm_batch_get_nearmiss_cls: one class byte per record of the VCF, in input order.
+ * qm_batch_get_nearmiss_truth: one class byte per key of the VCF's truth set's sorted distinct keys (T' of them), decoded on the
+ *   host from the VCF's four bit planes and its hit bitmap. */
+#define QM_NM_MAX_RADIUS 64
+#define QM_NM_R_CLASSES 6
+#define QM_NM_T_CLASSES 5
+#define QM_NM_NONE 255
+enum { QM_NM_R_IDCOL = 0, QM_NM_R_ALLELE = 1, QM_NM_R_REFBASE = 2, QM_NM_R_NEAR = 3, QM_NM_R_ISOLATED = 4, QM_NM_R_NOKEY = 5 };
+enum { QM_NM_T_FILTERED = 0, QM_NM_T_ALLELE = 1, QM_NM_T_POSITION = 2, QM_NM_T_NEAR = 3, QM_NM_T_UNCALLED = 4 };
+int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream);
+int qm_batch_get_nearmiss(qm_batch* b, uint64_t* rec /*[n_vcf][QM_NM_R_CLASSES] or NULL*/, uint64_t* tru /*[n_vcf][QM_NM_T_CLASSES] or NULL*/);
+int qm_batch_get_nearmiss_cls(qm_batch* b, int vcf, uint8_t* out /*[n_records]*/);
+int qm_batch_get_nearmiss_truth(qm_batch* b, int vcf, uint8_t* out /*[T']*/);
+/* with qm_batch_set_timing on: milliseconds of the latest qm_batch_nearmiss between HIP events on its stream -- [0]
+ * k_nearmiss_records, [1] k_nearmiss_truth.  Waits for the pass. */
+int qm_batch_nearmiss_timings(qm_batch* b, float* ms2);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -670,6 +711,33 @@ typedef struct qm_votes_args {
 int qm_extract_files_votes(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                            qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                            void* global_dev, const qm_votes_args* votes);
+
+/* qm_extract_files_ex plus the near-miss classes over its batch (single-base mode only: QM_E_STATE otherwise).
+ * Jobs with want[j] != 0 take part (pure-strain jobs never do); one radius per call (outside 0 .. QM_NM_MAX_RADIUS: QM_E_INVAL).
+ * Behind the batch's finish the call runs qm_batch_truth_hits and qm_batch_nearmiss; rec / tru: qm_batch_get_nearmiss' rows per
+ * job (zero for jobs that take no part).
+ * fp_why_out[j] (array or entries may be NULL): "#line\tPOS\tREF\tALT\tQUAL\tclass\n", then one row per FP line of the VCF in
+ * file order -- the 1-based line number in the input file, the line's own text of the four columns, the class name (idcol,
+ * allele, refbase, near, isolated, nokey).
+ * fn_why_out[j] (array or entries may be NULL): "#POS\tREF\tALT\tclass\n", then exactly the rows fn_out of
+ * qm_extract_files_truthside would hold for the job, in the same order, as their POS / REF / ALT text and the class name of
+ * their key (filtered, allele, position, near, uncalled); `.` for a row the device cannot hold.
+ * Both files are written atomically (temp file + rename).  A job that asks for fn_why_out and holds a kept line without a
+ * comparable key (QM_F_NOKEY) is refused with QM_E_NONCANON and a message that names the file and the line, as
+ * qm_extract_files_truthside does and for its reason; fp_why_out alone is not refused, such lines are class nokey.
+ * The VCF outputs, stats and roc are those of qm_extract_files_ex. */
+typedef struct qm_nearmiss_args {
+  const uint8_t* want;              /* [n_jobs] 0/1 */
+  int32_t radius;
+  int32_t reserved;
+  uint64_t* rec;                    /* [n_jobs][QM_NM_R_CLASSES] */
+  uint64_t* tru;                    /* [n_jobs][QM_NM_T_CLASSES] */
+  const char* const* fp_why_out;    /* [n_jobs] or NULL */
+  const char* const* fn_why_out;    /* [n_jobs] or NULL */
+} qm_nearmiss_args;
+int qm_extract_files_nearmiss(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                              qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                              void* global_dev, const qm_nearmiss_args* nearmiss);
 
 /* qm_extract_files_motifs plus the allele-frequency profile: both halves of rule mutationcontext in one call.
  * genome_id / motifs may be NULL (no spectra).  Jobs with want[j] != 0 have their INFO column scanned (qm_vcf_scan_af) and

@@ -36,6 +36,10 @@ QM_BOOT_RECORDS = 1
 QM_BOOT_TRUTH = 2
 QM_VOTE_GROUP_MAX = 32
 QM_VOTE_SLOTS = 33
+QM_NM_MAX_RADIUS = 64
+QM_NM_R_CLASSES = 6
+QM_NM_T_CLASSES = 5
+QM_NM_NONE = 255
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -57,6 +61,7 @@ EXPORTS = (
     "qm_extract_files_strata",
     "qm_batch_boot", "qm_batch_get_boot", "qm_boot_draws", "qm_extract_files_boot",
     "qm_batch_votes", "qm_batch_get_votes", "qm_batch_get_vote_keys", "qm_batch_vote_groups", "qm_batch_vote_timings", "qm_extract_files_votes",
+    "qm_batch_nearmiss", "qm_batch_get_nearmiss", "qm_batch_get_nearmiss_cls", "qm_batch_get_nearmiss_truth", "qm_batch_nearmiss_timings", "qm_extract_files_nearmiss",
 )
 
 
@@ -106,6 +111,12 @@ class VotesArgs(C.Structure):
                 ("private_tp", C.c_void_p), ("private_fp", C.c_void_p), ("consensus_k", C.c_void_p), ("consensus_out", C.POINTER(C.c_char_p))]
 
 
+class NearmissArgs(C.Structure):
+    """include/qmvt.h qm_nearmiss_args"""
+    _fields_ = [("want", C.c_void_p), ("radius", C.c_int32), ("reserved", C.c_int32), ("rec", C.c_void_p), ("tru", C.c_void_p),
+                ("fp_why_out", C.POINTER(C.c_char_p)), ("fn_why_out", C.POINTER(C.c_char_p))]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -126,7 +137,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -319,6 +330,13 @@ def lib():
     L.qm_batch_vote_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_extract_files_votes.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                          C.POINTER(VotesArgs)]
+    L.qm_batch_nearmiss.argtypes = [vp, i32, vp]
+    L.qm_batch_get_nearmiss.argtypes = [vp, vp, vp]
+    L.qm_batch_get_nearmiss_cls.argtypes = [vp, i32, vp]
+    L.qm_batch_get_nearmiss_truth.argtypes = [vp, i32, vp]
+    L.qm_batch_nearmiss_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_extract_files_nearmiss.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                            C.POINTER(NearmissArgs)]
     _lib = L
     return L
 

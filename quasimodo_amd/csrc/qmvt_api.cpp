@@ -28,6 +28,7 @@
 #include "qmvt_strata.h"
 #include "qmvt_votes.h"
 #include "qmvt_boot.h"
+#include "qmvt_nearmiss.h"
 
 using namespace qm;
 
@@ -768,6 +769,18 @@ struct qm_batch {
   bool vt_timed = false;              // the latest qm_batch_votes recorded them
   int32_t votes_groups = 0;
   bool votes_valid = false;           // qm_batch_votes was called behind the latest run
+  // qm_batch_nearmiss (lazy): the four bit planes, each laid out like d_hits (plane p of VCF v starts at word
+  // p * h_hit_off[n_vcf] + h_hit_off[v]), one class byte per record laid out like pos, the [n_vcf][6] and [n_vcf][5] counts one
+  // behind the other, the T' of every VCF for k_nearmiss_truth; ev_nm says when the pass is done
+  DevBuf<uint32_t> nm_planes;
+  DevBuf<uint8_t> nm_rcls;
+  DevBuf<uint64_t> nm_out;
+  DevBuf<int64_t> nm_tn;
+  bool nm_tn_uploaded = false;
+  hipEvent_t ev_nm = nullptr;
+  hipEvent_t ev_nmt[3] = {};          // qm_batch_set_timing: around k_nearmiss_records and k_nearmiss_truth
+  bool nm_timed = false;              // the latest qm_batch_nearmiss recorded them
+  bool nm_valid = false;              // qm_batch_nearmiss was called behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -794,6 +807,8 @@ static void batch_free(qm_batch* b) {
   if (b->ev_strata) (void)hipEventDestroy(b->ev_strata);
   if (b->ev_boot) (void)hipEventDestroy(b->ev_boot);
   if (b->ev_votes) (void)hipEventDestroy(b->ev_votes);
+  if (b->ev_nm) (void)hipEventDestroy(b->ev_nm);
+  for (auto& e : b->ev_nmt) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -1124,6 +1139,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->strata_made = 0;
   b->boot_made = 0;
   b->votes_valid = false;
+  b->nm_valid = false;
   b->last_global = g;
   return QM_OK;
 }
@@ -2543,6 +2559,8 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
   if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
   else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
+  for (hipEvent_t e : {b->ev_strata, b->ev_boot, b->ev_votes, b->ev_nm})   // and the passes that read the hit bitmaps, on whatever stream
+    if (e) HIPCHK(hipStreamWaitEvent(st, e, 0));
   // (the one pass that does not open with pass_stream: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
   rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_intruth.grow((int64_t)mask_words, &b->dev_bytes);
@@ -2800,6 +2818,113 @@ extern "C" int qm_batch_get_vote_keys(qm_batch* b, int group, uint32_t* keys, ui
   const int64_t off = b->vt_koff[(size_t)group];
   if (n && keys) HIPCHK(hipMemcpy(keys, b->vt_k[1] + off, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (n && masks) HIPCHK(hipMemcpy(masks, b->vt_v[1] + off, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+// why a line is FP and a truth key FN: the near-miss classes of the finished batch
+extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
+  NEED_FINISHED(b, "qm_batch_nearmiss");
+  if (b->ext) return fail(QM_E_STATE, "qm_batch_nearmiss: allele-extended batches have no truth-side bitmaps (single-base batches only)");
+  if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_nearmiss: needs a qm_batch_truth_hits behind the latest run");
+  if (radius < 0 || radius > QM_NM_MAX_RADIUS) return fail(QM_E_INVAL, "qm_batch_nearmiss: radius %d (0 to %d)", radius, QM_NM_MAX_RADIUS);
+  qm_ctx* c = b->ctx;
+  int rc = truths_live(b, "qm_batch_nearmiss");
+  if (rc != QM_OK) return rc;
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_nm, &st);
+  if (rc != QM_OK) return rc;
+  const size_t nv = (size_t)b->n_vcf;
+  const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);   // as d_hits
+  const size_t out_words = std::max<size_t>(nv, 1) * (NM_R_CLASSES + NM_T_CLASSES);
+  rc = b->nm_planes.grow((int64_t)(NM_PLANES * hw), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nm_rcls.grow(b->L.n_pad, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nm_out.grow((int64_t)out_words, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nm_tn.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc != QM_OK) { b->nm_valid = false; return rc; }
+  b->nm_valid = false;   // from here on the outputs are rewritten
+  if (!b->nm_tn_uploaded && nv) {
+    HIPCHK(hipMemcpy(b->nm_tn, b->h_hit_tn.data(), nv * 8, hipMemcpyHostToDevice));
+    b->nm_tn_uploaded = true;
+  }
+  HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+  HIPCHK(hipMemsetAsync(b->nm_planes, 0, NM_PLANES * hw * 4, st));
+  HIPCHK(hipMemsetAsync(b->nm_out, 0, out_words * 8, st));
+  NearmissParams P;
+  P.spans = b->d_spans; P.truths = c->d_truths; P.hit_off = b->d_hit_off;
+  P.pos = b->pos; P.anib = b->anib; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  P.planes = b->nm_planes; P.plane_words = (int64_t)hw; P.rcls = b->nm_rcls;
+  P.rec = reinterpret_cast<unsigned long long*>(b->nm_out.p);
+  P.n_spans = (int32_t)b->L.spans.size(); P.radius = radius;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_nmt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->nm_timed = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_nmt[0], st));
+  launch_nearmiss_records(P, st);
+  if (T) HIPCHK(hipEventRecord(b->ev_nmt[1], st));
+  NearmissTruthParams Q;
+  Q.hit_off = b->d_hit_off; Q.hit_tn = b->nm_tn; Q.hits = b->d_hits; Q.planes = b->nm_planes; Q.plane_words = (int64_t)hw;
+  Q.tru = P.rec + std::max<size_t>(nv, 1) * NM_R_CLASSES;
+  int64_t max_words = 0;
+  for (size_t v = 0; v < nv; ++v) max_words = std::max<int64_t>(max_words, b->h_hit_off[v + 1] - b->h_hit_off[v]);
+  launch_nearmiss_truth(Q, b->n_vcf, max_words, st);
+  if (T) { HIPCHK(hipEventRecord(b->ev_nmt[2], st)); b->nm_timed = true; }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(b->ev_nm, st));
+  b->nm_valid = true;
+  return QM_OK;
+}
+#define NEED_NEARMISS(b, name) \
+  if (!(b)) return fail(QM_E_INVAL, name ": NULL batch"); \
+  if (!(b)->nm_valid) return fail(QM_E_STATE, name ": no qm_batch_nearmiss behind the latest run")
+extern "C" int qm_batch_nearmiss_timings(qm_batch* b, float* ms2) {
+  NEED_NEARMISS(b, "qm_batch_nearmiss_timings");
+  if (!ms2) return fail(QM_E_INVAL, "qm_batch_nearmiss_timings: NULL");
+  if (!b->nm_timed) return fail(QM_E_STATE, "qm_batch_nearmiss_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_nmt[2]));
+  for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(ms2 + i, b->ev_nmt[i], b->ev_nmt[i + 1]));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_nearmiss(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  NEED_NEARMISS(b, "qm_batch_get_nearmiss");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_nm));
+  const size_t nv = (size_t)b->n_vcf;
+  if (!nv) return QM_OK;
+  if (rec) HIPCHK(hipMemcpy(rec, b->nm_out, nv * NM_R_CLASSES * 8, hipMemcpyDeviceToHost));
+  if (tru) HIPCHK(hipMemcpy(tru, b->nm_out + nv * NM_R_CLASSES, nv * NM_T_CLASSES * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_nearmiss_cls(qm_batch* b, int v, uint8_t* out) {
+  NEED_NEARMISS(b, "qm_batch_get_nearmiss_cls");
+  if (v < 0 || v >= b->n_vcf || !out) return fail(QM_E_INVAL, "qm_batch_get_nearmiss_cls: bad arguments");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_nm));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  if (d.n) HIPCHK(hipMemcpy(out, b->nm_rcls + d.off, (size_t)d.n, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_nearmiss_truth(qm_batch* b, int v, uint8_t* out) {
+  NEED_NEARMISS(b, "qm_batch_get_nearmiss_truth");
+  if (v < 0 || v >= b->n_vcf || !out) return fail(QM_E_INVAL, "qm_batch_get_nearmiss_truth: bad arguments");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_nm));
+  const int64_t off = b->h_hit_off[(size_t)v], words = b->h_hit_off[(size_t)v + 1] - off, tn = b->h_hit_tn[(size_t)v];
+  if (!words) return QM_OK;
+  const size_t hw = std::max<size_t>((size_t)b->h_hit_off[(size_t)b->n_vcf], 1);
+  std::vector<uint32_t> w((size_t)words * (NM_PLANES + 1));   // the hit words, then the four planes' (no per-key array on the device)
+  HIPCHK(hipMemcpy(w.data(), b->d_hits + off, (size_t)words * 4, hipMemcpyDeviceToHost));
+  for (int p = 0; p < NM_PLANES; ++p)
+    HIPCHK(hipMemcpy(w.data() + (size_t)(p + 1) * (size_t)words, b->nm_planes + (size_t)p * hw + (size_t)off, (size_t)words * 4, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < words; ++i) {
+    uint32_t x[NM_T_CLASSES];
+    nearmiss_truth_word(~w[(size_t)i], w[(size_t)(words + i)], w[(size_t)(2 * words + i)], w[(size_t)(3 * words + i)], w[(size_t)(4 * words + i)], x);
+    for (int64_t k = 32 * i; k < std::min<int64_t>(32 * i + 32, tn); ++k) {
+      uint8_t cls = (uint8_t)NM_NONE;
+      for (int t = 0; t < NM_T_CLASSES; ++t) if ((x[t] >> (k & 31)) & 1u) cls = (uint8_t)t;
+      out[k] = cls;
+    }
+  }
   return QM_OK;
 }
 // dst[i] += src[i] for device arrays (qm_extract_files_ex adds the per-truth sums of its batch into the caller's buffer)

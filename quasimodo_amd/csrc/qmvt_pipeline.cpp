@@ -184,8 +184,9 @@ int write_all_atomic(const char* path, const std::string& data) {
 // in `bits` (over the truth set's sorted distinct keys) is clear.  A row whose key the device cannot hold (POS spelled
 // non-canonically, a longer allele in mode 1) could only be matched by a kept line without a comparable key; the caller refuses
 // VCFs that have such lines, so the row is a missed one.
-int write_fn_file(const char* path, const TruthState& t, const uint32_t* bits) {
-  std::string head, rows;
+// (the rule itself: row(text, length, fields, field lengths, k) for every such row, k = the key's index among the truth set's
+// sorted distinct keys or -1 when the device cannot hold it; head gets the '#' lines)
+template <typename F> void missed_rows(const TruthState& t, const uint32_t* bits, std::string& head, F row) {
   const uint8_t* text = t.file.p;
   const size_t len = t.file.n;
   size_t off = 0;
@@ -209,15 +210,39 @@ int write_fn_file(const char* path, const TruthState& t, const uint32_t* bits) {
     const bool in_genome = t.mode == 0 ? (y >= 0 && z >= 0) : (n > 0 && !(fl[iy] == 1 && f[iy][0] == '.') && !(fl[iz] == 1 && f[iz][0] == '.'));
     if (!in_genome) continue;
     bool hit = false;
+    int64_t k = -1;
     uint32_t p = 0;
     if (y >= 0 && z >= 0 && ts_canon_pos(f[ix], fl[ix], &p)) {
       const uint32_t key = (p << 4) | ((uint32_t)y << 2) | (uint32_t)z;
       const auto it = std::lower_bound(t.keys.begin(), t.keys.end(), key);
-      if (it != t.keys.end() && *it == key && bits) { const size_t k = (size_t)(it - t.keys.begin()); hit = (bits[k >> 5] >> (k & 31)) & 1u; }
+      if (it != t.keys.end() && *it == key) {
+        k = (int64_t)(it - t.keys.begin());
+        if (bits) hit = (bits[(size_t)k >> 5] >> (k & 31)) & 1u;
+      }
     }
-    if (!hit) { rows.append((const char*)s, n); rows.push_back('\n'); }
+    if (!hit) row(s, n, f, fl, k);
   }
+}
+int write_fn_file(const char* path, const TruthState& t, const uint32_t* bits) {
+  std::string head, rows;
+  missed_rows(t, bits, head, [&](const uint8_t* s, size_t n, const uint8_t* const*, const size_t*, int64_t) { rows.append((const char*)s, n); rows.push_back('\n'); });
   return write_all_atomic(path, head + rows);
+}
+
+// ---- why-files of the near-miss pass ----
+const char* const NM_R_NAMES[QM_NM_R_CLASSES] = {"idcol", "allele", "refbase", "near", "isolated", "nokey"};
+const char* const NM_T_NAMES[QM_NM_T_CLASSES] = {"filtered", "allele", "position", "near", "uncalled"};
+// `#POS REF ALT class`, then exactly the rows the missed-variant list of the job holds, in its order: their POS / REF / ALT text
+// and the class of their key (tcls: one byte per sorted distinct key); `.` for a row the device cannot hold
+int write_fn_why_file(const char* path, const TruthState& t, const uint32_t* bits, const uint8_t* tcls) {
+  std::string head, rows = "#POS\tREF\tALT\tclass\n";
+  const int ix = t.mode == 0 ? 1 : 0, iy = t.mode == 0 ? 3 : 1, iz = t.mode == 0 ? 4 : 2;
+  missed_rows(t, bits, head, [&](const uint8_t*, size_t, const uint8_t* const* f, const size_t* fl, int64_t k) {
+    for (int i : {ix, iy, iz}) { rows.append((const char*)f[i], fl[i]); rows.push_back('\t'); }
+    rows.append(k >= 0 && tcls[k] < QM_NM_T_CLASSES ? NM_T_NAMES[tcls[k]] : ".");
+    rows.push_back('\n');
+  });
+  return write_all_atomic(path, rows);
 }
 
 // `Position Frequency type` of every counted record (kept by the class mask, single-base REF and ALT) of one profiled job: the
@@ -272,7 +297,7 @@ struct Passes {
   const int32_t* genome_id = nullptr;   // the motif pass: a genome id or -1 per job, with motifs_out
   uint64_t* motifs_out = nullptr;
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
-  const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr;
+  const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -535,6 +560,77 @@ int votes_pass(const PassCtx& c, const qm_votes_args* va, std::string& err) {
   return rc;
 }
 
+// ---- why a line is FP and a truth key FN ----
+// `#line POS REF ALT QUAL class`, then one row per FP line of the job in file order: the 1-based line number, the line's own
+// text of the four columns, the class of its record (rcls: one byte per record)
+int write_fp_why_file(const char* path, const JobState& s, const uint8_t* rcls) {
+  std::string out = "#line\tPOS\tREF\tALT\tQUAL\tclass\n";
+  const uint8_t* text = s.vcf.p;
+  const size_t len = s.vcf.n;
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    const int64_t r = rec++;
+    if (rcls[r] >= QM_NM_R_CLASSES) continue;
+    size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], len);
+    if (e > b && text[e - 1] == '\n') --e;
+    const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+    const uint8_t* q = text + b;
+    while (nf < 6) {
+      const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(text + e - q));
+      f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(text + e - q); ++nf;
+      if (!tb) break;
+      q = tb + 1;
+    }
+    out.append(std::to_string(i + 1));
+    for (int k : {1, 3, 4, 5}) { out.push_back('\t'); if (k < nf) out.append((const char*)f[k], fl[k]); }
+    out.push_back('\t');
+    out.append(NM_R_NAMES[rcls[r]]);
+    out.push_back('\n');
+  }
+  return write_all_atomic(path, out);
+}
+
+// the class counts of every wanted job, and the why-files of the jobs that name them
+int nearmiss_pass(const PassCtx& c, const qm_nearmiss_args* nm, std::string& err) {
+  auto want = [&](int j) { return !c.jobs[j].pure && nm->want[j] != 0; };
+  if (!nm || !c.any(want)) return QM_OK;
+  auto fp_path = [&](int j) { return want(j) && nm->fp_why_out ? nm->fp_why_out[j] : nullptr; };
+  auto fn_path = [&](int j) { return want(j) && nm->fn_why_out ? nm->fn_why_out[j] : nullptr; };
+  for (int j = 0; j < c.n_jobs; ++j)
+    if (fn_path(j) && c.J[(size_t)j].info.n_nokey_kept) return refuse_nokey(c.jobs[j].vcf_path, c.J[(size_t)j], "the explanation of the missed keys", err);
+  std::vector<uint64_t> rec(c.nv * QM_NM_R_CLASSES), tru(c.nv * QM_NM_T_CLASSES);
+  int rc = qm_batch_truth_hits(c.batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_nearmiss(c.batch, nm->radius, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_nearmiss(c.batch, rec.data(), tru.data());
+  if (rc == QM_OK) { c.scatter_rows(nm->rec, rec, QM_NM_R_CLASSES, want); c.scatter_rows(nm->tru, tru, QM_NM_T_CLASSES, want); }
+  struct WhyTask { int j; bool fn; std::vector<uint8_t> cls; std::vector<uint32_t> bits; };
+  std::vector<WhyTask> W;
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    const JobState& s = c.J[(size_t)j];
+    if (fp_path(j)) {
+      W.push_back({j, false, std::vector<uint8_t>((size_t)s.n_data + 1, (uint8_t)QM_NM_NONE), {}});
+      rc = qm_batch_get_nearmiss_cls(c.batch, s.batch_v, W.back().cls.data());
+    }
+    if (fn_path(j) && rc == QM_OK) {
+      const size_t tn = c.truth_of(j).keys.size();
+      W.push_back({j, true, std::vector<uint8_t>(tn + 1, (uint8_t)QM_NM_NONE), std::vector<uint32_t>((tn + 31) / 32 + 1, 0u)});
+      rc = qm_batch_get_nearmiss_truth(c.batch, s.batch_v, W.back().cls.data());
+      if (rc == QM_OK) rc = qm_batch_get_truth_hits(c.batch, s.batch_v, W.back().bits.data(), (int64_t)((tn + 31) / 32));
+    }
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  std::vector<int> wrc(W.size(), QM_OK);
+  parallel_for((int)W.size(), c.nthr, [&](int k) {
+    const WhyTask& w = W[(size_t)k];
+    wrc[(size_t)k] = w.fn ? write_fn_why_file(nm->fn_why_out[w.j], c.truth_of(w.j), w.bits.data(), w.cls.data())
+                          : write_fp_why_file(nm->fp_why_out[w.j], c.J[(size_t)w.j], w.cls.data());
+  });
+  for (size_t k = 0; k < W.size(); ++k)
+    if (wrc[k] != QM_OK) { err = std::string("cannot write ") + (W[k].fn ? nm->fn_why_out : nm->fp_why_out)[W[k].j]; return wrc[k]; }
+  return QM_OK;
+}
+
 }  // namespace
 
 extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
@@ -670,6 +766,23 @@ extern "C" int qm_extract_files_votes(qm_ctx* ctx, int n_jobs, const qm_file_job
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
+// the near-miss classes behind the worker: why the FP lines are FP and the missed truth keys missed
+extern "C" int qm_extract_files_nearmiss(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                         qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                         int n_slots, void* global_dev, const qm_nearmiss_args* nearmiss) {
+  const qm_nearmiss_args* nm = nearmiss;
+  if (!nm || (n_jobs > 0 && (!nm->want || !nm->rec || !nm->tru))) return fail(QM_E_INVAL, "qm_extract_files_nearmiss: NULL arguments");
+  if (nm->radius < 0 || nm->radius > QM_NM_MAX_RADIUS)
+    return fail(QM_E_INVAL, "qm_extract_files_nearmiss: radius " + std::to_string(nm->radius) + " (0 to " + std::to_string(QM_NM_MAX_RADIUS) + ")");
+  if (mode & QM_BATCH_ALLELES) return fail(QM_E_STATE, "qm_extract_files_nearmiss: allele-extended batches have no near-miss pass (single-base batches only)");
+  if (n_jobs > 0) {
+    memset(nm->rec, 0, sizeof(uint64_t) * QM_NM_R_CLASSES * (size_t)n_jobs);
+    memset(nm->tru, 0, sizeof(uint64_t) * QM_NM_T_CLASSES * (size_t)n_jobs);
+  }
+  Passes P; P.nm = nm;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
 static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict, qm_file_stats* stats,
                          uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot, int n_slots, void* global_dev, const Passes& P) {
   if (!ctx || n_jobs < 0 || (n_jobs && !jobs) || n_bins < 1 || n_bins > QM_MAX_BINS || (mode & ~(unsigned)QM_BATCH_ALLELES))
@@ -777,7 +890,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (k < 0) { truth_rc = (int)k; truth_msg = "qm_truth_scan failed for " + t.path; break; }
       const int rc = qm_truth_load(ctx, tp.data(), tr.data(), ta.data(), k, &t.tid);
       if (rc != QM_OK) { truth_rc = rc; truth_msg = qm_last_error(ctx); break; }
-      if (P.ts || P.va) {
+      if (P.ts || P.va || P.nm) {
         for (int64_t i = 0; i < k; ++i)
           if ((uint32_t)(tr[(size_t)i] | ta[(size_t)i]) < 4u) t.keys.push_back(((uint32_t)tp[(size_t)i] << 4) | ((uint32_t)tr[(size_t)i] << 2) | (uint32_t)ta[(size_t)i]);
         std::sort(t.keys.begin(), t.keys.end());
@@ -938,6 +1051,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = boot_pass(pc, P.ba, err);
       if (rc == QM_OK) rc = truthside_pass(pc, P.ts, err);
       if (rc == QM_OK) rc = votes_pass(pc, P.va, err);
+      if (rc == QM_OK) rc = nearmiss_pass(pc, P.nm, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;

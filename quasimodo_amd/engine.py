@@ -181,7 +181,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None, boot=None, votes=None):
+                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -204,6 +204,10 @@ class Engine:
         qm_extract_files_votes: the rows of grouped jobs gain `tp_votes`, `fp_votes` ([33] uint64), `private_tp`,
         `private_fp` ([32]; the same for every member, members in job order) and `vote_member` (the job's index in its group);
         the consensus VCFs of the groups with a level are written.
+        nearmiss: {"radius": 0 .. 64, "want": [0/1 per job], "fp_why": [path or None per job], "fn_why": [path or None per job]} --
+        qm_extract_files_nearmiss: wanted mixed-sample rows gain `nearmiss_rec` ([6] ints: the FP lines per class
+        nearmiss.RECORD_CLASSES) and `nearmiss_tru` ([5]: the missed truth keys per class nearmiss.TRUTH_CLASSES); the why-files
+        are written.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         from .passes import check_shared_call
@@ -213,7 +217,7 @@ class Engine:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
@@ -230,7 +234,7 @@ class Engine:
         entry, extra, unpack = self._L.qm_extract_files_ex, (), lambda k: {}
         for name, spec in specs.items():
             if spec is not None and not (name == "motifs" and profile is not None):
-                entry, extra, unpack = getattr(self, "_files_" + name)(n, spec, gids=gids, alleles=alleles)
+                entry, extra, unpack = getattr(self, "_files_" + name)(n, spec, gids=gids, alleles=alleles, file_jobs=file_jobs)
         check(entry(*args, *extra), self._h)
         rows = []
         for k in range(n):
@@ -324,6 +328,25 @@ class Engine:
             return {} if g < 0 else dict(zip(("tp_votes", "fp_votes", "private_tp", "private_fp"), (t[g].copy() for t in vtab)),
                                          vote_member=int((vgrp[:k] == g).sum()))
         return self._L.qm_extract_files_votes, (C.byref(va),), unpack
+
+    def _files_nearmiss(self, n, nearmiss, **kw):
+        nwant = _c([int(bool(w)) for w in nearmiss["want"]] or [0], np.uint8)
+        fpw, fnw = (list(nearmiss.get(k) or [None] * n) for k in ("fp_why", "fn_why"))
+        if (n and nwant.shape[0] != n) or len(fpw) != n or len(fnw) != n:
+            raise ValueError("nearmiss: %d want / %d fp_why / %d fn_why entries for %d jobs" % (len(nearmiss["want"]), len(fpw), len(fnw), n))
+        radius = int(nearmiss["radius"])
+        if not 0 <= radius <= _lib.QM_NM_MAX_RADIUS:
+            raise ValueError("nearmiss: radius %d (0 to %d)" % (radius, _lib.QM_NM_MAX_RADIUS))
+        nrec = np.zeros((max(n, 1), _lib.QM_NM_R_CLASSES), np.uint64)
+        ntru = np.zeros((max(n, 1), _lib.QM_NM_T_CLASSES), np.uint64)
+        enc = lambda x: None if x is None else os.fsencode(x)
+        fp_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in fpw])
+        fn_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in fnw])
+        na = _lib.NearmissArgs(_p(nwant), radius, 0, _p(nrec), _p(ntru), fp_arr, fn_arr)
+        pure = lambda k: bool(kw["file_jobs"][k].get("pure"))
+        unpack = lambda k: {"nearmiss_rec": [int(x) for x in nrec[k]], "nearmiss_tru": [int(x) for x in ntru[k]],
+                            "nearmiss_radius": radius} if nwant[k] and not pure(k) else {}
+        return self._L.qm_extract_files_nearmiss, (C.byref(na),), unpack
 
     def path_stats_total(self):
         """qm_path_stats_total: where the VCFs found out of order went, summed over every batch this context has finished
@@ -609,6 +632,41 @@ class Batch:
         keys, masks = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
         self._ck(self._L.qm_batch_get_vote_keys(self._h, int(g), _p(keys), _p(masks), int(keys.shape[0]), C.byref(n)))
         return keys[:n.value], masks[:n.value]
+
+    # -- near-miss classes of FP lines and missed truth keys --------
+    def nearmiss(self, radius, stream=None):
+        """qm_batch_nearmiss + qm_batch_get_nearmiss (needs truth_hits): (rec [n_vcf][6], tru [n_vcf][5]) uint64 -- the FP lines
+        of every VCF per class nearmiss.RECORD_CLASSES, its missed truth keys per class nearmiss.TRUTH_CLASSES"""
+        self._ck(self._L.qm_batch_nearmiss(self._h, int(radius), C.c_void_p(stream) if stream else None))
+        return self.nearmiss_counts()
+
+    def nearmiss_counts(self):
+        """qm_batch_get_nearmiss: the counts of the latest nearmiss()"""
+        rec = np.zeros((max(self.n_vcf, 1), _lib.QM_NM_R_CLASSES), np.uint64)
+        tru = np.zeros((max(self.n_vcf, 1), _lib.QM_NM_T_CLASSES), np.uint64)
+        self._ck(self._L.qm_batch_get_nearmiss(self._h, _p(rec), _p(tru)))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def nearmiss_timings(self):
+        """qm_batch_nearmiss_timings (set_timing on): milliseconds of the latest nearmiss() between HIP events, kernel by kernel"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.qm_batch_nearmiss_timings(self._h, ms))
+        return {"nearmiss_records_ms": ms[0], "nearmiss_truth_ms": ms[1]}
+
+    def nearmiss_classes(self, v):
+        """qm_batch_get_nearmiss_cls: uint8[n] -- the class of every FP line of VCF v in input order, 255 for the other records"""
+        n = int(self.n_records[int(v)])
+        out = np.zeros(max(n, 1), np.uint8)
+        self._ck(self._L.qm_batch_get_nearmiss_cls(self._h, int(v), _p(out)))
+        return out[:n]
+
+    def nearmiss_truth(self, v):
+        """qm_batch_get_nearmiss_truth: uint8[T'] -- the class of every missed key of VCF v's truth set (sorted distinct keys),
+        255 for the keys it hit"""
+        t = self.engine.truth_size(int(self.truth_ids[int(v)]))
+        out = np.zeros(max(t, 1), np.uint8)
+        self._ck(self._L.qm_batch_get_nearmiss_truth(self._h, int(v), _p(out)))
+        return out[:t]
 
     def path_stats(self):
         """qm_batch_path_stats: where the VCFs the last finish found out of order went"""

@@ -56,6 +56,10 @@ class Job:
     vote_group: str = None    # label of the job's vote group (1 to 32 jobs of one truth file): stats gain tp_votes / fp_votes / private_*
     consensus_k: int = 0      # the group's consensus level (any member may carry it, with consensus_out); 0 = no file
     consensus_out: str = None
+    # why the FP lines are FP and the missed truth keys missed; mixed samples only
+    explain: int = None       # the radius (0 to 64), None = off: stats gain nearmiss_rec / nearmiss_tru (the same radius for every such job of a call)
+    fp_why_out: str = None    # where the job's `line POS REF ALT QUAL class` table goes (extract_many(explain=) derives it)
+    fn_why_out: str = None    # where the job's `POS REF ALT class` table of its missed truth rows goes
 
 
 def _paths(job):
@@ -125,7 +129,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None):
+                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -156,11 +160,15 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     file each, a job in at most one): the members' stats gain tp_votes / fp_votes ([33]), private_tp / private_fp ([32]),
     vote_member (the job's index in its group) and vote_callers (the members' Job.caller, in member order = job order), and the
     groups with a level get their consensus VCF.  Over several GPUs a group must sit on one rank (WorkflowError otherwise).
+    explain: a radius, 0 to 64 (quasimodo_amd.nearmiss; default: the jobs' Job.explain / fp_why_out / fn_why_out): every
+    mixed-sample job gets stats["nearmiss_rec"] ([6]: its FP lines per class idcol, allele, refbase, near, isolated, nokey) and
+    stats["nearmiss_tru"] ([5]: its missed truth keys per class filtered, allele, position, near, uncalled), and
+    why/<x>.fp.why.tsv and why/<x>.fn.why.tsv beside fp/ and tp/.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
-             "strata": strata is not None, "boot": boot is not None, "votes": bool(votes)}
+             "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -177,6 +185,14 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                 jobs[i].consensus_k, jobs[i].consensus_out = int(ks[k]), outs[k]
     elif groups is not None:
         _label_groups(jobs, groups, "group", "g", MAX_GROUP, "truth-side", "")
+    if explain is not None:
+        from .nearmiss import check_radius, fn_why_path, fp_why_path
+        radius = check_radius(explain)
+        for j in jobs:
+            if not is_pure_strain(j.vcf_file):
+                _paths(j)
+                j.explain = radius
+                j.fp_why_out, j.fn_why_out = j.fp_why_out or fp_why_path(j), j.fn_why_out or fn_why_path(j)
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -208,7 +224,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     # ... which may share the call, and agree on the parameters of a pass
     check_shared_call({name for name, g in given.items() if g} | requested_by(jobs))
     for p in PASSES:
-        if p.agree and len({getattr(j, p.name) for j in jobs if getattr(j, p.name)}) > 1:
+        if p.agree and len({getattr(j, p.fields[0]) for j in jobs if getattr(j, p.fields[0]) is not None}) > 1:
             raise ValueError(p.agree)
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
@@ -237,7 +253,14 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = None
+    ts = vt = nm = None
+    if any(j.explain is not None and not p for j, p in zip(jobs, pure)):
+        from .nearmiss import check_radius
+        on = [j.explain is not None and not p for j, p in zip(jobs, pure)]
+        nm = {"radius": check_radius(next(j.explain for j, w in zip(jobs, on) if w)), "want": [int(w) for w in on],
+              "fp_why": [j.fp_why_out if w else None for j, w in zip(jobs, on)], "fn_why": [j.fn_why_out if w else None for j, w in zip(jobs, on)]}
+        for path in [x for x in nm["fp_why"] + nm["fn_why"] if x]:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     if any((j.fn_out or j.group is not None) and not p for j, p in zip(jobs, pure)):
         labels, index = _group_indices(jobs, pure, "group", MAX_GROUP, "truth-side")
         missed = [next((j.missed_out for j in jobs if j.group == lab and j.missed_out), None) for lab in labels]
@@ -292,7 +315,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

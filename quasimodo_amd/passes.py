@@ -15,6 +15,7 @@ PASSES = (
     Pass("boot", ("boot",), ("boot",), "--bootstrap",
          "boot: the resampled jobs of one call share one window, window count, replicate count and seed", ()),
     Pass("votes", ("vote_group",), ("votes",), "--votes", None, ()),
+    Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
 )
 
 

@@ -163,7 +163,7 @@ def _shared_call(**asked):
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
-                         votes=False, consensus_vcf=None):
+                         votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -190,11 +190,15 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     sample; final_tables/caller_consensus.tsv (TP, FP, FN, Precision, Recall, F1 of "at least k of n callers") and
     caller_private.tsv (what each caller alone calls) are written.  consensus_vcf=K (implies votes) also writes
     snp/consensus/{sample}.{ref}.k{K}.vcf; K above the sample's caller count is a WorkflowError that names the sample.
+    explain_errors: why the FP lines are FP and the missed truth keys missed (quasimodo_amd.nearmiss), with
+    explain_radius (default 10, 0 to 64): callers/{caller}/why/{sample}.{ref}.{caller}.fp.why.tsv and ...fn.why.tsv for every mixed
+    sample, and final_tables/caller_error_classes.tsv.
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
-                 truthside=truth_side, profile=snp_profile)
+                 truthside=truth_side, profile=snp_profile, nearmiss=explain_errors)
+    radius = _explain_radius(explain_errors, explain_radius)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if strata is not None:
@@ -254,6 +258,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 for s in samples:
                     if not s.endswith(("-1-0", "-0-1")):
                         print("consensus_vcf\t%s\t%d" % (s, int(consensus_vcf)))
+        if radius is not None:
+            for s, c, src in plan:
+                if not s.endswith(("-1-0", "-0-1")):
+                    print("explain_errors\t%s\t%s\t%d" % (c, s, radius))
+            print("caller_error_classes\t%s" % ",".join(callers))
         if truth_side:
             from .truthside import venn_callers
             for s, c, src in plan:
@@ -316,6 +325,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 if consensus_vcf is not None:
                     j.consensus_k = int(consensus_vcf)
                     j.consensus_out = os.path.join(snp_dir, "consensus", "%s.%s.k%d.vcf" % (s, SAMPLE_REF[s], int(consensus_vcf)))
+    if radius is not None:
+        _explain_jobs([j for (c, s), j in zip(meta, jobs) if s in mixed], radius)
     cmp_callers = [c for c in FP_COMPARED if c in callers]
     tables = os.path.join(results, "final_tables")
 
@@ -336,6 +347,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_caller_snp_venn(meta, jobs, tables, callers, mixed)
         if votes:
             _write_votes(meta, jobs, tables, mixed)
+        if radius is not None:
+            _write_error_classes([(c, s, j) for (c, s), j in zip(meta, jobs) if s in mixed], tables)
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -373,6 +386,43 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
 
 
 run_hcmv_variantcall.last_result = None
+
+
+def _explain_radius(explain_errors, explain_radius):
+    """the radius of --explain-errors (None: the pass is off)"""
+    from .nearmiss import DEFAULT_RADIUS, check_radius
+    if not explain_errors:
+        if explain_radius is not None:
+            raise WorkflowError("--explain-radius goes with --explain-errors")
+        return None
+    try:
+        return check_radius(DEFAULT_RADIUS if explain_radius is None else explain_radius)
+    except ValueError as e:
+        raise WorkflowError("--explain-radius: %s" % e) from None
+
+
+def _explain_jobs(jobs, radius):
+    """the near-miss pass and the two why-files of every mixed-sample job"""
+    from .extract import _paths
+    from .nearmiss import fn_why_path, fp_why_path
+    for j in jobs:
+        if not is_pure_strain(j.vcf_file):
+            _paths(j)
+            j.explain, j.fp_why_out, j.fn_why_out = radius, fp_why_path(j), fn_why_path(j)
+
+
+def _write_error_classes(rows, tables):
+    """final_tables/caller_error_classes.tsv from the rows of the explained jobs: (caller, sample, job)"""
+    from .nearmiss import write_caller_error_classes
+    out = []
+    for c, s, j in rows:
+        if j.stats.get("pure_strain"):
+            continue
+        if "nearmiss_rec" not in j.stats:
+            raise WorkflowError("%s/%s: no error classes came back" % (c, s))
+        out.append((c, s, j.stats["nearmiss_rec"], j.stats["nearmiss_tru"]))
+    if out:
+        write_caller_error_classes(os.path.join(tables, "caller_error_classes.tsv"), out)
 
 
 def _vote_plan(plan, consensus_vcf):
@@ -563,7 +613,7 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
 
 
 def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
-                truth_side=False, strata=None, bootstrap=None, votes=False, consensus_vcf=None):
+                truth_side=False, strata=None, bootstrap=None, votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
@@ -574,11 +624,14 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     votes: the labels form one vote group: final_tables/caller_consensus.tsv and caller_private.tsv (sample
     "custom"); more than 32 labels (or pure-strain names) are told so and get no table.  consensus_vcf=K (implies votes) also writes
     snp/consensus/custom.k{K}.vcf; K above the label count is a WorkflowError.
-    Each of the four runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
+    explain_errors, with explain_radius (default 10): callers/why/{label}.fp.why.tsv and {label}.fn.why.tsv for every VCF and
+    final_tables/caller_error_classes.tsv.
+    Each of the five runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
     from .truthside import MAX_GROUP
     from .consensus import MAX_GROUP as VOTE_MAX
     votes = bool(votes) or consensus_vcf is not None
-    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side)
+    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side, nearmiss=explain_errors)
+    radius = _explain_radius(explain_errors, explain_radius)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if strata is not None:
@@ -604,6 +657,10 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
             print("caller_consensus\t%s" % ",".join(labels))
             if consensus_vcf is not None:
                 print("consensus_vcf\tcustom\t%d" % int(consensus_vcf))
+        if radius is not None:
+            for lab in labels:
+                print("explain_errors\t%s\t%d" % (lab, radius))
+            print("caller_error_classes\t%s" % ",".join(labels))
         if truth_side:
             for lab in labels:
                 print("truthside_fn\t%s" % lab)
@@ -625,6 +682,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
             if not is_pure_strain(j.vcf_file):
                 j.fn_out = fn_path(j)
                 j.group = "vareval" if grouped else None
+    if radius is not None:
+        _explain_jobs(jobs, radius)
     if voted:
         for j in jobs:
             j.vote_group = "custom"
@@ -655,6 +714,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
         write_performance_ci(os.path.join(results, "final_tables", "snpcall_benchmark_ci.txt"), [(lab, None, j.stats) for lab, j in zip(labels, jobs)], custom=True)
     if voted:
         _write_votes([(lab, "custom") for lab in labels], jobs, os.path.join(results, "final_tables"), ["custom"])
+    if radius is not None:
+        _write_error_classes([(lab, "custom", j) for lab, j in zip(labels, jobs)], os.path.join(results, "final_tables"))
     if grouped:
         from .truthside import write_caller_snp_venn
         n = len(labels)

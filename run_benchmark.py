@@ -118,12 +118,16 @@ def _bootstrap_opts(n_rep, window, seed):
                    "callers agree', per mixed sample) and caller_private.tsv (what each caller alone calls).")
 @click.option("--consensus-vcf", "consensus_vcf", type=int, default=None,
               help="With the vote tables, also write snp/consensus/{sample}.{ref}.k{K}.vcf: one line per key that at least K callers call.")
+@click.option("--explain-errors", "explain_errors", is_flag=True, default=False,
+              help="Why every FP line is FP and every missed truth key missed: also write callers/*/why/*.fp.why.tsv and *.fn.why.tsv and final_tables/caller_error_classes.tsv.")
+@click.option("--explain-radius", "explain_radius", type=int, default=None,
+              help="--explain-errors: positions on either side within which a truth key (a call) counts as near [default: 10; 0 to 64].")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
          mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
-         votes=False, consensus_vcf=None):
+         votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -150,7 +154,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              snp_profile=dict(window=profile_window, n_pos_bins=profile_pos_bins, n_af_bins=profile_af_bins)
                                              if snp_profile else None, strata=strata_set,
                                              bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
-                                             votes=votes, consensus_vcf=consensus_vcf)
+                                             votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -186,9 +190,13 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                    "callers agree', over the labels) and caller_private.tsv; more than 32 labels: a note, no table.")
 @click.option("--consensus-vcf", "consensus_vcf", type=int, default=None,
               help="With the vote tables, also write snp/consensus/custom.k{K}.vcf: one line per key that at least K callers call.")
+@click.option("--explain-errors", "explain_errors", is_flag=True, default=False,
+              help="Why every FP line is FP and every missed truth key missed: also write callers/why/{label}.fp.why.tsv and {label}.fn.why.tsv and final_tables/caller_error_classes.tsv.")
+@click.option("--explain-radius", "explain_radius", type=int, default=None,
+              help="--explain-errors: positions on either side within which a truth key (a call) counts as near [default: 10; 0 to 64].")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
-            votes=False, consensus_vcf=None):
+            votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
     from quasimodo_amd import workflow
     try:
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
@@ -208,7 +216,7 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
         jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None,
                                     truth_side=truth_side, strata=_read_strata(strata, strata_by_name),
                                     bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
-                                    votes=votes, consensus_vcf=consensus_vcf)
+                                    votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius)
         if json_out and not dryrun:
             _write_json(json_out, "vareval", jobs, workflow.run_vareval)
     except Exception as e:
