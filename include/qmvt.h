@@ -438,6 +438,37 @@ int qm_batch_get_nearmiss_truth(qm_batch* b, int vcf, uint8_t* out /*[T']*/);
 /* with qm_batch_set_timing on: milliseconds of the latest qm_batch_nearmiss between HIP events on its stream -- [0]
  * k_nearmiss_records, [1] k_nearmiss_truth.  Waits for the pass. */
 int qm_batch_nearmiss_timings(qm_batch* b, float* ms2);
+
+/* ---- the filter surface: TP, FP and FN at every QUAL x AF threshold (build-defined, opt-in, single-base batches
+ * only) ----
+ * Parameters: q_step >= 1 (at most QM_SF_MAX_QUAL_STEP), 1 <= nq <= QM_SF_MAX_QUAL_BINS, 1 <= na <= QM_SF_MAX_AF_BINS,
+ * nq * na <= QM_SF_MAX_CELLS.  Per record: snp = both allele codes single bases; j = the index of its key in its VCF's truth
+ * set when snp and not QM_F_NOKEY; is_tp = (j found and QM_F_IDDOT) or (snp and QM_F_TPLINE); b = the ROC's quality bin with
+ * nq * q_step bins (NaN or floor(qual) < 0: none; clamped to the last), qb = b / q_step; ab = 0 when af is NaN or < 0 (every
+ * record of a VCF without qm_batch_upload_af has no af), else min(na - 1, (int)(af * (float)na)) with one float multiply.
+ * Counted: the records with snp and a bin, whatever QM_F_PASS says -- into cell [qb][ab] of the TP grid when is_tp, of the FP
+ * grid otherwise.  Every truth key is counted once in the U grid, in the lexicographically largest (qb, ab) among its counted
+ * records with j found and QM_F_IDDOT (the ROC's best record, with one more tie-break); keys without such a record nowhere.
+ * S[v][c][i][k] (c: QM_SF_TP, QM_SF_FP, QM_SF_U) = the sum of grid c over qb >= i and ab >= k: the count under the filter
+ * QUAL >= i * q_step and AF >= k / na.  FN = T' - S[U].  extra[v]: QM_SF_COUNTED, QM_SF_NO_AF (counted, af NaN),
+ * QM_SF_NO_BIN (snp records left out because they have no bin), QM_SF_TRUTH (T').
+ * qm_batch_surface: asynchronous on `stream` (NULL = the context's own); waits for the previous qm_batch_surface of the batch.
+ *   QM_E_INVAL for a parameter outside the limits (the message names it); QM_E_STATE unless the latest qm_batch_run was
+ *   finished, and for an allele-extended batch.  The first call allocates one u32 per (VCF, truth key) and the grids, counted
+ *   in qm_batch_device_bytes; may be repeated with other parameters.
+ * qm_batch_get_surface: waits for the pass, then copies (either pointer may be NULL).
+ * qm_batch_surface_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] k_surface_records, [1]
+ *   k_surface_truth, [2] k_surface_sums. */
+#define QM_SF_MAX_QUAL_BINS 256
+#define QM_SF_MAX_AF_BINS 64
+#define QM_SF_MAX_CELLS 4096
+#define QM_SF_MAX_QUAL_STEP 65536
+enum { QM_SF_TP = 0, QM_SF_FP = 1, QM_SF_U = 2 };
+enum { QM_SF_COUNTED = 0, QM_SF_NO_AF = 1, QM_SF_NO_BIN = 2, QM_SF_TRUTH = 3 };
+#define QM_SF_EXTRA 4
+int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t na, void* stream);
+int qm_batch_get_surface(qm_batch* b, uint64_t* S /*[n_vcf][3][nq][na] or NULL*/, uint64_t* extra /*[n_vcf][QM_SF_EXTRA] or NULL*/);
+int qm_batch_surface_timings(qm_batch* b, float* ms3);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -738,6 +769,21 @@ typedef struct qm_nearmiss_args {
 int qm_extract_files_nearmiss(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                               qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                               void* global_dev, const qm_nearmiss_args* nearmiss);
+
+/* qm_extract_files_ex plus the filter surface over its batch (single-base mode only: QM_E_STATE otherwise).
+ * Jobs with want[j] != 0 have their INFO column scanned (qm_vcf_scan_af) and uploaded beside the other columns, as in
+ * qm_extract_files_profile, and get their rows: S[j][3][nq][na] and extra[j][QM_SF_EXTRA] of qm_batch_get_surface; the others
+ * get zero rows.  A pure-strain job that asks is refused by name (QM_E_INVAL): it has no truth set.  One parameter triple per
+ * call, checked as qm_batch_surface checks it.  The VCF outputs, stats and roc are those of qm_extract_files_ex. */
+typedef struct qm_surface_args {
+  const uint8_t* want;              /* [n_jobs] 0/1 */
+  int32_t q_step, nq, na, reserved;
+  uint64_t* S;                      /* [n_jobs][3][nq][na] */
+  uint64_t* extra;                  /* [n_jobs][QM_SF_EXTRA] */
+} qm_surface_args;
+int qm_extract_files_surface(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                             void* global_dev, const qm_surface_args* surface);
 
 /* qm_extract_files_motifs plus the allele-frequency profile: both halves of rule mutationcontext in one call.
  * genome_id / motifs may be NULL (no spectra).  Jobs with want[j] != 0 have their INFO column scanned (qm_vcf_scan_af) and

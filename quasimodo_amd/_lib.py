@@ -40,6 +40,13 @@ QM_NM_MAX_RADIUS = 64
 QM_NM_R_CLASSES = 6
 QM_NM_T_CLASSES = 5
 QM_NM_NONE = 255
+QM_SF_MAX_QUAL_BINS = 256
+QM_SF_MAX_AF_BINS = 64
+QM_SF_MAX_CELLS = 4096
+QM_SF_MAX_QUAL_STEP = 65536
+QM_SF_TP, QM_SF_FP, QM_SF_U = 0, 1, 2
+QM_SF_COUNTED, QM_SF_NO_AF, QM_SF_NO_BIN, QM_SF_TRUTH = 0, 1, 2, 3
+QM_SF_EXTRA = 4
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -62,6 +69,7 @@ EXPORTS = (
     "qm_batch_boot", "qm_batch_get_boot", "qm_boot_draws", "qm_extract_files_boot",
     "qm_batch_votes", "qm_batch_get_votes", "qm_batch_get_vote_keys", "qm_batch_vote_groups", "qm_batch_vote_timings", "qm_extract_files_votes",
     "qm_batch_nearmiss", "qm_batch_get_nearmiss", "qm_batch_get_nearmiss_cls", "qm_batch_get_nearmiss_truth", "qm_batch_nearmiss_timings", "qm_extract_files_nearmiss",
+    "qm_batch_surface", "qm_batch_get_surface", "qm_batch_surface_timings", "qm_extract_files_surface",
 )
 
 
@@ -117,6 +125,12 @@ class NearmissArgs(C.Structure):
                 ("fp_why_out", C.POINTER(C.c_char_p)), ("fn_why_out", C.POINTER(C.c_char_p))]
 
 
+class SurfaceArgs(C.Structure):
+    """include/qmvt.h qm_surface_args"""
+    _fields_ = [("want", C.c_void_p), ("q_step", C.c_int32), ("nq", C.c_int32), ("na", C.c_int32), ("reserved", C.c_int32),
+                ("S", C.c_void_p), ("extra", C.c_void_p)]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -137,7 +151,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -337,6 +351,11 @@ def lib():
     L.qm_batch_nearmiss_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_extract_files_nearmiss.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                             C.POINTER(NearmissArgs)]
+    L.qm_batch_surface.argtypes = [vp, i32, i32, i32, vp]
+    L.qm_batch_get_surface.argtypes = [vp, vp, vp]
+    L.qm_batch_surface_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_extract_files_surface.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                           C.POINTER(SurfaceArgs)]
     _lib = L
     return L
 

@@ -29,6 +29,7 @@
 #include "qmvt_votes.h"
 #include "qmvt_boot.h"
 #include "qmvt_nearmiss.h"
+#include "qmvt_surface.h"
 
 using namespace qm;
 
@@ -781,6 +782,20 @@ struct qm_batch {
   hipEvent_t ev_nmt[3] = {};          // qm_batch_set_timing: around k_nearmiss_records and k_nearmiss_truth
   bool nm_timed = false;              // the latest qm_batch_nearmiss recorded them
   bool nm_valid = false;              // qm_batch_nearmiss was called behind the latest run
+  // qm_batch_surface (lazy): one u32 per (VCF, truth key) -- the best cell code of the key's records; row v starts
+  // at h_sf_off[v] --, the [n_vcf][3][nq * na] grids (suffix sums once k_surface_sums ran) and [n_vcf][QM_SF_EXTRA] extras one
+  // behind the other, the pass's own copy of the "has af" marks; ev_sf says when the pass is done
+  DevBuf<uint32_t> sf_best;
+  DevBuf<int64_t> sf_off;
+  DevBuf<uint64_t> sf_out;
+  DevBuf<uint8_t> sf_mark;
+  std::vector<int64_t> h_sf_off;      // [n_vcf + 1], from the truth sets' T' at the first call
+  bool sf_off_uploaded = false;
+  hipEvent_t ev_sf = nullptr;
+  hipEvent_t ev_sft[4] = {};          // qm_batch_set_timing: around the three kernels
+  bool sf_timed = false;              // the latest qm_batch_surface recorded them
+  int32_t sf_cells = 0;               // nq * na of the latest qm_batch_surface
+  bool sf_valid = false;              // qm_batch_surface was called behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -809,6 +824,8 @@ static void batch_free(qm_batch* b) {
   if (b->ev_votes) (void)hipEventDestroy(b->ev_votes);
   if (b->ev_nm) (void)hipEventDestroy(b->ev_nm);
   for (auto& e : b->ev_nmt) if (e) (void)hipEventDestroy(e);
+  if (b->ev_sf) (void)hipEventDestroy(b->ev_sf);
+  for (auto& e : b->ev_sft) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -1140,6 +1157,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->boot_made = 0;
   b->votes_valid = false;
   b->nm_valid = false;
+  b->sf_valid = false;
   b->last_global = g;
   return QM_OK;
 }
@@ -2924,6 +2942,94 @@ extern "C" int qm_batch_get_nearmiss_truth(qm_batch* b, int v, uint8_t* out) {
       for (int t = 0; t < NM_T_CLASSES; ++t) if ((x[t] >> (k & 31)) & 1u) cls = (uint8_t)t;
       out[k] = cls;
     }
+  }
+  return QM_OK;
+}
+// the filter surface of the finished batch: TP, FP and found truth keys at every QUAL x AF threshold
+extern "C" int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t na, void* stream) {
+  NEED_FINISHED(b, "qm_batch_surface");
+  if (b->ext) return fail(QM_E_STATE, "qm_batch_surface: allele-extended batches have no filter surface (single-base batches only)");
+  if (q_step < 1 || q_step > QM_SF_MAX_QUAL_STEP) return fail(QM_E_INVAL, "qm_batch_surface: q_step %d (1 to %d)", q_step, QM_SF_MAX_QUAL_STEP);
+  if (nq < 1 || nq > QM_SF_MAX_QUAL_BINS) return fail(QM_E_INVAL, "qm_batch_surface: nq %d (1 to %d)", nq, QM_SF_MAX_QUAL_BINS);
+  if (na < 1 || na > QM_SF_MAX_AF_BINS) return fail(QM_E_INVAL, "qm_batch_surface: na %d (1 to %d)", na, QM_SF_MAX_AF_BINS);
+  if (nq * na > QM_SF_MAX_CELLS) return fail(QM_E_INVAL, "qm_batch_surface: nq * na = %d cells (at most %d)", nq * na, QM_SF_MAX_CELLS);
+  qm_ctx* c = b->ctx;
+  int rc = truths_live(b, "qm_batch_surface");
+  if (rc != QM_OK) return rc;
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_sf, &st);
+  if (rc != QM_OK) return rc;
+  const size_t nv = (size_t)b->n_vcf, cells = (size_t)nq * (size_t)na;
+  if (b->h_sf_off.empty()) {   // (T' cannot change while the generations truths_live checks hold)
+    b->h_sf_off.assign(nv + 1, 0);
+    for (size_t v = 0; v < nv; ++v) b->h_sf_off[v + 1] = b->h_sf_off[v] + c->truths[(size_t)b->L.vcfs[v].truth].n;
+  }
+  const size_t nbest = std::max<size_t>((size_t)b->h_sf_off[nv], 1);
+  const size_t out_words = std::max<size_t>(nv, 1) * (SF_GRIDS * cells + SF_EXTRA);
+  b->sf_valid = false;   // from here on the outputs are rewritten
+  rc = b->sf_best.grow((int64_t)nbest, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->sf_off.grow((int64_t)nv + 1, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->sf_out.grow((int64_t)out_words, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->sf_mark.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  if (!b->sf_off_uploaded) {
+    HIPCHK(hipMemcpy(b->sf_off, b->h_sf_off.data(), (nv + 1) * 8, hipMemcpyHostToDevice));
+    b->sf_off_uploaded = true;
+  }
+  bool any_af = false;
+  for (size_t v = 0; v < nv; ++v) any_af = any_af || b->h_afmark[v];
+  if (nv) HIPCHK(hipMemcpy(b->sf_mark, b->h_afmark.data(), nv, hipMemcpyHostToDevice));   // blocking: the marks may change behind the call
+  HIPCHK(hipMemsetAsync(b->sf_best, 0, nbest * 4, st));
+  HIPCHK(hipMemsetAsync(b->sf_out, 0, out_words * 8, st));
+  SurfaceParams P;
+  P.spans = b->d_spans; P.truths = c->d_truths; P.has_af = b->sf_mark; P.best_off = b->sf_off;
+  P.pos = b->pos; P.anib = b->anib; P.flags = b->flags; P.qual = b->qual;
+  P.af = any_af ? b->d_af.p : nullptr;   // (no mark anywhere: there may be no column at all)
+  P.best = b->sf_best;
+  P.grid = reinterpret_cast<unsigned long long*>(b->sf_out.p);
+  P.extra = P.grid + std::max<size_t>(nv, 1) * SF_GRIDS * cells;
+  P.n_spans = (int32_t)b->L.spans.size();
+  P.q_step = q_step; P.nq = nq; P.na = na;
+  int64_t max_tn = 0;
+  for (size_t v = 0; v < nv; ++v) max_tn = std::max<int64_t>(max_tn, b->h_sf_off[v + 1] - b->h_sf_off[v]);
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_sft) if (!e) HIPCHK(hipEventCreate(&e));
+  b->sf_timed = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_sft[0], st));
+  launch_surface_records(P, st);
+  if (T) HIPCHK(hipEventRecord(b->ev_sft[1], st));
+  launch_surface_truth(P, b->n_vcf, max_tn, st);
+  if (T) HIPCHK(hipEventRecord(b->ev_sft[2], st));
+  launch_surface_sums(P, b->n_vcf, st);
+  if (T) { HIPCHK(hipEventRecord(b->ev_sft[3], st)); b->sf_timed = true; }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(b->ev_sf, st));
+  b->sf_cells = (int32_t)cells;
+  b->sf_valid = true;
+  return QM_OK;
+}
+#define NEED_SURFACE(b, name) \
+  if (!(b)) return fail(QM_E_INVAL, name ": NULL batch"); \
+  if (!(b)->sf_valid) return fail(QM_E_STATE, name ": no qm_batch_surface behind the latest run")
+extern "C" int qm_batch_surface_timings(qm_batch* b, float* ms3) {
+  NEED_SURFACE(b, "qm_batch_surface_timings");
+  if (!ms3) return fail(QM_E_INVAL, "qm_batch_surface_timings: NULL");
+  if (!b->sf_timed) return fail(QM_E_STATE, "qm_batch_surface_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_sft[3]));
+  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_sft[i], b->ev_sft[i + 1]));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_surface(qm_batch* b, uint64_t* S, uint64_t* extra) {
+  NEED_SURFACE(b, "qm_batch_get_surface");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_sf));
+  const size_t nv = (size_t)b->n_vcf, gw = (size_t)SF_GRIDS * (size_t)b->sf_cells;
+  if (!nv) return QM_OK;
+  if (S) HIPCHK(hipMemcpy(S, b->sf_out, nv * gw * 8, hipMemcpyDeviceToHost));
+  if (extra) {
+    HIPCHK(hipMemcpy(extra, b->sf_out + nv * gw, nv * SF_EXTRA * 8, hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < nv; ++v) extra[v * SF_EXTRA + QM_SF_TRUTH] = (uint64_t)(b->h_sf_off[v + 1] - b->h_sf_off[v]);   // T', as the rows of `best` were sized
   }
   return QM_OK;
 }

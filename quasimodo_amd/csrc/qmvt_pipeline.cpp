@@ -298,10 +298,13 @@ struct Passes {
   uint64_t* motifs_out = nullptr;
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
+  const qm_surface_args* sf = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
   bool wants_boot(int j) const { return ba && ba->want[j] != 0; }
+  bool wants_surface(int j) const { return sf && sf->want[j] != 0; }
+  bool wants_af(int j) const { return wants_profile(j) || wants_surface(j); }   // the INFO column is scanned and uploaded
   // the passes a pure-strain job joins the batch for (against an empty truth set, for its rows of the pass only: its files,
   // stats and ROC rows are made as for any pure-strain job); every mixed-sample job is in the batch anyway
   bool any_batch_only(int j) const { return has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j); }
@@ -631,6 +634,18 @@ int nearmiss_pass(const PassCtx& c, const qm_nearmiss_args* nm, std::string& err
   return QM_OK;
 }
 
+// the filter surface: S and extra of every wanted job
+int surface_pass(const PassCtx& c, const qm_surface_args* sf, std::string& err) {
+  auto want = [&](int j) { return sf->want[j] != 0; };
+  if (!sf || !c.any(want)) return QM_OK;
+  const size_t gw = 3 * (size_t)sf->nq * (size_t)sf->na;
+  std::vector<uint64_t> S(c.nv * gw), ex(c.nv * QM_SF_EXTRA);
+  int rc = qm_batch_surface(c.batch, sf->q_step, sf->nq, sf->na, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_surface(c.batch, S.data(), ex.data());
+  if (rc == QM_OK) { c.scatter_rows(sf->S, S, gw, want); c.scatter_rows(sf->extra, ex, QM_SF_EXTRA, want); }
+  return c.lib(rc, err);
+}
+
 }  // namespace
 
 extern "C" int qm_extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
@@ -780,6 +795,32 @@ extern "C" int qm_extract_files_nearmiss(qm_ctx* ctx, int n_jobs, const qm_file_
     memset(nm->tru, 0, sizeof(uint64_t) * QM_NM_T_CLASSES * (size_t)n_jobs);
   }
   Passes P; P.nm = nm;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// the filter surface behind the worker: TP, FP and found truth keys at every QUAL x AF threshold
+extern "C" int qm_extract_files_surface(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                        qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                        int n_slots, void* global_dev, const qm_surface_args* surface) {
+  const qm_surface_args* sf = surface;
+  if (!sf || (n_jobs > 0 && (!sf->want || !sf->S || !sf->extra))) return fail(QM_E_INVAL, "qm_extract_files_surface: NULL arguments");
+  if (sf->q_step < 1 || sf->q_step > QM_SF_MAX_QUAL_STEP)
+    return fail(QM_E_INVAL, "qm_extract_files_surface: q_step " + std::to_string(sf->q_step) + " (1 to " + std::to_string(QM_SF_MAX_QUAL_STEP) + ")");
+  if (sf->nq < 1 || sf->nq > QM_SF_MAX_QUAL_BINS)
+    return fail(QM_E_INVAL, "qm_extract_files_surface: nq " + std::to_string(sf->nq) + " (1 to " + std::to_string(QM_SF_MAX_QUAL_BINS) + ")");
+  if (sf->na < 1 || sf->na > QM_SF_MAX_AF_BINS)
+    return fail(QM_E_INVAL, "qm_extract_files_surface: na " + std::to_string(sf->na) + " (1 to " + std::to_string(QM_SF_MAX_AF_BINS) + ")");
+  if (sf->nq * sf->na > QM_SF_MAX_CELLS)
+    return fail(QM_E_INVAL, "qm_extract_files_surface: nq * na = " + std::to_string(sf->nq * sf->na) + " cells (at most " + std::to_string(QM_SF_MAX_CELLS) + ")");
+  if (mode & QM_BATCH_ALLELES) return fail(QM_E_STATE, "qm_extract_files_surface: allele-extended batches have no filter surface (single-base batches only)");
+  for (int j = 0; j < n_jobs; ++j)
+    if (sf->want[j] && jobs && jobs[j].pure)
+      return fail(QM_E_INVAL, std::string("qm_extract_files_surface: ") + jobs[j].vcf_path + " is a pure-strain job: it has no truth set and no filter surface");
+  if (n_jobs > 0) {
+    memset(sf->S, 0, sizeof(uint64_t) * 3 * (size_t)sf->nq * (size_t)sf->na * (size_t)n_jobs);
+    memset(sf->extra, 0, sizeof(uint64_t) * QM_SF_EXTRA * (size_t)n_jobs);
+  }
+  Passes P; P.sf = sf;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -967,7 +1008,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
         if (s.rc == QM_OK) s.rc = QM_E_INVAL;
         return;
       }
-      if (P.wants_profile(j)) {   // the INFO column, by a scanner of its own
+      if (P.wants_af(j)) {   // the INFO column, by a scanner of its own
         int64_t ai[2];
         s.af.resize((size_t)s.n_data + 1);
         s.rc = qm_vcf_scan_af(s.vcf.p, s.vcf.n, s.info.n_lines, s.line_off.data(), s.line_kind.data(), s.af.data(), ai);
@@ -975,7 +1016,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       }
       // the frequencies follow the columns (whose upload clears the VCF's mark); a blocking copy of this VCF's floats
       auto upload_af = [&]() {
-        if (s.rc != QM_OK || !P.wants_profile(j)) return;
+        if (s.rc != QM_OK || !P.wants_af(j)) return;
         s.rc = qm_batch_upload_af(batch, s.batch_v, s.af.data());
         if (s.rc != QM_OK) s.err = qm_last_error(ctx);
       };
@@ -1052,6 +1093,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = truthside_pass(pc, P.ts, err);
       if (rc == QM_OK) rc = votes_pass(pc, P.va, err);
       if (rc == QM_OK) rc = nearmiss_pass(pc, P.nm, err);
+      if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);
     t0 = now(); c0 = trace ? cpu_now() : 0.0;

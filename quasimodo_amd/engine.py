@@ -13,6 +13,20 @@ PATH_NAMES = ("unsorted", "bucket_direct", "bucket_hashed", "radix", "radix_afte
               "radix_chunks", "bucket_two_level", "bucket_partitions")
 
 
+def surface_params(q_step, nq, na):
+    """the parameter triple of the filter surface as ints; ValueError names the argument outside its limits"""
+    q_step, nq, na = int(q_step), int(nq), int(na)
+    if not 1 <= q_step <= _lib.QM_SF_MAX_QUAL_STEP:
+        raise ValueError("surface: q_step %d (1 to %d)" % (q_step, _lib.QM_SF_MAX_QUAL_STEP))
+    if not 1 <= nq <= _lib.QM_SF_MAX_QUAL_BINS:
+        raise ValueError("surface: nq %d (1 to %d)" % (nq, _lib.QM_SF_MAX_QUAL_BINS))
+    if not 1 <= na <= _lib.QM_SF_MAX_AF_BINS:
+        raise ValueError("surface: na %d (1 to %d)" % (na, _lib.QM_SF_MAX_AF_BINS))
+    if nq * na > _lib.QM_SF_MAX_CELLS:
+        raise ValueError("surface: nq * na = %d cells (at most %d)" % (nq * na, _lib.QM_SF_MAX_CELLS))
+    return q_step, nq, na
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -181,7 +195,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None):
+                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -208,6 +222,9 @@ class Engine:
         qm_extract_files_nearmiss: wanted mixed-sample rows gain `nearmiss_rec` ([6] ints: the FP lines per class
         nearmiss.RECORD_CLASSES) and `nearmiss_tru` ([5]: the missed truth keys per class nearmiss.TRUTH_CLASSES); the why-files
         are written.
+        surface: {"want": [0/1 per job], "q_step": 4, "nq": 64, "na": 50} -- qm_extract_files_surface: wanted rows
+        gain `surface` ([3][nq][na] uint64: TP records, FP records, found truth keys under QUAL >= i * q_step and AF >= k / na),
+        `surface_extra` ([QM_SF_EXTRA] ints: counted, counted without AF, left out, T') and `surface_params` (q_step, nq, na).
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         from .passes import check_shared_call
@@ -217,7 +234,7 @@ class Engine:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
@@ -347,6 +364,17 @@ class Engine:
         unpack = lambda k: {"nearmiss_rec": [int(x) for x in nrec[k]], "nearmiss_tru": [int(x) for x in ntru[k]],
                             "nearmiss_radius": radius} if nwant[k] and not pure(k) else {}
         return self._L.qm_extract_files_nearmiss, (C.byref(na),), unpack
+
+    def _files_surface(self, n, surface, **kw):
+        swant = _c([int(bool(w)) for w in surface["want"]] or [0], np.uint8)
+        if n and swant.shape[0] != n:
+            raise ValueError("surface: %d want entries for %d jobs" % (len(surface["want"]), n))
+        q, nq, na = surface_params(surface.get("q_step", 4), surface.get("nq", 64), surface.get("na", 50))
+        S = np.zeros((max(n, 1), 3, nq, na), np.uint64)
+        ex = np.zeros((max(n, 1), _lib.QM_SF_EXTRA), np.uint64)
+        sa = _lib.SurfaceArgs(_p(swant), q, nq, na, 0, _p(S), _p(ex))
+        unpack = lambda k: {"surface": S[k].copy(), "surface_extra": [int(x) for x in ex[k]], "surface_params": (q, nq, na)} if swant[k] else {}
+        return self._L.qm_extract_files_surface, (C.byref(sa),), unpack
 
     def path_stats_total(self):
         """qm_path_stats_total: where the VCFs found out of order went, summed over every batch this context has finished
@@ -632,6 +660,30 @@ class Batch:
         keys, masks = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
         self._ck(self._L.qm_batch_get_vote_keys(self._h, int(g), _p(keys), _p(masks), int(keys.shape[0]), C.byref(n)))
         return keys[:n.value], masks[:n.value]
+
+    # -- the filter surface ---------------------------------------
+    def surface(self, q_step=4, nq=64, na=50, stream=None, fetch=True):
+        """qm_batch_surface + qm_batch_get_surface: (S [n_vcf][3][nq][na], extra [n_vcf][QM_SF_EXTRA]) uint64 -- TP records, FP
+        records and found truth keys of every VCF under the filter QUAL >= i * q_step and AF >= k / na; extra: counted records,
+        counted records without AF, single-base records without a quality bin, T'.  fetch=False: enqueue only (surface_counts()
+        waits and copies)"""
+        self._ck(self._L.qm_batch_surface(self._h, int(q_step), int(nq), int(na), C.c_void_p(stream) if stream else None))
+        self._sf_shape = (int(nq), int(na))
+        return self.surface_counts() if fetch else None
+
+    def surface_counts(self):
+        """qm_batch_get_surface: the tables of the latest surface()"""
+        nq, na = getattr(self, "_sf_shape", (1, 1))
+        S = np.zeros((max(self.n_vcf, 1), 3, nq, na), np.uint64)
+        extra = np.zeros((max(self.n_vcf, 1), _lib.QM_SF_EXTRA), np.uint64)
+        self._ck(self._L.qm_batch_get_surface(self._h, _p(S), _p(extra)))
+        return S[:self.n_vcf], extra[:self.n_vcf]
+
+    def surface_timings(self):
+        """qm_batch_surface_timings (set_timing on): milliseconds of the latest surface() between HIP events, kernel by kernel"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.qm_batch_surface_timings(self._h, ms))
+        return {"surface_records_ms": ms[0], "surface_truth_ms": ms[1], "surface_sums_ms": ms[2]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

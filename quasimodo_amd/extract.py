@@ -60,6 +60,8 @@ class Job:
     explain: int = None       # the radius (0 to 64), None = off: stats gain nearmiss_rec / nearmiss_tru (the same radius for every such job of a call)
     fp_why_out: str = None    # where the job's `line POS REF ALT QUAL class` table goes (extract_many(explain=) derives it)
     fn_why_out: str = None    # where the job's `POS REF ALT class` table of its missed truth rows goes
+    # the filter surface; mixed samples only
+    surface: tuple = None     # (q_step, nq, na): stats gain surface / surface_extra / surface_params (the same for every swept job of a call)
 
 
 def _paths(job):
@@ -129,7 +131,8 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
-                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None):
+                 genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
+                 surface=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -164,11 +167,16 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     mixed-sample job gets stats["nearmiss_rec"] ([6]: its FP lines per class idcol, allele, refbase, near, isolated, nokey) and
     stats["nearmiss_tru"] ([5]: its missed truth keys per class filtered, allele, position, near, uncalled), and
     why/<x>.fp.why.tsv and why/<x>.fn.why.tsv beside fp/ and tp/.
+    surface: True or {"q_step": 4, "nq": 64, "na": 50} (quasimodo_amd.surface; default: the jobs' Job.surface): every mixed-sample
+    job gets stats["surface"] ([3][nq][na]: TP records, FP records and found truth keys under QUAL >= i * q_step and AF >= k / na),
+    stats["surface_extra"] ([4]: counted records, counted records without AF, records without a quality bin, T') and
+    stats["surface_params"].
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
-             "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None}
+             "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
+             "surface": surface is not None and surface is not False}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -193,6 +201,12 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                 _paths(j)
                 j.explain = radius
                 j.fp_why_out, j.fn_why_out = j.fp_why_out or fp_why_path(j), j.fn_why_out or fn_why_path(j)
+    if given["surface"]:
+        from .surface import params
+        spar = params(**(surface if isinstance(surface, dict) else {}))
+        for j in jobs:
+            if not is_pure_strain(j.vcf_file):
+                j.surface = spar
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -253,7 +267,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = None
+    ts = vt = nm = sf = None
+    if any(j.surface is not None for j in jobs):
+        from .surface import params
+        sf = dict(zip(("q_step", "nq", "na"), params(*next(j.surface for j in jobs if j.surface is not None))),
+                  want=[int(j.surface is not None) for j in jobs])
     if any(j.explain is not None and not p for j, p in zip(jobs, pure)):
         from .nearmiss import check_radius
         on = [j.explain is not None and not p for j, p in zip(jobs, pure)]
@@ -315,7 +333,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

@@ -163,7 +163,8 @@ def _shared_call(**asked):
 
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
-                         votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
+                         votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
+                         surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -193,12 +194,16 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     explain_errors: why the FP lines are FP and the missed truth keys missed (quasimodo_amd.nearmiss), with
     explain_radius (default 10, 0 to 64): callers/{caller}/why/{sample}.{ref}.{caller}.fp.why.tsv and ...fn.why.tsv for every mixed
     sample, and final_tables/caller_error_classes.tsv.
+    filter_surface: TP, FP and FN under every filter QUAL >= q and AF >= a (quasimodo_amd.surface), with
+    surface_qual_step / surface_qual_bins / surface_af_bins (default 4, 64, 50; QUAL 20 must be a grid line):
+    callers/{caller}/surface/{sample}.{ref}.{caller}.surface.tsv for every mixed sample and final_tables/caller_best_filter.tsv.
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
-                 truthside=truth_side, profile=snp_profile, nearmiss=explain_errors)
+                 truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface)
     radius = _explain_radius(explain_errors, explain_radius)
+    sweep = _surface_params(filter_surface, surface_qual_step, surface_qual_bins, surface_af_bins)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if strata is not None:
@@ -263,6 +268,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 if not s.endswith(("-1-0", "-0-1")):
                     print("explain_errors\t%s\t%s\t%d" % (c, s, radius))
             print("caller_error_classes\t%s" % ",".join(callers))
+        if sweep is not None:
+            for s, c, src in plan:
+                if not s.endswith(("-1-0", "-0-1")):
+                    print("filter_surface\t%s\t%s\t%d\t%d\t%d" % ((c, s) + sweep))
+            print("caller_best_filter\t%s" % ",".join(callers))
         if truth_side:
             from .truthside import venn_callers
             for s, c, src in plan:
@@ -327,6 +337,10 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                     j.consensus_out = os.path.join(snp_dir, "consensus", "%s.%s.k%d.vcf" % (s, SAMPLE_REF[s], int(consensus_vcf)))
     if radius is not None:
         _explain_jobs([j for (c, s), j in zip(meta, jobs) if s in mixed], radius)
+    if sweep is not None:
+        for (c, s), j in zip(meta, jobs):
+            if s in mixed:
+                j.surface = sweep
     cmp_callers = [c for c in FP_COMPARED if c in callers]
     tables = os.path.join(results, "final_tables")
 
@@ -349,6 +363,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_votes(meta, jobs, tables, mixed)
         if radius is not None:
             _write_error_classes([(c, s, j) for (c, s), j in zip(meta, jobs) if s in mixed], tables)
+        if sweep is not None:
+            _write_surface([(c, s, j) for (c, s), j in zip(meta, jobs) if s in mixed], tables, sweep[0])
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -399,6 +415,37 @@ def _explain_radius(explain_errors, explain_radius):
         return check_radius(DEFAULT_RADIUS if explain_radius is None else explain_radius)
     except ValueError as e:
         raise WorkflowError("--explain-radius: %s" % e) from None
+
+
+def _surface_params(filter_surface, q_step, nq, na):
+    """the parameter triple of --filter-surface (None: the pass is off)"""
+    from .surface import workflow_params
+    if not filter_surface:
+        if q_step is not None or nq is not None or na is not None:
+            raise WorkflowError("--surface-qual-step, --surface-qual-bins and --surface-af-bins go with --filter-surface")
+        return None
+    try:
+        return workflow_params(q_step, nq, na)
+    except ValueError as e:
+        raise WorkflowError("--filter-surface: %s" % e) from None
+
+
+def _write_surface(rows, tables, q_step):
+    """the surface table of every swept job beside its fp/ and tp/, and final_tables/caller_best_filter.tsv: (caller, sample, job)"""
+    from .extract import _paths
+    from .surface import TRUTH, surface_path, write_caller_best_filter, write_surface
+    out = []
+    for c, s, j in rows:
+        if j.stats.get("pure_strain"):
+            continue
+        if "surface" not in j.stats:
+            raise WorkflowError("%s/%s: no filter surface came back" % (c, s))
+        if not j.fp_out:
+            _paths(j)
+        write_surface(surface_path(j), j.stats["surface"], j.stats["surface_extra"][TRUTH], q_step)
+        out.append((c, s, j.stats["surface"], j.stats["surface_extra"]))
+    if out:
+        write_caller_best_filter(os.path.join(tables, "caller_best_filter.tsv"), out, q_step)
 
 
 def _explain_jobs(jobs, radius):
@@ -613,7 +660,8 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
 
 
 def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
-                truth_side=False, strata=None, bootstrap=None, votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
+                truth_side=False, strata=None, bootstrap=None, votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None,
+                filter_surface=False, surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
@@ -626,12 +674,15 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     snp/consensus/custom.k{K}.vcf; K above the label count is a WorkflowError.
     explain_errors, with explain_radius (default 10): callers/why/{label}.fp.why.tsv and {label}.fn.why.tsv for every VCF and
     final_tables/caller_error_classes.tsv.
-    Each of the five runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
+    filter_surface, with surface_qual_step / surface_qual_bins / surface_af_bins (default 4, 64, 50): callers/surface/{label}.surface.tsv
+    for every VCF and final_tables/caller_best_filter.tsv (sample "custom").
+    Each of the six runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
     from .truthside import MAX_GROUP
     from .consensus import MAX_GROUP as VOTE_MAX
     votes = bool(votes) or consensus_vcf is not None
-    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side, nearmiss=explain_errors)
+    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side, nearmiss=explain_errors, surface=filter_surface)
     radius = _explain_radius(explain_errors, explain_radius)
+    sweep = _surface_params(filter_surface, surface_qual_step, surface_qual_bins, surface_af_bins)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if strata is not None:
@@ -661,6 +712,11 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
             for lab in labels:
                 print("explain_errors\t%s\t%d" % (lab, radius))
             print("caller_error_classes\t%s" % ",".join(labels))
+        if sweep is not None:
+            for lab, v in zip(labels, vcfs):
+                if not is_pure_strain(v):
+                    print("filter_surface\t%s\t%d\t%d\t%d" % ((lab,) + sweep))
+            print("caller_best_filter\t%s" % ",".join(labels))
         if truth_side:
             for lab in labels:
                 print("truthside_fn\t%s" % lab)
@@ -684,6 +740,10 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
                 j.group = "vareval" if grouped else None
     if radius is not None:
         _explain_jobs(jobs, radius)
+    if sweep is not None:
+        for j in jobs:
+            if not is_pure_strain(j.vcf_file):
+                j.surface = sweep
     if voted:
         for j in jobs:
             j.vote_group = "custom"
@@ -716,6 +776,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
         _write_votes([(lab, "custom") for lab in labels], jobs, os.path.join(results, "final_tables"), ["custom"])
     if radius is not None:
         _write_error_classes([(lab, "custom", j) for lab, j in zip(labels, jobs)], os.path.join(results, "final_tables"))
+    if sweep is not None:
+        _write_surface([(lab, "custom", j) for lab, j in zip(labels, jobs)], os.path.join(results, "final_tables"), sweep[0])
     if grouped:
         from .truthside import write_caller_snp_venn
         n = len(labels)

@@ -122,12 +122,18 @@ def _bootstrap_opts(n_rep, window, seed):
               help="Why every FP line is FP and every missed truth key missed: also write callers/*/why/*.fp.why.tsv and *.fn.why.tsv and final_tables/caller_error_classes.tsv.")
 @click.option("--explain-radius", "explain_radius", type=int, default=None,
               help="--explain-errors: positions on either side within which a truth key (a call) counts as near [default: 10; 0 to 64].")
+@click.option("--filter-surface", "filter_surface", is_flag=True, default=False,
+              help="TP, FP and FN under every filter QUAL >= q and AF >= a: also write callers/*/surface/*.surface.tsv and final_tables/caller_best_filter.tsv (the filter of the largest F1 per caller).")
+@click.option("--surface-qual-step", "surface_qual_step", type=int, default=None, help="--filter-surface: QUAL units per grid line; must divide 20 [default: 4].")
+@click.option("--surface-qual-bins", "surface_qual_bins", type=int, default=None, help="--filter-surface: QUAL grid lines [default: 64; 1 to 256].")
+@click.option("--surface-af-bins", "surface_af_bins", type=int, default=None, help="--filter-surface: AF grid lines [default: 50; 1 to 64; at most 4096 cells].")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
          mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
-         votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
+         votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
+         surface_qual_bins=None, surface_af_bins=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -154,7 +160,9 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              snp_profile=dict(window=profile_window, n_pos_bins=profile_pos_bins, n_af_bins=profile_af_bins)
                                              if snp_profile else None, strata=strata_set,
                                              bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
-                                             votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius)
+                                             votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius,
+                                             filter_surface=filter_surface, surface_qual_step=surface_qual_step,
+                                             surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -194,9 +202,15 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="Why every FP line is FP and every missed truth key missed: also write callers/why/{label}.fp.why.tsv and {label}.fn.why.tsv and final_tables/caller_error_classes.tsv.")
 @click.option("--explain-radius", "explain_radius", type=int, default=None,
               help="--explain-errors: positions on either side within which a truth key (a call) counts as near [default: 10; 0 to 64].")
+@click.option("--filter-surface", "filter_surface", is_flag=True, default=False,
+              help="TP, FP and FN under every filter QUAL >= q and AF >= a: also write callers/surface/{label}.surface.tsv and final_tables/caller_best_filter.tsv (the filter of the largest F1 per caller).")
+@click.option("--surface-qual-step", "surface_qual_step", type=int, default=None, help="--filter-surface: QUAL units per grid line; must divide 20 [default: 4].")
+@click.option("--surface-qual-bins", "surface_qual_bins", type=int, default=None, help="--filter-surface: QUAL grid lines [default: 64; 1 to 256].")
+@click.option("--surface-af-bins", "surface_af_bins", type=int, default=None, help="--filter-surface: AF grid lines [default: 50; 1 to 64; at most 4096 cells].")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
-            votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None):
+            votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
+            surface_qual_bins=None, surface_af_bins=None):
     from quasimodo_amd import workflow
     try:
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
@@ -216,7 +230,9 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
         jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None,
                                     truth_side=truth_side, strata=_read_strata(strata, strata_by_name),
                                     bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
-                                    votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius)
+                                    votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius,
+                                    filter_surface=filter_surface, surface_qual_step=surface_qual_step,
+                                    surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins)
         if json_out and not dryrun:
             _write_json(json_out, "vareval", jobs, workflow.run_vareval)
     except Exception as e:
