@@ -469,6 +469,43 @@ enum { QM_SF_COUNTED = 0, QM_SF_NO_AF = 1, QM_SF_NO_BIN = 2, QM_SF_TRUTH = 3 };
 int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t na, void* stream);
 int qm_batch_get_surface(qm_batch* b, uint64_t* S /*[n_vcf][3][nq][na] or NULL*/, uint64_t* extra /*[n_vcf][QM_SF_EXTRA] or NULL*/);
 int qm_batch_surface_timings(qm_batch* b, float* ms3);
+
+/* ---- sequence-context profiles: TP, FP and FN per homopolymer x GC cell (build-defined, opt-in) ----
+ * G is one contig of qm_genome_load, length L; POS p is G[p], 1 <= p <= L.  Parameters: half window w, 0 .. QM_CX_MAX_HALF_WINDOW,
+ * and GC bins ng, 1 .. QM_CX_MAX_GC_BINS.  All integer:
+ *   run(i) = 0 when i < 1, i > L or G[i] is no base (not ACGTacgt), else the length of the maximal block of consecutive
+ *     positions around i whose base codes equal G[i]'s (case-insensitive);
+ *   hp(p) = min(15, max(run(p - 1), run(p), run(p + 1)))  -- a call next to a run is in its context; row 0: no base at or next to p;
+ *   nb, gc = the positions of [max(1, p - w), min(L, p + w)] that hold a base, those of them that are C or G;
+ *   cell(p) = hp(p) * ng + min(ng - 1, gc * ng / nb) when nb > 0, else NONE.
+ * NONE is byte QM_CX_NONE in the table and index 16 ng in every output array; n_cells = 16 ng + 1.
+ * qm_genome_context: builds the table of a genome for (w, ng) with the kernel the pass uses, or reuses the one the genome holds
+ *   (one per genome, rebuilt when the parameters change, freed by qm_genome_release; the genome owns it, no batch counts it),
+ *   and copies out cells[L] (cells[p - 1] = cell(p)) and gen[n_cells] = the positions 1 .. L per cell (sum L); either may be NULL.
+ * qm_batch_context: asynchronous on `stream` (NULL = the context's own) but for building a table, which is waited for; `what` =
+ *   QM_CX_RECORDS, QM_CX_TRUTH or both; genome_id_per_vcf[v] = the genome of VCF v or -1 (its rows stay zero).
+ *   Records: rec[v][n_cells + 1][3] = kept, TP and FP lines of qm_batch_strata's record population; a counted record with
+ *   QM_F_NOKEY goes to the last row `nokey` only (its pos is not consulted), every other one to cell(pos), NONE when pos < 1 or
+ *   pos > L.  The rows of a VCF with a genome sum to (QM_S_NPASS, QM_S_TP_LINES, QM_S_FP_LINES).
+ *   Truth: tru[v][n_cells][2]; column 0 = the distinct keys of v's truth set by cell(key >> 4) in v's genome, column 1 = those
+ *   with their bit in v's hit bitmap; the columns sum to QM_S_TRUTH and QM_S_TP_R.  Needs a qm_batch_truth_hits behind the
+ *   latest run and a single-base batch (QM_E_STATE otherwise).
+ *   QM_E_INVAL for a parameter outside the limits (the message names it); QM_E_STATE unless the latest qm_batch_run was finished,
+ *   and for a released genome.  The first call allocates the outputs, counted in qm_batch_device_bytes.
+ * qm_batch_get_context: waits for the pass, then copies (any pointer may be NULL); gen_per_vcf[v][n_cells] = the positions per
+ *   cell of v's genome.  QM_E_STATE if the batch ran since, or for a side the latest call did not make.
+ * qm_batch_context_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] building tables (0 when every
+ *   table was cached), [1] k_context_records, [2] k_context_truth. */
+#define QM_CX_MAX_HALF_WINDOW 1024
+#define QM_CX_MAX_GC_BINS 15
+#define QM_CX_NONE 255
+#define QM_CX_RECORDS 1u
+#define QM_CX_TRUTH 2u
+int qm_genome_context(qm_ctx* ctx, int genome_id, int32_t w, int32_t ng, uint8_t* cells /*[len] or NULL*/, uint64_t* gen /*[16*ng+1] or NULL*/);
+int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, int32_t w, int32_t ng, unsigned what, void* stream);
+int qm_batch_get_context(qm_batch* b, uint64_t* rec /*[n_vcf][16*ng+2][3] or NULL*/, uint64_t* tru /*[n_vcf][16*ng+1][2] or NULL*/,
+                         uint64_t* gen_per_vcf /*[n_vcf][16*ng+1] or NULL*/);
+int qm_batch_context_timings(qm_batch* b, float* ms3);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -819,6 +856,23 @@ typedef struct qm_strata_args {
 int qm_extract_files_strata(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                             void* global_dev, const qm_strata_args* strata);
+
+/* qm_extract_files_ex plus the counts per sequence-context cell over its batch.  Jobs with genome_id[j] >= 0 (a
+ * qm_genome_load id: the genome the VCF was called against) get their rows: rec[j][16 ng + 2][3], tru[j][16 ng + 1][2] and
+ * gen[j][16 ng + 1] of qm_batch_get_context for half window w and ng GC bins; the others (-1) get zero rows.  Single-base mode:
+ * truth hits and both halves run behind the batch's finish; QM_BATCH_ALLELES: the record side only (tru stays zero).  Wanted
+ * pure-strain jobs join the batch against an empty truth set, as in qm_extract_files_strata: everything kept is FP, their tru rows
+ * are zero.  The VCF outputs, stats and roc are those of qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_context_args {
+  int32_t w, ng;
+  const int32_t* genome_id;       /* [n_jobs], -1 = the job is not profiled */
+  uint64_t* rec;                  /* [n_jobs][16 ng + 2][3] */
+  uint64_t* tru;                  /* [n_jobs][16 ng + 1][2] */
+  uint64_t* gen;                  /* [n_jobs][16 ng + 1] */
+} qm_context_args;
+int qm_extract_files_context(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                             void* global_dev, const qm_context_args* context);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

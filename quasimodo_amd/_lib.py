@@ -47,6 +47,11 @@ QM_SF_MAX_QUAL_STEP = 65536
 QM_SF_TP, QM_SF_FP, QM_SF_U = 0, 1, 2
 QM_SF_COUNTED, QM_SF_NO_AF, QM_SF_NO_BIN, QM_SF_TRUTH = 0, 1, 2, 3
 QM_SF_EXTRA = 4
+QM_CX_MAX_HALF_WINDOW = 1024
+QM_CX_MAX_GC_BINS = 15
+QM_CX_NONE = 255
+QM_CX_RECORDS = 1
+QM_CX_TRUTH = 2
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -70,6 +75,8 @@ EXPORTS = (
     "qm_batch_votes", "qm_batch_get_votes", "qm_batch_get_vote_keys", "qm_batch_vote_groups", "qm_batch_vote_timings", "qm_extract_files_votes",
     "qm_batch_nearmiss", "qm_batch_get_nearmiss", "qm_batch_get_nearmiss_cls", "qm_batch_get_nearmiss_truth", "qm_batch_nearmiss_timings", "qm_extract_files_nearmiss",
     "qm_batch_surface", "qm_batch_get_surface", "qm_batch_surface_timings", "qm_extract_files_surface",
+    "qm_genome_context", "qm_batch_context", "qm_batch_get_context", "qm_batch_context_timings",
+    "qm_extract_files_context",
 )
 
 
@@ -131,6 +138,11 @@ class SurfaceArgs(C.Structure):
                 ("S", C.c_void_p), ("extra", C.c_void_p)]
 
 
+class ContextArgs(C.Structure):
+    """include/qmvt.h qm_context_args"""
+    _fields_ = [("w", C.c_int32), ("ng", C.c_int32), ("genome_id", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("gen", C.c_void_p)]
+
+
 class FileJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("truth_path", C.c_char_p), ("mode", C.c_int32), ("pure", C.c_int32),
                 ("filtered_out", C.c_char_p), ("tp_out", C.c_char_p), ("fp_out", C.c_char_p)]
@@ -151,7 +163,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -356,6 +368,12 @@ def lib():
     L.qm_batch_surface_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_extract_files_surface.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                            C.POINTER(SurfaceArgs)]
+    L.qm_genome_context.argtypes = [vp, i32, C.c_int32, C.c_int32, vp, vp]
+    L.qm_batch_context.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint, vp]
+    L.qm_batch_get_context.argtypes = [vp, vp, vp, vp]
+    L.qm_batch_context_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_extract_files_context.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                           C.POINTER(ContextArgs)]
     _lib = L
     return L
 

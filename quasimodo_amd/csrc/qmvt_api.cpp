@@ -26,6 +26,7 @@
 #include "qmvt_afprofile.h"
 #include "qmvt_truthside.h"
 #include "qmvt_strata.h"
+#include "qmvt_context.h"
 #include "qmvt_votes.h"
 #include "qmvt_boot.h"
 #include "qmvt_nearmiss.h"
@@ -81,6 +82,11 @@ struct Genome {
   uint32_t* d_words = nullptr;
   int64_t len = 0;
   bool released = false;
+  // the sequence-context table of qm_genome_context / qm_batch_context, built at first use and kept per
+  // (half window, GC bins): one cell byte per position (len rounded up to 16), the positions per cell; freed with the genome
+  uint8_t* d_ctab = nullptr;
+  unsigned long long* d_cgen = nullptr;   // [CX_MAX_CELLS]
+  int32_t cx_w = -1, cx_ng = -1;          // what the table was built with (-1: not built)
 };
 
 // a strata set of qm_strata_load: the flattened segment table on both sides, and, for tables too large for LDS,
@@ -195,7 +201,7 @@ extern "C" void qm_destroy(qm_ctx* c) {
     (void)hipFree(t.d_xkeys); (void)hipFree(t.d_xref); (void)hipFree(t.d_xalt); (void)hipFree(t.d_xtidx);
   }
   (void)hipFree(c->d_truths);
-  for (auto& g : c->genomes) (void)hipFree(g.d_words);
+  for (auto& g : c->genomes) { (void)hipFree(g.d_words); (void)hipFree(g.d_ctab); (void)hipFree(g.d_cgen); }
   for (auto& t : c->strata) { (void)hipFree(t.d_bp); (void)hipFree(t.d_masks); (void)hipFree(t.d_cidx); }
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->aux) (void)hipStreamDestroy(c->aux);
@@ -362,9 +368,51 @@ extern "C" int qm_genome_release(qm_ctx* c, int genome_id) {
   HIPCHK(hipDeviceSynchronize());   // a motif pass may still read it on a stream of the caller's
   Genome& g = c->genomes[(size_t)genome_id];
   (void)hipFree(g.d_words);
-  g.d_words = nullptr;
-  g.len = 0;
+  (void)hipFree(g.d_ctab);
+  (void)hipFree(g.d_cgen);
+  g = Genome();
   g.released = true;
+  return QM_OK;
+}
+
+// the sequence-context table of a genome
+static int context_params(const char* who, int32_t w, int32_t ng) {
+  if (w < 0 || w > QM_CX_MAX_HALF_WINDOW) return fail(QM_E_INVAL, "%s: half window %d (0 to %d)", who, w, QM_CX_MAX_HALF_WINDOW);
+  if (ng < 1 || ng > QM_CX_MAX_GC_BINS) return fail(QM_E_INVAL, "%s: %d GC bins (1 to %d)", who, ng, QM_CX_MAX_GC_BINS);
+  return QM_OK;
+}
+// The table of live genome `gid` for (w, ng): the cached one, or built on `st` and waited for, so that every later stream may read
+// it.  A rebuild first drains the device: a pass on another stream may still read the table it replaces.  *built: a kernel ran.
+static int context_table(qm_ctx* c, int gid, int32_t w, int32_t ng, hipStream_t st, bool* built) {
+  Genome& g = c->genomes[(size_t)gid];
+  if (g.cx_w == w && g.cx_ng == ng) return QM_OK;
+  if (g.cx_w >= 0) HIPCHK(hipDeviceSynchronize());
+  g.cx_w = g.cx_ng = -1;
+  if (!g.d_ctab) DALLOC(g.d_ctab, (size_t)((g.len + 15) / 16 * 16));
+  if (!g.d_cgen) DALLOC(g.d_cgen, (size_t)CX_MAX_CELLS);
+  HIPCHK(hipMemsetAsync(g.d_cgen, 0, CX_MAX_CELLS * 8, st));
+  ContextBuildParams P;
+  P.words = g.d_words; P.tab = g.d_ctab; P.gen = g.d_cgen;
+  P.len = (int32_t)g.len; P.w = w; P.ng = ng; P.pad = 0;
+  launch_context_build(P, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  g.cx_w = w; g.cx_ng = ng;
+  *built = true;
+  return QM_OK;
+}
+extern "C" int qm_genome_context(qm_ctx* c, int genome_id, int32_t w, int32_t ng, uint8_t* cells, uint64_t* gen) {
+  if (!c || genome_id < 0 || genome_id >= (int)c->genomes.size() || c->genomes[(size_t)genome_id].released)
+    return fail(QM_E_INVAL, "qm_genome_context: no live genome %d", genome_id);
+  int rc = context_params("qm_genome_context", w, ng);
+  if (rc != QM_OK) return rc;
+  HIPCHK(hipSetDevice(c->dev));
+  bool built = false;
+  rc = context_table(c, genome_id, w, ng, c->stream, &built);
+  if (rc != QM_OK) return rc;
+  const Genome& g = c->genomes[(size_t)genome_id];
+  if (cells) HIPCHK(hipMemcpy(cells, g.d_ctab, (size_t)g.len, hipMemcpyDeviceToHost));
+  if (gen) HIPCHK(hipMemcpy(gen, g.d_cgen, (size_t)(16 * ng + 1) * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 
@@ -796,6 +844,18 @@ struct qm_batch {
   bool sf_timed = false;              // the latest qm_batch_surface recorded them
   int32_t sf_cells = 0;               // nq * na of the latest qm_batch_surface
   bool sf_valid = false;              // qm_batch_surface was called behind the latest run
+  // qm_batch_context (lazy): [n_vcf][16 ng + 2][2] kept / TP lines, [n_vcf][16 ng + 1][2] truth keys / hit ones,
+  // [n_vcf][16 ng + 1] positions per cell (copies of the genomes' counts as the pass saw them), the per-VCF tables and the rows
+  // of k_context_truth; ev_cx says when the pass is done
+  DevBuf<uint64_t> cx_rec, cx_tru, cx_gen;
+  DevBuf<ContextTab> cx_tabs;
+  DevBuf<ContextTruthRow> cx_rows;
+  hipEvent_t ev_cx = nullptr;
+  hipEvent_t ev_cxt[4] = {};          // qm_batch_set_timing: around the table builds, k_context_records, k_context_truth
+  bool cx_timed = false;              // the latest qm_batch_context recorded them
+  bool cx_built = false;              // ... and built a table (else its build time is 0)
+  int32_t cx_ng = 0;                  // GC bins of the latest qm_batch_context
+  unsigned cx_made = 0;               // QM_CX_* halves the latest qm_batch_context made behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -826,6 +886,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_nmt) if (e) (void)hipEventDestroy(e);
   if (b->ev_sf) (void)hipEventDestroy(b->ev_sf);
   for (auto& e : b->ev_sft) if (e) (void)hipEventDestroy(e);
+  if (b->ev_cx) (void)hipEventDestroy(b->ev_cx);
+  for (auto& e : b->ev_cxt) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -1158,6 +1220,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->votes_valid = false;
   b->nm_valid = false;
   b->sf_valid = false;
+  b->cx_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -2480,6 +2543,123 @@ extern "C" int qm_batch_get_strata(qm_batch* b, uint64_t* rec, uint64_t* tru) {
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->d_stru, nv * (S + 1) * 2 * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
+// the counts per sequence-context cell of the finished batch
+extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, int32_t w, int32_t ng, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_context");
+  if (!genome_id_per_vcf) return fail(QM_E_INVAL, "qm_batch_context: NULL genome ids");
+  int rc = context_params("qm_batch_context", w, ng);
+  if (rc != QM_OK) return rc;
+  if (!what || (what & ~(QM_CX_RECORDS | QM_CX_TRUTH))) return fail(QM_E_INVAL, "qm_batch_context: what = %u", what);
+  qm_ctx* c = b->ctx;
+  for (int v = 0; v < b->n_vcf; ++v) {
+    const int gid = genome_id_per_vcf[v];
+    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_context: VCF %d names genome %d (have %zu)", v, gid, c->genomes.size());
+    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_context: VCF %d names released genome %d", v, gid);
+  }
+  if (what & QM_CX_TRUTH) {
+    if (b->ext) return fail(QM_E_STATE, "qm_batch_context: allele-extended batches have no truth-side bitmaps (QM_CX_RECORDS only)");
+    if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_context: QM_CX_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    rc = truths_live(b, "qm_batch_context");
+    if (rc != QM_OK) return rc;
+  }
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_cx, &st);
+  if (rc != QM_OK) return rc;
+  const size_t nv = (size_t)b->n_vcf, n_cells = (size_t)(16 * ng + 1);
+  b->cx_made = 0;   // from here on the outputs are rewritten
+  rc = b->cx_gen.grow((int64_t)std::max<size_t>(nv * n_cells, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->cx_tabs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_cxt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->cx_timed = false;
+  b->cx_built = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_cxt[0], st));
+  std::vector<ContextTab> tabs(nv, ContextTab{nullptr, 0});
+  HIPCHK(hipMemsetAsync(b->cx_gen, 0, std::max<size_t>(nv * n_cells, 1) * 8, st));
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = genome_id_per_vcf[v];
+    if (gid < 0) continue;
+    rc = context_table(c, gid, w, ng, st, &b->cx_built);
+    if (rc != QM_OK) return rc;
+    const Genome& g = c->genomes[(size_t)gid];
+    tabs[v] = ContextTab{g.d_ctab, g.len};
+    HIPCHK(hipMemcpyAsync(b->cx_gen + v * n_cells, g.d_cgen, n_cells * 8, hipMemcpyDeviceToDevice, st));
+  }
+  if (nv) HIPCHK(hipMemcpy(b->cx_tabs, tabs.data(), nv * sizeof(ContextTab), hipMemcpyHostToDevice));   // blocking: tabs dies here
+  if (T) HIPCHK(hipEventRecord(b->ev_cxt[1], st));
+  if (what & QM_CX_RECORDS) {
+    const size_t words = nv * (n_cells + 1) * 2;
+    rc = b->cx_rec.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
+    if (rc != QM_OK) return rc;
+    HIPCHK(hipMemsetAsync(b->cx_rec, 0, words * 8, st));
+    ContextRecParams P;
+    P.spans = b->d_spans; P.tabs = b->cx_tabs; P.pos = b->pos; P.flags = b->flags;
+    P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+    P.out = b->cx_rec;
+    P.n_spans = (int32_t)b->L.spans.size(); P.ng = ng;
+    launch_context_records(P, st);
+    HIPCHK(hipGetLastError());
+  }
+  if (T) HIPCHK(hipEventRecord(b->ev_cxt[2], st));
+  if (what & QM_CX_TRUTH) {
+    const size_t words = nv * n_cells * 2;
+    rc = b->cx_tru.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
+    if (rc == QM_OK) rc = b->cx_rows.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+    if (rc != QM_OK) return rc;
+    std::vector<ContextTruthRow> rows(nv);
+    int64_t max_n = 0;
+    for (size_t v = 0; v < nv; ++v) {
+      rows[v].keys = c->truths[(size_t)b->L.vcfs[v].truth].d_keys;
+      rows[v].hits = b->d_hits + b->h_hit_off[v];
+      rows[v].tab = tabs[v].tab;
+      rows[v].n = b->h_hit_tn[v];   // T' as the hit bitmaps were sized
+      rows[v].len = tabs[v].len;
+      max_n = std::max(max_n, rows[v].n);
+    }
+    HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+    if (nv) HIPCHK(hipMemcpy(b->cx_rows, rows.data(), nv * sizeof(ContextTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
+    HIPCHK(hipMemsetAsync(b->cx_tru, 0, words * 8, st));
+    launch_context_truth(b->cx_rows, (int)nv, max_n, ng, reinterpret_cast<unsigned long long*>(b->cx_tru.p), st);
+    HIPCHK(hipGetLastError());
+  }
+  if (T) { HIPCHK(hipEventRecord(b->ev_cxt[3], st)); b->cx_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_cx, st));
+  b->cx_ng = ng;
+  b->cx_made = what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_context(qm_batch* b, uint64_t* rec, uint64_t* tru, uint64_t* gen_per_vcf) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_context: NULL batch");
+  if (!b->cx_made) return fail(QM_E_STATE, "qm_batch_get_context: no qm_batch_context behind the latest run");
+  if ((rec && !(b->cx_made & QM_CX_RECORDS)) || (tru && !(b->cx_made & QM_CX_TRUTH)))
+    return fail(QM_E_STATE, "qm_batch_get_context: the latest qm_batch_context did not make the %s side", rec && !(b->cx_made & QM_CX_RECORDS) ? "record" : "truth");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_cx));
+  const size_t nv = (size_t)b->n_vcf, n_cells = (size_t)(16 * b->cx_ng + 1);
+  if (rec && nv) {
+    std::vector<uint64_t> kt(nv * (n_cells + 1) * 2);
+    HIPCHK(hipMemcpy(kt.data(), b->cx_rec, kt.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nv * (n_cells + 1); ++i) {   // FP lines = kept - TP
+      rec[3 * i] = kt[2 * i];
+      rec[3 * i + 1] = kt[2 * i + 1];
+      rec[3 * i + 2] = kt[2 * i] - kt[2 * i + 1];
+    }
+  }
+  if (tru && nv) HIPCHK(hipMemcpy(tru, b->cx_tru, nv * n_cells * 2 * 8, hipMemcpyDeviceToHost));
+  if (gen_per_vcf && nv) HIPCHK(hipMemcpy(gen_per_vcf, b->cx_gen, nv * n_cells * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_context_timings(qm_batch* b, float* ms3) {
+  if (!b || !ms3) return fail(QM_E_INVAL, "qm_batch_context_timings: NULL");
+  if (!b->cx_made) return fail(QM_E_STATE, "qm_batch_context_timings: no qm_batch_context behind the latest run");
+  if (!b->cx_timed) return fail(QM_E_STATE, "qm_batch_context_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_cxt[3]));
+  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_cxt[i], b->ev_cxt[i + 1]));
+  if (!b->cx_built) ms3[0] = 0.0f;   // every table was cached
+  return QM_OK;
+}
 // paired block-bootstrap replicates of the finished batch's counts
 extern "C" int qm_boot_draws(uint64_t seed, int32_t n_win, int32_t n_rep, uint16_t* mult) {
   if (n_win < 1 || n_win > QM_BOOT_MAX_WINDOWS || n_rep < 0 || n_rep > QM_BOOT_MAX_REP || (n_rep > 0 && !mult))
@@ -2577,7 +2757,7 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
   if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
   else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
-  for (hipEvent_t e : {b->ev_strata, b->ev_boot, b->ev_votes, b->ev_nm})   // and the passes that read the hit bitmaps, on whatever stream
+  for (hipEvent_t e : {b->ev_strata, b->ev_boot, b->ev_votes, b->ev_nm, b->ev_cx})   // and the passes that read the hit bitmaps, on whatever stream
     if (e) HIPCHK(hipStreamWaitEvent(st, e, 0));
   // (the one pass that does not open with pass_stream: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
   rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);

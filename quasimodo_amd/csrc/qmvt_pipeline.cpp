@@ -298,16 +298,17 @@ struct Passes {
   uint64_t* motifs_out = nullptr;
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
-  const qm_surface_args* sf = nullptr;
+  const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
   bool wants_boot(int j) const { return ba && ba->want[j] != 0; }
   bool wants_surface(int j) const { return sf && sf->want[j] != 0; }
+  bool wants_context(int j) const { return cx && cx->genome_id[j] >= 0; }
   bool wants_af(int j) const { return wants_profile(j) || wants_surface(j); }   // the INFO column is scanned and uploaded
   // the passes a pure-strain job joins the batch for (against an empty truth set, for its rows of the pass only: its files,
   // stats and ROC rows are made as for any pure-strain job); every mixed-sample job is in the batch anyway
-  bool any_batch_only(int j) const { return has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j); }
+  bool any_batch_only(int j) const { return has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j) || wants_context(j); }
 };
 
 // what a pass sees of the call: the finished batch and the jobs behind its VCFs
@@ -398,6 +399,22 @@ int strata_pass(const PassCtx& c, const qm_strata_args* sa, std::string& err) {
   if (rc == QM_OK) rc = qm_batch_strata(c.batch, sa->strata_id, c.ext ? QM_STRATA_RECORDS : (QM_STRATA_RECORDS | QM_STRATA_TRUTH), nullptr);
   if (rc == QM_OK) rc = qm_batch_get_strata(c.batch, rec.data(), c.ext ? nullptr : tru.data());
   if (rc == QM_OK) { c.scatter_rows(sa->rec, rec, rw, want); if (!c.ext) c.scatter_rows(sa->tru, tru, tw, want); }
+  return c.lib(rc, err);
+}
+
+// the counts per sequence-context cell, on the columns, masks and truth keys still in HBM
+int context_pass(const PassCtx& c, const Passes& P, std::string& err) {
+  const qm_context_args* cx = P.cx;
+  auto want = [&](int j) { return P.wants_context(j); };
+  if (!cx || !c.any(want)) return QM_OK;
+  const size_t nc = (size_t)(16 * cx->ng + 1), rw = 3 * (nc + 1), tw = 2 * nc;
+  std::vector<int32_t> gid(c.nv, -1);
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) gid[(size_t)c.J[(size_t)j].batch_v] = cx->genome_id[j];
+  std::vector<uint64_t> rec(c.nv * rw), tru(c.nv * tw), gen(c.nv * nc);
+  int rc = c.ext ? QM_OK : qm_batch_truth_hits(c.batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_context(c.batch, gid.data(), cx->w, cx->ng, c.ext ? QM_CX_RECORDS : (QM_CX_RECORDS | QM_CX_TRUTH), nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_context(c.batch, rec.data(), c.ext ? nullptr : tru.data(), gen.data());
+  if (rc == QM_OK) { c.scatter_rows(cx->rec, rec, rw, want); if (!c.ext) c.scatter_rows(cx->tru, tru, tw, want); c.scatter_rows(cx->gen, gen, nc, want); }
   return c.lib(rc, err);
 }
 
@@ -736,6 +753,26 @@ extern "C" int qm_extract_files_strata(qm_ctx* ctx, int n_jobs, const qm_file_jo
     memset(strata->tru, 0, sizeof(uint64_t) * 2 * (size_t)(info[0] + 1) * (size_t)n_jobs);
   }
   Passes P; P.sa = strata;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// the counts per sequence-context cell behind the worker
+extern "C" int qm_extract_files_context(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                        qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                        int n_slots, void* global_dev, const qm_context_args* context) {
+  const qm_context_args* cx = context;
+  if (!cx || (n_jobs > 0 && (!cx->genome_id || !cx->rec || !cx->tru || !cx->gen))) return fail(QM_E_INVAL, "qm_extract_files_context: NULL arguments");
+  if (cx->w < 0 || cx->w > QM_CX_MAX_HALF_WINDOW)
+    return fail(QM_E_INVAL, "qm_extract_files_context: half window " + std::to_string(cx->w) + " (0 to " + std::to_string(QM_CX_MAX_HALF_WINDOW) + ")");
+  if (cx->ng < 1 || cx->ng > QM_CX_MAX_GC_BINS)
+    return fail(QM_E_INVAL, "qm_extract_files_context: " + std::to_string(cx->ng) + " GC bins (1 to " + std::to_string(QM_CX_MAX_GC_BINS) + ")");
+  if (n_jobs > 0) {
+    const size_t nc = (size_t)(16 * cx->ng + 1);
+    memset(cx->rec, 0, sizeof(uint64_t) * 3 * (nc + 1) * (size_t)n_jobs);
+    memset(cx->tru, 0, sizeof(uint64_t) * 2 * nc * (size_t)n_jobs);
+    memset(cx->gen, 0, sizeof(uint64_t) * nc * (size_t)n_jobs);
+  }
+  Passes P; P.cx = cx;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -1093,6 +1130,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = truthside_pass(pc, P.ts, err);
       if (rc == QM_OK) rc = votes_pass(pc, P.va, err);
       if (rc == QM_OK) rc = nearmiss_pass(pc, P.nm, err);
+      if (rc == QM_OK) rc = context_pass(pc, P, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

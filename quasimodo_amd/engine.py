@@ -46,6 +46,7 @@ class Engine:
         self._h = h
         self.device = int(device)
         self._batches = weakref.WeakSet()   # a batch must not outlive its context (qm_batch_destroy uses it)
+        self._genome_len = {}               # genome id -> bases, as loaded (genome_context sizes its array by it)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -98,10 +99,21 @@ class Engine:
         seq = bytes(seq)
         gid = C.c_int(-1)
         check(self._L.qm_genome_load(self._h, seq, len(seq), C.byref(gid)), self._h)
+        self._genome_len[gid.value] = len(seq)
         return gid.value
 
     def genome_release(self, gid):
         check(self._L.qm_genome_release(self._h, int(gid)), self._h)
+
+    def genome_context(self, gid, w=50, ng=10):
+        """qm_genome_context: (cells uint8 [L] -- the context cell of every position, context.NONE_BYTE where it has none --,
+        gen uint64 [16 ng + 1] -- positions per cell) of a loaded genome, by the kernel the pass uses; context.cells restates it"""
+        from .context import check_params
+        w, ng = check_params(w, ng)
+        L = int(self._genome_len.get(int(gid), 0))   # (an id never loaded: the library refuses it)
+        cells, gen = np.zeros(L, np.uint8), np.zeros(16 * ng + 1, np.uint64)
+        check(self._L.qm_genome_context(self._h, int(gid), w, ng, _p(cells), _p(gen)), self._h)
+        return cells, gen
 
     # -- strata sets (counts per genome region, DESIGN.md 4.10) -------------------
     def strata_load(self, strata):
@@ -195,7 +207,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None):
+                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -225,6 +237,10 @@ class Engine:
         surface: {"want": [0/1 per job], "q_step": 4, "nq": 64, "na": 50} -- qm_extract_files_surface: wanted rows
         gain `surface` ([3][nq][na] uint64: TP records, FP records, found truth keys under QUAL >= i * q_step and AF >= k / na),
         `surface_extra` ([QM_SF_EXTRA] ints: counted, counted without AF, left out, T') and `surface_params` (q_step, nq, na).
+        context: {"genomes": [genome_load id or None / -1 per job], "half_window": 50, "n_gc": 10} -- qm_extract_files_context
+        (DESIGN.md 4.16): the rows of jobs with a genome gain `context_rec` ([16 n_gc + 2][3] uint64: kept, TP, FP lines per cell,
+        none, nokey), `context_tru` ([16 n_gc + 1][2]: truth keys, hit ones; None in the allele-extended mode), `context_gen`
+        ([16 n_gc + 1]: positions of the genome per cell) and `context_params` (half_window, n_gc).
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         from .passes import check_shared_call
@@ -234,7 +250,7 @@ class Engine:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
@@ -312,6 +328,22 @@ class Engine:
         sa = _lib.StrataArgs(int(strata["id"]), 0, _p(swant), _p(srec), _p(stru))
         unpack = lambda k: {"strata_rec": srec[k].copy(), "strata_tru": None if alleles else stru[k].copy()} if swant[k] else {}
         return self._L.qm_extract_files_strata, (C.byref(sa),), unpack
+
+    def _files_context(self, n, context, alleles=False, **kw):
+        from .context import check_params, n_cells
+        w, ng = check_params(context.get("half_window", 50), context.get("n_gc", 10))
+        cgid = _c([-1 if g is None else int(g) for g in context["genomes"]] or [-1], np.int32)
+        if n and cgid.shape[0] != n:
+            raise ValueError("context: %d genomes entries for %d jobs" % (len(context["genomes"]), n))
+        nc = n_cells(ng)
+        crec = np.zeros((max(n, 1), nc + 1, 3), np.uint64)
+        ctru = np.zeros((max(n, 1), nc, 2), np.uint64)
+        cgen = np.zeros((max(n, 1), nc), np.uint64)
+        ca = _lib.ContextArgs(w, ng, _p(cgid), _p(crec), _p(ctru), _p(cgen))
+        ca.keep = cgid   # (read during the call; the other arrays live in unpack)
+        unpack = lambda k: {"context_rec": crec[k].copy(), "context_tru": None if alleles else ctru[k].copy(), "context_gen": cgen[k].copy(),
+                            "context_params": (w, ng)} if cgid[k] >= 0 else {}
+        return self._L.qm_extract_files_context, (C.byref(ca),), unpack
 
     def _files_boot(self, n, boot, **kw):
         bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
@@ -684,6 +716,40 @@ class Batch:
         ms = (C.c_float * 3)()
         self._ck(self._L.qm_batch_surface_timings(self._h, ms))
         return {"surface_records_ms": ms[0], "surface_truth_ms": ms[1], "surface_sums_ms": ms[2]}
+
+    # -- sequence-context profiles ----------------------------------
+    def context(self, genome_ids, half_window=50, n_gc=10, truth=False, stream=None, fetch=True):
+        """qm_batch_context + qm_batch_get_context: the counts of the finished batch per homopolymer x GC cell (genome_ids: one
+        genome id or -1 per VCF); truth=True: the truth side too (needs truth_hits).  fetch=False: enqueue only
+        (context_counts() waits and copies)"""
+        from .context import check_params
+        w, ng = check_params(half_window, n_gc)
+        g = _c(genome_ids, np.int32)
+        if g.shape[0] != self.n_vcf:
+            raise ValueError("genome_ids: %d entries for %d VCFs" % (g.shape[0], self.n_vcf))
+        what = _lib.QM_CX_RECORDS | (_lib.QM_CX_TRUTH if truth else 0)
+        self._ck(self._L.qm_batch_context(self._h, _p(g) if self.n_vcf else _p(np.zeros(1, np.int32)), w, ng, what,
+                                          C.c_void_p(stream) if stream else None))
+        self._context = (ng, bool(truth))   # (a refused call leaves the library's latest pass, and this, as they were)
+        return self.context_counts() if fetch else None
+
+    def context_counts(self):
+        """qm_batch_get_context: (rec [n_vcf][n_cells + 1][3] uint64 -- kept, TP, FP lines; rows the cells hp * n_gc + gc_bin,
+        NONE, nokey --, tru [n_vcf][n_cells][2] -- truth keys, hit ones -- or None when the truth side was not made,
+        gen [n_vcf][n_cells] -- positions per cell of each VCF's genome); n_cells = 16 n_gc + 1"""
+        ng, truth = getattr(self, "_context", (1, False))
+        nc, nv = 16 * ng + 1, max(self.n_vcf, 1)
+        rec = np.zeros((nv, nc + 1, 3), np.uint64)
+        tru = np.zeros((nv, nc, 2), np.uint64) if truth else None
+        gen = np.zeros((nv, nc), np.uint64)
+        self._ck(self._L.qm_batch_get_context(self._h, _p(rec), _p(tru), _p(gen)))
+        return rec[:self.n_vcf], None if tru is None else tru[:self.n_vcf], gen[:self.n_vcf]
+
+    def context_timings(self):
+        """qm_batch_context_timings (set_timing on): milliseconds of the latest context() between HIP events"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.qm_batch_context_timings(self._h, ms))
+        return {"context_build_ms": ms[0], "context_records_ms": ms[1], "context_truth_ms": ms[2]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

@@ -62,6 +62,9 @@ class Job:
     fn_why_out: str = None    # where the job's `POS REF ALT class` table of its missed truth rows goes
     # the filter surface; mixed samples only
     surface: tuple = None     # (q_step, nq, na): stats gain surface / surface_extra / surface_params (the same for every swept job of a call)
+    # sequence-context profiles
+    context: tuple = None     # (half_window, n_gc): stats gain context_rec / context_tru / context_gen (the same for every profiled job of a call)
+    context_genome: str = None   # FASTA of the genome the VCF was called against: its positions are what the cells are made of
 
 
 def _paths(job):
@@ -132,7 +135,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None):
+                 surface=None, context=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -171,12 +174,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     job gets stats["surface"] ([3][nq][na]: TP records, FP records and found truth keys under QUAL >= i * q_step and AF >= k / na),
     stats["surface_extra"] ([4]: counted records, counted records without AF, records without a quality bin, T') and
     stats["surface_params"].
+    context: {"genomes": [FASTA path or None per job], "half_window": 50, "n_gc": 10} (quasimodo_amd.context; default: the jobs'
+    Job.context / Job.context_genome): the jobs with a genome get stats["context_rec"] ([16 n_gc + 2][3]: kept, TP, FP lines per
+    homopolymer x GC cell, then none, nokey), stats["context_tru"] ([16 n_gc + 1][2]: truth keys and hit ones; None in the
+    allele-extended mode; zero for pure-strain samples), stats["context_gen"] ([16 n_gc + 1]: the genome's positions per cell) and
+    stats["context_params"].  Every distinct FASTA is loaded once and released before this returns.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
-             "surface": surface is not None and surface is not False}
+             "surface": surface is not None and surface is not False, "context": context is not None}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -207,6 +215,14 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         for j in jobs:
             if not is_pure_strain(j.vcf_file):
                 j.surface = spar
+    if context is not None:
+        from .context import DEFAULT_GC_BINS, DEFAULT_HALF_WINDOW, check_params
+        cpar = check_params(context.get("half_window", DEFAULT_HALF_WINDOW), context.get("n_gc", DEFAULT_GC_BINS))
+        cgen = list(context["genomes"])
+        if len(cgen) != len(jobs):
+            raise ValueError("context: %d genomes entries for %d jobs" % (len(cgen), len(jobs)))
+        for j, g in zip(jobs, cgen):
+            j.context, j.context_genome = (cpar, g) if g else (None, None)
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -263,11 +279,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        need = not all(pure) or any(j.genome or j.profile or j.strata or j.boot for j in jobs)   # (a vote group holds no pure-strain sample)
+        need = not all(pure) or any(j.genome or j.profile or j.strata or j.boot or j.context for j in jobs)   # (a vote group holds no pure-strain sample)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = sf = None
+    ts = vt = nm = sf = cxs = None
+    if any(j.context is not None for j in jobs):
+        from .context import check_params
+        for j in jobs:
+            if j.context is not None and not j.context_genome:
+                raise ValueError("%s: Job.context without Job.context_genome (the FASTA the VCF was called against)" % j.vcf_file)
+        cxs = dict(zip(("half_window", "n_gc"), check_params(*next(j.context for j in jobs if j.context is not None))))
     if any(j.surface is not None for j in jobs):
         from .surface import params
         sf = dict(zip(("q_step", "nq", "na"), params(*next(j.surface for j in jobs if j.surface is not None))),
@@ -318,6 +340,12 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                     if j.genome and j.genome not in loaded:
                         loaded[j.genome] = engine.genome_load(read_fasta(j.genome))
                 gids = [loaded[j.genome] if j.genome else -1 for j in jobs]
+            if cxs is not None:
+                from .motifs import read_fasta
+                for j in jobs:
+                    if j.context is not None and j.context_genome not in loaded:
+                        loaded[j.context_genome] = engine.genome_load(read_fasta(j.context_genome))
+                cxs["genomes"] = [loaded[j.context_genome] if j.context is not None else -1 for j in jobs]
             # the passes with parameters: the tuple the jobs agreed on, and who wants the pass
             par = {f: next((getattr(j, f) for j in jobs if getattr(j, f)), None) for f in ("profile", "strata", "boot")}
             want = lambda f: [1 if getattr(j, f) else 0 for j in jobs]
@@ -333,7 +361,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

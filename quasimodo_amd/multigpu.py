@@ -83,7 +83,7 @@ def default_body(jobs, indices, device, opts):
     dev = torch.device("cuda", device)
     counters = torch.zeros((n_slots, 3, n_bins), dtype=torch.int64, device=dev) if on_gpu else None
     extra = None
-    need_engine = bool(jobs) and (not all(is_pure_strain(j.vcf_file) for j in jobs) or opts.get("post") or any(j.genome or j.profile or j.strata or j.boot for j in jobs))
+    need_engine = bool(jobs) and (not all(is_pure_strain(j.vcf_file) for j in jobs) or opts.get("post") or any(j.genome or j.profile or j.strata or j.boot or j.context for j in jobs))
     eng = Engine(device) if need_engine else None
     try:
         if jobs:

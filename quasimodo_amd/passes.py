@@ -16,6 +16,8 @@ PASSES = (
          "boot: the resampled jobs of one call share one window, window count, replicate count and seed", ()),
     Pass("votes", ("vote_group",), ("votes",), "--votes", None, ()),
     Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
+    Pass("context", ("context",), ("context",), "--seq-context",
+         "context: the profiled jobs of one call share one half window and one GC bin count", ()),
     Pass("surface", ("surface",), ("surface",), "--filter-surface",
          "surface: the swept jobs of one call share one QUAL step and one pair of bin counts", ()),
 )

@@ -164,7 +164,8 @@ def _shared_call(**asked):
 def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl",
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
-                         surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None):
+                         surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
+                         context_gc_bins=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -197,13 +198,18 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     filter_surface: TP, FP and FN under every filter QUAL >= q and AF >= a (quasimodo_amd.surface), with
     surface_qual_step / surface_qual_bins / surface_af_bins (default 4, 64, 50; QUAL 20 must be a grid line):
     callers/{caller}/surface/{sample}.{ref}.{caller}.surface.tsv for every mixed sample and final_tables/caller_best_filter.tsv.
+    seq_context: {"TM": FASTA, "TA": FASTA}, the genomes as for mutation_context, with context_window / context_gc_bins (default
+    50, 10; quasimodo_amd.context): the counts per homopolymer x GC cell are taken behind the classification and
+    final_tables/caller_performance_context.tsv is written (per caller x sample the cells in use, the marginals, none, nokey).
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
-                 truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface)
+                 truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
+                 context=seq_context is not None)
     radius = _explain_radius(explain_errors, explain_radius)
     sweep = _surface_params(filter_surface, surface_qual_step, surface_qual_bins, surface_af_bins)
+    cpar = _context_params(seq_context is not None, context_window, context_gc_bins)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if strata is not None:
@@ -241,6 +247,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             fa = mutation_context.get(mix)
             if not fa or not os.path.isfile(fa):
                 raise WorkflowError("mutation context: no genome FASTA for %s (%s)" % (mix, fa))
+    if cpar is not None:
+        for mix in mixes:
+            fa = seq_context.get(mix)
+            if not fa or not os.path.isfile(fa):
+                raise WorkflowError("sequence context: no genome FASTA for %s (%s)" % (mix, fa))
     if dryrun:
         for s, c, src in plan:
             print("extractTP\t%s\t%s" % (c, src))
@@ -256,6 +267,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("caller_performance_strata\t%s" % ",".join(s[0] for s in strata))
         if bootstrap is not None:
             print("caller_performance_ci\t%d" % _boot_params(bootstrap, [])[2])
+        if cpar is not None:
+            print("caller_performance_context.tsv\t%d\t%d" % cpar)
         if votes:
             _vote_plan(plan, consensus_vcf)
             print("caller_consensus\t%s" % ",".join(callers))
@@ -306,6 +319,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             jobs[-1].points_out = os.path.join(d, "profile", os.path.basename(src)[:-4] + ".points.tsv")
         jobs[-1].strata = strata
         jobs[-1].boot = boot
+        if cpar is not None:
+            jobs[-1].context, jobs[-1].context_genome = cpar, seq_context[s[:2]]
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -363,6 +378,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_votes(meta, jobs, tables, mixed)
         if radius is not None:
             _write_error_classes([(c, s, j) for (c, s), j in zip(meta, jobs) if s in mixed], tables)
+        if cpar is not None:
+            _write_context(os.path.join(tables, "caller_performance_context.tsv"), [(c, s, j) for (c, s), j in zip(meta, jobs)], cpar)
         if sweep is not None:
             _write_surface([(c, s, j) for (c, s), j in zip(meta, jobs) if s in mixed], tables, sweep[0])
     if gpus is not None and (int(gpus) > 1 or _body):
@@ -415,6 +432,38 @@ def _explain_radius(explain_errors, explain_radius):
         return check_radius(DEFAULT_RADIUS if explain_radius is None else explain_radius)
     except ValueError as e:
         raise WorkflowError("--explain-radius: %s" % e) from None
+
+
+def _context_params(on, window, gc_bins):
+    """the parameter pair of --seq-context (None: the pass is off)"""
+    from .context import DEFAULT_GC_BINS, DEFAULT_HALF_WINDOW, check_params
+    if not on:
+        if window is not None or gc_bins is not None:
+            raise WorkflowError("--context-window and --context-gc-bins go with --seq-context")
+        return None
+    try:
+        return check_params(DEFAULT_HALF_WINDOW if window is None else window, DEFAULT_GC_BINS if gc_bins is None else gc_bins)
+    except ValueError as e:
+        raise WorkflowError("--seq-context: %s" % e) from None
+
+
+def _write_context(path, rows, cpar, custom=False):
+    """the sequence-context table: rows of (caller or label, sample, job); genomediff per cell from the truth
+    file's rows as R counts them, placed through the numpy restatement of the genome's table (one per truth file and genome)"""
+    from .context import cells, truth_rows, write_performance_context
+    from .motifs import read_fasta
+    tabs, seen = {}, {}
+    for c, s, j in rows:
+        if "context_rec" not in j.stats:
+            raise WorkflowError("%s/%s: no sequence-context counts came back" % (c, s))
+        if not j.stats.get("pure_strain") and j.stats.get("context_tru") is not None:
+            key = (os.path.realpath(j.snp_file), j.mode, os.path.realpath(j.context_genome))
+            if key not in seen:
+                if key[2] not in tabs:
+                    tabs[key[2]] = cells(read_fasta(j.context_genome), *cpar)
+                seen[key] = truth_rows(j.snp_file, j.mode, tabs[key[2]], cpar[1])
+            j.stats["context_genomediff"] = seen[key]
+    write_performance_context(path, [(c, s, j.stats) for c, s, j in rows], cpar[1], custom=custom)
 
 
 def _surface_params(filter_surface, q_step, nq, na):
@@ -661,7 +710,8 @@ def indel_roc(engine, items, snp_dir, n_bins=256):
 
 def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False, gpus=None, _body=None, _backend="nccl", _same_device=False,
                 truth_side=False, strata=None, bootstrap=None, votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None,
-                filter_surface=False, surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None):
+                filter_surface=False, surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None,
+                context_window=None, context_gc_bins=None):
     """eval_variant_custom.smk with the genome difference (show-snps -CTHIlr TSV) already computed.
     gpus > 1: the VCFs are dealt to that many GPUs (one process each); the rows come back for the table.
     truth_side: callers/fn/{label}.fn.vcf for every VCF; up to five labels form one group (one rank) and
@@ -676,13 +726,20 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     final_tables/caller_error_classes.tsv.
     filter_surface, with surface_qual_step / surface_qual_bins / surface_af_bins (default 4, 64, 50): callers/surface/{label}.surface.tsv
     for every VCF and final_tables/caller_best_filter.tsv (sample "custom").
-    Each of the six runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
+    seq_context: the FASTA of the genome the VCFs were called against (the first reference: the POS of the genome-difference table
+    are its coordinates), with context_window / context_gc_bins (default 50, 10): final_tables/snpcall_benchmark_context.txt is
+    written.
+    Each of the seven runs alone (quasimodo_amd.passes; WorkflowError otherwise)."""
     from .truthside import MAX_GROUP
     from .consensus import MAX_GROUP as VOTE_MAX
     votes = bool(votes) or consensus_vcf is not None
-    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side, nearmiss=explain_errors, surface=filter_surface)
+    _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, truthside=truth_side, nearmiss=explain_errors, surface=filter_surface,
+                 context=seq_context is not None)
     radius = _explain_radius(explain_errors, explain_radius)
     sweep = _surface_params(filter_surface, surface_qual_step, surface_qual_bins, surface_af_bins)
+    cpar = _context_params(seq_context is not None, context_window, context_gc_bins)
+    if cpar is not None and not os.path.isfile(seq_context):
+        raise WorkflowError("sequence context: no genome FASTA (%s)" % seq_context)
     if consensus_vcf is not None and int(consensus_vcf) < 1:
         raise WorkflowError("--consensus-vcf %d: the level is at least 1" % int(consensus_vcf))
     if strata is not None:
@@ -704,6 +761,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     if dryrun:
         for lab, v in zip(labels, vcfs):
             print("extract_TP\t%s\t%s" % (lab, v))
+        if cpar is not None:
+            print("snpcall_benchmark_context.txt\t%d\t%d" % cpar)
         if voted:
             print("caller_consensus\t%s" % ",".join(labels))
             if consensus_vcf is not None:
@@ -728,6 +787,9 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
     os.makedirs(os.path.join(call_dir, "fp"), exist_ok=True)
     boot = _boot_params(bootstrap, [(snps_file, "custom")]) if bootstrap is not None else None
     jobs = [Job(v, snps_file, "custom", call_dir, lab, strata=strata, boot=boot) for lab, v in zip(labels, vcfs)]
+    if cpar is not None:
+        for j in jobs:
+            j.context, j.context_genome = cpar, seq_context
     grouped = truth_side and len(labels) <= MAX_GROUP and not any(is_pure_strain(v) for v in vcfs)
     if truth_side:
         from .extract import _paths, fn_path
@@ -772,6 +834,8 @@ def run_vareval(vcfs, snps_file, outpath, labels=None, engine=None, dryrun=False
         from .bootstrap import write_performance_ci
         _boot_extra(jobs)
         write_performance_ci(os.path.join(results, "final_tables", "snpcall_benchmark_ci.txt"), [(lab, None, j.stats) for lab, j in zip(labels, jobs)], custom=True)
+    if cpar is not None:
+        _write_context(os.path.join(results, "final_tables", "snpcall_benchmark_context.txt"), [(lab, None, j) for lab, j in zip(labels, jobs)], cpar, custom=True)
     if voted:
         _write_votes([(lab, "custom") for lab in labels], jobs, os.path.join(results, "final_tables"), ["custom"])
     if radius is not None:

@@ -127,13 +127,18 @@ def _bootstrap_opts(n_rep, window, seed):
 @click.option("--surface-qual-step", "surface_qual_step", type=int, default=None, help="--filter-surface: QUAL units per grid line; must divide 20 [default: 4].")
 @click.option("--surface-qual-bins", "surface_qual_bins", type=int, default=None, help="--filter-surface: QUAL grid lines [default: 64; 1 to 256].")
 @click.option("--surface-af-bins", "surface_af_bins", type=int, default=None, help="--filter-surface: AF grid lines [default: 50; 1 to 64; at most 4096 cells].")
+@click.option("--seq-context", "seq_context", is_flag=True, default=False,
+              help="TP, FP and FN per homopolymer x local-GC cell of the genome: also write final_tables/caller_performance_context.tsv "
+                   "(needs the genomes: --merlin-ref / --ad169-ref or the config).")
+@click.option("--context-window", "context_window", type=int, default=None, help="--seq-context: positions on either side of a call in its GC window [default: 50; 0 to 1024].")
+@click.option("--context-gc-bins", "context_gc_bins", type=int, default=None, help="--seq-context: GC bins [default: 10; 1 to 15].")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
          mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
-         surface_qual_bins=None, surface_af_bins=None):
+         surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -148,7 +153,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
     genomes = None
-    if mutation_context:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+    if mutation_context or seq_context:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
         pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
@@ -156,7 +161,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
         strata_set = _read_strata(strata, strata_by_name)
         workflow.run_hcmv_variantcall.last_result = None
         jobs = workflow.run_hcmv_variantcall(data or os.path.join(wd, "data", "snp"), out, dryrun=dryrun, gpus=gpus if gpus > 1 else None,
-                                             mutation_context=genomes, truth_side=truth_side,
+                                             mutation_context=genomes if mutation_context else None, truth_side=truth_side,
+                                             seq_context=genomes if seq_context else None, context_window=context_window, context_gc_bins=context_gc_bins,
                                              snp_profile=dict(window=profile_window, n_pos_bins=profile_pos_bins, n_af_bins=profile_af_bins)
                                              if snp_profile else None, strata=strata_set,
                                              bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
@@ -207,10 +213,15 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
 @click.option("--surface-qual-step", "surface_qual_step", type=int, default=None, help="--filter-surface: QUAL units per grid line; must divide 20 [default: 4].")
 @click.option("--surface-qual-bins", "surface_qual_bins", type=int, default=None, help="--filter-surface: QUAL grid lines [default: 64; 1 to 256].")
 @click.option("--surface-af-bins", "surface_af_bins", type=int, default=None, help="--filter-surface: AF grid lines [default: 50; 1 to 64; at most 4096 cells].")
+@click.option("--seq-context", "seq_context", is_flag=True, default=False,
+              help="TP, FP and FN per homopolymer x local-GC cell of the genome: also write final_tables/snpcall_benchmark_context.txt "
+                   "(the genome is the first file of -r/--refs: the one the VCFs were called against).")
+@click.option("--context-window", "context_window", type=int, default=None, help="--seq-context: positions on either side of a call in its GC window [default: 50; 0 to 1024].")
+@click.option("--context-gc-bins", "context_gc_bins", type=int, default=None, help="--seq-context: GC bins [default: 10; 1 to 15].")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
-            surface_qual_bins=None, surface_af_bins=None):
+            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None):
     from quasimodo_amd import workflow
     try:
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
@@ -226,13 +237,16 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
             snps = os.path.join(out, "results", "snp", "nucmer", "%s_%s.maskrepeat.snps" % (g[0], g[1]))   # eval_variant_custom.smk:14-17,40
         else:
             snps = os.path.join(cd, snps)
+        if seq_context and not st["refs"]:
+            raise workflow.PathNotGiven("--seq-context: the reference genome files are not specified (the first one is the genome the VCFs were called against).")
         workflow.run_vareval.last_result = None
         jobs = workflow.run_vareval(st["vcfs"], snps, out, labels=st["labels"], dryrun=dryrun, gpus=gpus if gpus > 1 else None,
                                     truth_side=truth_side, strata=_read_strata(strata, strata_by_name),
                                     bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
                                     votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius,
                                     filter_surface=filter_surface, surface_qual_step=surface_qual_step,
-                                    surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins)
+                                    surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
+                                    seq_context=st["refs"][0] if seq_context else None, context_window=context_window, context_gc_bins=context_gc_bins)
         if json_out and not dryrun:
             _write_json(json_out, "vareval", jobs, workflow.run_vareval)
     except Exception as e:
