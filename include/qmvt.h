@@ -506,6 +506,54 @@ int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, int32_t w, i
 int qm_batch_get_context(qm_batch* b, uint64_t* rec /*[n_vcf][16*ng+2][3] or NULL*/, uint64_t* tru /*[n_vcf][16*ng+1][2] or NULL*/,
                          uint64_t* gen_per_vcf /*[n_vcf][16*ng+1] or NULL*/);
 int qm_batch_context_timings(qm_batch* b, float* ms3);
+
+/* ---- indels and MNPs matched by normal form (build-defined, opt-in, QM_BATCH_ALLELES batches only) ----
+ * A variant is (p, R, A), R and A in [ACGT]+; G is one contig of qm_genome_load, G[p] 1-based, ACGTacgt are bases.
+ * Normalisable: both alleles have inline codes (1 .. QM_ALLELE_INLINE_MAX bases), no QM_F_NOKEY, R != A, 1 <= p and
+ *   p + len(R) - 1 <= L, and G[p .. p + len(R) - 1] spells R.  Otherwise the record keeps its spelling and is counted under the
+ *   first reason that applies: LONG (an allele without an inline code), NOKEY, NOVAR (R == A), RANGE, REFMISMATCH, and NOBASE
+ *   (the walk below met a position without a base).
+ * Normal form: repeat until nothing changes -- (1) if R and A end in the same base, and both have at least 2 bases or p > 1,
+ *   drop that base from both; (2) if either allele is now empty, prepend G[p - 1] to both and decrement p --, then, while both
+ *   alleles have at least 2 bases and the same first base, drop it from both and increment p.  No cap on the shift.
+ * form(v) = the normal form, or the spelling of a variant that has none.  The normalised truth set of (truth set, genome) = the
+ *   distinct forms of the truth set's allele-extended entries; VCFs that share a truth set must name one genome (QM_E_INVAL).
+ * Per record: hitN = it has valid allele codes, no QM_F_NOKEY, and its form is in the normalised truth set; a TP_N line is kept
+ *   and (hitN and QM_F_IDDOT, or QM_F_TPLINE).  The kept set is the batch's.
+ * rec[v][QM_NORM_R_COLS], over the kept records: QM_NORM_R_KEPT, _TP (the batch's TP lines), _TP_N, _RESCUED (TP_N and no TP
+ *   line), _RESPELLED (the normal form differs from the spelling), _SINGLE (respelled into two single bases), then one column
+ *   per reason in the order above.
+ * tru[v][QM_NORM_T_COLS]: QM_NORM_T_ENTRIES (allele-extended truth entries), _FORMS (distinct forms), _FOUND (forms of a kept
+ *   record with hitN, the ID column ignored), _FORM_ONLY (found forms none of whose entries is spelled like a kept record), _BAD
+ *   (entries that are not normalisable).  A VCF whose genome id is -1 keeps zero rows.
+ * Class byte per record, kept or not: QM_NORM_C_RESCUED for a rescued line, else QM_NORM_C_UNCHANGED / _RESPELLED or the
+ *   reason.  With QM_NORM_COLUMNS the pass also keeps every record's form as int32 codes (the input columns where it has no
+ *   normal form) and truth_row = the smallest index, in the order of the truth set's allele-extended table (sorted by
+ *   pos << 4 | nibble, ref, alt), of an entry with the record's form, -1 without hitN.
+ * qm_batch_normalize: asynchronous on `stream` (NULL = the context's own) but for one small blocking copy; it builds the tables
+ *   it needs on that stream at every call.  QM_E_STATE unless the latest qm_batch_run was finished, for a batch without
+ *   QM_BATCH_ALLELES, and for a released genome or truth set.  The first call allocates the outputs (qm_batch_device_bytes).
+ * qm_batch_get_normalize / qm_batch_get_normalized: wait for the pass, then copy; any pointer may be NULL.  QM_E_STATE if the
+ *   batch ran since, for a VCF that named no genome, and for columns the latest call did not keep.
+ * qm_batch_normalize_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] the tables (k_norm_truth,
+ *   k_norm_insert, k_norm_fill), [1] k_norm_records, [2] k_norm_found.
+ * qm_truth_normalized: the distinct forms of a truth set against a genome, sorted by (pos, ref, alt); *n_out = how many,
+ *   QM_E_RANGE (with *n_out set) when capacity is smaller.
+ * qm_truth_entries: the allele-extended entries of a truth set in the order of its table (what truth_row indexes), the same way. */
+#define QM_NORM_R_COLS 12
+#define QM_NORM_T_COLS 5
+#define QM_NORM_COLUMNS 2u
+enum { QM_NORM_R_KEPT = 0, QM_NORM_R_TP = 1, QM_NORM_R_TP_N = 2, QM_NORM_R_RESCUED = 3, QM_NORM_R_RESPELLED = 4, QM_NORM_R_SINGLE = 5,
+       QM_NORM_R_LONG = 6, QM_NORM_R_NOKEY = 7, QM_NORM_R_NOVAR = 8, QM_NORM_R_RANGE = 9, QM_NORM_R_REFMISMATCH = 10, QM_NORM_R_NOBASE = 11 };
+enum { QM_NORM_T_ENTRIES = 0, QM_NORM_T_FORMS = 1, QM_NORM_T_FOUND = 2, QM_NORM_T_FORM_ONLY = 3, QM_NORM_T_BAD = 4 };
+enum { QM_NORM_C_UNCHANGED = 0, QM_NORM_C_RESPELLED = 1, QM_NORM_C_RESCUED = 2, QM_NORM_C_LONG = 3, QM_NORM_C_NOKEY = 4, QM_NORM_C_NOVAR = 5,
+       QM_NORM_C_RANGE = 6, QM_NORM_C_REFMISMATCH = 7, QM_NORM_C_NOBASE = 8 };
+int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf, unsigned what /*0 or QM_NORM_COLUMNS*/, void* stream);
+int qm_batch_get_normalize(qm_batch* b, uint64_t* rec /*[n_vcf][QM_NORM_R_COLS] or NULL*/, uint64_t* tru /*[n_vcf][QM_NORM_T_COLS] or NULL*/);
+int qm_batch_get_normalized(qm_batch* b, int vcf, int32_t* pos, int32_t* ref, int32_t* alt, uint8_t* cls, int32_t* truth_row /*[n] each, or NULL*/);
+int qm_batch_normalize_timings(qm_batch* b, float* ms3);
+int qm_truth_normalized(qm_ctx* ctx, int truth_id, int genome_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out);
+int qm_truth_entries(qm_ctx* ctx, int truth_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -873,6 +921,23 @@ typedef struct qm_context_args {
 int qm_extract_files_context(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                              qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                              void* global_dev, const qm_context_args* context);
+
+/* qm_extract_files_ex plus the normalisation pass over its batch; mode must be QM_BATCH_ALLELES (QM_E_STATE
+ * otherwise).  Mixed-sample jobs with genome_id[j] >= 0 (a qm_genome_load id: the genome the VCF was called against) get their
+ * rows rec[j][QM_NORM_R_COLS] and tru[j][QM_NORM_T_COLS] of qm_batch_get_normalize; the others (-1, pure-strain samples) get zero
+ * rows.  rescued_out (may be NULL, entries may be NULL): per job a file `#line POS REF ALT NORM_POS NORM_REF NORM_ALT TRUTH_POS
+ * TRUTH_REF TRUTH_ALT`, one row per rescued line in file order -- the 1-based line number, the line's own text of the three
+ * columns, its normal form, and the truth entry of the smallest index with that form --, written atomically (temp file + rename).
+ * The VCF outputs, stats and roc are those of qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_normalize_args {
+  const int32_t* genome_id;         /* [n_jobs], -1 = the job takes no part */
+  uint64_t* rec;                    /* [n_jobs][QM_NORM_R_COLS] */
+  uint64_t* tru;                    /* [n_jobs][QM_NORM_T_COLS] */
+  const char* const* rescued_out;   /* [n_jobs] or NULL */
+} qm_normalize_args;
+int qm_extract_files_normalize(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                               qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                               void* global_dev, const qm_normalize_args* normalize);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

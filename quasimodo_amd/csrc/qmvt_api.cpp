@@ -31,6 +31,7 @@
 #include "qmvt_boot.h"
 #include "qmvt_nearmiss.h"
 #include "qmvt_surface.h"
+#include "qmvt_norm.h"
 
 using namespace qm;
 
@@ -856,6 +857,19 @@ struct qm_batch {
   bool cx_built = false;              // ... and built a table (else its build time is 0)
   int32_t cx_ng = 0;                  // GC bins of the latest qm_batch_context
   unsigned cx_made = 0;               // QM_CX_* halves the latest qm_batch_context made behind the latest run
+  // qm_batch_normalize (lazy): the tables of the (truth set, genome) pairs the VCFs name in one pool, the per-VCF
+  // descriptors and bitmaps, [n_vcf][QM_NORM_R_COLS] / [n_vcf][QM_NORM_T_COLS] counts, a class byte per record and, on request,
+  // the normalised columns with the truth row of every record's form; ev_norm says when the pass is done
+  DevBuf<uint32_t> nz_pool, nz_bits;
+  DevBuf<NormVcf> nz_vcfs;
+  DevBuf<uint64_t> nz_rec, nz_tru;
+  DevBuf<uint8_t> nz_cls;
+  DevBuf<int32_t> nz_cols;            // [4][n_pad]: pos, ref, alt, row
+  hipEvent_t ev_norm = nullptr;
+  hipEvent_t ev_nzt[4] = {};          // qm_batch_set_timing: around the table builds, k_norm_records, k_norm_found
+  bool nz_timed = false;              // the latest qm_batch_normalize recorded them
+  unsigned nz_made = 0;               // 1 | QM_NORM_COLUMNS: what the latest qm_batch_normalize made behind the latest run
+  std::vector<uint8_t> nz_has;        // [n_vcf] the VCF named a genome
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -888,6 +902,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_sft) if (e) (void)hipEventDestroy(e);
   if (b->ev_cx) (void)hipEventDestroy(b->ev_cx);
   for (auto& e : b->ev_cxt) if (e) (void)hipEventDestroy(e);
+  if (b->ev_norm) (void)hipEventDestroy(b->ev_norm);
+  for (auto& e : b->ev_nzt) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -1221,6 +1237,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->nm_valid = false;
   b->sf_valid = false;
   b->cx_made = 0;
+  b->nz_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -2658,6 +2675,222 @@ extern "C" int qm_batch_context_timings(qm_batch* b, float* ms3) {
   HIPCHK(hipEventSynchronize(b->ev_cxt[3]));
   for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_cxt[i], b->ev_cxt[i + 1]));
   if (!b->cx_built) ms3[0] = 0.0f;   // every table was cached
+  return QM_OK;
+}
+// ---- indels and MNPs matched by normal form ----
+// The pool words of one table: [claim | spos | sref | salt | sresp][slots], [fpos | fref | falt][xn], stats[2] (8-byte aligned)
+static size_t norm_pool_words(int64_t xn, uint32_t slots) {
+  return 5 * (size_t)slots + ((3 * (size_t)xn + 1) & ~(size_t)1) + 4;
+}
+static NormTable norm_table(const Truth& t, const Genome& g, uint32_t* pool, uint32_t slots) {
+  NormTable T;
+  memset(&T, 0, sizeof T);
+  T.words = g.d_words; T.len = g.len;
+  T.xkeys = t.d_xkeys; T.xref = t.d_xref; T.xalt = t.d_xalt; T.xn = t.xn;
+  T.slots = slots;
+  T.claim = pool;
+  T.spos = reinterpret_cast<int32_t*>(pool + (size_t)slots);
+  T.sref = reinterpret_cast<int32_t*>(pool + 2 * (size_t)slots);
+  T.salt = reinterpret_cast<int32_t*>(pool + 3 * (size_t)slots);
+  T.sresp = pool + 4 * (size_t)slots;
+  uint32_t* e = pool + 5 * (size_t)slots;
+  T.fpos = reinterpret_cast<int32_t*>(e);
+  T.fref = reinterpret_cast<int32_t*>(e + (size_t)t.xn);
+  T.falt = reinterpret_cast<int32_t*>(e + 2 * (size_t)t.xn);
+  T.stats = reinterpret_cast<unsigned long long*>(e + ((3 * (size_t)t.xn + 1) & ~(size_t)1));
+  return T;
+}
+// Builds the table on `st` (the pool words start at a multiple of 8 bytes).
+static int norm_build(const NormTable& T, hipStream_t st) {
+  HIPCHK(hipMemsetAsync(T.claim, 0, (size_t)T.slots * 4, st));
+  HIPCHK(hipMemsetAsync(T.sresp, 0, (size_t)T.slots * 4, st));
+  HIPCHK(hipMemsetAsync(T.stats, 0, 16, st));
+  launch_norm_truth(T, st);
+  HIPCHK(hipGetLastError());
+  return QM_OK;
+}
+extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_normalize");
+  if (!genome_id_per_vcf) return fail(QM_E_INVAL, "qm_batch_normalize: NULL genome ids");
+  if (what & ~QM_NORM_COLUMNS) return fail(QM_E_INVAL, "qm_batch_normalize: what = %u", what);
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_normalize: a single-base batch holds no indels or MNPs to normalise (create the batch with QM_BATCH_ALLELES)");
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = genome_id_per_vcf[v];
+    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_normalize: VCF %zu names genome %d (have %zu)", v, gid, c->genomes.size());
+    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_normalize: VCF %zu names released genome %d", v, gid);
+  }
+  int rc = truths_live(b, "qm_batch_normalize");
+  if (rc != QM_OK) return rc;
+  // one table per truth set: the VCFs that share one must name one genome
+  struct Pair { int truth, genome; size_t first_vcf, off; uint32_t slots; };
+  std::vector<Pair> pairs;
+  std::vector<int> pair_of(nv, -1);
+  size_t pool_words = 0, bit_words = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = genome_id_per_vcf[v], tid = b->L.vcfs[v].truth;
+    if (gid < 0) continue;
+    size_t k = 0;
+    while (k < pairs.size() && pairs[k].truth != tid) ++k;
+    if (k == pairs.size()) {
+      const uint32_t slots = norm_slots(c->truths[(size_t)tid].xn);
+      pairs.push_back(Pair{tid, gid, v, pool_words, slots});
+      pool_words += norm_pool_words(c->truths[(size_t)tid].xn, slots);
+    } else if (pairs[k].genome != gid) {
+      return fail(QM_E_INVAL, "qm_batch_normalize: VCF %zu and VCF %zu share truth set %d and name genomes %d and %d (a normalised truth set belongs to one genome)",
+                  pairs[k].first_vcf, v, tid, pairs[k].genome, gid);
+    }
+    pair_of[v] = (int)k;
+    bit_words += 2 * (size_t)(pairs[k].slots / 32u);
+  }
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_norm, &st);
+  if (rc != QM_OK) return rc;
+  b->nz_made = 0;   // from here on the outputs are rewritten
+  const size_t np = (size_t)b->L.n_pad;
+  rc = b->nz_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nz_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nz_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nz_rec.grow((int64_t)std::max<size_t>(nv * NORM_R_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nz_tru.grow((int64_t)std::max<size_t>(nv * NORM_T_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->nz_cls.grow((int64_t)np, &b->dev_bytes);
+  if (rc == QM_OK && (what & QM_NORM_COLUMNS)) rc = b->nz_cols.grow((int64_t)(4 * np), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_nzt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->nz_timed = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_nzt[0], st));
+  std::vector<NormTable> tabs(pairs.size());
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    tabs[k] = norm_table(c->truths[(size_t)pairs[k].truth], c->genomes[(size_t)pairs[k].genome], b->nz_pool + pairs[k].off, pairs[k].slots);
+    rc = norm_build(tabs[k], st);
+    if (rc != QM_OK) return rc;
+  }
+  std::vector<NormVcf> vcfs(std::max<size_t>(nv, 1));
+  memset(vcfs.data(), 0, vcfs.size() * sizeof(NormVcf));
+  b->nz_has.assign(nv, 0);
+  size_t bo = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    if (pair_of[v] < 0) continue;
+    const size_t w = tabs[(size_t)pair_of[v]].slots / 32u;
+    vcfs[v].t = tabs[(size_t)pair_of[v]];
+    vcfs[v].found = b->nz_bits + bo;
+    vcfs[v].found_eq = b->nz_bits + bo + w;
+    bo += 2 * w;
+    b->nz_has[v] = 1;
+  }
+  if (nv) HIPCHK(hipMemcpy(b->nz_vcfs, vcfs.data(), nv * sizeof(NormVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
+  HIPCHK(hipMemsetAsync(b->nz_bits, 0, std::max<size_t>(bit_words, 1) * 4, st));
+  HIPCHK(hipMemsetAsync(b->nz_rec, 0, std::max<size_t>(nv * NORM_R_COLS, 1) * 8, st));
+  HIPCHK(hipMemsetAsync(b->nz_tru, 0, std::max<size_t>(nv * NORM_T_COLS, 1) * 8, st));
+  HIPCHK(hipMemsetAsync(b->nz_cls, 0, np, st));
+  if (T) HIPCHK(hipEventRecord(b->ev_nzt[1], st));
+  NormRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.vcfs = b->nz_vcfs;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  P.cls = b->nz_cls;
+  if (what & QM_NORM_COLUMNS) { P.npos = b->nz_cols; P.nref = b->nz_cols + np; P.nalt = b->nz_cols + 2 * np; P.nrow = b->nz_cols + 3 * np; }
+  P.rec = b->nz_rec;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_norm_records(P, st);
+  HIPCHK(hipGetLastError());
+  if (T) HIPCHK(hipEventRecord(b->ev_nzt[2], st));
+  launch_norm_found(b->nz_vcfs, (int)nv, b->nz_tru, st);
+  HIPCHK(hipGetLastError());
+  if (T) { HIPCHK(hipEventRecord(b->ev_nzt[3], st)); b->nz_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_norm, st));
+  b->nz_made = 1u | what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_normalize(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_normalize: NULL batch");
+  if (!b->nz_made) return fail(QM_E_STATE, "qm_batch_get_normalize: no qm_batch_normalize behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_norm));
+  const size_t nv = (size_t)b->n_vcf;
+  if (rec && nv) HIPCHK(hipMemcpy(rec, b->nz_rec, nv * NORM_R_COLS * 8, hipMemcpyDeviceToHost));
+  if (tru && nv) HIPCHK(hipMemcpy(tru, b->nz_tru, nv * NORM_T_COLS * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_normalized(qm_batch* b, int v, int32_t* pos, int32_t* ref, int32_t* alt, uint8_t* cls, int32_t* truth_row) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_normalized: NULL batch");
+  if (!b->nz_made) return fail(QM_E_STATE, "qm_batch_get_normalized: no qm_batch_normalize behind the latest run");
+  if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_normalized: VCF %d (the batch has %d)", v, b->n_vcf);
+  if (!b->nz_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_normalized: VCF %d named no genome in the latest qm_batch_normalize", v);
+  if ((pos || ref || alt || truth_row) && !(b->nz_made & QM_NORM_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_get_normalized: the latest qm_batch_normalize did not keep the columns (QM_NORM_COLUMNS)");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_norm));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  if (d.n == 0) return QM_OK;
+  const size_t np = (size_t)b->L.n_pad, n = (size_t)d.n;
+  if (cls) HIPCHK(hipMemcpy(cls, b->nz_cls + d.off, n, hipMemcpyDeviceToHost));
+  int32_t* const outs[4] = {pos, ref, alt, truth_row};
+  for (size_t k = 0; k < 4; ++k)
+    if (outs[k]) HIPCHK(hipMemcpy(outs[k], b->nz_cols + k * np + d.off, n * 4, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_normalize_timings(qm_batch* b, float* ms3) {
+  if (!b || !ms3) return fail(QM_E_INVAL, "qm_batch_normalize_timings: NULL");
+  if (!b->nz_made) return fail(QM_E_STATE, "qm_batch_normalize_timings: no qm_batch_normalize behind the latest run");
+  if (!b->nz_timed) return fail(QM_E_STATE, "qm_batch_normalize_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_nzt[3]));
+  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_nzt[i], b->ev_nzt[i + 1]));
+  return QM_OK;
+}
+extern "C" int qm_truth_entries(qm_ctx* c, int truth_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out) {
+  if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_entries: bad arguments");
+  if (truth_id < 0 || truth_id >= (int)c->truths.size() || c->truths[(size_t)truth_id].released)
+    return fail(QM_E_INVAL, "qm_truth_entries: no live truth set %d", truth_id);
+  HIPCHK(hipSetDevice(c->dev));
+  const Truth& t = c->truths[(size_t)truth_id];
+  *n_out = t.xn;
+  if (t.xn > capacity) return fail(QM_E_RANGE, "qm_truth_entries: %lld entries, room for %lld", (long long)t.xn, (long long)capacity);
+  const size_t n = (size_t)t.xn;
+  if (!n) return QM_OK;
+  if (pos) {
+    HIPCHK(hipMemcpy(pos, t.d_xkeys, n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) pos[i] = (int32_t)((uint32_t)pos[i] >> 4);
+  }
+  if (ref) HIPCHK(hipMemcpy(ref, t.d_xref, n * 4, hipMemcpyDeviceToHost));
+  if (alt) HIPCHK(hipMemcpy(alt, t.d_xalt, n * 4, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_truth_normalized(qm_ctx* c, int truth_id, int genome_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out) {
+  if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_normalized: bad arguments");
+  if (truth_id < 0 || truth_id >= (int)c->truths.size() || c->truths[(size_t)truth_id].released)
+    return fail(QM_E_INVAL, "qm_truth_normalized: no live truth set %d", truth_id);
+  if (genome_id < 0 || genome_id >= (int)c->genomes.size() || c->genomes[(size_t)genome_id].released)
+    return fail(QM_E_INVAL, "qm_truth_normalized: no live genome %d", genome_id);
+  HIPCHK(hipSetDevice(c->dev));
+  const Truth& t = c->truths[(size_t)truth_id];
+  const uint32_t slots = norm_slots(t.xn);
+  uint32_t* pool = nullptr;
+  DALLOC(pool, norm_pool_words(t.xn, slots));
+  const NormTable T = norm_table(t, c->genomes[(size_t)genome_id], pool, slots);
+  std::vector<uint32_t> h(4 * (size_t)slots);
+  int rc = norm_build(T, c->stream);
+  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
+  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(h.data(), pool, h.size() * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(pool);
+  if (rc != QM_OK) return rc;
+  if (e != hipSuccess) return fail(QM_E_HIP, "qm_truth_normalized: %s", hipGetErrorString(e));
+  struct F { int32_t p, r, a; };
+  std::vector<F> forms;
+  for (size_t s = 0; s < slots; ++s)
+    if (h[s]) forms.push_back(F{(int32_t)h[slots + s], (int32_t)h[2 * (size_t)slots + s], (int32_t)h[3 * (size_t)slots + s]});
+  std::sort(forms.begin(), forms.end(), [](const F& x, const F& y) { return x.p != y.p ? x.p < y.p : x.r != y.r ? x.r < y.r : x.a < y.a; });
+  *n_out = (int64_t)forms.size();
+  if ((int64_t)forms.size() > capacity) return fail(QM_E_RANGE, "qm_truth_normalized: %zu forms, room for %lld", forms.size(), (long long)capacity);
+  for (size_t i = 0; i < forms.size(); ++i) {
+    if (pos) pos[i] = forms[i].p;
+    if (ref) ref[i] = forms[i].r;
+    if (alt) alt[i] = forms[i].a;
+  }
   return QM_OK;
 }
 // paired block-bootstrap replicates of the finished batch's counts

@@ -298,7 +298,7 @@ struct Passes {
   uint64_t* motifs_out = nullptr;
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
-  const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr;
+  const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -651,6 +651,96 @@ int nearmiss_pass(const PassCtx& c, const qm_nearmiss_args* nm, std::string& err
   return QM_OK;
 }
 
+// ---- indels and MNPs matched by normal form ----
+// the spelling of an inline allele code (include/qmvt.h), `.` for any other code
+std::string nz_spell(int32_t c) {
+  const uint32_t u = (uint32_t)c;
+  if (!(u < 4u || (u >= (2u << 26) && u < (14u << 26)))) return ".";
+  const uint32_t n = u < 4u ? 1u : u >> 26;
+  std::string out;
+  for (uint32_t k = 0; k < n; ++k) out.push_back("ACGT"[(u >> (2 * k)) & 3u]);
+  return out;
+}
+struct NzColumns { std::vector<int32_t> pos, ref, alt, row; std::vector<uint8_t> cls; };
+struct NzEntries { std::vector<int32_t> pos, ref, alt; };
+// `#line POS REF ALT NORM_POS NORM_REF NORM_ALT TRUTH_POS TRUTH_REF TRUTH_ALT`, then one row per rescued line of the job in file
+// order: the 1-based line number, the line's own text of the three columns, the record's normal form, the truth entry of the
+// smallest index with that form
+int write_rescued_file(const char* path, const JobState& s, const NzColumns& c, const NzEntries& t) {
+  std::string out = "#line\tPOS\tREF\tALT\tNORM_POS\tNORM_REF\tNORM_ALT\tTRUTH_POS\tTRUTH_REF\tTRUTH_ALT\n";
+  const uint8_t* text = s.vcf.p;
+  const size_t len = s.vcf.n;
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    const int64_t r = rec++;
+    if (c.cls[(size_t)r] != QM_NORM_C_RESCUED) continue;
+    size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], len);
+    if (e > b && text[e - 1] == '\n') --e;
+    const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+    const uint8_t* q = text + b;
+    while (nf < 6) {
+      const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(text + e - q));
+      f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(text + e - q); ++nf;
+      if (!tb) break;
+      q = tb + 1;
+    }
+    out.append(std::to_string(i + 1));
+    for (int k : {1, 3, 4}) { out.push_back('\t'); if (k < nf) out.append((const char*)f[k], fl[k]); }
+    out += "\t" + std::to_string(c.pos[(size_t)r]) + "\t" + nz_spell(c.ref[(size_t)r]) + "\t" + nz_spell(c.alt[(size_t)r]);
+    const int64_t k = c.row[(size_t)r];
+    if (k >= 0 && (size_t)k < t.pos.size()) out += "\t" + std::to_string(t.pos[(size_t)k]) + "\t" + nz_spell(t.ref[(size_t)k]) + "\t" + nz_spell(t.alt[(size_t)k]);
+    else out += "\t.\t.\t.";   // (a line the text side made a TP line: no truth entry carries its form)
+    out.push_back('\n');
+  }
+  return write_all_atomic(path, out);
+}
+
+// the counts of every wanted job, and the rescued-lines files of the jobs that name one
+int normalize_pass(const PassCtx& c, const Passes& P, std::string& err) {
+  const qm_normalize_args* na = P.nz;
+  auto want = [&](int j) { return !c.jobs[j].pure && na->genome_id[j] >= 0; };
+  if (!na || !c.any(want)) return QM_OK;
+  auto path = [&](int j) { return want(j) && na->rescued_out ? na->rescued_out[j] : nullptr; };
+  std::vector<int32_t> gid(c.nv, -1);
+  bool files = false;
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) { gid[(size_t)c.J[(size_t)j].batch_v] = na->genome_id[j]; files = files || path(j); }
+  std::vector<uint64_t> rec(c.nv * QM_NORM_R_COLS), tru(c.nv * QM_NORM_T_COLS);
+  int rc = qm_batch_normalize(c.batch, gid.data(), files ? QM_NORM_COLUMNS : 0u, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_normalize(c.batch, rec.data(), tru.data());
+  if (rc == QM_OK) { c.scatter_rows(na->rec, rec, QM_NORM_R_COLS, want); c.scatter_rows(na->tru, tru, QM_NORM_T_COLS, want); }
+  struct Task { int j; NzColumns cols; };
+  std::vector<Task> W;
+  std::vector<NzEntries> ent(c.T.size());
+  std::vector<uint8_t> have(c.T.size(), 0);
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    if (!path(j)) continue;
+    const JobState& s = c.J[(size_t)j];
+    const size_t n = (size_t)s.n_data + 1;
+    W.push_back({j, NzColumns{std::vector<int32_t>(n), std::vector<int32_t>(n), std::vector<int32_t>(n), std::vector<int32_t>(n, -1), std::vector<uint8_t>(n, 0)}});
+    NzColumns& k = W.back().cols;
+    rc = qm_batch_get_normalized(c.batch, s.batch_v, k.pos.data(), k.ref.data(), k.alt.data(), k.cls.data(), k.row.data());
+    if (rc == QM_OK && !have[(size_t)s.truth]) {
+      NzEntries& e = ent[(size_t)s.truth];
+      int64_t tn = 0;
+      (void)qm_truth_entries(c.ctx, c.truth_of(j).tid, nullptr, nullptr, nullptr, 0, &tn);   // (how many)
+      e.pos.resize((size_t)tn + 1); e.ref.resize((size_t)tn + 1); e.alt.resize((size_t)tn + 1);
+      rc = qm_truth_entries(c.ctx, c.truth_of(j).tid, e.pos.data(), e.ref.data(), e.alt.data(), tn, &tn);
+      e.pos.resize((size_t)tn); e.ref.resize((size_t)tn); e.alt.resize((size_t)tn);
+      have[(size_t)s.truth] = 1;
+    }
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  std::vector<int> wrc(W.size(), QM_OK);
+  parallel_for((int)W.size(), c.nthr, [&](int k) {
+    const Task& w = W[(size_t)k];
+    wrc[(size_t)k] = write_rescued_file(na->rescued_out[w.j], c.J[(size_t)w.j], w.cols, ent[(size_t)c.J[(size_t)w.j].truth]);
+  });
+  for (size_t k = 0; k < W.size(); ++k)
+    if (wrc[k] != QM_OK) { err = std::string("cannot write ") + na->rescued_out[W[k].j]; return wrc[k]; }
+  return QM_OK;
+}
+
 // the filter surface: S and extra of every wanted job
 int surface_pass(const PassCtx& c, const qm_surface_args* sf, std::string& err) {
   auto want = [&](int j) { return sf->want[j] != 0; };
@@ -773,6 +863,22 @@ extern "C" int qm_extract_files_context(qm_ctx* ctx, int n_jobs, const qm_file_j
     memset(cx->gen, 0, sizeof(uint64_t) * nc * (size_t)n_jobs);
   }
   Passes P; P.cx = cx;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// indels and MNPs matched by normal form behind the worker
+extern "C" int qm_extract_files_normalize(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                          qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                          int n_slots, void* global_dev, const qm_normalize_args* normalize) {
+  const qm_normalize_args* na = normalize;
+  if (!na || (n_jobs > 0 && (!na->genome_id || !na->rec || !na->tru))) return fail(QM_E_INVAL, "qm_extract_files_normalize: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_normalize: the normal form is taken of indels and MNPs, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (n_jobs > 0) {
+    memset(na->rec, 0, sizeof(uint64_t) * QM_NORM_R_COLS * (size_t)n_jobs);
+    memset(na->tru, 0, sizeof(uint64_t) * QM_NORM_T_COLS * (size_t)n_jobs);
+  }
+  Passes P; P.nz = na;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -1131,6 +1237,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = votes_pass(pc, P.va, err);
       if (rc == QM_OK) rc = nearmiss_pass(pc, P.nm, err);
       if (rc == QM_OK) rc = context_pass(pc, P, err);
+      if (rc == QM_OK) rc = normalize_pass(pc, P, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

@@ -115,6 +115,23 @@ class Engine:
         check(self._L.qm_genome_context(self._h, int(gid), w, ng, _p(cells), _p(gen)), self._h)
         return cells, gen
 
+    def truth_entries(self, tid):
+        """qm_truth_entries: (pos, ref, alt) int32 -- the allele-extended entries of a truth set in the order of its table"""
+        cap = max(self.truth_size(tid, alleles=True), 1)
+        pos, ref, alt = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int64()
+        check(self._L.qm_truth_entries(self._h, int(tid), _p(pos), _p(ref), _p(alt), cap, C.byref(n)), self._h)
+        return pos[:n.value], ref[:n.value], alt[:n.value]
+
+    def truth_normalized(self, tid, gid):
+        """qm_truth_normalized: (pos, ref, alt) int32 -- the distinct forms (normalize.py) of a truth set's
+        allele-extended entries against a loaded genome, sorted by (pos, ref, alt), from the kernels the pass uses"""
+        cap = max(self.truth_size(tid, alleles=True), 1)
+        pos, ref, alt = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int64()
+        check(self._L.qm_truth_normalized(self._h, int(tid), int(gid), _p(pos), _p(ref), _p(alt), cap, C.byref(n)), self._h)
+        return pos[:n.value], ref[:n.value], alt[:n.value]
+
     # -- strata sets (counts per genome region, DESIGN.md 4.10) -------------------
     def strata_load(self, strata):
         """strata: list of (name, starts, ends) BED intervals (quasimodo_amd.strata); returns the set's id"""
@@ -207,7 +224,7 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None):
+                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -241,17 +258,21 @@ class Engine:
         (DESIGN.md 4.16): the rows of jobs with a genome gain `context_rec` ([16 n_gc + 2][3] uint64: kept, TP, FP lines per cell,
         none, nokey), `context_tru` ([16 n_gc + 1][2]: truth keys, hit ones; None in the allele-extended mode), `context_gen`
         ([16 n_gc + 1]: positions of the genome per cell) and `context_params` (half_window, n_gc).
+        normalize: {"genomes": [genome_load id or None / -1 per job], "rescued": [path or None per job]} --
+        qm_extract_files_normalize (alleles=True only): the rows of mixed-sample jobs with a genome gain `norm_rec`
+        ([12] uint64, columns normalize.R_COLS) and `norm_tru` ([5], normalize.T_COLS); the rescued-lines files are written.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_shared_call
+        from .passes import check_normalize, check_shared_call
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
+        check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -344,6 +365,20 @@ class Engine:
         unpack = lambda k: {"context_rec": crec[k].copy(), "context_tru": None if alleles else ctru[k].copy(), "context_gen": cgen[k].copy(),
                             "context_params": (w, ng)} if cgid[k] >= 0 else {}
         return self._L.qm_extract_files_context, (C.byref(ca),), unpack
+
+    def _files_normalize(self, n, normalize, file_jobs=(), **kw):
+        ngid = _c([-1 if g is None else int(g) for g in normalize["genomes"]] or [-1], np.int32)
+        paths = list(normalize.get("rescued") or [None] * n)
+        if (n and ngid.shape[0] != n) or len(paths) != n:
+            raise ValueError("normalize: %d genomes / %d rescued entries for %d jobs" % (len(normalize["genomes"]), len(paths), n))
+        nrec = np.zeros((max(n, 1), _lib.QM_NORM_R_COLS), np.uint64)
+        ntru = np.zeros((max(n, 1), _lib.QM_NORM_T_COLS), np.uint64)
+        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        na = _lib.NormalizeArgs(_p(ngid), _p(nrec), _p(ntru), out_arr)
+        na.keep = (ngid, out_arr)   # (read during the call; the other arrays live in unpack)
+        took = lambda k: ngid[k] >= 0 and not file_jobs[k].get("pure")
+        unpack = lambda k: {"norm_rec": nrec[k].copy(), "norm_tru": ntru[k].copy()} if took(k) else {}
+        return self._L.qm_extract_files_normalize, (C.byref(na),), unpack
 
     def _files_boot(self, n, boot, **kw):
         bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
@@ -750,6 +785,44 @@ class Batch:
         ms = (C.c_float * 3)()
         self._ck(self._L.qm_batch_context_timings(self._h, ms))
         return {"context_build_ms": ms[0], "context_records_ms": ms[1], "context_truth_ms": ms[2]}
+
+    # -- indels and MNPs matched by normal form ------------------------
+    def normalize(self, genome_ids, columns=False, stream=None, fetch=True):
+        """qm_batch_normalize + qm_batch_get_normalize (allele-extended batches): (rec [n_vcf][12], tru [n_vcf][5]) uint64, columns
+        normalize.R_COLS / normalize.T_COLS (genome_ids: one genome id or -1 per VCF); columns=True keeps every record's form for
+        normalized().  fetch=False: enqueue only (normalize_counts() waits and copies)"""
+        g = _c(genome_ids, np.int32)
+        if g.shape[0] != self.n_vcf:
+            raise ValueError("genome_ids: %d entries for %d VCFs" % (g.shape[0], self.n_vcf))
+        self._ck(self._L.qm_batch_normalize(self._h, _p(g) if self.n_vcf else _p(np.zeros(1, np.int32)),
+                                            _lib.QM_NORM_COLUMNS if columns else 0, C.c_void_p(stream) if stream else None))
+        return self.normalize_counts() if fetch else None
+
+    def normalize_counts(self):
+        """qm_batch_get_normalize: the counts of the latest normalize()"""
+        rec = np.zeros((max(self.n_vcf, 1), _lib.QM_NORM_R_COLS), np.uint64)
+        tru = np.zeros((max(self.n_vcf, 1), _lib.QM_NORM_T_COLS), np.uint64)
+        self._ck(self._L.qm_batch_get_normalize(self._h, _p(rec), _p(tru)))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def normalized(self, v, columns=True):
+        """qm_batch_get_normalized: (pos, ref, alt int32 [n] -- every record's form as allele codes --, cls uint8 [n] -- the class
+        bytes normalize.CLASS_NAMES --, truth_row int32 [n] -- the smallest truth entry index with that form, -1 for none) of VCF
+        v in input order; columns=False: (cls,) alone, for a normalize() that kept no columns"""
+        n = int(self.n_records[int(v)])
+        cls = np.zeros(max(n, 1), np.uint8)
+        if not columns:
+            self._ck(self._L.qm_batch_get_normalized(self._h, int(v), None, None, None, _p(cls), None))
+            return (cls[:n],)
+        cols = [np.zeros(max(n, 1), np.int32) for _ in range(4)]
+        self._ck(self._L.qm_batch_get_normalized(self._h, int(v), _p(cols[0]), _p(cols[1]), _p(cols[2]), _p(cls), _p(cols[3])))
+        return cols[0][:n], cols[1][:n], cols[2][:n], cls[:n], cols[3][:n]
+
+    def normalize_timings(self):
+        """qm_batch_normalize_timings (set_timing on): milliseconds of the latest normalize() between HIP events"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.qm_batch_normalize_timings(self._h, ms))
+        return {"norm_truth_ms": ms[0], "norm_records_ms": ms[1], "norm_found_ms": ms[2]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
-from .passes import PASSES, check_shared_call, requested_by
+from .passes import PASSES, check_normalize, check_shared_call, requested_by
 from .vcfio import scan_vcf
 
 
@@ -65,6 +65,9 @@ class Job:
     # sequence-context profiles
     context: tuple = None     # (half_window, n_gc): stats gain context_rec / context_tru / context_gen (the same for every profiled job of a call)
     context_genome: str = None   # FASTA of the genome the VCF was called against: its positions are what the cells are made of
+    # indels and MNPs matched by normal form; mixed samples, allele-extended mode only
+    normalize: str = None     # FASTA of the genome the VCF was called against: stats gain norm_rec / norm_tru
+    rescued_out: str = None   # where the job's rescued-lines table goes (extract_many(normalize=) derives it)
 
 
 def _paths(job):
@@ -135,7 +138,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None):
+                 surface=None, context=None, normalize=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -179,12 +182,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     homopolymer x GC cell, then none, nokey), stats["context_tru"] ([16 n_gc + 1][2]: truth keys and hit ones; None in the
     allele-extended mode; zero for pure-strain samples), stats["context_gen"] ([16 n_gc + 1]: the genome's positions per cell) and
     stats["context_params"].  Every distinct FASTA is loaded once and released before this returns.
+    normalize: {"genomes": [FASTA path or None per job]} or that list itself (quasimodo_amd.normalize; default: the
+    jobs' Job.normalize / Job.rescued_out; alleles=True only, ValueError otherwise): every mixed-sample job with a genome gets
+    stats["norm_rec"] ([12]: kept, TP, TP_N, rescued, respelled, single-base lines and the lines per reason a record has no normal
+    form) and stats["norm_tru"] ([5]: truth entries, distinct forms, forms found, found by form only, entries without a normal
+    form), and norm/<x>.rescued.tsv beside fp/ and tp/.  VCFs of one truth file name one genome.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
-             "surface": surface is not None and surface is not False, "context": context is not None}
+             "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -223,6 +231,16 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             raise ValueError("context: %d genomes entries for %d jobs" % (len(cgen), len(jobs)))
         for j, g in zip(jobs, cgen):
             j.context, j.context_genome = (cpar, g) if g else (None, None)
+    if normalize is not None:
+        from .normalize import rescued_path
+        ngen = list(normalize["genomes"] if isinstance(normalize, dict) else normalize)
+        if len(ngen) != len(jobs):
+            raise ValueError("normalize: %d genomes entries for %d jobs" % (len(ngen), len(jobs)))
+        for j, g in zip(jobs, ngen):
+            j.normalize = g if g and not is_pure_strain(j.vcf_file) else None
+            if j.normalize:
+                _paths(j)
+                j.rescued_out = j.rescued_out or rescued_path(j)
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -258,6 +276,12 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             raise ValueError(p.agree)
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
+    check_normalize(requested_by(jobs), alleles)
+    by_truth = {}
+    for j in jobs:
+        if j.normalize and by_truth.setdefault(os.path.realpath(j.snp_file), (j.normalize, j.vcf_file))[0] != j.normalize:
+            raise ValueError("normalize: %s and %s share the truth file %s and name the genomes %s and %s (a normalised truth set belongs to one genome)"
+                             % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.normalize))
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -283,7 +307,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = sf = cxs = None
+    ts = vt = nm = sf = cxs = nzs = None
     if any(j.context is not None for j in jobs):
         from .context import check_params
         for j in jobs:
@@ -346,6 +370,15 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                     if j.context is not None and j.context_genome not in loaded:
                         loaded[j.context_genome] = engine.genome_load(read_fasta(j.context_genome))
                 cxs["genomes"] = [loaded[j.context_genome] if j.context is not None else -1 for j in jobs]
+            if any(j.normalize for j in jobs):
+                from .motifs import read_fasta
+                for j in jobs:
+                    if j.normalize and j.normalize not in loaded:
+                        loaded[j.normalize] = engine.genome_load(read_fasta(j.normalize))
+                nzs = {"genomes": [loaded[j.normalize] if j.normalize else -1 for j in jobs],
+                       "rescued": [j.rescued_out if j.normalize else None for j in jobs]}
+                for path in [x for x in nzs["rescued"] if x]:
+                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             # the passes with parameters: the tuple the jobs agreed on, and who wants the pass
             par = {f: next((getattr(j, f) for j in jobs if getattr(j, f)), None) for f in ("profile", "strata", "boot")}
             want = lambda f: [1 if getattr(j, f) else 0 for j in jobs]
@@ -361,7 +394,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

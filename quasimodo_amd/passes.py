@@ -16,6 +16,7 @@ PASSES = (
          "boot: the resampled jobs of one call share one window, window count, replicate count and seed", ()),
     Pass("votes", ("vote_group",), ("votes",), "--votes", None, ()),
     Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
+    Pass("normalize", ("normalize",), ("normalize",), "--normalize", None, ()),
     Pass("context", ("context",), ("context",), "--seq-context",
          "context: the profiled jobs of one call share one half window and one GC bin count", ()),
     Pass("surface", ("surface",), ("surface",), "--filter-surface",
@@ -43,6 +44,12 @@ def check_shared_call(requested):
         for b in want[:i]:
             if b.name not in a.shares:
                 raise SharedCallError(a, b)
+
+
+def check_normalize(requested, alleles):
+    """--normalize reads indels and MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
+    if "normalize" in requested and not alleles:
+        raise ValueError("normalize (--normalize) needs the allele-extended mode (--alleles): a single-base batch holds no indels or MNPs")
 
 
 def requested_by(jobs):

@@ -165,7 +165,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
-                         context_gc_bins=None):
+                         context_gc_bins=None, alleles=False, normalize=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -201,12 +201,19 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     seq_context: {"TM": FASTA, "TA": FASTA}, the genomes as for mutation_context, with context_window / context_gc_bins (default
     50, 10; quasimodo_amd.context): the counts per homopolymer x GC cell are taken behind the classification and
     final_tables/caller_performance_context.tsv is written (per caller x sample the cells in use, the marginals, none, nokey).
+    alleles: the allele-extended mode (include/qmvt.h): indels and MNPs take part, matched by spelling.
+    normalize: {"TM": FASTA, "TA": FASTA}, the genomes as for seq_context (quasimodo_amd.normalize; needs alleles,
+    WorkflowError before a file is touched otherwise): indels and MNPs are also matched by normal form behind the classification;
+    final_tables/caller_performance_normalized.tsv (TP, FP, FN, Precision, Recall, F1 by spelling and by normal form side by side,
+    the rescued, respelled and reason counts) and callers/{caller}/norm/{sample}.{ref}.{caller}.rescued.tsv for every mixed sample.
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
-                 context=seq_context is not None)
+                 context=seq_context is not None, normalize=normalize is not None)
+    if normalize is not None and not alleles:
+        raise WorkflowError("--normalize needs --alleles: the normal form is taken of indels and MNPs, which only the allele-extended mode reads")
     radius = _explain_radius(explain_errors, explain_radius)
     sweep = _surface_params(filter_surface, surface_qual_step, surface_qual_bins, surface_af_bins)
     cpar = _context_params(seq_context is not None, context_window, context_gc_bins)
@@ -252,9 +259,16 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             fa = seq_context.get(mix)
             if not fa or not os.path.isfile(fa):
                 raise WorkflowError("sequence context: no genome FASTA for %s (%s)" % (mix, fa))
+    if normalize is not None:
+        for mix in mixes:
+            fa = normalize.get(mix)
+            if not fa or not os.path.isfile(fa):
+                raise WorkflowError("normalize: no genome FASTA for %s (%s)" % (mix, fa))
     if dryrun:
         for s, c, src in plan:
             print("extractTP\t%s\t%s" % (c, src))
+        if normalize is not None:
+            print("caller_performance_normalized.tsv\t%s" % ",".join(callers))
         if mutation_context is not None:
             for mix in mixes:
                 for c in callers:
@@ -321,6 +335,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         jobs[-1].boot = boot
         if cpar is not None:
             jobs[-1].context, jobs[-1].context_genome = cpar, seq_context[s[:2]]
+        if normalize is not None and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].normalize = normalize[s[:2]]
+            jobs[-1].rescued_out = os.path.join(d, "norm", os.path.basename(src)[:-4] + ".rescued.tsv")
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -382,13 +399,16 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             _write_context(os.path.join(tables, "caller_performance_context.tsv"), [(c, s, j) for (c, s), j in zip(meta, jobs)], cpar)
         if sweep is not None:
             _write_surface([(c, s, j) for (c, s), j in zip(meta, jobs) if s in mixed], tables, sweep[0])
+        if normalize is not None:
+            from .normalize import write_performance_normalized
+            write_performance_normalized(os.path.join(tables, "caller_performance_normalized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
         from .multigpu import extract_many_sharded
         groups = [[i for i, (c, s) in enumerate(meta) if s == smp] for smp in samples]
         jobs, res = extract_many_sharded(jobs, int(gpus), backend=_backend, body=_body, same_device=_same_device, groups=groups,
-                                         post="quasimodo_amd.workflow:hcmv_rank_post",
+                                         alleles=True if alleles else None, post="quasimodo_amd.workflow:hcmv_rank_post",
                                          post_args=dict(meta=meta, cmp_callers=cmp_callers, snp_dir=snp_dir))
         write_tables(jobs)
         if mixed and len(cmp_callers) >= 2:
@@ -405,7 +425,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     if own:
         engine = Engine(int(os.environ.get("QM_DEVICE", "0")))
     try:
-        extract_many(jobs, engine=engine)                                # extractTP, one batch
+        extract_many(jobs, engine=engine, alleles=True if alleles else None)   # extractTP, one batch
         write_tables(jobs)
         indel_roc(engine, [(c, smp, j) for (c, smp), j in zip(meta, jobs) if not j.stats.get("pure_strain")], snp_dir)
         if mixed and len(cmp_callers) >= 2:                              # compareFP (counts only)

@@ -132,13 +132,19 @@ def _bootstrap_opts(n_rep, window, seed):
                    "(needs the genomes: --merlin-ref / --ad169-ref or the config).")
 @click.option("--context-window", "context_window", type=int, default=None, help="--seq-context: positions on either side of a call in its GC window [default: 50; 0 to 1024].")
 @click.option("--context-gc-bins", "context_gc_bins", type=int, default=None, help="--seq-context: GC bins [default: 10; 1 to 15].")
+@click.option("--alleles", "alleles", is_flag=True, default=False,
+              help="Allele-extended mode: records and truth rows with REF and ALT of any length [ACGT]+ take part (indels, MNPs), matched by spelling.")
+@click.option("--normalize", "normalize", is_flag=True, default=False,
+              help="With --alleles: also match indels and MNPs by normal form (trimmed, left-aligned against the genome): write "
+                   "final_tables/caller_performance_normalized.tsv and callers/*/norm/*.rescued.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config).")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
          mutation_context=False, merlin_ref=None, ad169_ref=None, truth_side=False, snp_profile=False, profile_window=1024,
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
-         surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None):
+         surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
+         normalize=False):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -153,7 +159,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
     genomes = None
-    if mutation_context or seq_context:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+    if mutation_context or seq_context or normalize:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
         pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
@@ -168,7 +174,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              bootstrap=_bootstrap_opts(bootstrap, bootstrap_window, bootstrap_seed),
                                              votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius,
                                              filter_surface=filter_surface, surface_qual_step=surface_qual_step,
-                                             surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins)
+                                             surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
+                                             alleles=alleles, normalize=genomes if normalize else None)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -218,12 +225,17 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                    "(the genome is the first file of -r/--refs: the one the VCFs were called against).")
 @click.option("--context-window", "context_window", type=int, default=None, help="--seq-context: positions on either side of a call in its GC window [default: 50; 0 to 1024].")
 @click.option("--context-gc-bins", "context_gc_bins", type=int, default=None, help="--seq-context: GC bins [default: 10; 1 to 15].")
+@click.option("--normalize", "normalize", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode to normalise (hcmv has it).")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
-            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None):
+            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False):
     from quasimodo_amd import workflow
     try:
+        if normalize:
+            raise workflow.WorkflowError("--normalize needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --normalize)")
         # what the command line leaves out comes from config/customize_data.yaml (run_benchmark.py:153-166,
         # rules/load_config_custom.smk:3, eval_variant_custom.smk:3-34)
         cfg_file = config or os.path.join(wd, "config", "customize_data.yaml")
