@@ -554,6 +554,54 @@ int qm_batch_get_normalized(qm_batch* b, int vcf, int32_t* pos, int32_t* ref, in
 int qm_batch_normalize_timings(qm_batch* b, float* ms3);
 int qm_truth_normalized(qm_ctx* ctx, int truth_id, int genome_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out);
 int qm_truth_entries(qm_ctx* ctx, int truth_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out);
+
+/* ---- MNPs matched against adjacent SNVs (build-defined, opt-in, QM_BATCH_ALLELES batches only) ----
+ * A variant is (p, R, A) with allele codes as above.  Atomisable: both alleles have inline codes (1 .. QM_ALLELE_INLINE_MAX
+ *   bases), no QM_F_NOKEY, len(R) == len(A), R != A, p >= 0 and p + len(R) - 1 < 2^28.  Otherwise the record keeps its exact-match
+ *   verdict and is counted under the first reason that applies: LONG (an allele without an inline code), NOKEY, NOVAR (R == A),
+ *   UNEQUAL (indels and complex records of different lengths), RANGE.
+ * Atoms of an atomisable variant: for every k with R[k] != A[k] the single-base variant (p + k, R[k], A[k]), 1 to 13 of them,
+ *   each one 32-bit word (pos << 4) | (ref << 2) | alt.  An SNV is its own atom.  No genome takes part.
+ * Atom set of a truth set: the distinct atoms of its atomisable allele-extended entries (the entries and order of
+ *   qm_truth_entries); the entries that are not atomisable stay in the matching by spelling only.
+ * Per record: n_atoms; hit_mask, bit k set if the atom at offset k is in the atom set; n_hit its popcount.  hitA = all atoms hit
+ *   for an atomisable record, the batch's exact hit for any other.  A TP_A line is kept and (hitA and QM_F_IDDOT, or
+ *   QM_F_TPLINE); an exact TP line is always a TP_A line.  rescued = TP_A and no TP line; partial = kept, atomisable and
+ *   0 < n_hit < n_atoms.
+ * rec[v][QM_ATOM_R_COLS], over the kept records: QM_ATOM_R_KEPT, _TP (the batch's TP lines), _TP_A, _RESCUED, _MULTI (atomisable
+ *   with at least 2 atoms), _PARTIAL, _ATOMS / _ATOMS_HIT (sums of n_atoms / n_hit over the atomisable kept records), then one
+ *   column per reason in the order above.
+ * tru[v][QM_ATOM_T_COLS]: QM_ATOM_T_ENTRIES (allele-extended truth entries), _ATOMISABLE, _ATOMS (distinct atoms), _ATOMS_FOUND
+ *   (atoms carried by an atomisable kept record, the ID column ignored), _FOUND (entries spelled like a kept record with valid
+ *   codes and no QM_F_NOKEY, the ID ignored), _FOUND_A (atomisable entries whose atoms are all found, plus the entries that are
+ *   not atomisable and FOUND).  FOUND <= FOUND_A; without kept QM_F_NOKEY records FOUND == QM_S_TP_R.
+ * With QM_ATOM_COLUMNS the pass also keeps per record, kept or not: a class byte (QM_ATOM_C_RESCUED for a rescued line, else
+ *   _FULL / _PARTIAL / _NONE by n_hit for an atomisable record, else the reason), n_atoms as uint8 (0 where the record is not
+ *   atomisable) and hit_mask as uint16.
+ * qm_batch_atomize: asynchronous on `stream` (NULL = the context's own) but for one small blocking copy; it builds the sets on
+ *   that stream at every call (the first call that meets a truth set counts its atoms once, and waits for that number).
+ *   QM_E_STATE unless the latest qm_batch_run was finished, for a batch without QM_BATCH_ALLELES, and for a released truth set.
+ *   The first call allocates the outputs (qm_batch_device_bytes).
+ * qm_batch_get_atomize / qm_batch_get_atomized: wait for the pass, then copy; any pointer may be NULL.  QM_E_STATE if the batch
+ *   ran since, and for columns the latest call did not keep.
+ * qm_batch_atomize_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] the sets (k_atom_truth),
+ *   [1] k_atom_records, [2] k_atom_found.
+ * qm_truth_atoms: the atom set of a truth set, sorted ascending; *n_out = how many, QM_E_RANGE (with *n_out set) when capacity
+ *   is smaller. */
+#define QM_ATOM_R_COLS 13
+#define QM_ATOM_T_COLS 6
+#define QM_ATOM_COLUMNS 2u
+enum { QM_ATOM_R_KEPT = 0, QM_ATOM_R_TP = 1, QM_ATOM_R_TP_A = 2, QM_ATOM_R_RESCUED = 3, QM_ATOM_R_MULTI = 4, QM_ATOM_R_PARTIAL = 5,
+       QM_ATOM_R_ATOMS = 6, QM_ATOM_R_ATOMS_HIT = 7, QM_ATOM_R_LONG = 8, QM_ATOM_R_NOKEY = 9, QM_ATOM_R_NOVAR = 10, QM_ATOM_R_UNEQUAL = 11,
+       QM_ATOM_R_RANGE = 12 };
+enum { QM_ATOM_T_ENTRIES = 0, QM_ATOM_T_ATOMISABLE = 1, QM_ATOM_T_ATOMS = 2, QM_ATOM_T_ATOMS_FOUND = 3, QM_ATOM_T_FOUND = 4, QM_ATOM_T_FOUND_A = 5 };
+enum { QM_ATOM_C_FULL = 0, QM_ATOM_C_PARTIAL = 1, QM_ATOM_C_NONE = 2, QM_ATOM_C_RESCUED = 3, QM_ATOM_C_LONG = 4, QM_ATOM_C_NOKEY = 5,
+       QM_ATOM_C_NOVAR = 6, QM_ATOM_C_UNEQUAL = 7, QM_ATOM_C_RANGE = 8 };
+int qm_batch_atomize(qm_batch* b, unsigned what /*0 or QM_ATOM_COLUMNS*/, void* stream);
+int qm_batch_get_atomize(qm_batch* b, uint64_t* rec /*[n_vcf][QM_ATOM_R_COLS] or NULL*/, uint64_t* tru /*[n_vcf][QM_ATOM_T_COLS] or NULL*/);
+int qm_batch_get_atomized(qm_batch* b, int vcf, uint8_t* cls, uint8_t* n_atoms, uint16_t* hit_mask /*[n] each, or NULL*/);
+int qm_batch_atomize_timings(qm_batch* b, float* ms3);
+int qm_truth_atoms(qm_ctx* ctx, int truth_id, uint32_t* keys, int64_t capacity, int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -938,6 +986,24 @@ typedef struct qm_normalize_args {
 int qm_extract_files_normalize(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                                void* global_dev, const qm_normalize_args* normalize);
+
+/* qm_extract_files_ex plus the atomisation pass over its batch; mode must be QM_BATCH_ALLELES (QM_E_STATE
+ * otherwise).  Jobs with want[j] != 0 get their rows rec[j][QM_ATOM_R_COLS] and tru[j][QM_ATOM_T_COLS] of qm_batch_get_atomize;
+ * the others get zero rows.  A wanted pure-strain job joins the batch against an empty truth set: its tru row stays zero and
+ * every kept line is FP.  atoms_out (may be NULL, entries may be NULL): per job a file `#line POS REF ALT N_ATOMS N_HIT HIT_MASK
+ * CLASS`, one row per kept atomisable line with at least 2 atoms in file order -- the 1-based line number, the line's own text
+ * of the three columns, the atom count, the hit count, the hit mask in hexadecimal and the class name --, written atomically
+ * (temp file + rename).  The VCF outputs, stats and roc are those of qm_extract_files_ex.  Combines with none of the other
+ * opt-in views. */
+typedef struct qm_atomize_args {
+  const uint8_t* want;              /* [n_jobs] */
+  uint64_t* rec;                    /* [n_jobs][QM_ATOM_R_COLS] */
+  uint64_t* tru;                    /* [n_jobs][QM_ATOM_T_COLS] */
+  const char* const* atoms_out;     /* [n_jobs] or NULL */
+} qm_atomize_args;
+int qm_extract_files_atomize(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                             void* global_dev, const qm_atomize_args* atomize);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

@@ -55,6 +55,9 @@ QM_CX_TRUTH = 2
 QM_NORM_R_COLS = 12
 QM_NORM_T_COLS = 5
 QM_NORM_COLUMNS = 2
+QM_ATOM_R_COLS = 13
+QM_ATOM_T_COLS = 6
+QM_ATOM_COLUMNS = 2
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -81,6 +84,7 @@ EXPORTS = (
     "qm_genome_context", "qm_batch_context", "qm_batch_get_context", "qm_batch_context_timings",
     "qm_extract_files_context",
     "qm_batch_normalize", "qm_batch_get_normalize", "qm_batch_get_normalized", "qm_batch_normalize_timings", "qm_truth_normalized", "qm_truth_entries", "qm_extract_files_normalize",
+    "qm_batch_atomize", "qm_batch_get_atomize", "qm_batch_get_atomized", "qm_batch_atomize_timings", "qm_truth_atoms", "qm_extract_files_atomize",
 )
 
 
@@ -147,6 +151,11 @@ class NormalizeArgs(C.Structure):
     _fields_ = [("genome_id", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("rescued_out", C.POINTER(C.c_char_p))]
 
 
+class AtomizeArgs(C.Structure):
+    """include/qmvt.h qm_atomize_args"""
+    _fields_ = [("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("atoms_out", C.POINTER(C.c_char_p))]
+
+
 class ContextArgs(C.Structure):
     """include/qmvt.h qm_context_args"""
     _fields_ = [("w", C.c_int32), ("ng", C.c_int32), ("genome_id", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("gen", C.c_void_p)]
@@ -172,7 +181,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -391,6 +400,13 @@ def lib():
     L.qm_batch_normalize_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_truth_normalized.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.qm_truth_entries.argtypes = [vp, i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.qm_extract_files_atomize.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                           C.POINTER(AtomizeArgs)]
+    L.qm_batch_atomize.argtypes = [vp, C.c_uint, vp]
+    L.qm_batch_get_atomize.argtypes = [vp, vp, vp]
+    L.qm_batch_get_atomized.argtypes = [vp, i32, vp, vp, vp]
+    L.qm_batch_atomize_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_truth_atoms.argtypes = [vp, i32, vp, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

@@ -32,6 +32,7 @@
 #include "qmvt_nearmiss.h"
 #include "qmvt_surface.h"
 #include "qmvt_norm.h"
+#include "qmvt_atom.h"
 
 using namespace qm;
 
@@ -65,6 +66,7 @@ struct Truth {
   int32_t *d_xref = nullptr, *d_xalt = nullptr, *d_xtidx = nullptr;
   int32_t xshift = 0, xnb = 0;
   int64_t xn = 0;
+  int64_t atom_total = -1;   // the atoms of the atomisable entries, repeats included; -1: not counted yet
   // how a synthetic truth set was generated (qm_truth_synth*): lets qm_batch_synth generate every VCF of a batch
   // against the truth set it is assigned to
   bool synthetic = false;
@@ -870,6 +872,18 @@ struct qm_batch {
   bool nz_timed = false;              // the latest qm_batch_normalize recorded them
   unsigned nz_made = 0;               // 1 | QM_NORM_COLUMNS: what the latest qm_batch_normalize made behind the latest run
   std::vector<uint8_t> nz_has;        // [n_vcf] the VCF named a genome
+  // qm_batch_atomize (lazy): the atom sets of the batch's truth sets in one pool, the per-VCF descriptors and
+  // bitmaps, [n_vcf][QM_ATOM_R_COLS] / [n_vcf][QM_ATOM_T_COLS] counts and, on request, a class byte, an atom count and a hit mask
+  // per record; ev_atom says when the pass is done
+  DevBuf<uint32_t> at_pool, at_bits;
+  DevBuf<AtomVcf> at_vcfs;
+  DevBuf<uint64_t> at_rec, at_tru;
+  DevBuf<uint8_t> at_cls;             // [2][n_pad]: class bytes, atom counts
+  DevBuf<uint16_t> at_hm;             // [n_pad]
+  hipEvent_t ev_atom = nullptr;
+  hipEvent_t ev_att[4] = {};          // qm_batch_set_timing: around the set builds, k_atom_records, k_atom_found
+  bool at_timed = false;              // the latest qm_batch_atomize recorded them
+  unsigned at_made = 0;               // 1 | QM_ATOM_COLUMNS: what the latest qm_batch_atomize made behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -904,6 +918,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_cxt) if (e) (void)hipEventDestroy(e);
   if (b->ev_norm) (void)hipEventDestroy(b->ev_norm);
   for (auto& e : b->ev_nzt) if (e) (void)hipEventDestroy(e);
+  if (b->ev_atom) (void)hipEventDestroy(b->ev_atom);
+  for (auto& e : b->ev_att) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -1238,6 +1254,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->sf_valid = false;
   b->cx_made = 0;
   b->nz_made = 0;
+  b->at_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -2891,6 +2908,201 @@ extern "C" int qm_truth_normalized(qm_ctx* c, int truth_id, int genome_id, int32
     if (ref) ref[i] = forms[i].r;
     if (alt) alt[i] = forms[i].a;
   }
+  return QM_OK;
+}
+// ---- MNPs matched against adjacent SNVs ----
+// The pool words of one set: set[slots], stats[2] (8-byte aligned: slots is even)
+static size_t atom_pool_words(uint32_t slots) { return (size_t)slots + 4; }
+static AtomTable atom_table(const Truth& t, uint32_t* pool, uint32_t slots) {
+  AtomTable T;
+  memset(&T, 0, sizeof T);
+  T.xkeys = t.d_xkeys; T.xref = t.d_xref; T.xalt = t.d_xalt; T.xn = t.xn;
+  T.slots = slots;
+  T.set = pool;
+  T.stats = reinterpret_cast<unsigned long long*>(pool + (size_t)slots);
+  return T;
+}
+// Builds the set on `st` (the pool words start at a multiple of 8 bytes).
+static int atom_build(const AtomTable& T, hipStream_t st) {
+  HIPCHK(hipMemsetAsync(T.set, 0xff, (size_t)T.slots * 4, st));
+  HIPCHK(hipMemsetAsync(T.stats, 0, 16, st));
+  launch_atom_truth(T, st);
+  HIPCHK(hipGetLastError());
+  return QM_OK;
+}
+// How many atoms the atomisable entries of a truth set have together (what sizes its set): counted on the device at the first
+// call that meets the truth set, one blocking 8-byte copy, and kept with it.
+static int atom_total(qm_ctx* c, Truth& t, int64_t* out) {
+  if (t.atom_total < 0) {
+    unsigned long long* d = nullptr;
+    unsigned long long h = 0;
+    DALLOC(d, 1);
+    hipError_t e = hipMemsetAsync(d, 0, 8, c->stream);
+    if (e == hipSuccess) {
+      launch_atom_count(atom_table(t, nullptr, ATOM_MIN_SLOTS), d, c->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(QM_E_HIP, "qm_batch_atomize: counting the atoms of a truth set: %s", hipGetErrorString(e));
+    t.atom_total = (int64_t)h;
+  }
+  *out = t.atom_total;
+  return QM_OK;
+}
+extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_atomize");
+  if (what & ~QM_ATOM_COLUMNS) return fail(QM_E_INVAL, "qm_batch_atomize: what = %u", what);
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_atomize: a single-base batch holds no MNPs to split into atoms (create the batch with QM_BATCH_ALLELES)");
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  int rc = truths_live(b, "qm_batch_atomize");
+  if (rc != QM_OK) return rc;
+  HIPCHK(hipSetDevice(c->dev));
+  // one set per truth set
+  struct Set { int truth; size_t off; uint32_t slots; };
+  std::vector<Set> sets;
+  std::vector<size_t> set_of(nv, 0);
+  size_t pool_words = 0, bit_words = 0;
+  int64_t max_lanes = 1;
+  for (size_t v = 0; v < nv; ++v) {
+    const int tid = b->L.vcfs[v].truth;
+    size_t k = 0;
+    while (k < sets.size() && sets[k].truth != tid) ++k;
+    if (k == sets.size()) {
+      int64_t total = 0;
+      rc = atom_total(c, c->truths[(size_t)tid], &total);
+      if (rc != QM_OK) return rc;
+      const uint32_t slots = atom_slots(total);
+      sets.push_back(Set{tid, pool_words, slots});
+      pool_words += atom_pool_words(slots);
+    }
+    set_of[v] = k;
+    const int64_t xn = c->truths[(size_t)tid].xn;
+    bit_words += (size_t)(sets[k].slots / 32u) + (size_t)(xn / 32 + 1);
+    max_lanes = std::max<int64_t>(max_lanes, std::max<int64_t>(xn, (int64_t)(sets[k].slots / 32u)));
+  }
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_atom, &st);
+  if (rc != QM_OK) return rc;
+  b->at_made = 0;   // from here on the outputs are rewritten
+  const size_t np = (size_t)b->L.n_pad;
+  rc = b->at_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->at_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->at_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->at_rec.grow((int64_t)std::max<size_t>(nv * ATOM_R_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->at_tru.grow((int64_t)std::max<size_t>(nv * ATOM_T_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK && (what & QM_ATOM_COLUMNS)) rc = b->at_cls.grow((int64_t)std::max<size_t>(2 * np, 1), &b->dev_bytes);
+  if (rc == QM_OK && (what & QM_ATOM_COLUMNS)) rc = b->at_hm.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_att) if (!e) HIPCHK(hipEventCreate(&e));
+  b->at_timed = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_att[0], st));
+  std::vector<AtomTable> tabs(sets.size());
+  for (size_t k = 0; k < sets.size(); ++k) {
+    tabs[k] = atom_table(c->truths[(size_t)sets[k].truth], b->at_pool + sets[k].off, sets[k].slots);
+    rc = atom_build(tabs[k], st);
+    if (rc != QM_OK) return rc;
+  }
+  std::vector<AtomVcf> vcfs(std::max<size_t>(nv, 1));
+  memset(vcfs.data(), 0, vcfs.size() * sizeof(AtomVcf));
+  size_t bo = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    vcfs[v].t = tabs[set_of[v]];
+    vcfs[v].abits = b->at_bits + bo;
+    bo += (size_t)(vcfs[v].t.slots / 32u);
+    vcfs[v].ebits = b->at_bits + bo;
+    bo += (size_t)(vcfs[v].t.xn / 32 + 1);
+  }
+  if (nv) HIPCHK(hipMemcpy(b->at_vcfs, vcfs.data(), nv * sizeof(AtomVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
+  HIPCHK(hipMemsetAsync(b->at_bits, 0, std::max<size_t>(bit_words, 1) * 4, st));
+  HIPCHK(hipMemsetAsync(b->at_rec, 0, std::max<size_t>(nv * ATOM_R_COLS, 1) * 8, st));
+  HIPCHK(hipMemsetAsync(b->at_tru, 0, std::max<size_t>(nv * ATOM_T_COLS, 1) * 8, st));
+  if (what & QM_ATOM_COLUMNS) {
+    HIPCHK(hipMemsetAsync(b->at_cls, 0, std::max<size_t>(2 * np, 1), st));
+    HIPCHK(hipMemsetAsync(b->at_hm, 0, std::max<size_t>(np, 1) * 2, st));
+  }
+  if (T) HIPCHK(hipEventRecord(b->ev_att[1], st));
+  AtomRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.vcfs = b->at_vcfs;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  if (what & QM_ATOM_COLUMNS) { P.cls = b->at_cls; P.n_atoms = b->at_cls + np; P.hit_mask = b->at_hm; }
+  P.rec = b->at_rec;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_atom_records(P, st);
+  HIPCHK(hipGetLastError());
+  if (T) HIPCHK(hipEventRecord(b->ev_att[2], st));
+  launch_atom_found(b->at_vcfs, (int)nv, max_lanes, b->at_tru, st);
+  HIPCHK(hipGetLastError());
+  if (T) { HIPCHK(hipEventRecord(b->ev_att[3], st)); b->at_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_atom, st));
+  b->at_made = 1u | what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_atomize(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_atomize: NULL batch");
+  if (!b->at_made) return fail(QM_E_STATE, "qm_batch_get_atomize: no qm_batch_atomize behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_atom));
+  const size_t nv = (size_t)b->n_vcf;
+  if (rec && nv) HIPCHK(hipMemcpy(rec, b->at_rec, nv * ATOM_R_COLS * 8, hipMemcpyDeviceToHost));
+  if (tru && nv) HIPCHK(hipMemcpy(tru, b->at_tru, nv * ATOM_T_COLS * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_atomized(qm_batch* b, int v, uint8_t* cls, uint8_t* n_atoms, uint16_t* hit_mask) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_atomized: NULL batch");
+  if (!b->at_made) return fail(QM_E_STATE, "qm_batch_get_atomized: no qm_batch_atomize behind the latest run");
+  if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_atomized: VCF %d (the batch has %d)", v, b->n_vcf);
+  if (!(b->at_made & QM_ATOM_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_get_atomized: the latest qm_batch_atomize did not keep the columns (QM_ATOM_COLUMNS)");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_atom));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  if (d.n == 0) return QM_OK;
+  const size_t np = (size_t)b->L.n_pad, n = (size_t)d.n;
+  if (cls) HIPCHK(hipMemcpy(cls, b->at_cls + d.off, n, hipMemcpyDeviceToHost));
+  if (n_atoms) HIPCHK(hipMemcpy(n_atoms, b->at_cls + np + d.off, n, hipMemcpyDeviceToHost));
+  if (hit_mask) HIPCHK(hipMemcpy(hit_mask, b->at_hm + d.off, n * 2, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_atomize_timings(qm_batch* b, float* ms3) {
+  if (!b || !ms3) return fail(QM_E_INVAL, "qm_batch_atomize_timings: NULL");
+  if (!b->at_made) return fail(QM_E_STATE, "qm_batch_atomize_timings: no qm_batch_atomize behind the latest run");
+  if (!b->at_timed) return fail(QM_E_STATE, "qm_batch_atomize_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_att[3]));
+  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_att[i], b->ev_att[i + 1]));
+  return QM_OK;
+}
+extern "C" int qm_truth_atoms(qm_ctx* c, int truth_id, uint32_t* keys, int64_t capacity, int64_t* n_out) {
+  if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_atoms: bad arguments");
+  if (truth_id < 0 || truth_id >= (int)c->truths.size() || c->truths[(size_t)truth_id].released)
+    return fail(QM_E_INVAL, "qm_truth_atoms: no live truth set %d", truth_id);
+  HIPCHK(hipSetDevice(c->dev));
+  Truth& t = c->truths[(size_t)truth_id];
+  int64_t total = 0;
+  int rc = atom_total(c, t, &total);
+  if (rc != QM_OK) return rc;
+  const uint32_t slots = atom_slots(total);
+  uint32_t* pool = nullptr;
+  DALLOC(pool, atom_pool_words(slots));
+  const AtomTable T = atom_table(t, pool, slots);
+  std::vector<uint32_t> h((size_t)slots);
+  rc = atom_build(T, c->stream);
+  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
+  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(h.data(), pool, h.size() * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(pool);
+  if (rc != QM_OK) return rc;
+  if (e != hipSuccess) return fail(QM_E_HIP, "qm_truth_atoms: %s", hipGetErrorString(e));
+  h.erase(std::remove(h.begin(), h.end(), ATOM_EMPTY), h.end());
+  std::sort(h.begin(), h.end());
+  *n_out = (int64_t)h.size();
+  if ((int64_t)h.size() > capacity) return fail(QM_E_RANGE, "qm_truth_atoms: %zu atoms, room for %lld", h.size(), (long long)capacity);
+  if (keys && !h.empty()) memcpy(keys, h.data(), h.size() * 4);
   return QM_OK;
 }
 // paired block-bootstrap replicates of the finished batch's counts

@@ -299,6 +299,7 @@ struct Passes {
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
+  const qm_atomize_args* at = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -308,7 +309,8 @@ struct Passes {
   bool wants_af(int j) const { return wants_profile(j) || wants_surface(j); }   // the INFO column is scanned and uploaded
   // the passes a pure-strain job joins the batch for (against an empty truth set, for its rows of the pass only: its files,
   // stats and ROC rows are made as for any pure-strain job); every mixed-sample job is in the batch anyway
-  bool any_batch_only(int j) const { return has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j) || wants_context(j); }
+  bool wants_atomize(int j) const { return at && at->want[j] != 0; }
+  bool any_batch_only(int j) const { return has_genome(j) || wants_profile(j) || wants_strata(j) || wants_boot(j) || wants_context(j) || wants_atomize(j); }
 };
 
 // what a pass sees of the call: the finished batch and the jobs behind its VCFs
@@ -741,6 +743,77 @@ int normalize_pass(const PassCtx& c, const Passes& P, std::string& err) {
   return QM_OK;
 }
 
+// ---- MNPs matched against adjacent SNVs ----
+struct AtColumns { std::vector<uint8_t> cls, na; std::vector<uint16_t> hm; std::vector<uint64_t> kept; };
+// `#line POS REF ALT N_ATOMS N_HIT HIT_MASK CLASS`, then one row per kept atomisable line of the job with at least 2 atoms in file
+// order: the 1-based line number, the line's own text of the three columns, the atom and hit counts, the hit mask in hexadecimal
+// and the class name
+int write_atoms_file(const char* path, const JobState& s, const AtColumns& c) {
+  static const char* const names[] = {"full", "partial", "none", "rescued", "long", "nokey", "novar", "unequal", "range"};
+  std::string out = "#line\tPOS\tREF\tALT\tN_ATOMS\tN_HIT\tHIT_MASK\tCLASS\n";
+  const uint8_t* text = s.vcf.p;
+  const size_t len = s.vcf.n;
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    const int64_t r = rec++;
+    if (c.na[(size_t)r] < 2 || !((c.kept[(size_t)r >> 6] >> (r & 63)) & 1ull)) continue;
+    size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], len);
+    if (e > b && text[e - 1] == '\n') --e;
+    const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+    const uint8_t* q = text + b;
+    while (nf < 6) {
+      const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(text + e - q));
+      f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(text + e - q); ++nf;
+      if (!tb) break;
+      q = tb + 1;
+    }
+    out.append(std::to_string(i + 1));
+    for (int k : {1, 3, 4}) { out.push_back('\t'); if (k < nf) out.append((const char*)f[k], fl[k]); }
+    char hex[16];
+    snprintf(hex, sizeof hex, "0x%04x", (unsigned)c.hm[(size_t)r]);
+    out += "\t" + std::to_string((int)c.na[(size_t)r]) + "\t" + std::to_string(__builtin_popcount((unsigned)c.hm[(size_t)r])) + "\t" + hex + "\t" +
+           names[std::min<size_t>(c.cls[(size_t)r], 8)];
+    out.push_back('\n');
+  }
+  return write_all_atomic(path, out);
+}
+
+// the counts of every wanted job, and the atoms files of the jobs that name one
+int atomize_pass(const PassCtx& c, const Passes& P, std::string& err) {
+  const qm_atomize_args* at = P.at;
+  auto want = [&](int j) { return P.wants_atomize(j); };
+  if (!at || !c.any(want)) return QM_OK;
+  auto path = [&](int j) { return want(j) && at->atoms_out ? at->atoms_out[j] : nullptr; };
+  bool files = false;
+  for (int j = 0; j < c.n_jobs; ++j) files = files || path(j);
+  std::vector<uint64_t> rec(c.nv * QM_ATOM_R_COLS), tru(c.nv * QM_ATOM_T_COLS);
+  int rc = qm_batch_atomize(c.batch, files ? QM_ATOM_COLUMNS : 0u, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_atomize(c.batch, rec.data(), tru.data());
+  if (rc == QM_OK) { c.scatter_rows(at->rec, rec, QM_ATOM_R_COLS, want); c.scatter_rows(at->tru, tru, QM_ATOM_T_COLS, want); }
+  struct Task { int j; AtColumns cols; };
+  std::vector<Task> W;
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    if (!path(j)) continue;
+    const JobState& s = c.J[(size_t)j];
+    const size_t n = (size_t)s.n_data + 1;
+    W.push_back({j, AtColumns{std::vector<uint8_t>(n, 0), std::vector<uint8_t>(n, 0), std::vector<uint16_t>(n, 0), std::vector<uint64_t>(n / 64 + 2, 0)}});
+    AtColumns& k = W.back().cols;
+    std::vector<uint64_t> tpm(k.kept.size());
+    rc = qm_batch_get_atomized(c.batch, s.batch_v, k.cls.data(), k.na.data(), k.hm.data());
+    if (rc == QM_OK) rc = qm_batch_get_masks(c.batch, s.batch_v, k.kept.data(), tpm.data());
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  std::vector<int> wrc(W.size(), QM_OK);
+  parallel_for((int)W.size(), c.nthr, [&](int k) {
+    const Task& w = W[(size_t)k];
+    wrc[(size_t)k] = write_atoms_file(at->atoms_out[w.j], c.J[(size_t)w.j], w.cols);
+  });
+  for (size_t k = 0; k < W.size(); ++k)
+    if (wrc[k] != QM_OK) { err = std::string("cannot write ") + at->atoms_out[W[k].j]; return wrc[k]; }
+  return QM_OK;
+}
+
 // the filter surface: S and extra of every wanted job
 int surface_pass(const PassCtx& c, const qm_surface_args* sf, std::string& err) {
   auto want = [&](int j) { return sf->want[j] != 0; };
@@ -879,6 +952,22 @@ extern "C" int qm_extract_files_normalize(qm_ctx* ctx, int n_jobs, const qm_file
     memset(na->tru, 0, sizeof(uint64_t) * QM_NORM_T_COLS * (size_t)n_jobs);
   }
   Passes P; P.nz = na;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// MNPs matched against adjacent SNVs behind the worker
+extern "C" int qm_extract_files_atomize(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                        qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                        int n_slots, void* global_dev, const qm_atomize_args* atomize) {
+  const qm_atomize_args* at = atomize;
+  if (!at || (n_jobs > 0 && (!at->want || !at->rec || !at->tru))) return fail(QM_E_INVAL, "qm_extract_files_atomize: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_atomize: atoms are taken of MNPs, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (n_jobs > 0) {
+    memset(at->rec, 0, sizeof(uint64_t) * QM_ATOM_R_COLS * (size_t)n_jobs);
+    memset(at->tru, 0, sizeof(uint64_t) * QM_ATOM_T_COLS * (size_t)n_jobs);
+  }
+  Passes P; P.at = at;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -1238,6 +1327,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = nearmiss_pass(pc, P.nm, err);
       if (rc == QM_OK) rc = context_pass(pc, P, err);
       if (rc == QM_OK) rc = normalize_pass(pc, P, err);
+      if (rc == QM_OK) rc = atomize_pass(pc, P, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

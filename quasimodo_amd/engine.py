@@ -132,6 +132,17 @@ class Engine:
         check(self._L.qm_truth_normalized(self._h, int(tid), int(gid), _p(pos), _p(ref), _p(alt), cap, C.byref(n)), self._h)
         return pos[:n.value], ref[:n.value], alt[:n.value]
 
+    def truth_atoms(self, tid):
+        """qm_truth_atoms: uint32 -- the atom set (atomize.py) of a truth set's allele-extended entries, each atom
+        (pos << 4) | (ref << 2) | alt, sorted ascending, from the kernel the pass uses"""
+        n = C.c_int64()
+        rc = self._L.qm_truth_atoms(self._h, int(tid), None, 0, C.byref(n))      # (how many: QM_E_RANGE unless there is none)
+        if rc not in (0, -5):                                                    # QM_E_RANGE
+            check(rc, self._h)
+        keys = np.zeros(max(n.value, 1), np.uint32)
+        check(self._L.qm_truth_atoms(self._h, int(tid), _p(keys), keys.shape[0], C.byref(n)), self._h)
+        return keys[:n.value]
+
     # -- strata sets (counts per genome region, DESIGN.md 4.10) -------------------
     def strata_load(self, strata):
         """strata: list of (name, starts, ends) BED intervals (quasimodo_amd.strata); returns the set's id"""
@@ -224,7 +235,8 @@ class Engine:
         return {k: getattr(r, k) for k, _ in r._fields_ if k != "reserved"}
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
-                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None):
+                      truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
+                      atomize=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -261,18 +273,22 @@ class Engine:
         normalize: {"genomes": [genome_load id or None / -1 per job], "rescued": [path or None per job]} --
         qm_extract_files_normalize (alleles=True only): the rows of mixed-sample jobs with a genome gain `norm_rec`
         ([12] uint64, columns normalize.R_COLS) and `norm_tru` ([5], normalize.T_COLS); the rescued-lines files are written.
+        atomize: {"want": [0/1 per job], "atoms": [path or None per job]} -- qm_extract_files_atomize (alleles=True
+        only): wanted rows gain `atom_rec` ([13] uint64, columns atomize.R_COLS) and `atom_tru` ([6], atomize.T_COLS); the atoms
+        files are written.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_normalize, check_shared_call
+        from .passes import check_atomize, check_normalize, check_shared_call
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
+        check_atomize({name for name, spec in specs.items() if spec is not None}, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -379,6 +395,19 @@ class Engine:
         took = lambda k: ngid[k] >= 0 and not file_jobs[k].get("pure")
         unpack = lambda k: {"norm_rec": nrec[k].copy(), "norm_tru": ntru[k].copy()} if took(k) else {}
         return self._L.qm_extract_files_normalize, (C.byref(na),), unpack
+
+    def _files_atomize(self, n, atomize, **kw):
+        awant = _c([int(bool(w)) for w in atomize["want"]] or [0], np.uint8)
+        paths = list(atomize.get("atoms") or [None] * n)
+        if (n and awant.shape[0] != n) or len(paths) != n:
+            raise ValueError("atomize: %d want / %d atoms entries for %d jobs" % (len(atomize["want"]), len(paths), n))
+        arec = np.zeros((max(n, 1), _lib.QM_ATOM_R_COLS), np.uint64)
+        atru = np.zeros((max(n, 1), _lib.QM_ATOM_T_COLS), np.uint64)
+        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        aa = _lib.AtomizeArgs(_p(awant), _p(arec), _p(atru), out_arr)
+        aa.keep = (awant, out_arr)   # (read during the call; the other arrays live in unpack)
+        unpack = lambda k: {"atom_rec": arec[k].copy(), "atom_tru": atru[k].copy()} if awant[k] else {}
+        return self._L.qm_extract_files_atomize, (C.byref(aa),), unpack
 
     def _files_boot(self, n, boot, **kw):
         bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
@@ -823,6 +852,35 @@ class Batch:
         ms = (C.c_float * 3)()
         self._ck(self._L.qm_batch_normalize_timings(self._h, ms))
         return {"norm_truth_ms": ms[0], "norm_records_ms": ms[1], "norm_found_ms": ms[2]}
+
+    # -- MNPs matched against adjacent SNVs ----------------------------
+    def atomize(self, columns=False, stream=None, fetch=True):
+        """qm_batch_atomize + qm_batch_get_atomize (allele-extended batches): (rec [n_vcf][13], tru [n_vcf][6]) uint64, columns
+        atomize.R_COLS / atomize.T_COLS; columns=True keeps every record's class byte, atom count and hit mask for atomized().
+        fetch=False: enqueue only (atomize_counts() waits and copies)"""
+        self._ck(self._L.qm_batch_atomize(self._h, _lib.QM_ATOM_COLUMNS if columns else 0, C.c_void_p(stream) if stream else None))
+        return self.atomize_counts() if fetch else None
+
+    def atomize_counts(self):
+        """qm_batch_get_atomize: the counts of the latest atomize()"""
+        rec = np.zeros((max(self.n_vcf, 1), _lib.QM_ATOM_R_COLS), np.uint64)
+        tru = np.zeros((max(self.n_vcf, 1), _lib.QM_ATOM_T_COLS), np.uint64)
+        self._ck(self._L.qm_batch_get_atomize(self._h, _p(rec), _p(tru)))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def atomized(self, v):
+        """qm_batch_get_atomized: (cls uint8 [n] -- the class bytes atomize.CLASS_NAMES --, n_atoms uint8 [n], hit_mask uint16
+        [n]) of VCF v in input order, after an atomize(columns=True)"""
+        n = int(self.n_records[int(v)])
+        cls, na, hm = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint16)
+        self._ck(self._L.qm_batch_get_atomized(self._h, int(v), _p(cls), _p(na), _p(hm)))
+        return cls[:n], na[:n], hm[:n]
+
+    def atomize_timings(self):
+        """qm_batch_atomize_timings (set_timing on): milliseconds of the latest atomize() between HIP events"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.qm_batch_atomize_timings(self._h, ms))
+        return {"atom_truth_ms": ms[0], "atom_records_ms": ms[1], "atom_found_ms": ms[2]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

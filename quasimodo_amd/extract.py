@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
-from .passes import PASSES, check_normalize, check_shared_call, requested_by
+from .passes import PASSES, check_atomize, check_normalize, check_shared_call, requested_by
 from .vcfio import scan_vcf
 
 
@@ -68,6 +68,9 @@ class Job:
     # indels and MNPs matched by normal form; mixed samples, allele-extended mode only
     normalize: str = None     # FASTA of the genome the VCF was called against: stats gain norm_rec / norm_tru
     rescued_out: str = None   # where the job's rescued-lines table goes (extract_many(normalize=) derives it)
+    # MNPs matched against adjacent SNVs; mixed samples, allele-extended mode only
+    atomize: bool = None      # True: stats gain atom_rec / atom_tru
+    atoms_out: str = None     # where the job's multi-atom lines table goes (extract_many(atomize=) derives it)
 
 
 def _paths(job):
@@ -138,7 +141,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None, normalize=None):
+                 surface=None, context=None, normalize=None, atomize=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -187,12 +190,18 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     stats["norm_rec"] ([12]: kept, TP, TP_N, rescued, respelled, single-base lines and the lines per reason a record has no normal
     form) and stats["norm_tru"] ([5]: truth entries, distinct forms, forms found, found by form only, entries without a normal
     form), and norm/<x>.rescued.tsv beside fp/ and tp/.  VCFs of one truth file name one genome.
+    atomize: True, or one truth value per job (quasimodo_amd.atomize; default: the jobs' Job.atomize /
+    Job.atoms_out; alleles=True only, ValueError otherwise): every wanted mixed-sample job gets stats["atom_rec"] ([13]: kept, TP,
+    TP_A, rescued, multi-atom and partial lines, atoms, atoms hit and the lines per reason a record is not atomisable) and
+    stats["atom_tru"] ([6]: truth entries, atomisable ones, distinct atoms, atoms found, entries found by spelling and by atoms),
+    and atoms/<x>.atoms.tsv beside fp/ and tp/.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
-             "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None}
+             "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
+             "atomize": atomize is not None and atomize is not False}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -241,6 +250,16 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if j.normalize:
                 _paths(j)
                 j.rescued_out = j.rescued_out or rescued_path(j)
+    if atomize is not None and atomize is not False:
+        from .atomize import atoms_path
+        awant = [True] * len(jobs) if atomize is True else [bool(w) for w in atomize]
+        if len(awant) != len(jobs):
+            raise ValueError("atomize: %d entries for %d jobs" % (len(awant), len(jobs)))
+        for j, w in zip(jobs, awant):
+            j.atomize = True if w and not is_pure_strain(j.vcf_file) else None
+            if j.atomize:
+                _paths(j)
+                j.atoms_out = j.atoms_out or atoms_path(j)
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -277,6 +296,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
     check_normalize(requested_by(jobs), alleles)
+    check_atomize(requested_by(jobs), alleles)
     by_truth = {}
     for j in jobs:
         if j.normalize and by_truth.setdefault(os.path.realpath(j.snp_file), (j.normalize, j.vcf_file))[0] != j.normalize:
@@ -307,7 +327,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = sf = cxs = nzs = None
+    ts = vt = nm = sf = cxs = nzs = ats = None
     if any(j.context is not None for j in jobs):
         from .context import check_params
         for j in jobs:
@@ -379,6 +399,10 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                        "rescued": [j.rescued_out if j.normalize else None for j in jobs]}
                 for path in [x for x in nzs["rescued"] if x]:
                     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            if any(j.atomize for j in jobs):
+                ats = {"want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]}
+                for path in [x for x in ats["atoms"] if x]:
+                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             # the passes with parameters: the tuple the jobs agreed on, and who wants the pass
             par = {f: next((getattr(j, f) for j in jobs if getattr(j, f)), None) for f in ("profile", "strata", "boot")}
             want = lambda f: [1 if getattr(j, f) else 0 for j in jobs]
@@ -394,7 +418,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

@@ -17,6 +17,7 @@ PASSES = (
     Pass("votes", ("vote_group",), ("votes",), "--votes", None, ()),
     Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
     Pass("normalize", ("normalize",), ("normalize",), "--normalize", None, ()),
+    Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
     Pass("context", ("context",), ("context",), "--seq-context",
          "context: the profiled jobs of one call share one half window and one GC bin count", ()),
     Pass("surface", ("surface",), ("surface",), "--filter-surface",
@@ -50,6 +51,12 @@ def check_normalize(requested, alleles):
     """--normalize reads indels and MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
     if "normalize" in requested and not alleles:
         raise ValueError("normalize (--normalize) needs the allele-extended mode (--alleles): a single-base batch holds no indels or MNPs")
+
+
+def check_atomize(requested, alleles):
+    """--atomize splits MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
+    if "atomize" in requested and not alleles:
+        raise ValueError("atomize (--atomize) needs the allele-extended mode (--alleles): a single-base batch holds no MNPs")
 
 
 def requested_by(jobs):

@@ -165,7 +165,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
-                         context_gc_bins=None, alleles=False, normalize=None):
+                         context_gc_bins=None, alleles=False, normalize=None, atomize=False):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -206,14 +206,20 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     WorkflowError before a file is touched otherwise): indels and MNPs are also matched by normal form behind the classification;
     final_tables/caller_performance_normalized.tsv (TP, FP, FN, Precision, Recall, F1 by spelling and by normal form side by side,
     the rescued, respelled and reason counts) and callers/{caller}/norm/{sample}.{ref}.{caller}.rescued.tsv for every mixed sample.
+    atomize: MNPs are also matched against adjacent SNVs, atom by atom (quasimodo_amd.atomize; needs alleles,
+    WorkflowError before a file is touched otherwise): final_tables/caller_performance_atomized.tsv (TP, FP, FN, Precision, Recall,
+    F1 by spelling and by atoms side by side, the rescued, multi-atom, partial and reason counts) and
+    callers/{caller}/atoms/{sample}.{ref}.{caller}.atoms.tsv for every mixed sample.
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
-                 context=seq_context is not None, normalize=normalize is not None)
+                 context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize))
     if normalize is not None and not alleles:
         raise WorkflowError("--normalize needs --alleles: the normal form is taken of indels and MNPs, which only the allele-extended mode reads")
+    if atomize and not alleles:
+        raise WorkflowError("--atomize needs --alleles: atoms are taken of MNPs, which only the allele-extended mode reads")
     radius = _explain_radius(explain_errors, explain_radius)
     sweep = _surface_params(filter_surface, surface_qual_step, surface_qual_bins, surface_af_bins)
     cpar = _context_params(seq_context is not None, context_window, context_gc_bins)
@@ -269,6 +275,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("extractTP\t%s\t%s" % (c, src))
         if normalize is not None:
             print("caller_performance_normalized.tsv\t%s" % ",".join(callers))
+        if atomize:
+            print("caller_performance_atomized.tsv\t%s" % ",".join(callers))
         if mutation_context is not None:
             for mix in mixes:
                 for c in callers:
@@ -338,6 +346,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if normalize is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].normalize = normalize[s[:2]]
             jobs[-1].rescued_out = os.path.join(d, "norm", os.path.basename(src)[:-4] + ".rescued.tsv")
+        if atomize and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].atomize = True
+            jobs[-1].atoms_out = os.path.join(d, "atoms", os.path.basename(src)[:-4] + ".atoms.tsv")
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -402,6 +413,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if normalize is not None:
             from .normalize import write_performance_normalized
             write_performance_normalized(os.path.join(tables, "caller_performance_normalized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
+        if atomize:
+            from .atomize import write_performance_atomized
+            write_performance_atomized(os.path.join(tables, "caller_performance_atomized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")

@@ -137,6 +137,9 @@ def _bootstrap_opts(n_rep, window, seed):
 @click.option("--normalize", "normalize", is_flag=True, default=False,
               help="With --alleles: also match indels and MNPs by normal form (trimmed, left-aligned against the genome): write "
                    "final_tables/caller_performance_normalized.tsv and callers/*/norm/*.rescued.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config).")
+@click.option("--atomize", "atomize", is_flag=True, default=False,
+              help="With --alleles: also match MNPs against adjacent SNVs, atom by atom (every equal-length substitution split into its "
+                   "single-base differences, on both sides): write final_tables/caller_performance_atomized.tsv and callers/*/atoms/*.atoms.tsv.")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
@@ -144,7 +147,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False):
+         normalize=False, atomize=False):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -175,7 +178,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius,
                                              filter_surface=filter_surface, surface_qual_step=surface_qual_step,
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
-                                             alleles=alleles, normalize=genomes if normalize else None)
+                                             alleles=alleles, normalize=genomes if normalize else None, atomize=atomize)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -227,12 +230,17 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
 @click.option("--context-gc-bins", "context_gc_bins", type=int, default=None, help="--seq-context: GC bins [default: 10; 1 to 15].")
 @click.option("--normalize", "normalize", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode to normalise (hcmv has it).")
+@click.option("--atomize", "atomize", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose MNPs could be split (hcmv has it).")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
-            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False):
+            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False):
     from quasimodo_amd import workflow
     try:
+        if atomize:
+            raise workflow.WorkflowError("--atomize needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --atomize)")
         if normalize:
             raise workflow.WorkflowError("--normalize needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --normalize)")
