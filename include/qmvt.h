@@ -225,7 +225,15 @@ int qm_bench_synth(qm_ctx* ctx, const qm_synth_cfg* cfg, int n_vcf, int64_t reco
  * stream): classify -> finalize (ROC suffix sums, tile offsets, per-truth sums)
  * -> compaction of TP/FP line indices.  Asynchronous.  If global_dev is not
  * NULL it must be a device buffer of [qm_batch_n_truth(b)][3][n_bins] uint64 that
- * receives the per-truth sums (the caller all-reduces it across ranks). */
+ * receives the per-truth sums (the caller all-reduces it across ranks).
+ *
+ * Ordering against the passes over a finished batch (qm_batch_motifs ... qm_batch_atomize below), each of which may have been
+ * enqueued on a stream of the caller's: a call that rewrites what passes read (qm_batch_run, qm_batch_upload,
+ * qm_batch_upload_async, qm_batch_synth, qm_batch_upload_af) is ordered behind every pass of the batch still in flight, on
+ * whatever stream.  The asynchronous ones (qm_batch_run, qm_batch_upload_async) make their stream wait for the passes' events;
+ * the blocking ones (qm_batch_upload, qm_batch_synth, qm_batch_upload_af) return when those passes are done.  A pass left in
+ * flight this way still completes, but its results belong to the run before: its getter answers QM_E_STATE.  A batch that never
+ * ran a pass pays nothing for this.  (qm_batch_finish takes the stream of the run it finishes.) */
 int qm_batch_run(qm_batch* b, void* stream, void* global_dev);
 /* Wait for the stream, then redo VCFs found unsorted through the radix-sort path. */
 int qm_batch_finish(qm_batch* b, void* stream);

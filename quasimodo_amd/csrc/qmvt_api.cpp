@@ -928,6 +928,28 @@ static void batch_free(qm_batch* b) {
   delete b;   // the device arrays go with it
 }
 
+// ---- the passes of a batch still in flight (include/qmvt.h at qm_batch_run) ----
+// One row per pass over a finished batch: the event it records behind its last kernel, and whether it reads the hit bitmaps and the
+// record mask qm_batch_truth_hits writes.  A new pass adds its event HERE: the wait list of everything that rewrites what passes read.
+struct PassEvent { hipEvent_t qm_batch::* ev; bool reads_hits; };
+static const PassEvent PASS_EVENTS[] = {
+    {&qm_batch::ev_motif, false}, {&qm_batch::ev_afp, false},  {&qm_batch::ev_truth, false}, {&qm_batch::ev_strata, true},
+    {&qm_batch::ev_boot, true},   {&qm_batch::ev_votes, true}, {&qm_batch::ev_nm, true},     {&qm_batch::ev_sf, false},
+    {&qm_batch::ev_cx, true},     {&qm_batch::ev_norm, false}, {&qm_batch::ev_atom, false},
+};
+// Orders what follows behind every pass of the batch still in flight, on whatever stream it was enqueued: `st` waits for the passes'
+// events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps.  An event exists once its pass has
+// been called: a batch that never ran a pass makes no HIP call here.
+static int wait_passes(qm_batch* b, hipStream_t st, bool wait_host, bool hit_readers = false) {
+  for (const PassEvent& p : PASS_EVENTS) {
+    const hipEvent_t e = b->*(p.ev);
+    if (!e || (hit_readers && !p.reads_hits)) continue;
+    if (wait_host) HIPCHK(hipEventSynchronize(e));
+    else HIPCHK(hipStreamWaitEvent(st, e, 0));
+  }
+  return QM_OK;
+}
+
 static int upload_layout(qm_batch* b) {
   const Layout& L = b->L;
   HIPCHK(hipMemcpy(b->d_vcfs, L.vcfs.data(), sizeof(VcfDesc) * L.vcfs.size(), hipMemcpyHostToDevice));
@@ -1036,6 +1058,8 @@ extern "C" int qm_batch_upload(qm_batch* b, int v, const int32_t* pos, const int
   if (d.n == 0) return QM_OK;
   if (!pos || !ref || !alt || !qual || !flags) return fail(QM_E_INVAL, "qm_batch_upload: NULL column");
   HIPCHK(hipSetDevice(b->ctx->dev));
+  const int rcw = wait_passes(b, nullptr, true);   // a pass still in flight reads the columns
+  if (rcw != QM_OK) return rcw;
   const size_t n = (size_t)d.n;
   HIPCHK(hipMemcpy(b->pos + d.off, pos, n * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(b->ref + d.off, ref, n * 4, hipMemcpyHostToDevice));
@@ -1063,6 +1087,8 @@ extern "C" int qm_batch_upload_async(qm_batch* b, int v, const int32_t* pos, con
   if (!pos || !ref || !alt || !qual || !flags) return fail(QM_E_INVAL, "qm_batch_upload_async: NULL column");
   HIPCHK(hipSetDevice(b->ctx->dev));
   hipStream_t st = stream ? (hipStream_t)stream : b->ctx->stream;
+  const int rcw = wait_passes(b, st, false);   // a pass still in flight reads the columns
+  if (rcw != QM_OK) return rcw;
   const size_t n = (size_t)d.n;
   HIPCHK(hipMemcpyAsync(b->pos + d.off, pos, n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(b->ref + d.off, ref, n * 4, hipMemcpyHostToDevice, st));
@@ -1124,6 +1150,8 @@ extern "C" int qm_batch_synth(qm_batch* b, const qm_synth_cfg* cfg) {
     a += 2;
   }
   S.perm_a = a; S.perm_b = 12345;
+  const int rcw = wait_passes(b, b->ctx->stream, false);   // a pass still in flight reads the columns
+  if (rcw != QM_OK) return rcw;
   launch_synth(S, b->n_vcf, L.max_n, b->ctx->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(b->ctx->stream));
@@ -1187,6 +1215,9 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
     if (tg.first >= (int)c->truths.size() || c->truths[(size_t)tg.first].released || c->truths[(size_t)tg.first].gen != tg.second)
       return fail(QM_E_STATE, "qm_batch_run: truth set %d was released after the batch was created", tg.first);
   const size_t gbytes = (size_t)b->n_truth * 3 * (size_t)b->n_bins * 8;   // as allocated at batch creation
+  // a pass still in flight, on whatever stream, reads the masks and rows this run rewrites (include/qmvt.h)
+  const int rcw = wait_passes(b, st, false);
+  if (rcw != QM_OK) return rcw;
   hipEvent_t* ev = b->ev[b->n_timed % qm_batch::EV_RING];
   const bool T = b->timing;
   if (T) HIPCHK(hipEventRecord(ev[0], st));
@@ -2433,7 +2464,11 @@ extern "C" int qm_batch_upload_af(qm_batch* b, int v, const float* af) {
       HIPCHK(hipStreamSynchronize(b->ctx->stream));
     }
   }
-  if (d.n > 0) HIPCHK(hipMemcpy(b->d_af + d.off, af, (size_t)d.n * sizeof(float), hipMemcpyHostToDevice));
+  if (d.n > 0) {
+    const int rcw = wait_passes(b, nullptr, true);   // a pass still in flight reads the frequencies
+    if (rcw != QM_OK) return rcw;
+    HIPCHK(hipMemcpy(b->d_af + d.off, af, (size_t)d.n * sizeof(float), hipMemcpyHostToDevice));
+  }
   b->h_afmark[(size_t)v] = 1;
   return QM_OK;
 }
@@ -3202,8 +3237,8 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
   if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
   else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
-  for (hipEvent_t e : {b->ev_strata, b->ev_boot, b->ev_votes, b->ev_nm, b->ev_cx})   // and the passes that read the hit bitmaps, on whatever stream
-    if (e) HIPCHK(hipStreamWaitEvent(st, e, 0));
+  rc = wait_passes(b, st, false, true);   // and the passes that read the hit bitmaps, on whatever stream (PASS_EVENTS)
+  if (rc != QM_OK) return rc;
   // (the one pass that does not open with pass_stream: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
   rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_intruth.grow((int64_t)mask_words, &b->dev_bytes);
