@@ -227,7 +227,7 @@ int qm_bench_synth(qm_ctx* ctx, const qm_synth_cfg* cfg, int n_vcf, int64_t reco
  * NULL it must be a device buffer of [qm_batch_n_truth(b)][3][n_bins] uint64 that
  * receives the per-truth sums (the caller all-reduces it across ranks).
  *
- * Ordering against the passes over a finished batch (qm_batch_motifs ... qm_batch_atomize below), each of which may have been
+ * Ordering against the passes over a finished batch (qm_batch_motifs ... qm_batch_types below), each of which may have been
  * enqueued on a stream of the caller's: a call that rewrites what passes read (qm_batch_run, qm_batch_upload,
  * qm_batch_upload_async, qm_batch_synth, qm_batch_upload_af) is ordered behind every pass of the batch still in flight, on
  * whatever stream.  The asynchronous ones (qm_batch_run, qm_batch_upload_async) make their stream wait for the passes' events;
@@ -610,6 +610,42 @@ int qm_batch_get_atomize(qm_batch* b, uint64_t* rec /*[n_vcf][QM_ATOM_R_COLS] or
 int qm_batch_get_atomized(qm_batch* b, int vcf, uint8_t* cls, uint8_t* n_atoms, uint16_t* hit_mask /*[n] each, or NULL*/);
 int qm_batch_atomize_timings(qm_batch* b, float* ms3);
 int qm_truth_atoms(qm_ctx* ctx, int truth_id, uint32_t* keys, int64_t capacity, int64_t* n_out);
+
+/* ---- TP, FP and FN by variant type and size (build-defined, opt-in, QM_BATCH_ALLELES batches only) ----
+ * Type and size of a variant (R, A), R != A, m = min(|R|, |A|): cp = the longest common prefix, at most m; cs = the longest common
+ *   suffix of what is left, at most m - cp (the prefix goes first); tr = |R| - cp - cs, ta = |A| - cp - cs.  tr == 0: QM_TYPE_INS
+ *   of size ta; ta == 0: QM_TYPE_DEL of size tr; tr == ta == 1: QM_TYPE_SNV of size 1; tr == ta >= 2: QM_TYPE_MNP of size tr (the
+ *   trimmed span); otherwise QM_TYPE_CPX of size max(tr, ta).  No genome takes part.
+ * Long alleles (dictionary ids) are typed through a shape table with one row per id (qm_dict_shapes): len >= 14, head = the
+ *   first QM_ALLELE_INLINE_MAX bases, tail = the last ones, 2 bits per base, base k at bits 2 k.  A pair with ONE long allele is
+ *   decided exactly by it (the other allele has at most 13 bases, so neither trim looks further).
+ * Rows: sizes are binned by n_bins (1 .. QM_TYPE_MAX_BINS) ascending lower edges, edges[0] == 1; bin b holds edges[b] <= size <
+ *   edges[b + 1], the last bin is open.  A typed variant lies in row type * n_bins + bin; four rows follow the grid, the first
+ *   that applies wins: 5 n_bins + QM_TYPE_X_NOKEY (QM_F_NOKEY or an invalid code), _NOVAR (equal codes), _LONGPAIR (both alleles
+ *   long: counted, not guessed), _NOSHAPE (a long allele without a row in the table, or no table).  n_rows = 5 n_bins + 4.
+ * rec[v][n_rows][2]: the kept records of the row, and those of them that are TP lines by the batch's own masks.
+ * tru[v][n_rows][2]: the allele-extended entries of the VCF's truth set in the row (the entries of qm_truth_entries; never in
+ *   NOKEY), and those of them spelled like a kept record with valid codes and no QM_F_NOKEY (QM_ATOM_T_FOUND by another route).
+ * With QM_TYPE_COLUMNS the pass also keeps the row of every record, kept or not, as one byte.
+ * qm_batch_types: asynchronous on `stream` (NULL = the context's own) but for the small blocking copies of the table and the
+ *   descriptors; the shape arrays are read during the call only (NULL / n_shapes = 0: no table).  QM_E_INVAL for edges that do
+ *   not ascend from 1, n_bins outside 1 .. QM_TYPE_MAX_BINS and a shape row with len < 14; QM_E_STATE unless the latest
+ *   qm_batch_run was finished, for a batch without QM_BATCH_ALLELES, and for a released truth set.  The first call allocates the
+ *   outputs (qm_batch_device_bytes).
+ * qm_batch_get_types / qm_batch_get_typed: wait for the pass, then copy ([n_vcf][n_rows][2] with the n_rows of the latest call;
+ *   either pointer may be NULL).  QM_E_STATE if the batch ran since, and for row bytes the latest call did not keep
+ *   (QM_TYPE_COLUMNS).
+ * qm_batch_types_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] k_type_records, [1] k_type_truth. */
+#define QM_TYPE_MAX_BINS 16
+#define QM_TYPE_MAX_ROWS 84
+#define QM_TYPE_COLUMNS 2u
+enum { QM_TYPE_SNV = 0, QM_TYPE_MNP = 1, QM_TYPE_INS = 2, QM_TYPE_DEL = 3, QM_TYPE_CPX = 4 };
+enum { QM_TYPE_X_NOKEY = 0, QM_TYPE_X_NOVAR = 1, QM_TYPE_X_LONGPAIR = 2, QM_TYPE_X_NOSHAPE = 3 };
+int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t* len, const uint32_t* head, const uint32_t* tail,
+                   int64_t n_shapes, unsigned what /*0 or QM_TYPE_COLUMNS*/, void* stream);
+int qm_batch_get_types(qm_batch* b, uint64_t* rec /*[n_vcf][n_rows][2] or NULL*/, uint64_t* tru /*[n_vcf][n_rows][2] or NULL*/);
+int qm_batch_get_typed(qm_batch* b, int vcf, uint8_t* row /*[n]*/);
+int qm_batch_types_timings(qm_batch* b, float* ms2);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -731,6 +767,9 @@ int64_t qm_dict_size(qm_dict* d);
 int32_t qm_allele_code(qm_dict* d, const uint8_t* s, size_t n);
 /* spelling of a code into out[cap]; returns its length, -1 if the code is no allele / does not fit */
 int64_t qm_allele_spell(qm_dict* d, int32_t code, uint8_t* out, size_t cap);
+/* The shape rows of ids first .. first + cap - 1 (as far as the dictionary holds them) for qm_batch_types: the allele's length,
+ * its first QM_ALLELE_INLINE_MAX bases and its last ones, 2 bits per base, base k at bits 2 k.  Returns the rows written. */
+int64_t qm_dict_shapes(qm_dict* d, int64_t first, int64_t cap, int32_t* len, uint32_t* head, uint32_t* tail);
 int qm_vcf_scan_ext(const uint8_t* text, size_t len, int64_t cap_lines, int64_t* line_off, uint8_t* line_kind,
                     int32_t* pos, int32_t* ref, int32_t* alt, float* qual, uint8_t* flags, qm_vcf_cols* info,
                     qm_dict* dict);
@@ -1012,6 +1051,23 @@ typedef struct qm_atomize_args {
 int qm_extract_files_atomize(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                              qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                              void* global_dev, const qm_atomize_args* atomize);
+
+/* qm_extract_files_ex plus the variant-type pass over its batch; mode must be QM_BATCH_ALLELES (QM_E_STATE
+ * otherwise).  The shape table is built from the call's own dictionary once every file is tokenised.  Mixed-sample jobs with
+ * want[j] != 0 get their rows rec[j][n_rows][2] and tru[j][n_rows][2] of qm_batch_get_types (n_rows = 5 n_bins + 4); the others,
+ * pure-strain jobs among them, get zero rows.  The VCF outputs, stats and roc are those of qm_extract_files_ex.  Combines with
+ * none of the other opt-in views. */
+typedef struct qm_types_args {
+  const int32_t* edges;             /* [n_bins] */
+  int32_t n_bins;
+  int32_t reserved;
+  const uint8_t* want;              /* [n_jobs] */
+  uint64_t* rec;                    /* [n_jobs][5 n_bins + 4][2] */
+  uint64_t* tru;                    /* [n_jobs][5 n_bins + 4][2] */
+} qm_types_args;
+int qm_extract_files_types(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                           qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                           void* global_dev, const qm_types_args* types);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

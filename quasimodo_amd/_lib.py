@@ -58,6 +58,11 @@ QM_NORM_COLUMNS = 2
 QM_ATOM_R_COLS = 13
 QM_ATOM_T_COLS = 6
 QM_ATOM_COLUMNS = 2
+QM_TYPE_MAX_BINS = 16
+QM_TYPE_MAX_ROWS = 84
+QM_TYPE_COLUMNS = 2
+QM_TYPE_SNV, QM_TYPE_MNP, QM_TYPE_INS, QM_TYPE_DEL, QM_TYPE_CPX = range(5)
+QM_TYPE_X_NOKEY, QM_TYPE_X_NOVAR, QM_TYPE_X_LONGPAIR, QM_TYPE_X_NOSHAPE = range(4)
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -85,6 +90,7 @@ EXPORTS = (
     "qm_extract_files_context",
     "qm_batch_normalize", "qm_batch_get_normalize", "qm_batch_get_normalized", "qm_batch_normalize_timings", "qm_truth_normalized", "qm_truth_entries", "qm_extract_files_normalize",
     "qm_batch_atomize", "qm_batch_get_atomize", "qm_batch_get_atomized", "qm_batch_atomize_timings", "qm_truth_atoms", "qm_extract_files_atomize",
+    "qm_dict_shapes", "qm_batch_types", "qm_batch_get_types", "qm_batch_get_typed", "qm_batch_types_timings", "qm_extract_files_types",
 )
 
 
@@ -156,6 +162,11 @@ class AtomizeArgs(C.Structure):
     _fields_ = [("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("atoms_out", C.POINTER(C.c_char_p))]
 
 
+class TypesArgs(C.Structure):
+    """include/qmvt.h qm_types_args"""
+    _fields_ = [("edges", C.c_void_p), ("n_bins", C.c_int32), ("reserved", C.c_int32), ("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p)]
+
+
 class ContextArgs(C.Structure):
     """include/qmvt.h qm_context_args"""
     _fields_ = [("w", C.c_int32), ("ng", C.c_int32), ("genome_id", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("gen", C.c_void_p)]
@@ -181,7 +192,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -407,6 +418,14 @@ def lib():
     L.qm_batch_get_atomized.argtypes = [vp, i32, vp, vp, vp]
     L.qm_batch_atomize_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_truth_atoms.argtypes = [vp, i32, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.qm_dict_shapes.argtypes = [vp, i64, i64, vp, vp, vp]
+    L.qm_dict_shapes.restype = i64
+    L.qm_batch_types.argtypes = [vp, vp, i32, vp, vp, vp, i64, C.c_uint, vp]
+    L.qm_batch_get_types.argtypes = [vp, vp, vp]
+    L.qm_batch_get_typed.argtypes = [vp, i32, vp]
+    L.qm_batch_types_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_extract_files_types.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                         C.POINTER(TypesArgs)]
     _lib = L
     return L
 

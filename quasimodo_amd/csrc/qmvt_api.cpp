@@ -33,6 +33,7 @@
 #include "qmvt_surface.h"
 #include "qmvt_norm.h"
 #include "qmvt_atom.h"
+#include "qmvt_types.h"
 
 using namespace qm;
 
@@ -884,6 +885,18 @@ struct qm_batch {
   hipEvent_t ev_att[4] = {};          // qm_batch_set_timing: around the set builds, k_atom_records, k_atom_found
   bool at_timed = false;              // the latest qm_batch_atomize recorded them
   unsigned at_made = 0;               // 1 | QM_ATOM_COLUMNS: what the latest qm_batch_atomize made behind the latest run
+  // qm_batch_types (lazy): the per-VCF descriptors and the pass's own found bitmaps, [n_vcf][n_rows][2] counts of
+  // records and of truth entries, the shape table ([3][n]: len, head, tail) and, on request, a row byte per record; ev_types
+  // says when the pass is done
+  DevBuf<uint32_t> ty_bits, ty_shapes;
+  DevBuf<TypeVcf> ty_vcfs;
+  DevBuf<uint64_t> ty_rec, ty_tru;
+  DevBuf<uint8_t> ty_row;             // [n_pad]
+  hipEvent_t ev_types = nullptr;
+  hipEvent_t ev_tyt[3] = {};          // qm_batch_set_timing: around k_type_records and k_type_truth
+  bool ty_timed = false;              // the latest qm_batch_types recorded them
+  int32_t ty_rows = 0;                // n_rows of the latest qm_batch_types
+  unsigned ty_made = 0;               // 1 | QM_TYPE_COLUMNS: what the latest qm_batch_types made behind the latest run
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -920,6 +933,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_nzt) if (e) (void)hipEventDestroy(e);
   if (b->ev_atom) (void)hipEventDestroy(b->ev_atom);
   for (auto& e : b->ev_att) if (e) (void)hipEventDestroy(e);
+  if (b->ev_types) (void)hipEventDestroy(b->ev_types);
+  for (auto& e : b->ev_tyt) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -936,6 +951,7 @@ static const PassEvent PASS_EVENTS[] = {
     {&qm_batch::ev_motif, false}, {&qm_batch::ev_afp, false},  {&qm_batch::ev_truth, false}, {&qm_batch::ev_strata, true},
     {&qm_batch::ev_boot, true},   {&qm_batch::ev_votes, true}, {&qm_batch::ev_nm, true},     {&qm_batch::ev_sf, false},
     {&qm_batch::ev_cx, true},     {&qm_batch::ev_norm, false}, {&qm_batch::ev_atom, false},
+    {&qm_batch::ev_types, false},
 };
 // Orders what follows behind every pass of the batch still in flight, on whatever stream it was enqueued: `st` waits for the passes'
 // events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps.  An event exists once its pass has
@@ -1286,6 +1302,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->cx_made = 0;
   b->nz_made = 0;
   b->at_made = 0;
+  b->ty_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -3138,6 +3155,131 @@ extern "C" int qm_truth_atoms(qm_ctx* c, int truth_id, uint32_t* keys, int64_t c
   *n_out = (int64_t)h.size();
   if ((int64_t)h.size() > capacity) return fail(QM_E_RANGE, "qm_truth_atoms: %zu atoms, room for %lld", h.size(), (long long)capacity);
   if (keys && !h.empty()) memcpy(keys, h.data(), h.size() * 4);
+  return QM_OK;
+}
+// ---- TP, FP and FN by variant type and size ----
+extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t* len, const uint32_t* head, const uint32_t* tail,
+                              int64_t n_shapes, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_types");
+  if (what & ~QM_TYPE_COLUMNS) return fail(QM_E_INVAL, "qm_batch_types: what = %u", what);
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_types: a single-base batch holds SNVs only, there is nothing to type (create the batch with QM_BATCH_ALLELES)");
+  if (!edges || n_bins < 1 || n_bins > QM_TYPE_MAX_BINS) return fail(QM_E_INVAL, "qm_batch_types: %d size bins (1 to %d)", n_bins, QM_TYPE_MAX_BINS);
+  if (edges[0] != 1) return fail(QM_E_INVAL, "qm_batch_types: the first size edge is %d (it must be 1)", edges[0]);
+  for (int i = 1; i < n_bins; ++i)
+    if (edges[i] <= edges[i - 1]) return fail(QM_E_INVAL, "qm_batch_types: size edge %d is %d behind %d (the edges ascend)", i, edges[i], edges[i - 1]);
+  if (n_shapes < 0 || n_shapes > 0x40000000ll || (n_shapes > 0 && (!len || !head || !tail))) return fail(QM_E_INVAL, "qm_batch_types: %lld shape rows (NULL arrays?)", (long long)n_shapes);
+  for (int64_t i = 0; i < n_shapes; ++i)
+    if (len[i] <= QM_ALLELE_INLINE_MAX)
+      return fail(QM_E_INVAL, "qm_batch_types: shape row %lld has len %d (a dictionary id names an allele of at least %d bases)", (long long)i, len[i], QM_ALLELE_INLINE_MAX + 1);
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  int rc = truths_live(b, "qm_batch_types");
+  if (rc != QM_OK) return rc;
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_types, &st);
+  if (rc != QM_OK) return rc;
+  b->ty_made = 0;   // from here on the outputs are rewritten
+  TypeBins B;
+  memset(&B, 0, sizeof B);
+  for (int i = 0; i < n_bins; ++i) B.edges[i] = edges[i];
+  B.n_bins = n_bins;
+  B.n_rows = TYPE_KINDS * n_bins + TYPE_OFFGRID;
+  const size_t cells = 2 * (size_t)B.n_rows, np = (size_t)b->L.n_pad, ns = (size_t)n_shapes;
+  size_t bit_words = 0;
+  int64_t max_entries = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    const int64_t xn = c->truths[(size_t)b->L.vcfs[v].truth].xn;
+    bit_words += (size_t)(xn / 32 + 1);
+    max_entries = std::max(max_entries, xn);
+  }
+  rc = b->ty_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->ty_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->ty_rec.grow((int64_t)std::max<size_t>(nv * 2 * TYPE_MAX_ROWS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->ty_tru.grow((int64_t)std::max<size_t>(nv * 2 * TYPE_MAX_ROWS, 1), &b->dev_bytes);
+  if (rc == QM_OK && ns) rc = b->ty_shapes.grow((int64_t)(3 * ns), &b->dev_bytes);
+  if (rc == QM_OK && (what & QM_TYPE_COLUMNS)) rc = b->ty_row.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_tyt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->ty_timed = false;
+  std::vector<TypeVcf> vcfs(std::max<size_t>(nv, 1));
+  memset(vcfs.data(), 0, vcfs.size() * sizeof(TypeVcf));
+  size_t bo = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    const Truth& t = c->truths[(size_t)b->L.vcfs[v].truth];
+    vcfs[v].xkeys = t.d_xkeys; vcfs[v].xref = t.d_xref; vcfs[v].xalt = t.d_xalt; vcfs[v].xn = t.xn;
+    vcfs[v].ebits = b->ty_bits + bo;
+    bo += (size_t)(t.xn / 32 + 1);
+  }
+  // blocking copies: vcfs dies here, and the caller's shape arrays are read during the call only (the previous call of the pass
+  // is done: pass_stream waited for it)
+  if (nv) HIPCHK(hipMemcpy(b->ty_vcfs, vcfs.data(), nv * sizeof(TypeVcf), hipMemcpyHostToDevice));
+  TypeShapes S;
+  memset(&S, 0, sizeof S);
+  if (ns) {
+    uint32_t* d = b->ty_shapes;
+    HIPCHK(hipMemcpy(d, len, ns * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + ns, head, ns * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + 2 * ns, tail, ns * 4, hipMemcpyHostToDevice));
+    S.len = reinterpret_cast<const int32_t*>(d); S.head = d + ns; S.tail = d + 2 * ns; S.n = n_shapes;
+  }
+  HIPCHK(hipMemsetAsync(b->ty_bits, 0, std::max<size_t>(bit_words, 1) * 4, st));
+  HIPCHK(hipMemsetAsync(b->ty_rec, 0, std::max<size_t>(nv * cells, 1) * 8, st));
+  HIPCHK(hipMemsetAsync(b->ty_tru, 0, std::max<size_t>(nv * cells, 1) * 8, st));
+  if (what & QM_TYPE_COLUMNS) HIPCHK(hipMemsetAsync(b->ty_row, 0, std::max<size_t>(np, 1), st));
+  if (T) HIPCHK(hipEventRecord(b->ev_tyt[0], st));
+  TypeRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.vcfs = b->ty_vcfs;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  if (what & QM_TYPE_COLUMNS) P.row = b->ty_row;
+  P.rec = b->ty_rec;
+  P.shapes = S; P.bins = B;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_type_records(P, st);
+  HIPCHK(hipGetLastError());
+  if (T) HIPCHK(hipEventRecord(b->ev_tyt[1], st));
+  TypeTruthParams Q;
+  memset(&Q, 0, sizeof Q);
+  Q.vcfs = b->ty_vcfs; Q.tru = b->ty_tru; Q.shapes = S; Q.bins = B;
+  launch_type_truth(Q, (int)nv, max_entries, st);
+  HIPCHK(hipGetLastError());
+  if (T) { HIPCHK(hipEventRecord(b->ev_tyt[2], st)); b->ty_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_types, st));
+  b->ty_rows = B.n_rows;
+  b->ty_made = 1u | what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_types(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_types: NULL batch");
+  if (!b->ty_made) return fail(QM_E_STATE, "qm_batch_get_types: no qm_batch_types behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_types));
+  const size_t bytes = (size_t)b->n_vcf * 2 * (size_t)b->ty_rows * 8;
+  if (rec && bytes) HIPCHK(hipMemcpy(rec, b->ty_rec, bytes, hipMemcpyDeviceToHost));
+  if (tru && bytes) HIPCHK(hipMemcpy(tru, b->ty_tru, bytes, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_typed(qm_batch* b, int v, uint8_t* row) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_typed: NULL batch");
+  if (!b->ty_made) return fail(QM_E_STATE, "qm_batch_get_typed: no qm_batch_types behind the latest run");
+  if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_typed: VCF %d (the batch has %d)", v, b->n_vcf);
+  if (!(b->ty_made & QM_TYPE_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_get_typed: the latest qm_batch_types did not keep the row bytes (QM_TYPE_COLUMNS)");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_types));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  if (d.n && row) HIPCHK(hipMemcpy(row, b->ty_row + d.off, (size_t)d.n, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_types_timings(qm_batch* b, float* ms2) {
+  if (!b || !ms2) return fail(QM_E_INVAL, "qm_batch_types_timings: NULL");
+  if (!b->ty_made) return fail(QM_E_STATE, "qm_batch_types_timings: no qm_batch_types behind the latest run");
+  if (!b->ty_timed) return fail(QM_E_STATE, "qm_batch_types_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_tyt[2]));
+  for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(ms2 + i, b->ev_tyt[i], b->ev_tyt[i + 1]));
   return QM_OK;
 }
 // paired block-bootstrap replicates of the finished batch's counts

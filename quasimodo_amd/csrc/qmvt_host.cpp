@@ -690,6 +690,25 @@ extern "C" int64_t qm_allele_spell(qm_dict* d, int32_t code, uint8_t* out, size_
   }
   return -1;
 }
+// the shape rows of the variant-type pass: length, first 13 bases, last 13 bases of ids first .. first + cap - 1
+extern "C" int64_t qm_dict_shapes(qm_dict* d, int64_t first, int64_t cap, int32_t* len, uint32_t* head, uint32_t* tail) {
+  if (!d || first < 0 || cap <= 0 || !len || !head || !tail) return 0;
+  std::lock_guard<std::mutex> g(d->mu);
+  const int64_t n = std::min<int64_t>(cap, (int64_t)d->strings.size() - first);
+  for (int64_t i = 0; i < n; ++i) {
+    const std::string& s = d->strings[(size_t)(first + i)];
+    const size_t k = std::min<size_t>(s.size(), (size_t)QM_ALLELE_INLINE_MAX);
+    uint32_t h = 0, t = 0;
+    for (size_t j = 0; j < k; ++j) {
+      h |= (uint32_t)base_code((uint8_t)s[j]) << (2 * j);
+      t |= (uint32_t)base_code((uint8_t)s[s.size() - k + j]) << (2 * j);
+    }
+    len[i] = (int32_t)s.size();
+    head[i] = h;
+    tail[i] = t;
+  }
+  return std::max<int64_t>(n, 0);
+}
 
 extern "C" int64_t qm_truth_scan(const uint8_t* text, size_t len, int mode, int64_t cap, int32_t* pos, int32_t* ref, int32_t* alt,
                                  int64_t* out_counts) {

@@ -299,7 +299,7 @@ struct Passes {
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
-  const qm_atomize_args* at = nullptr;
+  const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -319,6 +319,7 @@ struct PassCtx {
   const std::vector<JobState>& J; const std::vector<TruthState>& T;
   size_t nv;   // VCFs in the batch
   bool ext; int nthr;
+  qm_dict* dict;   // the long alleles of the call's files (allele-extended calls), complete once stage one is
   // the one rule for errors: a pass that fails sets err
   int lib(int rc, std::string& err) const { if (rc != QM_OK) err = qm_last_error(ctx); return rc; }
   template <typename W> bool any(W want) const { for (int j = 0; j < n_jobs; ++j) if (want(j)) return true; return false; }
@@ -814,6 +815,26 @@ int atomize_pass(const PassCtx& c, const Passes& P, std::string& err) {
   return QM_OK;
 }
 
+// TP, FP and FN by variant type and size: the shape table from the call's dictionary, the rows of every wanted
+// mixed-sample job (a pure-strain job has no truth set to be measured against: its rows stay zero)
+int types_pass(const PassCtx& c, const qm_types_args* ty, std::string& err) {
+  if (!ty) return QM_OK;
+  auto want = [&](int j) { return ty->want[j] != 0 && !c.jobs[j].pure; };
+  if (!c.any(want)) return QM_OK;
+  const int64_t ns = c.dict ? qm_dict_size(c.dict) : 0;
+  std::vector<int32_t> len((size_t)ns);
+  std::vector<uint32_t> head((size_t)ns), tail((size_t)ns);
+  const int64_t got = ns ? qm_dict_shapes(c.dict, 0, ns, len.data(), head.data(), tail.data()) : 0;
+  const size_t w = 2 * (size_t)(5 * ty->n_bins + 4);
+  std::vector<uint64_t> rec(c.nv * w), tru(c.nv * w);
+  int rc = qm_batch_types(c.batch, ty->edges, ty->n_bins, len.data(), head.data(), tail.data(), got, 0u, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_types(c.batch, rec.data(), tru.data());
+  if (rc != QM_OK) return c.lib(rc, err);
+  c.scatter_rows(ty->rec, rec, w, want);
+  c.scatter_rows(ty->tru, tru, w, want);
+  return QM_OK;
+}
+
 // the filter surface: S and extra of every wanted job
 int surface_pass(const PassCtx& c, const qm_surface_args* sf, std::string& err) {
   auto want = [&](int j) { return sf->want[j] != 0; };
@@ -968,6 +989,28 @@ extern "C" int qm_extract_files_atomize(qm_ctx* ctx, int n_jobs, const qm_file_j
     memset(at->tru, 0, sizeof(uint64_t) * QM_ATOM_T_COLS * (size_t)n_jobs);
   }
   Passes P; P.at = at;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// TP, FP and FN by variant type and size behind the worker
+extern "C" int qm_extract_files_types(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                      qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                      int n_slots, void* global_dev, const qm_types_args* types) {
+  const qm_types_args* ty = types;
+  if (!ty || !ty->edges || (n_jobs > 0 && (!ty->want || !ty->rec || !ty->tru))) return fail(QM_E_INVAL, "qm_extract_files_types: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_types: variants are typed by their alleles, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (ty->n_bins < 1 || ty->n_bins > QM_TYPE_MAX_BINS)
+    return fail(QM_E_INVAL, "qm_extract_files_types: " + std::to_string(ty->n_bins) + " size bins (1 to " + std::to_string(QM_TYPE_MAX_BINS) + ")");
+  for (int i = 0; i < ty->n_bins; ++i)
+    if (i == 0 ? ty->edges[0] != 1 : ty->edges[i] <= ty->edges[i - 1])
+      return fail(QM_E_INVAL, "qm_extract_files_types: the size edges ascend from 1 (edge " + std::to_string(i) + " is " + std::to_string(ty->edges[i]) + ")");
+  if (n_jobs > 0) {
+    const size_t w = 2 * (size_t)(5 * ty->n_bins + 4);
+    memset(ty->rec, 0, sizeof(uint64_t) * w * (size_t)n_jobs);
+    memset(ty->tru, 0, sizeof(uint64_t) * w * (size_t)n_jobs);
+  }
+  Passes P; P.ty = ty;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -1317,7 +1360,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       }
       if (rc != QM_OK) err = qm_last_error(ctx);
       // the passes, on the columns, masks and truth keys the classification leaves in HBM; the one that fails sets err
-      const PassCtx pc{ctx, batch, n_jobs, jobs, J, T, nrec.size(), ext, nthr};
+      const PassCtx pc{ctx, batch, n_jobs, jobs, J, T, nrec.size(), ext, nthr, dict};
       if (rc == QM_OK) rc = motifs_pass(pc, P, err);
       if (rc == QM_OK) rc = profile_pass(pc, P.pa, err);
       if (rc == QM_OK) rc = strata_pass(pc, P.sa, err);
@@ -1328,6 +1371,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = context_pass(pc, P, err);
       if (rc == QM_OK) rc = normalize_pass(pc, P, err);
       if (rc == QM_OK) rc = atomize_pass(pc, P, err);
+      if (rc == QM_OK) rc = types_pass(pc, P.ty, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

@@ -1,0 +1,182 @@
+// qmvt_types.hip -- TP, FP and FN by variant type and size: every record of a finished allele-extended batch and
+// every entry of its truth sets is typed SNV, MNP, INS, DEL or CPX from its two allele codes -- the common prefix, then the common
+// suffix of what is left, are trimmed; what remains names the type and the size --, binned by size and counted per VCF.
+// k_type_records streams the batch in input order, counts the kept records and the TP lines among them per row and marks the
+// truth entries spelled like a kept record; k_type_truth counts the entries and the marked ones per row.  Alleles of more than 13
+// bases are dictionary ids: a table of (length, first 13 bases, last 13 bases) per id decides every pair with ONE long allele.
+// Integer work only: no output depends on the order the lanes run in.  Its own translation unit: qm_kernels_id
+// (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
+#include "qmvt_types.h"
+
+#include <algorithm>
+
+namespace qm {
+
+typedef int vt_int4 __attribute__((ext_vector_type(4)));
+
+// inline codes (include/qmvt.h): 0 .. 3 one base, len << 26 | bases for 2 .. 13 bases
+__device__ inline bool vt_inline(int32_t c) {
+  const uint32_t u = (uint32_t)c;
+  return u < 4u || (u - (2u << 26)) < (12u << 26);
+}
+
+// bit 2 k: field k of the two words differs
+__device__ inline uint32_t vt_diff(uint32_t x, uint32_t y) {
+  const uint32_t d = x ^ y;
+  return (d | d >> 1) & 0x1555555u;
+}
+
+// The row of the variant (r, a): TYPE_KINDS * n_bins + the first off-grid reason that applies, else type * n_bins + bin.
+// What the trimming reads of an allele: its length, the word of its first bases and the word of its last `e` ones (base k at bits
+// 2 k in both).  An inline code is both words itself; a long allele takes them from its row of the shape table.
+__device__ inline uint32_t vt_row(int32_t r, int32_t a, bool nokey, const TypeShapes& S, const TypeBins& B) {
+  const uint32_t off = (uint32_t)(TYPE_KINDS * B.n_bins);
+  if (nokey || !allele_valid(r) || !allele_valid(a)) return off + TYPE_NOKEY;
+  if (r == a) return off + TYPE_NOVAR;
+  const bool long_r = !vt_inline(r), long_a = !vt_inline(a);
+  if (long_r && long_a) return off + TYPE_LONGPAIR;
+  const uint32_t ur = (uint32_t)r, ua = (uint32_t)a;
+  uint32_t len_r = ur < 4u ? 1u : ur >> 26, len_a = ua < 4u ? 1u : ua >> 26;   // (of the inline ones)
+  uint32_t head_r = ur & 0x03ffffffu, head_a = ua & 0x03ffffffu;
+  uint32_t tail_r = head_r, tail_a = head_a, e_r = len_r, e_a = len_a;
+  if (long_r || long_a) {
+    // (a valid code under the dictionary's base is no inline code and no id: it has no row either)
+    const uint32_t u = long_r ? ur : ua;
+    const int64_t id = u >= 0x40000000u ? (int64_t)(u & 0x3fffffffu) : S.n;
+    if (id >= S.n) return off + TYPE_NOSHAPE;
+    const uint32_t len = (uint32_t)S.len[id], head = S.head[id] & 0x03ffffffu, tail = S.tail[id] & 0x03ffffffu;
+    len_r = long_r ? len : len_r; head_r = long_r ? head : head_r; tail_r = long_r ? tail : tail_r; e_r = long_r ? TYPE_LONG_HEAD : e_r;
+    len_a = long_a ? len : len_a; head_a = long_a ? head : head_a; tail_a = long_a ? tail : tail_a; e_a = long_a ? TYPE_LONG_HEAD : e_a;
+  }
+  // at most one allele is long, so m <= 13: neither count looks past the 13 bases a word holds
+  const uint32_t m = min(len_r, len_a);
+  const uint32_t fields = (1u << (2u * m)) - 1u;
+  const uint32_t cp = (uint32_t)__builtin_ctz((vt_diff(head_r, head_a) & fields) | (1u << (2u * m))) >> 1;
+  // the last m bases of either allele, base k of them at bits 2 k: equal fields are counted from the top
+  const uint32_t ds = vt_diff(tail_r >> (2u * (e_r - m)), tail_a >> (2u * (e_a - m))) & fields;
+  const uint32_t cs = min(ds ? (uint32_t)__builtin_clz(ds << (32u - 2u * m)) >> 1 : m, m - cp);   // the prefix went first
+  const uint32_t tr = len_r - cp - cs, ta = len_a - cp - cs;
+  const uint32_t type = tr == 0u ? TYPE_INS : ta == 0u ? TYPE_DEL : tr != ta ? TYPE_CPX : tr == 1u ? TYPE_SNV : TYPE_MNP;
+  const uint32_t size = max(tr, ta);
+  uint32_t bin = 0u;
+#pragma unroll
+  for (int i = 1; i < TYPE_MAX_BINS; ++i) bin += (i < B.n_bins && size >= (uint32_t)B.edges[i]) ? 1u : 0u;
+  return type * (uint32_t)B.n_bins + bin;
+}
+
+// the index of the entry spelled (p, r, a) in the truth set's sorted table, or -1 (0 <= p < 2^28: the caller's duty)
+__device__ inline int64_t vt_entry(const TypeVcf& V, int32_t p, int32_t r, int32_t a) {
+  const uint32_t key = ((uint32_t)p << 4) | allele_nib(r, a);
+  int64_t lo = 0, hi = V.xn;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const uint32_t k = V.xkeys[mid];
+    bool less = k < key;
+    if (k == key) {
+      const int32_t rr = V.xref[mid];
+      less = rr < r || (rr == r && V.xalt[mid] < a);
+    }
+    if (less) lo = mid + 1; else hi = mid;
+  }
+  return lo < V.xn && V.xkeys[lo] == key && V.xref[lo] == r && V.xalt[lo] == a ? lo : -1;
+}
+
+// One workgroup per TYPE_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte accesses).  Every kept
+// record adds one to its row's cell of the workgroup's LDS histogram (a TP line one more to the cell beside it): one LDS atomic
+// per count, no reduction over the wave (DESIGN.md 4.19 says why).  The histogram goes to the VCF's rows when the VCF changes.
+__global__ __launch_bounds__(256) void k_type_records(TypeRecParams P) {
+  __shared__ uint32_t hist[2 * TYPE_MAX_ROWS];   // at most TYPE_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  if (threadIdx.x < 2 * TYPE_MAX_ROWS) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  const int cells = 2 * P.bins.n_rows;
+  const int s0 = blockIdx.x * TYPE_SPANS;
+  const int s1 = min(s0 + TYPE_SPANS, P.n_spans);
+  int cur = -1;
+  auto flush = [&]() {   // (uniform over the workgroup)
+    __syncthreads();
+    if ((int)threadIdx.x < cells && hist[threadIdx.x]) {
+      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * cells + threadIdx.x), (unsigned long long)hist[threadIdx.x]);
+      hist[threadIdx.x] = 0u;
+    }
+    __syncthreads();
+  };
+  for (int s = s0; s < s1; ++s) {
+    const SpanDesc sd = P.spans[s];
+    if (sd.vcf != cur) {
+      if (cur >= 0) flush();
+      cur = sd.vcf;
+    }
+    const TypeVcf& V = P.vcfs[cur];
+    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
+      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
+      if (g >= sd.end) continue;
+      const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (bits and columns past the VCF's last record are not defined)
+      const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & 15u;
+      const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
+      const vt_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.pos + g));   // read once
+      const vt_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.ref + g));
+      const vt_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.alt + g));
+      const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
+      uint32_t row4 = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= nrec) continue;
+        const bool kept = (kb >> k) & 1u, tp = (tb >> k) & 1u, nokey = ((f4 >> (8 * k)) & QMF_NOKEY) != 0u;
+        const int32_t p = p4[k], r = r4[k], a = a4[k];
+        const uint32_t row = vt_row(r, a, nokey, P.shapes, P.bins);
+        row4 |= row << (8 * k);
+        if (!kept) continue;
+        atomicAdd(hist + 2u * row, 1u);
+        if (tp) atomicAdd(hist + 2u * row + 1u, 1u);
+        if (!nokey && allele_valid(r) && allele_valid(a) && (uint32_t)p < (1u << 28)) {
+          const int64_t e = vt_entry(V, p, r, a);
+          if (e >= 0) {
+            const uint32_t bit = 1u << ((uint32_t)e & 31u);
+            if (!(V.ebits[e >> 5] & bit)) atomicOr(V.ebits + (e >> 5), bit);   // (a stale read only repeats the atomic)
+          }
+        }
+      }
+      if (P.row) *reinterpret_cast<uint32_t*>(P.row + g) = row4;
+    }
+  }
+  if (cur >= 0) flush();
+}
+
+// grid (x, VCF), a lane per entry of the VCF's truth set: its row, and whether k_type_records marked it
+__global__ __launch_bounds__(256) void k_type_truth(TypeTruthParams P) {
+  __shared__ uint32_t hist[2 * TYPE_MAX_ROWS];
+  if (threadIdx.x < 2 * TYPE_MAX_ROWS) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  const TypeVcf& V = P.vcfs[blockIdx.y];
+  const int cells = 2 * P.bins.n_rows;
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < V.xn) {
+    const uint32_t row = vt_row(V.xref[j], V.xalt[j], false, P.shapes, P.bins);
+    atomicAdd(hist + 2u * row, 1u);
+    if ((V.ebits[j >> 5] >> ((uint32_t)j & 31u)) & 1u) atomicAdd(hist + 2u * row + 1u, 1u);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < cells && hist[threadIdx.x])
+    atomicAdd(reinterpret_cast<unsigned long long*>(P.tru + (int64_t)blockIdx.y * cells + threadIdx.x), (unsigned long long)hist[threadIdx.x]);
+}
+
+void launch_type_records(const TypeRecParams& P, hipStream_t st) {
+  if (P.n_spans <= 0) return;
+  const dim3 grid((unsigned)((P.n_spans + TYPE_SPANS - 1) / TYPE_SPANS));
+  hipLaunchKernelGGL(k_type_records, grid, dim3(256), 0, st, P);
+}
+
+void launch_type_truth(const TypeTruthParams& P, int n_vcf, int64_t max_entries, hipStream_t st) {
+  if (max_entries <= 0) return;
+  const unsigned gx = (unsigned)((max_entries + 255) / 256);
+  for (int v0 = 0; v0 < n_vcf; v0 += 65535) {   // (the y dimension of a grid holds 65535 blocks)
+    const int nv = std::min(n_vcf - v0, 65535);
+    TypeTruthParams Q = P;
+    Q.vcfs = P.vcfs + v0;
+    Q.tru = P.tru + (int64_t)v0 * 2 * P.bins.n_rows;
+    hipLaunchKernelGGL(k_type_truth, dim3(gx, (unsigned)nv), dim3(256), 0, st, Q);
+  }
+}
+
+}  // namespace qm

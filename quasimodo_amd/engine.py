@@ -236,7 +236,7 @@ class Engine:
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
                       truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
-                      atomize=None):
+                      atomize=None, vartype=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -276,19 +276,23 @@ class Engine:
         atomize: {"want": [0/1 per job], "atoms": [path or None per job]} -- qm_extract_files_atomize (alleles=True
         only): wanted rows gain `atom_rec` ([13] uint64, columns atomize.R_COLS) and `atom_tru` ([6], atomize.T_COLS); the atoms
         files are written.
+        vartype: {"want": [0/1 per job], "edges": None or the size edges} -- qm_extract_files_types (alleles=True
+        only): wanted mixed-sample rows gain `type_rec` and `type_tru` ([n_rows][2] uint64, rows vartype.row_names(edges)) and
+        `type_edges`.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_atomize, check_normalize, check_shared_call
+        from .passes import check_atomize, check_normalize, check_shared_call, check_vartype
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "vartype": vartype, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_atomize({name for name, spec in specs.items() if spec is not None}, alleles)
+        check_vartype({name for name, spec in specs.items() if spec is not None}, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -408,6 +412,21 @@ class Engine:
         aa.keep = (awant, out_arr)   # (read during the call; the other arrays live in unpack)
         unpack = lambda k: {"atom_rec": arec[k].copy(), "atom_tru": atru[k].copy()} if awant[k] else {}
         return self._L.qm_extract_files_atomize, (C.byref(aa),), unpack
+
+    def _files_vartype(self, n, vartype, file_jobs=(), **kw):
+        from .vartype import check_edges, n_rows
+        edges = check_edges(vartype.get("edges"))
+        twant = _c([int(bool(w)) for w in vartype["want"]] or [0], np.uint8)
+        if n and twant.shape[0] != n:
+            raise ValueError("vartype: %d want entries for %d jobs" % (len(vartype["want"]), n))
+        e = _c(edges, np.int32)
+        trec = np.zeros((max(n, 1), n_rows(edges), 2), np.uint64)
+        ttru = np.zeros((max(n, 1), n_rows(edges), 2), np.uint64)
+        ta = _lib.TypesArgs(_p(e), len(edges), 0, _p(twant), _p(trec), _p(ttru))
+        ta.keep = (e, twant)   # (read during the call; the other arrays live in unpack)
+        took = lambda k: twant[k] and not file_jobs[k].get("pure")
+        unpack = lambda k: {"type_rec": trec[k].copy(), "type_tru": ttru[k].copy(), "type_edges": edges} if took(k) else {}
+        return self._L.qm_extract_files_types, (C.byref(ta),), unpack
 
     def _files_boot(self, n, boot, **kw):
         bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
@@ -881,6 +900,45 @@ class Batch:
         ms = (C.c_float * 3)()
         self._ck(self._L.qm_batch_atomize_timings(self._h, ms))
         return {"atom_truth_ms": ms[0], "atom_records_ms": ms[1], "atom_found_ms": ms[2]}
+
+    # -- TP, FP and FN by variant type and size ------------------------
+    def vartype(self, edges=None, shapes=None, columns=False, stream=None, fetch=True):
+        """qm_batch_types + qm_batch_get_types (allele-extended batches): (rec, tru) uint64 [n_vcf][n_rows][2] -- per row
+        (vartype.row_names(edges)) the kept records and the TP lines among them, the truth entries and the found ones.  edges:
+        the ascending lower edges of the size bins (None: vartype.DEFAULT_EDGES); shapes: the (len, head, tail) rows of the
+        dictionary ids (AlleleDict.shapes, vartype.shapes_of) or None; columns=True keeps every record's row byte for vartyped().
+        fetch=False: enqueue only (vartype_counts() waits and copies)"""
+        from .vartype import check_edges
+        e = _c(check_edges(edges), np.int32)
+        ln, head, tail = (None, None, None) if shapes is None else (_c(shapes[0], np.int32), _c(shapes[1], np.uint32), _c(shapes[2], np.uint32))
+        n = 0 if shapes is None else int(ln.shape[0])
+        if shapes is not None and not (head.shape[0] == tail.shape[0] == n):
+            raise ValueError("vartype: shape columns of %d, %d and %d rows" % (n, head.shape[0], tail.shape[0]))
+        self._ck(self._L.qm_batch_types(self._h, _p(e), int(e.shape[0]), _p(ln) if n else None, _p(head) if n else None, _p(tail) if n else None, n,
+                                        _lib.QM_TYPE_COLUMNS if columns else 0, C.c_void_p(stream) if stream else None))
+        self._type_rows = 5 * int(e.shape[0]) + 4
+        return self.vartype_counts() if fetch else None
+
+    def vartype_counts(self):
+        """qm_batch_get_types: the counts of the latest vartype()"""
+        nr = getattr(self, "_type_rows", _lib.QM_TYPE_MAX_ROWS)
+        rec = np.zeros((max(self.n_vcf, 1), nr, 2), np.uint64)
+        tru = np.zeros((max(self.n_vcf, 1), nr, 2), np.uint64)
+        self._ck(self._L.qm_batch_get_types(self._h, _p(rec), _p(tru)))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def vartyped(self, v):
+        """qm_batch_get_typed: the row (uint8 [n]) of every record of VCF v in input order, after a vartype(columns=True)"""
+        n = int(self.n_records[int(v)])
+        row = np.zeros(max(n, 1), np.uint8)
+        self._ck(self._L.qm_batch_get_typed(self._h, int(v), _p(row)))
+        return row[:n]
+
+    def vartype_timings(self):
+        """qm_batch_types_timings (set_timing on): milliseconds of the latest vartype() between HIP events"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.qm_batch_types_timings(self._h, ms))
+        return {"type_records_ms": ms[0], "type_truth_ms": ms[1]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

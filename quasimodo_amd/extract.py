@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
-from .passes import PASSES, check_atomize, check_normalize, check_shared_call, requested_by
+from .passes import PASSES, check_atomize, check_normalize, check_shared_call, check_vartype, requested_by
 from .vcfio import scan_vcf
 
 
@@ -71,6 +71,8 @@ class Job:
     # MNPs matched against adjacent SNVs; mixed samples, allele-extended mode only
     atomize: bool = None      # True: stats gain atom_rec / atom_tru
     atoms_out: str = None     # where the job's multi-atom lines table goes (extract_many(atomize=) derives it)
+    # TP, FP and FN by variant type and size; mixed samples, allele-extended mode only
+    vartype: tuple = None     # the size edges: stats gain type_rec / type_tru / type_edges (the same edges for every typed job of a call)
 
 
 def _paths(job):
@@ -141,7 +143,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None, normalize=None, atomize=None):
+                 surface=None, context=None, normalize=None, atomize=None, vartype=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -195,13 +197,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     TP_A, rescued, multi-atom and partial lines, atoms, atoms hit and the lines per reason a record is not atomisable) and
     stats["atom_tru"] ([6]: truth entries, atomisable ones, distinct atoms, atoms found, entries found by spelling and by atoms),
     and atoms/<x>.atoms.tsv beside fp/ and tp/.
+    vartype: True (the default size edges 1,2,3,4,5,6,16,51) or the ascending lower edges of the size bins (quasimodo_amd.vartype,
+    DESIGN.md 4.19; default: the jobs' Job.vartype; alleles=True only, ValueError otherwise): every mixed-sample job gets
+    stats["type_rec"] ([5 n_bins + 4][2]: per type x size row, then NOKEY, NOVAR, LONGPAIR, NOSHAPE, the kept lines and the TP
+    lines among them), stats["type_tru"] (the same rows: truth entries and the found ones) and stats["type_edges"].
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
              "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
-             "atomize": atomize is not None and atomize is not False}
+             "atomize": atomize is not None and atomize is not False, "vartype": vartype is not None and vartype is not False}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -260,6 +266,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if j.atomize:
                 _paths(j)
                 j.atoms_out = j.atoms_out or atoms_path(j)
+    if given["vartype"]:
+        from .vartype import check_edges
+        tedges = check_edges(None if vartype is True else vartype)
+        for j in jobs:
+            j.vartype = None if is_pure_strain(j.vcf_file) else tedges
     if boot is not None:
         from .bootstrap import DEFAULTS
         par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
@@ -297,6 +308,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     alleles = _alleles_default() if alleles is None else bool(alleles)
     check_normalize(requested_by(jobs), alleles)
     check_atomize(requested_by(jobs), alleles)
+    check_vartype(requested_by(jobs), alleles)
     by_truth = {}
     for j in jobs:
         if j.normalize and by_truth.setdefault(os.path.realpath(j.snp_file), (j.normalize, j.vcf_file))[0] != j.normalize:
@@ -327,7 +339,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = sf = cxs = nzs = ats = None
+    ts = vt = nm = sf = cxs = nzs = ats = tys = None
+    if any(j.vartype is not None and not p for j, p in zip(jobs, pure)):
+        from .vartype import check_edges
+        tys = {"edges": check_edges(next(j.vartype for j in jobs if j.vartype is not None)),
+               "want": [int(j.vartype is not None and not p) for j, p in zip(jobs, pure)]}
     if any(j.context is not None for j in jobs):
         from .context import check_params
         for j in jobs:
@@ -418,7 +434,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats, vartype=tys)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

@@ -18,6 +18,7 @@ PASSES = (
     Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
     Pass("normalize", ("normalize",), ("normalize",), "--normalize", None, ()),
     Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
+    Pass("vartype", ("vartype",), ("vartype",), "--by-type", "vartype: the typed jobs of one call share one list of size edges", ()),
     Pass("context", ("context",), ("context",), "--seq-context",
          "context: the profiled jobs of one call share one half window and one GC bin count", ()),
     Pass("surface", ("surface",), ("surface",), "--filter-surface",
@@ -57,6 +58,13 @@ def check_atomize(requested, alleles):
     """--atomize splits MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
     if "atomize" in requested and not alleles:
         raise ValueError("atomize (--atomize) needs the allele-extended mode (--alleles): a single-base batch holds no MNPs")
+
+
+def check_vartype(requested, alleles):
+    """--by-type types indels, MNPs and complex records, which only the allele-extended mode holds: ValueError before a file is
+    touched"""
+    if "vartype" in requested and not alleles:
+        raise ValueError("vartype (--by-type) needs the allele-extended mode (--alleles): a single-base batch holds SNVs only")
 
 
 def requested_by(jobs):

@@ -107,6 +107,13 @@ class AlleleDict:
     def code(self, allele: bytes) -> int:
         return int(self._L.qm_allele_code(self._h, allele, len(allele)))
 
+    def shapes(self):
+        """qm_dict_shapes of every id: (len int32, head uint32, tail uint32), the shape table Batch.vartype takes (vartype.py)"""
+        n = len(self)
+        ln, head, tail = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        got = int(self._L.qm_dict_shapes(self._h, 0, n, ln.ctypes.data_as(C.c_void_p), head.ctypes.data_as(C.c_void_p), tail.ctypes.data_as(C.c_void_p)))
+        return ln[:got], head[:got], tail[:got]
+
     def spell(self, code: int) -> bytes:
         buf = C.create_string_buffer(1 << 16)
         n = int(self._L.qm_allele_spell(self._h, int(code), buf, len(buf)))

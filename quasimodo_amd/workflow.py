@@ -165,7 +165,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
-                         context_gc_bins=None, alleles=False, normalize=None, atomize=False):
+                         context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -210,12 +210,25 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     WorkflowError before a file is touched otherwise): final_tables/caller_performance_atomized.tsv (TP, FP, FN, Precision, Recall,
     F1 by spelling and by atoms side by side, the rescued, multi-atom, partial and reason counts) and
     callers/{caller}/atoms/{sample}.{ref}.{caller}.atoms.tsv for every mixed sample.
+    by_type: True, or the size edges as a list or as the CLI's `1,2,6` (quasimodo_amd.vartype; needs alleles,
+    WorkflowError before a file is touched otherwise): TP, FP and FN by variant type and size are counted behind the
+    classification and final_tables/caller_performance_types.tsv is written (per caller x mixed sample one row per type and size
+    bin, a marginal per type, the four rows behind the grid, then a pooled block per caller).
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
-                 context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize))
+                 context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False)
+    tedges = None
+    if by_type is not None and by_type is not False:
+        from .vartype import check_edges, parse_edges
+        if not alleles:
+            raise WorkflowError("--by-type needs --alleles: indels, MNPs and complex records are typed, which only the allele-extended mode reads")
+        try:
+            tedges = check_edges(None) if by_type is True else parse_edges(by_type) if isinstance(by_type, str) else check_edges(by_type)
+        except ValueError as e:
+            raise WorkflowError("--type-bins: %s" % e) from None
     if normalize is not None and not alleles:
         raise WorkflowError("--normalize needs --alleles: the normal form is taken of indels and MNPs, which only the allele-extended mode reads")
     if atomize and not alleles:
@@ -277,6 +290,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("caller_performance_normalized.tsv\t%s" % ",".join(callers))
         if atomize:
             print("caller_performance_atomized.tsv\t%s" % ",".join(callers))
+        if tedges is not None:
+            print("caller_performance_types.tsv\t%s\t%s" % (",".join(callers), ",".join(str(e) for e in tedges)))
         if mutation_context is not None:
             for mix in mixes:
                 for c in callers:
@@ -349,6 +364,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if atomize and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].atomize = True
             jobs[-1].atoms_out = os.path.join(d, "atoms", os.path.basename(src)[:-4] + ".atoms.tsv")
+        if tedges is not None and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].vartype = tedges
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -416,6 +433,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if atomize:
             from .atomize import write_performance_atomized
             write_performance_atomized(os.path.join(tables, "caller_performance_atomized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
+        if tedges is not None:
+            from .vartype import write_performance_types
+            write_performance_types(os.path.join(tables, "caller_performance_types.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)], tedges)
     if gpus is not None and (int(gpus) > 1 or _body):
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")

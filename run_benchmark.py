@@ -88,6 +88,13 @@ def _bootstrap_opts(n_rep, window, seed):
     return None if n_rep is None else {"n_rep": n_rep, "window": window, "seed": seed}
 
 
+def _type_bins(by_type, type_bins):
+    """--by-type / --type-bins -> what the workflow takes: None without --by-type, True for the default edges, else the edges' text"""
+    if type_bins is not None and not by_type:
+        raise click.UsageError("--type-bins needs --by-type")
+    return None if not by_type else True if type_bins is None else type_bins
+
+
 @cli.command(help="Benchmarking for HCMV dataset")
 @common_options
 @click.option("-e", "--evaluation", required=True, type=click.Choice(["all", "variantcall", "assembly"]), help="The evaluation to run.")
@@ -140,6 +147,11 @@ def _bootstrap_opts(n_rep, window, seed):
 @click.option("--atomize", "atomize", is_flag=True, default=False,
               help="With --alleles: also match MNPs against adjacent SNVs, atom by atom (every equal-length substitution split into its "
                    "single-base differences, on both sides): write final_tables/caller_performance_atomized.tsv and callers/*/atoms/*.atoms.tsv.")
+@click.option("--by-type", "by_type", is_flag=True, default=False,
+              help="With --alleles: also count TP, FP and FN by variant type (SNV, MNP, INS, DEL, complex) and size: write "
+                   "final_tables/caller_performance_types.tsv.")
+@click.option("--type-bins", "type_bins", default=None,
+              help="--by-type: the ascending lower edges of the size bins, at most 16, the first one 1 [default: 1,2,3,4,5,6,16,51].")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
@@ -147,7 +159,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False, atomize=False):
+         normalize=False, atomize=False, by_type=False, type_bins=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -178,7 +190,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              votes=votes, consensus_vcf=consensus_vcf, explain_errors=explain_errors, explain_radius=explain_radius,
                                              filter_surface=filter_surface, surface_qual_step=surface_qual_step,
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
-                                             alleles=alleles, normalize=genomes if normalize else None, atomize=atomize)
+                                             alleles=alleles, normalize=genomes if normalize else None, atomize=atomize,
+                                             by_type=_type_bins(by_type, type_bins))
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -232,12 +245,19 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode to normalise (hcmv has it).")
 @click.option("--atomize", "atomize", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose MNPs could be split (hcmv has it).")
+@click.option("--by-type", "by_type", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose variants could be typed (hcmv has it).")
+@click.option("--type-bins", "type_bins", default=None, help="Not available here (see --by-type).")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
-            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False):
+            surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False,
+            by_type=False, type_bins=None):
     from quasimodo_amd import workflow
     try:
+        if by_type or type_bins is not None:
+            raise workflow.WorkflowError("--by-type needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --by-type)")
         if atomize:
             raise workflow.WorkflowError("--atomize needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --atomize)")
