@@ -227,7 +227,7 @@ int qm_bench_synth(qm_ctx* ctx, const qm_synth_cfg* cfg, int n_vcf, int64_t reco
  * NULL it must be a device buffer of [qm_batch_n_truth(b)][3][n_bins] uint64 that
  * receives the per-truth sums (the caller all-reduces it across ranks).
  *
- * Ordering against the passes over a finished batch (qm_batch_motifs ... qm_batch_types below), each of which may have been
+ * Ordering against the passes over a finished batch (qm_batch_motifs ... qm_batch_haplotypes below), each of which may have been
  * enqueued on a stream of the caller's: a call that rewrites what passes read (qm_batch_run, qm_batch_upload,
  * qm_batch_upload_async, qm_batch_synth, qm_batch_upload_af) is ordered behind every pass of the batch still in flight, on
  * whatever stream.  The asynchronous ones (qm_batch_run, qm_batch_upload_async) make their stream wait for the passes' events;
@@ -646,6 +646,77 @@ int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t*
 int qm_batch_get_types(qm_batch* b, uint64_t* rec /*[n_vcf][n_rows][2] or NULL*/, uint64_t* tru /*[n_vcf][n_rows][2] or NULL*/);
 int qm_batch_get_typed(qm_batch* b, int vcf, uint8_t* row /*[n]*/);
 int qm_batch_types_timings(qm_batch* b, float* ms2);
+
+/* ---- clusters of records matched by replayed haplotype (build-defined, opt-in, QM_BATCH_ALLELES batches only) ----
+ * The bounded core of rtg vcfeval / hap.py xcmp: the unmatched records of a small region and the unmatched truth entries of the
+ * same region are each replayed onto the genome; both sides are rescued when the two sequences are equal.  All or nothing per
+ * region.  The classification, its masks and its counts stay untouched.
+ * G: one contig of qm_genome_load, 1-based, length L, read as qm_batch_normalize reads it (lower case counts as its base); every
+ *   byte that is no base is one symbol of its own (code 15), equal to itself only.
+ * Usable: a variant (p, R, A) with inline codes for both alleles, no QM_F_NOKEY, R != A, 1 <= p and p + |R| - 1 <= L, and G
+ *   spelling R.  Otherwise it is counted under the first reason that applies: LONG, NOKEY, NOVAR, RANGE, REFMISMATCH.
+ * Trimmed form (q, r, a) of a usable variant, with cp and cs of qm_batch_types (prefix first and greedy, then suffix): q = p + cp,
+ *   r = R[cp : |R| - cs], a = A[cp : |A| - cs]; one of r, a may be empty.  Footprint: lo = q, hi = max(q, q + |r| - 1).
+ * Sites of a (truth set, genome, gap g), 0 <= g <= QM_HAP_MAX_GAP: the usable allele-extended entries in the table's order; the
+ *   next entry joins the current site iff its lo <= (the largest hi so far) + 2 g, else it opens a new site.  A site's window is
+ *   [max(1, min lo - g), min(L + 1, max hi + g)]; a site whose window is longer than QM_HAP_MAX_WINDOW is TOOLONG for every VCF.
+ *   Window ends never descend.  A footprint [lo, hi] lies in the first site whose window ends at or behind hi, if that window
+ *   starts at or before lo (windows of different sites are disjoint, but where a common prefix moved an entry's footprint behind
+ *   the next entry's: then the first such site is the one).
+ * Per VCF: an entry is FOUND when a kept record with valid codes and no QM_F_NOKEY spells it (qm_batch_types' found), and open
+ *   when it is usable and not FOUND.  A record is MATCHED_SPELLING when it has valid codes, no QM_F_NOKEY and spells an entry;
+ *   it is open when it is kept, usable, not MATCHED_SPELLING and its footprint lies in a site's window; a kept, usable, unmatched
+ *   record in no window is OUTSIDE.  Open records of a TOOLONG site are TOOLONG; an open record of a site without an open entry
+ *   is LONE.
+ * A site with an open record and an open entry that is not TOOLONG is tried: TOOMANY when either side has more than
+ *   QM_HAP_MAX_ITEMS open lines or entries; otherwise identical spellings of a side collapse, the variants of a side are sorted by
+ *   (q, |r|), and the site is CONFLICT when for two neighbours of a side q_next < q_prev + |r_prev|, or q_next == q_prev and
+ *   |r_next| == 0.  The replay of a side over the window [ws, we]: cur = ws; per variant G[cur .. q - 1], then a, cur = q + |r|;
+ *   at the end G[cur .. min(we, L)].  MATCH iff the two replays are equal in length and in every symbol, else MISMATCH.
+ * In a MATCH site every open record is rescued (class RESCUED) and every open entry is found by haplotype.  hitH = hit by
+ *   spelling, or rescued; a TP_H line is kept and (hitH and QM_F_IDDOT, or QM_F_TPLINE): qm_batch_normalize's rule with hitN
+ *   replaced by hitH; an exact TP line is always a TP_H line.
+ * rec[v][QM_HAP_R_COLS] over the kept records: KEPT, TP (the batch's own), TP_H, RESCUED (TP_H lines that are no TP lines), OPEN
+ *   (all open records, whatever became of them), then the records per class OUTSIDE .. REFMISMATCH.
+ * tru[v][QM_HAP_T_COLS]: ENTRIES, FOUND, FOUND_H (FOUND plus found by haplotype), OPEN, UNUSABLE, SITES, TRIED, MATCHED (sites).
+ * With QM_HAP_COLUMNS the pass also hands out a class byte per record, kept or not (QM_HAP_C_*; NOTKEPT: usable, unmatched and
+ *   not kept), the site of every usable record (-1: none), and per VCF a class byte per truth entry (MATCHED_SPELLING: found;
+ *   RESCUED: found by haplotype; LONE: open, its site was not tried; the site's class; or the reason it is not usable).
+ * Out of scope: a subset search inside a site (one true FP beside a respelled pair leaves the site MISMATCH), alleles of more
+ *   than QM_ALLELE_INLINE_MAX bases, phasing and genotypes, FP_R and the ROC after rescue, genomes of several contigs, vareval,
+ *   single-base batches (QM_E_STATE).
+ * qm_batch_haplotypes: genome_id_per_vcf[v] = a genome id or -1 (the VCF's rows stay zero); asynchronous on `stream` (NULL = the
+ *   context's own) but for the blocking copy of the descriptors and ONE 8-byte readback, the number of (VCF, open site) pairs,
+ *   which sizes their lists.  The site tables are rebuilt on the stream at every call.  QM_E_INVAL for a gap outside 0 ..
+ *   QM_HAP_MAX_GAP and when VCFs that share a truth set name different genomes; QM_E_RANGE for a batch of more than 65535 VCFs
+ *   (one grid dimension holds them) and for more than (2^31 - 1) / 11 (VCF, open site) pairs (the lists are indexed in 32 bits); QM_E_STATE unless the latest qm_batch_run was
+ *   finished, for a batch without QM_BATCH_ALLELES, and for a released truth set or genome.
+ * qm_batch_get_haplotypes / qm_batch_get_haplotyped: wait for the pass, then copy (any pointer may be NULL).  QM_E_STATE if the
+ *   batch ran since, for a VCF that named no genome, and without QM_HAP_COLUMNS in the latest call.
+ * qm_batch_haplotype_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] the site tables, [1]
+ *   k_hap_records, [2] k_hap_truth, k_hap_rank and the readback, [3] k_hap_pairs and k_hap_claim, [4] k_hap_replay.
+ * qm_truth_sites: the sites of a truth set, in order: the first entry (index into qm_truth_entries) and the window of each. */
+#define QM_HAP_R_COLS 16
+#define QM_HAP_T_COLS 8
+#define QM_HAP_MAX_GAP 32
+#define QM_HAP_DEFAULT_GAP 10
+#define QM_HAP_MAX_WINDOW 256
+#define QM_HAP_MAX_ITEMS 8
+#define QM_HAP_COLUMNS 2u
+enum { QM_HAP_R_KEPT = 0, QM_HAP_R_TP = 1, QM_HAP_R_TP_H = 2, QM_HAP_R_RESCUED = 3, QM_HAP_R_OPEN = 4, QM_HAP_R_OUTSIDE = 5, QM_HAP_R_LONE = 6,
+       QM_HAP_R_MISMATCH = 7, QM_HAP_R_CONFLICT = 8, QM_HAP_R_TOOMANY = 9, QM_HAP_R_TOOLONG = 10, QM_HAP_R_LONG = 11, QM_HAP_R_NOKEY = 12,
+       QM_HAP_R_NOVAR = 13, QM_HAP_R_RANGE = 14, QM_HAP_R_REFMISMATCH = 15 };
+enum { QM_HAP_T_ENTRIES = 0, QM_HAP_T_FOUND = 1, QM_HAP_T_FOUND_H = 2, QM_HAP_T_OPEN = 3, QM_HAP_T_UNUSABLE = 4, QM_HAP_T_SITES = 5,
+       QM_HAP_T_TRIED = 6, QM_HAP_T_MATCHED = 7 };
+enum { QM_HAP_C_MATCHED_SPELLING = 0, QM_HAP_C_RESCUED = 1, QM_HAP_C_OUTSIDE = 2, QM_HAP_C_LONE = 3, QM_HAP_C_MISMATCH = 4,
+       QM_HAP_C_CONFLICT = 5, QM_HAP_C_TOOMANY = 6, QM_HAP_C_TOOLONG = 7, QM_HAP_C_LONG = 8, QM_HAP_C_NOKEY = 9, QM_HAP_C_NOVAR = 10,
+       QM_HAP_C_RANGE = 11, QM_HAP_C_REFMISMATCH = 12, QM_HAP_C_NOTKEPT = 13 };
+int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf, int gap, unsigned what /*0 or QM_HAP_COLUMNS*/, void* stream);
+int qm_batch_get_haplotypes(qm_batch* b, uint64_t* rec /*[n_vcf][QM_HAP_R_COLS] or NULL*/, uint64_t* tru /*[n_vcf][QM_HAP_T_COLS] or NULL*/);
+int qm_batch_get_haplotyped(qm_batch* b, int vcf, uint8_t* cls /*[n]*/, int32_t* site /*[n]*/, uint8_t* entry_cls /*[entries]*/);
+int qm_batch_haplotype_timings(qm_batch* b, float* ms5);
+int qm_truth_sites(qm_ctx* ctx, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
+                   int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
  * has capacity limits (a bucket's records, the truth keys of its positions, the VCF's size); a VCF beyond them is redone by
  * the radix sort -- correct, several times slower -- and these counters say how often that happened. */
@@ -1068,6 +1139,30 @@ typedef struct qm_types_args {
 int qm_extract_files_types(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                            qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                            void* global_dev, const qm_types_args* types);
+
+/* qm_extract_files_ex plus the haplotype pass over its batch; mode must be QM_BATCH_ALLELES (QM_E_STATE
+ * otherwise).  Mixed-sample jobs with genome_id[j] >= 0 (a qm_genome_load id: the genome the VCF was called against) get their
+ * rows rec[j][QM_HAP_R_COLS] and tru[j][QM_HAP_T_COLS] of qm_batch_get_haplotypes; the others (-1, pure-strain samples) get zero
+ * rows.  sites_out (may be NULL, entries may be NULL): per job a file `#site WIN_LO WIN_HI LINES ENTRIES REPLAY_LINES
+ * REPLAY_TRUTH`, one row per MATCH site in site order -- the site's index and window, its rescued lines as `line:POS:REF:ALT`
+ * joined by `;` (the 1-based line number and the line's own text of the three columns, in file order), its entries found by
+ * haplotype as `POS:REF:ALT` in the table's order, and the two replayed strings (bases the genome does not hold print as N) --,
+ * written atomically (temp file + rename).  A job that names a file names its genome's bytes too: genome_seq[j] (genome_len[j]
+ * of them, the ones handed to qm_genome_load; read during the call only) -- the device keeps the packed genome, the host none.
+ * The VCF outputs, stats and roc are those of qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_haplotypes_args {
+  const int32_t* genome_id;         /* [n_jobs], -1 = the job takes no part */
+  int32_t gap;                      /* 0 .. QM_HAP_MAX_GAP, one for the call */
+  int32_t reserved;
+  uint64_t* rec;                    /* [n_jobs][QM_HAP_R_COLS] */
+  uint64_t* tru;                    /* [n_jobs][QM_HAP_T_COLS] */
+  const char* const* sites_out;     /* [n_jobs] or NULL */
+  const uint8_t* const* genome_seq; /* [n_jobs] or NULL (then sites_out is NULL too) */
+  const int64_t* genome_len;        /* [n_jobs] or NULL */
+} qm_haplotypes_args;
+int qm_extract_files_haplotypes(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                                void* global_dev, const qm_haplotypes_args* haplotypes);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

@@ -63,6 +63,13 @@ QM_TYPE_MAX_ROWS = 84
 QM_TYPE_COLUMNS = 2
 QM_TYPE_SNV, QM_TYPE_MNP, QM_TYPE_INS, QM_TYPE_DEL, QM_TYPE_CPX = range(5)
 QM_TYPE_X_NOKEY, QM_TYPE_X_NOVAR, QM_TYPE_X_LONGPAIR, QM_TYPE_X_NOSHAPE = range(4)
+QM_HAP_R_COLS = 16
+QM_HAP_T_COLS = 8
+QM_HAP_MAX_GAP = 32
+QM_HAP_DEFAULT_GAP = 10
+QM_HAP_MAX_WINDOW = 256
+QM_HAP_MAX_ITEMS = 8
+QM_HAP_COLUMNS = 2
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -91,6 +98,7 @@ EXPORTS = (
     "qm_batch_normalize", "qm_batch_get_normalize", "qm_batch_get_normalized", "qm_batch_normalize_timings", "qm_truth_normalized", "qm_truth_entries", "qm_extract_files_normalize",
     "qm_batch_atomize", "qm_batch_get_atomize", "qm_batch_get_atomized", "qm_batch_atomize_timings", "qm_truth_atoms", "qm_extract_files_atomize",
     "qm_dict_shapes", "qm_batch_types", "qm_batch_get_types", "qm_batch_get_typed", "qm_batch_types_timings", "qm_extract_files_types",
+    "qm_batch_haplotypes", "qm_batch_get_haplotypes", "qm_batch_get_haplotyped", "qm_batch_haplotype_timings", "qm_truth_sites", "qm_extract_files_haplotypes",
 )
 
 
@@ -162,6 +170,12 @@ class AtomizeArgs(C.Structure):
     _fields_ = [("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("atoms_out", C.POINTER(C.c_char_p))]
 
 
+class HaplotypesArgs(C.Structure):
+    """include/qmvt.h qm_haplotypes_args"""
+    _fields_ = [("genome_id", C.c_void_p), ("gap", C.c_int32), ("reserved", C.c_int32), ("rec", C.c_void_p), ("tru", C.c_void_p),
+                ("sites_out", C.POINTER(C.c_char_p)), ("genome_seq", C.POINTER(C.c_char_p)), ("genome_len", C.c_void_p)]
+
+
 class TypesArgs(C.Structure):
     """include/qmvt.h qm_types_args"""
     _fields_ = [("edges", C.c_void_p), ("n_bins", C.c_int32), ("reserved", C.c_int32), ("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p)]
@@ -192,7 +206,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_haplo.hip", "qmvt_haplo.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -424,6 +438,13 @@ def lib():
     L.qm_batch_get_types.argtypes = [vp, vp, vp]
     L.qm_batch_get_typed.argtypes = [vp, i32, vp]
     L.qm_batch_types_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_batch_haplotypes.argtypes = [vp, vp, i32, C.c_uint, vp]
+    L.qm_batch_get_haplotypes.argtypes = [vp, vp, vp]
+    L.qm_batch_get_haplotyped.argtypes = [vp, i32, vp, vp, vp]
+    L.qm_batch_haplotype_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_extract_files_haplotypes.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                              C.POINTER(HaplotypesArgs)]
+    L.qm_truth_sites.argtypes = [vp, i32, i32, i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.qm_extract_files_types.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                          C.POINTER(TypesArgs)]
     _lib = L

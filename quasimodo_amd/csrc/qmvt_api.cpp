@@ -34,6 +34,7 @@
 #include "qmvt_norm.h"
 #include "qmvt_atom.h"
 #include "qmvt_types.h"
+#include "qmvt_haplo.h"
 
 using namespace qm;
 
@@ -897,6 +898,23 @@ struct qm_batch {
   bool ty_timed = false;              // the latest qm_batch_types recorded them
   int32_t ty_rows = 0;                // n_rows of the latest qm_batch_types
   unsigned ty_made = 0;               // 1 | QM_TYPE_COLUMNS: what the latest qm_batch_types made behind the latest run
+  // qm_batch_haplotypes (lazy): the site tables of the (truth set, genome) pairs the VCFs name in one pool, the
+  // per-VCF descriptors and bitmaps, [n_vcf][QM_HAP_R_COLS] / [n_vcf][QM_HAP_T_COLS] counts, a class byte and a site index per
+  // record, the open lines of every (VCF, open site) pair and, on request, a class byte per (VCF, truth entry); ev_haplo says
+  // when the pass is done
+  DevBuf<uint32_t> hp_pool, hp_bits;
+  DevBuf<HapVcf> hp_vcfs;
+  DevBuf<uint64_t> hp_rec, hp_tru;
+  DevBuf<unsigned long long> hp_total;
+  DevBuf<uint8_t> hp_cls, hp_ecls;    // [n_pad]; the entries of every VCF's truth set, VCF after VCF
+  DevBuf<int32_t> hp_site;            // [n_pad]
+  DevBuf<int32_t> hp_pairs;           // [pairs][QM_HAP_MAX_ITEMS + 3]
+  hipEvent_t ev_haplo = nullptr;
+  hipEvent_t ev_hpt[6] = {};          // qm_batch_set_timing: around the site builds, k_hap_records, k_hap_truth, k_hap_claim, k_hap_replay
+  bool hp_timed = false;              // the latest qm_batch_haplotypes recorded them
+  unsigned hp_made = 0;               // 1 | QM_HAP_COLUMNS: what the latest qm_batch_haplotypes made behind the latest run
+  std::vector<uint8_t> hp_has;        // [n_vcf] the VCF named a genome
+  std::vector<int64_t> hp_eoff;       // [n_vcf + 1] the VCF's entries in hp_ecls
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -935,6 +953,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_att) if (e) (void)hipEventDestroy(e);
   if (b->ev_types) (void)hipEventDestroy(b->ev_types);
   for (auto& e : b->ev_tyt) if (e) (void)hipEventDestroy(e);
+  if (b->ev_haplo) (void)hipEventDestroy(b->ev_haplo);
+  for (auto& e : b->ev_hpt) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -951,8 +971,10 @@ static const PassEvent PASS_EVENTS[] = {
     {&qm_batch::ev_motif, false}, {&qm_batch::ev_afp, false},  {&qm_batch::ev_truth, false}, {&qm_batch::ev_strata, true},
     {&qm_batch::ev_boot, true},   {&qm_batch::ev_votes, true}, {&qm_batch::ev_nm, true},     {&qm_batch::ev_sf, false},
     {&qm_batch::ev_cx, true},     {&qm_batch::ev_norm, false}, {&qm_batch::ev_atom, false},
-    {&qm_batch::ev_types, false},
+    {&qm_batch::ev_types, false}, {&qm_batch::ev_haplo, false},
 };
+// (ev_haplo: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
+// flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
 // Orders what follows behind every pass of the batch still in flight, on whatever stream it was enqueued: `st` waits for the passes'
 // events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps.  An event exists once its pass has
 // been called: a batch that never ran a pass makes no HIP call here.
@@ -1303,6 +1325,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->nz_made = 0;
   b->at_made = 0;
   b->ty_made = 0;
+  b->hp_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -3280,6 +3303,224 @@ extern "C" int qm_batch_types_timings(qm_batch* b, float* ms2) {
   HIPCHK(hipSetDevice(b->ctx->dev));
   HIPCHK(hipEventSynchronize(b->ev_tyt[2]));
   for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(ms2 + i, b->ev_tyt[i], b->ev_tyt[i + 1]));
+  return QM_OK;
+}
+// ---- clusters of records matched by replayed haplotype ----
+// The pool words of one site table: [elo | ehi | esite | slo | shi][xn], sfirst[xn + 1], n_sites[2], ewhy[xn] as bytes
+static size_t hap_pool_words(int64_t xn) { return 6 * (size_t)xn + 3 + ((size_t)xn + 3) / 4; }
+static HapSites hap_sites(const Truth& t, const Genome& g, int gap, uint32_t* pool) {
+  HapSites S;
+  memset(&S, 0, sizeof S);
+  const size_t xn = (size_t)t.xn;
+  S.words = g.d_words; S.len = g.len;
+  S.xkeys = t.d_xkeys; S.xref = t.d_xref; S.xalt = t.d_xalt; S.xn = t.xn;
+  int32_t* w = reinterpret_cast<int32_t*>(pool);
+  S.elo = w; S.ehi = w + xn; S.esite = w + 2 * xn; S.slo = w + 3 * xn; S.shi = w + 4 * xn;
+  S.sfirst = w + 5 * xn;
+  S.n_sites = w + 6 * xn + 1;
+  S.ewhy = reinterpret_cast<uint8_t*>(w + 6 * xn + 3);
+  S.gap = gap;
+  return S;
+}
+static int hap_build(const HapSites& S, hipStream_t st) {
+  launch_hap_sites(S, st);
+  HIPCHK(hipGetLastError());
+  return QM_OK;
+}
+extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf, int gap, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_haplotypes");
+  if (!genome_id_per_vcf) return fail(QM_E_INVAL, "qm_batch_haplotypes: NULL genome ids");
+  if (what & ~QM_HAP_COLUMNS) return fail(QM_E_INVAL, "qm_batch_haplotypes: what = %u", what);
+  if (gap < 0 || gap > QM_HAP_MAX_GAP) return fail(QM_E_INVAL, "qm_batch_haplotypes: gap %d (0 to %d)", gap, QM_HAP_MAX_GAP);
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_haplotypes: a single-base batch holds no indels, MNPs or complex records to replay (create the batch with QM_BATCH_ALLELES)");
+  if (b->n_vcf > 65535) return fail(QM_E_RANGE, "qm_batch_haplotypes: %d VCFs (at most 65535 in one batch)", b->n_vcf);
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = genome_id_per_vcf[v];
+    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_haplotypes: VCF %zu names genome %d (have %zu)", v, gid, c->genomes.size());
+    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_haplotypes: VCF %zu names released genome %d", v, gid);
+  }
+  int rc = truths_live(b, "qm_batch_haplotypes");
+  if (rc != QM_OK) return rc;
+  // one site table per truth set: the VCFs that share one must name one genome
+  struct Pair { int truth, genome; size_t first_vcf, off; };
+  std::vector<Pair> pairs;
+  std::vector<int> pair_of(nv, -1);
+  size_t pool_words = 0, bit_words = 0;
+  int64_t max_entries = 0;
+  b->hp_eoff.assign(nv + 1, 0);
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = genome_id_per_vcf[v], tid = b->L.vcfs[v].truth;
+    b->hp_eoff[v + 1] = b->hp_eoff[v];
+    if (gid < 0) continue;
+    const int64_t xn = c->truths[(size_t)tid].xn;
+    size_t k = 0;
+    while (k < pairs.size() && pairs[k].truth != tid) ++k;
+    if (k == pairs.size()) {
+      pairs.push_back(Pair{tid, gid, v, pool_words});
+      pool_words += hap_pool_words(xn);
+    } else if (pairs[k].genome != gid) {
+      return fail(QM_E_INVAL, "qm_batch_haplotypes: VCF %zu and VCF %zu share truth set %d and name genomes %d and %d (the sites of a truth set belong to one genome)",
+                  pairs[k].first_vcf, v, tid, pairs[k].genome, gid);
+    }
+    pair_of[v] = (int)k;
+    bit_words += 3 * (size_t)(xn / 32 + 1);
+    max_entries = std::max(max_entries, xn);
+    b->hp_eoff[v + 1] += xn;
+  }
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_haplo, &st);
+  if (rc != QM_OK) return rc;
+  b->hp_made = 0;   // from here on the outputs are rewritten
+  const size_t np = (size_t)b->L.n_pad;
+  const bool cols = (what & QM_HAP_COLUMNS) != 0;
+  rc = b->hp_pool.grow((int64_t)std::max<size_t>(pool_words, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_rec.grow((int64_t)std::max<size_t>(nv * HAP_R_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_tru.grow((int64_t)std::max<size_t>(nv * HAP_T_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_total.grow(1, &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_cls.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hp_site.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
+  if (rc == QM_OK && cols) rc = b->hp_ecls.grow(std::max<int64_t>(b->hp_eoff[nv], 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_hpt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->hp_timed = false;
+  if (T) HIPCHK(hipEventRecord(b->ev_hpt[0], st));
+  std::vector<HapSites> tabs(pairs.size());
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    tabs[k] = hap_sites(c->truths[(size_t)pairs[k].truth], c->genomes[(size_t)pairs[k].genome], gap, b->hp_pool + pairs[k].off);
+    rc = hap_build(tabs[k], st);
+    if (rc != QM_OK) return rc;
+  }
+  std::vector<HapVcf> vcfs(std::max<size_t>(nv, 1));
+  memset(vcfs.data(), 0, vcfs.size() * sizeof(HapVcf));
+  b->hp_has.assign(nv, 0);
+  size_t bo = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    if (pair_of[v] < 0) continue;
+    const size_t w = (size_t)(tabs[(size_t)pair_of[v]].xn / 32 + 1);
+    vcfs[v].s = tabs[(size_t)pair_of[v]];
+    vcfs[v].off = b->L.vcfs[v].off;
+    vcfs[v].ebits = b->hp_bits + bo;
+    vcfs[v].sbits = b->hp_bits + bo + w;
+    vcfs[v].srank = b->hp_bits + bo + 2 * w;
+    if (cols) vcfs[v].ecls = b->hp_ecls + b->hp_eoff[v];
+    bo += 3 * w;
+    b->hp_has[v] = 1;
+  }
+  if (nv) HIPCHK(hipMemcpy(b->hp_vcfs, vcfs.data(), nv * sizeof(HapVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
+  HIPCHK(hipMemsetAsync(b->hp_bits, 0, std::max<size_t>(bit_words, 1) * 4, st));
+  HIPCHK(hipMemsetAsync(b->hp_rec, 0, std::max<size_t>(nv * HAP_R_COLS, 1) * 8, st));
+  HIPCHK(hipMemsetAsync(b->hp_tru, 0, std::max<size_t>(nv * HAP_T_COLS, 1) * 8, st));
+  HIPCHK(hipMemsetAsync(b->hp_total, 0, 8, st));
+  HIPCHK(hipMemsetAsync(b->hp_cls, 0, std::max<size_t>(np, 1), st));
+  HIPCHK(hipMemsetAsync(b->hp_site, 0xff, std::max<size_t>(np, 1) * 4, st));
+  if (T) HIPCHK(hipEventRecord(b->ev_hpt[1], st));
+  HapRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.vcfs = b->hp_vcfs;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.flags = b->flags;
+  P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  P.cls = b->hp_cls; P.site = b->hp_site; P.rec = b->hp_rec;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_hap_records(P, st);
+  HIPCHK(hipGetLastError());
+  if (T) HIPCHK(hipEventRecord(b->ev_hpt[2], st));
+  launch_hap_truth(b->hp_vcfs, (int)nv, max_entries, b->hp_tru, b->hp_total, st);
+  HIPCHK(hipGetLastError());
+  // the one blocking readback of the pass: how many (VCF, open site) pairs there are sizes their lists
+  unsigned long long n_pairs = 0;
+  HIPCHK(hipMemcpyAsync(&n_pairs, b->hp_total, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (n_pairs > (unsigned long long)(0x7fffffff / HAP_PAIR_WORDS)) return fail(QM_E_RANGE, "qm_batch_haplotypes: %llu (VCF, open site) pairs", n_pairs);
+  rc = b->hp_pairs.grow((int64_t)std::max<size_t>((size_t)n_pairs * HAP_PAIR_WORDS, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  if (T) HIPCHK(hipEventRecord(b->ev_hpt[3], st));
+  P.pairs = b->hp_pairs;
+  // (also without a pair: the pending lines of sites whose entries are all found become LONE there; no list is touched then)
+  launch_hap_claim(P, (int)nv, max_entries, st);
+  HIPCHK(hipGetLastError());
+  if (T) HIPCHK(hipEventRecord(b->ev_hpt[4], st));
+  HapReplayParams Q;
+  memset(&Q, 0, sizeof Q);
+  Q.vcfs = b->hp_vcfs;
+  Q.pos = b->pos; Q.ref = b->ref; Q.alt = b->alt; Q.flags = b->flags; Q.mask_tp = b->mask_tp;
+  Q.cls = b->hp_cls; Q.rec = b->hp_rec; Q.tru = b->hp_tru;
+  Q.pairs = b->hp_pairs; Q.n_pairs = (int64_t)n_pairs;
+  launch_hap_replay(Q, st);
+  HIPCHK(hipGetLastError());
+  if (T) { HIPCHK(hipEventRecord(b->ev_hpt[5], st)); b->hp_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_haplo, st));
+  b->hp_made = 1u | what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_haplotypes(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_haplotypes: NULL batch");
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_haplotypes: no qm_batch_haplotypes behind the latest run");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_haplo));
+  const size_t nv = (size_t)b->n_vcf;
+  if (rec && nv) HIPCHK(hipMemcpy(rec, b->hp_rec, nv * HAP_R_COLS * 8, hipMemcpyDeviceToHost));
+  if (tru && nv) HIPCHK(hipMemcpy(tru, b->hp_tru, nv * HAP_T_COLS * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_haplotyped(qm_batch* b, int v, uint8_t* cls, int32_t* site, uint8_t* entry_cls) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_haplotyped: NULL batch");
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_haplotyped: no qm_batch_haplotypes behind the latest run");
+  if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_haplotyped: VCF %d (the batch has %d)", v, b->n_vcf);
+  if (!b->hp_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_haplotyped: VCF %d named no genome in the latest qm_batch_haplotypes", v);
+  if (!(b->hp_made & QM_HAP_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_get_haplotyped: the latest qm_batch_haplotypes did not keep the columns (QM_HAP_COLUMNS)");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_haplo));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  const size_t n = (size_t)d.n, ne = (size_t)(b->hp_eoff[(size_t)v + 1] - b->hp_eoff[(size_t)v]);
+  if (cls && n) HIPCHK(hipMemcpy(cls, b->hp_cls + d.off, n, hipMemcpyDeviceToHost));
+  if (site && n) HIPCHK(hipMemcpy(site, b->hp_site + d.off, n * 4, hipMemcpyDeviceToHost));
+  if (entry_cls && ne) HIPCHK(hipMemcpy(entry_cls, b->hp_ecls + b->hp_eoff[(size_t)v], ne, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_haplotype_timings(qm_batch* b, float* ms5) {
+  if (!b || !ms5) return fail(QM_E_INVAL, "qm_batch_haplotype_timings: NULL");
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_haplotype_timings: no qm_batch_haplotypes behind the latest run");
+  if (!b->hp_timed) return fail(QM_E_STATE, "qm_batch_haplotype_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_hpt[5]));
+  for (int i = 0; i < 5; ++i) HIPCHK(hipEventElapsedTime(ms5 + i, b->ev_hpt[i], b->ev_hpt[i + 1]));
+  return QM_OK;
+}
+extern "C" int qm_truth_sites(qm_ctx* c, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
+                              int64_t* n_out) {
+  if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_sites: bad arguments");
+  if (gap < 0 || gap > QM_HAP_MAX_GAP) return fail(QM_E_INVAL, "qm_truth_sites: gap %d (0 to %d)", gap, QM_HAP_MAX_GAP);
+  if (truth_id < 0 || truth_id >= (int)c->truths.size() || c->truths[(size_t)truth_id].released)
+    return fail(QM_E_INVAL, "qm_truth_sites: no live truth set %d", truth_id);
+  if (genome_id < 0 || genome_id >= (int)c->genomes.size() || c->genomes[(size_t)genome_id].released)
+    return fail(QM_E_INVAL, "qm_truth_sites: no live genome %d", genome_id);
+  HIPCHK(hipSetDevice(c->dev));
+  const Truth& t = c->truths[(size_t)truth_id];
+  const size_t xn = (size_t)t.xn;
+  uint32_t* pool = nullptr;
+  DALLOC(pool, hap_pool_words(t.xn));
+  const HapSites S = hap_sites(t, c->genomes[(size_t)genome_id], gap, pool);
+  std::vector<int32_t> h(3 * xn + 3);   // slo | shi | sfirst[xn + 1] | n_sites
+  int rc = hap_build(S, c->stream);
+  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
+  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(h.data(), S.slo, (3 * xn + 3) * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(pool);
+  if (rc != QM_OK) return rc;
+  if (e != hipSuccess) return fail(QM_E_HIP, "qm_truth_sites: %s", hipGetErrorString(e));
+  const int64_t ns = h[3 * xn + 1];
+  *n_out = ns;
+  if (ns > capacity) return fail(QM_E_RANGE, "qm_truth_sites: %lld sites, room for %lld", (long long)ns, (long long)capacity);
+  for (int64_t s = 0; s < ns; ++s) {
+    if (first_entry) first_entry[s] = h[2 * xn + (size_t)s];
+    if (lo) lo[s] = h[(size_t)s];
+    if (hi) hi[s] = h[xn + (size_t)s];
+  }
   return QM_OK;
 }
 // paired block-bootstrap replicates of the finished batch's counts

@@ -1,0 +1,559 @@
+// qmvt_haplo.hip -- clusters of records matched by replayed haplotype: the kept records of a finished
+// allele-extended batch that no truth entry spells, and the truth entries no kept record spells, are grouped by the sites of the
+// truth set -- chains of entries at most 2 g bases apart --, each side of a site is replayed onto the genome over the site's
+// window, and both sides are rescued where the two sequences are equal.  k_hap_entries / k_hap_sites / k_hap_windows build the
+// sites of a (truth set, genome, gap); k_hap_records streams the batch in input order, classes every record, finds its site and
+// marks the entries it spells; k_hap_truth / k_hap_rank / k_hap_pairs count the truth side and number the (VCF, site) pairs
+// with an open entry; k_hap_claim hands every open line to its pair; k_hap_replay decides one pair per wave.  Integer work only:
+// no output depends on the order the lanes run in.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h)
+// stays the id the classification pass's profiles are keyed on.
+#include "qmvt_haplo.h"
+
+#include <algorithm>
+
+namespace qm {
+
+typedef int hp_int4 __attribute__((ext_vector_type(4)));
+
+constexpr int32_t HP_NO_HI = -(1 << 30);   // the largest footprint end before the first usable entry
+
+// inline codes (include/qmvt.h): 0 .. 3 one base, len << 26 | bases for 2 .. 13 bases
+__device__ inline bool hp_inline(int32_t c) {
+  const uint32_t u = (uint32_t)c;
+  return u < 4u || (u - (2u << 26)) < (12u << 26);
+}
+__device__ inline uint32_t hp_len(int32_t c) { return (uint32_t)c < 4u ? 1u : (uint32_t)c >> 26; }
+__device__ inline uint32_t hp_bits(int32_t c) { return (uint32_t)c & 0x03ffffffu; }
+// G[q], 1 <= q <= len (the caller's duty): 0 .. 3, or the code that is no base
+__device__ inline uint32_t hp_base(const uint32_t* words, int32_t q) { return (words[(q - 1) >> 3] >> (4 * ((q - 1) & 7))) & 15u; }
+// bit 2 k: field k of the two words differs
+__device__ inline uint32_t hp_diff(uint32_t x, uint32_t y) {
+  const uint32_t d = x ^ y;
+  return (d | d >> 1) & 0x1555555u;
+}
+
+// 0 for a usable variant, else the first reason that applies
+__device__ inline uint32_t hp_why(const uint32_t* words, int64_t len, int32_t p, int32_t r, int32_t a, bool nokey) {
+  if (!hp_inline(r) || !hp_inline(a)) return HAP_LONG;
+  if (nokey) return HAP_NOKEY;
+  if (r == a) return HAP_NOVAR;
+  const uint32_t lr = hp_len(r), br = hp_bits(r);
+  if (p < 1 || (int64_t)p + (int64_t)lr - 1 > len) return HAP_RANGE;
+  for (uint32_t k = 0; k < lr; ++k)
+    if (hp_base(words, p + (int32_t)k) != ((br >> (2 * k)) & 3u)) return HAP_REFMISMATCH;   // (no base: a mismatch too)
+  return 0u;
+}
+
+// the trimmed form of two different inline codes: the common prefix goes first, then the common suffix of what is left
+__device__ inline void hp_trim(int32_t p, int32_t r, int32_t a, int32_t& q, uint32_t& tr, uint32_t& ta, uint32_t& ab) {
+  const uint32_t lr = hp_len(r), la = hp_len(a), br = hp_bits(r), ba = hp_bits(a);
+  const uint32_t m = min(lr, la);
+  const uint32_t fields = (1u << (2u * m)) - 1u;
+  const uint32_t cp = (uint32_t)__builtin_ctz((hp_diff(br, ba) & fields) | (1u << (2u * m))) >> 1;
+  const uint32_t ds = hp_diff(br >> (2u * (lr - m)), ba >> (2u * (la - m))) & fields;
+  const uint32_t cs = min(ds ? (uint32_t)__builtin_clz(ds << (32u - 2u * m)) >> 1 : m, m - cp);
+  q = p + (int32_t)cp;
+  tr = lr - cp - cs;
+  ta = la - cp - cs;
+  ab = (ba >> (2u * cp)) & ((1u << (2u * ta)) - 1u);
+}
+
+// the index of the entry spelled (p, r, a) in the truth set's sorted table, or -1 (0 <= p < 2^28: the caller's duty)
+__device__ inline int64_t hp_entry(const HapSites& S, int32_t p, int32_t r, int32_t a) {
+  const uint32_t key = ((uint32_t)p << 4) | allele_nib(r, a);
+  int64_t lo = 0, hi = S.xn;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const uint32_t k = S.xkeys[mid];
+    bool less = k < key;
+    if (k == key) {
+      const int32_t rr = S.xref[mid];
+      less = rr < r || (rr == r && S.xalt[mid] < a);
+    }
+    if (less) lo = mid + 1; else hi = mid;
+  }
+  return lo < S.xn && S.xkeys[lo] == key && S.xref[lo] == r && S.xalt[lo] == a ? lo : -1;
+}
+
+// The site whose window holds the footprint [lo, hi], or -1: the first site whose window ends at or behind hi, if it starts at
+// or before lo.  (Window ends never descend: the largest footprint end of a site is larger than that of the site before.)
+__device__ inline int32_t hp_site(const HapSites& S, int32_t ns, int32_t lo, int32_t hi) {
+  int32_t x = 0, y = ns;
+  while (x < y) {
+    const int32_t mid = (x + y) >> 1;
+    if (S.shi[mid] < hi) x = mid + 1; else y = mid;
+  }
+  return x < ns && S.slo[x] <= lo ? x : -1;
+}
+
+// ---- the sites of a (truth set, genome, gap) ----
+// a lane per entry: usable or why not, and the footprint of its trimmed form
+__global__ __launch_bounds__(256) void k_hap_entries(HapSites S) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= S.xn) return;
+  const int32_t p = (int32_t)(S.xkeys[j] >> 4), r = S.xref[j], a = S.xalt[j];
+  const uint32_t why = hp_why(S.words, S.len, p, r, a, false);
+  int32_t q = 0;
+  uint32_t tr = 0u, ta = 0u, ab = 0u;
+  if (!why) hp_trim(p, r, a, q, tr, ta, ab);
+  S.ewhy[j] = (uint8_t)why;
+  S.elo[j] = q;
+  S.ehi[j] = max(q, q + (int32_t)tr - 1);
+}
+
+// One workgroup walks the table in its order, 256 entries a step: the running maximum of the footprint ends decides whether a
+// usable entry opens a site (its footprint starts more than 2 g behind every end before it), a running sum numbers the sites.
+__global__ __launch_bounds__(256) void k_hap_sites(HapSites S) {
+  __shared__ int32_t smax[256];
+  __shared__ int32_t ssum[256];
+  const int t = (int)threadIdx.x;
+  int32_t cmax = HP_NO_HI, ccnt = 0;
+  for (int64_t base = 0; base < S.xn; base += 256) {
+    const int64_t j = base + t;
+    const bool use = j < S.xn && S.ewhy[j] == 0;
+    const int32_t lo = use ? S.elo[j] : 0, hi = use ? S.ehi[j] : HP_NO_HI;
+    smax[t] = hi;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+      const int32_t v = t >= d ? max(smax[t], smax[t - d]) : smax[t];
+      __syncthreads();
+      smax[t] = v;
+      __syncthreads();
+    }
+    const int32_t before = max(cmax, t ? smax[t - 1] : HP_NO_HI);
+    const bool opens = use && lo > before + 2 * S.gap;   // (the first usable entry: lo >= 1 > HP_NO_HI + 64)
+    ssum[t] = opens ? 1 : 0;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+      const int32_t v = t >= d ? ssum[t] + ssum[t - d] : ssum[t];
+      __syncthreads();
+      ssum[t] = v;
+      __syncthreads();
+    }
+    const int32_t idx = ccnt + ssum[t] - 1;
+    if (j < S.xn) S.esite[j] = use ? idx : -1;
+    if (opens) S.sfirst[idx] = (int32_t)j;
+    cmax = max(cmax, smax[255]);
+    ccnt += ssum[255];
+    __syncthreads();
+  }
+  if (t == 0) {
+    S.n_sites[0] = ccnt;
+    S.sfirst[ccnt] = (int32_t)S.xn;
+  }
+}
+
+// a lane per site: the window over the footprints of its usable entries
+__global__ __launch_bounds__(256) void k_hap_windows(HapSites S) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S.n_sites[0]) return;
+  int32_t lo = 0x7fffffff, hi = HP_NO_HI;
+  for (int32_t j = S.sfirst[s]; j < S.sfirst[s + 1]; ++j) {
+    if (S.ewhy[j]) continue;
+    lo = min(lo, S.elo[j]);
+    hi = max(hi, S.ehi[j]);
+  }
+  S.slo[s] = max(1, lo - S.gap);
+  S.shi[s] = (int32_t)min(S.len + 1, (int64_t)hi + S.gap);
+}
+
+// ---- the records ----
+// One workgroup per HAP_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte accesses).  Every kept
+// record adds to its columns of the workgroup's LDS row, which goes to the VCF's row when the VCF changes.  A kept, usable,
+// unmatched record inside the window of a site that is not TOOLONG stays HAP_PENDING for k_hap_claim.
+__global__ __launch_bounds__(256) void k_hap_records(HapRecParams P) {
+  __shared__ uint32_t hist[HAP_R_COLS];   // at most HAP_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  if (threadIdx.x < HAP_R_COLS) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  const int s0 = blockIdx.x * HAP_SPANS;
+  const int s1 = min(s0 + HAP_SPANS, P.n_spans);
+  int cur = -1;
+  auto flush = [&]() {   // (uniform over the workgroup)
+    __syncthreads();
+    if (threadIdx.x < HAP_R_COLS && hist[threadIdx.x]) {
+      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * HAP_R_COLS + threadIdx.x), (unsigned long long)hist[threadIdx.x]);
+      hist[threadIdx.x] = 0u;
+    }
+    __syncthreads();
+  };
+  for (int s = s0; s < s1; ++s) {
+    const SpanDesc sd = P.spans[s];
+    if (sd.vcf != cur) {
+      if (cur >= 0) flush();
+      cur = sd.vcf;
+    }
+    const HapVcf& V = P.vcfs[cur];
+    if (!V.s.words) continue;   // (uniform over the workgroup)
+    const int32_t ns = V.s.n_sites[0];
+    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
+      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
+      if (g >= sd.end) continue;
+      const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (bits and columns past the VCF's last record are not defined)
+      const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & 15u;
+      const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
+      const hp_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const hp_int4*>(P.pos + g));   // read once
+      const hp_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const hp_int4*>(P.ref + g));
+      const hp_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const hp_int4*>(P.alt + g));
+      const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
+      hp_int4 st4 = {-1, -1, -1, -1};
+      uint32_t c4 = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= nrec) continue;
+        const bool kept = (kb >> k) & 1u, tp = (tb >> k) & 1u, nokey = ((f4 >> (8 * k)) & QMF_NOKEY) != 0u;
+        const int32_t p = p4[k], r = r4[k], a = a4[k];
+        int64_t e = -1;
+        if (!nokey && allele_valid(r) && allele_valid(a) && (uint32_t)p < (1u << 28)) e = hp_entry(V.s, p, r, a);
+        const uint32_t why = hp_why(V.s.words, V.s.len, p, r, a, nokey);
+        int32_t st = -1;
+        if (!why) {
+          int32_t q;
+          uint32_t tr, ta, ab;
+          hp_trim(p, r, a, q, tr, ta, ab);
+          st = hp_site(V.s, ns, q, max(q, q + (int32_t)tr - 1));
+        }
+        uint32_t c;
+        if (e >= 0) c = HAP_MATCHED;
+        else if (why) c = why;
+        else if (!kept) c = HAP_NOTKEPT;
+        else if (st < 0) c = HAP_OUTSIDE;
+        else c = V.s.shi[st] - V.s.slo[st] + 1 > HAP_MAX_WINDOW ? HAP_TOOLONG : HAP_PENDING;
+        st4[k] = st;
+        c4 |= c << (8 * k);
+        if (!kept) continue;
+        atomicAdd(hist + HAP_R_KEPT, 1u);
+        if (tp) {
+          atomicAdd(hist + HAP_R_TP, 1u);
+          atomicAdd(hist + HAP_R_TP_H, 1u);
+        }
+        if (e >= 0) {
+          const uint32_t bit = 1u << ((uint32_t)e & 31u);
+          if (!(V.ebits[e >> 5] & bit)) atomicOr(V.ebits + (e >> 5), bit);   // (a stale read only repeats the atomic)
+        } else {
+          if (c == HAP_PENDING || c == HAP_TOOLONG) atomicAdd(hist + HAP_R_OPEN, 1u);
+          if (c != HAP_PENDING) atomicAdd(hist + HAP_R_CLASS0 + c, 1u);
+        }
+      }
+      *reinterpret_cast<uint32_t*>(P.cls + g) = c4;
+      *reinterpret_cast<hp_int4*>(P.site + g) = st4;
+    }
+  }
+  if (cur >= 0) flush();
+}
+
+// ---- the truth side ----
+// grid (x, VCF), a lane per entry of the VCF's truth set: found, unusable or open; an open entry marks its site unless the
+// site is TOOLONG
+__global__ __launch_bounds__(256) void k_hap_truth(const HapVcf* vcfs, unsigned long long* tru) {
+  const HapVcf& V = vcfs[blockIdx.y];
+  if (!V.s.words) return;   // (uniform over the workgroup)
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool found = false, bad = false, open = false;
+  if (j < V.s.xn) {
+    found = (V.ebits[j >> 5] >> ((uint32_t)j & 31u)) & 1u;
+    const uint32_t why = V.s.ewhy[j];
+    bad = why != 0u;
+    open = !found && !bad;
+    uint32_t c = found ? HAP_MATCHED : why;
+    if (open) {
+      const int32_t s = V.s.esite[j];
+      const bool toolong = V.s.shi[s] - V.s.slo[s] + 1 > HAP_MAX_WINDOW;
+      c = toolong ? HAP_TOOLONG : HAP_LONE;   // (LONE until k_hap_replay says what became of the site)
+      const uint32_t bit = 1u << ((uint32_t)s & 31u);
+      if (!toolong && !(V.sbits[s >> 5] & bit)) atomicOr(V.sbits + (s >> 5), bit);
+    }
+    if (V.ecls) V.ecls[j] = (uint8_t)c;
+  }
+  unsigned long long* o = tru + (int64_t)blockIdx.y * HAP_T_COLS;
+  const uint64_t mf = __ballot(found), mb = __ballot(bad), mo = __ballot(open);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (mf) {
+      atomicAdd(o + HAP_T_FOUND, (unsigned long long)__popcll(mf));
+      atomicAdd(o + HAP_T_FOUND_H, (unsigned long long)__popcll(mf));
+    }
+    if (mo) atomicAdd(o + HAP_T_OPEN, (unsigned long long)__popcll(mo));
+    if (mb) atomicAdd(o + HAP_T_UNUSABLE, (unsigned long long)__popcll(mb));
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    o[HAP_T_ENTRIES] = (unsigned long long)V.s.xn;
+    o[HAP_T_SITES] = (unsigned long long)V.s.n_sites[0];
+  }
+}
+
+// One workgroup, VCF after VCF: the number of marked sites before every word of a VCF's bitmap, counted over all VCFs, so that
+// the pair of (VCF, site) is one load and one popcount away; total[0] = the number of pairs.
+__global__ __launch_bounds__(256) void k_hap_rank(const HapVcf* vcfs, int n_vcf, unsigned long long* total) {
+  __shared__ uint32_t ssum[256];
+  const int t = (int)threadIdx.x;
+  uint32_t run = 0u;
+  for (int v = 0; v < n_vcf; ++v) {
+    const HapVcf& V = vcfs[v];
+    if (!V.s.words) continue;
+    const int64_t nw = ((int64_t)V.s.n_sites[0] + 31) / 32;
+    for (int64_t base = 0; base < nw; base += 256) {
+      const int64_t w = base + t;
+      const uint32_t n = w < nw ? (uint32_t)__popc(V.sbits[w]) : 0u;
+      ssum[t] = n;
+      __syncthreads();
+      for (int d = 1; d < 256; d <<= 1) {
+        const uint32_t x = t >= d ? ssum[t] + ssum[t - d] : ssum[t];
+        __syncthreads();
+        ssum[t] = x;
+        __syncthreads();
+      }
+      if (w < nw) V.srank[w] = run + ssum[t] - n;
+      run += ssum[255];
+      __syncthreads();
+    }
+  }
+  if (t == 0) total[0] = run;
+}
+
+// grid (x, VCF), a lane per word of the VCF's bitmap: names the pairs of its marked sites, no open line yet
+__global__ __launch_bounds__(256) void k_hap_pairs(const HapVcf* vcfs, int32_t* pairs) {
+  const HapVcf& V = vcfs[blockIdx.y];
+  if (!V.s.words) return;
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= ((int64_t)V.s.n_sites[0] + 31) / 32) return;
+  uint32_t bits = V.sbits[w];
+  int64_t pair = V.srank[w];
+  while (bits) {
+    const int b = __builtin_ctz(bits);
+    bits &= bits - 1u;
+    int32_t* pr = pairs + pair * HAP_PAIR_WORDS;
+    pr[0] = (int32_t)blockIdx.y;
+    pr[1] = (int32_t)(w * 32 + b);
+    pr[2] = 0;
+    ++pair;
+  }
+}
+
+// The span walk again, over the class bytes alone: a pending line whose site has no open entry is LONE; every other one takes a
+// slot of its pair with one atomic add -- past HAP_MAX_ITEMS it only marks the pair, and is TOOMANY itself.
+__global__ __launch_bounds__(256) void k_hap_claim(HapRecParams P) {
+  __shared__ uint32_t hist[2];
+  if (threadIdx.x < 2) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  const int s0 = blockIdx.x * HAP_SPANS;
+  const int s1 = min(s0 + HAP_SPANS, P.n_spans);
+  int cur = -1;
+  auto flush = [&]() {   // (uniform over the workgroup)
+    __syncthreads();
+    if (threadIdx.x < 2 && hist[threadIdx.x]) {
+      const int col = HAP_R_CLASS0 + (int)(threadIdx.x ? HAP_TOOMANY : HAP_LONE);
+      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * HAP_R_COLS + col), (unsigned long long)hist[threadIdx.x]);
+      hist[threadIdx.x] = 0u;
+    }
+    __syncthreads();
+  };
+  for (int s = s0; s < s1; ++s) {
+    const SpanDesc sd = P.spans[s];
+    if (sd.vcf != cur) {
+      if (cur >= 0) flush();
+      cur = sd.vcf;
+    }
+    const HapVcf& V = P.vcfs[cur];
+    if (!V.s.words) continue;   // (uniform over the workgroup)
+    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
+      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
+      if (g >= sd.end) continue;
+      const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);
+      const uint32_t c4 = *reinterpret_cast<const uint32_t*>(P.cls + g);
+      uint32_t o4 = c4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if ((uint32_t)k >= nrec || ((c4 >> (8 * k)) & 255u) != HAP_PENDING) continue;
+        const int32_t st = P.site[g + k];
+        const uint32_t word = V.sbits[st >> 5], below = (1u << ((uint32_t)st & 31u)) - 1u;
+        uint32_t c = HAP_LONE;
+        if ((word >> ((uint32_t)st & 31u)) & 1u) {
+          int32_t* pr = P.pairs + ((int64_t)V.srank[st >> 5] + __popc(word & below)) * HAP_PAIR_WORDS;
+          const int32_t slot = atomicAdd(pr + 2, 1);
+          c = HAP_PENDING;   // (k_hap_replay writes it)
+          if (slot < HAP_MAX_ITEMS) pr[3 + slot] = (int32_t)(g + k - V.off);
+          else c = HAP_TOOMANY;
+        }
+        if (c == HAP_LONE) atomicAdd(hist, 1u);
+        if (c == HAP_TOOMANY) atomicAdd(hist + 1, 1u);
+        o4 = (o4 & ~(255u << (8 * k))) | (c << (8 * k));
+      }
+      if (o4 != c4) *reinterpret_cast<uint32_t*>(P.cls + g) = o4;
+    }
+  }
+  if (cur >= 0) flush();
+}
+
+// ---- the replay ----
+// One wave (a workgroup of its own) per pair.  Lanes 0 .. 7 hold the open lines, lanes 8 .. 15 the open entries; identical
+// spellings of a side collapse, every remaining item takes its rank by (q, |r|, lane) among its side, neighbours in that order
+// are tested for a conflict, and the output offset of every ALT piece is its window offset plus the length deltas before it.
+// The two replays are never stored: lane t computes symbols t, t + 64, ... of both and compares them.
+__global__ __launch_bounds__(64) void k_hap_replay(HapReplayParams P) {
+  __shared__ int32_t ent[HAP_MAX_ITEMS];
+  __shared__ int32_t it_p[16], it_r[16], it_a[16], it_q[16];
+  __shared__ uint32_t it_lr[16], it_dup[16];
+  __shared__ int32_t vq[2][HAP_MAX_ITEMS], vst[2][HAP_MAX_ITEMS];
+  __shared__ uint32_t vlr[2][HAP_MAX_ITEMS], vla[2][HAP_MAX_ITEMS], vab[2][HAP_MAX_ITEMS];
+  __shared__ int32_t tot[2], dlt[2];
+  const int t = (int)threadIdx.x;
+  const int32_t* pr = P.pairs + (int64_t)blockIdx.x * HAP_PAIR_WORDS;
+  const int32_t v = pr[0], s = pr[1], cnt = pr[2];
+  if (cnt <= 0) return;   // (uniform: no open line, the site is not tried)
+  const HapVcf& V = P.vcfs[v];
+  const HapSites& S = V.s;
+  const int nrec = min(cnt, HAP_MAX_ITEMS);
+  const int32_t e0 = S.sfirst[s], e1 = S.sfirst[s + 1];
+  int nent = 0;
+  for (int32_t b = e0; b < e1; b += 64) {
+    const int32_t j = b + t;
+    const bool open = j < e1 && S.ewhy[j] == 0 && !((V.ebits[j >> 5] >> ((uint32_t)j & 31u)) & 1u);
+    const uint64_t m = __ballot(open);
+    if (open) {
+      const int r = nent + __popcll(m & ((1ull << t) - 1ull));
+      if (r < HAP_MAX_ITEMS) ent[r] = j;
+    }
+    nent += __popcll(m);
+  }
+  __syncthreads();
+  uint32_t outcome = HAP_TOOMANY;
+  if (cnt <= HAP_MAX_ITEMS && nent <= HAP_MAX_ITEMS) {
+    const int side = t >> 3, k = t & 7;
+    const bool have = t < 16 && k < (side ? nent : nrec);
+    int32_t p = 0, r = 0, a = 1, q = 0;
+    uint32_t tr = 0u, ta = 0u, ab = 0u;
+    if (have) {
+      if (side) {
+        const int32_t j = ent[k];
+        p = (int32_t)(S.xkeys[j] >> 4); r = S.xref[j]; a = S.xalt[j];
+      } else {
+        const int64_t gi = V.off + pr[3 + k];
+        p = P.pos[gi]; r = P.ref[gi]; a = P.alt[gi];
+      }
+      hp_trim(p, r, a, q, tr, ta, ab);
+    }
+    if (t < 16) { it_p[t] = p; it_r[t] = r; it_a[t] = a; it_q[t] = q; it_lr[t] = tr; }
+    __syncthreads();
+    bool dup = false;
+    if (have)
+      for (int i = side * 8; i < t; ++i) dup = dup || (it_p[i] == p && it_r[i] == r && it_a[i] == a);
+    if (t < 16) it_dup[t] = (!have || dup) ? 1u : 0u;
+    __syncthreads();
+    if (have && !dup) {
+      int rank = 0;
+      for (int i = side * 8; i < side * 8 + 8; ++i) {
+        if (it_dup[i] || i == t) continue;
+        const bool less = it_q[i] != q ? it_q[i] < q : it_lr[i] != tr ? it_lr[i] < tr : i < t;
+        rank += less ? 1 : 0;
+      }
+      vq[side][rank] = q; vlr[side][rank] = tr; vla[side][rank] = ta; vab[side][rank] = ab;
+    }
+    const uint64_t mk = __ballot(have && !dup);
+    const int nv0 = __popcll(mk & 0xffull), nv1 = __popcll(mk & 0xff00ull);
+    __syncthreads();
+    const int nvs = side ? nv1 : nv0;
+    bool bad = false;
+    if (t < 16 && k + 1 < nvs) {
+      const int32_t qa = vq[side][k], qb = vq[side][k + 1];
+      bad = qb < qa + (int32_t)vlr[side][k] || (qb == qa && vlr[side][k + 1] == 0u);
+    }
+    if (__ballot(bad)) {
+      outcome = HAP_CONFLICT;
+    } else {
+      const int32_t ws = S.slo[s], wend = (int32_t)min((int64_t)S.shi[s], S.len);
+      if (t < 2) {   // (side t: at most eight pieces)
+        int32_t d = 0;
+        const int n = t ? nv1 : nv0;
+        for (int i = 0; i < n; ++i) {
+          vst[t][i] = vq[t][i] - ws + d;
+          d += (int32_t)vla[t][i] - (int32_t)vlr[t][i];
+        }
+        dlt[t] = d;
+        tot[t] = wend - ws + 1 + d;
+      }
+      __syncthreads();
+      bool differ = tot[0] != tot[1];
+      if (!differ) {
+        for (int32_t o = t; o < tot[0]; o += 64) {
+          uint32_t sym[2];
+#pragma unroll
+          for (int sd = 0; sd < 2; ++sd) {
+            const int n = sd ? nv1 : nv0;
+            int32_t gq = ws + o - dlt[sd];   // behind the last piece
+            uint32_t c = 16u;
+            for (int i = 0; i < n; ++i) {
+              const int32_t b0 = vst[sd][i];
+              if (o < b0) { gq = o - b0 + vq[sd][i]; break; }
+              if (o < b0 + (int32_t)vla[sd][i]) { c = (vab[sd][i] >> (2 * (o - b0))) & 3u; break; }
+            }
+            sym[sd] = c < 16u ? c : hp_base(S.words, gq);
+          }
+          differ = differ || sym[0] != sym[1];
+        }
+      }
+      outcome = __ballot(differ) ? HAP_MISMATCH : HAP_RESCUED;
+    }
+  }
+  // what became of the site, to its lines and entries
+  bool gained = false;
+  if (t < nrec) {
+    const int64_t gi = V.off + pr[3 + t];
+    P.cls[gi] = (uint8_t)outcome;
+    if (outcome == HAP_RESCUED) gained = (P.flags[gi] & QMF_IDDOT) && !((P.mask_tp[gi >> 6] >> (int)(gi & 63)) & 1ull);
+  }
+  const uint64_t mg = __ballot(gained);
+  if (V.ecls)
+    for (int32_t j = e0 + t; j < e1; j += 64)
+      if (S.ewhy[j] == 0 && !((V.ebits[j >> 5] >> ((uint32_t)j & 31u)) & 1u)) V.ecls[j] = (uint8_t)outcome;
+  if (t == 0) {
+    unsigned long long* orec = reinterpret_cast<unsigned long long*>(P.rec) + (int64_t)v * HAP_R_COLS;
+    unsigned long long* otru = reinterpret_cast<unsigned long long*>(P.tru) + (int64_t)v * HAP_T_COLS;
+    atomicAdd(otru + HAP_T_TRIED, 1ull);
+    if (outcome == HAP_RESCUED) {
+      atomicAdd(otru + HAP_T_MATCHED, 1ull);
+      atomicAdd(otru + HAP_T_FOUND_H, (unsigned long long)nent);
+      if (mg) {
+        atomicAdd(orec + HAP_R_TP_H, (unsigned long long)__popcll(mg));
+        atomicAdd(orec + HAP_R_RESCUED, (unsigned long long)__popcll(mg));
+      }
+    } else {
+      atomicAdd(orec + HAP_R_CLASS0 + outcome, (unsigned long long)nrec);
+    }
+  }
+}
+
+// ---- launchers ----
+void launch_hap_sites(const HapSites& S, hipStream_t st) {
+  if (S.xn > 0) hipLaunchKernelGGL(k_hap_entries, dim3((unsigned)((S.xn + 255) / 256)), dim3(256), 0, st, S);
+  hipLaunchKernelGGL(k_hap_sites, dim3(1), dim3(256), 0, st, S);
+  if (S.xn > 0) hipLaunchKernelGGL(k_hap_windows, dim3((unsigned)((S.xn + 255) / 256)), dim3(256), 0, st, S);
+}
+
+void launch_hap_records(const HapRecParams& P, hipStream_t st) {
+  if (P.n_spans <= 0) return;
+  hipLaunchKernelGGL(k_hap_records, dim3((unsigned)((P.n_spans + HAP_SPANS - 1) / HAP_SPANS)), dim3(256), 0, st, P);
+}
+
+// (the y dimension of a grid holds 65535 blocks: qm_batch_haplotypes refuses a batch of more VCFs)
+void launch_hap_truth(const HapVcf* vcfs, int n_vcf, int64_t max_entries, uint64_t* tru, unsigned long long* total, hipStream_t st) {
+  if (n_vcf > 0 && max_entries > 0)
+    hipLaunchKernelGGL(k_hap_truth, dim3((unsigned)((max_entries + 255) / 256), (unsigned)n_vcf), dim3(256), 0, st, vcfs,
+                       reinterpret_cast<unsigned long long*>(tru));
+  hipLaunchKernelGGL(k_hap_rank, dim3(1), dim3(256), 0, st, vcfs, n_vcf, total);
+}
+
+void launch_hap_claim(const HapRecParams& P, int n_vcf, int64_t max_entries, hipStream_t st) {
+  if (n_vcf <= 0 || max_entries <= 0 || P.n_spans <= 0) return;
+  const unsigned gx = (unsigned)((max_entries / 32 + 1 + 255) / 256);
+  const HapVcf* vcfs = P.vcfs;
+  int32_t* pairs = P.pairs;
+  hipLaunchKernelGGL(k_hap_pairs, dim3(gx, (unsigned)n_vcf), dim3(256), 0, st, vcfs, pairs);
+  hipLaunchKernelGGL(k_hap_claim, dim3((unsigned)((P.n_spans + HAP_SPANS - 1) / HAP_SPANS)), dim3(256), 0, st, P);
+}
+
+void launch_hap_replay(const HapReplayParams& P, hipStream_t st) {
+  if (P.n_pairs <= 0) return;
+  hipLaunchKernelGGL(k_hap_replay, dim3((unsigned)P.n_pairs), dim3(64), 0, st, P);
+}
+
+}  // namespace qm

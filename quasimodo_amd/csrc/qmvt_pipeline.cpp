@@ -299,7 +299,7 @@ struct Passes {
   const qm_profile_args* pa = nullptr; const qm_strata_args* sa = nullptr; const qm_boot_args* ba = nullptr;
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
-  const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr;
+  const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr; const qm_haplotypes_args* hp = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -835,6 +835,136 @@ int types_pass(const PassCtx& c, const qm_types_args* ty, std::string& err) {
   return QM_OK;
 }
 
+// ---- clusters of records matched by replayed haplotype ----
+struct HpColumns { std::vector<uint8_t> cls, ecls; std::vector<int32_t> site; };
+struct HpSites { std::vector<int32_t> first, lo, hi; };
+// the trimmed form of two different strings over ACGT: the common prefix goes first, then the common suffix of what is left
+struct HpForm { int64_t q; std::string r, a; };
+HpForm hp_trim(int64_t p, const std::string& R, const std::string& A) {
+  const size_t m = std::min(R.size(), A.size());
+  size_t cp = 0, cs = 0;
+  while (cp < m && R[cp] == A[cp]) ++cp;
+  while (cs < m - cp && R[R.size() - 1 - cs] == A[A.size() - 1 - cs]) ++cs;
+  return HpForm{p + (int64_t)cp, R.substr(cp, R.size() - cp - cs), A.substr(cp, A.size() - cp - cs)};
+}
+// the window [ws, we] of the genome with the variants of one side substituted (identical spellings collapsed, sorted by (q, |r|):
+// the site is a MATCH one, so they do not conflict)
+std::string hp_replay(const uint8_t* seq, int64_t len, int64_t ws, int64_t we, std::vector<HpForm> v) {
+  std::sort(v.begin(), v.end(), [](const HpForm& x, const HpForm& y) { return x.q != y.q ? x.q < y.q : x.r.size() != y.r.size() ? x.r.size() < y.r.size() : x.a < y.a; });
+  v.erase(std::unique(v.begin(), v.end(), [](const HpForm& x, const HpForm& y) { return x.q == y.q && x.r == y.r && x.a == y.a; }), v.end());
+  std::string out;
+  auto genome = [&](int64_t from, int64_t to) {   // G[from .. to]
+    for (int64_t q = std::max<int64_t>(from, 1); q <= std::min(to, len); ++q) {
+      const char ch = (char)(seq[q - 1] & ~0x20);
+      out.push_back(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' ? ch : 'N');
+    }
+  };
+  int64_t cur = ws;
+  for (const HpForm& f : v) { genome(cur, f.q - 1); out += f.a; cur = f.q + (int64_t)f.r.size(); }
+  genome(cur, we);
+  return out;
+}
+// `#site WIN_LO WIN_HI LINES ENTRIES REPLAY_LINES REPLAY_TRUTH`, one row per MATCH site of the job in site order
+int write_sites_file(const char* path, const JobState& s, const HpColumns& c, const NzEntries& t, const HpSites& st, const uint8_t* seq, int64_t len) {
+  std::string out = "#site\tWIN_LO\tWIN_HI\tLINES\tENTRIES\tREPLAY_LINES\tREPLAY_TRUTH\n";
+  const uint8_t* text = s.vcf.p;
+  const size_t tlen = s.vcf.n;
+  const size_t ns = st.first.size();
+  std::vector<std::string> lines(ns);
+  std::vector<std::vector<HpForm>> side(ns);
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    const int64_t r = rec++;
+    if (c.cls[(size_t)r] != QM_HAP_C_RESCUED) continue;
+    const int32_t k = c.site[(size_t)r];
+    if (k < 0 || (size_t)k >= ns) continue;
+    size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], tlen);
+    if (e > b && text[e - 1] == '\n') --e;
+    const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+    const uint8_t* q = text + b;
+    while (nf < 6) {
+      const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(text + e - q));
+      f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(text + e - q); ++nf;
+      if (!tb) break;
+      q = tb + 1;
+    }
+    if (nf < 5) continue;
+    std::string& L = lines[(size_t)k];
+    if (!L.empty()) L.push_back(';');
+    L += std::to_string(i + 1);
+    for (int x : {1, 3, 4}) { L.push_back(':'); L.append((const char*)f[x], fl[x]); }
+    side[(size_t)k].push_back(hp_trim(s.pos[r], nz_spell(s.ref[r]), nz_spell(s.alt[r])));
+  }
+  for (size_t k = 0; k < ns; ++k) {
+    if (lines[k].empty()) continue;
+    const size_t e0 = (size_t)st.first[k], e1 = k + 1 < ns ? (size_t)st.first[k + 1] : t.pos.size();
+    std::string ents;
+    std::vector<HpForm> tside;
+    for (size_t j = e0; j < e1; ++j) {
+      if (c.ecls[j] != QM_HAP_C_RESCUED) continue;
+      if (!ents.empty()) ents.push_back(';');
+      ents += std::to_string(t.pos[j]) + ":" + nz_spell(t.ref[j]) + ":" + nz_spell(t.alt[j]);
+      tside.push_back(hp_trim(t.pos[j], nz_spell(t.ref[j]), nz_spell(t.alt[j])));
+    }
+    out += std::to_string(k) + "\t" + std::to_string(st.lo[k]) + "\t" + std::to_string(st.hi[k]) + "\t" + lines[k] + "\t" + ents + "\t" +
+           hp_replay(seq, len, st.lo[k], st.hi[k], side[k]) + "\t" + hp_replay(seq, len, st.lo[k], st.hi[k], tside) + "\n";
+  }
+  return write_all_atomic(path, out);
+}
+
+// the counts of every wanted job, and the sites files of the jobs that name one
+int haplo_pass(const PassCtx& c, const qm_haplotypes_args* ha, std::string& err) {
+  if (!ha) return QM_OK;
+  auto want = [&](int j) { return !c.jobs[j].pure && ha->genome_id[j] >= 0; };
+  if (!c.any(want)) return QM_OK;
+  auto path = [&](int j) { return want(j) && ha->sites_out ? ha->sites_out[j] : nullptr; };
+  std::vector<int32_t> gid(c.nv, -1);
+  bool files = false;
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) { gid[(size_t)c.J[(size_t)j].batch_v] = ha->genome_id[j]; files = files || path(j); }
+  std::vector<uint64_t> rec(c.nv * QM_HAP_R_COLS), tru(c.nv * QM_HAP_T_COLS);
+  int rc = qm_batch_haplotypes(c.batch, gid.data(), ha->gap, files ? QM_HAP_COLUMNS : 0u, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_haplotypes(c.batch, rec.data(), tru.data());
+  if (rc == QM_OK) { c.scatter_rows(ha->rec, rec, QM_HAP_R_COLS, want); c.scatter_rows(ha->tru, tru, QM_HAP_T_COLS, want); }
+  struct Task { int j; HpColumns cols; };
+  std::vector<Task> W;
+  std::vector<NzEntries> ent(c.T.size());
+  std::vector<HpSites> sites(c.T.size());
+  std::vector<uint8_t> have(c.T.size(), 0);
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    if (!path(j)) continue;
+    const JobState& s = c.J[(size_t)j];
+    const size_t n = (size_t)s.n_data + 1;
+    if (!have[(size_t)s.truth]) {
+      NzEntries& e = ent[(size_t)s.truth];
+      HpSites& st = sites[(size_t)s.truth];
+      int64_t tn = 0, sn = 0;
+      (void)qm_truth_entries(c.ctx, c.truth_of(j).tid, nullptr, nullptr, nullptr, 0, &tn);   // (how many)
+      e.pos.resize((size_t)tn + 1); e.ref.resize((size_t)tn + 1); e.alt.resize((size_t)tn + 1);
+      rc = qm_truth_entries(c.ctx, c.truth_of(j).tid, e.pos.data(), e.ref.data(), e.alt.data(), tn, &tn);
+      e.pos.resize((size_t)tn); e.ref.resize((size_t)tn); e.alt.resize((size_t)tn);
+      st.first.resize((size_t)tn + 1); st.lo.resize((size_t)tn + 1); st.hi.resize((size_t)tn + 1);
+      if (rc == QM_OK) rc = qm_truth_sites(c.ctx, c.truth_of(j).tid, ha->genome_id[j], ha->gap, st.first.data(), st.lo.data(), st.hi.data(), tn + 1, &sn);
+      st.first.resize((size_t)sn); st.lo.resize((size_t)sn); st.hi.resize((size_t)sn);
+      have[(size_t)s.truth] = 1;
+    }
+    if (rc != QM_OK) break;
+    W.push_back({j, HpColumns{std::vector<uint8_t>(n, 0), std::vector<uint8_t>(ent[(size_t)s.truth].pos.size() + 1, 0), std::vector<int32_t>(n, -1)}});
+    HpColumns& k = W.back().cols;
+    rc = qm_batch_get_haplotyped(c.batch, s.batch_v, k.cls.data(), k.site.data(), k.ecls.data());
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  std::vector<int> wrc(W.size(), QM_OK);
+  parallel_for((int)W.size(), c.nthr, [&](int k) {
+    const Task& w = W[(size_t)k];
+    const size_t t = (size_t)c.J[(size_t)w.j].truth;
+    wrc[(size_t)k] = write_sites_file(ha->sites_out[w.j], c.J[(size_t)w.j], w.cols, ent[t], sites[t], ha->genome_seq[w.j], ha->genome_len[w.j]);
+  });
+  for (size_t k = 0; k < W.size(); ++k)
+    if (wrc[k] != QM_OK) { err = std::string("cannot write ") + ha->sites_out[W[k].j]; return wrc[k]; }
+  return QM_OK;
+}
+
 // the filter surface: S and extra of every wanted job
 int surface_pass(const PassCtx& c, const qm_surface_args* sf, std::string& err) {
   auto want = [&](int j) { return sf->want[j] != 0; };
@@ -1011,6 +1141,27 @@ extern "C" int qm_extract_files_types(qm_ctx* ctx, int n_jobs, const qm_file_job
     memset(ty->tru, 0, sizeof(uint64_t) * w * (size_t)n_jobs);
   }
   Passes P; P.ty = ty;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// clusters of records matched by replayed haplotype behind the worker
+extern "C" int qm_extract_files_haplotypes(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                           qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                           int n_slots, void* global_dev, const qm_haplotypes_args* haplotypes) {
+  const qm_haplotypes_args* ha = haplotypes;
+  if (!ha || (n_jobs > 0 && (!ha->genome_id || !ha->rec || !ha->tru))) return fail(QM_E_INVAL, "qm_extract_files_haplotypes: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_haplotypes: haplotypes are replayed from indels, MNPs and complex records, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (ha->gap < 0 || ha->gap > QM_HAP_MAX_GAP)
+    return fail(QM_E_INVAL, "qm_extract_files_haplotypes: gap " + std::to_string(ha->gap) + " (0 to " + std::to_string(QM_HAP_MAX_GAP) + ")");
+  for (int j = 0; j < n_jobs; ++j)
+    if (ha->sites_out && ha->sites_out[j] && ha->genome_id[j] >= 0 && (!ha->genome_seq || !ha->genome_len || !ha->genome_seq[j] || ha->genome_len[j] < 1))
+      return fail(QM_E_INVAL, "qm_extract_files_haplotypes: job " + std::to_string(j) + " names a sites file and not the bytes of its genome");
+  if (n_jobs > 0) {
+    memset(ha->rec, 0, sizeof(uint64_t) * QM_HAP_R_COLS * (size_t)n_jobs);
+    memset(ha->tru, 0, sizeof(uint64_t) * QM_HAP_T_COLS * (size_t)n_jobs);
+  }
+  Passes P; P.hp = ha;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -1372,6 +1523,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = normalize_pass(pc, P, err);
       if (rc == QM_OK) rc = atomize_pass(pc, P, err);
       if (rc == QM_OK) rc = types_pass(pc, P.ty, err);
+      if (rc == QM_OK) rc = haplo_pass(pc, P.hp, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

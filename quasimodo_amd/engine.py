@@ -132,6 +132,16 @@ class Engine:
         check(self._L.qm_truth_normalized(self._h, int(tid), int(gid), _p(pos), _p(ref), _p(alt), cap, C.byref(n)), self._h)
         return pos[:n.value], ref[:n.value], alt[:n.value]
 
+    def truth_sites(self, tid, gid, gap=None):
+        """qm_truth_sites: (first_entry, lo, hi) int32 -- the sites (haplo.py) of a truth set's allele-extended
+        entries against a loaded genome: the first entry and the window of each, from the kernels the pass uses"""
+        from .haplo import check_gap
+        cap = max(self.truth_size(tid, alleles=True), 1)
+        first, lo, hi = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int64()
+        check(self._L.qm_truth_sites(self._h, int(tid), int(gid), check_gap(gap), _p(first), _p(lo), _p(hi), cap, C.byref(n)), self._h)
+        return first[:n.value], lo[:n.value], hi[:n.value]
+
     def truth_atoms(self, tid):
         """qm_truth_atoms: uint32 -- the atom set (atomize.py) of a truth set's allele-extended entries, each atom
         (pos << 4) | (ref << 2) | alt, sorted ascending, from the kernel the pass uses"""
@@ -236,7 +246,7 @@ class Engine:
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
                       truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
-                      atomize=None, vartype=None):
+                      atomize=None, vartype=None, haplo=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -279,20 +289,25 @@ class Engine:
         vartype: {"want": [0/1 per job], "edges": None or the size edges} -- qm_extract_files_types (alleles=True
         only): wanted mixed-sample rows gain `type_rec` and `type_tru` ([n_rows][2] uint64, rows vartype.row_names(edges)) and
         `type_edges`.
+        haplo: {"genomes": [genome_load id or None / -1 per job], "gap": None or 0 .. 32, "sites": [path or None per job], "seqs":
+        [the genome's bytes per job that names a sites file]} -- qm_extract_files_haplotypes (alleles=True only):
+        the rows of mixed-sample jobs with a genome gain `hap_rec` ([16] uint64, columns haplo.R_COLS), `hap_tru` ([8],
+        haplo.T_COLS) and `hap_gap`; the sites files are written.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_atomize, check_normalize, check_shared_call, check_vartype
+        from .passes import check_atomize, check_haplo, check_normalize, check_shared_call, check_vartype
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "vartype": vartype, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "vartype": vartype, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_atomize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_vartype({name for name, spec in specs.items() if spec is not None}, alleles)
+        check_haplo({name for name, spec in specs.items() if spec is not None}, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -427,6 +442,26 @@ class Engine:
         took = lambda k: twant[k] and not file_jobs[k].get("pure")
         unpack = lambda k: {"type_rec": trec[k].copy(), "type_tru": ttru[k].copy(), "type_edges": edges} if took(k) else {}
         return self._L.qm_extract_files_types, (C.byref(ta),), unpack
+
+    def _files_haplo(self, n, haplo, file_jobs=(), **kw):
+        from .haplo import check_gap
+        gap = check_gap(haplo.get("gap"))
+        hgid = _c([-1 if g is None else int(g) for g in haplo["genomes"]] or [-1], np.int32)
+        paths = list(haplo.get("sites") or [None] * n)
+        seqs = list(haplo.get("seqs") or [None] * n)
+        if (n and hgid.shape[0] != n) or len(paths) != n or len(seqs) != n:
+            raise ValueError("haplo: %d genomes / %d sites / %d seqs entries for %d jobs" % (len(haplo["genomes"]), len(paths), len(seqs), n))
+        hrec = np.zeros((max(n, 1), _lib.QM_HAP_R_COLS), np.uint64)
+        htru = np.zeros((max(n, 1), _lib.QM_HAP_T_COLS), np.uint64)
+        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        seqs = [None if x is None else bytes(x) for x in seqs]
+        seq_arr = (C.c_char_p * max(n, 1))(*seqs)
+        lens = _c([0 if x is None else len(x) for x in seqs] or [0], np.int64)
+        ha = _lib.HaplotypesArgs(_p(hgid), gap, 0, _p(hrec), _p(htru), out_arr, seq_arr, _p(lens))
+        ha.keep = (hgid, out_arr, seqs, seq_arr, lens)   # (read during the call; the other arrays live in unpack)
+        took = lambda k: hgid[k] >= 0 and not file_jobs[k].get("pure")
+        unpack = lambda k: {"hap_rec": hrec[k].copy(), "hap_tru": htru[k].copy(), "hap_gap": gap} if took(k) else {}
+        return self._L.qm_extract_files_haplotypes, (C.byref(ha),), unpack
 
     def _files_boot(self, n, boot, **kw):
         bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
@@ -939,6 +974,43 @@ class Batch:
         ms = (C.c_float * 2)()
         self._ck(self._L.qm_batch_types_timings(self._h, ms))
         return {"type_records_ms": ms[0], "type_truth_ms": ms[1]}
+
+    # -- clusters of records matched by replayed haplotype ----------------
+    def haplotypes(self, genome_ids, gap=None, columns=False, stream=None, fetch=True):
+        """qm_batch_haplotypes + qm_batch_get_haplotypes (allele-extended batches): (rec [n_vcf][16], tru [n_vcf][8]) uint64,
+        columns haplo.R_COLS / haplo.T_COLS (genome_ids: one genome id or -1 per VCF; gap: 0 .. haplo.MAX_GAP, None:
+        haplo.DEFAULT_GAP); columns=True keeps the class bytes and site indices for haplotyped().  fetch=False: enqueue only
+        (haplotype_counts() waits and copies)"""
+        from .haplo import check_gap
+        g = _c(genome_ids, np.int32)
+        if g.shape[0] != self.n_vcf:
+            raise ValueError("genome_ids: %d entries for %d VCFs" % (g.shape[0], self.n_vcf))
+        self._ck(self._L.qm_batch_haplotypes(self._h, _p(g) if self.n_vcf else _p(np.zeros(1, np.int32)), check_gap(gap),
+                                             _lib.QM_HAP_COLUMNS if columns else 0, C.c_void_p(stream) if stream else None))
+        return self.haplotype_counts() if fetch else None
+
+    def haplotype_counts(self):
+        """qm_batch_get_haplotypes: the counts of the latest haplotypes()"""
+        rec = np.zeros((max(self.n_vcf, 1), _lib.QM_HAP_R_COLS), np.uint64)
+        tru = np.zeros((max(self.n_vcf, 1), _lib.QM_HAP_T_COLS), np.uint64)
+        self._ck(self._L.qm_batch_get_haplotypes(self._h, _p(rec), _p(tru)))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def haplotyped(self, v):
+        """qm_batch_get_haplotyped: (cls uint8 [n] -- the class bytes haplo.CLASS_NAMES --, site int32 [n] -- the site of every
+        usable record, -1 for none --, entry_cls uint8 [entries] -- a class byte per entry of the VCF's truth set) of VCF v in
+        input order, after a haplotypes(columns=True)"""
+        n = int(self.n_records[int(v)])
+        ne = self.engine.truth_size(int(self.truth_ids[int(v)]), alleles=True)
+        cls, site, ecls = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(max(ne, 1), np.uint8)
+        self._ck(self._L.qm_batch_get_haplotyped(self._h, int(v), _p(cls), _p(site), _p(ecls)))
+        return cls[:n], site[:n], ecls[:ne]
+
+    def haplotype_timings(self):
+        """qm_batch_haplotype_timings (set_timing on): milliseconds of the latest haplotypes() between HIP events"""
+        ms = (C.c_float * 5)()
+        self._ck(self._L.qm_batch_haplotype_timings(self._h, ms))
+        return {"hap_sites_ms": ms[0], "hap_records_ms": ms[1], "hap_truth_ms": ms[2], "hap_claim_ms": ms[3], "hap_replay_ms": ms[4]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

@@ -17,6 +17,7 @@ PASSES = (
     Pass("votes", ("vote_group",), ("votes",), "--votes", None, ()),
     Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
     Pass("normalize", ("normalize",), ("normalize",), "--normalize", None, ()),
+    Pass("haplo", ("haplo",), ("haplo",), "--haplotypes", "haplo: the jobs of one call share one gap", ()),
     Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
     Pass("vartype", ("vartype",), ("vartype",), "--by-type", "vartype: the typed jobs of one call share one list of size edges", ()),
     Pass("context", ("context",), ("context",), "--seq-context",
@@ -58,6 +59,13 @@ def check_atomize(requested, alleles):
     """--atomize splits MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
     if "atomize" in requested and not alleles:
         raise ValueError("atomize (--atomize) needs the allele-extended mode (--alleles): a single-base batch holds no MNPs")
+
+
+def check_haplo(requested, alleles):
+    """--haplotypes replays indels, MNPs and complex records, which only the allele-extended mode holds: ValueError before a file
+    is touched"""
+    if "haplo" in requested and not alleles:
+        raise ValueError("haplo (--haplotypes) needs the allele-extended mode (--alleles): a single-base batch holds no indels, MNPs or complex records to replay")
 
 
 def check_vartype(requested, alleles):

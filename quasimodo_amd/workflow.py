@@ -165,7 +165,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          _same_device=False, mutation_context=None, truth_side=False, snp_profile=None, strata=None, bootstrap=None,
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
-                         context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None):
+                         context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None, haplotypes=None,
+                         hap_gap=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -214,12 +215,29 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     WorkflowError before a file is touched otherwise): TP, FP and FN by variant type and size are counted behind the
     classification and final_tables/caller_performance_types.tsv is written (per caller x mixed sample one row per type and size
     bin, a marginal per type, the four rows behind the grid, then a pooled block per caller).
+    haplotypes: {"TM": FASTA, "TA": FASTA}, the genomes as for normalize, with hap_gap (default 10, 0 to 32; quasimodo_amd.haplo,
+    DESIGN.md 4.20; needs alleles, WorkflowError before a file is touched otherwise): the unmatched lines and the unmatched truth
+    entries of every small region are replayed onto the genome and rescued where the two sequences are equal;
+    final_tables/caller_performance_haplotype.tsv (TP, FP, FN, Precision, Recall, F1 by spelling and by haplotype side by side, then
+    the class counts) and callers/{caller}/hap/{sample}.{ref}.{caller}.sites.tsv for every mixed sample.
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
-                 context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False)
+                 context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False,
+                 haplo=haplotypes is not None)
+    hgap = None
+    if haplotypes is not None:
+        from .haplo import check_gap
+        if not alleles:
+            raise WorkflowError("--haplotypes needs --alleles: haplotypes are replayed from indels, MNPs and complex records, which only the allele-extended mode reads")
+        try:
+            hgap = check_gap(hap_gap)
+        except ValueError as e:
+            raise WorkflowError("--hap-gap: %s" % e) from None
+    elif hap_gap is not None:
+        raise WorkflowError("--hap-gap needs --haplotypes")
     tedges = None
     if by_type is not None and by_type is not False:
         from .vartype import check_edges, parse_edges
@@ -283,9 +301,16 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             fa = normalize.get(mix)
             if not fa or not os.path.isfile(fa):
                 raise WorkflowError("normalize: no genome FASTA for %s (%s)" % (mix, fa))
+    if haplotypes is not None:
+        for mix in mixes:
+            fa = haplotypes.get(mix)
+            if not fa or not os.path.isfile(fa):
+                raise WorkflowError("haplotypes: no genome FASTA for %s (%s)" % (mix, fa))
     if dryrun:
         for s, c, src in plan:
             print("extractTP\t%s\t%s" % (c, src))
+        if haplotypes is not None:
+            print("caller_performance_haplotype.tsv\t%s\t%d" % (",".join(callers), hgap))
         if normalize is not None:
             print("caller_performance_normalized.tsv\t%s" % ",".join(callers))
         if atomize:
@@ -366,6 +391,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             jobs[-1].atoms_out = os.path.join(d, "atoms", os.path.basename(src)[:-4] + ".atoms.tsv")
         if tedges is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].vartype = tedges
+        if haplotypes is not None and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].haplo, jobs[-1].haplo_genome = hgap, haplotypes[s[:2]]
+            jobs[-1].sites_out = os.path.join(d, "hap", os.path.basename(src)[:-4] + ".sites.tsv")
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -430,6 +458,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if normalize is not None:
             from .normalize import write_performance_normalized
             write_performance_normalized(os.path.join(tables, "caller_performance_normalized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
+        if haplotypes is not None:
+            from .haplo import write_performance_haplotype
+            write_performance_haplotype(os.path.join(tables, "caller_performance_haplotype.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
         if atomize:
             from .atomize import write_performance_atomized
             write_performance_atomized(os.path.join(tables, "caller_performance_atomized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])

@@ -88,6 +88,13 @@ def _bootstrap_opts(n_rep, window, seed):
     return None if n_rep is None else {"n_rep": n_rep, "window": window, "seed": seed}
 
 
+def _hap_gap(haplotypes, hap_gap):
+    """--haplotypes / --hap-gap -> the gap the workflow takes (None: its default)"""
+    if hap_gap is not None and not haplotypes:
+        raise click.UsageError("--hap-gap needs --haplotypes")
+    return hap_gap
+
+
 def _type_bins(by_type, type_bins):
     """--by-type / --type-bins -> what the workflow takes: None without --by-type, True for the default edges, else the edges' text"""
     if type_bins is not None and not by_type:
@@ -152,6 +159,12 @@ def _type_bins(by_type, type_bins):
                    "final_tables/caller_performance_types.tsv.")
 @click.option("--type-bins", "type_bins", default=None,
               help="--by-type: the ascending lower edges of the size bins, at most 16, the first one 1 [default: 1,2,3,4,5,6,16,51].")
+@click.option("--haplotypes", "haplotypes", is_flag=True, default=False,
+              help="With --alleles: also match clusters of lines by replayed haplotype (the unmatched lines and the unmatched truth entries of a small "
+                   "region, each replayed onto the genome, are rescued where the two sequences are equal): write "
+                   "final_tables/caller_performance_haplotype.tsv and callers/*/hap/*.sites.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config).")
+@click.option("--hap-gap", "hap_gap", type=int, default=None,
+              help="--haplotypes: truth entries at most twice this many bases apart share a region, whose window reaches this far on either side [default: 10; 0 to 32].")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
 @click.option("--ad169-ref", type=click.Path(), default=None, help="AD169 FASTA for TA (default: AD169Ref of config/config.yaml).")
 def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, threads=2, data=None, gpus=1, json_out=None,
@@ -159,7 +172,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False, atomize=False, by_type=False, type_bins=None):
+         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None):
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -174,7 +187,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
     genomes = None
-    if mutation_context or seq_context or normalize:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+    if mutation_context or seq_context or normalize or haplotypes:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
         pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
@@ -191,7 +204,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              filter_surface=filter_surface, surface_qual_step=surface_qual_step,
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
                                              alleles=alleles, normalize=genomes if normalize else None, atomize=atomize,
-                                             by_type=_type_bins(by_type, type_bins))
+                                             by_type=_type_bins(by_type, type_bins), haplotypes=genomes if haplotypes else None,
+                                             hap_gap=_hap_gap(haplotypes, hap_gap))
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -248,13 +262,19 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose variants could be typed (hcmv has it).")
 @click.option("--type-bins", "type_bins", default=None, help="Not available here (see --by-type).")
+@click.option("--haplotypes", "haplotypes", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose lines could be replayed (hcmv has it).")
+@click.option("--hap-gap", "hap_gap", type=int, default=None, help="Not available here (see --haplotypes).")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
             surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False,
-            by_type=False, type_bins=None):
+            by_type=False, type_bins=None, haplotypes=False, hap_gap=None):
     from quasimodo_amd import workflow
     try:
+        if haplotypes or hap_gap is not None:
+            raise workflow.WorkflowError("--haplotypes needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --haplotypes)")
         if by_type or type_bins is not None:
             raise workflow.WorkflowError("--by-type needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --by-type)")
