@@ -1,7 +1,13 @@
 """The planted family of the haplotype tests: a random genome with planted repeats, a truth set and the
 records of one VCF, laid out in slots of SLOT bases so that -- at the default gap -- every planted case is a site of its own.
 The cases are planted, not drawn: a random family would be all LONE and OUTSIDE and prove nothing.  Strings throughout; `codes`
-turns them into the columns the device takes."""
+turns them into the columns the device takes.
+
+What this family does NOT reach (Family(20), the largest one the per-VCF comparisons use: 430 truth entries, 184 sites): a second
+step of k_hap_rank or a second block of k_hap_pairs (six words of the site bitmap), a second gather round of k_hap_replay (no
+site holds more than some 16 entries), anything particular on the 255|256 seam of k_hap_sites, a byte that is no base (the genome
+is pure ACGT), a window clipped at 1 or at L + 1 (the first planted base is at 80, the last slot is empty), alleles of 8 to 13
+bases.  Those are planted by haplo_edges.py."""
 import numpy as np
 
 from quasimodo_amd import haplo as hp

@@ -1,7 +1,10 @@
 """Clusters of records matched by replayed haplotype on the device (qm_batch_haplotypes; qmvt_haplo.hip) against
 the restatement of quasimodo_amd.haplo, exactly: both count blocks, the class bytes, the site indices, the entry classes and
 qm_truth_sites, on the planted family of haplo_family.py; tied to the batch's masks and scalars, to the truth set's table and
--- through the found entries -- to the variant-type pass, an independent kernel.  Every comparison is exact: these are integers."""
+-- through the found entries -- to the variant-type pass, an independent kernel.  Every comparison is exact: these are integers.
+One planted family: it leaves the scans, the bitmap rank and the gather loop on their first iteration, its genome is pure ACGT and
+no window of it touches an end of the genome -- the step seams, more than 8192 sites, more than 64 entries per site, the genome's
+ends, bytes that are no base and every pair of inline lengths are test_gpu_haplo_edges.py's."""
 import numpy as np
 import pytest
 
