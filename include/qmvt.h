@@ -691,6 +691,9 @@ int qm_batch_types_timings(qm_batch* b, float* ms2);
  *   QM_HAP_MAX_GAP and when VCFs that share a truth set name different genomes; QM_E_RANGE for a batch of more than 65535 VCFs
  *   (one grid dimension holds them) and for more than (2^31 - 1) / 11 (VCF, open site) pairs (the lists are indexed in 32 bits); QM_E_STATE unless the latest qm_batch_run was
  *   finished, for a batch without QM_BATCH_ALLELES, and for a released truth set or genome.
+ *   A search behind the previous call (qm_batch_hapsubsets, maybe on another stream) is waited for on the HOST first, not on the
+ *   stream: this call regrows and refills from the host, with a blocking copy of the per-VCF descriptors, what that search still
+ *   reads.  A haplotype call behind a search in flight therefore holds the calling thread until the search is done.
  * qm_batch_get_haplotypes / qm_batch_get_haplotyped: wait for the pass, then copy (any pointer may be NULL).  QM_E_STATE if the
  *   batch ran since, for a VCF that named no genome, and without QM_HAP_COLUMNS in the latest call.
  * qm_batch_haplotype_timings (qm_batch_set_timing on): milliseconds between HIP events -- [0] the site tables, [1]
@@ -715,6 +718,47 @@ int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf, int gap, 
 int qm_batch_get_haplotypes(qm_batch* b, uint64_t* rec /*[n_vcf][QM_HAP_R_COLS] or NULL*/, uint64_t* tru /*[n_vcf][QM_HAP_T_COLS] or NULL*/);
 int qm_batch_get_haplotyped(qm_batch* b, int vcf, uint8_t* cls /*[n]*/, int32_t* site /*[n]*/, uint8_t* entry_cls /*[entries]*/);
 int qm_batch_haplotype_timings(qm_batch* b, float* ms5);
+
+/* ---- a subset search inside the mismatched sites of the haplotype pass (build-defined, opt-in) ----
+ * Behind a qm_batch_haplotypes, with its gap and genomes.  A site is SEARCHED for a VCF when the pass tried it and its outcome is
+ * MISMATCH or CONFLICT; every other site and class stays as it is.
+ * Forms: each side is reduced to its distinct trimmed forms (q, r, a) -- spellings that trim to one form collapse, a chosen form
+ *   rescues every line that spells it --, ordered by (q, |r|, |a|, a as a string over A<C<G<T); bit k of a side's mask is its
+ *   k-th form.  A subset is admissible when no two of its forms conflict: for a before b, q_b < q_a + |r_a|, or q_b = q_a and
+ *   |r_b| = 0.
+ * The optimum: over all pairs (S, T) of non-empty admissible subsets of the line forms and of the entry forms whose replays over
+ *   the site's window are equal (in length and in every symbol; a byte that is no base is a symbol of its own), the largest
+ *   |S| + |T|, then the larger |T|, then the smallest S mask, then the smallest T mask.  A searched site with an optimum is
+ *   PARTIAL, one without is NOSUBSET.  Hashes only order the work: every answer is verified symbol by symbol.
+ * In a PARTIAL site the open lines whose form is in S are rescued by subset, the open entries whose form is in T are found by
+ *   subset; the others are left.  hitS = hit by spelling, rescue by haplotype or rescue by subset; a TP_S line is kept and
+ *   satisfies (hitS and QM_F_IDDOT, or QM_F_TPLINE).
+ * sub[v][QM_HAPSUB_COLS]: SEARCHED, PARTIAL, NOSUBSET (sites), TP_S (TP_H plus the lines the subset rescue gains), RESCUED_S
+ *   (lines rescued by subset, whatever their ID), FOUND_S (FOUND_H plus the entries found by subset), LEFT_LINES, LEFT_ENTRIES
+ *   (over PARTIAL sites).
+ * With QM_HAPSUB_COLUMNS (needs QM_HAP_COLUMNS in the haplotype call) the search hands out second class bytes per record and per
+ *   truth entry: the pass's own but inside PARTIAL sites, where they are QM_HAP_C_SUBSET or QM_HAP_C_LEFT.  The arrays, rec and
+ *   tru of the pass itself are never touched.  QM_HAPSUB_NARROW_HASH is a self-check: hashes of 4 bits, so that nearly every
+ *   candidate collides and the answer rests on the verification alone; its results equal the normal mode's bit for bit.
+ * qm_batch_hapsubsets: asynchronous on `stream` (NULL = the context's own), ordered behind the haplotype call on whatever stream;
+ *   QM_E_INVAL for any other bit of `what`; QM_E_STATE without a qm_batch_haplotypes behind the latest run, if a truth set or a
+ *   genome of that call was released, and for QM_HAPSUB_COLUMNS without QM_HAP_COLUMNS.  A new qm_batch_haplotypes waits for a
+ *   search still in flight and forgets its results.
+ * qm_batch_get_hapsubsets / qm_batch_get_hapsubsetted: wait for the search, then copy (any pointer may be NULL).  The second one
+ *   returns the two class arrays (QM_E_STATE without QM_HAPSUB_COLUMNS) and, per PARTIAL site of the VCF, sites ascending, the
+ *   site index and the two masks; *n_out = their number, QM_E_RANGE if it is more than `capacity`.
+ * qm_batch_hapsubset_timings (qm_batch_set_timing on): milliseconds of the latest search between HIP events. */
+#define QM_HAPSUB_COLS 8
+#define QM_HAPSUB_COLUMNS 2u
+#define QM_HAPSUB_NARROW_HASH 4u
+enum { QM_HAPSUB_SEARCHED = 0, QM_HAPSUB_PARTIAL = 1, QM_HAPSUB_NOSUBSET = 2, QM_HAPSUB_TP_S = 3, QM_HAPSUB_RESCUED_S = 4,
+       QM_HAPSUB_FOUND_S = 5, QM_HAPSUB_LEFT_LINES = 6, QM_HAPSUB_LEFT_ENTRIES = 7 };
+enum { QM_HAP_C_SUBSET = 14, QM_HAP_C_LEFT = 15 };
+int qm_batch_hapsubsets(qm_batch* b, unsigned what /*0, QM_HAPSUB_COLUMNS, QM_HAPSUB_NARROW_HASH or both*/, void* stream);
+int qm_batch_get_hapsubsets(qm_batch* b, uint64_t* sub /*[n_vcf][QM_HAPSUB_COLS]*/);
+int qm_batch_get_hapsubsetted(qm_batch* b, int vcf, uint8_t* cls_s /*[n]*/, uint8_t* entry_cls_s /*[entries]*/, int32_t* site_s /*[capacity]*/,
+                              uint8_t* smask /*[capacity]*/, uint8_t* tmask /*[capacity]*/, int64_t capacity, int64_t* n_out);
+int qm_batch_hapsubset_timings(qm_batch* b, float* ms1);
 int qm_truth_sites(qm_ctx* ctx, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
                    int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
@@ -1163,6 +1207,29 @@ typedef struct qm_haplotypes_args {
 int qm_extract_files_haplotypes(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                 qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                                 void* global_dev, const qm_haplotypes_args* haplotypes);
+
+/* qm_extract_files_haplotypes plus the subset search behind the pass: the first fields are those of
+ * qm_haplotypes_args and give what that call gives -- rec, tru and the sites files, byte for byte --; sub[j][QM_HAPSUB_COLS] is
+ * the job's row of qm_batch_get_hapsubsets.  subsets_out (may be NULL, entries may be NULL): per job a file `#site WIN_LO WIN_HI
+ * RESCUED LEFT_LINES FOUND LEFT_ENTRIES REPLAY_LINES REPLAY_TRUTH`, one row per PARTIAL site in site order -- the lines rescued by
+ * subset and the lines left as `line:POS:REF:ALT` joined by `;`, the entries found by subset and the entries left as
+ * `POS:REF:ALT`, an empty list as `.`, and the replays of the two chosen subsets --, written atomically.  A job that names either
+ * file names its genome's bytes too. */
+typedef struct qm_hapsub_args {
+  const int32_t* genome_id;         /* [n_jobs], -1 = the job takes no part */
+  int32_t gap;                      /* 0 .. QM_HAP_MAX_GAP, one for the call */
+  int32_t reserved;
+  uint64_t* rec;                    /* [n_jobs][QM_HAP_R_COLS] */
+  uint64_t* tru;                    /* [n_jobs][QM_HAP_T_COLS] */
+  const char* const* sites_out;     /* [n_jobs] or NULL */
+  const uint8_t* const* genome_seq; /* [n_jobs] or NULL (then both lists of files are NULL too) */
+  const int64_t* genome_len;        /* [n_jobs] or NULL */
+  uint64_t* sub;                    /* [n_jobs][QM_HAPSUB_COLS] */
+  const char* const* subsets_out;   /* [n_jobs] or NULL */
+} qm_hapsub_args;
+int qm_extract_files_hapsubsets(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                                void* global_dev, const qm_hapsub_args* hapsubsets);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

@@ -70,6 +70,9 @@ QM_HAP_DEFAULT_GAP = 10
 QM_HAP_MAX_WINDOW = 256
 QM_HAP_MAX_ITEMS = 8
 QM_HAP_COLUMNS = 2
+QM_HAPSUB_COLS = 8
+QM_HAPSUB_COLUMNS = 2
+QM_HAPSUB_NARROW_HASH = 4
 
 # every symbol include/qmvt.h declares
 EXPORTS = (
@@ -99,6 +102,8 @@ EXPORTS = (
     "qm_batch_atomize", "qm_batch_get_atomize", "qm_batch_get_atomized", "qm_batch_atomize_timings", "qm_truth_atoms", "qm_extract_files_atomize",
     "qm_dict_shapes", "qm_batch_types", "qm_batch_get_types", "qm_batch_get_typed", "qm_batch_types_timings", "qm_extract_files_types",
     "qm_batch_haplotypes", "qm_batch_get_haplotypes", "qm_batch_get_haplotyped", "qm_batch_haplotype_timings", "qm_truth_sites", "qm_extract_files_haplotypes",
+    "qm_batch_hapsubsets", "qm_batch_get_hapsubsets", "qm_batch_get_hapsubsetted", "qm_batch_hapsubset_timings",
+    "qm_extract_files_hapsubsets",
 )
 
 
@@ -168,6 +173,13 @@ class NormalizeArgs(C.Structure):
 class AtomizeArgs(C.Structure):
     """include/qmvt.h qm_atomize_args"""
     _fields_ = [("want", C.c_void_p), ("rec", C.c_void_p), ("tru", C.c_void_p), ("atoms_out", C.POINTER(C.c_char_p))]
+
+
+class HapsubArgs(C.Structure):
+    """include/qmvt.h qm_hapsub_args"""
+    _fields_ = [("genome_id", C.c_void_p), ("gap", C.c_int32), ("reserved", C.c_int32), ("rec", C.c_void_p), ("tru", C.c_void_p),
+                ("sites_out", C.POINTER(C.c_char_p)), ("genome_seq", C.POINTER(C.c_char_p)), ("genome_len", C.c_void_p),
+                ("sub", C.c_void_p), ("subsets_out", C.POINTER(C.c_char_p))]
 
 
 class HaplotypesArgs(C.Structure):
@@ -442,9 +454,15 @@ def lib():
     L.qm_batch_get_haplotypes.argtypes = [vp, vp, vp]
     L.qm_batch_get_haplotyped.argtypes = [vp, i32, vp, vp, vp]
     L.qm_batch_haplotype_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_batch_hapsubsets.argtypes = [vp, C.c_uint, vp]
+    L.qm_batch_get_hapsubsets.argtypes = [vp, vp]
+    L.qm_batch_get_hapsubsetted.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.qm_batch_hapsubset_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_extract_files_haplotypes.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                               C.POINTER(HaplotypesArgs)]
     L.qm_truth_sites.argtypes = [vp, i32, i32, i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.qm_extract_files_hapsubsets.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                              C.POINTER(HapsubArgs)]
     L.qm_extract_files_types.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                          C.POINTER(TypesArgs)]
     _lib = L

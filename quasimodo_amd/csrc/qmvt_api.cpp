@@ -915,6 +915,19 @@ struct qm_batch {
   unsigned hp_made = 0;               // 1 | QM_HAP_COLUMNS: what the latest qm_batch_haplotypes made behind the latest run
   std::vector<uint8_t> hp_has;        // [n_vcf] the VCF named a genome
   std::vector<int64_t> hp_eoff;       // [n_vcf + 1] the VCF's entries in hp_ecls
+  std::vector<int32_t> hp_gids;       // [n_vcf] the genome ids of the latest qm_batch_haplotypes
+  int64_t hp_npairs = 0;              // the (VCF, open site) pairs it read back
+  // qm_batch_hapsubsets (lazy): [n_vcf][QM_HAPSUB_COLS] counts, a word per pair (searched or not, the two masks)
+  // and, on request, second class bytes per record and per (VCF, truth entry); ev_hapsub says when the search is done
+  DevBuf<uint64_t> hs_sub;
+  DevBuf<uint32_t> hs_res;
+  DevBuf<uint8_t> hs_cls, hs_ecls;
+  hipEvent_t ev_hapsub = nullptr;
+  hipEvent_t ev_hst[2] = {};          // qm_batch_set_timing: around the search
+  bool hs_timed = false;
+  unsigned hs_made = 0;               // 1 | what: what the latest qm_batch_hapsubsets made behind the latest qm_batch_haplotypes
+  bool hs_listed = false;             // hs_list holds the PARTIAL pairs of the latest search
+  std::vector<int32_t> hs_list;       // (VCF, site, S mask, T mask) per PARTIAL pair, VCF after VCF, sites ascending
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -955,6 +968,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_tyt) if (e) (void)hipEventDestroy(e);
   if (b->ev_haplo) (void)hipEventDestroy(b->ev_haplo);
   for (auto& e : b->ev_hpt) if (e) (void)hipEventDestroy(e);
+  if (b->ev_hapsub) (void)hipEventDestroy(b->ev_hapsub);
+  for (auto& e : b->ev_hst) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -971,7 +986,7 @@ static const PassEvent PASS_EVENTS[] = {
     {&qm_batch::ev_motif, false}, {&qm_batch::ev_afp, false},  {&qm_batch::ev_truth, false}, {&qm_batch::ev_strata, true},
     {&qm_batch::ev_boot, true},   {&qm_batch::ev_votes, true}, {&qm_batch::ev_nm, true},     {&qm_batch::ev_sf, false},
     {&qm_batch::ev_cx, true},     {&qm_batch::ev_norm, false}, {&qm_batch::ev_atom, false},
-    {&qm_batch::ev_types, false}, {&qm_batch::ev_haplo, false},
+    {&qm_batch::ev_types, false}, {&qm_batch::ev_haplo, false}, {&qm_batch::ev_hapsub, false},
 };
 // (ev_haplo: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
 // flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
@@ -1326,6 +1341,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->at_made = 0;
   b->ty_made = 0;
   b->hp_made = 0;
+  b->hs_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -3349,10 +3365,10 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   std::vector<int> pair_of(nv, -1);
   size_t pool_words = 0, bit_words = 0;
   int64_t max_entries = 0;
-  b->hp_eoff.assign(nv + 1, 0);
+  std::vector<int64_t> eoff(nv + 1, 0);   // (committed with hp_made: a call refused below leaves the previous call's offsets)
   for (size_t v = 0; v < nv; ++v) {
     const int gid = genome_id_per_vcf[v], tid = b->L.vcfs[v].truth;
-    b->hp_eoff[v + 1] = b->hp_eoff[v];
+    eoff[v + 1] = eoff[v];
     if (gid < 0) continue;
     const int64_t xn = c->truths[(size_t)tid].xn;
     size_t k = 0;
@@ -3367,12 +3383,16 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
     pair_of[v] = (int)k;
     bit_words += 3 * (size_t)(xn / 32 + 1);
     max_entries = std::max(max_entries, xn);
-    b->hp_eoff[v + 1] += xn;
+    eoff[v + 1] += xn;
   }
   hipStream_t st;
   rc = pass_stream(b, stream, &b->ev_haplo, &st);
   if (rc != QM_OK) return rc;
+  // A search behind the previous call (qm_batch_hapsubsets, maybe on another stream) reads what this call rewrites, regrows and
+  // copies over from the host: it is waited for here, not only on the stream.
+  if (b->ev_hapsub) HIPCHK(hipEventSynchronize(b->ev_hapsub));
   b->hp_made = 0;   // from here on the outputs are rewritten
+  b->hs_made = 0;   // ... and the search's results belong to the call before
   const size_t np = (size_t)b->L.n_pad;
   const bool cols = (what & QM_HAP_COLUMNS) != 0;
   rc = b->hp_pool.grow((int64_t)std::max<size_t>(pool_words, 1), &b->dev_bytes);
@@ -3383,7 +3403,7 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   if (rc == QM_OK) rc = b->hp_total.grow(1, &b->dev_bytes);
   if (rc == QM_OK) rc = b->hp_cls.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
   if (rc == QM_OK) rc = b->hp_site.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
-  if (rc == QM_OK && cols) rc = b->hp_ecls.grow(std::max<int64_t>(b->hp_eoff[nv], 1), &b->dev_bytes);
+  if (rc == QM_OK && cols) rc = b->hp_ecls.grow(std::max<int64_t>(eoff[nv], 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
   const bool T = b->timing;
   if (T) for (auto& e : b->ev_hpt) if (!e) HIPCHK(hipEventCreate(&e));
@@ -3407,7 +3427,7 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
     vcfs[v].ebits = b->hp_bits + bo;
     vcfs[v].sbits = b->hp_bits + bo + w;
     vcfs[v].srank = b->hp_bits + bo + 2 * w;
-    if (cols) vcfs[v].ecls = b->hp_ecls + b->hp_eoff[v];
+    if (cols) vcfs[v].ecls = b->hp_ecls + eoff[v];
     bo += 3 * w;
     b->hp_has[v] = 1;
   }
@@ -3455,6 +3475,9 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   if (T) { HIPCHK(hipEventRecord(b->ev_hpt[5], st)); b->hp_timed = true; }
   HIPCHK(hipEventRecord(b->ev_haplo, st));
   b->hp_made = 1u | what;
+  b->hp_eoff = eoff;
+  b->hp_gids.assign(genome_id_per_vcf, genome_id_per_vcf + nv);
+  b->hp_npairs = (int64_t)n_pairs;
   return QM_OK;
 }
 extern "C" int qm_batch_get_haplotypes(qm_batch* b, uint64_t* rec, uint64_t* tru) {
@@ -3490,6 +3513,128 @@ extern "C" int qm_batch_haplotype_timings(qm_batch* b, float* ms5) {
   HIPCHK(hipSetDevice(b->ctx->dev));
   HIPCHK(hipEventSynchronize(b->ev_hpt[5]));
   for (int i = 0; i < 5; ++i) HIPCHK(hipEventElapsedTime(ms5 + i, b->ev_hpt[i], b->ev_hpt[i + 1]));
+  return QM_OK;
+}
+// ---- a subset search inside the mismatched sites of the haplotype pass ----
+extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_hapsubsets");
+  if (what & ~(QM_HAPSUB_COLUMNS | QM_HAPSUB_NARROW_HASH)) return fail(QM_E_INVAL, "qm_batch_hapsubsets: what = %u", what);
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_hapsubsets: no qm_batch_haplotypes behind the latest run");
+  const bool cols = (what & QM_HAPSUB_COLUMNS) != 0;
+  if (cols && !(b->hp_made & QM_HAP_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_hapsubsets: QM_HAPSUB_COLUMNS needs the columns of the latest qm_batch_haplotypes (QM_HAP_COLUMNS)");
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  for (size_t v = 0; v < nv; ++v) {
+    const int gid = b->hp_gids[v];
+    if (gid >= 0 && (gid >= (int)c->genomes.size() || c->genomes[(size_t)gid].released))
+      return fail(QM_E_STATE, "qm_batch_hapsubsets: VCF %zu names released genome %d", v, gid);
+  }
+  int rc = truths_live(b, "qm_batch_hapsubsets");
+  if (rc != QM_OK) return rc;
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_hapsub, &st);
+  if (rc != QM_OK) return rc;
+  b->hs_made = 0;   // from here on the outputs are rewritten
+  b->hs_listed = false;
+  const size_t np = (size_t)b->L.n_pad, npairs = (size_t)b->hp_npairs, ne = (size_t)b->hp_eoff[nv];
+  rc = b->hs_sub.grow((int64_t)std::max<size_t>(nv * HAPSUB_COLS, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->hs_res.grow((int64_t)std::max<size_t>(npairs, 1), &b->dev_bytes);
+  if (rc == QM_OK && cols) rc = b->hs_cls.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
+  if (rc == QM_OK && cols) rc = b->hs_ecls.grow((int64_t)std::max<size_t>(ne, 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_hst) if (!e) HIPCHK(hipEventCreate(&e));
+  b->hs_timed = false;
+  HIPCHK(hipStreamWaitEvent(st, b->ev_haplo, 0));   // the pass may have run on another stream
+  if (T) HIPCHK(hipEventRecord(b->ev_hst[0], st));
+  HIPCHK(hipMemsetAsync(b->hs_res, 0, std::max<size_t>(npairs, 1) * 4, st));
+  if (cols) {
+    HIPCHK(hipMemcpyAsync(b->hs_cls, b->hp_cls, std::max<size_t>(np, 1), hipMemcpyDeviceToDevice, st));
+    if (ne) HIPCHK(hipMemcpyAsync(b->hs_ecls, b->hp_ecls, ne, hipMemcpyDeviceToDevice, st));
+  }
+  HapSubParams P;
+  memset(&P, 0, sizeof P);
+  P.vcfs = b->hp_vcfs;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.flags = b->flags; P.mask_tp = b->mask_tp;
+  P.cls = b->hp_cls; P.ecls = cols ? (const uint8_t*)b->hp_ecls : nullptr;
+  P.rec = b->hp_rec; P.tru = b->hp_tru;
+  P.pairs = b->hp_pairs; P.n_pairs = b->hp_npairs;
+  P.sub = b->hs_sub; P.res = b->hs_res;
+  P.cls_s = cols ? (uint8_t*)b->hs_cls : nullptr; P.ecls_s = cols ? (uint8_t*)b->hs_ecls : nullptr;
+  P.n_vcf = (int32_t)nv; P.narrow = (what & QM_HAPSUB_NARROW_HASH) ? 1 : 0;
+  launch_hap_subsets(P, st);
+  HIPCHK(hipGetLastError());
+  if (T) { HIPCHK(hipEventRecord(b->ev_hst[1], st)); b->hs_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_hapsub, st));
+  b->hs_made = 1u | what;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_hapsubsets(qm_batch* b, uint64_t* sub) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_hapsubsets: NULL batch");
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsets: no qm_batch_haplotypes behind the latest run");
+  if (!b->hs_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsets: no qm_batch_hapsubsets behind the latest qm_batch_haplotypes");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_hapsub));
+  const size_t nv = (size_t)b->n_vcf;
+  if (sub && nv) HIPCHK(hipMemcpy(sub, b->hs_sub, nv * HAPSUB_COLS * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_hapsubsetted(qm_batch* b, int v, uint8_t* cls_s, uint8_t* entry_cls_s, int32_t* site_s, uint8_t* smask, uint8_t* tmask,
+                                         int64_t capacity, int64_t* n_out) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: NULL batch");
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: no qm_batch_haplotypes behind the latest run");
+  if (!b->hs_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: no qm_batch_hapsubsets behind the latest qm_batch_haplotypes");
+  if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: VCF %d (the batch has %d)", v, b->n_vcf);
+  if (capacity < 0) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: capacity %lld", (long long)capacity);
+  if (!b->hp_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: VCF %d named no genome in the latest qm_batch_haplotypes", v);
+  if ((cls_s || entry_cls_s) && !(b->hs_made & QM_HAPSUB_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: the latest qm_batch_hapsubsets did not keep the columns (QM_HAPSUB_COLUMNS)");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_hapsub));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  const size_t n = (size_t)d.n, ne = (size_t)(b->hp_eoff[(size_t)v + 1] - b->hp_eoff[(size_t)v]);
+  if (cls_s && n) HIPCHK(hipMemcpy(cls_s, b->hs_cls + d.off, n, hipMemcpyDeviceToHost));
+  if (entry_cls_s && ne) HIPCHK(hipMemcpy(entry_cls_s, b->hs_ecls + b->hp_eoff[(size_t)v], ne, hipMemcpyDeviceToHost));
+  if (!b->hs_listed) {   // the PARTIAL pairs, once per search: the pairs are numbered VCF after VCF, sites ascending
+    const size_t npairs = (size_t)b->hp_npairs;
+    std::vector<uint32_t> res(npairs);
+    std::vector<int32_t> vs(2 * npairs);
+    if (npairs) {
+      HIPCHK(hipMemcpy(res.data(), b->hs_res, npairs * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy2D(vs.data(), 8, b->hp_pairs, (size_t)HAP_PAIR_WORDS * 4, 8, npairs, hipMemcpyDeviceToHost));
+    }
+    b->hs_list.clear();
+    for (size_t k = 0; k < npairs; ++k)
+      if (res[k] & HAPSUB_RES_PARTIAL) {
+        b->hs_list.push_back(vs[2 * k]); b->hs_list.push_back(vs[2 * k + 1]);
+        b->hs_list.push_back((int32_t)((res[k] >> 8) & 255u)); b->hs_list.push_back((int32_t)(res[k] & 255u));
+      }
+    b->hs_listed = true;
+  }
+  int64_t m = 0;
+  for (size_t k = 0; k + 3 < b->hs_list.size(); k += 4) {
+    if (b->hs_list[k] != v) continue;
+    if (m < capacity) {
+      if (site_s) site_s[m] = b->hs_list[k + 1];
+      if (smask) smask[m] = (uint8_t)b->hs_list[k + 2];
+      if (tmask) tmask[m] = (uint8_t)b->hs_list[k + 3];
+    }
+    ++m;
+  }
+  if (n_out) *n_out = m;
+  if (m > capacity && (site_s || smask || tmask))
+    return fail(QM_E_RANGE, "qm_batch_get_hapsubsetted: %lld PARTIAL sites, room for %lld", (long long)m, (long long)capacity);
+  return QM_OK;
+}
+extern "C" int qm_batch_hapsubset_timings(qm_batch* b, float* ms1) {
+  if (!b || !ms1) return fail(QM_E_INVAL, "qm_batch_hapsubset_timings: NULL");
+  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_hapsubset_timings: no qm_batch_haplotypes behind the latest run");
+  if (!b->hs_made) return fail(QM_E_STATE, "qm_batch_hapsubset_timings: no qm_batch_hapsubsets behind the latest qm_batch_haplotypes");
+  if (!b->hs_timed) return fail(QM_E_STATE, "qm_batch_hapsubset_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_hst[1]));
+  HIPCHK(hipEventElapsedTime(ms1, b->ev_hst[0], b->ev_hst[1]));
   return QM_OK;
 }
 extern "C" int qm_truth_sites(qm_ctx* c, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,

@@ -84,6 +84,39 @@ struct HapReplayParams {
   int64_t n_pairs;
 };
 
+// ---- the subset search behind the pass (k_hap_subsets) ----
+constexpr int HAPSUB_COLS = 8;               // include/qmvt.h QM_HAPSUB_COLS
+constexpr uint32_t HAP_SUBSET = 14u, HAP_LEFT = 15u;   // QM_HAP_C_SUBSET / _LEFT: in the search's own class arrays only (14 is HAP_PENDING inside the pass)
+constexpr int HAPSUB_SEARCHED = 0, HAPSUB_PARTIAL = 1, HAPSUB_NOSUBSET = 2, HAPSUB_TP_S = 3, HAPSUB_RESCUED_S = 4, HAPSUB_FOUND_S = 5,
+              HAPSUB_LEFT_LINES = 6, HAPSUB_LEFT_ENTRIES = 7;
+// the word of a pair in HapSubParams::res: 0 not searched, HAPSUB_RES_NOSUBSET, or HAPSUB_RES_PARTIAL | S mask << 8 | T mask
+constexpr uint32_t HAPSUB_RES_PARTIAL = 1u << 16, HAPSUB_RES_NOSUBSET = 1u << 17;
+
+// What qm_batch_haplotypes left in the batch, read only, and the search's own outputs.
+struct HapSubParams {
+  const HapVcf* vcfs;
+  const int32_t* pos;
+  const int32_t* ref;
+  const int32_t* alt;
+  const uint8_t* flags;
+  const uint64_t* mask_tp;
+  const uint8_t* cls;        // the pass's class bytes
+  const uint8_t* ecls;       // the pass's entry classes (the base every HapVcf::ecls points into), or null
+  const uint64_t* rec;       // [n_vcf][HAP_R_COLS]
+  const uint64_t* tru;       // [n_vcf][HAP_T_COLS]
+  const int32_t* pairs;
+  int64_t n_pairs;
+  uint64_t* sub;             // [n_vcf][HAPSUB_COLS]
+  uint32_t* res;             // [n_pairs], cleared on the same stream before the launch
+  uint8_t* cls_s;            // [n_pad] a copy of cls made on the same stream before the launch, or null
+  uint8_t* ecls_s;           // as ecls, or null
+  int32_t n_vcf;
+  int32_t narrow;            // QM_HAPSUB_NARROW_HASH: hashes of 4 bits, the answer rests on the verification alone
+};
+
+// k_hap_subsets_init + k_hap_subsets: sub starts from TP_H and FOUND_H, then one wave per pair
+void launch_hap_subsets(const HapSubParams& P, hipStream_t st);
+
 // builds S on `st`: per-entry arrays, site indices, windows
 void launch_hap_sites(const HapSites& S, hipStream_t st);
 // k_hap_records: classes, sites, the counts that need no replay, the found bitmaps

@@ -522,7 +522,302 @@ __global__ __launch_bounds__(64) void k_hap_replay(HapReplayParams P) {
   }
 }
 
+// ---- the subset search ----
+// a < b in the total order of distinct trimmed forms: (q, |r|, |a|, a as a string over A<C<G<T -- base k of an allele sits in bits
+// 2 k, so the lowest field that differs decides)
+__device__ inline bool hs_less(int32_t q1, uint32_t r1, uint32_t a1, uint32_t b1, int32_t q2, uint32_t r2, uint32_t a2, uint32_t b2) {
+  if (q1 != q2) return q1 < q2;
+  if (r1 != r2) return r1 < r2;
+  if (a1 != a2) return a1 < a2;
+  const uint32_t d = b1 ^ b2;
+  if (!d) return false;
+  const uint32_t sh = (uint32_t)__builtin_ctz(d) & ~1u;
+  return ((b1 >> sh) & 3u) < ((b2 >> sh) & 3u);
+}
+
+constexpr uint32_t HS_B1 = 0x9E3779B1u, HS_B2 = 0x85EBCA77u;   // the bases of the two polynomial hashes mod 2^32 (odd)
+constexpr int32_t HS_NONE = (int32_t)0x80000000;               // the length delta of a subset that is not admissible
+constexpr int HS_TAB = HAP_MAX_WINDOW + 4;                      // prefix tables: offsets 0 .. HAP_MAX_WINDOW
+
+// a lane per VCF: TP_S and FOUND_S start from the pass's TP_H and FOUND_H
+__global__ __launch_bounds__(256) void k_hap_subsets_init(HapSubParams P) {
+  const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (v >= P.n_vcf) return;
+  uint64_t* o = P.sub + (int64_t)v * HAPSUB_COLS;
+  for (int k = 0; k < HAPSUB_COLS; ++k) o[k] = 0ull;
+  o[HAPSUB_TP_S] = P.rec[(int64_t)v * HAP_R_COLS + HAP_R_TP_H];
+  o[HAPSUB_FOUND_S] = P.tru[(int64_t)v * HAP_T_COLS + HAP_T_FOUND_H];
+}
+
+// One wave (a workgroup of its own) per pair; a pair that was not tried, or whose site is neither MISMATCH nor CONFLICT, returns
+// at once.  Lanes 0 .. 7 hold the open lines, lanes 8 .. 15 the open entries, gathered as k_hap_replay gathers them.  Spellings
+// that trim to one form collapse; the forms of a side take their rank in the total order (no lane, no slot of the pair list takes
+// part: the lists fill in the order the claims arrive).  Every non-empty subset of a side gets its admissibility (8 x 8 conflict
+// bits), its length delta and two 32-bit polynomial hashes of its replay, composed in O(its forms) from prefix hashes of the
+// window's genome symbols and the hashes of the ALT pieces.  The candidates -- pairs of subsets whose deltas and hashes agree -- are
+// taken in the optimum's order (each lane keeps the least order key of its S masks over all T masks, a wave minimum picks one) and
+// VERIFIED symbol by symbol as k_hap_replay compares, nothing stored; a candidate that fails is the floor of the next round.  The
+// answer never rests on a hash: narrow hashes (4 bits) give the same result through more rounds.
+__global__ __launch_bounds__(64) void k_hap_subsets(HapSubParams P) {
+  __shared__ int32_t ent[HAP_MAX_ITEMS];
+  __shared__ int32_t it_q[16];
+  __shared__ uint32_t it_lr[16], it_la[16], it_ab[16], it_dup[16];
+  __shared__ int32_t fq[2][HAP_MAX_ITEMS];
+  __shared__ uint32_t flr[2][HAP_MAX_ITEMS], fla[2][HAP_MAX_ITEMS], fab[2][HAP_MAX_ITEMS], fcf[2][HAP_MAX_ITEMS];
+  __shared__ uint32_t fh1[2][HAP_MAX_ITEMS], fh2[2][HAP_MAX_ITEMS];
+  __shared__ uint32_t pw1[HS_TAB], pw2[HS_TAB], gh1[HS_TAB], gh2[HS_TAB];
+  __shared__ uint32_t sc1[64], sc2[64];
+  __shared__ uint32_t sh1[2][256], sh2[2][256];
+  __shared__ int32_t sdl[2][256];
+  __shared__ int32_t vq[2][HAP_MAX_ITEMS], vst[2][HAP_MAX_ITEMS];
+  __shared__ uint32_t vla[2][HAP_MAX_ITEMS], vab[2][HAP_MAX_ITEMS];
+  __shared__ int32_t vn[2], dlt[2], tot[2];
+  const int t = (int)threadIdx.x;
+  const int32_t* pr = P.pairs + (int64_t)blockIdx.x * HAP_PAIR_WORDS;
+  const int32_t v = pr[0], s = pr[1], cnt = pr[2];
+  if (cnt <= 0 || cnt > HAP_MAX_ITEMS) return;   // (uniform: not tried, or TOOMANY)
+  const HapVcf& V = P.vcfs[v];
+  const HapSites& S = V.s;
+  const uint32_t c0 = P.cls[V.off + pr[3]];
+  if (c0 != HAP_MISMATCH && c0 != HAP_CONFLICT) return;   // (uniform: every open line of a site carries the site's outcome)
+  const int nrec = cnt;
+  const int32_t e0 = S.sfirst[s], e1 = S.sfirst[s + 1];
+  int nent = 0;
+  for (int32_t b = e0; b < e1; b += 64) {
+    const int32_t j = b + t;
+    const bool open = j < e1 && S.ewhy[j] == 0 && !((V.ebits[j >> 5] >> ((uint32_t)j & 31u)) & 1u);
+    const uint64_t m = __ballot(open);
+    if (open) {
+      const int r = nent + __popcll(m & ((1ull << t) - 1ull));
+      if (r < HAP_MAX_ITEMS) ent[r] = j;
+    }
+    nent += __popcll(m);
+  }
+  if (nent <= 0 || nent > HAP_MAX_ITEMS) return;   // (uniform; a MISMATCH or CONFLICT site holds 1 .. 8 open entries)
+  __syncthreads();
+  // the items and their forms
+  const int side = (t >> 3) & 1, k = t & 7;
+  const bool have = t < 16 && k < (side ? nent : nrec);
+  int32_t q = 0;
+  uint32_t tr = 0u, ta = 0u, ab = 0u;
+  if (have) {
+    int32_t p, r, a;
+    if (side) {
+      const int32_t j = ent[k];
+      p = (int32_t)(S.xkeys[j] >> 4); r = S.xref[j]; a = S.xalt[j];
+    } else {
+      const int64_t gi = V.off + pr[3 + k];
+      p = P.pos[gi]; r = P.ref[gi]; a = P.alt[gi];
+    }
+    hp_trim(p, r, a, q, tr, ta, ab);
+  }
+  if (t < 16) { it_q[t] = q; it_lr[t] = tr; it_la[t] = ta; it_ab[t] = ab; }
+  __syncthreads();
+  bool dup = false;
+  if (have)
+    for (int i = side * 8; i < t; ++i) dup = dup || (it_q[i] == q && it_lr[i] == tr && it_la[i] == ta && it_ab[i] == ab);
+  if (t < 16) it_dup[t] = (!have || dup) ? 1u : 0u;
+  __syncthreads();
+  int frank = 0;   // the bit of this item's form in its side's masks
+  if (have) {
+    for (int i = side * 8; i < side * 8 + 8; ++i)
+      if (!it_dup[i] && hs_less(it_q[i], it_lr[i], it_la[i], it_ab[i], q, tr, ta, ab)) ++frank;
+    if (!dup) {
+      uint32_t h1 = 0u, h2 = 0u;
+      for (uint32_t i = 0; i < ta; ++i) {
+        const uint32_t c = ((ab >> (2u * i)) & 3u) + 1u;
+        h1 = h1 * HS_B1 + c;
+        h2 = h2 * HS_B2 + c;
+      }
+      fq[side][frank] = q; flr[side][frank] = tr; fla[side][frank] = ta; fab[side][frank] = ab;
+      fh1[side][frank] = h1; fh2[side][frank] = h2;
+    }
+  }
+  const uint64_t mk = __ballot(have && !dup);
+  const int nf0 = __popcll(mk & 0xffull), nf1 = __popcll(mk & 0xff00ull);
+  __syncthreads();
+  // the conflict bits of every form against the others of its side, all pairs
+  if (t < 16 && k < (side ? nf1 : nf0)) {
+    const int n = side ? nf1 : nf0;
+    uint32_t cf = 0u;
+    for (int j = 0; j < n; ++j) {
+      if (j == k) continue;
+      const int x = min(j, k), y = max(j, k);
+      const bool bad = fq[side][y] < fq[side][x] + (int32_t)flr[side][x] || (fq[side][y] == fq[side][x] && flr[side][y] == 0u);
+      cf |= bad ? 1u << j : 0u;
+    }
+    fcf[side][k] = cf;
+  }
+  // powers of the bases and prefix hashes of the window's symbols: lane t owns offsets 4 t .. 4 t + 3 (symbols past the window
+  // count as 0; no prefix that is used holds one)
+  const int32_t ws = S.slo[s], wend = (int32_t)min((int64_t)S.shi[s], S.len);
+  const int32_t W = min(max(wend - ws + 1, 0), HAP_MAX_WINDOW);
+  {
+    uint32_t p1 = 1u, p2 = 1u, x1 = HS_B1, x2 = HS_B2;
+    for (uint32_t e = 4u * (uint32_t)t; e; e >>= 1) {
+      if (e & 1u) { p1 *= x1; p2 *= x2; }
+      x1 *= x1; x2 *= x2;
+    }
+    for (int i = 0; i < 4; ++i) {
+      pw1[4 * t + i] = p1; pw2[4 * t + i] = p2;
+      p1 *= HS_B1; p2 *= HS_B2;
+    }
+    if (t == 63) { pw1[256] = p1; pw2[256] = p2; }
+  }
+  uint32_t sy[4];
+  uint32_t c1 = 0u, c2 = 0u;
+  for (int i = 0; i < 4; ++i) {
+    const int32_t o = 4 * t + i;
+    sy[i] = o < W ? hp_base(S.words, ws + o) + 1u : 0u;
+    c1 = c1 * HS_B1 + sy[i];
+    c2 = c2 * HS_B2 + sy[i];
+  }
+  sc1[t] = c1; sc2[t] = c2;
+  __syncthreads();
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y1 = t >= d ? sc1[t - d] * pw1[4 * d] + sc1[t] : sc1[t];
+    const uint32_t y2 = t >= d ? sc2[t - d] * pw2[4 * d] + sc2[t] : sc2[t];
+    __syncthreads();
+    sc1[t] = y1; sc2[t] = y2;
+    __syncthreads();
+  }
+  {
+    uint32_t g1 = t ? sc1[t - 1] : 0u, g2 = t ? sc2[t - 1] : 0u;
+    for (int i = 0; i < 4; ++i) {
+      gh1[4 * t + i] = g1; gh2[4 * t + i] = g2;
+      g1 = g1 * HS_B1 + sy[i];
+      g2 = g2 * HS_B2 + sy[i];
+    }
+    if (t == 63) { gh1[256] = g1; gh2[256] = g2; }
+  }
+  __syncthreads();
+  // every subset of a side: admissible or not, its length delta, the hashes of its replay
+  for (int sd = 0; sd < 2; ++sd) {
+    const int n = sd ? nf1 : nf0;
+    for (uint32_t m = (uint32_t)t; m < (1u << n); m += 64u) {
+      if (!m) continue;
+      bool adm = true;
+      int32_t cur = 0, d = 0;
+      uint32_t h1 = 0u, h2 = 0u;
+      for (int i = 0; i < n; ++i) {
+        if (!((m >> i) & 1u)) continue;
+        adm = adm && !(fcf[sd][i] & m);
+        if (!adm) break;
+        const int32_t qo = fq[sd][i] - ws, len = qo - cur;   // (admissible so far: 0 <= cur <= qo <= W)
+        h1 = (h1 * pw1[len] + gh1[qo] - gh1[cur] * pw1[len]) * pw1[fla[sd][i]] + fh1[sd][i];
+        h2 = (h2 * pw2[len] + gh2[qo] - gh2[cur] * pw2[len]) * pw2[fla[sd][i]] + fh2[sd][i];
+        cur = qo + (int32_t)flr[sd][i];
+        d += (int32_t)fla[sd][i] - (int32_t)flr[sd][i];
+      }
+      if (adm) {
+        const int32_t len = W - cur;
+        h1 = h1 * pw1[len] + gh1[W] - gh1[cur] * pw1[len];
+        h2 = h2 * pw2[len] + gh2[W] - gh2[cur] * pw2[len];
+      }
+      sh1[sd][m] = P.narrow ? h1 >> 28 : h1;   // (the top bits: the low ones of a polynomial mod 2^32 mix nothing)
+      sh2[sd][m] = P.narrow ? 0u : h2;
+      sdl[sd][m] = adm ? d : HS_NONE;
+    }
+  }
+  __syncthreads();
+  // the candidates in the optimum's order: the largest |S| + |T|, then the larger |T|, then the smallest S mask, then the smallest
+  // T mask -- one order key, smaller is better
+  uint32_t floor = 0u, found = 0u;
+  for (;;) {
+    uint32_t best = 0xffffffffu;
+    for (uint32_t ms = (uint32_t)t; ms < (1u << nf0); ms += 64u) {
+      if (!ms) continue;
+      const int32_t ds = sdl[0][ms];
+      if (ds == HS_NONE) continue;
+      const uint32_t a1 = sh1[0][ms], a2 = sh2[0][ms];
+      const uint32_t ps = (uint32_t)__popc(ms);
+      for (uint32_t mt = 1u; mt < (1u << nf1); ++mt) {
+        if (sdl[1][mt] != ds || sh1[1][mt] != a1 || sh2[1][mt] != a2) continue;
+        const uint32_t pt = (uint32_t)__popc(mt);
+        const uint32_t key = ((16u - ps - pt) << 20) | ((8u - pt) << 16) | (ms << 8) | mt;
+        if (key > floor && key < best) best = key;
+      }
+    }
+    for (int off = 32; off; off >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, off));
+    if (best == 0xffffffffu) break;   // (uniform) no candidate is left: NOSUBSET
+    const uint32_t ms = (best >> 8) & 255u, mt = best & 255u;
+    if (t < 2) {   // (side t: the pieces of its subset)
+      const uint32_t m = t ? mt : ms;
+      const int n = t ? nf1 : nf0;
+      int32_t d = 0;
+      int c = 0;
+      for (int i = 0; i < n; ++i) {
+        if (!((m >> i) & 1u)) continue;
+        vq[t][c] = fq[t][i]; vla[t][c] = fla[t][i]; vab[t][c] = fab[t][i];
+        vst[t][c] = fq[t][i] - ws + d;
+        d += (int32_t)fla[t][i] - (int32_t)flr[t][i];
+        ++c;
+      }
+      vn[t] = c;
+      dlt[t] = d;
+      tot[t] = W + d;
+    }
+    __syncthreads();
+    bool differ = tot[0] != tot[1];
+    if (!differ) {
+      for (int32_t o = t; o < tot[0]; o += 64) {
+        uint32_t sym[2];
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) {
+          const int n = vn[sd];
+          int32_t gq = ws + o - dlt[sd];   // behind the last piece
+          uint32_t c = 16u;
+          for (int i = 0; i < n; ++i) {
+            const int32_t b0 = vst[sd][i];
+            if (o < b0) { gq = o - b0 + vq[sd][i]; break; }
+            if (o < b0 + (int32_t)vla[sd][i]) { c = (vab[sd][i] >> (2 * (o - b0))) & 3u; break; }
+          }
+          sym[sd] = c < 16u ? c : hp_base(S.words, max(min(max(gq, ws), wend), 1));   // (ws <= gq <= wend as it is: the load stays inside the genome whatever the tables hold)
+        }
+        differ = differ || sym[0] != sym[1];
+      }
+    }
+    const bool same = !__ballot(differ);
+    __syncthreads();   // (the piece tables are rebuilt in the next round)
+    if (same) { found = best; break; }
+    floor = best;
+  }
+  // what became of the site
+  const uint32_t ms = (found >> 8) & 255u, mt = found & 255u;
+  const bool in = have && found && (((side ? mt : ms) >> frank) & 1u);
+  bool gained = false;
+  if (found && have) {
+    if (!side) {
+      const int64_t gi = V.off + pr[3 + k];
+      gained = in && (P.flags[gi] & QMF_IDDOT) && !((P.mask_tp[gi >> 6] >> (int)(gi & 63)) & 1ull);
+      if (P.cls_s) P.cls_s[gi] = (uint8_t)(in ? HAP_SUBSET : HAP_LEFT);
+    } else if (P.ecls_s && V.ecls) {
+      P.ecls_s[(V.ecls - P.ecls) + ent[k]] = (uint8_t)(in ? HAP_SUBSET : HAP_LEFT);
+    }
+  }
+  const uint64_t mi = __ballot(in), mg = __ballot(gained);
+  if (t == 0) {
+    unsigned long long* o = reinterpret_cast<unsigned long long*>(P.sub) + (int64_t)v * HAPSUB_COLS;
+    atomicAdd(o + HAPSUB_SEARCHED, 1ull);
+    atomicAdd(o + (found ? HAPSUB_PARTIAL : HAPSUB_NOSUBSET), 1ull);
+    if (found) {
+      const int rl = __popcll(mi & 0xffull), fe = __popcll(mi & 0xff00ull);
+      atomicAdd(o + HAPSUB_RESCUED_S, (unsigned long long)rl);
+      atomicAdd(o + HAPSUB_FOUND_S, (unsigned long long)fe);
+      if (mg) atomicAdd(o + HAPSUB_TP_S, (unsigned long long)__popcll(mg));
+      if (nrec - rl) atomicAdd(o + HAPSUB_LEFT_LINES, (unsigned long long)(nrec - rl));
+      if (nent - fe) atomicAdd(o + HAPSUB_LEFT_ENTRIES, (unsigned long long)(nent - fe));
+    }
+    P.res[blockIdx.x] = found ? (HAPSUB_RES_PARTIAL | (found & 0xffffu)) : HAPSUB_RES_NOSUBSET;
+  }
+}
+
 // ---- launchers ----
+void launch_hap_subsets(const HapSubParams& P, hipStream_t st) {
+  if (P.n_vcf > 0) hipLaunchKernelGGL(k_hap_subsets_init, dim3((unsigned)((P.n_vcf + 255) / 256)), dim3(256), 0, st, P);
+  if (P.n_pairs > 0) hipLaunchKernelGGL(k_hap_subsets, dim3((unsigned)P.n_pairs), dim3(64), 0, st, P);
+}
+
 void launch_hap_sites(const HapSites& S, hipStream_t st) {
   if (S.xn > 0) hipLaunchKernelGGL(k_hap_entries, dim3((unsigned)((S.xn + 255) / 256)), dim3(256), 0, st, S);
   hipLaunchKernelGGL(k_hap_sites, dim3(1), dim3(256), 0, st, S);

@@ -300,6 +300,7 @@ struct Passes {
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
   const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr; const qm_haplotypes_args* hp = nullptr;
+  const qm_hapsub_args* hs = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -914,13 +915,13 @@ int write_sites_file(const char* path, const JobState& s, const HpColumns& c, co
 }
 
 // the counts of every wanted job, and the sites files of the jobs that name one
-int haplo_pass(const PassCtx& c, const qm_haplotypes_args* ha, std::string& err) {
+int haplo_pass(const PassCtx& c, const qm_haplotypes_args* ha, std::string& err, bool columns = false) {
   if (!ha) return QM_OK;
   auto want = [&](int j) { return !c.jobs[j].pure && ha->genome_id[j] >= 0; };
   if (!c.any(want)) return QM_OK;
   auto path = [&](int j) { return want(j) && ha->sites_out ? ha->sites_out[j] : nullptr; };
   std::vector<int32_t> gid(c.nv, -1);
-  bool files = false;
+  bool files = columns;   // (the subset search behind this pass asks for the columns too)
   for (int j = 0; j < c.n_jobs; ++j) if (want(j)) { gid[(size_t)c.J[(size_t)j].batch_v] = ha->genome_id[j]; files = files || path(j); }
   std::vector<uint64_t> rec(c.nv * QM_HAP_R_COLS), tru(c.nv * QM_HAP_T_COLS);
   int rc = qm_batch_haplotypes(c.batch, gid.data(), ha->gap, files ? QM_HAP_COLUMNS : 0u, nullptr);
@@ -962,6 +963,127 @@ int haplo_pass(const PassCtx& c, const qm_haplotypes_args* ha, std::string& err)
   });
   for (size_t k = 0; k < W.size(); ++k)
     if (wrc[k] != QM_OK) { err = std::string("cannot write ") + ha->sites_out[W[k].j]; return wrc[k]; }
+  return QM_OK;
+}
+
+// ---- a subset search inside the mismatched sites of the haplotype pass ----
+// `line:POS:REF:ALT` of data line i (1-based line number, the line's own text of the three columns) appended to L; false: no such columns
+bool hs_line_text(const JobState& s, int64_t i, std::string& L) {
+  const uint8_t* text = s.vcf.p;
+  const size_t tlen = s.vcf.n;
+  size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], tlen);
+  if (e > b && text[e - 1] == '\n') --e;
+  const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+  const uint8_t* q = text + b;
+  while (nf < 6) {
+    const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(text + e - q));
+    f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(text + e - q); ++nf;
+    if (!tb) break;
+    q = tb + 1;
+  }
+  if (nf < 5) return false;
+  if (!L.empty()) L.push_back(';');
+  L += std::to_string(i + 1);
+  for (int x : {1, 3, 4}) { L.push_back(':'); L.append((const char*)f[x], fl[x]); }
+  return true;
+}
+// `#site WIN_LO WIN_HI RESCUED LEFT_LINES FOUND LEFT_ENTRIES REPLAY_LINES REPLAY_TRUTH`, one row per PARTIAL site of the job in
+// site order; an empty list prints as `.`; the two strings replay the CHOSEN forms on the host, as for sites.tsv
+int write_subsets_file(const char* path, const JobState& s, const std::vector<uint8_t>& cls_s, const std::vector<int32_t>& site,
+                       const std::vector<uint8_t>& ecls_s, const NzEntries& t, const HpSites& st, const uint8_t* seq, int64_t len) {
+  std::string out = "#site\tWIN_LO\tWIN_HI\tRESCUED\tLEFT_LINES\tFOUND\tLEFT_ENTRIES\tREPLAY_LINES\tREPLAY_TRUTH\n";
+  const size_t ns = st.first.size();
+  std::vector<std::string> got(ns), left(ns);
+  std::vector<std::vector<HpForm>> side(ns);
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    const int64_t r = rec++;
+    const uint8_t c = cls_s[(size_t)r];
+    if (c != QM_HAP_C_SUBSET && c != QM_HAP_C_LEFT) continue;
+    const int32_t k = site[(size_t)r];
+    if (k < 0 || (size_t)k >= ns) continue;
+    if (!hs_line_text(s, i, c == QM_HAP_C_SUBSET ? got[(size_t)k] : left[(size_t)k])) continue;
+    if (c == QM_HAP_C_SUBSET) side[(size_t)k].push_back(hp_trim(s.pos[r], nz_spell(s.ref[r]), nz_spell(s.alt[r])));
+  }
+  auto dot = [](const std::string& x) { return x.empty() ? std::string(".") : x; };
+  for (size_t k = 0; k < ns; ++k) {
+    if (got[k].empty()) continue;
+    const size_t e0 = (size_t)st.first[k], e1 = k + 1 < ns ? (size_t)st.first[k + 1] : t.pos.size();
+    std::string found, eleft;
+    std::vector<HpForm> tside;
+    for (size_t j = e0; j < e1; ++j) {
+      if (ecls_s[j] != QM_HAP_C_SUBSET && ecls_s[j] != QM_HAP_C_LEFT) continue;
+      std::string& E = ecls_s[j] == QM_HAP_C_SUBSET ? found : eleft;
+      if (!E.empty()) E.push_back(';');
+      E += std::to_string(t.pos[j]) + ":" + nz_spell(t.ref[j]) + ":" + nz_spell(t.alt[j]);
+      if (ecls_s[j] == QM_HAP_C_SUBSET) tside.push_back(hp_trim(t.pos[j], nz_spell(t.ref[j]), nz_spell(t.alt[j])));
+    }
+    out += std::to_string(k) + "\t" + std::to_string(st.lo[k]) + "\t" + std::to_string(st.hi[k]) + "\t" + got[k] + "\t" + dot(left[k]) + "\t" +
+           dot(found) + "\t" + dot(eleft) + "\t" + hp_replay(seq, len, st.lo[k], st.hi[k], side[k]) + "\t" +
+           hp_replay(seq, len, st.lo[k], st.hi[k], tside) + "\n";
+  }
+  return write_all_atomic(path, out);
+}
+
+// the haplotype pass (its rows and its sites files, as haplo_pass alone leaves them), then the search: its rows, and the subsets
+// files of the jobs that name one
+int hapsub_pass(const PassCtx& c, const qm_hapsub_args* hs, std::string& err) {
+  if (!hs) return QM_OK;
+  auto want = [&](int j) { return !c.jobs[j].pure && hs->genome_id[j] >= 0; };
+  if (!c.any(want)) return QM_OK;
+  auto path = [&](int j) { return want(j) && hs->subsets_out ? hs->subsets_out[j] : nullptr; };
+  bool files = false;
+  for (int j = 0; j < c.n_jobs; ++j) files = files || path(j);
+  qm_haplotypes_args ha;
+  memset(&ha, 0, sizeof ha);
+  ha.genome_id = hs->genome_id; ha.gap = hs->gap; ha.rec = hs->rec; ha.tru = hs->tru;
+  ha.sites_out = hs->sites_out; ha.genome_seq = hs->genome_seq; ha.genome_len = hs->genome_len;
+  int rc = haplo_pass(c, &ha, err, files);
+  if (rc != QM_OK) return rc;
+  std::vector<uint64_t> sub(c.nv * QM_HAPSUB_COLS);
+  rc = qm_batch_hapsubsets(c.batch, files ? QM_HAPSUB_COLUMNS : 0u, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_hapsubsets(c.batch, sub.data());
+  if (rc == QM_OK) c.scatter_rows(hs->sub, sub, QM_HAPSUB_COLS, want);
+  struct Task { int j; std::vector<uint8_t> cls_s, ecls_s, cls, ecls; std::vector<int32_t> site; };
+  std::vector<Task> W;
+  std::vector<NzEntries> ent(c.T.size());
+  std::vector<HpSites> sites(c.T.size());
+  std::vector<uint8_t> have(c.T.size(), 0);
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    if (!path(j)) continue;
+    const JobState& s = c.J[(size_t)j];
+    const size_t n = (size_t)s.n_data + 1;
+    if (!have[(size_t)s.truth]) {
+      NzEntries& e = ent[(size_t)s.truth];
+      HpSites& st = sites[(size_t)s.truth];
+      int64_t tn = 0, sn = 0;
+      (void)qm_truth_entries(c.ctx, c.truth_of(j).tid, nullptr, nullptr, nullptr, 0, &tn);   // (how many)
+      e.pos.resize((size_t)tn + 1); e.ref.resize((size_t)tn + 1); e.alt.resize((size_t)tn + 1);
+      rc = qm_truth_entries(c.ctx, c.truth_of(j).tid, e.pos.data(), e.ref.data(), e.alt.data(), tn, &tn);
+      e.pos.resize((size_t)tn); e.ref.resize((size_t)tn); e.alt.resize((size_t)tn);
+      st.first.resize((size_t)tn + 1); st.lo.resize((size_t)tn + 1); st.hi.resize((size_t)tn + 1);
+      if (rc == QM_OK) rc = qm_truth_sites(c.ctx, c.truth_of(j).tid, hs->genome_id[j], hs->gap, st.first.data(), st.lo.data(), st.hi.data(), tn + 1, &sn);
+      st.first.resize((size_t)sn); st.lo.resize((size_t)sn); st.hi.resize((size_t)sn);
+      have[(size_t)s.truth] = 1;
+    }
+    if (rc != QM_OK) break;
+    const size_t ne = ent[(size_t)s.truth].pos.size() + 1;
+    W.push_back({j, std::vector<uint8_t>(n, 0), std::vector<uint8_t>(ne, 0), std::vector<uint8_t>(n, 0), std::vector<uint8_t>(ne, 0), std::vector<int32_t>(n, -1)});
+    Task& k = W.back();
+    rc = qm_batch_get_haplotyped(c.batch, s.batch_v, k.cls.data(), k.site.data(), k.ecls.data());
+    int64_t m = 0;
+    if (rc == QM_OK) rc = qm_batch_get_hapsubsetted(c.batch, s.batch_v, k.cls_s.data(), k.ecls_s.data(), nullptr, nullptr, nullptr, 0, &m);
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  std::vector<int> wrc(W.size(), QM_OK);
+  parallel_for((int)W.size(), c.nthr, [&](int k) {
+    const Task& w = W[(size_t)k];
+    const size_t t = (size_t)c.J[(size_t)w.j].truth;
+    wrc[(size_t)k] = write_subsets_file(hs->subsets_out[w.j], c.J[(size_t)w.j], w.cls_s, w.site, w.ecls_s, ent[t], sites[t], hs->genome_seq[w.j], hs->genome_len[w.j]);
+  });
+  for (size_t k = 0; k < W.size(); ++k)
+    if (wrc[k] != QM_OK) { err = std::string("cannot write ") + hs->subsets_out[W[k].j]; return wrc[k]; }
   return QM_OK;
 }
 
@@ -1162,6 +1284,30 @@ extern "C" int qm_extract_files_haplotypes(qm_ctx* ctx, int n_jobs, const qm_fil
     memset(ha->tru, 0, sizeof(uint64_t) * QM_HAP_T_COLS * (size_t)n_jobs);
   }
   Passes P; P.hp = ha;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
+// the subset search behind the haplotype pass behind the worker
+extern "C" int qm_extract_files_hapsubsets(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                           qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                           int n_slots, void* global_dev, const qm_hapsub_args* hapsubsets) {
+  const qm_hapsub_args* hs = hapsubsets;
+  if (!hs || (n_jobs > 0 && (!hs->genome_id || !hs->rec || !hs->tru || !hs->sub))) return fail(QM_E_INVAL, "qm_extract_files_hapsubsets: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_hapsubsets: haplotypes are replayed from indels, MNPs and complex records, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (hs->gap < 0 || hs->gap > QM_HAP_MAX_GAP)
+    return fail(QM_E_INVAL, "qm_extract_files_hapsubsets: gap " + std::to_string(hs->gap) + " (0 to " + std::to_string(QM_HAP_MAX_GAP) + ")");
+  for (int j = 0; j < n_jobs; ++j) {
+    const bool file = (hs->sites_out && hs->sites_out[j]) || (hs->subsets_out && hs->subsets_out[j]);
+    if (file && hs->genome_id[j] >= 0 && (!hs->genome_seq || !hs->genome_len || !hs->genome_seq[j] || hs->genome_len[j] < 1))
+      return fail(QM_E_INVAL, "qm_extract_files_hapsubsets: job " + std::to_string(j) + " names a sites or subsets file and not the bytes of its genome");
+  }
+  if (n_jobs > 0) {
+    memset(hs->rec, 0, sizeof(uint64_t) * QM_HAP_R_COLS * (size_t)n_jobs);
+    memset(hs->tru, 0, sizeof(uint64_t) * QM_HAP_T_COLS * (size_t)n_jobs);
+    memset(hs->sub, 0, sizeof(uint64_t) * QM_HAPSUB_COLS * (size_t)n_jobs);
+  }
+  Passes P; P.hs = hs;
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
@@ -1524,6 +1670,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = atomize_pass(pc, P, err);
       if (rc == QM_OK) rc = types_pass(pc, P.ty, err);
       if (rc == QM_OK) rc = haplo_pass(pc, P.hp, err);
+      if (rc == QM_OK) rc = hapsub_pass(pc, P.hs, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

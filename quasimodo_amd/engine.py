@@ -246,7 +246,7 @@ class Engine:
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
                       truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
-                      atomize=None, vartype=None, haplo=None):
+                      atomize=None, vartype=None, haplo=None, hapsub=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -293,21 +293,24 @@ class Engine:
         [the genome's bytes per job that names a sites file]} -- qm_extract_files_haplotypes (alleles=True only):
         the rows of mixed-sample jobs with a genome gain `hap_rec` ([16] uint64, columns haplo.R_COLS), `hap_tru` ([8],
         haplo.T_COLS) and `hap_gap`; the sites files are written.
+        hapsub: the dict of haplo plus "subsets": [path or None per job] -- qm_extract_files_hapsubsets, in place
+        of haplo: the same rows and sites files, `hap_sub` ([8] uint64, columns haplo.SUB_COLS) and the subsets files.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_atomize, check_haplo, check_normalize, check_shared_call, check_vartype
+        from .passes import check_atomize, check_haplo, check_hapsub, check_normalize, check_shared_call, check_vartype
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "vartype": vartype, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_atomize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_vartype({name for name, spec in specs.items() if spec is not None}, alleles)
         check_haplo({name for name, spec in specs.items() if spec is not None}, alleles)
+        check_hapsub({name for name, spec in specs.items() if spec is not None}, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -462,6 +465,32 @@ class Engine:
         took = lambda k: hgid[k] >= 0 and not file_jobs[k].get("pure")
         unpack = lambda k: {"hap_rec": hrec[k].copy(), "hap_tru": htru[k].copy(), "hap_gap": gap} if took(k) else {}
         return self._L.qm_extract_files_haplotypes, (C.byref(ha),), unpack
+
+    def _files_hapsub(self, n, hapsub, file_jobs=(), **kw):
+        """hapsub: the dict `haplo` takes (gap, genomes, sites, seqs) plus "subsets": [path or None per job] -- the haplotype pass
+        and the search behind it from one call; a job that names either file needs its genome's bytes in `seqs`"""
+        from .haplo import check_gap
+        haplo = hapsub
+        gap = check_gap(haplo.get("gap"))
+        hgid = _c([-1 if g is None else int(g) for g in haplo["genomes"]] or [-1], np.int32)
+        paths = list(haplo.get("sites") or [None] * n)
+        seqs = list(haplo.get("seqs") or [None] * n)
+        subs = list(hapsub.get("subsets") or [None] * n)
+        if (n and hgid.shape[0] != n) or len(paths) != n or len(seqs) != n or len(subs) != n:
+            raise ValueError("hapsub: %d genomes / %d sites / %d seqs / %d subsets entries for %d jobs" % (len(haplo["genomes"]), len(paths), len(seqs), len(subs), n))
+        hrec = np.zeros((max(n, 1), _lib.QM_HAP_R_COLS), np.uint64)
+        htru = np.zeros((max(n, 1), _lib.QM_HAP_T_COLS), np.uint64)
+        hsub = np.zeros((max(n, 1), _lib.QM_HAPSUB_COLS), np.uint64)
+        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        sub_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in subs])
+        seqs = [None if x is None else bytes(x) for x in seqs]
+        seq_arr = (C.c_char_p * max(n, 1))(*seqs)
+        lens = _c([0 if x is None else len(x) for x in seqs] or [0], np.int64)
+        ha = _lib.HapsubArgs(_p(hgid), gap, 0, _p(hrec), _p(htru), out_arr, seq_arr, _p(lens), _p(hsub), sub_arr)
+        ha.keep = (hgid, out_arr, sub_arr, seqs, seq_arr, lens)   # (read during the call; the other arrays live in unpack)
+        took = lambda k: hgid[k] >= 0 and not file_jobs[k].get("pure")
+        unpack = lambda k: {"hap_rec": hrec[k].copy(), "hap_tru": htru[k].copy(), "hap_gap": gap, "hap_sub": hsub[k].copy()} if took(k) else {}
+        return self._L.qm_extract_files_hapsubsets, (C.byref(ha),), unpack
 
     def _files_boot(self, n, boot, **kw):
         bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
@@ -1011,6 +1040,43 @@ class Batch:
         ms = (C.c_float * 5)()
         self._ck(self._L.qm_batch_haplotype_timings(self._h, ms))
         return {"hap_sites_ms": ms[0], "hap_records_ms": ms[1], "hap_truth_ms": ms[2], "hap_claim_ms": ms[3], "hap_replay_ms": ms[4]}
+
+    # -- a subset search inside the mismatched sites of the haplotype pass --
+    def hapsubsets(self, columns=False, narrow_hash=False, stream=None, fetch=True):
+        """qm_batch_hapsubsets + qm_batch_get_hapsubsets behind a haplotypes(): sub [n_vcf][8] uint64, columns haplo.SUB_COLS.
+        columns=True (needs haplotypes(columns=True)) keeps the second class bytes for hapsubsetted(); narrow_hash=True is the
+        self-check mode (hashes of 4 bits: the same results, bit for bit).  fetch=False: enqueue only (hapsubset_counts() waits
+        and copies)"""
+        what = (_lib.QM_HAPSUB_COLUMNS if columns else 0) | (_lib.QM_HAPSUB_NARROW_HASH if narrow_hash else 0)
+        self._ck(self._L.qm_batch_hapsubsets(self._h, what, C.c_void_p(stream) if stream else None))
+        return self.hapsubset_counts() if fetch else None
+
+    def hapsubset_counts(self):
+        """qm_batch_get_hapsubsets: the counts of the latest hapsubsets()"""
+        sub = np.zeros((max(self.n_vcf, 1), _lib.QM_HAPSUB_COLS), np.uint64)
+        self._ck(self._L.qm_batch_get_hapsubsets(self._h, _p(sub)))
+        return sub[:self.n_vcf]
+
+    def hapsubsetted(self, v, columns=True):
+        """qm_batch_get_hapsubsetted: (cls_s uint8 [n], entry_cls_s uint8 [entries] -- the class bytes of haplotyped(v) but inside
+        PARTIAL sites, where they are haplo.SUBSET or haplo.LEFT; None both without columns --, site int32 [m], smask uint8 [m],
+        tmask uint8 [m] -- the PARTIAL sites of VCF v, ascending, and the masks of their optima over haplo.forms)"""
+        n = int(self.n_records[int(v)])
+        ne = self.engine.truth_size(int(self.truth_ids[int(v)]), alleles=True)
+        cls, ecls = (np.zeros(max(n, 1), np.uint8), np.zeros(max(ne, 1), np.uint8)) if columns else (None, None)
+        m = C.c_int64(0)
+        self._ck(self._L.qm_batch_get_hapsubsetted(self._h, int(v), _p(cls) if columns else None, _p(ecls) if columns else None,
+                                                   None, None, None, 0, C.byref(m)))
+        k = int(m.value)
+        site, sm, tm = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.uint8), np.zeros(max(k, 1), np.uint8)
+        self._ck(self._L.qm_batch_get_hapsubsetted(self._h, int(v), None, None, _p(site), _p(sm), _p(tm), k, C.byref(m)))
+        return (cls[:n] if columns else None), (ecls[:ne] if columns else None), site[:k], sm[:k], tm[:k]
+
+    def hapsubset_timings(self):
+        """qm_batch_hapsubset_timings (set_timing on): milliseconds of the latest hapsubsets() between HIP events"""
+        ms = (C.c_float * 1)()
+        self._ck(self._L.qm_batch_hapsubset_timings(self._h, ms))
+        return {"hap_subsets_ms": ms[0]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

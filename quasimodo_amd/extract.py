@@ -19,13 +19,18 @@ import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
-from .passes import PASSES, check_atomize, check_haplo, check_normalize, check_shared_call, check_vartype, requested_by
+from .passes import PASSES, check_atomize, check_haplo, check_hapsub, check_normalize, check_shared_call, check_vartype, requested_by
 from .vcfio import scan_vcf
 
 
 def is_pure_strain(vcf_file):
     """extract_TP_FP_SNPs.py:33 -- sample name ends in -1-0 / -0-1: no truth comparison."""
     return os.path.basename(vcf_file).split(".")[0].endswith(("-1-0", "-0-1"))
+
+
+def _hap_gap(j):
+    """the gap of the job's haplotype pass, asked for as Job.haplo or -- with the subset search behind it -- as Job.hapsub"""
+    return j.hapsub if j.hapsub is not None else j.haplo
 
 
 @dataclass
@@ -77,6 +82,9 @@ class Job:
     haplo: int = None         # the gap g (0 to 32): stats gain hap_rec / hap_tru / hap_gap (the same gap for every such job of a call)
     haplo_genome: str = None  # FASTA of the genome the VCF was called against (with Job.haplo)
     sites_out: str = None     # where the job's table of MATCH sites goes (extract_many(haplo=) derives it)
+    # a subset search inside the sites the haplotype pass left MISMATCH or CONFLICT; with Job.haplo
+    hapsub: int = None        # the gap g, IN PLACE OF Job.haplo: the pass and the search behind it; stats gain hap_sub ([8], haplo.SUB_COLS) too
+    subsets_out: str = None   # where the job's table of PARTIAL sites goes (extract_many(hapsub=True) derives it)
 
 
 def _paths(job):
@@ -147,7 +155,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None):
+                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -212,7 +220,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
              "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
              "atomize": atomize is not None and atomize is not False, "vartype": vartype is not None and vartype is not False,
-             "haplo": haplo is not None and haplo is not False}
+             "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub)}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -276,19 +284,24 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         tedges = check_edges(None if vartype is True else vartype)
         for j in jobs:
             j.vartype = None if is_pure_strain(j.vcf_file) else tedges
-    if given["haplo"]:
-        from .haplo import check_gap, sites_path
+    if hapsub and (haplo is None or haplo is False):
+        raise ValueError("hapsub (--hap-subsets) searches the sites of the haplotype pass: it needs haplo= (the gap, or the gap and the genomes) in the same call")
+    if given["haplo"] or given["hapsub"]:
+        from .haplo import check_gap, sites_path, subsets_path
         hopt = haplo if isinstance(haplo, dict) else {"gap": None if haplo is True else haplo}
         hgap = check_gap(hopt.get("gap"))
         hgen = list(hopt["genomes"]) if hopt.get("genomes") is not None else [j.haplo_genome for j in jobs]
         if len(hgen) != len(jobs):
             raise ValueError("haplo: %d genomes entries for %d jobs" % (len(hgen), len(jobs)))
         for j, g in zip(jobs, hgen):
-            j.haplo, j.haplo_genome = (hgap, g) if g and not is_pure_strain(j.vcf_file) else (None, None)
-            if j.haplo is not None:
+            on, j.haplo_genome = (hgap, g) if g and not is_pure_strain(j.vcf_file) else (None, None)
+            j.haplo, j.hapsub = (None, on) if hapsub else (on, None)   # (hapsub: the pass and the search from one call, asked for in place of haplo)
+            if on is not None:
                 _paths(j)
                 j.sites_out = j.sites_out or sites_path(j)
-        if not any(j.haplo is not None for j in jobs) and not all(is_pure_strain(j.vcf_file) for j in jobs):
+                if hapsub:
+                    j.subsets_out = j.subsets_out or subsets_path(j)
+        if not any(_hap_gap(j) is not None for j in jobs) and not all(is_pure_strain(j.vcf_file) for j in jobs):
             raise ValueError("haplo: no job names the genome its VCF was called against (Job.haplo_genome, or haplo={'genomes': [...]})")
     if boot is not None:
         from .bootstrap import DEFAULTS
@@ -329,12 +342,13 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     check_atomize(requested_by(jobs), alleles)
     check_vartype(requested_by(jobs), alleles)
     check_haplo(requested_by(jobs), alleles)
+    check_hapsub(requested_by(jobs), alleles)
     for j in jobs:
-        if j.haplo is not None and not j.haplo_genome:
+        if _hap_gap(j) is not None and not j.haplo_genome:
             raise ValueError("%s: Job.haplo without Job.haplo_genome (the FASTA the VCF was called against)" % j.vcf_file)
     by_truth = {}
     for j in jobs:
-        if j.haplo is not None and by_truth.setdefault(os.path.realpath(j.snp_file), (j.haplo_genome, j.vcf_file))[0] != j.haplo_genome:
+        if _hap_gap(j) is not None and by_truth.setdefault(os.path.realpath(j.snp_file), (j.haplo_genome, j.vcf_file))[0] != j.haplo_genome:
             raise ValueError("haplo: %s and %s share the truth file %s and name the genomes %s and %s (the sites of a truth set belong to one genome)"
                              % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.haplo_genome))
     by_truth = {}
@@ -367,7 +381,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = sf = cxs = nzs = ats = tys = hps = None
+    ts = vt = nm = sf = cxs = nzs = ats = tys = hps = hss = None
     if any(j.vartype is not None and not p for j, p in zip(jobs, pure)):
         from .vartype import check_edges
         tys = {"edges": check_edges(next(j.vartype for j in jobs if j.vartype is not None)),
@@ -443,21 +457,26 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                        "rescued": [j.rescued_out if j.normalize else None for j in jobs]}
                 for path in [x for x in nzs["rescued"] if x]:
                     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            if any(j.haplo is not None for j in jobs):
+            if any(_hap_gap(j) is not None for j in jobs):
                 from .haplo import check_gap
                 from .motifs import read_fasta
                 seqs = {}
                 for j in jobs:
-                    if j.haplo is not None and j.haplo_genome not in seqs:
+                    if _hap_gap(j) is not None and j.haplo_genome not in seqs:
                         seqs[j.haplo_genome] = bytes(read_fasta(j.haplo_genome))
                         loaded[("haplo", j.haplo_genome)] = engine.genome_load(seqs[j.haplo_genome])
-                on = [j.haplo is not None for j in jobs]
-                hps = {"gap": check_gap(next(j.haplo for j in jobs if j.haplo is not None)),
+                on = [_hap_gap(j) is not None for j in jobs]
+                hps = {"gap": check_gap(next(_hap_gap(j) for j in jobs if _hap_gap(j) is not None)),
                        "genomes": [loaded[("haplo", j.haplo_genome)] if w else -1 for j, w in zip(jobs, on)],
                        "sites": [j.sites_out if w else None for j, w in zip(jobs, on)],
-                       "seqs": [seqs[j.haplo_genome] if w and j.sites_out else None for j, w in zip(jobs, on)]}
+                       "seqs": [seqs[j.haplo_genome] if w and (j.sites_out or (j.hapsub is not None and j.subsets_out)) else None for j, w in zip(jobs, on)]}
                 for path in [x for x in hps["sites"] if x]:
                     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                if any(j.hapsub is not None for j in jobs):   # (the pass table let no job ask for haplo beside it)
+                    hss = dict(hps, subsets=[j.subsets_out if j.hapsub is not None else None for j in jobs])
+                    hps = None
+                    for path in [x for x in hss["subsets"] if x]:
+                        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
             if any(j.atomize for j in jobs):
                 ats = {"want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]}
                 for path in [x for x in ats["atoms"] if x]:
@@ -477,7 +496,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats, vartype=tys, haplo=hps)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats, vartype=tys, haplo=hps, hapsub=hss)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

@@ -1,6 +1,7 @@
 """Clusters of records matched by replayed haplotype: the unmatched records of a small region and the unmatched
 truth entries of the same region are each replayed onto the genome; where the two sequences are equal, both sides are rescued.
-The bounded core of what `rtg vcfeval` and hap.py's `xcmp` do: all or nothing per region, no subset search.
+The bounded core of what `rtg vcfeval` and hap.py's `xcmp` do: all or nothing per region.  Behind it, opt-in, a subset search
+inside the regions that did not match (k_hap_subsets): `forms`, `search`, `subset_counts` below.
 
 Everything here is the definition on strings, which k_hap_sites / k_hap_truth / k_hap_records / k_hap_claim / k_hap_replay
 (csrc/qmvt_haplo.hip) restate on allele codes and the 4-bit packed genome; `counts` restates the pass's tables for one VCF; the
@@ -238,6 +239,111 @@ def counts(genome, truth, pos, ref, alt, flags, kept, tp, gap=None, detail=None)
     return rec, tru, cls, site, ecls
 
 
+# ---- a subset search inside a mismatched site ---------------------------------------------------------------
+# class bytes of the second arrays (QM_HAP_C_SUBSET / QM_HAP_C_LEFT): inside a PARTIAL site only
+SUBSET, LEFT = 14, 15
+SUB_CLASS_NAMES = CLASS_NAMES + ("subset", "left")
+SUB_COLS = ("searched", "partial", "nosubset", "tp_s", "rescued_s", "found_s", "left_lines", "left_entries")   # QM_HAPSUB_*
+SEARCHED_OUTCOMES = (MISMATCH, CONFLICT)
+
+
+def form_key(f):
+    """the total order of distinct trimmed forms: (q, |r|, |a|, a as a string over A<C<G<T)"""
+    return f[0], len(f[1]), len(f[2]), f[2]
+
+
+def forms(side):
+    """the distinct trimmed forms of a side -- spellings (p, ref, alt) --: spellings that trim to one form collapse; in the total
+    order of form_key.  Bit k of a side's mask is forms(side)[k]."""
+    return sorted({trim(*v) for v in side}, key=form_key)
+
+
+def conflict(a, b):
+    """two forms, a before b in the order: b starts inside a's REF, or b is an insertion at a's start"""
+    return b[0] < a[0] + len(a[1]) or (b[0] == a[0] and not b[1])
+
+
+def subset(fs, mask):
+    return [f for k, f in enumerate(fs) if mask >> k & 1]
+
+
+def admissible(fs, mask):
+    """no two forms of the subset conflict (the neighbour test: `conflicts` on the subset in order)"""
+    return mask != 0 and not conflicts(subset(fs, mask))
+
+
+def _bits(m):
+    return bin(m).count("1")
+
+
+def search(G, ws, we, recs, ents):
+    """The optimum of a site: recs / ents are the spellings of its open lines and open entries (at most MAX_ITEMS each).  A
+    candidate is a non-empty admissible subset S of the line forms and one T of the entry forms whose replays over [ws, we] are
+    equal; the optimum has the largest |S| + |T|, then the larger |T|, then the smallest S mask, then the smallest T mask.
+    Returns (S mask, T mask, line forms, entry forms, the replay) or None."""
+    if len(recs) > MAX_ITEMS or len(ents) > MAX_ITEMS:
+        raise ValueError("haplo.search: %d lines and %d entries (at most %d each)" % (len(recs), len(ents), MAX_ITEMS))
+    fa, fb = forms(recs), forms(ents)
+    by_replay = {}
+    for mt in range(1, 1 << len(fb)):
+        if admissible(fb, mt):
+            by_replay.setdefault(replay(G, ws, we, subset(fb, mt)), []).append(mt)
+    best = None
+    for ms in range(1, 1 << len(fa)):
+        if not admissible(fa, ms):
+            continue
+        x = replay(G, ws, we, subset(fa, ms))
+        for mt in by_replay.get(x, ()):
+            key = (-(_bits(ms) + _bits(mt)), -_bits(mt), ms, mt)
+            if best is None or key < best[0]:
+                best = (key, x)
+    return None if best is None else (best[0][2], best[0][3], fa, fb, best[1])
+
+
+def subset_counts(genome, truth, pos, ref, alt, flags, kept, tp, gap=None, detail=None, counted=None):
+    """The search behind the pass for one VCF, restated.  counted: (what `counts` returned, the list its detail= filled) for
+    the same arguments, or None: `counts` runs here.  Returns (sub [len(SUB_COLS)] uint64, cls_s uint8 [n], ecls_s uint8
+    [entries]): the count block and the second class bytes -- the pass's own but inside PARTIAL sites, where they are SUBSET
+    or LEFT.  detail: a list that receives (site, S mask, T mask, rescued record indices, left record indices, found entry
+    indices, left entry indices, the replay) of every PARTIAL site, sites ascending."""
+    if counted is None:
+        tried = []
+        res = counts(genome, truth, pos, ref, alt, flags, kept, tp, gap, tried)
+    else:
+        res, tried = counted
+    rec, tru, cls, _, ecls = res
+    G = symbols(genome)
+    ent_s = [(p, spell(r), spell(a)) for p, r, a in truth_order(*truth)]
+    sub = np.zeros(len(SUB_COLS), np.uint64)
+    cls_s, ecls_s = cls.copy(), ecls.copy()
+    sub[3], sub[5] = rec[2], tru[2]
+    for s, ws, we, what, recs, ents, _, _ in tried:
+        if what not in SEARCHED_OUTCOMES:
+            continue
+        sub[0] += 1
+        spelled = [(int(pos[i]), spell(ref[i]), spell(alt[i])) for i in recs]
+        got = search(G, ws, we, spelled, [ent_s[j] for j in ents])
+        if got is None:
+            sub[2] += 1
+            continue
+        ms, mt, fa, fb, x = got
+        sub[1] += 1
+        chosen_a, chosen_b = set(subset(fa, ms)), set(subset(fb, mt))
+        inr = [i for i, v in zip(recs, spelled) if trim(*v) in chosen_a]
+        outr = [i for i in recs if i not in inr]
+        ine = [j for j in ents if trim(*ent_s[j]) in chosen_b]
+        oute = [j for j in ents if j not in ine]
+        cls_s[inr], cls_s[outr], ecls_s[ine], ecls_s[oute] = SUBSET, LEFT, SUBSET, LEFT
+        sub[3] += sum(1 for i in inr if int(flags[i]) & F_IDDOT and not tp[i])
+        sub[4] += len(inr)
+        sub[5] += len(ine)
+        sub[6] += len(outr)
+        sub[7] += len(oute)
+        if detail is not None:
+            detail.append((s, ms, mt, inr, outr, ine, oute, x))
+    return sub, cls_s, ecls_s
+
+
 def truth_sites(genome, truth, gap=None):
     """(first_entry, lo, hi) int32 arrays: the sites of a truth set, what qm_truth_sites returns"""
     ent_s = [(p, spell(r), spell(a)) for p, r, a in truth_order(*truth)]
@@ -253,6 +359,34 @@ def sites_path(job):
     """the MATCH sites of a job beside fp/ and tp/: hap/<x>.sites.tsv"""
     d, base = os.path.split(job.fp_out)
     return os.path.join(os.path.dirname(d), "hap", base[:-len(".fp.vcf")] + ".sites.tsv")
+
+
+SUBSETS_HEADER = "#site\tWIN_LO\tWIN_HI\tRESCUED\tLEFT_LINES\tFOUND\tLEFT_ENTRIES\tREPLAY_LINES\tREPLAY_TRUTH"
+
+
+def subsets_path(job):
+    """the PARTIAL sites of a job beside its sites file: hap/<x>.subsets.tsv"""
+    return sites_path(job)[:-len(".sites.tsv")] + ".subsets.tsv"
+
+
+def read_subsets(path):
+    """[(site, window_lo, window_hi, the lines rescued by subset and the lines left as [(line number in the input VCF, POS, REF,
+    ALT as the line spells them)], the entries found by subset and the entries left as [(pos, ref, alt)], the replay of the
+    chosen lines, the replay of the chosen entries)]; an empty list is written as `.`"""
+    with open(path, newline="\n") as fh:
+        lines = fh.read().split("\n")
+    if lines[0] != SUBSETS_HEADER or lines[-1] != "":
+        raise ValueError("%s: not a subsets file (header %r)" % (path, lines[0]))
+    cells = lambda c: [] if c == "." else [y.split(":") for y in c.split(";")]
+    out = []
+    for k, ln in enumerate(lines[1:-1]):
+        r = ln.split("\t")
+        if len(r) != 9:
+            raise ValueError("%s row %d: %r" % (path, k + 1, ln))
+        recs = [[(int(x[0]), x[1], x[2], x[3]) for x in cells(c)] for c in r[3:5]]
+        ents = [[(int(x[0]), x[1], x[2]) for x in cells(c)] for c in r[5:7]]
+        out.append((int(r[0]), int(r[1]), int(r[2]), recs[0], recs[1], ents[0], ents[1], r[7], r[8]))
+    return out
 
 
 def read_sites(path):
@@ -292,6 +426,44 @@ def performance_row(rec, tru):
         p, r = r_round3(r_div(tp, kept)), r_round3(r_div(hit, entries))
         out += [tp, kept - tp, entries - hit, p, r, r_round3(r_div(2 * (p * r), p + r))]
     return out + rec[3:] + [tru[0], tru[3], tru[4], tru[5], tru[6], tru[7]]
+
+
+SUBSETS_TABLE_HEADER = (("caller", "mixture"), (TABLE_HEADER[1][:12] + ("TP_S", "FP_S", "FN_S", "Precision_S", "Recall_S", "F1_S")
+                        + ("sites_searched", "sites_partial", "sites_nosubset", "rescued_S", "left_lines", "left_entries")))
+
+
+def performance_row_subsets(rec, tru, sub):
+    """One VCF's rows of the pass and of the search -> TP, FP, FN, Precision, Recall, F1 by spelling, by haplotype (_H) and by
+    subset (_S: TP_S lines out of the kept lines, FOUND_S entries out of the entries), then the six counts of the search;
+    ratios and NA as performance_row"""
+    from .tables import r_div, r_round3
+    sub = [int(x) for x in sub]
+    kept, entries = int(rec[0]), int(tru[0])
+    out = performance_row(rec, tru)[:12]
+    if kept == 0:
+        out += [0, 0, entries - sub[5], None, None, None]
+    else:
+        p, r = r_round3(r_div(sub[3], kept)), r_round3(r_div(sub[5], entries))
+        out += [sub[3], kept - sub[3], entries - sub[5], p, r, r_round3(r_div(2 * (p * r), p + r))]
+    return out + [sub[0], sub[1], sub[2], sub[4], sub[6], sub[7]]
+
+
+def write_performance_hapsubsets(path, rows, custom=False):
+    """final_tables/caller_performance_hapsubsets.tsv (custom: without the mixture column).  rows: iterable of (caller_lower or
+    label, sample, stats) with stats["hap_rec"] / stats["hap_tru"] / stats["hap_sub"]; jobs without them are left out.  Written
+    atomically."""
+    from .tables import CALLER_MAP, r_str
+    head = (SUBSETS_TABLE_HEADER[0][:1] if custom else SUBSETS_TABLE_HEADER[0]) + SUBSETS_TABLE_HEADER[1]
+    lines = ["\t".join(head)]
+    for caller, sample, stats in rows:
+        if "hap_sub" not in stats:
+            continue
+        name = [caller] if custom else [CALLER_MAP.get(caller, caller), sample]
+        lines.append("\t".join(name + [r_str(v) for v in performance_row_subsets(stats["hap_rec"], stats["hap_tru"], stats["hap_sub"])]))
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    with open(tmp, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    os.replace(tmp, path)
 
 
 def write_performance_haplotype(path, rows, custom=False):

@@ -18,6 +18,8 @@ PASSES = (
     Pass("nearmiss", ("explain",), ("explain",), "--explain-errors", "explain: the explained jobs of one call share one radius", ()),
     Pass("normalize", ("normalize",), ("normalize",), "--normalize", None, ()),
     Pass("haplo", ("haplo",), ("haplo",), "--haplotypes", "haplo: the jobs of one call share one gap", ()),
+    # the haplotype pass AND the subset search behind it, from one call: asked for in place of haplo, never beside it
+    Pass("hapsub", ("hapsub",), ("hapsub",), "--hap-subsets", "hapsub: the jobs of one call share one gap", ()),
     Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
     Pass("vartype", ("vartype",), ("vartype",), "--by-type", "vartype: the typed jobs of one call share one list of size edges", ()),
     Pass("context", ("context",), ("context",), "--seq-context",
@@ -66,6 +68,13 @@ def check_haplo(requested, alleles):
     is touched"""
     if "haplo" in requested and not alleles:
         raise ValueError("haplo (--haplotypes) needs the allele-extended mode (--alleles): a single-base batch holds no indels, MNPs or complex records to replay")
+
+
+def check_hapsub(requested, alleles):
+    """--hap-subsets runs the haplotype pass and searches the sites it left MISMATCH or CONFLICT: like that pass it needs the
+    allele-extended mode.  ValueError before a file is touched"""
+    if "hapsub" in requested and not alleles:
+        raise ValueError("hapsub (--hap-subsets) needs the allele-extended mode (--alleles): a single-base batch holds no indels, MNPs or complex records to replay")
 
 
 def check_vartype(requested, alleles):

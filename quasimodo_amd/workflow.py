@@ -166,7 +166,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
                          context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None, haplotypes=None,
-                         hap_gap=None):
+                         hap_gap=None, hap_subsets=False):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -226,7 +226,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
                  context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False,
-                 haplo=haplotypes is not None)
+                 haplo=haplotypes is not None and not hap_subsets, hapsub=bool(hap_subsets))
+    if hap_subsets and haplotypes is None:
+        raise WorkflowError("--hap-subsets searches the sites of the haplotype pass: it needs --haplotypes (and the genomes)")
     hgap = None
     if haplotypes is not None:
         from .haplo import check_gap
@@ -311,6 +313,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("extractTP\t%s\t%s" % (c, src))
         if haplotypes is not None:
             print("caller_performance_haplotype.tsv\t%s\t%d" % (",".join(callers), hgap))
+        if hap_subsets:
+            print("caller_performance_hapsubsets.tsv\t%s\t%d" % (",".join(callers), hgap))
         if normalize is not None:
             print("caller_performance_normalized.tsv\t%s" % ",".join(callers))
         if atomize:
@@ -392,8 +396,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if tedges is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].vartype = tedges
         if haplotypes is not None and not s.endswith(("-1-0", "-0-1")):
-            jobs[-1].haplo, jobs[-1].haplo_genome = hgap, haplotypes[s[:2]]
+            jobs[-1].haplo_genome = haplotypes[s[:2]]
+            jobs[-1].haplo, jobs[-1].hapsub = (None, hgap) if hap_subsets else (hgap, None)
             jobs[-1].sites_out = os.path.join(d, "hap", os.path.basename(src)[:-4] + ".sites.tsv")
+            if hap_subsets:
+                jobs[-1].subsets_out = os.path.join(d, "hap", os.path.basename(src)[:-4] + ".subsets.tsv")
         meta.append((c, s))
     from .vcfio import split_variants
     for kind in ("xsnp", "xindel"):                                      # extract_snp / extract_indel / extract_nucmer_*:
@@ -461,6 +468,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if haplotypes is not None:
             from .haplo import write_performance_haplotype
             write_performance_haplotype(os.path.join(tables, "caller_performance_haplotype.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
+        if hap_subsets:
+            from .haplo import write_performance_hapsubsets
+            write_performance_hapsubsets(os.path.join(tables, "caller_performance_hapsubsets.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
         if atomize:
             from .atomize import write_performance_atomized
             write_performance_atomized(os.path.join(tables, "caller_performance_atomized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])

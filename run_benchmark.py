@@ -163,6 +163,10 @@ def _type_bins(by_type, type_bins):
               help="With --alleles: also match clusters of lines by replayed haplotype (the unmatched lines and the unmatched truth entries of a small "
                    "region, each replayed onto the genome, are rescued where the two sequences are equal): write "
                    "final_tables/caller_performance_haplotype.tsv and callers/*/hap/*.sites.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config).")
+@click.option("--hap-subsets", "hap_subsets", is_flag=True, default=False,
+              help="With --alleles (implies --haplotypes): also search the regions that did not match for the largest pair of subsets of their lines and "
+                   "truth entries whose replayed sequences are equal (one true FP or one missed entry beside a respelled pair no longer costs the "
+                   "whole region): write final_tables/caller_performance_hapsubsets.tsv and callers/*/hap/*.subsets.tsv beside the outputs of --haplotypes.")
 @click.option("--hap-gap", "hap_gap", type=int, default=None,
               help="--haplotypes: truth entries at most twice this many bases apart share a region, whose window reaches this far on either side [default: 10; 0 to 32].")
 @click.option("--merlin-ref", type=click.Path(), default=None, help="Merlin FASTA for TM (default: MerlinRef of config/config.yaml).")
@@ -172,7 +176,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None):
+         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False):
+    haplotypes = haplotypes or hap_subsets   # the search runs behind the haplotype pass of the same call
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
         sys.exit(2)
@@ -205,7 +210,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
                                              alleles=alleles, normalize=genomes if normalize else None, atomize=atomize,
                                              by_type=_type_bins(by_type, type_bins), haplotypes=genomes if haplotypes else None,
-                                             hap_gap=_hap_gap(haplotypes, hap_gap))
+                                             hap_gap=_hap_gap(haplotypes, hap_gap), hap_subsets=hap_subsets)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -265,13 +270,17 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
 @click.option("--haplotypes", "haplotypes", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose lines could be replayed (hcmv has it).")
 @click.option("--hap-gap", "hap_gap", type=int, default=None, help="Not available here (see --haplotypes).")
+@click.option("--hap-subsets", "hap_subsets", is_flag=True, default=False, help="Not available here (see --haplotypes).")
 def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, novenn=False, outpath=None, threads=2, snps=None, gpus=1,
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
             surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False,
-            by_type=False, type_bins=None, haplotypes=False, hap_gap=None):
+            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False):
     from quasimodo_amd import workflow
     try:
+        if hap_subsets:
+            raise workflow.WorkflowError("--hap-subsets needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --haplotypes --hap-subsets)")
         if haplotypes or hap_gap is not None:
             raise workflow.WorkflowError("--haplotypes needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --haplotypes)")
