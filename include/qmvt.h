@@ -759,6 +759,35 @@ int qm_batch_get_hapsubsets(qm_batch* b, uint64_t* sub /*[n_vcf][QM_HAPSUB_COLS]
 int qm_batch_get_hapsubsetted(qm_batch* b, int vcf, uint8_t* cls_s /*[n]*/, uint8_t* entry_cls_s /*[entries]*/, int32_t* site_s /*[capacity]*/,
                               uint8_t* smask /*[capacity]*/, uint8_t* tmask /*[capacity]*/, int64_t capacity, int64_t* n_out);
 int qm_batch_hapsubset_timings(qm_batch* b, float* ms1);
+/* The QUAL ROC under normal-form and atom matching: the 256-threshold sweep of qm_batch_get_roc, with the hit of
+ * qm_batch_normalize (hitN) or of qm_batch_atomize (hitA) in place of the hit by spelling.  It reads what those passes left in
+ * the batch and normalises or atomises nothing again.  Build-defined, parity unpinned, as both passes are.
+ * Universe, as in qm_batch_get_roc of an allele-extended batch: records with two valid allele codes and a QUAL bin b >= 0
+ *   (floor(QUAL) clamped to n_bins - 1; NaN and QUAL < 0 have none), kept or not.
+ * By normal form: tpN = (hitN and QM_F_IDDOT) or QM_F_TPLINE; TP_N_hist[b]++ if tpN, else FP_N_hist[b]++.  The truth-side unit
+ *   is the form; its best is the highest b over the records with hitN and QM_F_IDDOT whose form it is; U_N_hist[b] = forms whose
+ *   best is b.  Baseline: QM_NORM_T_FORMS.  A VCF that named no genome in qm_batch_normalize has zero rows and a zero baseline.
+ * By atoms: hitA = all atoms in the atom set for an atomisable record, the hit by spelling (valid codes, no QM_F_NOKEY, the
+ *   spelling in the truth set's allele-extended table) for any other; tpA and the two histograms as above.  The truth-side unit
+ *   is the allele-extended entry.  Carriers are the records of the universe with QM_F_IDDOT and without QM_F_NOKEY: an
+ *   atomisable carrier raises the best of every atom of its hit mask (a partial record's too), any other carrier the best of the
+ *   entry it is spelled like.  The best of an atomisable entry is the minimum over its atoms (none if an atom has none), that of
+ *   any other entry its own.  Baseline: QM_ATOM_T_ENTRIES.
+ * roc_n / roc_a [v][3][n_bins]: the suffix sums TP(t), FP(t), U(t) in the layout of qm_batch_get_roc; base[v][2]: the two
+ *   baselines (0 for a matching not swept); FN_X(t) = base_X - U_X(t).
+ * qm_batch_rescue_roc: asynchronous on `stream` (NULL = the context's own), ordered behind both producers on whatever stream.
+ *   QM_E_INVAL for which = 0 or any other bit; QM_E_STATE for a single-base batch, if a truth set was released, and if the batch
+ *   has not finished qm_batch_normalize(.., QM_NORM_COLUMNS) (QM_RROC_NORM) or qm_batch_atomize(QM_ATOM_COLUMNS) (QM_RROC_ATOM)
+ *   since its latest run.  A new call of a producer waits for a sweep still in flight and forgets that matching's rows.
+ * qm_batch_get_rescue_roc: waits for the sweep, then copies (any pointer may be NULL; QM_E_STATE for the rows of a matching the
+ *   latest sweep did not make).
+ * qm_batch_rescue_roc_timings (qm_batch_set_timing on): milliseconds between HIP events of k_rroc_records and k_rroc_units by
+ *   normal form, then by atoms (0 for a matching not swept). */
+#define QM_RROC_NORM 1u
+#define QM_RROC_ATOM 2u
+int qm_batch_rescue_roc(qm_batch* b, unsigned which /*QM_RROC_NORM | QM_RROC_ATOM*/, void* stream);
+int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n /*[n_vcf][3][n_bins]*/, uint64_t* roc_a /*[n_vcf][3][n_bins]*/, uint64_t* base /*[n_vcf][2]*/);
+int qm_batch_rescue_roc_timings(qm_batch* b, float* ms4);
 int qm_truth_sites(qm_ctx* ctx, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
                    int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
@@ -1230,6 +1259,23 @@ typedef struct qm_hapsub_args {
 int qm_extract_files_hapsubsets(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                 qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                                 void* global_dev, const qm_hapsub_args* hapsubsets);
+
+/* qm_extract_files_ex plus the QUAL ROC under normal-form and atom matching over its batch; mode must be
+ * QM_BATCH_ALLELES (QM_E_STATE otherwise).  The call runs qm_batch_normalize and qm_batch_atomize with their columns itself and
+ * hands out none of their rows or files.  Mixed-sample jobs with want[j] != 0 get roc_n[j][3][n_bins], roc_a[j][3][n_bins] and
+ * base[j][2] of qm_batch_get_rescue_roc (genome_id[j]: a qm_genome_load id, or -1: the rows by normal form and their baseline
+ * stay zero); the others, pure-strain jobs among them, get zero rows.  The VCF outputs, stats and roc are those of
+ * qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_rescue_roc_args {
+  const int32_t* genome_id;         /* [n_jobs], -1 = no genome */
+  const uint8_t* want;              /* [n_jobs] */
+  uint64_t* roc_n;                  /* [n_jobs][3][n_bins] */
+  uint64_t* roc_a;                  /* [n_jobs][3][n_bins] */
+  uint64_t* base;                   /* [n_jobs][2] */
+} qm_rescue_roc_args;
+int qm_extract_files_rescue_roc(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                                void* global_dev, const qm_rescue_roc_args* rescue_roc);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

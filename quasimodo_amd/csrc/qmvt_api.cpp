@@ -35,6 +35,7 @@
 #include "qmvt_atom.h"
 #include "qmvt_types.h"
 #include "qmvt_haplo.h"
+#include "qmvt_rroc.h"
 
 using namespace qm;
 
@@ -928,6 +929,16 @@ struct qm_batch {
   unsigned hs_made = 0;               // 1 | what: what the latest qm_batch_hapsubsets made behind the latest qm_batch_haplotypes
   bool hs_listed = false;             // hs_list holds the PARTIAL pairs of the latest search
   std::vector<int32_t> hs_list;       // (VCF, site, S mask, T mask) per PARTIAL pair, VCF after VCF, sites ascending
+  // qm_batch_rescue_roc (lazy): the 16-bit best cells of every VCF's units in one pool (by normal form: a cell per
+  // truth entry; by atoms: a cell per slot of the atom set and per entry), the per-VCF descriptors, [2][n_vcf][3][n_bins] rows
+  // (suffix sums once k_rroc_units ran) and [n_vcf][2] baselines one behind the other; ev_rroc says when the sweep is done
+  DevBuf<uint32_t> rr_best;
+  DevBuf<RrocVcf> rr_vcfs;
+  DevBuf<uint64_t> rr_out;
+  hipEvent_t ev_rroc = nullptr;
+  hipEvent_t ev_rrt[5] = {};          // qm_batch_set_timing: around the two kernels of either matching
+  bool rr_timed = false;
+  unsigned rr_made = 0;               // QM_RROC_*: what the latest qm_batch_rescue_roc made behind the latest run of its producers
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -970,6 +981,8 @@ static void batch_free(qm_batch* b) {
   for (auto& e : b->ev_hpt) if (e) (void)hipEventDestroy(e);
   if (b->ev_hapsub) (void)hipEventDestroy(b->ev_hapsub);
   for (auto& e : b->ev_hst) if (e) (void)hipEventDestroy(e);
+  if (b->ev_rroc) (void)hipEventDestroy(b->ev_rroc);
+  for (auto& e : b->ev_rrt) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
@@ -987,6 +1000,7 @@ static const PassEvent PASS_EVENTS[] = {
     {&qm_batch::ev_boot, true},   {&qm_batch::ev_votes, true}, {&qm_batch::ev_nm, true},     {&qm_batch::ev_sf, false},
     {&qm_batch::ev_cx, true},     {&qm_batch::ev_norm, false}, {&qm_batch::ev_atom, false},
     {&qm_batch::ev_types, false}, {&qm_batch::ev_haplo, false}, {&qm_batch::ev_hapsub, false},
+    {&qm_batch::ev_rroc, false},
 };
 // (ev_haplo: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
 // flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
@@ -1342,6 +1356,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   b->ty_made = 0;
   b->hp_made = 0;
   b->hs_made = 0;
+  b->rr_made = 0;
   b->last_global = g;
   return QM_OK;
 }
@@ -2855,7 +2870,11 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   hipStream_t st;
   rc = pass_stream(b, stream, &b->ev_norm, &st);
   if (rc != QM_OK) return rc;
+  // A sweep behind the previous call (qm_batch_rescue_roc, maybe on another stream) reads the columns this call rewrites and may
+  // regrow: it is waited for here, not only on the stream.
+  if (b->ev_rroc) HIPCHK(hipEventSynchronize(b->ev_rroc));
   b->nz_made = 0;   // from here on the outputs are rewritten
+  b->rr_made &= ~QM_RROC_NORM;   // ... and the sweep's rows belong to the call before
   const size_t np = (size_t)b->L.n_pad;
   rc = b->nz_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->nz_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -3077,7 +3096,9 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
   hipStream_t st;
   rc = pass_stream(b, stream, &b->ev_atom, &st);
   if (rc != QM_OK) return rc;
+  if (b->ev_rroc) HIPCHK(hipEventSynchronize(b->ev_rroc));   // (as in qm_batch_normalize: the sweep reads the sets and the columns)
   b->at_made = 0;   // from here on the outputs are rewritten
+  b->rr_made &= ~QM_RROC_ATOM;
   const size_t np = (size_t)b->L.n_pad;
   rc = b->at_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->at_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -3194,6 +3215,114 @@ extern "C" int qm_truth_atoms(qm_ctx* c, int truth_id, uint32_t* keys, int64_t c
   *n_out = (int64_t)h.size();
   if ((int64_t)h.size() > capacity) return fail(QM_E_RANGE, "qm_truth_atoms: %zu atoms, room for %lld", h.size(), (long long)capacity);
   if (keys && !h.empty()) memcpy(keys, h.data(), h.size() * 4);
+  return QM_OK;
+}
+// ---- the QUAL ROC under normal-form and atom matching ----
+extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
+  NEED_FINISHED(b, "qm_batch_rescue_roc");
+  if (which == 0 || (which & ~(QM_RROC_NORM | QM_RROC_ATOM))) return fail(QM_E_INVAL, "qm_batch_rescue_roc: which = %u", which);
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_rescue_roc: a single-base batch has no rescue passes to sweep (create the batch with QM_BATCH_ALLELES)");
+  const bool wn = (which & QM_RROC_NORM) != 0, wa = (which & QM_RROC_ATOM) != 0;
+  if (wn && !(b->nz_made & QM_NORM_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_rescue_roc: QM_RROC_NORM needs qm_batch_normalize(.., QM_NORM_COLUMNS) behind the latest run");
+  if (wa && !(b->at_made & QM_ATOM_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_rescue_roc: QM_RROC_ATOM needs qm_batch_atomize(QM_ATOM_COLUMNS) behind the latest run");
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf, nb = (size_t)b->n_bins;
+  int rc = truths_live(b, "qm_batch_rescue_roc");
+  if (rc != QM_OK) return rc;
+  // the cells of every VCF, one behind the other (a VCF's own: what one VCF carries is nothing to the next on the same truth set)
+  std::vector<RrocVcf> vcfs(std::max<size_t>(nv, 1));
+  memset(vcfs.data(), 0, vcfs.size() * sizeof(RrocVcf));
+  std::vector<size_t> off_n(nv, 0), off_a(nv, 0), off_e(nv, 0);
+  size_t words = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    Truth& t = c->truths[(size_t)b->L.vcfs[v].truth];
+    vcfs[v].xn = t.xn;
+    if (wn && b->nz_has[v]) { off_n[v] = words; words += rroc_cell_words(t.xn) + 1; }
+    if (wa) {
+      int64_t total = 0;
+      rc = atom_total(c, t, &total);   // (kept with the truth set since qm_batch_atomize met it: the slots of its set)
+      if (rc != QM_OK) return rc;
+      off_a[v] = words; words += (size_t)(atom_slots(total) / 2u);
+      off_e[v] = words; words += rroc_cell_words(t.xn) + 1;
+    }
+  }
+  hipStream_t st;
+  rc = pass_stream(b, stream, &b->ev_rroc, &st);
+  if (rc != QM_OK) return rc;
+  b->rr_made = 0;   // from here on the outputs are rewritten
+  const size_t rows = nv * 3 * nb, out_words = std::max<size_t>(2 * rows + 2 * nv, 1);
+  rc = b->rr_best.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->rr_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->rr_out.grow((int64_t)out_words, &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  for (size_t v = 0; v < nv; ++v) {
+    if (wn && b->nz_has[v]) vcfs[v].best_n = b->rr_best + off_n[v];
+    if (wa) { vcfs[v].best_atom = b->rr_best + off_a[v]; vcfs[v].best_entry = b->rr_best + off_e[v]; }
+  }
+  const bool T = b->timing;
+  if (T) for (auto& e : b->ev_rrt) if (!e) HIPCHK(hipEventCreate(&e));
+  b->rr_timed = false;
+  if (wn) HIPCHK(hipStreamWaitEvent(st, b->ev_norm, 0));   // the producers may have run on other streams
+  if (wa) HIPCHK(hipStreamWaitEvent(st, b->ev_atom, 0));
+  if (nv) HIPCHK(hipMemcpy(b->rr_vcfs, vcfs.data(), nv * sizeof(RrocVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
+  HIPCHK(hipMemsetAsync(b->rr_best, 0, std::max<size_t>(words, 1) * 4, st));
+  HIPCHK(hipMemsetAsync(b->rr_out, 0, out_words * 8, st));
+  const size_t np = (size_t)b->L.n_pad;
+  uint64_t* const base = b->rr_out + 2 * rows;
+  RrocRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.vcfs = b->rr_vcfs;
+  P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.qual = b->qual; P.flags = b->flags;
+  P.n_spans = (int32_t)b->L.spans.size(); P.n_bins = b->n_bins;
+  if (T) HIPCHK(hipEventRecord(b->ev_rrt[0], st));
+  if (wn) {
+    P.nrow = b->nz_cols + 3 * np; P.hist = b->rr_out;
+    launch_rroc_records(RROC_N, P, st);
+    HIPCHK(hipGetLastError());
+  }
+  if (T) HIPCHK(hipEventRecord(b->ev_rrt[1], st));
+  if (wn) {
+    launch_rroc_units(RROC_N, b->rr_vcfs, nullptr, (int)nv, b->rr_out, b->n_bins, base, b->nz_tru, NORM_T_COLS, QM_NORM_T_FORMS, st);
+    HIPCHK(hipGetLastError());
+  }
+  if (T) HIPCHK(hipEventRecord(b->ev_rrt[2], st));
+  if (wa) {
+    P.nrow = nullptr; P.avcfs = b->at_vcfs; P.hit_mask = b->at_hm; P.hist = b->rr_out + rows;
+    launch_rroc_records(RROC_A, P, st);
+    HIPCHK(hipGetLastError());
+  }
+  if (T) HIPCHK(hipEventRecord(b->ev_rrt[3], st));
+  if (wa) {
+    launch_rroc_units(RROC_A, b->rr_vcfs, b->at_vcfs, (int)nv, b->rr_out + rows, b->n_bins, base, b->at_tru, ATOM_T_COLS, QM_ATOM_T_ENTRIES, st);
+    HIPCHK(hipGetLastError());
+  }
+  if (T) { HIPCHK(hipEventRecord(b->ev_rrt[4], st)); b->rr_timed = true; }
+  HIPCHK(hipEventRecord(b->ev_rroc, st));
+  b->rr_made = which;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n, uint64_t* roc_a, uint64_t* base) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_rescue_roc: NULL batch");
+  if (!b->rr_made) return fail(QM_E_STATE, "qm_batch_get_rescue_roc: no qm_batch_rescue_roc behind the latest run of its producers");
+  if ((roc_n && !(b->rr_made & QM_RROC_NORM)) || (roc_a && !(b->rr_made & QM_RROC_ATOM)))
+    return fail(QM_E_STATE, "qm_batch_get_rescue_roc: the latest qm_batch_rescue_roc did not sweep by %s", roc_n && !(b->rr_made & QM_RROC_NORM) ? "normal form" : "atoms");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_rroc));
+  const size_t nv = (size_t)b->n_vcf, rows = nv * 3 * (size_t)b->n_bins;
+  if (roc_n && nv) HIPCHK(hipMemcpy(roc_n, b->rr_out, rows * 8, hipMemcpyDeviceToHost));
+  if (roc_a && nv) HIPCHK(hipMemcpy(roc_a, b->rr_out + rows, rows * 8, hipMemcpyDeviceToHost));
+  if (base && nv) HIPCHK(hipMemcpy(base, b->rr_out + 2 * rows, nv * 2 * 8, hipMemcpyDeviceToHost));   // (0 for a matching not swept)
+  return QM_OK;
+}
+extern "C" int qm_batch_rescue_roc_timings(qm_batch* b, float* ms4) {
+  if (!b || !ms4) return fail(QM_E_INVAL, "qm_batch_rescue_roc_timings: NULL");
+  if (!b->rr_made) return fail(QM_E_STATE, "qm_batch_rescue_roc_timings: no qm_batch_rescue_roc behind the latest run of its producers");
+  if (!b->rr_timed) return fail(QM_E_STATE, "qm_batch_rescue_roc_timings: timing is off");
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(b->ev_rrt[4]));
+  for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(ms4 + i, b->ev_rrt[i], b->ev_rrt[i + 1]));
   return QM_OK;
 }
 // ---- TP, FP and FN by variant type and size ----

@@ -300,7 +300,7 @@ struct Passes {
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
   const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr; const qm_haplotypes_args* hp = nullptr;
-  const qm_hapsub_args* hs = nullptr;
+  const qm_hapsub_args* hs = nullptr; const qm_rescue_roc_args* rr = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -836,6 +836,28 @@ int types_pass(const PassCtx& c, const qm_types_args* ty, std::string& err) {
   return QM_OK;
 }
 
+// The QUAL ROC under normal-form and atom matching: the two producer passes with their columns, run here as the
+// batch calls they are -- none of their rows or files is handed out --, then the sweep; the rows of every wanted mixed-sample job
+// (a pure-strain job has no truth set to be measured against: its rows stay zero)
+int rroc_pass(const PassCtx& c, const qm_rescue_roc_args* rr, int n_bins, std::string& err) {
+  if (!rr) return QM_OK;
+  auto want = [&](int j) { return rr->want[j] != 0 && !c.jobs[j].pure; };
+  if (!c.any(want)) return QM_OK;
+  std::vector<int32_t> gid(c.nv, -1);
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) gid[(size_t)c.J[(size_t)j].batch_v] = rr->genome_id[j];
+  const size_t w = 3 * (size_t)n_bins;
+  std::vector<uint64_t> rn(c.nv * w), ra(c.nv * w), base(c.nv * 2);
+  int rc = qm_batch_normalize(c.batch, gid.data(), QM_NORM_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_atomize(c.batch, QM_ATOM_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_rescue_roc(c.batch, QM_RROC_NORM | QM_RROC_ATOM, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_rescue_roc(c.batch, rn.data(), ra.data(), base.data());
+  if (rc != QM_OK) return c.lib(rc, err);
+  c.scatter_rows(rr->roc_n, rn, w, want);
+  c.scatter_rows(rr->roc_a, ra, w, want);
+  c.scatter_rows(rr->base, base, 2, want);
+  return QM_OK;
+}
+
 // ---- clusters of records matched by replayed haplotype ----
 struct HpColumns { std::vector<uint8_t> cls, ecls; std::vector<int32_t> site; };
 struct HpSites { std::vector<int32_t> first, lo, hi; };
@@ -1311,6 +1333,25 @@ extern "C" int qm_extract_files_hapsubsets(qm_ctx* ctx, int n_jobs, const qm_fil
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
+// the QUAL ROC under normal-form and atom matching behind the worker
+extern "C" int qm_extract_files_rescue_roc(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                           qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                           int n_slots, void* global_dev, const qm_rescue_roc_args* rescue_roc) {
+  const qm_rescue_roc_args* rr = rescue_roc;
+  if (!rr || (n_jobs > 0 && (!rr->genome_id || !rr->want || !rr->roc_n || !rr->roc_a || !rr->base)))
+    return fail(QM_E_INVAL, "qm_extract_files_rescue_roc: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_rescue_roc: the rescue passes it sweeps match indels and MNPs, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (n_bins < 1 || n_bins > 256) return fail(QM_E_INVAL, "qm_extract_files_rescue_roc: n_bins = " + std::to_string(n_bins) + " (1 to 256)");
+  if (n_jobs > 0) {
+    memset(rr->roc_n, 0, sizeof(uint64_t) * 3 * (size_t)n_bins * (size_t)n_jobs);
+    memset(rr->roc_a, 0, sizeof(uint64_t) * 3 * (size_t)n_bins * (size_t)n_jobs);
+    memset(rr->base, 0, sizeof(uint64_t) * 2 * (size_t)n_jobs);
+  }
+  Passes P; P.rr = rr;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
 // the bootstrap pass behind the worker
 extern "C" int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                      qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
@@ -1671,6 +1712,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = types_pass(pc, P.ty, err);
       if (rc == QM_OK) rc = haplo_pass(pc, P.hp, err);
       if (rc == QM_OK) rc = hapsub_pass(pc, P.hs, err);
+      if (rc == QM_OK) rc = rroc_pass(pc, P.rr, n_bins, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

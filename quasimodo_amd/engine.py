@@ -246,7 +246,7 @@ class Engine:
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
                       truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
-                      atomize=None, vartype=None, haplo=None, hapsub=None):
+                      atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -295,22 +295,27 @@ class Engine:
         haplo.T_COLS) and `hap_gap`; the sites files are written.
         hapsub: the dict of haplo plus "subsets": [path or None per job] -- qm_extract_files_hapsubsets, in place
         of haplo: the same rows and sites files, `hap_sub` ([8] uint64, columns haplo.SUB_COLS) and the subsets files.
+        rescue_roc: {"genomes": [genome_load id or None / -1 per job], "want": [0/1 per job]} -- qm_extract_files_rescue_roc
+        (alleles=True only), in place of normalize and atomize, which it runs itself: wanted mixed-sample rows gain
+        `rroc_n`, `rroc_a` ([3][n_bins] uint64: TP(t), FP(t), U(t) by normal form and by atoms, laid out like `roc`) and `rroc_base`
+        ([2]: the distinct forms and the entries of the truth set).
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_atomize, check_haplo, check_hapsub, check_normalize, check_shared_call, check_vartype
+        from .passes import check_atomize, check_haplo, check_hapsub, check_normalize, check_rescueroc, check_shared_call, check_vartype
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface, "rescueroc": rescue_roc}
         check_shared_call({name for name, spec in specs.items() if spec is not None})
         check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_atomize({name for name, spec in specs.items() if spec is not None}, alleles)
         check_vartype({name for name, spec in specs.items() if spec is not None}, alleles)
         check_haplo({name for name, spec in specs.items() if spec is not None}, alleles)
         check_hapsub({name for name, spec in specs.items() if spec is not None}, alleles)
+        check_rescueroc({name for name, spec in specs.items() if spec is not None}, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -326,7 +331,7 @@ class Engine:
         entry, extra, unpack = self._L.qm_extract_files_ex, (), lambda k: {}
         for name, spec in specs.items():
             if spec is not None and not (name == "motifs" and profile is not None):
-                entry, extra, unpack = getattr(self, "_files_" + name)(n, spec, gids=gids, alleles=alleles, file_jobs=file_jobs)
+                entry, extra, unpack = getattr(self, "_files_" + name)(n, spec, gids=gids, alleles=alleles, file_jobs=file_jobs, n_bins=int(n_bins))
         check(entry(*args, *extra), self._h)
         rows = []
         for k in range(n):
@@ -430,6 +435,22 @@ class Engine:
         aa.keep = (awant, out_arr)   # (read during the call; the other arrays live in unpack)
         unpack = lambda k: {"atom_rec": arec[k].copy(), "atom_tru": atru[k].copy()} if awant[k] else {}
         return self._L.qm_extract_files_atomize, (C.byref(aa),), unpack
+
+    def _files_rescue_roc(self, n, rescue_roc, file_jobs=(), n_bins=256, **kw):
+        rgid = _c([-1 if g is None else int(g) for g in rescue_roc["genomes"]] or [-1], np.int32)
+        rwant = _c([int(bool(w)) for w in rescue_roc["want"]] or [0], np.uint8)
+        if n and (rgid.shape[0] != n or rwant.shape[0] != n):
+            raise ValueError("rescue_roc: %d genomes / %d want entries for %d jobs" % (len(rescue_roc["genomes"]), len(rescue_roc["want"]), n))
+        rn = np.zeros((max(n, 1), 3, n_bins), np.uint64)
+        ra = np.zeros((max(n, 1), 3, n_bins), np.uint64)
+        base = np.zeros((max(n, 1), 2), np.uint64)
+        args = _lib.RescueRocArgs(_p(rgid), _p(rwant), _p(rn), _p(ra), _p(base))
+        args.keep = (rgid, rwant)   # (read during the call; the other arrays live in unpack)
+        took = lambda k: rwant[k] and not file_jobs[k].get("pure")
+        unpack = lambda k: {"rroc_n": rn[k].copy(), "rroc_a": ra[k].copy(), "rroc_base": base[k].copy()} if took(k) else {}
+        return self._L.qm_extract_files_rescue_roc, (C.byref(args),), unpack
+
+    _files_rescueroc = _files_rescue_roc   # (the pass's name in quasimodo_amd.passes)
 
     def _files_vartype(self, n, vartype, file_jobs=(), **kw):
         from .vartype import check_edges, n_rows
@@ -1077,6 +1098,30 @@ class Batch:
         ms = (C.c_float * 1)()
         self._ck(self._L.qm_batch_hapsubset_timings(self._h, ms))
         return {"hap_subsets_ms": ms[0]}
+
+    # -- the QUAL ROC under normal-form and atom matching ---------------
+    def rescue_roc(self, which=_lib.QM_RROC_NORM | _lib.QM_RROC_ATOM, stream=None, fetch=True):
+        """qm_batch_rescue_roc + qm_batch_get_rescue_roc behind a normalize(columns=True) (QM_RROC_NORM) and / or an
+        atomize(columns=True) (QM_RROC_ATOM): (roc_n, roc_a uint64 [n_vcf][3][n_bins] -- TP(t), FP(t), U(t) as roc() lays them
+        out; None for a matching not asked for --, base uint64 [n_vcf][2] -- the forms and the entries of every VCF's truth
+        set; FN_X(t) = base_X - U_X(t)).  fetch=False: enqueue only (rescue_roc_counts() waits and copies)"""
+        self._ck(self._L.qm_batch_rescue_roc(self._h, int(which), C.c_void_p(stream) if stream else None))
+        return self.rescue_roc_counts(which) if fetch else None
+
+    def rescue_roc_counts(self, which=_lib.QM_RROC_NORM | _lib.QM_RROC_ATOM):
+        """qm_batch_get_rescue_roc: the rows of the latest rescue_roc()"""
+        shape = (max(self.n_vcf, 1), 3, self.n_bins)
+        rn = np.zeros(shape, np.uint64) if which & _lib.QM_RROC_NORM else None
+        ra = np.zeros(shape, np.uint64) if which & _lib.QM_RROC_ATOM else None
+        base = np.zeros((max(self.n_vcf, 1), 2), np.uint64)
+        self._ck(self._L.qm_batch_get_rescue_roc(self._h, _p(rn) if rn is not None else None, _p(ra) if ra is not None else None, _p(base)))
+        return (rn[:self.n_vcf] if rn is not None else None), (ra[:self.n_vcf] if ra is not None else None), base[:self.n_vcf]
+
+    def rescue_roc_timings(self):
+        """qm_batch_rescue_roc_timings (set_timing on): milliseconds of the latest rescue_roc() between HIP events, kernel by kernel"""
+        ms = (C.c_float * 4)()
+        self._ck(self._L.qm_batch_rescue_roc_timings(self._h, ms))
+        return {"rroc_norm_records_ms": ms[0], "rroc_norm_units_ms": ms[1], "rroc_atom_records_ms": ms[2], "rroc_atom_units_ms": ms[3]}
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

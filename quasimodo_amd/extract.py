@@ -19,7 +19,7 @@ import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
-from .passes import PASSES, check_atomize, check_haplo, check_hapsub, check_normalize, check_shared_call, check_vartype, requested_by
+from .passes import PASSES, check_atomize, check_haplo, check_hapsub, check_normalize, check_rescueroc, check_shared_call, check_vartype, requested_by
 from .vcfio import scan_vcf
 
 
@@ -76,6 +76,8 @@ class Job:
     # MNPs matched against adjacent SNVs; mixed samples, allele-extended mode only
     atomize: bool = None      # True: stats gain atom_rec / atom_tru
     atoms_out: str = None     # where the job's multi-atom lines table goes (extract_many(atomize=) derives it)
+    # the QUAL ROC under normal-form and atom matching; mixed samples, allele-extended mode only
+    rescue_roc: str = None    # FASTA of the genome the VCF was called against, IN PLACE OF Job.normalize / Job.atomize: stats gain rroc_n / rroc_a / rroc_base
     # TP, FP and FN by variant type and size; mixed samples, allele-extended mode only
     vartype: tuple = None     # the size edges: stats gain type_rec / type_tru / type_edges (the same edges for every typed job of a call)
     # clusters of records matched by replayed haplotype; mixed samples, allele-extended mode only
@@ -155,7 +157,7 @@ def _group_indices(jobs, pure, field, max_members, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None):
+                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -213,6 +215,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     DESIGN.md 4.19; default: the jobs' Job.vartype; alleles=True only, ValueError otherwise): every mixed-sample job gets
     stats["type_rec"] ([5 n_bins + 4][2]: per type x size row, then NOKEY, NOVAR, LONGPAIR, NOSHAPE, the kept lines and the TP
     lines among them), stats["type_tru"] (the same rows: truth entries and the found ones) and stats["type_edges"].
+    rescue_roc: {"genomes": [FASTA path or None per job]} or that list itself (quasimodo_amd.rescueroc; default: the
+    jobs' Job.rescue_roc; alleles=True only, ValueError otherwise), in place of normalize and atomize, which the call runs itself:
+    every mixed-sample job with a genome gets stats["rroc_n"] and stats["rroc_a"] ([3][n_bins]: TP(t), FP(t), U(t) under QUAL >= t
+    by normal form and by atoms, beside stats["roc"] by spelling) and stats["rroc_base"] ([2]: the distinct forms and the entries
+    of its truth set; FN(t) = base - U(t)).  VCFs of one truth file name one genome.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     from .consensus import MAX_GROUP as VMAX
     from .truthside import MAX_GROUP
@@ -220,7 +227,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
              "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
              "atomize": atomize is not None and atomize is not False, "vartype": vartype is not None and vartype is not False,
-             "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub)}
+             "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub), "rescueroc": rescue_roc is not None}
     # the keywords onto the jobs ...
     if votes:
         if groups is None:
@@ -269,6 +276,12 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if j.normalize:
                 _paths(j)
                 j.rescued_out = j.rescued_out or rescued_path(j)
+    if rescue_roc is not None:
+        rgen = list(rescue_roc["genomes"] if isinstance(rescue_roc, dict) else rescue_roc)
+        if len(rgen) != len(jobs):
+            raise ValueError("rescue_roc: %d genomes entries for %d jobs" % (len(rgen), len(jobs)))
+        for j, g in zip(jobs, rgen):
+            j.rescue_roc = g if g and not is_pure_strain(j.vcf_file) else None
     if atomize is not None and atomize is not False:
         from .atomize import atoms_path
         awant = [True] * len(jobs) if atomize is True else [bool(w) for w in atomize]
@@ -343,6 +356,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     check_vartype(requested_by(jobs), alleles)
     check_haplo(requested_by(jobs), alleles)
     check_hapsub(requested_by(jobs), alleles)
+    check_rescueroc(requested_by(jobs), alleles)
     for j in jobs:
         if _hap_gap(j) is not None and not j.haplo_genome:
             raise ValueError("%s: Job.haplo without Job.haplo_genome (the FASTA the VCF was called against)" % j.vcf_file)
@@ -356,6 +370,11 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         if j.normalize and by_truth.setdefault(os.path.realpath(j.snp_file), (j.normalize, j.vcf_file))[0] != j.normalize:
             raise ValueError("normalize: %s and %s share the truth file %s and name the genomes %s and %s (a normalised truth set belongs to one genome)"
                              % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.normalize))
+    by_truth = {}
+    for j in jobs:
+        if j.rescue_roc and by_truth.setdefault(os.path.realpath(j.snp_file), (j.rescue_roc, j.vcf_file))[0] != j.rescue_roc:
+            raise ValueError("rescue_roc: %s and %s share the truth file %s and name the genomes %s and %s (a normalised truth set belongs to one genome)"
+                             % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.rescue_roc))
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -381,7 +400,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
     loaded = {}
     sid = None
-    ts = vt = nm = sf = cxs = nzs = ats = tys = hps = hss = None
+    ts = vt = nm = sf = cxs = nzs = ats = tys = hps = hss = rrs = None
     if any(j.vartype is not None and not p for j, p in zip(jobs, pure)):
         from .vartype import check_edges
         tys = {"edges": check_edges(next(j.vartype for j in jobs if j.vartype is not None)),
@@ -477,6 +496,12 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
                     hps = None
                     for path in [x for x in hss["subsets"] if x]:
                         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            if any(j.rescue_roc for j in jobs):
+                from .motifs import read_fasta
+                for j in jobs:
+                    if j.rescue_roc and j.rescue_roc not in loaded:
+                        loaded[j.rescue_roc] = engine.genome_load(read_fasta(j.rescue_roc))
+                rrs = {"genomes": [loaded[j.rescue_roc] if j.rescue_roc else -1 for j in jobs], "want": [1 if j.rescue_roc else 0 for j in jobs]}
             if any(j.atomize for j in jobs):
                 ats = {"want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]}
                 for path in [x for x in ats["atoms"] if x]:
@@ -496,7 +521,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             if par["boot"]:
                 bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats, vartype=tys, haplo=hps, hapsub=hss)
+                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats, vartype=tys, haplo=hps, hapsub=hss, rescue_roc=rrs)
             if vt is not None:
                 for r, j in zip(rows, jobs):
                     if j.vote_group is not None:

@@ -20,6 +20,8 @@ PASSES = (
     Pass("haplo", ("haplo",), ("haplo",), "--haplotypes", "haplo: the jobs of one call share one gap", ()),
     # the haplotype pass AND the subset search behind it, from one call: asked for in place of haplo, never beside it
     Pass("hapsub", ("hapsub",), ("hapsub",), "--hap-subsets", "hapsub: the jobs of one call share one gap", ()),
+    # the QUAL sweep of normalize AND atomize, which it runs itself: asked for in place of them, never beside them
+    Pass("rescueroc", ("rescue_roc",), ("rescue_roc",), "--rescue-roc", None, ()),
     Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
     Pass("vartype", ("vartype",), ("vartype",), "--by-type", "vartype: the typed jobs of one call share one list of size edges", ()),
     Pass("context", ("context",), ("context",), "--seq-context",
@@ -61,6 +63,12 @@ def check_atomize(requested, alleles):
     """--atomize splits MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
     if "atomize" in requested and not alleles:
         raise ValueError("atomize (--atomize) needs the allele-extended mode (--alleles): a single-base batch holds no MNPs")
+
+
+def check_rescueroc(requested, alleles):
+    """--rescue-roc sweeps the two rescue passes, which only the allele-extended mode has: ValueError before a file is touched"""
+    if "rescueroc" in requested and not alleles:
+        raise ValueError("rescueroc (--rescue-roc) needs the allele-extended mode (--alleles): a single-base batch has no rescue passes to sweep")
 
 
 def check_haplo(requested, alleles):

@@ -206,3 +206,36 @@ def write_weighted_roc(path, roc, truth_unique):
     else:
         with open(path, "wb") as fh:
             fh.write(data)
+
+
+RESCUE_ROC_MATCHINGS = {"spelling": ("exact-match", "distinct allele-extended truth entries"),
+                        "normalized": ("normal-form", "distinct normal forms of the truth entries"),
+                        "atomized": ("atom", "allele-extended truth entries")}
+
+
+def write_rescue_roc(path, roc, baseline, matching):
+    """One ROC of the rescue sweep in the eight columns of write_weighted_roc; the #Version line names the
+    matching (a key of RESCUE_ROC_MATCHINGS) and the unit the baseline counts.  The same deterministic gzip: equal numbers
+    give equal bytes."""
+    import gzip
+    how, unit = RESCUE_ROC_MATCHINGS[matching]
+    baseline = int(baseline)
+    lines = ["#Version qmvt %s ROC (not rtg vcfeval), baseline = %s" % (how, unit),
+             "#total baseline variants: %d" % baseline,
+             "#score field: QUAL",
+             "#score\ttrue_positives_baseline\tfalse_positives\ttrue_positives_call\tfalse_negatives\tprecision\tsensitivity\tf_measure"]
+    for t in range(roc.shape[1] - 1, -1, -1):
+        tp_call, fp, tp_base = int(roc[0, t]), int(roc[1, t]), int(roc[2, t])
+        if tp_call + fp == 0:
+            continue
+        prec = tp_call / (tp_call + fp)
+        sens = tp_base / baseline if baseline else 0.0
+        f1 = 2 * prec * sens / (prec + sens) if prec + sens > 0 else 0.0
+        lines.append("%d\t%d\t%d\t%d\t%d\t%.4f\t%.4f\t%.4f" % (t, tp_base, fp, tp_call, baseline - tp_base, prec, sens, f1))
+    data = ("\n".join(lines) + "\n").encode()
+    if str(path).endswith(".gz"):
+        with open(path, "wb") as raw, gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0) as fh:
+            fh.write(data)
+    else:
+        with open(path, "wb") as fh:
+            fh.write(data)

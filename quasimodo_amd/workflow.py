@@ -166,7 +166,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
                          context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None, haplotypes=None,
-                         hap_gap=None, hap_subsets=False):
+                         hap_gap=None, hap_subsets=False, rescue_roc=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -220,13 +220,20 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     entries of every small region are replayed onto the genome and rescued where the two sequences are equal;
     final_tables/caller_performance_haplotype.tsv (TP, FP, FN, Precision, Recall, F1 by spelling and by haplotype side by side, then
     the class counts) and callers/{caller}/hap/{sample}.{ref}.{caller}.sites.tsv for every mixed sample.
+    rescue_roc: {"TM": FASTA, "TA": FASTA}, the genomes as for normalize (quasimodo_amd.rescueroc; needs alleles,
+    WorkflowError before a file is touched otherwise), in place of normalize and atomize, which the run's call makes itself: the
+    QUAL ROC by spelling, by normal form and by atoms side by side, snp/qmvt_roc/{caller}/{sample}.{ref}.rescue/spelling_roc.tsv.gz,
+    normalized_roc.tsv.gz and atomized_roc.tsv.gz for every mixed sample, and final_tables/caller_roc_rescue.tsv (TP, FP, FN,
+    Precision, Recall, F1 at QUAL >= 20 and at the threshold of the largest F1, per caller, mixture and matching, then pooled).
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
                  context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False,
-                 haplo=haplotypes is not None and not hap_subsets, hapsub=bool(hap_subsets))
+                 haplo=haplotypes is not None and not hap_subsets, hapsub=bool(hap_subsets), rescueroc=rescue_roc is not None)
+    if rescue_roc is not None and not alleles:
+        raise WorkflowError("--rescue-roc needs --alleles: it sweeps the matching by normal form and by atoms, which only the allele-extended mode has")
     if hap_subsets and haplotypes is None:
         raise WorkflowError("--hap-subsets searches the sites of the haplotype pass: it needs --haplotypes (and the genomes)")
     hgap = None
@@ -303,6 +310,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             fa = normalize.get(mix)
             if not fa or not os.path.isfile(fa):
                 raise WorkflowError("normalize: no genome FASTA for %s (%s)" % (mix, fa))
+    if rescue_roc is not None:
+        for mix in mixes:
+            fa = rescue_roc.get(mix)
+            if not fa or not os.path.isfile(fa):
+                raise WorkflowError("rescue ROC: no genome FASTA for %s (%s)" % (mix, fa))
     if haplotypes is not None:
         for mix in mixes:
             fa = haplotypes.get(mix)
@@ -319,6 +331,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("caller_performance_normalized.tsv\t%s" % ",".join(callers))
         if atomize:
             print("caller_performance_atomized.tsv\t%s" % ",".join(callers))
+        if rescue_roc is not None:
+            for s, c, src in plan:
+                if not s.endswith(("-1-0", "-0-1")):
+                    print("rescue_roc\t%s\t%s" % (c, s))
+            print("caller_roc_rescue.tsv\t%s" % ",".join(callers))
         if tedges is not None:
             print("caller_performance_types.tsv\t%s\t%s" % (",".join(callers), ",".join(str(e) for e in tedges)))
         if mutation_context is not None:
@@ -395,6 +412,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             jobs[-1].atoms_out = os.path.join(d, "atoms", os.path.basename(src)[:-4] + ".atoms.tsv")
         if tedges is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].vartype = tedges
+        if rescue_roc is not None and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].rescue_roc = rescue_roc[s[:2]]
         if haplotypes is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].haplo_genome = haplotypes[s[:2]]
             jobs[-1].haplo, jobs[-1].hapsub = (None, hgap) if hap_subsets else (hgap, None)
@@ -474,6 +493,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if atomize:
             from .atomize import write_performance_atomized
             write_performance_atomized(os.path.join(tables, "caller_performance_atomized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
+        if rescue_roc is not None:
+            _write_rescue_rocs(meta, jobs, snp_dir, tables)
         if tedges is not None:
             from .vartype import write_performance_types
             write_performance_types(os.path.join(tables, "caller_performance_types.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)], tedges)
@@ -764,6 +785,33 @@ def _write_snp_rocs(meta, jobs, snp_dir):
             d = os.path.join(snp_dir, "qmvt_roc", c, "%s.%s.xsnp" % (smp, SAMPLE_REF[smp]))
             os.makedirs(d, exist_ok=True)
             write_weighted_roc(os.path.join(d, "exact_roc.tsv.gz"), j.stats["roc"], j.stats["truth_unique"])
+
+
+def write_job_rescue_rocs(d, stats):
+    """spelling_roc.tsv.gz (the batch's own ROC, for the side by side), normalized_roc.tsv.gz and atomized_roc.tsv.gz of one job
+    under d, in the layout of exact_roc.tsv.gz; returns {matching: (roc, baseline)}, None for a job without the
+    rows (a pure-strain sample)"""
+    import numpy as np
+    from .tables import write_rescue_roc
+    if stats.get("pure_strain") or "rroc_n" not in stats:
+        return None
+    rocs = {"spelling": (stats["roc"], int(stats["truth_unique"])), "normalized": (stats["rroc_n"], int(stats["rroc_base"][0])),
+            "atomized": (stats["rroc_a"], int(stats["rroc_base"][1]))}
+    os.makedirs(d, exist_ok=True)
+    for m, (roc, base) in rocs.items():
+        write_rescue_roc(os.path.join(d, "%s_roc.tsv.gz" % m), np.asarray(roc), base, m)
+    return rocs
+
+
+def _write_rescue_rocs(meta, jobs, snp_dir, tables):
+    """the three ROC files of every mixed sample under snp/qmvt_roc/{caller}/{sample}.{ref}.rescue/ -- a directory of their own
+    beside the exact-match ROC's -- and final_tables/caller_roc_rescue.tsv"""
+    from .rescueroc import write_caller_roc_rescue
+    rows = []
+    for (c, smp), j in zip(meta, jobs):
+        rocs = write_job_rescue_rocs(os.path.join(snp_dir, "qmvt_roc", c, "%s.%s.rescue" % (smp, SAMPLE_REF[smp])), j.stats)
+        rows.append((c, smp, {"rroc": rocs} if rocs else {}))
+    write_caller_roc_rescue(os.path.join(tables, "caller_roc_rescue.tsv"), rows)
 
 
 def indel_roc(engine, items, snp_dir, n_bins=256):

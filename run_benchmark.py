@@ -154,6 +154,10 @@ def _type_bins(by_type, type_bins):
 @click.option("--atomize", "atomize", is_flag=True, default=False,
               help="With --alleles: also match MNPs against adjacent SNVs, atom by atom (every equal-length substitution split into its "
                    "single-base differences, on both sides): write final_tables/caller_performance_atomized.tsv and callers/*/atoms/*.atoms.tsv.")
+@click.option("--rescue-roc", "rescue_roc", is_flag=True, default=False,
+              help="With --alleles, in place of --normalize and --atomize: sweep the QUAL threshold under the matching by normal form and by atoms "
+                   "(precision and recall at every QUAL >= t, as by spelling): write snp/qmvt_roc/*/*.rescue/{spelling,normalized,atomized}_roc.tsv.gz and "
+                   "final_tables/caller_roc_rescue.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config).")
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="With --alleles: also count TP, FP and FN by variant type (SNV, MNP, INS, DEL, complex) and size: write "
                    "final_tables/caller_performance_types.tsv.")
@@ -176,7 +180,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False):
+         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False):
     haplotypes = haplotypes or hap_subsets   # the search runs behind the haplotype pass of the same call
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
@@ -192,7 +196,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
     genomes = None
-    if mutation_context or seq_context or normalize or haplotypes:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+    if mutation_context or seq_context or normalize or haplotypes or rescue_roc:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
         pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
@@ -210,7 +214,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
                                              alleles=alleles, normalize=genomes if normalize else None, atomize=atomize,
                                              by_type=_type_bins(by_type, type_bins), haplotypes=genomes if haplotypes else None,
-                                             hap_gap=_hap_gap(haplotypes, hap_gap), hap_subsets=hap_subsets)
+                                             hap_gap=_hap_gap(haplotypes, hap_gap), hap_subsets=hap_subsets,
+                                             rescue_roc=genomes if rescue_roc else None)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -264,6 +269,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode to normalise (hcmv has it).")
 @click.option("--atomize", "atomize", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose MNPs could be split (hcmv has it).")
+@click.option("--rescue-roc", "rescue_roc", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose rescue passes could be swept (hcmv has it).")
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose variants could be typed (hcmv has it).")
 @click.option("--type-bins", "type_bins", default=None, help="Not available here (see --by-type).")
@@ -275,9 +282,12 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
             surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False,
-            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False):
+            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False):
     from quasimodo_amd import workflow
     try:
+        if rescue_roc:
+            raise workflow.WorkflowError("--rescue-roc needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --rescue-roc)")
         if hap_subsets:
             raise workflow.WorkflowError("--hap-subsets needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --haplotypes --hap-subsets)")
