@@ -648,6 +648,33 @@ static void build_layout(const int64_t* n_records, const int32_t* truth_ids, int
 // the paths of a VCF found out of order (route())
 enum class Path : uint8_t { Radix, OneLevel, TwoLevel, Partitions, Wide };
 
+// ---- the passes over a finished batch (include/qmvt.h at qm_batch_run) ----
+enum PassId { P_MOTIFS, P_AFP, P_TRUTH, P_STRATA, P_BOOT, P_VOTES, P_NEARMISS, P_SURFACE, P_CONTEXT, P_NORM, P_ATOM, P_TYPES, P_HAPLO,
+              P_HAPSUB, P_RROC, N_PASSES };
+constexpr int PASS_MAX_MARKS = 6;   // qm_batch_haplotypes'
+// What a batch keeps of every pass, qm_batch::pass[id].  Both kinds of event are created at first use: a batch that never ran a
+// pass holds none, and whatever walks the passes (wait_passes, the reset in qm_batch_run, batch_free) makes no HIP call for it.
+struct PassState {
+  hipEvent_t done = nullptr;              // behind the last kernel of the latest call, on whatever stream it was enqueued (no timing)
+  hipEvent_t mark[PASS_MAX_MARKS] = {};   // qm_batch_set_timing: around its kernels (pass_marks, pass_mark)
+  bool timed = false;                     // the latest call recorded them
+  unsigned made = 0;                      // what the latest call made behind the latest run (1, or the pass's own bits); 0: nothing
+};
+// One row per pass, indexed by PassId: the entry point that enqueues it (as the getters' refusals name it), its timing marks
+// (0: the pass has no qm_batch_*_timings) and whether it reads the hit bitmaps and the record mask qm_batch_truth_hits writes.
+// A new pass adds its PassId and its row HERE, and nothing else: the members of qm_batch, batch_free, the reset in qm_batch_run
+// and the wait list of everything that rewrites what passes read (wait_passes) all follow from the table.
+struct PassInfo { const char* name; int marks; bool reads_hits; };
+static const PassInfo PASSES[N_PASSES] = {
+    {"qm_batch_motifs", 0, false},     {"qm_batch_af_profile", 0, false}, {"qm_batch_truth_hits", 0, false},
+    {"qm_batch_strata", 0, true},      {"qm_batch_boot", 0, true},        {"qm_batch_votes", 5, true},
+    {"qm_batch_nearmiss", 3, true},    {"qm_batch_surface", 4, false},    {"qm_batch_context", 4, true},
+    {"qm_batch_normalize", 4, false},  {"qm_batch_atomize", 4, false},    {"qm_batch_types", 3, false},
+    {"qm_batch_haplotypes", 6, false}, {"qm_batch_hapsubsets", 2, false}, {"qm_batch_rescue_roc", 5, false},
+};
+// (P_HAPLO: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
+// flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
+
 struct qm_batch {
   qm_ctx* ctx = nullptr;
   int n_vcf = 0, n_bins = 256;
@@ -738,7 +765,7 @@ struct qm_batch {
   static constexpr int EV_RING = 32;   // per-kernel events of the latest runs
   static constexpr int EV_PER_RUN = 2 + 5;   // [0] start [1] end, classify start / end, finalize end, compact start / end
   hipEvent_t ev[EV_RING][EV_PER_RUN] = {};
-  int64_t n_timed = 0;
+  int64_t timed_runs = 0;
   bool ran = false, finished = false;
   bool ext = false;   // allele-extended: any valid allele code takes part (build-defined widening, config 5)
   uint64_t* last_global = nullptr;
@@ -768,13 +795,14 @@ struct qm_batch {
   bool known_dirty = false;           // the device copy is stale
   DevBuf<uint8_t> d_known;
   bool run_used_known = false;        // the run in flight was launched with d_known
+  // The passes over the finished batch: the events, timing marks and "made behind the latest run" word of each (PassState).  What
+  // follows, pass by pass, is the data of the pass alone.
+  PassState pass[N_PASSES];
   // qm_batch_motifs (lazy: a batch that never asks allocates nothing): the [n_vcf][3][QM_MOTIF_COLS] counts, the per-VCF genome
-  // descriptors (page-locked: copied on the call's stream; ev_motif says when the copy and the pass are done)
+  // descriptors (page-locked: copied on the call's stream; the pass's event says when the copy and the pass are done)
   DevBuf<uint64_t> d_motifs;
   DevBuf<GenomeRef> d_mgen;
   GenomeRef* h_mgen = nullptr;
-  hipEvent_t ev_motif = nullptr;
-  bool motifs_valid = false;          // qm_batch_motifs was called behind the latest run
   // qm_batch_upload_af / qm_batch_af_profile (lazy, DESIGN.md 4.9: a batch that never uploads frequencies allocates nothing): the
   // af column laid out like pos, the per-VCF "has af" marks (host: set by qm_batch_upload_af, cleared by every writer of the
   // VCF's columns; device: the copy the latest pass read), the [n_vcf][2][n_af][n_pos] grids and [n_vcf][2][QM_AFP_EXTRA] extras
@@ -783,126 +811,88 @@ struct qm_batch {
   std::mutex af_mu;                   // the first qm_batch_upload_af allocates the column
   DevBuf<uint8_t> d_afmark;
   DevBuf<uint64_t> d_afgrid, d_afextra;
-  hipEvent_t ev_afp = nullptr;
   int32_t afp_cells = 0;              // n_af * n_pos of the latest qm_batch_af_profile
-  bool afp_valid = false;             // qm_batch_af_profile was called behind the latest run
   // qm_batch_truth_hits (lazy): the per-VCF hit bitmaps one behind the other (h_hit_off[v] = first word of VCF v,
-  // h_hit_off[n_vcf] = all), the record mask (the size of mask_pass), the lookup counter; ev_truth says when the pass is done
+  // h_hit_off[n_vcf] = all), the record mask (the size of mask_pass), the lookup counter
   DevBuf<uint32_t> d_hits;
   DevBuf<uint64_t> d_intruth;
   DevBuf<int64_t> d_hit_off;
   std::vector<int64_t> h_hit_off, h_hit_tn;   // h_hit_tn[v]: T' of VCF v's truth set when the bitmaps were sized
   bool hit_off_uploaded = false, intruth_cleared = false, hits_enqueued = false;
-  hipEvent_t ev_truth = nullptr;
-  bool hits_valid = false;            // qm_batch_truth_hits was called behind the latest run
   // qm_batch_strata (lazy): [n_vcf][S + 2][2] kept / TP lines, [n_vcf][S + 1][2] truth keys / hit ones, the bit
-  // planes of every distinct truth set one behind the other, the per-VCF rows of k_strata_truth; ev_strata says when the pass is done
+  // planes of every distinct truth set one behind the other, the per-VCF rows of k_strata_truth
   DevBuf<uint64_t> d_srec, d_stru;
   DevBuf<uint32_t> d_splanes;
   DevBuf<StrataTruthRow> d_srows;
-  hipEvent_t ev_strata = nullptr;
   int32_t strata_S = 0;               // strata of the latest qm_batch_strata
-  unsigned strata_made = 0;           // QM_STRATA_* halves the latest qm_batch_strata made behind the latest run
   // qm_batch_boot (lazy): [n_vcf][n_win + 2][4] counts, [n_vcf][n_rep][4] replicates, the per-VCF rows of
-  // k_boot_truth; ev_boot says when the pass is done
+  // k_boot_truth
   DevBuf<uint64_t> d_bcnt, d_brep;
   DevBuf<BootTruthRow> d_brows;
-  hipEvent_t ev_boot = nullptr;
   int32_t boot_nwin = 0, boot_nrep = 0;   // of the latest qm_batch_boot
-  unsigned boot_made = 0;             // QM_BOOT_* sides the latest qm_batch_boot made behind the latest run
   // qm_batch_votes (lazy): the (key, member) pair buffers of the radix sort (the second pair holds the distinct keys
   // and their masks afterwards), its histograms and tables, the per-group descriptors, cursors, counts and the five output
-  // tables one behind the other; ev_votes says when the pass is done
+  // tables one behind the other
   DevBuf<uint32_t> vt_k[2], vt_v[2], vt_hist, vt_thd, vt_cursor;   // vt_cursor: [n_groups] pairs written, then [n_groups] distinct keys
   DevBuf<SortSeg> vt_segs;
   DevBuf<int32_t> vt_tile_seg, vt_slot;
   DevBuf<VoteGroup> vt_groups;
   DevBuf<uint64_t> vt_out;
   std::vector<int64_t> vt_koff;       // first pair of every group of the latest qm_batch_votes
-  hipEvent_t ev_votes = nullptr;
-  hipEvent_t ev_vt[5] = {};           // qm_batch_set_timing: around k_vote_truth, k_vote_keys + k_vote_segs, the sort, the run kernels
-  bool vt_timed = false;              // the latest qm_batch_votes recorded them
   int32_t votes_groups = 0;
-  bool votes_valid = false;           // qm_batch_votes was called behind the latest run
   // qm_batch_nearmiss (lazy): the four bit planes, each laid out like d_hits (plane p of VCF v starts at word
   // p * h_hit_off[n_vcf] + h_hit_off[v]), one class byte per record laid out like pos, the [n_vcf][6] and [n_vcf][5] counts one
-  // behind the other, the T' of every VCF for k_nearmiss_truth; ev_nm says when the pass is done
+  // behind the other, the T' of every VCF for k_nearmiss_truth
   DevBuf<uint32_t> nm_planes;
   DevBuf<uint8_t> nm_rcls;
   DevBuf<uint64_t> nm_out;
   DevBuf<int64_t> nm_tn;
   bool nm_tn_uploaded = false;
-  hipEvent_t ev_nm = nullptr;
-  hipEvent_t ev_nmt[3] = {};          // qm_batch_set_timing: around k_nearmiss_records and k_nearmiss_truth
-  bool nm_timed = false;              // the latest qm_batch_nearmiss recorded them
-  bool nm_valid = false;              // qm_batch_nearmiss was called behind the latest run
   // qm_batch_surface (lazy): one u32 per (VCF, truth key) -- the best cell code of the key's records; row v starts
   // at h_sf_off[v] --, the [n_vcf][3][nq * na] grids (suffix sums once k_surface_sums ran) and [n_vcf][QM_SF_EXTRA] extras one
-  // behind the other, the pass's own copy of the "has af" marks; ev_sf says when the pass is done
+  // behind the other, the pass's own copy of the "has af" marks
   DevBuf<uint32_t> sf_best;
   DevBuf<int64_t> sf_off;
   DevBuf<uint64_t> sf_out;
   DevBuf<uint8_t> sf_mark;
   std::vector<int64_t> h_sf_off;      // [n_vcf + 1], from the truth sets' T' at the first call
   bool sf_off_uploaded = false;
-  hipEvent_t ev_sf = nullptr;
-  hipEvent_t ev_sft[4] = {};          // qm_batch_set_timing: around the three kernels
-  bool sf_timed = false;              // the latest qm_batch_surface recorded them
   int32_t sf_cells = 0;               // nq * na of the latest qm_batch_surface
-  bool sf_valid = false;              // qm_batch_surface was called behind the latest run
   // qm_batch_context (lazy): [n_vcf][16 ng + 2][2] kept / TP lines, [n_vcf][16 ng + 1][2] truth keys / hit ones,
   // [n_vcf][16 ng + 1] positions per cell (copies of the genomes' counts as the pass saw them), the per-VCF tables and the rows
-  // of k_context_truth; ev_cx says when the pass is done
+  // of k_context_truth
   DevBuf<uint64_t> cx_rec, cx_tru, cx_gen;
   DevBuf<ContextTab> cx_tabs;
   DevBuf<ContextTruthRow> cx_rows;
-  hipEvent_t ev_cx = nullptr;
-  hipEvent_t ev_cxt[4] = {};          // qm_batch_set_timing: around the table builds, k_context_records, k_context_truth
-  bool cx_timed = false;              // the latest qm_batch_context recorded them
   bool cx_built = false;              // ... and built a table (else its build time is 0)
   int32_t cx_ng = 0;                  // GC bins of the latest qm_batch_context
-  unsigned cx_made = 0;               // QM_CX_* halves the latest qm_batch_context made behind the latest run
   // qm_batch_normalize (lazy): the tables of the (truth set, genome) pairs the VCFs name in one pool, the per-VCF
   // descriptors and bitmaps, [n_vcf][QM_NORM_R_COLS] / [n_vcf][QM_NORM_T_COLS] counts, a class byte per record and, on request,
-  // the normalised columns with the truth row of every record's form; ev_norm says when the pass is done
+  // the normalised columns with the truth row of every record's form
   DevBuf<uint32_t> nz_pool, nz_bits;
   DevBuf<NormVcf> nz_vcfs;
   DevBuf<uint64_t> nz_rec, nz_tru;
   DevBuf<uint8_t> nz_cls;
   DevBuf<int32_t> nz_cols;            // [4][n_pad]: pos, ref, alt, row
-  hipEvent_t ev_norm = nullptr;
-  hipEvent_t ev_nzt[4] = {};          // qm_batch_set_timing: around the table builds, k_norm_records, k_norm_found
-  bool nz_timed = false;              // the latest qm_batch_normalize recorded them
-  unsigned nz_made = 0;               // 1 | QM_NORM_COLUMNS: what the latest qm_batch_normalize made behind the latest run
   std::vector<uint8_t> nz_has;        // [n_vcf] the VCF named a genome
   // qm_batch_atomize (lazy): the atom sets of the batch's truth sets in one pool, the per-VCF descriptors and
   // bitmaps, [n_vcf][QM_ATOM_R_COLS] / [n_vcf][QM_ATOM_T_COLS] counts and, on request, a class byte, an atom count and a hit mask
-  // per record; ev_atom says when the pass is done
+  // per record
   DevBuf<uint32_t> at_pool, at_bits;
   DevBuf<AtomVcf> at_vcfs;
   DevBuf<uint64_t> at_rec, at_tru;
   DevBuf<uint8_t> at_cls;             // [2][n_pad]: class bytes, atom counts
   DevBuf<uint16_t> at_hm;             // [n_pad]
-  hipEvent_t ev_atom = nullptr;
-  hipEvent_t ev_att[4] = {};          // qm_batch_set_timing: around the set builds, k_atom_records, k_atom_found
-  bool at_timed = false;              // the latest qm_batch_atomize recorded them
-  unsigned at_made = 0;               // 1 | QM_ATOM_COLUMNS: what the latest qm_batch_atomize made behind the latest run
   // qm_batch_types (lazy): the per-VCF descriptors and the pass's own found bitmaps, [n_vcf][n_rows][2] counts of
-  // records and of truth entries, the shape table ([3][n]: len, head, tail) and, on request, a row byte per record; ev_types
-  // says when the pass is done
+  // records and of truth entries, the shape table ([3][n]: len, head, tail) and, on request, a row byte per record
   DevBuf<uint32_t> ty_bits, ty_shapes;
   DevBuf<TypeVcf> ty_vcfs;
   DevBuf<uint64_t> ty_rec, ty_tru;
   DevBuf<uint8_t> ty_row;             // [n_pad]
-  hipEvent_t ev_types = nullptr;
-  hipEvent_t ev_tyt[3] = {};          // qm_batch_set_timing: around k_type_records and k_type_truth
-  bool ty_timed = false;              // the latest qm_batch_types recorded them
   int32_t ty_rows = 0;                // n_rows of the latest qm_batch_types
-  unsigned ty_made = 0;               // 1 | QM_TYPE_COLUMNS: what the latest qm_batch_types made behind the latest run
   // qm_batch_haplotypes (lazy): the site tables of the (truth set, genome) pairs the VCFs name in one pool, the
   // per-VCF descriptors and bitmaps, [n_vcf][QM_HAP_R_COLS] / [n_vcf][QM_HAP_T_COLS] counts, a class byte and a site index per
-  // record, the open lines of every (VCF, open site) pair and, on request, a class byte per (VCF, truth entry); ev_haplo says
-  // when the pass is done
+  // record, the open lines of every (VCF, open site) pair and, on request, a class byte per (VCF, truth entry)
   DevBuf<uint32_t> hp_pool, hp_bits;
   DevBuf<HapVcf> hp_vcfs;
   DevBuf<uint64_t> hp_rec, hp_tru;
@@ -910,35 +900,23 @@ struct qm_batch {
   DevBuf<uint8_t> hp_cls, hp_ecls;    // [n_pad]; the entries of every VCF's truth set, VCF after VCF
   DevBuf<int32_t> hp_site;            // [n_pad]
   DevBuf<int32_t> hp_pairs;           // [pairs][QM_HAP_MAX_ITEMS + 3]
-  hipEvent_t ev_haplo = nullptr;
-  hipEvent_t ev_hpt[6] = {};          // qm_batch_set_timing: around the site builds, k_hap_records, k_hap_truth, k_hap_claim, k_hap_replay
-  bool hp_timed = false;              // the latest qm_batch_haplotypes recorded them
-  unsigned hp_made = 0;               // 1 | QM_HAP_COLUMNS: what the latest qm_batch_haplotypes made behind the latest run
   std::vector<uint8_t> hp_has;        // [n_vcf] the VCF named a genome
   std::vector<int64_t> hp_eoff;       // [n_vcf + 1] the VCF's entries in hp_ecls
   std::vector<int32_t> hp_gids;       // [n_vcf] the genome ids of the latest qm_batch_haplotypes
   int64_t hp_npairs = 0;              // the (VCF, open site) pairs it read back
   // qm_batch_hapsubsets (lazy): [n_vcf][QM_HAPSUB_COLS] counts, a word per pair (searched or not, the two masks)
-  // and, on request, second class bytes per record and per (VCF, truth entry); ev_hapsub says when the search is done
+  // and, on request, second class bytes per record and per (VCF, truth entry)
   DevBuf<uint64_t> hs_sub;
   DevBuf<uint32_t> hs_res;
   DevBuf<uint8_t> hs_cls, hs_ecls;
-  hipEvent_t ev_hapsub = nullptr;
-  hipEvent_t ev_hst[2] = {};          // qm_batch_set_timing: around the search
-  bool hs_timed = false;
-  unsigned hs_made = 0;               // 1 | what: what the latest qm_batch_hapsubsets made behind the latest qm_batch_haplotypes
   bool hs_listed = false;             // hs_list holds the PARTIAL pairs of the latest search
   std::vector<int32_t> hs_list;       // (VCF, site, S mask, T mask) per PARTIAL pair, VCF after VCF, sites ascending
   // qm_batch_rescue_roc (lazy): the 16-bit best cells of every VCF's units in one pool (by normal form: a cell per
   // truth entry; by atoms: a cell per slot of the atom set and per entry), the per-VCF descriptors, [2][n_vcf][3][n_bins] rows
-  // (suffix sums once k_rroc_units ran) and [n_vcf][2] baselines one behind the other; ev_rroc says when the sweep is done
+  // (suffix sums once k_rroc_units ran) and [n_vcf][2] baselines one behind the other
   DevBuf<uint32_t> rr_best;
   DevBuf<RrocVcf> rr_vcfs;
   DevBuf<uint64_t> rr_out;
-  hipEvent_t ev_rroc = nullptr;
-  hipEvent_t ev_rrt[5] = {};          // qm_batch_set_timing: around the two kernels of either matching
-  bool rr_timed = false;
-  unsigned rr_made = 0;               // QM_RROC_*: what the latest qm_batch_rescue_roc made behind the latest run of its producers
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -959,31 +937,10 @@ static void batch_free(qm_batch* b) {
   if (b->sub) { batch_free(b->sub); b->sub = nullptr; }
   if (b->h_summary) (void)hipHostFree(b->h_summary);
   if (b->h_mgen) (void)hipHostFree(b->h_mgen);
-  if (b->ev_motif) (void)hipEventDestroy(b->ev_motif);
-  if (b->ev_truth) (void)hipEventDestroy(b->ev_truth);
-  if (b->ev_afp) (void)hipEventDestroy(b->ev_afp);
-  if (b->ev_strata) (void)hipEventDestroy(b->ev_strata);
-  if (b->ev_boot) (void)hipEventDestroy(b->ev_boot);
-  if (b->ev_votes) (void)hipEventDestroy(b->ev_votes);
-  if (b->ev_nm) (void)hipEventDestroy(b->ev_nm);
-  for (auto& e : b->ev_nmt) if (e) (void)hipEventDestroy(e);
-  if (b->ev_sf) (void)hipEventDestroy(b->ev_sf);
-  for (auto& e : b->ev_sft) if (e) (void)hipEventDestroy(e);
-  if (b->ev_cx) (void)hipEventDestroy(b->ev_cx);
-  for (auto& e : b->ev_cxt) if (e) (void)hipEventDestroy(e);
-  if (b->ev_norm) (void)hipEventDestroy(b->ev_norm);
-  for (auto& e : b->ev_nzt) if (e) (void)hipEventDestroy(e);
-  if (b->ev_atom) (void)hipEventDestroy(b->ev_atom);
-  for (auto& e : b->ev_att) if (e) (void)hipEventDestroy(e);
-  if (b->ev_types) (void)hipEventDestroy(b->ev_types);
-  for (auto& e : b->ev_tyt) if (e) (void)hipEventDestroy(e);
-  if (b->ev_haplo) (void)hipEventDestroy(b->ev_haplo);
-  for (auto& e : b->ev_hpt) if (e) (void)hipEventDestroy(e);
-  if (b->ev_hapsub) (void)hipEventDestroy(b->ev_hapsub);
-  for (auto& e : b->ev_hst) if (e) (void)hipEventDestroy(e);
-  if (b->ev_rroc) (void)hipEventDestroy(b->ev_rroc);
-  for (auto& e : b->ev_rrt) if (e) (void)hipEventDestroy(e);
-  for (auto& e : b->ev_vt) if (e) (void)hipEventDestroy(e);
+  for (PassState& p : b->pass) {
+    if (p.done) (void)hipEventDestroy(p.done);
+    for (auto& e : p.mark) if (e) (void)hipEventDestroy(e);
+  }
   for (auto& r : b->ev) for (auto& e : r) if (e) (void)hipEventDestroy(e);
   for (auto& e : b->ev_sync) if (e) (void)hipEventDestroy(e);
   if (b->ev_join) (void)hipEventDestroy(b->ev_join);
@@ -992,25 +949,14 @@ static void batch_free(qm_batch* b) {
 }
 
 // ---- the passes of a batch still in flight (include/qmvt.h at qm_batch_run) ----
-// One row per pass over a finished batch: the event it records behind its last kernel, and whether it reads the hit bitmaps and the
-// record mask qm_batch_truth_hits writes.  A new pass adds its event HERE: the wait list of everything that rewrites what passes read.
-struct PassEvent { hipEvent_t qm_batch::* ev; bool reads_hits; };
-static const PassEvent PASS_EVENTS[] = {
-    {&qm_batch::ev_motif, false}, {&qm_batch::ev_afp, false},  {&qm_batch::ev_truth, false}, {&qm_batch::ev_strata, true},
-    {&qm_batch::ev_boot, true},   {&qm_batch::ev_votes, true}, {&qm_batch::ev_nm, true},     {&qm_batch::ev_sf, false},
-    {&qm_batch::ev_cx, true},     {&qm_batch::ev_norm, false}, {&qm_batch::ev_atom, false},
-    {&qm_batch::ev_types, false}, {&qm_batch::ev_haplo, false}, {&qm_batch::ev_hapsub, false},
-    {&qm_batch::ev_rroc, false},
-};
-// (ev_haplo: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
-// flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
 // Orders what follows behind every pass of the batch still in flight, on whatever stream it was enqueued: `st` waits for the passes'
-// events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps.  An event exists once its pass has
-// been called: a batch that never ran a pass makes no HIP call here.
+// done events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps (PASSES).  The wait list of
+// everything that rewrites what passes read is the table of passes itself: no pass can be missing from it.  A done event exists
+// once its pass has been called: a batch that never ran a pass makes no HIP call here.
 static int wait_passes(qm_batch* b, hipStream_t st, bool wait_host, bool hit_readers = false) {
-  for (const PassEvent& p : PASS_EVENTS) {
-    const hipEvent_t e = b->*(p.ev);
-    if (!e || (hit_readers && !p.reads_hits)) continue;
+  for (int id = 0; id < N_PASSES; ++id) {
+    const hipEvent_t e = b->pass[id].done;
+    if (!e || (hit_readers && !PASSES[id].reads_hits)) continue;
     if (wait_host) HIPCHK(hipEventSynchronize(e));
     else HIPCHK(hipStreamWaitEvent(st, e, 0));
   }
@@ -1267,7 +1213,7 @@ extern "C" int qm_batch_set_timing(qm_batch* b, int on) {
   if (!b) return fail(QM_E_INVAL, "qm_batch_set_timing: NULL batch");
   HIPCHK(hipSetDevice(b->ctx->dev));
   b->timing = on != 0;
-  b->n_timed = 0;   // averages restart
+  b->timed_runs = 0;   // averages restart
   if (b->timing && !b->ev[0][0]) for (auto& r : b->ev) for (auto& e : r) HIPCHK(hipEventCreate(&e));
   return QM_OK;
 }
@@ -1285,7 +1231,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
   // a pass still in flight, on whatever stream, reads the masks and rows this run rewrites (include/qmvt.h)
   const int rcw = wait_passes(b, st, false);
   if (rcw != QM_OK) return rcw;
-  hipEvent_t* ev = b->ev[b->n_timed % qm_batch::EV_RING];
+  hipEvent_t* ev = b->ev[b->timed_runs % qm_batch::EV_RING];
   const bool T = b->timing;
   if (T) HIPCHK(hipEventRecord(ev[0], st));
   // VCFs an earlier finish found out of order, columns unchanged since: their spans return at once (qm_batch: known)
@@ -1338,36 +1284,22 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
     if (T) HIPCHK(hipEventRecord(ev[6], st));
     HIPCHK(hipStreamWaitEvent(st, b->ev_sync[1], 0));   // the rows of k_finalize
   }
-  if (T) { HIPCHK(hipEventRecord(ev[1], st)); b->n_timed++; }
+  if (T) { HIPCHK(hipEventRecord(ev[1], st)); b->timed_runs++; }
   HIPCHK(hipGetLastError());
   b->ran = true;
   b->finished = false;
-  b->motifs_valid = false;
-  b->afp_valid = false;
-  b->hits_valid = false;
-  b->strata_made = 0;
-  b->boot_made = 0;
-  b->votes_valid = false;
-  b->nm_valid = false;
-  b->sf_valid = false;
-  b->cx_made = 0;
-  b->nz_made = 0;
-  b->at_made = 0;
-  b->ty_made = 0;
-  b->hp_made = 0;
-  b->hs_made = 0;
-  b->rr_made = 0;
+  for (PassState& p : b->pass) p.made = 0;   // every pass's result belongs to the run before
   b->last_global = g;
   return QM_OK;
 }
 
 extern "C" int qm_batch_timings(qm_batch* b, float* ms4) {
-  if (!b || !ms4 || !b->timing || b->n_timed == 0) return fail(QM_E_STATE, "qm_batch_timings: timing is off or nothing ran");
+  if (!b || !ms4 || !b->timing || b->timed_runs == 0) return fail(QM_E_STATE, "qm_batch_timings: timing is off or nothing ran");
   HIPCHK(hipSetDevice(b->ctx->dev));
-  const int n = (int)std::min<int64_t>(b->n_timed, qm_batch::EV_RING);
+  const int n = (int)std::min<int64_t>(b->timed_runs, qm_batch::EV_RING);
   double acc[4] = {0, 0, 0, 0};
   for (int i = 0; i < n; ++i) {   // averages over the latest runs since qm_batch_set_timing(1)
-    const int slot = (int)((b->n_timed - 1 - i) % qm_batch::EV_RING);
+    const int slot = (int)((b->timed_runs - 1 - i) % qm_batch::EV_RING);
     hipEvent_t* ev = b->ev[slot];
     HIPCHK(hipEventSynchronize(ev[1]));
     float t;
@@ -2385,13 +2317,123 @@ static int truths_live(const qm_batch* b, const char* who) {
       return fail(QM_E_STATE, "%s: truth set %d was released after the batch was created", who, tg.first);
   return QM_OK;
 }
-// How a pass opens (PassStream of DESIGN.md 4.13): the context's device, the caller's stream or the context's, and the pass's event -- created at first use,
+// Every genome a VCF names (ids[v] >= 0; -1: none) is in range and live.
+static int genomes_named(const qm_ctx* c, const char* who, const int32_t* ids, int nv) {
+  for (int v = 0; v < nv; ++v) {
+    const int gid = ids[v];
+    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "%s: VCF %d names genome %d (have %zu)", who, v, gid, c->genomes.size());
+    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "%s: VCF %d names released genome %d", who, v, gid);
+  }
+  return QM_OK;
+}
+// One pooled table per truth set that a VCF with a genome names (qm_batch_normalize, qm_batch_haplotypes): tabs[k] is the table of
+// truth set tabs[k].truth over genome tabs[k].genome and starts at word tabs[k].off of the pool, words(truth set) long; tab_of[v]
+// is the table of VCF v, -1 for a VCF that names no genome.  The VCFs that share a truth set must name one genome (`why`).
+struct TruthTab { int truth, genome; size_t first_vcf, off; };
+template <typename F>
+static int tabs_by_truth(const qm_batch* b, const char* who, const char* why, const int32_t* genome_ids, F&& words, std::vector<TruthTab>* tabs,
+                         std::vector<int>* tab_of, size_t* pool_words) {
+  tab_of->assign((size_t)b->n_vcf, -1);
+  for (size_t v = 0; v < (size_t)b->n_vcf; ++v) {
+    const int gid = genome_ids[v], tid = b->L.vcfs[v].truth;
+    if (gid < 0) continue;
+    size_t k = 0;
+    while (k < tabs->size() && (*tabs)[k].truth != tid) ++k;
+    if (k == tabs->size()) {
+      tabs->push_back(TruthTab{tid, gid, v, *pool_words});
+      *pool_words += words(b->ctx->truths[(size_t)tid]);
+    } else if ((*tabs)[k].genome != gid) {
+      return fail(QM_E_INVAL, "%s: VCF %zu and VCF %zu share truth set %d and name genomes %d and %d (%s)", who, (*tabs)[k].first_vcf, v, tid,
+                  (*tabs)[k].genome, gid, why);
+    }
+    (*tab_of)[v] = (int)k;
+  }
+  return QM_OK;
+}
+// A table built once in a pool of its own and read back (qm_truth_normalized, qm_truth_atoms, qm_truth_sites): build(pool, &src)
+// lays the table out in the pool, enqueues its build on the context's stream and says where the `bytes` for `out` start.
+template <typename F>
+static int build_and_read(qm_ctx* c, const char* who, size_t pool_words, void* out, size_t bytes, F&& build) {
+  uint32_t* pool = nullptr;
+  DALLOC(pool, pool_words);
+  const void* src = pool;
+  const int rc = build(pool, &src);
+  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
+  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(pool);
+  if (rc != QM_OK) return rc;
+  if (e != hipSuccess) return fail(QM_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  return QM_OK;
+}
+// `rows` device rows of (kept, TP) lines as the caller's rows of (kept, TP, FP = kept - TP)
+static int widen_kept_tp(const uint64_t* d_kt, size_t rows, uint64_t* out) {
+  std::vector<uint64_t> kt(rows * 2);
+  HIPCHK(hipMemcpy(kt.data(), d_kt, kt.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < rows; ++i) {
+    out[3 * i] = kt[2 * i];
+    out[3 * i + 1] = kt[2 * i + 1];
+    out[3 * i + 2] = kt[2 * i] - kt[2 * i + 1];
+  }
+  return QM_OK;
+}
+
+// ---- the state of a pass (PassState, PASSES): how it opens, marks its kernels and closes; how its getters open ----
+// How a pass opens: the context's device, the caller's stream or the context's, and the pass's done event -- created at first use,
 // waited for on the host afterwards (the previous call of the pass has read its tables and left its outputs).
-static int pass_stream(qm_batch* b, void* stream, hipEvent_t* ev, hipStream_t* st) {
+static int pass_open(qm_batch* b, PassId id, void* stream, hipStream_t* st) {
+  hipEvent_t* ev = &b->pass[id].done;
   HIPCHK(hipSetDevice(b->ctx->dev));
   *st = stream ? (hipStream_t)stream : b->ctx->stream;
   if (!*ev) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   else HIPCHK(hipEventSynchronize(*ev));
+  return QM_OK;
+}
+// In front of the first mark of a call: with qm_batch_set_timing on, the marks of the pass exist from here on (they need timing;
+// the done events do without); the call has recorded none yet.
+static hipError_t pass_marks(qm_batch* b, PassId id) {
+  PassState& p = b->pass[id];
+  for (int i = 0; b->timing && i < PASSES[id].marks; ++i)
+    if (!p.mark[i]) { const hipError_t e = hipEventCreate(&p.mark[i]); if (e != hipSuccess) return e; }
+  p.timed = false;
+  return hipSuccess;
+}
+// Mark i of the pass on `st`, with timing on; the last mark of a pass says that the call recorded them all.
+static hipError_t pass_mark(qm_batch* b, PassId id, int i, hipStream_t st) {
+  if (!b->timing) return hipSuccess;
+  const hipError_t e = hipEventRecord(b->pass[id].mark[i], st);
+  if (e == hipSuccess && i == PASSES[id].marks - 1) b->pass[id].timed = true;
+  return e;
+}
+// How a pass closes: its done event behind its last kernel, and what it made.
+static hipError_t pass_done(qm_batch* b, PassId id, hipStream_t st, unsigned made) {
+  const hipError_t e = hipEventRecord(b->pass[id].done, st);
+  if (e == hipSuccess) b->pass[id].made = made;
+  return e;
+}
+// How the getters of a pass open: refused while the pass made nothing behind the latest `since` ...
+static int pass_ran(const qm_batch* b, PassId id, const char* who, const char* since = "run") {
+  if (b->pass[id].made) return QM_OK;
+  return fail(QM_E_STATE, "%s: no %s behind the latest %s", who, PASSES[id].name, since);
+}
+#define NEED_PASS(b, id, who) \
+  if (!(b)) return fail(QM_E_INVAL, who ": NULL batch"); \
+  if (pass_ran(b, id, who) != QM_OK) return QM_E_STATE
+// ... then, behind the checks of their own arguments, the context's device and a wait on the host for the pass.
+static hipError_t pass_result(qm_batch* b, PassId id) {
+  const hipError_t e = hipSetDevice(b->ctx->dev);
+  return e != hipSuccess ? e : hipEventSynchronize(b->pass[id].done);
+}
+// The qm_batch_*_timings of a pass: the milliseconds between its marks, one value fewer than there are marks.
+static int pass_timings(qm_batch* b, PassId id, const char* who, const char* since, float* ms) {
+  if (!b || !ms) return fail(QM_E_INVAL, "%s: NULL", who);
+  const int rc = pass_ran(b, id, who, since);
+  if (rc != QM_OK) return rc;
+  const PassState& p = b->pass[id];
+  if (!p.timed) return fail(QM_E_STATE, "%s: timing is off", who);
+  const int n = PASSES[id].marks - 1;
+  HIPCHK(hipSetDevice(b->ctx->dev));
+  HIPCHK(hipEventSynchronize(p.mark[n]));
+  for (int i = 0; i < n; ++i) HIPCHK(hipEventElapsedTime(ms + i, p.mark[i], p.mark[i + 1]));
   return QM_OK;
 }
 // One group of a pass over the hit bitmaps (G: TruthGroup, VoteGroup): VCFs vcf_ids[group_offsets[g] .. group_offsets[g + 1]), 1 to
@@ -2480,13 +2522,10 @@ extern "C" int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, vo
   NEED_FINISHED(b, "qm_batch_motifs");
   if (!genome_id_per_vcf) return fail(QM_E_INVAL, "qm_batch_motifs: NULL genome ids");
   qm_ctx* c = b->ctx;
-  for (int v = 0; v < b->n_vcf; ++v) {
-    const int gid = genome_id_per_vcf[v];
-    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_motifs: VCF %d names genome %d (have %zu)", v, gid, c->genomes.size());
-    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_motifs: VCF %d names released genome %d", v, gid);
-  }
+  int rc = genomes_named(c, "qm_batch_motifs", genome_id_per_vcf, b->n_vcf);
+  if (rc != QM_OK) return rc;
   hipStream_t st;   // (the previous call's copy has read the page-locked descriptors)
-  int rc = pass_stream(b, stream, &b->ev_motif, &st);
+  rc = pass_open(b, P_MOTIFS, stream, &st);
   if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf;
   // first use: every piece on its own, so that a call that failed half way is completed by the next
@@ -2508,15 +2547,13 @@ extern "C" int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, vo
   P.n_spans = (int32_t)b->L.spans.size();
   launch_motif(P, b->ext, st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(b->ev_motif, st));
-  b->motifs_valid = true;
+  HIPCHK(pass_done(b, P_MOTIFS, st, 1));
   return QM_OK;
 }
 extern "C" int qm_batch_get_motifs(qm_batch* b, uint64_t* out) {
   if (!b || !out) return fail(QM_E_INVAL, "qm_batch_get_motifs: bad arguments");
-  if (!b->motifs_valid) return fail(QM_E_STATE, "qm_batch_get_motifs: no qm_batch_motifs behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_motif));
+  NEED_PASS(b, P_MOTIFS, "qm_batch_get_motifs");
+  HIPCHK(pass_result(b, P_MOTIFS));
   HIPCHK(hipMemcpy(out, b->d_motifs, (size_t)b->n_vcf * MOTIF_ROW_WORDS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
@@ -2548,7 +2585,7 @@ extern "C" int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bi
   if (window < 1 || window >= QM_POS_LIMIT || n_pos_bins < 1 || n_af_bins < 1 || (int64_t)n_pos_bins * n_af_bins > QM_AFP_MAX_CELLS)
     return fail(QM_E_INVAL, "qm_batch_af_profile: window %d, %d x %d bins (1 <= window < 2^28, at most %d cells)", window, n_af_bins, n_pos_bins, QM_AFP_MAX_CELLS);
   hipStream_t st;   // (the previous pass has read the marks and left the outputs)
-  int rc = pass_stream(b, stream, &b->ev_afp, &st);
+  int rc = pass_open(b, P_AFP, stream, &st);
   if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf, cells = (size_t)n_pos_bins * (size_t)n_af_bins;
   rc = b->d_afgrid.grow((int64_t)(nv * 2 * cells), &b->dev_bytes);
@@ -2572,16 +2609,14 @@ extern "C" int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bi
     launch_af_profile(P, b->ext, st);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(b->ev_afp, st));
+  HIPCHK(pass_done(b, P_AFP, st, 1));
   b->afp_cells = (int32_t)cells;
-  b->afp_valid = true;
   return QM_OK;
 }
 extern "C" int qm_batch_get_af_profile(qm_batch* b, uint64_t* grid, uint64_t* extra) {
   if (!b || !grid) return fail(QM_E_INVAL, "qm_batch_get_af_profile: bad arguments");
-  if (!b->afp_valid) return fail(QM_E_STATE, "qm_batch_get_af_profile: no qm_batch_af_profile behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_afp));
+  NEED_PASS(b, P_AFP, "qm_batch_get_af_profile");
+  HIPCHK(pass_result(b, P_AFP));
   HIPCHK(hipMemcpy(grid, b->d_afgrid, (size_t)b->n_vcf * 2 * (size_t)b->afp_cells * 8, hipMemcpyDeviceToHost));
   if (extra) HIPCHK(hipMemcpy(extra, b->d_afextra, (size_t)b->n_vcf * 2 * AFP_EXTRA * 8, hipMemcpyDeviceToHost));
   return QM_OK;
@@ -2595,16 +2630,16 @@ extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* 
   if (!what || (what & ~(QM_STRATA_RECORDS | QM_STRATA_TRUTH))) return fail(QM_E_INVAL, "qm_batch_strata: what = %u", what);
   if (what & QM_STRATA_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_strata: allele-extended batches have no truth-side bitmaps (QM_STRATA_RECORDS only)");
-    if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_strata: QM_STRATA_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_strata: QM_STRATA_TRUTH needs a qm_batch_truth_hits behind the latest run");
     const int rc = truths_live(b, "qm_batch_strata");
     if (rc != QM_OK) return rc;
   }
   hipStream_t st;
-  const int rc0 = pass_stream(b, stream, &b->ev_strata, &st);
+  const int rc0 = pass_open(b, P_STRATA, stream, &st);
   if (rc0 != QM_OK) return rc0;
   const size_t nv = (size_t)b->n_vcf;
   const int S = t->n_strata;
-  b->strata_made = 0;
+  b->pass[P_STRATA].made = 0;
   StrataTable tab;
   tab.bp = t->d_bp; tab.masks = t->d_masks; tab.cidx = t->d_cidx;
   tab.m = (int32_t)t->bp.size(); tab.shift = t->shift; tab.n_strata = S; tab.pad = 0;
@@ -2640,7 +2675,7 @@ extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* 
     if (rc != QM_OK) return rc;
     std::vector<StrataTruthRow> rows(nv);
     std::vector<uint8_t> done(c->truths.size(), 0);
-    HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
     for (size_t v = 0; v < nv; ++v) {
       const size_t tid = (size_t)b->L.vcfs[v].truth;
       const int64_t tn = b->h_hit_tn[v];
@@ -2658,27 +2693,19 @@ extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* 
     launch_strata_truth(b->d_srows, (int)nv, max_words, S, reinterpret_cast<unsigned long long*>(b->d_stru.p), st);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(b->ev_strata, st));
+  HIPCHK(pass_done(b, P_STRATA, st, what));
   b->strata_S = S;
-  b->strata_made = what;
   return QM_OK;
 }
 extern "C" int qm_batch_get_strata(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_strata: NULL batch");
-  if (!b->strata_made) return fail(QM_E_STATE, "qm_batch_get_strata: no qm_batch_strata behind the latest run");
-  if ((rec && !(b->strata_made & QM_STRATA_RECORDS)) || (tru && !(b->strata_made & QM_STRATA_TRUTH)))
-    return fail(QM_E_STATE, "qm_batch_get_strata: the latest qm_batch_strata did not make the %s side", rec && !(b->strata_made & QM_STRATA_RECORDS) ? "record" : "truth");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_strata));
+  NEED_PASS(b, P_STRATA, "qm_batch_get_strata");
+  if ((rec && !(b->pass[P_STRATA].made & QM_STRATA_RECORDS)) || (tru && !(b->pass[P_STRATA].made & QM_STRATA_TRUTH)))
+    return fail(QM_E_STATE, "qm_batch_get_strata: the latest qm_batch_strata did not make the %s side", rec && !(b->pass[P_STRATA].made & QM_STRATA_RECORDS) ? "record" : "truth");
+  HIPCHK(pass_result(b, P_STRATA));
   const size_t nv = (size_t)b->n_vcf, S = (size_t)b->strata_S;
   if (rec && nv) {
-    std::vector<uint64_t> kt(nv * (S + 2) * 2);
-    HIPCHK(hipMemcpy(kt.data(), b->d_srec, kt.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < nv * (S + 2); ++i) {   // FP lines = kept - TP
-      rec[3 * i] = kt[2 * i];
-      rec[3 * i + 1] = kt[2 * i + 1];
-      rec[3 * i + 2] = kt[2 * i] - kt[2 * i + 1];
-    }
+    const int rc = widen_kept_tp(b->d_srec, nv * (S + 2), rec);
+    if (rc != QM_OK) return rc;
   }
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->d_stru, nv * (S + 1) * 2 * 8, hipMemcpyDeviceToHost));
   return QM_OK;
@@ -2691,30 +2718,25 @@ extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, i
   if (rc != QM_OK) return rc;
   if (!what || (what & ~(QM_CX_RECORDS | QM_CX_TRUTH))) return fail(QM_E_INVAL, "qm_batch_context: what = %u", what);
   qm_ctx* c = b->ctx;
-  for (int v = 0; v < b->n_vcf; ++v) {
-    const int gid = genome_id_per_vcf[v];
-    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_context: VCF %d names genome %d (have %zu)", v, gid, c->genomes.size());
-    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_context: VCF %d names released genome %d", v, gid);
-  }
+  rc = genomes_named(c, "qm_batch_context", genome_id_per_vcf, b->n_vcf);
+  if (rc != QM_OK) return rc;
   if (what & QM_CX_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_context: allele-extended batches have no truth-side bitmaps (QM_CX_RECORDS only)");
-    if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_context: QM_CX_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_context: QM_CX_TRUTH needs a qm_batch_truth_hits behind the latest run");
     rc = truths_live(b, "qm_batch_context");
     if (rc != QM_OK) return rc;
   }
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_cx, &st);
+  rc = pass_open(b, P_CONTEXT, stream, &st);
   if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf, n_cells = (size_t)(16 * ng + 1);
-  b->cx_made = 0;   // from here on the outputs are rewritten
+  b->pass[P_CONTEXT].made = 0;   // from here on the outputs are rewritten
   rc = b->cx_gen.grow((int64_t)std::max<size_t>(nv * n_cells, 1), &b->dev_bytes);
   if (rc == QM_OK) rc = b->cx_tabs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_cxt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->cx_timed = false;
+  HIPCHK(pass_marks(b, P_CONTEXT));
   b->cx_built = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_cxt[0], st));
+  HIPCHK(pass_mark(b, P_CONTEXT, 0, st));
   std::vector<ContextTab> tabs(nv, ContextTab{nullptr, 0});
   HIPCHK(hipMemsetAsync(b->cx_gen, 0, std::max<size_t>(nv * n_cells, 1) * 8, st));
   for (size_t v = 0; v < nv; ++v) {
@@ -2727,7 +2749,7 @@ extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, i
     HIPCHK(hipMemcpyAsync(b->cx_gen + v * n_cells, g.d_cgen, n_cells * 8, hipMemcpyDeviceToDevice, st));
   }
   if (nv) HIPCHK(hipMemcpy(b->cx_tabs, tabs.data(), nv * sizeof(ContextTab), hipMemcpyHostToDevice));   // blocking: tabs dies here
-  if (T) HIPCHK(hipEventRecord(b->ev_cxt[1], st));
+  HIPCHK(pass_mark(b, P_CONTEXT, 1, st));
   if (what & QM_CX_RECORDS) {
     const size_t words = nv * (n_cells + 1) * 2;
     rc = b->cx_rec.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
@@ -2741,7 +2763,7 @@ extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, i
     launch_context_records(P, st);
     HIPCHK(hipGetLastError());
   }
-  if (T) HIPCHK(hipEventRecord(b->ev_cxt[2], st));
+  HIPCHK(pass_mark(b, P_CONTEXT, 2, st));
   if (what & QM_CX_TRUTH) {
     const size_t words = nv * n_cells * 2;
     rc = b->cx_tru.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
@@ -2757,48 +2779,35 @@ extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, i
       rows[v].len = tabs[v].len;
       max_n = std::max(max_n, rows[v].n);
     }
-    HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
     if (nv) HIPCHK(hipMemcpy(b->cx_rows, rows.data(), nv * sizeof(ContextTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
     HIPCHK(hipMemsetAsync(b->cx_tru, 0, words * 8, st));
     launch_context_truth(b->cx_rows, (int)nv, max_n, ng, reinterpret_cast<unsigned long long*>(b->cx_tru.p), st);
     HIPCHK(hipGetLastError());
   }
-  if (T) { HIPCHK(hipEventRecord(b->ev_cxt[3], st)); b->cx_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_cx, st));
+  HIPCHK(pass_mark(b, P_CONTEXT, 3, st));
+  HIPCHK(pass_done(b, P_CONTEXT, st, what));
   b->cx_ng = ng;
-  b->cx_made = what;
   return QM_OK;
 }
 extern "C" int qm_batch_get_context(qm_batch* b, uint64_t* rec, uint64_t* tru, uint64_t* gen_per_vcf) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_context: NULL batch");
-  if (!b->cx_made) return fail(QM_E_STATE, "qm_batch_get_context: no qm_batch_context behind the latest run");
-  if ((rec && !(b->cx_made & QM_CX_RECORDS)) || (tru && !(b->cx_made & QM_CX_TRUTH)))
-    return fail(QM_E_STATE, "qm_batch_get_context: the latest qm_batch_context did not make the %s side", rec && !(b->cx_made & QM_CX_RECORDS) ? "record" : "truth");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_cx));
+  NEED_PASS(b, P_CONTEXT, "qm_batch_get_context");
+  if ((rec && !(b->pass[P_CONTEXT].made & QM_CX_RECORDS)) || (tru && !(b->pass[P_CONTEXT].made & QM_CX_TRUTH)))
+    return fail(QM_E_STATE, "qm_batch_get_context: the latest qm_batch_context did not make the %s side", rec && !(b->pass[P_CONTEXT].made & QM_CX_RECORDS) ? "record" : "truth");
+  HIPCHK(pass_result(b, P_CONTEXT));
   const size_t nv = (size_t)b->n_vcf, n_cells = (size_t)(16 * b->cx_ng + 1);
   if (rec && nv) {
-    std::vector<uint64_t> kt(nv * (n_cells + 1) * 2);
-    HIPCHK(hipMemcpy(kt.data(), b->cx_rec, kt.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < nv * (n_cells + 1); ++i) {   // FP lines = kept - TP
-      rec[3 * i] = kt[2 * i];
-      rec[3 * i + 1] = kt[2 * i + 1];
-      rec[3 * i + 2] = kt[2 * i] - kt[2 * i + 1];
-    }
+    const int rc = widen_kept_tp(b->cx_rec, nv * (n_cells + 1), rec);
+    if (rc != QM_OK) return rc;
   }
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->cx_tru, nv * n_cells * 2 * 8, hipMemcpyDeviceToHost));
   if (gen_per_vcf && nv) HIPCHK(hipMemcpy(gen_per_vcf, b->cx_gen, nv * n_cells * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_context_timings(qm_batch* b, float* ms3) {
-  if (!b || !ms3) return fail(QM_E_INVAL, "qm_batch_context_timings: NULL");
-  if (!b->cx_made) return fail(QM_E_STATE, "qm_batch_context_timings: no qm_batch_context behind the latest run");
-  if (!b->cx_timed) return fail(QM_E_STATE, "qm_batch_context_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_cxt[3]));
-  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_cxt[i], b->ev_cxt[i + 1]));
-  if (!b->cx_built) ms3[0] = 0.0f;   // every table was cached
-  return QM_OK;
+  const int rc = pass_timings(b, P_CONTEXT, "qm_batch_context_timings", "run", ms3);
+  if (rc == QM_OK && !b->cx_built) ms3[0] = 0.0f;   // every table was cached
+  return rc;
 }
 // ---- indels and MNPs matched by normal form ----
 // The pool words of one table: [claim | spos | sref | salt | sresp][slots], [fpos | fref | falt][xn], stats[2] (8-byte aligned)
@@ -2839,42 +2848,26 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   if (!b->ext) return fail(QM_E_STATE, "qm_batch_normalize: a single-base batch holds no indels or MNPs to normalise (create the batch with QM_BATCH_ALLELES)");
   qm_ctx* c = b->ctx;
   const size_t nv = (size_t)b->n_vcf;
-  for (size_t v = 0; v < nv; ++v) {
-    const int gid = genome_id_per_vcf[v];
-    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_normalize: VCF %zu names genome %d (have %zu)", v, gid, c->genomes.size());
-    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_normalize: VCF %zu names released genome %d", v, gid);
-  }
-  int rc = truths_live(b, "qm_batch_normalize");
+  int rc = genomes_named(c, "qm_batch_normalize", genome_id_per_vcf, b->n_vcf);
+  if (rc == QM_OK) rc = truths_live(b, "qm_batch_normalize");
   if (rc != QM_OK) return rc;
   // one table per truth set: the VCFs that share one must name one genome
-  struct Pair { int truth, genome; size_t first_vcf, off; uint32_t slots; };
-  std::vector<Pair> pairs;
-  std::vector<int> pair_of(nv, -1);
+  std::vector<TruthTab> pairs;
+  std::vector<int> pair_of;
   size_t pool_words = 0, bit_words = 0;
-  for (size_t v = 0; v < nv; ++v) {
-    const int gid = genome_id_per_vcf[v], tid = b->L.vcfs[v].truth;
-    if (gid < 0) continue;
-    size_t k = 0;
-    while (k < pairs.size() && pairs[k].truth != tid) ++k;
-    if (k == pairs.size()) {
-      const uint32_t slots = norm_slots(c->truths[(size_t)tid].xn);
-      pairs.push_back(Pair{tid, gid, v, pool_words, slots});
-      pool_words += norm_pool_words(c->truths[(size_t)tid].xn, slots);
-    } else if (pairs[k].genome != gid) {
-      return fail(QM_E_INVAL, "qm_batch_normalize: VCF %zu and VCF %zu share truth set %d and name genomes %d and %d (a normalised truth set belongs to one genome)",
-                  pairs[k].first_vcf, v, tid, pairs[k].genome, gid);
-    }
-    pair_of[v] = (int)k;
-    bit_words += 2 * (size_t)(pairs[k].slots / 32u);
-  }
+  rc = tabs_by_truth(b, "qm_batch_normalize", "a normalised truth set belongs to one genome", genome_id_per_vcf,
+                     [](const Truth& t) { return norm_pool_words(t.xn, norm_slots(t.xn)); }, &pairs, &pair_of, &pool_words);
+  if (rc != QM_OK) return rc;
+  for (size_t v = 0; v < nv; ++v)
+    if (pair_of[v] >= 0) bit_words += 2 * (size_t)(norm_slots(c->truths[(size_t)b->L.vcfs[v].truth].xn) / 32u);
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_norm, &st);
+  rc = pass_open(b, P_NORM, stream, &st);
   if (rc != QM_OK) return rc;
   // A sweep behind the previous call (qm_batch_rescue_roc, maybe on another stream) reads the columns this call rewrites and may
   // regrow: it is waited for here, not only on the stream.
-  if (b->ev_rroc) HIPCHK(hipEventSynchronize(b->ev_rroc));
-  b->nz_made = 0;   // from here on the outputs are rewritten
-  b->rr_made &= ~QM_RROC_NORM;   // ... and the sweep's rows belong to the call before
+  if (b->pass[P_RROC].done) HIPCHK(hipEventSynchronize(b->pass[P_RROC].done));
+  b->pass[P_NORM].made = 0;   // from here on the outputs are rewritten
+  b->pass[P_RROC].made &= ~QM_RROC_NORM;   // ... and the sweep's rows belong to the call before
   const size_t np = (size_t)b->L.n_pad;
   rc = b->nz_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->nz_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -2884,13 +2877,12 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   if (rc == QM_OK) rc = b->nz_cls.grow((int64_t)np, &b->dev_bytes);
   if (rc == QM_OK && (what & QM_NORM_COLUMNS)) rc = b->nz_cols.grow((int64_t)(4 * np), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_nzt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->nz_timed = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_nzt[0], st));
+  HIPCHK(pass_marks(b, P_NORM));
+  HIPCHK(pass_mark(b, P_NORM, 0, st));
   std::vector<NormTable> tabs(pairs.size());
   for (size_t k = 0; k < pairs.size(); ++k) {
-    tabs[k] = norm_table(c->truths[(size_t)pairs[k].truth], c->genomes[(size_t)pairs[k].genome], b->nz_pool + pairs[k].off, pairs[k].slots);
+    const Truth& t = c->truths[(size_t)pairs[k].truth];
+    tabs[k] = norm_table(t, c->genomes[(size_t)pairs[k].genome], b->nz_pool + pairs[k].off, norm_slots(t.xn));
     rc = norm_build(tabs[k], st);
     if (rc != QM_OK) return rc;
   }
@@ -2912,7 +2904,7 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   HIPCHK(hipMemsetAsync(b->nz_rec, 0, std::max<size_t>(nv * NORM_R_COLS, 1) * 8, st));
   HIPCHK(hipMemsetAsync(b->nz_tru, 0, std::max<size_t>(nv * NORM_T_COLS, 1) * 8, st));
   HIPCHK(hipMemsetAsync(b->nz_cls, 0, np, st));
-  if (T) HIPCHK(hipEventRecord(b->ev_nzt[1], st));
+  HIPCHK(pass_mark(b, P_NORM, 1, st));
   NormRecParams P;
   memset(&P, 0, sizeof P);
   P.spans = b->d_spans; P.vcfs = b->nz_vcfs;
@@ -2924,33 +2916,28 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   P.n_spans = (int32_t)b->L.spans.size();
   launch_norm_records(P, st);
   HIPCHK(hipGetLastError());
-  if (T) HIPCHK(hipEventRecord(b->ev_nzt[2], st));
+  HIPCHK(pass_mark(b, P_NORM, 2, st));
   launch_norm_found(b->nz_vcfs, (int)nv, b->nz_tru, st);
   HIPCHK(hipGetLastError());
-  if (T) { HIPCHK(hipEventRecord(b->ev_nzt[3], st)); b->nz_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_norm, st));
-  b->nz_made = 1u | what;
+  HIPCHK(pass_mark(b, P_NORM, 3, st));
+  HIPCHK(pass_done(b, P_NORM, st, 1u | what));
   return QM_OK;
 }
 extern "C" int qm_batch_get_normalize(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_normalize: NULL batch");
-  if (!b->nz_made) return fail(QM_E_STATE, "qm_batch_get_normalize: no qm_batch_normalize behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_norm));
+  NEED_PASS(b, P_NORM, "qm_batch_get_normalize");
+  HIPCHK(pass_result(b, P_NORM));
   const size_t nv = (size_t)b->n_vcf;
   if (rec && nv) HIPCHK(hipMemcpy(rec, b->nz_rec, nv * NORM_R_COLS * 8, hipMemcpyDeviceToHost));
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->nz_tru, nv * NORM_T_COLS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_normalized(qm_batch* b, int v, int32_t* pos, int32_t* ref, int32_t* alt, uint8_t* cls, int32_t* truth_row) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_normalized: NULL batch");
-  if (!b->nz_made) return fail(QM_E_STATE, "qm_batch_get_normalized: no qm_batch_normalize behind the latest run");
+  NEED_PASS(b, P_NORM, "qm_batch_get_normalized");
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_normalized: VCF %d (the batch has %d)", v, b->n_vcf);
   if (!b->nz_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_normalized: VCF %d named no genome in the latest qm_batch_normalize", v);
-  if ((pos || ref || alt || truth_row) && !(b->nz_made & QM_NORM_COLUMNS))
+  if ((pos || ref || alt || truth_row) && !(b->pass[P_NORM].made & QM_NORM_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_get_normalized: the latest qm_batch_normalize did not keep the columns (QM_NORM_COLUMNS)");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_norm));
+  HIPCHK(pass_result(b, P_NORM));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   if (d.n == 0) return QM_OK;
   const size_t np = (size_t)b->L.n_pad, n = (size_t)d.n;
@@ -2961,13 +2948,7 @@ extern "C" int qm_batch_get_normalized(qm_batch* b, int v, int32_t* pos, int32_t
   return QM_OK;
 }
 extern "C" int qm_batch_normalize_timings(qm_batch* b, float* ms3) {
-  if (!b || !ms3) return fail(QM_E_INVAL, "qm_batch_normalize_timings: NULL");
-  if (!b->nz_made) return fail(QM_E_STATE, "qm_batch_normalize_timings: no qm_batch_normalize behind the latest run");
-  if (!b->nz_timed) return fail(QM_E_STATE, "qm_batch_normalize_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_nzt[3]));
-  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_nzt[i], b->ev_nzt[i + 1]));
-  return QM_OK;
+  return pass_timings(b, P_NORM, "qm_batch_normalize_timings", "run", ms3);
 }
 extern "C" int qm_truth_entries(qm_ctx* c, int truth_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out) {
   if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_entries: bad arguments");
@@ -2996,16 +2977,11 @@ extern "C" int qm_truth_normalized(qm_ctx* c, int truth_id, int genome_id, int32
   HIPCHK(hipSetDevice(c->dev));
   const Truth& t = c->truths[(size_t)truth_id];
   const uint32_t slots = norm_slots(t.xn);
-  uint32_t* pool = nullptr;
-  DALLOC(pool, norm_pool_words(t.xn, slots));
-  const NormTable T = norm_table(t, c->genomes[(size_t)genome_id], pool, slots);
-  std::vector<uint32_t> h(4 * (size_t)slots);
-  int rc = norm_build(T, c->stream);
-  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
-  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(h.data(), pool, h.size() * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(pool);
+  std::vector<uint32_t> h(4 * (size_t)slots);   // claim | spos | sref | salt: the head of the pool
+  const int rc = build_and_read(c, "qm_truth_normalized", norm_pool_words(t.xn, slots), h.data(), h.size() * 4, [&](uint32_t* pool, const void**) {
+    return norm_build(norm_table(t, c->genomes[(size_t)genome_id], pool, slots), c->stream);
+  });
   if (rc != QM_OK) return rc;
-  if (e != hipSuccess) return fail(QM_E_HIP, "qm_truth_normalized: %s", hipGetErrorString(e));
   struct F { int32_t p, r, a; };
   std::vector<F> forms;
   for (size_t s = 0; s < slots; ++s)
@@ -3094,11 +3070,11 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
     max_lanes = std::max<int64_t>(max_lanes, std::max<int64_t>(xn, (int64_t)(sets[k].slots / 32u)));
   }
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_atom, &st);
+  rc = pass_open(b, P_ATOM, stream, &st);
   if (rc != QM_OK) return rc;
-  if (b->ev_rroc) HIPCHK(hipEventSynchronize(b->ev_rroc));   // (as in qm_batch_normalize: the sweep reads the sets and the columns)
-  b->at_made = 0;   // from here on the outputs are rewritten
-  b->rr_made &= ~QM_RROC_ATOM;
+  if (b->pass[P_RROC].done) HIPCHK(hipEventSynchronize(b->pass[P_RROC].done));   // (as in qm_batch_normalize: the sweep reads the sets and the columns)
+  b->pass[P_ATOM].made = 0;   // from here on the outputs are rewritten
+  b->pass[P_RROC].made &= ~QM_RROC_ATOM;
   const size_t np = (size_t)b->L.n_pad;
   rc = b->at_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->at_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -3108,10 +3084,8 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
   if (rc == QM_OK && (what & QM_ATOM_COLUMNS)) rc = b->at_cls.grow((int64_t)std::max<size_t>(2 * np, 1), &b->dev_bytes);
   if (rc == QM_OK && (what & QM_ATOM_COLUMNS)) rc = b->at_hm.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_att) if (!e) HIPCHK(hipEventCreate(&e));
-  b->at_timed = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_att[0], st));
+  HIPCHK(pass_marks(b, P_ATOM));
+  HIPCHK(pass_mark(b, P_ATOM, 0, st));
   std::vector<AtomTable> tabs(sets.size());
   for (size_t k = 0; k < sets.size(); ++k) {
     tabs[k] = atom_table(c->truths[(size_t)sets[k].truth], b->at_pool + sets[k].off, sets[k].slots);
@@ -3136,7 +3110,7 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
     HIPCHK(hipMemsetAsync(b->at_cls, 0, std::max<size_t>(2 * np, 1), st));
     HIPCHK(hipMemsetAsync(b->at_hm, 0, std::max<size_t>(np, 1) * 2, st));
   }
-  if (T) HIPCHK(hipEventRecord(b->ev_att[1], st));
+  HIPCHK(pass_mark(b, P_ATOM, 1, st));
   AtomRecParams P;
   memset(&P, 0, sizeof P);
   P.spans = b->d_spans; P.vcfs = b->at_vcfs;
@@ -3147,32 +3121,27 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
   P.n_spans = (int32_t)b->L.spans.size();
   launch_atom_records(P, st);
   HIPCHK(hipGetLastError());
-  if (T) HIPCHK(hipEventRecord(b->ev_att[2], st));
+  HIPCHK(pass_mark(b, P_ATOM, 2, st));
   launch_atom_found(b->at_vcfs, (int)nv, max_lanes, b->at_tru, st);
   HIPCHK(hipGetLastError());
-  if (T) { HIPCHK(hipEventRecord(b->ev_att[3], st)); b->at_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_atom, st));
-  b->at_made = 1u | what;
+  HIPCHK(pass_mark(b, P_ATOM, 3, st));
+  HIPCHK(pass_done(b, P_ATOM, st, 1u | what));
   return QM_OK;
 }
 extern "C" int qm_batch_get_atomize(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_atomize: NULL batch");
-  if (!b->at_made) return fail(QM_E_STATE, "qm_batch_get_atomize: no qm_batch_atomize behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_atom));
+  NEED_PASS(b, P_ATOM, "qm_batch_get_atomize");
+  HIPCHK(pass_result(b, P_ATOM));
   const size_t nv = (size_t)b->n_vcf;
   if (rec && nv) HIPCHK(hipMemcpy(rec, b->at_rec, nv * ATOM_R_COLS * 8, hipMemcpyDeviceToHost));
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->at_tru, nv * ATOM_T_COLS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_atomized(qm_batch* b, int v, uint8_t* cls, uint8_t* n_atoms, uint16_t* hit_mask) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_atomized: NULL batch");
-  if (!b->at_made) return fail(QM_E_STATE, "qm_batch_get_atomized: no qm_batch_atomize behind the latest run");
+  NEED_PASS(b, P_ATOM, "qm_batch_get_atomized");
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_atomized: VCF %d (the batch has %d)", v, b->n_vcf);
-  if (!(b->at_made & QM_ATOM_COLUMNS))
+  if (!(b->pass[P_ATOM].made & QM_ATOM_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_get_atomized: the latest qm_batch_atomize did not keep the columns (QM_ATOM_COLUMNS)");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_atom));
+  HIPCHK(pass_result(b, P_ATOM));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   if (d.n == 0) return QM_OK;
   const size_t np = (size_t)b->L.n_pad, n = (size_t)d.n;
@@ -3182,13 +3151,7 @@ extern "C" int qm_batch_get_atomized(qm_batch* b, int v, uint8_t* cls, uint8_t* 
   return QM_OK;
 }
 extern "C" int qm_batch_atomize_timings(qm_batch* b, float* ms3) {
-  if (!b || !ms3) return fail(QM_E_INVAL, "qm_batch_atomize_timings: NULL");
-  if (!b->at_made) return fail(QM_E_STATE, "qm_batch_atomize_timings: no qm_batch_atomize behind the latest run");
-  if (!b->at_timed) return fail(QM_E_STATE, "qm_batch_atomize_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_att[3]));
-  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_att[i], b->ev_att[i + 1]));
-  return QM_OK;
+  return pass_timings(b, P_ATOM, "qm_batch_atomize_timings", "run", ms3);
 }
 extern "C" int qm_truth_atoms(qm_ctx* c, int truth_id, uint32_t* keys, int64_t capacity, int64_t* n_out) {
   if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_atoms: bad arguments");
@@ -3200,16 +3163,11 @@ extern "C" int qm_truth_atoms(qm_ctx* c, int truth_id, uint32_t* keys, int64_t c
   int rc = atom_total(c, t, &total);
   if (rc != QM_OK) return rc;
   const uint32_t slots = atom_slots(total);
-  uint32_t* pool = nullptr;
-  DALLOC(pool, atom_pool_words(slots));
-  const AtomTable T = atom_table(t, pool, slots);
-  std::vector<uint32_t> h((size_t)slots);
-  rc = atom_build(T, c->stream);
-  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
-  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(h.data(), pool, h.size() * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(pool);
+  std::vector<uint32_t> h((size_t)slots);   // the set: the head of the pool
+  rc = build_and_read(c, "qm_truth_atoms", atom_pool_words(slots), h.data(), h.size() * 4, [&](uint32_t* pool, const void**) {
+    return atom_build(atom_table(t, pool, slots), c->stream);
+  });
   if (rc != QM_OK) return rc;
-  if (e != hipSuccess) return fail(QM_E_HIP, "qm_truth_atoms: %s", hipGetErrorString(e));
   h.erase(std::remove(h.begin(), h.end(), ATOM_EMPTY), h.end());
   std::sort(h.begin(), h.end());
   *n_out = (int64_t)h.size();
@@ -3223,9 +3181,9 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
   if (which == 0 || (which & ~(QM_RROC_NORM | QM_RROC_ATOM))) return fail(QM_E_INVAL, "qm_batch_rescue_roc: which = %u", which);
   if (!b->ext) return fail(QM_E_STATE, "qm_batch_rescue_roc: a single-base batch has no rescue passes to sweep (create the batch with QM_BATCH_ALLELES)");
   const bool wn = (which & QM_RROC_NORM) != 0, wa = (which & QM_RROC_ATOM) != 0;
-  if (wn && !(b->nz_made & QM_NORM_COLUMNS))
+  if (wn && !(b->pass[P_NORM].made & QM_NORM_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_rescue_roc: QM_RROC_NORM needs qm_batch_normalize(.., QM_NORM_COLUMNS) behind the latest run");
-  if (wa && !(b->at_made & QM_ATOM_COLUMNS))
+  if (wa && !(b->pass[P_ATOM].made & QM_ATOM_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_rescue_roc: QM_RROC_ATOM needs qm_batch_atomize(QM_ATOM_COLUMNS) behind the latest run");
   qm_ctx* c = b->ctx;
   const size_t nv = (size_t)b->n_vcf, nb = (size_t)b->n_bins;
@@ -3249,9 +3207,9 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
     }
   }
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_rroc, &st);
+  rc = pass_open(b, P_RROC, stream, &st);
   if (rc != QM_OK) return rc;
-  b->rr_made = 0;   // from here on the outputs are rewritten
+  b->pass[P_RROC].made = 0;   // from here on the outputs are rewritten
   const size_t rows = nv * 3 * nb, out_words = std::max<size_t>(2 * rows + 2 * nv, 1);
   rc = b->rr_best.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
   if (rc == QM_OK) rc = b->rr_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
@@ -3261,11 +3219,9 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
     if (wn && b->nz_has[v]) vcfs[v].best_n = b->rr_best + off_n[v];
     if (wa) { vcfs[v].best_atom = b->rr_best + off_a[v]; vcfs[v].best_entry = b->rr_best + off_e[v]; }
   }
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_rrt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->rr_timed = false;
-  if (wn) HIPCHK(hipStreamWaitEvent(st, b->ev_norm, 0));   // the producers may have run on other streams
-  if (wa) HIPCHK(hipStreamWaitEvent(st, b->ev_atom, 0));
+  HIPCHK(pass_marks(b, P_RROC));
+  if (wn) HIPCHK(hipStreamWaitEvent(st, b->pass[P_NORM].done, 0));   // the producers may have run on other streams
+  if (wa) HIPCHK(hipStreamWaitEvent(st, b->pass[P_ATOM].done, 0));
   if (nv) HIPCHK(hipMemcpy(b->rr_vcfs, vcfs.data(), nv * sizeof(RrocVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
   HIPCHK(hipMemsetAsync(b->rr_best, 0, std::max<size_t>(words, 1) * 4, st));
   HIPCHK(hipMemsetAsync(b->rr_out, 0, out_words * 8, st));
@@ -3276,40 +3232,38 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
   P.spans = b->d_spans; P.vcfs = b->rr_vcfs;
   P.pos = b->pos; P.ref = b->ref; P.alt = b->alt; P.qual = b->qual; P.flags = b->flags;
   P.n_spans = (int32_t)b->L.spans.size(); P.n_bins = b->n_bins;
-  if (T) HIPCHK(hipEventRecord(b->ev_rrt[0], st));
+  HIPCHK(pass_mark(b, P_RROC, 0, st));
   if (wn) {
     P.nrow = b->nz_cols + 3 * np; P.hist = b->rr_out;
     launch_rroc_records(RROC_N, P, st);
     HIPCHK(hipGetLastError());
   }
-  if (T) HIPCHK(hipEventRecord(b->ev_rrt[1], st));
+  HIPCHK(pass_mark(b, P_RROC, 1, st));
   if (wn) {
     launch_rroc_units(RROC_N, b->rr_vcfs, nullptr, (int)nv, b->rr_out, b->n_bins, base, b->nz_tru, NORM_T_COLS, QM_NORM_T_FORMS, st);
     HIPCHK(hipGetLastError());
   }
-  if (T) HIPCHK(hipEventRecord(b->ev_rrt[2], st));
+  HIPCHK(pass_mark(b, P_RROC, 2, st));
   if (wa) {
     P.nrow = nullptr; P.avcfs = b->at_vcfs; P.hit_mask = b->at_hm; P.hist = b->rr_out + rows;
     launch_rroc_records(RROC_A, P, st);
     HIPCHK(hipGetLastError());
   }
-  if (T) HIPCHK(hipEventRecord(b->ev_rrt[3], st));
+  HIPCHK(pass_mark(b, P_RROC, 3, st));
   if (wa) {
     launch_rroc_units(RROC_A, b->rr_vcfs, b->at_vcfs, (int)nv, b->rr_out + rows, b->n_bins, base, b->at_tru, ATOM_T_COLS, QM_ATOM_T_ENTRIES, st);
     HIPCHK(hipGetLastError());
   }
-  if (T) { HIPCHK(hipEventRecord(b->ev_rrt[4], st)); b->rr_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_rroc, st));
-  b->rr_made = which;
+  HIPCHK(pass_mark(b, P_RROC, 4, st));
+  HIPCHK(pass_done(b, P_RROC, st, which));
   return QM_OK;
 }
 extern "C" int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n, uint64_t* roc_a, uint64_t* base) {
   if (!b) return fail(QM_E_INVAL, "qm_batch_get_rescue_roc: NULL batch");
-  if (!b->rr_made) return fail(QM_E_STATE, "qm_batch_get_rescue_roc: no qm_batch_rescue_roc behind the latest run of its producers");
-  if ((roc_n && !(b->rr_made & QM_RROC_NORM)) || (roc_a && !(b->rr_made & QM_RROC_ATOM)))
-    return fail(QM_E_STATE, "qm_batch_get_rescue_roc: the latest qm_batch_rescue_roc did not sweep by %s", roc_n && !(b->rr_made & QM_RROC_NORM) ? "normal form" : "atoms");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_rroc));
+  if (pass_ran(b, P_RROC, "qm_batch_get_rescue_roc", "run of its producers") != QM_OK) return QM_E_STATE;
+  if ((roc_n && !(b->pass[P_RROC].made & QM_RROC_NORM)) || (roc_a && !(b->pass[P_RROC].made & QM_RROC_ATOM)))
+    return fail(QM_E_STATE, "qm_batch_get_rescue_roc: the latest qm_batch_rescue_roc did not sweep by %s", roc_n && !(b->pass[P_RROC].made & QM_RROC_NORM) ? "normal form" : "atoms");
+  HIPCHK(pass_result(b, P_RROC));
   const size_t nv = (size_t)b->n_vcf, rows = nv * 3 * (size_t)b->n_bins;
   if (roc_n && nv) HIPCHK(hipMemcpy(roc_n, b->rr_out, rows * 8, hipMemcpyDeviceToHost));
   if (roc_a && nv) HIPCHK(hipMemcpy(roc_a, b->rr_out + rows, rows * 8, hipMemcpyDeviceToHost));
@@ -3317,13 +3271,7 @@ extern "C" int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n, uint64_t* r
   return QM_OK;
 }
 extern "C" int qm_batch_rescue_roc_timings(qm_batch* b, float* ms4) {
-  if (!b || !ms4) return fail(QM_E_INVAL, "qm_batch_rescue_roc_timings: NULL");
-  if (!b->rr_made) return fail(QM_E_STATE, "qm_batch_rescue_roc_timings: no qm_batch_rescue_roc behind the latest run of its producers");
-  if (!b->rr_timed) return fail(QM_E_STATE, "qm_batch_rescue_roc_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_rrt[4]));
-  for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(ms4 + i, b->ev_rrt[i], b->ev_rrt[i + 1]));
-  return QM_OK;
+  return pass_timings(b, P_RROC, "qm_batch_rescue_roc_timings", "run of its producers", ms4);
 }
 // ---- TP, FP and FN by variant type and size ----
 extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t* len, const uint32_t* head, const uint32_t* tail,
@@ -3344,9 +3292,9 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
   int rc = truths_live(b, "qm_batch_types");
   if (rc != QM_OK) return rc;
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_types, &st);
+  rc = pass_open(b, P_TYPES, stream, &st);
   if (rc != QM_OK) return rc;
-  b->ty_made = 0;   // from here on the outputs are rewritten
+  b->pass[P_TYPES].made = 0;   // from here on the outputs are rewritten
   TypeBins B;
   memset(&B, 0, sizeof B);
   for (int i = 0; i < n_bins; ++i) B.edges[i] = edges[i];
@@ -3367,9 +3315,7 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
   if (rc == QM_OK && ns) rc = b->ty_shapes.grow((int64_t)(3 * ns), &b->dev_bytes);
   if (rc == QM_OK && (what & QM_TYPE_COLUMNS)) rc = b->ty_row.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_tyt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->ty_timed = false;
+  HIPCHK(pass_marks(b, P_TYPES));
   std::vector<TypeVcf> vcfs(std::max<size_t>(nv, 1));
   memset(vcfs.data(), 0, vcfs.size() * sizeof(TypeVcf));
   size_t bo = 0;
@@ -3380,7 +3326,7 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
     bo += (size_t)(t.xn / 32 + 1);
   }
   // blocking copies: vcfs dies here, and the caller's shape arrays are read during the call only (the previous call of the pass
-  // is done: pass_stream waited for it)
+  // is done: pass_open waited for it)
   if (nv) HIPCHK(hipMemcpy(b->ty_vcfs, vcfs.data(), nv * sizeof(TypeVcf), hipMemcpyHostToDevice));
   TypeShapes S;
   memset(&S, 0, sizeof S);
@@ -3395,7 +3341,7 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
   HIPCHK(hipMemsetAsync(b->ty_rec, 0, std::max<size_t>(nv * cells, 1) * 8, st));
   HIPCHK(hipMemsetAsync(b->ty_tru, 0, std::max<size_t>(nv * cells, 1) * 8, st));
   if (what & QM_TYPE_COLUMNS) HIPCHK(hipMemsetAsync(b->ty_row, 0, std::max<size_t>(np, 1), st));
-  if (T) HIPCHK(hipEventRecord(b->ev_tyt[0], st));
+  HIPCHK(pass_mark(b, P_TYPES, 0, st));
   TypeRecParams P;
   memset(&P, 0, sizeof P);
   P.spans = b->d_spans; P.vcfs = b->ty_vcfs;
@@ -3407,48 +3353,37 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
   P.n_spans = (int32_t)b->L.spans.size();
   launch_type_records(P, st);
   HIPCHK(hipGetLastError());
-  if (T) HIPCHK(hipEventRecord(b->ev_tyt[1], st));
+  HIPCHK(pass_mark(b, P_TYPES, 1, st));
   TypeTruthParams Q;
   memset(&Q, 0, sizeof Q);
   Q.vcfs = b->ty_vcfs; Q.tru = b->ty_tru; Q.shapes = S; Q.bins = B;
   launch_type_truth(Q, (int)nv, max_entries, st);
   HIPCHK(hipGetLastError());
-  if (T) { HIPCHK(hipEventRecord(b->ev_tyt[2], st)); b->ty_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_types, st));
+  HIPCHK(pass_mark(b, P_TYPES, 2, st));
+  HIPCHK(pass_done(b, P_TYPES, st, 1u | what));
   b->ty_rows = B.n_rows;
-  b->ty_made = 1u | what;
   return QM_OK;
 }
 extern "C" int qm_batch_get_types(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_types: NULL batch");
-  if (!b->ty_made) return fail(QM_E_STATE, "qm_batch_get_types: no qm_batch_types behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_types));
+  NEED_PASS(b, P_TYPES, "qm_batch_get_types");
+  HIPCHK(pass_result(b, P_TYPES));
   const size_t bytes = (size_t)b->n_vcf * 2 * (size_t)b->ty_rows * 8;
   if (rec && bytes) HIPCHK(hipMemcpy(rec, b->ty_rec, bytes, hipMemcpyDeviceToHost));
   if (tru && bytes) HIPCHK(hipMemcpy(tru, b->ty_tru, bytes, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_typed(qm_batch* b, int v, uint8_t* row) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_typed: NULL batch");
-  if (!b->ty_made) return fail(QM_E_STATE, "qm_batch_get_typed: no qm_batch_types behind the latest run");
+  NEED_PASS(b, P_TYPES, "qm_batch_get_typed");
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_typed: VCF %d (the batch has %d)", v, b->n_vcf);
-  if (!(b->ty_made & QM_TYPE_COLUMNS))
+  if (!(b->pass[P_TYPES].made & QM_TYPE_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_get_typed: the latest qm_batch_types did not keep the row bytes (QM_TYPE_COLUMNS)");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_types));
+  HIPCHK(pass_result(b, P_TYPES));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   if (d.n && row) HIPCHK(hipMemcpy(row, b->ty_row + d.off, (size_t)d.n, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_types_timings(qm_batch* b, float* ms2) {
-  if (!b || !ms2) return fail(QM_E_INVAL, "qm_batch_types_timings: NULL");
-  if (!b->ty_made) return fail(QM_E_STATE, "qm_batch_types_timings: no qm_batch_types behind the latest run");
-  if (!b->ty_timed) return fail(QM_E_STATE, "qm_batch_types_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_tyt[2]));
-  for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(ms2 + i, b->ev_tyt[i], b->ev_tyt[i + 1]));
-  return QM_OK;
+  return pass_timings(b, P_TYPES, "qm_batch_types_timings", "run", ms2);
 }
 // ---- clusters of records matched by replayed haplotype ----
 // The pool words of one site table: [elo | ehi | esite | slo | shi][xn], sfirst[xn + 1], n_sites[2], ewhy[xn] as bytes
@@ -3481,47 +3416,34 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   if (b->n_vcf > 65535) return fail(QM_E_RANGE, "qm_batch_haplotypes: %d VCFs (at most 65535 in one batch)", b->n_vcf);
   qm_ctx* c = b->ctx;
   const size_t nv = (size_t)b->n_vcf;
-  for (size_t v = 0; v < nv; ++v) {
-    const int gid = genome_id_per_vcf[v];
-    if (gid < -1 || gid >= (int)c->genomes.size()) return fail(QM_E_INVAL, "qm_batch_haplotypes: VCF %zu names genome %d (have %zu)", v, gid, c->genomes.size());
-    if (gid >= 0 && c->genomes[(size_t)gid].released) return fail(QM_E_STATE, "qm_batch_haplotypes: VCF %zu names released genome %d", v, gid);
-  }
-  int rc = truths_live(b, "qm_batch_haplotypes");
+  int rc = genomes_named(c, "qm_batch_haplotypes", genome_id_per_vcf, b->n_vcf);
+  if (rc == QM_OK) rc = truths_live(b, "qm_batch_haplotypes");
   if (rc != QM_OK) return rc;
   // one site table per truth set: the VCFs that share one must name one genome
-  struct Pair { int truth, genome; size_t first_vcf, off; };
-  std::vector<Pair> pairs;
-  std::vector<int> pair_of(nv, -1);
+  std::vector<TruthTab> pairs;
+  std::vector<int> pair_of;
   size_t pool_words = 0, bit_words = 0;
+  rc = tabs_by_truth(b, "qm_batch_haplotypes", "the sites of a truth set belong to one genome", genome_id_per_vcf,
+                     [](const Truth& t) { return hap_pool_words(t.xn); }, &pairs, &pair_of, &pool_words);
+  if (rc != QM_OK) return rc;
   int64_t max_entries = 0;
-  std::vector<int64_t> eoff(nv + 1, 0);   // (committed with hp_made: a call refused below leaves the previous call's offsets)
+  std::vector<int64_t> eoff(nv + 1, 0);   // (committed with what the pass made: a call refused below leaves the previous call's offsets)
   for (size_t v = 0; v < nv; ++v) {
-    const int gid = genome_id_per_vcf[v], tid = b->L.vcfs[v].truth;
     eoff[v + 1] = eoff[v];
-    if (gid < 0) continue;
-    const int64_t xn = c->truths[(size_t)tid].xn;
-    size_t k = 0;
-    while (k < pairs.size() && pairs[k].truth != tid) ++k;
-    if (k == pairs.size()) {
-      pairs.push_back(Pair{tid, gid, v, pool_words});
-      pool_words += hap_pool_words(xn);
-    } else if (pairs[k].genome != gid) {
-      return fail(QM_E_INVAL, "qm_batch_haplotypes: VCF %zu and VCF %zu share truth set %d and name genomes %d and %d (the sites of a truth set belong to one genome)",
-                  pairs[k].first_vcf, v, tid, pairs[k].genome, gid);
-    }
-    pair_of[v] = (int)k;
+    if (pair_of[v] < 0) continue;
+    const int64_t xn = c->truths[(size_t)b->L.vcfs[v].truth].xn;
     bit_words += 3 * (size_t)(xn / 32 + 1);
     max_entries = std::max(max_entries, xn);
     eoff[v + 1] += xn;
   }
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_haplo, &st);
+  rc = pass_open(b, P_HAPLO, stream, &st);
   if (rc != QM_OK) return rc;
   // A search behind the previous call (qm_batch_hapsubsets, maybe on another stream) reads what this call rewrites, regrows and
   // copies over from the host: it is waited for here, not only on the stream.
-  if (b->ev_hapsub) HIPCHK(hipEventSynchronize(b->ev_hapsub));
-  b->hp_made = 0;   // from here on the outputs are rewritten
-  b->hs_made = 0;   // ... and the search's results belong to the call before
+  if (b->pass[P_HAPSUB].done) HIPCHK(hipEventSynchronize(b->pass[P_HAPSUB].done));
+  b->pass[P_HAPLO].made = 0;   // from here on the outputs are rewritten
+  b->pass[P_HAPSUB].made = 0;   // ... and the search's results belong to the call before
   const size_t np = (size_t)b->L.n_pad;
   const bool cols = (what & QM_HAP_COLUMNS) != 0;
   rc = b->hp_pool.grow((int64_t)std::max<size_t>(pool_words, 1), &b->dev_bytes);
@@ -3534,10 +3456,8 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   if (rc == QM_OK) rc = b->hp_site.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
   if (rc == QM_OK && cols) rc = b->hp_ecls.grow(std::max<int64_t>(eoff[nv], 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_hpt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->hp_timed = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_hpt[0], st));
+  HIPCHK(pass_marks(b, P_HAPLO));
+  HIPCHK(pass_mark(b, P_HAPLO, 0, st));
   std::vector<HapSites> tabs(pairs.size());
   for (size_t k = 0; k < pairs.size(); ++k) {
     tabs[k] = hap_sites(c->truths[(size_t)pairs[k].truth], c->genomes[(size_t)pairs[k].genome], gap, b->hp_pool + pairs[k].off);
@@ -3567,7 +3487,7 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   HIPCHK(hipMemsetAsync(b->hp_total, 0, 8, st));
   HIPCHK(hipMemsetAsync(b->hp_cls, 0, std::max<size_t>(np, 1), st));
   HIPCHK(hipMemsetAsync(b->hp_site, 0xff, std::max<size_t>(np, 1) * 4, st));
-  if (T) HIPCHK(hipEventRecord(b->ev_hpt[1], st));
+  HIPCHK(pass_mark(b, P_HAPLO, 1, st));
   HapRecParams P;
   memset(&P, 0, sizeof P);
   P.spans = b->d_spans; P.vcfs = b->hp_vcfs;
@@ -3577,7 +3497,7 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   P.n_spans = (int32_t)b->L.spans.size();
   launch_hap_records(P, st);
   HIPCHK(hipGetLastError());
-  if (T) HIPCHK(hipEventRecord(b->ev_hpt[2], st));
+  HIPCHK(pass_mark(b, P_HAPLO, 2, st));
   launch_hap_truth(b->hp_vcfs, (int)nv, max_entries, b->hp_tru, b->hp_total, st);
   HIPCHK(hipGetLastError());
   // the one blocking readback of the pass: how many (VCF, open site) pairs there are sizes their lists
@@ -3587,12 +3507,12 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   if (n_pairs > (unsigned long long)(0x7fffffff / HAP_PAIR_WORDS)) return fail(QM_E_RANGE, "qm_batch_haplotypes: %llu (VCF, open site) pairs", n_pairs);
   rc = b->hp_pairs.grow((int64_t)std::max<size_t>((size_t)n_pairs * HAP_PAIR_WORDS, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  if (T) HIPCHK(hipEventRecord(b->ev_hpt[3], st));
+  HIPCHK(pass_mark(b, P_HAPLO, 3, st));
   P.pairs = b->hp_pairs;
   // (also without a pair: the pending lines of sites whose entries are all found become LONE there; no list is touched then)
   launch_hap_claim(P, (int)nv, max_entries, st);
   HIPCHK(hipGetLastError());
-  if (T) HIPCHK(hipEventRecord(b->ev_hpt[4], st));
+  HIPCHK(pass_mark(b, P_HAPLO, 4, st));
   HapReplayParams Q;
   memset(&Q, 0, sizeof Q);
   Q.vcfs = b->hp_vcfs;
@@ -3601,33 +3521,28 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   Q.pairs = b->hp_pairs; Q.n_pairs = (int64_t)n_pairs;
   launch_hap_replay(Q, st);
   HIPCHK(hipGetLastError());
-  if (T) { HIPCHK(hipEventRecord(b->ev_hpt[5], st)); b->hp_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_haplo, st));
-  b->hp_made = 1u | what;
+  HIPCHK(pass_mark(b, P_HAPLO, 5, st));
+  HIPCHK(pass_done(b, P_HAPLO, st, 1u | what));
   b->hp_eoff = eoff;
   b->hp_gids.assign(genome_id_per_vcf, genome_id_per_vcf + nv);
   b->hp_npairs = (int64_t)n_pairs;
   return QM_OK;
 }
 extern "C" int qm_batch_get_haplotypes(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_haplotypes: NULL batch");
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_haplotypes: no qm_batch_haplotypes behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_haplo));
+  NEED_PASS(b, P_HAPLO, "qm_batch_get_haplotypes");
+  HIPCHK(pass_result(b, P_HAPLO));
   const size_t nv = (size_t)b->n_vcf;
   if (rec && nv) HIPCHK(hipMemcpy(rec, b->hp_rec, nv * HAP_R_COLS * 8, hipMemcpyDeviceToHost));
   if (tru && nv) HIPCHK(hipMemcpy(tru, b->hp_tru, nv * HAP_T_COLS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_haplotyped(qm_batch* b, int v, uint8_t* cls, int32_t* site, uint8_t* entry_cls) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_haplotyped: NULL batch");
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_haplotyped: no qm_batch_haplotypes behind the latest run");
+  NEED_PASS(b, P_HAPLO, "qm_batch_get_haplotyped");
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_haplotyped: VCF %d (the batch has %d)", v, b->n_vcf);
   if (!b->hp_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_haplotyped: VCF %d named no genome in the latest qm_batch_haplotypes", v);
-  if (!(b->hp_made & QM_HAP_COLUMNS))
+  if (!(b->pass[P_HAPLO].made & QM_HAP_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_get_haplotyped: the latest qm_batch_haplotypes did not keep the columns (QM_HAP_COLUMNS)");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_haplo));
+  HIPCHK(pass_result(b, P_HAPLO));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   const size_t n = (size_t)d.n, ne = (size_t)(b->hp_eoff[(size_t)v + 1] - b->hp_eoff[(size_t)v]);
   if (cls && n) HIPCHK(hipMemcpy(cls, b->hp_cls + d.off, n, hipMemcpyDeviceToHost));
@@ -3636,21 +3551,15 @@ extern "C" int qm_batch_get_haplotyped(qm_batch* b, int v, uint8_t* cls, int32_t
   return QM_OK;
 }
 extern "C" int qm_batch_haplotype_timings(qm_batch* b, float* ms5) {
-  if (!b || !ms5) return fail(QM_E_INVAL, "qm_batch_haplotype_timings: NULL");
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_haplotype_timings: no qm_batch_haplotypes behind the latest run");
-  if (!b->hp_timed) return fail(QM_E_STATE, "qm_batch_haplotype_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_hpt[5]));
-  for (int i = 0; i < 5; ++i) HIPCHK(hipEventElapsedTime(ms5 + i, b->ev_hpt[i], b->ev_hpt[i + 1]));
-  return QM_OK;
+  return pass_timings(b, P_HAPLO, "qm_batch_haplotype_timings", "run", ms5);
 }
 // ---- a subset search inside the mismatched sites of the haplotype pass ----
 extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   NEED_FINISHED(b, "qm_batch_hapsubsets");
   if (what & ~(QM_HAPSUB_COLUMNS | QM_HAPSUB_NARROW_HASH)) return fail(QM_E_INVAL, "qm_batch_hapsubsets: what = %u", what);
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_hapsubsets: no qm_batch_haplotypes behind the latest run");
+  if (pass_ran(b, P_HAPLO, "qm_batch_hapsubsets") != QM_OK) return QM_E_STATE;
   const bool cols = (what & QM_HAPSUB_COLUMNS) != 0;
-  if (cols && !(b->hp_made & QM_HAP_COLUMNS))
+  if (cols && !(b->pass[P_HAPLO].made & QM_HAP_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_hapsubsets: QM_HAPSUB_COLUMNS needs the columns of the latest qm_batch_haplotypes (QM_HAP_COLUMNS)");
   qm_ctx* c = b->ctx;
   const size_t nv = (size_t)b->n_vcf;
@@ -3662,9 +3571,9 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   int rc = truths_live(b, "qm_batch_hapsubsets");
   if (rc != QM_OK) return rc;
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_hapsub, &st);
+  rc = pass_open(b, P_HAPSUB, stream, &st);
   if (rc != QM_OK) return rc;
-  b->hs_made = 0;   // from here on the outputs are rewritten
+  b->pass[P_HAPSUB].made = 0;   // from here on the outputs are rewritten
   b->hs_listed = false;
   const size_t np = (size_t)b->L.n_pad, npairs = (size_t)b->hp_npairs, ne = (size_t)b->hp_eoff[nv];
   rc = b->hs_sub.grow((int64_t)std::max<size_t>(nv * HAPSUB_COLS, 1), &b->dev_bytes);
@@ -3672,11 +3581,9 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   if (rc == QM_OK && cols) rc = b->hs_cls.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
   if (rc == QM_OK && cols) rc = b->hs_ecls.grow((int64_t)std::max<size_t>(ne, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_hst) if (!e) HIPCHK(hipEventCreate(&e));
-  b->hs_timed = false;
-  HIPCHK(hipStreamWaitEvent(st, b->ev_haplo, 0));   // the pass may have run on another stream
-  if (T) HIPCHK(hipEventRecord(b->ev_hst[0], st));
+  HIPCHK(pass_marks(b, P_HAPSUB));
+  HIPCHK(hipStreamWaitEvent(st, b->pass[P_HAPLO].done, 0));   // the pass may have run on another stream
+  HIPCHK(pass_mark(b, P_HAPSUB, 0, st));
   HIPCHK(hipMemsetAsync(b->hs_res, 0, std::max<size_t>(npairs, 1) * 4, st));
   if (cols) {
     HIPCHK(hipMemcpyAsync(b->hs_cls, b->hp_cls, std::max<size_t>(np, 1), hipMemcpyDeviceToDevice, st));
@@ -3694,33 +3601,28 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   P.n_vcf = (int32_t)nv; P.narrow = (what & QM_HAPSUB_NARROW_HASH) ? 1 : 0;
   launch_hap_subsets(P, st);
   HIPCHK(hipGetLastError());
-  if (T) { HIPCHK(hipEventRecord(b->ev_hst[1], st)); b->hs_timed = true; }
-  HIPCHK(hipEventRecord(b->ev_hapsub, st));
-  b->hs_made = 1u | what;
+  HIPCHK(pass_mark(b, P_HAPSUB, 1, st));
+  HIPCHK(pass_done(b, P_HAPSUB, st, 1u | what));
   return QM_OK;
 }
 extern "C" int qm_batch_get_hapsubsets(qm_batch* b, uint64_t* sub) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_hapsubsets: NULL batch");
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsets: no qm_batch_haplotypes behind the latest run");
-  if (!b->hs_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsets: no qm_batch_hapsubsets behind the latest qm_batch_haplotypes");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_hapsub));
+  NEED_PASS(b, P_HAPLO, "qm_batch_get_hapsubsets");
+  if (pass_ran(b, P_HAPSUB, "qm_batch_get_hapsubsets", "qm_batch_haplotypes") != QM_OK) return QM_E_STATE;
+  HIPCHK(pass_result(b, P_HAPSUB));
   const size_t nv = (size_t)b->n_vcf;
   if (sub && nv) HIPCHK(hipMemcpy(sub, b->hs_sub, nv * HAPSUB_COLS * 8, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_hapsubsetted(qm_batch* b, int v, uint8_t* cls_s, uint8_t* entry_cls_s, int32_t* site_s, uint8_t* smask, uint8_t* tmask,
                                          int64_t capacity, int64_t* n_out) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: NULL batch");
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: no qm_batch_haplotypes behind the latest run");
-  if (!b->hs_made) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: no qm_batch_hapsubsets behind the latest qm_batch_haplotypes");
+  NEED_PASS(b, P_HAPLO, "qm_batch_get_hapsubsetted");
+  if (pass_ran(b, P_HAPSUB, "qm_batch_get_hapsubsetted", "qm_batch_haplotypes") != QM_OK) return QM_E_STATE;
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: VCF %d (the batch has %d)", v, b->n_vcf);
   if (capacity < 0) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: capacity %lld", (long long)capacity);
   if (!b->hp_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: VCF %d named no genome in the latest qm_batch_haplotypes", v);
-  if ((cls_s || entry_cls_s) && !(b->hs_made & QM_HAPSUB_COLUMNS))
+  if ((cls_s || entry_cls_s) && !(b->pass[P_HAPSUB].made & QM_HAPSUB_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: the latest qm_batch_hapsubsets did not keep the columns (QM_HAPSUB_COLUMNS)");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_hapsub));
+  HIPCHK(pass_result(b, P_HAPSUB));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   const size_t n = (size_t)d.n, ne = (size_t)(b->hp_eoff[(size_t)v + 1] - b->hp_eoff[(size_t)v]);
   if (cls_s && n) HIPCHK(hipMemcpy(cls_s, b->hs_cls + d.off, n, hipMemcpyDeviceToHost));
@@ -3758,13 +3660,8 @@ extern "C" int qm_batch_get_hapsubsetted(qm_batch* b, int v, uint8_t* cls_s, uin
 }
 extern "C" int qm_batch_hapsubset_timings(qm_batch* b, float* ms1) {
   if (!b || !ms1) return fail(QM_E_INVAL, "qm_batch_hapsubset_timings: NULL");
-  if (!b->hp_made) return fail(QM_E_STATE, "qm_batch_hapsubset_timings: no qm_batch_haplotypes behind the latest run");
-  if (!b->hs_made) return fail(QM_E_STATE, "qm_batch_hapsubset_timings: no qm_batch_hapsubsets behind the latest qm_batch_haplotypes");
-  if (!b->hs_timed) return fail(QM_E_STATE, "qm_batch_hapsubset_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_hst[1]));
-  HIPCHK(hipEventElapsedTime(ms1, b->ev_hst[0], b->ev_hst[1]));
-  return QM_OK;
+  if (pass_ran(b, P_HAPLO, "qm_batch_hapsubset_timings") != QM_OK) return QM_E_STATE;
+  return pass_timings(b, P_HAPSUB, "qm_batch_hapsubset_timings", "qm_batch_haplotypes", ms1);
 }
 extern "C" int qm_truth_sites(qm_ctx* c, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
                               int64_t* n_out) {
@@ -3777,16 +3674,13 @@ extern "C" int qm_truth_sites(qm_ctx* c, int truth_id, int genome_id, int gap, i
   HIPCHK(hipSetDevice(c->dev));
   const Truth& t = c->truths[(size_t)truth_id];
   const size_t xn = (size_t)t.xn;
-  uint32_t* pool = nullptr;
-  DALLOC(pool, hap_pool_words(t.xn));
-  const HapSites S = hap_sites(t, c->genomes[(size_t)genome_id], gap, pool);
   std::vector<int32_t> h(3 * xn + 3);   // slo | shi | sfirst[xn + 1] | n_sites
-  int rc = hap_build(S, c->stream);
-  hipError_t e = rc == QM_OK ? hipStreamSynchronize(c->stream) : hipSuccess;
-  if (rc == QM_OK && e == hipSuccess) e = hipMemcpy(h.data(), S.slo, (3 * xn + 3) * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(pool);
+  const int rc = build_and_read(c, "qm_truth_sites", hap_pool_words(t.xn), h.data(), h.size() * 4, [&](uint32_t* pool, const void** src) {
+    const HapSites S = hap_sites(t, c->genomes[(size_t)genome_id], gap, pool);
+    *src = S.slo;
+    return hap_build(S, c->stream);
+  });
   if (rc != QM_OK) return rc;
-  if (e != hipSuccess) return fail(QM_E_HIP, "qm_truth_sites: %s", hipGetErrorString(e));
   const int64_t ns = h[3 * xn + 1];
   *n_out = ns;
   if (ns > capacity) return fail(QM_E_RANGE, "qm_truth_sites: %lld sites, room for %lld", (long long)ns, (long long)capacity);
@@ -3815,15 +3709,15 @@ extern "C" int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t
   if (!what || (what & ~(QM_BOOT_RECORDS | QM_BOOT_TRUTH))) return fail(QM_E_INVAL, "qm_batch_boot: what = %u", what);
   if (what & QM_BOOT_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_boot: allele-extended batches have no truth-side bitmaps (QM_BOOT_RECORDS only)");
-    if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_boot: QM_BOOT_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_boot: QM_BOOT_TRUTH needs a qm_batch_truth_hits behind the latest run");
     const int rc = truths_live(b, "qm_batch_boot");
     if (rc != QM_OK) return rc;
   }
   hipStream_t st;
-  int rc = pass_stream(b, stream, &b->ev_boot, &st);
+  int rc = pass_open(b, P_BOOT, stream, &st);
   if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf;
-  b->boot_made = 0;
+  b->pass[P_BOOT].made = 0;
   const size_t cw = nv * (size_t)(n_win + 2) * BOOT_COLS, rw = nv * (size_t)n_rep * BOOT_COLS;
   rc = b->d_bcnt.grow((int64_t)std::max<size_t>(cw, 1), &b->dev_bytes);
   if (rc == QM_OK && n_rep) rc = b->d_brep.grow((int64_t)std::max<size_t>(rw, 1), &b->dev_bytes);
@@ -3847,24 +3741,21 @@ extern "C" int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t
       rows[v].hits = b->d_hits + b->h_hit_off[v];
       rows[v].n = b->h_hit_tn[v];   // T' as the hit bitmaps were sized
     }
-    HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
     HIPCHK(hipMemcpy(b->d_brows, rows.data(), nv * sizeof(BootTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
     launch_boot_truth(b->d_brows, (int)nv, window, n_win, b->d_bcnt, st);
     HIPCHK(hipGetLastError());
   }
   launch_boot_resample(b->d_bcnt, (int)nv, n_win, n_rep, seed, b->d_brep, st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(b->ev_boot, st));
+  HIPCHK(pass_done(b, P_BOOT, st, what));
   b->boot_nwin = n_win;
   b->boot_nrep = n_rep;
-  b->boot_made = what;
   return QM_OK;
 }
 extern "C" int qm_batch_get_boot(qm_batch* b, uint64_t* cnt, uint64_t* rep) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_boot: NULL batch");
-  if (!b->boot_made) return fail(QM_E_STATE, "qm_batch_get_boot: no qm_batch_boot behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_boot));
+  NEED_PASS(b, P_BOOT, "qm_batch_get_boot");
+  HIPCHK(pass_result(b, P_BOOT));
   const size_t nv = (size_t)b->n_vcf;
   if (cnt && nv) HIPCHK(hipMemcpy(cnt, b->d_bcnt, nv * (size_t)(b->boot_nwin + 2) * BOOT_COLS * 8, hipMemcpyDeviceToHost));
   if (rep && nv && b->boot_nrep) HIPCHK(hipMemcpy(rep, b->d_brep, nv * (size_t)b->boot_nrep * BOOT_COLS * 8, hipMemcpyDeviceToHost));
@@ -3892,11 +3783,11 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
     }
   }
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
-  if (!b->ev_truth) HIPCHK(hipEventCreateWithFlags(&b->ev_truth, hipEventDisableTiming));
-  else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // an earlier pass, on whatever stream, still writes the same buffers
-  rc = wait_passes(b, st, false, true);   // and the passes that read the hit bitmaps, on whatever stream (PASS_EVENTS)
+  if (!b->pass[P_TRUTH].done) HIPCHK(hipEventCreateWithFlags(&b->pass[P_TRUTH].done, hipEventDisableTiming));
+  else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // an earlier pass, on whatever stream, still writes the same buffers
+  rc = wait_passes(b, st, false, true);   // and the passes that read the hit bitmaps, on whatever stream (PASSES)
   if (rc != QM_OK) return rc;
-  // (the one pass that does not open with pass_stream: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
+  // (the one pass that does not open with pass_open: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
   rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_intruth.grow((int64_t)mask_words, &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_hits.grow((int64_t)hw, &b->dev_bytes);
@@ -3918,29 +3809,23 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   P.n_spans = (int32_t)b->L.spans.size();
   launch_truth_hits(P, st);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(b->ev_truth, st));
+  HIPCHK(pass_done(b, P_TRUTH, st, 1));
   b->hits_enqueued = true;
-  b->hits_valid = true;
   return QM_OK;
 }
-#define NEED_HITS(b, name) \
-  if (!(b)) return fail(QM_E_INVAL, name ": NULL batch"); \
-  if (!(b)->hits_valid) return fail(QM_E_STATE, name ": no qm_batch_truth_hits behind the latest run")
 extern "C" int qm_batch_get_truth_hits(qm_batch* b, int v, uint32_t* bits, int64_t n_words) {
-  NEED_HITS(b, "qm_batch_get_truth_hits");
+  NEED_PASS(b, P_TRUTH, "qm_batch_get_truth_hits");
   if (v < 0 || v >= b->n_vcf || (!bits && n_words)) return fail(QM_E_INVAL, "qm_batch_get_truth_hits: bad arguments");
   const int64_t have = b->h_hit_off[(size_t)v + 1] - b->h_hit_off[(size_t)v];
   if (n_words != have) return fail(QM_E_INVAL, "qm_batch_get_truth_hits: VCF %d has %lld words, not %lld", v, (long long)have, (long long)n_words);
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_truth));
+  HIPCHK(pass_result(b, P_TRUTH));
   if (have) HIPCHK(hipMemcpy(bits, b->d_hits + b->h_hit_off[(size_t)v], (size_t)have * 4, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_intruth_mask(qm_batch* b, int v, uint64_t* mask) {
-  NEED_HITS(b, "qm_batch_get_intruth_mask");
+  NEED_PASS(b, P_TRUTH, "qm_batch_get_intruth_mask");
   if (v < 0 || v >= b->n_vcf || !mask) return fail(QM_E_INVAL, "qm_batch_get_intruth_mask: bad arguments");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_truth));
+  HIPCHK(pass_result(b, P_TRUTH));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   const size_t nw = (size_t)((d.n + 63) / 64);
   if (nw) {
@@ -3951,7 +3836,7 @@ extern "C" int qm_batch_get_intruth_mask(qm_batch* b, int v, uint64_t* mask) {
 }
 extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, uint64_t* regions,
                                       uint32_t* union_bits) {
-  NEED_HITS(b, "qm_batch_truth_regions");
+  NEED_PASS(b, P_TRUTH, "qm_batch_truth_regions");
   if (n_groups < 0 || (n_groups && (!group_offsets || !vcf_ids || !regions))) return fail(QM_E_INVAL, "qm_batch_truth_regions: bad arguments");
   if (n_groups == 0) return QM_OK;
   std::vector<TruthGroup> G((size_t)n_groups);
@@ -3968,8 +3853,7 @@ extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* 
     max_words = std::max(max_words, t.words);
   }
   qm_ctx* c = b->ctx;
-  HIPCHK(hipSetDevice(c->dev));
-  HIPCHK(hipEventSynchronize(b->ev_truth));
+  HIPCHK(pass_result(b, P_TRUTH));
   TruthGroup* d_groups = nullptr;
   unsigned long long* d_reg = nullptr;
   uint32_t* d_uni = nullptr;
@@ -3996,7 +3880,7 @@ extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* 
 extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, void* stream) {
   NEED_FINISHED(b, "qm_batch_votes");
   if (b->ext) return fail(QM_E_STATE, "qm_batch_votes: allele-extended batches have no truth-side bitmaps (single-base batches only)");
-  if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_votes: needs a qm_batch_truth_hits behind the latest run");
+  if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_votes: needs a qm_batch_truth_hits behind the latest run");
   int rc = truths_live(b, "qm_batch_votes");
   if (rc != QM_OK) return rc;
   if (n_groups < 0 || (n_groups && (!group_offsets || !vcf_ids))) return fail(QM_E_INVAL, "qm_batch_votes: bad arguments");
@@ -4016,7 +3900,7 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
     max_words = std::max(max_words, t.words);
   }
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_votes, &st);
+  rc = pass_open(b, P_VOTES, stream, &st);
   if (rc != QM_OK) return rc;
   // a group's segment of the pair buffers holds its members' kept lines: the finished n_pass scalars bound the pairs from above
   std::vector<int64_t> sc(std::max<size_t>(nv, 1) * QM_N_SCALARS, 0);
@@ -4052,15 +3936,14 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   if (rc == QM_OK) rc = b->vt_out.grow((int64_t)std::max<size_t>(out_words, 1), &b->dev_bytes);
   // (growing keeps what fits: a call refused up to here leaves the previous pass and its outputs as they were, unless an
   //  array had to be replaced and then could not be)
-  if (rc != QM_OK) { b->votes_valid = false; return rc; }
-  b->votes_valid = false;   // from here on the outputs are rewritten
+  if (rc != QM_OK) { b->pass[P_VOTES].made = 0; return rc; }
+  b->pass[P_VOTES].made = 0;   // from here on the outputs are rewritten
   b->vt_koff.assign(ng + 1, 0);
   for (size_t g = 0; g < ng; ++g) b->vt_koff[g] = segs[g].koff;
   b->vt_koff[ng] = koff;
   b->votes_groups = n_groups;
   if (n_groups == 0) {
-    HIPCHK(hipEventRecord(b->ev_votes, st));
-    b->votes_valid = true;
+    HIPCHK(pass_done(b, P_VOTES, st, 1));
     return QM_OK;
   }
   // blocking copies: the tables die here
@@ -4068,7 +3951,7 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   if (nst) HIPCHK(hipMemcpy(b->vt_tile_seg, tile_seg.data(), (size_t)nst * 4, hipMemcpyHostToDevice));
   if (nv) HIPCHK(hipMemcpy(b->vt_slot, slot.data(), nv * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(b->vt_groups, G.data(), ng * sizeof(VoteGroup), hipMemcpyHostToDevice));
-  HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps and the record mask, on whatever stream they were made
+  HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps and the record mask, on whatever stream they were made
   HIPCHK(hipMemsetAsync(b->vt_out, 0, out_words * 8, st));
   HIPCHK(hipMemsetAsync(b->vt_cursor, 0, 2 * ng * 4, st));
   VoteOut O;
@@ -4077,12 +3960,10 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   O.ptp = O.fp + ng * VT_SLOTS;
   O.pfp = O.ptp + ng * VT_MAX_GROUP;
   O.nokey = O.pfp + ng * VT_MAX_GROUP;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_vt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->vt_timed = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_vt[0], st));
+  HIPCHK(pass_marks(b, P_VOTES));
+  HIPCHK(pass_mark(b, P_VOTES, 0, st));
   launch_vote_truth(b->vt_groups, n_groups, max_words, O, st);
-  if (T) HIPCHK(hipEventRecord(b->ev_vt[1], st));
+  HIPCHK(pass_mark(b, P_VOTES, 1, st));
   VoteKeysParams P;
   P.spans = b->d_spans; P.vcf_slot = b->vt_slot; P.segs = b->vt_segs;
   P.pos = b->pos; P.anib = b->anib; P.flags = b->flags;
@@ -4091,35 +3972,30 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   P.n_spans = (int32_t)b->L.spans.size();
   launch_vote_keys(P, st);
   launch_vote_segs(b->vt_segs, b->vt_cursor, n_groups, st);
-  if (T) HIPCHK(hipEventRecord(b->ev_vt[2], st));
+  HIPCHK(pass_mark(b, P_VOTES, 2, st));
   int cur = 0;
   for (int shift = 0; shift < 32; shift += 8) {
     launch_sort_pass(b->vt_segs, b->vt_tile_seg, n_groups, (int)nst, b->vt_k[cur], nullptr, b->vt_v[cur], shift, b->vt_hist, b->vt_k[cur ^ 1], nullptr,
                      b->vt_v[cur ^ 1], 0, st);
     cur ^= 1;
   }
-  if (T) HIPCHK(hipEventRecord(b->ev_vt[3], st));
+  HIPCHK(pass_mark(b, P_VOTES, 3, st));
   // (four passes: the sorted pairs are back in the first pair of buffers, the second takes the distinct keys and masks)
   launch_vote_runs(b->vt_segs, b->vt_tile_seg, n_groups, (int)nst, b->vt_k[0], b->vt_v[0], b->vt_thd, b->vt_k[1], b->vt_v[1], b->vt_cursor + ng, O, st);
-  if (T) { HIPCHK(hipEventRecord(b->ev_vt[4], st)); b->vt_timed = true; }
+  HIPCHK(pass_mark(b, P_VOTES, 4, st));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(b->ev_votes, st));
-  b->votes_valid = true;
+  HIPCHK(pass_done(b, P_VOTES, st, 1));
   return QM_OK;
 }
 extern "C" int qm_batch_vote_timings(qm_batch* b, float* ms4) {
   if (!b || !ms4) return fail(QM_E_INVAL, "qm_batch_vote_timings: NULL");
-  if (!b->votes_valid || !b->vt_timed) return fail(QM_E_STATE, "qm_batch_vote_timings: timing is off or no qm_batch_votes behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_vt[4]));
-  for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(ms4 + i, b->ev_vt[i], b->ev_vt[i + 1]));
-  return QM_OK;
+  if (!b->pass[P_VOTES].made || !b->pass[P_VOTES].timed)   // (one message for both)
+    return fail(QM_E_STATE, "qm_batch_vote_timings: timing is off or no qm_batch_votes behind the latest run");
+  return pass_timings(b, P_VOTES, "qm_batch_vote_timings", "run", ms4);
 }
 extern "C" int qm_batch_get_votes(qm_batch* b, uint64_t* tp_votes, uint64_t* fp_votes, uint64_t* private_tp, uint64_t* private_fp, int64_t* nokey) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_votes: NULL batch");
-  if (!b->votes_valid) return fail(QM_E_STATE, "qm_batch_get_votes: no qm_batch_votes behind the latest run");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_votes));
+  NEED_PASS(b, P_VOTES, "qm_batch_get_votes");
+  HIPCHK(pass_result(b, P_VOTES));
   const size_t ng = (size_t)b->votes_groups;
   if (!ng) return QM_OK;
   const uint64_t* o = b->vt_out;
@@ -4135,16 +4011,13 @@ extern "C" int qm_batch_get_votes(qm_batch* b, uint64_t* tp_votes, uint64_t* fp_
   return QM_OK;
 }
 extern "C" int qm_batch_vote_groups(qm_batch* b) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_vote_groups: NULL batch");
-  if (!b->votes_valid) return fail(QM_E_STATE, "qm_batch_vote_groups: no qm_batch_votes behind the latest run");
+  NEED_PASS(b, P_VOTES, "qm_batch_vote_groups");
   return b->votes_groups;
 }
 extern "C" int qm_batch_get_vote_keys(qm_batch* b, int group, uint32_t* keys, uint32_t* masks, int64_t capacity, int64_t* n_out) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_vote_keys: NULL batch");
-  if (!b->votes_valid) return fail(QM_E_STATE, "qm_batch_get_vote_keys: no qm_batch_votes behind the latest run");
+  NEED_PASS(b, P_VOTES, "qm_batch_get_vote_keys");
   if (group < 0 || group >= b->votes_groups || capacity < 0) return fail(QM_E_INVAL, "qm_batch_get_vote_keys: group %d (the pass had %d)", group, b->votes_groups);
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_votes));
+  HIPCHK(pass_result(b, P_VOTES));
   uint32_t n = 0;
   HIPCHK(hipMemcpy(&n, b->vt_cursor + (size_t)b->votes_groups + (size_t)group, 4, hipMemcpyDeviceToHost));
   if (n_out) *n_out = (int64_t)n;
@@ -4159,13 +4032,13 @@ extern "C" int qm_batch_get_vote_keys(qm_batch* b, int group, uint32_t* keys, ui
 extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
   NEED_FINISHED(b, "qm_batch_nearmiss");
   if (b->ext) return fail(QM_E_STATE, "qm_batch_nearmiss: allele-extended batches have no truth-side bitmaps (single-base batches only)");
-  if (!b->hits_valid) return fail(QM_E_STATE, "qm_batch_nearmiss: needs a qm_batch_truth_hits behind the latest run");
+  if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_nearmiss: needs a qm_batch_truth_hits behind the latest run");
   if (radius < 0 || radius > QM_NM_MAX_RADIUS) return fail(QM_E_INVAL, "qm_batch_nearmiss: radius %d (0 to %d)", radius, QM_NM_MAX_RADIUS);
   qm_ctx* c = b->ctx;
   int rc = truths_live(b, "qm_batch_nearmiss");
   if (rc != QM_OK) return rc;
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_nm, &st);
+  rc = pass_open(b, P_NEARMISS, stream, &st);
   if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf;
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);   // as d_hits
@@ -4174,13 +4047,13 @@ extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
   if (rc == QM_OK) rc = b->nm_rcls.grow(b->L.n_pad, &b->dev_bytes);
   if (rc == QM_OK) rc = b->nm_out.grow((int64_t)out_words, &b->dev_bytes);
   if (rc == QM_OK) rc = b->nm_tn.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
-  if (rc != QM_OK) { b->nm_valid = false; return rc; }
-  b->nm_valid = false;   // from here on the outputs are rewritten
+  if (rc != QM_OK) { b->pass[P_NEARMISS].made = 0; return rc; }
+  b->pass[P_NEARMISS].made = 0;   // from here on the outputs are rewritten
   if (!b->nm_tn_uploaded && nv) {
     HIPCHK(hipMemcpy(b->nm_tn, b->h_hit_tn.data(), nv * 8, hipMemcpyHostToDevice));
     b->nm_tn_uploaded = true;
   }
-  HIPCHK(hipStreamWaitEvent(st, b->ev_truth, 0));   // the hit bitmaps, on whatever stream they were made
+  HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
   HIPCHK(hipMemsetAsync(b->nm_planes, 0, NM_PLANES * hw * 4, st));
   HIPCHK(hipMemsetAsync(b->nm_out, 0, out_words * 8, st));
   NearmissParams P;
@@ -4190,40 +4063,28 @@ extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
   P.planes = b->nm_planes; P.plane_words = (int64_t)hw; P.rcls = b->nm_rcls;
   P.rec = reinterpret_cast<unsigned long long*>(b->nm_out.p);
   P.n_spans = (int32_t)b->L.spans.size(); P.radius = radius;
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_nmt) if (!e) HIPCHK(hipEventCreate(&e));
-  b->nm_timed = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_nmt[0], st));
+  HIPCHK(pass_marks(b, P_NEARMISS));
+  HIPCHK(pass_mark(b, P_NEARMISS, 0, st));
   launch_nearmiss_records(P, st);
-  if (T) HIPCHK(hipEventRecord(b->ev_nmt[1], st));
+  HIPCHK(pass_mark(b, P_NEARMISS, 1, st));
   NearmissTruthParams Q;
   Q.hit_off = b->d_hit_off; Q.hit_tn = b->nm_tn; Q.hits = b->d_hits; Q.planes = b->nm_planes; Q.plane_words = (int64_t)hw;
   Q.tru = P.rec + std::max<size_t>(nv, 1) * NM_R_CLASSES;
   int64_t max_words = 0;
   for (size_t v = 0; v < nv; ++v) max_words = std::max<int64_t>(max_words, b->h_hit_off[v + 1] - b->h_hit_off[v]);
   launch_nearmiss_truth(Q, b->n_vcf, max_words, st);
-  if (T) { HIPCHK(hipEventRecord(b->ev_nmt[2], st)); b->nm_timed = true; }
+  HIPCHK(pass_mark(b, P_NEARMISS, 2, st));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(b->ev_nm, st));
-  b->nm_valid = true;
+  HIPCHK(pass_done(b, P_NEARMISS, st, 1));
   return QM_OK;
 }
-#define NEED_NEARMISS(b, name) \
-  if (!(b)) return fail(QM_E_INVAL, name ": NULL batch"); \
-  if (!(b)->nm_valid) return fail(QM_E_STATE, name ": no qm_batch_nearmiss behind the latest run")
 extern "C" int qm_batch_nearmiss_timings(qm_batch* b, float* ms2) {
-  NEED_NEARMISS(b, "qm_batch_nearmiss_timings");
-  if (!ms2) return fail(QM_E_INVAL, "qm_batch_nearmiss_timings: NULL");
-  if (!b->nm_timed) return fail(QM_E_STATE, "qm_batch_nearmiss_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_nmt[2]));
-  for (int i = 0; i < 2; ++i) HIPCHK(hipEventElapsedTime(ms2 + i, b->ev_nmt[i], b->ev_nmt[i + 1]));
-  return QM_OK;
+  NEED_PASS(b, P_NEARMISS, "qm_batch_nearmiss_timings");
+  return pass_timings(b, P_NEARMISS, "qm_batch_nearmiss_timings", "run", ms2);
 }
 extern "C" int qm_batch_get_nearmiss(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  NEED_NEARMISS(b, "qm_batch_get_nearmiss");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_nm));
+  NEED_PASS(b, P_NEARMISS, "qm_batch_get_nearmiss");
+  HIPCHK(pass_result(b, P_NEARMISS));
   const size_t nv = (size_t)b->n_vcf;
   if (!nv) return QM_OK;
   if (rec) HIPCHK(hipMemcpy(rec, b->nm_out, nv * NM_R_CLASSES * 8, hipMemcpyDeviceToHost));
@@ -4231,19 +4092,17 @@ extern "C" int qm_batch_get_nearmiss(qm_batch* b, uint64_t* rec, uint64_t* tru) 
   return QM_OK;
 }
 extern "C" int qm_batch_get_nearmiss_cls(qm_batch* b, int v, uint8_t* out) {
-  NEED_NEARMISS(b, "qm_batch_get_nearmiss_cls");
+  NEED_PASS(b, P_NEARMISS, "qm_batch_get_nearmiss_cls");
   if (v < 0 || v >= b->n_vcf || !out) return fail(QM_E_INVAL, "qm_batch_get_nearmiss_cls: bad arguments");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_nm));
+  HIPCHK(pass_result(b, P_NEARMISS));
   const VcfDesc& d = b->L.vcfs[(size_t)v];
   if (d.n) HIPCHK(hipMemcpy(out, b->nm_rcls + d.off, (size_t)d.n, hipMemcpyDeviceToHost));
   return QM_OK;
 }
 extern "C" int qm_batch_get_nearmiss_truth(qm_batch* b, int v, uint8_t* out) {
-  NEED_NEARMISS(b, "qm_batch_get_nearmiss_truth");
+  NEED_PASS(b, P_NEARMISS, "qm_batch_get_nearmiss_truth");
   if (v < 0 || v >= b->n_vcf || !out) return fail(QM_E_INVAL, "qm_batch_get_nearmiss_truth: bad arguments");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_nm));
+  HIPCHK(pass_result(b, P_NEARMISS));
   const int64_t off = b->h_hit_off[(size_t)v], words = b->h_hit_off[(size_t)v + 1] - off, tn = b->h_hit_tn[(size_t)v];
   if (!words) return QM_OK;
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[(size_t)b->n_vcf], 1);
@@ -4274,7 +4133,7 @@ extern "C" int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t
   int rc = truths_live(b, "qm_batch_surface");
   if (rc != QM_OK) return rc;
   hipStream_t st;
-  rc = pass_stream(b, stream, &b->ev_sf, &st);
+  rc = pass_open(b, P_SURFACE, stream, &st);
   if (rc != QM_OK) return rc;
   const size_t nv = (size_t)b->n_vcf, cells = (size_t)nq * (size_t)na;
   if (b->h_sf_off.empty()) {   // (T' cannot change while the generations truths_live checks hold)
@@ -4283,7 +4142,7 @@ extern "C" int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t
   }
   const size_t nbest = std::max<size_t>((size_t)b->h_sf_off[nv], 1);
   const size_t out_words = std::max<size_t>(nv, 1) * (SF_GRIDS * cells + SF_EXTRA);
-  b->sf_valid = false;   // from here on the outputs are rewritten
+  b->pass[P_SURFACE].made = 0;   // from here on the outputs are rewritten
   rc = b->sf_best.grow((int64_t)nbest, &b->dev_bytes);
   if (rc == QM_OK) rc = b->sf_off.grow((int64_t)nv + 1, &b->dev_bytes);
   if (rc == QM_OK) rc = b->sf_out.grow((int64_t)out_words, &b->dev_bytes);
@@ -4309,38 +4168,26 @@ extern "C" int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t
   P.q_step = q_step; P.nq = nq; P.na = na;
   int64_t max_tn = 0;
   for (size_t v = 0; v < nv; ++v) max_tn = std::max<int64_t>(max_tn, b->h_sf_off[v + 1] - b->h_sf_off[v]);
-  const bool T = b->timing;
-  if (T) for (auto& e : b->ev_sft) if (!e) HIPCHK(hipEventCreate(&e));
-  b->sf_timed = false;
-  if (T) HIPCHK(hipEventRecord(b->ev_sft[0], st));
+  HIPCHK(pass_marks(b, P_SURFACE));
+  HIPCHK(pass_mark(b, P_SURFACE, 0, st));
   launch_surface_records(P, st);
-  if (T) HIPCHK(hipEventRecord(b->ev_sft[1], st));
+  HIPCHK(pass_mark(b, P_SURFACE, 1, st));
   launch_surface_truth(P, b->n_vcf, max_tn, st);
-  if (T) HIPCHK(hipEventRecord(b->ev_sft[2], st));
+  HIPCHK(pass_mark(b, P_SURFACE, 2, st));
   launch_surface_sums(P, b->n_vcf, st);
-  if (T) { HIPCHK(hipEventRecord(b->ev_sft[3], st)); b->sf_timed = true; }
+  HIPCHK(pass_mark(b, P_SURFACE, 3, st));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(b->ev_sf, st));
+  HIPCHK(pass_done(b, P_SURFACE, st, 1));
   b->sf_cells = (int32_t)cells;
-  b->sf_valid = true;
   return QM_OK;
 }
-#define NEED_SURFACE(b, name) \
-  if (!(b)) return fail(QM_E_INVAL, name ": NULL batch"); \
-  if (!(b)->sf_valid) return fail(QM_E_STATE, name ": no qm_batch_surface behind the latest run")
 extern "C" int qm_batch_surface_timings(qm_batch* b, float* ms3) {
-  NEED_SURFACE(b, "qm_batch_surface_timings");
-  if (!ms3) return fail(QM_E_INVAL, "qm_batch_surface_timings: NULL");
-  if (!b->sf_timed) return fail(QM_E_STATE, "qm_batch_surface_timings: timing is off");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_sft[3]));
-  for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms3 + i, b->ev_sft[i], b->ev_sft[i + 1]));
-  return QM_OK;
+  NEED_PASS(b, P_SURFACE, "qm_batch_surface_timings");
+  return pass_timings(b, P_SURFACE, "qm_batch_surface_timings", "run", ms3);
 }
 extern "C" int qm_batch_get_surface(qm_batch* b, uint64_t* S, uint64_t* extra) {
-  NEED_SURFACE(b, "qm_batch_get_surface");
-  HIPCHK(hipSetDevice(b->ctx->dev));
-  HIPCHK(hipEventSynchronize(b->ev_sf));
+  NEED_PASS(b, P_SURFACE, "qm_batch_get_surface");
+  HIPCHK(pass_result(b, P_SURFACE));
   const size_t nv = (size_t)b->n_vcf, gw = (size_t)SF_GRIDS * (size_t)b->sf_cells;
   if (!nv) return QM_OK;
   if (S) HIPCHK(hipMemcpy(S, b->sf_out, nv * gw * 8, hipMemcpyDeviceToHost));

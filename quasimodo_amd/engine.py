@@ -661,6 +661,12 @@ class Batch:
     def finish(self, stream=None):
         self._ck(self._L.qm_batch_finish(self._h, C.c_void_p(stream) if stream else None))
 
+    def _pass_timings(self, entry, names):
+        """the qm_batch_*_timings of one pass: its milliseconds under their names"""
+        ms = (C.c_float * len(names))()
+        self._ck(entry(self._h, ms))
+        return dict(zip(names, ms))
+
     def timings(self):
         ms = (C.c_float * 4)()
         self._ck(self._L.qm_batch_timings(self._h, ms))
@@ -848,9 +854,7 @@ class Batch:
 
     def vote_timings(self):
         """qm_batch_vote_timings (set_timing on): milliseconds of the latest votes() between HIP events, stage by stage"""
-        ms = (C.c_float * 4)()
-        self._ck(self._L.qm_batch_vote_timings(self._h, ms))
-        return {"vote_truth_ms": ms[0], "vote_keys_ms": ms[1], "sort_ms": ms[2], "vote_runs_ms": ms[3]}
+        return self._pass_timings(self._L.qm_batch_vote_timings, ("vote_truth_ms", "vote_keys_ms", "sort_ms", "vote_runs_ms"))
 
     def vote_keys(self, g):
         """qm_batch_get_vote_keys: (ukeys, umasks) uint32 -- the ascending distinct keys pos << 4 | ref << 2 | alt of group g
@@ -881,9 +885,7 @@ class Batch:
 
     def surface_timings(self):
         """qm_batch_surface_timings (set_timing on): milliseconds of the latest surface() between HIP events, kernel by kernel"""
-        ms = (C.c_float * 3)()
-        self._ck(self._L.qm_batch_surface_timings(self._h, ms))
-        return {"surface_records_ms": ms[0], "surface_truth_ms": ms[1], "surface_sums_ms": ms[2]}
+        return self._pass_timings(self._L.qm_batch_surface_timings, ("surface_records_ms", "surface_truth_ms", "surface_sums_ms"))
 
     # -- sequence-context profiles (DESIGN.md 4.16) ----------------------------------
     def context(self, genome_ids, half_window=50, n_gc=10, truth=False, stream=None, fetch=True):
@@ -915,9 +917,7 @@ class Batch:
 
     def context_timings(self):
         """qm_batch_context_timings (set_timing on): milliseconds of the latest context() between HIP events"""
-        ms = (C.c_float * 3)()
-        self._ck(self._L.qm_batch_context_timings(self._h, ms))
-        return {"context_build_ms": ms[0], "context_records_ms": ms[1], "context_truth_ms": ms[2]}
+        return self._pass_timings(self._L.qm_batch_context_timings, ("context_build_ms", "context_records_ms", "context_truth_ms"))
 
     # -- indels and MNPs matched by normal form (DESIGN.md 4.17) ------------------------
     def normalize(self, genome_ids, columns=False, stream=None, fetch=True):
@@ -953,9 +953,7 @@ class Batch:
 
     def normalize_timings(self):
         """qm_batch_normalize_timings (set_timing on): milliseconds of the latest normalize() between HIP events"""
-        ms = (C.c_float * 3)()
-        self._ck(self._L.qm_batch_normalize_timings(self._h, ms))
-        return {"norm_truth_ms": ms[0], "norm_records_ms": ms[1], "norm_found_ms": ms[2]}
+        return self._pass_timings(self._L.qm_batch_normalize_timings, ("norm_truth_ms", "norm_records_ms", "norm_found_ms"))
 
     # -- MNPs matched against adjacent SNVs (DESIGN.md 4.18) ----------------------------
     def atomize(self, columns=False, stream=None, fetch=True):
@@ -982,9 +980,7 @@ class Batch:
 
     def atomize_timings(self):
         """qm_batch_atomize_timings (set_timing on): milliseconds of the latest atomize() between HIP events"""
-        ms = (C.c_float * 3)()
-        self._ck(self._L.qm_batch_atomize_timings(self._h, ms))
-        return {"atom_truth_ms": ms[0], "atom_records_ms": ms[1], "atom_found_ms": ms[2]}
+        return self._pass_timings(self._L.qm_batch_atomize_timings, ("atom_truth_ms", "atom_records_ms", "atom_found_ms"))
 
     # -- TP, FP and FN by variant type and size (DESIGN.md 4.19) ------------------------
     def vartype(self, edges=None, shapes=None, columns=False, stream=None, fetch=True):
@@ -1021,9 +1017,7 @@ class Batch:
 
     def vartype_timings(self):
         """qm_batch_types_timings (set_timing on): milliseconds of the latest vartype() between HIP events"""
-        ms = (C.c_float * 2)()
-        self._ck(self._L.qm_batch_types_timings(self._h, ms))
-        return {"type_records_ms": ms[0], "type_truth_ms": ms[1]}
+        return self._pass_timings(self._L.qm_batch_types_timings, ("type_records_ms", "type_truth_ms"))
 
     # -- clusters of records matched by replayed haplotype (DESIGN.md 4.20) ----------------
     def haplotypes(self, genome_ids, gap=None, columns=False, stream=None, fetch=True):
@@ -1058,9 +1052,7 @@ class Batch:
 
     def haplotype_timings(self):
         """qm_batch_haplotype_timings (set_timing on): milliseconds of the latest haplotypes() between HIP events"""
-        ms = (C.c_float * 5)()
-        self._ck(self._L.qm_batch_haplotype_timings(self._h, ms))
-        return {"hap_sites_ms": ms[0], "hap_records_ms": ms[1], "hap_truth_ms": ms[2], "hap_claim_ms": ms[3], "hap_replay_ms": ms[4]}
+        return self._pass_timings(self._L.qm_batch_haplotype_timings, ("hap_sites_ms", "hap_records_ms", "hap_truth_ms", "hap_claim_ms", "hap_replay_ms"))
 
     # -- a subset search inside the mismatched sites of the haplotype pass (DESIGN.md 4.21) --
     def hapsubsets(self, columns=False, narrow_hash=False, stream=None, fetch=True):
@@ -1095,9 +1087,7 @@ class Batch:
 
     def hapsubset_timings(self):
         """qm_batch_hapsubset_timings (set_timing on): milliseconds of the latest hapsubsets() between HIP events"""
-        ms = (C.c_float * 1)()
-        self._ck(self._L.qm_batch_hapsubset_timings(self._h, ms))
-        return {"hap_subsets_ms": ms[0]}
+        return self._pass_timings(self._L.qm_batch_hapsubset_timings, ("hap_subsets_ms",))
 
     # -- the QUAL ROC under normal-form and atom matching (DESIGN.md 4.22) ---------------
     def rescue_roc(self, which=_lib.QM_RROC_NORM | _lib.QM_RROC_ATOM, stream=None, fetch=True):
@@ -1119,9 +1109,7 @@ class Batch:
 
     def rescue_roc_timings(self):
         """qm_batch_rescue_roc_timings (set_timing on): milliseconds of the latest rescue_roc() between HIP events, kernel by kernel"""
-        ms = (C.c_float * 4)()
-        self._ck(self._L.qm_batch_rescue_roc_timings(self._h, ms))
-        return {"rroc_norm_records_ms": ms[0], "rroc_norm_units_ms": ms[1], "rroc_atom_records_ms": ms[2], "rroc_atom_units_ms": ms[3]}
+        return self._pass_timings(self._L.qm_batch_rescue_roc_timings, ("rroc_norm_records_ms", "rroc_norm_units_ms", "rroc_atom_records_ms", "rroc_atom_units_ms"))
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):
@@ -1139,9 +1127,7 @@ class Batch:
 
     def nearmiss_timings(self):
         """qm_batch_nearmiss_timings (set_timing on): milliseconds of the latest nearmiss() between HIP events, kernel by kernel"""
-        ms = (C.c_float * 2)()
-        self._ck(self._L.qm_batch_nearmiss_timings(self._h, ms))
-        return {"nearmiss_records_ms": ms[0], "nearmiss_truth_ms": ms[1]}
+        return self._pass_timings(self._L.qm_batch_nearmiss_timings, ("nearmiss_records_ms", "nearmiss_truth_ms"))
 
     def nearmiss_classes(self, v):
         """qm_batch_get_nearmiss_cls: uint8[n] -- the class of every FP line of VCF v in input order, 255 for the other records"""
