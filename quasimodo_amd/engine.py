@@ -35,6 +35,28 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+# -- what the _files_<pass> builders make of a spec's lists.  None of these raises: each builder says its own lengths, with the
+# len() of what it was given, before it hands out an array of max(n, 1) entries (never an empty buffer).
+def _want(ws):   # a want list as uint8
+    return _c([int(bool(w)) for w in ws] or [0], np.uint8)
+
+
+def _ids(ids):   # genome or group ids as int32, None as -1
+    return _c([-1 if g is None else int(g) for g in ids] or [-1], np.int32)
+
+
+def _path_array(paths, n):   # n paths (None: no file) as a c_char_p array
+    return (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+
+
+def _rows(n, *shape, dtype=np.uint64):   # the zeroed table the library fills: one row of `shape` per job or group
+    return np.zeros((max(n, 1),) + shape, dtype)
+
+
+def _mixed(wanted, job):   # the job asked for the pass and is no pure-strain sample (whose truth is never read: its row gains nothing)
+    return bool(wanted) and not job.get("pure")
+
+
 class Engine:
     """One context per process and GPU (qm_init).  Raises QmvtError(QM_E_NODEVICE)
     when no HIP device is usable -- there is no CPU path."""
@@ -301,7 +323,7 @@ class Engine:
         ([2]: the distinct forms and the entries of the truth set).
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
-        from .passes import check_atomize, check_haplo, check_hapsub, check_normalize, check_rescueroc, check_shared_call, check_vartype
+        from .passes import check_alleles, check_shared_call
         n = len(file_jobs)
         gids = None if genomes is None else _c([-1 if g is None else int(g) for g in genomes], np.int32)
         if gids is not None and gids.shape[0] != n:
@@ -309,13 +331,9 @@ class Engine:
         if gids is not None and not (gids >= 0).any():
             gids = None
         specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface, "rescueroc": rescue_roc}
-        check_shared_call({name for name, spec in specs.items() if spec is not None})
-        check_normalize({name for name, spec in specs.items() if spec is not None}, alleles)
-        check_atomize({name for name, spec in specs.items() if spec is not None}, alleles)
-        check_vartype({name for name, spec in specs.items() if spec is not None}, alleles)
-        check_haplo({name for name, spec in specs.items() if spec is not None}, alleles)
-        check_hapsub({name for name, spec in specs.items() if spec is not None}, alleles)
-        check_rescueroc({name for name, spec in specs.items() if spec is not None}, alleles)
+        requested = {name for name, spec in specs.items() if spec is not None}
+        check_shared_call(requested)
+        check_alleles(requested, alleles)
         arr = (_lib.FileJob * max(n, 1))()
         enc = lambda p: None if p is None else os.fsencode(p)
         for k, j in enumerate(file_jobs):
@@ -346,22 +364,20 @@ class Engine:
 
     # -- the passes of extract_files: (entry point, its arguments behind the common ones, row k -> what the job's row gains) --
     def _files_motifs(self, n, spec, gids=None, **kw):   # (spec: the genome ids themselves)
-        motifs = np.zeros((max(n, 1), 3, _lib.QM_MOTIF_COLS), np.uint64)
+        motifs = _rows(n, 3, _lib.QM_MOTIF_COLS)
         return self._L.qm_extract_files_motifs, (_p(gids), _p(motifs)), lambda k: {"motifs": motifs[k].copy()}
 
     def _files_profile(self, n, profile, gids=None, **kw):
-        want = _c([int(bool(w)) for w in profile["want"]] or [0], np.uint8)
+        want = _want(profile["want"])
         pts = list(profile.get("points") or [None] * n)
         if (n and want.shape[0] != n) or len(pts) != n:
             raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(profile["want"]), len(pts), n))
         nA, nP = int(profile.get("n_af_bins", 20)), int(profile.get("n_pos_bins", 256))
         if nA < 1 or nP < 1 or nA * nP > _lib.QM_AFP_MAX_CELLS:
             raise ValueError("profile: %d x %d bins (at most %d cells)" % (nA, nP, _lib.QM_AFP_MAX_CELLS))
-        afg = np.zeros((max(n, 1), 2, nA, nP), np.uint64)
-        afx = np.zeros((max(n, 1), 2, _lib.QM_AFP_EXTRA), np.uint64)
-        pt_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in pts])
-        pa = _lib.ProfileArgs(_p(want), int(profile.get("window", 1024)), nP, nA, 0, _p(afg), _p(afx), pt_arr)
-        motifs = None if gids is None else np.zeros((max(n, 1), 3, _lib.QM_MOTIF_COLS), np.uint64)
+        afg, afx = _rows(n, 2, nA, nP), _rows(n, 2, _lib.QM_AFP_EXTRA)
+        pa = _lib.ProfileArgs(_p(want), int(profile.get("window", 1024)), nP, nA, 0, _p(afg), _p(afx), _path_array(pts, n))
+        motifs = None if gids is None else _rows(n, 3, _lib.QM_MOTIF_COLS)
 
         def unpack(k):
             r = {} if motifs is None else {"motifs": motifs[k].copy()}
@@ -369,26 +385,21 @@ class Engine:
         return self._L.qm_extract_files_profile, (_p(gids), _p(motifs), C.byref(pa)), unpack
 
     def _files_truthside(self, n, truthside, **kw):
-        enc = lambda x: None if x is None else os.fsencode(x)
-        grp = _c([-1 if g is None else int(g) for g in truthside["group"]] or [-1], np.int32)
+        grp = _ids(truthside["group"])
         ng = len(truthside.get("missed") or []) or (int(grp.max()) + 1 if n else 0)
         if len(truthside["fn"]) != n or (n and grp.shape[0] != n):
             raise ValueError("truthside: %d fn / %d group entries for %d jobs" % (len(truthside["fn"]), grp.shape[0], n))
-        fn_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in truthside["fn"]])
-        ms_arr = (C.c_char_p * max(ng, 1))(*[enc(x) for x in truthside.get("missed") or [None] * ng])
-        regs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.uint64)
-        fregs = np.zeros((max(ng, 1), _lib.QM_TRUTH_REGIONS), np.int64)
-        ta = _lib.TruthSideArgs(fn_arr, _p(grp), ng, 0, _p(regs), _p(fregs), ms_arr)
+        regs, fregs = _rows(ng, _lib.QM_TRUTH_REGIONS), _rows(ng, _lib.QM_TRUTH_REGIONS, dtype=np.int64)
+        ta = _lib.TruthSideArgs(_path_array(truthside["fn"], n), _p(grp), ng, 0, _p(regs), _p(fregs), _path_array(truthside.get("missed") or [None] * ng, ng))
         unpack = lambda k: {"truth_regions": regs[grp[k]].astype(np.int64), "fp_regions": fregs[grp[k]].copy()} if grp[k] >= 0 else {}
         return self._L.qm_extract_files_truthside, (C.byref(ta),), unpack
 
     def _files_strata(self, n, strata, alleles=False, **kw):
-        swant = _c([int(bool(w)) for w in strata["want"]] or [0], np.uint8)
+        swant = _want(strata["want"])
         if n and swant.shape[0] != n:
             raise ValueError("strata: %d want entries for %d jobs" % (len(strata["want"]), n))
         S = self.strata_info(strata["id"])[0]
-        srec = np.zeros((max(n, 1), S + 2, 3), np.uint64)
-        stru = np.zeros((max(n, 1), S + 1, 2), np.uint64)
+        srec, stru = _rows(n, S + 2, 3), _rows(n, S + 1, 2)
         sa = _lib.StrataArgs(int(strata["id"]), 0, _p(swant), _p(srec), _p(stru))
         unpack = lambda k: {"strata_rec": srec[k].copy(), "strata_tru": None if alleles else stru[k].copy()} if swant[k] else {}
         return self._L.qm_extract_files_strata, (C.byref(sa),), unpack
@@ -396,13 +407,11 @@ class Engine:
     def _files_context(self, n, context, alleles=False, **kw):
         from .context import check_params, n_cells
         w, ng = check_params(context.get("half_window", 50), context.get("n_gc", 10))
-        cgid = _c([-1 if g is None else int(g) for g in context["genomes"]] or [-1], np.int32)
+        cgid = _ids(context["genomes"])
         if n and cgid.shape[0] != n:
             raise ValueError("context: %d genomes entries for %d jobs" % (len(context["genomes"]), n))
         nc = n_cells(ng)
-        crec = np.zeros((max(n, 1), nc + 1, 3), np.uint64)
-        ctru = np.zeros((max(n, 1), nc, 2), np.uint64)
-        cgen = np.zeros((max(n, 1), nc), np.uint64)
+        crec, ctru, cgen = _rows(n, nc + 1, 3), _rows(n, nc, 2), _rows(n, nc)
         ca = _lib.ContextArgs(w, ng, _p(cgid), _p(crec), _p(ctru), _p(cgen))
         ca.keep = cgid   # (read during the call; the other arrays live in unpack)
         unpack = lambda k: {"context_rec": crec[k].copy(), "context_tru": None if alleles else ctru[k].copy(), "context_gen": cgen[k].copy(),
@@ -410,44 +419,35 @@ class Engine:
         return self._L.qm_extract_files_context, (C.byref(ca),), unpack
 
     def _files_normalize(self, n, normalize, file_jobs=(), **kw):
-        ngid = _c([-1 if g is None else int(g) for g in normalize["genomes"]] or [-1], np.int32)
+        ngid = _ids(normalize["genomes"])
         paths = list(normalize.get("rescued") or [None] * n)
         if (n and ngid.shape[0] != n) or len(paths) != n:
             raise ValueError("normalize: %d genomes / %d rescued entries for %d jobs" % (len(normalize["genomes"]), len(paths), n))
-        nrec = np.zeros((max(n, 1), _lib.QM_NORM_R_COLS), np.uint64)
-        ntru = np.zeros((max(n, 1), _lib.QM_NORM_T_COLS), np.uint64)
-        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        nrec, ntru, out_arr = _rows(n, _lib.QM_NORM_R_COLS), _rows(n, _lib.QM_NORM_T_COLS), _path_array(paths, n)
         na = _lib.NormalizeArgs(_p(ngid), _p(nrec), _p(ntru), out_arr)
         na.keep = (ngid, out_arr)   # (read during the call; the other arrays live in unpack)
-        took = lambda k: ngid[k] >= 0 and not file_jobs[k].get("pure")
-        unpack = lambda k: {"norm_rec": nrec[k].copy(), "norm_tru": ntru[k].copy()} if took(k) else {}
+        unpack = lambda k: {"norm_rec": nrec[k].copy(), "norm_tru": ntru[k].copy()} if _mixed(ngid[k] >= 0, file_jobs[k]) else {}
         return self._L.qm_extract_files_normalize, (C.byref(na),), unpack
 
     def _files_atomize(self, n, atomize, **kw):
-        awant = _c([int(bool(w)) for w in atomize["want"]] or [0], np.uint8)
+        awant = _want(atomize["want"])
         paths = list(atomize.get("atoms") or [None] * n)
         if (n and awant.shape[0] != n) or len(paths) != n:
             raise ValueError("atomize: %d want / %d atoms entries for %d jobs" % (len(atomize["want"]), len(paths), n))
-        arec = np.zeros((max(n, 1), _lib.QM_ATOM_R_COLS), np.uint64)
-        atru = np.zeros((max(n, 1), _lib.QM_ATOM_T_COLS), np.uint64)
-        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        arec, atru, out_arr = _rows(n, _lib.QM_ATOM_R_COLS), _rows(n, _lib.QM_ATOM_T_COLS), _path_array(paths, n)
         aa = _lib.AtomizeArgs(_p(awant), _p(arec), _p(atru), out_arr)
         aa.keep = (awant, out_arr)   # (read during the call; the other arrays live in unpack)
         unpack = lambda k: {"atom_rec": arec[k].copy(), "atom_tru": atru[k].copy()} if awant[k] else {}
         return self._L.qm_extract_files_atomize, (C.byref(aa),), unpack
 
     def _files_rescue_roc(self, n, rescue_roc, file_jobs=(), n_bins=256, **kw):
-        rgid = _c([-1 if g is None else int(g) for g in rescue_roc["genomes"]] or [-1], np.int32)
-        rwant = _c([int(bool(w)) for w in rescue_roc["want"]] or [0], np.uint8)
+        rgid, rwant = _ids(rescue_roc["genomes"]), _want(rescue_roc["want"])
         if n and (rgid.shape[0] != n or rwant.shape[0] != n):
             raise ValueError("rescue_roc: %d genomes / %d want entries for %d jobs" % (len(rescue_roc["genomes"]), len(rescue_roc["want"]), n))
-        rn = np.zeros((max(n, 1), 3, n_bins), np.uint64)
-        ra = np.zeros((max(n, 1), 3, n_bins), np.uint64)
-        base = np.zeros((max(n, 1), 2), np.uint64)
+        rn, ra, base = _rows(n, 3, n_bins), _rows(n, 3, n_bins), _rows(n, 2)
         args = _lib.RescueRocArgs(_p(rgid), _p(rwant), _p(rn), _p(ra), _p(base))
         args.keep = (rgid, rwant)   # (read during the call; the other arrays live in unpack)
-        took = lambda k: rwant[k] and not file_jobs[k].get("pure")
-        unpack = lambda k: {"rroc_n": rn[k].copy(), "rroc_a": ra[k].copy(), "rroc_base": base[k].copy()} if took(k) else {}
+        unpack = lambda k: {"rroc_n": rn[k].copy(), "rroc_a": ra[k].copy(), "rroc_base": base[k].copy()} if _mixed(rwant[k], file_jobs[k]) else {}
         return self._L.qm_extract_files_rescue_roc, (C.byref(args),), unpack
 
     _files_rescueroc = _files_rescue_roc   # (the pass's name in quasimodo_amd.passes)
@@ -455,79 +455,62 @@ class Engine:
     def _files_vartype(self, n, vartype, file_jobs=(), **kw):
         from .vartype import check_edges, n_rows
         edges = check_edges(vartype.get("edges"))
-        twant = _c([int(bool(w)) for w in vartype["want"]] or [0], np.uint8)
+        twant = _want(vartype["want"])
         if n and twant.shape[0] != n:
             raise ValueError("vartype: %d want entries for %d jobs" % (len(vartype["want"]), n))
         e = _c(edges, np.int32)
-        trec = np.zeros((max(n, 1), n_rows(edges), 2), np.uint64)
-        ttru = np.zeros((max(n, 1), n_rows(edges), 2), np.uint64)
+        trec, ttru = _rows(n, n_rows(edges), 2), _rows(n, n_rows(edges), 2)
         ta = _lib.TypesArgs(_p(e), len(edges), 0, _p(twant), _p(trec), _p(ttru))
         ta.keep = (e, twant)   # (read during the call; the other arrays live in unpack)
-        took = lambda k: twant[k] and not file_jobs[k].get("pure")
-        unpack = lambda k: {"type_rec": trec[k].copy(), "type_tru": ttru[k].copy(), "type_edges": edges} if took(k) else {}
+        unpack = lambda k: {"type_rec": trec[k].copy(), "type_tru": ttru[k].copy(), "type_edges": edges} if _mixed(twant[k], file_jobs[k]) else {}
         return self._L.qm_extract_files_types, (C.byref(ta),), unpack
 
-    def _files_haplo(self, n, haplo, file_jobs=(), **kw):
+    def _files_haplo(self, n, spec, file_jobs=(), subsets=False, **kw):
+        """spec: the dict `haplo` takes (gap, genomes, sites, seqs); subsets (_files_hapsub): plus "subsets": [path or None per job] -- the
+        haplotype pass and the search behind it from one call; a job that names either file needs its genome's bytes in `seqs`"""
         from .haplo import check_gap
-        gap = check_gap(haplo.get("gap"))
-        hgid = _c([-1 if g is None else int(g) for g in haplo["genomes"]] or [-1], np.int32)
-        paths = list(haplo.get("sites") or [None] * n)
-        seqs = list(haplo.get("seqs") or [None] * n)
-        if (n and hgid.shape[0] != n) or len(paths) != n or len(seqs) != n:
-            raise ValueError("haplo: %d genomes / %d sites / %d seqs entries for %d jobs" % (len(haplo["genomes"]), len(paths), len(seqs), n))
-        hrec = np.zeros((max(n, 1), _lib.QM_HAP_R_COLS), np.uint64)
-        htru = np.zeros((max(n, 1), _lib.QM_HAP_T_COLS), np.uint64)
-        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
+        gap = check_gap(spec.get("gap"))
+        hgid = _ids(spec["genomes"])
+        paths, seqs, subs = (list(spec.get(key) or [None] * n) for key in ("sites", "seqs", "subsets"))
+        short = (n and hgid.shape[0] != n) or len(paths) != n or len(seqs) != n
+        if subsets and (short or len(subs) != n):
+            raise ValueError("hapsub: %d genomes / %d sites / %d seqs / %d subsets entries for %d jobs" % (len(spec["genomes"]), len(paths), len(seqs), len(subs), n))
+        if short:
+            raise ValueError("haplo: %d genomes / %d sites / %d seqs entries for %d jobs" % (len(spec["genomes"]), len(paths), len(seqs), n))
+        hrec, htru, out_arr = _rows(n, _lib.QM_HAP_R_COLS), _rows(n, _lib.QM_HAP_T_COLS), _path_array(paths, n)
         seqs = [None if x is None else bytes(x) for x in seqs]
         seq_arr = (C.c_char_p * max(n, 1))(*seqs)
         lens = _c([0 if x is None else len(x) for x in seqs] or [0], np.int64)
-        ha = _lib.HaplotypesArgs(_p(hgid), gap, 0, _p(hrec), _p(htru), out_arr, seq_arr, _p(lens))
-        ha.keep = (hgid, out_arr, seqs, seq_arr, lens)   # (read during the call; the other arrays live in unpack)
-        took = lambda k: hgid[k] >= 0 and not file_jobs[k].get("pure")
-        unpack = lambda k: {"hap_rec": hrec[k].copy(), "hap_tru": htru[k].copy(), "hap_gap": gap} if took(k) else {}
-        return self._L.qm_extract_files_haplotypes, (C.byref(ha),), unpack
-
-    def _files_hapsub(self, n, hapsub, file_jobs=(), **kw):
-        """hapsub: the dict `haplo` takes (gap, genomes, sites, seqs) plus "subsets": [path or None per job] -- the haplotype pass
-        and the search behind it from one call; a job that names either file needs its genome's bytes in `seqs`"""
-        from .haplo import check_gap
-        haplo = hapsub
-        gap = check_gap(haplo.get("gap"))
-        hgid = _c([-1 if g is None else int(g) for g in haplo["genomes"]] or [-1], np.int32)
-        paths = list(haplo.get("sites") or [None] * n)
-        seqs = list(haplo.get("seqs") or [None] * n)
-        subs = list(hapsub.get("subsets") or [None] * n)
-        if (n and hgid.shape[0] != n) or len(paths) != n or len(seqs) != n or len(subs) != n:
-            raise ValueError("hapsub: %d genomes / %d sites / %d seqs / %d subsets entries for %d jobs" % (len(haplo["genomes"]), len(paths), len(seqs), len(subs), n))
-        hrec = np.zeros((max(n, 1), _lib.QM_HAP_R_COLS), np.uint64)
-        htru = np.zeros((max(n, 1), _lib.QM_HAP_T_COLS), np.uint64)
-        hsub = np.zeros((max(n, 1), _lib.QM_HAPSUB_COLS), np.uint64)
-        out_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in paths])
-        sub_arr = (C.c_char_p * max(n, 1))(*[None if x is None else os.fsencode(x) for x in subs])
-        seqs = [None if x is None else bytes(x) for x in seqs]
-        seq_arr = (C.c_char_p * max(n, 1))(*seqs)
-        lens = _c([0 if x is None else len(x) for x in seqs] or [0], np.int64)
-        ha = _lib.HapsubArgs(_p(hgid), gap, 0, _p(hrec), _p(htru), out_arr, seq_arr, _p(lens), _p(hsub), sub_arr)
+        common = (_p(hgid), gap, 0, _p(hrec), _p(htru), out_arr, seq_arr, _p(lens))
+        took = lambda k: _mixed(hgid[k] >= 0, file_jobs[k])
+        if not subsets:
+            ha = _lib.HaplotypesArgs(*common)
+            ha.keep = (hgid, out_arr, seqs, seq_arr, lens)   # (read during the call; the other arrays live in unpack)
+            unpack = lambda k: {"hap_rec": hrec[k].copy(), "hap_tru": htru[k].copy(), "hap_gap": gap} if took(k) else {}
+            return self._L.qm_extract_files_haplotypes, (C.byref(ha),), unpack
+        hsub, sub_arr = _rows(n, _lib.QM_HAPSUB_COLS), _path_array(subs, n)
+        ha = _lib.HapsubArgs(*common, _p(hsub), sub_arr)
         ha.keep = (hgid, out_arr, sub_arr, seqs, seq_arr, lens)   # (read during the call; the other arrays live in unpack)
-        took = lambda k: hgid[k] >= 0 and not file_jobs[k].get("pure")
         unpack = lambda k: {"hap_rec": hrec[k].copy(), "hap_tru": htru[k].copy(), "hap_gap": gap, "hap_sub": hsub[k].copy()} if took(k) else {}
         return self._L.qm_extract_files_hapsubsets, (C.byref(ha),), unpack
 
+    def _files_hapsub(self, n, hapsub, file_jobs=(), **kw):
+        return Engine._files_haplo(self, n, hapsub, file_jobs, subsets=True)
+
     def _files_boot(self, n, boot, **kw):
-        bwant = _c([int(bool(w)) for w in boot["want"]] or [0], np.uint8)
+        bwant = _want(boot["want"])
         if n and bwant.shape[0] != n:
             raise ValueError("boot: %d want entries for %d jobs" % (len(boot["want"]), n))
         bw, bn, br = int(boot.get("window", 1024)), int(boot.get("n_win", 256)), int(boot.get("n_rep", 1000))
         if bw < 1 or not 1 <= bn <= _lib.QM_BOOT_MAX_WINDOWS or not 0 <= br <= _lib.QM_BOOT_MAX_REP:
             raise ValueError("boot: window %d, n_win %d (1 to %d), n_rep %d (0 to %d)" % (bw, bn, _lib.QM_BOOT_MAX_WINDOWS, br, _lib.QM_BOOT_MAX_REP))
-        bcnt = np.zeros((max(n, 1), bn + 2, 4), np.uint64)
-        brep = np.zeros((max(n, 1), max(br, 1), 4), np.uint64)
+        bcnt, brep = _rows(n, bn + 2, 4), _rows(n, max(br, 1), 4)
         ba = _lib.BootArgs(bw, bn, br, 0, int(boot.get("seed", 0)) & ((1 << 64) - 1), _p(bwant), _p(bcnt), _p(brep))
         unpack = lambda k: {"boot_cnt": bcnt[k].copy(), "boot_rep": brep[k, :br].copy()} if bwant[k] else {}
         return self._L.qm_extract_files_boot, (C.byref(ba),), unpack
 
     def _files_votes(self, n, votes, **kw):
-        vgrp = _c([-1 if g is None else int(g) for g in votes["group"]] or [-1], np.int32)
+        vgrp = _ids(votes["group"])
         if n and vgrp.shape[0] != n:
             raise ValueError("votes: %d group entries for %d jobs" % (vgrp.shape[0], n))
         vng = (int(vgrp.max()) + 1) if n else 0
@@ -535,9 +518,8 @@ class Engine:
         vout = list(votes.get("out") or [None] * vng)
         if vng and (vk.shape[0] != vng or len(vout) != vng):
             raise ValueError("votes: %d levels / %d files for %d groups" % (vk.shape[0], len(vout), vng))
-        vtab = [np.zeros((max(vng, 1), w), np.uint64) for w in (_lib.QM_VOTE_SLOTS, _lib.QM_VOTE_SLOTS, _lib.QM_VOTE_GROUP_MAX, _lib.QM_VOTE_GROUP_MAX)]
-        out_arr = (C.c_char_p * max(vng, 1))(*[None if x is None else os.fsencode(x) for x in vout])
-        va = _lib.VotesArgs(_p(vgrp), vng, 0, _p(vtab[0]), _p(vtab[1]), _p(vtab[2]), _p(vtab[3]), _p(vk), out_arr)
+        vtab = [_rows(vng, w) for w in (_lib.QM_VOTE_SLOTS, _lib.QM_VOTE_SLOTS, _lib.QM_VOTE_GROUP_MAX, _lib.QM_VOTE_GROUP_MAX)]
+        va = _lib.VotesArgs(_p(vgrp), vng, 0, _p(vtab[0]), _p(vtab[1]), _p(vtab[2]), _p(vtab[3]), _p(vk), _path_array(vout, vng))
         va.keep = vk   # (the levels are read during the call; the other arrays live in unpack)
 
         def unpack(k):
@@ -546,32 +528,26 @@ class Engine:
                                          vote_member=int((vgrp[:k] == g).sum()))
         return self._L.qm_extract_files_votes, (C.byref(va),), unpack
 
-    def _files_nearmiss(self, n, nearmiss, **kw):
-        nwant = _c([int(bool(w)) for w in nearmiss["want"]] or [0], np.uint8)
+    def _files_nearmiss(self, n, nearmiss, file_jobs=(), **kw):
+        nwant = _want(nearmiss["want"])
         fpw, fnw = (list(nearmiss.get(k) or [None] * n) for k in ("fp_why", "fn_why"))
         if (n and nwant.shape[0] != n) or len(fpw) != n or len(fnw) != n:
             raise ValueError("nearmiss: %d want / %d fp_why / %d fn_why entries for %d jobs" % (len(nearmiss["want"]), len(fpw), len(fnw), n))
         radius = int(nearmiss["radius"])
         if not 0 <= radius <= _lib.QM_NM_MAX_RADIUS:
             raise ValueError("nearmiss: radius %d (0 to %d)" % (radius, _lib.QM_NM_MAX_RADIUS))
-        nrec = np.zeros((max(n, 1), _lib.QM_NM_R_CLASSES), np.uint64)
-        ntru = np.zeros((max(n, 1), _lib.QM_NM_T_CLASSES), np.uint64)
-        enc = lambda x: None if x is None else os.fsencode(x)
-        fp_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in fpw])
-        fn_arr = (C.c_char_p * max(n, 1))(*[enc(x) for x in fnw])
-        na = _lib.NearmissArgs(_p(nwant), radius, 0, _p(nrec), _p(ntru), fp_arr, fn_arr)
-        pure = lambda k: bool(kw["file_jobs"][k].get("pure"))
+        nrec, ntru = _rows(n, _lib.QM_NM_R_CLASSES), _rows(n, _lib.QM_NM_T_CLASSES)
+        na = _lib.NearmissArgs(_p(nwant), radius, 0, _p(nrec), _p(ntru), _path_array(fpw, n), _path_array(fnw, n))
         unpack = lambda k: {"nearmiss_rec": [int(x) for x in nrec[k]], "nearmiss_tru": [int(x) for x in ntru[k]],
-                            "nearmiss_radius": radius} if nwant[k] and not pure(k) else {}
+                            "nearmiss_radius": radius} if _mixed(nwant[k], file_jobs[k]) else {}
         return self._L.qm_extract_files_nearmiss, (C.byref(na),), unpack
 
     def _files_surface(self, n, surface, **kw):
-        swant = _c([int(bool(w)) for w in surface["want"]] or [0], np.uint8)
+        swant = _want(surface["want"])
         if n and swant.shape[0] != n:
             raise ValueError("surface: %d want entries for %d jobs" % (len(surface["want"]), n))
         q, nq, na = surface_params(surface.get("q_step", 4), surface.get("nq", 64), surface.get("na", 50))
-        S = np.zeros((max(n, 1), 3, nq, na), np.uint64)
-        ex = np.zeros((max(n, 1), _lib.QM_SF_EXTRA), np.uint64)
+        S, ex = _rows(n, 3, nq, na), _rows(n, _lib.QM_SF_EXTRA)
         sa = _lib.SurfaceArgs(_p(swant), q, nq, na, 0, _p(S), _p(ex))
         unpack = lambda k: {"surface": S[k].copy(), "surface_extra": [int(x) for x in ex[k]], "surface_params": (q, nq, na)} if swant[k] else {}
         return self._L.qm_extract_files_surface, (C.byref(sa),), unpack

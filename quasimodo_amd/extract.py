@@ -13,13 +13,14 @@ Differences from the reference, all deliberate:
   * fp/ and tp/ are created when missing (the reference relies on Snakemake for fp/).
 """
 import os
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from ._lib import SCALAR_NAMES, QmvtError
 from .engine import Engine
-from .passes import PASSES, check_atomize, check_haplo, check_hapsub, check_normalize, check_rescueroc, check_shared_call, check_vartype, requested_by
+from .passes import PASSES, check_alleles, check_shared_call, requested_by
 from .vcfio import scan_vcf
 
 
@@ -115,14 +116,6 @@ def _strict_default():
     return os.environ.get("QM_LENIENT", "0") in ("", "0")
 
 
-def _io_threads():
-    try:
-        n = int(os.environ.get("QM_IO_THREADS", "0"))
-    except ValueError:
-        n = 0
-    return n if n > 0 else min(16, os.cpu_count() or 1)
-
-
 def _alleles_default():
     return os.environ.get("QM_ALLELES", "0") not in ("", "0")
 
@@ -153,6 +146,315 @@ def _group_indices(jobs, pure, field, max_members, what):
         if k > max_members:
             raise ValueError("%s group %r holds %d jobs (1 to %d)" % (what, lab, k, max_members))
     return labels, [-1 if getattr(j, field) is None else labels.index(getattr(j, field)) for j in jobs]
+
+
+def _mixed(j):
+    return not is_pure_strain(j.vcf_file)
+
+
+def _per_job(xs, jobs, said):
+    """a keyword's list, one entry per job"""
+    xs = list(xs)
+    if len(xs) != len(jobs):
+        raise ValueError(said % (len(xs), len(jobs)))
+    return xs
+
+
+class _Loaded:
+    """load(path of a FASTA) -> genome id: every distinct file is read and loaded once, and released with the strata set behind the
+    call.  One dict keyed by the path serves every pass, because no two genome-taking passes share a call (check_shared_call).
+    keep: the bases stay in .seqs (the haplotype pass writes its files from them).  Without an engine nothing is loaded: the call
+    holds pure-strain samples only, which read no genome."""
+
+    def __init__(self, engine):
+        self.engine, self.ids, self.seqs, self.sid = engine, {}, {}, None
+
+    def __call__(self, path, keep=False):
+        if self.engine is not None and path not in self.ids:
+            from .motifs import read_fasta
+            seq = read_fasta(path)
+            if keep:
+                seq = self.seqs[path] = bytes(seq)
+            self.ids[path] = self.engine.genome_load(seq)
+        return self.ids.get(path, -1)
+
+    def strata(self, frozen):
+        self.sid = self.engine.strata_load(frozen)
+        return self.sid
+
+    def release(self):
+        for gid in self.ids.values():
+            self.engine.genome_release(gid)
+        if self.sid is not None:
+            self.engine.strata_release(self.sid)
+
+
+# ---- the passes (DESIGN.md 4.13), each from its keyword to its Job fields to the dict Engine.extract_files takes ----------------
+# name: the pass in quasimodo_amd.passes; key: Engine.extract_files' keyword for it.
+# onto_jobs(jobs, **kw): called when the pass's keyword is given (kw: all of extract_many's).  Puts it onto the Job fields, the derived output paths included.
+# spec(jobs, pure, load): the dict the engine takes, or None when no job asks; load: a _Loaded.  outs: the keys of that dict that hold output paths,
+#   whose directories must exist.  on_pure: the pass runs on pure-strain samples too, so a call of those alone needs an engine for it.
+# after(rows, jobs, spec, alleles): what the pass adds to the rows behind the call.
+PassIO = namedtuple("PassIO", "name key onto_jobs spec outs on_pure after", defaults=((), False, None))
+
+
+def _votes_onto_jobs(jobs, votes, groups, **kw):
+    from .consensus import MAX_GROUP as VMAX
+    if groups is None:
+        raise ValueError("votes: groups (lists of job indices) are needed")
+    opt = votes if isinstance(votes, dict) else {}
+    ks, outs = list(opt.get("k") or [0] * len(groups)), list(opt.get("out") or [None] * len(groups))
+    if len(ks) != len(groups) or len(outs) != len(groups):
+        raise ValueError("votes: %d levels / %d files for %d groups" % (len(ks), len(outs), len(groups)))
+    _label_groups(jobs, groups, "vote_group", "v", VMAX, "vote", "vote ")
+    for k, g in enumerate(groups):
+        if not 0 <= int(ks[k]) <= len(g):
+            raise ValueError("vote group %d: consensus level %d with %d members" % (k, int(ks[k]), len(g)))
+        for i in g:
+            jobs[i].consensus_k, jobs[i].consensus_out = int(ks[k]), outs[k]
+
+
+def _groups_onto_jobs(jobs, groups, votes, **kw):
+    from .truthside import MAX_GROUP
+    if groups is not None and not votes:   # (with votes= they are the vote groups)
+        _label_groups(jobs, groups, "group", "g", MAX_GROUP, "truth-side", "")
+
+
+def _votes_spec(jobs, pure, load):
+    from .consensus import MAX_GROUP as VMAX
+    if not any(j.vote_group is not None for j in jobs):
+        return None
+    labels, index = _group_indices(jobs, pure, "vote_group", VMAX, "vote")
+    vt = {"group": index, "k": [], "out": []}
+    for lab in labels:
+        mem = [j for j in jobs if j.vote_group == lab]
+        k = next((j.consensus_k for j in mem if j.consensus_k), 0)
+        out = next((j.consensus_out for j in mem if j.consensus_out), None)
+        if k > len(mem):
+            raise ValueError("vote group %r: consensus level %d with %d members" % (lab, k, len(mem)))
+        vt["k"].append(k if out else 0)
+        vt["out"].append(out if k else None)
+    return vt
+
+
+def _votes_after(rows, jobs, spec, alleles):
+    for r, j in zip(rows, jobs):
+        if j.vote_group is not None:
+            r["vote_callers"] = [m.caller for m in jobs if m.vote_group == j.vote_group]
+
+
+def _fn_onto_jobs(jobs, fn, **kw):
+    for j in jobs:
+        if fn and j.fn_out is None and _mixed(j):
+            _paths(j)
+            j.fn_out = fn_path(j)
+
+
+def _truthside_spec(jobs, pure, load):
+    from .truthside import MAX_GROUP
+    if not any((j.fn_out or j.group is not None) and not p for j, p in zip(jobs, pure)):
+        return None
+    labels, index = _group_indices(jobs, pure, "group", MAX_GROUP, "truth-side")
+    missed = [next((j.missed_out for j in jobs if j.group == lab and j.missed_out), None) for lab in labels]
+    return {"fn": [None if p else j.fn_out for j, p in zip(jobs, pure)], "group": index, "missed": missed}
+
+
+def _explain_onto_jobs(jobs, explain, **kw):
+    from .nearmiss import check_radius, fn_why_path, fp_why_path
+    radius = check_radius(explain)
+    for j in filter(_mixed, jobs):
+        _paths(j)
+        j.explain = radius
+        j.fp_why_out, j.fn_why_out = j.fp_why_out or fp_why_path(j), j.fn_why_out or fn_why_path(j)
+
+
+def _nearmiss_spec(jobs, pure, load):
+    from .nearmiss import check_radius
+    on = [j.explain is not None and not p for j, p in zip(jobs, pure)]
+    return {"radius": check_radius(next(j.explain for j, w in zip(jobs, on) if w)), "want": [int(w) for w in on],
+            "fp_why": [j.fp_why_out if w else None for j, w in zip(jobs, on)],
+            "fn_why": [j.fn_why_out if w else None for j, w in zip(jobs, on)]} if any(on) else None
+
+
+def _surface_onto_jobs(jobs, surface, **kw):
+    from .surface import params
+    spar = params(**(surface if isinstance(surface, dict) else {}))
+    for j in filter(_mixed, jobs):
+        j.surface = spar
+
+
+def _surface_spec(jobs, pure, load):
+    from .surface import params
+    on = [j.surface is not None for j in jobs]
+    return dict(zip(("q_step", "nq", "na"), params(*next(j.surface for j in jobs if j.surface is not None))), want=[int(w) for w in on]) if any(on) else None
+
+
+def _context_onto_jobs(jobs, context, **kw):
+    from .context import DEFAULT_GC_BINS, DEFAULT_HALF_WINDOW, check_params
+    cpar = check_params(context.get("half_window", DEFAULT_HALF_WINDOW), context.get("n_gc", DEFAULT_GC_BINS))
+    for j, g in zip(jobs, _per_job(context["genomes"], jobs, "context: %d genomes entries for %d jobs")):
+        j.context, j.context_genome = (cpar, g) if g else (None, None)
+
+
+def _context_spec(jobs, pure, load):
+    from .context import check_params
+    on = [j.context is not None for j in jobs]
+    for j, w in zip(jobs, on):
+        if w and not j.context_genome:
+            raise ValueError("%s: Job.context without Job.context_genome (the FASTA the VCF was called against)" % j.vcf_file)
+    return dict(zip(("half_window", "n_gc"), check_params(*next(j.context for j in jobs if j.context is not None))),
+                genomes=[load(j.context_genome) if w else -1 for j, w in zip(jobs, on)]) if any(on) else None
+
+
+def _normalize_onto_jobs(jobs, normalize, **kw):
+    from .normalize import rescued_path
+    for j, g in zip(jobs, _per_job(normalize["genomes"] if isinstance(normalize, dict) else normalize, jobs, "normalize: %d genomes entries for %d jobs")):
+        j.normalize = g if g and _mixed(j) else None
+        if j.normalize:
+            _paths(j)
+            j.rescued_out = j.rescued_out or rescued_path(j)
+
+
+def _rescue_roc_onto_jobs(jobs, rescue_roc, **kw):
+    for j, g in zip(jobs, _per_job(rescue_roc["genomes"] if isinstance(rescue_roc, dict) else rescue_roc, jobs, "rescue_roc: %d genomes entries for %d jobs")):
+        j.rescue_roc = g if g and _mixed(j) else None
+
+
+def _atomize_onto_jobs(jobs, atomize, **kw):
+    from .atomize import atoms_path
+    awant = [True] * len(jobs) if atomize is True else [bool(w) for w in atomize]
+    for j, w in zip(jobs, _per_job(awant, jobs, "atomize: %d entries for %d jobs")):
+        j.atomize = True if w and _mixed(j) else None
+        if j.atomize:
+            _paths(j)
+            j.atoms_out = j.atoms_out or atoms_path(j)
+
+
+def _vartype_onto_jobs(jobs, vartype, **kw):
+    from .vartype import check_edges
+    tedges = check_edges(None if vartype is True else vartype)
+    for j in jobs:
+        j.vartype = tedges if _mixed(j) else None
+
+
+def _vartype_spec(jobs, pure, load):
+    from .vartype import check_edges
+    on = [j.vartype is not None and not p for j, p in zip(jobs, pure)]
+    return {"edges": check_edges(next(j.vartype for j in jobs if j.vartype is not None)), "want": [int(w) for w in on]} if any(on) else None
+
+
+def _haplo_onto_jobs(jobs, haplo, hapsub, **kw):
+    """haplo= (the gap, or the gap and the genomes), and with hapsub=True the subset search behind the pass, asked for in place of it"""
+    if hapsub and (haplo is None or haplo is False):
+        raise ValueError("hapsub (--hap-subsets) searches the sites of the haplotype pass: it needs haplo= (the gap, or the gap and the genomes) in the same call")
+    from .haplo import check_gap, sites_path, subsets_path
+    hopt = haplo if isinstance(haplo, dict) else {"gap": None if haplo is True else haplo}
+    hgap = check_gap(hopt.get("gap"))
+    hgen = hopt["genomes"] if hopt.get("genomes") is not None else [j.haplo_genome for j in jobs]
+    for j, g in zip(jobs, _per_job(hgen, jobs, "haplo: %d genomes entries for %d jobs")):
+        on, j.haplo_genome = (hgap, g) if g and _mixed(j) else (None, None)
+        j.haplo, j.hapsub = (None, on) if hapsub else (on, None)
+        if on is not None:
+            _paths(j)
+            j.sites_out = j.sites_out or sites_path(j)
+            if hapsub:
+                j.subsets_out = j.subsets_out or subsets_path(j)
+    if not any(_hap_gap(j) is not None for j in jobs) and any(_mixed(j) for j in jobs):
+        raise ValueError("haplo: no job names the genome its VCF was called against (Job.haplo_genome, or haplo={'genomes': [...]})")
+
+
+def _haplo_spec(jobs, pure, load, subsets=False):
+    """the dict of the haplotype pass; when a job asks for the search behind it (the pass table let none ask for haplo beside it), the
+    dict goes under hapsub with the subsets files, and nothing under haplo"""
+    from .haplo import check_gap
+    on = [_hap_gap(j) is not None for j in jobs]
+    if not any(on) or any(j.hapsub is not None for j in jobs) != subsets:
+        return None
+    hps = {"gap": check_gap(next(_hap_gap(j) for j, w in zip(jobs, on) if w)),
+           "genomes": [load(j.haplo_genome, keep=True) if w else -1 for j, w in zip(jobs, on)],
+           "sites": [j.sites_out if w else None for j, w in zip(jobs, on)]}
+    hps["seqs"] = [load.seqs.get(j.haplo_genome) if w and (j.sites_out or (j.hapsub is not None and j.subsets_out)) else None for j, w in zip(jobs, on)]
+    return dict(hps, subsets=[j.subsets_out if j.hapsub is not None else None for j in jobs]) if subsets else hps
+
+
+def _boot_onto_jobs(jobs, boot, **kw):
+    from .bootstrap import DEFAULTS
+    par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
+    for j in jobs:
+        j.boot = par
+
+
+def _agreed(jobs, field, names=(), **more):
+    """the parameter tuple the jobs agreed on in Job.<field> under its names and who wants the pass, or None when no job does"""
+    par = next((getattr(j, field) for j in jobs if getattr(j, field)), None)
+    return dict(zip(names, par), want=[1 if getattr(j, field) else 0 for j in jobs], **{k: f(par) for k, f in more.items()}) if par else None
+
+
+def _boot_after(rows, jobs, spec, alleles):
+    for r in rows:
+        if "boot_cnt" in r:
+            r["boot_params"] = {k: spec[k] for k in ("window", "n_win", "n_rep", "seed")}
+            r["boot_truth"] = not alleles
+
+
+def _strata_onto_jobs(jobs, strata, **kw):
+    from .strata import freeze
+    frozen = freeze(strata)
+    for j in jobs:
+        j.strata = frozen
+
+
+def _genomes_onto_jobs(jobs, genomes, **kw):
+    for j, g in zip(jobs, _per_job(genomes, jobs, "genomes: %d entries for %d jobs")):
+        j.genome = g
+
+
+def _profile_onto_jobs(jobs, profile, **kw):
+    want = list(profile["want"])
+    pts = list(profile.get("points") or [None] * len(jobs))
+    if len(want) != len(jobs) or len(pts) != len(jobs):
+        raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(want), len(pts), len(jobs)))
+    par = (int(profile.get("window", 1024)), int(profile.get("n_pos_bins", 256)), int(profile.get("n_af_bins", 20)))
+    for j, w, pt in zip(jobs, want, pts):
+        j.profile = par if w else None
+        j.points_out = pt if w else None
+
+
+# In the order extract_many has always applied the keywords: when two of them are wrong at once, the earlier one speaks.  That is
+# not the order of passes.PASSES (which decides the wording of check_shared_call).  So truthside stands twice: its `groups` are
+# labelled where votes' are, its fn files derived last (the first row has no spec).  hapsub=True goes onto the jobs with haplo=.
+PASS_IO = (
+    PassIO("votes", "votes", _votes_onto_jobs, _votes_spec, ("out",), after=_votes_after),
+    PassIO("truthside", None, _groups_onto_jobs, None),
+    PassIO("nearmiss", "nearmiss", _explain_onto_jobs, _nearmiss_spec, ("fp_why", "fn_why")),
+    PassIO("surface", "surface", _surface_onto_jobs, _surface_spec),
+    PassIO("context", "context", _context_onto_jobs, _context_spec, on_pure=True),
+    PassIO("normalize", "normalize", _normalize_onto_jobs, lambda jobs, pure, load: {
+        "genomes": [load(j.normalize) if j.normalize else -1 for j in jobs],
+        "rescued": [j.rescued_out if j.normalize else None for j in jobs]} if any(j.normalize for j in jobs) else None, ("rescued",)),
+    PassIO("rescueroc", "rescue_roc", _rescue_roc_onto_jobs, lambda jobs, pure, load: {
+        "genomes": [load(j.rescue_roc) if j.rescue_roc else -1 for j in jobs], "want": [1 if j.rescue_roc else 0 for j in jobs]} if any(j.rescue_roc for j in jobs) else None),
+    PassIO("atomize", "atomize", _atomize_onto_jobs, lambda jobs, pure, load: {
+        "want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]} if any(j.atomize for j in jobs) else None, ("atoms",)),
+    PassIO("vartype", "vartype", _vartype_onto_jobs, _vartype_spec),
+    PassIO("haplo", "haplo", _haplo_onto_jobs, _haplo_spec, ("sites",)),
+    PassIO("hapsub", "hapsub", _haplo_onto_jobs, lambda jobs, pure, load: _haplo_spec(jobs, pure, load, True), ("sites", "subsets")),
+    PassIO("boot", "boot", _boot_onto_jobs, lambda jobs, pure, load: _agreed(jobs, "boot", ("window", "n_win", "n_rep", "seed")), on_pure=True, after=_boot_after),
+    PassIO("strata", "strata", _strata_onto_jobs, lambda jobs, pure, load: _agreed(jobs, "strata", id=load.strata), on_pure=True),
+    PassIO("motifs", "genomes", _genomes_onto_jobs, lambda jobs, pure, load: [load(j.genome) if j.genome else -1 for j in jobs] if any(j.genome for j in jobs) else None, on_pure=True),
+    PassIO("profile", "profile", _profile_onto_jobs, lambda jobs, pure, load: _agreed(
+        jobs, "profile", ("window", "n_pos_bins", "n_af_bins"), points=lambda par: [j.points_out if j.profile else None for j in jobs]), ("points",), on_pure=True),
+    PassIO("truthside", "truthside", _fn_onto_jobs, _truthside_spec, ("fn", "missed")),
+)
+
+
+def _one_genome_per_truth(jobs, field, who, what):
+    """VCFs of one truth file name one genome in Job.<field>"""
+    by_truth = {}
+    for j in jobs:
+        g, truth = getattr(j, field), os.path.realpath(j.snp_file)
+        if g and by_truth.setdefault(truth, (g, j.vcf_file))[0] != g:
+            raise ValueError("%s: %s and %s share the truth file %s and name the genomes %s and %s (%s)" % (who, by_truth[truth][1], j.vcf_file, j.snp_file, by_truth[truth][0], g, what))
 
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
@@ -221,129 +523,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     by normal form and by atoms, beside stats["roc"] by spelling) and stats["rroc_base"] ([2]: the distinct forms and the entries
     of its truth set; FN(t) = base - U(t)).  VCFs of one truth file name one genome.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
-    from .consensus import MAX_GROUP as VMAX
-    from .truthside import MAX_GROUP
+    kw = dict(genomes=genomes, fn=fn, groups=groups, profile=profile, strata=strata, boot=boot, votes=votes, explain=explain, surface=surface,
+              context=context, normalize=normalize, atomize=atomize, vartype=vartype, haplo=haplo, hapsub=hapsub, rescue_roc=rescue_roc)
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
              "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
              "atomize": atomize is not None and atomize is not False, "vartype": vartype is not None and vartype is not False,
              "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub), "rescueroc": rescue_roc is not None}
     # the keywords onto the jobs ...
-    if votes:
-        if groups is None:
-            raise ValueError("votes: groups (lists of job indices) are needed")
-        opt = votes if isinstance(votes, dict) else {}
-        ks, outs = list(opt.get("k") or [0] * len(groups)), list(opt.get("out") or [None] * len(groups))
-        if len(ks) != len(groups) or len(outs) != len(groups):
-            raise ValueError("votes: %d levels / %d files for %d groups" % (len(ks), len(outs), len(groups)))
-        _label_groups(jobs, groups, "vote_group", "v", VMAX, "vote", "vote ")
-        for k, g in enumerate(groups):
-            if not 0 <= int(ks[k]) <= len(g):
-                raise ValueError("vote group %d: consensus level %d with %d members" % (k, int(ks[k]), len(g)))
-            for i in g:
-                jobs[i].consensus_k, jobs[i].consensus_out = int(ks[k]), outs[k]
-    elif groups is not None:
-        _label_groups(jobs, groups, "group", "g", MAX_GROUP, "truth-side", "")
-    if explain is not None:
-        from .nearmiss import check_radius, fn_why_path, fp_why_path
-        radius = check_radius(explain)
-        for j in jobs:
-            if not is_pure_strain(j.vcf_file):
-                _paths(j)
-                j.explain = radius
-                j.fp_why_out, j.fn_why_out = j.fp_why_out or fp_why_path(j), j.fn_why_out or fn_why_path(j)
-    if given["surface"]:
-        from .surface import params
-        spar = params(**(surface if isinstance(surface, dict) else {}))
-        for j in jobs:
-            if not is_pure_strain(j.vcf_file):
-                j.surface = spar
-    if context is not None:
-        from .context import DEFAULT_GC_BINS, DEFAULT_HALF_WINDOW, check_params
-        cpar = check_params(context.get("half_window", DEFAULT_HALF_WINDOW), context.get("n_gc", DEFAULT_GC_BINS))
-        cgen = list(context["genomes"])
-        if len(cgen) != len(jobs):
-            raise ValueError("context: %d genomes entries for %d jobs" % (len(cgen), len(jobs)))
-        for j, g in zip(jobs, cgen):
-            j.context, j.context_genome = (cpar, g) if g else (None, None)
-    if normalize is not None:
-        from .normalize import rescued_path
-        ngen = list(normalize["genomes"] if isinstance(normalize, dict) else normalize)
-        if len(ngen) != len(jobs):
-            raise ValueError("normalize: %d genomes entries for %d jobs" % (len(ngen), len(jobs)))
-        for j, g in zip(jobs, ngen):
-            j.normalize = g if g and not is_pure_strain(j.vcf_file) else None
-            if j.normalize:
-                _paths(j)
-                j.rescued_out = j.rescued_out or rescued_path(j)
-    if rescue_roc is not None:
-        rgen = list(rescue_roc["genomes"] if isinstance(rescue_roc, dict) else rescue_roc)
-        if len(rgen) != len(jobs):
-            raise ValueError("rescue_roc: %d genomes entries for %d jobs" % (len(rgen), len(jobs)))
-        for j, g in zip(jobs, rgen):
-            j.rescue_roc = g if g and not is_pure_strain(j.vcf_file) else None
-    if atomize is not None and atomize is not False:
-        from .atomize import atoms_path
-        awant = [True] * len(jobs) if atomize is True else [bool(w) for w in atomize]
-        if len(awant) != len(jobs):
-            raise ValueError("atomize: %d entries for %d jobs" % (len(awant), len(jobs)))
-        for j, w in zip(jobs, awant):
-            j.atomize = True if w and not is_pure_strain(j.vcf_file) else None
-            if j.atomize:
-                _paths(j)
-                j.atoms_out = j.atoms_out or atoms_path(j)
-    if given["vartype"]:
-        from .vartype import check_edges
-        tedges = check_edges(None if vartype is True else vartype)
-        for j in jobs:
-            j.vartype = None if is_pure_strain(j.vcf_file) else tedges
-    if hapsub and (haplo is None or haplo is False):
-        raise ValueError("hapsub (--hap-subsets) searches the sites of the haplotype pass: it needs haplo= (the gap, or the gap and the genomes) in the same call")
-    if given["haplo"] or given["hapsub"]:
-        from .haplo import check_gap, sites_path, subsets_path
-        hopt = haplo if isinstance(haplo, dict) else {"gap": None if haplo is True else haplo}
-        hgap = check_gap(hopt.get("gap"))
-        hgen = list(hopt["genomes"]) if hopt.get("genomes") is not None else [j.haplo_genome for j in jobs]
-        if len(hgen) != len(jobs):
-            raise ValueError("haplo: %d genomes entries for %d jobs" % (len(hgen), len(jobs)))
-        for j, g in zip(jobs, hgen):
-            on, j.haplo_genome = (hgap, g) if g and not is_pure_strain(j.vcf_file) else (None, None)
-            j.haplo, j.hapsub = (None, on) if hapsub else (on, None)   # (hapsub: the pass and the search from one call, asked for in place of haplo)
-            if on is not None:
-                _paths(j)
-                j.sites_out = j.sites_out or sites_path(j)
-                if hapsub:
-                    j.subsets_out = j.subsets_out or subsets_path(j)
-        if not any(_hap_gap(j) is not None for j in jobs) and not all(is_pure_strain(j.vcf_file) for j in jobs):
-            raise ValueError("haplo: no job names the genome its VCF was called against (Job.haplo_genome, or haplo={'genomes': [...]})")
-    if boot is not None:
-        from .bootstrap import DEFAULTS
-        par = tuple(int(boot.get(k, DEFAULTS[k])) for k in ("window", "n_win", "n_rep", "seed"))
-        for j in jobs:
-            j.boot = par
-    if strata is not None:
-        from .strata import freeze
-        frozen = freeze(strata)
-        for j in jobs:
-            j.strata = frozen
-    if genomes is not None:
-        if len(genomes) != len(jobs):
-            raise ValueError("genomes: %d entries for %d jobs" % (len(genomes), len(jobs)))
-        for j, g in zip(jobs, genomes):
-            j.genome = g
-    if profile is not None:
-        want = list(profile["want"])
-        pts = list(profile.get("points") or [None] * len(jobs))
-        if len(want) != len(jobs) or len(pts) != len(jobs):
-            raise ValueError("profile: %d want / %d points entries for %d jobs" % (len(want), len(pts), len(jobs)))
-        par = (int(profile.get("window", 1024)), int(profile.get("n_pos_bins", 256)), int(profile.get("n_af_bins", 20)))
-        for j, w, pt in zip(jobs, want, pts):
-            j.profile = par if w else None
-            j.points_out = pt if w else None
-    for j in jobs:
-        if fn and j.fn_out is None and not is_pure_strain(j.vcf_file):
-            _paths(j)
-            j.fn_out = fn_path(j)
+    for p in PASS_IO:
+        if given[p.name]:
+            p.onto_jobs(jobs, **kw)
     # ... which may share the call, and agree on the parameters of a pass
     check_shared_call({name for name, g in given.items() if g} | requested_by(jobs))
     for p in PASSES:
@@ -351,30 +541,13 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             raise ValueError(p.agree)
     strict = _strict_default() if strict is None else strict
     alleles = _alleles_default() if alleles is None else bool(alleles)
-    check_normalize(requested_by(jobs), alleles)
-    check_atomize(requested_by(jobs), alleles)
-    check_vartype(requested_by(jobs), alleles)
-    check_haplo(requested_by(jobs), alleles)
-    check_hapsub(requested_by(jobs), alleles)
-    check_rescueroc(requested_by(jobs), alleles)
+    check_alleles(requested_by(jobs), alleles)
     for j in jobs:
         if _hap_gap(j) is not None and not j.haplo_genome:
             raise ValueError("%s: Job.haplo without Job.haplo_genome (the FASTA the VCF was called against)" % j.vcf_file)
-    by_truth = {}
-    for j in jobs:
-        if _hap_gap(j) is not None and by_truth.setdefault(os.path.realpath(j.snp_file), (j.haplo_genome, j.vcf_file))[0] != j.haplo_genome:
-            raise ValueError("haplo: %s and %s share the truth file %s and name the genomes %s and %s (the sites of a truth set belong to one genome)"
-                             % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.haplo_genome))
-    by_truth = {}
-    for j in jobs:
-        if j.normalize and by_truth.setdefault(os.path.realpath(j.snp_file), (j.normalize, j.vcf_file))[0] != j.normalize:
-            raise ValueError("normalize: %s and %s share the truth file %s and name the genomes %s and %s (a normalised truth set belongs to one genome)"
-                             % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.normalize))
-    by_truth = {}
-    for j in jobs:
-        if j.rescue_roc and by_truth.setdefault(os.path.realpath(j.snp_file), (j.rescue_roc, j.vcf_file))[0] != j.rescue_roc:
-            raise ValueError("rescue_roc: %s and %s share the truth file %s and name the genomes %s and %s (a normalised truth set belongs to one genome)"
-                             % (by_truth[os.path.realpath(j.snp_file)][1], j.vcf_file, j.snp_file, by_truth[os.path.realpath(j.snp_file)][0], j.rescue_roc))
+    _one_genome_per_truth([j for j in jobs if _hap_gap(j) is not None], "haplo_genome", "haplo", "the sites of a truth set belong to one genome")
+    _one_genome_per_truth(jobs, "normalize", "normalize", "a normalised truth set belongs to one genome")
+    _one_genome_per_truth(jobs, "rescue_roc", "rescue_roc", "a normalised truth set belongs to one genome")
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -396,52 +569,13 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     pure = [is_pure_strain(j.vcf_file) for j in jobs]
     if engine is None:
         # a context is needed even for a batch of pure-strain samples only when something is to be classified
-        need = not all(pure) or any(j.genome or j.profile or j.strata or j.boot or j.context for j in jobs)   # (a vote group holds no pure-strain sample)
+        need = not all(pure) or any(getattr(j, f) for io in PASS_IO if io.on_pure for p in PASSES if p.name == io.name for f in p.fields for j in jobs)
         engine = Engine(int(os.environ.get("QM_DEVICE", "0"))) if need else None
-    loaded = {}
-    sid = None
-    ts = vt = nm = sf = cxs = nzs = ats = tys = hps = hss = rrs = None
-    if any(j.vartype is not None and not p for j, p in zip(jobs, pure)):
-        from .vartype import check_edges
-        tys = {"edges": check_edges(next(j.vartype for j in jobs if j.vartype is not None)),
-               "want": [int(j.vartype is not None and not p) for j, p in zip(jobs, pure)]}
-    if any(j.context is not None for j in jobs):
-        from .context import check_params
-        for j in jobs:
-            if j.context is not None and not j.context_genome:
-                raise ValueError("%s: Job.context without Job.context_genome (the FASTA the VCF was called against)" % j.vcf_file)
-        cxs = dict(zip(("half_window", "n_gc"), check_params(*next(j.context for j in jobs if j.context is not None))))
-    if any(j.surface is not None for j in jobs):
-        from .surface import params
-        sf = dict(zip(("q_step", "nq", "na"), params(*next(j.surface for j in jobs if j.surface is not None))),
-                  want=[int(j.surface is not None) for j in jobs])
-    if any(j.explain is not None and not p for j, p in zip(jobs, pure)):
-        from .nearmiss import check_radius
-        on = [j.explain is not None and not p for j, p in zip(jobs, pure)]
-        nm = {"radius": check_radius(next(j.explain for j, w in zip(jobs, on) if w)), "want": [int(w) for w in on],
-              "fp_why": [j.fp_why_out if w else None for j, w in zip(jobs, on)], "fn_why": [j.fn_why_out if w else None for j, w in zip(jobs, on)]}
-        for path in [x for x in nm["fp_why"] + nm["fn_why"] if x]:
-            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    if any((j.fn_out or j.group is not None) and not p for j, p in zip(jobs, pure)):
-        labels, index = _group_indices(jobs, pure, "group", MAX_GROUP, "truth-side")
-        missed = [next((j.missed_out for j in jobs if j.group == lab and j.missed_out), None) for lab in labels]
-        ts = {"fn": [None if p else j.fn_out for j, p in zip(jobs, pure)], "group": index, "missed": missed}
-        for path in [x for x in ts["fn"] + missed if x]:
-            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    if any(j.vote_group is not None for j in jobs):
-        labels, index = _group_indices(jobs, pure, "vote_group", VMAX, "vote")
-        vt = {"group": index, "k": [], "out": []}
-        for lab in labels:
-            mem = [j for j in jobs if j.vote_group == lab]
-            k = next((j.consensus_k for j in mem if j.consensus_k), 0)
-            out = next((j.consensus_out for j in mem if j.consensus_out), None)
-            if k > len(mem):
-                raise ValueError("vote group %r: consensus level %d with %d members" % (lab, k, len(mem)))
-            vt["k"].append(k if out else 0)
-            vt["out"].append(out if k else None)
-            if k and out:
-                os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    load = _Loaded(engine)
     try:
+        specs = {p.key: p.spec(jobs, pure, load) for p in PASS_IO if p.spec}
+        for path in [x for p in PASS_IO if engine is not None and specs.get(p.key) for k in p.outs for x in specs[p.key][k] if x]:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         for job, p in zip(jobs, pure):
             os.makedirs(os.path.dirname(job.fp_out) or ".", exist_ok=True)
             os.makedirs(os.path.dirname(job.filtered_out) or ".", exist_ok=True)
@@ -454,92 +588,17 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
             rows = _pure_only(fj, strict)
         else:
             before = engine.path_stats_total()
-            gids = None
-            if any(j.genome for j in jobs):
-                from .motifs import read_fasta
-                for j in jobs:
-                    if j.genome and j.genome not in loaded:
-                        loaded[j.genome] = engine.genome_load(read_fasta(j.genome))
-                gids = [loaded[j.genome] if j.genome else -1 for j in jobs]
-            if cxs is not None:
-                from .motifs import read_fasta
-                for j in jobs:
-                    if j.context is not None and j.context_genome not in loaded:
-                        loaded[j.context_genome] = engine.genome_load(read_fasta(j.context_genome))
-                cxs["genomes"] = [loaded[j.context_genome] if j.context is not None else -1 for j in jobs]
-            if any(j.normalize for j in jobs):
-                from .motifs import read_fasta
-                for j in jobs:
-                    if j.normalize and j.normalize not in loaded:
-                        loaded[j.normalize] = engine.genome_load(read_fasta(j.normalize))
-                nzs = {"genomes": [loaded[j.normalize] if j.normalize else -1 for j in jobs],
-                       "rescued": [j.rescued_out if j.normalize else None for j in jobs]}
-                for path in [x for x in nzs["rescued"] if x]:
-                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            if any(_hap_gap(j) is not None for j in jobs):
-                from .haplo import check_gap
-                from .motifs import read_fasta
-                seqs = {}
-                for j in jobs:
-                    if _hap_gap(j) is not None and j.haplo_genome not in seqs:
-                        seqs[j.haplo_genome] = bytes(read_fasta(j.haplo_genome))
-                        loaded[("haplo", j.haplo_genome)] = engine.genome_load(seqs[j.haplo_genome])
-                on = [_hap_gap(j) is not None for j in jobs]
-                hps = {"gap": check_gap(next(_hap_gap(j) for j in jobs if _hap_gap(j) is not None)),
-                       "genomes": [loaded[("haplo", j.haplo_genome)] if w else -1 for j, w in zip(jobs, on)],
-                       "sites": [j.sites_out if w else None for j, w in zip(jobs, on)],
-                       "seqs": [seqs[j.haplo_genome] if w and (j.sites_out or (j.hapsub is not None and j.subsets_out)) else None for j, w in zip(jobs, on)]}
-                for path in [x for x in hps["sites"] if x]:
-                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-                if any(j.hapsub is not None for j in jobs):   # (the pass table let no job ask for haplo beside it)
-                    hss = dict(hps, subsets=[j.subsets_out if j.hapsub is not None else None for j in jobs])
-                    hps = None
-                    for path in [x for x in hss["subsets"] if x]:
-                        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            if any(j.rescue_roc for j in jobs):
-                from .motifs import read_fasta
-                for j in jobs:
-                    if j.rescue_roc and j.rescue_roc not in loaded:
-                        loaded[j.rescue_roc] = engine.genome_load(read_fasta(j.rescue_roc))
-                rrs = {"genomes": [loaded[j.rescue_roc] if j.rescue_roc else -1 for j in jobs], "want": [1 if j.rescue_roc else 0 for j in jobs]}
-            if any(j.atomize for j in jobs):
-                ats = {"want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]}
-                for path in [x for x in ats["atoms"] if x]:
-                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            # the passes with parameters: the tuple the jobs agreed on, and who wants the pass
-            par = {f: next((getattr(j, f) for j in jobs if getattr(j, f)), None) for f in ("profile", "strata", "boot")}
-            want = lambda f: [1 if getattr(j, f) else 0 for j in jobs]
-            prof = strat = bt = None
-            if par["profile"]:
-                prof = dict(zip(("window", "n_pos_bins", "n_af_bins"), par["profile"]), want=want("profile"),
-                            points=[j.points_out if j.profile else None for j in jobs])
-                for path in [x for x in prof["points"] if x]:
-                    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-            if par["strata"]:
-                sid = engine.strata_load(par["strata"])
-                strat = {"id": sid, "want": want("strata")}
-            if par["boot"]:
-                bt = dict(zip(("window", "n_win", "n_rep", "seed"), par["boot"]), want=want("boot"))
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, genomes=gids, truthside=ts, profile=prof, strata=strat, boot=bt, votes=vt, nearmiss=nm, surface=sf, context=cxs, normalize=nzs, atomize=ats, vartype=tys, haplo=hps, hapsub=hss, rescue_roc=rrs)
-            if vt is not None:
-                for r, j in zip(rows, jobs):
-                    if j.vote_group is not None:
-                        r["vote_callers"] = [m.caller for m in jobs if m.vote_group == j.vote_group]
-            if bt is not None:
-                for r in rows:
-                    if "boot_cnt" in r:
-                        r["boot_params"] = {k: bt[k] for k in ("window", "n_win", "n_rep", "seed")}
-                        r["boot_truth"] = not alleles
+                                                global_dev=global_dev, **specs)
+            for p in PASS_IO:
+                if p.after and specs[p.key] is not None:
+                    p.after(rows, jobs, specs[p.key], alleles)
             extract_many.last_phases = phases
             # where the VCFs found out of order went (bucket paths / radix sort: a silent fall onto the slow path shows here)
             extract_many.last_paths = {k: v - before[k] for k, v in engine.path_stats_total().items()}
     finally:
         if engine is not None:
-            for gid in loaded.values():
-                engine.genome_release(gid)
-            if sid is not None:
-                engine.strata_release(sid)
+            load.release()
         if own and engine is not None:
             engine.close()
     for job, p, r in zip(jobs, pure, rows):

@@ -53,43 +53,25 @@ def check_shared_call(requested):
                 raise SharedCallError(a, b)
 
 
-def check_normalize(requested, alleles):
-    """--normalize reads indels and MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
-    if "normalize" in requested and not alleles:
-        raise ValueError("normalize (--normalize) needs the allele-extended mode (--alleles): a single-base batch holds no indels or MNPs")
+# The passes that read indels, MNPs or complex records, which only the allele-extended mode holds, in the order they are asked about,
+# and what a single-base batch lacks for each: Pass.needs_alleles (None for every other pass).  A column beside the table, not a
+# seventh field of it: the tests of the passes compare whole six-field rows.
+NEEDS_ALLELES = {
+    "normalize": "a single-base batch holds no indels or MNPs",
+    "atomize": "a single-base batch holds no MNPs",
+    "vartype": "a single-base batch holds SNVs only",
+    "haplo": "a single-base batch holds no indels, MNPs or complex records to replay",
+    "hapsub": "a single-base batch holds no indels, MNPs or complex records to replay",   # (it runs the haplotype pass)
+    "rescueroc": "a single-base batch has no rescue passes to sweep",
+}
+Pass.needs_alleles = property(lambda p: NEEDS_ALLELES.get(p.name))
 
 
-def check_atomize(requested, alleles):
-    """--atomize splits MNPs, which only the allele-extended mode holds: ValueError before a file is touched"""
-    if "atomize" in requested and not alleles:
-        raise ValueError("atomize (--atomize) needs the allele-extended mode (--alleles): a single-base batch holds no MNPs")
-
-
-def check_rescueroc(requested, alleles):
-    """--rescue-roc sweeps the two rescue passes, which only the allele-extended mode has: ValueError before a file is touched"""
-    if "rescueroc" in requested and not alleles:
-        raise ValueError("rescueroc (--rescue-roc) needs the allele-extended mode (--alleles): a single-base batch has no rescue passes to sweep")
-
-
-def check_haplo(requested, alleles):
-    """--haplotypes replays indels, MNPs and complex records, which only the allele-extended mode holds: ValueError before a file
-    is touched"""
-    if "haplo" in requested and not alleles:
-        raise ValueError("haplo (--haplotypes) needs the allele-extended mode (--alleles): a single-base batch holds no indels, MNPs or complex records to replay")
-
-
-def check_hapsub(requested, alleles):
-    """--hap-subsets runs the haplotype pass and searches the sites it left MISMATCH or CONFLICT: like that pass it needs the
-    allele-extended mode.  ValueError before a file is touched"""
-    if "hapsub" in requested and not alleles:
-        raise ValueError("hapsub (--hap-subsets) needs the allele-extended mode (--alleles): a single-base batch holds no indels, MNPs or complex records to replay")
-
-
-def check_vartype(requested, alleles):
-    """--by-type types indels, MNPs and complex records, which only the allele-extended mode holds: ValueError before a file is
-    touched"""
-    if "vartype" in requested and not alleles:
-        raise ValueError("vartype (--by-type) needs the allele-extended mode (--alleles): a single-base batch holds SNVs only")
+def check_alleles(requested, alleles):
+    """ValueError, before a file is touched, for the first pass of NEEDS_ALLELES that is requested without the allele-extended mode"""
+    for p in (p for name in NEEDS_ALLELES for p in PASSES if p.name == name):
+        if p.name in requested and not alleles:
+            raise ValueError("%s (%s) needs the allele-extended mode (--alleles): %s" % (p.name, p.flag, p.needs_alleles))
 
 
 def requested_by(jobs):

@@ -295,31 +295,10 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 raise WorkflowError("missing input %s" % src)
             plan.append((s, c, src))
     mixes = sorted({s[:2] for s in samples}, reverse=True)              # TM, TA
-    if mutation_context is not None:
-        for mix in mixes:
-            fa = mutation_context.get(mix)
-            if not fa or not os.path.isfile(fa):
-                raise WorkflowError("mutation context: no genome FASTA for %s (%s)" % (mix, fa))
-    if cpar is not None:
-        for mix in mixes:
-            fa = seq_context.get(mix)
-            if not fa or not os.path.isfile(fa):
-                raise WorkflowError("sequence context: no genome FASTA for %s (%s)" % (mix, fa))
-    if normalize is not None:
-        for mix in mixes:
-            fa = normalize.get(mix)
-            if not fa or not os.path.isfile(fa):
-                raise WorkflowError("normalize: no genome FASTA for %s (%s)" % (mix, fa))
-    if rescue_roc is not None:
-        for mix in mixes:
-            fa = rescue_roc.get(mix)
-            if not fa or not os.path.isfile(fa):
-                raise WorkflowError("rescue ROC: no genome FASTA for %s (%s)" % (mix, fa))
-    if haplotypes is not None:
-        for mix in mixes:
-            fa = haplotypes.get(mix)
-            if not fa or not os.path.isfile(fa):
-                raise WorkflowError("haplotypes: no genome FASTA for %s (%s)" % (mix, fa))
+    for fastas, what in ((mutation_context, "mutation context"), (seq_context, "sequence context"), (normalize, "normalize"), (rescue_roc, "rescue ROC"), (haplotypes, "haplotypes")):
+        for mix in mixes if fastas is not None else ():
+            if not fastas.get(mix) or not os.path.isfile(fastas.get(mix)):
+                raise WorkflowError("%s: no genome FASTA for %s (%s)" % (what, mix, fastas.get(mix)))
     if dryrun:
         for s, c, src in plan:
             print("extractTP\t%s\t%s" % (c, src))

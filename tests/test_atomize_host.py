@@ -230,9 +230,9 @@ def test_refusals_in_front_of_any_file(tmp_path):
             extract_many(mk(), alleles=True, atomize=True, **other)
     with pytest.raises(passes.SharedCallError):
         passes.check_shared_call({"atomize", "normalize"})
-    passes.check_atomize({"atomize"}, True)
+    passes.check_alleles({"atomize"}, True)
     with pytest.raises(ValueError, match="--alleles"):
-        passes.check_atomize({"atomize"}, False)
+        passes.check_alleles({"atomize"}, False)
     with pytest.raises(workflow.WorkflowError, match="--atomize needs --alleles"):
         workflow.run_hcmv_variantcall(str(tmp_path / "nodata"), str(tmp_path / "out"), atomize=True)
     with pytest.raises(workflow.WorkflowError, match="cannot be combined"):

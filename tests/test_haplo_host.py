@@ -228,10 +228,11 @@ def test_the_pass_table():
             with pytest.raises(passes.SharedCallError):
                 passes.check_shared_call({"haplo", other})
     passes.check_shared_call({"haplo"})
-    passes.check_haplo({"haplo"}, True)
-    passes.check_haplo({"normalize"}, False)
+    passes.check_alleles({"haplo"}, True)
+    with pytest.raises(ValueError, match=r"^normalize \("):                      # (the one rule names the pass that was asked for, not this one)
+        passes.check_alleles({"normalize"}, False)
     with pytest.raises(ValueError, match="--alleles"):
-        passes.check_haplo({"haplo"}, False)
+        passes.check_alleles({"haplo"}, False)
 
 
 def test_refusals_in_front_of_any_file(tmp_path):

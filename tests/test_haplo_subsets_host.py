@@ -201,11 +201,12 @@ def test_the_table_rows_against_hand_derived_ones(tmp_path):
 def test_check_hapsub_and_the_pass_table():
     """the pass `hapsub` is the haplotype pass and the search behind it from one call: asked for in place of `haplo`, it needs the
     allele-extended mode, its jobs share one gap, and it shares its call with no other pass -- `haplo` included"""
-    from quasimodo_amd.passes import PASSES, Pass, SharedCallError, check_hapsub, check_shared_call
-    check_hapsub({"haplo"}, False)                                  # not asked for: nothing to say
-    check_hapsub({"hapsub"}, True)
+    from quasimodo_amd.passes import PASSES, Pass, SharedCallError, check_alleles, check_shared_call
+    with pytest.raises(ValueError, match=r"^haplo \("):              # not asked for: the one rule names haplo, which was
+        check_alleles({"haplo"}, False)
+    check_alleles({"hapsub"}, True)
     with pytest.raises(ValueError, match="--alleles"):
-        check_hapsub({"hapsub"}, False)
+        check_alleles({"hapsub"}, False)
     (p,) = [x for x in PASSES if x.name == "hapsub"]
     assert p == Pass("hapsub", ("hapsub",), ("hapsub",), "--hap-subsets", "hapsub: the jobs of one call share one gap", ())
     check_shared_call({"hapsub"})

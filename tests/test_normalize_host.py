@@ -251,7 +251,7 @@ def test_refusals_in_front_of_any_file(tmp_path):
             extract_many(mk(), alleles=True, normalize=[fa, fa], **other)
     with pytest.raises(passes.SharedCallError):
         passes.check_shared_call({"normalize", "motifs"})
-    passes.check_normalize({"normalize"}, True)
+    passes.check_alleles({"normalize"}, True)
     with pytest.raises(workflow.WorkflowError, match="--normalize needs --alleles"):
         workflow.run_hcmv_variantcall(str(tmp_path / "nodata"), str(tmp_path / "out"), normalize={"TM": fa, "TA": fa})
     with pytest.raises(workflow.WorkflowError, match="cannot be combined"):

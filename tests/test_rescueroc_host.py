@@ -226,16 +226,17 @@ def test_caller_roc_rescue_table_literal(tmp_path):
 
 # ---- the flag ---------------------------------------------------------------------------------------------------------------
 def test_refusals_come_before_any_file(tmp_path):
-    """check_rescueroc and the shared-call rule: without the allele-extended mode, beside normalize or atomize (the sweep runs
+    """check_alleles and the shared-call rule: without the allele-extended mode, beside normalize or atomize (the sweep runs
     them itself) or any other pass -- said before an engine is made or a file written"""
     from quasimodo_amd import passes, workflow
     from quasimodo_amd.extract import Job, extract_many
     p = next(x for x in passes.PASSES if x.name == "rescueroc")
     assert p == passes.Pass("rescueroc", ("rescue_roc",), ("rescue_roc",), "--rescue-roc", None, ())
-    passes.check_rescueroc({"rescueroc"}, True)
-    passes.check_rescueroc({"normalize"}, False)
+    passes.check_alleles({"rescueroc"}, True)
+    with pytest.raises(ValueError, match=r"^normalize \("):                      # (the one rule names the pass that was asked for, not this one)
+        passes.check_alleles({"normalize"}, False)
     with pytest.raises(ValueError, match="--alleles"):
-        passes.check_rescueroc({"rescueroc"}, False)
+        passes.check_alleles({"rescueroc"}, False)
     for other in ("normalize", "atomize", "haplo", "vartype", "motifs"):
         with pytest.raises(passes.SharedCallError) as ei:
             passes.check_shared_call({"rescueroc", other})

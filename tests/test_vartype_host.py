@@ -192,10 +192,11 @@ def test_the_pass_table():
             with pytest.raises(passes.SharedCallError):
                 passes.check_shared_call({"vartype", other})
     passes.check_shared_call({"vartype"})
-    passes.check_vartype({"vartype"}, True)
-    passes.check_vartype({"atomize"}, False)
+    passes.check_alleles({"vartype"}, True)
+    with pytest.raises(ValueError, match=r"^atomize \("):                        # (the one rule names the pass that was asked for, not this one)
+        passes.check_alleles({"atomize"}, False)
     with pytest.raises(ValueError, match="--alleles"):
-        passes.check_vartype({"vartype"}, False)
+        passes.check_alleles({"vartype"}, False)
 
 
 def test_refusals_in_front_of_any_file(tmp_path):
