@@ -22,6 +22,7 @@
 
 #include "../../include/qmvt.h"
 #include "qmvt_dev.h"
+#include "qmvt_classify_pair.h"
 #include "qmvt_motif.h"
 #include "qmvt_afprofile.h"
 #include "qmvt_truthside.h"
@@ -1257,7 +1258,7 @@ extern "C" int qm_batch_run(qm_batch* b, void* stream, void* global_dev) {
     else HIPCHK(hipMemsetAsync(g, 0, gbytes, st));   // a batch of empty VCFs launches nothing
     if (use_known) P.known = b->d_known;
     if (T) HIPCHK(hipEventRecord(ev[2], st));
-    launch_classify(P, ns, st);
+    launch_classify_any(P, ns, st);
     if (T) HIPCHK(hipEventRecord(ev[3], st));
     FinalizeParams F = finalize_params(b, g);
     // (no summary word: with the mirrors, qm_batch_finish looks through the VCFs' flag words itself -- and every workgroup of a
@@ -1734,7 +1735,7 @@ static int radix_chunk(qm_batch* b, const std::vector<int>& vs, hipStream_t st, 
   const uint32_t* perm = b->sv[cur];
   if (b->ext) launch_sort_gather_alleles(b->d_segs, b->d_tile_seg, nst, perm, b->ref, b->alt, s->ref, s->alt, st);
   // --- 3. the normal path on the sorted copies (their ROC rows go into the caller's per-truth sums)
-  launch_classify(classify_params(s), (int)s->L.spans.size(), st);
+  launch_classify_any(classify_params(s), (int)s->L.spans.size(), st);
   launch_finalize(finalize_params(s, b->last_global), nseg, st);
   // --- 4. results back under the original VCFs: ROC + scalar rows, class bits in input order
   launch_sort_copy_rows(b->d_segs, nseg, s->roc, s->scalars, b->roc, b->scalars, b->n_bins, st);

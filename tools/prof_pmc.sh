@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes for k_classify (separate from any trace run, as the pool requires).
+# PMC passes for the classification kernel of the batch (k_classify_pair for sorted single-base columns, k_classify otherwise; separate from any trace run, as the pool requires).
 # usage: bash tools/prof_pmc.sh <tag> [n_vcf]      RARGS="0 30": run_once.py's further arguments (shuffled, indel_pct) -- the allele-extended instantiation
 set -e
 TAG=${1:-x}; NV=${2:-256}
@@ -8,7 +8,8 @@ OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 run() { # name counters...
   local name=$1; shift
-  (cd /tmp && rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $OLDPWD/tools/run_once.py $NV 2 ${RARGS:-} > $OUT/$name.log 2>&1) || true
+  # every pass under its own time limit; the first one that fails ends the script (nothing more is started on the GPU behind it)
+  (cd /tmp && timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $OLDPWD/tools/run_once.py $NV 2 ${RARGS:-} > $OUT/$name.log 2>&1) || { echo "pass $name failed"; tail -5 $OUT/$name.log; exit 1; }
 }
 OLDPWD=$PWD
 run sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM
