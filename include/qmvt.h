@@ -788,6 +788,41 @@ int qm_batch_hapsubset_timings(qm_batch* b, float* ms1);
 int qm_batch_rescue_roc(qm_batch* b, unsigned which /*QM_RROC_NORM | QM_RROC_ATOM*/, void* stream);
 int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n /*[n_vcf][3][n_bins]*/, uint64_t* roc_a /*[n_vcf][3][n_bins]*/, uint64_t* base /*[n_vcf][2]*/);
 int qm_batch_rescue_roc_timings(qm_batch* b, float* ms4);
+/* The four rescues combined: final TP, FP and FN when everything the engine knows is applied, and the Venn of
+ * methods.  It reads what qm_batch_normalize, qm_batch_atomize, qm_batch_haplotypes and -- with QM_LADDER_SUBSETS --
+ * qm_batch_hapsubsets left in the batch and normalises, atomises and replays nothing again.  Build-defined, parity unpinned, as
+ * the four passes are.
+ * Per record one mask byte, 0 for a record that is not kept, else: QM_LADDER_M_K always; QM_LADDER_M_S if the record is one of
+ *   the batch's TP lines; QM_LADDER_M_N if its class byte of the normalisation pass is QM_NORM_C_RESCUED; QM_LADDER_M_A if that of
+ *   the atomisation pass is QM_ATOM_C_RESCUED; QM_LADDER_M_H if that of the haplotype pass is QM_HAP_C_RESCUED and it has
+ *   QM_F_IDDOT and is no TP line; QM_LADDER_M_B if the search's second class byte is QM_HAP_C_SUBSET and it has QM_F_IDDOT and is
+ *   no TP line (always 0 without QM_LADDER_SUBSETS).  N, A, H and B are never set with S, H and B never together.  A VCF that named
+ *   no genome (-1) in the normalisation call has N zero throughout, one that named none in the haplotype call H and B.
+ * Per truth entry of a VCF (allele-extended table order) one mask byte: S if the entry is spelled like a kept record with valid
+ *   codes and no QM_F_NOKEY (QM_ATOM_T_FOUND); N if its form was found by a kept record; A if it is atomisable and every one of
+ *   its atoms is carried by a kept atomisable record; H if its entry class is QM_HAP_C_RESCUED; B if its second entry class is
+ *   QM_HAP_C_SUBSET (0 without QM_LADDER_SUBSETS).  The bits are raw: S usually implies N.
+ * rec[v][QM_LADDER_COLS]: QM_LADDER_KEPT, QM_LADDER_TP, then 16 cells: cell m (column QM_LADDER_CELL0 + m) = the kept lines that
+ *   are no TP lines and whose low four bits are m; cell 0 is the final FP.  tru[v][QM_LADDER_COLS]: the entries, those with S, then
+ *   16 cells over the entries without S; cell 0 is the final FN.
+ * qm_batch_ladder: asynchronous on `stream` (NULL = the context's own), ordered behind its producers on whatever stream.
+ *   QM_E_INVAL for any other bit in `what`; QM_E_STATE for a single-base batch, if a truth set was released, and if the batch has
+ *   not finished, since its latest run, qm_batch_normalize(.., QM_NORM_COLUMNS), qm_batch_atomize(QM_ATOM_COLUMNS),
+ *   qm_batch_haplotypes(.., QM_HAP_COLUMNS) or -- for QM_LADDER_SUBSETS -- qm_batch_hapsubsets(QM_HAPSUB_COLUMNS): the first one
+ *   missing, in that order, is named.  A new call of a producer waits for a ladder still in flight and forgets its rows.
+ * qm_batch_get_ladder: waits for the pass, then copies (either pointer may be NULL).
+ * qm_batch_get_laddered: the mask bytes of one VCF (either pointer may be NULL); QM_E_STATE without QM_LADDER_COLUMNS in the
+ *   latest call.
+ * qm_batch_ladder_timings (qm_batch_set_timing on): milliseconds between HIP events of k_ladder_records and k_ladder_truth. */
+#define QM_LADDER_SUBSETS 1u
+#define QM_LADDER_COLUMNS 2u
+#define QM_LADDER_COLS 18
+enum { QM_LADDER_KEPT = 0, QM_LADDER_TP = 1, QM_LADDER_CELL0 = 2 };      /* truth side: the entries, those with S, the cells */
+enum { QM_LADDER_M_N = 1, QM_LADDER_M_A = 2, QM_LADDER_M_H = 4, QM_LADDER_M_B = 8, QM_LADDER_M_K = 64, QM_LADDER_M_S = 128 };
+int qm_batch_ladder(qm_batch* b, unsigned what /*0, QM_LADDER_SUBSETS, QM_LADDER_COLUMNS or both*/, void* stream);
+int qm_batch_get_ladder(qm_batch* b, uint64_t* rec /*[n_vcf][QM_LADDER_COLS]*/, uint64_t* tru /*[n_vcf][QM_LADDER_COLS]*/);
+int qm_batch_get_laddered(qm_batch* b, int vcf, uint8_t* mask /*[n]*/, uint8_t* entry_mask /*[entries]*/);
+int qm_batch_ladder_timings(qm_batch* b, float* ms2);
 int qm_truth_sites(qm_ctx* ctx, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
                    int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
@@ -1276,6 +1311,29 @@ typedef struct qm_rescue_roc_args {
 int qm_extract_files_rescue_roc(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                 qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                                 void* global_dev, const qm_rescue_roc_args* rescue_roc);
+
+/* qm_extract_files_ex plus the four rescues combined over its batch; mode must be QM_BATCH_ALLELES (QM_E_STATE
+ * otherwise).  The call runs qm_batch_normalize, qm_batch_atomize, qm_batch_haplotypes (gap: 0 .. QM_HAP_MAX_GAP) and -- subsets
+ * != 0 -- qm_batch_hapsubsets with their columns itself and hands out none of their rows or files.  Mixed-sample jobs with
+ * want[j] != 0 get rec[j][QM_LADDER_COLS] and tru[j][QM_LADDER_COLS] of qm_batch_get_ladder (genome_id[j]: a qm_genome_load id,
+ * named in the normalisation and in the haplotype call; -1: the bits N, H and B stay zero); the others, pure-strain jobs among
+ * them, get zero rows.  ladder_out (NULL, or per job NULL or a path): `#kind line POS REF ALT METHODS TIER`, one row per kept line
+ * that is no TP line in file order (kind `line`, the 1-based line number, the line's own text of the three columns, its method
+ * set as letters of NAHB joined by `+` or `none`, its tier normalized / atomized / haplotype / subset or `none`), then one row
+ * per truth entry no kept record spells in table order (kind `entry`, `.`, the entry).  The VCF outputs, stats and roc are those
+ * of qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_ladder_args {
+  const int32_t* genome_id;         /* [n_jobs], -1 = no genome */
+  int32_t gap;
+  int32_t subsets;
+  const uint8_t* want;              /* [n_jobs] */
+  uint64_t* rec;                    /* [n_jobs][QM_LADDER_COLS] */
+  uint64_t* tru;                    /* [n_jobs][QM_LADDER_COLS] */
+  const char* const* ladder_out;    /* NULL, or [n_jobs] */
+} qm_ladder_args;
+int qm_extract_files_ladder(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                            qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                            void* global_dev, const qm_ladder_args* ladder);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

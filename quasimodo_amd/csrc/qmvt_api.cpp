@@ -37,6 +37,7 @@
 #include "qmvt_types.h"
 #include "qmvt_haplo.h"
 #include "qmvt_rroc.h"
+#include "qmvt_ladder.h"
 
 using namespace qm;
 
@@ -651,7 +652,7 @@ enum class Path : uint8_t { Radix, OneLevel, TwoLevel, Partitions, Wide };
 
 // ---- the passes over a finished batch (include/qmvt.h at qm_batch_run) ----
 enum PassId { P_MOTIFS, P_AFP, P_TRUTH, P_STRATA, P_BOOT, P_VOTES, P_NEARMISS, P_SURFACE, P_CONTEXT, P_NORM, P_ATOM, P_TYPES, P_HAPLO,
-              P_HAPSUB, P_RROC, N_PASSES };
+              P_HAPSUB, P_RROC, P_LADDER, N_PASSES };
 constexpr int PASS_MAX_MARKS = 6;   // qm_batch_haplotypes'
 // What a batch keeps of every pass, qm_batch::pass[id].  Both kinds of event are created at first use: a batch that never ran a
 // pass holds none, and whatever walks the passes (wait_passes, the reset in qm_batch_run, batch_free) makes no HIP call for it.
@@ -672,6 +673,7 @@ static const PassInfo PASSES[N_PASSES] = {
     {"qm_batch_nearmiss", 3, true},    {"qm_batch_surface", 4, false},    {"qm_batch_context", 4, true},
     {"qm_batch_normalize", 4, false},  {"qm_batch_atomize", 4, false},    {"qm_batch_types", 3, false},
     {"qm_batch_haplotypes", 6, false}, {"qm_batch_hapsubsets", 2, false}, {"qm_batch_rescue_roc", 5, false},
+    {"qm_batch_ladder", 3, false},
 };
 // (P_HAPLO: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
 // flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
@@ -918,6 +920,12 @@ struct qm_batch {
   DevBuf<uint32_t> rr_best;
   DevBuf<RrocVcf> rr_vcfs;
   DevBuf<uint64_t> rr_out;
+  // qm_batch_ladder (lazy): the per-VCF descriptors, [n_vcf][QM_LADDER_COLS] counts of records and of truth entries
+  // one behind the other and, on request, a mask byte per record and per (VCF, truth entry)
+  DevBuf<LadderVcf> ld_vcfs;
+  DevBuf<uint64_t> ld_out;
+  DevBuf<uint8_t> ld_mask, ld_emask;   // [n_pad]; the entries of every VCF's truth set, VCF after VCF
+  std::vector<int64_t> ld_eoff;        // [n_vcf + 1] the VCF's entries in ld_emask
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -2867,8 +2875,10 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   // A sweep behind the previous call (qm_batch_rescue_roc, maybe on another stream) reads the columns this call rewrites and may
   // regrow: it is waited for here, not only on the stream.
   if (b->pass[P_RROC].done) HIPCHK(hipEventSynchronize(b->pass[P_RROC].done));
+  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (the ladder reads the class bytes and the bitmaps)
   b->pass[P_NORM].made = 0;   // from here on the outputs are rewritten
   b->pass[P_RROC].made &= ~QM_RROC_NORM;   // ... and the sweep's rows belong to the call before
+  b->pass[P_LADDER].made = 0;              // ... and so do the ladder's
   const size_t np = (size_t)b->L.n_pad;
   rc = b->nz_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->nz_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -3074,8 +3084,10 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
   rc = pass_open(b, P_ATOM, stream, &st);
   if (rc != QM_OK) return rc;
   if (b->pass[P_RROC].done) HIPCHK(hipEventSynchronize(b->pass[P_RROC].done));   // (as in qm_batch_normalize: the sweep reads the sets and the columns)
+  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (and the ladder)
   b->pass[P_ATOM].made = 0;   // from here on the outputs are rewritten
   b->pass[P_RROC].made &= ~QM_RROC_ATOM;
+  b->pass[P_LADDER].made = 0;
   const size_t np = (size_t)b->L.n_pad;
   rc = b->at_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->at_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -3274,6 +3286,105 @@ extern "C" int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n, uint64_t* r
 extern "C" int qm_batch_rescue_roc_timings(qm_batch* b, float* ms4) {
   return pass_timings(b, P_RROC, "qm_batch_rescue_roc_timings", "run of its producers", ms4);
 }
+// ---- the four rescues combined: final TP, FP and FN and the Venn of methods ----
+extern "C" int qm_batch_ladder(qm_batch* b, unsigned what, void* stream) {
+  NEED_FINISHED(b, "qm_batch_ladder");
+  if (what & ~(QM_LADDER_SUBSETS | QM_LADDER_COLUMNS)) return fail(QM_E_INVAL, "qm_batch_ladder: what = %u", what);
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_ladder: a single-base batch has no rescue passes to combine (create the batch with QM_BATCH_ALLELES)");
+  const bool subsets = (what & QM_LADDER_SUBSETS) != 0, cols = (what & QM_LADDER_COLUMNS) != 0;
+  if (!(b->pass[P_NORM].made & QM_NORM_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_ladder: needs qm_batch_normalize(.., QM_NORM_COLUMNS) behind the latest run");
+  if (!(b->pass[P_ATOM].made & QM_ATOM_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_ladder: needs qm_batch_atomize(QM_ATOM_COLUMNS) behind the latest run");
+  if (!(b->pass[P_HAPLO].made & QM_HAP_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_ladder: needs qm_batch_haplotypes(.., QM_HAP_COLUMNS) behind the latest run");
+  if (subsets && !(b->pass[P_HAPSUB].made & QM_HAPSUB_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_ladder: QM_LADDER_SUBSETS needs qm_batch_hapsubsets(QM_HAPSUB_COLUMNS) behind the latest qm_batch_haplotypes");
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  int rc = truths_live(b, "qm_batch_ladder");
+  if (rc != QM_OK) return rc;
+  std::vector<LadderVcf> vcfs(std::max<size_t>(nv, 1));
+  memset(vcfs.data(), 0, vcfs.size() * sizeof(LadderVcf));
+  std::vector<int64_t> eoff(nv + 1, 0);
+  int64_t max_entries = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    const int64_t xn = c->truths[(size_t)b->L.vcfs[v].truth].xn;
+    eoff[v + 1] = eoff[v] + xn;
+    max_entries = std::max(max_entries, xn);
+    vcfs[v].eoff = eoff[v];
+    vcfs[v].heoff = b->hp_eoff[v];
+    vcfs[v].has = (b->nz_has[v] ? LADDER_HAS_NORM : 0u) | (b->hp_has[v] ? LADDER_HAS_HAP : 0u);
+  }
+  hipStream_t st;
+  rc = pass_open(b, P_LADDER, stream, &st);
+  if (rc != QM_OK) return rc;
+  b->pass[P_LADDER].made = 0;   // from here on the outputs are rewritten
+  const size_t np = (size_t)b->L.n_pad, rows = nv * LADDER_COLS, out_words = std::max<size_t>(2 * rows, 1);
+  rc = b->ld_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
+  if (rc == QM_OK) rc = b->ld_out.grow((int64_t)out_words, &b->dev_bytes);
+  if (rc == QM_OK && cols) rc = b->ld_mask.grow((int64_t)std::max<size_t>(np, 1), &b->dev_bytes);
+  if (rc == QM_OK && cols) rc = b->ld_emask.grow(std::max<int64_t>(eoff[nv], 1), &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  b->ld_eoff = eoff;
+  HIPCHK(pass_marks(b, P_LADDER));
+  HIPCHK(hipStreamWaitEvent(st, b->pass[P_NORM].done, 0));   // the producers may have run on other streams
+  HIPCHK(hipStreamWaitEvent(st, b->pass[P_ATOM].done, 0));
+  HIPCHK(hipStreamWaitEvent(st, b->pass[P_HAPLO].done, 0));
+  if (subsets) HIPCHK(hipStreamWaitEvent(st, b->pass[P_HAPSUB].done, 0));
+  if (nv) HIPCHK(hipMemcpy(b->ld_vcfs, vcfs.data(), nv * sizeof(LadderVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
+  HIPCHK(hipMemsetAsync(b->ld_out, 0, out_words * 8, st));
+  HIPCHK(pass_mark(b, P_LADDER, 0, st));
+  LadderRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.vcfs = b->ld_vcfs;
+  P.flags = b->flags; P.mask_pass = b->mask_pass; P.mask_tp = b->mask_tp;
+  P.cls_n = b->nz_cls; P.cls_a = b->at_cls; P.cls_h = b->hp_cls;
+  P.cls_b = subsets ? (const uint8_t*)b->hs_cls : nullptr;
+  P.mask = cols ? (uint8_t*)b->ld_mask : nullptr;
+  P.rec = b->ld_out;
+  P.n_spans = (int32_t)b->L.spans.size();
+  launch_ladder_records(P, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(pass_mark(b, P_LADDER, 1, st));
+  LadderTruthParams Q;
+  memset(&Q, 0, sizeof Q);
+  Q.vcfs = b->ld_vcfs; Q.nvcfs = b->nz_vcfs; Q.avcfs = b->at_vcfs; Q.hvcfs = b->hp_vcfs;
+  Q.ecls_b = subsets ? (const uint8_t*)b->hs_ecls : nullptr;
+  Q.emask = cols ? (uint8_t*)b->ld_emask : nullptr;
+  Q.tru = b->ld_out + rows;
+  Q.n_vcf = (int32_t)nv;
+  launch_ladder_truth(Q, max_entries, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(pass_mark(b, P_LADDER, 2, st));
+  HIPCHK(pass_done(b, P_LADDER, st, 4u | what));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_ladder(qm_batch* b, uint64_t* rec, uint64_t* tru) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_ladder: NULL batch");
+  if (pass_ran(b, P_LADDER, "qm_batch_get_ladder", "run of its producers") != QM_OK) return QM_E_STATE;
+  HIPCHK(pass_result(b, P_LADDER));
+  const size_t nv = (size_t)b->n_vcf, rows = nv * LADDER_COLS;
+  if (rec && nv) HIPCHK(hipMemcpy(rec, b->ld_out, rows * 8, hipMemcpyDeviceToHost));
+  if (tru && nv) HIPCHK(hipMemcpy(tru, b->ld_out + rows, rows * 8, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_get_laddered(qm_batch* b, int v, uint8_t* mask, uint8_t* entry_mask) {
+  if (!b) return fail(QM_E_INVAL, "qm_batch_get_laddered: NULL batch");
+  if (pass_ran(b, P_LADDER, "qm_batch_get_laddered", "run of its producers") != QM_OK) return QM_E_STATE;
+  if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_laddered: VCF %d (the batch has %d)", v, b->n_vcf);
+  if (!(b->pass[P_LADDER].made & QM_LADDER_COLUMNS))
+    return fail(QM_E_STATE, "qm_batch_get_laddered: the latest qm_batch_ladder did not keep the columns (QM_LADDER_COLUMNS)");
+  HIPCHK(pass_result(b, P_LADDER));
+  const VcfDesc& d = b->L.vcfs[(size_t)v];
+  const size_t n = (size_t)d.n, ne = (size_t)(b->ld_eoff[(size_t)v + 1] - b->ld_eoff[(size_t)v]);
+  if (mask && n) HIPCHK(hipMemcpy(mask, b->ld_mask + d.off, n, hipMemcpyDeviceToHost));
+  if (entry_mask && ne) HIPCHK(hipMemcpy(entry_mask, b->ld_emask + b->ld_eoff[(size_t)v], ne, hipMemcpyDeviceToHost));
+  return QM_OK;
+}
+extern "C" int qm_batch_ladder_timings(qm_batch* b, float* ms2) {
+  return pass_timings(b, P_LADDER, "qm_batch_ladder_timings", "run of its producers", ms2);
+}
 // ---- TP, FP and FN by variant type and size ----
 extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t* len, const uint32_t* head, const uint32_t* tail,
                               int64_t n_shapes, unsigned what, void* stream) {
@@ -3443,8 +3554,10 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
   // A search behind the previous call (qm_batch_hapsubsets, maybe on another stream) reads what this call rewrites, regrows and
   // copies over from the host: it is waited for here, not only on the stream.
   if (b->pass[P_HAPSUB].done) HIPCHK(hipEventSynchronize(b->pass[P_HAPSUB].done));
+  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (as in qm_batch_normalize: the ladder reads the classes)
   b->pass[P_HAPLO].made = 0;   // from here on the outputs are rewritten
   b->pass[P_HAPSUB].made = 0;   // ... and the search's results belong to the call before
+  b->pass[P_LADDER].made = 0;   // ... and so do the ladder's rows
   const size_t np = (size_t)b->L.n_pad;
   const bool cols = (what & QM_HAP_COLUMNS) != 0;
   rc = b->hp_pool.grow((int64_t)std::max<size_t>(pool_words, 1), &b->dev_bytes);
@@ -3574,7 +3687,9 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   hipStream_t st;
   rc = pass_open(b, P_HAPSUB, stream, &st);
   if (rc != QM_OK) return rc;
+  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (as in qm_batch_normalize: the ladder reads the second classes)
   b->pass[P_HAPSUB].made = 0;   // from here on the outputs are rewritten
+  b->pass[P_LADDER].made = 0;   // ... and the ladder's rows belong to the call before
   b->hs_listed = false;
   const size_t np = (size_t)b->L.n_pad, npairs = (size_t)b->hp_npairs, ne = (size_t)b->hp_eoff[nv];
   rc = b->hs_sub.grow((int64_t)std::max<size_t>(nv * HAPSUB_COLS, 1), &b->dev_bytes);

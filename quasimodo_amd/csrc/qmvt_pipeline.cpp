@@ -300,7 +300,7 @@ struct Passes {
   const qm_truthside_args* ts = nullptr; const qm_votes_args* va = nullptr; const qm_nearmiss_args* nm = nullptr;
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
   const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr; const qm_haplotypes_args* hp = nullptr;
-  const qm_hapsub_args* hs = nullptr; const qm_rescue_roc_args* rr = nullptr;
+  const qm_hapsub_args* hs = nullptr; const qm_rescue_roc_args* rr = nullptr; const qm_ladder_args* ld = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -858,6 +858,109 @@ int rroc_pass(const PassCtx& c, const qm_rescue_roc_args* rr, int n_bins, std::s
   return QM_OK;
 }
 
+// ---- the four rescues combined ----
+struct LdColumns { std::vector<uint8_t> mask, emask; };
+std::string ld_set_name(unsigned m) {
+  std::string out;
+  for (int k = 0; k < 4; ++k)
+    if ((m >> k) & 1u) { if (!out.empty()) out.push_back('+'); out.push_back("NAHB"[k]); }
+  return out.empty() ? "none" : out;
+}
+const char* ld_tier(unsigned m) {
+  static const char* const names[] = {"normalized", "atomized", "haplotype", "subset"};
+  for (int k = 0; k < 4; ++k)
+    if ((m >> k) & 1u) return names[k];
+  return "none";
+}
+// `#kind line POS REF ALT METHODS TIER`: every kept line of the job that is no TP line, in file order, then every truth entry no
+// kept record spells, in table order (quasimodo_amd.ladder.job_rows)
+int write_ladder_file(const char* path, const JobState& s, const LdColumns& c, const NzEntries& t) {
+  std::string out = "#kind\tline\tPOS\tREF\tALT\tMETHODS\tTIER\n";
+  const uint8_t* text = s.vcf.p;
+  const size_t len = s.vcf.n;
+  int64_t rec = 0;
+  for (int64_t i = 0; i < s.info.n_lines; ++i) {
+    if (is_header(s.line_kind[(size_t)i])) continue;
+    const int64_t r = rec++;
+    const unsigned m = c.mask[(size_t)r];
+    if (!(m & QM_LADDER_M_K) || (m & QM_LADDER_M_S)) continue;
+    size_t b = (size_t)s.line_off[(size_t)i], e = std::min((size_t)s.line_off[(size_t)i + 1], len);
+    if (e > b && text[e - 1] == '\n') --e;
+    const uint8_t* f[6]; size_t fl[6]; int nf = 0;
+    const uint8_t* q = text + b;
+    while (nf < 6) {
+      const uint8_t* tb = (const uint8_t*)memchr(q, '\t', (size_t)(text + e - q));
+      f[nf] = q; fl[nf] = tb ? (size_t)(tb - q) : (size_t)(text + e - q); ++nf;
+      if (!tb) break;
+      q = tb + 1;
+    }
+    out += "line\t" + std::to_string(i + 1);
+    for (int k : {1, 3, 4}) { out.push_back('\t'); if (k < nf) out.append((const char*)f[k], fl[k]); }
+    out += "\t" + ld_set_name(m & 15u) + "\t" + ld_tier(m & 15u) + "\n";
+  }
+  for (size_t j = 0; j < t.pos.size() && j < c.emask.size(); ++j) {
+    const unsigned m = c.emask[j];
+    if (m & QM_LADDER_M_S) continue;
+    out += "entry\t.\t" + std::to_string(t.pos[j]) + "\t" + nz_spell(t.ref[j]) + "\t" + nz_spell(t.alt[j]) + "\t" + ld_set_name(m & 15u) + "\t" +
+           ld_tier(m & 15u) + "\n";
+  }
+  return write_all_atomic(path, out);
+}
+
+// The four producer passes with their columns, run here as the batch calls they are -- none of their rows or files is handed out
+// --, then the ladder; the rows of every wanted mixed-sample job (a pure-strain job has no truth set to be measured against: its
+// rows stay zero) and the ladder files of the jobs that name one
+int ladder_pass(const PassCtx& c, const qm_ladder_args* la, std::string& err) {
+  if (!la) return QM_OK;
+  auto want = [&](int j) { return la->want[j] != 0 && !c.jobs[j].pure; };
+  if (!c.any(want)) return QM_OK;
+  auto path = [&](int j) { return want(j) && la->ladder_out ? la->ladder_out[j] : nullptr; };
+  std::vector<int32_t> gid(c.nv, -1);
+  bool files = false;
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) { gid[(size_t)c.J[(size_t)j].batch_v] = la->genome_id[j]; files = files || path(j); }
+  const unsigned what = (la->subsets ? QM_LADDER_SUBSETS : 0u) | (files ? QM_LADDER_COLUMNS : 0u);
+  std::vector<uint64_t> rec(c.nv * QM_LADDER_COLS), tru(c.nv * QM_LADDER_COLS);
+  int rc = qm_batch_normalize(c.batch, gid.data(), QM_NORM_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_atomize(c.batch, QM_ATOM_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_haplotypes(c.batch, gid.data(), la->gap, QM_HAP_COLUMNS, nullptr);
+  if (rc == QM_OK && la->subsets) rc = qm_batch_hapsubsets(c.batch, QM_HAPSUB_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_ladder(c.batch, what, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_ladder(c.batch, rec.data(), tru.data());
+  if (rc != QM_OK) return c.lib(rc, err);
+  c.scatter_rows(la->rec, rec, QM_LADDER_COLS, want);
+  c.scatter_rows(la->tru, tru, QM_LADDER_COLS, want);
+  struct Task { int j; LdColumns cols; };
+  std::vector<Task> W;
+  std::vector<NzEntries> ent(c.T.size());
+  std::vector<uint8_t> have(c.T.size(), 0);
+  for (int j = 0; j < c.n_jobs && rc == QM_OK; ++j) {
+    if (!path(j)) continue;
+    const JobState& s = c.J[(size_t)j];
+    if (!have[(size_t)s.truth]) {
+      NzEntries& e = ent[(size_t)s.truth];
+      int64_t tn = 0;
+      (void)qm_truth_entries(c.ctx, c.truth_of(j).tid, nullptr, nullptr, nullptr, 0, &tn);   // (how many)
+      e.pos.resize((size_t)tn + 1); e.ref.resize((size_t)tn + 1); e.alt.resize((size_t)tn + 1);
+      rc = qm_truth_entries(c.ctx, c.truth_of(j).tid, e.pos.data(), e.ref.data(), e.alt.data(), tn, &tn);
+      e.pos.resize((size_t)tn); e.ref.resize((size_t)tn); e.alt.resize((size_t)tn);
+      have[(size_t)s.truth] = 1;
+    }
+    if (rc != QM_OK) break;
+    W.push_back({j, LdColumns{std::vector<uint8_t>((size_t)s.n_data + 1, 0), std::vector<uint8_t>(ent[(size_t)s.truth].pos.size() + 1, 0)}});
+    rc = qm_batch_get_laddered(c.batch, s.batch_v, W.back().cols.mask.data(), W.back().cols.emask.data());
+    W.back().cols.emask.resize(ent[(size_t)s.truth].pos.size());
+  }
+  if (rc != QM_OK) return c.lib(rc, err);
+  std::vector<int> wrc(W.size(), QM_OK);
+  parallel_for((int)W.size(), c.nthr, [&](int k) {
+    const Task& w = W[(size_t)k];
+    wrc[(size_t)k] = write_ladder_file(la->ladder_out[w.j], c.J[(size_t)w.j], w.cols, ent[(size_t)c.J[(size_t)w.j].truth]);
+  });
+  for (size_t k = 0; k < W.size(); ++k)
+    if (wrc[k] != QM_OK) { err = std::string("cannot write ") + la->ladder_out[W[k].j]; return wrc[k]; }
+  return QM_OK;
+}
+
 // ---- clusters of records matched by replayed haplotype ----
 struct HpColumns { std::vector<uint8_t> cls, ecls; std::vector<int32_t> site; };
 struct HpSites { std::vector<int32_t> first, lo, hi; };
@@ -1352,6 +1455,25 @@ extern "C" int qm_extract_files_rescue_roc(qm_ctx* ctx, int n_jobs, const qm_fil
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
+// the four rescues combined behind the worker
+extern "C" int qm_extract_files_ladder(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                       qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                       int n_slots, void* global_dev, const qm_ladder_args* ladder) {
+  const qm_ladder_args* la = ladder;
+  if (!la || (n_jobs > 0 && (!la->genome_id || !la->want || !la->rec || !la->tru)))
+    return fail(QM_E_INVAL, "qm_extract_files_ladder: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_ladder: the rescue passes it combines match indels and MNPs, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (la->gap < 0 || la->gap > QM_HAP_MAX_GAP)
+    return fail(QM_E_INVAL, "qm_extract_files_ladder: gap " + std::to_string(la->gap) + " (0 to " + std::to_string(QM_HAP_MAX_GAP) + ")");
+  if (n_jobs > 0) {
+    memset(la->rec, 0, sizeof(uint64_t) * QM_LADDER_COLS * (size_t)n_jobs);
+    memset(la->tru, 0, sizeof(uint64_t) * QM_LADDER_COLS * (size_t)n_jobs);
+  }
+  Passes P; P.ld = la;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
 // the bootstrap pass behind the worker
 extern "C" int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                      qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
@@ -1713,6 +1835,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = haplo_pass(pc, P.hp, err);
       if (rc == QM_OK) rc = hapsub_pass(pc, P.hs, err);
       if (rc == QM_OK) rc = rroc_pass(pc, P.rr, n_bins, err);
+      if (rc == QM_OK) rc = ladder_pass(pc, P.ld, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

@@ -268,7 +268,7 @@ class Engine:
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
                       truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
-                      atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None):
+                      atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None, ladder=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -321,6 +321,10 @@ class Engine:
         (alleles=True only), in place of normalize and atomize, which it runs itself: wanted mixed-sample rows gain
         `rroc_n`, `rroc_a` ([3][n_bins] uint64: TP(t), FP(t), U(t) by normal form and by atoms, laid out like `roc`) and `rroc_base`
         ([2]: the distinct forms and the entries of the truth set).
+        ladder: {"genomes": [genome_load id or None / -1 per job], "want": [0/1 per job], "gap": None or 0 .. 32, "subsets": True,
+        "out": [path or None per job]} -- qm_extract_files_ladder (alleles=True only), in place of normalize,
+        atomize, haplo and hapsub, which it runs itself: wanted mixed-sample rows gain `ladder_rec` and `ladder_tru` ([18] uint64,
+        columns ladder.COLS / ladder.T_COLS); the ladder files are written.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         from .passes import check_alleles, check_shared_call
@@ -330,7 +334,7 @@ class Engine:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface, "rescueroc": rescue_roc}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface, "rescueroc": rescue_roc, "ladder": ladder}
         requested = {name for name, spec in specs.items() if spec is not None}
         check_shared_call(requested)
         check_alleles(requested, alleles)
@@ -451,6 +455,18 @@ class Engine:
         return self._L.qm_extract_files_rescue_roc, (C.byref(args),), unpack
 
     _files_rescueroc = _files_rescue_roc   # (the pass's name in quasimodo_amd.passes)
+
+    def _files_ladder(self, n, ladder, file_jobs=(), **kw):
+        from .haplo import check_gap
+        lgid, lwant = _ids(ladder["genomes"]), _want(ladder["want"])
+        paths = list(ladder.get("out") or [None] * n)
+        if (n and (lgid.shape[0] != n or lwant.shape[0] != n)) or len(paths) != n:
+            raise ValueError("ladder: %d genomes / %d want / %d out entries for %d jobs" % (len(ladder["genomes"]), len(ladder["want"]), len(paths), n))
+        rec, tru, out_arr = _rows(n, _lib.QM_LADDER_COLS), _rows(n, _lib.QM_LADDER_COLS), _path_array(paths, n)
+        args = _lib.LadderArgs(_p(lgid), check_gap(ladder.get("gap")), 1 if ladder.get("subsets", True) else 0, _p(lwant), _p(rec), _p(tru), out_arr)
+        args.keep = (lgid, lwant, out_arr)   # (read during the call; the other arrays live in unpack)
+        unpack = lambda k: {"ladder_rec": rec[k].copy(), "ladder_tru": tru[k].copy()} if _mixed(lwant[k], file_jobs[k]) else {}
+        return self._L.qm_extract_files_ladder, (C.byref(args),), unpack
 
     def _files_vartype(self, n, vartype, file_jobs=(), **kw):
         from .vartype import check_edges, n_rows
@@ -1086,6 +1102,37 @@ class Batch:
     def rescue_roc_timings(self):
         """qm_batch_rescue_roc_timings (set_timing on): milliseconds of the latest rescue_roc() between HIP events, kernel by kernel"""
         return self._pass_timings(self._L.qm_batch_rescue_roc_timings, ("rroc_norm_records_ms", "rroc_norm_units_ms", "rroc_atom_records_ms", "rroc_atom_units_ms"))
+
+    # -- the four rescues combined: final TP, FP, FN and the Venn of methods (DESIGN.md 4.23) --
+    def ladder(self, subsets=False, columns=False, fetch=True, stream=None):
+        """qm_batch_ladder + qm_batch_get_ladder behind normalize(columns=True), atomize(columns=True), haplotypes(columns=True)
+        and -- subsets=True -- hapsubsets(columns=True): (rec, tru uint64 [n_vcf][18], columns ladder.COLS -- kept, TP lines and
+        the 16 cells of the method bits over the kept lines that are no TP by spelling; entries, spelled-alike entries and the
+        16 cells over the others).  columns=True keeps the mask bytes for laddered().  fetch=False: enqueue only
+        (ladder_counts() waits and copies)"""
+        what = (_lib.QM_LADDER_SUBSETS if subsets else 0) | (_lib.QM_LADDER_COLUMNS if columns else 0)
+        self._ck(self._L.qm_batch_ladder(self._h, what, C.c_void_p(stream) if stream else None))
+        return self.ladder_counts() if fetch else None
+
+    def ladder_counts(self):
+        """qm_batch_get_ladder: the counts of the latest ladder()"""
+        rec = np.zeros((max(self.n_vcf, 1), _lib.QM_LADDER_COLS), np.uint64)
+        tru = np.zeros((max(self.n_vcf, 1), _lib.QM_LADDER_COLS), np.uint64)
+        self._ck(self._L.qm_batch_get_ladder(self._h, _p(rec), _p(tru)))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def laddered(self, v):
+        """qm_batch_get_laddered: (mask uint8 [n] -- the mask byte of every record of VCF v in input order, bits ladder.S, K, N,
+        A, H, B --, entry_mask uint8 [entries] -- that of every entry of its truth set), after a ladder(columns=True)"""
+        n = int(self.n_records[int(v)])
+        ne = self.engine.truth_size(int(self.truth_ids[int(v)]), alleles=True)
+        mask, emask = np.zeros(max(n, 1), np.uint8), np.zeros(max(ne, 1), np.uint8)
+        self._ck(self._L.qm_batch_get_laddered(self._h, int(v), _p(mask), _p(emask)))
+        return mask[:n], emask[:ne]
+
+    def ladder_timings(self):
+        """qm_batch_ladder_timings (set_timing on): milliseconds of the latest ladder() between HIP events, kernel by kernel"""
+        return self._pass_timings(self._L.qm_batch_ladder_timings, ("ladder_records_ms", "ladder_truth_ms"))
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

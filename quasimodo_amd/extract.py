@@ -88,6 +88,10 @@ class Job:
     # a subset search inside the sites the haplotype pass left MISMATCH or CONFLICT; with Job.haplo
     hapsub: int = None        # the gap g, IN PLACE OF Job.haplo: the pass and the search behind it; stats gain hap_sub ([8], haplo.SUB_COLS) too
     subsets_out: str = None   # where the job's table of PARTIAL sites goes (extract_many(hapsub=True) derives it)
+    # the four rescues combined; mixed samples, allele-extended mode only
+    ladder: int = None        # the gap g of the haplotype pass, IN PLACE OF Job.normalize / atomize / haplo / hapsub: stats gain ladder_rec / ladder_tru
+    ladder_genome: str = None  # FASTA of the genome the VCF was called against (with Job.ladder)
+    ladder_out: str = None    # where the job's table of lines and entries with their method sets goes (extract_many(ladder=) derives it)
 
 
 def _paths(job):
@@ -320,6 +324,29 @@ def _rescue_roc_onto_jobs(jobs, rescue_roc, **kw):
         j.rescue_roc = g if g and _mixed(j) else None
 
 
+def _ladder_onto_jobs(jobs, ladder, **kw):
+    """ladder= (the genomes, or the genomes and the gap): all four rescue passes and the ladder behind them, asked for in place of them"""
+    from .haplo import check_gap
+    from .ladder import ladder_path
+    opt = ladder if isinstance(ladder, dict) else {"genomes": ladder}
+    gap = check_gap(opt.get("gap"))
+    for j, g in zip(jobs, _per_job(opt["genomes"], jobs, "ladder: %d genomes entries for %d jobs")):
+        j.ladder, j.ladder_genome = (gap, g) if g and _mixed(j) else (None, None)
+        if j.ladder is not None:
+            _paths(j)
+            j.ladder_out = j.ladder_out or ladder_path(j)
+
+
+def _ladder_spec(jobs, pure, load):
+    from .haplo import check_gap
+    on = [j.ladder is not None for j in jobs]
+    if not any(on):
+        return None
+    return {"gap": check_gap(next(j.ladder for j in jobs if j.ladder is not None)), "subsets": True,
+            "genomes": [load(j.ladder_genome) if w else -1 for j, w in zip(jobs, on)], "want": [int(w) for w in on],
+            "out": [j.ladder_out if w else None for j, w in zip(jobs, on)]}
+
+
 def _atomize_onto_jobs(jobs, atomize, **kw):
     from .atomize import atoms_path
     awant = [True] * len(jobs) if atomize is True else [bool(w) for w in atomize]
@@ -434,6 +461,7 @@ PASS_IO = (
         "rescued": [j.rescued_out if j.normalize else None for j in jobs]} if any(j.normalize for j in jobs) else None, ("rescued",)),
     PassIO("rescueroc", "rescue_roc", _rescue_roc_onto_jobs, lambda jobs, pure, load: {
         "genomes": [load(j.rescue_roc) if j.rescue_roc else -1 for j in jobs], "want": [1 if j.rescue_roc else 0 for j in jobs]} if any(j.rescue_roc for j in jobs) else None),
+    PassIO("ladder", "ladder", _ladder_onto_jobs, _ladder_spec, ("out",)),
     PassIO("atomize", "atomize", _atomize_onto_jobs, lambda jobs, pure, load: {
         "want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]} if any(j.atomize for j in jobs) else None, ("atoms",)),
     PassIO("vartype", "vartype", _vartype_onto_jobs, _vartype_spec),
@@ -448,6 +476,11 @@ PASS_IO = (
 )
 
 
+# extract_files is called with the keyword of every pass, None where none is asked for -- but for these, which go only when asked for
+# (the call of a run without them is the call it has always been)
+_WHEN_ASKED = ("ladder",)
+
+
 def _one_genome_per_truth(jobs, field, who, what):
     """VCFs of one truth file name one genome in Job.<field>"""
     by_truth = {}
@@ -459,7 +492,7 @@ def _one_genome_per_truth(jobs, field, who, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None):
+                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None, ladder=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -522,14 +555,21 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     every mixed-sample job with a genome gets stats["rroc_n"] and stats["rroc_a"] ([3][n_bins]: TP(t), FP(t), U(t) under QUAL >= t
     by normal form and by atoms, beside stats["roc"] by spelling) and stats["rroc_base"] ([2]: the distinct forms and the entries
     of its truth set; FN(t) = base - U(t)).  VCFs of one truth file name one genome.
+    ladder: [FASTA path or None per job] or {"genomes": that list, "gap": None or 0 .. 32} (quasimodo_amd.ladder, DESIGN.md 4.23;
+    default: the jobs' Job.ladder / Job.ladder_genome / Job.ladder_out; alleles=True only, ValueError otherwise), in place of
+    normalize, atomize, haplo and hapsub, which the call runs itself: every mixed-sample job with a genome gets
+    stats["ladder_rec"] ([18]: kept, TP lines, then the 16 cells of the method bits over the kept lines that are no TP by
+    spelling; cell 0 is the final FP) and stats["ladder_tru"] ([18]: entries, entries a kept record spells, then the 16 cells
+    over the others; cell 0 is the final FN), and ladder/<x>.ladder.tsv beside fp/ and tp/.  VCFs of one truth file name one genome.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     kw = dict(genomes=genomes, fn=fn, groups=groups, profile=profile, strata=strata, boot=boot, votes=votes, explain=explain, surface=surface,
-              context=context, normalize=normalize, atomize=atomize, vartype=vartype, haplo=haplo, hapsub=hapsub, rescue_roc=rescue_roc)
+              context=context, normalize=normalize, atomize=atomize, vartype=vartype, haplo=haplo, hapsub=hapsub, rescue_roc=rescue_roc, ladder=ladder)
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
              "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
              "atomize": atomize is not None and atomize is not False, "vartype": vartype is not None and vartype is not False,
-             "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub), "rescueroc": rescue_roc is not None}
+             "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub), "rescueroc": rescue_roc is not None,
+             "ladder": ladder is not None}
     # the keywords onto the jobs ...
     for p in PASS_IO:
         if given[p.name]:
@@ -548,6 +588,10 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     _one_genome_per_truth([j for j in jobs if _hap_gap(j) is not None], "haplo_genome", "haplo", "the sites of a truth set belong to one genome")
     _one_genome_per_truth(jobs, "normalize", "normalize", "a normalised truth set belongs to one genome")
     _one_genome_per_truth(jobs, "rescue_roc", "rescue_roc", "a normalised truth set belongs to one genome")
+    for j in jobs:
+        if j.ladder is not None and not j.ladder_genome:
+            raise ValueError("%s: Job.ladder without Job.ladder_genome (the FASTA the VCF was called against)" % j.vcf_file)
+    _one_genome_per_truth([j for j in jobs if j.ladder is not None], "ladder_genome", "ladder", "a normalised truth set belongs to one genome")
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")
@@ -589,7 +633,7 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         else:
             before = engine.path_stats_total()
             rows, phases = engine.extract_files(fj, n_bins=n_bins, alleles=alleles, strict=strict, truth_slots=truth_slots, n_slots=n_slots,
-                                                global_dev=global_dev, **specs)
+                                                global_dev=global_dev, **{k: v for k, v in specs.items() if v is not None or k not in _WHEN_ASKED})
             for p in PASS_IO:
                 if p.after and specs[p.key] is not None:
                     p.after(rows, jobs, specs[p.key], alleles)

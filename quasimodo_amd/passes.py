@@ -22,6 +22,8 @@ PASSES = (
     Pass("hapsub", ("hapsub",), ("hapsub",), "--hap-subsets", "hapsub: the jobs of one call share one gap", ()),
     # the QUAL sweep of normalize AND atomize, which it runs itself: asked for in place of them, never beside them
     Pass("rescueroc", ("rescue_roc",), ("rescue_roc",), "--rescue-roc", None, ()),
+    # the four rescue passes, which it runs itself, combined: asked for in place of them, never beside them
+    Pass("ladder", ("ladder",), ("ladder",), "--match-ladder", "ladder: the jobs of one call share one gap", ()),
     Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
     Pass("vartype", ("vartype",), ("vartype",), "--by-type", "vartype: the typed jobs of one call share one list of size edges", ()),
     Pass("context", ("context",), ("context",), "--seq-context",
@@ -63,6 +65,7 @@ NEEDS_ALLELES = {
     "haplo": "a single-base batch holds no indels, MNPs or complex records to replay",
     "hapsub": "a single-base batch holds no indels, MNPs or complex records to replay",   # (it runs the haplotype pass)
     "rescueroc": "a single-base batch has no rescue passes to sweep",
+    "ladder": "a single-base batch has no rescue passes to combine",
 }
 Pass.needs_alleles = property(lambda p: NEEDS_ALLELES.get(p.name))
 

@@ -166,7 +166,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
                          context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None, haplotypes=None,
-                         hap_gap=None, hap_subsets=False, rescue_roc=None):
+                         hap_gap=None, hap_subsets=False, rescue_roc=None, match_ladder=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -225,13 +225,22 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     QUAL ROC by spelling, by normal form and by atoms side by side, snp/qmvt_roc/{caller}/{sample}.{ref}.rescue/spelling_roc.tsv.gz,
     normalized_roc.tsv.gz and atomized_roc.tsv.gz for every mixed sample, and final_tables/caller_roc_rescue.tsv (TP, FP, FN,
     Precision, Recall, F1 at QUAL >= 20 and at the threshold of the largest F1, per caller, mixture and matching, then pooled).
+    match_ladder: {"TM": FASTA, "TA": FASTA}, the genomes as for normalize, with hap_gap (quasimodo_amd.ladder; needs
+    alleles, WorkflowError before a file is touched otherwise), in place of normalize, atomize, haplotypes and hap_subsets, which
+    the run's call makes itself, all four: final_tables/caller_performance_ladder.tsv (TP, FP, FN, Precision, Recall, F1 by spelling
+    and after normal form, atoms, haplotype and subset, cumulative, then the 15 non-empty method sets of lines and of entries; per
+    caller and mixture, then pooled per caller) and callers/{caller}/ladder/{sample}.{ref}.{caller}.ladder.tsv for every mixed
+    sample (every kept line that is no TP by spelling and every truth entry no kept record spells, with its method set and tier).
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
     _shared_call(votes=votes, boot=bootstrap is not None, strata=strata is not None, motifs=mutation_context is not None,
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
                  context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False,
-                 haplo=haplotypes is not None and not hap_subsets, hapsub=bool(hap_subsets), rescueroc=rescue_roc is not None)
+                 haplo=haplotypes is not None and not hap_subsets, hapsub=bool(hap_subsets), rescueroc=rescue_roc is not None,
+                 ladder=match_ladder is not None)
+    if match_ladder is not None and not alleles:
+        raise WorkflowError("--match-ladder needs --alleles: it combines the matching by normal form, by atoms and by haplotype, which only the allele-extended mode has")
     if rescue_roc is not None and not alleles:
         raise WorkflowError("--rescue-roc needs --alleles: it sweeps the matching by normal form and by atoms, which only the allele-extended mode has")
     if hap_subsets and haplotypes is None:
@@ -245,8 +254,14 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             hgap = check_gap(hap_gap)
         except ValueError as e:
             raise WorkflowError("--hap-gap: %s" % e) from None
+    elif match_ladder is not None:
+        from .haplo import check_gap
+        try:
+            hgap = check_gap(hap_gap)
+        except ValueError as e:
+            raise WorkflowError("--hap-gap: %s" % e) from None
     elif hap_gap is not None:
-        raise WorkflowError("--hap-gap needs --haplotypes")
+        raise WorkflowError("--hap-gap needs --haplotypes or --match-ladder")
     tedges = None
     if by_type is not None and by_type is not False:
         from .vartype import check_edges, parse_edges
@@ -295,7 +310,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 raise WorkflowError("missing input %s" % src)
             plan.append((s, c, src))
     mixes = sorted({s[:2] for s in samples}, reverse=True)              # TM, TA
-    for fastas, what in ((mutation_context, "mutation context"), (seq_context, "sequence context"), (normalize, "normalize"), (rescue_roc, "rescue ROC"), (haplotypes, "haplotypes")):
+    for fastas, what in ((mutation_context, "mutation context"), (seq_context, "sequence context"), (normalize, "normalize"), (rescue_roc, "rescue ROC"), (haplotypes, "haplotypes"), (match_ladder, "match ladder")):
         for mix in mixes if fastas is not None else ():
             if not fastas.get(mix) or not os.path.isfile(fastas.get(mix)):
                 raise WorkflowError("%s: no genome FASTA for %s (%s)" % (what, mix, fastas.get(mix)))
@@ -315,6 +330,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 if not s.endswith(("-1-0", "-0-1")):
                     print("rescue_roc\t%s\t%s" % (c, s))
             print("caller_roc_rescue.tsv\t%s" % ",".join(callers))
+        if match_ladder is not None:
+            print("caller_performance_ladder.tsv\t%s\t%d" % (",".join(callers), hgap))
         if tedges is not None:
             print("caller_performance_types.tsv\t%s\t%s" % (",".join(callers), ",".join(str(e) for e in tedges)))
         if mutation_context is not None:
@@ -393,6 +410,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             jobs[-1].vartype = tedges
         if rescue_roc is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].rescue_roc = rescue_roc[s[:2]]
+        if match_ladder is not None and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].ladder, jobs[-1].ladder_genome = hgap, match_ladder[s[:2]]
+            jobs[-1].ladder_out = os.path.join(d, "ladder", os.path.basename(src)[:-4] + ".ladder.tsv")
         if haplotypes is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].haplo_genome = haplotypes[s[:2]]
             jobs[-1].haplo, jobs[-1].hapsub = (None, hgap) if hap_subsets else (hgap, None)
@@ -474,6 +494,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             write_performance_atomized(os.path.join(tables, "caller_performance_atomized.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
         if rescue_roc is not None:
             _write_rescue_rocs(meta, jobs, snp_dir, tables)
+        if match_ladder is not None:
+            from .ladder import write_performance_ladder
+            write_performance_ladder(os.path.join(tables, "caller_performance_ladder.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
         if tedges is not None:
             from .vartype import write_performance_types
             write_performance_types(os.path.join(tables, "caller_performance_types.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)], tedges)

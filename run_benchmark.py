@@ -158,6 +158,11 @@ def _type_bins(by_type, type_bins):
               help="With --alleles, in place of --normalize and --atomize: sweep the QUAL threshold under the matching by normal form and by atoms "
                    "(precision and recall at every QUAL >= t, as by spelling): write snp/qmvt_roc/*/*.rescue/{spelling,normalized,atomized}_roc.tsv.gz and "
                    "final_tables/caller_roc_rescue.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config).")
+@click.option("--match-ladder", "match_ladder", is_flag=True, default=False,
+              help="With --alleles, in place of --normalize, --atomize, --haplotypes and --hap-subsets, which it always runs, all four: combine them -- "
+                   "TP, FP and FN by spelling and after each method in turn (normal form, atoms, haplotype, subset), cumulative, and how many lines and "
+                   "truth entries every set of methods reaches: write final_tables/caller_performance_ladder.tsv and callers/*/ladder/*.ladder.tsv "
+                   "(needs the genomes: --merlin-ref / --ad169-ref or the config; --hap-gap as for --haplotypes).")
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="With --alleles: also count TP, FP and FN by variant type (SNV, MNP, INS, DEL, complex) and size: write "
                    "final_tables/caller_performance_types.tsv.")
@@ -180,7 +185,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False):
+         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False, match_ladder=False):
     haplotypes = haplotypes or hap_subsets   # the search runs behind the haplotype pass of the same call
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
@@ -196,7 +201,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
     genomes = None
-    if mutation_context or seq_context or normalize or haplotypes or rescue_roc:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+    if mutation_context or seq_context or normalize or haplotypes or rescue_roc or match_ladder:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
         pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
@@ -214,8 +219,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
                                              alleles=alleles, normalize=genomes if normalize else None, atomize=atomize,
                                              by_type=_type_bins(by_type, type_bins), haplotypes=genomes if haplotypes else None,
-                                             hap_gap=_hap_gap(haplotypes, hap_gap), hap_subsets=hap_subsets,
-                                             rescue_roc=genomes if rescue_roc else None)
+                                             hap_gap=_hap_gap(haplotypes or match_ladder, hap_gap), hap_subsets=hap_subsets,
+                                             rescue_roc=genomes if rescue_roc else None, match_ladder=genomes if match_ladder else None)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -271,6 +276,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose MNPs could be split (hcmv has it).")
 @click.option("--rescue-roc", "rescue_roc", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose rescue passes could be swept (hcmv has it).")
+@click.option("--match-ladder", "match_ladder", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose rescue passes could be combined (hcmv has it).")
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose variants could be typed (hcmv has it).")
 @click.option("--type-bins", "type_bins", default=None, help="Not available here (see --by-type).")
@@ -282,9 +289,12 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
             surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False,
-            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False):
+            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False, match_ladder=False):
     from quasimodo_amd import workflow
     try:
+        if match_ladder:
+            raise workflow.WorkflowError("--match-ladder needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --match-ladder)")
         if rescue_roc:
             raise workflow.WorkflowError("--rescue-roc needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --rescue-roc)")
