@@ -11,7 +11,6 @@ constexpr int AFP_OUTSIDE = 1;
 constexpr int AFP_N_GRID = 2;
 constexpr int AFP_EXTRA = 3;
 constexpr int AFP_MAX_CELLS = 8192;      // n_af * n_pos at most: 2 * 8192 u32 = 64 KiB of LDS
-constexpr int AFP_SPANS = 4;             // batch spans (SPAN_TILES tiles of one VCF each) per workgroup
 constexpr int AFP_POS_BITS = 28;         // the reciprocal divides every (pos - 1) < 2^28 exactly
 
 // floor(n / d) for every n < 2^28 as (n * mul) >> shift: shift = 28 + ceil(log2 d), mul = floor(2^shift / d) + 1 < 2^29.

@@ -4,13 +4,11 @@
 // byte, in input order.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the
 // classification pass's profiles are keyed on.
 #include "qmvt_afprofile.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int afp_int4 __attribute__((ext_vector_type(4)));
-typedef float afp_float4 __attribute__((ext_vector_type(4)));
 
 // Adds the workgroup's grids and the lanes' extras to the VCF's rows and clears both.  h: [2][cells] u32 in LDS (at least
 // 2 * AFP_EXTRA words), laid out like the VCF's rows of the output; c: this lane's extras, summed through the first words of h
@@ -39,18 +37,19 @@ __device__ inline void afp_flush(uint32_t* h, uint32_t (&c)[2 * AFP_EXTRA], int 
   __syncthreads();
 }
 
-// One workgroup per AFP_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads).
 template <bool EXT>
 __global__ __launch_bounds__(256) void k_af_profile(AfProfileParams P) {
-  extern __shared__ uint32_t afp_h[];   // [TP, FP][n_af][n_pos]: at most AFP_SPANS * SPAN_TILES * K1_TILE records, u32 suffices
+  extern __shared__ uint32_t afp_h[];   // [TP, FP][n_af][n_pos]: at most PASS_SPANS * SPAN_TILES * K1_TILE records, u32 suffices
   const int cells = P.n_af * P.n_pos;
   for (int i = threadIdx.x; i < max(2 * cells, 2 * AFP_EXTRA); i += blockDim.x) afp_h[i] = 0u;
   __syncthreads();
   uint32_t c[2 * AFP_EXTRA] = {0u, 0u, 0u, 0u, 0u, 0u};
   const float fa = (float)P.n_af;
-  const int s0 = blockIdx.x * AFP_SPANS;
-  const int s1 = min(s0 + AFP_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   bool on = false;
   for (int s = s0; s < s1; ++s) {
@@ -67,8 +66,8 @@ __global__ __launch_bounds__(256) void k_af_profile(AfProfileParams P) {
       if (sd.end - g < 4) kb &= (1u << (uint32_t)(sd.end - g)) - 1u;   // bits past the VCF's last record are not defined
       if (!kb) continue;
       const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> sh) & 15u;
-      const afp_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const afp_int4*>(P.pos + g));      // read once
-      const afp_float4 f4 = __builtin_nontemporal_load(reinterpret_cast<const afp_float4*>(P.af + g));
+      const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));      // read once
+      const qm_float4 f4 = __builtin_nontemporal_load(reinterpret_cast<const qm_float4*>(P.af + g));
       uint32_t ab4 = 0u;   // four allele bytes: ref << 2 | alt, ANIB_NONE when either is not a single base
       if constexpr (EXT) {
         const int4 r4 = *reinterpret_cast<const int4*>(P.ref + g);
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(256) void k_af_profile(AfProfileParams P) {
 
 void launch_af_profile(const AfProfileParams& P, bool ext, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + AFP_SPANS - 1) / AFP_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   const size_t lds = std::max((size_t)2 * (size_t)P.n_af * (size_t)P.n_pos, (size_t)2 * AFP_EXTRA) * sizeof(uint32_t);
   if (ext) hipLaunchKernelGGL(k_af_profile<true>, grid, dim3(256), lds, st, P);
   else hipLaunchKernelGGL(k_af_profile<false>, grid, dim3(256), lds, st, P);

@@ -8,7 +8,6 @@ namespace qm {
 
 constexpr int ATOM_R_COLS = 13;              // include/qmvt.h QM_ATOM_R_COLS
 constexpr int ATOM_T_COLS = 6;               // QM_ATOM_T_COLS
-constexpr int ATOM_SPANS = 4;                // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_atom_records
 constexpr uint32_t ATOM_MIN_SLOTS = 64u;     // the smallest set: two words of the atom bitmap
 constexpr uint32_t ATOM_EMPTY = 0xffffffffu; // no atom: an atom's REF and ALT differ, so its low nibble is never 15
 // class bytes (QM_ATOM_C_*)

@@ -5,13 +5,11 @@
 // carried by kept records.  Integer work only: no output depends on the order the lanes run in.  Its own translation unit:
 // qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
 #include "qmvt_atom.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int at_int4 __attribute__((ext_vector_type(4)));
-typedef unsigned at_uint2 __attribute__((ext_vector_type(2)));
 
 // inline codes (include/qmvt.h): 0 .. 3 one base, len << 26 | bases for 2 .. 13 bases
 __device__ inline bool at_inline(int32_t c) {
@@ -127,18 +125,19 @@ __global__ __launch_bounds__(256) void k_atom_truth(AtomTable T) {
   }
 }
 
-// One workgroup per ATOM_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte accesses).  Every lane stays
 // in the loop for all of a span's steps: the wave's ballots need them together.  The counters are wave-uniform registers (the
 // two atom sums: one register per lane, reduced over the wave at the flush), added to LDS and from there to the VCF's row when
 // the VCF changes.
 __global__ __launch_bounds__(256) void k_atom_records(AtomRecParams P) {
-  __shared__ uint32_t cnt[ATOM_R_COLS];   // at most ATOM_SPANS * SPAN_TILES * K1_TILE records of at most 13 atoms per workgroup: u32 suffices
+  __shared__ uint32_t cnt[ATOM_R_COLS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE records of at most 13 atoms per workgroup: u32 suffices
   if (threadIdx.x < ATOM_R_COLS) cnt[threadIdx.x] = 0u;
   __syncthreads();
   const int lane = (int)(threadIdx.x & 63u);
-  const int s0 = blockIdx.x * ATOM_SPANS;
-  const int s1 = min(s0 + ATOM_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   uint32_t acc[ATOM_R_COLS];
 #pragma unroll
   for (int c = 0; c < ATOM_R_COLS; ++c) acc[c] = 0u;
@@ -155,12 +154,7 @@ __global__ __launch_bounds__(256) void k_atom_records(AtomRecParams P) {
     }
 #pragma unroll
     for (int c = 0; c < ATOM_R_COLS; ++c) acc[c] = 0u;
-    __syncthreads();
-    if (threadIdx.x < ATOM_R_COLS && cnt[threadIdx.x]) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * ATOM_R_COLS + threadIdx.x), (unsigned long long)cnt[threadIdx.x]);
-      cnt[threadIdx.x] = 0u;
-    }
-    __syncthreads();
+    flush_counts(cnt, ATOM_R_COLS, reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * ATOM_R_COLS));
   };
   for (int s = s0; s < s1; ++s) {
     const SpanDesc sd = P.spans[s];
@@ -176,12 +170,12 @@ __global__ __launch_bounds__(256) void k_atom_records(AtomRecParams P) {
         const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (bits and columns past the VCF's last record are not defined)
         const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & 15u;
         const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-        const at_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const at_int4*>(P.pos + g));   // read once
-        const at_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const at_int4*>(P.ref + g));
-        const at_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const at_int4*>(P.alt + g));
+        const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
+        const qm_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.ref + g));
+        const qm_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.alt + g));
         const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
         uint32_t c4 = 0u, n4 = 0u;
-        at_uint2 h4 = {0u, 0u};
+        qm_uint2 h4 = {0u, 0u};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           if ((uint32_t)k >= nrec) continue;
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(256) void k_atom_records(AtomRecParams P) {
         if (P.cls) {
           *reinterpret_cast<uint32_t*>(P.cls + g) = c4;
           *reinterpret_cast<uint32_t*>(P.n_atoms + g) = n4;
-          *reinterpret_cast<at_uint2*>(P.hit_mask + g) = h4;
+          *reinterpret_cast<qm_uint2*>(P.hit_mask + g) = h4;
         }
       }
 #pragma unroll
@@ -294,7 +288,7 @@ void launch_atom_truth(const AtomTable& T, hipStream_t st) {
 
 void launch_atom_records(const AtomRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + ATOM_SPANS - 1) / ATOM_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   hipLaunchKernelGGL(k_atom_records, grid, dim3(256), 0, st, P);
 }
 

@@ -8,7 +8,6 @@ namespace qm {
 
 constexpr int BOOT_MAX_WINDOWS = 4096;     // include/qmvt.h QM_BOOT_MAX_WINDOWS: [4096 + 2][2] u32 counters = 32 784 B of LDS
 constexpr int BOOT_MAX_REP = 16384;        // QM_BOOT_MAX_REP
-constexpr int BOOT_SPANS = 4;              // batch spans (SPAN_TILES tiles of one VCF each) per workgroup
 constexpr int BOOT_COLS = 4;               // kept lines, TP lines, truth keys, hit keys
 constexpr int BOOT_VCF_SPLIT = 64;         // at most this many workgroups share the VCFs of one replicate
 // The reduction that the wave's ballot replaced stays buildable, not shipped: -DQM_BOOT_VARIANT=1 one LDS atomic per counted

@@ -5,12 +5,12 @@
 // sums per VCF.  Integers only.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the
 // classification pass's profiles are keyed on.
 #include "qmvt_boot.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
 
-typedef int bt_int4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long bt_u64x2 __attribute__((ext_vector_type(2)));
 
 // Adds the workgroup's counters to the VCF's rows and clears them.  c: [n_win + 2][2] u32 in LDS (kept, TP); out: the VCF's
@@ -51,18 +51,19 @@ __device__ inline void boot_count(uint32_t* c, bool in, bool tp, int32_t row, bo
   }
 }
 
-// One workgroup per BOOT_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads).  Every lane stays
 // in the loop for all of a span's steps: the wave's ballots need them together.
 __global__ __launch_bounds__(256) void k_boot_records(BootRecParams P) {
-  extern __shared__ uint32_t boot_c[];   // [n_win + 2][2]: at most BOOT_SPANS * SPAN_TILES * K1_TILE = 65 536 records, u32 suffices
+  extern __shared__ uint32_t boot_c[];   // [n_win + 2][2]: at most PASS_SPANS * SPAN_TILES * K1_TILE = 65 536 records, u32 suffices
   const int32_t nw = P.n_win;
   const int words = 2 * (nw + 2);
   for (int i = threadIdx.x; i < words; i += blockDim.x) boot_c[i] = 0u;
   __syncthreads();
   const bool first = (threadIdx.x & 63u) == 0u;
-  const int s0 = blockIdx.x * BOOT_SPANS;
-  const int s1 = min(s0 + BOOT_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   for (int s = s0; s < s1; ++s) {
     const SpanDesc sd = P.spans[s];
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void k_boot_records(BootRecParams P) {
       int32_t row[4] = {0, 0, 0, 0};
       if (kb) {
         tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-        const bt_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const bt_int4*>(P.pos + g));   // read once
+        const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
         const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void k_boot_resample(const uint64_t* cnt, int 
 
 void launch_boot_records(const BootRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + BOOT_SPANS - 1) / BOOT_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   hipLaunchKernelGGL(k_boot_records, grid, dim3(256), (size_t)2 * (size_t)(P.n_win + 2) * sizeof(uint32_t), st, P);
 }
 

@@ -13,7 +13,6 @@ constexpr int CX_MAX_CELLS = CX_HP_ROWS * CX_MAX_GC_BINS + 1;   // the grid and 
 constexpr uint32_t CX_NONE = 255u;           // the table's byte of a position without a cell
 constexpr int CX_TILE = 4096;                // positions per workgroup of k_context_build: 16 per lane, one 16-byte store
 constexpr int CX_STAGE = CX_TILE + 2 * CX_MAX_HALF_WINDOW;   // the tile and its halo: 24 staged positions per lane
-constexpr int CX_SPANS = 4;                  // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_context_records
 // The reduction that lost the A/B of LABNOTES round 17 stays buildable, not shipped: -DQM_CX_VARIANT=1 a wave's records of one cell
 // are added once (ballot / match on the cell) instead of one LDS atomic per record.  The outputs are the same.
 #ifndef QM_CX_VARIANT

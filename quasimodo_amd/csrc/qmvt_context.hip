@@ -6,13 +6,11 @@
 // only.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's
 // profiles are keyed on.
 #include "qmvt_context.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int cx_int4 __attribute__((ext_vector_type(4)));
-typedef uint32_t cx_uint4 __attribute__((ext_vector_type(4)));
 
 static_assert(CX_TILE == 16 * 256 && CX_STAGE == 24 * 256, "k_context_build: 16 positions and 24 staged positions per lane");
 static_assert(CX_MAX_HALF_WINDOW % 8 == 0 && CX_TILE % 16 == 0, "a lane's staged positions are whole genome words");
@@ -112,9 +110,9 @@ __global__ __launch_bounds__(256) void k_context_build(ContextBuildParams P) {
       }
       cells[k >> 2] |= cell << (8 * (k & 3));
     }
-    cx_uint4 v4;
+    qm_uint4 v4;
     v4.x = cells[0]; v4.y = cells[1]; v4.z = cells[2]; v4.w = cells[3];
-    *reinterpret_cast<cx_uint4*>(P.tab + i0) = v4;
+    *reinterpret_cast<qm_uint4*>(P.tab + i0) = v4;
   }
   __syncthreads();
   for (int i = t; i < n_cells; i += 256)
@@ -168,19 +166,20 @@ __device__ inline void cx_count(uint32_t* cnt, bool in, bool tp, uint32_t row, i
   }
 }
 
-// One workgroup per CX_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads).  Every lane stays
 // in the loop for all of a span's steps: the wave's ballots need them together.
 template <bool AGG>
 __global__ __launch_bounds__(256) void k_context_records(ContextRecParams P) {
-  __shared__ uint32_t cnt[2 * (CX_MAX_CELLS + 1)];   // at most CX_SPANS * SPAN_TILES * K1_TILE = 65 536 records: u32 suffices
+  __shared__ uint32_t cnt[2 * (CX_MAX_CELLS + 1)];   // at most PASS_SPANS * SPAN_TILES * K1_TILE = 65 536 records: u32 suffices
   const uint32_t none = (uint32_t)(CX_HP_ROWS * P.ng);
   const int words = 2 * ((int)none + 2);   // the grid, NONE, nokey
   for (int i = threadIdx.x; i < 2 * (CX_MAX_CELLS + 1); i += blockDim.x) cnt[i] = 0u;
   __syncthreads();
   const int lane = (int)(threadIdx.x & 63u);
-  const int s0 = blockIdx.x * CX_SPANS;
-  const int s1 = min(s0 + CX_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   ContextTab T{nullptr, 0};
   for (int s = s0; s < s1; ++s) {
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(256) void k_context_records(ContextRecParams P) {
       uint32_t row[4] = {0u, 0u, 0u, 0u};
       if (kb) {
         tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-        const cx_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const cx_int4*>(P.pos + g));   // read once
+        const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
         const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -244,7 +243,7 @@ void launch_context_build(const ContextBuildParams& P, hipStream_t st) {
 
 void launch_context_records(const ContextRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + CX_SPANS - 1) / CX_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   hipLaunchKernelGGL(k_context_records<CX_AGGREGATE>, grid, dim3(256), 0, st, P);
 }
 

@@ -11,7 +11,6 @@ constexpr int HAP_T_COLS = 8;                // QM_HAP_T_COLS
 constexpr int HAP_MAX_GAP = 32;              // QM_HAP_MAX_GAP
 constexpr int HAP_MAX_WINDOW = 256;          // QM_HAP_MAX_WINDOW
 constexpr int HAP_MAX_ITEMS = 8;             // QM_HAP_MAX_ITEMS
-constexpr int HAP_SPANS = 4;                 // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of the record walks
 constexpr int HAP_PAIR_WORDS = HAP_MAX_ITEMS + 3;   // a (VCF, open site) pair: VCF, site, count of open lines, their record indices
 // class bytes (QM_HAP_C_*); HAP_PENDING lives between k_hap_records and k_hap_claim / k_hap_replay only
 constexpr uint32_t HAP_MATCHED = 0u, HAP_RESCUED = 1u, HAP_OUTSIDE = 2u, HAP_LONE = 3u, HAP_MISMATCH = 4u, HAP_CONFLICT = 5u,

@@ -8,12 +8,11 @@
 // no output depends on the order the lanes run in.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h)
 // stays the id the classification pass's profiles are keyed on.
 #include "qmvt_haplo.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int hp_int4 __attribute__((ext_vector_type(4)));
 
 constexpr int32_t HP_NO_HI = -(1 << 30);   // the largest footprint end before the first usable entry
 
@@ -158,88 +157,76 @@ __global__ __launch_bounds__(256) void k_hap_windows(HapSites S) {
 }
 
 // ---- the records ----
-// One workgroup per HAP_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
-// begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte accesses).  Every kept
-// record adds to its columns of the workgroup's LDS row, which goes to the VCF's row when the VCF changes.  A kept, usable,
-// unmatched record inside the window of a site that is not TOOLONG stays HAP_PENDING for k_hap_claim.
+// The span walk of qmvt_walk.h, 4 records per lane (aligned 16-byte / 4-byte accesses).  Every kept record adds to its columns
+// of the workgroup's LDS row, which goes to the VCF's row when the VCF changes.  A kept, usable, unmatched record inside the
+// window of a site that is not TOOLONG stays HAP_PENDING for k_hap_claim.
 __global__ __launch_bounds__(256) void k_hap_records(HapRecParams P) {
-  __shared__ uint32_t hist[HAP_R_COLS];   // at most HAP_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  __shared__ uint32_t hist[HAP_R_COLS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
   if (threadIdx.x < HAP_R_COLS) hist[threadIdx.x] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * HAP_SPANS;
-  const int s1 = min(s0 + HAP_SPANS, P.n_spans);
-  int cur = -1;
-  auto flush = [&]() {   // (uniform over the workgroup)
-    __syncthreads();
-    if (threadIdx.x < HAP_R_COLS && hist[threadIdx.x]) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * HAP_R_COLS + threadIdx.x), (unsigned long long)hist[threadIdx.x]);
-      hist[threadIdx.x] = 0u;
-    }
-    __syncthreads();
-  };
-  for (int s = s0; s < s1; ++s) {
-    const SpanDesc sd = P.spans[s];
-    if (sd.vcf != cur) {
-      if (cur >= 0) flush();
-      cur = sd.vcf;
-    }
-    const HapVcf& V = P.vcfs[cur];
-    if (!V.s.words) continue;   // (uniform over the workgroup)
-    const int32_t ns = V.s.n_sites[0];
-    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
-      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
-      if (g >= sd.end) continue;
-      const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (bits and columns past the VCF's last record are not defined)
-      const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & 15u;
-      const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-      const hp_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const hp_int4*>(P.pos + g));   // read once
-      const hp_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const hp_int4*>(P.ref + g));
-      const hp_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const hp_int4*>(P.alt + g));
-      const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
-      hp_int4 st4 = {-1, -1, -1, -1};
-      uint32_t c4 = 0u;
+  const HapVcf* vp = nullptr;
+  int32_t ns = 0;
+  walk_spans<4>(
+      P.spans, P.n_spans,
+      [&](int vcf, const SpanDesc&) {
+        vp = P.vcfs + vcf;
+        if (!vp->s.words) return false;
+        ns = vp->s.n_sites[0];
+        return true;
+      },
+      [&](int, const SpanDesc& sd, int64_t g) {
+        if (g >= sd.end) return;
+        const HapVcf& V = *vp;
+        const uint32_t live = rec_live<4>(g, sd.end);
+        const uint32_t kb = mask_bits<4>(P.mask_pass, g);
+        const uint32_t tb = mask_bits<4>(P.mask_tp, g);
+        const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
+        const qm_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.ref + g));
+        const qm_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.alt + g));
+        const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
+        qm_int4 st4 = {-1, -1, -1, -1};
+        uint32_t c4 = 0u;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if ((uint32_t)k >= nrec) continue;
-        const bool kept = (kb >> k) & 1u, tp = (tb >> k) & 1u, nokey = ((f4 >> (8 * k)) & QMF_NOKEY) != 0u;
-        const int32_t p = p4[k], r = r4[k], a = a4[k];
-        int64_t e = -1;
-        if (!nokey && allele_valid(r) && allele_valid(a) && (uint32_t)p < (1u << 28)) e = hp_entry(V.s, p, r, a);
-        const uint32_t why = hp_why(V.s.words, V.s.len, p, r, a, nokey);
-        int32_t st = -1;
-        if (!why) {
-          int32_t q;
-          uint32_t tr, ta, ab;
-          hp_trim(p, r, a, q, tr, ta, ab);
-          st = hp_site(V.s, ns, q, max(q, q + (int32_t)tr - 1));
+        for (int k = 0; k < 4; ++k) {
+          if (!((live >> k) & 1u)) continue;
+          const bool kept = (kb >> k) & 1u, tp = (tb >> k) & 1u, nokey = ((f4 >> (8 * k)) & QMF_NOKEY) != 0u;
+          const int32_t p = p4[k], r = r4[k], a = a4[k];
+          int64_t e = -1;
+          if (!nokey && allele_valid(r) && allele_valid(a) && (uint32_t)p < (1u << 28)) e = hp_entry(V.s, p, r, a);
+          const uint32_t why = hp_why(V.s.words, V.s.len, p, r, a, nokey);
+          int32_t st = -1;
+          if (!why) {
+            int32_t q;
+            uint32_t tr, ta, ab;
+            hp_trim(p, r, a, q, tr, ta, ab);
+            st = hp_site(V.s, ns, q, max(q, q + (int32_t)tr - 1));
+          }
+          uint32_t c;
+          if (e >= 0) c = HAP_MATCHED;
+          else if (why) c = why;
+          else if (!kept) c = HAP_NOTKEPT;
+          else if (st < 0) c = HAP_OUTSIDE;
+          else c = V.s.shi[st] - V.s.slo[st] + 1 > HAP_MAX_WINDOW ? HAP_TOOLONG : HAP_PENDING;
+          st4[k] = st;
+          c4 |= c << (8 * k);
+          if (!kept) continue;
+          atomicAdd(hist + HAP_R_KEPT, 1u);
+          if (tp) {
+            atomicAdd(hist + HAP_R_TP, 1u);
+            atomicAdd(hist + HAP_R_TP_H, 1u);
+          }
+          if (e >= 0) {
+            const uint32_t bit = 1u << ((uint32_t)e & 31u);
+            if (!(V.ebits[e >> 5] & bit)) atomicOr(V.ebits + (e >> 5), bit);   // (a stale read only repeats the atomic)
+          } else {
+            if (c == HAP_PENDING || c == HAP_TOOLONG) atomicAdd(hist + HAP_R_OPEN, 1u);
+            if (c != HAP_PENDING) atomicAdd(hist + HAP_R_CLASS0 + c, 1u);
+          }
         }
-        uint32_t c;
-        if (e >= 0) c = HAP_MATCHED;
-        else if (why) c = why;
-        else if (!kept) c = HAP_NOTKEPT;
-        else if (st < 0) c = HAP_OUTSIDE;
-        else c = V.s.shi[st] - V.s.slo[st] + 1 > HAP_MAX_WINDOW ? HAP_TOOLONG : HAP_PENDING;
-        st4[k] = st;
-        c4 |= c << (8 * k);
-        if (!kept) continue;
-        atomicAdd(hist + HAP_R_KEPT, 1u);
-        if (tp) {
-          atomicAdd(hist + HAP_R_TP, 1u);
-          atomicAdd(hist + HAP_R_TP_H, 1u);
-        }
-        if (e >= 0) {
-          const uint32_t bit = 1u << ((uint32_t)e & 31u);
-          if (!(V.ebits[e >> 5] & bit)) atomicOr(V.ebits + (e >> 5), bit);   // (a stale read only repeats the atomic)
-        } else {
-          if (c == HAP_PENDING || c == HAP_TOOLONG) atomicAdd(hist + HAP_R_OPEN, 1u);
-          if (c != HAP_PENDING) atomicAdd(hist + HAP_R_CLASS0 + c, 1u);
-        }
-      }
-      *reinterpret_cast<uint32_t*>(P.cls + g) = c4;
-      *reinterpret_cast<hp_int4*>(P.site + g) = st4;
-    }
-  }
-  if (cur >= 0) flush();
+        *reinterpret_cast<uint32_t*>(P.cls + g) = c4;
+        *reinterpret_cast<qm_int4*>(P.site + g) = st4;
+      },
+      [&](int vcf) { flush_counts(hist, HAP_R_COLS, reinterpret_cast<unsigned long long*>(P.rec + (int64_t)vcf * HAP_R_COLS)); });
 }
 
 // ---- the truth side ----
@@ -335,53 +322,47 @@ __global__ __launch_bounds__(256) void k_hap_claim(HapRecParams P) {
   __shared__ uint32_t hist[2];
   if (threadIdx.x < 2) hist[threadIdx.x] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * HAP_SPANS;
-  const int s1 = min(s0 + HAP_SPANS, P.n_spans);
-  int cur = -1;
-  auto flush = [&]() {   // (uniform over the workgroup)
-    __syncthreads();
-    if (threadIdx.x < 2 && hist[threadIdx.x]) {
-      const int col = HAP_R_CLASS0 + (int)(threadIdx.x ? HAP_TOOMANY : HAP_LONE);
-      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * HAP_R_COLS + col), (unsigned long long)hist[threadIdx.x]);
-      hist[threadIdx.x] = 0u;
-    }
-    __syncthreads();
-  };
-  for (int s = s0; s < s1; ++s) {
-    const SpanDesc sd = P.spans[s];
-    if (sd.vcf != cur) {
-      if (cur >= 0) flush();
-      cur = sd.vcf;
-    }
-    const HapVcf& V = P.vcfs[cur];
-    if (!V.s.words) continue;   // (uniform over the workgroup)
-    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
-      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
-      if (g >= sd.end) continue;
-      const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);
-      const uint32_t c4 = *reinterpret_cast<const uint32_t*>(P.cls + g);
-      uint32_t o4 = c4;
+  const HapVcf* vp = nullptr;
+  walk_spans<4>(
+      P.spans, P.n_spans,
+      [&](int vcf, const SpanDesc&) {
+        vp = P.vcfs + vcf;
+        return vp->s.words != nullptr;
+      },
+      [&](int, const SpanDesc& sd, int64_t g) {
+        if (g >= sd.end) return;
+        const HapVcf& V = *vp;
+        const uint32_t live = rec_live<4>(g, sd.end);
+        const uint32_t c4 = *reinterpret_cast<const uint32_t*>(P.cls + g);
+        uint32_t o4 = c4;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if ((uint32_t)k >= nrec || ((c4 >> (8 * k)) & 255u) != HAP_PENDING) continue;
-        const int32_t st = P.site[g + k];
-        const uint32_t word = V.sbits[st >> 5], below = (1u << ((uint32_t)st & 31u)) - 1u;
-        uint32_t c = HAP_LONE;
-        if ((word >> ((uint32_t)st & 31u)) & 1u) {
-          int32_t* pr = P.pairs + ((int64_t)V.srank[st >> 5] + __popc(word & below)) * HAP_PAIR_WORDS;
-          const int32_t slot = atomicAdd(pr + 2, 1);
-          c = HAP_PENDING;   // (k_hap_replay writes it)
-          if (slot < HAP_MAX_ITEMS) pr[3 + slot] = (int32_t)(g + k - V.off);
-          else c = HAP_TOOMANY;
+        for (int k = 0; k < 4; ++k) {
+          if (!((live >> k) & 1u) || ((c4 >> (8 * k)) & 255u) != HAP_PENDING) continue;
+          const int32_t st = P.site[g + k];
+          const uint32_t word = V.sbits[st >> 5], below = (1u << ((uint32_t)st & 31u)) - 1u;
+          uint32_t c = HAP_LONE;
+          if ((word >> ((uint32_t)st & 31u)) & 1u) {
+            int32_t* pr = P.pairs + ((int64_t)V.srank[st >> 5] + __popc(word & below)) * HAP_PAIR_WORDS;
+            const int32_t slot = atomicAdd(pr + 2, 1);
+            c = HAP_PENDING;   // (k_hap_replay writes it)
+            if (slot < HAP_MAX_ITEMS) pr[3 + slot] = (int32_t)(g + k - V.off);
+            else c = HAP_TOOMANY;
+          }
+          if (c == HAP_LONE) atomicAdd(hist, 1u);
+          if (c == HAP_TOOMANY) atomicAdd(hist + 1, 1u);
+          o4 = (o4 & ~(255u << (8 * k))) | (c << (8 * k));
         }
-        if (c == HAP_LONE) atomicAdd(hist, 1u);
-        if (c == HAP_TOOMANY) atomicAdd(hist + 1, 1u);
-        o4 = (o4 & ~(255u << (8 * k))) | (c << (8 * k));
-      }
-      if (o4 != c4) *reinterpret_cast<uint32_t*>(P.cls + g) = o4;
-    }
-  }
-  if (cur >= 0) flush();
+        if (o4 != c4) *reinterpret_cast<uint32_t*>(P.cls + g) = o4;
+      },
+      [&](int vcf) {   // (the two cells are columns apart in the VCF's row: a flush of its own)
+        __syncthreads();
+        if (threadIdx.x < 2 && hist[threadIdx.x]) {
+          const int col = HAP_R_CLASS0 + (int)(threadIdx.x ? HAP_TOOMANY : HAP_LONE);
+          atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)vcf * HAP_R_COLS + col), (unsigned long long)hist[threadIdx.x]);
+          hist[threadIdx.x] = 0u;
+        }
+        __syncthreads();
+      });
 }
 
 // ---- the replay ----
@@ -826,7 +807,7 @@ void launch_hap_sites(const HapSites& S, hipStream_t st) {
 
 void launch_hap_records(const HapRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  hipLaunchKernelGGL(k_hap_records, dim3((unsigned)((P.n_spans + HAP_SPANS - 1) / HAP_SPANS)), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_hap_records, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 // (the y dimension of a grid holds 65535 blocks: qm_batch_haplotypes refuses a batch of more VCFs)
@@ -843,7 +824,7 @@ void launch_hap_claim(const HapRecParams& P, int n_vcf, int64_t max_entries, hip
   const HapVcf* vcfs = P.vcfs;
   int32_t* pairs = P.pairs;
   hipLaunchKernelGGL(k_hap_pairs, dim3(gx, (unsigned)n_vcf), dim3(256), 0, st, vcfs, pairs);
-  hipLaunchKernelGGL(k_hap_claim, dim3((unsigned)((P.n_spans + HAP_SPANS - 1) / HAP_SPANS)), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_hap_claim, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 void launch_hap_replay(const HapReplayParams& P, hipStream_t st) {

@@ -9,7 +9,6 @@
 namespace qm {
 
 constexpr int LADDER_COLS = 18;              // include/qmvt.h QM_LADDER_COLS: two totals, then the 16 cells of the four method bits
-constexpr int LADDER_SPANS = 4;              // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_ladder_records
 // the bits of a mask byte (QM_LADDER_M_*)
 constexpr uint32_t LADDER_N = 1u, LADDER_A = 2u, LADDER_H = 4u, LADDER_B = 8u, LADDER_K = 64u, LADDER_S = 128u;
 // LadderVcf::has

@@ -6,21 +6,20 @@
 // work only: no output depends on the order the lanes run in.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip +
 // qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
 #include "qmvt_ladder.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
 
-typedef unsigned ld_uint4 __attribute__((ext_vector_type(4)));
-
 // 16 bytes of a column; a lane at its VCF's tail reads the nrec < 16 bytes the VCF has, one by one
-__device__ inline ld_uint4 ld_load16(const uint8_t* p, uint32_t nrec) {
-  if (nrec >= 16u) return __builtin_nontemporal_load(reinterpret_cast<const ld_uint4*>(p));   // read once
+__device__ inline qm_uint4 ld_load16(const uint8_t* p, uint32_t nrec) {
+  if (nrec >= 16u) return __builtin_nontemporal_load(reinterpret_cast<const qm_uint4*>(p));   // read once
   uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (uint32_t k = 0; k < 16u; ++k)
     if (k < nrec) w[k >> 2] |= (uint32_t)p[k] << (8u * (k & 3u));
-  ld_uint4 v = {w[0], w[1], w[2], w[3]};
+  qm_uint4 v = {w[0], w[1], w[2], w[3]};
   return v;
 }
 
@@ -80,16 +79,17 @@ __device__ inline int32_t ld_atom_probe(const AtomTable& T, uint32_t key) {
   return -1;
 }
 
-// One workgroup per LADDER_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans the register counts of this kernel end up in scratch memory).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 16 t + 4096 i .. + 15 (every span starts at a multiple of 256 records: aligned 16-byte loads, and the 16 bits of either
 // record mask sit in one word).  Every lane counts its own records by popcounts of 16-bit masks, in registers; the counts go to
 // the LDS histogram and from there to the VCF's 64-bit row when the VCF changes and at the end.
 __global__ __launch_bounds__(256) void k_ladder_records(LadderRecParams P) {
-  __shared__ uint32_t cnt[LADDER_COLS];   // at most LADDER_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  __shared__ uint32_t cnt[LADDER_COLS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
   if (threadIdx.x < LADDER_COLS) cnt[threadIdx.x] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * LADDER_SPANS;
-  const int s1 = min(s0 + LADDER_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   uint32_t acc[LADDER_COLS];
 #pragma unroll
   for (int c = 0; c < LADDER_COLS; ++c) acc[c] = 0u;
@@ -100,12 +100,7 @@ __global__ __launch_bounds__(256) void k_ladder_records(LadderRecParams P) {
       if (acc[c]) atomicAdd(cnt + c, acc[c]);
       acc[c] = 0u;
     }
-    __syncthreads();
-    if (threadIdx.x < LADDER_COLS && cnt[threadIdx.x]) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * LADDER_COLS + threadIdx.x), (unsigned long long)cnt[threadIdx.x]);
-      cnt[threadIdx.x] = 0u;
-    }
-    __syncthreads();
+    flush_counts(cnt, LADDER_COLS, reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * LADDER_COLS));
   };
   for (int s = s0; s < s1; ++s) {
     const SpanDesc sd = P.spans[s];
@@ -122,11 +117,11 @@ __global__ __launch_bounds__(256) void k_ladder_records(LadderRecParams P) {
       const uint32_t live = (1u << nrec) - 1u;
       const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & live;
       const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & kb;
-      const ld_uint4 f16 = ld_load16(P.flags + g, nrec);
-      const ld_uint4 n16 = ld_load16(P.cls_n + g, nrec);
-      const ld_uint4 a16 = ld_load16(P.cls_a + g, nrec);
-      const ld_uint4 h16 = ld_load16(P.cls_h + g, nrec);
-      ld_uint4 b16 = {0u, 0u, 0u, 0u};
+      const qm_uint4 f16 = ld_load16(P.flags + g, nrec);
+      const qm_uint4 n16 = ld_load16(P.cls_n + g, nrec);
+      const qm_uint4 a16 = ld_load16(P.cls_a + g, nrec);
+      const qm_uint4 h16 = ld_load16(P.cls_h + g, nrec);
+      qm_uint4 b16 = {0u, 0u, 0u, 0u};
       if (sub) b16 = ld_load16(P.cls_b + g, nrec);
       uint32_t mN = 0u, mA = 0u, mH = 0u, mB = 0u, mI = 0u;   // bit k: record k has the class, or QMF_IDDOT
 #pragma unroll
@@ -162,8 +157,8 @@ __global__ __launch_bounds__(256) void k_ladder_records(LadderRecParams P) {
           o[k >> 2] |= byte << (8 * (k & 3));
         }
         if (nrec >= 16u) {
-          const ld_uint4 v = {o[0], o[1], o[2], o[3]};
-          *reinterpret_cast<ld_uint4*>(P.mask + g) = v;
+          const qm_uint4 v = {o[0], o[1], o[2], o[3]};
+          *reinterpret_cast<qm_uint4*>(P.mask + g) = v;
         } else {
 #pragma unroll
           for (uint32_t k = 0; k < 16u; ++k)
@@ -238,8 +233,7 @@ __global__ __launch_bounds__(256) void k_ladder_truth(LadderTruthParams P) {
 
 void launch_ladder_records(const LadderRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + LADDER_SPANS - 1) / LADDER_SPANS));
-  hipLaunchKernelGGL(k_ladder_records, grid, dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_ladder_records, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 void launch_ladder_truth(const LadderTruthParams& P, int64_t max_entries, hipStream_t st) {

@@ -10,7 +10,6 @@ constexpr int MOTIF_COLS = 98;           // include/qmvt.h QM_MOTIF_COLS: 96 mot
 constexpr int MOTIF_OTHER = 96;
 constexpr int MOTIF_REF_MISMATCH = 97;
 constexpr int MOTIF_ROW_WORDS = 3 * MOTIF_COLS;   // kept, TP, FP
-constexpr int MOTIF_SPANS = 4;           // batch spans (SPAN_TILES tiles of one VCF each) per workgroup
 constexpr uint32_t GENOME_NOBASE = 15u;  // 4-bit genome code of a byte that is not ACGTacgt
 
 // One genome as the device holds it: base i in bits 4 (i % 8) .. + 3 of word i / 8 (A=0 C=1 G=2 T=3, GENOME_NOBASE

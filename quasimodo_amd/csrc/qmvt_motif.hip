@@ -4,6 +4,7 @@
 // a 4-bit packed genome that sits in L2.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id
 // the classification pass's profiles are keyed on.
 #include "qmvt_motif.h"
+#include "qmvt_walk.h"
 
 namespace qm {
 
@@ -21,15 +22,17 @@ __device__ inline void motif_flush(uint32_t* h, uint64_t* out) {
   __syncthreads();
 }
 
-// One workgroup per MOTIF_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out, in the form in which every lane leaves on its own: the body holds no wave-wide operation and must
+// not gain one (through walk_spans k_motif<true> needs 82 registers for 72 and loses two waves per SIMD).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads).
 template <bool EXT>
 __global__ __launch_bounds__(256) void k_motif(MotifParams P) {
-  __shared__ uint32_t h[2 * MOTIF_COLS];   // [TP, FP][MOTIF_COLS]: at most MOTIF_SPANS * SPAN_TILES * K1_TILE records, u32 suffices
+  __shared__ uint32_t h[2 * MOTIF_COLS];   // [TP, FP][MOTIF_COLS]: at most PASS_SPANS * SPAN_TILES * K1_TILE records, u32 suffices
   for (int i = threadIdx.x; i < 2 * MOTIF_COLS; i += blockDim.x) h[i] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * MOTIF_SPANS;
-  const int s1 = min(s0 + MOTIF_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   GenomeRef G{nullptr, 0};
   for (int s = s0; s < s1; ++s) {
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(256) void k_motif(MotifParams P) {
 
 void launch_motif(const MotifParams& P, bool ext, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + MOTIF_SPANS - 1) / MOTIF_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   if (ext) hipLaunchKernelGGL(k_motif<true>, grid, dim3(256), 0, st, P);
   else hipLaunchKernelGGL(k_motif<false>, grid, dim3(256), 0, st, P);
 }

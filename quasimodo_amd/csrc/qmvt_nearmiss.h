@@ -6,7 +6,6 @@
 
 namespace qm {
 
-constexpr int NM_SPANS = 4;              // batch spans per workgroup (k_truth_hits' frame)
 constexpr int NM_PLANES = 4;             // FILTERED, ALLELE, POSITION, NEAR: one bit per truth key each, laid out like the hit bitmap
 constexpr int NM_LDS_WORDS = 1024;       // words of every plane a workgroup collects in LDS (4 x 4 KB: truth sets up to 32 768 keys)
 constexpr int NM_MAX_RADIUS = 64;        // include/qmvt.h QM_NM_MAX_RADIUS

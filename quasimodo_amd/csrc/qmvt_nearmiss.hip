@@ -6,17 +6,16 @@
 // k_truth_hits to the classes of the missed keys.  Its own translation unit: qm_kernels_id stays the id the classification
 // pass's profiles are keyed on.
 #include "qmvt_nearmiss.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
 
-typedef int32_t v4i __attribute__((ext_vector_type(4)));
-
 // a lane's class counts between two flushes, 10 bits per class in one register pair: it sees at most 8 records per 2048 of
-// NM_SPANS spans
+// PASS_SPANS spans
 constexpr int NM_CNT_BITS = 10;
-static_assert((int64_t)NM_SPANS * SPAN_TILES * K1_TILE / 256 < (1 << NM_CNT_BITS), "packed per-lane class counts");
+static_assert((int64_t)PASS_SPANS * SPAN_TILES * K1_TILE / 256 < (1 << NM_CNT_BITS), "packed per-lane class counts");
 static_assert(NM_R_CLASSES * NM_CNT_BITS <= 64, "packed per-lane class counts");
 
 // Behind the last record of a VCF inside the workgroup: the lanes' class counts meet in LDS and leave as one 64-bit atomic per
@@ -48,103 +47,97 @@ __device__ inline void nearmiss_flush(uint32_t* lds, uint32_t* rc, uint64_t& cnt
   __syncthreads();
 }
 
-// One workgroup per NM_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
-// begin + 8 t + 2048 i .. + 7: one whole byte of every record mask, eight class bytes.
+// The span walk of qmvt_walk.h, 8 records per lane: one whole byte of every record mask, eight class bytes.
 __global__ __launch_bounds__(256) void k_nearmiss_records(NearmissParams P) {
   __shared__ uint32_t lds[NM_PLANES * NM_LDS_WORDS];
   __shared__ uint32_t rc[8];
   for (int i = threadIdx.x; i < NM_PLANES * NM_LDS_WORDS; i += blockDim.x) lds[i] = 0u;
   if (threadIdx.x < 8) rc[threadIdx.x] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * NM_SPANS;
-  const int s1 = min(s0 + NM_SPANS, P.n_spans);
   const uint32_t radius = (uint32_t)P.radius;
-  int cur = -1;
   TruthDev T{};
   int64_t off = 0;
   int32_t words = 0;
   bool in_lds = false;
   uint64_t cnt = 0;
-  for (int s = s0; s < s1; ++s) {
-    const SpanDesc sd = P.spans[s];
-    if (sd.vcf != cur) {
-      if (cur >= 0) nearmiss_flush(lds, rc, cnt, P, cur, off, words, in_lds);
-      cur = sd.vcf;
-      T = P.truths[sd.truth];
-      off = P.hit_off[cur];
-      words = (int32_t)((T.n + 31) >> 5);
-      in_lds = words <= NM_LDS_WORDS;
-    }
-    for (int64_t g = sd.begin + 8 * (int64_t)threadIdx.x; g < sd.end; g += 8 * (int64_t)blockDim.x) {
-      const int sh = (int)(g & 63);
-      const uint32_t valid = sd.end - g < 8 ? (1u << (uint32_t)(sd.end - g)) - 1u : 255u;   // bits past the VCF's last record are not defined
-      const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> sh) & valid;
-      const uint32_t fb = kb & ~((uint32_t)(P.mask_tp[g >> 6] >> sh));   // the FP lines: kept, no TP line
-      const v4i pa = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.pos + g));
-      const v4i pb = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.pos + g + 4));
-      const uint2 ab8 = *reinterpret_cast<const uint2*>(P.anib + g);
-      const uint2 f8 = *reinterpret_cast<const uint2*>(P.flags + g);
-      const int32_t pp[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
-      uint64_t cls8 = ~0ull;   // NM_NONE in every byte
+  walk_spans<8>(
+      P.spans, P.n_spans,
+      [&](int vcf, const SpanDesc& sd) {
+        T = P.truths[sd.truth];
+        off = P.hit_off[vcf];
+        words = (int32_t)((T.n + 31) >> 5);
+        in_lds = words <= NM_LDS_WORDS;
+        return true;
+      },
+      [&](int, const SpanDesc& sd, int64_t g) {
+        if (g >= sd.end) return;
+        const uint32_t valid = rec_live<8>(g, sd.end);   // bits past the VCF's last record are not defined
+        const uint32_t kb = mask_bits<8>(P.mask_pass, g) & valid;
+        const uint32_t fb = kb & ~mask_bits<8>(P.mask_tp, g);   // the FP lines: kept, no TP line
+        const qm_int4 pa = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));
+        const qm_int4 pb = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g + 4));
+        const uint2 ab8 = *reinterpret_cast<const uint2*>(P.anib + g);
+        const uint2 f8 = *reinterpret_cast<const uint2*>(P.flags + g);
+        const int32_t pp[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
+        uint64_t cls8 = ~0ull;   // NM_NONE in every byte
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (!((valid >> k) & 1u)) continue;
-        const uint32_t ab = ((k < 4 ? ab8.x : ab8.y) >> (8 * (k & 3))) & 0xffu;
-        const uint32_t fl = ((k < 4 ? f8.x : f8.y) >> (8 * (k & 3))) & 0xffu;
-        const bool kept = (kb >> k) & 1u;
-        const bool fpl = (fb >> k) & 1u;
-        uint32_t c = NM_R_NOKEY;
-        if (!(fl & QMF_NOKEY)) {   // a usable position: the truth keys of [pos - radius, pos + radius]
-          const bool cmp = !(ab & ANIB_NONE);
-          const uint32_t p = (uint32_t)pp[k];
-          const uint32_t lo = p > radius ? p - radius : 0u;
-          const uint64_t hi = (uint64_t)p + radius;
-          const uint32_t b = lo >> T.shift;
-          bool exact = false, sra = false, atpos = false, near = false;
-          if (b <= (uint32_t)T.nb) {   // (tidx has nb + 2 entries)
-            int32_t j = T.tidx[b];
-            int32_t e = T.tidx[b + 1];
-            const uint64_t lokey = (uint64_t)lo << 4;
-            while (j < e) {   // the first key at or behind the window's first position; none in the cell: the next cell's first
-              const int32_t mid = (j + e) >> 1;
-              if ((uint64_t)T.keys[mid] < lokey) j = mid + 1; else e = mid;
-            }
-            for (; j < (int32_t)T.n; ++j) {   // at most 16 keys per position, 2 radius + 1 positions
-              const uint32_t key = T.keys[j];
-              const uint32_t kp = key >> 4;
-              if ((uint64_t)kp > hi) break;
-              int plane = NM_P_NEAR;
-              if (kp != p) near = true;
-              else {
-                atpos = true;
-                plane = NM_P_POSITION;
-                if (cmp) {
-                  if ((key & 15u) == ab) { exact = true; plane = kept ? -1 : NM_P_FILTERED; }
-                  else if (((key >> 2) & 3u) == (ab >> 2)) { sra = true; plane = NM_P_ALLELE; }
+        for (int k = 0; k < 8; ++k) {
+          if (!((valid >> k) & 1u)) continue;
+          const uint32_t ab = ((k < 4 ? ab8.x : ab8.y) >> (8 * (k & 3))) & 0xffu;
+          const uint32_t fl = ((k < 4 ? f8.x : f8.y) >> (8 * (k & 3))) & 0xffu;
+          const bool kept = (kb >> k) & 1u;
+          const bool fpl = (fb >> k) & 1u;
+          uint32_t c = NM_R_NOKEY;
+          if (!(fl & QMF_NOKEY)) {   // a usable position: the truth keys of [pos - radius, pos + radius]
+            const bool cmp = !(ab & ANIB_NONE);
+            const uint32_t p = (uint32_t)pp[k];
+            const uint32_t lo = p > radius ? p - radius : 0u;
+            const uint64_t hi = (uint64_t)p + radius;
+            const uint32_t b = lo >> T.shift;
+            bool exact = false, sra = false, atpos = false, near = false;
+            if (b <= (uint32_t)T.nb) {   // (tidx has nb + 2 entries)
+              int32_t j = T.tidx[b];
+              int32_t e = T.tidx[b + 1];
+              const uint64_t lokey = (uint64_t)lo << 4;
+              while (j < e) {   // the first key at or behind the window's first position; none in the cell: the next cell's first
+                const int32_t mid = (j + e) >> 1;
+                if ((uint64_t)T.keys[mid] < lokey) j = mid + 1; else e = mid;
+              }
+              for (; j < (int32_t)T.n; ++j) {   // at most 16 keys per position, 2 radius + 1 positions
+                const uint32_t key = T.keys[j];
+                const uint32_t kp = key >> 4;
+                if ((uint64_t)kp > hi) break;
+                int plane = NM_P_NEAR;
+                if (kp != p) near = true;
+                else {
+                  atpos = true;
+                  plane = NM_P_POSITION;
+                  if (cmp) {
+                    if ((key & 15u) == ab) { exact = true; plane = kept ? -1 : NM_P_FILTERED; }
+                    else if (((key >> 2) & 3u) == (ab >> 2)) { sra = true; plane = NM_P_ALLELE; }
+                  }
+                }
+                if (plane < 0) continue;
+                const uint32_t bit = 1u << (j & 31);   // bits are only ever set: a plain look first spares the atomic where a neighbour was here
+                if (in_lds) {
+                  uint32_t* w = lds + plane * NM_LDS_WORDS + (j >> 5);
+                  if (!(*(volatile uint32_t*)w & bit)) atomicOr(w, bit);
+                } else {
+                  uint32_t* w = P.planes + (int64_t)plane * P.plane_words + off + (j >> 5);
+                  if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(w, bit);
                 }
               }
-              if (plane < 0) continue;
-              const uint32_t bit = 1u << (j & 31);   // bits are only ever set: a plain look first spares the atomic where a neighbour was here
-              if (in_lds) {
-                uint32_t* w = lds + plane * NM_LDS_WORDS + (j >> 5);
-                if (!(*(volatile uint32_t*)w & bit)) atomicOr(w, bit);
-              } else {
-                uint32_t* w = P.planes + (int64_t)plane * P.plane_words + off + (j >> 5);
-                if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(w, bit);
-              }
             }
+            if (cmp) c = exact ? NM_R_IDCOL : sra ? NM_R_ALLELE : atpos ? NM_R_REFBASE : near ? NM_R_NEAR : NM_R_ISOLATED;
           }
-          if (cmp) c = exact ? NM_R_IDCOL : sra ? NM_R_ALLELE : atpos ? NM_R_REFBASE : near ? NM_R_NEAR : NM_R_ISOLATED;
+          if (fpl) {
+            cls8 ^= (uint64_t)(c ^ NM_NONE) << (8 * k);
+            cnt += 1ull << (NM_CNT_BITS * c);
+          }
         }
-        if (fpl) {
-          cls8 ^= (uint64_t)(c ^ NM_NONE) << (8 * k);
-          cnt += 1ull << (NM_CNT_BITS * c);
-        }
-      }
-      *reinterpret_cast<uint64_t*>(P.rcls + g) = cls8;
-    }
-  }
-  if (cur >= 0) nearmiss_flush(lds, rc, cnt, P, cur, off, words, in_lds);
+        *reinterpret_cast<uint64_t*>(P.rcls + g) = cls8;
+      },
+      [&](int vcf) { nearmiss_flush(lds, rc, cnt, P, vcf, off, words, in_lds); });
 }
 
 // grid (x, VCF), strided over the VCF's words: the hit bitmap and the four planes, 32 keys per word, to the five counts of the missed keys.
@@ -178,8 +171,7 @@ __global__ __launch_bounds__(256) void k_nearmiss_truth(NearmissTruthParams P) {
 
 void launch_nearmiss_records(const NearmissParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + NM_SPANS - 1) / NM_SPANS));
-  hipLaunchKernelGGL(k_nearmiss_records, grid, dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_nearmiss_records, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 void launch_nearmiss_truth(const NearmissTruthParams& P, int n_vcf, int64_t max_words, hipStream_t st) {

@@ -8,7 +8,6 @@ namespace qm {
 
 constexpr int NORM_R_COLS = 12;              // include/qmvt.h QM_NORM_R_COLS
 constexpr int NORM_T_COLS = 5;               // QM_NORM_T_COLS
-constexpr int NORM_SPANS = 4;                // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_norm_records
 constexpr uint32_t NORM_MIN_SLOTS = 64u;     // the smallest table: two words of every bitmap
 // class bytes (QM_NORM_C_*)
 constexpr uint32_t NORM_UNCHANGED = 0u, NORM_RESPELLED = 1u, NORM_RESCUED = 2u, NORM_LONG = 3u, NORM_NOKEY = 4u, NORM_NOVAR = 5u,

@@ -6,12 +6,11 @@
 // lanes run in.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's
 // profiles are keyed on.
 #include "qmvt_norm.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int nm_int4 __attribute__((ext_vector_type(4)));
 
 // inline codes (include/qmvt.h): 0 .. 3 one base, len << 26 | bases for 2 .. 13 bases
 __device__ inline bool nm_inline(int32_t c) {
@@ -166,99 +165,86 @@ __global__ __launch_bounds__(256) void k_norm_fill(NormTable T) {
   if (m && (threadIdx.x & 63u) == 0u) atomicAdd(T.stats, (unsigned long long)__popcll(m));
 }
 
-// One workgroup per NORM_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
-// begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte accesses).  Every lane stays
-// in the loop for all of a span's steps: the wave's ballots need them together.  The counters are wave-uniform registers, added
-// to LDS and from there to the VCF's row when the VCF changes.
+// The span walk of qmvt_walk.h, 4 records per lane (aligned 16-byte / 4-byte accesses).  The counters are wave-uniform registers,
+// taken by ballots over the whole wave, added to LDS and from there to the VCF's row when the VCF changes.
 __global__ __launch_bounds__(256) void k_norm_records(NormRecParams P) {
-  __shared__ uint32_t cnt[NORM_R_COLS];   // at most NORM_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  __shared__ uint32_t cnt[NORM_R_COLS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
   if (threadIdx.x < NORM_R_COLS) cnt[threadIdx.x] = 0u;
   __syncthreads();
   const int lane = (int)(threadIdx.x & 63u);
-  const int s0 = blockIdx.x * NORM_SPANS;
-  const int s1 = min(s0 + NORM_SPANS, P.n_spans);
   uint32_t acc[NORM_R_COLS];
 #pragma unroll
   for (int c = 0; c < NORM_R_COLS; ++c) acc[c] = 0u;
-  int cur = -1;
-  auto flush = [&]() {   // (uniform over the workgroup)
-    if (lane == 0) {
+  const NormVcf* vp = nullptr;
+  walk_spans<4>(
+      P.spans, P.n_spans,
+      [&](int vcf, const SpanDesc&) {
+        vp = P.vcfs + vcf;
+        return vp->t.words != nullptr;
+      },
+      [&](int, const SpanDesc& sd, int64_t g) {
+        const NormVcf& V = *vp;
+        uint32_t m[4] = {0u, 0u, 0u, 0u};   // bit c: the record counts in column c
+        if (g < sd.end) {
+          const uint32_t live = rec_live<4>(g, sd.end);
+          const uint32_t kb = mask_bits<4>(P.mask_pass, g);
+          const uint32_t tb = mask_bits<4>(P.mask_tp, g);
+          const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
+          const qm_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.ref + g));
+          const qm_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.alt + g));
+          const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
+          qm_int4 op = p4, orf = r4, oa = a4, orow = {-1, -1, -1, -1};
+          uint32_t c4 = 0u;
 #pragma unroll
-      for (int c = 0; c < NORM_R_COLS; ++c)
-        if (acc[c]) atomicAdd(cnt + c, acc[c]);
-    }
-#pragma unroll
-    for (int c = 0; c < NORM_R_COLS; ++c) acc[c] = 0u;
-    __syncthreads();
-    if (threadIdx.x < NORM_R_COLS && cnt[threadIdx.x]) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(P.rec + (int64_t)cur * NORM_R_COLS + threadIdx.x), (unsigned long long)cnt[threadIdx.x]);
-      cnt[threadIdx.x] = 0u;
-    }
-    __syncthreads();
-  };
-  for (int s = s0; s < s1; ++s) {
-    const SpanDesc sd = P.spans[s];
-    if (sd.vcf != cur) {
-      if (cur >= 0) flush();
-      cur = sd.vcf;
-    }
-    const NormVcf& V = P.vcfs[cur];
-    if (!V.t.words) continue;   // (uniform over the workgroup)
-    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
-      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
-      uint32_t m[4] = {0u, 0u, 0u, 0u};   // bit c: the record counts in column c
-      if (g < sd.end) {
-        const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (bits and columns past the VCF's last record are not defined)
-        const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & 15u;
-        const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-        const nm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const nm_int4*>(P.pos + g));   // read once
-        const nm_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const nm_int4*>(P.ref + g));
-        const nm_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const nm_int4*>(P.alt + g));
-        const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
-        nm_int4 op = p4, orf = r4, oa = a4, orow = {-1, -1, -1, -1};
-        uint32_t c4 = 0u;
+          for (int k = 0; k < 4; ++k) {
+            if (!((live >> k) & 1u)) continue;
+            const uint32_t fl = (f4 >> (8 * k)) & 255u;
+            const bool kept = (kb >> k) & 1u, tp = (tb >> k) & 1u, nokey = (fl & QMF_NOKEY) != 0u;
+            const NmForm f = nm_normalize(V.t.words, V.t.len, p4[k], r4[k], a4[k], nokey);
+            int32_t slot = -1;
+            if (!nokey && allele_valid(r4[k]) && allele_valid(a4[k])) slot = nm_probe(V.t, f.p, f.r, f.a);
+            const bool tp_n = kept && ((slot >= 0 && (fl & QMF_IDDOT)) || (fl & QMF_TPLINE));
+            const bool rescued = tp_n && !tp;
+            if (kept && slot >= 0) {
+              const uint32_t w = (uint32_t)slot >> 5, bit = 1u << ((uint32_t)slot & 31u);
+              if (!(V.found[w] & bit)) atomicOr(V.found + w, bit);   // (a stale read only repeats the atomic)
+              if (!(V.found_eq[w] & bit) && nm_is_entry(V.t, p4[k], r4[k], a4[k])) atomicOr(V.found_eq + w, bit);
+            }
+            op[k] = f.p; orf[k] = f.r; oa[k] = f.a;
+            if (slot >= 0) orow[k] = (int32_t)V.t.claim[slot] - 1;
+            c4 |= (rescued ? NORM_RESCUED : f.cls) << (8 * k);
+            if (kept) {
+              uint32_t mk = 1u | (tp ? 2u : 0u) | (tp_n ? 4u : 0u) | (rescued ? 8u : 0u);
+              if (f.cls == NORM_RESPELLED) mk |= 16u | (((uint32_t)(f.r | f.a) < 4u) ? 32u : 0u);
+              if (f.cls > NORM_RESCUED) mk |= 1u << (6u + f.cls - NORM_LONG);
+              m[k] = mk;
+            }
+          }
+          *reinterpret_cast<uint32_t*>(P.cls + g) = c4;
+          if (P.npos) {
+            *reinterpret_cast<qm_int4*>(P.npos + g) = op;
+            *reinterpret_cast<qm_int4*>(P.nref + g) = orf;
+            *reinterpret_cast<qm_int4*>(P.nalt + g) = oa;
+            *reinterpret_cast<qm_int4*>(P.nrow + g) = orow;
+          }
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          if ((uint32_t)k >= nrec) continue;
-          const uint32_t fl = (f4 >> (8 * k)) & 255u;
-          const bool kept = (kb >> k) & 1u, tp = (tb >> k) & 1u, nokey = (fl & QMF_NOKEY) != 0u;
-          const NmForm f = nm_normalize(V.t.words, V.t.len, p4[k], r4[k], a4[k], nokey);
-          int32_t slot = -1;
-          if (!nokey && allele_valid(r4[k]) && allele_valid(a4[k])) slot = nm_probe(V.t, f.p, f.r, f.a);
-          const bool tp_n = kept && ((slot >= 0 && (fl & QMF_IDDOT)) || (fl & QMF_TPLINE));
-          const bool rescued = tp_n && !tp;
-          if (kept && slot >= 0) {
-            const uint32_t w = (uint32_t)slot >> 5, bit = 1u << ((uint32_t)slot & 31u);
-            if (!(V.found[w] & bit)) atomicOr(V.found + w, bit);   // (a stale read only repeats the atomic)
-            if (!(V.found_eq[w] & bit) && nm_is_entry(V.t, p4[k], r4[k], a4[k])) atomicOr(V.found_eq + w, bit);
-          }
-          op[k] = f.p; orf[k] = f.r; oa[k] = f.a;
-          if (slot >= 0) orow[k] = (int32_t)V.t.claim[slot] - 1;
-          c4 |= (rescued ? NORM_RESCUED : f.cls) << (8 * k);
-          if (kept) {
-            uint32_t mk = 1u | (tp ? 2u : 0u) | (tp_n ? 4u : 0u) | (rescued ? 8u : 0u);
-            if (f.cls == NORM_RESPELLED) mk |= 16u | (((uint32_t)(f.r | f.a) < 4u) ? 32u : 0u);
-            if (f.cls > NORM_RESCUED) mk |= 1u << (6u + f.cls - NORM_LONG);
-            m[k] = mk;
-          }
-        }
-        *reinterpret_cast<uint32_t*>(P.cls + g) = c4;
-        if (P.npos) {
-          *reinterpret_cast<nm_int4*>(P.npos + g) = op;
-          *reinterpret_cast<nm_int4*>(P.nref + g) = orf;
-          *reinterpret_cast<nm_int4*>(P.nalt + g) = oa;
-          *reinterpret_cast<nm_int4*>(P.nrow + g) = orow;
-        }
-      }
+          if (!__ballot(m[k] != 0u)) continue;   // (uniform over the wave)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (!__ballot(m[k] != 0u)) continue;   // (uniform over the wave)
+          for (int c = 0; c < NORM_R_COLS; ++c) acc[c] += (uint32_t)__popcll(__ballot((m[k] >> c) & 1u));
+        }
+      },
+      [&](int vcf) {
+        if (lane == 0) {
 #pragma unroll
-        for (int c = 0; c < NORM_R_COLS; ++c) acc[c] += (uint32_t)__popcll(__ballot((m[k] >> c) & 1u));
-      }
-    }
-  }
-  if (cur >= 0) flush();
+          for (int c = 0; c < NORM_R_COLS; ++c)
+            if (acc[c]) atomicAdd(cnt + c, acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < NORM_R_COLS; ++c) acc[c] = 0u;
+        flush_counts(cnt, NORM_R_COLS, reinterpret_cast<unsigned long long*>(P.rec + (int64_t)vcf * NORM_R_COLS));
+      });
 }
 
 // a workgroup per VCF: the popcounts of its bitmaps beside the numbers of its table
@@ -298,8 +284,7 @@ void launch_norm_truth(const NormTable& T, hipStream_t st) {
 
 void launch_norm_records(const NormRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + NORM_SPANS - 1) / NORM_SPANS));
-  hipLaunchKernelGGL(k_norm_records, grid, dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_norm_records, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 void launch_norm_found(const NormVcf* vcfs, int n_vcf, uint64_t* tru, hipStream_t st) {

@@ -6,7 +6,6 @@
 
 namespace qm {
 
-constexpr int RROC_SPANS = 4;                // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_rroc_records
 constexpr int RROC_N = 0, RROC_A = 1;        // the two matchings (QM_RROC_NORM, QM_RROC_ATOM are 1 << these)
 constexpr int RROC_MAX_BINS = 256;           // a batch has 1 .. 256 QUAL bins: b + 1 fits a 16-bit best cell
 

@@ -7,14 +7,11 @@
 // order the lanes run in.  Its own translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the
 // classification pass's profiles are keyed on.
 #include "qmvt_rroc.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int rr_int4 __attribute__((ext_vector_type(4)));
-typedef float rr_float4 __attribute__((ext_vector_type(4)));
-typedef unsigned rr_uint2 __attribute__((ext_vector_type(2)));
 
 // floor(q) clamped to n_bins - 1; NaN and q < 0 give -1: the bin of the batch's own ROC
 __device__ inline int rr_qual_bin(float q, int n_bins) {
@@ -95,92 +92,76 @@ __device__ inline void rr_raise(uint32_t* cells, int64_t i, uint32_t v) {
   }
 }
 
-// One workgroup per RROC_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
-// begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 8-byte / 4-byte accesses).  The two
-// histograms of the workgroup's VCF live in LDS and leave for the VCF's 64-bit rows when the VCF changes and at the end.
+// The span walk of qmvt_walk.h, 4 records per lane (aligned 16-byte / 8-byte / 4-byte accesses).  The two histograms of the
+// workgroup's VCF live in LDS and leave for the VCF's 64-bit rows when the VCF changes and at the end.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_rroc_records(RrocRecParams P) {
-  __shared__ uint32_t h[2 * RROC_MAX_BINS];   // at most RROC_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  __shared__ uint32_t h[2 * RROC_MAX_BINS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
   const int nb = P.n_bins;
   for (int i = (int)threadIdx.x; i < 2 * nb; i += (int)blockDim.x) h[i] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * RROC_SPANS;
-  const int s1 = min(s0 + RROC_SPANS, P.n_spans);
-  int cur = -1;
-  auto flush = [&]() {   // (uniform over the workgroup)
-    __syncthreads();
-    unsigned long long* row = reinterpret_cast<unsigned long long*>(P.hist) + (int64_t)cur * 3 * nb;
-    for (int i = (int)threadIdx.x; i < 2 * nb; i += (int)blockDim.x) {
-      const uint32_t c = h[i];
-      if (c) { atomicAdd(row + i, (unsigned long long)c); h[i] = 0u; }
-    }
-    __syncthreads();
-  };
-  for (int s = s0; s < s1; ++s) {
-    const SpanDesc sd = P.spans[s];
-    if (sd.vcf != cur) {
-      if (cur >= 0) flush();
-      cur = sd.vcf;
-    }
-    const RrocVcf V = P.vcfs[cur];
-    if (MODE == RROC_N && !V.best_n) continue;   // (uniform over the workgroup)
-    for (int64_t g0 = sd.begin; g0 < sd.end; g0 += 4 * (int64_t)blockDim.x) {
-      const int64_t g = g0 + 4 * (int64_t)threadIdx.x;
-      if (g >= sd.end) continue;
-      const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (columns past the VCF's last record are not defined)
-      const rr_float4 q4 = __builtin_nontemporal_load(reinterpret_cast<const rr_float4*>(P.qual + g));   // read once
-      const rr_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const rr_int4*>(P.ref + g));
-      const rr_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const rr_int4*>(P.alt + g));
-      const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
-      rr_int4 x4 = {0, 0, 0, 0};          // normal form: the truth rows; atoms: the positions
-      rr_uint2 m2 = {0u, 0u};             // atoms: the hit masks
-      if (MODE == RROC_N) {
-        x4 = __builtin_nontemporal_load(reinterpret_cast<const rr_int4*>(P.nrow + g));
-      } else {
-        x4 = __builtin_nontemporal_load(reinterpret_cast<const rr_int4*>(P.pos + g));
-        m2 = __builtin_nontemporal_load(reinterpret_cast<const rr_uint2*>(P.hit_mask + g));
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if ((uint32_t)k >= nrec) continue;
-        const int32_t r = r4[k], a = a4[k];
-        const int b = rr_qual_bin(q4[k], nb);
-        if (b < 0 || !allele_valid(r) || !allele_valid(a)) continue;   // the universe of the batch's own ROC
-        const uint32_t fl = (f4 >> (8 * k)) & 255u;
-        const bool iddot = (fl & QMF_IDDOT) != 0u;
-        bool hit;
+  RrocVcf V{};
+  walk_spans<4>(
+      P.spans, P.n_spans,
+      [&](int vcf, const SpanDesc&) {
+        V = P.vcfs[vcf];
+        return MODE != RROC_N || V.best_n != nullptr;
+      },
+      [&](int vcf, const SpanDesc& sd, int64_t g) {
+        if (g >= sd.end) return;
+        const uint32_t live = rec_live<4>(g, sd.end);   // (columns past the VCF's last record are not defined)
+        const qm_float4 q4 = __builtin_nontemporal_load(reinterpret_cast<const qm_float4*>(P.qual + g));   // read once
+        const qm_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.ref + g));
+        const qm_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.alt + g));
+        const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
+        qm_int4 x4 = {0, 0, 0, 0};          // normal form: the truth rows; atoms: the positions
+        qm_uint2 m2 = {0u, 0u};             // atoms: the hit masks
         if (MODE == RROC_N) {
-          const int32_t row = x4[k];
-          hit = row >= 0 && (int64_t)row < V.xn;
-          if (hit && iddot && rr_cell(V.best_n, row) < (uint32_t)b + 1u) rr_raise(V.best_n, row, (uint32_t)b + 1u);
+          x4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.nrow + g));
         } else {
-          const AtomTable& T = P.avcfs[cur].t;
-          const int32_t p = x4[k];
-          const bool nokey = (fl & QMF_NOKEY) != 0u;
-          uint32_t mm;
-          if (rr_atomisable(p, r, a, nokey, mm)) {
-            uint32_t hm = (m2[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-            hit = (uint32_t)__popc(hm) == (uint32_t)__popc(mm);
-            if (iddot) {   // a carrier: every atom it hits, a partial record's too
-              while (hm) {
-                const uint32_t o = (uint32_t)__builtin_ctz(hm);
-                hm &= hm - 1u;
-                const int32_t slot = rr_probe(T, rr_atom(p, r, a, o));   // (the producer found it: the probe succeeds)
-                if (slot >= 0 && rr_cell(V.best_atom, slot) < (uint32_t)b + 1u) rr_raise(V.best_atom, slot, (uint32_t)b + 1u);
-              }
-            }
-          } else {
-            const int64_t e = (!nokey && (uint32_t)p < (1u << 28)) ? rr_entry(T, p, r, a) : -1;
-            hit = e >= 0;
-            if (hit && iddot && rr_cell(V.best_entry, e) < (uint32_t)b + 1u) rr_raise(V.best_entry, e, (uint32_t)b + 1u);
-          }
+          x4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));
+          m2 = __builtin_nontemporal_load(reinterpret_cast<const qm_uint2*>(P.hit_mask + g));
         }
-        const bool tp = (hit && iddot) || (fl & QMF_TPLINE);
-        atomicAdd(h + (tp ? 0 : nb) + b, 1u);
-      }
-    }
-  }
-  if (cur >= 0) flush();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!((live >> k) & 1u)) continue;
+          const int32_t r = r4[k], a = a4[k];
+          const int b = rr_qual_bin(q4[k], nb);
+          if (b < 0 || !allele_valid(r) || !allele_valid(a)) continue;   // the universe of the batch's own ROC
+          const uint32_t fl = (f4 >> (8 * k)) & 255u;
+          const bool iddot = (fl & QMF_IDDOT) != 0u;
+          bool hit;
+          if (MODE == RROC_N) {
+            const int32_t row = x4[k];
+            hit = row >= 0 && (int64_t)row < V.xn;
+            if (hit && iddot && rr_cell(V.best_n, row) < (uint32_t)b + 1u) rr_raise(V.best_n, row, (uint32_t)b + 1u);
+          } else {
+            const AtomTable& T = P.avcfs[vcf].t;
+            const int32_t p = x4[k];
+            const bool nokey = (fl & QMF_NOKEY) != 0u;
+            uint32_t mm;
+            if (rr_atomisable(p, r, a, nokey, mm)) {
+              uint32_t hm = (m2[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+              hit = (uint32_t)__popc(hm) == (uint32_t)__popc(mm);
+              if (iddot) {   // a carrier: every atom it hits, a partial record's too
+                while (hm) {
+                  const uint32_t o = (uint32_t)__builtin_ctz(hm);
+                  hm &= hm - 1u;
+                  const int32_t slot = rr_probe(T, rr_atom(p, r, a, o));   // (the producer found it: the probe succeeds)
+                  if (slot >= 0 && rr_cell(V.best_atom, slot) < (uint32_t)b + 1u) rr_raise(V.best_atom, slot, (uint32_t)b + 1u);
+                }
+              }
+            } else {
+              const int64_t e = (!nokey && (uint32_t)p < (1u << 28)) ? rr_entry(T, p, r, a) : -1;
+              hit = e >= 0;
+              if (hit && iddot && rr_cell(V.best_entry, e) < (uint32_t)b + 1u) rr_raise(V.best_entry, e, (uint32_t)b + 1u);
+            }
+          }
+          const bool tp = (hit && iddot) || (fl & QMF_TPLINE);
+          atomicAdd(h + (tp ? 0 : nb) + b, 1u);
+        }
+      },
+      [&](int vcf) { flush_counts(h, 2 * nb, reinterpret_cast<unsigned long long*>(P.hist) + (int64_t)vcf * 3 * nb); });
 }
 
 // A workgroup per VCF: the histogram of the bests of its units in LDS, then the suffix sums of the three rows in place (one lane
@@ -234,7 +215,7 @@ __global__ __launch_bounds__(256) void k_rroc_units(const RrocVcf* vcfs, const A
 
 void launch_rroc_records(int mode, const RrocRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + RROC_SPANS - 1) / RROC_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   if (mode == RROC_N) hipLaunchKernelGGL(k_rroc_records<RROC_N>, grid, dim3(256), 0, st, P);
   else hipLaunchKernelGGL(k_rroc_records<RROC_A>, grid, dim3(256), 0, st, P);
 }

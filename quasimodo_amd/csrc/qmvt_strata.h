@@ -8,7 +8,6 @@ namespace qm {
 
 constexpr int STRATA_MAX = 32;               // include/qmvt.h QM_STRATA_MAX
 constexpr int STRATA_LDS_SEGMENTS = 4096;    // QM_STRATA_LDS_SEGMENTS: 16 KiB of breakpoints + 16 KiB of masks
-constexpr int STRATA_SPANS = 4;              // batch spans (SPAN_TILES tiles of one VCF each) per workgroup
 constexpr int STRATA_REC_ROWS = STRATA_MAX + 2;   // the strata, outside, nokey
 constexpr int STRATA_PLANE_KEYS = 4096;      // truth keys per workgroup of k_strata_planes (the staged table is paid for once)
 // The reduction that lost the A/B of LABNOTES round 12 stays buildable, not shipped: -DQM_STRATA_VARIANT=1 one LDS atomic per

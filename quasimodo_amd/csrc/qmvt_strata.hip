@@ -4,12 +4,11 @@
 // k_strata_truth counts them against the hit bitmaps of qm_batch_truth_hits.  Its own translation unit: qm_kernels_id
 // (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
 #include "qmvt_strata.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int st_int4 __attribute__((ext_vector_type(4)));
 
 // Index of the segment that holds p: upper_bound(bp, p) - 1, for every int32 p (bp[0] = INT32_MIN).  `prev` is the segment the
 // lane's previous lookup ended in and is tried first: in a sorted VCF consecutive records almost always share it.  STAGED: bp is
@@ -87,14 +86,15 @@ __device__ inline void strata_count(uint32_t* cnt, bool in, bool tp, uint64_t ro
   }
 }
 
-// One workgroup per STRATA_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads).  Every lane stays
 // in the loop for all of a span's steps: the wave's ballots need them together.
 template <bool STAGED>
 __global__ __launch_bounds__(256) void k_strata_records(StrataRecParams P) {
   __shared__ int32_t s_bp[STAGED ? STRATA_LDS_SEGMENTS : 1];
   __shared__ uint32_t s_mask[STAGED ? STRATA_LDS_SEGMENTS : 1];
-  __shared__ uint32_t cnt[2 * STRATA_REC_ROWS];   // at most STRATA_SPANS * SPAN_TILES * K1_TILE = 65 536 records: u32 suffices
+  __shared__ uint32_t cnt[2 * STRATA_REC_ROWS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE = 65 536 records: u32 suffices
   const StrataTable T = P.tab;
   const int S = T.n_strata;
   const int words = 2 * (S + 2);
@@ -104,8 +104,8 @@ __global__ __launch_bounds__(256) void k_strata_records(StrataRecParams P) {
   const int32_t* bp = STAGED ? s_bp : T.bp;
   const uint32_t* masks = STAGED ? s_mask : T.masks;
   const bool first = (threadIdx.x & 63u) == 0u;
-  const int s0 = blockIdx.x * STRATA_SPANS;
-  const int s1 = min(s0 + STRATA_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   int32_t seg = 0;
   for (int s = s0; s < s1; ++s) {
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void k_strata_records(StrataRecParams P) {
       uint64_t row[4] = {0ull, 0ull, 0ull, 0ull};
       if (kb) {
         tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-        const st_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const st_int4*>(P.pos + g));   // read once
+        const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
         const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void k_strata_truth(const StrataTruthRow* rows
 
 void launch_strata_records(const StrataRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + STRATA_SPANS - 1) / STRATA_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   if (P.tab.m <= STRATA_LDS_SEGMENTS) hipLaunchKernelGGL(k_strata_records<true>, grid, dim3(256), 0, st, P);
   else hipLaunchKernelGGL(k_strata_records<false>, grid, dim3(256), 0, st, P);
 }

@@ -6,7 +6,6 @@
 
 namespace qm {
 
-constexpr int SF_SPANS = 4;              // batch spans per workgroup (k_af_profile's frame)
 constexpr int SF_MAX_NQ = 256;           // include/qmvt.h QM_SF_MAX_QUAL_BINS
 constexpr int SF_MAX_NA = 64;            // include/qmvt.h QM_SF_MAX_AF_BINS
 constexpr int SF_MAX_CELLS = 4096;       // include/qmvt.h QM_SF_MAX_CELLS: nq * na at most (two u32 grids: 32 KiB of LDS)
@@ -18,7 +17,6 @@ constexpr int SF_TRUTH_CHUNK = 8192;     // truth keys per workgroup of k_surfac
 // dynamic LDS of k_surface_records, in u32 words: the two grids, the extras, the staged codes -- 49 168 bytes at the cell limit
 inline size_t sf_records_lds_words(int cells) { return (size_t)2 * (size_t)cells + SF_EXTRA + SF_STAGE; }
 static_assert(((size_t)2 * SF_MAX_CELLS + SF_EXTRA + SF_STAGE) * 4 <= 65536, "grids plus staging: what a launch gets without asking");
-static_assert((int64_t)SF_SPANS * SPAN_TILES * K1_TILE < (1ll << 32), "u32 cells per workgroup");
 
 struct SurfaceParams {
   const SpanDesc* spans;

@@ -6,13 +6,11 @@
 // add only: the result does not depend on the order of the records.  Its own translation unit: qm_kernels_id stays the id the
 // classification pass's profiles are keyed on.
 #include "qmvt_surface.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int sf_int4 __attribute__((ext_vector_type(4)));
-typedef float sf_float4 __attribute__((ext_vector_type(4)));
 
 // index of `key` among the truth set's sorted distinct keys, or -1 (k_truth_hits' lookup: equality only, no window)
 __device__ inline int32_t sf_find(const TruthDev& T, uint32_t pos, uint32_t key) {
@@ -64,7 +62,8 @@ __device__ inline void sf_flush(uint32_t* h, uint32_t (&c)[SF_REC_EXTRA], int ce
   __syncthreads();
 }
 
-// One workgroup per SF_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads).
 __global__ __launch_bounds__(256) void k_surface_records(SurfaceParams P) {
   extern __shared__ uint32_t sf_h[];   // [TP, FP][nq][na], SF_EXTRA extras, SF_STAGE staged codes
@@ -76,8 +75,8 @@ __global__ __launch_bounds__(256) void k_surface_records(SurfaceParams P) {
   uint32_t c[SF_REC_EXTRA] = {0u, 0u, 0u};
   const float fa = (float)P.na;
   const int limit = P.nq * P.q_step;
-  const int s0 = blockIdx.x * SF_SPANS;
-  const int s1 = min(s0 + SF_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   TruthDev T{};
   bool on = false, staged = false;
@@ -94,12 +93,12 @@ __global__ __launch_bounds__(256) void k_surface_records(SurfaceParams P) {
     }
     for (int64_t g = sd.begin + 4 * (int64_t)threadIdx.x; g < sd.end; g += 4 * (int64_t)blockDim.x) {
       const uint32_t valid = sd.end - g < 4 ? (1u << (uint32_t)(sd.end - g)) - 1u : 15u;   // records past the VCF's last are not defined
-      const sf_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const sf_int4*>(P.pos + g));      // read once
-      const sf_float4 q4 = __builtin_nontemporal_load(reinterpret_cast<const sf_float4*>(P.qual + g));
+      const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));      // read once
+      const qm_float4 q4 = __builtin_nontemporal_load(reinterpret_cast<const qm_float4*>(P.qual + g));
       const uint32_t ab4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(P.anib + g));
       const uint32_t fl4 = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(P.flags + g));
-      sf_float4 f4 = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (on) f4 = __builtin_nontemporal_load(reinterpret_cast<const sf_float4*>(P.af + g));
+      qm_float4 f4 = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (on) f4 = __builtin_nontemporal_load(reinterpret_cast<const qm_float4*>(P.af + g));
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const uint32_t anib = (ab4 >> (8 * k)) & 0xffu;
@@ -179,7 +178,7 @@ __global__ __launch_bounds__(256) void k_surface_sums(SurfaceParams P) {
 
 void launch_surface_records(const SurfaceParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + SF_SPANS - 1) / SF_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   const size_t lds = sf_records_lds_words(P.nq * P.na) * sizeof(uint32_t);
   hipLaunchKernelGGL(k_surface_records, grid, dim3(256), lds, st, P);
 }

@@ -6,7 +6,6 @@
 
 namespace qm {
 
-constexpr int TS_SPANS = 4;              // batch spans (SPAN_TILES tiles of one VCF each) per workgroup
 constexpr int TS_LDS_WORDS = 4096;       // hit-bitmap words a workgroup collects in LDS (16 KB: truth sets up to 131 072 keys)
 constexpr int TS_MAX_GROUP = 5;          // include/qmvt.h QM_TRUTH_GROUP_MAX: VCFs per group of k_truth_regions
 constexpr int TS_REGIONS = 32;           // 1 << TS_MAX_GROUP slots per group

@@ -5,10 +5,9 @@
 // Venn diagram of scripts/caller_performance_compare.R:110-119,510-549 -- and writes the OR of the group's bitmaps.  Its own
 // translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
 #include "qmvt_truthside.h"
+#include "qmvt_walk.h"
 
 namespace qm {
-
-typedef int32_t v4i __attribute__((ext_vector_type(4)));
 
 // index of `key` among the truth set's sorted distinct keys, or -1: the coarse position index, then a bisection of its cell
 __device__ inline int32_t truth_find(const TruthDev& T, uint32_t pos, uint32_t key) {
@@ -34,60 +33,55 @@ __device__ inline void hits_flush(uint32_t* lds, uint32_t* row, int32_t words) {
   __syncthreads();
 }
 
-// One workgroup per TS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
-// begin + 8 t + 2048 i .. + 7 (every span starts at a multiple of 256 records: aligned loads, one whole mask byte per lane).
+// The span walk of qmvt_walk.h, 8 records per lane (aligned loads, one whole mask byte per lane).
 __global__ __launch_bounds__(256) void k_truth_hits(TruthHitsParams P) {
   __shared__ uint32_t lds[TS_LDS_WORDS];
   for (int i = threadIdx.x; i < TS_LDS_WORDS; i += blockDim.x) lds[i] = 0u;
   __syncthreads();
-  const int s0 = blockIdx.x * TS_SPANS;
-  const int s1 = min(s0 + TS_SPANS, P.n_spans);
-  int cur = -1;
   TruthDev T{};
   uint32_t* row = nullptr;
   int32_t words = 0;
   bool in_lds = false;
-  for (int s = s0; s < s1; ++s) {
-    const SpanDesc sd = P.spans[s];
-    if (sd.vcf != cur) {
-      if (in_lds) hits_flush(lds, row, words);
-      cur = sd.vcf;
-      T = P.truths[sd.truth];
-      row = P.hits + P.hit_off[cur];
-      words = (int32_t)((T.n + 31) >> 5);
-      in_lds = TS_USE_LDS && words <= TS_LDS_WORDS;
-    }
-    for (int64_t g = sd.begin + 8 * (int64_t)threadIdx.x; g < sd.end; g += 8 * (int64_t)blockDim.x) {
-      const int sh = (int)(g & 63);
-      uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> sh) & 255u;
-      if (sd.end - g < 8) kb &= (1u << (uint32_t)(sd.end - g)) - 1u;   // bits past the VCF's last record are not defined
-      uint32_t out = 0u;
-      if (kb) {
-        const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> sh) & 255u;
-        const v4i pa = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.pos + g));
-        const v4i pb = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(P.pos + g + 4));
-        const uint2 ab8 = *reinterpret_cast<const uint2*>(P.anib + g);
-        const uint2 f8 = *reinterpret_cast<const uint2*>(P.flags + g);
-        const int32_t pp[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
+  walk_spans<8>(
+      P.spans, P.n_spans,
+      [&](int vcf, const SpanDesc& sd) {
+        T = P.truths[sd.truth];
+        row = P.hits + P.hit_off[vcf];
+        words = (int32_t)((T.n + 31) >> 5);
+        in_lds = TS_USE_LDS && words <= TS_LDS_WORDS;
+        return true;
+      },
+      [&](int, const SpanDesc& sd, int64_t g) {
+        if (g >= sd.end) return;
+        const uint32_t kb = mask_bits<8>(P.mask_pass, g) & rec_live<8>(g, sd.end);
+        uint32_t out = 0u;
+        if (kb) {
+          const uint32_t tb = mask_bits<8>(P.mask_tp, g);
+          const qm_int4 pa = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));
+          const qm_int4 pb = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g + 4));
+          const uint2 ab8 = *reinterpret_cast<const uint2*>(P.anib + g);
+          const uint2 f8 = *reinterpret_cast<const uint2*>(P.flags + g);
+          const int32_t pp[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const uint32_t ab = ((k < 4 ? ab8.x : ab8.y) >> (8 * (k & 3))) & 0xffu;
-          const uint32_t fl = ((k < 4 ? f8.x : f8.y) >> (8 * (k & 3))) & 0xffu;
-          if (!((kb >> k) & 1u) || (ab & ANIB_NONE) || (fl & QMF_NOKEY)) continue;   // not kept, or no comparable key
-          // a kept '.'-ID line with a key that is no TP line: its key is not in the truth set (exact: DESIGN.md 4.8)
-          if (TS_SHORTCUT && (fl & QMF_IDDOT) && !((tb >> k) & 1u)) continue;
-          const uint32_t p = (uint32_t)pp[k];
-          const int32_t j = truth_find(T, p, (p << 4) | ab);
-          if (j < 0) continue;
-          out |= 1u << k;
-          if (in_lds) atomicOr(lds + (j >> 5), 1u << (j & 31));
-          else atomicOr(row + (j >> 5), 1u << (j & 31));
+          for (int k = 0; k < 8; ++k) {
+            const uint32_t ab = ((k < 4 ? ab8.x : ab8.y) >> (8 * (k & 3))) & 0xffu;
+            const uint32_t fl = ((k < 4 ? f8.x : f8.y) >> (8 * (k & 3))) & 0xffu;
+            if (!((kb >> k) & 1u) || (ab & ANIB_NONE) || (fl & QMF_NOKEY)) continue;   // not kept, or no comparable key
+            // a kept '.'-ID line with a key that is no TP line: its key is not in the truth set (exact: DESIGN.md 4.8)
+            if (TS_SHORTCUT && (fl & QMF_IDDOT) && !((tb >> k) & 1u)) continue;
+            const uint32_t p = (uint32_t)pp[k];
+            const int32_t j = truth_find(T, p, (p << 4) | ab);
+            if (j < 0) continue;
+            out |= 1u << k;
+            if (in_lds) atomicOr(lds + (j >> 5), 1u << (j & 31));
+            else atomicOr(row + (j >> 5), 1u << (j & 31));
+          }
         }
-      }
-      P.mask_intruth[g >> 3] = (uint8_t)out;
-    }
-  }
-  if (in_lds) hits_flush(lds, row, words);
+        P.mask_intruth[g >> 3] = (uint8_t)out;
+      },
+      [&](int) {
+        if (in_lds) hits_flush(lds, row, words);   // (uniform over the workgroup)
+      });
 }
 
 // grid (x, group): regions[group][m] += truth keys whose membership mask over the group's VCFs is m, 32 keys per word
@@ -123,8 +117,7 @@ __global__ __launch_bounds__(256) void k_truth_regions(const TruthGroup* groups,
 
 void launch_truth_hits(const TruthHitsParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + TS_SPANS - 1) / TS_SPANS));
-  hipLaunchKernelGGL(k_truth_hits, grid, dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_truth_hits, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 void launch_truth_regions(const TruthGroup* groups, int n_groups, int64_t max_words, unsigned long long* regions, hipStream_t st) {

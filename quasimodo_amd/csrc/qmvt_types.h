@@ -10,7 +10,6 @@ constexpr int TYPE_MAX_BINS = 16;            // include/qmvt.h QM_TYPE_MAX_BINS
 constexpr int TYPE_KINDS = 5;                // SNV, MNP, INS, DEL, CPX: the grid is [TYPE_KINDS][n_bins]
 constexpr int TYPE_OFFGRID = 4;              // the rows behind the grid
 constexpr int TYPE_MAX_ROWS = TYPE_KINDS * TYPE_MAX_BINS + TYPE_OFFGRID;   // QM_TYPE_MAX_ROWS
-constexpr int TYPE_SPANS = 4;                // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_type_records
 constexpr uint32_t TYPE_SNV = 0u, TYPE_MNP = 1u, TYPE_INS = 2u, TYPE_DEL = 3u, TYPE_CPX = 4u;   // QM_TYPE_*
 constexpr uint32_t TYPE_NOKEY = 0u, TYPE_NOVAR = 1u, TYPE_LONGPAIR = 2u, TYPE_NOSHAPE = 3u;     // + TYPE_KINDS * n_bins
 constexpr uint32_t TYPE_LONG_HEAD = 13u;     // bases of a long allele the shape table keeps at either end (QM_ALLELE_INLINE_MAX)

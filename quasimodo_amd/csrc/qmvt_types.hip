@@ -7,12 +7,11 @@
 // Integer work only: no output depends on the order the lanes run in.  Its own translation unit: qm_kernels_id
 // (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
 #include "qmvt_types.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int vt_int4 __attribute__((ext_vector_type(4)));
 
 // inline codes (include/qmvt.h): 0 .. 3 one base, len << 26 | bases for 2 .. 13 bases
 __device__ inline bool vt_inline(int32_t c) {
@@ -81,17 +80,18 @@ __device__ inline int64_t vt_entry(const TypeVcf& V, int32_t p, int32_t r, int32
   return lo < V.xn && V.xkeys[lo] == key && V.xref[lo] == r && V.xalt[lo] == a ? lo : -1;
 }
 
-// One workgroup per TYPE_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte accesses).  Every kept
 // record adds one to its row's cell of the workgroup's LDS histogram (a TP line one more to the cell beside it): one LDS atomic
 // per count, no reduction over the wave (DESIGN.md 4.19 says why).  The histogram goes to the VCF's rows when the VCF changes.
 __global__ __launch_bounds__(256) void k_type_records(TypeRecParams P) {
-  __shared__ uint32_t hist[2 * TYPE_MAX_ROWS];   // at most TYPE_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
+  __shared__ uint32_t hist[2 * TYPE_MAX_ROWS];   // at most PASS_SPANS * SPAN_TILES * K1_TILE records per workgroup: u32 suffices
   if (threadIdx.x < 2 * TYPE_MAX_ROWS) hist[threadIdx.x] = 0u;
   __syncthreads();
   const int cells = 2 * P.bins.n_rows;
-  const int s0 = blockIdx.x * TYPE_SPANS;
-  const int s1 = min(s0 + TYPE_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   int cur = -1;
   auto flush = [&]() {   // (uniform over the workgroup)
     __syncthreads();
@@ -114,9 +114,9 @@ __global__ __launch_bounds__(256) void k_type_records(TypeRecParams P) {
       const uint32_t nrec = (uint32_t)min((int64_t)4, sd.end - g);   // (bits and columns past the VCF's last record are not defined)
       const uint32_t kb = (uint32_t)(P.mask_pass[g >> 6] >> (int)(g & 63)) & 15u;
       const uint32_t tb = (uint32_t)(P.mask_tp[g >> 6] >> (int)(g & 63)) & 15u;
-      const vt_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.pos + g));   // read once
-      const vt_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.ref + g));
-      const vt_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.alt + g));
+      const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
+      const qm_int4 r4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.ref + g));
+      const qm_int4 a4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.alt + g));
       const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
       uint32_t row4 = 0u;
 #pragma unroll
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_type_truth(TypeTruthParams P) {
 
 void launch_type_records(const TypeRecParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  const dim3 grid((unsigned)((P.n_spans + TYPE_SPANS - 1) / TYPE_SPANS));
+  const dim3 grid(pass_grid(P.n_spans));
   hipLaunchKernelGGL(k_type_records, grid, dim3(256), 0, st, P);
 }
 

@@ -9,7 +9,6 @@ namespace qm {
 constexpr int VT_MAX_GROUP = 32;         // include/qmvt.h QM_VOTE_GROUP_MAX: VCFs per group
 constexpr int VT_SLOTS = VT_MAX_GROUP + 1;   // vote counts 0 .. 32
 constexpr int VT_PLANES = 6;             // bit planes of the carry-save counter: 0 .. 63 >= 32
-constexpr int VT_SPANS = 4;              // batch spans (SPAN_TILES tiles of one VCF each) per workgroup of k_vote_keys
 constexpr int VT_RUN_TILE = 1024;        // sorted pairs per workgroup of k_vote_heads / k_vote_runs (4 consecutive per lane)
 static_assert(SORT_TILE % VT_RUN_TILE == 0, "a run tile lies inside one sort tile (the sort's tile table names its group)");
 constexpr int VT_RUN_PER_SORT = SORT_TILE / VT_RUN_TILE;

@@ -5,13 +5,11 @@
 // k_vote_runs turn the sorted pairs into the ascending distinct keys, their member masks and the vote histogram.  Its own
 // translation unit: qm_kernels_id (qmvt_kernels.hip + qmvt_dev.h) stays the id the classification pass's profiles are keyed on.
 #include "qmvt_votes.h"
+#include "qmvt_walk.h"
 
 #include <algorithm>
 
 namespace qm {
-
-typedef int32_t vt_int4 __attribute__((ext_vector_type(4)));
-typedef uint32_t vt_uint4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t vt_lanes_below(uint64_t b) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
@@ -81,14 +79,15 @@ __global__ __launch_bounds__(256) void k_vote_truth(const VoteGroup* groups, Vot
   vote_flush(s_hist, s_priv, out.tp + (int64_t)blockIdx.y * VT_SLOTS, out.ptp + (int64_t)blockIdx.y * VT_MAX_GROUP);
 }
 
-// One workgroup per VT_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
+// The span walk written out (through walk_spans this kernel measured slower than its own frame, LABNOTES round 29).
+// One workgroup per PASS_SPANS consecutive spans of the batch layout (a span never crosses a VCF); lane t takes records
 // begin + 4 t + 1024 i .. + 3 (every span starts at a multiple of 256 records: aligned 16-byte / 4-byte loads, one nibble of the
 // masks per lane).  The records with kept, not in the truth set and a comparable key leave as (key, member) pairs: four ballots
 // say where a lane's pairs go inside the wave's piece, and lane 0 reserves the piece with one atomic on the group's cursor.
 __global__ __launch_bounds__(256) void k_vote_keys(VoteKeysParams P) {
   const int lane = (int)(threadIdx.x & 63u);
-  const int s0 = blockIdx.x * VT_SPANS;
-  const int s1 = min(s0 + VT_SPANS, P.n_spans);
+  const int s0 = blockIdx.x * PASS_SPANS;
+  const int s1 = min(s0 + PASS_SPANS, P.n_spans);
   for (int s = s0; s < s1; ++s) {
     const SpanDesc sd = P.spans[s];
     const int32_t slot = P.vcf_slot[sd.vcf];
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(256) void k_vote_keys(VoteKeysParams P) {
       uint32_t sel = 0u, nk = 0u, key[4] = {0u, 0u, 0u, 0u};
       if (kb) {
         const uint32_t it = (uint32_t)(P.mask_intruth[g >> 6] >> (int)(g & 63)) & 15u;
-        const vt_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const vt_int4*>(P.pos + g));   // read once
+        const qm_int4 p4 = __builtin_nontemporal_load(reinterpret_cast<const qm_int4*>(P.pos + g));   // read once
         const uint32_t a4 = *reinterpret_cast<const uint32_t*>(P.anib + g);
         const uint32_t f4 = *reinterpret_cast<const uint32_t*>(P.flags + g);
 #pragma unroll
@@ -166,9 +165,9 @@ __device__ inline VoteLane vote_load(const uint32_t* keys, const uint32_t* vals,
   for (int k = 0; k < 4; ++k) { L.key[k] = 0u; L.bit[k] = 0u; L.valid[k] = false; L.head[k] = false; }
   if (i >= n) return L;
   // koff is a multiple of 64 and i of 4, the buffers are padded: whole 16-byte loads, the tail masked
-  const vt_uint4 k4 = *reinterpret_cast<const vt_uint4*>(keys + koff + i);
-  vt_uint4 v4 = {0u, 0u, 0u, 0u};
-  if (want_bits) v4 = *reinterpret_cast<const vt_uint4*>(vals + koff + i);
+  const qm_uint4 k4 = *reinterpret_cast<const qm_uint4*>(keys + koff + i);
+  qm_uint4 v4 = {0u, 0u, 0u, 0u};
+  if (want_bits) v4 = *reinterpret_cast<const qm_uint4*>(vals + koff + i);
   uint32_t prev = i > 0 ? keys[koff + i - 1] : 0u;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -351,7 +350,7 @@ void launch_vote_truth(const VoteGroup* groups, int n_groups, int64_t max_words,
 
 void launch_vote_keys(const VoteKeysParams& P, hipStream_t st) {
   if (P.n_spans <= 0) return;
-  hipLaunchKernelGGL(k_vote_keys, dim3((unsigned)((P.n_spans + VT_SPANS - 1) / VT_SPANS)), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(k_vote_keys, dim3(pass_grid(P.n_spans)), dim3(256), 0, st, P);
 }
 
 void launch_vote_segs(SortSeg* segs, const uint32_t* cursor, int n_groups, hipStream_t st) {

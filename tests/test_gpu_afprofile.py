@@ -146,7 +146,7 @@ def test_hand_cases(engine):
 
 
 # ---- shapes: VCFs smaller than a workgroup's share, several per workgroup, one without frequencies ------------------------
-SIZES = (0, 1, 3, 255, 256, 257, 1025, 3000)
+SIZES = (0, 1, 3, 255, 256, 257, 1025, 3000, 1023, 1024, 16384, 16385)   # 1023 .. 1025: a step of the span walk; 16 384: a span
 BINS = [(1, 1, 1), (1000, 256, 20), (1 << 27, 128, 64)]          # (window, n_pos_bins, n_af_bins); 128 x 64 = the 8 192 limit
 
 

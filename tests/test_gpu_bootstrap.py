@@ -19,7 +19,7 @@ F_PASS, F_IDDOT, F_NOKEY = 1, 2, 4
 I32MAX = (1 << 31) - 1
 S_NPASS, S_TP_LINES, S_TP_R, S_TRUTH = 0, 1, 3, 7
 SHAPES = [(1, 1), (7, 2), (1024, 236), (3, 4096)]
-SIZES = [1, 63, 64, 65, 257, 1025, 5000, 300]          # the last one holds no kept record
+SIZES = [0, 1, 3, 63, 64, 65, 257, 1023, 1024, 1025, 5000, 16384, 16385, 300]   # 1023 .. 1025: a step of the span walk; 16 384: a span; the last one holds no kept record
 TOP = 250000                                            # beyond 1024 * 236 = 241 664
 
 

@@ -92,9 +92,9 @@ def test_table_refuses(engine, planted):
 
 
 # ---- records and truth --------------------------------------------------------------------------------------------------
-SIZES = [70000, 0, 1, 255, 256, 257]               # 70 000: more than the 65 536 records one workgroup may see
-WHICH_TRUTH = [0, 1, 0, 1, 0, 0]                   # VCFs 0 and 4 share a truth set and name different genomes
-WHICH_GENOME = [0, 0, 1, -1, 1, 0]
+SIZES = [70000, 0, 1, 255, 256, 257, 3, 1023, 1024, 1025, 16384, 16385]   # 70 000: more than the 65 536 records one workgroup may see; 1023 .. 1025: a step of the span walk; 16 384: a span
+WHICH_TRUTH = [0, 1, 0, 1, 0, 0, 1, 0, 1, 0, 1, 0]   # VCFs 0 and 4 share a truth set and name different genomes
+WHICH_GENOME = [0, 0, 1, -1, 1, 0, 1, 0, -1, 1, 0, 1]
 LEN_B = 37003
 
 

@@ -163,9 +163,10 @@ def test_random_sorted_shuffled_and_runs(engine):
         base = [random_columns(rng, n, L, truth) for n in (70_000, 50_000, 40_000)]
         perm = rng.permutation(len(base[1][0]))
         cols = [base[0], tuple(np.ascontiguousarray(c[perm]) for c in base[1]), _runs(base[2], rng, 24)]
-        b = run_batch(engine, cols, [tid] * 3, [gid] * 3)
-        first = check_rows(b, cols, {gid: genome}, [gid] * 3)
-        b.motifs([gid] * 3)
+        cols += [random_columns(rng, n, L, truth) for n in (16_384, 16_385)]      # a VCF that ends with its span, and one record more
+        b = run_batch(engine, cols, [tid] * 5, [gid] * 5)
+        first = check_rows(b, cols, {gid: genome}, [gid] * 5)
+        b.motifs([gid] * 5)
         np.testing.assert_array_equal(b.motif_counts(), first)      # two calls, the same counts
         b.close()
     finally:

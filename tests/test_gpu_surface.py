@@ -14,7 +14,7 @@ F_PASS, F_IDDOT, F_NOKEY, F_TPLINE = 1, 2, 4, 8
 STAGE = 4096                      # qmvt_surface.h SF_STAGE: truth sets up to here stage their best codes in LDS
 GENOME = 5000
 PARAMS = [(1, 256, 8), (4, 64, 50), (1, 1, 1), (7, 3, 64), (1, 64, 64)]
-SIZES = [0, 1, 7, 8, 9, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049]
+SIZES = [0, 1, 7, 8, 9, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 3, 1023, 1024, 1025, 4095, 4096, 16384, 16385]   # 1023 .. 1025: a step of the span walk; 16 384: a span
 TRUTH_SIZES = [0, 1, 31, 32, 33, STAGE - 1, STAGE, STAGE + 1]
 N_BINS = 256
 
@@ -80,7 +80,7 @@ class Case:
 
 @pytest.fixture(scope="module")
 def case(engine):
-    """one batch of 40 VCFs over eight truth sets, finished; the per-record facts that no parameter changes are restated once"""
+    """one batch of 48 VCFs over eight truth sets, finished; the per-record facts that no parameter changes are restated once"""
     rng = np.random.default_rng(1615)
     qpool, apool = _f32_pool()
     c = Case()
@@ -92,9 +92,9 @@ def case(engine):
     c.which[-2], c.which[-1] = TRUTH_SIZES.index(STAGE), TRUTH_SIZES.index(STAGE + 1)     # a staged and an unstaged truth set
     made = [_vcf(rng, n, c.truths[w], qpool, apool, shuffle=(v % 2 == 1)) for v, (n, w) in enumerate(zip(sizes, c.which))]
     c.cols, c.af = [m[0] for m in made], [m[1] for m in made]
-    c.no_af = 21                                                       # this VCF's frequencies are never uploaded
+    c.no_af = 29                                                       # this VCF's frequencies are never uploaded
     c.af[c.no_af] = None
-    assert len(sizes) == 40 and len(c.cols[c.no_af][0]) > 0
+    assert len(sizes) == 48 and len(c.cols[c.no_af][0]) > 0
     b = engine.batch([len(x[0]) for x in c.cols], [c.tids[w] for w in c.which], n_bins=N_BINS)
     for v, x in enumerate(c.cols):
         b.upload(v, *x)
@@ -156,11 +156,11 @@ def restate(case, v, q_step, nq, na):
 def test_surface_equals_the_restatement(case, q_step, nq, na):
     b = case.b
     S, extra = b.surface(q_step, nq, na)
-    assert S.shape == (40, 3, nq, na) and extra.shape == (40, 4) and S.dtype == np.uint64
+    assert S.shape == (48, 3, nq, na) and extra.shape == (48, 4) and S.dtype == np.uint64
     roc = b.roc()
     lines = [i for i in range(nq) if i * q_step < N_BINS]
     some_u = some_fp = 0
-    for v in range(40):
+    for v in range(48):
         wS, wx = restate(case, v, q_step, nq, na)
         g = S[v].astype(np.int64)
         bad = np.argwhere(g != wS)

@@ -191,9 +191,10 @@ def test_random_sorted_shuffled_runs_two_truth_sets(engine):
         perm = rng.permutation(len(base[1][0]))
         cols = [base[0], tuple(np.ascontiguousarray(c[perm]) for c in base[1]), _runs(base[2], rng, 24), base[3], base[4],
                 random_columns(rng, 60_000, L, t2), random_columns(rng, 45_000, L, t2, sorted_=False)]
-        tids = [tid1] * 5 + [tid2] * 2
+        cols += [random_columns(rng, n, L, t2) for n in (16_384, 16_385)]         # a VCF that ends with its span, and one record more
+        tids = [tid1] * 5 + [tid2] * 4
         b = run_batch(engine, cols, tids)
-        want = check_batch(b, cols, [t1] * 5 + [t2] * 2)
+        want = check_batch(b, cols, [t1] * 5 + [t2] * 4)
         groups = [[0, 1, 2, 3, 4], [3], [5, 6], [4, 0, 2]]
         reg, uni = b.truth_regions(groups, union=True)
         for g, ids in enumerate(groups):

@@ -181,6 +181,9 @@ def wide(engine):
     tid = engine.truth_load(*truth)
     sizes = [int(x) for x in rng.integers(200, 2_500, 33)]
     sizes[7] = 0                                             # an empty member
+    seams = {3: 16_385, 4: 16_384, 9: 1_024, 12: 3, 18: 1_025, 21: 1_023}   # cut to these below: a span of the record walk, a step of it
+    for v, n in seams.items():
+        sizes[v] = n
     cols = _share([random_columns(rng, n, L, truth, weird=False) for n in sizes], rng, L, 1_200, p=0.4)
     for v in range(33):
         if v % 3 == 0:
@@ -189,6 +192,8 @@ def wide(engine):
             o = rng.permutation(len(cols[v][0]))
             cols[v] = tuple(np.ascontiguousarray(x[o]) for x in cols[v])
     cols[7] = tuple(np.zeros(0, dt) for dt in (np.int32, np.int32, np.int32, np.float32, np.uint8))
+    for v, n in seams.items():                               # (members v % 3 == 0: sorted, and still sorted)
+        cols[v] = tuple(np.ascontiguousarray(x[:n]) for x in cols[v])
     b = run_batch(engine, cols, [tid] * 33)
     b.truth_hits()
     yield b, cols, truth
