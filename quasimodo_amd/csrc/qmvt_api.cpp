@@ -55,10 +55,10 @@ static int fail(int code, const char* fmt, ...) {
 
 void qm_set_error(const char* msg) { g_err = msg ? msg : ""; }   // for the other translation units of the library
 
-#define HIPCHK(expr)                                                                          \
+#define HIPCHK(...) /* (variadic: a call with template arguments holds commas) */             \
   do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) return fail(QM_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    hipError_t e_ = (__VA_ARGS__);                                                            \
+    if (e_ != hipSuccess) return fail(QM_E_HIP, "%s failed: %s (%s:%d)", #__VA_ARGS__, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
 struct Truth {
@@ -663,20 +663,51 @@ struct PassState {
   unsigned made = 0;                      // what the latest call made behind the latest run (1, or the pass's own bits); 0: nothing
 };
 // One row per pass, indexed by PassId: the entry point that enqueues it (as the getters' refusals name it), its timing marks
-// (0: the pass has no qm_batch_*_timings) and whether it reads the hit bitmaps and the record mask qm_batch_truth_hits writes.
-// A new pass adds its PassId and its row HERE, and nothing else: the members of qm_batch, batch_free, the reset in qm_batch_run
-// and the wait list of everything that rewrites what passes read (wait_passes) all follow from the table.
-struct PassInfo { const char* name; int marks; bool reads_hits; };
+// (0: the pass has no qm_batch_*_timings) and since when its result counts ("no <name> behind the latest <since>").
+// A new pass adds its PassId and its row HERE, a row of READS for every pass it reads, and nothing else: the members of qm_batch,
+// batch_free, the reset in qm_batch_run, wait_passes and what a producer called again does about its readers follow from the two tables.
+struct PassInfo { const char* name; int marks; const char* since; };
 static const PassInfo PASSES[N_PASSES] = {
-    {"qm_batch_motifs", 0, false},     {"qm_batch_af_profile", 0, false}, {"qm_batch_truth_hits", 0, false},
-    {"qm_batch_strata", 0, true},      {"qm_batch_boot", 0, true},        {"qm_batch_votes", 5, true},
-    {"qm_batch_nearmiss", 3, true},    {"qm_batch_surface", 4, false},    {"qm_batch_context", 4, true},
-    {"qm_batch_normalize", 4, false},  {"qm_batch_atomize", 4, false},    {"qm_batch_types", 3, false},
-    {"qm_batch_haplotypes", 6, false}, {"qm_batch_hapsubsets", 2, false}, {"qm_batch_rescue_roc", 5, false},
-    {"qm_batch_ladder", 3, false},
+    {"qm_batch_motifs", 0, "run"},     {"qm_batch_af_profile", 0, "run"}, {"qm_batch_truth_hits", 0, "run"},
+    {"qm_batch_strata", 0, "run"},     {"qm_batch_boot", 0, "run"},       {"qm_batch_votes", 5, "run"},
+    {"qm_batch_nearmiss", 3, "run"},   {"qm_batch_surface", 4, "run"},    {"qm_batch_context", 4, "run"},
+    {"qm_batch_normalize", 4, "run"},  {"qm_batch_atomize", 4, "run"},    {"qm_batch_types", 3, "run"},
+    {"qm_batch_haplotypes", 6, "run"}, {"qm_batch_hapsubsets", 2, "qm_batch_haplotypes"},
+    {"qm_batch_rescue_roc", 5, "run of its producers"},                   {"qm_batch_ladder", 3, "run of its producers"},
 };
 // (P_HAPLO: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
 // flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
+
+// Which pass reads which, one row per edge.  need: the bits of the producer's made the reader asks for (~0u: that it ran); call:
+// the producer's call as the reader's refusal prints it (pass_needs).  forget: the bits of the READER's made that go when the
+// producer is called again: it rewrites and may regrow what the reader reads, so it first waits on the host for the reader
+// (pass_open, in the order of the rows).  None for the readers of P_TRUTH: the bitmaps of one run are the same whoever asks for
+// them again, and that pass orders itself behind them on the stream (wait_passes).  A reader decides per call which edges it uses.
+struct PassRead { PassId reader, producer; unsigned need, forget; const char* call; };
+constexpr PassRead READS[] = {
+    {P_STRATA, P_TRUTH, ~0u, 0, "a qm_batch_truth_hits"},   {P_BOOT, P_TRUTH, ~0u, 0, "a qm_batch_truth_hits"},
+    {P_VOTES, P_TRUTH, ~0u, 0, "a qm_batch_truth_hits"},    {P_NEARMISS, P_TRUTH, ~0u, 0, "a qm_batch_truth_hits"},
+    {P_CONTEXT, P_TRUTH, ~0u, 0, "a qm_batch_truth_hits"},
+    {P_RROC, P_NORM, QM_NORM_COLUMNS, QM_RROC_NORM, "qm_batch_normalize(.., QM_NORM_COLUMNS)"},
+    {P_LADDER, P_NORM, QM_NORM_COLUMNS, ~0u, "qm_batch_normalize(.., QM_NORM_COLUMNS)"},
+    {P_RROC, P_ATOM, QM_ATOM_COLUMNS, QM_RROC_ATOM, "qm_batch_atomize(QM_ATOM_COLUMNS)"},
+    {P_LADDER, P_ATOM, QM_ATOM_COLUMNS, ~0u, "qm_batch_atomize(QM_ATOM_COLUMNS)"},
+    {P_HAPSUB, P_HAPLO, ~0u, ~0u, "qm_batch_haplotypes"},   // (refused by pass_ran and a sentence of the search's own)
+    {P_LADDER, P_HAPLO, QM_HAP_COLUMNS, ~0u, "qm_batch_haplotypes(.., QM_HAP_COLUMNS)"},
+    {P_LADDER, P_HAPSUB, QM_HAPSUB_COLUMNS, ~0u, "qm_batch_hapsubsets(QM_HAPSUB_COLUMNS)"},
+};
+// The row of an edge, -1 without one: a pass that refuses for, or waits for, a pass it is not said to read does not compile.
+constexpr int read_row(int reader, int producer) {
+  for (int i = 0; i < (int)(sizeof READS / sizeof READS[0]); ++i)
+    if (READS[i].reader == reader && READS[i].producer == producer) return i;
+  return -1;
+}
+constexpr bool reads_sound() {
+  for (const PassRead& r : READS)
+    if (r.reader == r.producer || r.reader >= N_PASSES || r.producer >= N_PASSES || !r.need) return false;
+  return true;
+}
+static_assert(reads_sound(), "READS: a pass reads itself, names no pass or needs nothing");
 
 struct qm_batch {
   qm_ctx* ctx = nullptr;
@@ -959,13 +990,13 @@ static void batch_free(qm_batch* b) {
 
 // ---- the passes of a batch still in flight (include/qmvt.h at qm_batch_run) ----
 // Orders what follows behind every pass of the batch still in flight, on whatever stream it was enqueued: `st` waits for the passes'
-// done events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps (PASSES).  The wait list of
-// everything that rewrites what passes read is the table of passes itself: no pass can be missing from it.  A done event exists
-// once its pass has been called: a batch that never ran a pass makes no HIP call here.
+// done events (wait_host: the host does).  hit_readers: only the passes that read the hit bitmaps (READS: the readers of P_TRUTH).
+// The wait list of everything that rewrites what passes read is the table of passes itself: no pass can be missing from it.  A
+// done event exists once its pass has been called: a batch that never ran a pass makes no HIP call here.
 static int wait_passes(qm_batch* b, hipStream_t st, bool wait_host, bool hit_readers = false) {
   for (int id = 0; id < N_PASSES; ++id) {
     const hipEvent_t e = b->pass[id].done;
-    if (!e || (hit_readers && !PASSES[id].reads_hits)) continue;
+    if (!e || (hit_readers && read_row(id, P_TRUTH) < 0)) continue;
     if (wait_host) HIPCHK(hipEventSynchronize(e));
     else HIPCHK(hipStreamWaitEvent(st, e, 0));
   }
@@ -2388,14 +2419,39 @@ static int widen_kept_tp(const uint64_t* d_kt, size_t rows, uint64_t* out) {
 
 // ---- the state of a pass (PassState, PASSES): how it opens, marks its kernels and closes; how its getters open ----
 // How a pass opens: the context's device, the caller's stream or the context's, and the pass's done event -- created at first use,
-// waited for on the host afterwards (the previous call of the pass has read its tables and left its outputs).
+// waited for on the host afterwards (the previous call of the pass has read its tables and left its outputs).  Then its readers
+// (READS): one behind the previous call, maybe on another stream, reads what this call rewrites and may regrow, so it is waited
+// for on the host, not only on the stream, and its result belongs to the call before.  OPEN_PASS declares `st` and returns a failure.
 static int pass_open(qm_batch* b, PassId id, void* stream, hipStream_t* st) {
   hipEvent_t* ev = &b->pass[id].done;
   HIPCHK(hipSetDevice(b->ctx->dev));
   *st = stream ? (hipStream_t)stream : b->ctx->stream;
   if (!*ev) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   else HIPCHK(hipEventSynchronize(*ev));
+  for (const PassRead& r : READS)
+    if (r.producer == id && r.forget) {
+      if (b->pass[r.reader].done) HIPCHK(hipEventSynchronize(b->pass[r.reader].done));
+      b->pass[r.reader].made &= ~r.forget;
+    }
   return QM_OK;
+}
+#define OPEN_PASS(b, id, stream, st) \
+  hipStream_t st;                    \
+  if (const int rc_ = pass_open(b, id, stream, &st); rc_ != QM_OK) return rc_
+// What a reader asks of a pass it reads (READS), in front of its own opening: refused unless the producer made what it needs;
+// `flag`: the reader's own flag that asks for this edge, if one does ...
+template <PassId READER, PassId PRODUCER>
+static int pass_needs(const qm_batch* b, const char* flag = "") {
+  constexpr int row = read_row(READER, PRODUCER);
+  static_assert(row >= 0, "READS has no such edge");
+  if (b->pass[PRODUCER].made & READS[row].need) return QM_OK;
+  return fail(QM_E_STATE, "%s: %s%sneeds %s behind the latest %s", PASSES[READER].name, flag, *flag ? " " : "", READS[row].call, PASSES[PRODUCER].since);
+}
+// ... and, in front of its first kernel that reads it: `st` waits for the producer, on whatever stream it was enqueued.
+template <PassId READER, PassId PRODUCER>
+static hipError_t pass_wait(qm_batch* b, hipStream_t st) {
+  static_assert(read_row(READER, PRODUCER) >= 0, "READS has no such edge");
+  return hipStreamWaitEvent(st, b->pass[PRODUCER].done, 0);
 }
 // In front of the first mark of a call: with qm_batch_set_timing on, the marks of the pass exist from here on (they need timing;
 // the done events do without); the call has recorded none yet.
@@ -2419,10 +2475,10 @@ static hipError_t pass_done(qm_batch* b, PassId id, hipStream_t st, unsigned mad
   if (e == hipSuccess) b->pass[id].made = made;
   return e;
 }
-// How the getters of a pass open: refused while the pass made nothing behind the latest `since` ...
-static int pass_ran(const qm_batch* b, PassId id, const char* who, const char* since = "run") {
+// How the getters of a pass open: refused while the pass made nothing behind the latest run, or what else it counts since ...
+static int pass_ran(const qm_batch* b, PassId id, const char* who) {
   if (b->pass[id].made) return QM_OK;
-  return fail(QM_E_STATE, "%s: no %s behind the latest %s", who, PASSES[id].name, since);
+  return fail(QM_E_STATE, "%s: no %s behind the latest %s", who, PASSES[id].name, PASSES[id].since);
 }
 #define NEED_PASS(b, id, who) \
   if (!(b)) return fail(QM_E_INVAL, who ": NULL batch"); \
@@ -2433,9 +2489,9 @@ static hipError_t pass_result(qm_batch* b, PassId id) {
   return e != hipSuccess ? e : hipEventSynchronize(b->pass[id].done);
 }
 // The qm_batch_*_timings of a pass: the milliseconds between its marks, one value fewer than there are marks.
-static int pass_timings(qm_batch* b, PassId id, const char* who, const char* since, float* ms) {
+static int pass_timings(qm_batch* b, PassId id, const char* who, float* ms) {
   if (!b || !ms) return fail(QM_E_INVAL, "%s: NULL", who);
-  const int rc = pass_ran(b, id, who, since);
+  const int rc = pass_ran(b, id, who);
   if (rc != QM_OK) return rc;
   const PassState& p = b->pass[id];
   if (!p.timed) return fail(QM_E_STATE, "%s: timing is off", who);
@@ -2533,9 +2589,7 @@ extern "C" int qm_batch_motifs(qm_batch* b, const int32_t* genome_id_per_vcf, vo
   qm_ctx* c = b->ctx;
   int rc = genomes_named(c, "qm_batch_motifs", genome_id_per_vcf, b->n_vcf);
   if (rc != QM_OK) return rc;
-  hipStream_t st;   // (the previous call's copy has read the page-locked descriptors)
-  rc = pass_open(b, P_MOTIFS, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_MOTIFS, stream, st);   // (the previous call's copy has read the page-locked descriptors)
   const size_t nv = (size_t)b->n_vcf;
   // first use: every piece on its own, so that a call that failed half way is completed by the next
   rc = b->d_motifs.grow((int64_t)(nv * MOTIF_ROW_WORDS), &b->dev_bytes);
@@ -2593,11 +2647,9 @@ extern "C" int qm_batch_af_profile(qm_batch* b, int32_t window, int32_t n_pos_bi
   NEED_FINISHED(b, "qm_batch_af_profile");
   if (window < 1 || window >= QM_POS_LIMIT || n_pos_bins < 1 || n_af_bins < 1 || (int64_t)n_pos_bins * n_af_bins > QM_AFP_MAX_CELLS)
     return fail(QM_E_INVAL, "qm_batch_af_profile: window %d, %d x %d bins (1 <= window < 2^28, at most %d cells)", window, n_af_bins, n_pos_bins, QM_AFP_MAX_CELLS);
-  hipStream_t st;   // (the previous pass has read the marks and left the outputs)
-  int rc = pass_open(b, P_AFP, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_AFP, stream, st);   // (the previous pass has read the marks and left the outputs)
   const size_t nv = (size_t)b->n_vcf, cells = (size_t)n_pos_bins * (size_t)n_af_bins;
-  rc = b->d_afgrid.grow((int64_t)(nv * 2 * cells), &b->dev_bytes);
+  int rc = b->d_afgrid.grow((int64_t)(nv * 2 * cells), &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_afextra.grow((int64_t)(nv * 2 * AFP_EXTRA), &b->dev_bytes);
   if (rc == QM_OK) rc = b->d_afmark.grow((int64_t)nv, &b->dev_bytes);
   if (rc != QM_OK) return rc;
@@ -2639,13 +2691,11 @@ extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* 
   if (!what || (what & ~(QM_STRATA_RECORDS | QM_STRATA_TRUTH))) return fail(QM_E_INVAL, "qm_batch_strata: what = %u", what);
   if (what & QM_STRATA_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_strata: allele-extended batches have no truth-side bitmaps (QM_STRATA_RECORDS only)");
-    if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_strata: QM_STRATA_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    if (pass_needs<P_STRATA, P_TRUTH>(b, "QM_STRATA_TRUTH") != QM_OK) return QM_E_STATE;
     const int rc = truths_live(b, "qm_batch_strata");
     if (rc != QM_OK) return rc;
   }
-  hipStream_t st;
-  const int rc0 = pass_open(b, P_STRATA, stream, &st);
-  if (rc0 != QM_OK) return rc0;
+  OPEN_PASS(b, P_STRATA, stream, st);
   const size_t nv = (size_t)b->n_vcf;
   const int S = t->n_strata;
   b->pass[P_STRATA].made = 0;
@@ -2684,7 +2734,7 @@ extern "C" int qm_batch_strata(qm_batch* b, int strata_id, unsigned what, void* 
     if (rc != QM_OK) return rc;
     std::vector<StrataTruthRow> rows(nv);
     std::vector<uint8_t> done(c->truths.size(), 0);
-    HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(pass_wait<P_STRATA, P_TRUTH>(b, st));   // the hit bitmaps, on whatever stream they were made
     for (size_t v = 0; v < nv; ++v) {
       const size_t tid = (size_t)b->L.vcfs[v].truth;
       const int64_t tn = b->h_hit_tn[v];
@@ -2731,13 +2781,11 @@ extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, i
   if (rc != QM_OK) return rc;
   if (what & QM_CX_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_context: allele-extended batches have no truth-side bitmaps (QM_CX_RECORDS only)");
-    if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_context: QM_CX_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    if (pass_needs<P_CONTEXT, P_TRUTH>(b, "QM_CX_TRUTH") != QM_OK) return QM_E_STATE;
     rc = truths_live(b, "qm_batch_context");
     if (rc != QM_OK) return rc;
   }
-  hipStream_t st;
-  rc = pass_open(b, P_CONTEXT, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_CONTEXT, stream, st);
   const size_t nv = (size_t)b->n_vcf, n_cells = (size_t)(16 * ng + 1);
   b->pass[P_CONTEXT].made = 0;   // from here on the outputs are rewritten
   rc = b->cx_gen.grow((int64_t)std::max<size_t>(nv * n_cells, 1), &b->dev_bytes);
@@ -2788,7 +2836,7 @@ extern "C" int qm_batch_context(qm_batch* b, const int32_t* genome_id_per_vcf, i
       rows[v].len = tabs[v].len;
       max_n = std::max(max_n, rows[v].n);
     }
-    HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(pass_wait<P_CONTEXT, P_TRUTH>(b, st));   // the hit bitmaps, on whatever stream they were made
     if (nv) HIPCHK(hipMemcpy(b->cx_rows, rows.data(), nv * sizeof(ContextTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
     HIPCHK(hipMemsetAsync(b->cx_tru, 0, words * 8, st));
     launch_context_truth(b->cx_rows, (int)nv, max_n, ng, reinterpret_cast<unsigned long long*>(b->cx_tru.p), st);
@@ -2814,7 +2862,7 @@ extern "C" int qm_batch_get_context(qm_batch* b, uint64_t* rec, uint64_t* tru, u
   return QM_OK;
 }
 extern "C" int qm_batch_context_timings(qm_batch* b, float* ms3) {
-  const int rc = pass_timings(b, P_CONTEXT, "qm_batch_context_timings", "run", ms3);
+  const int rc = pass_timings(b, P_CONTEXT, "qm_batch_context_timings", ms3);
   if (rc == QM_OK && !b->cx_built) ms3[0] = 0.0f;   // every table was cached
   return rc;
 }
@@ -2869,16 +2917,8 @@ extern "C" int qm_batch_normalize(qm_batch* b, const int32_t* genome_id_per_vcf,
   if (rc != QM_OK) return rc;
   for (size_t v = 0; v < nv; ++v)
     if (pair_of[v] >= 0) bit_words += 2 * (size_t)(norm_slots(c->truths[(size_t)b->L.vcfs[v].truth].xn) / 32u);
-  hipStream_t st;
-  rc = pass_open(b, P_NORM, stream, &st);
-  if (rc != QM_OK) return rc;
-  // A sweep behind the previous call (qm_batch_rescue_roc, maybe on another stream) reads the columns this call rewrites and may
-  // regrow: it is waited for here, not only on the stream.
-  if (b->pass[P_RROC].done) HIPCHK(hipEventSynchronize(b->pass[P_RROC].done));
-  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (the ladder reads the class bytes and the bitmaps)
-  b->pass[P_NORM].made = 0;   // from here on the outputs are rewritten
-  b->pass[P_RROC].made &= ~QM_RROC_NORM;   // ... and the sweep's rows belong to the call before
-  b->pass[P_LADDER].made = 0;              // ... and so do the ladder's
+  OPEN_PASS(b, P_NORM, stream, st);
+  b->pass[P_NORM].made = 0;   // from here on the outputs are rewritten (pass_open: the sweep and the ladder are done and forgotten)
   const size_t np = (size_t)b->L.n_pad;
   rc = b->nz_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->nz_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -2959,7 +2999,7 @@ extern "C" int qm_batch_get_normalized(qm_batch* b, int v, int32_t* pos, int32_t
   return QM_OK;
 }
 extern "C" int qm_batch_normalize_timings(qm_batch* b, float* ms3) {
-  return pass_timings(b, P_NORM, "qm_batch_normalize_timings", "run", ms3);
+  return pass_timings(b, P_NORM, "qm_batch_normalize_timings", ms3);
 }
 extern "C" int qm_truth_entries(qm_ctx* c, int truth_id, int32_t* pos, int32_t* ref, int32_t* alt, int64_t capacity, int64_t* n_out) {
   if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_entries: bad arguments");
@@ -3080,14 +3120,8 @@ extern "C" int qm_batch_atomize(qm_batch* b, unsigned what, void* stream) {
     bit_words += (size_t)(sets[k].slots / 32u) + (size_t)(xn / 32 + 1);
     max_lanes = std::max<int64_t>(max_lanes, std::max<int64_t>(xn, (int64_t)(sets[k].slots / 32u)));
   }
-  hipStream_t st;
-  rc = pass_open(b, P_ATOM, stream, &st);
-  if (rc != QM_OK) return rc;
-  if (b->pass[P_RROC].done) HIPCHK(hipEventSynchronize(b->pass[P_RROC].done));   // (as in qm_batch_normalize: the sweep reads the sets and the columns)
-  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (and the ladder)
-  b->pass[P_ATOM].made = 0;   // from here on the outputs are rewritten
-  b->pass[P_RROC].made &= ~QM_RROC_ATOM;
-  b->pass[P_LADDER].made = 0;
+  OPEN_PASS(b, P_ATOM, stream, st);
+  b->pass[P_ATOM].made = 0;   // from here on the outputs are rewritten (as in qm_batch_normalize)
   const size_t np = (size_t)b->L.n_pad;
   rc = b->at_pool.grow((int64_t)std::max<size_t>(pool_words, 2), &b->dev_bytes);
   if (rc == QM_OK) rc = b->at_bits.grow((int64_t)std::max<size_t>(bit_words, 1), &b->dev_bytes);
@@ -3164,7 +3198,7 @@ extern "C" int qm_batch_get_atomized(qm_batch* b, int v, uint8_t* cls, uint8_t* 
   return QM_OK;
 }
 extern "C" int qm_batch_atomize_timings(qm_batch* b, float* ms3) {
-  return pass_timings(b, P_ATOM, "qm_batch_atomize_timings", "run", ms3);
+  return pass_timings(b, P_ATOM, "qm_batch_atomize_timings", ms3);
 }
 extern "C" int qm_truth_atoms(qm_ctx* c, int truth_id, uint32_t* keys, int64_t capacity, int64_t* n_out) {
   if (!c || !n_out || capacity < 0) return fail(QM_E_INVAL, "qm_truth_atoms: bad arguments");
@@ -3194,10 +3228,8 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
   if (which == 0 || (which & ~(QM_RROC_NORM | QM_RROC_ATOM))) return fail(QM_E_INVAL, "qm_batch_rescue_roc: which = %u", which);
   if (!b->ext) return fail(QM_E_STATE, "qm_batch_rescue_roc: a single-base batch has no rescue passes to sweep (create the batch with QM_BATCH_ALLELES)");
   const bool wn = (which & QM_RROC_NORM) != 0, wa = (which & QM_RROC_ATOM) != 0;
-  if (wn && !(b->pass[P_NORM].made & QM_NORM_COLUMNS))
-    return fail(QM_E_STATE, "qm_batch_rescue_roc: QM_RROC_NORM needs qm_batch_normalize(.., QM_NORM_COLUMNS) behind the latest run");
-  if (wa && !(b->pass[P_ATOM].made & QM_ATOM_COLUMNS))
-    return fail(QM_E_STATE, "qm_batch_rescue_roc: QM_RROC_ATOM needs qm_batch_atomize(QM_ATOM_COLUMNS) behind the latest run");
+  if (wn && pass_needs<P_RROC, P_NORM>(b, "QM_RROC_NORM") != QM_OK) return QM_E_STATE;
+  if (wa && pass_needs<P_RROC, P_ATOM>(b, "QM_RROC_ATOM") != QM_OK) return QM_E_STATE;
   qm_ctx* c = b->ctx;
   const size_t nv = (size_t)b->n_vcf, nb = (size_t)b->n_bins;
   int rc = truths_live(b, "qm_batch_rescue_roc");
@@ -3219,9 +3251,7 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
       off_e[v] = words; words += rroc_cell_words(t.xn) + 1;
     }
   }
-  hipStream_t st;
-  rc = pass_open(b, P_RROC, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_RROC, stream, st);
   b->pass[P_RROC].made = 0;   // from here on the outputs are rewritten
   const size_t rows = nv * 3 * nb, out_words = std::max<size_t>(2 * rows + 2 * nv, 1);
   rc = b->rr_best.grow((int64_t)std::max<size_t>(words, 1), &b->dev_bytes);
@@ -3233,8 +3263,8 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
     if (wa) { vcfs[v].best_atom = b->rr_best + off_a[v]; vcfs[v].best_entry = b->rr_best + off_e[v]; }
   }
   HIPCHK(pass_marks(b, P_RROC));
-  if (wn) HIPCHK(hipStreamWaitEvent(st, b->pass[P_NORM].done, 0));   // the producers may have run on other streams
-  if (wa) HIPCHK(hipStreamWaitEvent(st, b->pass[P_ATOM].done, 0));
+  if (wn) HIPCHK(pass_wait<P_RROC, P_NORM>(b, st));   // the producers may have run on other streams
+  if (wa) HIPCHK(pass_wait<P_RROC, P_ATOM>(b, st));
   if (nv) HIPCHK(hipMemcpy(b->rr_vcfs, vcfs.data(), nv * sizeof(RrocVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
   HIPCHK(hipMemsetAsync(b->rr_best, 0, std::max<size_t>(words, 1) * 4, st));
   HIPCHK(hipMemsetAsync(b->rr_out, 0, out_words * 8, st));
@@ -3272,8 +3302,7 @@ extern "C" int qm_batch_rescue_roc(qm_batch* b, unsigned which, void* stream) {
   return QM_OK;
 }
 extern "C" int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n, uint64_t* roc_a, uint64_t* base) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_rescue_roc: NULL batch");
-  if (pass_ran(b, P_RROC, "qm_batch_get_rescue_roc", "run of its producers") != QM_OK) return QM_E_STATE;
+  NEED_PASS(b, P_RROC, "qm_batch_get_rescue_roc");
   if ((roc_n && !(b->pass[P_RROC].made & QM_RROC_NORM)) || (roc_a && !(b->pass[P_RROC].made & QM_RROC_ATOM)))
     return fail(QM_E_STATE, "qm_batch_get_rescue_roc: the latest qm_batch_rescue_roc did not sweep by %s", roc_n && !(b->pass[P_RROC].made & QM_RROC_NORM) ? "normal form" : "atoms");
   HIPCHK(pass_result(b, P_RROC));
@@ -3284,7 +3313,7 @@ extern "C" int qm_batch_get_rescue_roc(qm_batch* b, uint64_t* roc_n, uint64_t* r
   return QM_OK;
 }
 extern "C" int qm_batch_rescue_roc_timings(qm_batch* b, float* ms4) {
-  return pass_timings(b, P_RROC, "qm_batch_rescue_roc_timings", "run of its producers", ms4);
+  return pass_timings(b, P_RROC, "qm_batch_rescue_roc_timings", ms4);
 }
 // ---- the four rescues combined: final TP, FP and FN and the Venn of methods ----
 extern "C" int qm_batch_ladder(qm_batch* b, unsigned what, void* stream) {
@@ -3292,14 +3321,10 @@ extern "C" int qm_batch_ladder(qm_batch* b, unsigned what, void* stream) {
   if (what & ~(QM_LADDER_SUBSETS | QM_LADDER_COLUMNS)) return fail(QM_E_INVAL, "qm_batch_ladder: what = %u", what);
   if (!b->ext) return fail(QM_E_STATE, "qm_batch_ladder: a single-base batch has no rescue passes to combine (create the batch with QM_BATCH_ALLELES)");
   const bool subsets = (what & QM_LADDER_SUBSETS) != 0, cols = (what & QM_LADDER_COLUMNS) != 0;
-  if (!(b->pass[P_NORM].made & QM_NORM_COLUMNS))
-    return fail(QM_E_STATE, "qm_batch_ladder: needs qm_batch_normalize(.., QM_NORM_COLUMNS) behind the latest run");
-  if (!(b->pass[P_ATOM].made & QM_ATOM_COLUMNS))
-    return fail(QM_E_STATE, "qm_batch_ladder: needs qm_batch_atomize(QM_ATOM_COLUMNS) behind the latest run");
-  if (!(b->pass[P_HAPLO].made & QM_HAP_COLUMNS))
-    return fail(QM_E_STATE, "qm_batch_ladder: needs qm_batch_haplotypes(.., QM_HAP_COLUMNS) behind the latest run");
-  if (subsets && !(b->pass[P_HAPSUB].made & QM_HAPSUB_COLUMNS))
-    return fail(QM_E_STATE, "qm_batch_ladder: QM_LADDER_SUBSETS needs qm_batch_hapsubsets(QM_HAPSUB_COLUMNS) behind the latest qm_batch_haplotypes");
+  if (pass_needs<P_LADDER, P_NORM>(b) != QM_OK) return QM_E_STATE;
+  if (pass_needs<P_LADDER, P_ATOM>(b) != QM_OK) return QM_E_STATE;
+  if (pass_needs<P_LADDER, P_HAPLO>(b) != QM_OK) return QM_E_STATE;
+  if (subsets && pass_needs<P_LADDER, P_HAPSUB>(b, "QM_LADDER_SUBSETS") != QM_OK) return QM_E_STATE;
   qm_ctx* c = b->ctx;
   const size_t nv = (size_t)b->n_vcf;
   int rc = truths_live(b, "qm_batch_ladder");
@@ -3316,9 +3341,7 @@ extern "C" int qm_batch_ladder(qm_batch* b, unsigned what, void* stream) {
     vcfs[v].heoff = b->hp_eoff[v];
     vcfs[v].has = (b->nz_has[v] ? LADDER_HAS_NORM : 0u) | (b->hp_has[v] ? LADDER_HAS_HAP : 0u);
   }
-  hipStream_t st;
-  rc = pass_open(b, P_LADDER, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_LADDER, stream, st);
   b->pass[P_LADDER].made = 0;   // from here on the outputs are rewritten
   const size_t np = (size_t)b->L.n_pad, rows = nv * LADDER_COLS, out_words = std::max<size_t>(2 * rows, 1);
   rc = b->ld_vcfs.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
@@ -3328,10 +3351,10 @@ extern "C" int qm_batch_ladder(qm_batch* b, unsigned what, void* stream) {
   if (rc != QM_OK) return rc;
   b->ld_eoff = eoff;
   HIPCHK(pass_marks(b, P_LADDER));
-  HIPCHK(hipStreamWaitEvent(st, b->pass[P_NORM].done, 0));   // the producers may have run on other streams
-  HIPCHK(hipStreamWaitEvent(st, b->pass[P_ATOM].done, 0));
-  HIPCHK(hipStreamWaitEvent(st, b->pass[P_HAPLO].done, 0));
-  if (subsets) HIPCHK(hipStreamWaitEvent(st, b->pass[P_HAPSUB].done, 0));
+  HIPCHK(pass_wait<P_LADDER, P_NORM>(b, st));   // the producers may have run on other streams
+  HIPCHK(pass_wait<P_LADDER, P_ATOM>(b, st));
+  HIPCHK(pass_wait<P_LADDER, P_HAPLO>(b, st));
+  if (subsets) HIPCHK(pass_wait<P_LADDER, P_HAPSUB>(b, st));
   if (nv) HIPCHK(hipMemcpy(b->ld_vcfs, vcfs.data(), nv * sizeof(LadderVcf), hipMemcpyHostToDevice));   // blocking: vcfs dies here
   HIPCHK(hipMemsetAsync(b->ld_out, 0, out_words * 8, st));
   HIPCHK(pass_mark(b, P_LADDER, 0, st));
@@ -3361,8 +3384,7 @@ extern "C" int qm_batch_ladder(qm_batch* b, unsigned what, void* stream) {
   return QM_OK;
 }
 extern "C" int qm_batch_get_ladder(qm_batch* b, uint64_t* rec, uint64_t* tru) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_ladder: NULL batch");
-  if (pass_ran(b, P_LADDER, "qm_batch_get_ladder", "run of its producers") != QM_OK) return QM_E_STATE;
+  NEED_PASS(b, P_LADDER, "qm_batch_get_ladder");
   HIPCHK(pass_result(b, P_LADDER));
   const size_t nv = (size_t)b->n_vcf, rows = nv * LADDER_COLS;
   if (rec && nv) HIPCHK(hipMemcpy(rec, b->ld_out, rows * 8, hipMemcpyDeviceToHost));
@@ -3370,8 +3392,7 @@ extern "C" int qm_batch_get_ladder(qm_batch* b, uint64_t* rec, uint64_t* tru) {
   return QM_OK;
 }
 extern "C" int qm_batch_get_laddered(qm_batch* b, int v, uint8_t* mask, uint8_t* entry_mask) {
-  if (!b) return fail(QM_E_INVAL, "qm_batch_get_laddered: NULL batch");
-  if (pass_ran(b, P_LADDER, "qm_batch_get_laddered", "run of its producers") != QM_OK) return QM_E_STATE;
+  NEED_PASS(b, P_LADDER, "qm_batch_get_laddered");
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_laddered: VCF %d (the batch has %d)", v, b->n_vcf);
   if (!(b->pass[P_LADDER].made & QM_LADDER_COLUMNS))
     return fail(QM_E_STATE, "qm_batch_get_laddered: the latest qm_batch_ladder did not keep the columns (QM_LADDER_COLUMNS)");
@@ -3383,7 +3404,7 @@ extern "C" int qm_batch_get_laddered(qm_batch* b, int v, uint8_t* mask, uint8_t*
   return QM_OK;
 }
 extern "C" int qm_batch_ladder_timings(qm_batch* b, float* ms2) {
-  return pass_timings(b, P_LADDER, "qm_batch_ladder_timings", "run of its producers", ms2);
+  return pass_timings(b, P_LADDER, "qm_batch_ladder_timings", ms2);
 }
 // ---- TP, FP and FN by variant type and size ----
 extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t* len, const uint32_t* head, const uint32_t* tail,
@@ -3403,9 +3424,7 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
   const size_t nv = (size_t)b->n_vcf;
   int rc = truths_live(b, "qm_batch_types");
   if (rc != QM_OK) return rc;
-  hipStream_t st;
-  rc = pass_open(b, P_TYPES, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_TYPES, stream, st);
   b->pass[P_TYPES].made = 0;   // from here on the outputs are rewritten
   TypeBins B;
   memset(&B, 0, sizeof B);
@@ -3495,7 +3514,7 @@ extern "C" int qm_batch_get_typed(qm_batch* b, int v, uint8_t* row) {
   return QM_OK;
 }
 extern "C" int qm_batch_types_timings(qm_batch* b, float* ms2) {
-  return pass_timings(b, P_TYPES, "qm_batch_types_timings", "run", ms2);
+  return pass_timings(b, P_TYPES, "qm_batch_types_timings", ms2);
 }
 // ---- clusters of records matched by replayed haplotype ----
 // The pool words of one site table: [elo | ehi | esite | slo | shi][xn], sfirst[xn + 1], n_sites[2], ewhy[xn] as bytes
@@ -3548,16 +3567,8 @@ extern "C" int qm_batch_haplotypes(qm_batch* b, const int32_t* genome_id_per_vcf
     max_entries = std::max(max_entries, xn);
     eoff[v + 1] += xn;
   }
-  hipStream_t st;
-  rc = pass_open(b, P_HAPLO, stream, &st);
-  if (rc != QM_OK) return rc;
-  // A search behind the previous call (qm_batch_hapsubsets, maybe on another stream) reads what this call rewrites, regrows and
-  // copies over from the host: it is waited for here, not only on the stream.
-  if (b->pass[P_HAPSUB].done) HIPCHK(hipEventSynchronize(b->pass[P_HAPSUB].done));
-  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (as in qm_batch_normalize: the ladder reads the classes)
-  b->pass[P_HAPLO].made = 0;   // from here on the outputs are rewritten
-  b->pass[P_HAPSUB].made = 0;   // ... and the search's results belong to the call before
-  b->pass[P_LADDER].made = 0;   // ... and so do the ladder's rows
+  OPEN_PASS(b, P_HAPLO, stream, st);
+  b->pass[P_HAPLO].made = 0;   // from here on the outputs are rewritten (pass_open: the search and the ladder are done and forgotten)
   const size_t np = (size_t)b->L.n_pad;
   const bool cols = (what & QM_HAP_COLUMNS) != 0;
   rc = b->hp_pool.grow((int64_t)std::max<size_t>(pool_words, 1), &b->dev_bytes);
@@ -3665,7 +3676,7 @@ extern "C" int qm_batch_get_haplotyped(qm_batch* b, int v, uint8_t* cls, int32_t
   return QM_OK;
 }
 extern "C" int qm_batch_haplotype_timings(qm_batch* b, float* ms5) {
-  return pass_timings(b, P_HAPLO, "qm_batch_haplotype_timings", "run", ms5);
+  return pass_timings(b, P_HAPLO, "qm_batch_haplotype_timings", ms5);
 }
 // ---- a subset search inside the mismatched sites of the haplotype pass ----
 extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
@@ -3684,12 +3695,8 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   }
   int rc = truths_live(b, "qm_batch_hapsubsets");
   if (rc != QM_OK) return rc;
-  hipStream_t st;
-  rc = pass_open(b, P_HAPSUB, stream, &st);
-  if (rc != QM_OK) return rc;
-  if (b->pass[P_LADDER].done) HIPCHK(hipEventSynchronize(b->pass[P_LADDER].done));   // (as in qm_batch_normalize: the ladder reads the second classes)
-  b->pass[P_HAPSUB].made = 0;   // from here on the outputs are rewritten
-  b->pass[P_LADDER].made = 0;   // ... and the ladder's rows belong to the call before
+  OPEN_PASS(b, P_HAPSUB, stream, st);
+  b->pass[P_HAPSUB].made = 0;   // from here on the outputs are rewritten (as in qm_batch_normalize: the ladder reads the second classes)
   b->hs_listed = false;
   const size_t np = (size_t)b->L.n_pad, npairs = (size_t)b->hp_npairs, ne = (size_t)b->hp_eoff[nv];
   rc = b->hs_sub.grow((int64_t)std::max<size_t>(nv * HAPSUB_COLS, 1), &b->dev_bytes);
@@ -3698,7 +3705,7 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
   if (rc == QM_OK && cols) rc = b->hs_ecls.grow((int64_t)std::max<size_t>(ne, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
   HIPCHK(pass_marks(b, P_HAPSUB));
-  HIPCHK(hipStreamWaitEvent(st, b->pass[P_HAPLO].done, 0));   // the pass may have run on another stream
+  HIPCHK(pass_wait<P_HAPSUB, P_HAPLO>(b, st));   // the pass may have run on another stream
   HIPCHK(pass_mark(b, P_HAPSUB, 0, st));
   HIPCHK(hipMemsetAsync(b->hs_res, 0, std::max<size_t>(npairs, 1) * 4, st));
   if (cols) {
@@ -3723,7 +3730,7 @@ extern "C" int qm_batch_hapsubsets(qm_batch* b, unsigned what, void* stream) {
 }
 extern "C" int qm_batch_get_hapsubsets(qm_batch* b, uint64_t* sub) {
   NEED_PASS(b, P_HAPLO, "qm_batch_get_hapsubsets");
-  if (pass_ran(b, P_HAPSUB, "qm_batch_get_hapsubsets", "qm_batch_haplotypes") != QM_OK) return QM_E_STATE;
+  if (pass_ran(b, P_HAPSUB, "qm_batch_get_hapsubsets") != QM_OK) return QM_E_STATE;
   HIPCHK(pass_result(b, P_HAPSUB));
   const size_t nv = (size_t)b->n_vcf;
   if (sub && nv) HIPCHK(hipMemcpy(sub, b->hs_sub, nv * HAPSUB_COLS * 8, hipMemcpyDeviceToHost));
@@ -3732,7 +3739,7 @@ extern "C" int qm_batch_get_hapsubsets(qm_batch* b, uint64_t* sub) {
 extern "C" int qm_batch_get_hapsubsetted(qm_batch* b, int v, uint8_t* cls_s, uint8_t* entry_cls_s, int32_t* site_s, uint8_t* smask, uint8_t* tmask,
                                          int64_t capacity, int64_t* n_out) {
   NEED_PASS(b, P_HAPLO, "qm_batch_get_hapsubsetted");
-  if (pass_ran(b, P_HAPSUB, "qm_batch_get_hapsubsetted", "qm_batch_haplotypes") != QM_OK) return QM_E_STATE;
+  if (pass_ran(b, P_HAPSUB, "qm_batch_get_hapsubsetted") != QM_OK) return QM_E_STATE;
   if (v < 0 || v >= b->n_vcf) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: VCF %d (the batch has %d)", v, b->n_vcf);
   if (capacity < 0) return fail(QM_E_INVAL, "qm_batch_get_hapsubsetted: capacity %lld", (long long)capacity);
   if (!b->hp_has[(size_t)v]) return fail(QM_E_STATE, "qm_batch_get_hapsubsetted: VCF %d named no genome in the latest qm_batch_haplotypes", v);
@@ -3777,7 +3784,7 @@ extern "C" int qm_batch_get_hapsubsetted(qm_batch* b, int v, uint8_t* cls_s, uin
 extern "C" int qm_batch_hapsubset_timings(qm_batch* b, float* ms1) {
   if (!b || !ms1) return fail(QM_E_INVAL, "qm_batch_hapsubset_timings: NULL");
   if (pass_ran(b, P_HAPLO, "qm_batch_hapsubset_timings") != QM_OK) return QM_E_STATE;
-  return pass_timings(b, P_HAPSUB, "qm_batch_hapsubset_timings", "qm_batch_haplotypes", ms1);
+  return pass_timings(b, P_HAPSUB, "qm_batch_hapsubset_timings", ms1);
 }
 extern "C" int qm_truth_sites(qm_ctx* c, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
                               int64_t* n_out) {
@@ -3825,17 +3832,15 @@ extern "C" int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t
   if (!what || (what & ~(QM_BOOT_RECORDS | QM_BOOT_TRUTH))) return fail(QM_E_INVAL, "qm_batch_boot: what = %u", what);
   if (what & QM_BOOT_TRUTH) {
     if (b->ext) return fail(QM_E_STATE, "qm_batch_boot: allele-extended batches have no truth-side bitmaps (QM_BOOT_RECORDS only)");
-    if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_boot: QM_BOOT_TRUTH needs a qm_batch_truth_hits behind the latest run");
+    if (pass_needs<P_BOOT, P_TRUTH>(b, "QM_BOOT_TRUTH") != QM_OK) return QM_E_STATE;
     const int rc = truths_live(b, "qm_batch_boot");
     if (rc != QM_OK) return rc;
   }
-  hipStream_t st;
-  int rc = pass_open(b, P_BOOT, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_BOOT, stream, st);
   const size_t nv = (size_t)b->n_vcf;
   b->pass[P_BOOT].made = 0;
   const size_t cw = nv * (size_t)(n_win + 2) * BOOT_COLS, rw = nv * (size_t)n_rep * BOOT_COLS;
-  rc = b->d_bcnt.grow((int64_t)std::max<size_t>(cw, 1), &b->dev_bytes);
+  int rc = b->d_bcnt.grow((int64_t)std::max<size_t>(cw, 1), &b->dev_bytes);
   if (rc == QM_OK && n_rep) rc = b->d_brep.grow((int64_t)std::max<size_t>(rw, 1), &b->dev_bytes);
   if (rc == QM_OK && (what & QM_BOOT_TRUTH)) rc = b->d_brows.grow((int64_t)std::max<size_t>(nv, 1), &b->dev_bytes);
   if (rc != QM_OK) return rc;
@@ -3857,7 +3862,7 @@ extern "C" int qm_batch_boot(qm_batch* b, int32_t window, int32_t n_win, int32_t
       rows[v].hits = b->d_hits + b->h_hit_off[v];
       rows[v].n = b->h_hit_tn[v];   // T' as the hit bitmaps were sized
     }
-    HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
+    HIPCHK(pass_wait<P_BOOT, P_TRUTH>(b, st));   // the hit bitmaps, on whatever stream they were made
     HIPCHK(hipMemcpy(b->d_brows, rows.data(), nv * sizeof(BootTruthRow), hipMemcpyHostToDevice));   // blocking: rows dies here
     launch_boot_truth(b->d_brows, (int)nv, window, n_win, b->d_bcnt, st);
     HIPCHK(hipGetLastError());
@@ -3901,7 +3906,7 @@ extern "C" int qm_batch_truth_hits(qm_batch* b, void* stream) {
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);
   if (!b->pass[P_TRUTH].done) HIPCHK(hipEventCreateWithFlags(&b->pass[P_TRUTH].done, hipEventDisableTiming));
   else if (b->hits_enqueued) HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // an earlier pass, on whatever stream, still writes the same buffers
-  rc = wait_passes(b, st, false, true);   // and the passes that read the hit bitmaps, on whatever stream (PASSES)
+  rc = wait_passes(b, st, false, true);   // and the passes that read the hit bitmaps, on whatever stream (READS)
   if (rc != QM_OK) return rc;
   // (the one pass that does not open with pass_open: a stream wait, not a host wait -- the host reads nothing the pass leaves here)
   rc = b->d_hit_off.grow((int64_t)nv + 1, &b->dev_bytes);
@@ -3996,7 +4001,7 @@ extern "C" int qm_batch_truth_regions(qm_batch* b, int n_groups, const int32_t* 
 extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_offsets, const int32_t* vcf_ids, void* stream) {
   NEED_FINISHED(b, "qm_batch_votes");
   if (b->ext) return fail(QM_E_STATE, "qm_batch_votes: allele-extended batches have no truth-side bitmaps (single-base batches only)");
-  if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_votes: needs a qm_batch_truth_hits behind the latest run");
+  if (pass_needs<P_VOTES, P_TRUTH>(b) != QM_OK) return QM_E_STATE;
   int rc = truths_live(b, "qm_batch_votes");
   if (rc != QM_OK) return rc;
   if (n_groups < 0 || (n_groups && (!group_offsets || !vcf_ids))) return fail(QM_E_INVAL, "qm_batch_votes: bad arguments");
@@ -4015,9 +4020,7 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
     if (rc != QM_OK) return rc;
     max_words = std::max(max_words, t.words);
   }
-  hipStream_t st;
-  rc = pass_open(b, P_VOTES, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_VOTES, stream, st);
   // a group's segment of the pair buffers holds its members' kept lines: the finished n_pass scalars bound the pairs from above
   std::vector<int64_t> sc(std::max<size_t>(nv, 1) * QM_N_SCALARS, 0);
   if (nv) HIPCHK(hipMemcpy(sc.data(), b->scalars, nv * QM_N_SCALARS * 8, hipMemcpyDeviceToHost));
@@ -4067,7 +4070,7 @@ extern "C" int qm_batch_votes(qm_batch* b, int n_groups, const int32_t* group_of
   if (nst) HIPCHK(hipMemcpy(b->vt_tile_seg, tile_seg.data(), (size_t)nst * 4, hipMemcpyHostToDevice));
   if (nv) HIPCHK(hipMemcpy(b->vt_slot, slot.data(), nv * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(b->vt_groups, G.data(), ng * sizeof(VoteGroup), hipMemcpyHostToDevice));
-  HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps and the record mask, on whatever stream they were made
+  HIPCHK(pass_wait<P_VOTES, P_TRUTH>(b, st));   // the hit bitmaps and the record mask, on whatever stream they were made
   HIPCHK(hipMemsetAsync(b->vt_out, 0, out_words * 8, st));
   HIPCHK(hipMemsetAsync(b->vt_cursor, 0, 2 * ng * 4, st));
   VoteOut O;
@@ -4107,7 +4110,7 @@ extern "C" int qm_batch_vote_timings(qm_batch* b, float* ms4) {
   if (!b || !ms4) return fail(QM_E_INVAL, "qm_batch_vote_timings: NULL");
   if (!b->pass[P_VOTES].made || !b->pass[P_VOTES].timed)   // (one message for both)
     return fail(QM_E_STATE, "qm_batch_vote_timings: timing is off or no qm_batch_votes behind the latest run");
-  return pass_timings(b, P_VOTES, "qm_batch_vote_timings", "run", ms4);
+  return pass_timings(b, P_VOTES, "qm_batch_vote_timings", ms4);
 }
 extern "C" int qm_batch_get_votes(qm_batch* b, uint64_t* tp_votes, uint64_t* fp_votes, uint64_t* private_tp, uint64_t* private_fp, int64_t* nokey) {
   NEED_PASS(b, P_VOTES, "qm_batch_get_votes");
@@ -4148,14 +4151,12 @@ extern "C" int qm_batch_get_vote_keys(qm_batch* b, int group, uint32_t* keys, ui
 extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
   NEED_FINISHED(b, "qm_batch_nearmiss");
   if (b->ext) return fail(QM_E_STATE, "qm_batch_nearmiss: allele-extended batches have no truth-side bitmaps (single-base batches only)");
-  if (!b->pass[P_TRUTH].made) return fail(QM_E_STATE, "qm_batch_nearmiss: needs a qm_batch_truth_hits behind the latest run");
+  if (pass_needs<P_NEARMISS, P_TRUTH>(b) != QM_OK) return QM_E_STATE;
   if (radius < 0 || radius > QM_NM_MAX_RADIUS) return fail(QM_E_INVAL, "qm_batch_nearmiss: radius %d (0 to %d)", radius, QM_NM_MAX_RADIUS);
   qm_ctx* c = b->ctx;
   int rc = truths_live(b, "qm_batch_nearmiss");
   if (rc != QM_OK) return rc;
-  hipStream_t st;
-  rc = pass_open(b, P_NEARMISS, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_NEARMISS, stream, st);
   const size_t nv = (size_t)b->n_vcf;
   const size_t hw = std::max<size_t>((size_t)b->h_hit_off[nv], 1);   // as d_hits
   const size_t out_words = std::max<size_t>(nv, 1) * (NM_R_CLASSES + NM_T_CLASSES);
@@ -4169,7 +4170,7 @@ extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
     HIPCHK(hipMemcpy(b->nm_tn, b->h_hit_tn.data(), nv * 8, hipMemcpyHostToDevice));
     b->nm_tn_uploaded = true;
   }
-  HIPCHK(hipStreamWaitEvent(st, b->pass[P_TRUTH].done, 0));   // the hit bitmaps, on whatever stream they were made
+  HIPCHK(pass_wait<P_NEARMISS, P_TRUTH>(b, st));   // the hit bitmaps, on whatever stream they were made
   HIPCHK(hipMemsetAsync(b->nm_planes, 0, NM_PLANES * hw * 4, st));
   HIPCHK(hipMemsetAsync(b->nm_out, 0, out_words * 8, st));
   NearmissParams P;
@@ -4196,7 +4197,7 @@ extern "C" int qm_batch_nearmiss(qm_batch* b, int32_t radius, void* stream) {
 }
 extern "C" int qm_batch_nearmiss_timings(qm_batch* b, float* ms2) {
   NEED_PASS(b, P_NEARMISS, "qm_batch_nearmiss_timings");
-  return pass_timings(b, P_NEARMISS, "qm_batch_nearmiss_timings", "run", ms2);
+  return pass_timings(b, P_NEARMISS, "qm_batch_nearmiss_timings", ms2);
 }
 extern "C" int qm_batch_get_nearmiss(qm_batch* b, uint64_t* rec, uint64_t* tru) {
   NEED_PASS(b, P_NEARMISS, "qm_batch_get_nearmiss");
@@ -4248,9 +4249,7 @@ extern "C" int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t
   qm_ctx* c = b->ctx;
   int rc = truths_live(b, "qm_batch_surface");
   if (rc != QM_OK) return rc;
-  hipStream_t st;
-  rc = pass_open(b, P_SURFACE, stream, &st);
-  if (rc != QM_OK) return rc;
+  OPEN_PASS(b, P_SURFACE, stream, st);
   const size_t nv = (size_t)b->n_vcf, cells = (size_t)nq * (size_t)na;
   if (b->h_sf_off.empty()) {   // (T' cannot change while the generations truths_live checks hold)
     b->h_sf_off.assign(nv + 1, 0);
@@ -4299,7 +4298,7 @@ extern "C" int qm_batch_surface(qm_batch* b, int32_t q_step, int32_t nq, int32_t
 }
 extern "C" int qm_batch_surface_timings(qm_batch* b, float* ms3) {
   NEED_PASS(b, P_SURFACE, "qm_batch_surface_timings");
-  return pass_timings(b, P_SURFACE, "qm_batch_surface_timings", "run", ms3);
+  return pass_timings(b, P_SURFACE, "qm_batch_surface_timings", ms3);
 }
 extern "C" int qm_batch_get_surface(qm_batch* b, uint64_t* S, uint64_t* extra) {
   NEED_PASS(b, P_SURFACE, "qm_batch_get_surface");

@@ -1,5 +1,5 @@
 """The state every pass over a finished batch keeps in qmvt_api.cpp: what it made behind the latest run, whether
-it recorded timing marks, and the event its getters wait for.  One table row per pass -- all fifteen of them -- says how the pass
+it recorded timing marks, and the event its getters wait for.  One table row per pass -- all sixteen of them -- says how the pass
 is enqueued, how its result is fetched, how its timings are read, and the refusals of the library WORD FOR WORD: the strings below
 are the library's own, so a change of the host code that moves a check, a message or the point where a pass forgets its result
 shows here, whatever the kernels compute.
