@@ -15,6 +15,10 @@
 // ROUND -- which records are loaded, whose positions enter the position-OR, how many mask words of a ragged end are
 // stored -- keeps the round as its unit here.
 //
+// A full pair whose 512 records are live and strictly ascending -- every pair of the flagship, most pairs of a real sorted
+// VCF -- is "plain": one test on the raw loads sends it through specialisations of the unpack, the join and the per-record pass
+// that carry no liveness select, no order test, no repeated-position ladder and no walk of a run (plain_pair below).
+//
 // The device helpers are this file's own copies (namespace qm::cpair): qmvt_kernels.hip and qmvt_dev.h do not change.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,9 +68,11 @@ __device__ __forceinline__ int floor_to_int(float c) {
   return r;
 }
 // the main loop's packer: one LDS read per record; a record out of range is caught by the round's position-OR
+// (PLAIN: a record of a plain pair -- in range and single-base by the pair's test, so `live` is a constant)
+template <bool PLAIN>
 __device__ __forceinline__ void pack_record_fast(int p, uint32_t d, float q, uint32_t f4x4, float nbm1f, const uint32_t* flut,
                                                  uint32_t& key, uint32_t& inf) {
-  const bool live = ((uint32_t)p | (d << 24)) < (uint32_t)QM_POS_LIMIT_DEV;
+  const bool live = PLAIN || ((uint32_t)p | (d << 24)) < (uint32_t)QM_POS_LIMIT_DEV;
   key = ((uint32_t)p << 4) | (live ? d : 0u);
   const float c = fminf(fmaxf(q, -1.0f), nbm1f);   // NaN -> -1
   const uint32_t b1 = (uint32_t)(floor_to_int(c) + 1);
@@ -93,11 +99,12 @@ __device__ __forceinline__ void load_raw(const Cols& C, int idx, Raw4& R) {
   R.q = make_float4(vq.x, vq.y, vq.z, vq.w);
   R.f = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(C.flags + idx));
 }
+template <bool PLAIN>
 __device__ __forceinline__ void unpack_raw(const Raw4& R, float nbm1f, In4& X, const uint32_t* flut) {
-  pack_record_fast(R.p.x, R.d & 0xffu, R.q.x, (R.f << 2) & 0x3cu, nbm1f, flut, X.key[0], X.inf[0]);
-  pack_record_fast(R.p.y, (R.d >> 8) & 0xffu, R.q.y, (R.f >> 6) & 0x3cu, nbm1f, flut, X.key[1], X.inf[1]);
-  pack_record_fast(R.p.z, (R.d >> 16) & 0xffu, R.q.z, (R.f >> 14) & 0x3cu, nbm1f, flut, X.key[2], X.inf[2]);
-  pack_record_fast(R.p.w, R.d >> 24, R.q.w, (R.f >> 22) & 0x3cu, nbm1f, flut, X.key[3], X.inf[3]);
+  pack_record_fast<PLAIN>(R.p.x, R.d & 0xffu, R.q.x, (R.f << 2) & 0x3cu, nbm1f, flut, X.key[0], X.inf[0]);
+  pack_record_fast<PLAIN>(R.p.y, (R.d >> 8) & 0xffu, R.q.y, (R.f >> 6) & 0x3cu, nbm1f, flut, X.key[1], X.inf[1]);
+  pack_record_fast<PLAIN>(R.p.z, (R.d >> 16) & 0xffu, R.q.z, (R.f >> 14) & 0x3cu, nbm1f, flut, X.key[2], X.inf[2]);
+  pack_record_fast<PLAIN>(R.p.w, R.d >> 24, R.q.w, (R.f >> 22) & 0x3cu, nbm1f, flut, X.key[3], X.inf[3]);
   X.posor = (uint32_t)R.p.x | (uint32_t)R.p.y | (uint32_t)R.p.z | (uint32_t)R.p.w;
 }
 
@@ -213,7 +220,9 @@ __device__ __forceinline__ void stage_half(uint32_t* lds, In4& X, int half, int 
 // NREC = 512: the whole pair (records 0 .. nrec - 1 of it); NREC = 256: the half that starts at record `r0` (0 or 256), for
 // the round-by-round path of an oversize slice.  own_a: INT32_MIN when the segment owns the run at its first position, else
 // that position (the run started in an earlier segment, which owns its truth entries).
-template <int NREC>
+// PLAIN (a plain pair: strictly ascending, every record live, own_a == INT32_MIN): a truth key's position holds at most one
+// staged record, so the walk of the run is one straight-line trip.
+template <int NREC, bool PLAIN>
 __device__ __forceinline__ void join_staged(uint32_t* lds, const Slice& S, int r0, int nrec, int own_a, int lane) {
   if (S.m <= 0 || nrec <= 0) return;
   const int kb = L_RKEY + r0 + ((r0 >> 5) << 2);   // first staged key of the searched records
@@ -246,17 +255,28 @@ __device__ __forceinline__ void join_staged(uint32_t* lds, const Slice& S, int r
       s += r0;
       const int send = r0 + nrec;
       uint32_t mx = 0, rf = 0;
-      for (; s < send; ++s) {   // the run of records at this position
-        const uint32_t rkey = lds[rk(s)];
-        if ((rkey & ~15u) != kfloor) break;
-        if (rkey != kkey) continue;
-        const uint32_t inf = (lds[L_RINF + (s >> 1)] >> (16 * (s & 1))) & 0xffffu;
-        if ((inf & (I_LIVE | I_NOKEY)) != I_LIVE) continue;
-        atomicOr(&lds[L_HITS + (s >> 5)], 1u << (s & 31));
-        if ((int)kpos != own_a) {
-          const uint32_t b1 = inf & I_BIN1;
-          if ((inf & I_IDDOT) && b1 > mx) mx = b1;
-          rf |= (inf & I_PASS) ? 1u : 0u;
+      if constexpr (PLAIN) {   // the one record that can carry this key (no LDS word behind the staged keys is read)
+        if (s < send && lds[rk(s)] == kkey) {
+          const uint32_t inf = (lds[L_RINF + (s >> 1)] >> (16 * (s & 1))) & 0xffffu;
+          if ((inf & (I_LIVE | I_NOKEY)) == I_LIVE) {
+            atomicOr(&lds[L_HITS + (s >> 5)], 1u << (s & 31));
+            if (inf & I_IDDOT) mx = inf & I_BIN1;
+            rf = (inf & I_PASS) ? 1u : 0u;
+          }
+        }
+      } else {
+        for (; s < send; ++s) {   // the run of records at this position
+          const uint32_t rkey = lds[rk(s)];
+          if ((rkey & ~15u) != kfloor) break;
+          if (rkey != kkey) continue;
+          const uint32_t inf = (lds[L_RINF + (s >> 1)] >> (16 * (s & 1))) & 0xffffu;
+          if ((inf & (I_LIVE | I_NOKEY)) != I_LIVE) continue;
+          atomicOr(&lds[L_HITS + (s >> 5)], 1u << (s & 31));
+          if ((int)kpos != own_a) {
+            const uint32_t b1 = inf & I_BIN1;
+            if ((inf & I_IDDOT) && b1 > mx) mx = b1;
+            rf |= (inf & I_PASS) ? 1u : 0u;
+          }
         }
       }
       if (mx) atomicMax(&lds[L_SMAX + j], mx);
@@ -332,6 +352,9 @@ __device__ __forceinline__ uint32_t or_reduce8(uint32_t v) {
 
 // ---- phase C: per-record work on the packed registers of ONE round (a half of the pair) ---------------------------------------
 // hword: the half's first hit word; prev_last: position of the record before the round; mslot: the round's first mask word
+// PLAIN (a half of a plain pair): every position is in range and above its predecessor, so no order or range bit is set, no
+// record repeats its predecessor's position (no `cand`, no repeated_key) and the predecessor is never fetched
+template <bool PLAIN>
 __device__ __forceinline__ void classify_half(uint32_t* lds, const Cols& C, const In4& X, int hword, int rbase, int prev_last, int nb,
                                               int mslot, Acc& A, int lane) {
   const uint32_t hit = (lds[hword + (lane >> 3)] >> (4 * (lane & 7))) & 15u;
@@ -342,7 +365,7 @@ __device__ __forceinline__ void classify_half(uint32_t* lds, const Cols& C, cons
     anyinf |= X.inf[k];
   }
   const uint32_t pass = nib & 15u, iddot = (nib >> 4) & 15u, tpline = (nib >> 8) & 15u;
-  A.bad |= ((anyinf & I_BADPOS) | (X.posor >> 28)) ? 2u : 0u;
+  if (!PLAIN) A.bad |= ((anyinf & I_BADPOS) | (X.posor >> 28)) ? 2u : 0u;
   A.posor |= X.posor;
   const uint32_t tpkey = (hit & iddot) | tpline;
   const uint32_t tp = pass & tpkey;
@@ -359,15 +382,20 @@ __device__ __forceinline__ void classify_half(uint32_t* lds, const Cols& C, cons
       lds[L_MASK + 32 * MASK_TILES + mslot + (lane >> 3)] = wt;
     }
   }
-  int pp = __shfl_up((int)(X.key[3] >> 4), 1);
-  if (lane == 0) pp = prev_last;
+  int pp = 0;
+  if (!PLAIN) {
+    pp = __shfl_up((int)(X.key[3] >> 4), 1);
+    if (lane == 0) pp = prev_last;
+  }
   const int i0 = rbase + lane * 4;
   uint32_t cand = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int p = (int)(X.key[k] >> 4);
-    A.bad |= (p < pp) ? 1u : 0u;
-    cand |= ((p == pp) ? 1u : 0u) << k;
+    if (!PLAIN) {
+      A.bad |= (p < pp) ? 1u : 0u;
+      cand |= ((p == pp) ? 1u : 0u) << k;
+    }
     {
       const uint32_t b1 = X.inf[k] & I_BIN1;
       const uint32_t notp = ((~tpkey) >> k) & 1u;
@@ -422,13 +450,33 @@ __device__ __forceinline__ void oversize_round(uint32_t* lds, const Cols& C, con
     S.m = (rhi - c0) < K1_SLICE ? (rhi - c0) : K1_SLICE;
     stage_slice(lds, tr, c0, S, lane);
     __syncthreads();
-    join_staged<256>(lds, S, r0, rend - rbase, r_own_a, lane);
+    join_staged<256, false>(lds, S, r0, rend - rbase, r_own_a, lane);
     if (RB.nextp == RB.b && !(r_started && RB.a == RB.b)) continue_run(C, lds, S, rend, vn, RB.b, nb, lane);
     __syncthreads();
     acc_tpr += flush_slice(lds, S, lane);
     __syncthreads();
   }
   S.m = 0;
+}
+
+// ---- the plain pair ---------------------------------------------------------------------------------------------
+// Decided once per FULL pair on the raw loads, one ballot: each of the 512 positions is above its predecessor (inside a lane
+// the record in front of it, across lanes the previous lane's fourth record, for lane 0 the record before the half), no position
+// has a bit at or above 28 (which also rejects a negative one), no allele byte is ANIB_NONE.  Such a pair holds none of what the
+// general path tests per record -- a dead or out-of-range record, a descent, a repeated position -- and runs through the PLAIN
+// specialisations of the unpack, the join and the per-record pass, in which those conditions are compile-time constants.
+#ifndef QM_PAIR_PLAIN
+#define QM_PAIR_PLAIN 1   // 0: the test is constant false and the kernel is the general path alone (the A/B arm)
+#endif
+__device__ __forceinline__ bool plain_pair(const Raw4& N0, const Raw4& N1, int prev_last, int lane) {
+  int pp0 = __shfl_up(N0.p.w, 1), pp1 = __shfl_up(N1.p.w, 1);
+  const int last0 = __builtin_amdgcn_readlane(N0.p.w, 63);
+  if (lane == 0) { pp0 = prev_last; pp1 = last0; }
+  const bool asc = (N0.p.x > pp0) & (N0.p.y > N0.p.x) & (N0.p.z > N0.p.y) & (N0.p.w > N0.p.z) &
+                   (N1.p.x > pp1) & (N1.p.y > N1.p.x) & (N1.p.z > N1.p.y) & (N1.p.w > N1.p.z);
+  const uint32_t por = (uint32_t)(N0.p.x | N0.p.y | N0.p.z | N0.p.w | N1.p.x | N1.p.y | N1.p.z | N1.p.w);
+  const bool ok = asc & (((por & 0xf0000000u) | ((N0.d | N1.d) & 0xf0f0f0f0u)) == 0u);
+  return ballot64(!ok) == 0ull;
 }
 
 #ifndef QM_PAIR_WAVES_PER_EU
@@ -524,9 +572,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QM_PAIR_WAVE
       const int hbase = pbase + 256;                           // the second half's first record
       const int pend = pbase + PAIR < te ? pbase + PAIR : te;
       const bool two = hbase < te;                             // the second half holds records (wave-uniform)
+      // wave-uniform; a tile that starts inside a run of one position (own_a set) stays on the general path, which knows own_a
+      const bool plain = QM_PAIR_PLAIN && !oversize && !started_before && pbase + PAIR <= te && plain_pair(N0, N1, prev_last, lane);
       In4 X0, X1;
-      unpack_raw(N0, nbm1f, X0, lds + L_FLUT);
-      unpack_raw(N1, nbm1f, X1, lds + L_FLUT);                 // (a half behind the tile's end: staged as padding, never classified)
+      if (plain) {
+        unpack_raw<true>(N0, nbm1f, X0, lds + L_FLUT);
+        unpack_raw<true>(N1, nbm1f, X1, lds + L_FLUT);
+      } else {
+        unpack_raw<false>(N0, nbm1f, X0, lds + L_FLUT);
+        unpack_raw<false>(N1, nbm1f, X1, lds + L_FLUT);        // (a half behind the tile's end: staged as padding, never classified)
+      }
       // the next tile's slice is fetched as a side chain spread over this tile's pairs, so none of its three dependent
       // global round trips (bounds -> position index -> keys) is exposed: bounds in front of the loop, the index behind the first
       // pair's join, the keys here in the second pair
@@ -545,16 +600,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QM_PAIR_WAVE
       stage_half(lds, X1, 1, hbase + lane * 4, te, lane);
       if (lane < PAIR / 32) lds[L_HITS + lane] = 0;
       __syncthreads();
-      if (!oversize) {
-        join_staged<PAIR>(lds, S, 0, pend - pbase, own_a, lane);
+      if (plain) {
+        join_staged<PAIR, true>(lds, S, 0, PAIR, INT32_MIN, lane);
+      } else if (!oversize) {
+        join_staged<PAIR, false>(lds, S, 0, pend - pbase, own_a, lane);
       } else {
         oversize_round(lds, C, tr, X0, S, 0, pbase, two ? hbase : pend, vn, nb, A, acc_tpr, lane);
         if (two) oversize_round(lds, C, tr, X1, S, 256, hbase, pend, vn, nb, A, acc_tpr, lane);
       }
       if (has_next_tile && pr == 0) slice_range(tr, NB.a, NB.b, nlo, nhi);
       __syncthreads();
-      classify_half(lds, C, X0, L_HITS, pbase, prev_last, nb, mtile + 16 * pr, A, lane);
-      if (two) classify_half(lds, C, X1, L_HITS + 8, hbase, (int)(lds[rk(255)] >> 4), nb, mtile + 16 * pr + 8, A, lane);
+      if (plain) {   // both halves hold records; no predecessor is looked at
+        classify_half<true>(lds, C, X0, L_HITS, pbase, 0, nb, mtile + 16 * pr, A, lane);
+        classify_half<true>(lds, C, X1, L_HITS + 8, hbase, 0, nb, mtile + 16 * pr + 8, A, lane);
+      } else {
+        classify_half<false>(lds, C, X0, L_HITS, pbase, prev_last, nb, mtile + 16 * pr, A, lane);
+        if (two) classify_half<false>(lds, C, X1, L_HITS + 8, hbase, (int)(lds[rk(255)] >> 4), nb, mtile + 16 * pr + 8, A, lane);
+      }
       prev_last = (int)(lds[rk(PAIR - 1)] >> 4);
       __syncthreads();
     }
