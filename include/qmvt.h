@@ -823,6 +823,34 @@ int qm_batch_ladder(qm_batch* b, unsigned what /*0, QM_LADDER_SUBSETS, QM_LADDER
 int qm_batch_get_ladder(qm_batch* b, uint64_t* rec /*[n_vcf][QM_LADDER_COLS]*/, uint64_t* tru /*[n_vcf][QM_LADDER_COLS]*/);
 int qm_batch_get_laddered(qm_batch* b, int vcf, uint8_t* mask /*[n]*/, uint8_t* entry_mask /*[entries]*/);
 int qm_batch_ladder_timings(qm_batch* b, float* ms2);
+/* The match ladder per variant type and size: the rows of the latest qm_batch_types crossed with the 18
+ * columns of the latest qm_batch_ladder.  It reads the row byte per record that qm_batch_types(.., QM_TYPE_COLUMNS) left and
+ * the mask byte per record and per (VCF, truth entry) that qm_batch_ladder(.., QM_LADDER_COLUMNS) left; nothing is normalised,
+ * atomised, replayed or typed by new rules.  Build-defined, parity unpinned, as its two producers are.
+ * Rows: those of the latest qm_batch_types call, n_rows = 5 n_bins + 4 (at most QM_TYPE_MAX_ROWS), with its edges, its shape
+ *   table and its four off-grid rows.  A record's row is its row byte: records are typed AS SPELLED, so a respelled deletion
+ *   counts in the row of its spelling, whatever normal form rescued it.  A truth entry's row is the row of its (ref, alt) codes
+ *   without QM_F_NOKEY, as in tru of qm_batch_get_types: truth entries never land in QM_TYPE_X_NOKEY.
+ * Columns: the ladder's (QM_LADDER_KEPT, QM_LADDER_TP, QM_LADDER_CELL0 + m).
+ * rec[v][row][QM_LADDER_COLS], over the records of VCF v with that row byte whose mask byte is not 0 (the kept ones): all of
+ *   them; those with QM_LADDER_M_S; cell m = those without S whose low four bits are m (cell 0: the row's final FP).
+ * tru[v][row][QM_LADDER_COLS], over the entries of v's truth set in that row: all of them; those with S; the 16 cells over
+ *   the entries without S (cell 0: the row's final FN).  A VCF without a genome in the normalisation or the haplotype call takes
+ *   part with the bits it has.
+ * Summed over the rows, both are rec and tru of qm_batch_get_ladder; columns 0 and 1 of every row are the row's pair of
+ *   qm_batch_get_types (its "found" and the ladder's S are one rule); in every row the 16 cells sum to column 0 - column 1.
+ *   The tier order and the cumulative TP, FP and FN after every tier stay a convention of the host (quasimodo_amd.ladder).
+ * qm_batch_ladder_types: asynchronous on `stream` (NULL = the context's own), ordered behind its producers on whatever stream.
+ *   QM_E_STATE for a single-base batch, if a truth set was released, and if the batch has not finished, since its latest run,
+ *   qm_batch_types(.., QM_TYPE_COLUMNS) or qm_batch_ladder(.., QM_LADDER_COLUMNS): the first one missing, in that order, is
+ *   named.  A new call of either, or of any of the ladder's four producers, waits for this pass still in flight and forgets its
+ *   rows.
+ * qm_batch_get_ladder_types: waits for the pass, then copies (any pointer may be NULL); n_rows_out: the rows of a VCF's block.
+ * qm_batch_ladder_types_timings (qm_batch_set_timing on): milliseconds between HIP events of k_ltype_records and k_ltype_truth. */
+int qm_batch_ladder_types(qm_batch* b, void* stream);
+int qm_batch_get_ladder_types(qm_batch* b, uint64_t* rec /*[n_vcf][n_rows][QM_LADDER_COLS]*/, uint64_t* tru /*[n_vcf][n_rows][QM_LADDER_COLS]*/,
+                              int* n_rows_out);
+int qm_batch_ladder_types_timings(qm_batch* b, float* ms2);
 int qm_truth_sites(qm_ctx* ctx, int truth_id, int genome_id, int gap, int32_t* first_entry, int32_t* lo, int32_t* hi, int64_t capacity,
                    int64_t* n_out);
 /* Where the VCFs that the last qm_batch_finish found out of order went (a sorted batch reports zeros).  The bucket path
@@ -1334,6 +1362,28 @@ typedef struct qm_ladder_args {
 int qm_extract_files_ladder(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                             qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
                             void* global_dev, const qm_ladder_args* ladder);
+
+/* qm_extract_files_ex plus the match ladder per variant type and size over its batch; mode must be
+ * QM_BATCH_ALLELES (QM_E_STATE otherwise).  The call runs the four rescues with their columns as qm_extract_files_ladder does,
+ * then qm_batch_types with its row bytes (the shape table from the call's own dictionary, as in qm_extract_files_types) and
+ * qm_batch_ladder with its mask bytes, and hands out none of their rows or files.  Mixed-sample jobs with want[j] != 0 get
+ * rec[j][n_rows][QM_LADDER_COLS] and tru[j][n_rows][QM_LADDER_COLS] of qm_batch_get_ladder_types (n_rows = 5 n_bins + 4;
+ * genome_id[j] as in qm_ladder_args); the others, pure-strain jobs among them, get zero rows.  The VCF outputs, stats and roc are
+ * those of qm_extract_files_ex.  Combines with none of the other opt-in views. */
+typedef struct qm_ladder_types_args {
+  const int32_t* genome_id;         /* [n_jobs], -1 = no genome */
+  int32_t gap;
+  int32_t subsets;
+  const uint8_t* want;              /* [n_jobs] */
+  const int32_t* edges;             /* [n_bins] */
+  int32_t n_bins;
+  int32_t reserved;
+  uint64_t* rec;                    /* [n_jobs][5 n_bins + 4][QM_LADDER_COLS] */
+  uint64_t* tru;                    /* [n_jobs][5 n_bins + 4][QM_LADDER_COLS] */
+} qm_ladder_types_args;
+int qm_extract_files_ladder_types(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                  qm_file_stats* stats, uint64_t* roc, double* phase_seconds, const int32_t* truth_slot, int n_slots,
+                                  void* global_dev, const qm_ladder_types_args* ladder_types);
 
 /* qm_extract_files_ex plus the bootstrap pass over its batch.  Jobs with want[j] != 0 get their rows:
  * cnt[j][n_win + 2][4] and rep[j][n_rep][4] of qm_batch_get_boot; the others get zero rows.  Single-base mode: truth hits and

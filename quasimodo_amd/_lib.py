@@ -111,6 +111,7 @@ EXPORTS = (
     "qm_extract_files_hapsubsets",
     "qm_batch_rescue_roc", "qm_batch_get_rescue_roc", "qm_batch_rescue_roc_timings", "qm_extract_files_rescue_roc",
     "qm_batch_ladder", "qm_batch_get_ladder", "qm_batch_get_laddered", "qm_batch_ladder_timings", "qm_extract_files_ladder",
+    "qm_batch_ladder_types", "qm_batch_get_ladder_types", "qm_batch_ladder_types_timings", "qm_extract_files_ladder_types",
 )
 
 
@@ -200,6 +201,12 @@ class LadderArgs(C.Structure):
                 ("tru", C.c_void_p), ("ladder_out", C.POINTER(C.c_char_p))]
 
 
+class LadderTypesArgs(C.Structure):
+    """include/qmvt.h qm_ladder_types_args"""
+    _fields_ = [("genome_id", C.c_void_p), ("gap", C.c_int32), ("subsets", C.c_int32), ("want", C.c_void_p), ("edges", C.c_void_p),
+                ("n_bins", C.c_int32), ("reserved", C.c_int32), ("rec", C.c_void_p), ("tru", C.c_void_p)]
+
+
 class HaplotypesArgs(C.Structure):
     """include/qmvt.h qm_haplotypes_args"""
     _fields_ = [("genome_id", C.c_void_p), ("gap", C.c_int32), ("reserved", C.c_int32), ("rec", C.c_void_p), ("tru", C.c_void_p),
@@ -236,7 +243,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_walk.h", "qmvt_classify_pair.hip", "qmvt_classify_pair.h", "qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_haplo.hip", "qmvt_haplo.h", "qmvt_rroc.hip", "qmvt_rroc.h", "qmvt_ladder.hip", "qmvt_ladder.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_walk.h", "qmvt_classify_pair.hip", "qmvt_classify_pair.h", "qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_haplo.hip", "qmvt_haplo.h", "qmvt_rroc.hip", "qmvt_rroc.h", "qmvt_ladder.hip", "qmvt_ladder.h", "qmvt_ltypes.hip", "qmvt_ltypes.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):
@@ -483,6 +490,9 @@ def lib():
     L.qm_batch_get_ladder.argtypes = [vp, vp, vp]
     L.qm_batch_get_laddered.argtypes = [vp, i32, vp, vp]
     L.qm_batch_ladder_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    L.qm_batch_ladder_types.argtypes = [vp, vp]
+    L.qm_batch_get_ladder_types.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
+    L.qm_batch_ladder_types_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.qm_extract_files_haplotypes.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                               C.POINTER(HaplotypesArgs)]
     L.qm_truth_sites.argtypes = [vp, i32, i32, i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
@@ -492,6 +502,8 @@ def lib():
                                               C.POINTER(RescueRocArgs)]
     L.qm_extract_files_ladder.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                           C.POINTER(LadderArgs)]
+    L.qm_extract_files_ladder_types.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
+                                                C.POINTER(LadderTypesArgs)]
     L.qm_extract_files_types.argtypes = [vp, i32, C.POINTER(FileJob), i32, C.c_uint, i32, C.POINTER(FileStats), vp, C.POINTER(C.c_double), vp, i32, vp,
                                          C.POINTER(TypesArgs)]
     _lib = L

@@ -38,6 +38,7 @@
 #include "qmvt_haplo.h"
 #include "qmvt_rroc.h"
 #include "qmvt_ladder.h"
+#include "qmvt_ltypes.h"
 
 using namespace qm;
 
@@ -652,7 +653,7 @@ enum class Path : uint8_t { Radix, OneLevel, TwoLevel, Partitions, Wide };
 
 // ---- the passes over a finished batch (include/qmvt.h at qm_batch_run) ----
 enum PassId { P_MOTIFS, P_AFP, P_TRUTH, P_STRATA, P_BOOT, P_VOTES, P_NEARMISS, P_SURFACE, P_CONTEXT, P_NORM, P_ATOM, P_TYPES, P_HAPLO,
-              P_HAPSUB, P_RROC, P_LADDER, N_PASSES };
+              P_HAPSUB, P_RROC, P_LADDER, P_LTYPES, N_PASSES };
 constexpr int PASS_MAX_MARKS = 6;   // qm_batch_haplotypes'
 // What a batch keeps of every pass, qm_batch::pass[id].  Both kinds of event are created at first use: a batch that never ran a
 // pass holds none, and whatever walks the passes (wait_passes, the reset in qm_batch_run, batch_free) makes no HIP call for it.
@@ -674,6 +675,7 @@ static const PassInfo PASSES[N_PASSES] = {
     {"qm_batch_normalize", 4, "run"},  {"qm_batch_atomize", 4, "run"},    {"qm_batch_types", 3, "run"},
     {"qm_batch_haplotypes", 6, "run"}, {"qm_batch_hapsubsets", 2, "qm_batch_haplotypes"},
     {"qm_batch_rescue_roc", 5, "run of its producers"},                   {"qm_batch_ladder", 3, "run of its producers"},
+    {"qm_batch_ladder_types", 3, "run of its producers"},
 };
 // (P_HAPLO: qm_batch_haplotypes waits on the host for its own stream at its readback, so only its last three kernels can be in
 // flight behind the call; no test holds them up, the ordering effect of that row is not pinned by any -- tests/test_gpu_haplo_streams.py)
@@ -695,6 +697,13 @@ constexpr PassRead READS[] = {
     {P_HAPSUB, P_HAPLO, ~0u, ~0u, "qm_batch_haplotypes"},   // (refused by pass_ran and a sentence of the search's own)
     {P_LADDER, P_HAPLO, QM_HAP_COLUMNS, ~0u, "qm_batch_haplotypes(.., QM_HAP_COLUMNS)"},
     {P_LADDER, P_HAPSUB, QM_HAPSUB_COLUMNS, ~0u, "qm_batch_hapsubsets(QM_HAPSUB_COLUMNS)"},
+    {P_LTYPES, P_TYPES, QM_TYPE_COLUMNS, ~0u, "qm_batch_types(.., QM_TYPE_COLUMNS)"},
+    {P_LTYPES, P_LADDER, QM_LADDER_COLUMNS, ~0u, "qm_batch_ladder(.., QM_LADDER_COLUMNS)"},
+    // (never asked for nor waited for by qm_batch_ladder_types: its ladder stands behind them.  The rows say what a rescue called
+    // again does: it forgets the ladder it fed, and with it the cross of that ladder's mask bytes -- forgetting is per edge, not
+    // passed on from reader to reader)
+    {P_LTYPES, P_NORM, ~0u, ~0u, "qm_batch_normalize"},     {P_LTYPES, P_ATOM, ~0u, ~0u, "qm_batch_atomize"},
+    {P_LTYPES, P_HAPLO, ~0u, ~0u, "qm_batch_haplotypes"},   {P_LTYPES, P_HAPSUB, ~0u, ~0u, "qm_batch_hapsubsets"},
 };
 // The row of an edge, -1 without one: a pass that refuses for, or waits for, a pass it is not said to read does not compile.
 constexpr int read_row(int reader, int producer) {
@@ -924,6 +933,8 @@ struct qm_batch {
   DevBuf<uint64_t> ty_rec, ty_tru;
   DevBuf<uint8_t> ty_row;             // [n_pad]
   int32_t ty_rows = 0;                // n_rows of the latest qm_batch_types
+  TypeBins ty_bins = {};              // ... its size bins and the rows of its shape table in ty_shapes: what types a truth entry
+  int64_t ty_nshapes = 0;             //     again (qm_batch_ladder_types)
   // qm_batch_haplotypes (lazy): the site tables of the (truth set, genome) pairs the VCFs name in one pool, the
   // per-VCF descriptors and bitmaps, [n_vcf][QM_HAP_R_COLS] / [n_vcf][QM_HAP_T_COLS] counts, a class byte and a site index per
   // record, the open lines of every (VCF, open site) pair and, on request, a class byte per (VCF, truth entry)
@@ -957,6 +968,10 @@ struct qm_batch {
   DevBuf<uint64_t> ld_out;
   DevBuf<uint8_t> ld_mask, ld_emask;   // [n_pad]; the entries of every VCF's truth set, VCF after VCF
   std::vector<int64_t> ld_eoff;        // [n_vcf + 1] the VCF's entries in ld_emask
+  // qm_batch_ladder_types (lazy): [n_vcf][n_rows][QM_LADDER_COLS] counts of records and of truth entries one
+  // behind the other; the per-VCF descriptors it reads are the ones its two producers left (ty_vcfs, ld_vcfs)
+  DevBuf<uint64_t> lt_out;
+  int32_t lt_rows = 0;                 // n_rows of the latest qm_batch_ladder_types
 };
 
 static bool memo_on() {   // read at every run / finish: bench.py times a batch with and without its memory in one process
@@ -3406,6 +3421,67 @@ extern "C" int qm_batch_get_laddered(qm_batch* b, int v, uint8_t* mask, uint8_t*
 extern "C" int qm_batch_ladder_timings(qm_batch* b, float* ms2) {
   return pass_timings(b, P_LADDER, "qm_batch_ladder_timings", ms2);
 }
+// ---- the match ladder per variant type and size ----
+extern "C" int qm_batch_ladder_types(qm_batch* b, void* stream) {
+  NEED_FINISHED(b, "qm_batch_ladder_types");
+  if (!b->ext) return fail(QM_E_STATE, "qm_batch_ladder_types: a single-base batch has neither types nor rescue passes to cross (create the batch with QM_BATCH_ALLELES)");
+  if (pass_needs<P_LTYPES, P_TYPES>(b) != QM_OK) return QM_E_STATE;
+  if (pass_needs<P_LTYPES, P_LADDER>(b) != QM_OK) return QM_E_STATE;
+  qm_ctx* c = b->ctx;
+  const size_t nv = (size_t)b->n_vcf;
+  int rc = truths_live(b, "qm_batch_ladder_types");
+  if (rc != QM_OK) return rc;
+  int64_t max_entries = 0;
+  for (size_t v = 0; v < nv; ++v) max_entries = std::max(max_entries, c->truths[(size_t)b->L.vcfs[v].truth].xn);
+  OPEN_PASS(b, P_LTYPES, stream, st);
+  b->pass[P_LTYPES].made = 0;   // from here on the outputs are rewritten
+  const TypeBins& B = b->ty_bins;
+  const size_t block = nv * (size_t)B.n_rows * LADDER_COLS, out_words = std::max<size_t>(2 * block, 1);
+  rc = b->lt_out.grow((int64_t)out_words, &b->dev_bytes);
+  if (rc != QM_OK) return rc;
+  HIPCHK(pass_marks(b, P_LTYPES));
+  HIPCHK(pass_wait<P_LTYPES, P_TYPES>(b, st));   // the producers may have run on other streams
+  HIPCHK(pass_wait<P_LTYPES, P_LADDER>(b, st));
+  HIPCHK(hipMemsetAsync(b->lt_out, 0, out_words * 8, st));
+  HIPCHK(pass_mark(b, P_LTYPES, 0, st));
+  LtypeRecParams P;
+  memset(&P, 0, sizeof P);
+  P.spans = b->d_spans; P.row = b->ty_row; P.mask = b->ld_mask;
+  P.rec = b->lt_out;
+  P.n_spans = (int32_t)b->L.spans.size();
+  P.n_rows = B.n_rows;
+  launch_ltype_records(P, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(pass_mark(b, P_LTYPES, 1, st));
+  LtypeTruthParams Q;
+  memset(&Q, 0, sizeof Q);
+  Q.tvcfs = b->ty_vcfs; Q.lvcfs = b->ld_vcfs; Q.emask = b->ld_emask;
+  Q.tru = b->lt_out + block;
+  Q.bins = B;
+  if (b->ty_nshapes) {
+    const uint32_t* d = b->ty_shapes;
+    const size_t ns = (size_t)b->ty_nshapes;
+    Q.shapes.len = reinterpret_cast<const int32_t*>(d); Q.shapes.head = d + ns; Q.shapes.tail = d + 2 * ns; Q.shapes.n = b->ty_nshapes;
+  }
+  launch_ltype_truth(Q, (int)nv, max_entries, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(pass_mark(b, P_LTYPES, 2, st));
+  HIPCHK(pass_done(b, P_LTYPES, st, 1u));
+  b->lt_rows = B.n_rows;
+  return QM_OK;
+}
+extern "C" int qm_batch_get_ladder_types(qm_batch* b, uint64_t* rec, uint64_t* tru, int* n_rows_out) {
+  NEED_PASS(b, P_LTYPES, "qm_batch_get_ladder_types");
+  HIPCHK(pass_result(b, P_LTYPES));
+  const size_t block = (size_t)b->n_vcf * (size_t)b->lt_rows * LADDER_COLS;
+  if (rec && block) HIPCHK(hipMemcpy(rec, b->lt_out, block * 8, hipMemcpyDeviceToHost));
+  if (tru && block) HIPCHK(hipMemcpy(tru, b->lt_out + block, block * 8, hipMemcpyDeviceToHost));
+  if (n_rows_out) *n_rows_out = b->lt_rows;
+  return QM_OK;
+}
+extern "C" int qm_batch_ladder_types_timings(qm_batch* b, float* ms2) {
+  return pass_timings(b, P_LTYPES, "qm_batch_ladder_types_timings", ms2);
+}
 // ---- TP, FP and FN by variant type and size ----
 extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, const int32_t* len, const uint32_t* head, const uint32_t* tail,
                               int64_t n_shapes, unsigned what, void* stream) {
@@ -3493,6 +3569,8 @@ extern "C" int qm_batch_types(qm_batch* b, const int32_t* edges, int n_bins, con
   HIPCHK(pass_mark(b, P_TYPES, 2, st));
   HIPCHK(pass_done(b, P_TYPES, st, 1u | what));
   b->ty_rows = B.n_rows;
+  b->ty_bins = B;
+  b->ty_nshapes = n_shapes;
   return QM_OK;
 }
 extern "C" int qm_batch_get_types(qm_batch* b, uint64_t* rec, uint64_t* tru) {

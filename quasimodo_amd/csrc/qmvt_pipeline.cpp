@@ -301,6 +301,7 @@ struct Passes {
   const qm_surface_args* sf = nullptr; const qm_context_args* cx = nullptr; const qm_normalize_args* nz = nullptr;
   const qm_atomize_args* at = nullptr; const qm_types_args* ty = nullptr; const qm_haplotypes_args* hp = nullptr;
   const qm_hapsub_args* hs = nullptr; const qm_rescue_roc_args* rr = nullptr; const qm_ladder_args* ld = nullptr;
+  const qm_ladder_types_args* lt = nullptr;
   bool has_genome(int j) const { return genome_id && genome_id[j] >= 0; }
   bool wants_profile(int j) const { return pa && pa->want[j] != 0; }
   bool wants_strata(int j) const { return sa && sa->want[j] != 0; }
@@ -961,6 +962,36 @@ int ladder_pass(const PassCtx& c, const qm_ladder_args* la, std::string& err) {
   return QM_OK;
 }
 
+// The match ladder per variant type and size: the four rescues with their columns, the type pass with its row
+// bytes (the shape table from the call's dictionary, so no long allele is without a row) and the ladder with its mask bytes, run
+// here as the batch calls they are -- none of their rows or files is handed out --, then the cross; the blocks of every wanted
+// mixed-sample job (a pure-strain job has no truth set to be measured against: its rows stay zero)
+int ltypes_pass(const PassCtx& c, const qm_ladder_types_args* lt, std::string& err) {
+  if (!lt) return QM_OK;
+  auto want = [&](int j) { return lt->want[j] != 0 && !c.jobs[j].pure; };
+  if (!c.any(want)) return QM_OK;
+  std::vector<int32_t> gid(c.nv, -1);
+  for (int j = 0; j < c.n_jobs; ++j) if (want(j)) gid[(size_t)c.J[(size_t)j].batch_v] = lt->genome_id[j];
+  const int64_t ns = c.dict ? qm_dict_size(c.dict) : 0;
+  std::vector<int32_t> len((size_t)ns);
+  std::vector<uint32_t> head((size_t)ns), tail((size_t)ns);
+  const int64_t got = ns ? qm_dict_shapes(c.dict, 0, ns, len.data(), head.data(), tail.data()) : 0;
+  const size_t w = (size_t)(5 * lt->n_bins + 4) * QM_LADDER_COLS;
+  std::vector<uint64_t> rec(c.nv * w), tru(c.nv * w);
+  int rc = qm_batch_normalize(c.batch, gid.data(), QM_NORM_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_atomize(c.batch, QM_ATOM_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_haplotypes(c.batch, gid.data(), lt->gap, QM_HAP_COLUMNS, nullptr);
+  if (rc == QM_OK && lt->subsets) rc = qm_batch_hapsubsets(c.batch, QM_HAPSUB_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_types(c.batch, lt->edges, lt->n_bins, len.data(), head.data(), tail.data(), got, QM_TYPE_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_ladder(c.batch, (lt->subsets ? QM_LADDER_SUBSETS : 0u) | QM_LADDER_COLUMNS, nullptr);
+  if (rc == QM_OK) rc = qm_batch_ladder_types(c.batch, nullptr);
+  if (rc == QM_OK) rc = qm_batch_get_ladder_types(c.batch, rec.data(), tru.data(), nullptr);
+  if (rc != QM_OK) return c.lib(rc, err);
+  c.scatter_rows(lt->rec, rec, w, want);
+  c.scatter_rows(lt->tru, tru, w, want);
+  return QM_OK;
+}
+
 // ---- clusters of records matched by replayed haplotype ----
 struct HpColumns { std::vector<uint8_t> cls, ecls; std::vector<int32_t> site; };
 struct HpSites { std::vector<int32_t> first, lo, hi; };
@@ -1474,6 +1505,31 @@ extern "C" int qm_extract_files_ladder(qm_ctx* ctx, int n_jobs, const qm_file_jo
   return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
 }
 
+// the match ladder per variant type and size behind the worker
+extern "C" int qm_extract_files_ladder_types(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
+                                             qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
+                                             int n_slots, void* global_dev, const qm_ladder_types_args* ladder_types) {
+  const qm_ladder_types_args* lt = ladder_types;
+  if (!lt || !lt->edges || (n_jobs > 0 && (!lt->genome_id || !lt->want || !lt->rec || !lt->tru)))
+    return fail(QM_E_INVAL, "qm_extract_files_ladder_types: NULL arguments");
+  if (!(mode & QM_BATCH_ALLELES))
+    return fail(QM_E_STATE, "qm_extract_files_ladder_types: the types and the rescue passes it crosses read indels and MNPs, which only the allele-extended mode (QM_BATCH_ALLELES) reads");
+  if (lt->gap < 0 || lt->gap > QM_HAP_MAX_GAP)
+    return fail(QM_E_INVAL, "qm_extract_files_ladder_types: gap " + std::to_string(lt->gap) + " (0 to " + std::to_string(QM_HAP_MAX_GAP) + ")");
+  if (lt->n_bins < 1 || lt->n_bins > QM_TYPE_MAX_BINS)
+    return fail(QM_E_INVAL, "qm_extract_files_ladder_types: " + std::to_string(lt->n_bins) + " size bins (1 to " + std::to_string(QM_TYPE_MAX_BINS) + ")");
+  for (int i = 0; i < lt->n_bins; ++i)
+    if (i == 0 ? lt->edges[0] != 1 : lt->edges[i] <= lt->edges[i - 1])
+      return fail(QM_E_INVAL, "qm_extract_files_ladder_types: the size edges ascend from 1 (edge " + std::to_string(i) + " is " + std::to_string(lt->edges[i]) + ")");
+  if (n_jobs > 0) {
+    const size_t w = (size_t)(5 * lt->n_bins + 4) * QM_LADDER_COLS;
+    memset(lt->rec, 0, sizeof(uint64_t) * w * (size_t)n_jobs);
+    memset(lt->tru, 0, sizeof(uint64_t) * w * (size_t)n_jobs);
+  }
+  Passes P; P.lt = lt;
+  return extract_files(ctx, n_jobs, jobs, n_bins, mode, strict, stats, roc_out, phase_seconds, truth_slot, n_slots, global_dev, P);
+}
+
 // the bootstrap pass behind the worker
 extern "C" int qm_extract_files_boot(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n_bins, unsigned mode, int strict,
                                      qm_file_stats* stats, uint64_t* roc_out, double* phase_seconds, const int32_t* truth_slot,
@@ -1836,6 +1892,7 @@ static int extract_files(qm_ctx* ctx, int n_jobs, const qm_file_job* jobs, int n
       if (rc == QM_OK) rc = hapsub_pass(pc, P.hs, err);
       if (rc == QM_OK) rc = rroc_pass(pc, P.rr, n_bins, err);
       if (rc == QM_OK) rc = ladder_pass(pc, P.ld, err);
+      if (rc == QM_OK) rc = ltypes_pass(pc, P.lt, err);
       if (rc == QM_OK) rc = surface_pass(pc, P.sf, err);
     }
     add_ph(4, now() - t0, trace ? cpu_now() - c0 : 0.0);

@@ -268,7 +268,7 @@ class Engine:
 
     def extract_files(self, file_jobs, n_bins=256, alleles=False, strict=True, truth_slots=None, n_slots=0, global_dev=None, genomes=None,
                       truthside=None, profile=None, strata=None, boot=None, votes=None, nearmiss=None, surface=None, context=None, normalize=None,
-                      atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None, ladder=None):
+                      atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None, ladder=None, ladder_types=None):
         """qm_extract_files(_ex): files in, files out, everything between in the library (host threads + ONE engine batch).
         file_jobs: list of dicts vcf / truth / mode ("hcmv" | "custom") / pure / filtered / tp / fp.
         truth_slots / n_slots / global_dev (device pointer, int): one rank of a multi-GPU run -- the per-truth-file sums of
@@ -325,6 +325,11 @@ class Engine:
         "out": [path or None per job]} -- qm_extract_files_ladder (alleles=True only), in place of normalize,
         atomize, haplo and hapsub, which it runs itself: wanted mixed-sample rows gain `ladder_rec` and `ladder_tru` ([18] uint64,
         columns ladder.COLS / ladder.T_COLS); the ladder files are written.
+        ladder_types: {"genomes": [genome_load id or None / -1 per job], "want": [0/1 per job], "gap": None or 0 .. 32, "subsets":
+        True, "edges": None or the size edges} -- qm_extract_files_ladder_types (alleles=True only), in place of
+        ladder and vartype, which it runs itself behind the four rescues: wanted mixed-sample rows gain `ladder_types_rec` and
+        `ladder_types_tru` ([n_rows][18] uint64: rows vartype.row_names(edges), columns ladder.COLS / ladder.T_COLS) and
+        `ladder_types_edges`.
         Which of these may share a call: quasimodo_amd.passes (ValueError otherwise).
         Returns (list of per-VCF dicts: scalars by name + n_lines, genomediff, header_kept, host_decided, roc; phase seconds)."""
         from .passes import check_alleles, check_shared_call
@@ -334,7 +339,7 @@ class Engine:
             raise ValueError("genomes: %d entries for %d jobs" % (gids.shape[0], n))
         if gids is not None and not (gids >= 0).any():
             gids = None
-        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface, "rescueroc": rescue_roc, "ladder": ladder}
+        specs = {"motifs": gids, "truthside": truthside, "profile": profile, "strata": strata, "boot": boot, "votes": votes, "nearmiss": nearmiss, "context": context, "normalize": normalize, "atomize": atomize, "haplo": haplo, "hapsub": hapsub, "vartype": vartype, "surface": surface, "rescueroc": rescue_roc, "ladder": ladder, "laddertypes": ladder_types}
         requested = {name for name, spec in specs.items() if spec is not None}
         check_shared_call(requested)
         check_alleles(requested, alleles)
@@ -467,6 +472,24 @@ class Engine:
         args.keep = (lgid, lwant, out_arr)   # (read during the call; the other arrays live in unpack)
         unpack = lambda k: {"ladder_rec": rec[k].copy(), "ladder_tru": tru[k].copy()} if _mixed(lwant[k], file_jobs[k]) else {}
         return self._L.qm_extract_files_ladder, (C.byref(args),), unpack
+
+    def _files_ladder_types(self, n, ladder_types, file_jobs=(), **kw):
+        from .haplo import check_gap
+        from .vartype import check_edges, n_rows
+        edges = check_edges(ladder_types.get("edges"))
+        lgid, lwant = _ids(ladder_types["genomes"]), _want(ladder_types["want"])
+        if n and (lgid.shape[0] != n or lwant.shape[0] != n):
+            raise ValueError("ladder_types: %d genomes / %d want entries for %d jobs" % (len(ladder_types["genomes"]), len(ladder_types["want"]), n))
+        e = _c(edges, np.int32)
+        rec, tru = _rows(n, n_rows(edges), _lib.QM_LADDER_COLS), _rows(n, n_rows(edges), _lib.QM_LADDER_COLS)
+        args = _lib.LadderTypesArgs(_p(lgid), check_gap(ladder_types.get("gap")), 1 if ladder_types.get("subsets", True) else 0, _p(lwant), _p(e),
+                                    len(edges), 0, _p(rec), _p(tru))
+        args.keep = (lgid, lwant, e)   # (read during the call; the other arrays live in unpack)
+        unpack = lambda k: ({"ladder_types_rec": rec[k].copy(), "ladder_types_tru": tru[k].copy(), "ladder_types_edges": edges}
+                            if _mixed(lwant[k], file_jobs[k]) else {})
+        return self._L.qm_extract_files_ladder_types, (C.byref(args),), unpack
+
+    _files_laddertypes = _files_ladder_types   # (the pass's name in quasimodo_amd.passes)
 
     def _files_vartype(self, n, vartype, file_jobs=(), **kw):
         from .vartype import check_edges, n_rows
@@ -1133,6 +1156,28 @@ class Batch:
     def ladder_timings(self):
         """qm_batch_ladder_timings (set_timing on): milliseconds of the latest ladder() between HIP events, kernel by kernel"""
         return self._pass_timings(self._L.qm_batch_ladder_timings, ("ladder_records_ms", "ladder_truth_ms"))
+
+    # -- the match ladder per variant type and size (DESIGN.md 4.24) ---------------------
+    def ladder_types(self, fetch=True, stream=None):
+        """qm_batch_ladder_types + qm_batch_get_ladder_types behind a vartype(columns=True) and a ladder(columns=True): (rec, tru
+        uint64 [n_vcf][n_rows][18]) -- the rows of that vartype() (vartype.row_names(edges); records typed as spelled), the
+        columns of the ladder (ladder.COLS / ladder.T_COLS).  fetch=False: enqueue only (ladder_type_counts() waits and
+        copies)"""
+        self._ck(self._L.qm_batch_ladder_types(self._h, C.c_void_p(stream) if stream else None))
+        return self.ladder_type_counts() if fetch else None
+
+    def ladder_type_counts(self):
+        """qm_batch_get_ladder_types: the counts of the latest ladder_types()"""
+        nr = C.c_int(0)
+        self._ck(self._L.qm_batch_get_ladder_types(self._h, None, None, C.byref(nr)))
+        rec = np.zeros((max(self.n_vcf, 1), max(nr.value, 1), _lib.QM_LADDER_COLS), np.uint64)
+        tru = np.zeros_like(rec)
+        self._ck(self._L.qm_batch_get_ladder_types(self._h, _p(rec), _p(tru), None))
+        return rec[:self.n_vcf], tru[:self.n_vcf]
+
+    def ladder_type_timings(self):
+        """qm_batch_ladder_types_timings (set_timing on): milliseconds of the latest ladder_types() between HIP events, kernel by kernel"""
+        return self._pass_timings(self._L.qm_batch_ladder_types_timings, ("ltype_records_ms", "ltype_truth_ms"))
 
     # -- near-miss classes of FP lines and missed truth keys (DESIGN.md 4.14) --------
     def nearmiss(self, radius, stream=None):

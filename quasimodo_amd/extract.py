@@ -92,6 +92,9 @@ class Job:
     ladder: int = None        # the gap g of the haplotype pass, IN PLACE OF Job.normalize / atomize / haplo / hapsub: stats gain ladder_rec / ladder_tru
     ladder_genome: str = None  # FASTA of the genome the VCF was called against (with Job.ladder)
     ladder_out: str = None    # where the job's table of lines and entries with their method sets goes (extract_many(ladder=) derives it)
+    # the match ladder per variant type and size; mixed samples, allele-extended mode only
+    ladder_types: tuple = None   # (gap, size edges), IN PLACE OF Job.ladder and Job.vartype: stats gain ladder_types_rec / ladder_types_tru / ladder_types_edges
+    ladder_types_genome: str = None   # FASTA of the genome the VCF was called against (with Job.ladder_types)
 
 
 def _paths(job):
@@ -347,6 +350,27 @@ def _ladder_spec(jobs, pure, load):
             "out": [j.ladder_out if w else None for j, w in zip(jobs, on)]}
 
 
+def _ladder_types_onto_jobs(jobs, ladder_types, **kw):
+    """ladder_types= {"genomes": ..., "gap": ..., "edges": ...}: the four rescue passes, the type pass, the ladder and their cross"""
+    from .haplo import check_gap
+    from .vartype import check_edges
+    opt = ladder_types if isinstance(ladder_types, dict) else {"genomes": ladder_types}
+    par = (check_gap(opt.get("gap")), check_edges(opt.get("edges")))
+    for j, g in zip(jobs, _per_job(opt["genomes"], jobs, "ladder_types: %d genomes entries for %d jobs")):
+        j.ladder_types, j.ladder_types_genome = (par, g) if g and _mixed(j) else (None, None)
+
+
+def _ladder_types_spec(jobs, pure, load):
+    from .haplo import check_gap
+    from .vartype import check_edges
+    on = [j.ladder_types is not None and not p for j, p in zip(jobs, pure)]
+    if not any(on):
+        return None
+    gap, edges = next(j.ladder_types for j in jobs if j.ladder_types is not None)
+    return {"gap": check_gap(gap), "edges": check_edges(edges), "subsets": True,
+            "genomes": [load(j.ladder_types_genome) if w else -1 for j, w in zip(jobs, on)], "want": [int(w) for w in on]}
+
+
 def _atomize_onto_jobs(jobs, atomize, **kw):
     from .atomize import atoms_path
     awant = [True] * len(jobs) if atomize is True else [bool(w) for w in atomize]
@@ -462,6 +486,7 @@ PASS_IO = (
     PassIO("rescueroc", "rescue_roc", _rescue_roc_onto_jobs, lambda jobs, pure, load: {
         "genomes": [load(j.rescue_roc) if j.rescue_roc else -1 for j in jobs], "want": [1 if j.rescue_roc else 0 for j in jobs]} if any(j.rescue_roc for j in jobs) else None),
     PassIO("ladder", "ladder", _ladder_onto_jobs, _ladder_spec, ("out",)),
+    PassIO("laddertypes", "ladder_types", _ladder_types_onto_jobs, _ladder_types_spec),
     PassIO("atomize", "atomize", _atomize_onto_jobs, lambda jobs, pure, load: {
         "want": [1 if j.atomize else 0 for j in jobs], "atoms": [j.atoms_out if j.atomize else None for j in jobs]} if any(j.atomize for j in jobs) else None, ("atoms",)),
     PassIO("vartype", "vartype", _vartype_onto_jobs, _vartype_spec),
@@ -478,7 +503,7 @@ PASS_IO = (
 
 # extract_files is called with the keyword of every pass, None where none is asked for -- but for these, which go only when asked for
 # (the call of a run without them is the call it has always been)
-_WHEN_ASKED = ("ladder",)
+_WHEN_ASKED = ("ladder", "ladder_types")
 
 
 def _one_genome_per_truth(jobs, field, who, what):
@@ -492,7 +517,8 @@ def _one_genome_per_truth(jobs, field, who, what):
 
 def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=None, truth_slots=None, n_slots=0, global_dev=None,
                  genomes=None, fn=False, groups=None, profile=None, strata=None, boot=None, votes=None, explain=None,
-                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None, ladder=None):
+                 surface=None, context=None, normalize=None, atomize=None, vartype=None, haplo=None, hapsub=None, rescue_roc=None, ladder=None,
+                 ladder_types=None):
     """Classify and write filtered / tp / fp VCFs for a list of Job.  Returns the jobs
     with .stats filled (line counts, R-path counts, ROC rows).
     gpus > 1: the VCFs are dealt to that many GPUs of this node, one process each (quasimodo_amd.multigpu).
@@ -561,15 +587,22 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
     stats["ladder_rec"] ([18]: kept, TP lines, then the 16 cells of the method bits over the kept lines that are no TP by
     spelling; cell 0 is the final FP) and stats["ladder_tru"] ([18]: entries, entries a kept record spells, then the 16 cells
     over the others; cell 0 is the final FN), and ladder/<x>.ladder.tsv beside fp/ and tp/.  VCFs of one truth file name one genome.
+    ladder_types: {"genomes": [FASTA path or None per job], "gap": None or 0 .. 32, "edges": None or the size edges} or the list of
+    genomes itself (quasimodo_amd.laddertypes, DESIGN.md 4.24; default: the jobs' Job.ladder_types / Job.ladder_types_genome;
+    alleles=True only, ValueError otherwise), in place of ladder and vartype, which the call runs itself with all four rescues:
+    every mixed-sample job with a genome gets stats["ladder_types_rec"] and stats["ladder_types_tru"] ([5 n_bins + 4][18]: the
+    rows of vartype -- records typed as spelled --, the columns of ladder) and stats["ladder_types_edges"].  VCFs of one truth
+    file name one genome.
     Which of these may share a call: quasimodo_amd.passes -- genomes with profile, every other pass alone (ValueError)."""
     kw = dict(genomes=genomes, fn=fn, groups=groups, profile=profile, strata=strata, boot=boot, votes=votes, explain=explain, surface=surface,
-              context=context, normalize=normalize, atomize=atomize, vartype=vartype, haplo=haplo, hapsub=hapsub, rescue_roc=rescue_roc, ladder=ladder)
+              context=context, normalize=normalize, atomize=atomize, vartype=vartype, haplo=haplo, hapsub=hapsub, rescue_roc=rescue_roc, ladder=ladder,
+              ladder_types=ladder_types)
     given = {"motifs": genomes is not None, "truthside": bool(fn) or (groups is not None and not votes), "profile": profile is not None,
              "strata": strata is not None, "boot": boot is not None, "votes": bool(votes), "nearmiss": explain is not None,
              "surface": surface is not None and surface is not False, "context": context is not None, "normalize": normalize is not None,
              "atomize": atomize is not None and atomize is not False, "vartype": vartype is not None and vartype is not False,
              "haplo": haplo is not None and haplo is not False and not hapsub, "hapsub": bool(hapsub), "rescueroc": rescue_roc is not None,
-             "ladder": ladder is not None}
+             "ladder": ladder is not None, "laddertypes": ladder_types is not None}
     # the keywords onto the jobs ...
     for p in PASS_IO:
         if given[p.name]:
@@ -592,6 +625,10 @@ def extract_many(jobs, engine=None, strict=None, n_bins=256, alleles=None, gpus=
         if j.ladder is not None and not j.ladder_genome:
             raise ValueError("%s: Job.ladder without Job.ladder_genome (the FASTA the VCF was called against)" % j.vcf_file)
     _one_genome_per_truth([j for j in jobs if j.ladder is not None], "ladder_genome", "ladder", "a normalised truth set belongs to one genome")
+    for j in jobs:
+        if j.ladder_types is not None and not j.ladder_types_genome:
+            raise ValueError("%s: Job.ladder_types without Job.ladder_types_genome (the FASTA the VCF was called against)" % j.vcf_file)
+    _one_genome_per_truth([j for j in jobs if j.ladder_types is not None], "ladder_types_genome", "ladder_types", "a normalised truth set belongs to one genome")
     if gpus is not None and int(gpus) > 1:
         if engine is not None:
             raise ValueError("gpus > 1 starts one process (and one engine) per GPU: do not pass an engine")

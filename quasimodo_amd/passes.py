@@ -24,6 +24,9 @@ PASSES = (
     Pass("rescueroc", ("rescue_roc",), ("rescue_roc",), "--rescue-roc", None, ()),
     # the four rescue passes, which it runs itself, combined: asked for in place of them, never beside them
     Pass("ladder", ("ladder",), ("ladder",), "--match-ladder", "ladder: the jobs of one call share one gap", ()),
+    # the four rescue passes, the type pass and the ladder, all of which it runs itself, crossed: asked for in place of them
+    Pass("laddertypes", ("ladder_types",), ("ladder_types",), "--ladder-by-type",
+         "ladder_types: the jobs of one call share one gap and one list of size edges", ()),
     Pass("atomize", ("atomize",), ("atomize",), "--atomize", None, ()),
     Pass("vartype", ("vartype",), ("vartype",), "--by-type", "vartype: the typed jobs of one call share one list of size edges", ()),
     Pass("context", ("context",), ("context",), "--seq-context",
@@ -66,6 +69,7 @@ NEEDS_ALLELES = {
     "hapsub": "a single-base batch holds no indels, MNPs or complex records to replay",   # (it runs the haplotype pass)
     "rescueroc": "a single-base batch has no rescue passes to sweep",
     "ladder": "a single-base batch has no rescue passes to combine",
+    "laddertypes": "a single-base batch has neither types nor rescue passes to cross",
 }
 Pass.needs_alleles = property(lambda p: NEEDS_ALLELES.get(p.name))
 

@@ -166,7 +166,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False,
                          surface_qual_step=None, surface_qual_bins=None, surface_af_bins=None, seq_context=None, context_window=None,
                          context_gc_bins=None, alleles=False, normalize=None, atomize=False, by_type=None, haplotypes=None,
-                         hap_gap=None, hap_subsets=False, rescue_roc=None, match_ladder=None):
+                         hap_gap=None, hap_subsets=False, rescue_roc=None, match_ladder=None, ladder_by_type=None, ladder_type_bins=None):
     """data_dir: the unpacked bundle (data/snp): vcf/{caller}/{sample}.{ref}.{caller}.vcf and
     nucmer/{TM,TA}.maskrepeat.variants.vcf (rules/load_config.smk:28-36); when it is absent and <data_dir>.tar.gz exists,
     that is unpacked first (:28-31).
@@ -231,6 +231,12 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
     and after normal form, atoms, haplotype and subset, cumulative, then the 15 non-empty method sets of lines and of entries; per
     caller and mixture, then pooled per caller) and callers/{caller}/ladder/{sample}.{ref}.{caller}.ladder.tsv for every mixed
     sample (every kept line that is no TP by spelling and every truth entry no kept record spells, with its method set and tier).
+    ladder_by_type: {"TM": FASTA, "TA": FASTA}, the genomes as for match_ladder, with hap_gap and ladder_type_bins (the size edges
+    as for by_type; None: the default ones) (quasimodo_amd.laddertypes; needs alleles, WorkflowError before a file
+    is touched otherwise), in place of match_ladder and by_type, both of which the run's call makes itself behind all four
+    rescues: final_tables/caller_performance_ladder_types.tsv (per caller and mixture one row per type and size bin -- records
+    typed as spelled --, a marginal per type, the four rows behind the grid as plain counts, each with TP, FP, FN, Precision,
+    Recall, F1 by spelling and after each tier; then a pooled block per caller).
     Which of these may share a run: quasimodo_amd.passes (mutation_context with snp_profile; WorkflowError otherwise)."""
     callers = list(callers or SNPCALLERS)
     votes = bool(votes) or consensus_vcf is not None
@@ -238,7 +244,11 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                  truthside=truth_side, profile=snp_profile, nearmiss=explain_errors, surface=filter_surface,
                  context=seq_context is not None, normalize=normalize is not None, atomize=bool(atomize), vartype=by_type is not None and by_type is not False,
                  haplo=haplotypes is not None and not hap_subsets, hapsub=bool(hap_subsets), rescueroc=rescue_roc is not None,
-                 ladder=match_ladder is not None)
+                 ladder=match_ladder is not None, laddertypes=ladder_by_type is not None)
+    if ladder_by_type is not None and not alleles:
+        raise WorkflowError("--ladder-by-type needs --alleles: it crosses the variant types with the matching by normal form, by atoms and by haplotype, which only the allele-extended mode has")
+    if ladder_type_bins is not None and ladder_by_type is None:
+        raise WorkflowError("ladder_type_bins needs ladder_by_type (--type-bins needs --by-type or --ladder-by-type)")
     if match_ladder is not None and not alleles:
         raise WorkflowError("--match-ladder needs --alleles: it combines the matching by normal form, by atoms and by haplotype, which only the allele-extended mode has")
     if rescue_roc is not None and not alleles:
@@ -254,7 +264,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             hgap = check_gap(hap_gap)
         except ValueError as e:
             raise WorkflowError("--hap-gap: %s" % e) from None
-    elif match_ladder is not None:
+    elif match_ladder is not None or ladder_by_type is not None:
         from .haplo import check_gap
         try:
             hgap = check_gap(hap_gap)
@@ -262,6 +272,13 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             raise WorkflowError("--hap-gap: %s" % e) from None
     elif hap_gap is not None:
         raise WorkflowError("--hap-gap needs --haplotypes or --match-ladder")
+    ltedges = None
+    if ladder_by_type is not None:
+        from .vartype import check_edges, parse_edges
+        try:
+            ltedges = parse_edges(ladder_type_bins) if isinstance(ladder_type_bins, str) else check_edges(ladder_type_bins)
+        except ValueError as e:
+            raise WorkflowError("--type-bins: %s" % e) from None
     tedges = None
     if by_type is not None and by_type is not False:
         from .vartype import check_edges, parse_edges
@@ -310,7 +327,7 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
                 raise WorkflowError("missing input %s" % src)
             plan.append((s, c, src))
     mixes = sorted({s[:2] for s in samples}, reverse=True)              # TM, TA
-    for fastas, what in ((mutation_context, "mutation context"), (seq_context, "sequence context"), (normalize, "normalize"), (rescue_roc, "rescue ROC"), (haplotypes, "haplotypes"), (match_ladder, "match ladder")):
+    for fastas, what in ((mutation_context, "mutation context"), (seq_context, "sequence context"), (normalize, "normalize"), (rescue_roc, "rescue ROC"), (haplotypes, "haplotypes"), (match_ladder, "match ladder"), (ladder_by_type, "ladder by type")):
         for mix in mixes if fastas is not None else ():
             if not fastas.get(mix) or not os.path.isfile(fastas.get(mix)):
                 raise WorkflowError("%s: no genome FASTA for %s (%s)" % (what, mix, fastas.get(mix)))
@@ -332,6 +349,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
             print("caller_roc_rescue.tsv\t%s" % ",".join(callers))
         if match_ladder is not None:
             print("caller_performance_ladder.tsv\t%s\t%d" % (",".join(callers), hgap))
+        if ladder_by_type is not None:
+            print("caller_performance_ladder_types.tsv\t%s\t%d\t%s" % (",".join(callers), hgap, ",".join(str(e) for e in ltedges)))
         if tedges is not None:
             print("caller_performance_types.tsv\t%s\t%s" % (",".join(callers), ",".join(str(e) for e in tedges)))
         if mutation_context is not None:
@@ -413,6 +432,8 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if match_ladder is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].ladder, jobs[-1].ladder_genome = hgap, match_ladder[s[:2]]
             jobs[-1].ladder_out = os.path.join(d, "ladder", os.path.basename(src)[:-4] + ".ladder.tsv")
+        if ladder_by_type is not None and not s.endswith(("-1-0", "-0-1")):
+            jobs[-1].ladder_types, jobs[-1].ladder_types_genome = (hgap, ltedges), ladder_by_type[s[:2]]
         if haplotypes is not None and not s.endswith(("-1-0", "-0-1")):
             jobs[-1].haplo_genome = haplotypes[s[:2]]
             jobs[-1].haplo, jobs[-1].hapsub = (None, hgap) if hap_subsets else (hgap, None)
@@ -497,6 +518,9 @@ def run_hcmv_variantcall(data_dir, outpath, callers=None, engine=None, dryrun=Fa
         if match_ladder is not None:
             from .ladder import write_performance_ladder
             write_performance_ladder(os.path.join(tables, "caller_performance_ladder.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)])
+        if ladder_by_type is not None:
+            from .laddertypes import write_performance_ladder_types
+            write_performance_ladder_types(os.path.join(tables, "caller_performance_ladder_types.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)], ltedges)
         if tedges is not None:
             from .vartype import write_performance_types
             write_performance_types(os.path.join(tables, "caller_performance_types.tsv"), [(c, s, j.stats) for (c, s), j in zip(meta, jobs)], tedges)

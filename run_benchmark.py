@@ -95,9 +95,9 @@ def _hap_gap(haplotypes, hap_gap):
     return hap_gap
 
 
-def _type_bins(by_type, type_bins):
+def _type_bins(by_type, type_bins, ladder_by_type=False):
     """--by-type / --type-bins -> what the workflow takes: None without --by-type, True for the default edges, else the edges' text"""
-    if type_bins is not None and not by_type:
+    if type_bins is not None and not by_type and not ladder_by_type:
         raise click.UsageError("--type-bins needs --by-type")
     return None if not by_type else True if type_bins is None else type_bins
 
@@ -163,6 +163,11 @@ def _type_bins(by_type, type_bins):
                    "TP, FP and FN by spelling and after each method in turn (normal form, atoms, haplotype, subset), cumulative, and how many lines and "
                    "truth entries every set of methods reaches: write final_tables/caller_performance_ladder.tsv and callers/*/ladder/*.ladder.tsv "
                    "(needs the genomes: --merlin-ref / --ad169-ref or the config; --hap-gap as for --haplotypes).")
+@click.option("--ladder-by-type", "ladder_by_type", is_flag=True, default=False,
+              help="With --alleles, in place of --match-ladder and --by-type, both of which it always runs behind all four rescues: TP, FP and FN per "
+                   "variant type and size -- typed as the record is spelled -- by spelling and after each method in turn: write "
+                   "final_tables/caller_performance_ladder_types.tsv (needs the genomes: --merlin-ref / --ad169-ref or the config; --hap-gap as for "
+                   "--haplotypes, --type-bins as for --by-type).")
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="With --alleles: also count TP, FP and FN by variant type (SNV, MNP, INS, DEL, complex) and size: write "
                    "final_tables/caller_performance_types.tsv.")
@@ -185,7 +190,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
          profile_pos_bins=256, profile_af_bins=20, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
          votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
          surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, alleles=False,
-         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False, match_ladder=False):
+         normalize=False, atomize=False, by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False, match_ladder=False,
+         ladder_by_type=False):
     haplotypes = haplotypes or hap_subsets   # the search runs behind the haplotype pass of the same call
     if slow:
         click.echo("--slow (reads -> VCF) is outside the accelerated path; not supported", err=True)
@@ -201,7 +207,7 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
     else:   # rules/load_config.smk:5,17: config/config.yaml, relative to the workflow's directory
         out = os.path.join(wd, str(cfg.get("outpath") or "../revision_output_1"))
     genomes = None
-    if mutation_context or seq_context or normalize or haplotypes or rescue_roc or match_ladder:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
+    if mutation_context or seq_context or normalize or haplotypes or rescue_roc or match_ladder or ladder_by_type:   # rules/load_config.smk:8-10: MerlinRef / AD169Ref, absolute from the workflow's directory
         pick = lambda cli, key: os.path.join(cd, cli) if cli else (os.path.join(wd, str(cfg[key])) if cfg.get(key) else None)
         genomes = {"TM": pick(merlin_ref, "MerlinRef"), "TA": pick(ad169_ref, "AD169Ref")}
     try:
@@ -218,9 +224,11 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
                                              filter_surface=filter_surface, surface_qual_step=surface_qual_step,
                                              surface_qual_bins=surface_qual_bins, surface_af_bins=surface_af_bins,
                                              alleles=alleles, normalize=genomes if normalize else None, atomize=atomize,
-                                             by_type=_type_bins(by_type, type_bins), haplotypes=genomes if haplotypes else None,
-                                             hap_gap=_hap_gap(haplotypes or match_ladder, hap_gap), hap_subsets=hap_subsets,
-                                             rescue_roc=genomes if rescue_roc else None, match_ladder=genomes if match_ladder else None)
+                                             by_type=_type_bins(by_type, type_bins, ladder_by_type), haplotypes=genomes if haplotypes else None,
+                                             hap_gap=_hap_gap(haplotypes or match_ladder or ladder_by_type, hap_gap), hap_subsets=hap_subsets,
+                                             rescue_roc=genomes if rescue_roc else None, match_ladder=genomes if match_ladder else None,
+                                             ladder_by_type=genomes if ladder_by_type else None,
+                                             ladder_type_bins=type_bins if ladder_by_type and not by_type else None)
         if json_out and not dryrun:
             _write_json(json_out, "hcmv", jobs, workflow.run_hcmv_variantcall)
     except Exception as e:
@@ -278,6 +286,8 @@ def hcmv(evaluation, dryrun=False, conda_prefix=None, slow=False, outpath=None, 
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose rescue passes could be swept (hcmv has it).")
 @click.option("--match-ladder", "match_ladder", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose rescue passes could be combined (hcmv has it).")
+@click.option("--ladder-by-type", "ladder_by_type", is_flag=True, default=False,
+              help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose types and rescue passes could be crossed (hcmv has it).")
 @click.option("--by-type", "by_type", is_flag=True, default=False,
               help="Not available here: the show-snps table of a custom run holds single-base rows only, so there is no allele-extended mode whose variants could be typed (hcmv has it).")
 @click.option("--type-bins", "type_bins", default=None, help="Not available here (see --by-type).")
@@ -289,9 +299,12 @@ def vareval(dryrun=False, conda_prefix=None, vcfs=None, labels=None, refs=None, 
             config=None, json_out=None, truth_side=False, strata=(), strata_by_name=None, bootstrap=None, bootstrap_window=1024, bootstrap_seed=0,
             votes=False, consensus_vcf=None, explain_errors=False, explain_radius=None, filter_surface=False, surface_qual_step=None,
             surface_qual_bins=None, surface_af_bins=None, seq_context=False, context_window=None, context_gc_bins=None, normalize=False, atomize=False,
-            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False, match_ladder=False):
+            by_type=False, type_bins=None, haplotypes=False, hap_gap=None, hap_subsets=False, rescue_roc=False, match_ladder=False, ladder_by_type=False):
     from quasimodo_amd import workflow
     try:
+        if ladder_by_type:
+            raise workflow.WorkflowError("--ladder-by-type needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
+                                         "custom run holds single-base rows (use hcmv -e variantcall --alleles --ladder-by-type)")
         if match_ladder:
             raise workflow.WorkflowError("--match-ladder needs the allele-extended mode, which reads VCF truth sets only: the show-snps table of a "
                                          "custom run holds single-base rows (use hcmv -e variantcall --alleles --match-ladder)")
