@@ -243,7 +243,7 @@ def library_path():
 
 
 _KSRC = ("qmvt_kernels.hip", "qmvt_dev.h")
-_ASRC = _KSRC + ("qmvt_walk.h", "qmvt_classify_pair.hip", "qmvt_classify_pair.h", "qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_haplo.hip", "qmvt_haplo.h", "qmvt_rroc.hip", "qmvt_rroc.h", "qmvt_ladder.hip", "qmvt_ladder.h", "qmvt_ltypes.hip", "qmvt_ltypes.h", "qmvt_api.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
+_ASRC = _KSRC + ("qmvt_walk.h", "qmvt_classify_pair.hip", "qmvt_classify_pair.h", "qmvt_motif.hip", "qmvt_motif.h", "qmvt_truthside.hip", "qmvt_truthside.h", "qmvt_afprofile.hip", "qmvt_afprofile.h", "qmvt_strata.hip", "qmvt_strata.h", "qmvt_boot.hip", "qmvt_boot.h", "qmvt_votes.hip", "qmvt_votes.h", "qmvt_nearmiss.hip", "qmvt_nearmiss.h", "qmvt_surface.hip", "qmvt_surface.h", "qmvt_context.hip", "qmvt_context.h", "qmvt_norm.hip", "qmvt_norm.h", "qmvt_atom.hip", "qmvt_atom.h", "qmvt_types.hip", "qmvt_types.h", "qmvt_haplo.hip", "qmvt_haplo.h", "qmvt_rroc.hip", "qmvt_rroc.h", "qmvt_ladder.hip", "qmvt_ladder.h", "qmvt_ltypes.hip", "qmvt_ltypes.h", "qmvt_batch.h", "qmvt_api.cpp", "qmvt_finish.cpp", "qmvt_comm.cpp", "qmvt_host.cpp", "qmvt_pipeline.cpp", os.path.join("..", "..", "include", "qmvt.h"), "Makefile")
 
 
 def _sha16(files):

@@ -40,6 +40,29 @@ def test_the_library_says_which_sources_it_was_built_from(qmlib, tmp_path):
     assert _lib.embedded_ids(str(other)) == (None, None) and _lib.embedded_ids(str(tmp_path / "missing.so")) == (None, None)
 
 
+def test_the_three_lists_of_the_librarys_sources_agree():
+    """The sources of libqmvt.so are listed three times: OBJS and ASRC in the Makefile, _ASRC in _lib.py.  A source missing from
+    ASRC / _ASRC is a source whose edits change no build id, so build_library() keeps a stale binary; one missing from OBJS is not
+    linked.  All three follow from the files under csrc/."""
+    from quasimodo_amd import _lib
+    csrc = os.path.join(ROOT, "quasimodo_amd", "csrc")
+    var = {}
+    for line in open(os.path.join(csrc, "Makefile")):
+        m = re.match(r"\s*(?:override\s+)?(OBJS|KSRC|ASRC)\s*[+:?!]*=", line)
+        if m:   # each is set once, by a plain `NAME = words` line: a later `+=` would add a source behind this test's back
+            assert m.group(1) not in var, "two lines set %s" % m.group(1)
+            assert line.startswith(m.group(1) + " = ") and not line.rstrip().endswith("\\"), line
+            var[m.group(1)] = line.split(" = ", 1)[1].split()
+    ksrc, objs = var["KSRC"], var["OBJS"]
+    asrc = [w for x in var["ASRC"] for w in (ksrc if x == "$(KSRC)" else [x])]
+    assert ksrc == list(_lib._KSRC)
+    assert asrc == [f.replace(os.sep, "/") for f in _lib._ASRC]   # in order: the build id hashes their concatenation
+    assert len(set(asrc)) == len(asrc) and len(set(objs)) == len(objs)
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp")))
+    assert files == sorted(f for f in asrc if f not in ("../../include/qmvt.h", "Makefile"))
+    assert sorted(objs) == sorted(os.path.splitext(f)[0] + ".o" for f in files if f.endswith((".hip", ".cpp")))
+
+
 def test_caller_allocated_structs_have_the_headers_size_everywhere(qmlib):
     """qm_vcf_cols / qm_file_stats / qm_file_job / qm_bench_result are allocated by the CALLER and filled by the library: a binding
     that declares fewer fields than the header lets the library write past its allocation (round 4: the stub of INTEGRATION.md was

@@ -1,8 +1,8 @@
-"""The state every pass over a finished batch keeps in qmvt_api.cpp: what it made behind the latest run, whether
-it recorded timing marks, and the event its getters wait for.  One table row per pass -- all sixteen of them -- says how the pass
-is enqueued, how its result is fetched, how its timings are read, and the refusals of the library WORD FOR WORD: the strings below
-are the library's own, so a change of the host code that moves a check, a message or the point where a pass forgets its result
-shows here, whatever the kernels compute.
+"""The state every pass over a finished batch keeps (PassState in qmvt_batch.h, the helpers that handle it in qmvt_api.cpp;
+DESIGN.md 4.13): what it made behind the latest run, whether it recorded timing marks, and the event its getters wait for.  One
+table row per pass -- all sixteen of them -- says how the pass is enqueued, how its result is fetched, how its timings are read,
+and the refusals of the library WORD FOR WORD: the strings below are the library's own, so a change of the host code that moves
+a check, a message or the point where a pass forgets its result shows here, whatever the kernels compute.
 
 Nothing depends on a kernel's result: two batches of two VCFs of 100 records each (a single-base one, an allele-extended one whose
 truth set holds indels and an MNP) are enough, on an engine of the module's own -- the refusals of a genome id print how many

@@ -1,6 +1,7 @@
-"""The batch passes on streams of the caller's, and the ordering between streams that qmvt_api.cpp keeps from its two tables, PASSES
-and READS (include/qmvt.h at qm_batch_run): pass_open()'s host wait, the readers' wait for the hit bitmaps'
-event (pass_wait), the wait list of everything that rewrites what passes read (wait_passes), the getters' wait for their pass.
+"""The batch passes on streams of the caller's, and the ordering between streams that qmvt_api.cpp keeps from the two tables of
+qmvt_batch.h, PASSES and READS (include/qmvt.h at qm_batch_run): pass_open()'s host wait, the readers' wait for
+the hit bitmaps' event (pass_wait), the wait list of everything that rewrites what passes read (wait_passes), the getters' wait
+for their pass.
 
 The method.  A missing wait between two streams shows only while the producer is still running when the consumer is enqueued.
 Every case therefore puts a BOUNDED STALL in front of the producer, on the producer's stream: work that is long, touches nothing

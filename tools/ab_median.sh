@@ -9,12 +9,13 @@ S=$ROOT/quasimodo_amd/csrc
 cd /tmp
 for spec in "$@"; do
   TAG=${spec%%=*}; FLAGS=${spec#*=}
-  D=/tmp/abm/$TAG; mkdir -p $D
-  KSRC=$S/qmvt_kernels.hip
-  if [ "${FLAGS:0:1}" = "@" ]; then KSRC=$GRAFT_REPO_ROOT/${FLAGS%% *}; KSRC=${KSRC/@/}; FLAGS="${FLAGS#* } -I$S"; [ "$FLAGS" = "${spec#*=} -I$S" ] && FLAGS="-I$S"; fi   # "<tag>=@<kernel source> <flags>": another kernels file (e.g. last round's)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FLAGS -c -o $D/k.o $KSRC 2>$D/build.err || { echo "build failed: $TAG"; head -5 $D/build.err; }
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FLAGS -x hip -c -o $D/a.o $S/qmvt_api.cpp 2>>$D/build.err || echo "api build failed: $TAG"
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $D/libqmvt.so $D/k.o $D/a.o $S/qmvt_host.o $S/qmvt_pipeline.o -lz
+  D=/tmp/abm/$TAG; W=$D/src/quasimodo_amd/csrc; mkdir -p $W $D/src/include
+  # the library as the Makefile builds it, from a copy of the sources (the objects exist in one place: its OBJS), with the variant's flags behind its own
+  cp $S/*.hip $S/*.h $S/*.cpp $S/Makefile $W/ && cp $ROOT/include/qmvt.h $D/src/include/
+  if [ "${FLAGS:0:1}" = "@" ]; then K=${FLAGS%% *}; cp "$ROOT/${K#@}" $W/qmvt_kernels.hip; case "$FLAGS" in *" "*) FLAGS=${FLAGS#* };; *) FLAGS=;; esac; fi   # "<tag>=@<kernel source> <flags>": another kernels file (e.g. last round's)
+  printf '\nCXXFLAGS += %s\n' "$FLAGS" >> $W/Makefile   # the copy's last line: the recipes read CXXFLAGS when they run
+  rm -f $D/libqmvt.so $W/libqmvt.so   # a failed build leaves no library of an earlier run to be timed under this tag
+  make -s -C $W -j${MAX_JOBS:-16} libqmvt.so 2>$D/build.err && cp $W/libqmvt.so $D/libqmvt.so || { echo "build failed: $TAG"; head -5 $D/build.err; }
 done
 : > /tmp/abm/all.log
 for rep in $(seq 1 ${ROUNDS:-5}); do for spec in "$@"; do
